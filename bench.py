@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- RGB-D front-end throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config std640|big1280|batch256] [--mode batch|stream]
+    python bench.py --gpus N --steps K --warmup W [--config std640|big1280|batch256] [--mode batch|stream] [--full] [--dump-outputs DIR]
 
 mode batch (default): one "step" = one pass of the whole front-end (ORB 1000 features + LSD/LBD lines + PEAC planes)
 over one batch of B synthetic RGB-D frames that is already resident in HBM (BASELINE.json configs[1]; 256 distinct
@@ -11,12 +11,15 @@ collective ("weak" scaling: B frames per GPU); at N > 1 the result slabs are all
 mode stream (BASELINE.json configs[4]): one frame at a time through hvo_stream_* (pinned staging, `--depth` frames in
 flight, SearchByProjection(Cur, Last) + line matching against the previous frame on the device); a "step" is a frame.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps and prints the
+headline ("metric", "value", "unit", "ms_per_step", ...).  --full adds everything else, measured after the timed steps:
   "roofline":       HBM roofline of the dominant kernel group, from hipEvents recorded on the kernels' own stream
                     (hvo_profile_last); "kernel_roofline" has the same figure for every kernel group
   "cpu_baseline":   the CPU oracle (kind "port") in the reference's own shape: one frame at a time, ORB || LSD || planes on
                     three threads (src/Frame.cc:210-215); "cpu_baseline_all_cores": frames spread over every host core
   "latency_ms", "pcie_inclusive_frames_per_s": single-frame / small-batch latency and the rate with upload and download.
+  "parity_*":       frames of the timed batch compared with the CPU oracle; "std_only", the workload statistics, at N > 1 "gather".
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, see dump_outputs).
 `--gpus N` without a torchrun environment starts the N ranks itself (before anything touches the GPU).
 """
 import argparse
@@ -52,8 +55,11 @@ def parse_args():
     ap.add_argument("--stages", default="", help="comma list of orb,lsd,planes,tail (tail = isLineGood + vanishing points + ComputePlanes' tail + grids); default: orb,lsd,planes (batch), orb,lsd,planes,tail (stream: the whole Frame constructor)")
     ap.add_argument("--distinct", type=int, default=256, help="distinct synthetic frames (3/4 std, 1/4 lowtex)")
     ap.add_argument("--depth", type=int, default=4, help="stream mode: frames in flight")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the latency / PCIe-inclusive side measurements")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything besides the headline: "
+                    "per-kernel roofline, oracle parity, CPU baselines, latency / PCIe-inclusive rates, std-only scenes, the N > 1 gather")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the latency / PCIe-inclusive side measurements")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, the default) or gloo (rehearsal of the N>1 path on a 1-GPU box)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses GPU 0")
     return ap.parse_args()
@@ -271,14 +277,18 @@ def parity_sample(ge, np, stages, res, g0, d0, kinds, nfeat, want=32, scale=1.0)
 # synthetic workload
 # ---------------------------------------------------------------------------------------------------------------
 def make_frames(synth, n, w, h, seed0):
-    """n distinct frames, every fourth one `lowtex` (the paper's target regime), the rest `std`"""
+    """n distinct frames, every fourth one `lowtex` (the paper's target regime), the rest `std`.  A frame depends on its seed alone and
+    synth's whole-image numpy passes release the GIL, so up to 16 threads make them (the same bytes as one thread, in a fraction of the
+    set-up time)."""
     import numpy as np
+    from concurrent.futures import ThreadPoolExecutor
     g = np.empty((n, h, w), np.uint8); d = np.empty((n, h, w), np.uint16)
-    kinds = []
-    for k in range(n):
-        kind = "lowtex" if k % 4 == 3 else "std"
-        g[k], d[k] = synth.make_frame(kind, seed0 + k, w, h)
-        kinds.append(kind)
+    kinds = ["lowtex" if k % 4 == 3 else "std" for k in range(n)]
+
+    def one(k):
+        g[k], d[k] = synth.make_frame(kinds[k], seed0 + k, w, h)
+    with ThreadPoolExecutor(max(1, min(16, n, len(os.sched_getaffinity(0))))) as pool:
+        list(pool.map(one, range(n)))
     return g, d, kinds
 
 
@@ -377,6 +387,60 @@ def end_to_end(hvo, np, ctx, g, d, mask, B, rounds=4):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path handed its caller in the last step, as float arrays
+# ---------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_FRAMES = 64                   # batch mode: records of a fixed, seeded sample of the distinct frames ...
+DUMP_LABEL_BYTES = 24 << 20        # ... and the label images of as many of them as fit here
+
+
+def as_float(np, a):
+    """float32 for u8 / i8 / u16 / i16 / f32 (exact), float64 for the rest; structured records become float64 columns in field order
+    (a sub-array field such as PLANE_DT.normal gives one column per element)"""
+    a = np.asarray(a)
+    if a.dtype.names:
+        return np.concatenate([as_float(np, a[k]).astype(np.float64).reshape(len(a), int(np.prod(a.dtype[k].shape, dtype=np.int64)))
+                               for k in a.dtype.names], axis=1)
+    return a.astype(np.float32 if a.dtype in (np.uint8, np.int8, np.uint16, np.int16, np.float32) else np.float64)
+
+
+def flat_items(d, prefix=""):
+    """(name, value) of a result dict, nested dicts / tuples named by path (vp -> vp_vps, pt_grid -> pt_grid_0 ...)"""
+    for k, v in d.items():
+        if isinstance(v, dict):
+            yield from flat_items(v, prefix + k + "_")
+        elif isinstance(v, (tuple, list)):
+            yield from flat_items({str(i): x for i, x in enumerate(v)}, prefix + k + "_")
+        else:
+            yield prefix + k, v
+
+
+def dump_outputs(np, out_dir, frames, label_frames, extra=None):
+    """Per-frame result dicts (as batch_download / Stream.collect return them) -> out_dir/<name>.npy.  A scalar per frame (status)
+    becomes one value per frame; a record array is concatenated over the frames in order, with <name>_count (records per frame)
+    beside it; the label image of the first `label_frames` frames is stacked (labels: frames x H x W, float32).  `extra`: more named arrays."""
+    per = [dict(flat_items(f)) for f in frames]
+    arrays = {}
+    for k in per[0]:
+        vals = [p[k] for p in per]
+        if k == "labels":
+            arrays[k] = np.stack([np.asarray(v).astype(np.float32) for v in vals[:label_frames]])      # plane ids / -1: exact in float32
+        elif np.ndim(vals[0]) == 0:
+            arrays[k] = np.array(vals, np.float64)
+        else:
+            arrays[k] = np.concatenate([as_float(np, v) for v in vals])
+            arrays[k + "_count"] = np.array([len(v) for v in vals], np.float64)
+    for k, v in (extra or {}).items():
+        arrays[k] = as_float(np, v)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # stream mode
 # ---------------------------------------------------------------------------------------------------------------
 def stream_queries(np, last, shift, sf, bf, th=15):
@@ -389,12 +453,13 @@ def stream_queries(np, last, shift, sf, bf, th=15):
     return sel, u, v, rad, (octv - 1).astype(np.int32), (octv + 1).astype(np.int32), ur, np.ones(len(sel), np.uint8)
 
 
-def run_stream(hvo, np, g, d, off, mask, depth, device, nframes, paced_hz=0.0):
+def run_stream(hvo, np, g, d, off, mask, depth, device, nframes, paced_hz=0.0, keep=None):
     """frames through hvo_stream_* with up to depth - 1 in flight (one slot keeps the previous frame resident for the
     matching); every frame is collected and matched against its predecessor (SearchByProjection(Cur, Last) +
     LSDmatcher::match).  paced_hz = 0: the next frame is submitted as soon as a slot is free (sustained rate); paced_hz > 0:
     frames arrive on a camera clock and a frame is collected as soon as it is complete (latency under a 30 fps feed).
-    Returns (seconds, per-frame latency ms from submit to results + matches in hand, matches per frame)."""
+    Returns (seconds, per-frame latency ms from submit to results + matches in hand, matches per frame).  keep (a dict): receives the
+    last frame's results ("frame") and its matches against the frame before ("matches")."""
     bf = 40.0
     st = hvo.Stream(width=g.shape[2], height=g.shape[1], depth=depth, stages=mask, bf=bf, device=device)
     sf = np.cumprod(np.concatenate([[np.float32(1.0)], np.full(7, np.float32(1.2), np.float32)])).astype(np.float32)
@@ -406,15 +471,17 @@ def run_stream(hvo, np, g, d, off, mask, depth, device, nframes, paced_hz=0.0):
 
         def finish(i):                                    # collect frame i, match it against frame i - 1
             cur = st.collect(tick[i], labels=True)
-            last = state["last"]
+            last = state["last"]; got = {}
             if last is not None and (mask & 1):
                 shift = off[i % len(off)] - off[(i - 1) % len(off)] if i % len(off) else (0, 0)
                 sel, u, v, rad, lmin, lmax, ur, blocks = stream_queries(np, last, shift, sf, bf)
-                n, _, _ = st.search_by_projection(tick[i], tick[i - 1], sel, u, v, rad, lmin, lmax, ur, blocks)
+                n, got["point_idx"], got["point_dist"] = st.search_by_projection(tick[i], tick[i - 1], sel, u, v, rad, lmin, lmax, ur, blocks)
                 nm[0] += n
             if last is not None and (mask & 2):
-                n, _ = st.match_lines(tick[i - 1], tick[i], hvo.LINE_MATCH_NNR, nnratio=0.95)
+                n, got["line_match"] = st.match_lines(tick[i - 1], tick[i], hvo.LINE_MATCH_NNR, nnratio=0.95)
                 nm[1] += n
+            if keep is not None:
+                keep["frame"], keep["matches"] = cur, got
             lat.append((time.perf_counter() - tsub[i]) * 1e3)
             state["last"] = cur; state["done"] = i + 1
 
@@ -499,8 +566,11 @@ def main():
             g, d, off = synth.make_sequence("std", 0x5EED3000 + 1000 * rank, ndist, w, h)
         run_stream(hvo, np, g, d, off, mask, args.depth, local_rank, max(args.warmup, 2))          # warm-up: plans, pinned buffers
         barrier()
-        el, lat, mpts, mlines = run_stream(hvo, np, g, d, off, mask, args.depth, local_rank, nframes)
+        kept = {} if args.dump_outputs and rank == 0 else None
+        el, lat, mpts, mlines = run_stream(hvo, np, g, d, off, mask, args.depth, local_rank, nframes, keep=kept)
         barrier()
+        if kept is not None:
+            dump_outputs(np, args.dump_outputs, [kept["frame"]], 1, extra=kept["matches"])
         if dist is not None:
             t = torch.tensor([el], dtype=torch.float64, device=red_dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -519,7 +589,7 @@ def main():
                 "latency_ms": {"pipelined_p50": round(float(np.percentile(lat, 50)), 3), "pipelined_p99": round(float(np.percentile(lat, 99)), 3)},
                 "roofline": None,
             }
-            if not args.no_extras:
+            if args.full and not args.no_extras:
                 # single-frame latency: nothing else in flight (submit, collect, match, then the next frame)
                 _, lat1, _, _ = run_stream(hvo, np, g, d, off, mask, 2, local_rank, min(nframes, 64))
                 out["latency_ms"].update(single_frame_p50=round(float(np.percentile(lat1, 50)), 3), single_frame_p99=round(float(np.percentile(lat1, 99)), 3))
@@ -532,7 +602,7 @@ def main():
                 out["paced_30fps"] = sustain
                 ok = [int(k[5:]) for k, v in sustain.items() if v["fps"] >= 29.5 and v["latency_ms_p99"] < 1000.0 / 30.0 * (int(k[5:]) - 1) + 5.0]
                 out["pipeline_depth_sustaining_30fps"] = min(ok) if ok else None
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_reference_shaped(ge, stages, g, d)
                 out["latency_ms"]["cpu_reference_shaped_3_threads_p50"] = out["cpu_baseline"]["latency_ms_p50"]
             print(json.dumps(out))
@@ -576,6 +646,37 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, still resident, for a fixed seeded sample of the distinct frames (frame f + k * ndistinct
+        # repeats frame f), as hvo_batch_download hands them to a caller
+        pick = np.sort(np.random.default_rng(0x5EED).choice(ndistinct, min(DUMP_FRAMES, ndistinct), replace=False))
+        got = ctx.batch_download(mask, n=int(pick[-1]) + 1)
+        dump_outputs(np, args.dump_outputs, [got[f] for f in pick], max(1, DUMP_LABEL_BYTES // (4 * w * h)), extra={"frame_index": pick})
+        del got
+
+    frames = (256 if (args.config == "batch256" and args.batch <= 0) else world * B) * steps      # (batch256: the ranks' shards of 256 frames may differ by one)
+    value = frames / dt
+    out = {
+        "metric": "RGB-D frames/sec (640×480, 1k ORB + LSD + PEAC) at 1/2/4/8 GPUs", "value": round(value, 2), "unit": "frames/s",
+        "n_gpus": world, "steps": steps, "warmup": args.warmup, "ms_per_step": round(dt / steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/u16 integer + f32/f64",
+        "data": "synthetic",
+        "config": {"workload": "%dx%d synthetic RGB-D, %d ORB (quota; 3/4 std + 1/4 lowtex scenes) + LSD lines + PEAC planes, %d frames per GPU per step (%s)"
+                               % (w, h, nfeat, B, args.config),
+                   "stages": stages, "frames_per_gpu": B, "parallelism": "frames sharded, %d rank(s), no data-path collective" % world,
+                   "distinct_frames": ndistinct, "scene_mix": {k: kinds.count(k) for k in sorted(set(kinds))},
+                   "resident_bytes_per_frame_estimate": int(per_frame)},
+    }
+    if not args.full:
+        ctx.close()
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # --full: everything below is measured or checked after the timed steps and does not change the headline.
     # Per-kernel durations for the roofline: the same steps again with hipEvents on the kernels' stream
     # and the three subsystems serialised, so that a group's time is its own (with the streams
     # overlapped a group's event interval mostly measures waiting for CU slots held by the others).
@@ -632,8 +733,6 @@ def main():
     parity = parity_sample(ge, np, stages, res, g0, d0, kinds, nfeat, scale=w / 640.0) if rank == 0 else None
 
     if rank == 0:
-        frames = (256 if (args.config == "batch256" and args.batch <= 0) else world * B) * steps      # (batch256: the ranks' shards of 256 frames may differ by one)
-        value = frames / dt
         groups = {k: v / psteps for k, v in prof.items()}           # ms per launch group per step (serialised pass)
         if "lsd_gradient" in groups and "lsd_blur_scale" not in groups: groups["lsd_pre"] = groups.pop("lsd_gradient")      # the fused preamble reports under the second kernel's name
         table, pass_bytes = algorithmic_bytes(w, h, nkp, nlines)
@@ -667,23 +766,17 @@ def main():
                 # ... and with the quadtree, which sits between FAST and the orientation on the same stream
                 oq = orb_ms + groups.get("orb_octree", 0.0)
                 roof["orb_pyramid_brief_pass_with_quadtree_frac"] = round(pass_bytes * B / (oq * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-        out = {
-            "metric": "RGB-D frames/sec (640×480, 1k ORB + LSD + PEAC) at 1/2/4/8 GPUs", "value": round(value, 2), "unit": "frames/s",
-            "n_gpus": world, "steps": steps, "warmup": args.warmup, "ms_per_step": round(dt / steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/u16 integer + f32/f64",
-            "data": "synthetic",
-            "config": {"workload": "%dx%d synthetic RGB-D, %d ORB (quota; %.0f realised per frame: 3/4 std + 1/4 lowtex scenes) + LSD lines + PEAC planes, %d frames per GPU per step (%s)"
-                                   % (w, h, nfeat, nkp, B, args.config),
-                       "stages": stages, "frames_per_gpu": B, "parallelism": "frames sharded, %d rank(s), no data-path collective" % world,
-                       "distinct_frames": ndistinct, "scene_mix": {k: kinds.count(k) for k in sorted(set(kinds))},
-                       "mean_keypoints": round(nkp, 1), "mean_lines": round(nlines, 1), "mean_planes": round(nplanes, 2),
-                       "frames_with_capacity_flags": bad, "resident_bytes_per_frame_estimate": int(per_frame)},
+        out["config"].update(
+            workload="%dx%d synthetic RGB-D, %d ORB (quota; %.0f realised per frame: 3/4 std + 1/4 lowtex scenes) + LSD lines + PEAC planes, %d frames per GPU per step (%s)"
+                     % (w, h, nfeat, nkp, B, args.config),
+            mean_keypoints=round(nkp, 1), mean_lines=round(nlines, 1), mean_planes=round(nplanes, 2), frames_with_capacity_flags=bad)
+        out.update({
             "kernel_ms_per_step_serialised": {k: round(v, 4) for k, v in sorted(groups.items(), key=lambda kv: -kv[1])},
             "kernel_roofline": kroof,
             "roofline": roof,
             "parity_checked_frames": parity[0], "parity_failures": parity[1], "parity_lowtex_frames": parity[3],
             "parity_note": "frames of the timed resident batch compared with the CPU oracle after the timed region, every stage" + ("; FAILED: " + "; ".join(parity[2]) if parity[1] else ""),
-        }
+        })
         if gather:
             out["gather"] = gather
         if world == 1 and not args.no_extras:

@@ -1,4 +1,4 @@
-"""bench.py prints ONE JSON line with the keys the driver reads (task contract)."""
+"""bench.py prints ONE JSON line with the keys the driver reads (task contract); --full adds the side measurements and checks."""
 import json
 import os
 import subprocess
@@ -22,7 +22,7 @@ def test_bench_keys_are_in_the_source():
 
 @pytest.mark.gpu
 def test_bench_prints_the_contract_line():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -47,7 +47,7 @@ def test_bench_prints_the_contract_line():
 
 @pytest.mark.gpu
 def test_bench_stream_mode_line():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "stream", "--steps", "24", "--warmup", "2", "--no-extras"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "stream", "--steps", "24", "--warmup", "2", "--no-extras", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -56,6 +56,36 @@ def test_bench_stream_mode_line():
     assert d["unit"] == "frames/s" and d["value"] > 0 and d["steps"] == 24 and d["config"]["mode"] == "stream"
     assert d["latency_ms"]["pipelined_p50"] > 0 and d["cpu_baseline"]["cores"] == 3
     assert d["config"]["mean_point_matches"] > 100
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run prints the headline only; --dump-outputs writes the last timed step's results as float arrays (<= 64 MB), the
+    same in two runs with the same arguments"""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "64",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+        assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "u8/u16 integer + f32/f64"
+        assert "roofline" not in line and "cpu_baseline" not in line and "parity_checked_frames" not in line
+    names = sorted(f.name for f in dirs[0].iterdir())
+    assert names == sorted(f.name for f in dirs[1].iterdir())
+    for k in ("kp.npy", "desc.npy", "kl.npy", "ldesc.npy", "planes.npy", "labels.npy", "status.npy", "frame_index.npy"):
+        assert k in names, k
+    assert sum((dirs[0] / n).stat().st_size for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64), n
+        assert np.array_equal(a, b, equal_nan=True), n
+    assert len(np.load(dirs[0] / "kp.npy")) == np.load(dirs[0] / "kp_count.npy").sum() > 0
+    assert np.load(dirs[0] / "labels.npy").shape[1:] == (480, 640)
 
 
 def test_gpus_flag_must_match_world_size():

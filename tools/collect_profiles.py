@@ -34,7 +34,7 @@ acc = defaultdict(list)
 for r in csv.DictReader(open(find("kt_kernel_trace.csv"))):
     acc[r["Kernel_Name"].split("(")[0]].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)
 with open(os.path.join(P, tag + "_kernel_durations_ms.txt"), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats of `python bench.py --steps 5 --warmup 2` (default: %d frames of 640x480 per step).\n" % B)
+    f.write("# rocprofv3 --kernel-trace --stats of `python bench.py --steps 5 --warmup 2 --full` (default: %d frames of 640x480 per step).\n" % B)
     f.write("# 7 steps with ORB || LSD || PEAC on concurrent streams (durations inflated by contention) followed by the 3\n")
     f.write("# serialised profiling steps; `min` is therefore the contention-free duration bench.py reports per kernel group.\n")
     for k, v in sorted(acc.items(), key=lambda kv: -sum(kv[1])):
@@ -47,7 +47,7 @@ def summary(dirname):
 
 
 with open(os.path.join(P, tag + "_pmc_sq_summary.txt"), "w") as f:
-    f.write("# rocprofv3 --pmc SQ_* pass of `python bench.py --steps 1 --warmup 0` (%d frames per launch); tools/pmc_summary.py, largest-grid launch of each kernel\n" % B)
+    f.write("# rocprofv3 --pmc SQ_* pass of `python bench.py --steps 1 --warmup 0 --full` (%d frames per launch); tools/pmc_summary.py, largest-grid launch of each kernel\n" % B)
     f.write(summary("pmc_sq"))
 with open(os.path.join(P, tag + "_pmc_hbm_summary.txt"), "w") as f:
     f.write("# rocprofv3 --pmc FETCH_SIZE pass (KiB per frame)\n" + summary("pmc_fetch"))

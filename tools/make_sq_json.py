@@ -23,7 +23,7 @@ for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=T
         if k.startswith("__amd"): continue
         acc[k][r["Counter_Name"]] += float(r["Counter_Value"])
         if k == "k_peac_blocks" and r["Counter_Name"] == "SQ_INSTS_VALU": steps += 1
-out = {"note": "rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS of `python bench.py --steps 1 --warmup 0`; "
+out = {"note": "rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS of `python bench.py --steps 1 --warmup 0 --full`; "
                "per-frame sums over all launches of a kernel.  SQ_WAVE_CYCLES / SQ_ACTIVE_INST_* count quad-cycles summed over waves (MI355X_MICROARCH.md): a wave64 "
                "VALU instruction keeps the SIMD's VALU busy for 1 quad-cycle, so sum(ACTIVE_INST_VALU) x frames/s / (simds x clock_hz / 4) is the VALU pipes' busy fraction; "
                "ACTIVE_INST_ANY sums over waves that can have instructions of different kinds in flight at once and is only meaningful relative to WAVE_CYCLES.",

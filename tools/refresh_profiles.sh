@@ -8,10 +8,10 @@ set -e
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/prof
 mkdir -p $O
-Q="--no-cpu-baseline --no-extras"
+Q="--full --no-cpu-baseline --no-extras"
 if [ "$1" = "a" ]; then
 cd /tmp; export TMPDIR=/tmp
-echo "[a1] default bench"; timeout -k 10 500 python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+echo "[a1] default bench"; timeout -k 10 500 python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "[a2] kernel trace"; rm -rf $O/kt; timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 $Q > $O/bench_under_rocprof.json 2> $O/kt.err
 echo "[a3] pmc sq"; rm -rf $O/pmc_sq; timeout -k 10 400 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS -d $O/pmc_sq -o pmc --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 $Q > $O/pmc_sq.log 2>&1
 echo "[a4] pmc fetch"; rm -rf $O/pmc_fetch; timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o pmc --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 $Q > $O/pmc_fetch.log 2>&1
@@ -19,9 +19,9 @@ echo "[a5] pmc write"; rm -rf $O/pmc_write; timeout -k 10 400 rocprofv3 --pmc WR
 find $O -name "*.csv" -size +8M -delete
 else
 cd $R
-echo "[b1] stream bench"; timeout -k 10 400 python3 bench.py --mode stream > $O/bench_stream.json 2> $O/bench_stream.err
-echo "[b2] big1280"; timeout -k 10 400 python3 bench.py --config big1280 --steps 5 > $O/bench_big1280.json 2> $O/bench_big1280.err
-echo "[b3] batch256"; timeout -k 10 400 python3 bench.py --config batch256 --steps 20 > $O/bench_batch256.json 2> $O/bench_batch256.err
+echo "[b1] stream bench"; timeout -k 10 400 python3 bench.py --mode stream --full > $O/bench_stream.json 2> $O/bench_stream.err
+echo "[b2] big1280"; timeout -k 10 400 python3 bench.py --config big1280 --steps 5 --full > $O/bench_big1280.json 2> $O/bench_big1280.err
+echo "[b3] batch256"; timeout -k 10 400 python3 bench.py --config batch256 --steps 20 --full > $O/bench_batch256.json 2> $O/bench_batch256.err
 echo "[b4] lowtex / std latency"; timeout -k 10 300 python3 tools/latency.py std > $O/latency_std.json 2>/dev/null; timeout -k 10 300 python3 tools/latency.py lowtex > $O/latency_lowtex.json 2>/dev/null
 echo "[b5] stream scaling"; timeout -k 10 300 python3 tools/stream_scaling.py 150 > $O/stream_scaling_q4.json 2>/dev/null; GPU_MAX_HW_QUEUES=16 timeout -k 10 300 python3 tools/stream_scaling.py 150 > $O/stream_scaling_q16.json 2>/dev/null
 echo "[b6] pcie"; (for a in "1024 1" "1024 3" "2048 3" "3072 3"; do timeout -k 10 200 python3 tools/pcie_overlap.py $a 4 2>/dev/null | tail -1; done; LOCKS=0 timeout -k 10 200 python3 tools/pcie_overlap.py 2048 3 4 2>/dev/null | tail -1) > $O/pcie_note.txt

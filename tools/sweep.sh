@@ -26,7 +26,7 @@ for setting in "$@"; do
   [ "$setting" = "-" ] && setting="HVO_NOP=1"
   echo -n "[$setting] "
   if [ "$mode" = bench ]; then
-    env $setting timeout -k 10 400 python bench.py --no-cpu-baseline --no-extras "${args[@]}" 2>/dev/null | python3 -c "
+    env $setting timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-extras "${args[@]}" 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['config']['frames_per_gpu'], d['value'], d['ms_per_step'], {k: round(v, 1) for k, v in d['kernel_ms_per_step_serialised'].items()})"
   else
