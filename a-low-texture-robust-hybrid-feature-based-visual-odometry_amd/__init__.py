@@ -65,7 +65,7 @@ READING_BLUR_FLOAT, READING_LSD_8U = 1, 2
 EXPORTS = [
     "hvo_abi_version", "hvo_default_params", "hvo_create", "hvo_destroy", "hvo_strerror", "hvo_last_error",
     "hvo_extract_orb", "hvo_extract_lsd", "hvo_compute_planes",
-    "hvo_hamming_matrix", "hvo_hamming_knn2", "hvo_match_nnr", "hvo_match_lines_geom", "hvo_search_lines_by_projection", "hvo_stream_match_lines_geom", "hvo_stream_search_lines_by_projection", "hvo_search_by_projection", "hvo_stereo_from_rgbd",
+    "hvo_hamming_matrix", "hvo_hamming_knn2", "hvo_match_nnr", "hvo_match_lines_geom", "hvo_search_lines_by_projection", "hvo_stream_match_lines_geom", "hvo_stream_search_lines_by_projection", "hvo_search_lines_by_projection_map", "hvo_stream_search_lines_by_projection_map", "hvo_search_by_projection", "hvo_stereo_from_rgbd",
     "hvo_undistort_keypoints", "hvo_image_bounds", "hvo_assign_features_to_grid", "hvo_assign_lines_to_grid",
     "hvo_extract_lsd_culled", "hvo_set_line_culling", "hvo_lines_3d", "hvo_vanishing_points", "hvo_plane_clouds", "hvo_surface_normals", "hvo_search_by_projection_map", "hvo_frame_bf_match", "hvo_search_double",
     "hvo_batch_upload", "hvo_batch_run", "hvo_batch_download", "hvo_extract_batch", "hvo_batch_slab_layout", "hvo_batch_pack_results", "hvo_batch_slab_layout_ex", "hvo_batch_pack_results_ex", "hvo_batch_stage_upload", "hvo_batch_commit_staged", "hvo_batch_results_async", "hvo_batch_results_wait",
@@ -198,6 +198,8 @@ def lib():
         L.hvo_search_lines_by_projection.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_stream_match_lines_geom.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.hvo_stream_search_lines_by_projection.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.hvo_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.hvo_stream_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_search_by_projection_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_stereo_from_rgbd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
         L.hvo_extract_lsd_culled.argtypes = L.hvo_extract_lsd.argtypes
@@ -453,6 +455,26 @@ class Context:
         mi = np.zeros(max(nq, 1), np.int32); md = np.zeros(max(nq, 1), np.int32); n = C.c_int(0)
         self._chk(lib().hvo_search_lines_by_projection(self.h, nq, _p(q_xyxy), _p(q_kl), _p(q_desc), _p(q_blocks), _p(t_kl), _p(t_linefn), _p(t_desc), _p(t_occupied), nt,
                                                        _p(cs), _p(ci), _p(b), th, _p(mi), _p(md), C.byref(n)), "search_lines_by_projection")
+        return n.value, mi[:nq], md[:nq]
+
+    def search_lines_by_projection_map(self, q_xyxy, q_view_cos, q_wvec, q_desc, q_blocks, t_kl, t_linefn, t_l3d, t_desc, t_occupied, cell_start, cell_items,
+                                       bounds4, th=1.0, nn_ratio=0.95):
+        """LSDmatcher::SearchByProjection(F, vpMapLines, eval_orient, th), the local-map line search (src/LSDmatcher.cpp:709-801) -> (nmatches, match_idx,
+        match_dist).  q_blocks / t_occupied may be None; t_l3d: LINE3D_DT (mvLines3D of the current frame)"""
+        q_xyxy = np.ascontiguousarray(q_xyxy, np.float32).reshape(-1, 4); nq = len(q_xyxy)
+        q_view_cos = np.ascontiguousarray(q_view_cos, np.float32).reshape(-1); q_wvec = np.ascontiguousarray(q_wvec, np.float64).reshape(-1, 3)
+        q_desc = np.ascontiguousarray(q_desc, np.uint8).reshape(-1, 32)
+        t_kl = np.ascontiguousarray(t_kl); nt = len(t_kl); t_l3d = np.ascontiguousarray(t_l3d, LINE3D_DT)
+        t_linefn = np.ascontiguousarray(t_linefn, np.float64); t_desc = np.ascontiguousarray(t_desc, np.uint8); b = np.ascontiguousarray(bounds4, np.float32)
+        assert len(q_view_cos) == nq and len(q_wvec) == nq and len(q_desc) == nq and len(t_l3d) == nt and len(t_desc) == nt
+        keep = [None if a is None else np.ascontiguousarray(a, np.uint8) for a in (q_blocks, t_occupied)]
+        cs = np.ascontiguousarray(cell_start, np.int32); ci = np.ascontiguousarray(cell_items, np.int32)
+        if len(ci) == 0: ci = np.zeros(1, np.int32)
+        pp = lambda a: None if a is None else _p(a)
+        mi = np.zeros(max(nq, 1), np.int32); md = np.zeros(max(nq, 1), np.int32); n = C.c_int(0)
+        self._chk(lib().hvo_search_lines_by_projection_map(self.h, nq, pp(q_xyxy), pp(q_view_cos), pp(q_wvec), pp(q_desc), pp(keep[0]), pp(t_kl), pp(t_linefn),
+                                                           pp(t_l3d), pp(t_desc), pp(keep[1]), nt, _p(cs), _p(ci), _p(b), th, nn_ratio, _p(mi), _p(md), C.byref(n)),
+                  "search_lines_by_projection_map")
         return n.value, mi[:nq], md[:nq]
 
     def set_readings(self, blur_float=False, lsd_8u=False):
@@ -885,6 +907,20 @@ class Stream:
         self._chk(lib().hvo_stream_search_lines_by_projection(self.h, cur, last, nq, _p(q_index), _p(q_xyxy), None if keep[0] is None else _p(keep[0]),
                                                               None if keep[1] is None else _p(keep[1]), None if keep[2] is None else _p(keep[2]), th,
                                                               _p(mi), _p(md), C.byref(n)), "stream_search_lines_by_projection")
+        return n.value, mi[:nq], md[:nq]
+
+    def search_lines_by_projection_map(self, cur, q_xyxy, q_view_cos, q_wvec, q_desc, q_blocks=None, t_occupied=None, th=1.0, nn_ratio=0.95):
+        """LSDmatcher::SearchByProjection(F, vpMapLines, eval_orient, th) on the resident frame `cur` (needs STAGE_GRIDS | STAGE_LINES3D and depth)
+        -> (nmatches, match_idx, match_dist)"""
+        q_xyxy = np.ascontiguousarray(q_xyxy, np.float32).reshape(-1, 4); nq = len(q_xyxy)
+        q_view_cos = np.ascontiguousarray(q_view_cos, np.float32).reshape(-1); q_wvec = np.ascontiguousarray(q_wvec, np.float64).reshape(-1, 3)
+        q_desc = np.ascontiguousarray(q_desc, np.uint8).reshape(-1, 32)
+        assert len(q_view_cos) == nq and len(q_wvec) == nq and len(q_desc) == nq
+        keep = [None if a is None else np.ascontiguousarray(a, np.uint8) for a in (q_blocks, t_occupied)]
+        pp = lambda a: None if a is None else _p(a)
+        mi = np.zeros(max(nq, 1), np.int32); md = np.zeros(max(nq, 1), np.int32); n = C.c_int(0)
+        self._chk(lib().hvo_stream_search_lines_by_projection_map(self.h, cur, nq, pp(q_xyxy), pp(q_view_cos), pp(q_wvec), pp(q_desc), pp(keep[0]), pp(keep[1]),
+                                                                  th, nn_ratio, _p(mi), _p(md), C.byref(n)), "stream_search_lines_by_projection_map")
         return n.value, mi[:nq], md[:nq]
 
     def match_lines(self, frm, to, mode=LINE_MATCH_NNR, th=50.0, nnratio=0.95):

@@ -619,6 +619,25 @@ int hvo_search_lines_by_projection(hvo_ctx *ctx, int nq, const float *q_xyxy, co
                                             match_idx, match_dist, n_matches);
 }
 
+// LSDmatcher::SearchByProjection(F, vpMapLines, eval_orient, th) (LSDmatcher.cpp:709-801), the local-map line search (line_map.inc)
+int hvo_search_lines_by_projection_map(hvo_ctx *ctx, int nq, const float *q_xyxy, const float *q_view_cos, const double *q_wvec,
+                                       const uint8_t *q_desc, const uint8_t *q_blocks,
+                                       const hvo_keyline *t_kl, const double *t_linefn, const hvo_line3d *t_l3d, const uint8_t *t_desc, const uint8_t *t_occupied, int nt,
+                                       const int32_t *cell_start, const int32_t *cell_items, const float bounds4[4], float th, float nn_ratio,
+                                       int32_t *match_idx, int32_t *match_dist, int *n_matches)
+{
+    if (!ctx || !match_idx || !match_dist || !n_matches || !bounds4 || nq < 0 || nt < 0) return HVO_ERR_INVALID_ARG;
+    *n_matches = 0;
+    for (int i = 0; i < nq; i++) { match_idx[i] = -1; match_dist[i] = 256; }
+    if (nq > 0 && (!q_xyxy || !q_view_cos || !q_wvec || !q_desc)) return HVO_ERR_INVALID_ARG;
+    if (nt > 0 && (!t_kl || !t_linefn || !t_l3d || !t_desc || !cell_start)) return HVO_ERR_INVALID_ARG;
+    const int n_items = nt > 0 ? cell_start[HVO_GRID_COLS * HVO_GRID_ROWS] : 0;
+    if (nt > 0 && (!(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]) || n_items < 0 || (n_items > 0 && !cell_items))) return HVO_ERR_INVALID_ARG;
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    return match_search_lines_by_projection_map(ctx, nq, q_xyxy, q_view_cos, q_wvec, q_desc, q_blocks, t_kl, t_linefn, t_l3d, t_desc, t_occupied, nt,
+                                                cell_start, cell_items, n_items, bounds4, th, nn_ratio, match_idx, match_dist, n_matches);
+}
+
 // LSDmatcher::SearchDouble / SearchByDescriptor core (LSDmatcher.cpp:902-939): FrameBFMatch in both directions + mutual check
 int hvo_search_double(hvo_ctx *ctx, const uint8_t *d1, int n1, const uint8_t *d2, int n2, float th, float nnratio,
                       int32_t *m12, int *n_matches)

@@ -332,6 +332,24 @@ int match_search_lines_by_projection(hvo_ctx *ctx, int nq, const float *q_xyxy, 
                                      const hvo_keyline *t_kl, const double *t_linefn, const uint8_t *t_desc, const uint8_t *t_occupied, int nt,
                                      const int32_t *cell_start, const int32_t *cell_items, int n_items, const float *bounds4, float th,
                                      int32_t *match_idx, int32_t *match_dist, int *n_matches);
+// line_map.inc (part of match.hip): LSDmatcher::SearchByProjection(F, vpMapLines, eval_orient, th), the local-map line search
+#define LSBP_MAP_MAXQ 16384       // map lines per call (the key rows take nq x nt x 8 bytes of scratch)
+struct LsbpTop;
+struct LsbpMapDev {
+    int nq, nt;
+    const float *q_xyxy; const float *q_view_cos; const double *q_wvec; const uint8_t *q_desc; const uint8_t *q_blocks;
+    const hvo_keyline *t_kl; const double *t_fn; const hvo_line3d *t_l3d; const uint8_t *t_desc; const uint8_t *t_occ;
+    const int32_t *cell_start, *cell_items; int n_items;
+    float mnMinX, mnMaxX, mnMinY, mnMaxY, th, nn_ratio; double cos_normal;
+    unsigned long long *keys; LsbpTop *top; int32_t *match_idx, *match_dist; int *n_matches;
+};
+size_t match_lsbp_map_scratch_bytes(int nq, int nt);
+int match_lsbp_map_enqueue(hipStream_t st, LsbpMapDev a, void *scratch);
+const char *match_lsbp_map_limit_text(int nq, int nt);
+int match_search_lines_by_projection_map(hvo_ctx *ctx, int nq, const float *q_xyxy, const float *q_view_cos, const double *q_wvec, const uint8_t *q_desc,
+                                         const uint8_t *q_blocks, const hvo_keyline *t_kl, const double *t_linefn, const hvo_line3d *t_l3d, const uint8_t *t_desc,
+                                         const uint8_t *t_occupied, int nt, const int32_t *cell_start, const int32_t *cell_items, int n_items,
+                                         const float *bounds4, float th, float nn_ratio, int32_t *match_idx, int32_t *match_dist, int *n_matches);
 int match_stereo_enqueue(hipStream_t st, const hvo_keypoint *d_kp, const hvo_keypoint *d_kpun, const int *d_n, int n_max, const uint16_t *d_depth, int pitch,
                          int w, int h, float dfac, float bf, float *d_uright, float *d_zdepth);
 int match_stereo_from_rgbd(hvo_ctx *ctx, const hvo_keypoint *kp, const hvo_keypoint *kpun, int n, const uint16_t *depth, int w, int h, int stride,

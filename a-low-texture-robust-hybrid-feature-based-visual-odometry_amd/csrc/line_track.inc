@@ -61,48 +61,57 @@ __global__ __launch_bounds__(256) void k_lines_geom_gate(int32_t *__restrict__ m
 }
 
 
-__global__ __launch_bounds__(64) void k_lsbp_keys(LsbpDev a)
+// Frame::GetFeaturesInAreaForLine's window walk (src/Frame.cc:1557-1627) by one wave: rank[j] (LDS, preset to ~0) receives the smallest visit
+// position at which line j passes the direction test (|cos| >= dir_th; a NaN passes) and the distance test for that sample point; r is the radius.
+static __device__ __forceinline__ void lsbp_window(unsigned *rank, const float *__restrict__ q4, float r, float dir_th, const int32_t *__restrict__ cell_start,
+                                                   const int32_t *__restrict__ cell_items, int n_items, const hvo_keyline *__restrict__ t_kl,
+                                                   const double *__restrict__ t_fn, int nt, float mnMinX, float mnMaxX, float mnMinY, float mnMaxY, int lane)
 {
-    __shared__ unsigned rank[LSBP_MAXT];
-    const int q = blockIdx.x, lane = threadIdx.x, nt = a.nt;
-    for (int j = lane; j < nt; j += 64) rank[j] = 0xFFFFFFFFu;
-    __syncthreads();
-    const float x1 = a.q_xyxy[4 * q], y1 = a.q_xyxy[4 * q + 1], x2 = a.q_xyxy[4 * q + 2], y2 = a.q_xyxy[4 * q + 3], r = a.th;
-    const float xs[3] = { x1, (float)((double)__fadd_rn(x1, x2) / 2.0), x2 }, ys[3] = { y1, (float)((double)__fadd_rn(y1, y2) / 2.0), y2 };
+    const float x1 = q4[0], y1 = q4[1], x2 = q4[2], y2 = q4[3];
+    const float xm = (float)((double)__fadd_rn(x1, x2) / 2.0), ym = (float)((double)__fadd_rn(y1, y2) / 2.0);      // the sample points: start, middle, end
     float d1x = __fsub_rn(x1, x2), d1y = __fsub_rn(y1, y2);
     const float n1 = sqrtf(__fadd_rn(__fmul_rn(d1x, d1x), __fmul_rn(d1y, d1y)));
     d1x = d1x / n1; d1y = d1y / n1;
-    const float invW = (float)HVO_GRID_COLS / __fsub_rn(a.mnMaxX, a.mnMinX), invH = (float)HVO_GRID_ROWS / __fsub_rn(a.mnMaxY, a.mnMinY);
+    const float invW = (float)HVO_GRID_COLS / __fsub_rn(mnMaxX, mnMinX), invH = (float)HVO_GRID_ROWS / __fsub_rn(mnMaxY, mnMinY);
     unsigned base = 0;                                           // visits so far (uniform)
     for (int i = 0; i < 3; i++) {
-        const float x = xs[i], y = ys[i];
-        int cx0 = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, a.mnMinX), r), invW)); if (cx0 < 0) cx0 = 0;
+        const float x = i == 0 ? x1 : i == 1 ? xm : x2, y = i == 0 ? y1 : i == 1 ? ym : y2;      // (selects: no stack array)
+        int cx0 = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, mnMinX), r), invW)); if (cx0 < 0) cx0 = 0;
         if (cx0 >= HVO_GRID_COLS) continue;
-        int cx1 = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, a.mnMinX), r), invW)); if (cx1 > HVO_GRID_COLS - 1) cx1 = HVO_GRID_COLS - 1;
+        int cx1 = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, mnMinX), r), invW)); if (cx1 > HVO_GRID_COLS - 1) cx1 = HVO_GRID_COLS - 1;
         if (cx1 < 0) continue;
-        int cy0 = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, a.mnMinY), r), invH)); if (cy0 < 0) cy0 = 0;
+        int cy0 = (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, mnMinY), r), invH)); if (cy0 < 0) cy0 = 0;
         if (cy0 >= HVO_GRID_ROWS) continue;
-        int cy1 = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, a.mnMinY), r), invH)); if (cy1 > HVO_GRID_ROWS - 1) cy1 = HVO_GRID_ROWS - 1;
+        int cy1 = (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, mnMinY), r), invH)); if (cy1 > HVO_GRID_ROWS - 1) cy1 = HVO_GRID_ROWS - 1;
         if (cy1 < 0) continue;
         for (int ix = cx0; ix <= cx1; ix++) {
             // cells (ix, cy0 .. cy1) are neighbours in the CSR: one contiguous range of items, in the reference's visiting order
-            const int k0 = a.cell_start[ix * HVO_GRID_ROWS + cy0], k1 = min(a.cell_start[ix * HVO_GRID_ROWS + cy1 + 1], a.n_items);
+            const int k0 = cell_start[ix * HVO_GRID_ROWS + cy0], k1 = min(cell_start[ix * HVO_GRID_ROWS + cy1 + 1], n_items);
             for (int k = k0 + lane; k < k1; k += 64) {
-                const int j = a.cell_items[k];
+                const int j = cell_items[k];
                 if ((unsigned)j >= (unsigned)nt) continue;
-                const hvo_keyline t = a.t_kl[j];
+                const hvo_keyline t = t_kl[j];
                 float d2x = __fsub_rn(t.sx, t.ex), d2y = __fsub_rn(t.sy, t.ey);
                 const float n2 = sqrtf(__fadd_rn(__fmul_rn(d2x, d2x), __fmul_rn(d2y, d2y)));
                 d2x = d2x / n2; d2y = d2y / n2;
                 const float cs = fabsf(__fadd_rn(__fmul_rn(d1x, d2x), __fmul_rn(d1y, d2y)));
-                if (cs < 0.96f) continue;                        // (a NaN passes, as in the reference)
-                const double *fn = a.t_fn + 3 * (size_t)j;
+                if (cs < dir_th) continue;                       // (a NaN passes, as in the reference)
+                const double *fn = t_fn + 3 * (size_t)j;
                 const float dist = (float)(fn[0] * (double)x + fn[1] * (double)y + fn[2]);
                 if (fabsf(dist) < r) atomicMin(&rank[j], base + (unsigned)(k - k0));
             }
             base += (unsigned)max(k1 - k0, 0);
         }
     }
+}
+
+__global__ __launch_bounds__(64) void k_lsbp_keys(LsbpDev a)
+{
+    __shared__ unsigned rank[LSBP_MAXT];
+    const int q = blockIdx.x, lane = threadIdx.x, nt = a.nt;
+    for (int j = lane; j < nt; j += 64) rank[j] = 0xFFFFFFFFu;
+    __syncthreads();
+    lsbp_window(rank, a.q_xyxy + 4 * (size_t)q, a.th, 0.96f, a.cell_start, a.cell_items, a.n_items, a.t_kl, a.t_fn, nt, a.mnMinX, a.mnMaxX, a.mnMinY, a.mnMaxY, lane);
     __syncthreads();
     const int qi = a.q_index ? a.q_index[q] : q;
     const hvo_keyline ql = a.q_kl[qi];
@@ -217,7 +226,7 @@ int match_search_lines_by_projection(hvo_ctx *ctx, int nq, const float *q_xyxy, 
                                      const int32_t *cell_start, const int32_t *cell_items, int n_items, const float *bounds4, float th,
                                      int32_t *match_idx, int32_t *match_dist, int *n_matches)
 {
-    if (nt > LSBP_MAXT || nq > 65535 || n_items >= (1 << 22)) return HVO_ERR_UNSUPPORTED;
+    if (nt > LSBP_MAXT || nq > 65535 || n_items >= (1 << 22)) { ctx->last_error = "guided line search: more than 2048 current lines, 65535 queries or 2^22 line grid items"; return HVO_ERR_UNSUPPORTED; }
     const int ncell = HVO_GRID_COLS * HVO_GRID_ROWS + 1;
     const size_t in_b = AL(nq * 4, float) + AL(nq, hvo_keyline) + AL(nq * 32, char) + AL(nq, char) + AL(nt, hvo_keyline) + AL(nt * 3, double) + AL(nt * 32, char) + AL(nt, char) +
                         AL(ncell, int32_t) + AL(n_items, int32_t);

@@ -51,6 +51,8 @@ struct hvo_stream {
     const float *bounds4() const { return bounds; }
     // matching scratch (device + pinned), sized for kp_cap queries
     char *d_ms = nullptr, *h_ms = nullptr; size_t ms_bytes = 0;
+    // the local-map line search's scratch (hvo_stream_search_lines_by_projection_map): allocated on its first call, grow-only
+    char *d_lm = nullptr, *h_lm = nullptr; size_t lm_dbytes = 0, lm_hbytes = 0;
     hipStream_t s_match = nullptr;         // the matching calls run here, behind the two frames' events (not behind a frame's line chain)
     std::string last_error;
 };
@@ -83,6 +85,8 @@ void hvo_stream_destroy(hvo_stream *s)
     }
     if (s->d_ms) (void)hipFree(s->d_ms);
     if (s->h_ms) (void)hipHostFree(s->h_ms);
+    if (s->d_lm) (void)hipFree(s->d_lm);
+    if (s->h_lm) (void)hipHostFree(s->h_lm);
     if (s->s_match) (void)hipStreamDestroy(s->s_match);
     delete s;
 }
@@ -683,7 +687,78 @@ int hvo_stream_search_lines_by_projection(hvo_stream *s, int64_t cur, int64_t la
     if (off > s->ms_bytes) { s->last_error = "matching scratch too small"; return HVO_ERR_CAPACITY; }
     a.match_idx = dout; a.match_dist = dout + nq; a.n_matches = dout + 2 * nq;
     int rc = match_lsbp_enqueue(st, a, scratch);
-    if (rc) return rc;
+    if (rc) { s->last_error = rc == HVO_ERR_UNSUPPORTED ? "guided line search: more than 2048 current lines (or 2^22 line grid items)" : "guided line search launch"; return rc; }
+    ST_HIP(hipMemcpyAsync(hout, dout, (2 * (size_t)nq + 1) * 4, hipMemcpyDeviceToHost, st));
+    ST_HIP(hipStreamSynchronize(st));
+    memcpy(match_idx, hout, (size_t)nq * 4); memcpy(match_dist, hout + nq, (size_t)nq * 4);
+    *n_matches = hout[2 * nq];
+    return HVO_OK;
+}
+
+// LSDmatcher::SearchByProjection(F, vpMapLines, eval_orient, th) on the resident frame `cur` (src/LSDmatcher.cpp:709-801; Tracking::SearchLocalLines,
+// src/Tracking.cc:3279-3355): key lines, line functions, descriptors, LINE GRID and 3-D lines are the resident ones (HVO_STAGE_GRIDS | HVO_STAGE_LINES3D);
+// per query only the map line's projection, viewing cosine, world vector, descriptor and observation flag go up
+int hvo_stream_search_lines_by_projection_map(hvo_stream *s, int64_t cur, int nq, const float *q_xyxy, const float *q_view_cos,
+                                              const double *q_wvec, const uint8_t *q_desc, const uint8_t *q_blocks, const uint8_t *t_occupied, float th, float nn_ratio,
+                                              int32_t *match_idx, int32_t *match_dist, int *n_matches)
+{
+    if (!s || !match_idx || !match_dist || !n_matches || nq < 0) return HVO_ERR_INVALID_ARG;
+    *n_matches = 0;
+    const unsigned need = HVO_STAGE_GRIDS | HVO_STAGE_LINES3D;
+    if (!(s->sp.stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL)) || (s->tail_stages & need) != need) {
+        s->last_error = "local-map line search: the stream must run HVO_STAGE_GRIDS and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
+    }
+    StreamSlot *B = slot_of(s, cur);
+    if (!B) return HVO_ERR_INVALID_ARG;
+    if (!B->had_depth) { s->last_error = "local-map line search: the frame was submitted without depth (no 3-D lines)"; return HVO_ERR_INVALID_ARG; }
+    for (int i = 0; i < nq; i++) { match_idx[i] = -1; match_dist[i] = 256; }
+    if (nq == 0) return HVO_OK;
+    if (!q_xyxy || !q_view_cos || !q_wvec || !q_desc) return HVO_ERR_INVALID_ARG;
+    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    ST_HIP(hipEventSynchronize(B->ev_lsd));                     // (recorded behind the tail stages -- 3-D lines, line grid -- and their downloads)
+    const int n2 = ((const int *)(B->h_out + s->lay.counts))[4];
+    if (n2 <= 0) return HVO_OK;
+    const TailLayout &T = s->tl;
+    const int n_items = ((const int *)(B->h_tail + T.counts))[3];
+    if (n_items < 0 || n_items > T.ln_cap) { s->last_error = "line grid overflowed its capacity"; return HVO_ERR_CAPACITY; }
+    if (n2 > 2048 || nq > LSBP_MAP_MAXQ || n_items >= (1 << 22)) { s->last_error = match_lsbp_map_limit_text(nq, n2); return HVO_ERR_UNSUPPORTED; }
+    hipStream_t st = s->s_match;
+    const size_t up_b = al64((size_t)nq * 16) + al64((size_t)nq * 4) + al64((size_t)nq * 24) + al64((size_t)nq * 32) + al64((size_t)nq) + al64((size_t)n2);
+    const size_t out_b = al64((2 * (size_t)nq + 1) * 4), sb = match_lsbp_map_scratch_bytes(nq, n2);
+    if (s->lm_dbytes < up_b + out_b + sb || s->lm_hbytes < up_b + out_b) {
+        ST_HIP(hipStreamSynchronize(st));
+        if (s->d_lm) (void)hipFree(s->d_lm);
+        if (s->h_lm) (void)hipHostFree(s->h_lm);
+        s->d_lm = s->h_lm = nullptr; s->lm_dbytes = s->lm_hbytes = 0;
+        const size_t db = up_b + out_b + sb, hb = up_b + out_b;
+        ST_HIP(hipMalloc((void **)&s->d_lm, db));
+        ST_HIP(hipHostMalloc((void **)&s->h_lm, hb, hipHostMallocDefault));
+        s->lm_dbytes = db; s->lm_hbytes = hb;
+    }
+    char *d = s->d_lm, *hh = s->h_lm; size_t off = 0;
+    auto up = [&](const void *src, size_t bytes) -> void * {
+        void *dp = d + off, *hp = hh + off; off += al64(bytes);
+        memcpy(hp, src, bytes);
+        if (hipMemcpyAsync(dp, hp, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return nullptr;
+        return dp;
+    };
+    LsbpMapDev a; memset(&a, 0, sizeof(a));
+    a.nq = nq; a.nt = n2;
+    a.q_xyxy = (const float *)up(q_xyxy, (size_t)nq * 16); a.q_view_cos = (const float *)up(q_view_cos, (size_t)nq * 4);
+    a.q_wvec = (const double *)up(q_wvec, (size_t)nq * 24); a.q_desc = (const uint8_t *)up(q_desc, (size_t)nq * 32);
+    a.q_blocks = q_blocks ? (const uint8_t *)up(q_blocks, (size_t)nq) : nullptr;
+    a.t_occ = t_occupied ? (const uint8_t *)up(t_occupied, (size_t)n2) : nullptr;
+    if (!a.q_xyxy || !a.q_view_cos || !a.q_wvec || !a.q_desc || (q_blocks && !a.q_blocks) || (t_occupied && !a.t_occ)) { s->last_error = "local-map line search upload"; return HVO_ERR_HIP; }
+    a.t_kl = B->lv.d_kl; a.t_fn = B->lv.d_fn; a.t_desc = B->lv.d_desc; a.t_l3d = (const hvo_line3d *)(B->d_tail + T.lines3d);
+    a.cell_start = (const int32_t *)(B->d_tail + T.ln_start); a.cell_items = (const int32_t *)(B->d_tail + T.ln_items); a.n_items = n_items;
+    a.mnMinX = s->bounds[0]; a.mnMaxX = s->bounds[1]; a.mnMinY = s->bounds[2]; a.mnMaxY = s->bounds[3]; a.th = th; a.nn_ratio = nn_ratio;
+    a.cos_normal = cos(15.0 / 180.0 * M_PI);
+    off = up_b;
+    int32_t *dout = (int32_t *)(d + off); int32_t *hout = (int32_t *)(hh + off); off += out_b;
+    void *scratch = d + off;
+    a.match_idx = dout; a.match_dist = dout + nq; a.n_matches = dout + 2 * nq;
+    int rc = match_lsbp_map_enqueue(st, a, scratch);
+    if (rc) { s->last_error = "local-map line search launch"; return rc; }
     ST_HIP(hipMemcpyAsync(hout, dout, (2 * (size_t)nq + 1) * 4, hipMemcpyDeviceToHost, st));
     ST_HIP(hipStreamSynchronize(st));
     memcpy(match_idx, hout, (size_t)nq * 4); memcpy(match_dist, hout + nq, (size_t)nq * 4);

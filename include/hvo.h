@@ -205,6 +205,23 @@ typedef struct {
 } hvo_line3d;
 int hvo_lines_3d(hvo_ctx *ctx, const hvo_keyline *kl, int n, const uint16_t *depth, int w, int h, int stride, uint32_t seed, hvo_line3d *out);
 
+/* LSDmatcher::SearchByProjection(F, vpMapLines, eval_orient, th), the local-map line search (reference src/LSDmatcher.cpp:709-801 over
+ * Frame::GetFeaturesInAreaForLine with its default direction gate 0.998, src/Frame.cc:1557-1627; called by Tracking::SearchLocalLines,
+ * src/Tracking.cc:3279-3355) on host arrays.  One query per map line with mbTrackInView && !isBad(), in vpMapLines order (the caller filters):
+ * q_xyxy[4 i ..] = (mTrackProjX1, mTrackProjY1, mTrackProjX2, mTrackProjY2), q_view_cos[i] = mTrackViewCos (radius 5 when > 0.998, else 8:
+ * RadiusByViewingCos 1436-1442; times th when th != 1), q_wvec[3 i ..] = GetWorldVector(), q_desc (nq x 32) = GetDescriptor(), q_blocks[i] != 0
+ * when Observations() > 0 (may be NULL: none).  mnTrackScaleLevel and eval_orient are not read by the reference.  t_l3d = the current frame's
+ * mvLines3D (hvo_lines_3d): a line is skipped when |(A - B) . wvec| / (|A - B| |wvec|) < cos 15 degrees (NaN passes); t_occupied (may be NULL):
+ * lines already holding a map line with observations.  Best and second best distance; accepted if best <= 95 and not (same octave && best >
+ * nn_ratio * second).  match_idx[i] = the current line or -1, match_dist[i] = its distance or 256; the reference assigns F.mvpMapLines[match_idx[i]]
+ * in query order (a later acceptance overwrites a claim by a map line without observations).  At most 2048 current lines and 16384 queries
+ * (HVO_ERR_UNSUPPORTED).  See hvo_stream_search_lines_by_projection_map. */
+int hvo_search_lines_by_projection_map(hvo_ctx *ctx, int nq, const float *q_xyxy, const float *q_view_cos, const double *q_wvec,
+                                       const uint8_t *q_desc, const uint8_t *q_blocks,
+                                       const hvo_keyline *t_kl, const double *t_linefn, const hvo_line3d *t_l3d, const uint8_t *t_desc, const uint8_t *t_occupied, int nt,
+                                       const int32_t *cell_start, const int32_t *cell_items, const float bounds4[4], float th, float nn_ratio,
+                                       int32_t *match_idx, int32_t *match_dist, int *n_matches);
+
 /* The vanishing-point clustering of the key lines that the Frame constructor runs on every frame (reference src/Frame.cc:330-337,
  * SURVEY.md 8f.4): Frame::getVPHypVia2Lines (442-545: 105 random pairs of lines x 360 rotations = 37 800 hypotheses of three
  * orthogonal vanishing directions), getSphereGrids (546-650: the 90 x 360 grid of pairwise line intersections, weighted, 3x3
@@ -461,6 +478,13 @@ int  hvo_stream_match_lines_geom(hvo_stream *s, int64_t cur, int64_t last, float
  * descriptors and line grid are the resident ones: the stream must run HVO_STAGE_GRIDS.  match_idx[i] = current line or -1 (accepted at <= 95). */
 int  hvo_stream_search_lines_by_projection(hvo_stream *s, int64_t cur, int64_t last, int nq, const int32_t *q_index, const float *q_xyxy, const uint8_t *q_desc,
                                            const uint8_t *q_blocks, const uint8_t *t_occupied, float th, int32_t *match_idx, int32_t *match_dist, int *n_matches);
+/* LSDmatcher::SearchByProjection(F, vpMapLines, eval_orient, th) on the resident frame `cur` (reference src/LSDmatcher.cpp:709-801): its key lines, line
+ * functions, descriptors, line grid and 3-D lines are read on the device; per query only the map line's fields go up (as in
+ * hvo_search_lines_by_projection_map; t_occupied: n_kl(cur) flags, may be NULL).  The stream must run HVO_STAGE_GRIDS and HVO_STAGE_LINES3D and the
+ * frame must have been submitted with depth (else HVO_ERR_INVALID_ARG).  Its scratch is allocated on the first call and grows on demand. */
+int  hvo_stream_search_lines_by_projection_map(hvo_stream *s, int64_t cur, int nq, const float *q_xyxy, const float *q_view_cos,
+                                               const double *q_wvec, const uint8_t *q_desc, const uint8_t *q_blocks, const uint8_t *t_occupied, float th, float nn_ratio,
+                                               int32_t *match_idx, int32_t *match_dist, int *n_matches);
 
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer.  Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally

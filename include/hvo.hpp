@@ -326,7 +326,8 @@ public:
         LineMatches.resize(n1);
         return n;
     }
-    explicit LSDmatcher(hvo_ctx *ctx) : ctx_(ctx) {}
+    // LSDmatcher(nnratio = 0.95, checkOri) (include/LSDmatcher.h:23): mfNNratio is read by the local-map SearchByProjection only
+    explicit LSDmatcher(hvo_ctx *ctx, float nnratio = 0.95f) : ctx_(ctx), mfNNratio(nnratio) {}
     // int match(desc1, desc2, nnr, matches_12) -> matchNNR (LSDmatcher.cpp:828-863, 803-826)
     int match(const uint8_t *desc1, int n1, const uint8_t *desc2, int n2, float nnr, std::vector<int> &matches_12) const
     {
@@ -361,8 +362,24 @@ public:
         match_idx.resize(nq);
         return n;
     }
+    // int SearchByProjection(F, vpMapLines, eval_orient, th) (LSDmatcher.cpp:709-801), the local-map line search of Tracking::SearchLocalLines: one
+    // query per map line with mbTrackInView && !isBad() (mTrackProjX1/Y1/X2/Y2, mTrackViewCos, GetWorldVector(), GetDescriptor(), Observations() > 0);
+    // the current frame's key lines, line functions, 3-D lines (mvLines3D), descriptors, occupied flags and line grid.  eval_orient is not read by
+    // the reference and is not taken.  The caller assigns F.mvpMapLines[match_idx[i]] = pML in query order.
+    int SearchByProjection(int nq, const float *q_xyxy, const float *q_view_cos, const double *q_wvec, const uint8_t *q_desc, const uint8_t *q_blocks,
+                           const hvo_keyline *t_kl, const double *t_linefn, const hvo_line3d *t_l3d, const uint8_t *t_desc, const uint8_t *t_occupied, int nt,
+                           const int32_t *cell_start, const int32_t *cell_items, const float bounds4[4], float th, std::vector<int32_t> &match_idx) const
+    {
+        match_idx.assign(nq > 0 ? nq : 1, -1); std::vector<int32_t> dist(nq > 0 ? nq : 1, 256);
+        int n = 0;
+        check(hvo_search_lines_by_projection_map(ctx_, nq, q_xyxy, q_view_cos, q_wvec, q_desc, q_blocks, t_kl, t_linefn, t_l3d, t_desc, t_occupied, nt,
+                                                 cell_start, cell_items, bounds4, th, mfNNratio, match_idx.data(), dist.data(), &n), "hvo_search_lines_by_projection_map");
+        match_idx.resize(nq);
+        return n;
+    }
 private:
     hvo_ctx *ctx_;
+    float mfNNratio;
 };
 
 
@@ -453,6 +470,19 @@ public:
         int n = 0;
         check(hvo_stream_search_lines_by_projection(s_, cur, last, nq, q_index.data(), q_xyxy.data(), q_desc, q_blocks, t_occupied, th, match_idx.data(), dist.data(), &n),
               "hvo_stream_search_lines_by_projection");
+        match_idx.resize(nq);
+        return n;
+    }
+    // Tracking::SearchLocalLines' matcher.SearchByProjection(mCurrentFrame, mvpLocalMapLines, eval_orient, th) (Tracking.cc:3279-3355 ->
+    // LSDmatcher.cpp:709-801) on the resident frame `cur`: per query the map line's fields as in LSDmatcher::SearchByProjection above; the frame's lines,
+    // line grid and 3-D lines stay on the device.  The stream must run HVO_STAGE_GRIDS | HVO_STAGE_LINES3D and the frame must come with depth.
+    int searchLocalLines(int64_t cur, int nq, const float *q_xyxy, const float *q_view_cos, const double *q_wvec, const uint8_t *q_desc, const uint8_t *q_blocks,
+                         const uint8_t *t_occupied, float th, std::vector<int32_t> &match_idx, float nnratio = 0.95f)
+    {
+        match_idx.assign(nq > 0 ? nq : 1, -1); std::vector<int32_t> dist(nq > 0 ? nq : 1, 256);
+        int n = 0;
+        check(hvo_stream_search_lines_by_projection_map(s_, cur, nq, q_xyxy, q_view_cos, q_wvec, q_desc, q_blocks, t_occupied, th, nnratio,
+                                                        match_idx.data(), dist.data(), &n), "hvo_stream_search_lines_by_projection_map");
         match_idx.resize(nq);
         return n;
     }
