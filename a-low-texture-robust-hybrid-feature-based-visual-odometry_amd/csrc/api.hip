@@ -238,7 +238,11 @@ int hvo_batch_stage_upload(hvo_ctx *ctx, int n, const hvo_frame_in *in, int w, i
     // (batch k would then run on blank images in the documented stage(k + 1) / run(k) loop).  Such a call is refused; a first batch, or a
     // context whose resident batch was given up (hvo_batch_upload of the new geometry), builds the plans here.
     const int pb = std::max(n, ctx->p.max_batch);
-    if (ctx->batch_n > 0 && (!orb_plan_covers(ctx, w, h, pb) || (depth && !peac_plan_covers(ctx, w, h, pb)))) return HVO_ERR_INVALID_ARG;
+    if (ctx->batch_n > 0 && (!orb_plan_covers(ctx, w, h, pb) || (depth && !peac_plan_covers(ctx, w, h, pb)))) {
+        ctx->last_error = "staging would rebuild the resident batch's plans (another geometry, more frames, or depth the resident batch had none of): "
+                          "call hvo_batch_upload for the new geometry or size first";
+        return HVO_ERR_INVALID_ARG;
+    }
     // the plans first (their geometry gives the staging slabs' sizes)
     int rc = orb_ensure_plan(ctx, w, h, pb);
     if (rc) return rc;

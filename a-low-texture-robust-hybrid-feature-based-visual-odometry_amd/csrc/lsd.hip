@@ -1729,6 +1729,7 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
     int rc = lsd_ensure_plan(ctx, O.w, O.h, std::max(n, ctx->p.max_batch));
     if (rc) return rc;
     LsdPlan *P = plan_of(ctx);
+    P->async_last_n = P->async_last_w = 0;                     // hvo_lsd_async_report describes THIS launch: nothing async until it is
     hipStream_t st = hvo_stream_lsd(ctx);
     const int w = P->w, h = P->h, sw = P->sw, sh = P->sh;
     const uint8_t *gray = O.d_pyr + O.lev[0].img_off;
@@ -1818,6 +1819,9 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
     if (n <= 2 && (size_t)sw * sh >= 600000) aw = 64;          // a lone large frame (1280x960: 5.4 k seeds): more regions in flight
     if (P->kn.async_w.set) aw = std::min(std::max(P->kn.async_w.v, 0), LA_MAXW);
     if (ctx->readings & HVO_READING_LSD_8U) aw = 0;             // (the async growing's fall-back forms a frame again with the default preamble)
+    // the fall-back of the split preamble forms the frames again from d_blur, which holds the last chunk only: with more frames than a
+    // chunk it could not (HVO_LSD_PRE_SPLIT=1 with HVO_LSD_CHUNK < n, an A/B layout), so such a batch is not grown async
+    if (!P->pre_fused && n > P->chunk) aw = 0;
     if (aw > 0 && n <= 1024 && !P->compact) {
         // scratch for (n frames, aw workers): owner tags and control block per frame; region list, held-pixel list and membership byte map per worker
         const size_t need_f = (size_t)n, need_w = (size_t)n * aw;
@@ -1857,7 +1861,7 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
                                    w, h, sw, sh, P->d_xofs, P->d_xa, P->d_yofs, P->d_yb, P->d_px, P->d_defined, P->nwords, P->rhoT, P->k7[0], P->k7[1], P->k7[2], P->k7[3], (const int *)P->d_flags);
             else
                 hipLaunchKernelGGL(k_lsd_resize_grad, dim3(gx, (sh + GRAD_ROWS - 1) / GRAD_ROWS, n), dim3(256), 0, st, P->d_blur, w, h, sw, sh, P->d_xofs, P->d_xa, P->d_yofs, P->d_yb,
-                                   P->d_px, P->d_defined, P->nwords, P->rho);      // (the split preamble: n <= 16 <= chunk, the blurred images are still there; every frame is formed again)
+                                   P->d_px, P->d_defined, P->nwords, P->rho);      // (the split preamble: n <= chunk, checked above, so the blurred images of all n frames are still in d_blur; every frame is formed again)
             { GrowArgs g2 = g; g2.redo = 1; g2.redo_count = P->d_redo; g2.perm = nullptr; hipLaunchKernelGGL(k_lsd_grow, dim3(n), dim3(64), 0, st, g2); }
         }
     } else aw = 0;

@@ -51,7 +51,7 @@ struct PeacPlan {
     double c15 = 0, c60 = 0, c30 = 0;   // cos thresholds evaluated on the host (glibc), like the oracle
     double ang_factor = 0, ang_near = 0;
     // tuning variables, read when the plan is built (peac_build_plan)
-    struct { Knob edges, gl, perm, lend, slots, heads_maxn, heads, heads_big, poolcap, ldsq, flood_t, flood_epl, flood_perm; } kn;
+    struct { Knob edges, gl, perm, lend, slots, heads_maxn, heads, heads_big, poolcap, ldsq, flood_t, flood_epl, flood_perm, flood_delay; } kn;
 };
 
 static PeacPlan *plan_of(hvo_ctx *ctx) { return (PeacPlan *)ctx->peac; }
@@ -1450,6 +1450,7 @@ struct RfArgs {
     float fx, fy, cx, cy, dfac;
     int *blkmap; int *isvalid; uint32_t *state; int *queue; int qcap; int *plidmap; const int *perm;
     hvo_plane *planes; double c30;
+    int flood_delay;          // HVO_FLOOD_DELAY (a test hook, 0 = off): wave 0 sleeps before it clears its hash slots in ranked rounds
 };
 
 // k_peac_flood: seeds + floodFill (AHCPlaneFitter.hpp:543-575, 428-476), FLOOD_T threads per frame.
@@ -1765,6 +1766,8 @@ __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long 
         lds_barrier();
         const int cxr = s_cx[par];
         const bool complex_round = (cxr & 2) != 0;
+        if (r.flood_delay && (cxr & 1) && wv == 0)     // test hook: widen the window between this wave's clear and the other waves' publish
+            for (int i = 0; i < r.flood_delay; i++) __builtin_amdgcn_s_sleep(127);
 #pragma unroll
         for (int p = 0; p < FLOOD_NP; p++) if (p < npass && ev[p]) { hkeys[hs[p]] = -1; hcnt[hs[p]] = 0; }   // leave the hash empty for the next round
         FT(2)
@@ -1789,6 +1792,9 @@ __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long 
 #ifdef HVO_PEAC_TIMING
                 ft[6]++;
 #endif
+                // the distances go into hkeys by compact event index: every wave must have cleared its hash slots first, or a late
+                // wave's clear overwrites a distance another wave has already published (cxr is uniform: every wave gets here)
+                if (NW > 1) lds_barrier();
 #pragma unroll
                 for (int p = 0; p < FLOOD_NP; p++) if (p < npass && multi[p]) hkeys[p * FLOOD_T + tid] = (int)(eok[p] ? __float_as_uint(ecd[p]) : 0xFFFFFFFFu);
                 lds_barrier();
@@ -2020,7 +2026,7 @@ static int peac_build_plan(hvo_ctx *ctx, int w, int h, int batch)
     ctx->peac = P;
     P->kn.edges.read("HVO_PEAC_EDGES"); P->kn.gl.read("HVO_PEAC_GL"); P->kn.perm.read("HVO_PEAC_PERM"); P->kn.lend.read("HVO_PEAC_LEND"); P->kn.slots.read("HVO_PEAC_SLOTS"); P->kn.heads_maxn.read("HVO_PEAC_HEADS_MAXN");
     P->kn.heads.read("HVO_PEAC_HEADS"); P->kn.heads_big.read("HVO_PEAC_HEADS_BIG"); P->kn.poolcap.read("HVO_PEAC_POOLCAP"); P->kn.ldsq.read("HVO_PEAC_LDSQ");
-    P->kn.flood_t.read("HVO_FLOOD_T"); P->kn.flood_epl.read("HVO_FLOOD_EPL"); P->kn.flood_perm.read("HVO_FLOOD_PERM");
+    P->kn.flood_t.read("HVO_FLOOD_T"); P->kn.flood_epl.read("HVO_FLOOD_EPL"); P->kn.flood_perm.read("HVO_FLOOD_PERM"); P->kn.flood_delay.read("HVO_FLOOD_DELAY");
     P->w = w; P->h = h; P->pitch = (w + 31) & ~31; P->Nw = w / WIN; P->Nh = h / WIN; P->nblk = P->Nw * P->Nh;
     P->segcap = 2 * P->nblk + 2 * MAX_PLANES; P->poolcap = 16 * P->nblk + 2 * MAX_PLANES * MAX_PLANES; P->qcap = 2 * w * h + 65536; P->batch = batch;
 #define HVO_DEG2RAD(d) ((d) * 3.14159265358979323846 / 180.0)      /* MACRO_DEG2RAD, AHCParamSet.hpp:33: (d)*M_PI/180.0, in that order */
@@ -2142,6 +2148,9 @@ int peac_run(hvo_ctx *ctx, int n)
         a.perm = hvo_frame_perm(ctx, (n + (64 / use) - 1) / (64 / use));
         if (P->kn.perm.off()) a.perm = nullptr;
         a.tq_lds_keys = 0;
+        // the slot form packs a label into a signed 16-bit half (peac_slots.inc); labels run up to segcap - 1 (nblk <= 16320: 1280x960 has
+        // 12 288 blocks).  Larger frames take ah_cluster_lend, as HVO_PEAC_SLOTS=0 does
+        const bool slots_fit = a.segcap <= 32768;
         // a handful of frames (the latency case): several queue heads per round, one wave each (peac_heads.inc); HVO_PEAC_HEADS = 0 / 2 / 3 / 4
         const int heads_max = P->kn.heads_maxn.or_(256);
         // three heads + the queue wave = one wave per SIMD of the frame's CU: 256 frames fill the chip exactly, and a lone frame loses nothing
@@ -2191,11 +2200,11 @@ int peac_run(hvo_ctx *ctx, int n)
         else if (use == 32) hipLaunchKernelGGL((k_peac_cluster<32, false>), dim3((n + 1) / 2), dim3(64), 2 * lq, st, a, n);
         else if (use == 16 && P->kn.poolcap.set && P->kn.poolcap.v >= 7 * a.nblk && P->kn.poolcap.v < a.poolcap) {   // tests: force the pool's compaction in the four-frames-per-wave kernels
             ClArgs b = a; b.poolcap = P->kn.poolcap.v;
-            if (!P->kn.slots.off() && !P->kn.lend.off() && a.nblk < 32768 && P->d_lq) hipLaunchKernelGGL(k_peac_cluster_slots, dim3((n + 3) / 4), dim3(64), 4 * lq, st, b, n);
+            if (!P->kn.slots.off() && !P->kn.lend.off() && slots_fit && P->d_lq) hipLaunchKernelGGL(k_peac_cluster_slots, dim3((n + 3) / 4), dim3(64), 4 * lq, st, b, n);
             else if (P->kn.lend.off()) hipLaunchKernelGGL((k_peac_cluster<16, false>), dim3((n + 3) / 4), dim3(64), 4 * lq, st, b, n);
             else hipLaunchKernelGGL((k_peac_cluster<16, true>), dim3((n + 3) / 4), dim3(64), 4 * lq, st, b, n);
         }
-        else if (!P->kn.slots.off() && !P->kn.lend.off() && a.nblk < 32768 && P->d_lq) hipLaunchKernelGGL(k_peac_cluster_slots, dim3((n + 3) / 4), dim3(64), 4 * lq, st, a, n);   // HVO_PEAC_SLOTS=0: a new record per merge
+        else if (!P->kn.slots.off() && !P->kn.lend.off() && slots_fit && P->d_lq) hipLaunchKernelGGL(k_peac_cluster_slots, dim3((n + 3) / 4), dim3(64), 4 * lq, st, a, n);   // HVO_PEAC_SLOTS=0: a new record per merge
         else if (P->kn.lend.off()) hipLaunchKernelGGL((k_peac_cluster<16, false>), dim3((n + 3) / 4), dim3(64), 4 * lq, st, a, n);
         else hipLaunchKernelGGL((k_peac_cluster<16, true>), dim3((n + 3) / 4), dim3(64), 4 * lq, st, a, n);   // HVO_PEAC_LEND=0: the lanes of a frame stay with it
     }
@@ -2208,6 +2217,7 @@ int peac_run(hvo_ctx *ctx, int n)
     r.fx = p.fx; r.fy = p.fy; r.cx = p.cx; r.cy = p.cy; r.dfac = p.depth_map_factor;
     r.blkmap = P->d_blkmap; r.isvalid = P->d_isvalid; r.state = P->d_state; r.queue = P->d_queue; r.perm = nullptr;
     r.qcap = P->qcap; r.plidmap = P->d_plidmap; r.planes = P->d_planes; r.c30 = P->c30;
+    r.flood_delay = std::min(std::max(P->kn.flood_delay.or_(0), 0), 64);     // HVO_FLOOD_DELAY: sleeps of 127 x 64 clocks per ranked round, at most 64
     {
         // threads per frame (one queue entry = 4 events per thread and round); HVO_FLOOD_T overrides
         const int flood_t = P->kn.flood_t.or_(-1);

@@ -10,8 +10,11 @@
 // deg(D) <= min(deg p, deg partner).
 //
 // Ids.  The reference orders by creation id in three places -- the candidate rule's ties, the queue's ties, and the ids k_peac_final sees --
-// so a slot carries the LABEL (creation id, nseg++) of the node that lives in it: in the upper half of HotNode::rid (rid < 2^16 blocks), and
-// as (label << 16 | slot) in the queue's id words, which therefore order by label exactly as before while naming the slot.  Extracted planes
+// so a slot carries the LABEL (creation id, nseg++) of the node that lives in it: in the upper half of HotNode::rid, and as (label << 16 | slot)
+// in the queue's id words, which therefore order by label exactly as before while naming the slot.  Both halves are read back as SIGNED
+// 16-bit numbers (rid >> 16): a label must stay below 2^15, or it turns negative, breaks the id order, collides with the -1 "no candidate"
+// sentinel and reaches ext[] as a segment id.  Labels run up to segcap - 1 = 2 * nblk + 127, so peac_run launches this form only while
+// segcap <= 32768 (nblk <= 16320; 1280x960 has 12 288 blocks) and gives larger frames to ah_cluster_lend.  Extracted planes
 // are written to segD / segI under their labels, as k_peac_final expects.  The queue loses an update per merge (D leaves, K gets the new
 // key and label: two slots instead of three ids) and half of its entries (slots < nblk).
 //

@@ -630,7 +630,7 @@ int hvo_stream_match_lines_geom(hvo_stream *s, int64_t cur, int64_t last, float 
     if (off > s->ms_bytes) { s->last_error = "matching scratch too small"; return HVO_ERR_CAPACITY; }
     if (last_has_mapline) { memcpy(hml, last_has_mapline, (size_t)n1); ST_HIP(hipMemcpyAsync(dml, hml, (size_t)n1, hipMemcpyHostToDevice, st)); }
     int rc = match_lines_geom_enqueue(st, A->lv.d_desc, A->lv.d_kl, last_has_mapline ? dml : nullptr, n1, B->lv.d_desc, B->lv.d_kl, n2, desc_th, s->bounds4(), scratch, dm, da);
-    if (rc) return rc;
+    if (rc) { s->last_error = "line matching launch"; return rc; }
     ST_HIP(hipMemcpyAsync(hm, dm, ((size_t)n1 + 1) * 4, hipMemcpyDeviceToHost, st));
     ST_HIP(hipMemcpyAsync(ha, da, (size_t)n1, hipMemcpyDeviceToHost, st));
     ST_HIP(hipStreamSynchronize(st));

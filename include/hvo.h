@@ -386,7 +386,10 @@ int hvo_batch_pack_results_ex(hvo_ctx *ctx, int n, void *d_slabs, unsigned flags
  * contiguous copy into `host_slabs`, n * slab_bytes of page-locked memory; hvo_batch_results_wait waits for it).  hvo_batch_commit_staged
  * waits for the staged upload and makes it the resident batch (a device-to-device copy: ~6 ms per 8192 frames).  One host thread:
  *     stage_upload(0); commit
- *     loop k:  stage_upload(k + 1);  hvo_batch_run;  results_async(k);  commit            -- run(k) overlaps upload(k + 1) and download(k - 1) */
+ *     loop k:  stage_upload(k + 1);  hvo_batch_run;  results_async(k);  commit            -- run(k) overlaps upload(k + 1) and download(k - 1)
+ * Staging never rebuilds the plans under a resident batch (that would blank its slabs before it runs): while one is resident, a staged
+ * batch must have its geometry, no more frames than the plans hold, and depth only if the plane plan exists (the resident batch had depth).
+ * Otherwise the call returns HVO_ERR_INVALID_ARG and hvo_last_error says so; hvo_batch_upload of the new geometry or size comes first. */
 int hvo_batch_stage_upload(hvo_ctx *ctx, int n, const hvo_frame_in *in, int w, int h);
 int hvo_batch_commit_staged(hvo_ctx *ctx);
 int hvo_batch_results_async(hvo_ctx *ctx, int n, unsigned flags, void *host_slabs);

@@ -75,6 +75,7 @@ def test_staged_upload_never_rebuilds_under_a_resident_batch(hvo, orc, synth):
             with pytest.raises(hvo.HvoError) as e:
                 ctx.batch_stage_upload(gg, dd)
             assert e.value.status == -1
+            assert "hvo_batch_upload" in str(e.value), str(e.value)          # the refusal says what to do
         ctx.batch_stage_upload(g[:2], d[:2])                       # fewer frames, same geometry: allowed, and batch 0 is untouched
         ctx.batch_run(hvo.STAGE_ORB | hvo.STAGE_PLANES)
         res = ctx.batch_download(hvo.STAGE_ALL)

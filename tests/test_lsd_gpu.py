@@ -95,6 +95,26 @@ def test_lines_preamble_fused_and_split(hvo, orc, synth, monkeypatch, split, hh,
         ctx.close()
 
 
+@pytest.mark.parametrize("hh,ww", [(480, 640), (397, 501)])
+def test_lines_lbd_split(hvo, orc, synth, monkeypatch, hh, ww):
+    """HVO_LBD_SPLIT=1: the two-kernel LBD formulation (k_lbd_blur5 writes the blurred u8 image, k_lbd_sobel reads it) that A/B runs
+    compare with the fused k_lbd_blur_sobel; a batch, an odd geometry, twice on the same context"""
+    monkeypatch.setenv("HVO_LBD_SPLIT", "1")
+    g = np.ascontiguousarray(np.stack([synth.make_gray(k, s)[:hh, :ww] for k, s in (("std", 0x5EED0002), ("lowtex", 0x5EED0001), ("std", 0x5EED1003))]))
+    ref = [orc.line_extract(g[b]) for b in range(3)]
+    ctx = hvo.Context(max_batch=3)
+    try:
+        ctx.batch_upload(g, np.zeros((3, hh, ww), np.uint16))
+        for _ in range(2):
+            ctx.batch_run(hvo.STAGE_LSD)
+            res = ctx.batch_download(hvo.STAGE_LSD)
+            for b in range(3):
+                assert res[b]["status"] == 0
+                check(res[b]["kl"], res[b]["ldesc"], res[b]["linefn"], *ref[b])
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("hh,ww", [(397, 501), (479, 638), (400, 642)])
 def test_lines_odd_geometry(hvo, orc, synth, hh, ww):
     """widths that are not a multiple of 4 (scalar tails of the LBD blur / Sobel strips, unaligned Sobel rows) and lines

@@ -152,6 +152,69 @@ def test_orb_chunked_batch(hvo, orc, synth, monkeypatch, fused, sched):
         ctx.close()
 
 
+ORB_PARAMS = [(1.5, 5, 20, 7, 1000), (2.0, 3, 12, 5, 500), (1.1, 8, 40, 20, 1500), (1.33, 8, 20, 7, 1000), (1.2, 1, 20, 7, 1000), (1.2, 8, 12, 5, 1500)]
+
+
+def test_orb_extractor_parameters(hvo, orc, synth, monkeypatch):
+    """ORBextractor(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST) under other parameters than the TUM yaml's: level geometry,
+    per-level quotas, cell grids and tile plans follow from them, and a scale factor above 4/3 takes the byte-load resize (k_resize, or
+    the fused pass's byte path).  Both ORB paths, a textured and a low-texture frame, against the oracle; which path each plan took is
+    recorded, and both must occur across the set (the fused pass may decline a pyramid: that is not asserted per setting)."""
+    frames = [synth.make_gray("std", 0x5EED5700), synth.make_gray("lowtex", 0x5EED5701)]
+    paths = set()
+    for sf, nl, ini, mn, nf in ORB_PARAMS:
+        o = orc.Orb(nfeatures=nf, scale_factor=sf, nlevels=nl, ini_th=ini, min_th=mn)
+        ref = [o.extract(g) for g in frames]
+        for fused in ("1", "0"):
+            monkeypatch.setenv("HVO_ORB_FUSED", fused)
+            ctx = hvo.Context(orb_nfeatures=nf, orb_scale_factor=sf, orb_nlevels=nl, orb_ini_th_fast=ini, orb_min_th_fast=mn)
+            try:
+                for g, (kp_o, d_o) in zip(frames, ref):
+                    kp_g, d_g = ctx.extract_orb(g)
+                    try:
+                        check_orb(kp_g, d_g, kp_o, d_o)
+                    except AssertionError as e:
+                        raise AssertionError("params %s, HVO_ORB_FUSED=%s: %s" % ((sf, nl, ini, mn, nf), fused, e)) from e
+                plan = _orb_plan(hvo, ctx)
+            finally:
+                ctx.close()
+            if fused == "0": assert plan[0] == 0, (sf, nl, plan)
+            paths.add(plan[0])
+    assert paths == {0, 1}, paths
+
+
+def test_orb_byte_load_resize_at_the_default_parameters(hvo, orc, synth, monkeypatch):
+    """HVO_RESIZE_BYTES=1 sends the default pyramid (scale factor 1.2) through the byte-load k_resize on the separate-kernel path"""
+    monkeypatch.setenv("HVO_RESIZE_BYTES", "1"); monkeypatch.setenv("HVO_ORB_FUSED", "0")
+    o = orc.Orb()
+    ctx = hvo.Context()
+    try:
+        for g in (synth.make_gray("std", 0x5EED5702), synth.make_gray("lowtex", 0x5EED5703)):
+            kp_g, d_g = ctx.extract_orb(g)
+            check_orb(kp_g, d_g, *o.extract(g))
+        assert _orb_plan(hvo, ctx)[0] == 0
+    finally:
+        ctx.close()
+
+
+def test_orb_degenerate_pyramid_is_rejected_again(hvo, orc, synth):
+    """scale factor 2 over 8 levels: the smallest level of a 640x480 image is 5 pixels wide, with no 30-pixel FAST cell between its borders
+    (a division by zero in the reference, src/ORBextractor.cc:782-785).  HVO_ERR_UNSUPPORTED, on the second call too, and the context
+    stays usable for the stages that do not need the pyramid"""
+    g, d = synth.make_frame("std", 0x5EED5704)
+    ctx = hvo.Context(orb_scale_factor=2.0, orb_nlevels=8)
+    try:
+        for _ in range(2):
+            with pytest.raises(hvo.HvoError) as e:
+                ctx.extract_orb(g)
+            assert e.value.status == -4
+        lg, pg = ctx.compute_planes(d)
+    finally:
+        ctx.close()
+    lo, po = orc.peac(d)
+    assert len(pg) == len(po) >= 1 and np.array_equal(lg, lo)
+
+
 def test_orb_flat_image_gives_nothing(gpu_ctx):
     kp, d = gpu_ctx.extract_orb(np.full((480, 640), 128, np.uint8))
     assert len(kp) == 0 and d.shape == (0, 32)

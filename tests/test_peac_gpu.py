@@ -316,6 +316,26 @@ def test_peac_queue_heads(hvo, orc, synth, monkeypatch, heads, poolcap, big):
     if heads == "2": assert 0 < stats["ahc_rounds"] < 0.75 * merges, stats
 
 
+@pytest.mark.parametrize("ldsq", ["0", "1"])
+def test_peac_one_frame_per_wave_queue_keys(hvo, orc, synth, monkeypatch, ldsq):
+    """k_peac_cluster<64, false>, the AHC of 257-3071 resident frames, forced onto six frames (HVO_PEAC_HEADS_MAXN=1 turns the queue heads
+    off beyond one frame): with the queue's keys in global memory (HVO_PEAC_LDSQ=0, the default from 257 frames on) and in LDS"""
+    monkeypatch.setenv("HVO_PEAC_HEADS_MAXN", "1"); monkeypatch.setenv("HVO_PEAC_LDSQ", ldsq)
+    depth = np.stack([synth.make_depth(0x5EED0002), synth.make_depth(0x5EED1003), corner_depth(3, 25, cu=323.0, cv=236.0),
+                      corner_depth(4, 60, cu=317.5, cv=243.5), polyhedron_depth(103), polyhedron_depth(111)])
+    ctx = hvo.Context(max_batch=len(depth))
+    try:
+        ctx.batch_upload(np.zeros((len(depth), 480, 640), np.uint8), depth)
+        ctx.batch_run(hvo.STAGE_PLANES)
+        res = ctx.batch_download(hvo.STAGE_PLANES)
+    finally:
+        ctx.close()
+    for b in range(len(depth)):
+        lo, po = orc.peac(depth[b])
+        assert res[b]["status"] == 0
+        check(res[b]["labels"], res[b]["planes"], lo, po)
+
+
 def test_peac_four_frames_per_wave_1280(hvo, orc, synth, monkeypatch):
     """the slot AHC at 1280x960 (12 288 blocks: initGraph's edges inside the kernel, 15-bit labels, a queue of 48 super-buckets), forced onto six frames"""
     monkeypatch.setenv("HVO_PEAC_GL", "16")
