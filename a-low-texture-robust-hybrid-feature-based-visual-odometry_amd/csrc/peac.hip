@@ -51,7 +51,7 @@ struct PeacPlan {
     double c15 = 0, c60 = 0, c30 = 0;   // cos thresholds evaluated on the host (glibc), like the oracle
     double ang_factor = 0, ang_near = 0;
     // tuning variables, read when the plan is built (peac_build_plan)
-    struct { Knob edges, gl, perm, lend, slots, heads_maxn, heads, heads_big, poolcap, ldsq, flood_t, flood_epl, flood_perm, flood_delay; } kn;
+    struct { Knob edges, gl, perm, lend, slots, heads_maxn, heads, heads_big, poolcap, ldsq, flood_t, flood_epl, flood_perm, flood_delay, flood_slim; } kn;
 };
 
 static PeacPlan *plan_of(hvo_ctx *ctx) { return (PeacPlan *)ctx->peac; }
@@ -1451,6 +1451,7 @@ struct RfArgs {
     int *blkmap; int *isvalid; uint32_t *state; int *queue; int qcap; int *plidmap; const int *perm;
     hvo_plane *planes; double c30;
     int flood_delay;          // HVO_FLOOD_DELAY (a test hook, 0 = off): wave 0 sleeps before it clears its hash slots in ranked rounds
+    int flood_lo;             // k_peac_flood leaves frames with at most this many coarse planes to the slim form launched beside it (-1: none)
 };
 
 // k_peac_flood: seeds + floodFill (AHCPlaneFitter.hpp:543-575, 428-476), FLOOD_T threads per frame.
@@ -1486,9 +1487,16 @@ static __device__ __forceinline__ void lds_barrier()
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
-template <int FLOOD_T, int EPL>
+#ifndef HVO_FLOOD_SLIM_WPE
+#define HVO_FLOOD_SLIM_WPE 6
+#endif
+template <int FLOOD_T, int EPL, int PMAX>
 #ifdef HVO_WPE_FLOOD
 __attribute__((amdgpu_waves_per_eu(HVO_WPE_FLOOD)))
+#else
+// the slim form fits six waves per SIMD as written (80 VGPRs, no scratch, no spills; 6160 B of LDS): the hint only makes the allocator
+// hold that band (without it: 84 VGPRs, five waves).  The MAX_PLANES forms keep the compiler's own choice (1 = no lower bound).
+__attribute__((amdgpu_waves_per_eu(PMAX < MAX_PLANES ? HVO_FLOOD_SLIM_WPE : 1)))
 #endif
 __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long long *__restrict__ adj_out)
 {
@@ -1503,8 +1511,11 @@ __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long 
     // dependent instructions per wave: ~1000 of every kind per round at ~1.8 ns each, profiles/r05_valu_salu_issue.txt; frames in flight are its throughput)
     constexpr bool HL8 = NEV <= 256;
     typedef typename std::conditional<HL8, unsigned char, typename std::conditional<(NEV > 1024), unsigned int, unsigned short>::type>::type hl_t;
-    __shared__ double pl[MAX_PLANES][7];          // center[3], normal[3], mse
-    __shared__ unsigned long long adj[MAX_PLANES], simok[MAX_PLANES];
+    // PMAX: coarse planes the frame may have (16 or MAX_PLANES; a frame with more is left to the MAX_PLANES form); plane bit sets in the narrowest word
+    static_assert(PMAX == 16 || PMAX == MAX_PLANES, "plane table sizes");
+    typedef typename std::conditional<(PMAX <= 32), unsigned, unsigned long long>::type pm_t;
+    __shared__ double pl[PMAX][7];                // center[3], normal[3], mse
+    __shared__ pm_t adj[PMAX], simok[PMAX];
     __shared__ int hkeys[FLOOD_HS], hcnt[FLOOD_HS];       // (a ranked round borrows both, by compact event index, once they are empty again: distances and push flags)
     __shared__ __attribute__((aligned(16))) hl_t hlist[FLOOD_HS * FLOOD_HL];
     __shared__ uint2 rec[NEV];                    // the round's live events in event order: packed (plane, y, x) of the target pixel, its state word
@@ -1516,6 +1527,8 @@ __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long 
     const int w = r.w, h = r.h, Nw = a.Nw, nblk = a.nblk;
     int *meta = a.meta + (size_t)frame * 16;
     const int nold = meta[2];
+    // the frame is another launch's: more planes than this form holds, or few enough for the slim form that runs beside this one
+    if (nold > PMAX || nold <= r.flood_lo) return;
     const int *ext = a.extracted + (size_t)frame * 2 * MAX_PLANES;
     const double *segD = a.segD + (size_t)frame * a.segcap * SEG_D;
     const int *blkmap = r.blkmap + (size_t)frame * nblk;
@@ -1523,7 +1536,7 @@ __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long 
     const int stw = FS_TW(w);
     int *queue = r.queue + (size_t)frame * r.qcap;
     int flags = 0;
-    if (tid < MAX_PLANES) {
+    if (tid < PMAX) {
         adj[tid] = 0;
         if (tid < nold) { const double *sd = segD + (size_t)ext[tid] * SEG_D; for (int k = 0; k < 7; k++) pl[tid][k] = sd[9 + k]; }
     }
@@ -1532,11 +1545,11 @@ __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long 
     __syncthreads();
     // which pairs of planes count as adjacent when they meet on a pixel (|n_p . n_q| >= cos 30 deg,
     // AHCPlaneFitter.hpp:457-462): evaluated once per pair instead of once per contested event
-    if (tid < MAX_PLANES) {
-        unsigned long long m = 0;
+    if (tid < PMAX) {
+        pm_t m = 0;
         if (tid < nold) for (int q = 0; q < nold; q++) {
             const double *P = pl[tid], *Q = pl[q];
-            if (fabs(P[3] * Q[3] + P[4] * Q[4] + P[5] * Q[5]) >= r.c30) m |= 1ull << q;
+            if (fabs(P[3] * Q[3] + P[4] * Q[4] + P[5] * Q[5]) >= r.c30) m |= (pm_t)1 << q;
         }
         simok[tid] = m;
     }
@@ -1708,58 +1721,64 @@ __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long 
 #endif
         FT(1)
         // ---- live events, FLOOD_T at a time: distance, then group by pixel ----
-        unsigned eq[FLOOD_NP], es[FLOOD_NP]; float ed[FLOOD_NP], ecd[FLOOD_NP]; bool eok[FLOOD_NP], ev[FLOOD_NP], push[FLOOD_NP]; int hs[FLOOD_NP], eix[FLOOD_NP];
+        // what a pass keeps across the round's barriers is one word: hash slot, group size, flags -- among them the outcome of the
+        // distance test (ok, and ok && cdist < odist, which is all a one-plane group needs).  The event's queue entry and state word stay
+        // in rec[] until the round ends and are read back where they are needed, its state index is recomputed from the entry, and the
+        // events of a ranked group (1.6 % of the rounds) recompute their distances.  (Seven values per pass before, over four unrolled
+        // passes: 118 VGPRs, four waves per SIMD.)
+        constexpr unsigned W_EV = 1u << 16, W_OK = 1u << 17, W_FIRST = 1u << 18, W_MULTI = 1u << 19, W_PUSH = 1u << 20, W_CLOSER = 1u << 21;
+        static_assert(FLOOD_HS <= 4096 && FLOOD_HL < 8, "pass word: 12 bits of hash slot, 3 of group size");
+        unsigned pw[FLOOD_NP];
 #pragma unroll
         for (int p = 0; p < FLOOD_NP; p++) {
-            ev[p] = false; push[p] = false; eq[p] = 0; es[p] = 0; ed[p] = 0; ecd[p] = -1; eok[p] = false; hs[p] = 0; eix[p] = 0;
-            if (p < npass) {
-                const int c = p * FLOOD_T + tid;
-                ev[p] = c < na;
-                if (ev[p]) {
-                    const uint2 R = rec[c];
-                    eq[p] = R.x; es[p] = R.y;
-                    const int ep = (int)(R.x >> 26), ex_ = (int)(R.x & 8191u), ey = (int)((R.x >> 13) & 8191u);
-                    eix[p] = FS_IDX(ex_, ey, stw);
-                    geom(pl[ep], ex_, ey, (int)(R.y >> 16), FS_LABEL(R.y), ecd[p], eok[p], ed[p]);
-                    int s = (int)(((unsigned)eix[p] * 2654435761u) >> 19) & (FLOOD_HS - 1);
-                    for (;;) {
-                        const int old = atomicCAS(&hkeys[s], -1, eix[p]);
-                        if (old == -1 || old == eix[p]) break;
-                        s = (s + 1) & (FLOOD_HS - 1);
-                    }
-                    const int pos = atomicAdd(&hcnt[s], 1);
-                    if (pos < FLOOD_HL) hlist[s * FLOOD_HL + pos] = HL8 ? (hl_t)c : (hl_t)((ep << IXB) | c);
-                    hs[p] = s;
+            pw[p] = 0;
+            const int c = p * FLOOD_T + tid;
+            if (p < npass && c < na) {
+                const uint2 R = rec[c];
+                const int ep = (int)(R.x >> 26), ex_ = (int)(R.x & 8191u), ey = (int)((R.x >> 13) & 8191u);
+                const int eix = FS_IDX(ex_, ey, stw);
+                float cd, od; bool ok;
+                geom(pl[ep], ex_, ey, (int)(R.y >> 16), FS_LABEL(R.y), cd, ok, od);
+                int s = (int)(((unsigned)eix * 2654435761u) >> 19) & (FLOOD_HS - 1);
+                for (;;) {
+                    const int old = atomicCAS(&hkeys[s], -1, eix);
+                    if (old == -1 || old == eix) break;
+                    s = (s + 1) & (FLOOD_HS - 1);
                 }
+                const int pos = atomicAdd(&hcnt[s], 1);
+                if (pos < FLOOD_HL) hlist[s * FLOOD_HL + pos] = HL8 ? (hl_t)c : (hl_t)((ep << IXB) | c);
+                pw[p] = W_EV | (ok ? W_OK : 0u) | (ok && cd < od ? W_CLOSER : 0u) | (unsigned)s;
             }
         }
         lds_barrier();
         // ---- first event of every pixel group, group size; groups that have no closed form flag the round ----
-        bool first[FLOOD_NP], multi[FLOOD_NP]; int cnt[FLOOD_NP]; int cx = 0;
+        int cx = 0;
 #pragma unroll
         for (int p = 0; p < FLOOD_NP; p++) {
-            first[p] = false; multi[p] = false; cnt[p] = 1;
-            if (p < npass && ev[p]) {
-                cnt[p] = hcnt[hs[p]];
-                first[p] = true;
-                if (cnt[p] > FLOOD_HL) cx |= 2;
-                else if (cnt[p] > 1) {
-                    const unsigned me = ((eq[p] >> 26) << IXB) | (unsigned)(p * FLOOD_T + tid);
-                    const hl_t *hp_ = &hlist[hs[p] * FLOOD_HL];
+            if (p < npass && (pw[p] & W_EV)) {
+                const int c = p * FLOOD_T + tid, cnt = hcnt[pw[p] & 4095u];
+                bool first = true, multi = false;
+                if (cnt > FLOOD_HL) cx |= 2;
+                else if (cnt > 1) {
+                    const uint2 R = rec[c];
+                    const unsigned me = ((R.x >> 26) << IXB) | (unsigned)c;
+                    const hl_t *hp_ = &hlist[(pw[p] & 4095u) * FLOOD_HL];
                     unsigned l[4] = { hp_[0], hp_[1], hp_[2], hp_[3] };
                     if (HL8) {
 #pragma unroll
-                        for (int t = 0; t < 4; t++) if (t < cnt[p]) l[t] |= (rec[l[t]].x >> 26) << IXB;
+                        for (int t = 0; t < 4; t++) if (t < cnt) l[t] |= (rec[l[t]].x >> 26) << IXB;
                     }
 #pragma unroll
-                    for (int t = 0; t < 4; t++) if (t < cnt[p]) {
-                        if ((l[t] ^ me) >> IXB) multi[p] = true;                   // another plane on the same pixel
-                        if ((l[t] & IXM) < (me & IXM)) first[p] = false;           // compact index == event order
+                    for (int t = 0; t < 4; t++) if (t < cnt) {
+                        if ((l[t] ^ me) >> IXB) multi = true;                      // another plane on the same pixel
+                        if ((l[t] & IXM) < (me & IXM)) first = false;              // compact index == event order
                     }
                     // two planes racing for an unlabelled pixel: ranked replay by the group's first event (below);
                     // on a labelled pixel the passive events of a third plane could matter: serial replay of the round
-                    if (multi[p]) cx |= FS_LABEL(es[p]) < 0 ? 1 : 2;
+                    if (multi) cx |= FS_LABEL(R.y) < 0 ? 1 : 2;
                 }
+                // the group size is read back only where the round has a closed form (cnt <= FLOOD_HL)
+                pw[p] |= ((unsigned)min(cnt, 7) << 12) | (first ? W_FIRST : 0u) | (multi ? W_MULTI : 0u);
             }
         }
         if (cx) atomicOr(&s_cx[par], cx);
@@ -1769,20 +1788,21 @@ __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long 
         if (r.flood_delay && (cxr & 1) && wv == 0)     // test hook: widen the window between this wave's clear and the other waves' publish
             for (int i = 0; i < r.flood_delay; i++) __builtin_amdgcn_s_sleep(127);
 #pragma unroll
-        for (int p = 0; p < FLOOD_NP; p++) if (p < npass && ev[p]) { hkeys[hs[p]] = -1; hcnt[hs[p]] = 0; }   // leave the hash empty for the next round
+        for (int p = 0; p < FLOOD_NP; p++) if (p < npass && (pw[p] & W_EV)) { hkeys[pw[p] & 4095u] = -1; hcnt[pw[p] & 4095u] = 0; }   // leave the hash empty for the next round
         FT(2)
         int total = 0;
         if (!complex_round) {
             // ---- closed form of a one-plane group, applied by its first event (AHCPlaneFitter.hpp:445-470) ----
 #pragma unroll
             for (int p = 0; p < FLOOD_NP; p++) {
-                if (p < npass && first[p] && !multi[p]) {
-                    const int ep = (int)(eq[p] >> 26), trail = FS_LABEL(es[p]);
-                    const bool closer = eok[p] && ecd[p] < ed[p];
-                    if (eok[p] && trail >= 0 && ((simok[ep] >> trail) & 1ull)) { atomicOr(&adj[trail], 1ull << ep); atomicOr(&adj[ep], 1ull << trail); }
-                    const int nl = closer ? ep : (trail < 0 ? max(trail - cnt[p], -6) : trail);
-                    push[p] = closer;
-                    if (nl != trail) state[eix[p]] = (es[p] & ~0xFFu) | ((unsigned)nl & 0xFFu);          // (closer: nl = ep != trail)
+                if (p < npass && (pw[p] & (W_FIRST | W_MULTI)) == W_FIRST) {
+                    const uint2 R = rec[p * FLOOD_T + tid];
+                    const int ep = (int)(R.x >> 26), trail = FS_LABEL(R.y), cnt = (int)((pw[p] >> 12) & 7u);
+                    const bool ok = (pw[p] & W_OK) != 0, closer = (pw[p] & W_CLOSER) != 0;
+                    if (ok && trail >= 0 && ((simok[ep] >> trail) & 1u)) { atomicOr(&adj[trail], (pm_t)1 << ep); atomicOr(&adj[ep], (pm_t)1 << trail); }
+                    const int nl = closer ? ep : (trail < 0 ? max(trail - cnt, -6) : trail);
+                    if (closer) pw[p] |= W_PUSH;
+                    if (nl != trail) state[FS_IDX((int)(R.x & 8191u), (int)((R.x >> 13) & 8191u), stw)] = (R.y & ~0xFFu) | ((unsigned)nl & 0xFFu);   // (closer: nl = ep != trail)
                 }
             }
             if (cxr & 1) {
@@ -1796,45 +1816,54 @@ __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long 
                 // wave's clear overwrites a distance another wave has already published (cxr is uniform: every wave gets here)
                 if (NW > 1) lds_barrier();
 #pragma unroll
-                for (int p = 0; p < FLOOD_NP; p++) if (p < npass && multi[p]) hkeys[p * FLOOD_T + tid] = (int)(eok[p] ? __float_as_uint(ecd[p]) : 0xFFFFFFFFu);
+                for (int p = 0; p < FLOOD_NP; p++) if (p < npass && (pw[p] & W_MULTI)) {
+                    const uint2 R = rec[p * FLOOD_T + tid];
+                    float cd, od; bool ok;
+                    geom(pl[R.x >> 26], (int)(R.x & 8191u), (int)((R.x >> 13) & 8191u), (int)(R.y >> 16), FS_LABEL(R.y), cd, ok, od);
+                    hkeys[p * FLOOD_T + tid] = (int)(ok ? __float_as_uint(cd) : 0xFFFFFFFFu);
+                }
                 lds_barrier();
 #pragma unroll
                 for (int p = 0; p < FLOOD_NP; p++) {
-                    if (p < npass && first[p] && multi[p]) {
-                        const hl_t *hp_ = &hlist[hs[p] * FLOOD_HL];
+                    if (p < npass && (pw[p] & (W_FIRST | W_MULTI)) == (W_FIRST | W_MULTI)) {
+                        const int cnt = (int)((pw[p] >> 12) & 7u);
+                        const hl_t *hp_ = &hlist[(pw[p] & 4095u) * FLOOD_HL];
                         unsigned l[4] = { hp_[0], hp_[1], hp_[2], hp_[3] };
                         if (HL8) {
 #pragma unroll
-                            for (int t = 0; t < 4; t++) if (t < cnt[p]) l[t] |= (rec[l[t]].x >> 26) << IXB;
+                            for (int t = 0; t < 4; t++) if (t < cnt) l[t] |= (rec[l[t]].x >> 26) << IXB;
                         }
-                        int trail = FS_LABEL(es[p]); float dist = ed[p];
+                        const uint2 R = rec[p * FLOOD_T + tid];
+                        float dist, cd0; bool ok0;
+                        geom(pl[R.x >> 26], (int)(R.x & 8191u), (int)((R.x >> 13) & 8191u), (int)(R.y >> 16), FS_LABEL(R.y), cd0, ok0, dist);
+                        int trail = FS_LABEL(R.y);
                         int last = -1;
-                        for (int it = 0; it < cnt[p]; it++) {
+                        for (int it = 0; it < cnt; it++) {
                             unsigned best = 0; int c = 1 << 20;                     // next event of the group in event order
 #pragma unroll
-                            for (int t = 0; t < 4; t++) { const int ct = (int)(l[t] & IXM); if (t < cnt[p] && ct > last && ct < c) { c = ct; best = l[t]; } }
+                            for (int t = 0; t < 4; t++) { const int ct = (int)(l[t] & IXM); if (t < cnt && ct > last && ct < c) { c = ct; best = l[t]; } }
                             const int ep = (int)(best >> IXB);
                             last = c;
                             const unsigned okcd = (unsigned)hkeys[c];
                             const bool ok = okcd != 0xFFFFFFFFu; const float cd = __uint_as_float(okcd);
                             const bool live = !(trail <= -6 || trail == ep);
                             const bool closer = live && ok && cd < dist;
-                            if (live && ok && trail >= 0 && ((simok[ep] >> trail) & 1ull)) { atomicOr(&adj[trail], 1ull << ep); atomicOr(&adj[ep], 1ull << trail); }
+                            if (live && ok && trail >= 0 && ((simok[ep] >> trail) & 1u)) { atomicOr(&adj[trail], (pm_t)1 << ep); atomicOr(&adj[ep], (pm_t)1 << trail); }
                             trail = closer ? ep : ((live && trail < 0) ? trail - 1 : trail);
                             dist = closer ? cd : dist;
                             hcnt[c] = closer ? 1 : 0;
                         }
-                        state[eix[p]] = (es[p] & ~0xFFu) | ((unsigned)trail & 0xFFu);
+                        state[FS_IDX((int)(R.x & 8191u), (int)((R.x >> 13) & 8191u), stw)] = (R.y & ~0xFFu) | ((unsigned)trail & 0xFFu);
                     }
                 }
                 lds_barrier();
 #pragma unroll
-                for (int p = 0; p < FLOOD_NP; p++) if (p < npass && multi[p]) { push[p] = hcnt[p * FLOOD_T + tid] != 0; hkeys[p * FLOOD_T + tid] = -1; hcnt[p * FLOOD_T + tid] = 0; }     // (the table is empty again)
+                for (int p = 0; p < FLOOD_NP; p++) if (p < npass && (pw[p] & W_MULTI)) { if (hcnt[p * FLOOD_T + tid] != 0) pw[p] |= W_PUSH; hkeys[p * FLOOD_T + tid] = -1; hcnt[p * FLOOD_T + tid] = 0; }     // (the table is empty again)
             }
             // ---- ordered append: exclusive scan of the pushes in compact (= event) order ----
             unsigned long long bm[FLOOD_NP]; int off[FLOOD_NP];
 #pragma unroll
-            for (int p = 0; p < FLOOD_NP; p++) { bm[p] = 0; if (p < npass) bm[p] = __ballot(push[p]); }
+            for (int p = 0; p < FLOOD_NP; p++) { bm[p] = 0; if (p < npass) bm[p] = __ballot((pw[p] & W_PUSH) != 0); }
             if (NW > 1) {
                 if (lane == 0) for (int p = 0; p < FLOOD_NP; p++) psum[p * NW + wv] = __popcll(bm[p]);
                 lds_barrier();
@@ -1848,9 +1877,9 @@ __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long 
                 for (int p = 0; p < FLOOD_NP; p++) { off[p] = total; total += __popcll(bm[p]); }
             }
 #pragma unroll
-            for (int p = 0; p < FLOOD_NP; p++) if (p < npass && push[p]) {
+            for (int p = 0; p < FLOOD_NP; p++) if (p < npass && (pw[p] & W_PUSH)) {
                 const int pos = nq + off[p] + __popcll(bm[p] & ltm);
-                if (pos < r.qcap) queue[pos] = (int)eq[p];
+                if (pos < r.qcap) queue[pos] = (int)rec[p * FLOOD_T + tid].x;
             }
         } else {
             // ---- complex round: replay its entries in queue order on one thread (the reference loop) ----
@@ -1873,7 +1902,7 @@ __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long 
                         float cd; bool ok;
                         geom(pl[ep], x, y, (int)(s >> 16), trail, cd, ok, dist);
                         if (ok) {
-                            if (trail >= 0 && ((simok[ep] >> trail) & 1ull)) { atomicOr(&adj[trail], 1ull << ep); atomicOr(&adj[ep], 1ull << trail); }
+                            if (trail >= 0 && ((simok[ep] >> trail) & 1u)) { atomicOr(&adj[trail], (pm_t)1 << ep); atomicOr(&adj[ep], (pm_t)1 << trail); }
                             if (cd < dist) { trail = ep; dist = cd; if (nqs < r.qcap) queue[nqs] = FQ_PACK(x, y, ep); nqs++; }
                             else if (trail < 0) trail -= 1;
                         } else if (trail < 0) trail -= 1;
@@ -1895,7 +1924,7 @@ __global__ __launch_bounds__(FLOOD_T) void k_peac_flood(RfArgs r, unsigned long 
 #ifdef HVO_PEAC_TIMING
     if (tid == 0) { for (int q = 0; q < 6; q++) atomicAdd(&g_peac_t[16 + q], ft[q]); for (int q = 6; q < 12; q++) atomicAdd(&g_peac_t[18 + q], ft[q]); atomicAdd(&g_peac_t[22], (unsigned long long)nq); atomicAdd(&g_peac_t[23], 1ull); }
 #endif
-    if (tid < MAX_PLANES) adj_out[(size_t)frame * MAX_PLANES + tid] = adj[tid];
+    for (int i = tid; i < MAX_PLANES; i += FLOOD_T) adj_out[(size_t)frame * MAX_PLANES + i] = i < PMAX ? (unsigned long long)adj[i] : 0ull;   // k_peac_final reads all MAX_PLANES
     if (tid == 0) { meta[5] = nq; meta[7] = flags; meta[8] = n_rounds; meta[9] = n_ranked; meta[10] = n_serial; }
 }
 
@@ -2026,7 +2055,7 @@ static int peac_build_plan(hvo_ctx *ctx, int w, int h, int batch)
     ctx->peac = P;
     P->kn.edges.read("HVO_PEAC_EDGES"); P->kn.gl.read("HVO_PEAC_GL"); P->kn.perm.read("HVO_PEAC_PERM"); P->kn.lend.read("HVO_PEAC_LEND"); P->kn.slots.read("HVO_PEAC_SLOTS"); P->kn.heads_maxn.read("HVO_PEAC_HEADS_MAXN");
     P->kn.heads.read("HVO_PEAC_HEADS"); P->kn.heads_big.read("HVO_PEAC_HEADS_BIG"); P->kn.poolcap.read("HVO_PEAC_POOLCAP"); P->kn.ldsq.read("HVO_PEAC_LDSQ");
-    P->kn.flood_t.read("HVO_FLOOD_T"); P->kn.flood_epl.read("HVO_FLOOD_EPL"); P->kn.flood_perm.read("HVO_FLOOD_PERM"); P->kn.flood_delay.read("HVO_FLOOD_DELAY");
+    P->kn.flood_t.read("HVO_FLOOD_T"); P->kn.flood_epl.read("HVO_FLOOD_EPL"); P->kn.flood_perm.read("HVO_FLOOD_PERM"); P->kn.flood_delay.read("HVO_FLOOD_DELAY"); P->kn.flood_slim.read("HVO_FLOOD_SLIM");
     P->w = w; P->h = h; P->pitch = (w + 31) & ~31; P->Nw = w / WIN; P->Nh = h / WIN; P->nblk = P->Nw * P->Nh;
     P->segcap = 2 * P->nblk + 2 * MAX_PLANES; P->poolcap = 16 * P->nblk + 2 * MAX_PLANES * MAX_PLANES; P->qcap = 2 * w * h + 65536; P->batch = batch;
 #define HVO_DEG2RAD(d) ((d) * 3.14159265358979323846 / 180.0)      /* MACRO_DEG2RAD, AHCParamSet.hpp:33: (d)*M_PI/180.0, in that order */
@@ -2228,11 +2257,19 @@ int peac_run(hvo_ctx *ctx, int n)
         r.perm = hvo_frame_perm(ctx, n);                   // one wave per frame for its whole life: frames of a SIMD decorrelated
         if ((ctx->sched == 5 || ctx->sched == 7) && ctx->fast_recorded && !ctx->serialize) HVO_HIP(hipStreamWaitEvent(st, ctx->ev_fast, 0));      // experiment: the flood takes all LDS, k_fast_cells needs some
         if (P->kn.flood_perm.off()) r.perm = nullptr;
-        if (ft == 64 && fe == 2) hipLaunchKernelGGL((k_peac_flood<64, 2>), dim3(n), dim3(64), 0, st, r, P->d_adj);
-        else if (ft == 64) hipLaunchKernelGGL((k_peac_flood<64, 1>), dim3(n), dim3(64), 0, st, r, P->d_adj);
-        else if (ft == 512) hipLaunchKernelGGL((k_peac_flood<512, 1>), dim3(n), dim3(512), 0, st, r, P->d_adj);
-        else if (ft == 256) hipLaunchKernelGGL((k_peac_flood<256, 1>), dim3(n), dim3(256), 0, st, r, P->d_adj);
-        else hipLaunchKernelGGL((k_peac_flood<128, 1>), dim3(n), dim3(128), 0, st, r, P->d_adj);
+        // the one-wave form in two launches on the stream: frames with at most 16 coarse planes (nearly all) take the slim plane table and
+        // fit five waves per SIMD, the rest the MAX_PLANES form; a frame that is not a launch's own costs an empty workgroup.
+        // HVO_FLOOD_SLIM=0: the MAX_PLANES form takes every frame
+        r.flood_lo = -1;
+        if (ft == 64 && fe != 2 && !P->kn.flood_slim.off()) {
+            hipLaunchKernelGGL((k_peac_flood<64, 1, 16>), dim3(n), dim3(64), 0, st, r, P->d_adj);
+            r.flood_lo = 16;
+        }
+        if (ft == 64 && fe == 2) hipLaunchKernelGGL((k_peac_flood<64, 2, MAX_PLANES>), dim3(n), dim3(64), 0, st, r, P->d_adj);
+        else if (ft == 64) hipLaunchKernelGGL((k_peac_flood<64, 1, MAX_PLANES>), dim3(n), dim3(64), 0, st, r, P->d_adj);
+        else if (ft == 512) hipLaunchKernelGGL((k_peac_flood<512, 1, MAX_PLANES>), dim3(n), dim3(512), 0, st, r, P->d_adj);
+        else if (ft == 256) hipLaunchKernelGGL((k_peac_flood<256, 1, MAX_PLANES>), dim3(n), dim3(256), 0, st, r, P->d_adj);
+        else hipLaunchKernelGGL((k_peac_flood<128, 1, MAX_PLANES>), dim3(n), dim3(128), 0, st, r, P->d_adj);
     }
     hipLaunchKernelGGL(k_peac_final, dim3(n), dim3(64), 0, st, r, P->d_adj);
     hipLaunchKernelGGL(k_peac_relabel, dim3(64, n), dim3(256), 0, st, P->d_state, P->d_labels, P->d_plidmap, P->w, P->h, ((size_t)P->w * P->h + 3) & ~(size_t)3);
