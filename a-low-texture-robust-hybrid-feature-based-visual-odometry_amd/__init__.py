@@ -74,6 +74,7 @@ EXPORTS = [
     "hvo_stream_submit", "hvo_stream_poll", "hvo_stream_collect", "hvo_stream_stage_ms",
     "hvo_stream_search_by_projection", "hvo_stream_match_lines", "hvo_stream_project_last", "hvo_search_by_projection_tracked",
     "hvo_tail_capacity", "hvo_set_tail_params", "hvo_batch_download_tail", "hvo_stream_collect_tail", "hvo_normals_lpvo",
+    "hvo_track_manhattan", "hvo_stream_track_manhattan", "hvo_batch_track_manhattan",
 ]
 
 
@@ -116,6 +117,31 @@ class FrameTail(C.Structure):
                 ("pt_cell_start", C.c_void_p), ("pt_cell_items", C.c_void_p), ("pt_items_cap", C.c_int), ("n_pt_items", C.c_int),
                 ("ln_cell_start", C.c_void_p), ("ln_cell_items", C.c_void_p), ("ln_items_cap", C.c_int), ("n_ln_items", C.c_int),
                 ("status", C.c_int)]
+
+
+class MfResult(C.Structure):
+    """hvo_mf_result: one Tracking::TrackManhattanFrame call (R row-major)"""
+    _fields_ = [("R", C.c_float * 9), ("axis_vec", (C.c_float * 3) * 3), ("density", C.c_float * 3),
+                ("found", C.c_int32 * 3), ("n_found", C.c_int32), ("n_in_cone", C.c_int32 * 3), ("n_selected", C.c_int32 * 3),
+                ("min_num_sn", C.c_int32), ("tracked", C.c_int32), ("status", C.c_int32)]
+
+    def to_dict(self):
+        return dict(R=np.array(self.R[:], np.float32).reshape(3, 3), axis_vec=np.array([r[:] for r in self.axis_vec], np.float32),
+                    density=np.array(self.density[:], np.float32), found=list(self.found), n_found=self.n_found, n_in_cone=list(self.n_in_cone),
+                    n_selected=list(self.n_selected), min_num_sn=self.min_num_sn, tracked=self.tracked, status=self.status)
+
+
+assert C.sizeof(MfResult) == 21 * 4 + 13 * 4
+
+
+def _normals_arg(normals):
+    """SURFACE_NORMAL_DT array, or (N, 3) floats taken as the normals"""
+    a = np.asarray(normals)
+    if a.dtype == SURFACE_NORMAL_DT:
+        return np.ascontiguousarray(a).reshape(-1)
+    a = np.asarray(a, np.float32).reshape(-1, 3)
+    out = np.zeros(len(a), SURFACE_NORMAL_DT); out["normal"] = a
+    return out
 
 
 def _tail_buffers(kp_cap, kl_cap, w, h):
@@ -198,6 +224,9 @@ def lib():
         L.hvo_search_lines_by_projection.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_stream_match_lines_geom.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.hvo_stream_search_lines_by_projection.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.hvo_track_manhattan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MfResult), C.c_void_p, C.c_void_p]
+        L.hvo_stream_track_manhattan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MfResult), C.c_void_p, C.c_void_p]
+        L.hvo_batch_track_manhattan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.hvo_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_stream_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_search_by_projection_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
@@ -476,6 +505,28 @@ class Context:
                                                            pp(t_l3d), pp(t_desc), pp(keep[1]), nt, _p(cs), _p(ci), _p(b), th, nn_ratio, _p(mi), _p(md), C.byref(n)),
                   "search_lines_by_projection_map")
         return n.value, mi[:nq], md[:nq]
+
+    def track_manhattan(self, normals, l3d, R_last, axes=False):
+        """Tracking::TrackManhattanFrame(R_last, vSurfaceNormal, mVF3DLines) (src/Tracking.cc:1172-1348) -> MfResult, or (MfResult,
+        normal_axes, line_axes) with axes=True.  normals: SURFACE_NORMAL_DT or (N, 3) floats; l3d: LINE3D_DT of every key line (None: no
+        lines); R_last: 3 x 3 (R_cm of the last frame)."""
+        sn = _normals_arg(normals)
+        l3d = np.zeros(0, LINE3D_DT) if l3d is None else np.ascontiguousarray(l3d, LINE3D_DT).reshape(-1)
+        R = np.ascontiguousarray(R_last, np.float32).reshape(9)
+        res = MfResult()
+        na = np.zeros(max(len(sn), 1), np.uint8); la = np.zeros(max(len(l3d), 1), np.uint8)
+        self._chk(lib().hvo_track_manhattan(self.h, _p(sn) if len(sn) else None, len(sn), _p(l3d) if len(l3d) else None, len(l3d), _p(R), C.byref(res),
+                                            _p(na) if axes else None, _p(la) if axes else None), "track_manhattan")
+        return (res, na[:len(sn)], la[:len(l3d)]) if axes else res
+
+    def batch_track_manhattan(self, R0, n=None):
+        """the first n (default all) frames of the resident batch as a sequence, frame k from frame k-1's R (needs STAGE_PLANE_TAIL |
+        STAGE_LINES3D in the last batch_run) -> list of MfResult"""
+        n = self._B if n is None else n
+        R = np.ascontiguousarray(R0, np.float32).reshape(9)
+        res = (MfResult * n)()
+        self._chk(lib().hvo_batch_track_manhattan(self.h, n, _p(R), res), "batch_track_manhattan")
+        return list(res)
 
     def set_readings(self, blur_float=False, lsd_8u=False):
         """the alternative readings of cv::GaussianBlur / cv::LineSegmentDetector (include/hvo.h HVO_READING_*); the next extraction uses them"""
@@ -922,6 +973,17 @@ class Stream:
         self._chk(lib().hvo_stream_search_lines_by_projection_map(self.h, cur, nq, pp(q_xyxy), pp(q_view_cos), pp(q_wvec), pp(q_desc), pp(keep[0]), pp(keep[1]),
                                                                   th, nn_ratio, _p(mi), _p(md), C.byref(n)), "stream_search_lines_by_projection_map")
         return n.value, mi[:nq], md[:nq]
+
+    def track_manhattan(self, cur, R_last, axes=False):
+        """Tracking::TrackManhattanFrame on the resident frame `cur` (needs STAGE_PLANE_TAIL | STAGE_LINES3D and depth): its normals and 3-D
+        lines stay on the device -> MfResult, or (MfResult, normal_axes, line_axes over the key lines) with axes=True"""
+        R = np.ascontiguousarray(R_last, np.float32).reshape(9)
+        res = MfResult()
+        nn = C.c_int(0); lib().hvo_tail_capacity(self.kl_cap, self.w, self.hgt, None, C.byref(nn), None)
+        na = np.zeros(max(nn.value, 1), np.uint8); la = np.zeros(max(self.kl_cap, 1), np.uint8)
+        self._chk(lib().hvo_stream_track_manhattan(self.h, cur, _p(R), C.byref(res), _p(na) if axes else None, _p(la) if axes else None),
+                  "stream_track_manhattan")
+        return (res, na[:nn.value], la) if axes else res
 
     def match_lines(self, frm, to, mode=LINE_MATCH_NNR, th=50.0, nnratio=0.95):
         m = np.full(self.kl_cap, -1, np.int32); n1 = C.c_int(0); n = C.c_int(0)

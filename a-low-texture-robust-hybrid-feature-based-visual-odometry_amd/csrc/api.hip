@@ -642,6 +642,56 @@ int hvo_search_lines_by_projection_map(hvo_ctx *ctx, int nq, const float *q_xyxy
                                                 cell_start, cell_items, n_items, bounds4, th, nn_ratio, match_idx, match_dist, n_matches);
 }
 
+// Tracking::TrackManhattanFrame (Tracking.cc:1172-1348) on host arrays (manhattan.hip)
+int hvo_track_manhattan(hvo_ctx *ctx, const hvo_surface_normal *normals, int n_normals, const hvo_line3d *l3d, int n_lines,
+                        const float R_last[9], hvo_mf_result *res, uint8_t *normal_axes, uint8_t *line_axes)
+{
+    if (!ctx || !R_last || !res || n_normals < 0 || n_lines < 0 || (n_normals > 0 && !normals) || (n_lines > 0 && !l3d)) return HVO_ERR_INVALID_ARG;
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t b_sn = al((size_t)n_normals * sizeof(hvo_surface_normal)), b_l = al((size_t)n_lines * sizeof(hvo_line3d)), b_r = al(sizeof(hvo_mf_result));
+    const size_t b_na = al((size_t)n_normals), b_la = al((size_t)n_lines);
+    char *a = (char *)hvo_call_arena(ctx, b_sn + b_l + b_r + b_na + b_la);
+    if (!a) return HVO_ERR_HIP;
+    hvo_surface_normal *d_sn = (hvo_surface_normal *)a; hvo_line3d *d_l = (hvo_line3d *)(a + b_sn); hvo_mf_result *d_r = (hvo_mf_result *)(a + b_sn + b_l);
+    uint8_t *d_na = (uint8_t *)(a + b_sn + b_l + b_r), *d_la = d_na + b_na;
+    hipStream_t st = ctx->stream;
+    if (n_normals) HVO_HIP(hipMemcpyAsync(d_sn, normals, (size_t)n_normals * sizeof(hvo_surface_normal), hipMemcpyHostToDevice, st));
+    if (n_lines) HVO_HIP(hipMemcpyAsync(d_l, l3d, (size_t)n_lines * sizeof(hvo_line3d), hipMemcpyHostToDevice, st));
+    int rc = mf_enqueue(st, d_sn, n_normals, 0, d_l, n_lines, 0, nullptr, 1, R_last, d_r, normal_axes ? d_na : nullptr, line_axes ? d_la : nullptr);
+    if (rc) { ctx->last_error = "Manhattan tracking launch"; return rc; }
+    HVO_HIP(hipMemcpyAsync(res, d_r, sizeof(hvo_mf_result), hipMemcpyDeviceToHost, st));
+    if (normal_axes && n_normals) HVO_HIP(hipMemcpyAsync(normal_axes, d_na, (size_t)n_normals, hipMemcpyDeviceToHost, st));
+    if (line_axes && n_lines) HVO_HIP(hipMemcpyAsync(line_axes, d_la, (size_t)n_lines, hipMemcpyDeviceToHost, st));
+    HVO_HIP(hipStreamSynchronize(st));
+    return HVO_OK;
+}
+
+// the resident batch as a sequence: frame k from frame k-1's R, one launch over the tail blocks of the last hvo_batch_run
+int hvo_batch_track_manhattan(hvo_ctx *ctx, int n, const float R0[9], hvo_mf_result *res)
+{
+    if (!ctx || !R0 || !res || n < 1 || n > ctx->batch_n) return HVO_ERR_INVALID_ARG;
+    const unsigned need = HVO_STAGE_PLANE_TAIL | HVO_STAGE_LINES3D;
+    if ((ctx->last_stages & need) != need) {
+        ctx->last_error = "Manhattan tracking: the last hvo_batch_run must include HVO_STAGE_PLANE_TAIL and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    char *d_out = nullptr; TailLayout L;
+    if (tail_batch_view(ctx, &d_out, &L)) { ctx->last_error = "Manhattan tracking: no resident tail results"; return HVO_ERR_INVALID_ARG; }
+    LsdView lv; memset(&lv, 0, sizeof(lv));
+    int rc;
+    if ((rc = lsd_prepare(ctx, ctx->batch_w, ctx->batch_h, std::max(n, ctx->p.max_batch), ctx->last_cull, &lv))) return rc;
+    hvo_mf_result *d_r = (hvo_mf_result *)hvo_call_arena(ctx, (size_t)n * sizeof(hvo_mf_result));
+    if (!d_r) return HVO_ERR_HIP;
+    hipStream_t st = ctx->stream;
+    rc = mf_enqueue(st, (const hvo_surface_normal *)(d_out + L.normals), L.n_normals, L.total, (const hvo_line3d *)(d_out + L.lines3d), L.nfeat, L.total,
+                    lv.d_nkl, n, R0, d_r, nullptr, nullptr);
+    if (rc) { ctx->last_error = "Manhattan tracking launch"; return rc; }
+    HVO_HIP(hipMemcpyAsync(res, d_r, (size_t)n * sizeof(hvo_mf_result), hipMemcpyDeviceToHost, st));
+    HVO_HIP(hipStreamSynchronize(st));
+    return HVO_OK;
+}
+
 // LSDmatcher::SearchDouble / SearchByDescriptor core (LSDmatcher.cpp:902-939): FrameBFMatch in both directions + mutual check
 int hvo_search_double(hvo_ctx *ctx, const uint8_t *d1, int n1, const uint8_t *d2, int n2, float th, float nnratio,
                       int32_t *m12, int *n_matches)

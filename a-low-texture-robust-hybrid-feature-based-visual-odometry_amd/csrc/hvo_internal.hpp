@@ -412,6 +412,14 @@ int tail_enqueue_points(hvo_ctx *ctx, hipStream_t st, unsigned stages, const Tai
 int tail_unpack(const TailLayout &L, unsigned stages, const char *ho, int n_kl, hvo_frame_tail *out);
 int tail_batch_run(hvo_ctx *ctx, unsigned stages);
 void tail_batch_free(hvo_ctx *ctx);
+// the resident batch's tail blocks (frame f at *d_out + f * L->total) after hvo_batch_run with tail stages; HVO_ERR_INVALID_ARG when none
+int tail_batch_view(hvo_ctx *ctx, char **d_out, TailLayout *L);
+
+// manhattan.hip: Tracking::TrackManhattanFrame over nframes frames chained in order (frame f's normals at (char *)d_sn + f * sn_stride, its
+// key lines' 3-D lines at (char *)d_l3d + f * l3d_stride; d_nl: per-frame line counts capped at nl, or null for nl lines).  The membership
+// bits (may be null) are frame 0's.
+int mf_enqueue(hipStream_t st, const hvo_surface_normal *d_sn, int nn, size_t sn_stride, const hvo_line3d *d_l3d, int nl, size_t l3d_stride,
+               const int *d_nl, int nframes, const float R_last[9], hvo_mf_result *d_res, uint8_t *d_normal_axes, uint8_t *d_line_axes);
 
 // peac.hip
 struct PeacView { uint16_t *d_depth; int pitch; size_t dframe; int8_t *d_labels8; hvo_plane *d_planes; int *d_meta; int npix, max_planes; size_t lstride /* bytes between two frames' label images */; };

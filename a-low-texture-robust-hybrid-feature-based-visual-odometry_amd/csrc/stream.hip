@@ -53,6 +53,8 @@ struct hvo_stream {
     char *d_ms = nullptr, *h_ms = nullptr; size_t ms_bytes = 0;
     // the local-map line search's scratch (hvo_stream_search_lines_by_projection_map): allocated on its first call, grow-only
     char *d_lm = nullptr, *h_lm = nullptr; size_t lm_dbytes = 0, lm_hbytes = 0;
+    // Manhattan tracking's result block (hvo_stream_track_manhattan): allocated on its first call, grow-only
+    char *d_mf = nullptr, *h_mf = nullptr; size_t mf_bytes = 0;
     hipStream_t s_match = nullptr;         // the matching calls run here, behind the two frames' events (not behind a frame's line chain)
     std::string last_error;
 };
@@ -87,6 +89,8 @@ void hvo_stream_destroy(hvo_stream *s)
     if (s->h_ms) (void)hipHostFree(s->h_ms);
     if (s->d_lm) (void)hipFree(s->d_lm);
     if (s->h_lm) (void)hipHostFree(s->h_lm);
+    if (s->d_mf) (void)hipFree(s->d_mf);
+    if (s->h_mf) (void)hipHostFree(s->h_mf);
     if (s->s_match) (void)hipStreamDestroy(s->s_match);
     delete s;
 }
@@ -770,6 +774,50 @@ int hvo_stream_set_readings(hvo_stream *s, unsigned mask)
 {
     if (!s) return HVO_ERR_INVALID_ARG;
     for (int i = 0; i < s->depth; i++) { const int rc = hvo_set_readings(s->slot[i].ctx, mask); if (rc) return rc; }
+    return HVO_OK;
+}
+
+// Tracking::TrackManhattanFrame (src/Tracking.cc:1172-1348) on the resident frame `cur`: its surface normals (HVO_STAGE_PLANE_TAIL) and 3-D lines
+// (HVO_STAGE_LINES3D) are read where the tail stages left them; only R_last goes up (as a kernel argument) and the result comes down
+int hvo_stream_track_manhattan(hvo_stream *s, int64_t cur, const float R_last[9], hvo_mf_result *res, uint8_t *normal_axes, uint8_t *line_axes)
+{
+    if (!s || !R_last || !res) return HVO_ERR_INVALID_ARG;
+    const unsigned need = HVO_STAGE_PLANE_TAIL | HVO_STAGE_LINES3D;
+    if ((s->tail_stages & need) != need) {
+        s->last_error = "Manhattan tracking: the stream must run HVO_STAGE_PLANE_TAIL and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
+    }
+    StreamSlot *B = slot_of(s, cur);
+    if (!B) { s->last_error = "Manhattan tracking: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    if (!B->had_depth) { s->last_error = "Manhattan tracking: the frame was submitted without depth (no normals, no 3-D lines)"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    const TailLayout &T = s->tl;
+    const int nn = T.n_normals, nf = T.nfeat;
+    const size_t b_r = al64(sizeof(hvo_mf_result)), b_na = al64((size_t)nn), b_la = al64((size_t)nf), bytes = b_r + b_na + b_la;
+    hipStream_t st = s->s_match;
+    if (s->mf_bytes < bytes) {
+        ST_HIP(hipStreamSynchronize(st));
+        if (s->d_mf) (void)hipFree(s->d_mf);
+        if (s->h_mf) (void)hipHostFree(s->h_mf);
+        s->d_mf = s->h_mf = nullptr; s->mf_bytes = 0;
+        ST_HIP(hipMalloc((void **)&s->d_mf, bytes));
+        ST_HIP(hipHostMalloc((void **)&s->h_mf, bytes, hipHostMallocDefault));
+        s->mf_bytes = bytes;
+    }
+    ST_HIP(hipStreamWaitEvent(st, B->ev_orb, 0));                // the normals (recorded behind them on the frame's ORB stream)
+    ST_HIP(hipStreamWaitEvent(st, B->ev_lsd, 0));                // the 3-D lines and the key-line count
+    hvo_mf_result *d_r = (hvo_mf_result *)s->d_mf; uint8_t *d_na = (uint8_t *)s->d_mf + b_r, *d_la = d_na + b_na;
+    int rc = mf_enqueue(st, (const hvo_surface_normal *)(B->d_tail + T.normals), nn, 0, (const hvo_line3d *)(B->d_tail + T.lines3d), nf, 0, B->lv.d_nkl, 1,
+                        R_last, d_r, normal_axes ? d_na : nullptr, line_axes ? d_la : nullptr);
+    if (rc) { s->last_error = "Manhattan tracking launch"; return rc; }
+    ST_HIP(hipMemcpyAsync(s->h_mf, s->d_mf, normal_axes || line_axes ? bytes : b_r, hipMemcpyDeviceToHost, st));
+    ST_HIP(hipStreamSynchronize(st));
+    memcpy(res, s->h_mf, sizeof(hvo_mf_result));
+    if (normal_axes) memcpy(normal_axes, s->h_mf + b_r, (size_t)nn);
+    if (line_axes) {
+        int n_kl = ((const int *)(B->h_out + s->lay.counts))[4];
+        n_kl = n_kl < 0 ? 0 : (n_kl > nf ? nf : n_kl);
+        memcpy(line_axes, s->h_mf + b_r + b_na, (size_t)n_kl);
+    }
     return HVO_OK;
 }
 

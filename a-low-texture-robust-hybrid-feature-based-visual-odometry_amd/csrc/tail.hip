@@ -215,6 +215,14 @@ int tail_batch_run(hvo_ctx *ctx, unsigned stages)
     return HVO_OK;
 }
 
+int tail_batch_view(hvo_ctx *ctx, char **d_out, TailLayout *L)
+{
+    TailBatch *T = (TailBatch *)ctx->tail;
+    if (!T || !T->d_out || T->frames < ctx->batch_n) return HVO_ERR_INVALID_ARG;
+    *d_out = T->d_out; *L = T->L;
+    return HVO_OK;
+}
+
 extern "C" int hvo_batch_download_tail(hvo_ctx *ctx, int n, hvo_frame_tail *out)
 {
     if (!ctx || !out || n < 1 || n > ctx->batch_n) return HVO_ERR_INVALID_ARG;

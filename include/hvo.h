@@ -489,6 +489,38 @@ int  hvo_stream_search_lines_by_projection_map(hvo_stream *s, int64_t cur, int n
                                                const double *q_wvec, const uint8_t *q_desc, const uint8_t *q_blocks, const uint8_t *t_occupied, float th, float nn_ratio,
                                                int32_t *match_idx, int32_t *match_dist, int *n_matches);
 
+/* ---- Manhattan-frame tracking (csrc/manhattan.hip) ----
+ * Tracking::TrackManhattanFrame(R_last, vSurfaceNormal, mVF3DLines) (reference src/Tracking.cc:1172-1348, called on every tracked frame at
+ * :706 and at initialisation at :659), with ProjectSN2Conic (953-1026), ProjectSN2MF (1028-1150) and MeanShift (1152-1170).  Per axis a = 1..3
+ * the normals within asin(sin 0.2018) and the 3-D line directions within asin(sin 0.1018) of column a-1 of R_last form the cone (numInCone
+ * counts the normals); the threshold is size/20, or (b + a) / 2 of the sorted counts when the middle one is below it (1215-1226); each axis's
+ * cone elements within sin 0.2518 of the CURRENT R_cm_update give m_j, and more than the threshold of them a mean shift and a new column a-1.
+ * R_cm in the reference is a shallow cv::Mat copy of R_cm_update (1181), so axes 2 and 3 read the columns the earlier axes replaced.  Two
+ * found axes: the third column is the code's cross product (negated when |det + 1| < 0.5); two or three: R = U V^T of the SVD.  Fewer than
+ * two: no SVD, R is R_last with the one found column (if any) replaced.  DESIGN.md section 7 lists the readings of OpenCV's arithmetic. */
+typedef struct {
+    float   R[9];                 /* returned R_cm_update, row-major: the orthonormalised update when tracked, else R_last with a found column */
+    float   axis_vec[3][3];       /* R_cm_Rec per axis, zeros when not found */
+    float   density[3];           /* s_j_density per axis (0 when not found) */
+    int32_t found[3], n_found;    /* directionFound1..3, numDirectionFound */
+    int32_t n_in_cone[3], n_selected[3], min_num_sn;   /* numInCone, m_j_selected.size(), numOfSN */
+    int32_t tracked;              /* 1: >= 2 axes, R is the orthonormalised update */
+    int32_t status;               /* HVO_OK (written by the kernel for every frame it ran; a refused call returns its error instead) */
+} hvo_mf_result;
+/* On host arrays: normals = vSurfaceNormal (n_normals entries, NaN ones included: they count in size/20), l3d = hvo_lines_3d of every key
+ * line (n_lines entries; the good ones, in order, are mVF3DLines), R_last row-major.  normal_axes (n_normals) / line_axes (n_lines) are
+ * optional: bit a-1 is set where the element enters ProjectSN2MF's lists for axis a (vSurfaceNormal{x,y,z}, vVanishingLine{x,y,z}). */
+int hvo_track_manhattan(hvo_ctx *ctx, const hvo_surface_normal *normals, int n_normals, const hvo_line3d *l3d, int n_lines,
+                        const float R_last[9], hvo_mf_result *res, uint8_t *normal_axes, uint8_t *line_axes);
+/* On the resident frame `cur`: its surface normals and 3-D lines stay on the device.  The stream must run HVO_STAGE_PLANE_TAIL and
+ * HVO_STAGE_LINES3D and the frame must have been submitted with depth (else HVO_ERR_INVALID_ARG with hvo_stream_last_error set).  A tracker
+ * threads mLastRcm through by passing the previous call's res->R as the next R_last.  line_axes has n_kl(cur) entries.  The result buffer is
+ * allocated on the first call and grows on demand. */
+int hvo_stream_track_manhattan(hvo_stream *s, int64_t cur, const float R_last[9], hvo_mf_result *res, uint8_t *normal_axes, uint8_t *line_axes);
+/* The first n frames of the resident batch as a sequence, in one launch: frame k starts from frame k-1's R, frame 0 from R0.  Needs
+ * HVO_STAGE_PLANE_TAIL and HVO_STAGE_LINES3D from the last hvo_batch_run. */
+int hvo_batch_track_manhattan(hvo_ctx *ctx, int n, const float R0[9], hvo_mf_result *res);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer.  Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

@@ -486,11 +486,46 @@ public:
         match_idx.resize(nq);
         return n;
     }
+    // Tracking::TrackManhattanFrame(mLastRcm, mCurrentFrame.vSurfaceNormal, mCurrentFrame.mVF3DLines) (Tracking.cc:1172-1348) on the resident
+    // frame `cur`: its normals and 3-D lines stay on the device.  The stream must run HVO_STAGE_PLANE_TAIL | HVO_STAGE_LINES3D.  Call before
+    // collect() releases the slot.  normal_axes / line_axes (optional): n_normals / klCap() entries.
+    hvo_mf_result trackManhattanFrame(int64_t cur, const float R_last[9], uint8_t *normal_axes = nullptr, uint8_t *line_axes = nullptr)
+    {
+        hvo_mf_result r;
+        check(hvo_stream_track_manhattan(s_, cur, R_last, &r, normal_axes, line_axes), "hvo_stream_track_manhattan");
+        return r;
+    }
     void setReadings(unsigned mask) { check(hvo_stream_set_readings(s_, mask), "hvo_stream_set_readings"); }
     hvo_stream *get() const { return s_; }
     int kpCap() const { return kp_cap_; } int klCap() const { return kl_cap_; } int plCap() const { return pl_cap_; }
 private:
     hvo_stream *s_ = nullptr; int kp_cap_ = 0, kl_cap_ = 0, pl_cap_ = 0;
+};
+
+// The Manhattan-frame part of Tracking (src/Tracking.cc:706-718 and 1172-1348): it keeps mLastRcm and threads it through the per-frame calls,
+// MF_can = TrackManhattanFrame(mLastRcm, vSurfaceNormal, mVF3DLines); MF_can.copyTo(mLastRcm).  The caller seeds mLastRcm with the
+// initialisation's Rotation_cm (Map::FindManhattan, which stays on the host) and forms mRotation_wc = (Rotation_cm * MF_can^T)^T itself.
+class ManhattanTracking {
+public:
+    ManhattanTracking(hvo_ctx *ctx, const float R_init[9]) : ctx_(ctx) { for (int i = 0; i < 9; i++) mLastRcm[i] = R_init[i]; }
+    // on host arrays: vSurfaceNormal (NaN ones included) and hvo_lines_3d of every key line (the good ones are mVF3DLines)
+    hvo_mf_result TrackManhattanFrame(const hvo_surface_normal *normals, int n_normals, const hvo_line3d *l3d, int n_lines)
+    {
+        hvo_mf_result r;
+        check(hvo_track_manhattan(ctx_, normals, n_normals, l3d, n_lines, mLastRcm, &r, nullptr, nullptr), "hvo_track_manhattan");
+        for (int i = 0; i < 9; i++) mLastRcm[i] = r.R[i];
+        return r;
+    }
+    // on the resident frame `cur` of a stream
+    hvo_mf_result TrackManhattanFrame(FrameStream &fs, int64_t cur)
+    {
+        const hvo_mf_result r = fs.trackManhattanFrame(cur, mLastRcm);
+        for (int i = 0; i < 9; i++) mLastRcm[i] = r.R[i];
+        return r;
+    }
+    float mLastRcm[9];          // R_cm of the last frame, row-major
+private:
+    hvo_ctx *ctx_;
 };
 
 }  // namespace hvo
