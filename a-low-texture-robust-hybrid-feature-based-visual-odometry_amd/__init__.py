@@ -75,6 +75,8 @@ EXPORTS = [
     "hvo_stream_search_by_projection", "hvo_stream_match_lines", "hvo_stream_project_last", "hvo_search_by_projection_tracked",
     "hvo_tail_capacity", "hvo_set_tail_params", "hvo_batch_download_tail", "hvo_stream_collect_tail", "hvo_normals_lpvo",
     "hvo_track_manhattan", "hvo_stream_track_manhattan", "hvo_batch_track_manhattan",
+    "hvo_plane_map_create", "hvo_plane_map_destroy", "hvo_plane_map_set", "hvo_plane_map_set_bad", "hvo_plane_map_counts", "hvo_plane_map_slot",
+    "hvo_plane_map_last_error", "hvo_match_planes", "hvo_stream_match_planes", "hvo_batch_match_planes",
 ]
 
 
@@ -132,6 +134,27 @@ class MfResult(C.Structure):
 
 
 assert C.sizeof(MfResult) == 21 * 4 + 13 * 4
+
+
+class PlaneMatch(C.Structure):
+    """hvo_plane_match: one PlaneMatcher::SearchMapByCoefficients call (slots, -1 = none)"""
+    _fields_ = [("n_planes", C.c_int32), ("n_matches", C.c_int32), ("match", C.c_int32 * 64), ("vertical", C.c_int32 * 64),
+                ("parallel", C.c_int32 * 64), ("plane_idx", C.c_int32 * 64), ("dist", C.c_float * 64), ("pM", (C.c_float * 4) * 64)]
+
+    def to_dict(self):
+        n = self.n_planes
+        return dict(n_planes=n, n_matches=self.n_matches, match=np.array(self.match[:n], np.int32), vertical=np.array(self.vertical[:n], np.int32),
+                    parallel=np.array(self.parallel[:n], np.int32), plane_idx=np.array(self.plane_idx[:n], np.int32),
+                    dist=np.array(self.dist[:n], np.float32), pM=np.array([r[:] for r in self.pM], np.float32).reshape(64, 4)[:n])
+
+
+assert C.sizeof(PlaneMatch) == 8 + 5 * 64 * 4 + 64 * 16
+
+PLANE_MATCH_DEFAULT_TH = (0.1, 0.86, 0.08716, 0.9962)       # PlaneMatcher's constructor defaults (include/PlaneMatcher.h:17)
+
+
+def _th_arg(th):
+    return None if th is None else np.ascontiguousarray(th, np.float32).reshape(4)
 
 
 def _normals_arg(normals):
@@ -227,6 +250,16 @@ def lib():
         L.hvo_track_manhattan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MfResult), C.c_void_p, C.c_void_p]
         L.hvo_stream_track_manhattan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MfResult), C.c_void_p, C.c_void_p]
         L.hvo_batch_track_manhattan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.hvo_plane_map_create.argtypes = [C.c_int, C.c_int, C.c_int64]; L.hvo_plane_map_create.restype = C.c_void_p
+        L.hvo_plane_map_destroy.argtypes = [C.c_void_p]; L.hvo_plane_map_destroy.restype = None
+        L.hvo_plane_map_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.hvo_plane_map_set_bad.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.hvo_plane_map_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+        L.hvo_plane_map_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.hvo_plane_map_last_error.argtypes = [C.c_void_p]; L.hvo_plane_map_last_error.restype = C.c_char_p
+        L.hvo_match_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PlaneMatch), C.c_void_p, C.c_void_p]
+        L.hvo_stream_match_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PlaneMatch)]
+        L.hvo_batch_match_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hvo_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_stream_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_search_by_projection_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
@@ -294,6 +327,48 @@ def default_params(**kw):
             raise TypeError("unknown hvo_params field " + k)
         setattr(p, k, v)
     return p
+
+
+class PlaneMap:
+    """hvo_plane_map: the map's planes resident on one device (world coefficients, bad flag, cloud per slot).  Slot index = position in the
+    vector PlaneMatcher::SearchMapByCoefficients would have received.  Not thread-safe; usable from any Context / Stream of its device."""
+
+    def __init__(self, device=0, slots=0, points=0):
+        self.h = lib().hvo_plane_map_create(device, slots, points)
+        if not self.h:
+            raise HvoError(-3, "hvo_plane_map_create")
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().hvo_plane_map_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _chk(self, rc, what):
+        if rc != HVO_OK:
+            raise HvoError(rc, what + ": " + lib().hvo_plane_map_last_error(self.h).decode())
+
+    def set(self, slot, coef, xyz):
+        """set or replace a slot: coef = GetWorldPos() (4 floats), xyz = mvPlanePoints as (n, 3) floats (n may be 0)"""
+        c = np.ascontiguousarray(coef, np.float32).reshape(4)
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        self._chk(lib().hvo_plane_map_set(self.h, slot, _p(c), _p(x) if len(x) else None, len(x)), "plane_map_set")
+
+    def set_bad(self, slot, bad=True):
+        self._chk(lib().hvo_plane_map_set_bad(self.h, slot, 1 if bad else 0), "plane_map_set_bad")
+
+    def counts(self):
+        """(slots, good slots, points of all slots)"""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int64(0)
+        self._chk(lib().hvo_plane_map_counts(self.h, C.byref(a), C.byref(b), C.byref(c)), "plane_map_counts")
+        return a.value, b.value, c.value
+
+    def slot(self, slot):
+        """(coef, n_points, bad) of one slot"""
+        c = np.zeros(4, np.float32); n, b = C.c_int(0), C.c_int(0)
+        self._chk(lib().hvo_plane_map_slot(self.h, slot, _p(c), C.byref(n), C.byref(b)), "plane_map_slot")
+        return c, n.value, bool(b.value)
 
 
 class Context:
@@ -526,6 +601,29 @@ class Context:
         R = np.ascontiguousarray(R0, np.float32).reshape(9)
         res = (MfResult * n)()
         self._chk(lib().hvo_batch_track_manhattan(self.h, n, _p(R), res), "batch_track_manhattan")
+        return list(res)
+
+    def match_planes(self, pmap, coef, Tcw, th=None, matrices=False):
+        """PlaneMatcher::SearchMapByCoefficients (src/PlaneMatcher.cpp:10-68) of the frame planes coef ((n, 4) floats, camera frame) under the pose
+        Tcw (3 x 4) against the resident PlaneMap -> PlaneMatch, or (PlaneMatch, dist (n, slots), angle (n, slots)) with matrices=True.
+        th = (dTh, aTh, verTh, parTh), None for the constructor's defaults."""
+        c = np.ascontiguousarray(coef, np.float32).reshape(-1, 4)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12)
+        t = _th_arg(th)
+        res = PlaneMatch()
+        ns = pmap.counts()[0]
+        dm = np.zeros((len(c), ns), np.float32); am = np.zeros((len(c), ns), np.float32)
+        self._chk(lib().hvo_match_planes(self.h, pmap.h, _p(c) if len(c) else None, len(c), _p(T), None if t is None else _p(t), C.byref(res),
+                                         _p(dm) if matrices and dm.size else None, _p(am) if matrices and am.size else None), "match_planes")
+        return (res, dm, am) if matrices else res
+
+    def batch_match_planes(self, pmap, Tcw, th=None):
+        """the first len(Tcw) frames of the resident batch (needs STAGE_PLANE_TAIL in the last batch_run), frame k under Tcw[k] (3 x 4), every
+        frame against the same PlaneMap in one launch sequence -> list of PlaneMatch"""
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 12)
+        t = _th_arg(th)
+        res = (PlaneMatch * len(T))()
+        self._chk(lib().hvo_batch_match_planes(self.h, pmap.h, len(T), _p(T), None if t is None else _p(t), res), "batch_match_planes")
         return list(res)
 
     def set_readings(self, blur_float=False, lsd_8u=False):
@@ -984,6 +1082,15 @@ class Stream:
         self._chk(lib().hvo_stream_track_manhattan(self.h, cur, _p(R), C.byref(res), _p(na) if axes else None, _p(la) if axes else None),
                   "stream_track_manhattan")
         return (res, na[:nn.value], la) if axes else res
+
+    def match_planes(self, pmap, cur, Tcw, th=None):
+        """PlaneMatcher::SearchMapByCoefficients on the resident frame `cur` (needs STAGE_PLANE_TAIL and depth): the valid planes of its plane
+        tail stay on the device -> PlaneMatch (plane_idx: each frame plane's index among the 64 plane_clouds records)"""
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12)
+        t = _th_arg(th)
+        res = PlaneMatch()
+        self._chk(lib().hvo_stream_match_planes(self.h, pmap.h, cur, _p(T), None if t is None else _p(t), C.byref(res)), "stream_match_planes")
+        return res
 
     def match_lines(self, frm, to, mode=LINE_MATCH_NNR, th=50.0, nnratio=0.95):
         m = np.full(self.kl_cap, -1, np.int32); n1 = C.c_int(0); n = C.c_int(0)

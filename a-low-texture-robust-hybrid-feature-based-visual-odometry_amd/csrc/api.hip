@@ -692,6 +692,35 @@ int hvo_batch_track_manhattan(hvo_ctx *ctx, int n, const float R0[9], hvo_mf_res
     return HVO_OK;
 }
 
+// PlaneMatcher::SearchMapByCoefficients (PlaneMatcher.cpp:10-68) of host coefficients against a resident plane map (plane_assoc.hip)
+int hvo_match_planes(hvo_ctx *ctx, hvo_plane_map *m, const float *coef, int n, const float Tcw[12], const float th[4], hvo_plane_match *res,
+                     float *dist_mat, float *angle_mat)
+{
+    if (!ctx || !m || !Tcw || !res || n < 0 || n > 64 || (n > 0 && !coef)) return HVO_ERR_INVALID_ARG;
+    if (pa_map_device(m) != ctx->device) { ctx->last_error = "plane association: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    static const float none[4] = { 0.f, 0.f, 0.f, 0.f };
+    const int rc = pa_match(ctx->stream, m, n ? coef : none, n, nullptr, 0, 1, Tcw, th, res, dist_mat, angle_mat);
+    if (rc) ctx->last_error = pa_map_error(m);
+    return rc;
+}
+
+// the same over the first n frames of the resident batch: the plane tail's records where the last hvo_batch_run left them, one Tcw per frame
+int hvo_batch_match_planes(hvo_ctx *ctx, hvo_plane_map *m, int n, const float *Tcw, const float th[4], hvo_plane_match *res)
+{
+    if (!ctx || !m || !Tcw || !res || n < 1 || n > ctx->batch_n) return HVO_ERR_INVALID_ARG;
+    if (!(ctx->last_stages & HVO_STAGE_PLANE_TAIL)) {
+        ctx->last_error = "plane association: the last hvo_batch_run must include HVO_STAGE_PLANE_TAIL"; return HVO_ERR_INVALID_ARG;
+    }
+    if (pa_map_device(m) != ctx->device) { ctx->last_error = "plane association: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    char *d_out = nullptr; TailLayout L;
+    if (tail_batch_view(ctx, &d_out, &L)) { ctx->last_error = "plane association: no resident tail results"; return HVO_ERR_INVALID_ARG; }
+    const int rc = pa_match(ctx->stream, m, nullptr, 0, (const hvo_plane_cloud *)(d_out + L.pclouds), L.total, n, Tcw, th, res, nullptr, nullptr);
+    if (rc) ctx->last_error = pa_map_error(m);
+    return rc;
+}
+
 // LSDmatcher::SearchDouble / SearchByDescriptor core (LSDmatcher.cpp:902-939): FrameBFMatch in both directions + mutual check
 int hvo_search_double(hvo_ctx *ctx, const uint8_t *d1, int n1, const uint8_t *d2, int n2, float th, float nnratio,
                       int32_t *m12, int *n_matches)

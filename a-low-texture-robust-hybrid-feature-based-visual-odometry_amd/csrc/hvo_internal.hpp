@@ -421,6 +421,15 @@ int tail_batch_view(hvo_ctx *ctx, char **d_out, TailLayout *L);
 int mf_enqueue(hipStream_t st, const hvo_surface_normal *d_sn, int nn, size_t sn_stride, const hvo_line3d *d_l3d, int nl, size_t l3d_stride,
                const int *d_nl, int nframes, const float R_last[9], hvo_mf_result *d_res, uint8_t *d_normal_axes, uint8_t *d_line_axes);
 
+// plane_assoc.hip: PlaneMatcher::SearchMapByCoefficients of nframes frames against a resident plane map, on stream st; it returns after the
+// stream has drained, with the results in res (host, nframes entries).  The frame planes are either the host array coef (n x 4 floats, one
+// frame) or the plane tail's records (frame f's 64 hvo_plane_cloud at (char *)d_pc + f * pc_stride).  Tcw: host, nframes x 12; th: the four
+// thresholds or null for the defaults; dist_mat / angle_mat: host, n x slots, host form only, may be null.
+int pa_match(hipStream_t st, hvo_plane_map *m, const float *coef, int n, const hvo_plane_cloud *d_pc, size_t pc_stride, int nframes, const float *Tcw,
+             const float th[4], hvo_plane_match *res, float *dist_mat, float *angle_mat);
+int pa_map_device(const hvo_plane_map *m);
+const char *pa_map_error(const hvo_plane_map *m);
+
 // peac.hip
 struct PeacView { uint16_t *d_depth; int pitch; size_t dframe; int8_t *d_labels8; hvo_plane *d_planes; int *d_meta; int npix, max_planes; size_t lstride /* bytes between two frames' label images */; };
 bool peac_plan_covers(const hvo_ctx *ctx, int w, int h, int batch);

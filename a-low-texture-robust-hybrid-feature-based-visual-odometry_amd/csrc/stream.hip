@@ -821,4 +821,22 @@ int hvo_stream_track_manhattan(hvo_stream *s, int64_t cur, const float R_last[9]
     return HVO_OK;
 }
 
+// PlaneMatcher::SearchMapByCoefficients (src/PlaneMatcher.cpp:10-68) on the resident frame `cur` against a resident plane map: the frame's
+// hvo_plane_cloud records are read where HVO_STAGE_PLANE_TAIL left them; only Tcw and the thresholds go up.  The scratch is the map's.
+int hvo_stream_match_planes(hvo_stream *s, hvo_plane_map *m, int64_t cur, const float Tcw[12], const float th[4], hvo_plane_match *res)
+{
+    if (!s || !m || !Tcw || !res) return HVO_ERR_INVALID_ARG;
+    if (!(s->tail_stages & HVO_STAGE_PLANE_TAIL)) { s->last_error = "plane association: the stream must run HVO_STAGE_PLANE_TAIL"; return HVO_ERR_INVALID_ARG; }
+    StreamSlot *B = slot_of(s, cur);
+    if (!B) { s->last_error = "plane association: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    if (!B->had_depth) { s->last_error = "plane association: the frame was submitted without depth (no planes)"; return HVO_ERR_INVALID_ARG; }
+    if (pa_map_device(m) != s->p.device) { s->last_error = "plane association: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    hipStream_t st = s->s_match;
+    ST_HIP(hipStreamWaitEvent(st, B->ev_peac, 0));               // the plane tail runs on the frame's plane stream
+    const int rc = pa_match(st, m, nullptr, 0, (const hvo_plane_cloud *)(B->d_tail + s->tl.pclouds), 0, 1, Tcw, th, res, nullptr, nullptr);
+    if (rc) s->last_error = pa_map_error(m);
+    return rc;
+}
+
 }  // extern "C"

@@ -521,6 +521,62 @@ int hvo_stream_track_manhattan(hvo_stream *s, int64_t cur, const float R_last[9]
  * HVO_STAGE_PLANE_TAIL and HVO_STAGE_LINES3D from the last hvo_batch_run. */
 int hvo_batch_track_manhattan(hvo_ctx *ctx, int n, const float R0[9], hvo_mf_result *res);
 
+/* ---- Map-plane association (csrc/plane_assoc.hip) ----
+ * PlaneMatcher::SearchMapByCoefficients(Frame, GetAllMapPlanes()) (reference src/PlaneMatcher.cpp:10-68 with PointDistanceFromPlane :69-81 and
+ * Frame::ComputePlaneWorldCoeff src/Frame.cc:2275-2280; called from src/Tracking.cc:2012 / :2407 and :2827).  For frame plane i and the map's
+ * slots j in ascending order, bad slots skipped: pM = Tcw^T coef_i (sums in double, rounded to float), angle = the float
+ * dot product of the two normals, left to right.  |angle| beyond aTh: dis = the smallest |pM . (x, y, z, 1)| over the slot's cloud in float
+ * (100 for an empty cloud; a NaN distance never wins); dis below the running dTh makes j the match and lowers the threshold to dis.  Otherwise
+ * (a gated slot whose dis is not below the running threshold included) |angle| below the running verTh makes j the vertical plane, else |angle|
+ * beyond the running parTh makes j the parallel plane; each role lowers / raises its threshold to |angle|.  Every comparison is strict: the
+ * first slot wins a tie.
+ *
+ * hvo_plane_map: the map's planes resident on one device -- per slot the world coefficients, a bad flag and the cloud (mvPlanePoints' xyz).
+ * A slot's index is its position in the vector the tracker would have passed.  The map belongs to a device, not to a context: any hvo_ctx or
+ * hvo_stream of that device may match against it.  Like a context it is NOT thread-safe: one call at a time on a map, the matching calls
+ * included (they use the map's grow-only scratch).  Every call here returns after its device work has finished, so a set is visible to the
+ * next match, and nothing is allocated by a call once the slot table, the point pool and the scratch have grown to the sizes in use. */
+typedef struct hvo_plane_map hvo_plane_map;
+#define HVO_PLANE_MAP_MAX_SLOTS (1 << 20)
+/* slots / points: initial capacities (both grow on demand; 0 = a small default).  NULL when the device or the allocation fails. */
+hvo_plane_map *hvo_plane_map_create(int device, int slots, int64_t points);
+void hvo_plane_map_destroy(hvo_plane_map *m);
+/* Set or replace slot `slot` (0 <= slot < HVO_PLANE_MAP_MAX_SLOTS): coef = GetWorldPos(), xyz = n_points x 3 floats (may be NULL when
+ * n_points is 0).  A slot past the end extends the map; the slots skipped over start bad with no points.  A new slot starts good, a replaced
+ * one keeps its flag.  A cloud that outgrows the slot's room moves that slot alone; the other slots' results do not change. */
+int hvo_plane_map_set(hvo_plane_map *m, int slot, const float coef[4], const float *xyz, int n_points);
+/* MapPlane::SetBadFlag / a slot taken back into use: bad != 0 makes the matcher skip the slot.  The slot must exist. */
+int hvo_plane_map_set_bad(hvo_plane_map *m, int slot, int bad);
+/* each pointer may be NULL: slots in the map, the good ones among them, the points of all slots */
+int hvo_plane_map_counts(const hvo_plane_map *m, int *n_slots, int *n_good, int64_t *n_points);
+/* one slot as the map holds it (each pointer may be NULL) */
+int hvo_plane_map_slot(const hvo_plane_map *m, int slot, float coef[4], int *n_points, int *bad);
+const char *hvo_plane_map_last_error(const hvo_plane_map *m);
+
+typedef struct {
+    int32_t n_planes;             /* mnPlaneNum: the frame planes matched (the valid ones, in order) */
+    int32_t n_matches;            /* the return value: frame planes with a match */
+    int32_t match[64];            /* mvpMapPlanes[i]: slot, or -1 (the reference leaves NULL) */
+    int32_t vertical[64];         /* mvpVerticalPlanes[i] */
+    int32_t parallel[64];         /* mvpParallelPlanes[i] */
+    int32_t plane_idx[64];        /* the frame plane's index among the 64 plane_clouds records (resident forms; i itself on host arrays), -1 past n_planes */
+    float   dist[64];             /* the matched slot's distance, 100 without a match */
+    float   pM[64][4];            /* ComputePlaneWorldCoeff(i) */
+} hvo_plane_match;
+/* th = { dTh, aTh, verTh, parTh } (Plane.AssociationDisRef, AssociationAngRef, VerticalThreshold, ParallelThreshold), none NaN; NULL takes the
+ * constructor's defaults { 0.1, 0.86, 0.08716, 0.9962 }.  Tcw: rows 0..2 of the pose, row-major 3 x 4, as in hvo_stream_project_last.
+ * On host arrays: coef = n x 4 floats in the camera frame (mvPlaneCoefficients), n <= 64.  dist_mat / angle_mat (optional, n x slots
+ * floats each, slots = the map's count): every pair's distance (100 where the gate did not pass or the slot is bad) and angle (computed for
+ * bad slots too).  An empty map or n == 0 is not an error. */
+int hvo_match_planes(hvo_ctx *ctx, hvo_plane_map *m, const float *coef, int n, const float Tcw[12], const float th[4], hvo_plane_match *res,
+                     float *dist_mat, float *angle_mat);
+/* On the resident frame `cur`: the valid hvo_plane_cloud records are read where HVO_STAGE_PLANE_TAIL left them; only Tcw and the thresholds
+ * go up.  Without that stage, or for a frame submitted without depth: HVO_ERR_INVALID_ARG with hvo_stream_last_error set. */
+int hvo_stream_match_planes(hvo_stream *s, hvo_plane_map *m, int64_t cur, const float Tcw[12], const float th[4], hvo_plane_match *res);
+/* The first n frames of the resident batch (after hvo_batch_run with HVO_STAGE_PLANE_TAIL), frame k under Tcw + 12 k, in one launch
+ * sequence: the map's clouds are read once for all n frames.  res: n entries. */
+int hvo_batch_match_planes(hvo_ctx *ctx, hvo_plane_map *m, int n, const float *Tcw, const float th[4], hvo_plane_match *res);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer.  Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

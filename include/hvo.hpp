@@ -528,4 +528,47 @@ private:
     hvo_ctx *ctx_;
 };
 
+// The map's planes resident on one device (hvo_plane_map): per slot GetWorldPos(), isBad() and mvPlanePoints' xyz.  The slot index is the
+// position in the vector PlaneMatcher::SearchMapByCoefficients would have received (mpMap->GetAllMapPlanes()).  The local mapper calls set()
+// where MapPlane's constructor / UpdateCoefficientsAndPoints produce a cloud and setBad() where SetBadFlag runs.  Not thread-safe.
+class PlaneMap {
+public:
+    explicit PlaneMap(int device = 0, int slots = 0, int64_t points = 0) : m_(hvo_plane_map_create(device, slots, points))
+    {
+        if (!m_) throw Error(HVO_ERR_HIP, "hvo_plane_map_create");
+    }
+    ~PlaneMap() { hvo_plane_map_destroy(m_); }
+    PlaneMap(const PlaneMap &) = delete;
+    PlaneMap &operator=(const PlaneMap &) = delete;
+    void set(int slot, const float coef[4], const float *xyz, int n_points) { check(hvo_plane_map_set(m_, slot, coef, xyz, n_points), "hvo_plane_map_set"); }
+    void setBad(int slot, bool bad = true) { check(hvo_plane_map_set_bad(m_, slot, bad ? 1 : 0), "hvo_plane_map_set_bad"); }
+    int size() const { int n = 0; check(hvo_plane_map_counts(m_, &n, nullptr, nullptr), "hvo_plane_map_counts"); return n; }
+    int64_t points() const { int64_t n = 0; check(hvo_plane_map_counts(m_, nullptr, nullptr, &n), "hvo_plane_map_counts"); return n; }
+    hvo_plane_map *get() const { return m_; }
+private:
+    hvo_plane_map *m_;
+};
+
+// PlaneMatcher (include/PlaneMatcher.h, src/PlaneMatcher.cpp): the constructor's four thresholds and SearchMapByCoefficients over a resident
+// PlaneMap.  The result's match / vertical / parallel hold slot indices where the reference fills mvpMapPlanes / mvpVerticalPlanes /
+// mvpParallelPlanes (-1: left NULL); the return value of the reference is res.n_matches.
+class PlaneMatcher {
+public:
+    PlaneMatcher(float dTh = 0.1f, float aTh = 0.86f, float verTh = 0.08716f, float parTh = 0.9962f) { th_[0] = dTh; th_[1] = aTh; th_[2] = verTh; th_[3] = parTh; }
+    // on host arrays: mvPlaneCoefficients (n x 4 floats, n <= 64) and rows 0..2 of mTcw
+    int SearchMapByCoefficients(hvo_ctx *ctx, const float *coef, int n, const float Tcw[12], const PlaneMap &map, hvo_plane_match &res) const
+    {
+        check(hvo_match_planes(ctx, map.get(), coef, n, Tcw, th_, &res, nullptr, nullptr), "hvo_match_planes");
+        return res.n_matches;
+    }
+    // on the resident frame `cur` of a stream (HVO_STAGE_PLANE_TAIL); call before collect() releases the slot
+    int SearchMapByCoefficients(FrameStream &fs, int64_t cur, const float Tcw[12], const PlaneMap &map, hvo_plane_match &res) const
+    {
+        check(hvo_stream_match_planes(fs.get(), map.get(), cur, Tcw, th_, &res), "hvo_stream_match_planes");
+        return res.n_matches;
+    }
+private:
+    float th_[4];
+};
+
 }  // namespace hvo
