@@ -76,7 +76,7 @@ EXPORTS = [
     "hvo_tail_capacity", "hvo_set_tail_params", "hvo_batch_download_tail", "hvo_stream_collect_tail", "hvo_normals_lpvo",
     "hvo_track_manhattan", "hvo_stream_track_manhattan", "hvo_batch_track_manhattan",
     "hvo_plane_map_create", "hvo_plane_map_destroy", "hvo_plane_map_set", "hvo_plane_map_set_bad", "hvo_plane_map_counts", "hvo_plane_map_slot",
-    "hvo_plane_map_last_error", "hvo_match_planes", "hvo_stream_match_planes", "hvo_batch_match_planes",
+    "hvo_plane_map_last_error", "hvo_match_planes", "hvo_stream_match_planes", "hvo_batch_match_planes", "hvo_pose_optimize", "hvo_stream_pose_optimize", "hvo_batch_pose_optimize", "hvo_pose_last_kernel_ms", "hvo_stream_pose_last_kernel_ms",
 ]
 
 
@@ -151,6 +151,95 @@ class PlaneMatch(C.Structure):
 assert C.sizeof(PlaneMatch) == 8 + 5 * 64 * 4 + 64 * 16
 
 PLANE_MATCH_DEFAULT_TH = (0.1, 0.86, 0.08716, 0.9962)       # PlaneMatcher's constructor defaults (include/PlaneMatcher.h:17)
+
+
+class PosePlaneParams(C.Structure):
+    """hvo_pose_plane_params: Plane.AngleInfo, DistanceInfo, ParallelInfo, VerticalInfo, Chi, VPChi of the settings file"""
+    _fields_ = [(k, C.c_double) for k in ("angle_info", "distance_info", "parallel_info", "vertical_info", "chi", "vp_chi")]
+
+
+class PoseCamera(C.Structure):
+    _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "bf", "b")]
+
+
+class PoseProblem(C.Structure):
+    """hvo_pose_problem: one frame's Optimizer::PoseOptimization input (include/hvo.h)"""
+    _fields_ = [("Tcw", C.c_float * 12), ("n_points", C.c_int32), ("n_lines", C.c_int32), ("n_planes", C.c_int32), ("reserved", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("kp_un", "uright", "inv_sigma2", "linefn", "lines3d", "plane_coef",
+                                          "pt_has", "pt_xyz", "ln_has", "ln_xyz", "pl_has", "pl_coef_w",
+                                          "plane_map", "slot_match", "slot_parallel", "slot_vertical")]
+
+
+class PoseFlags(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("pt_outlier", "ln_outlier", "pl_outlier", "vp_outlier")]
+
+
+class PoseResult(C.Structure):
+    """hvo_pose_result; after a call through the binding the outlier flags hang on it as numpy arrays (pt_outlier, ln_outlier, pl_outlier
+    (n_planes x 3: plane, parallel, vertical), vp_outlier)"""
+    _fields_ = [("Tcw_d", C.c_double * 12), ("Tcw", C.c_float * 12), ("ret", C.c_int32), ("n_initial", C.c_int32), ("n_bad", C.c_int32),
+                ("n_line_bad", C.c_int32), ("n_edges", C.c_int32), ("rounds", C.c_int32), ("iterations", C.c_int32 * 4), ("trials", C.c_int32 * 4),
+                ("status", C.c_int32), ("reserved", C.c_int32), ("lam", C.c_double * 4), ("chi2", C.c_double * 4)]
+
+    def to_dict(self):
+        d = {k: (np.array(getattr(self, k)) if hasattr(getattr(self, k), "__len__") else getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+        d["Tcw_d"] = d["Tcw_d"].reshape(3, 4); d["Tcw"] = d["Tcw"].reshape(3, 4)
+        for k in ("pt_outlier", "ln_outlier", "pl_outlier", "vp_outlier"):
+            if hasattr(self, k): d[k] = getattr(self, k)
+        return d
+
+
+def _pose_problem(Tcw, kp_un=None, uright=None, inv_sigma2=None, linefn=None, lines3d=None, plane_coef=None,
+                  pt_has=None, pt_xyz=None, ln_has=None, ln_xyz=None, pl_has=None, pl_coef_w=None, counts=None, plane_map=None, plane_match=None):
+    """(PoseProblem, PoseFlags, the arrays that must stay alive).  counts = (n_points, n_lines, n_planes) when the frame side is resident.
+    plane_map + plane_match (a PlaneMatch, or a dict with match / parallel / vertical slot arrays): the plane side as slots of a PlaneMap."""
+    keep = {}
+    def arr(k, a, dt, shape):
+        if a is None: return None
+        keep[k] = np.ascontiguousarray(a, dt).reshape(shape); return keep[k]
+    kp = arr("kp_un", kp_un, KEYPOINT_DT, -1); fn = arr("linefn", linefn, np.float64, (-1, 3)); pc = arr("plane_coef", plane_coef, np.float32, (-1, 4))
+    px = arr("pt_xyz", pt_xyz, np.float32, (-1, 3)); lx = arr("ln_xyz", ln_xyz, np.float64, (-1, 6)); pw = arr("pl_coef_w", pl_coef_w, np.float32, (-1, 3, 4))
+    n = counts[0] if counts else (0 if kp is None else len(kp))
+    nl = counts[1] if counts else (0 if fn is None else len(fn))
+    m = counts[2] if counts else (0 if pc is None else len(pc))
+    arr("uright", uright, np.float32, n); arr("inv_sigma2", inv_sigma2, np.float32, n); arr("lines3d", lines3d, LINE3D_DT, nl)
+    if n and px is None: raise ValueError("pt_xyz is needed with points")
+    keep["pt_has"] = np.ones(n, np.uint8) if pt_has is None else np.ascontiguousarray(pt_has, np.uint8).reshape(n)
+    keep["ln_has"] = np.ones(nl, np.uint8) if ln_has is None else np.ascontiguousarray(ln_has, np.uint8).reshape(nl)
+    keep["pl_has"] = (np.ones((m, 3), np.uint8) if pw is not None else np.zeros((m, 3), np.uint8)) if pl_has is None else np.ascontiguousarray(pl_has, np.uint8).reshape(m, 3)
+    if pw is None: keep["pl_coef_w"] = np.zeros((m, 3, 4), np.float32)
+    if px is None: keep["pt_xyz"] = np.zeros((n, 3), np.float32)
+    if lx is None: keep["ln_xyz"] = np.zeros((nl, 6), np.float64)
+    for k, cnt in (("pt_xyz", n), ("ln_xyz", nl), ("pl_coef_w", m)):
+        if len(keep[k]) != cnt: raise ValueError("%s: %d rows for %d features" % (k, len(keep[k]), cnt))
+    P = PoseProblem()
+    P.Tcw[:] = np.ascontiguousarray(Tcw, np.float32).reshape(12).tolist()
+    P.n_points, P.n_lines, P.n_planes = n, nl, m
+    if plane_map is not None:
+        g = (lambda k: plane_match[k]) if isinstance(plane_match, dict) else (lambda k: getattr(plane_match, k))
+        for k in ("match", "parallel", "vertical"):
+            keep["slot_" + k] = np.ascontiguousarray(np.array(g(k), np.int32)[:m]) if m else np.zeros(0, np.int32)
+        P.plane_map = plane_map.h
+        keep["pl_has"] = np.stack([keep["slot_" + k] >= 0 for k in ("match", "parallel", "vertical")], axis=1).astype(np.uint8).reshape(m, 3)
+    for k, a in keep.items():
+        setattr(P, k, a.ctypes.data if a.size else None)
+    fl = dict(pt_outlier=np.zeros(n, np.uint8), ln_outlier=np.zeros(nl, np.uint8), pl_outlier=np.zeros((m, 3), np.uint8), vp_outlier=np.zeros(nl, np.uint8))
+    F = PoseFlags()
+    for k, a in fl.items():
+        setattr(F, k, a.ctypes.data if a.size else None)
+    return P, F, keep, fl
+
+
+def _pose_cam(cam):
+    c = PoseCamera()
+    c.fx, c.fy, c.cx, c.cy, c.bf = [float(v) for v in cam[:5]]
+    c.b = float(cam[5]) if len(cam) > 5 else 0.0
+    return c
+
+
+def _pose_pp(pp):
+    if pp is None: return None
+    return C.byref(pp if isinstance(pp, PosePlaneParams) else PosePlaneParams(**pp))
 
 
 def _th_arg(th):
@@ -247,6 +336,11 @@ def lib():
         L.hvo_search_lines_by_projection.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_stream_match_lines_geom.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.hvo_stream_search_lines_by_projection.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.hvo_pose_optimize.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.c_void_p, C.c_int, C.POINTER(PoseProblem), C.POINTER(PoseResult), C.POINTER(PoseFlags)]
+        L.hvo_batch_pose_optimize.argtypes = L.hvo_pose_optimize.argtypes
+        L.hvo_pose_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.hvo_stream_pose_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
+        L.hvo_stream_pose_optimize.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(PoseProblem), C.POINTER(PoseResult), C.POINTER(PoseFlags)]
         L.hvo_track_manhattan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MfResult), C.c_void_p, C.c_void_p]
         L.hvo_stream_track_manhattan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MfResult), C.c_void_p, C.c_void_p]
         L.hvo_batch_track_manhattan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -602,6 +696,38 @@ class Context:
         res = (MfResult * n)()
         self._chk(lib().hvo_batch_track_manhattan(self.h, n, _p(R), res), "batch_track_manhattan")
         return list(res)
+
+    def _pose_call(self, fn, what, cam, probs, plane_params, resident):
+        built = [_pose_problem(**p) for p in probs]
+        n = len(built)
+        P = (PoseProblem * n)(*[b[0] for b in built]); F = (PoseFlags * n)(*[b[1] for b in built]); R = (PoseResult * n)()
+        c = _pose_cam(cam)
+        self._chk(fn(self.h, C.byref(c), _pose_pp(plane_params), n, P, R, F), what)
+        out = []
+        for i in range(n):
+            r = PoseResult.from_buffer_copy(R[i])
+            for k, a in built[i][3].items(): setattr(r, k, a)
+            out.append(r)
+        return out
+
+    def pose_optimize(self, cam, problems, plane_params=None):
+        """Optimizer::PoseOptimization (src/Optimizer.cc:590-1478) of one problem (a dict of _pose_problem's keywords: Tcw, kp_un, uright,
+        inv_sigma2, linefn, lines3d, plane_coef, pt_has, pt_xyz, ln_has, ln_xyz, pl_has, pl_coef_w or plane_map + plane_match) or of a list of
+        them in one launch, one workgroup each -> PoseResult or list of PoseResult.  cam = (fx, fy, cx, cy, bf); plane_params: PosePlaneParams,
+        dict or None (TUM3.yaml)."""
+        single = isinstance(problems, dict)
+        out = self._pose_call(lib().hvo_pose_optimize, "pose_optimize", cam, [problems] if single else list(problems), plane_params, False)
+        return out[0] if single else out
+
+    def batch_pose_optimize(self, cam, problems, plane_params=None):
+        """the first len(problems) frames of the resident batch (needs STAGE_ORB, an LSD stage, STAGE_LINES3D, STAGE_PLANE_TAIL and depth), frame
+        k under problems[k]: a dict with Tcw, counts = (n_points, n_lines, n_planes) and the map side -> list of PoseResult"""
+        return self._pose_call(lib().hvo_batch_pose_optimize, "batch_pose_optimize", cam, list(problems), plane_params, True)
+
+    def pose_last_kernel_ms(self):
+        ms = C.c_float(0)
+        self._chk(lib().hvo_pose_last_kernel_ms(self.h, C.byref(ms)), "pose_last_kernel_ms")
+        return ms.value
 
     def match_planes(self, pmap, coef, Tcw, th=None, matrices=False):
         """PlaneMatcher::SearchMapByCoefficients (src/PlaneMatcher.cpp:10-68) of the frame planes coef ((n, 4) floats, camera frame) under the pose
@@ -1082,6 +1208,21 @@ class Stream:
         self._chk(lib().hvo_stream_track_manhattan(self.h, cur, _p(R), C.byref(res), _p(na) if axes else None, _p(la) if axes else None),
                   "stream_track_manhattan")
         return (res, na[:nn.value], la) if axes else res
+
+    def pose_optimize(self, cur, cam, Tcw, counts, plane_params=None, **map_side):
+        """Optimizer::PoseOptimization on the resident frame `cur` (needs STAGE_LINES3D, STAGE_PLANE_TAIL, bf > 0 and depth): only the pose and
+        the map side (pt_has, pt_xyz, ln_has, ln_xyz, pl_has, pl_coef_w, indexed by feature) go up.  counts = (n_points, n_lines, n_planes)
+        of those arrays -> PoseResult with the flag arrays."""
+        P, F, keep, fl = _pose_problem(Tcw, counts=tuple(int(v) for v in counts), **map_side)
+        c = _pose_cam(cam); r = PoseResult()
+        self._chk(lib().hvo_stream_pose_optimize(self.h, cur, C.byref(c), _pose_pp(plane_params), C.byref(P), C.byref(r), C.byref(F)), "stream_pose_optimize")
+        for k, a in fl.items(): setattr(r, k, a)
+        return r
+
+    def pose_last_kernel_ms(self, cur):
+        ms = C.c_float(0)
+        self._chk(lib().hvo_stream_pose_last_kernel_ms(self.h, cur, C.byref(ms)), "stream_pose_last_kernel_ms")
+        return ms.value
 
     def match_planes(self, pmap, cur, Tcw, th=None):
         """PlaneMatcher::SearchMapByCoefficients on the resident frame `cur` (needs STAGE_PLANE_TAIL and depth): the valid planes of its plane

@@ -149,6 +149,7 @@ void hvo_destroy(hvo_ctx *ctx)
     if (ctx->s_peac) (void)hipStreamDestroy(ctx->s_peac);
     if (ctx->ev_lsd_pre) (void)hipEventDestroy(ctx->ev_lsd_pre);
     if (ctx->ev_fast) (void)hipEventDestroy(ctx->ev_fast);
+    for (hipEvent_t e : ctx->po_ev) if (e) (void)hipEventDestroy(e);
     delete ctx;
 }
 
@@ -719,6 +720,56 @@ int hvo_batch_match_planes(hvo_ctx *ctx, hvo_plane_map *m, int n, const float *T
     const int rc = pa_match(ctx->stream, m, nullptr, 0, (const hvo_plane_cloud *)(d_out + L.pclouds), L.total, n, Tcw, th, res, nullptr, nullptr);
     if (rc) ctx->last_error = pa_map_error(m);
     return rc;
+}
+
+// Optimizer::PoseOptimization (Optimizer.cc:590-1478) of n problems on host arrays, one launch (pose_opt.hip)
+int hvo_pose_optimize(hvo_ctx *ctx, const hvo_camera *cam, const hvo_pose_plane_params *pp, int n, const hvo_pose_problem *prob,
+                      hvo_pose_result *res, const hvo_pose_flags *flags)
+{
+    if (!ctx || !cam || !prob || !res || n < 1) return HVO_ERR_INVALID_ARG;
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    float inv_s2[HVO_MAX_LEVELS];                                // mvInvLevelSigma2 (ORBextractor.cc:428-436)
+    for (int i = 0; i < HVO_MAX_LEVELS; i++) inv_s2[i] = i < ctx->p.orb_nlevels ? 1.0f / (ctx->scale[i] * ctx->scale[i]) : 1.0f;
+    return po_run(ctx, ctx->stream, cam, pp, inv_s2, n, prob, nullptr, res, flags, &ctx->last_error);
+}
+
+// the same on the first n frames of the resident batch: the frame side where the last hvo_batch_run left it, mvuRight formed in the kernel
+int hvo_batch_pose_optimize(hvo_ctx *ctx, const hvo_camera *cam, const hvo_pose_plane_params *pp, int n, const hvo_pose_problem *prob,
+                            hvo_pose_result *res, const hvo_pose_flags *flags)
+{
+    if (!ctx || !cam || !prob || !res || n < 1) return HVO_ERR_INVALID_ARG;
+    if (n > ctx->batch_n) { ctx->last_error = "pose optimisation: n beyond the resident batch"; return HVO_ERR_INVALID_ARG; }
+    const unsigned need = HVO_STAGE_ORB | HVO_STAGE_LSD | HVO_STAGE_LINES3D | HVO_STAGE_PLANE_TAIL;
+    if ((ctx->last_stages & need) != need) {
+        ctx->last_error = "pose optimisation: the last hvo_batch_run must include HVO_STAGE_ORB, an LSD stage, HVO_STAGE_LINES3D and HVO_STAGE_PLANE_TAIL"; return HVO_ERR_INVALID_ARG;
+    }
+    if (!ctx->have_depth) { ctx->last_error = "pose optimisation: the batch was uploaded without depth (no mvuRight, 3-D lines or planes)"; return HVO_ERR_INVALID_ARG; }
+    if (!(cam->bf > 0)) { ctx->last_error = "pose optimisation: bf <= 0 (no mvuRight)"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    char *d_out = nullptr; TailLayout L;
+    if (tail_batch_view(ctx, &d_out, &L)) { ctx->last_error = "pose optimisation: no resident tail results"; return HVO_ERR_INVALID_ARG; }
+    LsdView lv; PeacView pv; memset(&lv, 0, sizeof(lv)); memset(&pv, 0, sizeof(pv));
+    int rc;
+    if ((rc = lsd_prepare(ctx, ctx->batch_w, ctx->batch_h, std::max(n, ctx->p.max_batch), ctx->last_cull, &lv))) return rc;
+    if ((rc = peac_prepare(ctx, ctx->batch_w, ctx->batch_h, std::max(n, ctx->p.max_batch), &pv))) return rc;
+    std::vector<PoResident> R((size_t)n);
+    for (int f = 0; f < n; f++) {
+        PoResident &r = R[f];
+        r.kp_un = ctx->orb.d_kp + (size_t)f * ctx->orb.kp_cap; r.uright = nullptr; r.d_nkp = ctx->orb.d_nkp + f;
+        r.linefn = lv.d_fn + (size_t)f * lv.nfeat * 3; r.d_nkl = lv.d_nkl + f;
+        r.l3d = (const hvo_line3d *)(d_out + (size_t)f * L.total + L.lines3d); r.pclouds = (const hvo_plane_cloud *)(d_out + (size_t)f * L.total + L.pclouds);
+        r.depth = pv.d_depth + (size_t)f * pv.dframe; r.pitch = pv.pitch; r.w = ctx->batch_w; r.h = ctx->batch_h; r.dfac = ctx->p.depth_map_factor;
+    }
+    float inv_s2[HVO_MAX_LEVELS];
+    for (int i = 0; i < HVO_MAX_LEVELS; i++) inv_s2[i] = i < ctx->p.orb_nlevels ? 1.0f / (ctx->scale[i] * ctx->scale[i]) : 1.0f;
+    return po_run(ctx, ctx->stream, cam, pp, inv_s2, n, prob, R.data(), res, flags, &ctx->last_error);
+}
+
+int hvo_pose_last_kernel_ms(const hvo_ctx *ctx, float *ms)
+{
+    if (!ctx || !ms) return HVO_ERR_INVALID_ARG;
+    *ms = ctx->po_ms;
+    return HVO_OK;
 }
 
 // LSDmatcher::SearchDouble / SearchByDescriptor core (LSDmatcher.cpp:902-939): FrameBFMatch in both directions + mutual check

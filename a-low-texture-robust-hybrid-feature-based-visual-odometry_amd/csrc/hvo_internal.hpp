@@ -147,6 +147,7 @@ struct hvo_ctx {
     // staging arena of the host-array entry points of the Frame tail (hvo_lines_3d, hvo_vanishing_points, hvo_plane_clouds, ...): one
     // grow-only device buffer per context instead of hipMalloc / hipFree per call (hvo_call_arena)
     void *call_arena = nullptr; size_t call_arena_cap = 0;
+    hipEvent_t po_ev[2] = { nullptr, nullptr }; float po_ms = 0.f;   // pose_opt.hip: events around the last launch (hvo_pose_last_kernel_ms)
     void *tail = nullptr;                  // resident-batch Frame tail (tail.hip)
     // opaque per-subsystem state (peac.hip / lsd.hip own these)
     void *peac = nullptr;
@@ -429,6 +430,14 @@ int pa_match(hipStream_t st, hvo_plane_map *m, const float *coef, int n, const h
              const float th[4], hvo_plane_match *res, float *dist_mat, float *angle_mat);
 int pa_map_device(const hvo_plane_map *m);
 const char *pa_map_error(const hvo_plane_map *m);
+
+// pose_opt.hip: Optimizer::PoseOptimization of n frames in one launch on stream st, scratch from ctx's call arena; returns after the stream
+// has drained.  rsd null: prob's frame-side host arrays go up too; else frame f's frame side is read at rsd[f]'s device pointers.
+// depth set (resident batch, which holds no mvuRight): uright is null and the kernel forms mvuRight from the depth image like k_stereo_from_rgbd.
+struct PoResident { const hvo_keypoint *kp_un; const float *uright; const double *linefn; const hvo_line3d *l3d; const hvo_plane_cloud *pclouds; const int *d_nkp, *d_nkl;
+                    const uint16_t *depth; int pitch, w, h; float dfac; };
+int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_plane_params *pp, const float *inv_level_sigma2,
+           int n, const hvo_pose_problem *prob, const PoResident *rsd, hvo_pose_result *res, const hvo_pose_flags *flags, std::string *err);
 
 // peac.hip
 struct PeacView { uint16_t *d_depth; int pitch; size_t dframe; int8_t *d_labels8; hvo_plane *d_planes; int *d_meta; int npix, max_planes; size_t lstride /* bytes between two frames' label images */; };

@@ -839,4 +839,42 @@ int hvo_stream_match_planes(hvo_stream *s, hvo_plane_map *m, int64_t cur, const 
     return rc;
 }
 
+// Optimizer::PoseOptimization (src/Optimizer.cc:590-1478) on the resident frame `cur`: the frame side of every edge is read where the stages
+// left it; the pose and the map side go up.  Scratch: the slot's own context's call arena (grow-only).
+int hvo_stream_pose_optimize(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_pose_plane_params *pp, const hvo_pose_problem *prob,
+                             hvo_pose_result *res, const hvo_pose_flags *flags)
+{
+    if (!s || !cam || !prob || !res) return HVO_ERR_INVALID_ARG;
+    const unsigned need = HVO_STAGE_PLANE_TAIL | HVO_STAGE_LINES3D;
+    if ((s->tail_stages & need) != need || !(s->sp.stages & HVO_STAGE_ORB)) {
+        s->last_error = "pose optimisation: the stream must run HVO_STAGE_ORB, HVO_STAGE_LINES3D and HVO_STAGE_PLANE_TAIL"; return HVO_ERR_INVALID_ARG;
+    }
+    if (!(s->sp.bf > 0)) { s->last_error = "pose optimisation: the stream was created with bf <= 0 (no mvuRight)"; return HVO_ERR_INVALID_ARG; }
+    StreamSlot *B = slot_of(s, cur);
+    if (!B) { s->last_error = "pose optimisation: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    if (!B->had_depth) { s->last_error = "pose optimisation: the frame was submitted without depth (no mvuRight, 3-D lines or planes)"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    hipStream_t st = s->s_match;
+    ST_HIP(hipStreamWaitEvent(st, B->ev_orb, 0));
+    ST_HIP(hipStreamWaitEvent(st, B->ev_lsd, 0));
+    ST_HIP(hipStreamWaitEvent(st, B->ev_peac, 0));
+    hvo_ctx *c = B->ctx;
+    PoResident R;
+    R.kp_un = B->d_kp_un; R.uright = B->d_uright; R.linefn = B->lv.d_fn; R.l3d = (const hvo_line3d *)(B->d_tail + s->tl.lines3d);
+    R.pclouds = (const hvo_plane_cloud *)(B->d_tail + s->tl.pclouds); R.d_nkp = c->orb.d_nkp; R.d_nkl = B->lv.d_nkl;
+    R.depth = nullptr; R.pitch = R.w = R.h = 0; R.dfac = 0.f;      // the slot holds mvuRight
+    float inv_s2[HVO_MAX_LEVELS];
+    for (int i = 0; i < HVO_MAX_LEVELS; i++) inv_s2[i] = i < c->p.orb_nlevels ? 1.0f / (c->scale[i] * c->scale[i]) : 1.0f;
+    return po_run(c, st, cam, pp, inv_s2, 1, prob, &R, res, flags, &s->last_error);
+}
+
+int hvo_stream_pose_last_kernel_ms(hvo_stream *s, int64_t cur, float *ms)
+{
+    if (!s || !ms) return HVO_ERR_INVALID_ARG;
+    StreamSlot *B = slot_of(s, cur);
+    if (!B) { s->last_error = "pose optimisation: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    *ms = B->ctx->po_ms;
+    return HVO_OK;
+}
+
 }  // extern "C"

@@ -577,6 +577,88 @@ int hvo_stream_match_planes(hvo_stream *s, hvo_plane_map *m, int64_t cur, const 
  * sequence: the map's clouds are read once for all n frames.  res: n entries. */
 int hvo_batch_match_planes(hvo_ctx *ctx, hvo_plane_map *m, int n, const float *Tcw, const float th[4], hvo_plane_match *res);
 
+/* ---- Motion-only pose optimisation (csrc/pose_opt.hip) ----
+ * Optimizer::PoseOptimization(Frame *) of the RGB-D tracker (reference src/Optimizer.cc:590-1478; called from src/Tracking.cc:2026, :2418, :2836
+ * and :3859-3890): one SE3 vertex, and in the reference's insertion order the edges EdgeSE3ProjectXYZOnlyPose (mvuRight < 0) /
+ * EdgeStereoSE3ProjectXYZOnlyPose per matched point, two DistPt2Line2DMultiFrameOnlyPose per matched line (start, end), DistVp2VpOnlyPose per
+ * matched line whose 3-D direction and map direction have no zero component, EdgePlaneOnlyPose / EdgeParallelPlaneOnlyPose /
+ * EdgeVerticalPlaneOnlyPose per frame plane and role; g2o's numeric Jacobians (central differences, 1e-9), Huber kernels, the dense 6 x 6 solve
+ * and the Levenberg loop, four rounds from the initial pose with the outlier classification between them -- one kernel launch, one workgroup
+ * per frame, all arithmetic in double.  Bit parity with g2o is not claimed (libm, a 1e-9 difference quotient); DESIGN.md section 7 lists the
+ * readings.  Defined where the reference is not: an evaluation of DistVp2VpOnlyPose that takes its early return (a direction with z == 0)
+ * contributes error 0 -- the reference keeps a stale or uninitialised _error -- and the edge is flagged in vp_outlier when a round's
+ * classification reads that evaluation.  At most 8192 points, 4096 lines and 64 planes per frame (HVO_ERR_UNSUPPORTED).
+ * The vanishing-direction measurement is B - A of the line's hvo_line3d record whatever its `good` flag: mvLines3D[i] holds the fitted pair
+ * for every key line, and a record without a fit holds A = B = 0 (hvo_lines_3d), so Optimizer.cc:827 drops that edge here as there; a fitted
+ * line shorter than 0.02 (good == 0) keeps its edge, as in the reference, which does not consult mVF3DLines.
+ * A pose that is not finite in any of the n problems makes the call return HVO_ERR_INVALID_ARG before anything is launched or written. */
+typedef struct { double angle_info, distance_info, parallel_info, vertical_info, chi, vp_chi; } hvo_pose_plane_params;   /* Plane.AngleInfo .. Plane.VPChi of the settings file */
+typedef struct {
+    float   Tcw[12];              /* pFrame->mTcw, rows 0..2, row-major 3 x 4 */
+    int32_t n_points, n_lines, n_planes, reserved;   /* N, NL, mnPlaneNum: the lengths of the arrays below */
+    /* frame side (host arrays; ignored by hvo_stream_pose_optimize, which reads the resident frame) */
+    const hvo_keypoint *kp_un;    /* mvKeysUn: x, y, octave are read */
+    const float  *uright;         /* mvuRight (NULL: every point monocular) */
+    const float  *inv_sigma2;     /* mvInvLevelSigma2[octave] per point (NULL: the context's level table by octave) */
+    const double *linefn;         /* mvKeyLineFunctions, n_lines x 3 */
+    const hvo_line3d *lines3d;    /* mvLines3D: A = first, B = second are read */
+    const float  *plane_coef;     /* mvPlaneCoefficients, n_planes x 4 */
+    /* map side, indexed by feature */
+    const uint8_t *pt_has;        /* mvpMapPoints[i] != NULL */
+    const float  *pt_xyz;         /* GetWorldPos(), n_points x 3 */
+    const uint8_t *ln_has;        /* mvpMapLines[i] != NULL */
+    const double *ln_xyz;         /* mWorldPos (start, end), n_lines x 6 */
+    const uint8_t *pl_has;        /* n_planes x 3: mvpMapPlanes[i], mvpParallelPlanes[i], mvpVerticalPlanes[i] != NULL */
+    const float  *pl_coef_w;      /* their GetWorldPos(), n_planes x 3 x 4 */
+    /* or the plane side as slots of a resident plane map, so that an hvo_plane_match passes on as it is (match, parallel, vertical of the
+     * result; -1 = none; a NULL array = no plane of that role): when plane_map is set, pl_has / pl_coef_w are not read and the slots'
+     * coefficients are taken from the map as it stands at the call */
+    const hvo_plane_map *plane_map;
+    const int32_t *slot_match, *slot_parallel, *slot_vertical;
+} hvo_pose_problem;
+typedef struct {                  /* each pointer may be NULL; an entry is written only where there is a correspondence, like the reference */
+    uint8_t *pt_outlier;          /* mvbOutlier, n_points */
+    uint8_t *ln_outlier;          /* mvbLineOutlier, n_lines */
+    uint8_t *pl_outlier;          /* mvbPlaneOutlier / mvbParPlaneOutlier / mvbVerPlaneOutlier, n_planes x 3 */
+    uint8_t *vp_outlier;          /* the function's local VpOutlier, n_lines (every entry written) */
+} hvo_pose_flags;
+typedef struct {
+    double  Tcw_d[12];            /* the optimised pose in double */
+    float   Tcw[12];              /* as SetPose receives it (Converter::toCvMat: float); the initial pose when ret == 0 by too few correspondences */
+    int32_t ret;                  /* the return value nInitialCorrespondences - nBad - nLineBad; 0 with fewer than 3 correspondences */
+    int32_t n_initial, n_bad, n_line_bad;
+    int32_t n_edges;              /* optimizer.edges().size() */
+    int32_t rounds;               /* rounds run (1 when the graph has fewer than 10 edges) */
+    int32_t iterations[4], trials[4];   /* per round: solve() calls, Levenberg trials */
+    int32_t status;               /* HVO_OK for every problem the kernel ran */
+    int32_t reserved;
+    double  lambda[4], chi2[4];   /* per round: the final lambda and the final active robust chi2 */
+} hvo_pose_result;
+/* On host arrays, n problems in one launch (one workgroup each); pp NULL = TUM3.yaml's { 0.5, 50, 0.1, 0.1, 100, 50 }.  res: n entries;
+ * flags: n entries or NULL.  A problem equals the single call on it bit for bit. */
+int hvo_pose_optimize(hvo_ctx *ctx, const hvo_camera *cam, const hvo_pose_plane_params *pp, int n, const hvo_pose_problem *prob,
+                      hvo_pose_result *res, const hvo_pose_flags *flags);
+/* On the resident frame `cur`: undistorted key points, mvuRight, octaves, key-line functions, 3-D lines and the valid plane records are read
+ * where the stages left them; only the pose and the map side of `prob` go up (its frame-side pointers are ignored; n_points / n_lines are
+ * capped by the frame's counts, frame plane i = the i-th valid hvo_plane_cloud record as in hvo_plane_match).  The stream must run
+ * HVO_STAGE_LINES3D and HVO_STAGE_PLANE_TAIL with bf > 0 and the frame must have been submitted with depth, else HVO_ERR_INVALID_ARG with
+ * hvo_stream_last_error set.  The same bytes on host arrays through hvo_pose_optimize give the same result bit for bit. */
+int hvo_stream_pose_optimize(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_pose_plane_params *pp, const hvo_pose_problem *prob,
+                             hvo_pose_result *res, const hvo_pose_flags *flags);
+
+/* On the first n frames of the resident batch (after hvo_batch_run with HVO_STAGE_ORB, an LSD stage, HVO_STAGE_LINES3D and
+ * HVO_STAGE_PLANE_TAIL on frames uploaded with depth), frame k under prob[k]'s pose and map side, in one launch.  A batch context carries no
+ * distortion (k1 = 0: mvKeysUn = mvKeys, Frame.cc:1703-1707) and keeps no mvuRight: the kernel forms it per point from the resident depth
+ * image exactly as Frame::ComputeStereoFromRGBD / hvo_stereo_from_rgbd do, with cam->bf (> 0) and the context's depth_map_factor.  Frame k
+ * equals the stream form on the same image, pose and map side bit for bit.  n beyond the batch, a missing stage or no depth:
+ * HVO_ERR_INVALID_ARG with hvo_last_error set. */
+int hvo_batch_pose_optimize(hvo_ctx *ctx, const hvo_camera *cam, const hvo_pose_plane_params *pp, int n, const hvo_pose_problem *prob,
+                            hvo_pose_result *res, const hvo_pose_flags *flags);
+/* device time of the kernel launch of the last hvo_pose_optimize / hvo_batch_pose_optimize of this context, or of the last
+ * hvo_stream_pose_optimize on frame `cur` of the stream (hipEvents around the launch; uploads and downloads not included), in ms */
+int hvo_pose_last_kernel_ms(const hvo_ctx *ctx, float *ms);
+int hvo_stream_pose_last_kernel_ms(hvo_stream *s, int64_t cur, float *ms);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer.  Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

@@ -571,4 +571,47 @@ private:
     float th_[4];
 };
 
+// Optimizer (include/Optimizer.h, src/Optimizer.cc:590-1478): PoseOptimization on the mirror's frame handle.  The map side (one row per feature:
+// the matched map point's / map line's world position, the planes of the three roles as world coefficients or as slots of a PlaneMap) is what
+// the tracker fills from mvpMapPoints / mvpMapLines / mvpMapPlanes...; the frame side is read from the resident frame.  The optimised pose comes
+// back in res.Tcw (what SetPose receives), the flags in `flags`; the return value is the reference's.
+struct PoseMapSide {
+    int n_points = 0, n_lines = 0, n_planes = 0;
+    const uint8_t *pt_has = nullptr; const float *pt_xyz = nullptr;
+    const uint8_t *ln_has = nullptr; const double *ln_xyz = nullptr;
+    const uint8_t *pl_has = nullptr; const float *pl_coef_w = nullptr;
+    const PlaneMap *plane_map = nullptr; const hvo_plane_match *plane_match = nullptr;    // instead of pl_has / pl_coef_w
+    hvo_pose_flags flags = { nullptr, nullptr, nullptr, nullptr };
+};
+class Optimizer {
+public:
+    explicit Optimizer(const hvo_camera &cam, const hvo_pose_plane_params *pp = nullptr) : cam_(cam), has_pp_(pp != nullptr) { if (pp) pp_ = *pp; }
+    // int nInliers = Optimizer::PoseOptimization(&mCurrentFrame)  becomes  optimizer.PoseOptimization(fs, ticket, Tcw, side, res)
+    int PoseOptimization(FrameStream &fs, int64_t cur, const float Tcw[12], const PoseMapSide &m, hvo_pose_result &res) const
+    {
+        hvo_pose_problem p = fill(Tcw, m);
+        check(hvo_stream_pose_optimize(fs.get(), cur, &cam_, has_pp_ ? &pp_ : nullptr, &p, &res, &m.flags), "hvo_stream_pose_optimize");
+        return res.ret;
+    }
+    // on host arrays: p carries the frame side too
+    int PoseOptimization(hvo_ctx *ctx, const hvo_pose_problem &p, hvo_pose_result &res, const hvo_pose_flags *flags = nullptr) const
+    {
+        check(hvo_pose_optimize(ctx, &cam_, has_pp_ ? &pp_ : nullptr, 1, &p, &res, flags), "hvo_pose_optimize");
+        return res.ret;
+    }
+private:
+    static hvo_pose_problem fill(const float Tcw[12], const PoseMapSide &m)
+    {
+        hvo_pose_problem p = {};
+        for (int i = 0; i < 12; i++) p.Tcw[i] = Tcw[i];
+        p.n_points = m.n_points; p.n_lines = m.n_lines; p.n_planes = m.n_planes;
+        p.pt_has = m.pt_has; p.pt_xyz = m.pt_xyz; p.ln_has = m.ln_has; p.ln_xyz = m.ln_xyz; p.pl_has = m.pl_has; p.pl_coef_w = m.pl_coef_w;
+        if (m.plane_map && m.plane_match) {
+            p.plane_map = m.plane_map->get(); p.slot_match = m.plane_match->match; p.slot_parallel = m.plane_match->parallel; p.slot_vertical = m.plane_match->vertical;
+        }
+        return p;
+    }
+    hvo_camera cam_; hvo_pose_plane_params pp_ = { 0.5, 50.0, 0.1, 0.1, 100.0, 50.0 }; bool has_pp_;
+};
+
 }  // namespace hvo
