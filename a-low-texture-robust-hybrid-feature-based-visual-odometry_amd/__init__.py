@@ -77,6 +77,8 @@ EXPORTS = [
     "hvo_track_manhattan", "hvo_stream_track_manhattan", "hvo_batch_track_manhattan",
     "hvo_plane_map_create", "hvo_plane_map_destroy", "hvo_plane_map_set", "hvo_plane_map_set_bad", "hvo_plane_map_counts", "hvo_plane_map_slot",
     "hvo_plane_map_last_error", "hvo_match_planes", "hvo_stream_match_planes", "hvo_batch_match_planes", "hvo_pose_optimize", "hvo_stream_pose_optimize", "hvo_batch_pose_optimize", "hvo_pose_last_kernel_ms", "hvo_stream_pose_last_kernel_ms",
+    "hvo_line_struct_default_params", "hvo_line_struct_optimize", "hvo_stream_line_struct_optimize", "hvo_batch_line_struct_optimize",
+    "hvo_line_opt_last_kernel_ms", "hvo_stream_line_opt_last_kernel_ms",
 ]
 
 
@@ -187,6 +189,55 @@ class PoseResult(C.Structure):
         for k in ("pt_outlier", "ln_outlier", "pl_outlier", "vp_outlier"):
             if hasattr(self, k): d[k] = getattr(self, k)
         return d
+
+
+LINE_STRUCT_CONSTRAINTS, LINE_STRUCT_OPTIMIZE = 1, 2
+LINE_STRUCT_ROW_UNSET, LINE_STRUCT_ROW_Z0 = 0, 1
+
+
+class LineStructParams(C.Structure):
+    """hvo_line_struct_params: the thresholds of Manhattan::computeStructConstrains and the constants of Optimizer::LineOptStruct"""
+    _fields_ = [("cos_par", C.c_double), ("cos_perp", C.c_double), ("huber_delta", C.c_double), ("chi2_reject", C.c_double),
+                ("chi2_round", C.c_float * 2), ("min_constraints", C.c_int32), ("iterations", C.c_int32), ("row_rule", C.c_int32), ("mode", C.c_uint32)]
+
+
+class LineStructProblem(C.Structure):
+    _fields_ = [("n_lines", C.c_int32), ("reserved", C.c_int32), ("linefn", C.c_void_p), ("lines3d", C.c_void_p)]
+
+
+class LineOptResult(C.Structure):
+    """hvo_line_opt_result; the binding hangs rel (n x n int8) and lines (n x 6 doubles: A, B after the call) on it"""
+    _fields_ = [("n_lines", C.c_int32), ("n_lines_to_opt", C.c_int32), ("n_edges", C.c_int32), ("n_par_edges", C.c_int32), ("n_perp_edges", C.c_int32),
+                ("rounds", C.c_int32), ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2), ("n_flagged", C.c_int32 * 2),
+                ("written_back", C.c_int32), ("status", C.c_int32), ("lam", C.c_double * 2), ("chi2", C.c_double * 2)]
+
+
+assert C.sizeof(LineStructParams) == 56 and C.sizeof(LineStructProblem) == 24 and C.sizeof(LineOptResult) == 88
+
+
+def line_struct_params(**kw):
+    """the reference's values (hvo_line_struct_default_params) with the given fields replaced (mode, row_rule, ...)"""
+    p = LineStructParams()
+    lib().hvo_line_struct_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "chi2_round": p.chi2_round[0], p.chi2_round[1] = v
+        else: setattr(p, k, v)
+    return p
+
+
+def _ls_params(params, mode, row_rule):
+    p = line_struct_params() if params is None else (params if isinstance(params, LineStructParams) else line_struct_params(**params))
+    if mode is not None: p.mode = mode
+    if row_rule is not None: p.row_rule = row_rule
+    return p
+
+
+def rel_lists(rel_row):
+    """(mvParLinesIdx[k], mvPerpLinesIdx[k]) of one row of the relation matrix: partner indices in ascending order, -1 where LineOptStruct
+    rejected the constraint (the slot is kept)"""
+    r = np.asarray(rel_row)
+    ip, iq = np.nonzero(np.abs(r) == 1)[0], np.nonzero(np.abs(r) == 2)[0]
+    return np.where(r[ip] > 0, ip, -1).tolist(), np.where(r[iq] > 0, iq, -1).tolist()
 
 
 def _pose_problem(Tcw, kp_un=None, uright=None, inv_sigma2=None, linefn=None, lines3d=None, plane_coef=None,
@@ -341,6 +392,12 @@ def lib():
         L.hvo_pose_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.hvo_stream_pose_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
         L.hvo_stream_pose_optimize.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(PoseProblem), C.POINTER(PoseResult), C.POINTER(PoseFlags)]
+        L.hvo_line_struct_default_params.argtypes = [C.POINTER(LineStructParams)]
+        L.hvo_line_struct_optimize.argtypes = [C.c_void_p, C.POINTER(LineStructParams), C.c_int, C.POINTER(LineStructProblem), C.c_void_p, C.c_void_p, C.POINTER(LineOptResult)]
+        L.hvo_batch_line_struct_optimize.argtypes = [C.c_void_p, C.POINTER(LineStructParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LineOptResult)]
+        L.hvo_stream_line_struct_optimize.argtypes = [C.c_void_p, C.c_int64, C.POINTER(LineStructParams), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(LineOptResult)]
+        L.hvo_line_opt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.hvo_stream_line_opt_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
         L.hvo_track_manhattan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MfResult), C.c_void_p, C.c_void_p]
         L.hvo_stream_track_manhattan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MfResult), C.c_void_p, C.c_void_p]
         L.hvo_batch_track_manhattan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -723,6 +780,54 @@ class Context:
         """the first len(problems) frames of the resident batch (needs STAGE_ORB, an LSD stage, STAGE_LINES3D, STAGE_PLANE_TAIL and depth), frame
         k under problems[k]: a dict with Tcw, counts = (n_points, n_lines, n_planes) and the map side -> list of PoseResult"""
         return self._pose_call(lib().hvo_batch_pose_optimize, "batch_pose_optimize", cam, list(problems), plane_params, True)
+
+    def _ls_call(self, fn, what, p, sizes, probs, rels):
+        n = len(sizes)
+        rel = [np.zeros((c, c), np.int8) if r is None else np.ascontiguousarray(r, np.int8).reshape(c, c).copy() for c, r in zip(sizes, rels)]
+        out = [np.zeros((c, 6), np.float64) for c in sizes]
+        RP = (C.c_void_p * n)(*[r.ctypes.data for r in rel]); OP = (C.c_void_p * n)(*[o.ctypes.data for o in out]); R = (LineOptResult * n)()
+        if probs is None:
+            nl = np.array(sizes, np.int32)
+            self._chk(fn(self.h, C.byref(p), n, _p(nl), RP, OP, R), what)
+        else:
+            self._chk(fn(self.h, C.byref(p), n, probs, RP, OP, R), what)
+        res = []
+        for i in range(n):
+            r = LineOptResult.from_buffer_copy(R[i]); r.rel = rel[i]; r.lines = out[i]; res.append(r)
+        return res
+
+    def line_struct_optimize(self, problems, params=None, mode=None, row_rule=None):
+        """Manhattan::computeStructConstrains for every key line and Optimizer::LineOptStruct (src/Tracking.cc:270-335) of one problem or a list
+        of problems in one launch sequence.  A problem is a dict: linefn (n x 3 doubles, mvKeyLineFunctions; needed for part 1), lines3d
+        (LINE3D_DT: A, B, line_eq are read), rel (n x n int8; needed when mode is LINE_STRUCT_OPTIMIZE alone).  mode: LINE_STRUCT_CONSTRAINTS,
+        LINE_STRUCT_OPTIMIZE or both (default); row_rule: LINE_STRUCT_ROW_UNSET (default) / LINE_STRUCT_ROW_Z0 -> LineOptResult (or a list) with
+        .rel (0 none, 1 parallel, 2 perpendicular, negative = rejected) and .lines (n x 6: A, B after the call)."""
+        single = isinstance(problems, dict)
+        probs = [problems] if single else list(problems)
+        p = _ls_params(params, mode, row_rule)
+        keep, P = [], (LineStructProblem * len(probs))()
+        for i, d in enumerate(probs):
+            l3 = np.ascontiguousarray(d["lines3d"], LINE3D_DT).reshape(-1)
+            fn = None if d.get("linefn") is None else np.ascontiguousarray(d["linefn"], np.float64).reshape(-1, 3)
+            if fn is not None and len(fn) != len(l3): raise ValueError("linefn: %d rows for %d lines" % (len(fn), len(l3)))
+            if not (p.mode & LINE_STRUCT_CONSTRAINTS) and d.get("rel") is None: raise ValueError("rel is needed without LINE_STRUCT_CONSTRAINTS")
+            keep += [l3, fn]
+            P[i].n_lines = len(l3); P[i].lines3d = l3.ctypes.data if len(l3) else None; P[i].linefn = fn.ctypes.data if fn is not None and len(fn) else None
+        out = self._ls_call(lib().hvo_line_struct_optimize, "line_struct_optimize", p, [int(q.n_lines) for q in P], P, [d.get("rel") for d in probs])
+        return out[0] if single else out
+
+    def batch_line_struct_optimize(self, n_lines, params=None, mode=None, row_rule=None, rel=None):
+        """the same on the first len(n_lines) frames of the resident batch (needs an LSD stage, STAGE_LINES3D and depth): n_lines[k] is frame
+        k's key-line count; A, B of the resident 3-D line records are rewritten -> list of LineOptResult"""
+        sizes = [int(v) for v in n_lines]
+        return self._ls_call(lib().hvo_batch_line_struct_optimize, "batch_line_struct_optimize", _ls_params(params, mode, row_rule), sizes, None,
+                             rel if rel is not None else [None] * len(sizes))
+
+    def line_opt_last_kernel_ms(self):
+        """(pair pass, optimisation) device time of the last line_struct_optimize / batch_line_struct_optimize in ms"""
+        ms = (C.c_float * 2)()
+        self._chk(lib().hvo_line_opt_last_kernel_ms(self.h, ms), "line_opt_last_kernel_ms")
+        return ms[0], ms[1]
 
     def pose_last_kernel_ms(self):
         ms = C.c_float(0)
@@ -1218,6 +1323,22 @@ class Stream:
         self._chk(lib().hvo_stream_pose_optimize(self.h, cur, C.byref(c), _pose_pp(plane_params), C.byref(P), C.byref(r), C.byref(F)), "stream_pose_optimize")
         for k, a in fl.items(): setattr(r, k, a)
         return r
+
+    def line_struct_optimize(self, cur, n_lines, params=None, mode=None, row_rule=None, rel=None):
+        """Manhattan::computeStructConstrains + Optimizer::LineOptStruct on the resident frame `cur` (needs an LSD stage, STAGE_LINES3D and
+        depth): n_lines is the frame's key-line count; A, B of the resident 3-D line records are rewritten, so a following pose_optimize or
+        search_lines_by_projection_map on the frame sees the optimised lines -> LineOptResult with .rel and .lines"""
+        c = int(n_lines); p = _ls_params(params, mode, row_rule)
+        r_ = np.zeros((c, c), np.int8) if rel is None else np.ascontiguousarray(rel, np.int8).reshape(c, c).copy()
+        out = np.zeros((c, 6), np.float64); r = LineOptResult()
+        self._chk(lib().hvo_stream_line_struct_optimize(self.h, cur, C.byref(p), c, _p(r_), _p(out), C.byref(r)), "stream_line_struct_optimize")
+        r.rel = r_; r.lines = out
+        return r
+
+    def line_opt_last_kernel_ms(self, cur):
+        ms = (C.c_float * 2)()
+        self._chk(lib().hvo_stream_line_opt_last_kernel_ms(self.h, cur, ms), "stream_line_opt_last_kernel_ms")
+        return ms[0], ms[1]
 
     def pose_last_kernel_ms(self, cur):
         ms = C.c_float(0)

@@ -150,6 +150,7 @@ void hvo_destroy(hvo_ctx *ctx)
     if (ctx->ev_lsd_pre) (void)hipEventDestroy(ctx->ev_lsd_pre);
     if (ctx->ev_fast) (void)hipEventDestroy(ctx->ev_fast);
     for (hipEvent_t e : ctx->po_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->ls_ev) if (e) (void)hipEventDestroy(e);
     delete ctx;
 }
 
@@ -374,6 +375,7 @@ int hvo_batch_run(hvo_ctx *ctx, unsigned stages)
     if (want_lsd) ctx->last_stages = (ctx->last_stages & ~(HVO_STAGE_LSD | HVO_STAGE_LSD_CULL)) | HVO_STAGE_LSD | (want_cull ? HVO_STAGE_LSD_CULL : 0u);
     // the rest of the Frame constructor on the resident results (tail.hip)
     ctx->last_stages &= ~(HVO_STAGE_LINES3D | HVO_STAGE_VP | HVO_STAGE_PLANE_TAIL | HVO_STAGE_GRIDS);
+    ctx->ls_batch_done = false;
     return tail_batch_run(ctx, stages);
 }
 
@@ -763,6 +765,55 @@ int hvo_batch_pose_optimize(hvo_ctx *ctx, const hvo_camera *cam, const hvo_pose_
     float inv_s2[HVO_MAX_LEVELS];
     for (int i = 0; i < HVO_MAX_LEVELS; i++) inv_s2[i] = i < ctx->p.orb_nlevels ? 1.0f / (ctx->scale[i] * ctx->scale[i]) : 1.0f;
     return po_run(ctx, ctx->stream, cam, pp, inv_s2, n, prob, R.data(), res, flags, &ctx->last_error);
+}
+
+// Manhattan::computeStructConstrains for every key line + Optimizer::LineOptStruct (Tracking.cc:270-335) of n problems on host arrays (line_opt.hip)
+int hvo_line_struct_optimize(hvo_ctx *ctx, const hvo_line_struct_params *params, int n_frames, const hvo_line_struct_problem *problems,
+                             int8_t *const *rel, double *const *l3d_out, hvo_line_opt_result *res)
+{
+    if (!ctx || !problems || !rel || !res || n_frames < 1) return HVO_ERR_INVALID_ARG;
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    std::vector<int32_t> nl((size_t)n_frames);
+    for (int f = 0; f < n_frames; f++) nl[f] = problems[f].n_lines;
+    return ls_run(ctx, ctx->stream, params, n_frames, nl.data(), problems, nullptr, rel, l3d_out, res, &ctx->last_error);
+}
+
+// the same on the first n frames of the resident batch: key-line functions and 3-D lines where the last hvo_batch_run left them; A, B of the
+// resident records are rewritten
+int hvo_batch_line_struct_optimize(hvo_ctx *ctx, const hvo_line_struct_params *params, int n, const int32_t *n_lines, int8_t *const *rel,
+                                   double *const *l3d_out, hvo_line_opt_result *res)
+{
+    if (!ctx || !n_lines || !rel || !res || n < 1) return HVO_ERR_INVALID_ARG;
+    if (n > ctx->batch_n) { ctx->last_error = "line structure: n beyond the resident batch"; return HVO_ERR_INVALID_ARG; }
+    const unsigned need = HVO_STAGE_LSD | HVO_STAGE_LINES3D;
+    if ((ctx->last_stages & need) != need) {
+        ctx->last_error = "line structure: the last hvo_batch_run must include an LSD stage and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
+    }
+    if (!ctx->have_depth) { ctx->last_error = "line structure: the batch was uploaded without depth (no 3-D lines)"; return HVO_ERR_INVALID_ARG; }
+    const bool opt = !params || (params->mode & HVO_LINE_STRUCT_OPTIMIZE);
+    if (opt && ctx->ls_batch_done) { ctx->last_error = "line structure: the resident batch's 3-D lines have been optimised already"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    char *d_out = nullptr; TailLayout L;
+    if (tail_batch_view(ctx, &d_out, &L)) { ctx->last_error = "line structure: no resident tail results"; return HVO_ERR_INVALID_ARG; }
+    LsdView lv; memset(&lv, 0, sizeof(lv));
+    int rc;
+    if ((rc = lsd_prepare(ctx, ctx->batch_w, ctx->batch_h, std::max(n, ctx->p.max_batch), ctx->last_cull, &lv))) return rc;
+    for (int f = 0; f < n; f++) if (n_lines[f] > lv.nfeat) { ctx->last_error = "line structure: n_lines beyond the key-line capacity"; return HVO_ERR_INVALID_ARG; }
+    std::vector<LsResident> R((size_t)n);
+    for (int f = 0; f < n; f++) {
+        R[f].linefn = lv.d_fn + (size_t)f * lv.nfeat * 3; R[f].d_nkl = lv.d_nkl + f;
+        R[f].l3d = (hvo_line3d *)(d_out + (size_t)f * L.total + L.lines3d);
+    }
+    rc = ls_run(ctx, ctx->stream, params, n, n_lines, nullptr, R.data(), rel, l3d_out, res, &ctx->last_error);
+    if (rc == HVO_OK && opt) ctx->ls_batch_done = true;
+    return rc;
+}
+
+int hvo_line_opt_last_kernel_ms(const hvo_ctx *ctx, float ms2[2])
+{
+    if (!ctx || !ms2) return HVO_ERR_INVALID_ARG;
+    ms2[0] = ctx->ls_ms[0]; ms2[1] = ctx->ls_ms[1];
+    return HVO_OK;
 }
 
 int hvo_pose_last_kernel_ms(const hvo_ctx *ctx, float *ms)

@@ -148,6 +148,8 @@ struct hvo_ctx {
     // grow-only device buffer per context instead of hipMalloc / hipFree per call (hvo_call_arena)
     void *call_arena = nullptr; size_t call_arena_cap = 0;
     hipEvent_t po_ev[2] = { nullptr, nullptr }; float po_ms = 0.f;   // pose_opt.hip: events around the last launch (hvo_pose_last_kernel_ms)
+    hipEvent_t ls_ev[3] = { nullptr, nullptr, nullptr }; float ls_ms[2] = { 0.f, 0.f };   // line_opt.hip: events around the last call's two launches
+    bool ls_batch_done = false;            // hvo_batch_line_struct_optimize has optimised the resident batch's 3-D lines (cleared by hvo_batch_run)
     void *tail = nullptr;                  // resident-batch Frame tail (tail.hip)
     // opaque per-subsystem state (peac.hip / lsd.hip own these)
     void *peac = nullptr;
@@ -438,6 +440,13 @@ struct PoResident { const hvo_keypoint *kp_un; const float *uright; const double
                     const uint16_t *depth; int pitch, w, h; float dfac; };
 int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_plane_params *pp, const float *inv_level_sigma2,
            int n, const hvo_pose_problem *prob, const PoResident *rsd, hvo_pose_result *res, const hvo_pose_flags *flags, std::string *err);
+
+// line_opt.hip: computeStructConstrains + LineOptStruct of n frames on stream st (one pair-pass launch, one optimisation launch), scratch from
+// ctx's call arena; returns after the stream has drained.  rsd null: prob's host arrays go up; else frame f reads (and part 2 rewrites A, B of)
+// the resident records at rsd[f].  n_lines[f] is the side of rel[f].
+struct LsResident { const double *linefn; hvo_line3d *l3d; const int *d_nkl; };
+int ls_run(hvo_ctx *ctx, hipStream_t st, const hvo_line_struct_params *params, int n, const int32_t *n_lines, const hvo_line_struct_problem *prob,
+           const LsResident *rsd, int8_t *const *rel, double *const *l3d_out, hvo_line_opt_result *res, std::string *err);
 
 // peac.hip
 struct PeacView { uint16_t *d_depth; int pitch; size_t dframe; int8_t *d_labels8; hvo_plane *d_planes; int *d_meta; int npix, max_planes; size_t lstride /* bytes between two frames' label images */; };

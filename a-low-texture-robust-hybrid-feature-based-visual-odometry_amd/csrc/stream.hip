@@ -32,6 +32,7 @@ struct StreamSlot {
     hipEvent_t ev_kern[3] = { nullptr, nullptr, nullptr };      // kernels done (before the downloads), per subsystem: latency accounting
     hipEvent_t ev_t0 = nullptr;
     int64_t ticket = -1; bool busy = false, had_depth = false;
+    bool line_opt_done = false;            // hvo_stream_line_struct_optimize has rewritten this frame's 3-D lines
 };
 
 // layout of a slot's pinned result block
@@ -243,7 +244,7 @@ static int stream_submit_enqueue(hvo_stream *s, StreamSlot &S, const uint8_t *gr
         ST_HIP(hipMemcpy2DAsync(S.pv.d_depth, S.pv.pitch * sizeof(uint16_t), S.h_depth, (size_t)w * 2, (size_t)w * 2, h, hipMemcpyHostToDevice, c->s_peac));
         ST_HIP(hipEventRecord(S.ev_depth, c->s_peac));
     }
-    S.had_depth = depth != nullptr;
+    S.had_depth = depth != nullptr; S.line_opt_done = false;
     char *ho = S.h_out;
     const OutLayout &L = s->lay;
     int *hc = (int *)(ho + L.counts);
@@ -866,6 +867,42 @@ int hvo_stream_pose_optimize(hvo_stream *s, int64_t cur, const hvo_camera *cam, 
     float inv_s2[HVO_MAX_LEVELS];
     for (int i = 0; i < HVO_MAX_LEVELS; i++) inv_s2[i] = i < c->p.orb_nlevels ? 1.0f / (c->scale[i] * c->scale[i]) : 1.0f;
     return po_run(c, st, cam, pp, inv_s2, 1, prob, &R, res, flags, &s->last_error);
+}
+
+// Manhattan::computeStructConstrains for every key line + Optimizer::LineOptStruct (src/Tracking.cc:270-335) on the resident frame `cur`:
+// key-line functions and 3-D lines are read where the stages left them, A and B of the resident records are rewritten
+int hvo_stream_line_struct_optimize(hvo_stream *s, int64_t cur, const hvo_line_struct_params *params, int n_lines, int8_t *rel,
+                                    double *l3d_out, hvo_line_opt_result *res)
+{
+    if (!s || !res || n_lines < 0 || (n_lines && !rel)) return HVO_ERR_INVALID_ARG;
+    if (n_lines > s->nfeat && n_lines <= 4096) { s->last_error = "line structure: n_lines beyond the key-line capacity"; return HVO_ERR_INVALID_ARG; }
+    if (!(s->sp.stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL)) || !(s->tail_stages & HVO_STAGE_LINES3D)) {
+        s->last_error = "line structure: the stream must run an LSD stage and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
+    }
+    StreamSlot *B = slot_of(s, cur);
+    if (!B) { s->last_error = "line structure: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    if (!B->had_depth) { s->last_error = "line structure: the frame was submitted without depth (no 3-D lines)"; return HVO_ERR_INVALID_ARG; }
+    const bool opt = !params || (params->mode & HVO_LINE_STRUCT_OPTIMIZE);
+    if (opt && B->line_opt_done) { s->last_error = "line structure: this frame's 3-D lines have been optimised already"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    hipStream_t st = s->s_match;
+    ST_HIP(hipStreamWaitEvent(st, B->ev_lsd, 0));                // the 3-D lines and the key-line count
+    LsResident R;
+    R.linefn = B->lv.d_fn; R.l3d = (hvo_line3d *)(B->d_tail + s->tl.lines3d); R.d_nkl = B->lv.d_nkl;
+    const int32_t nl = n_lines;
+    int8_t *const relp[1] = { rel }; double *const outp[1] = { l3d_out };
+    const int rc = ls_run(B->ctx, st, params, 1, &nl, nullptr, &R, relp, outp, res, &s->last_error);
+    if (rc == HVO_OK && opt) B->line_opt_done = true;
+    return rc;
+}
+
+int hvo_stream_line_opt_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2])
+{
+    if (!s || !ms2) return HVO_ERR_INVALID_ARG;
+    StreamSlot *B = slot_of(s, cur);
+    if (!B) { s->last_error = "line structure: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    ms2[0] = B->ctx->ls_ms[0]; ms2[1] = B->ctx->ls_ms[1];
+    return HVO_OK;
 }
 
 int hvo_stream_pose_last_kernel_ms(hvo_stream *s, int64_t cur, float *ms)

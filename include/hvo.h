@@ -659,7 +659,81 @@ int hvo_batch_pose_optimize(hvo_ctx *ctx, const hvo_camera *cam, const hvo_pose_
 int hvo_pose_last_kernel_ms(const hvo_ctx *ctx, float *ms);
 int hvo_stream_pose_last_kernel_ms(hvo_stream *s, int64_t cur, float *ms);
 
-/* Page-lock (hipHostRegister) / unlock a caller's host buffer.  Images handed to hvo_batch_upload / hvo_stream_submit and result
+/* ---- Line structural constraints and LineOptStruct (csrc/line_opt.hip) ----
+ * The two per-frame steps between the Frame constructor and Track() in Tracking::GrabImageRGBD_wh (reference src/Tracking.cc:270-335):
+ *   part 1  Manhattan::computeStructConstrains(frame, k, par, perp) for every key line k (src/Manhattan.cpp:107-161): per ordered pair
+ *           (k, i), i != k, the 2-D cosine of (a/c, b/c) of both key-line functions and the 3-D cosine of both mvLineEq in double;
+ *           perpendicular when both are < cos_perp, else parallel when both are > cos_par.  Line k is skipped by the row rule; a partner i
+ *           with mvLineEq[i] == (-1,-1,-1) is not skipped (it may enter k's lists; part 2 gives it no edge).  c == 0 gives inf / NaN and
+ *           neither list.  IEEE double without contraction: the result equals tests/line_opt_ref.py on every pair.
+ *   part 2  Optimizer::LineOptStruct(frame) (src/Optimizer.cc:1480-1876): both 3-D end points of every line with at least
+ *           min_constraints list entries are vertices; one ParEptsNVector3DSingleFrame / PerpEptsNVector3DSingleFrame edge
+ *           (include/g2oMSC.h:123-190) per list entry whose partner has mvLineEq[2] != 0 and [0] != -1; g2o's numeric Jacobians (central
+ *           differences, 1e-9), Huber kernels, one global Levenberg lambda over a block-diagonal Hessian (one 6 x 6 block per line), two
+ *           rounds of optimize(iterations) without resetting the estimate, the classification on chi2 as float between them, and the final
+ *           rejection on chi2 <= chi2_reject.  One workgroup per frame, all arithmetic in double, every sum over a fixed tree.
+ * Relation matrix: int8 rel[n x n], row k: 0 none, 1 parallel, 2 perpendicular, -1 / -2 the same constraint rejected by part 2 (the
+ * reference writes -1 into the list slot and keeps the slot).  Entry j of mvParLinesIdx[k] is the j-th entry of row k with |value| == 1
+ * in ascending i, mvPerpLinesIdx[k] likewise with |value| == 2; a negative value is the reference's -1 in that slot.
+ * Kept as written: the write-back test asks for vertex 0 in its second operand (Optimizer.cc:1861), so when line 0 did not enter the graph
+ * NO line's end points are written back (the rejections still are) and when it did every line with vertices is; the function returns
+ * nothing, hvo_line_opt_result is defined instead; only A and B of a record change.  Readings: DESIGN.md section 7.
+ * At most 4096 lines per frame (HVO_ERR_UNSUPPORTED). */
+#define HVO_LINE_STRUCT_CONSTRAINTS 1u   /* part 1: fill rel */
+#define HVO_LINE_STRUCT_OPTIMIZE    2u   /* part 2 on rel: the one part 1 just filled, or, without HVO_LINE_STRUCT_CONSTRAINTS, the caller's */
+#define HVO_LINE_STRUCT_ROW_UNSET   0    /* row k skipped when mvLineEq[k] == (-1,-1,-1): GrabImageRGBD_wh, src/Tracking.cc:280 */
+#define HVO_LINE_STRUCT_ROW_Z0      1    /* row k skipped when mvLineEq[k][2] == 0.0: GrabImageRGBD, src/Tracking.cc:401 */
+typedef struct {
+    double  cos_par, cos_perp;    /* mCosThPar = cos(3 * 0.0174533), mCosThPerp = cos(87 * 0.0174533) (src/Manhattan.cpp:28-30) */
+    double  huber_delta;          /* thHuberLine: sqrt(0.02) rounded to float */
+    double  chi2_reject;          /* 0.02: the final rejection, in double */
+    float   chi2_round[2];        /* chi2Manh = { 0.02f, 0.01f }: the classification after each round, in float */
+    int32_t min_constraints;      /* 5 */
+    int32_t iterations;           /* optimize(5) */
+    int32_t row_rule;             /* HVO_LINE_STRUCT_ROW_* */
+    uint32_t mode;                /* HVO_LINE_STRUCT_CONSTRAINTS | HVO_LINE_STRUCT_OPTIMIZE */
+} hvo_line_struct_params;
+/* the reference's values: both parts, the row rule of GrabImageRGBD_wh */
+int hvo_line_struct_default_params(hvo_line_struct_params *p);
+typedef struct {
+    int32_t n_lines, reserved;    /* NL, the side of rel */
+    const double *linefn;         /* mvKeyLineFunctions, n_lines x 3 (part 1 only) */
+    const hvo_line3d *lines3d;    /* A, B (mvLines3D) and line_eq (mvLineEq) are read */
+} hvo_line_struct_problem;
+typedef struct {
+    int32_t n_lines;              /* the lines the call worked on (a resident frame's count caps the caller's) */
+    int32_t n_lines_to_opt;       /* lines that entered the graph */
+    int32_t n_edges, n_par_edges, n_perp_edges;
+    int32_t rounds;               /* 0: part 1 only; 1: the graph had fewer than 10 edges; else 2 */
+    int32_t iterations[2], trials[2];   /* per round: solve() calls, Levenberg trials (0, 0 when no vertex was active) */
+    int32_t n_flagged[2];         /* per round: edges whose chi2 exceeded chi2_round */
+    int32_t written_back;         /* 1: the end points were written back (line 0 had vertices) */
+    int32_t status;
+    double  lambda[2], chi2[2];   /* per round: the final lambda and active robust chi2 */
+} hvo_line_opt_result;
+/* On host arrays, n_frames problems in one launch sequence; a problem equals the single call on it bit for bit.  rel[f]: n_lines^2 bytes,
+ * written by part 1, or read (values 0, +-1, +-2) and rewritten by part 2 alone.  l3d_out (or l3d_out[f]) may be NULL; else n_lines x 6
+ * doubles: A, B of every line after the call.  params NULL = hvo_line_struct_default_params.  The caller's records are not written. */
+int hvo_line_struct_optimize(hvo_ctx *ctx, const hvo_line_struct_params *params, int n_frames, const hvo_line_struct_problem *problems,
+                             int8_t *const *rel, double *const *l3d_out, hvo_line_opt_result *res);
+/* On the resident frame `cur` of a stream that runs an LSD stage and HVO_STAGE_LINES3D: key-line functions and 3-D lines are read where the
+ * stages left them and A, B of the resident hvo_line3d records are overwritten (when written_back), so a following hvo_stream_pose_optimize
+ * or hvo_stream_search_lines_by_projection_map on that frame sees the optimised lines.  n_lines: the side of rel, the frame's key-line
+ * count as hvo_stream_collect reported it.  Only rel, the result and (l3d_out != NULL) n_lines x 6 doubles come down.  A second call with
+ * HVO_LINE_STRUCT_OPTIMIZE on the same frame would optimise optimised lines: HVO_ERR_INVALID_ARG, as for a missing stage or a frame
+ * without depth, with hvo_stream_last_error set. */
+int hvo_stream_line_struct_optimize(hvo_stream *s, int64_t cur, const hvo_line_struct_params *params, int n_lines, int8_t *rel,
+                                    double *l3d_out, hvo_line_opt_result *res);
+/* On the first n frames of the resident batch (after hvo_batch_run with an LSD stage and HVO_STAGE_LINES3D on frames uploaded with depth),
+ * one launch sequence; n_lines[f] is the side of rel[f].  Frame k equals the stream form on the same image bit for bit.  A second
+ * optimising call before the next hvo_batch_run, n beyond the batch, a missing stage or no depth: HVO_ERR_INVALID_ARG. */
+int hvo_batch_line_struct_optimize(hvo_ctx *ctx, const hvo_line_struct_params *params, int n, const int32_t *n_lines, int8_t *const *rel,
+                                   double *const *l3d_out, hvo_line_opt_result *res);
+/* device time of the last call's two launches in ms: ms2[0] the pair pass, ms2[1] the optimisation (0 for a part that did not run) */
+int hvo_line_opt_last_kernel_ms(const hvo_ctx *ctx, float ms2[2]);
+int hvo_stream_line_opt_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2]);
+
+/* Page-lock (hipHostRegister) / unlock a caller's host buffer. Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */
 int hvo_pin_host(void *p, size_t bytes);

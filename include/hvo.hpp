@@ -614,4 +614,51 @@ private:
     hvo_camera cam_; hvo_pose_plane_params pp_ = { 0.5, 50.0, 0.1, 0.1, 100.0, 50.0 }; bool has_pp_;
 };
 
+// The per-frame step between the Frame constructor and Track() (src/Tracking.cc:270-335): Manhattan::computeStructConstrains for every key line
+// and Optimizer::LineOptStruct, on the mirror's frame handle.  FrameLines holds what the reference keeps on the Frame: mvParLinesIdx /
+// mvPerpLinesIdx (partner indices in ascending order, -1 in a slot LineOptStruct rejected) and mvLines3D (start, end) after the call.
+struct FrameLines {
+    int NL = 0;
+    std::vector<int8_t> rel;                                   // NL x NL: 0 none, 1 parallel, 2 perpendicular, negative = rejected
+    std::vector<std::vector<int>> mvParLinesIdx, mvPerpLinesIdx;
+    std::vector<double> mvLines3D;                             // NL x 6
+    hvo_line_opt_result res = hvo_line_opt_result();
+    void rebuild()                                             // the vectors from rel
+    {
+        mvParLinesIdx.assign(NL, std::vector<int>()); mvPerpLinesIdx.assign(NL, std::vector<int>());
+        for (int k = 0; k < NL; k++) for (int i = 0; i < NL; i++) {
+            const int v = rel[(size_t)k * NL + i];
+            if (v == 1 || v == -1) mvParLinesIdx[k].push_back(v > 0 ? i : -1);
+            else if (v == 2 || v == -2) mvPerpLinesIdx[k].push_back(v > 0 ? i : -1);
+        }
+    }
+};
+class Manhattan {
+public:
+    // mpManh->computeStructConstrains(mCurrentFrame, k, par, perp) for every k at once (the loop at Tracking.cc:270-293); NL = the frame's key-line count
+    static void computeStructConstrains(FrameStream &fs, int64_t cur, int NL, FrameLines &f, int row_rule = HVO_LINE_STRUCT_ROW_UNSET)
+    {
+        run(fs, cur, NL, f, HVO_LINE_STRUCT_CONSTRAINTS, row_rule);
+    }
+    // the reference's per-line form, read from the lists computed above
+    static void computeStructConstrains(const FrameLines &f, int idx, std::vector<int> &idxPar, std::vector<int> &idxPerp)
+    {
+        idxPar = f.mvParLinesIdx[idx]; idxPerp = f.mvPerpLinesIdx[idx];
+    }
+    static void run(FrameStream &fs, int64_t cur, int NL, FrameLines &f, unsigned mode, int row_rule)
+    {
+        hvo_line_struct_params p; check(hvo_line_struct_default_params(&p), "hvo_line_struct_default_params");
+        p.mode = mode; p.row_rule = row_rule;
+        if (!(mode & HVO_LINE_STRUCT_CONSTRAINTS) && (f.NL != NL || f.rel.size() != (size_t)NL * NL)) throw Error(HVO_ERR_INVALID_ARG, "LineOptStruct without lists");
+        f.NL = NL; f.rel.resize((size_t)NL * NL); f.mvLines3D.resize((size_t)NL * 6);
+        check(hvo_stream_line_struct_optimize(fs.get(), cur, &p, NL, f.rel.data(), f.mvLines3D.data(), &f.res), "hvo_stream_line_struct_optimize");
+        f.rebuild();
+    }
+};
+// Optimizer::LineOptStruct(&mCurrentFrame) on the lists of f (computeStructConstrains first), or both steps in one call with both = true
+inline void LineOptStruct(FrameStream &fs, int64_t cur, int NL, FrameLines &f, bool both = false, int row_rule = HVO_LINE_STRUCT_ROW_UNSET)
+{
+    Manhattan::run(fs, cur, NL, f, both ? (HVO_LINE_STRUCT_CONSTRAINTS | HVO_LINE_STRUCT_OPTIMIZE) : HVO_LINE_STRUCT_OPTIMIZE, row_rule);
+}
+
 }  // namespace hvo
