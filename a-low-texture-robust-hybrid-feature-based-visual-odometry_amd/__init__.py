@@ -79,6 +79,9 @@ EXPORTS = [
     "hvo_plane_map_last_error", "hvo_match_planes", "hvo_stream_match_planes", "hvo_batch_match_planes", "hvo_pose_optimize", "hvo_stream_pose_optimize", "hvo_batch_pose_optimize", "hvo_pose_last_kernel_ms", "hvo_stream_pose_last_kernel_ms",
     "hvo_line_struct_default_params", "hvo_line_struct_optimize", "hvo_stream_line_struct_optimize", "hvo_batch_line_struct_optimize",
     "hvo_line_opt_last_kernel_ms", "hvo_stream_line_opt_last_kernel_ms",
+    "hvo_line_map_create", "hvo_line_map_destroy", "hvo_line_map_set", "hvo_line_map_set_many", "hvo_line_map_set_bad", "hvo_line_map_set_observed",
+    "hvo_line_map_counts", "hvo_line_map_slot", "hvo_line_map_last_error",
+    "hvo_search_local_lines", "hvo_stream_search_local_lines", "hvo_batch_search_local_lines",
 ]
 
 
@@ -213,6 +216,84 @@ class LineOptResult(C.Structure):
 
 
 assert C.sizeof(LineStructParams) == 56 and C.sizeof(LineStructProblem) == 24 and C.sizeof(LineOptResult) == 88
+
+
+LINE_MAP_MAX_QUERIES = 16384      # lines in view per call (the search core's limit)
+
+
+class LocalLinesParams(C.Structure):
+    """hvo_local_lines_params"""
+    _fields_ = [("bounds", C.c_float * 4), ("log_scale_factor", C.c_float), ("th", C.c_float), ("nn_ratio", C.c_float)]
+
+
+class LocalLinesFrame(C.Structure):
+    """hvo_local_lines_frame: the frame side on host arrays"""
+    _fields_ = [("kl", C.c_void_p), ("linefn", C.c_void_p), ("l3d", C.c_void_p), ("desc", C.c_void_p), ("n_kl", C.c_int32),
+                ("cell_start", C.c_void_p), ("cell_items", C.c_void_p)]
+
+
+class LocalLinesIO(C.Structure):
+    """hvo_local_lines_io: one frame's inputs and outputs"""
+    _fields_ = [("n_kl", C.c_int32), ("held", C.c_void_p), ("seen_extra", C.c_void_p), ("n_seen_extra", C.c_int32), ("in_view_slot", C.c_void_p),
+                ("proj", C.c_void_p), ("view_cos", C.c_void_p), ("level", C.c_void_p), ("match_idx", C.c_void_p), ("match_dist", C.c_void_p),
+                ("n_par", C.c_void_p), ("n_perp", C.c_void_p), ("rel_map", C.c_void_p)]
+
+
+class LocalLinesResult(C.Structure):
+    """hvo_local_lines_result: one Tracking::SearchLocalLines + computeStructConstInMap call.  The arrays (held, in_view_slot, proj, view_cos,
+    level, match_idx, match_dist, n_par, n_perp, rel_map or None) are attached as attributes by the calls that return it."""
+    _fields_ = [("n_slots_tested", C.c_int32), ("n_in_view", C.c_int32), ("n_matches", C.c_int32), ("n_gated", C.c_int32), ("status", C.c_int32),
+                ("kernel_ms", C.c_float * 3)]
+
+    def to_dict(self):
+        d = dict(n_slots_tested=self.n_slots_tested, n_in_view=self.n_in_view, n_matches=self.n_matches, n_gated=self.n_gated, status=self.status,
+                 kernel_ms=tuple(self.kernel_ms))
+        for k in ("held", "in_view_slot", "proj", "view_cos", "level", "match_idx", "match_dist", "n_par", "n_perp", "rel_map"):
+            d[k] = getattr(self, k, None)
+        return d
+
+
+assert C.sizeof(LocalLinesResult) == 32
+
+
+def _ll_params(bounds4, log_scale_factor, th, nn_ratio):
+    p = LocalLinesParams()
+    b = (0.0, 1.0, 0.0, 1.0) if bounds4 is None else [float(v) for v in np.asarray(bounds4).reshape(4)]
+    for k in range(4): p.bounds[k] = b[k]
+    p.log_scale_factor = log_scale_factor; p.th = th; p.nn_ratio = nn_ratio
+    return p
+
+
+def _ll_io(n_kl, n_slots, held, seen_extra, want_rel):
+    """-> (LocalLinesIO, dict of the arrays it points at)"""
+    capq = max(1, min(n_slots, LINE_MAP_MAX_QUERIES)); nk = max(n_kl, 1)
+    h = np.full(nk, -1, np.int32)
+    if held is not None:
+        hh = np.asarray(held, np.int32).reshape(-1)
+        if len(hh) != n_kl:
+            raise ValueError("held must have one entry per key line (%d)" % n_kl)
+        h[:n_kl] = hh
+    ex = np.ascontiguousarray([] if seen_extra is None else seen_extra, np.int32).reshape(-1)
+    a = dict(held=h, seen_extra=ex, in_view_slot=np.zeros(capq, np.int32), proj=np.zeros((capq, 4), np.float32), view_cos=np.zeros(capq, np.float32),
+             level=np.zeros(capq, np.int32), match_idx=np.full(capq, -1, np.int32), match_dist=np.full(capq, 256, np.int32),
+             n_par=np.zeros(nk, np.int32), n_perp=np.zeros(nk, np.int32), rel_map=np.zeros(nk * capq, np.int8) if want_rel else None)
+    io = LocalLinesIO()
+    io.n_kl = n_kl; io.n_seen_extra = len(ex)
+    for k, v in a.items():
+        if k == "seen_extra":
+            io.seen_extra = v.ctypes.data if len(v) else None
+        else:
+            setattr(io, k, None if v is None else v.ctypes.data)
+    return io, a
+
+
+def _ll_finish(r, a, n_kl):
+    nq = r.n_in_view if r.status == HVO_OK else 0
+    r.held = a["held"][:n_kl]; r.n_par = a["n_par"][:n_kl]; r.n_perp = a["n_perp"][:n_kl]
+    for k in ("in_view_slot", "proj", "view_cos", "level", "match_idx", "match_dist"):
+        setattr(r, k, a[k][:nq])
+    r.rel_map = None if a["rel_map"] is None else a["rel_map"][: n_kl * nq].reshape(n_kl, nq)
+    return r
 
 
 def line_struct_params(**kw):
@@ -411,6 +492,22 @@ def lib():
         L.hvo_match_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PlaneMatch), C.c_void_p, C.c_void_p]
         L.hvo_stream_match_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PlaneMatch)]
         L.hvo_batch_match_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hvo_line_map_create.argtypes = [C.c_int, C.c_int]; L.hvo_line_map_create.restype = C.c_void_p
+        L.hvo_line_map_destroy.argtypes = [C.c_void_p]; L.hvo_line_map_destroy.restype = None
+        L.hvo_line_map_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int]
+        L.hvo_line_map_set_many.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
+        L.hvo_line_map_set_bad.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.hvo_line_map_set_observed.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.hvo_line_map_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
+        L.hvo_line_map_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.hvo_line_map_last_error.argtypes = [C.c_void_p]; L.hvo_line_map_last_error.restype = C.c_char_p
+        L.hvo_search_local_lines.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalLinesParams), C.POINTER(LocalLinesFrame),
+                                             C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]
+        L.hvo_stream_search_local_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalLinesParams),
+                                                    C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]
+        L.hvo_batch_search_local_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalLinesParams),
+                                                   C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]
         L.hvo_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_stream_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_search_by_projection_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
@@ -520,6 +617,64 @@ class PlaneMap:
         c = np.zeros(4, np.float32); n, b = C.c_int(0), C.c_int(0)
         self._chk(lib().hvo_plane_map_slot(self.h, slot, _p(c), C.byref(n), C.byref(b)), "plane_map_slot")
         return c, n.value, bool(b.value)
+
+
+class LineMap:
+    """hvo_line_map: mvpLocalMapLines resident on one device (world end points, world vector, normal, distance range, descriptor, bad and
+    has-observations flags per slot).  Slot index = position in the vector Tracking::SearchLocalLines walks.  Not thread-safe; usable from
+    any Context / Stream of its device."""
+
+    def __init__(self, device=0, slots=0):
+        self.h = lib().hvo_line_map_create(device, slots)
+        if not self.h:
+            raise HvoError(-3, "hvo_line_map_create")
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().hvo_line_map_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _chk(self, rc, what):
+        if rc != HVO_OK:
+            raise HvoError(rc, what + ": " + lib().hvo_line_map_last_error(self.h).decode())
+
+    def set(self, slot, pos, wvec, normal, max_dist, min_dist, desc, observed=True):
+        """set or replace a slot: pos = GetWorldPos() (6), wvec = GetWorldVector(), normal = GetNormal(), the raw mfMaxDistance / mfMinDistance,
+        desc = GetDescriptor() (32 bytes), observed = Observations() > 0"""
+        a = [np.ascontiguousarray(pos, np.float64).reshape(6), np.ascontiguousarray(wvec, np.float64).reshape(3),
+             np.ascontiguousarray(normal, np.float64).reshape(3), np.ascontiguousarray(desc, np.uint8).reshape(32)]
+        self._chk(lib().hvo_line_map_set(self.h, slot, _p(a[0]), _p(a[1]), _p(a[2]), float(max_dist), float(min_dist), _p(a[3]), 1 if observed else 0), "line_map_set")
+
+    def set_many(self, first, pos, wvec, normal, max_dist, min_dist, desc, observed=None, bad=None):
+        """slots first .. first + n - 1 in one upload: pos (n, 6), wvec / normal (n, 3), max_dist / min_dist (n), desc (n, 32), observed / bad (n) or None"""
+        pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 6); n = len(pos)
+        a = [pos, np.ascontiguousarray(wvec, np.float64).reshape(n, 3), np.ascontiguousarray(normal, np.float64).reshape(n, 3),
+             np.ascontiguousarray(max_dist, np.float32).reshape(n), np.ascontiguousarray(min_dist, np.float32).reshape(n),
+             np.ascontiguousarray(desc, np.uint8).reshape(n, 32)]
+        fl = [None if v is None else np.ascontiguousarray(np.asarray(v).astype(bool), np.uint8).reshape(n) for v in (observed, bad)]
+        pp = lambda v: None if v is None or v.size == 0 else _p(v)
+        self._chk(lib().hvo_line_map_set_many(self.h, first, n, *[pp(v) for v in a], pp(fl[0]), pp(fl[1])), "line_map_set_many")
+
+    def set_bad(self, slot, bad=True):
+        self._chk(lib().hvo_line_map_set_bad(self.h, slot, 1 if bad else 0), "line_map_set_bad")
+
+    def set_observed(self, slot, observed=True):
+        self._chk(lib().hvo_line_map_set_observed(self.h, slot, 1 if observed else 0), "line_map_set_observed")
+
+    def counts(self):
+        """(slots, good slots, slots with observations)"""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(lib().hvo_line_map_counts(self.h, C.byref(a), C.byref(b), C.byref(c)), "line_map_counts")
+        return a.value, b.value, c.value
+
+    def slot(self, slot):
+        """dict(pos, wvec, normal, max_dist, min_dist, desc, bad, observed) of one slot"""
+        pos = np.zeros(6); w = np.zeros(3); nr = np.zeros(3); d = np.zeros(32, np.uint8)
+        mx, mn, b, o = C.c_float(0), C.c_float(0), C.c_int(0), C.c_int(0)
+        self._chk(lib().hvo_line_map_slot(self.h, slot, _p(pos), _p(w), _p(nr), C.byref(mx), C.byref(mn), _p(d), C.byref(b), C.byref(o)), "line_map_slot")
+        return dict(pos=pos, wvec=w, normal=nr, max_dist=mx.value, min_dist=mn.value, desc=d, bad=bool(b.value), observed=bool(o.value))
 
 
 class Context:
@@ -856,6 +1011,39 @@ class Context:
         res = (PlaneMatch * len(T))()
         self._chk(lib().hvo_batch_match_planes(self.h, pmap.h, len(T), _p(T), None if t is None else _p(t), res), "batch_match_planes")
         return list(res)
+
+    def search_local_lines(self, lmap, cam, Tcw, t_kl, t_linefn, t_l3d, t_desc, cell_start, cell_items, bounds4, held=None, seen_extra=None,
+                           log_scale_factor=float(np.log(np.float32(1.2))), th=1.0, nn_ratio=0.95, rel_map=False):
+        """Tracking::SearchLocalLines + Manhattan::computeStructConstInMap (src/Tracking.cc:3279-3392, src/Manhattan.cpp:163-224) of a frame on
+        host arrays against the resident LineMap under the pose Tcw (3 x 4): frustum test of every slot, the local-map line search on the
+        lines in view, the CosSita post-gate, the map constraints.  held: the slot each key line holds at entry (-1 = none) ->
+        LocalLinesResult with .held, .in_view_slot, .proj, .view_cos, .level, .match_idx, .match_dist, .n_par, .n_perp, .rel_map"""
+        nt = len(t_kl)
+        keep = [np.ascontiguousarray(t_kl), np.ascontiguousarray(t_linefn, np.float64), np.ascontiguousarray(t_l3d), np.ascontiguousarray(t_desc, np.uint8),
+                np.ascontiguousarray(cell_start, np.int32), np.ascontiguousarray(cell_items, np.int32)]
+        F = LocalLinesFrame(); F.n_kl = nt
+        for k, v in zip(("kl", "linefn", "l3d", "desc", "cell_start", "cell_items"), keep):
+            setattr(F, k, v.ctypes.data if v.size else None)
+        io, a = _ll_io(nt, lmap.counts()[0], held, seen_extra, rel_map)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12); c = _pose_cam(cam); p = _ll_params(bounds4, log_scale_factor, th, nn_ratio)
+        r = LocalLinesResult()
+        self._chk(lib().hvo_search_local_lines(self.h, lmap.h, C.byref(c), _p(T), C.byref(p), C.byref(F), C.byref(io), C.byref(r)), "search_local_lines")
+        return _ll_finish(r, a, nt)
+
+    def batch_search_local_lines(self, lmap, cam, Tcw, n_kl, held=None, seen_extra=None, log_scale_factor=float(np.log(np.float32(1.2))), th=1.0,
+                                 nn_ratio=0.95, rel_map=False):
+        """the first len(Tcw) frames of the resident batch (needs an LSD stage, STAGE_GRIDS | STAGE_LINES3D and depth), frame k under Tcw[k] with
+        n_kl[k] key lines, held[k] and seen_extra[k]; the map is read once for all frames -> list of LocalLinesResult"""
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 12); n = len(T)
+        ns = lmap.counts()[0]
+        ios = (LocalLinesIO * n)(); arrs = []
+        for k in range(n):
+            io, a = _ll_io(int(n_kl[k]), ns, None if held is None else held[k], None if seen_extra is None else seen_extra[k], rel_map)
+            ios[k] = io; arrs.append(a)
+        c = _pose_cam(cam); p = _ll_params(None, log_scale_factor, th, nn_ratio)
+        res = (LocalLinesResult * n)()
+        self._chk(lib().hvo_batch_search_local_lines(self.h, lmap.h, n, C.byref(c), _p(T), C.byref(p), ios, res), "batch_search_local_lines")
+        return [_ll_finish(res[k], arrs[k], int(n_kl[k])) for k in range(n)]
 
     def set_readings(self, blur_float=False, lsd_8u=False):
         """the alternative readings of cv::GaussianBlur / cv::LineSegmentDetector (include/hvo.h HVO_READING_*); the next extraction uses them"""
@@ -1302,6 +1490,17 @@ class Stream:
         self._chk(lib().hvo_stream_search_lines_by_projection_map(self.h, cur, nq, pp(q_xyxy), pp(q_view_cos), pp(q_wvec), pp(q_desc), pp(keep[0]), pp(keep[1]),
                                                                   th, nn_ratio, _p(mi), _p(md), C.byref(n)), "stream_search_lines_by_projection_map")
         return n.value, mi[:nq], md[:nq]
+
+    def search_local_lines(self, lmap, cur, cam, Tcw, n_kl, held=None, seen_extra=None, log_scale_factor=float(np.log(np.float32(1.2))), th=1.0,
+                           nn_ratio=0.95, rel_map=False):
+        """Tracking::SearchLocalLines + Manhattan::computeStructConstInMap on the resident frame `cur` (needs an LSD stage, STAGE_GRIDS |
+        STAGE_LINES3D and depth) against the resident LineMap: only the pose, held and seen_extra go up.  n_kl: the frame's key-line count
+        -> LocalLinesResult as Context.search_local_lines"""
+        io, a = _ll_io(int(n_kl), lmap.counts()[0], held, seen_extra, rel_map)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12); c = _pose_cam(cam); p = _ll_params(None, log_scale_factor, th, nn_ratio)
+        r = LocalLinesResult()
+        self._chk(lib().hvo_stream_search_local_lines(self.h, lmap.h, cur, C.byref(c), _p(T), C.byref(p), C.byref(io), C.byref(r)), "stream_search_local_lines")
+        return _ll_finish(r, a, int(n_kl))
 
     def track_manhattan(self, cur, R_last, axes=False):
         """Tracking::TrackManhattanFrame on the resident frame `cur` (needs STAGE_PLANE_TAIL | STAGE_LINES3D and depth): its normals and 3-D

@@ -809,6 +809,78 @@ int hvo_batch_line_struct_optimize(hvo_ctx *ctx, const hvo_line_struct_params *p
     return rc;
 }
 
+// Tracking::SearchLocalLines + Manhattan::computeStructConstInMap on host arrays against a resident line map (local_lines.hip)
+int hvo_search_local_lines(hvo_ctx *ctx, hvo_line_map *m, const hvo_camera *cam, const float Tcw[12], const hvo_local_lines_params *params,
+                           const hvo_local_lines_frame *frame, hvo_local_lines_io *io, hvo_local_lines_result *res)
+{
+    if (!ctx || !m || !cam || !Tcw || !params || !frame || !io || !res || frame->n_kl < 0) return HVO_ERR_INVALID_ARG;
+    const int nt = frame->n_kl;
+    if (nt > 0 && (!frame->kl || !frame->linefn || !frame->l3d || !frame->desc || !frame->cell_start)) return HVO_ERR_INVALID_ARG;
+    if (!(params->bounds[1] > params->bounds[0]) || !(params->bounds[3] > params->bounds[2])) return HVO_ERR_INVALID_ARG;
+    const int ncell = HVO_GRID_COLS * HVO_GRID_ROWS + 1, n_items = nt > 0 ? frame->cell_start[ncell - 1] : 0;
+    if (n_items < 0 || (n_items > 0 && !frame->cell_items)) return HVO_ERR_INVALID_ARG;
+    if (ll_map_device(m) != ctx->device) { ctx->last_error = "local lines: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
+    if (nt > 2048 || n_items >= (1 << 22)) { ctx->last_error = match_lsbp_map_limit_text(0, nt); return HVO_ERR_UNSUPPORTED; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t b_kl = al((size_t)nt * sizeof(hvo_keyline)), b_fn = al((size_t)nt * 24), b_l3 = al((size_t)nt * sizeof(hvo_line3d)), b_d = al((size_t)nt * 32),
+                 b_cs = al((size_t)ncell * 4), b_ci = al((size_t)n_items * 4);
+    char *a = (char *)hvo_call_arena(ctx, b_kl + b_fn + b_l3 + b_d + b_cs + b_ci + 256);
+    if (!a) return HVO_ERR_HIP;
+    LlFrameDev F; memset(&F, 0, sizeof(F));
+    F.nt = nt; F.n_items = n_items;
+    F.kl = (const hvo_keyline *)a; F.fn = (const double *)(a + b_kl); F.l3d = (const hvo_line3d *)(a + b_kl + b_fn); F.desc = (const uint8_t *)(a + b_kl + b_fn + b_l3);
+    F.cell_start = (const int32_t *)(a + b_kl + b_fn + b_l3 + b_d); F.cell_items = (const int32_t *)(a + b_kl + b_fn + b_l3 + b_d + b_cs);
+    hipStream_t st = ctx->stream;
+    if (nt) {
+        HVO_HIP(hipMemcpyAsync((void *)F.kl, frame->kl, (size_t)nt * sizeof(hvo_keyline), hipMemcpyHostToDevice, st));
+        HVO_HIP(hipMemcpyAsync((void *)F.fn, frame->linefn, (size_t)nt * 24, hipMemcpyHostToDevice, st));
+        HVO_HIP(hipMemcpyAsync((void *)F.l3d, frame->l3d, (size_t)nt * sizeof(hvo_line3d), hipMemcpyHostToDevice, st));
+        HVO_HIP(hipMemcpyAsync((void *)F.desc, frame->desc, (size_t)nt * 32, hipMemcpyHostToDevice, st));
+        HVO_HIP(hipMemcpyAsync((void *)F.cell_start, frame->cell_start, (size_t)ncell * 4, hipMemcpyHostToDevice, st));
+        if (n_items) HVO_HIP(hipMemcpyAsync((void *)F.cell_items, frame->cell_items, (size_t)n_items * 4, hipMemcpyHostToDevice, st));
+    }
+    const int rc = ll_run(st, m, cam, params, params->bounds, 1, &F, Tcw, io, res);
+    if (rc) ctx->last_error = ll_map_error(m);
+    return rc;
+}
+
+// the same over the first n frames of the resident batch: the frame side where the last hvo_batch_run left it, one pose per frame
+int hvo_batch_search_local_lines(hvo_ctx *ctx, hvo_line_map *m, int n, const hvo_camera *cam, const float *Tcw, const hvo_local_lines_params *params,
+                                 hvo_local_lines_io *io, hvo_local_lines_result *res)
+{
+    if (!ctx || !m || !cam || !Tcw || !params || !io || !res || n < 1) return HVO_ERR_INVALID_ARG;
+    if (n > ctx->batch_n) { ctx->last_error = "local lines: n beyond the resident batch"; return HVO_ERR_INVALID_ARG; }
+    const unsigned need = HVO_STAGE_GRIDS | HVO_STAGE_LINES3D;
+    if (!(ctx->last_stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL)) || (ctx->last_stages & need) != need) {
+        ctx->last_error = "local lines: the last hvo_batch_run must include an LSD stage, HVO_STAGE_GRIDS and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
+    }
+    if (!ctx->have_depth) { ctx->last_error = "local lines: the batch was uploaded without depth (no 3-D lines)"; return HVO_ERR_INVALID_ARG; }
+    if (ll_map_device(m) != ctx->device) { ctx->last_error = "local lines: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    char *d_out = nullptr; TailLayout L;
+    if (tail_batch_view(ctx, &d_out, &L)) { ctx->last_error = "local lines: no resident tail results"; return HVO_ERR_INVALID_ARG; }
+    LsdView lv; memset(&lv, 0, sizeof(lv));
+    int rc;
+    if ((rc = lsd_prepare(ctx, ctx->batch_w, ctx->batch_h, std::max(n, ctx->p.max_batch), ctx->last_cull, &lv))) return rc;
+    std::vector<LlFrameDev> F((size_t)n);
+    std::vector<int> nkl((size_t)n);                              // the resident counts: io[f].n_kl may say more, never less
+    HVO_HIP(hipMemcpyAsync(nkl.data(), lv.d_nkl, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HVO_HIP(hipStreamSynchronize(ctx->stream));
+    for (int f = 0; f < n; f++) {
+        if (io[f].n_kl < 0) return HVO_ERR_INVALID_ARG;
+        nkl[f] = std::max(0, std::min(nkl[f], lv.nfeat));
+        char *o = d_out + (size_t)f * L.total;
+        F[f].kl = lv.d_kl + (size_t)f * lv.nfeat; F[f].fn = lv.d_fn + (size_t)f * lv.nfeat * 3; F[f].desc = lv.d_desc + (size_t)f * lv.nfeat * 32;
+        F[f].l3d = (const hvo_line3d *)(o + L.lines3d); F[f].cell_start = (const int32_t *)(o + L.ln_start); F[f].cell_items = (const int32_t *)(o + L.ln_items);
+        F[f].n_items = L.ln_cap; F[f].nt = nkl[f];                  // (the item list is bounded by its capacity: its count lives on the device)
+    }
+    const float bounds[4] = { 0.f, (float)ctx->batch_w, 0.f, (float)ctx->batch_h };   // as tail_batch_run builds the grids
+    rc = ll_run(ctx->stream, m, cam, params, bounds, n, F.data(), Tcw, io, res);
+    if (rc) ctx->last_error = ll_map_error(m);
+    return rc;
+}
+
 int hvo_line_opt_last_kernel_ms(const hvo_ctx *ctx, float ms2[2])
 {
     if (!ctx || !ms2) return HVO_ERR_INVALID_ARG;

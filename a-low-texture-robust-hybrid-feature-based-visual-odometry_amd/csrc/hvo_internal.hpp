@@ -433,6 +433,15 @@ int pa_match(hipStream_t st, hvo_plane_map *m, const float *coef, int n, const h
 int pa_map_device(const hvo_plane_map *m);
 const char *pa_map_error(const hvo_plane_map *m);
 
+// local_lines.hip: SearchLocalLines + computeStructConstInMap of nframes frames against a resident line map, on stream st; it returns after
+// the stream has drained, with io / res (host, nframes entries) filled.  fr: every frame's frame side as device pointers (nt key lines;
+// n_items bounds the line grid's item list).  Tcw: host, nframes x 12.  bounds: the image bounds the line grids were built with.
+struct LlFrameDev { const hvo_keyline *kl; const double *fn; const hvo_line3d *l3d; const uint8_t *desc; const int32_t *cell_start, *cell_items; int n_items, nt; };
+int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_local_lines_params *P, const float bounds[4], int nframes,
+           const LlFrameDev *fr, const float *Tcw, hvo_local_lines_io *io, hvo_local_lines_result *res);
+int ll_map_device(const hvo_line_map *m);
+const char *ll_map_error(const hvo_line_map *m);
+
 // pose_opt.hip: Optimizer::PoseOptimization of n frames in one launch on stream st, scratch from ctx's call arena; returns after the stream
 // has drained.  rsd null: prob's frame-side host arrays go up too; else frame f's frame side is read at rsd[f]'s device pointers.
 // depth set (resident batch, which holds no mvuRight): uright is null and the kernel forms mvuRight from the depth image like k_stereo_from_rgbd.

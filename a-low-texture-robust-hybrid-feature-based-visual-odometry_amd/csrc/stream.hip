@@ -896,6 +896,36 @@ int hvo_stream_line_struct_optimize(hvo_stream *s, int64_t cur, const hvo_line_s
     return rc;
 }
 
+// Tracking::SearchLocalLines + Manhattan::computeStructConstInMap on the resident frame `cur` against a resident line map: the frame side is
+// read where the stages left it; the pose, held and seen_extra go up.  The scratch is the map's.
+int hvo_stream_search_local_lines(hvo_stream *s, hvo_line_map *m, int64_t cur, const hvo_camera *cam, const float Tcw[12],
+                                  const hvo_local_lines_params *params, hvo_local_lines_io *io, hvo_local_lines_result *res)
+{
+    if (!s || !m || !cam || !Tcw || !params || !io || !res) return HVO_ERR_INVALID_ARG;
+    const unsigned need = HVO_STAGE_GRIDS | HVO_STAGE_LINES3D;
+    if (!(s->sp.stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL)) || (s->tail_stages & need) != need) {
+        s->last_error = "local lines: the stream must run an LSD stage, HVO_STAGE_GRIDS and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
+    }
+    StreamSlot *B = slot_of(s, cur);
+    if (!B) { s->last_error = "local lines: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    if (!B->had_depth) { s->last_error = "local lines: the frame was submitted without depth (no 3-D lines)"; return HVO_ERR_INVALID_ARG; }
+    if (ll_map_device(m) != s->p.device) { s->last_error = "local lines: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    ST_HIP(hipEventSynchronize(B->ev_lsd));                     // (recorded behind the tail stages -- 3-D lines, line grid -- and their downloads)
+    int n2 = ((const int *)(B->h_out + s->lay.counts))[4];
+    if (n2 < 0) n2 = 0;
+    const TailLayout &T = s->tl;
+    const int n_items = ((const int *)(B->h_tail + T.counts))[3];
+    if (n_items < 0 || n_items > T.ln_cap) { s->last_error = "line grid overflowed its capacity"; return HVO_ERR_CAPACITY; }
+    if (n2 > 2048 || n_items >= (1 << 22)) { s->last_error = match_lsbp_map_limit_text(0, n2); return HVO_ERR_UNSUPPORTED; }
+    LlFrameDev F;
+    F.kl = B->lv.d_kl; F.fn = B->lv.d_fn; F.desc = B->lv.d_desc; F.l3d = (const hvo_line3d *)(B->d_tail + T.lines3d);
+    F.cell_start = (const int32_t *)(B->d_tail + T.ln_start); F.cell_items = (const int32_t *)(B->d_tail + T.ln_items); F.n_items = n_items; F.nt = n2;
+    const int rc = ll_run(s->s_match, m, cam, params, s->bounds, 1, &F, Tcw, io, res);
+    if (rc) s->last_error = ll_map_error(m);
+    return rc;
+}
+
 int hvo_stream_line_opt_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2])
 {
     if (!s || !ms2) return HVO_ERR_INVALID_ARG;

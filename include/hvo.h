@@ -733,6 +733,102 @@ int hvo_batch_line_struct_optimize(hvo_ctx *ctx, const hvo_line_struct_params *p
 int hvo_line_opt_last_kernel_ms(const hvo_ctx *ctx, float ms2[2]);
 int hvo_stream_line_opt_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2]);
 
+/* ---- The local map's lines resident on the device, SearchLocalLines and computeStructConstInMap (csrc/local_lines.hip) ----
+ * The line side of Tracking::TrackLocalMapWithLines (reference src/Tracking.cc:2816-2921) in one call: Tracking::SearchLocalLines
+ * (src/Tracking.cc:3279-3392) -- Frame::isInFrustum(MapLine *, 0.5) on every local map line (src/Frame.cc:1429-1499), the search core of
+ * hvo_search_lines_by_projection_map on the lines in view, the CosSita > 0.09 post-gate (3357-3386) -- and
+ * Manhattan::computeStructConstInMap (src/Manhattan.cpp:163-224) of every frame line against the lines in view.
+ *
+ * hvo_line_map: mvpLocalMapLines resident on one device.  A slot's index is the line's position in that vector.  Per slot: GetWorldPos()
+ * (6 doubles: start, end), GetWorldVector(), GetNormal() (3 doubles each), mfMaxDistance / mfMinDistance (the raw members: the kernel
+ * applies 1.2f and 0.8f), GetDescriptor() (32 bytes), isBad() and Observations() > 0.  Ownership and threading as for hvo_plane_map: the
+ * map belongs to a device, not to a context; it is NOT thread-safe (one call at a time on a map, the searching calls included: they use the
+ * map's grow-only scratch); every call returns after its device work has finished; storage grows only.
+ *
+ * Readings a caller can observe (DESIGN.md section 7 has all of them): Mat_<float> << double rounds each entry to float; Rcw X + tcw is the
+ * reading of hvo_stream_project_last (the row's products summed in float, left to right, then the translation added through double with one
+ * rounding); cv::norm is the square root of the double sum of squares stored to float; Mat::dot accumulates in double; PredictScale's log
+ * is the float overload, so `level` is ceilf(logf(mfMaxDistance / dist) / log_scale_factor); K.inv() is taken in closed form in double with
+ * each entry rounded to float; K.inv() x and Rcw v of the post-gate are products with double sums rounded to float once.  Both z tests are
+ * `< 0.0f` as written: z == 0 passes and divides, and a NaN projection passes the bounds tests (it compares false).  The predicted level is
+ * reported and never read by the search.  No arithmetic is contracted. */
+typedef struct hvo_line_map hvo_line_map;
+#define HVO_LINE_MAP_MAX_SLOTS (1 << 20)
+/* slots: initial capacity (grows on demand; 0 = a small default).  NULL when the device or the allocation fails. */
+hvo_line_map *hvo_line_map_create(int device, int slots);
+void hvo_line_map_destroy(hvo_line_map *m);
+/* Set or replace one slot (0 <= slot < HVO_LINE_MAP_MAX_SLOTS, else HVO_ERR_UNSUPPORTED).  A slot past the end extends the map; the slots
+ * skipped over start bad.  The slot written is good (not bad) afterwards. */
+int hvo_line_map_set(hvo_line_map *m, int slot, const double pos[6], const double wvec[3], const double normal[3], float max_dist, float min_dist,
+                     const uint8_t desc[32], int observed);
+/* Slots first .. first + n - 1 in one upload (a key frame replaces the local map): pos n x 6, wvec / normal n x 3, max_dist / min_dist n,
+ * desc n x 32; observed (n bytes; NULL = every line has observations) and bad (n bytes; NULL = none is bad).  The map never shrinks: a
+ * local map shorter than the one before leaves the slots past its end as they were, so the caller marks them bad (pass them in this call
+ * with bad = 1, or hvo_line_map_set_bad). */
+int hvo_line_map_set_many(hvo_line_map *m, int first, int n, const double *pos, const double *wvec, const double *normal, const float *max_dist,
+                          const float *min_dist, const uint8_t *desc, const uint8_t *observed, const uint8_t *bad);
+/* MapLine::SetBadFlag / Observations() crossing zero.  The slot must exist. */
+int hvo_line_map_set_bad(hvo_line_map *m, int slot, int bad);
+int hvo_line_map_set_observed(hvo_line_map *m, int slot, int observed);
+/* each pointer may be NULL: slots in the map, the good ones, the ones with observations */
+int hvo_line_map_counts(const hvo_line_map *m, int *n_slots, int *n_good, int *n_observed);
+/* one slot as the map holds it (each pointer may be NULL) */
+int hvo_line_map_slot(const hvo_line_map *m, int slot, double pos[6], double wvec[3], double normal[3], float *max_dist, float *min_dist,
+                      uint8_t desc[32], int *bad, int *observed);
+const char *hvo_line_map_last_error(const hvo_line_map *m);
+
+typedef struct {
+    float bounds[4];              /* mnMinX, mnMaxX, mnMinY, mnMaxY (host-array form; the resident forms take the bounds their line grid was built with) */
+    float log_scale_factor;       /* mfLogScaleFactor */
+    float th;                     /* SearchByProjection's th: 1, or 5 right after a relocalisation (Tracking.cc:3349-3352) */
+    float nn_ratio;               /* LSDmatcher's mfNNratio */
+} hvo_local_lines_params;
+typedef struct {                  /* the frame side on host arrays, as for hvo_search_lines_by_projection_map */
+    const hvo_keyline *kl; const double *linefn; const hvo_line3d *l3d; const uint8_t *desc; int32_t n_kl;
+    const int32_t *cell_start, *cell_items;
+} hvo_local_lines_frame;
+typedef struct {                  /* one frame's inputs and outputs */
+    int32_t n_kl;                 /* the length of held, n_par, n_perp: at least the frame's key-line count (on host arrays: frame->n_kl).  The
+                                   * resident forms read the frame's own count; entries past it are not touched, a shorter array is refused. */
+    int32_t *held;                /* in: the slot mvpMapLines[i] has at entry, or -1; out: after the call.  A held slot that is bad is set to -1
+                                   * first (3296-3299).  t_occupied (held and the slot has observations) and the lines with mnLastFrameSeen ==
+                                   * current (skipped at 3318) derive from it. */
+    const int32_t *seen_extra; int32_t n_seen_extra;   /* further slots to skip: lines TrackWithMotionModel discarded as outliers (2455-2456); may be NULL / 0 */
+    int32_t *in_view_slot;        /* out, room for min(slots, 16384) entries: mvpLocalMapLines_InFrustum as slots, ascending.  The caller does
+                                   * IncreaseVisible() from this list and from the held lines; the library holds no such counters. */
+    float *proj; float *view_cos; int32_t *level;      /* optional, per in-view entry: (u1, v1, u2, v2), mTrackViewCos, mnTrackScaleLevel */
+    int32_t *match_idx, *match_dist;                   /* optional, per in-view entry: the frame line it was assigned to (-1 / 256 = none) */
+    int32_t *n_par, *n_perp;      /* out, n_kl each: mvParallelLines[i]->size(), mvPerpLines[i]->size() */
+    int8_t *rel_map;              /* optional, n_kl x n_in_view (room for n_kl x min(slots, 16384)), rows packed at n_in_view: 0 / 1 parallel /
+                                   * 2 perpendicular against in-view entry j (the convention of hvo_line_struct_optimize's rel).  Not computed
+                                   * into host memory unless given.  mvLineEq is the line_eq of the hvo_line3d records: on a resident frame
+                                   * after hvo_stream_line_struct_optimize those are the optimised lines.  A (-1,-1,-1) or zero line_eq is not
+                                   * skipped (the reference does not); NaN compares false both ways and gives 0. */
+} hvo_local_lines_io;
+typedef struct {
+    int32_t n_slots_tested;       /* slots that reached isInFrustum (not bad, not seen) */
+    int32_t n_in_view;            /* nToMatch */
+    int32_t n_matches;            /* SearchByProjection's return value (0 when it did not run: nothing in view) */
+    int32_t n_gated;              /* held lines the post-gate removed, lines held before the call included (it runs only when n_matches > 0) */
+    int32_t status;
+    float kernel_ms[3];           /* device time of the call: mark + frustum + compaction, the search, assignment + post-gate + constraints */
+} hvo_local_lines_result;
+/* On host arrays.  cam: fx, fy, cx, cy are read.  Tcw: rows 0..2 of the pose, row-major 3 x 4.  Limits: 2048 frame lines, 16384 lines in
+ * view -- more gives HVO_ERR_UNSUPPORTED, never a truncated search: no output of io is written (held stays as passed in) and res
+ * carries n_in_view and status.  The in-view counts come back to the host once in the middle of the call (the search's grid depends on them). */
+int hvo_search_local_lines(hvo_ctx *ctx, hvo_line_map *m, const hvo_camera *cam, const float Tcw[12], const hvo_local_lines_params *params,
+                           const hvo_local_lines_frame *frame, hvo_local_lines_io *io, hvo_local_lines_result *res);
+/* On the resident frame `cur`: key lines, line functions, descriptors, line grid and 3-D lines are read where the stages left them; the pose,
+ * held and seen_extra go up.  io->n_kl must be at least the frame's key-line count.  The stream must run an LSD stage, HVO_STAGE_GRIDS and
+ * HVO_STAGE_LINES3D on a frame submitted with depth: otherwise HVO_ERR_INVALID_ARG with hvo_stream_last_error set. */
+int hvo_stream_search_local_lines(hvo_stream *s, hvo_line_map *m, int64_t cur, const hvo_camera *cam, const float Tcw[12],
+                                  const hvo_local_lines_params *params, hvo_local_lines_io *io, hvo_local_lines_result *res);
+/* On the first n frames of the resident batch (after hvo_batch_run with an LSD stage, HVO_STAGE_GRIDS and HVO_STAGE_LINES3D on frames
+ * uploaded with depth): frame k under Tcw + 12 k with io[k] / res[k]; the map is read once for all frames.  Frame k equals the stream form
+ * on the same image bit for bit. */
+int hvo_batch_search_local_lines(hvo_ctx *ctx, hvo_line_map *m, int n, const hvo_camera *cam, const float *Tcw, const hvo_local_lines_params *params,
+                                 hvo_local_lines_io *io, hvo_local_lines_result *res);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer. Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

@@ -571,6 +571,68 @@ private:
     float th_[4];
 };
 
+// The local map's lines resident on one device (hvo_line_map): per slot GetWorldPos(), GetWorldVector(), GetNormal(), mfMaxDistance,
+// mfMinDistance, GetDescriptor(), isBad() and Observations() > 0.  The slot index is the position in mvpLocalMapLines: the tracker calls
+// setMany() after UpdateLocalLines has rebuilt that vector.  Not thread-safe.
+class LineMap {
+public:
+    explicit LineMap(int device = 0, int slots = 0) : m_(hvo_line_map_create(device, slots))
+    {
+        if (!m_) throw Error(HVO_ERR_HIP, "hvo_line_map_create");
+    }
+    ~LineMap() { hvo_line_map_destroy(m_); }
+    LineMap(const LineMap &) = delete;
+    LineMap &operator=(const LineMap &) = delete;
+    void set(int slot, const double pos[6], const double wvec[3], const double normal[3], float maxDistance, float minDistance, const uint8_t desc[32], bool observed = true)
+    {
+        check(hvo_line_map_set(m_, slot, pos, wvec, normal, maxDistance, minDistance, desc, observed ? 1 : 0), "hvo_line_map_set");
+    }
+    void setMany(int first, int n, const double *pos, const double *wvec, const double *normal, const float *maxDistance, const float *minDistance,
+                 const uint8_t *desc, const uint8_t *observed = nullptr, const uint8_t *bad = nullptr)
+    {
+        check(hvo_line_map_set_many(m_, first, n, pos, wvec, normal, maxDistance, minDistance, desc, observed, bad), "hvo_line_map_set_many");
+    }
+    void setBad(int slot, bool bad = true) { check(hvo_line_map_set_bad(m_, slot, bad ? 1 : 0), "hvo_line_map_set_bad"); }
+    void setObserved(int slot, bool observed = true) { check(hvo_line_map_set_observed(m_, slot, observed ? 1 : 0), "hvo_line_map_set_observed"); }
+    int size() const { int n = 0; check(hvo_line_map_counts(m_, &n, nullptr, nullptr), "hvo_line_map_counts"); return n; }
+    const char *lastError() const { return hvo_line_map_last_error(m_); }
+    hvo_line_map *get() const { return m_; }
+private:
+    hvo_line_map *m_;
+};
+
+// Tracking::SearchLocalLines (src/Tracking.cc:3279-3392) together with Manhattan::computeStructConstInMap (src/Manhattan.cpp:163-224) over a
+// resident LineMap: io.held carries mvpMapLines as slots in and out, io.in_view_slot returns mvpLocalMapLines_InFrustum; the return value
+// is SearchByProjection's nmatches.  th: 1, or 5 right after a relocalisation.
+class LocalLines {
+public:
+    LocalLines(const hvo_camera &cam, float logScaleFactor, float nnratio = 0.95f) : cam_(cam) { p_ = hvo_local_lines_params(); p_.log_scale_factor = logScaleFactor; p_.nn_ratio = nnratio; }
+    // on host arrays; bounds4 = mnMinX, mnMaxX, mnMinY, mnMaxY
+    int SearchLocalLines(hvo_ctx *ctx, const LineMap &map, const float Tcw[12], const float bounds4[4], const hvo_local_lines_frame &frame, hvo_local_lines_io &io,
+                         hvo_local_lines_result &res, float th = 1.0f) const
+    {
+        hvo_local_lines_params p = p_; p.th = th;
+        for (int k = 0; k < 4; k++) p.bounds[k] = bounds4[k];
+        check(hvo_search_local_lines(ctx, map.get(), &cam_, Tcw, &p, &frame, &io, &res), "hvo_search_local_lines");
+        return res.n_matches;
+    }
+    // on the resident frame `cur` of a stream (an LSD stage, HVO_STAGE_GRIDS, HVO_STAGE_LINES3D, depth); call before collect() releases the slot
+    int SearchLocalLines(FrameStream &fs, int64_t cur, const LineMap &map, const float Tcw[12], hvo_local_lines_io &io, hvo_local_lines_result &res, float th = 1.0f) const
+    {
+        hvo_local_lines_params p = p_; p.th = th;
+        check(hvo_stream_search_local_lines(fs.get(), map.get(), cur, &cam_, Tcw, &p, &io, &res), "hvo_stream_search_local_lines");
+        return res.n_matches;
+    }
+    // on the first n frames of the context's resident batch, frame k under Tcw + 12 k with io[k] / res[k]
+    void SearchLocalLinesBatch(hvo_ctx *ctx, const LineMap &map, int n, const float *Tcw, hvo_local_lines_io *io, hvo_local_lines_result *res, float th = 1.0f) const
+    {
+        hvo_local_lines_params p = p_; p.th = th;
+        check(hvo_batch_search_local_lines(ctx, map.get(), n, &cam_, Tcw, &p, io, res), "hvo_batch_search_local_lines");
+    }
+private:
+    hvo_camera cam_; hvo_local_lines_params p_;
+};
+
 // Optimizer (include/Optimizer.h, src/Optimizer.cc:590-1478): PoseOptimization on the mirror's frame handle.  The map side (one row per feature:
 // the matched map point's / map line's world position, the planes of the three roles as world coefficients or as slots of a PlaneMap) is what
 // the tracker fills from mvpMapPoints / mvpMapLines / mvpMapPlanes...; the frame side is read from the resident frame.  The optimised pose comes
