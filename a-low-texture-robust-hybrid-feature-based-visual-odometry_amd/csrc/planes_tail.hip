@@ -686,12 +686,16 @@ static void sn_carve(SnArgs &a, int w, int h, char *base, size_t &bytes)
 }
 size_t sn_scratch_bytes(int w, int h) { SnArgs a; memset(&a, 0, sizeof(a)); size_t b; sn_carve(a, w, h, nullptr, b); return b; }
 int sn_count(int w, int h) { return (((h + 2) / 3) / 2) * (((w + 2) / 3) / 2); }
+// k_sn_serial's dynamic LDS: nine waves, three rows of W + 2 doubles each; a width whose rows do not fit in 160 KiB is refused
+static size_t sn_lds_bytes(int w) { return (size_t)9 * 3 * ((w + 2) / 3 + 2) * sizeof(double); }
 
 // device-resident form: depth in HBM, scratch of sn_scratch_bytes(w, h), d_out with sn_count(w, h) entries
 int sn_enqueue(hvo_ctx *ctx, hipStream_t st, const uint16_t *d_depth, int pitch, int w, int h, void *scratch, hvo_surface_normal *d_out)
 {
     SnArgs a; memset(&a, 0, sizeof(a));
     size_t b; sn_carve(a, w, h, (char *)scratch, b);
+    const size_t lds = sn_lds_bytes(w);
+    if (lds > 160 * 1024) return HVO_ERR_UNSUPPORTED;                         // refused before anything is launched
     a.pitch = pitch; a.depth = d_depth;
     a.fx = ctx->p.fx; a.fy = ctx->p.fy; a.cx = ctx->p.cx; a.cy = ctx->p.cy; a.dfac = ctx->p.depth_map_factor;
     const size_t N = (size_t)a.W * a.H;
@@ -699,12 +703,8 @@ int sn_enqueue(hvo_ctx *ctx, hipStream_t st, const uint16_t *d_depth, int pitch,
     a.out = d_out; a.cap = nout;
     hipLaunchKernelGGL(k_sn_cloud, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_sn_grad, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
-    {
-        const size_t lds = (size_t)9 * 3 * (a.W + 2) * sizeof(double);
-        if (lds > 160 * 1024) return HVO_ERR_UNSUPPORTED;
-        if (hvo_ensure_dyn_lds(reinterpret_cast<const void *>(k_sn_serial), lds)) return HVO_ERR_HIP;
-        hipLaunchKernelGGL(k_sn_serial, dim3(1), dim3(576), lds, st, a);
-    }
+    if (hvo_ensure_dyn_lds(reinterpret_cast<const void *>(k_sn_serial), lds)) return HVO_ERR_HIP;
+    hipLaunchKernelGGL(k_sn_serial, dim3(1), dim3(576), lds, st, a);
     if (nout > 0) hipLaunchKernelGGL(k_sn_normals, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, a);
     HVO_HIP(hipGetLastError());
     return HVO_OK;
@@ -715,6 +715,7 @@ extern "C" int hvo_surface_normals(hvo_ctx *ctx, const uint16_t *depth, int w, i
     if (!ctx || !n) return HVO_ERR_INVALID_ARG;
     *n = 0;
     if (!depth || !out || cap < 0 || w < 3 || h < 3 || stride < 2 * w) return HVO_ERR_INVALID_ARG;
+    if (sn_lds_bytes(w) > 160 * 1024) return HVO_ERR_UNSUPPORTED;           // before the upload: nothing is copied, nothing is launched
     if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
     hipStream_t st = ctx->stream;
     const int nout = sn_count(w, h);
