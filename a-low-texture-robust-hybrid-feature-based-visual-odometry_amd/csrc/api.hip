@@ -921,9 +921,10 @@ int hvo_search_by_projection(hvo_ctx *ctx, const uint8_t *q_desc, int nq, const 
     *n_matches = 0;
     if (nq == 0) return HVO_OK;
     if (!q_desc || !q_u || !q_v || !q_radius || !q_min_level || !q_max_level || !q_angle || !q_blocks || !match_idx || !match_dist) return HVO_ERR_INVALID_ARG;
+    if (nq > 16384 || nt > 65535) return HVO_ERR_UNSUPPORTED;       // the guided search's limits (match.hip), before any output is written
     for (int i = 0; i < nq; i++) { match_idx[i] = -1; match_dist[i] = 256; }
     if (nt == 0) return HVO_OK;
-    if (!t_kp || !t_desc || nt > 65535 || !(mnMaxX > mnMinX) || !(mnMaxY > mnMinY)) return HVO_ERR_INVALID_ARG;
+    if (!t_kp || !t_desc || !(mnMaxX > mnMinX) || !(mnMaxY > mnMinY)) return HVO_ERR_INVALID_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
     return match_search_by_projection(ctx, q_desc, nq, q_u, q_v, q_radius, q_min_level, q_max_level, q_ur, q_angle, q_blocks, t_kp, t_uright, t_occupied,
                                       t_desc, nt, mnMinX, mnMinY, mnMaxX, mnMaxY, th_high, check_orientation, 0, 0.f, match_idx, match_dist, n_matches);
@@ -941,10 +942,11 @@ int hvo_search_by_projection_tracked(hvo_ctx *ctx, const uint8_t *q_desc, int nq
     *n_matches = 0;
     if (nq == 0) return HVO_OK;
     if (!q_desc || !proj_x || !proj_y || !level || !view_cos || !q_blocks || !match_idx || !match_dist) return HVO_ERR_INVALID_ARG;
+    if (nq > 16384 || nt > 65535) return HVO_ERR_UNSUPPORTED;       // the guided search's limits (match.hip), before any output is written
     for (int i = 0; i < nq; i++) if (level[i] < 0 || level[i] >= ctx->p.orb_nlevels) return HVO_ERR_INVALID_ARG;      // mvScaleFactors[level] on the device
     for (int i = 0; i < nq; i++) { match_idx[i] = -1; match_dist[i] = 256; }
     if (nt == 0) return HVO_OK;
-    if (!t_kp || !t_desc || nt > 65535 || !(mnMaxX > mnMinX) || !(mnMaxY > mnMinY)) return HVO_ERR_INVALID_ARG;
+    if (!t_kp || !t_desc || !(mnMaxX > mnMinX) || !(mnMaxY > mnMinY)) return HVO_ERR_INVALID_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
     return match_search_by_projection_tracked(ctx, q_desc, nq, proj_x, proj_y, proj_xr, level, view_cos, q_blocks, th, t_kp, t_uright, t_occupied,
                                               t_desc, nt, mnMinX, mnMinY, mnMaxX, mnMaxY, th_high, nn_ratio, match_idx, match_dist, n_matches);
@@ -960,9 +962,10 @@ int hvo_search_by_projection_map(hvo_ctx *ctx, const uint8_t *q_desc, int nq, co
     *n_matches = 0;
     if (nq == 0) return HVO_OK;
     if (!q_desc || !q_u || !q_v || !q_radius || !q_min_level || !q_max_level || !q_blocks || !match_idx || !match_dist) return HVO_ERR_INVALID_ARG;
+    if (nq > 16384 || nt > 65535) return HVO_ERR_UNSUPPORTED;       // the guided search's limits (match.hip), before any output is written
     for (int i = 0; i < nq; i++) { match_idx[i] = -1; match_dist[i] = 256; }
     if (nt == 0) return HVO_OK;
-    if (!t_kp || !t_desc || nt > 65535 || !(mnMaxX > mnMinX) || !(mnMaxY > mnMinY)) return HVO_ERR_INVALID_ARG;
+    if (!t_kp || !t_desc || !(mnMaxX > mnMinX) || !(mnMaxY > mnMinY)) return HVO_ERR_INVALID_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
     return match_search_by_projection(ctx, q_desc, nq, q_u, q_v, q_radius, q_min_level, q_max_level, q_ur, nullptr, q_blocks, t_kp, t_uright, t_occupied,
                                       t_desc, nt, mnMinX, mnMinY, mnMaxX, mnMaxY, th_high, 0, 1, nn_ratio, match_idx, match_dist, n_matches);

@@ -171,7 +171,9 @@ int hvo_search_lines_by_projection(hvo_ctx *ctx, int nq, const float *q_xyxy, co
  * key-point angle (rotation histogram) and q_blocks[i] != 0 when the map point has observations (the feature
  * it claims is then skipped by later queries, :1425-1427).  t_* describe the current frame: undistorted key
  * points, mvuRight (may be NULL), features already holding an observed map point (may be NULL), descriptors;
- * mnMin/Max are the frame's image bounds (64 x 48 grid).  match_idx[i] = current-frame index or -1. */
+ * mnMin/Max are the frame's image bounds (64 x 48 grid).  match_idx[i] = current-frame index or -1.
+ * At most 16384 queries and 65535 current-frame features (also for the _map and _tracked forms): more is HVO_ERR_UNSUPPORTED and
+ * match_idx / match_dist are left as they were. */
 int hvo_search_by_projection(hvo_ctx *ctx, const uint8_t *q_desc, int nq, const float *q_u, const float *q_v, const float *q_radius,
                              const int32_t *q_min_level, const int32_t *q_max_level, const float *q_ur, const float *q_angle,
                              const uint8_t *q_blocks, const hvo_keypoint *t_kp, const float *t_uright, const uint8_t *t_occupied,

@@ -111,3 +111,40 @@ def test_search_by_projection_tracked(gpu_ctx, orc, synth, th):
     no, io, do = orc.search_by_projection_map(d1, px, py, rad, lo, hi, pxr, blocks, kp2, t_uright, t_occ, d2, BOUNDS, th_high=100, nn_ratio=0.8)
     ng, ig, dg = gpu_ctx.search_by_projection_tracked(d1, px, py, pxr, level, vcos, blocks, th, kp2, t_uright, t_occ, d2, BOUNDS, th_high=100, nn_ratio=0.8)
     assert no > 50 and ng == no and np.array_equal(ig, io) and np.array_equal(dg[ig >= 0], do[io >= 0])
+
+
+@pytest.mark.parametrize("n", [1, 257])
+def test_stereo_from_rgbd_view_and_edges(hvo, gpu_ctx, orc, n):
+    """a 37 x 29 depth image that is a view into a wider parent (stride != 2 * w); key points that truncate onto and off every edge
+    (x = -0.5 -> column 0, x = -1 -> outside, x = w - 0.01 -> column w - 1, x = w -> outside, the same in y) and raw depths 0, 34999, 35000,
+    35001 around the 7 m gate (Frame.cc:1955); one block with a single thread in use, and one thread into a second block"""
+    import ctypes as C
+    w, h = 37, 29
+    rng = np.random.default_rng(37 * 29 + n)
+    parent = rng.integers(1, 30000, (h, 61)).astype(np.uint16)
+    view = parent[:, 11:11 + w]
+    view[3, 4:8] = [0, 34999, 35000, 35001]
+    assert view.strides[0] == 122 != 2 * w
+    pts = [(-0.5, 5.0), (-1.0, 5.0), (w - 0.01, 5.0), (float(w), 5.0), (5.0, -0.5), (5.0, -1.0), (5.0, h - 0.01), (5.0, float(h)),
+           (4.25, 3.75), (5.5, 3.0), (6.0, 3.99), (7.9, 3.5), (0.0, 0.0), (w - 1.0, h - 1.0), (-1e6, 5.0), (1e6, 5.0), (5.0, -1e6), (5.0, 1e6)]
+    kp = np.zeros(n, hvo.KEYPOINT_DT)
+    kp["x"] = rng.uniform(-3, w + 3, n); kp["y"] = rng.uniform(-3, h + 3, n)
+    m = min(n, len(pts))
+    kp["x"][:m] = [p[0] for p in pts[:m]]; kp["y"][:m] = [p[1] for p in pts[:m]]
+    kpun = kp.copy(); kpun["x"] += np.float32(0.25)
+    bf = np.float32(40.0); dfac = np.float32(1.0) / np.float32(5000.0)
+    # by hand
+    u = np.trunc(kp["x"]).astype(np.int64); v = np.trunc(kp["y"]).astype(np.int64)
+    inside = (u >= 0) & (v >= 0) & (u < w) & (v < h)
+    d = np.where(inside, view[np.clip(v, 0, h - 1), np.clip(u, 0, w - 1)], 0).astype(np.float32) * dfac
+    ok = inside & (d > 0) & (d.astype(np.float64) < 7.0)
+    ze = np.where(ok, d, np.float32(-1)); ue = np.where(ok, kpun["x"] - bf / np.where(ok, d, np.float32(1)), np.float32(-1)).astype(np.float32)
+    if n > 1:
+        assert inside[:m].tolist() == [True, False, True, False, True, False, True, False] + [True] * 6 + [False] * 4
+        assert ok[8:12].tolist() == [False, True, bool(np.float32(35000) * dfac < 7.0), False]
+    uo, zo = orc.stereo_from_rgbd(kp, kpun, view, float(dfac), float(bf))
+    assert np.array_equal(zo, ze) and np.array_equal(uo, ue)
+    ug = np.full(n, 77, np.float32); zg = np.full(n, 77, np.float32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = hvo.lib().hvo_stereo_from_rgbd(gpu_ctx.h, p(kp), p(kpun), n, C.c_void_p(view.ctypes.data), w, h, view.strides[0], float(bf), p(ug), p(zg))
+    assert rc == 0 and np.array_equal(zg, zo) and np.array_equal(ug, uo)

@@ -67,3 +67,28 @@ def test_frame_bf_match_parity(gpu_ctx, orc, synth, mutual):
     assert n == 0 and np.all(m == -1)
     n, m = gpu_ctx.frame_bf_match(d1[:0], d2, 50.0, 0.9, mutual)
     assert n == 0 and len(m) == 0
+
+
+@pytest.mark.parametrize("nt", [1, 2, 63, 64, 65, 255, 256, 257])
+def test_knn2_and_matrix_around_the_block_geometry(gpu_ctx, orc, nt):
+    """nq = 5: one full block of four query waves and one with a single wave; nt on either side of the 64-lane stride and of the 256-thread block.
+    Descriptors are one base with 0..9 bits flipped, so every distance ties many times and the lower index has to win"""
+    rng = np.random.default_rng(100 + nt)
+    base = rng.integers(0, 256, 32, dtype=np.uint8)
+    def near(n):
+        bits = np.tile(np.unpackbits(base), (n, 1))
+        for i in range(n):
+            bits[i, rng.choice(256, int(rng.integers(0, 10)), replace=False)] ^= 1
+        return np.packbits(bits, axis=1)
+    q = near(5); t = near(nt)
+    d = gpu_ctx.hamming_matrix(q, t)
+    assert d.shape == (5, nt) and np.array_equal(d, orc.hamming_matrix(q, t))
+    ig, dg = gpu_ctx.hamming_knn2(q, t)
+    io, do = orc.hamming_knn2(q, t)
+    assert np.array_equal(ig, io) and np.array_equal(dg, do)
+    order = np.lexsort((np.arange(nt)[None, :].repeat(5, 0), d.astype(np.int64)), axis=1)        # by hand: ascending distance, ties to the lower index
+    assert np.array_equal(ig[:, 0], order[:, 0]) and np.array_equal(dg[:, 0], d[np.arange(5), order[:, 0]])
+    if nt == 1:
+        assert np.all(ig[:, 1] == -1) and np.all(dg[:, 1] == np.iinfo(np.int32).max)
+    else:
+        assert np.array_equal(ig[:, 1], order[:, 1]) and np.array_equal(dg[:, 1], d[np.arange(5), order[:, 1]])
