@@ -82,6 +82,9 @@ EXPORTS = [
     "hvo_line_map_create", "hvo_line_map_destroy", "hvo_line_map_set", "hvo_line_map_set_many", "hvo_line_map_set_bad", "hvo_line_map_set_observed",
     "hvo_line_map_counts", "hvo_line_map_slot", "hvo_line_map_last_error",
     "hvo_search_local_lines", "hvo_stream_search_local_lines", "hvo_batch_search_local_lines",
+    "hvo_vocabulary_create", "hvo_vocabulary_load_text", "hvo_vocabulary_destroy", "hvo_vocabulary_info",
+    "hvo_compute_bow", "hvo_stream_compute_bow", "hvo_batch_compute_bow", "hvo_search_by_bow", "hvo_stream_search_by_bow",
+    "hvo_bow_last_kernel_ms", "hvo_stream_bow_last_kernel_ms",
 ]
 
 
@@ -296,6 +299,75 @@ def _ll_finish(r, a, n_kl):
     return r
 
 
+VOC_TF_IDF, VOC_TF, VOC_IDF, VOC_BINARY = 0, 1, 2, 3                                                  # DBoW2::WeightingType
+VOC_L1_NORM, VOC_L2_NORM, VOC_CHI_SQUARE, VOC_KL, VOC_BHATTACHARYYA, VOC_DOT_PRODUCT = 0, 1, 2, 3, 4, 5    # DBoW2::ScoringType
+BOW_MAX_FEATURES = 4096
+
+
+class VocabularyDesc(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("k", "L", "n_nodes", "n_words", "scoring", "weighting", "device")]
+
+
+class Bow(C.Structure):
+    _fields_ = [("cap", C.c_int32), ("word_id", C.c_void_p), ("node_id", C.c_void_p), ("bow_word", C.c_void_p), ("bow_value", C.c_void_p),
+                ("fv_node", C.c_void_p), ("fv_start", C.c_void_p), ("fv_index", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("n_features", "n_words", "n_nodes", "n_valid", "n_short", "computed", "status")]
+
+
+class BowKeyframe(C.Structure):
+    _fields_ = [("desc", C.c_void_p), ("node_id", C.c_void_p), ("has_map_point", C.c_void_p), ("angle", C.c_void_p), ("n", C.c_int32)]
+
+
+class BowSearchParams(C.Structure):
+    _fields_ = [("nnratio", C.c_float), ("check_orientation", C.c_int32), ("th_low", C.c_int32)]
+
+
+class BowMatches(C.Structure):
+    _fields_ = [("match_kf", C.c_void_p), ("n_matches", C.c_int32), ("status", C.c_int32)]
+
+
+def _bow_out(cap):
+    """an hvo_bow with room for `cap` features and the arrays behind it"""
+    cap = max(int(cap), 1)
+    a = dict(word_id=np.full(cap, -1, np.int32), node_id=np.full(cap, -1, np.int32), bow_word=np.zeros(cap, np.int32), bow_value=np.zeros(cap, np.float64),
+             fv_node=np.zeros(cap, np.int32), fv_start=np.zeros(cap + 1, np.int32), fv_index=np.zeros(cap, np.int32))
+    b = Bow(); b.cap = cap
+    for k, v in a.items():
+        setattr(b, k, v.ctypes.data)
+    return b, a
+
+
+def _bow_finish(b, a):
+    """dict(word_id, node_id per feature; bow_word, bow_value; fv_node, fv_start, fv_index; n_short, computed)"""
+    n = b.n_features
+    return dict(word_id=a["word_id"][:n].copy(), node_id=a["node_id"][:n].copy(), bow_word=a["bow_word"][:b.n_words].copy(), bow_value=a["bow_value"][:b.n_words].copy(),
+                fv_node=a["fv_node"][:b.n_nodes].copy(), fv_start=a["fv_start"][:b.n_nodes + 1].copy(), fv_index=a["fv_index"][:b.n_valid].copy(),
+                n_short=b.n_short, computed=bool(b.computed))
+
+
+def _bow_side(desc, node_id, has_map_point=None, angle=None):
+    d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32); n = len(d)
+    keep = [d, np.ascontiguousarray(node_id, np.int32).reshape(n),
+            np.ones(n, np.uint8) if has_map_point is None else np.ascontiguousarray(np.asarray(has_map_point).astype(bool), np.uint8).reshape(n),
+            np.zeros(n, np.float32) if angle is None else np.ascontiguousarray(angle, np.float32).reshape(n)]
+    k = BowKeyframe(); k.n = n
+    k.desc, k.node_id, k.has_map_point, k.angle = [v.ctypes.data if n else None for v in keep]
+    return k, keep
+
+
+def _bow_search_args(n_frame, kfs, nnratio, check_orientation, th_low):
+    """kfs: a list of dict(desc, node_id, has_map_point, angle) or of tuples in that order"""
+    keep = []; K = (BowKeyframe * len(kfs))()
+    for j, kf in enumerate(kfs):
+        k, kp = _bow_side(**kf) if isinstance(kf, dict) else _bow_side(*kf)
+        K[j] = k; keep.append(kp)
+    P = BowSearchParams(float(nnratio), 1 if check_orientation else 0, int(th_low))
+    R = (BowMatches * len(kfs))(); m = np.full((len(kfs), max(n_frame, 1)), -1, np.int32)
+    for j in range(len(kfs)):
+        R[j].match_kf = m[j].ctypes.data
+    return K, P, R, m, keep
+
+
 def line_struct_params(**kw):
     """the reference's values (hvo_line_struct_default_params) with the given fields replaced (mode, row_rule, ...)"""
     p = LineStructParams()
@@ -508,6 +580,17 @@ def lib():
                                                     C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]
         L.hvo_batch_search_local_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalLinesParams),
                                                    C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]
+        L.hvo_vocabulary_create.argtypes = [C.c_int] * 6 + [C.c_void_p] * 4 + [C.POINTER(C.c_void_p)]
+        L.hvo_vocabulary_load_text.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.hvo_vocabulary_destroy.argtypes = [C.c_void_p]; L.hvo_vocabulary_destroy.restype = None
+        L.hvo_vocabulary_info.argtypes = [C.c_void_p, C.POINTER(VocabularyDesc)]
+        L.hvo_compute_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Bow)]
+        L.hvo_stream_compute_bow.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(Bow)]
+        L.hvo_batch_compute_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Bow)]
+        L.hvo_search_by_bow.argtypes = [C.c_void_p, C.POINTER(BowKeyframe), C.c_int, C.POINTER(BowKeyframe), C.POINTER(BowSearchParams), C.POINTER(BowMatches)]
+        L.hvo_stream_search_by_bow.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(BowKeyframe), C.POINTER(BowSearchParams), C.POINTER(BowMatches)]
+        L.hvo_bow_last_kernel_ms.argtypes = [C.c_void_p, C.c_void_p]
+        L.hvo_stream_bow_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.hvo_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_stream_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_search_by_projection_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
@@ -675,6 +758,47 @@ class LineMap:
         mx, mn, b, o = C.c_float(0), C.c_float(0), C.c_int(0), C.c_int(0)
         self._chk(lib().hvo_line_map_slot(self.h, slot, _p(pos), _p(w), _p(nr), C.byref(mx), C.byref(mn), _p(d), C.byref(b), C.byref(o)), "line_map_slot")
         return dict(pos=pos, wvec=w, normal=nr, max_dist=mx.value, min_dist=mn.value, desc=d, bad=bool(b.value), observed=bool(o.value))
+
+
+class Vocabulary:
+    """hvo_vocabulary: the ORB vocabulary (a k-ary tree of 32-byte descriptors) resident on one device, read-only.  The arrays are in the order
+    of the reference's text format: row i is node i + 1 (node 0, the root, has no row).  device=-1 makes a host-only vocabulary (validated,
+    answers info(), computes nothing)."""
+
+    def __init__(self, k, L, parent, is_leaf, desc, weight, scoring=VOC_L1_NORM, weighting=VOC_TF_IDF, device=0):
+        parent = np.ascontiguousarray(parent, np.int32).reshape(-1); n = len(parent)
+        a = [parent, np.ascontiguousarray(np.asarray(is_leaf).astype(bool), np.uint8).reshape(n), np.ascontiguousarray(desc, np.uint8).reshape(n, 32),
+             np.ascontiguousarray(weight, np.float64).reshape(n)]
+        h = C.c_void_p()
+        rc = lib().hvo_vocabulary_create(device, k, L, scoring, weighting, n, *[_p(v) if n else None for v in a], C.byref(h))
+        if rc != HVO_OK:
+            raise HvoError(rc, "hvo_vocabulary_create")
+        self.h = h
+
+    @classmethod
+    def load_text(cls, path, device=0):
+        """the reference's text format (ORBvoc.txt); the binary format is not read"""
+        h = C.c_void_p()
+        rc = lib().hvo_vocabulary_load_text(os.fsencode(path), device, C.byref(h))
+        if rc != HVO_OK:
+            raise HvoError(rc, "hvo_vocabulary_load_text")
+        v = cls.__new__(cls); v.h = h
+        return v
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().hvo_vocabulary_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def info(self):
+        """dict(k, L, n_nodes (the root included), n_words, scoring, weighting, device)"""
+        d = VocabularyDesc()
+        rc = lib().hvo_vocabulary_info(self.h, C.byref(d))
+        if rc != HVO_OK:
+            raise HvoError(rc, "hvo_vocabulary_info")
+        return {k: getattr(d, k) for k, _ in VocabularyDesc._fields_}
 
 
 class Context:
@@ -1044,6 +1168,41 @@ class Context:
         res = (LocalLinesResult * n)()
         self._chk(lib().hvo_batch_search_local_lines(self.h, lmap.h, n, C.byref(c), _p(T), C.byref(p), ios, res), "batch_search_local_lines")
         return [_ll_finish(res[k], arrs[k], int(n_kl[k])) for k in range(n)]
+
+    def compute_bow(self, voc, descs, levelsup=4):
+        """Frame::ComputeBoW on host descriptors: descs is one (n, 32) array or a list of them (all frames in one launch sequence)"""
+        single = not isinstance(descs, (list, tuple))
+        ds = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in ([descs] if single else descs)]
+        nf = len(ds); B = (Bow * nf)(); keep = []
+        for f, d in enumerate(ds):
+            B[f], a = _bow_out(len(d)); keep.append(a)
+        ptr = (C.c_void_p * nf)(*[d.ctypes.data if len(d) else None for d in ds]); nd = np.array([len(d) for d in ds], np.int32)
+        self._chk(lib().hvo_compute_bow(self.h, voc.h, levelsup, nf, ptr, _p(nd), B), "compute_bow")
+        r = [_bow_finish(B[f], keep[f]) for f in range(nf)]
+        return r[0] if single else r
+
+    def batch_compute_bow(self, voc, n, levelsup=4, cap=None):
+        """the same on the first n frames of the resident batch; the result stays with the batch until the next batch_run"""
+        cap = cap or BOW_MAX_FEATURES
+        B = (Bow * n)(); keep = []
+        for f in range(n):
+            B[f], a = _bow_out(cap); keep.append(a)
+        self._chk(lib().hvo_batch_compute_bow(self.h, voc.h, n, levelsup, B), "batch_compute_bow")
+        return [_bow_finish(B[f], keep[f]) for f in range(n)]
+
+    def bow_last_kernel_ms(self):
+        """(ComputeBoW kernels, SearchByBoW kernels): device ms of the last calls"""
+        ms = np.zeros(2, np.float32)
+        self._chk(lib().hvo_bow_last_kernel_ms(self.h, _p(ms)), "bow_last_kernel_ms")
+        return float(ms[0]), float(ms[1])
+
+    def search_by_bow(self, frame, kfs, nnratio=0.7, check_orientation=True, th_low=50):
+        """ORBmatcher::SearchByBoW on host arrays: frame = dict(desc, node_id, angle), kfs = list of dict(desc, node_id, has_map_point, angle).
+        Returns a list of (match_kf, n_matches), one per key frame."""
+        F, fkeep = _bow_side(frame["desc"], frame["node_id"], None, frame.get("angle"))
+        K, P, R, m, keep = _bow_search_args(F.n, kfs, nnratio, check_orientation, th_low)
+        self._chk(lib().hvo_search_by_bow(self.h, C.byref(F), len(kfs), K, C.byref(P), R), "search_by_bow")
+        return [(m[j, :F.n].copy(), R[j].n_matches) for j in range(len(kfs))]
 
     def set_readings(self, blur_float=False, lsd_8u=False):
         """the alternative readings of cv::GaussianBlur / cv::LineSegmentDetector (include/hvo.h HVO_READING_*); the next extraction uses them"""
@@ -1453,6 +1612,25 @@ class Stream:
                                                         _p(q_max_level), pp(q_ur), _p(q_blocks), pp(t_occupied), th_high, 1 if check_orientation else 0,
                                                         _p(mi), _p(md), C.byref(n)), "stream_search_by_projection")
         return n.value, mi[:nq], md[:nq]
+
+    def compute_bow(self, ticket, voc, levelsup=4):
+        """Frame::ComputeBoW on the resident frame `ticket`; kept with the frame (a second call with the same arguments returns computed=False)"""
+        b, a = _bow_out(self.kp_cap)
+        self._chk(lib().hvo_stream_compute_bow(self.h, ticket, voc.h, levelsup, C.byref(b)), "stream_compute_bow")
+        return _bow_finish(b, a)
+
+    def bow_last_kernel_ms(self, cur):
+        """(ComputeBoW kernels, SearchByBoW kernels): device ms of the last calls on the resident frame `cur`"""
+        ms = np.zeros(2, np.float32)
+        self._chk(lib().hvo_stream_bow_last_kernel_ms(self.h, cur, _p(ms)), "stream_bow_last_kernel_ms")
+        return float(ms[0]), float(ms[1])
+
+    def search_by_bow(self, cur, voc, kfs, nnratio=0.7, check_orientation=True, th_low=50):
+        """SearchByBoW of the key frames kfs (dicts of desc, node_id, has_map_point, angle) against the resident frame `cur`, which holds its bag
+        of words.  Returns a list of (match_kf, n_matches); match_kf has the stream's key-point capacity, entries past the frame's count are -1."""
+        K, P, R, m, keep = _bow_search_args(self.kp_cap, kfs, nnratio, check_orientation, th_low)
+        self._chk(lib().hvo_stream_search_by_bow(self.h, cur, voc.h, len(kfs), K, C.byref(P), R), "stream_search_by_bow")
+        return [(m[j].copy(), R[j].n_matches) for j in range(len(kfs))]
 
     def set_readings(self, blur_float=False, lsd_8u=False):
         lib().hvo_stream_set_readings.argtypes = [C.c_void_p, C.c_uint]

@@ -127,6 +127,7 @@ void hvo_destroy(hvo_ctx *ctx)
     for (auto &e : ctx->perms) (void)hipFree(e.second);
     ctx->perms.clear();
     tail_batch_free(ctx);
+    bow_state_free(&ctx->bow_batch); bow_state_free(&ctx->bow_call);
     if (ctx->call_arena) (void)hipFree(ctx->call_arena);
     orb_free_plan(ctx);
     match_free(ctx);
@@ -150,6 +151,7 @@ void hvo_destroy(hvo_ctx *ctx)
     if (ctx->ev_lsd_pre) (void)hipEventDestroy(ctx->ev_lsd_pre);
     if (ctx->ev_fast) (void)hipEventDestroy(ctx->ev_fast);
     for (hipEvent_t e : ctx->po_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->bow_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ls_ev) if (e) (void)hipEventDestroy(e);
     delete ctx;
 }
@@ -376,6 +378,7 @@ int hvo_batch_run(hvo_ctx *ctx, unsigned stages)
     // the rest of the Frame constructor on the resident results (tail.hip)
     ctx->last_stages &= ~(HVO_STAGE_LINES3D | HVO_STAGE_VP | HVO_STAGE_PLANE_TAIL | HVO_STAGE_GRIDS);
     ctx->ls_batch_done = false;
+    ctx->bow_batch.valid = false;
     return tail_batch_run(ctx, stages);
 }
 

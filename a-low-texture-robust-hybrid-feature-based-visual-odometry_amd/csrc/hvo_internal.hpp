@@ -83,6 +83,9 @@ struct OrbPlan {
     int *d_flags = nullptr;             // per frame error flags
 };
 
+// bow.hip: a frame's (or a resident batch's) bag of words as it stays on the device, with what it was computed from
+struct BowState { char *d_blk = nullptr; size_t bytes = 0; unsigned long long voc_uid = 0; int levelsup = 0, n = 0, cap = 0; bool valid = false; };
+
 struct ProfileRec { const char *name; hipEvent_t e0, e1; float ms; bool used; hipStream_t st; };
 
 // A tuning variable (environment) as it stood when a context or a plan was BUILT: launches read the copy, never the environment
@@ -151,6 +154,8 @@ struct hvo_ctx {
     hipEvent_t ls_ev[3] = { nullptr, nullptr, nullptr }; float ls_ms[2] = { 0.f, 0.f };   // line_opt.hip: events around the last call's two launches
     bool ls_batch_done = false;            // hvo_batch_line_struct_optimize has optimised the resident batch's 3-D lines (cleared by hvo_batch_run)
     void *tail = nullptr;                  // resident-batch Frame tail (tail.hip)
+    hipEvent_t bow_ev[4] = { nullptr, nullptr, nullptr, nullptr }; float bow_ms[2] = { 0.f, 0.f }; bool bow_ev_on[2] = { false, false };   // bow.hip: events around the last calls' launches
+    BowState bow_batch, bow_call;          // bow.hip: the resident batch's bag of words (cleared by hvo_batch_run), the host-array form's block
     // opaque per-subsystem state (peac.hip / lsd.hip own these)
     void *peac = nullptr;
     void *lsd = nullptr;
@@ -234,6 +239,30 @@ static __device__ __forceinline__ float hvo_fatan2_deg(float y, float x)
     if (x < 0) r = __fsub_rn(180.f, r);
     if (y < 0) r = __fsub_rn(360.f, r);
     return r;
+}
+
+// the rotation bin of an accepted match and ComputeThreeMaxima (ORBmatcher.cc:1630-1673), shared by the guided search (match.hip) and
+// SearchByBoW (bow.hip)
+static __device__ __forceinline__ int hvo_rot_bin(float angle_a, float angle_b, float factor)
+{
+    float r = __fsub_rn(angle_a, angle_b);
+    if (r < 0.0f) r = __fadd_rn(r, 360.0f);
+    int bin = (int)roundf(__fmul_rn(r, factor));
+    if (bin == 30) bin = 0;
+    return bin;
+}
+static __device__ __forceinline__ void hvo_three_maxima(const int *hist, int *keep)
+{
+    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    for (int b = 0; b < 30; b++) {
+        const int s = hist[b];
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = b; }
+        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = b; }
+        else if (s > max3) { max3 = s; ind3 = b; }
+    }
+    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
+    else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+    keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
 }
 
 static inline int hvo_grid(long long items, int wg_per_cu) {
@@ -441,6 +470,24 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
            const LlFrameDev *fr, const float *Tcw, hvo_local_lines_io *io, hvo_local_lines_result *res);
 int ll_map_device(const hvo_line_map *m);
 const char *ll_map_error(const hvo_line_map *m);
+
+// bow.hip: the resident vocabulary, ComputeBoW and SearchByBoW
+#define HVO_BOW_MAXN 4096                  // features of a frame (the sort keys of one frame live in 32 KB of LDS)
+struct BowLayout { int cap; size_t counts, word_id, node_id, flag, weight, bow_word, bow_val, fv_node, fv_start, fv_idx, total; };   // a frame's block for `cap` features
+void bow_layout(int cap, BowLayout &L);
+void bow_state_free(BowState *b);
+int bow_voc_device(const hvo_vocabulary *v);
+unsigned long long bow_voc_uid(const hvo_vocabulary *v);
+// ComputeBoW of nframes frames on stream st: frame f's descriptors at d_desc + f * desc_stride, its count at d_n[f * n_stride] (h_n: the same
+// counts on the host), blocks of `cap` features kept in *keep.  may_keep: a call with the vocabulary and levelsup the kept result was made
+// with launches nothing.  Returns after the stream has drained, out[f] filled.
+int bow_transform(hvo_ctx *ctx, hipStream_t st, const hvo_vocabulary *v, int levelsup, int nframes, const uint8_t *d_desc, size_t desc_stride,
+                  const int *d_n, int n_stride, int cap, const int *h_n, BowState *keep, bool may_keep, hvo_bow *out, std::string *err);
+// SearchByBoW's frame side: host arrays (h_desc set) or a resident frame's descriptors, angles and the FeatureVector rows of its block
+struct BowFrameSide { int n; const uint8_t *h_desc; const int32_t *h_node; const float *h_angle;
+                      const uint8_t *d_desc; const float *d_angle; int angle_step; const int *d_fv_node, *d_fv_start, *d_fv_idx, *d_n_rows; };
+int bow_search(hvo_ctx *ctx, hipStream_t st, const BowFrameSide &F, int n_kf, const hvo_bow_keyframe *kf, const hvo_bow_search_params *P,
+               hvo_bow_matches *res, std::string *err);
 
 // pose_opt.hip: Optimizer::PoseOptimization of n frames in one launch on stream st, scratch from ctx's call arena; returns after the stream
 // has drained.  rsd null: prob's frame-side host arrays go up too; else frame f's frame side is read at rsd[f]'s device pointers.

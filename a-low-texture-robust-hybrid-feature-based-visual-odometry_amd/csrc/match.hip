@@ -487,10 +487,7 @@ __global__ __launch_bounds__(64) void k_sbp_epilogue(SbpDev a)
                 mi = j; md = d; nm++;
                 if (a.q_blocks[i] && lane == 0) occ[j >> 5] |= 1u << (j & 31);
                 if (a.check_orientation && !a.map_mode) {
-                    float r = __fsub_rn(a.q_angle[i], a.t_kp[j].angle);
-                    if (r < 0.0f) r = __fadd_rn(r, 360.0f);
-                    bin = (int)roundf(__fmul_rn(r, factor));
-                    if (bin == 30) bin = 0;
+                    bin = hvo_rot_bin(a.q_angle[i], a.t_kp[j].angle, factor);
                 }
             }
         }
@@ -500,18 +497,7 @@ __global__ __launch_bounds__(64) void k_sbp_epilogue(SbpDev a)
     if (a.check_orientation && !a.map_mode) {              // ComputeThreeMaxima (ORBmatcher.cc:1630-1673) + cull (1473-1487)
         for (int i = lane; i < a.nq; i += 64) if (rot[i] >= 0) atomicAdd(&hist[rot[i]], 1);
         __syncthreads();
-        if (lane == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int b = 0; b < 30; b++) {
-                const int s = hist[b];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = b; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = b; }
-                else if (s > max3) { max3 = s; ind3 = b; }
-            }
-            if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-            keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
-        }
+        if (lane == 0) hvo_three_maxima(hist, keep);
         __syncthreads();
         int gone = 0;
         for (int i = lane; i < a.nq; i += 64) {

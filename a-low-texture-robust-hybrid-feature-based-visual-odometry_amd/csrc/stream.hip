@@ -14,6 +14,7 @@
 // descriptors, undistorted key points and mvuRight of the two frames (nothing but the per-query projections crosses PCIe).
 #include "hvo_internal.hpp"
 #include <string.h>
+#include <algorithm>
 #include <new>
 #include <vector>
 
@@ -33,6 +34,7 @@ struct StreamSlot {
     hipEvent_t ev_t0 = nullptr;
     int64_t ticket = -1; bool busy = false, had_depth = false;
     bool line_opt_done = false;            // hvo_stream_line_struct_optimize has rewritten this frame's 3-D lines
+    BowState bow;                          // the frame's bag of words (hvo_stream_compute_bow), dropped when the slot takes its next frame
 };
 
 // layout of a slot's pinned result block
@@ -84,6 +86,7 @@ void hvo_stream_destroy(hvo_stream *s)
         if (S.d_tail) (void)hipFree(S.d_tail);
         if (S.d_tail_scratch) (void)hipFree(S.d_tail_scratch);
         if (S.h_tail) (void)hipHostFree(S.h_tail);
+        bow_state_free(&S.bow);
         if (S.ctx) hvo_destroy(S.ctx);
     }
     if (s->d_ms) (void)hipFree(s->d_ms);
@@ -244,7 +247,7 @@ static int stream_submit_enqueue(hvo_stream *s, StreamSlot &S, const uint8_t *gr
         ST_HIP(hipMemcpy2DAsync(S.pv.d_depth, S.pv.pitch * sizeof(uint16_t), S.h_depth, (size_t)w * 2, (size_t)w * 2, h, hipMemcpyHostToDevice, c->s_peac));
         ST_HIP(hipEventRecord(S.ev_depth, c->s_peac));
     }
-    S.had_depth = depth != nullptr; S.line_opt_done = false;
+    S.had_depth = depth != nullptr; S.line_opt_done = false; S.bow.valid = false;
     char *ho = S.h_out;
     const OutLayout &L = s->lay;
     int *hc = (int *)(ho + L.counts);
@@ -436,6 +439,46 @@ int hvo_stream_stage_ms(hvo_stream *s, int64_t ticket, float ms3[3])
         if (on[k] && hipEventElapsedTime(&ms3[k], S->ev_t0, S->ev_kern[k]) != hipSuccess) ms3[k] = -1.f;
     }
     return HVO_OK;
+}
+
+// Frame::ComputeBoW (src/Frame.cc:1692-1699) on a resident frame: the ORB descriptors where the extractor left them (bow.hip)
+int hvo_stream_compute_bow(hvo_stream *s, int64_t ticket, const hvo_vocabulary *voc, int levelsup, hvo_bow *out)
+{
+    if (!s || !voc || !out) return HVO_ERR_INVALID_ARG;
+    if (!(s->sp.stages & HVO_STAGE_ORB)) { s->last_error = "bag of words: the stream must run HVO_STAGE_ORB"; return HVO_ERR_INVALID_ARG; }
+    StreamSlot *C = slot_of(s, ticket);
+    if (!C) return HVO_ERR_INVALID_ARG;
+    if (bow_voc_device(voc) != s->p.device) { s->last_error = "bag of words: the vocabulary lives on another device (or on none)"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    hipStream_t st = s->s_match;
+    ST_HIP(hipStreamWaitEvent(st, C->ev_orb, 0));
+    ST_HIP(hipEventSynchronize(C->ev_orb));                    // the key-point count arrived with the frame's download
+    const int n = ((const int *)(C->h_out + s->lay.counts))[0];
+    const OrbPlan &O = C->ctx->orb;
+    return bow_transform(C->ctx, st, voc, levelsup, 1, O.d_desc, 0, O.d_nkp, 0, s->kp_cap, &n, &C->bow, true, out, &s->last_error);
+}
+
+// ORBmatcher::SearchByBoW(pKF, F, ...) (src/ORBmatcher.cc:162-293) of n_kf key frames against the resident frame `cur`
+int hvo_stream_search_by_bow(hvo_stream *s, int64_t cur, const hvo_vocabulary *voc, int n_kf, const hvo_bow_keyframe *kf, const hvo_bow_search_params *params,
+                             hvo_bow_matches *res)
+{
+    if (!s || !voc || !kf || !params || !res || n_kf < 1) return HVO_ERR_INVALID_ARG;
+    StreamSlot *C = slot_of(s, cur);
+    if (!C) return HVO_ERR_INVALID_ARG;
+    if (!C->bow.valid || C->bow.voc_uid != bow_voc_uid(voc)) {
+        s->last_error = "search by bag of words: the frame holds no bag of words of this vocabulary (hvo_stream_compute_bow first)"; return HVO_ERR_INVALID_ARG;
+    }
+    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    ST_HIP(hipEventSynchronize(C->ev_orb));
+    BowLayout L; bow_layout(C->bow.cap, L);
+    BowFrameSide F; memset(&F, 0, sizeof(F));
+    F.n = std::max(0, std::min(((const int *)(C->h_out + s->lay.counts))[0], s->kp_cap));
+    const OrbPlan &O = C->ctx->orb;
+    F.d_desc = O.d_desc; F.d_angle = &O.d_kp->angle; F.angle_step = (int)(sizeof(hvo_keypoint) / sizeof(float));     // F.mvKeys[i].angle
+    F.d_fv_node = (const int *)(C->bow.d_blk + L.fv_node); F.d_fv_start = (const int *)(C->bow.d_blk + L.fv_start); F.d_fv_idx = (const int *)(C->bow.d_blk + L.fv_idx);
+    F.d_n_rows = (const int *)(C->bow.d_blk + L.counts) + 2;
+    if (F.n == 0) { for (int j = 0; j < n_kf; j++) { res[j].n_matches = 0; res[j].status = HVO_OK; } return HVO_OK; }
+    return bow_search(C->ctx, s->s_match, F, n_kf, kf, params, res, &s->last_error);
 }
 
 // ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, mono) core (src/ORBmatcher.cc:1353-1497) between two resident
@@ -933,6 +976,14 @@ int hvo_stream_line_opt_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2])
     if (!B) { s->last_error = "line structure: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
     ms2[0] = B->ctx->ls_ms[0]; ms2[1] = B->ctx->ls_ms[1];
     return HVO_OK;
+}
+
+int hvo_stream_bow_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2])
+{
+    if (!s || !ms2) return HVO_ERR_INVALID_ARG;
+    StreamSlot *B = slot_of(s, cur);
+    if (!B) { s->last_error = "bag of words: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    return hvo_bow_last_kernel_ms(B->ctx, ms2);
 }
 
 int hvo_stream_pose_last_kernel_ms(hvo_stream *s, int64_t cur, float *ms)

@@ -831,6 +831,84 @@ int hvo_stream_search_local_lines(hvo_stream *s, hvo_line_map *m, int64_t cur, c
 int hvo_batch_search_local_lines(hvo_ctx *ctx, hvo_line_map *m, int n, const hvo_camera *cam, const float *Tcw, const hvo_local_lines_params *params,
                                  hvo_local_lines_io *io, hvo_local_lines_result *res);
 
+/* ---- The ORB vocabulary resident on the device, Frame::ComputeBoW and ORBmatcher::SearchByBoW(KeyFrame, Frame) (csrc/bow.hip) ----
+ * The front of Tracking::TrackReferenceKeyFrame (reference src/Tracking.cc:1836, 1850) and Tracking::Relocalization (3763, 3796), and
+ * KeyFrame::ComputeBoW (src/LocalMapping.cc:194): DBoW2's TemplatedVocabulary::transform (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:
+ * 1139-1271, BowVector.cpp:34-84, FORB.cpp:81-101) and ORBmatcher::SearchByBoW (src/ORBmatcher.cc:162-293).
+ *
+ * hvo_vocabulary: a k-ary tree of 32-byte descriptors, read-only after creation, owned by a device like hvo_plane_map / hvo_line_map (usable
+ * from every context and stream of that device, from several threads at once).  The arrays of hvo_vocabulary_create are in the order of the
+ * reference's text format (TemplatedVocabulary.h:1350-1436): row i is node i + 1, node 0 is the root and has no row, a parent's children
+ * are in row order, the word id of a leaf is the running count of leaves.  2 <= k <= 20, 1 <= L <= 10, scoring 0..5, weighting 0..3.
+ * HVO_ERR_INVALID_ARG for: a parent id that is negative or >= its child's id, a parent that is a leaf, a node that is not a leaf and has no
+ * children, more than k children.  n_nodes = 0 (no words) is legal: every transform returns empty vectors (empty(), :1146) with all ids -1.
+ * device < 0 makes a host-only vocabulary: it is validated and answers hvo_vocabulary_info, and every computing call refuses it.
+ *
+ * DEFINED BEHAVIOUR (unbalanced tree): when the descent meets a leaf above level L - levelsup, the reference leaves the node id
+ * uninitialised; here node_id is that leaf's id, and hvo_bow.n_short counts such features (stopped words not included). */
+typedef struct hvo_vocabulary hvo_vocabulary;
+enum { HVO_VOC_TF_IDF = 0, HVO_VOC_TF = 1, HVO_VOC_IDF = 2, HVO_VOC_BINARY = 3 };                               /* DBoW2::WeightingType */
+enum { HVO_VOC_L1_NORM = 0, HVO_VOC_L2_NORM = 1, HVO_VOC_CHI_SQUARE = 2, HVO_VOC_KL = 3, HVO_VOC_BHATTACHARYYA = 4, HVO_VOC_DOT_PRODUCT = 5 };   /* DBoW2::ScoringType */
+typedef struct { int32_t k, L, n_nodes /* the root included */, n_words, scoring, weighting, device; } hvo_vocabulary_desc;
+int hvo_vocabulary_create(int device, int k, int L, int scoring, int weighting, int n_nodes, const int32_t *parent, const uint8_t *is_leaf, const uint8_t *desc,
+                          const double *weight, hvo_vocabulary **voc);
+/* the reference's text format (ORBvoc.txt): "k L scoring weighting", then one line per node "parent is_leaf b0 .. b31 weight".  Empty lines
+ * are skipped.  The binary format is not read. */
+int hvo_vocabulary_load_text(const char *path, int device, hvo_vocabulary **voc);
+void hvo_vocabulary_destroy(hvo_vocabulary *voc);
+int hvo_vocabulary_info(const hvo_vocabulary *voc, hvo_vocabulary_desc *info);
+
+/* One frame's bag of words.  In: cap and the arrays (each may be NULL); out: the rest.  word_id / node_id: per feature, -1 / -1 for a
+ * stopped word (weight > 0 fails); ids are the reference's.  BowVector: n_words ascending word ids with their values, bit-equal to the
+ * reference's doubles (TF / TF_IDF: the weight added once per feature in feature order; IDF / BINARY: the first weight; then the norm the
+ * scoring type asks for -- L1 for every type but L2_NORM and DOT_PRODUCT, summed in ascending word order -- or, for TF / TF_IDF under
+ * DOT_PRODUCT, one division by the number of words).  FeatureVector as CSR: n_nodes ascending node ids, fv_start (n_nodes + 1 entries),
+ * fv_index (n_valid feature indices, ascending inside a row). */
+typedef struct {
+    int32_t cap;                  /* room of every array in entries (fv_start: cap + 1); at least the frame's feature count */
+    int32_t *word_id, *node_id;
+    int32_t *bow_word; double *bow_value;
+    int32_t *fv_node, *fv_start, *fv_index;
+    int32_t n_features, n_words, n_nodes, n_valid /* features that are not stopped */, n_short;
+    int32_t computed;             /* 1: the kernels ran; 0: the frame held this result already (same vocabulary, same levelsup) */
+    int32_t status;
+} hvo_bow;
+/* On host descriptors: frame f has n_desc[f] descriptors of 32 bytes at desc[f]; all frames in one launch sequence.  At most 4096 features
+ * per frame (HVO_ERR_UNSUPPORTED beyond). */
+int hvo_compute_bow(hvo_ctx *ctx, const hvo_vocabulary *voc, int levelsup, int n_frames, const uint8_t *const *desc, const int32_t *n_desc, hvo_bow *out);
+/* On the resident frame `ticket`: the descriptors where HVO_STAGE_ORB left them.  The result stays with the frame for
+ * hvo_stream_search_by_bow.  A second call with the same vocabulary and levelsup launches nothing (`if (mBowVec.empty())`, src/Frame.cc:
+ * 1692-1699) and returns the kept result with computed = 0; another vocabulary or levelsup recomputes. */
+int hvo_stream_compute_bow(hvo_stream *s, int64_t ticket, const hvo_vocabulary *voc, int levelsup, hvo_bow *out);
+/* On the first n frames of the resident batch (after hvo_batch_run with HVO_STAGE_ORB), out[k] for frame k; kept until the next
+ * hvo_batch_run like the stream form.  Frame k equals the stream and the host-array forms on the same descriptors bit for bit. */
+int hvo_batch_compute_bow(hvo_ctx *ctx, const hvo_vocabulary *voc, int n, int levelsup, hvo_bow *out);
+
+/* SearchByBoW.  One side as host arrays: descriptors (n x 32), the per-feature node id hvo_*_compute_bow returned (-1: in no node), a byte
+ * per feature "has a map point that is not bad" (key-frame side only), the key points' angles (mvKeysUn of the key frame, mvKeys of the
+ * frame; read only with check_orientation). */
+typedef struct { const uint8_t *desc; const int32_t *node_id; const uint8_t *has_map_point; const float *angle; int32_t n; } hvo_bow_keyframe;
+typedef struct { float nnratio; int32_t check_orientation; int32_t th_low /* TH_LOW = 50 */; } hvo_bow_search_params;
+typedef struct {
+    int32_t *match_kf;            /* per frame feature: the key-frame feature whose map point it receives, or -1 (room for the frame's feature count) */
+    int32_t n_matches;            /* after the rotation filter */
+    int32_t status;
+} hvo_bow_matches;
+/* n_kf key frames against one frame in one launch, each with its own independent result (Relocalization's loop; TrackReferenceKeyFrame is
+ * n_kf = 1).  Only nodes present on both sides take part; inside a node the key-frame features are visited in ascending index; best is the
+ * first minimum among the node's frame features not yet claimed, second the second smallest of the multiset, both start at 256; accepted
+ * when best <= th_low and (float)best < nnratio * (float)second.  At most 4096 features on a side. */
+int hvo_search_by_bow(hvo_ctx *ctx, const hvo_bow_keyframe *frame, int n_kf, const hvo_bow_keyframe *kf, const hvo_bow_search_params *params, hvo_bow_matches *res);
+/* The frame side is the resident frame `cur` with the bag of words hvo_stream_compute_bow left on it for `voc` (otherwise
+ * HVO_ERR_INVALID_ARG): descriptors, key-point angles and FeatureVector never leave the device. */
+int hvo_stream_search_by_bow(hvo_stream *s, int64_t cur, const hvo_vocabulary *voc, int n_kf, const hvo_bow_keyframe *kf, const hvo_bow_search_params *params,
+                             hvo_bow_matches *res);
+
+/* device time in ms of the last ComputeBoW (ms2[0]: descent + assembly; 0 when the kept result was returned) and the last SearchByBoW
+ * (ms2[1]: the key frames' CSR + the search) of the context, or of the resident frame `cur` */
+int hvo_bow_last_kernel_ms(const hvo_ctx *ctx, float ms2[2]);
+int hvo_stream_bow_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2]);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer. Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

@@ -304,6 +304,17 @@ public:
                                                match_idx.data(), dist.data(), &n), "hvo_search_by_projection_tracked");
         return n;
     }
+    // SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:162-293) on host arrays: match_kf[i] is the key-frame feature whose map point frame
+    // feature i receives, or -1 (the caller turns it into vpMapPointMatches); the return value is nmatches.  Both sides carry the node ids
+    // ComputeBoW returned; the frame's has_map_point is not read.
+    int SearchByBoW(const hvo_bow_keyframe &kf, const hvo_bow_keyframe &frame, std::vector<int> &match_kf, float nnratio = 0.7f, bool checkOrientation = true) const
+    {
+        match_kf.assign((size_t)frame.n, -1);
+        hvo_bow_search_params p = { nnratio, checkOrientation ? 1 : 0, TH_LOW };
+        hvo_bow_matches r = { match_kf.data(), 0, 0 };
+        check(hvo_search_by_bow(ctx_, &frame, 1, &kf, &p, &r), "hvo_search_by_bow");
+        return r.n_matches;
+    }
 private:
     hvo_ctx *ctx_;
 };
@@ -631,6 +642,79 @@ public:
     }
 private:
     hvo_camera cam_; hvo_local_lines_params p_;
+};
+
+// ORBVocabulary (include/ORBVocabulary.h = DBoW2's TemplatedVocabulary<FORB::TDescriptor, FORB>) resident on one device, read-only.  BowVectors is
+// what Frame holds afterwards: mBowVec as (word, value) pairs in ascending word order, mFeatVec as CSR (node ids ascending, rows of ascending
+// feature indices), and the per-feature node ids SearchByBoW takes for a key frame.
+struct BowVectors {
+    std::vector<int32_t> word_id, node_id, bow_word, fv_node, fv_start, fv_index; std::vector<double> bow_value;
+    int n_short = 0; bool computed = false;
+    hvo_bow prepare(int cap)
+    {
+        const size_t c = (size_t)(cap < 1 ? 1 : cap);
+        word_id.assign(c, -1); node_id.assign(c, -1); bow_word.assign(c, 0); bow_value.assign(c, 0.0); fv_node.assign(c, 0); fv_start.assign(c + 1, 0); fv_index.assign(c, 0);
+        hvo_bow b = hvo_bow(); b.cap = (int32_t)c;
+        b.word_id = word_id.data(); b.node_id = node_id.data(); b.bow_word = bow_word.data(); b.bow_value = bow_value.data();
+        b.fv_node = fv_node.data(); b.fv_start = fv_start.data(); b.fv_index = fv_index.data();
+        return b;
+    }
+    void finish(const hvo_bow &b)
+    {
+        word_id.resize(b.n_features); node_id.resize(b.n_features); bow_word.resize(b.n_words); bow_value.resize(b.n_words);
+        fv_node.resize(b.n_nodes); fv_start.resize(b.n_nodes + 1); fv_index.resize(b.n_valid); n_short = b.n_short; computed = b.computed != 0;
+    }
+};
+class ORBVocabulary {
+public:
+    ORBVocabulary() : v_(nullptr) {}
+    ORBVocabulary(int device, int k, int L, int scoring, int weighting, int n_nodes, const int32_t *parent, const uint8_t *is_leaf, const uint8_t *desc, const double *weight)
+        : v_(nullptr) { check(hvo_vocabulary_create(device, k, L, scoring, weighting, n_nodes, parent, is_leaf, desc, weight, &v_), "hvo_vocabulary_create"); }
+    ~ORBVocabulary() { hvo_vocabulary_destroy(v_); }
+    ORBVocabulary(const ORBVocabulary &) = delete;
+    ORBVocabulary &operator=(const ORBVocabulary &) = delete;
+    // the text format (ORBvoc.txt); false when the file is missing or malformed, like the reference
+    bool loadFromTextFile(const std::string &filename, int device = 0)
+    {
+        hvo_vocabulary *v = nullptr;
+        if (hvo_vocabulary_load_text(filename.c_str(), device, &v) != HVO_OK) return false;
+        hvo_vocabulary_destroy(v_); v_ = v;
+        return true;
+    }
+    bool empty() const { hvo_vocabulary_desc d; return !v_ || hvo_vocabulary_info(v_, &d) != HVO_OK || d.n_words == 0; }
+    // transform(features, BowVector, FeatureVector, levelsup) on host descriptors (n x 32 bytes)
+    void transform(hvo_ctx *ctx, const uint8_t *desc, int n, BowVectors &out, int levelsup = 4) const
+    {
+        hvo_bow b = out.prepare(n); const int32_t nd = n;
+        check(hvo_compute_bow(ctx, v_, levelsup, 1, &desc, &nd, &b), "hvo_compute_bow");
+        out.finish(b);
+    }
+    hvo_vocabulary *get() const { return v_; }
+private:
+    hvo_vocabulary *v_;
+};
+// Frame::ComputeBoW (src/Frame.cc:1692-1699) and ORBmatcher::SearchByBoW(pKF, F, ...) on a resident frame of a stream: the bag of words stays
+// with the frame; a second ComputeBoW with the same vocabulary and levelsup launches nothing.
+struct Frame {
+    static void ComputeBoW(FrameStream &fs, int64_t ticket, const ORBVocabulary &voc, BowVectors &out, int levelsup = 4)
+    {
+        int kp = 0; check(hvo_stream_capacity(fs.get(), &kp, nullptr, nullptr), "hvo_stream_capacity");
+        hvo_bow b = out.prepare(kp);
+        check(hvo_stream_compute_bow(fs.get(), ticket, voc.get(), levelsup, &b), "hvo_stream_compute_bow");
+        out.finish(b);
+    }
+    // n_kf key frames in one launch (Relocalization's loop); match_kf[j] gets the stream's key-point capacity, entries past the frame's count stay -1
+    static void SearchByBoW(FrameStream &fs, int64_t cur, const ORBVocabulary &voc, int n_kf, const hvo_bow_keyframe *kf, std::vector<std::vector<int>> &match_kf,
+                            std::vector<int> &nmatches, float nnratio = 0.7f, bool checkOrientation = true, int th_low = 50)
+    {
+        int kp = 0; check(hvo_stream_capacity(fs.get(), &kp, nullptr, nullptr), "hvo_stream_capacity");
+        match_kf.assign((size_t)n_kf, std::vector<int>((size_t)kp, -1)); nmatches.assign((size_t)n_kf, 0);
+        std::vector<hvo_bow_matches> r((size_t)n_kf);
+        for (int j = 0; j < n_kf; j++) { r[j].match_kf = match_kf[j].data(); r[j].n_matches = 0; r[j].status = 0; }
+        hvo_bow_search_params p = { nnratio, checkOrientation ? 1 : 0, th_low };
+        check(hvo_stream_search_by_bow(fs.get(), cur, voc.get(), n_kf, kf, &p, r.data()), "hvo_stream_search_by_bow");
+        for (int j = 0; j < n_kf; j++) nmatches[j] = r[j].n_matches;
+    }
 };
 
 // Optimizer (include/Optimizer.h, src/Optimizer.cc:590-1478): PoseOptimization on the mirror's frame handle.  The map side (one row per feature:
