@@ -82,6 +82,9 @@ EXPORTS = [
     "hvo_line_map_create", "hvo_line_map_destroy", "hvo_line_map_set", "hvo_line_map_set_many", "hvo_line_map_set_bad", "hvo_line_map_set_observed",
     "hvo_line_map_counts", "hvo_line_map_slot", "hvo_line_map_last_error",
     "hvo_search_local_lines", "hvo_stream_search_local_lines", "hvo_batch_search_local_lines",
+    "hvo_point_map_create", "hvo_point_map_destroy", "hvo_point_map_set", "hvo_point_map_set_many", "hvo_point_map_set_bad", "hvo_point_map_set_observed",
+    "hvo_point_map_counts", "hvo_point_map_slot", "hvo_point_map_last_error",
+    "hvo_search_local_points", "hvo_stream_search_local_points", "hvo_batch_search_local_points",
     "hvo_vocabulary_create", "hvo_vocabulary_load_text", "hvo_vocabulary_destroy", "hvo_vocabulary_info",
     "hvo_compute_bow", "hvo_stream_compute_bow", "hvo_batch_compute_bow", "hvo_search_by_bow", "hvo_stream_search_by_bow",
     "hvo_bow_last_kernel_ms", "hvo_stream_bow_last_kernel_ms",
@@ -296,6 +299,82 @@ def _ll_finish(r, a, n_kl):
     for k in ("in_view_slot", "proj", "view_cos", "level", "match_idx", "match_dist"):
         setattr(r, k, a[k][:nq])
     r.rel_map = None if a["rel_map"] is None else a["rel_map"][: n_kl * nq].reshape(n_kl, nq)
+    return r
+
+
+POINT_MAP_MAX_SLOTS = 1 << 20
+POINT_MAP_MAX_QUERIES = 16384     # points in view per call (the search core's limit)
+HELD_FOREIGN_OBSERVED, HELD_FOREIGN_UNOBSERVED = -2, -3     # values of held besides a slot and -1: a map point that is not in the point map
+
+
+class LocalPointsParams(C.Structure):
+    """hvo_local_points_params"""
+    _fields_ = [("bounds", C.c_float * 4), ("log_scale_factor", C.c_float), ("n_levels", C.c_int32), ("bf", C.c_float), ("th", C.c_float),
+                ("th_high", C.c_int32), ("nn_ratio", C.c_float), ("view_cos_limit", C.c_float)]
+
+
+class LocalPointsFrame(C.Structure):
+    """hvo_local_points_frame: the frame side on host arrays"""
+    _fields_ = [("kp_un", C.c_void_p), ("uright", C.c_void_p), ("desc", C.c_void_p), ("n", C.c_int32)]
+
+
+class LocalPointsIO(C.Structure):
+    """hvo_local_points_io: one frame's inputs and outputs"""
+    _fields_ = [("n_kp", C.c_int32), ("held", C.c_void_p), ("seen_extra", C.c_void_p), ("n_seen_extra", C.c_int32), ("in_view_slot", C.c_void_p),
+                ("proj", C.c_void_p), ("view_cos", C.c_void_p), ("level", C.c_void_p), ("match_idx", C.c_void_p), ("match_dist", C.c_void_p)]
+
+
+class LocalPointsResult(C.Structure):
+    """hvo_local_points_result: one Tracking::SearchLocalPoints call.  The arrays (held, in_view_slot, proj, view_cos, level, match_idx,
+    match_dist) are attached as attributes by the calls that return it."""
+    _fields_ = [("n_slots_tested", C.c_int32), ("n_in_view", C.c_int32), ("n_matches", C.c_int32), ("status", C.c_int32), ("kernel_ms", C.c_float * 3)]
+
+    def to_dict(self):
+        d = dict(n_slots_tested=self.n_slots_tested, n_in_view=self.n_in_view, n_matches=self.n_matches, status=self.status, kernel_ms=tuple(self.kernel_ms))
+        for k in ("held", "in_view_slot", "proj", "view_cos", "level", "match_idx", "match_dist"):
+            d[k] = getattr(self, k, None)
+        return d
+
+
+assert C.sizeof(LocalPointsResult) == 28
+
+
+def _lp_params(bounds4, log_scale_factor, n_levels, bf, th, th_high, nn_ratio, view_cos_limit):
+    p = LocalPointsParams()
+    b = (0.0, 1.0, 0.0, 1.0) if bounds4 is None else [float(v) for v in np.asarray(bounds4).reshape(4)]
+    for k in range(4): p.bounds[k] = b[k]
+    p.log_scale_factor = log_scale_factor; p.n_levels = n_levels; p.bf = bf; p.th = th; p.th_high = th_high; p.nn_ratio = nn_ratio
+    p.view_cos_limit = view_cos_limit
+    return p
+
+
+def _lp_io(n_kp, n_slots, held, seen_extra):
+    """-> (LocalPointsIO, dict of the arrays it points at)"""
+    capq = max(1, min(n_slots, POINT_MAP_MAX_QUERIES)); nk = max(n_kp, 1)
+    h = np.full(nk, -1, np.int32)
+    if held is not None:
+        hh = np.asarray(held, np.int32).reshape(-1)
+        if len(hh) != n_kp:
+            raise ValueError("held must have one entry per key point (%d)" % n_kp)
+        h[:n_kp] = hh
+    ex = np.ascontiguousarray([] if seen_extra is None else seen_extra, np.int32).reshape(-1)
+    a = dict(held=h, seen_extra=ex, in_view_slot=np.zeros(capq, np.int32), proj=np.zeros((capq, 3), np.float32), view_cos=np.zeros(capq, np.float32),
+             level=np.zeros(capq, np.int32), match_idx=np.full(capq, -1, np.int32), match_dist=np.full(capq, 256, np.int32))
+    io = LocalPointsIO()
+    io.n_kp = n_kp; io.n_seen_extra = len(ex)
+    for k, v in a.items():
+        if k == "seen_extra":
+            io.seen_extra = v.ctypes.data if len(v) else None
+        else:
+            setattr(io, k, v.ctypes.data)
+    return io, a
+
+
+def _lp_finish(r, a, n_kp):
+    nq = r.n_in_view if r.status == HVO_OK else 0
+    r.held = a["held"][:n_kp]
+    for k in ("in_view_slot", "proj", "view_cos", "level", "match_idx", "match_dist"):
+        setattr(r, k, a[k][:nq])
     return r
 
 
@@ -580,6 +659,22 @@ def lib():
                                                     C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]
         L.hvo_batch_search_local_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalLinesParams),
                                                    C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]
+        L.hvo_point_map_create.argtypes = [C.c_int, C.c_int]; L.hvo_point_map_create.restype = C.c_void_p
+        L.hvo_point_map_destroy.argtypes = [C.c_void_p]; L.hvo_point_map_destroy.restype = None
+        L.hvo_point_map_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int]
+        L.hvo_point_map_set_many.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
+        L.hvo_point_map_set_bad.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.hvo_point_map_set_observed.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.hvo_point_map_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
+        L.hvo_point_map_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
+                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.hvo_point_map_last_error.argtypes = [C.c_void_p]; L.hvo_point_map_last_error.restype = C.c_char_p
+        L.hvo_search_local_points.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalPointsParams), C.POINTER(LocalPointsFrame),
+                                              C.POINTER(LocalPointsIO), C.POINTER(LocalPointsResult)]
+        L.hvo_stream_search_local_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalPointsParams),
+                                                     C.POINTER(LocalPointsIO), C.POINTER(LocalPointsResult)]
+        L.hvo_batch_search_local_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalPointsParams),
+                                                    C.POINTER(LocalPointsIO), C.POINTER(LocalPointsResult)]
         L.hvo_vocabulary_create.argtypes = [C.c_int] * 6 + [C.c_void_p] * 4 + [C.POINTER(C.c_void_p)]
         L.hvo_vocabulary_load_text.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
         L.hvo_vocabulary_destroy.argtypes = [C.c_void_p]; L.hvo_vocabulary_destroy.restype = None
@@ -758,6 +853,62 @@ class LineMap:
         mx, mn, b, o = C.c_float(0), C.c_float(0), C.c_int(0), C.c_int(0)
         self._chk(lib().hvo_line_map_slot(self.h, slot, _p(pos), _p(w), _p(nr), C.byref(mx), C.byref(mn), _p(d), C.byref(b), C.byref(o)), "line_map_slot")
         return dict(pos=pos, wvec=w, normal=nr, max_dist=mx.value, min_dist=mn.value, desc=d, bad=bool(b.value), observed=bool(o.value))
+
+
+class PointMap:
+    """hvo_point_map: mvpLocalMapPoints resident on one device (world position, normal, distance range, descriptor, bad and has-observations
+    flags per slot).  Slot index = position in the vector Tracking::SearchLocalPoints walks.  Not thread-safe; usable from any Context /
+    Stream of its device."""
+
+    def __init__(self, device=0, slots=0):
+        self.h = lib().hvo_point_map_create(device, slots)
+        if not self.h:
+            raise HvoError(-3, "hvo_point_map_create")
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().hvo_point_map_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _chk(self, rc, what):
+        if rc != HVO_OK:
+            raise HvoError(rc, what + ": " + lib().hvo_point_map_last_error(self.h).decode())
+
+    def set(self, slot, pos, normal, max_dist, min_dist, desc, observed=True):
+        """set or replace a slot: pos = GetWorldPos() (3), normal = GetNormal() (3), the raw mfMaxDistance / mfMinDistance, desc = GetDescriptor()
+        (32 bytes), observed = Observations() > 0"""
+        a = [np.ascontiguousarray(pos, np.float32).reshape(3), np.ascontiguousarray(normal, np.float32).reshape(3), np.ascontiguousarray(desc, np.uint8).reshape(32)]
+        self._chk(lib().hvo_point_map_set(self.h, slot, _p(a[0]), _p(a[1]), float(max_dist), float(min_dist), _p(a[2]), 1 if observed else 0), "point_map_set")
+
+    def set_many(self, first, pos, normal, max_dist, min_dist, desc, observed=None, bad=None):
+        """slots first .. first + n - 1 in one upload: pos / normal (n, 3), max_dist / min_dist (n), desc (n, 32), observed / bad (n) or None"""
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3); n = len(pos)
+        a = [pos, np.ascontiguousarray(normal, np.float32).reshape(n, 3), np.ascontiguousarray(max_dist, np.float32).reshape(n),
+             np.ascontiguousarray(min_dist, np.float32).reshape(n), np.ascontiguousarray(desc, np.uint8).reshape(n, 32)]
+        fl = [None if v is None else np.ascontiguousarray(np.asarray(v).astype(bool), np.uint8).reshape(n) for v in (observed, bad)]
+        pp = lambda v: None if v is None or v.size == 0 else _p(v)
+        self._chk(lib().hvo_point_map_set_many(self.h, first, n, *[pp(v) for v in a], pp(fl[0]), pp(fl[1])), "point_map_set_many")
+
+    def set_bad(self, slot, bad=True):
+        self._chk(lib().hvo_point_map_set_bad(self.h, slot, 1 if bad else 0), "point_map_set_bad")
+
+    def set_observed(self, slot, observed=True):
+        self._chk(lib().hvo_point_map_set_observed(self.h, slot, 1 if observed else 0), "point_map_set_observed")
+
+    def counts(self):
+        """(slots, good slots, slots with observations)"""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(lib().hvo_point_map_counts(self.h, C.byref(a), C.byref(b), C.byref(c)), "point_map_counts")
+        return a.value, b.value, c.value
+
+    def slot(self, slot):
+        """dict(pos, normal, max_dist, min_dist, desc, bad, observed) of one slot"""
+        pos = np.zeros(3, np.float32); nr = np.zeros(3, np.float32); d = np.zeros(32, np.uint8)
+        mx, mn, b, o = C.c_float(0), C.c_float(0), C.c_int(0), C.c_int(0)
+        self._chk(lib().hvo_point_map_slot(self.h, slot, _p(pos), _p(nr), C.byref(mx), C.byref(mn), _p(d), C.byref(b), C.byref(o)), "point_map_slot")
+        return dict(pos=pos, normal=nr, max_dist=mx.value, min_dist=mn.value, desc=d, bad=bool(b.value), observed=bool(o.value))
 
 
 class Vocabulary:
@@ -1168,6 +1319,39 @@ class Context:
         res = (LocalLinesResult * n)()
         self._chk(lib().hvo_batch_search_local_lines(self.h, lmap.h, n, C.byref(c), _p(T), C.byref(p), ios, res), "batch_search_local_lines")
         return [_ll_finish(res[k], arrs[k], int(n_kl[k])) for k in range(n)]
+
+    def search_local_points(self, pmap, cam, Tcw, t_kp_un, t_uright, t_desc, bounds4, held=None, seen_extra=None,
+                            log_scale_factor=float(np.log(np.float32(1.2))), n_levels=8, bf=None, th=1.0, th_high=100, nn_ratio=0.8, view_cos_limit=0.5):
+        """Tracking::SearchLocalPoints (src/Tracking.cc:3227-3277) of a frame on host arrays (mvKeysUn, mvuRight or None, mDescriptors) against
+        the resident PointMap under the pose Tcw (3 x 4): frustum test of every slot, SearchByProjection(F, vpMapPoints, th) on the points in
+        view, the assignment.  held: what each key point holds at entry (a slot, -1, HELD_FOREIGN_OBSERVED, HELD_FOREIGN_UNOBSERVED) ->
+        LocalPointsResult with .held, .in_view_slot, .proj (u, v, ur), .view_cos, .level, .match_idx, .match_dist"""
+        kp = np.ascontiguousarray(t_kp_un, KEYPOINT_DT); nt = len(kp)
+        ur = None if t_uright is None else np.ascontiguousarray(t_uright, np.float32).reshape(nt)
+        d = np.ascontiguousarray(t_desc, np.uint8).reshape(nt, 32)
+        F = LocalPointsFrame(); F.n = nt
+        F.kp_un = kp.ctypes.data if nt else None; F.uright = None if ur is None or not nt else ur.ctypes.data; F.desc = d.ctypes.data if nt else None
+        io, a = _lp_io(nt, pmap.counts()[0], held, seen_extra)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12); c = _pose_cam(cam)
+        p = _lp_params(bounds4, log_scale_factor, n_levels, float(cam[4]) if bf is None else bf, th, th_high, nn_ratio, view_cos_limit)
+        r = LocalPointsResult()
+        self._chk(lib().hvo_search_local_points(self.h, pmap.h, C.byref(c), _p(T), C.byref(p), C.byref(F), C.byref(io), C.byref(r)), "search_local_points")
+        return _lp_finish(r, a, nt)
+
+    def batch_search_local_points(self, pmap, cam, Tcw, n_kp, held=None, seen_extra=None, log_scale_factor=float(np.log(np.float32(1.2))), n_levels=8,
+                                  bf=None, th=1.0, th_high=100, nn_ratio=0.8, view_cos_limit=0.5):
+        """the first len(Tcw) frames of the resident batch (needs STAGE_ORB), frame k under Tcw[k] with n_kp[k] key points, held[k] and
+        seen_extra[k]; the map is read once for all frames; mvuRight is formed from the resident depth when bf (None: cam's) > 0 -> list of LocalPointsResult"""
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 12); n = len(T)
+        ns = pmap.counts()[0]
+        ios = (LocalPointsIO * n)(); arrs = []
+        for k in range(n):
+            io, a = _lp_io(int(n_kp[k]), ns, None if held is None else held[k], None if seen_extra is None else seen_extra[k])
+            ios[k] = io; arrs.append(a)
+        c = _pose_cam(cam); p = _lp_params(None, log_scale_factor, n_levels, float(cam[4]) if bf is None else bf, th, th_high, nn_ratio, view_cos_limit)
+        res = (LocalPointsResult * n)()
+        self._chk(lib().hvo_batch_search_local_points(self.h, pmap.h, n, C.byref(c), _p(T), C.byref(p), ios, res), "batch_search_local_points")
+        return [_lp_finish(res[k], arrs[k], int(n_kp[k])) for k in range(n)]
 
     def compute_bow(self, voc, descs, levelsup=4):
         """Frame::ComputeBoW on host descriptors: descs is one (n, 32) array or a list of them (all frames in one launch sequence)"""
@@ -1679,6 +1863,17 @@ class Stream:
         r = LocalLinesResult()
         self._chk(lib().hvo_stream_search_local_lines(self.h, lmap.h, cur, C.byref(c), _p(T), C.byref(p), C.byref(io), C.byref(r)), "stream_search_local_lines")
         return _ll_finish(r, a, int(n_kl))
+
+    def search_local_points(self, pmap, cur, cam, Tcw, n_kp, held=None, seen_extra=None, log_scale_factor=float(np.log(np.float32(1.2))), n_levels=8,
+                            bf=None, th=1.0, th_high=100, nn_ratio=0.8, view_cos_limit=0.5):
+        """Tracking::SearchLocalPoints on the resident frame `cur` (needs STAGE_ORB) against the resident PointMap: only the pose, held and
+        seen_extra go up.  n_kp: the frame's key-point count -> LocalPointsResult as Context.search_local_points"""
+        io, a = _lp_io(int(n_kp), pmap.counts()[0], held, seen_extra)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12); c = _pose_cam(cam)
+        p = _lp_params(None, log_scale_factor, n_levels, float(cam[4]) if bf is None else bf, th, th_high, nn_ratio, view_cos_limit)
+        r = LocalPointsResult()
+        self._chk(lib().hvo_stream_search_local_points(self.h, pmap.h, cur, C.byref(c), _p(T), C.byref(p), C.byref(io), C.byref(r)), "stream_search_local_points")
+        return _lp_finish(r, a, int(n_kp))
 
     def track_manhattan(self, cur, R_last, axes=False):
         """Tracking::TrackManhattanFrame on the resident frame `cur` (needs STAGE_PLANE_TAIL | STAGE_LINES3D and depth): its normals and 3-D

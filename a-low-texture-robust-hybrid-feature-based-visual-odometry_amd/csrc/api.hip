@@ -884,6 +884,64 @@ int hvo_batch_search_local_lines(hvo_ctx *ctx, hvo_line_map *m, int n, const hvo
     return rc;
 }
 
+// Tracking::SearchLocalPoints on host arrays against a resident point map (local_points.hip)
+int hvo_search_local_points(hvo_ctx *ctx, hvo_point_map *m, const hvo_camera *cam, const float Tcw[12], const hvo_local_points_params *params,
+                            const hvo_local_points_frame *frame, hvo_local_points_io *io, hvo_local_points_result *res)
+{
+    if (!ctx || !m || !cam || !Tcw || !params || !frame || !io || !res || frame->n < 0) return HVO_ERR_INVALID_ARG;
+    const int nt = frame->n;
+    if (nt > 0 && (!frame->kp_un || !frame->desc)) return HVO_ERR_INVALID_ARG;
+    if (lp_map_device(m) != ctx->device) { ctx->last_error = "local points: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    LpFrameDev F; memset(&F, 0, sizeof(F));
+    F.nt = nt;
+    hipStream_t st = ctx->stream;
+    if (nt > 0 && nt <= 65535) {                                  // (more is refused by lp_run before anything is read)
+        auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        const size_t b_kp = al((size_t)nt * sizeof(hvo_keypoint)), b_ur = al((size_t)nt * 4), b_d = al((size_t)nt * 32);
+        char *a = (char *)hvo_call_arena(ctx, b_kp + b_ur + b_d + 256);
+        if (!a) return HVO_ERR_HIP;
+        F.kp_un = (const hvo_keypoint *)a; F.uright = frame->uright ? (const float *)(a + b_kp) : nullptr; F.desc = (const uint8_t *)(a + b_kp + b_ur);
+        HVO_HIP(hipMemcpyAsync((void *)F.kp_un, frame->kp_un, (size_t)nt * sizeof(hvo_keypoint), hipMemcpyHostToDevice, st));
+        if (frame->uright) HVO_HIP(hipMemcpyAsync((void *)F.uright, frame->uright, (size_t)nt * 4, hipMemcpyHostToDevice, st));
+        HVO_HIP(hipMemcpyAsync((void *)F.desc, frame->desc, (size_t)nt * 32, hipMemcpyHostToDevice, st));
+    }
+    const int rc = lp_run(st, m, cam, params, params->bounds, ctx->scale, 1, &F, Tcw, io, res);
+    if (rc) ctx->last_error = lp_map_error(m);
+    return rc;
+}
+
+// the same over the first n frames of the resident batch: key points and descriptors where the last hvo_batch_run left them, mvuRight formed
+// from the resident depth image, one pose per frame
+int hvo_batch_search_local_points(hvo_ctx *ctx, hvo_point_map *m, int n, const hvo_camera *cam, const float *Tcw, const hvo_local_points_params *params,
+                                  hvo_local_points_io *io, hvo_local_points_result *res)
+{
+    if (!ctx || !m || !cam || !Tcw || !params || !io || !res || n < 1) return HVO_ERR_INVALID_ARG;
+    if (n > ctx->batch_n) { ctx->last_error = "local points: n beyond the resident batch"; return HVO_ERR_INVALID_ARG; }
+    if (!(ctx->last_stages & HVO_STAGE_ORB)) { ctx->last_error = "local points: the last hvo_batch_run must include HVO_STAGE_ORB"; return HVO_ERR_INVALID_ARG; }
+    if (lp_map_device(m) != ctx->device) { ctx->last_error = "local points: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    const bool stereo = ctx->have_depth && params->bf > 0;
+    PeacView pv; memset(&pv, 0, sizeof(pv));
+    int rc;
+    if (stereo && (rc = peac_prepare(ctx, ctx->batch_w, ctx->batch_h, std::max(n, ctx->p.max_batch), &pv))) return rc;
+    std::vector<LpFrameDev> F((size_t)n);
+    std::vector<int> nkp((size_t)n);                              // the resident counts: io[f].n_kp may say more, never less
+    HVO_HIP(hipMemcpyAsync(nkp.data(), ctx->orb.d_nkp, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HVO_HIP(hipStreamSynchronize(ctx->stream));
+    for (int f = 0; f < n; f++) {
+        if (io[f].n_kp < 0) return HVO_ERR_INVALID_ARG;
+        memset(&F[f], 0, sizeof(F[f]));
+        F[f].nt = std::max(0, std::min(nkp[f], ctx->orb.kp_cap));
+        F[f].kp_un = ctx->orb.d_kp + (size_t)f * ctx->orb.kp_cap; F[f].desc = ctx->orb.d_desc + (size_t)f * ctx->orb.kp_cap * 32;
+        if (stereo) { F[f].depth = pv.d_depth + (size_t)f * pv.dframe; F[f].pitch = pv.pitch; F[f].w = ctx->batch_w; F[f].h = ctx->batch_h; F[f].dfac = ctx->p.depth_map_factor; }
+    }
+    const float bounds[4] = { 0.f, (float)ctx->batch_w, 0.f, (float)ctx->batch_h };   // as tail_batch_run builds the grids
+    rc = lp_run(ctx->stream, m, cam, params, bounds, ctx->scale, n, F.data(), Tcw, io, res);
+    if (rc) ctx->last_error = lp_map_error(m);
+    return rc;
+}
+
 int hvo_line_opt_last_kernel_ms(const hvo_ctx *ctx, float ms2[2])
 {
     if (!ctx || !ms2) return HVO_ERR_INVALID_ARG;

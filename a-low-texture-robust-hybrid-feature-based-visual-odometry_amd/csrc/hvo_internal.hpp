@@ -471,6 +471,17 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
 int ll_map_device(const hvo_line_map *m);
 const char *ll_map_error(const hvo_line_map *m);
 
+// match.hip: the window kernel of SearchByProjection(F, vpMapPoints, th) (radius, band [level - 1, level]); local_points.hip launches it too
+__global__ void k_track_windows(int n, const int *level, const float *view_cos, float th, int bfactor, ProjDev P, float *q_radius, int *q_min, int *q_max);
+// local_points.hip: SearchLocalPoints of nframes frames against a resident point map, on stream st; it returns after the stream has drained,
+// with io / res (host, nframes entries) filled.  fr: every frame's frame side as device pointers (nt features; uright null: no stereo gate;
+// depth set: mvuRight is formed from it first, like k_stereo_from_rgbd with mvKeysUn = mvKeys).  sf: mvScaleFactors (HVO_MAX_LEVELS entries).
+struct LpFrameDev { const hvo_keypoint *kp_un; const float *uright; const uint8_t *desc; int nt; const uint16_t *depth; int pitch, w, h; float dfac; };
+int lp_run(hipStream_t st, hvo_point_map *m, const hvo_camera *cam, const hvo_local_points_params *P, const float bounds[4], const float *sf, int nframes,
+           const LpFrameDev *fr, const float *Tcw, hvo_local_points_io *io, hvo_local_points_result *res);
+int lp_map_device(const hvo_point_map *m);
+const char *lp_map_error(const hvo_point_map *m);
+
 // bow.hip: the resident vocabulary, ComputeBoW and SearchByBoW
 #define HVO_BOW_MAXN 4096                  // features of a frame (the sort keys of one frame live in 32 KB of LDS)
 struct BowLayout { int cap; size_t counts, word_id, node_id, flag, weight, bow_word, bow_val, fv_node, fv_start, fv_idx, total; };   // a frame's block for `cap` features

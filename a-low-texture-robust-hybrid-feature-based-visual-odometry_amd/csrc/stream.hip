@@ -969,6 +969,26 @@ int hvo_stream_search_local_lines(hvo_stream *s, hvo_line_map *m, int64_t cur, c
     return rc;
 }
 
+// Tracking::SearchLocalPoints on the resident frame `cur` against a resident point map: undistorted key points, mvuRight and descriptors are
+// read where the stages left them; the pose, held and seen_extra go up.  The scratch is the map's.
+int hvo_stream_search_local_points(hvo_stream *s, hvo_point_map *m, int64_t cur, const hvo_camera *cam, const float Tcw[12],
+                                   const hvo_local_points_params *params, hvo_local_points_io *io, hvo_local_points_result *res)
+{
+    if (!s || !m || !cam || !Tcw || !params || !io || !res) return HVO_ERR_INVALID_ARG;
+    if (!(s->sp.stages & HVO_STAGE_ORB)) { s->last_error = "local points: the stream must run HVO_STAGE_ORB"; return HVO_ERR_INVALID_ARG; }
+    StreamSlot *B = slot_of(s, cur);
+    if (!B) { s->last_error = "local points: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    if (lp_map_device(m) != s->p.device) { s->last_error = "local points: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    ST_HIP(hipEventSynchronize(B->ev_orb));                     // (recorded behind the undistortion, mvuRight and the frame's download)
+    const int nt = std::max(0, std::min(((const int *)(B->h_out + s->lay.counts))[0], s->kp_cap));
+    LpFrameDev F; memset(&F, 0, sizeof(F));
+    F.kp_un = B->d_kp_un; F.uright = (B->had_depth && s->sp.bf > 0) ? B->d_uright : nullptr; F.desc = B->ctx->orb.d_desc; F.nt = nt;
+    const int rc = lp_run(s->s_match, m, cam, params, s->bounds, B->ctx->scale, 1, &F, Tcw, io, res);
+    if (rc) s->last_error = lp_map_error(m);
+    return rc;
+}
+
 int hvo_stream_line_opt_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2])
 {
     if (!s || !ms2) return HVO_ERR_INVALID_ARG;

@@ -831,6 +831,102 @@ int hvo_stream_search_local_lines(hvo_stream *s, hvo_line_map *m, int64_t cur, c
 int hvo_batch_search_local_lines(hvo_ctx *ctx, hvo_line_map *m, int n, const hvo_camera *cam, const float *Tcw, const hvo_local_lines_params *params,
                                  hvo_local_lines_io *io, hvo_local_lines_result *res);
 
+/* ---- The local map's points resident on the device and SearchLocalPoints (csrc/local_points.hip) ----
+ * The point side of Tracking::TrackLocalMapWithLines in one call: Tracking::SearchLocalPoints (reference src/Tracking.cc:3227-3277) --
+ * Frame::isInFrustum(MapPoint *, 0.5) on every local map point (src/Frame.cc:1371-1427), MapPoint::PredictScale (src/MapPoint.cc:400-415)
+ * and ORBmatcher::SearchByProjection(F, vpMapPoints, th) (src/ORBmatcher.cc:45-132) on the points in view, through the search core of
+ * hvo_search_by_projection_tracked.
+ *
+ * hvo_point_map: mvpLocalMapPoints resident on one device.  A slot's index is the point's position in that vector.  Per slot: GetWorldPos()
+ * and GetNormal() (3 floats each: both are CV_32F), mfMaxDistance / mfMinDistance (the raw members: the kernel applies 1.2f and 0.8f),
+ * GetDescriptor() (32 bytes), isBad() and Observations() > 0.  Ownership, threading and growth as for hvo_line_map: the map belongs to a
+ * device, not to a context; it is NOT thread-safe (one call at a time on a map, the searching calls included: they use the map's grow-only
+ * scratch); every call returns after its device work has finished; storage grows only.
+ *
+ * Readings a caller can observe (DESIGN.md section 7 has all of them): Rcw P + tcw and mOw as for the line map; `PcZ < 0.0f` as written
+ * (z == 0 and -0.0 pass and divide; a NaN projection passes the bounds tests); invz is one float division; u = fx PcX invz + cx is float, left
+ * to right; cv::norm is the square root of the double sum of squares stored to float; the dot product and its quotient by dist are double,
+ * rounded to the float viewCos; PredictScale's log and ceil are the float overloads, and the clamp to [0, n_levels - 1] is part of it, so
+ * `level` is clamp((int)ceilf(logf(mfMaxDistance / dist) / log_scale_factor)) (a NaN gives 0).  No arithmetic is contracted. */
+typedef struct hvo_point_map hvo_point_map;
+#define HVO_POINT_MAP_MAX_SLOTS (1 << 20)
+/* values of hvo_local_points_io.held besides a slot (>= 0) and none (-1): a map point that is not in this map (the RGB-D tracker's temporal
+ * points of UpdateLastFrame can still be held), with observations (it blocks its feature, ORBmatcher.cc:88-90) or without (it is overwritten) */
+#define HVO_HELD_FOREIGN_OBSERVED (-2)
+#define HVO_HELD_FOREIGN_UNOBSERVED (-3)
+/* slots: initial capacity (grows on demand; 0 = a small default).  NULL when the device or the allocation fails. */
+hvo_point_map *hvo_point_map_create(int device, int slots);
+void hvo_point_map_destroy(hvo_point_map *m);
+/* Set or replace one slot (0 <= slot < HVO_POINT_MAP_MAX_SLOTS, else HVO_ERR_UNSUPPORTED).  A slot past the end extends the map; the slots
+ * skipped over start bad.  The slot written is good (not bad) afterwards. */
+int hvo_point_map_set(hvo_point_map *m, int slot, const float pos[3], const float normal[3], float max_dist, float min_dist, const uint8_t desc[32],
+                      int observed);
+/* Slots first .. first + n - 1 in one upload (a key frame replaces the local map): pos / normal n x 3, max_dist / min_dist n, desc n x 32;
+ * observed (n bytes; NULL = every point has observations) and bad (n bytes; NULL = none is bad).  The map never shrinks: a local map
+ * shorter than the one before leaves the slots past its end as they were, so the caller marks them bad. */
+int hvo_point_map_set_many(hvo_point_map *m, int first, int n, const float *pos, const float *normal, const float *max_dist, const float *min_dist,
+                           const uint8_t *desc, const uint8_t *observed, const uint8_t *bad);
+/* MapPoint::SetBadFlag / Observations() crossing zero.  The slot must exist. */
+int hvo_point_map_set_bad(hvo_point_map *m, int slot, int bad);
+int hvo_point_map_set_observed(hvo_point_map *m, int slot, int observed);
+/* each pointer may be NULL: slots in the map, the good ones, the ones with observations */
+int hvo_point_map_counts(const hvo_point_map *m, int *n_slots, int *n_good, int *n_observed);
+/* one slot as the map holds it (each pointer may be NULL) */
+int hvo_point_map_slot(const hvo_point_map *m, int slot, float pos[3], float normal[3], float *max_dist, float *min_dist, uint8_t desc[32], int *bad,
+                       int *observed);
+const char *hvo_point_map_last_error(const hvo_point_map *m);
+
+typedef struct {
+    float bounds[4];              /* mnMinX, mnMaxX, mnMinY, mnMaxY (host-array form; the resident forms take the bounds of their feature grid) */
+    float log_scale_factor;       /* mfLogScaleFactor */
+    int32_t n_levels;             /* mnScaleLevels, 1 .. 16: PredictScale clamps to [0, n_levels - 1]; the context's scale factors are read at the level */
+    float bf;                     /* mbf: mTrackProjXR = u - bf * invz; the batch form also forms mvuRight from the depth image with it */
+    float th;                     /* SearchByProjection's th: 1, 3 for RGB-D, 5 right after a relocalisation (Tracking.cc:3269-3274) */
+    int32_t th_high;              /* TH_HIGH (100) */
+    float nn_ratio;               /* ORBmatcher(0.8) */
+    float view_cos_limit;         /* isInFrustum's viewingCosLimit (0.5) */
+} hvo_local_points_params;
+typedef struct {                  /* the frame side on host arrays: mvKeysUn, mvuRight (NULL: monocular, the stereo gate is off), mDescriptors */
+    const hvo_keypoint *kp_un; const float *uright; const uint8_t *desc; int32_t n;
+} hvo_local_points_frame;
+typedef struct {                  /* one frame's inputs and outputs */
+    int32_t n_kp;                 /* the length of held: at least the frame's key-point count (on host arrays: frame->n).  The resident forms read
+                                   * the frame's own count; entries past it are not touched, a shorter array is refused. */
+    int32_t *held;                /* in: mvpMapPoints[i] at entry as a slot, -1, HVO_HELD_FOREIGN_OBSERVED or HVO_HELD_FOREIGN_UNOBSERVED; out: after
+                                   * the call.  A held slot that is bad is set to -1 first (3235-3238); every other held slot is "seen"
+                                   * (mnLastFrameSeen, 3242) and is not tested.  A foreign value stays unless a match overwrites it. */
+    const int32_t *seen_extra; int32_t n_seen_extra;   /* further slots to skip: points TrackWithMotionModel / TrackReferenceKeyFrame discarded
+                                                        * as outliers with mnLastFrameSeen = current (2113-2114, 2434-2435); may be NULL / 0 */
+    int32_t *in_view_slot;        /* out, room for min(slots, 16384) entries: the points with mbTrackInView as slots, ascending.  The caller does
+                                   * IncreaseVisible() from this list and from the held points, IncreaseFound() from held after the pose
+                                   * optimisation; the library holds no such counters. */
+    float *proj; float *view_cos; int32_t *level;      /* optional, per in-view entry: (mTrackProjX, mTrackProjY, mTrackProjXR), mTrackViewCos, mnTrackScaleLevel */
+    int32_t *match_idx, *match_dist;                   /* optional, per in-view entry: the feature it was assigned to (-1 / 256 = none) */
+} hvo_local_points_io;
+typedef struct {
+    int32_t n_slots_tested;       /* slots that reached isInFrustum (not bad, not seen) */
+    int32_t n_in_view;            /* nToMatch */
+    int32_t n_matches;            /* SearchByProjection's return value (0 when it did not run: nothing in view) */
+    int32_t status;
+    float kernel_ms[3];           /* device time of the call: mark + frustum + compaction, the search, the assignment */
+} hvo_local_points_result;
+/* On host arrays.  cam: fx, fy, cx, cy are read.  Tcw: rows 0..2 of the pose, row-major 3 x 4.  Limits: 65535 frame features, 16384 points
+ * in view -- more gives HVO_ERR_UNSUPPORTED, never a truncated search: no output of io is written (held stays as passed in) and res carries
+ * n_in_view and status.  The in-view count comes back to the host once in the middle of the call (the search's grid depends on it). */
+int hvo_search_local_points(hvo_ctx *ctx, hvo_point_map *m, const hvo_camera *cam, const float Tcw[12], const hvo_local_points_params *params,
+                            const hvo_local_points_frame *frame, hvo_local_points_io *io, hvo_local_points_result *res);
+/* On the resident frame `cur`: undistorted key points, mvuRight and descriptors are read where the stages left them; the pose, held and
+ * seen_extra go up.  The stream must run HVO_STAGE_ORB: otherwise HVO_ERR_INVALID_ARG with hvo_stream_last_error set.  mvuRight takes part
+ * when the frame was submitted with depth and the stream's bf is > 0. */
+int hvo_stream_search_local_points(hvo_stream *s, hvo_point_map *m, int64_t cur, const hvo_camera *cam, const float Tcw[12],
+                                   const hvo_local_points_params *params, hvo_local_points_io *io, hvo_local_points_result *res);
+/* On the first n frames of the resident batch (after hvo_batch_run with HVO_STAGE_ORB): frame k under Tcw + 12 k with io[k] / res[k]; the
+ * map is read once for all frames.  The batch holds no mvuRight: with depth uploaded and params->bf > 0 it is formed from the resident depth
+ * image with hvo_stereo_from_rgbd's arithmetic (mvKeysUn = mvKeys, as in hvo_batch_pose_optimize).  Frame k equals the stream form on the
+ * same image bit for bit. */
+int hvo_batch_search_local_points(hvo_ctx *ctx, hvo_point_map *m, int n, const hvo_camera *cam, const float *Tcw, const hvo_local_points_params *params,
+                                  hvo_local_points_io *io, hvo_local_points_result *res);
+
 /* ---- The ORB vocabulary resident on the device, Frame::ComputeBoW and ORBmatcher::SearchByBoW(KeyFrame, Frame) (csrc/bow.hip) ----
  * The front of Tracking::TrackReferenceKeyFrame (reference src/Tracking.cc:1836, 1850) and Tracking::Relocalization (3763, 3796), and
  * KeyFrame::ComputeBoW (src/LocalMapping.cc:194): DBoW2's TemplatedVocabulary::transform (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:

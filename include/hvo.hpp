@@ -644,6 +644,72 @@ private:
     hvo_camera cam_; hvo_local_lines_params p_;
 };
 
+// The local map's points resident on one device (hvo_point_map): per slot GetWorldPos(), GetNormal(), mfMaxDistance, mfMinDistance,
+// GetDescriptor(), isBad() and Observations() > 0.  The slot index is the position in mvpLocalMapPoints: the tracker calls setMany() after
+// UpdateLocalPoints has rebuilt that vector.  Not thread-safe.
+class PointMap {
+public:
+    explicit PointMap(int device = 0, int slots = 0) : m_(hvo_point_map_create(device, slots))
+    {
+        if (!m_) throw Error(HVO_ERR_HIP, "hvo_point_map_create");
+    }
+    ~PointMap() { hvo_point_map_destroy(m_); }
+    PointMap(const PointMap &) = delete;
+    PointMap &operator=(const PointMap &) = delete;
+    void set(int slot, const float pos[3], const float normal[3], float maxDistance, float minDistance, const uint8_t desc[32], bool observed = true)
+    {
+        check(hvo_point_map_set(m_, slot, pos, normal, maxDistance, minDistance, desc, observed ? 1 : 0), "hvo_point_map_set");
+    }
+    void setMany(int first, int n, const float *pos, const float *normal, const float *maxDistance, const float *minDistance, const uint8_t *desc,
+                 const uint8_t *observed = nullptr, const uint8_t *bad = nullptr)
+    {
+        check(hvo_point_map_set_many(m_, first, n, pos, normal, maxDistance, minDistance, desc, observed, bad), "hvo_point_map_set_many");
+    }
+    void setBad(int slot, bool bad = true) { check(hvo_point_map_set_bad(m_, slot, bad ? 1 : 0), "hvo_point_map_set_bad"); }
+    void setObserved(int slot, bool observed = true) { check(hvo_point_map_set_observed(m_, slot, observed ? 1 : 0), "hvo_point_map_set_observed"); }
+    int size() const { int n = 0; check(hvo_point_map_counts(m_, &n, nullptr, nullptr), "hvo_point_map_counts"); return n; }
+    const char *lastError() const { return hvo_point_map_last_error(m_); }
+    hvo_point_map *get() const { return m_; }
+private:
+    hvo_point_map *m_;
+};
+
+// Tracking::SearchLocalPoints (src/Tracking.cc:3227-3277) over a resident PointMap: io.held carries mvpMapPoints as slots (or -1,
+// HVO_HELD_FOREIGN_OBSERVED, HVO_HELD_FOREIGN_UNOBSERVED) in and out, io.in_view_slot returns the points with mbTrackInView; the return value
+// is SearchByProjection's nmatches.  th: 1, 3 for RGB-D, 5 right after a relocalisation.
+class LocalPoints {
+public:
+    LocalPoints(const hvo_camera &cam, float logScaleFactor, int nLevels, float nnratio = 0.8f) : cam_(cam)
+    {
+        p_ = hvo_local_points_params(); p_.log_scale_factor = logScaleFactor; p_.n_levels = nLevels; p_.bf = cam.bf; p_.th_high = 100; p_.nn_ratio = nnratio;
+        p_.view_cos_limit = 0.5f;
+    }
+    // on host arrays; bounds4 = mnMinX, mnMaxX, mnMinY, mnMaxY
+    int SearchLocalPoints(hvo_ctx *ctx, const PointMap &map, const float Tcw[12], const float bounds4[4], const hvo_local_points_frame &frame, hvo_local_points_io &io,
+                          hvo_local_points_result &res, float th = 1.0f) const
+    {
+        hvo_local_points_params p = p_; p.th = th;
+        for (int k = 0; k < 4; k++) p.bounds[k] = bounds4[k];
+        check(hvo_search_local_points(ctx, map.get(), &cam_, Tcw, &p, &frame, &io, &res), "hvo_search_local_points");
+        return res.n_matches;
+    }
+    // on the resident frame `cur` of a stream (HVO_STAGE_ORB); the slot stays resident until `depth` newer frames were submitted
+    int SearchLocalPoints(FrameStream &fs, int64_t cur, const PointMap &map, const float Tcw[12], hvo_local_points_io &io, hvo_local_points_result &res, float th = 1.0f) const
+    {
+        hvo_local_points_params p = p_; p.th = th;
+        check(hvo_stream_search_local_points(fs.get(), map.get(), cur, &cam_, Tcw, &p, &io, &res), "hvo_stream_search_local_points");
+        return res.n_matches;
+    }
+    // on the first n frames of the context's resident batch, frame k under Tcw + 12 k with io[k] / res[k]
+    void SearchLocalPointsBatch(hvo_ctx *ctx, const PointMap &map, int n, const float *Tcw, hvo_local_points_io *io, hvo_local_points_result *res, float th = 1.0f) const
+    {
+        hvo_local_points_params p = p_; p.th = th;
+        check(hvo_batch_search_local_points(ctx, map.get(), n, &cam_, Tcw, &p, io, res), "hvo_batch_search_local_points");
+    }
+private:
+    hvo_camera cam_; hvo_local_points_params p_;
+};
+
 // ORBVocabulary (include/ORBVocabulary.h = DBoW2's TemplatedVocabulary<FORB::TDescriptor, FORB>) resident on one device, read-only.  BowVectors is
 // what Frame holds afterwards: mBowVec as (word, value) pairs in ascending word order, mFeatVec as CSR (node ids ascending, rows of ascending
 // feature indices), and the per-feature node ids SearchByBoW takes for a key frame.
