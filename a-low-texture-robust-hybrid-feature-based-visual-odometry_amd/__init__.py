@@ -88,6 +88,7 @@ EXPORTS = [
     "hvo_vocabulary_create", "hvo_vocabulary_load_text", "hvo_vocabulary_destroy", "hvo_vocabulary_info",
     "hvo_compute_bow", "hvo_stream_compute_bow", "hvo_batch_compute_bow", "hvo_search_by_bow", "hvo_stream_search_by_bow",
     "hvo_bow_last_kernel_ms", "hvo_stream_bow_last_kernel_ms",
+    "hvo_pnp_default_params", "hvo_pnp_ransac", "hvo_stream_pnp_ransac", "hvo_pnp_last_kernel_ms", "hvo_stream_pnp_last_kernel_ms",
 ]
 
 
@@ -447,6 +448,115 @@ def _bow_search_args(n_frame, kfs, nnratio, check_orientation, th_low):
     return K, P, R, m, keep
 
 
+class PnpParams(C.Structure):
+    _fields_ = [("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("min_set", C.c_int32), ("epsilon", C.c_float), ("th2", C.c_float),
+                ("seed", C.c_uint32), ("extra_iterations", C.c_int32), ("max_events", C.c_int32)]
+
+
+class PnpProblem(C.Structure):
+    _fields_ = [("p3d", C.c_void_p), ("p2d", C.c_void_p), ("sigma2", C.c_void_p), ("feature_index", C.c_void_p), ("n", C.c_int32), ("n_features", C.c_int32)]
+
+
+class PnpEvent(C.Structure):
+    _fields_ = [("iteration", C.c_int32), ("n_inliers", C.c_int32), ("success", C.c_int32), ("hyp_n_inliers", C.c_int32), ("Tcw", C.c_float * 12), ("hyp_Tcw", C.c_float * 12),
+                ("inliers", C.c_void_p), ("hyp_inliers", C.c_void_p)]
+
+
+class PnpResult(C.Structure):
+    _fields_ = [("cap_hyp", C.c_int32), ("cap_events", C.c_int32), ("hyp_inliers", C.c_void_p), ("hyp_event", C.c_void_p), ("hyp_sample", C.c_void_p),
+                ("events", C.POINTER(PnpEvent)), ("best_inliers", C.c_void_p), ("best_Tcw", C.c_float * 12)] + \
+               [(k, C.c_int32) for k in ("best_n_inliers", "best_valid", "best_iteration", "n", "n_features", "min_inliers", "max_its")] + [("epsilon", C.c_float)] + \
+               [(k, C.c_int32) for k in ("n_hyp", "n_events", "no_more", "status")]
+
+
+class PnpKeyframeSide(C.Structure):
+    _fields_ = [("match_kf", C.c_void_p), ("pos", C.c_void_p), ("bad", C.c_void_p), ("n", C.c_int32)]
+
+
+PNP_MAX_HYP = 1024
+
+
+def pnp_params(**kw):
+    """hvo_pnp_default_params (SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991), seed 1, 8 extra iterations, 8 events) with fields overridden"""
+    P = PnpParams()
+    lib().hvo_pnp_default_params(C.byref(P))
+    for k, v in kw.items():
+        if not hasattr(P, k):
+            raise TypeError("unknown PnP parameter " + k)
+        setattr(P, k, v)
+    return P
+
+
+PNP_SENTINEL = 0xA5                  # what the result arrays hold where the call writes nothing: past T, past n_events, past n_features
+
+
+def _pnp_results(n_kf, n_features, P, want_sample, spare_events=0):
+    """hvo_pnp_result x n_kf with their arrays: room for max_iterations + extra_iterations hypotheses (at most 1024) and max_events (+ spare_events)
+    events, every byte PNP_SENTINEL (iteration = -99 in the event records) before the call"""
+    cap = max(1, min(PNP_MAX_HYP, P.max_iterations + P.extra_iterations)); E = max(int(P.max_events), 1) + int(spare_events)
+    sent32 = np.frombuffer(bytes([PNP_SENTINEL] * 4), np.int32)[0]
+    R = (PnpResult * n_kf)(); keep = []
+    for j in range(n_kf):
+        nf = max(int(n_features[j]), 1)
+        a = dict(hyp_inliers=np.full(cap, sent32, np.int32), hyp_event=np.full(cap, sent32, np.int32),
+                 hyp_sample=np.full((cap, max(P.min_set, 1)), sent32, np.int32) if want_sample else None,
+                 ev_inliers=np.full((E, nf), PNP_SENTINEL, np.uint8), ev_hyp_inliers=np.full((E, nf), PNP_SENTINEL, np.uint8),
+                 best_inliers=np.full(nf, PNP_SENTINEL, np.uint8), events=(PnpEvent * E)())
+        for e in range(E):
+            a["events"][e].iteration = -99
+            a["events"][e].inliers = a["ev_inliers"][e].ctypes.data; a["events"][e].hyp_inliers = a["ev_hyp_inliers"][e].ctypes.data
+        R[j].cap_hyp = cap; R[j].cap_events = E
+        R[j].hyp_inliers = a["hyp_inliers"].ctypes.data; R[j].hyp_event = a["hyp_event"].ctypes.data
+        R[j].hyp_sample = a["hyp_sample"].ctypes.data if want_sample else None
+        R[j].events = a["events"]; R[j].best_inliers = a["best_inliers"].ctypes.data
+        keep.append(a)
+    return R, keep
+
+
+def _pnp_finish(R, keep, min_set):
+    out = []
+    for r, a in zip(R, keep):
+        T, nf = r.n_hyp, r.n_features
+        ev = [dict(iteration=a["events"][e].iteration, n_inliers=a["events"][e].n_inliers, success=bool(a["events"][e].success),
+                   Tcw=np.array(a["events"][e].Tcw, np.float32), inliers=a["ev_inliers"][e, :nf].copy(), hyp_n_inliers=a["events"][e].hyp_n_inliers,
+                   hyp_Tcw=np.array(a["events"][e].hyp_Tcw, np.float32), hyp_inliers=a["ev_hyp_inliers"][e, :nf].copy()) for e in range(r.n_events)]
+        out.append(dict(N=r.n, n_features=nf, min_inliers=r.min_inliers, max_its=r.max_its, epsilon=np.float32(r.epsilon), T=T, no_more=bool(r.no_more), status=r.status,
+                        hyp_inliers=a["hyp_inliers"][:T].copy(), hyp_event=a["hyp_event"][:T].copy(),
+                        hyp_sample=None if a["hyp_sample"] is None else a["hyp_sample"][:T, :min_set].copy(), events=ev,
+                        best_n_inliers=r.best_n_inliers, best_valid=bool(r.best_valid), best_iteration=r.best_iteration, best_Tcw=np.array(r.best_Tcw, np.float32),
+                        best_inliers=a["best_inliers"][:nf].copy() if r.best_iteration > 0 else np.zeros(nf, np.uint8), raw=a))
+    return out
+
+
+def pnp_iterate(res, state, n_iterations):
+    """PnPsolver::iterate(nIterations, bNoMore, vbInliers, nInliers) (src/PnPsolver.cc:165-258) replayed over one candidate's result `res`
+    of pnp_ransac.  state: a dict that keeps mnIterations between calls (start with {}).  Returns (Tcw (12 floats) or None, bNoMore,
+    vbInliers or None, nInliers).  A replay that would need a hypothesis past the T evaluated ones reports bNoMore."""
+    it = state.get("mnIterations", 0)
+    if res["N"] < res["min_inliers"]:
+        return None, True, None, 0
+    cur = 0
+    while it < res["max_its"] or cur < n_iterations:
+        cur += 1; it += 1
+        state["mnIterations"] = it
+        if it > res["T"]:
+            return None, True, None, 0
+        e = int(res["hyp_event"][it - 1])
+        if e >= 0:
+            ev = res["events"][e]
+            return ev["Tcw"], False, ev["inliers"], ev["n_inliers"]
+    state["mnIterations"] = it
+    if it >= res["max_its"]:
+        last = None                                              # the best after `it` iterations: the latest record at or before it
+        for ev in res["events"]:
+            if ev["iteration"] <= it:
+                last = ev
+        if last is not None:
+            return last["hyp_Tcw"], True, last["hyp_inliers"], last["hyp_n_inliers"]
+        return None, True, None, 0
+    return None, False, None, 0
+
+
 def line_struct_params(**kw):
     """the reference's values (hvo_line_struct_default_params) with the given fields replaced (mode, row_rule, ...)"""
     p = LineStructParams()
@@ -686,6 +796,11 @@ def lib():
         L.hvo_stream_search_by_bow.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(BowKeyframe), C.POINTER(BowSearchParams), C.POINTER(BowMatches)]
         L.hvo_bow_last_kernel_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.hvo_stream_bow_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.hvo_pnp_default_params.argtypes = [C.POINTER(PnpParams)]; L.hvo_pnp_default_params.restype = None
+        L.hvo_pnp_ransac.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(PnpParams), C.c_int, C.POINTER(PnpProblem), C.POINTER(PnpResult)]
+        L.hvo_stream_pnp_ransac.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(PnpParams), C.c_int, C.POINTER(PnpKeyframeSide), C.POINTER(PnpResult)]
+        L.hvo_pnp_last_kernel_ms.argtypes = [C.c_void_p, C.c_void_p]
+        L.hvo_stream_pnp_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.hvo_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_stream_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_search_by_projection_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
@@ -1380,6 +1495,35 @@ class Context:
         self._chk(lib().hvo_bow_last_kernel_ms(self.h, _p(ms)), "bow_last_kernel_ms")
         return float(ms[0]), float(ms[1])
 
+    def pnp_ransac(self, cam, problems, params=None, want_sample=False, check=True, spare_events=0):
+        """PnPsolver's EPnP RANSAC of every candidate in one call.  cam = (fx, fy, cx, cy); problems: a list of dict(p3d (n x 3), p2d (n x 2),
+        sigma2 (n), feature_index (n), n_features); params: pnp_params(...).  Returns one dict per candidate (hyp_inliers, hyp_event, events,
+        best_*, the effective N / min_inliers / max_its / epsilon, T, no_more, status); pnp_iterate replays iterate() over it.  check=False:
+        a candidate with more records than max_events does not raise, its status is -5.  spare_events: room for that many events beyond max_events
+        (cap_events > max_events; the call leaves them alone).  Each dict's "raw" holds the whole arrays as the call left them."""
+        P = params or pnp_params()
+        Q = (PnpProblem * len(problems))(); keep = []
+        for j, pr in enumerate(problems):
+            a = [np.ascontiguousarray(pr["p3d"], np.float32).reshape(-1, 3), np.ascontiguousarray(pr["p2d"], np.float32).reshape(-1, 2),
+                 np.ascontiguousarray(pr["sigma2"], np.float32).reshape(-1), np.ascontiguousarray(pr["feature_index"], np.int32).reshape(-1)]
+            n = len(a[0])
+            if not (len(a[1]) == len(a[2]) == len(a[3]) == n):
+                raise ValueError("pnp_ransac: a problem's arrays differ in length")
+            Q[j].p3d, Q[j].p2d, Q[j].sigma2, Q[j].feature_index = [v.ctypes.data if n else None for v in a]
+            Q[j].n = n; Q[j].n_features = int(pr["n_features"]); keep.append(a)
+        R, rk = _pnp_results(len(problems), [pr["n_features"] for pr in problems], P, want_sample, spare_events)
+        cm = _pose_cam(tuple(cam[:4]) + (0.0,))
+        rc = lib().hvo_pnp_ransac(self.h, C.byref(cm), C.byref(P), len(problems), Q, R)
+        if rc != -5 or check:
+            self._chk(rc, "pnp_ransac")
+        return _pnp_finish(R, rk, P.min_set)
+
+    def pnp_last_kernel_ms(self):
+        """(hypothesis kernels, refine kernels): device ms of the last pnp_ransac"""
+        ms = np.zeros(2, np.float32)
+        self._chk(lib().hvo_pnp_last_kernel_ms(self.h, _p(ms)), "pnp_last_kernel_ms")
+        return float(ms[0]), float(ms[1])
+
     def search_by_bow(self, frame, kfs, nnratio=0.7, check_orientation=True, th_low=50):
         """ORBmatcher::SearchByBoW on host arrays: frame = dict(desc, node_id, angle), kfs = list of dict(desc, node_id, has_map_point, angle).
         Returns a list of (match_kf, n_matches), one per key frame."""
@@ -1807,6 +1951,33 @@ class Stream:
         """(ComputeBoW kernels, SearchByBoW kernels): device ms of the last calls on the resident frame `cur`"""
         ms = np.zeros(2, np.float32)
         self._chk(lib().hvo_stream_bow_last_kernel_ms(self.h, cur, _p(ms)), "stream_bow_last_kernel_ms")
+        return float(ms[0]), float(ms[1])
+
+    def pnp_ransac(self, cur, cam, kf_sides, params=None, want_sample=False, check=True):
+        """PnPsolver's RANSAC of every candidate against the resident frame `cur`: kf_sides is a list of dict(match_kf (as search_by_bow returned
+        it), pos (key-frame features x 3 world positions), bad (a byte per key-frame feature)).  Returns what Context.pnp_ransac returns."""
+        P = params or pnp_params()
+        K = (PnpKeyframeSide * len(kf_sides))(); keep = []
+        for j, kf in enumerate(kf_sides):
+            a = [np.ascontiguousarray(kf["match_kf"], np.int32).reshape(-1), np.ascontiguousarray(kf["pos"], np.float32).reshape(-1, 3),
+                 np.ascontiguousarray(np.asarray(kf["bad"]).astype(bool), np.uint8).reshape(-1)]
+            if len(a[0]) < self.kp_cap:
+                a[0] = np.concatenate([a[0], np.full(self.kp_cap - len(a[0]), -1, np.int32)])
+            if len(a[1]) != len(a[2]):
+                raise ValueError("pnp_ransac: pos and bad differ in length")
+            K[j].match_kf = a[0].ctypes.data; K[j].n = len(a[1])
+            K[j].pos, K[j].bad = [v.ctypes.data if len(a[1]) else None for v in a[1:]]
+            keep.append(a)
+        R, rk = _pnp_results(len(kf_sides), [self.kp_cap] * len(kf_sides), P, want_sample)
+        cm = _pose_cam(tuple(cam[:4]) + (0.0,))
+        rc = lib().hvo_stream_pnp_ransac(self.h, cur, C.byref(cm), C.byref(P), len(kf_sides), K, R)
+        if rc != -5 or check:
+            self._chk(rc, "stream_pnp_ransac")
+        return _pnp_finish(R, rk, P.min_set)
+
+    def pnp_last_kernel_ms(self, cur):
+        ms = np.zeros(2, np.float32)
+        self._chk(lib().hvo_stream_pnp_last_kernel_ms(self.h, cur, _p(ms)), "stream_pnp_last_kernel_ms")
         return float(ms[0]), float(ms[1])
 
     def search_by_bow(self, cur, voc, kfs, nnratio=0.7, check_orientation=True, th_low=50):

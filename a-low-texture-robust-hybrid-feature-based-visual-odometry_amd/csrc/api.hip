@@ -152,6 +152,7 @@ void hvo_destroy(hvo_ctx *ctx)
     if (ctx->ev_fast) (void)hipEventDestroy(ctx->ev_fast);
     for (hipEvent_t e : ctx->po_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->bow_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->pnp_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ls_ev) if (e) (void)hipEventDestroy(e);
     delete ctx;
 }

@@ -155,6 +155,7 @@ struct hvo_ctx {
     bool ls_batch_done = false;            // hvo_batch_line_struct_optimize has optimised the resident batch's 3-D lines (cleared by hvo_batch_run)
     void *tail = nullptr;                  // resident-batch Frame tail (tail.hip)
     hipEvent_t bow_ev[4] = { nullptr, nullptr, nullptr, nullptr }; float bow_ms[2] = { 0.f, 0.f }; bool bow_ev_on[2] = { false, false };   // bow.hip: events around the last calls' launches
+    hipEvent_t pnp_ev[3] = { nullptr, nullptr, nullptr }; float pnp_ms[2] = { 0.f, 0.f }; bool pnp_ev_on = false;   // pnp.hip: events around the last call's two kernel groups
     BowState bow_batch, bow_call;          // bow.hip: the resident batch's bag of words (cleared by hvo_batch_run), the host-array form's block
     // opaque per-subsystem state (peac.hip / lsd.hip own these)
     void *peac = nullptr;
@@ -499,6 +500,13 @@ struct BowFrameSide { int n; const uint8_t *h_desc; const int32_t *h_node; const
                       const uint8_t *d_desc; const float *d_angle; int angle_step; const int *d_fv_node, *d_fv_start, *d_fv_idx, *d_n_rows; };
 int bow_search(hvo_ctx *ctx, hipStream_t st, const BowFrameSide &F, int n_kf, const hvo_bow_keyframe *kf, const hvo_bow_search_params *P,
                hvo_bow_matches *res, std::string *err);
+
+// pnp.hip: PnPsolver's RANSAC of n_kf candidates on stream st, scratch from ctx's call arena; returns after the stream has drained.  rsd null:
+// prob's host arrays go up; else the frame side is the resident frame's undistorted key points (nf of them; sigma2 = mvLevelSigma2) and
+// the constructor's compaction runs on the device over kf[j]'s map side.
+struct PnpResident { const hvo_keypoint *d_kp_un; int nf; float sigma2[HVO_MAX_LEVELS]; const hvo_pnp_keyframe_side *kf; };
+int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_params *P, int n_kf, const hvo_pnp_problem *prob, const PnpResident *rsd,
+            hvo_pnp_result *res, std::string *err);
 
 // pose_opt.hip: Optimizer::PoseOptimization of n frames in one launch on stream st, scratch from ctx's call arena; returns after the stream
 // has drained.  rsd null: prob's frame-side host arrays go up too; else frame f's frame side is read at rsd[f]'s device pointers.

@@ -1006,6 +1006,32 @@ int hvo_stream_bow_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2])
     return hvo_bow_last_kernel_ms(B->ctx, ms2);
 }
 
+// PnPsolver's RANSAC of n_kf candidates against the resident frame `cur` (pnp.hip): mvKeysUn stays on the device, the map side goes up
+int hvo_stream_pnp_ransac(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_pnp_params *params, int n_kf, const hvo_pnp_keyframe_side *kf_sides,
+                          hvo_pnp_result *results)
+{
+    if (!s) return HVO_ERR_INVALID_ARG;
+    if (!cam || !params || !kf_sides || !results || n_kf < 1) { s->last_error = "pnp: a null argument or n_kf < 1"; return HVO_ERR_INVALID_ARG; }
+    if (!(s->sp.stages & HVO_STAGE_ORB)) { s->last_error = "pnp: the stream must run HVO_STAGE_ORB"; return HVO_ERR_INVALID_ARG; }
+    StreamSlot *B = slot_of(s, cur);
+    if (!B) { s->last_error = "pnp: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    ST_HIP(hipEventSynchronize(B->ev_orb));
+    hvo_ctx *c = B->ctx;
+    PnpResident R;
+    R.d_kp_un = B->d_kp_un; R.nf = std::max(0, std::min(((const int *)(B->h_out + s->lay.counts))[0], s->kp_cap)); R.kf = kf_sides;
+    for (int i = 0; i < HVO_MAX_LEVELS; i++) R.sigma2[i] = i < c->p.orb_nlevels ? c->scale[i] * c->scale[i] : 1.0f;
+    return pnp_run(c, s->s_match, cam, params, n_kf, nullptr, &R, results, &s->last_error);
+}
+
+int hvo_stream_pnp_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2])
+{
+    if (!s || !ms2) return HVO_ERR_INVALID_ARG;
+    StreamSlot *B = slot_of(s, cur);
+    if (!B) { s->last_error = "pnp: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    return hvo_pnp_last_kernel_ms(B->ctx, ms2);
+}
+
 int hvo_stream_pose_last_kernel_ms(hvo_stream *s, int64_t cur, float *ms)
 {
     if (!s || !ms) return HVO_ERR_INVALID_ARG;

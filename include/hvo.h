@@ -1005,6 +1005,76 @@ int hvo_stream_search_by_bow(hvo_stream *s, int64_t cur, const hvo_vocabulary *v
 int hvo_bow_last_kernel_ms(const hvo_ctx *ctx, float ms2[2]);
 int hvo_stream_bow_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2]);
 
+/* ---- The relocalisation PnP solver: PnPsolver's EPnP RANSAC for all candidates of a relocalisation in one call (csrc/pnp.hip) ----
+ * Restated: the PnPsolver constructor (src/PnPsolver.cc:67-110), SetRansacParameters (:121-157), iterate (:165-258), Refine (:260-305),
+ * CheckInliers (:308-339) and EPnP (:342-950), as Tracking::Relocalization drives them (src/Tracking.cc:3789-3909).  There is no batch
+ * form: a relocalisation is ONE frame against many key frames, and the many are the launch's width.
+ *
+ * iterate() is sequential only through mnIterations, mnBestInliers and mvbBestInliers, and Refine() depends on nothing but the current
+ * best set.  So one call evaluates all T hypotheses of every candidate and returns what a host replay of the loop needs (hvo::PnPsolver
+ * in hvo.hpp, hvo_amd.pnp_iterate in Python).  With it = 1..T: hypothesis it has a count hyp_inliers[it-1]; it PASSES when that count is
+ * >= min_inliers; a passing iteration is a RECORD when its count exceeds the running best (only passing iterations update the best);
+ * Refine runs EPnP on the record's inliers in ascending correspondence index and then CheckInliers, and succeeds when the refined count
+ * is STRICTLY greater than min_inliers (:292, against >= at :209); a passing iteration that is no record repeats the last record's Refine
+ * with the same outcome.  Every record is an event, in order; hyp_event[it-1] is the event iterate() returns in iteration it, or -1.
+ * T = the effective maxIts + extra_iterations (the loop's `mnIterations < maxIts || nCurrentIterations < nIterations` may overrun the cap
+ * by a chunk; a replay that needs hypothesis T + 1 reports bNoMore).  N < min_inliers: T = 0 and no_more is set (:173-177).
+ * Limits: T <= 1024, N <= 4096, 4 <= min_set <= 64, n_kf <= 256, max_events <= 64, and 1 GiB of device scratch per call
+ * (HVO_ERR_UNSUPPORTED beyond; min_set < 4 is HVO_ERR_INVALID_ARG).  More records than max_events: that candidate's status and the
+ * call's return value are HVO_ERR_CAPACITY, its first max_events events are complete, nothing past them is written, and hyp_event is -1
+ * where it would name a record that was not kept.
+ *
+ * Determinism and readings.  Random draws: the reference draws from the process-global rand(), shared by all solvers; here `seed` is a
+ * parameter, hypothesis (candidate j, iteration it) has its own xorshift32 stream seeded seed ^ (0x9E3779B9 * (1024 j + it)) (0 ->
+ * 0x6D2B79F5), a draw from a set of size s is x % s, removal is the reference's swap-with-last (:199-200).  Linear algebra (OpenCV is not
+ * in the tree): cvSVD of the symmetric 3 x 3 and 12 x 12 matrices is a cyclic two-sided Jacobi eigen-iteration, pairs in row-major order,
+ * exactly 12 sweeps, an exactly zero off-diagonal element giving the identity rotation, eigenpairs in descending eigenvalue with ties by
+ * index; cvSVD of ABt, cvInvert(CV_SVD) and the three cvSolve(CV_SVD) are one-sided (Hestenes) Jacobi, 12 sweeps, singular values at
+ * or below 2 DBL_EPSILON (sum of singular values) cut, so coplanar points take the pseudo-inverse; sums over correspondences
+ * (cvMulTransposed and the loops) are plain ascending sums for up to 64 rows and one fixed tree above (256 strided partials, each run
+ * of 64 halved, the four runs in order).  Only + - * / sqrt, in a fixed order, without contraction.  NOT claimed: with min_set = 4 the
+ * null space of MtM has dimension >= 4 and the four vectors EPnP takes are a basis of it fixed by the Jacobi order, OpenCV's another, so
+ * hypothesis-level parity with the reference binary cannot be claimed; claimed are bit equality with the restatement tests/pnp_ref.py
+ * and recovery of planted poses.  Kept as written: CheckInliers' mix of float and double, a[0] = 1.0f - ..., the 2.0f factors, qr_solve's
+ * pivot scan over rows k..nr-2, > in Refine against >= in iterate, N == min_inliers -> one iteration, the host libm log / pow / ceil of
+ * SetRansacParameters.  Defined: qr_solve's early return on a zero column is a zero step; a hypothesis with a non-finite pose counts 0. */
+typedef struct {
+    double probability; int32_t min_inliers, max_iterations, min_set; float epsilon, th2;      /* SetRansacParameters' arguments */
+    uint32_t seed; int32_t extra_iterations /* 8 */, max_events /* 8 */;
+} hvo_pnp_params;
+void hvo_pnp_default_params(hvo_pnp_params *p);               /* (0.99, 10, 300, 4, 0.5, 5.991), src/Tracking.cc:3805; seed 1 */
+/* One candidate's correspondences, already compacted as the constructor does: mvP3Dw (n x 3), mvP2D (n x 2), mvSigma2 (n), mvKeyPointIndices
+ * (n, each in [0, n_features)); n_features = F.N, the length of vbInliers. */
+typedef struct { const float *p3d, *p2d, *sigma2; const int32_t *feature_index; int32_t n, n_features; } hvo_pnp_problem;
+/* A record: its iteration (1-based), Refine's count, whether Refine succeeded, mRefinedTcw's upper 3 x 4 after convertTo(CV_32F)
+ * (row-major) and Refine's vbInliers (n_features bytes, caller-owned); and the record's own hypothesis -- mnBestInliers, mBestTcw and
+ * mvbBestInliers (by frame feature) for as long as it is the best, which is what iterate() returns with bNoMore when the loop ends
+ * between this record and the next (:241-255). */
+typedef struct { int32_t iteration, n_inliers, success, hyp_n_inliers; float Tcw[12], hyp_Tcw[12]; uint8_t *inliers, *hyp_inliers; } hvo_pnp_event;
+typedef struct {
+    int32_t cap_hyp, cap_events;                                /* in: room of the hyp_* arrays (>= T) and of events (>= max_events) */
+    int32_t *hyp_inliers, *hyp_event;                           /* caller-owned, cap_hyp entries */
+    int32_t *hyp_sample;                                        /* optional (may be null), cap_hyp x min_set: the drawn correspondence indices */
+    hvo_pnp_event *events;
+    uint8_t *best_inliers;                                      /* n_features bytes: mvbBestInliers through mvKeyPointIndices (:247-252), after all T */
+    float best_Tcw[12];                                         /* mBestTcw after all T hypotheses (= the last record's hyp_Tcw) */
+    int32_t best_n_inliers, best_valid /* best >= min_inliers */, best_iteration;
+    int32_t n, n_features, min_inliers, max_its; float epsilon; /* the effective N, F.N, mRansacMinInliers, mRansacMaxIts, mRansacEpsilon */
+    int32_t n_hyp /* T */, n_events, no_more, status;
+} hvo_pnp_result;
+/* n_kf candidates on host arrays, in one launch sequence */
+int hvo_pnp_ransac(hvo_ctx *ctx, const hvo_camera *cam, const hvo_pnp_params *params, int n_kf, const hvo_pnp_problem *problems, hvo_pnp_result *results);
+/* The frame side is the resident frame `cur`: mvKeysUn positions and octaves are read where the stages left them, mvSigma2 is the float
+ * scale[octave]^2 the pose optimisation forms.  Per candidate only the map side goes up: match_kf as hvo_stream_search_by_bow returned it
+ * (one entry per frame feature, -1: none), the key frame's per-feature world positions (n x 3) and a bad-point byte per key-frame feature.
+ * The constructor's compaction runs on the device in ascending frame-feature index.  The result is the host-array form's on the same data. */
+typedef struct { const int32_t *match_kf; const float *pos; const uint8_t *bad; int32_t n; } hvo_pnp_keyframe_side;
+int hvo_stream_pnp_ransac(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_pnp_params *params, int n_kf, const hvo_pnp_keyframe_side *kf_sides,
+                          hvo_pnp_result *results);
+/* device time in ms of the last call's hypothesis kernels (ms2[0]: hypotheses + scan) and refine kernels (ms2[1]: refine + events) */
+int hvo_pnp_last_kernel_ms(const hvo_ctx *ctx, float ms2[2]);
+int hvo_stream_pnp_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2]);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer. Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

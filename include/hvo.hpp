@@ -12,6 +12,7 @@
 // Frame.cc adaptor is a reinterpret of vector storage.  No CPU fallback: every call
 // throws hvo::Error when libhvo.so / a gfx950 device is unavailable.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <memory>
@@ -872,5 +873,83 @@ inline void LineOptStruct(FrameStream &fs, int64_t cur, int NL, FrameLines &f, b
 {
     Manhattan::run(fs, cur, NL, f, both ? (HVO_LINE_STRUCT_CONSTRAINTS | HVO_LINE_STRUCT_OPTIMIZE) : HVO_LINE_STRUCT_OPTIMIZE, row_rule);
 }
+
+// PnPsolver (src/PnPsolver.h) with the reference's surface and ONE device call underneath for all candidates of a relocalisation:
+// solve_candidates evaluates every hypothesis of every candidate (hvo_stream_pnp_ransac), iterate() is a host replay over hyp_event /
+// the events that keeps mnIterations between calls, so Tracking::Relocalization's round-robin loop (src/Tracking.cc:3834-3909) reads as it
+// does today.  A replay that would need a hypothesis past the T evaluated ones reports bNoMore.
+class PnPsolver {
+public:
+    PnPsolver() { hvo_pnp_default_params(&params_); }
+    // the result's pointers lead into this object's own vectors: a move carries the buffers along, a copy would leave them behind
+    PnPsolver(const PnPsolver &) = delete;
+    PnPsolver &operator=(const PnPsolver &) = delete;
+    PnPsolver(PnPsolver &&) = default;
+    PnPsolver &operator=(PnPsolver &&) = default;
+    // the reference sets the parameters per solver before iterating; here they apply to the next solve_candidates
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4f, float th2 = 5.991f)
+    {
+        params_.probability = probability; params_.min_inliers = minInliers; params_.max_iterations = maxIterations; params_.min_set = minSet;
+        params_.epsilon = epsilon; params_.th2 = th2;
+    }
+    hvo_pnp_params &params() { return params_; }
+    // one call for all candidates: solvers[j] takes candidate j's result (its parameters are solvers[0]'s: Relocalization gives every solver the same)
+    static void solve_candidates(FrameStream &fs, int64_t cur, const hvo_camera &cam, const std::vector<hvo_pnp_keyframe_side> &kf_sides, std::vector<PnPsolver> &solvers)
+    {
+        const int n = (int)kf_sides.size();
+        if (n < 1 || (int)solvers.size() != n) throw Error(HVO_ERR_INVALID_ARG, "PnPsolver::solve_candidates");
+        const hvo_pnp_params P = solvers[0].params_;
+        std::vector<hvo_pnp_result> res((size_t)n);
+        for (int j = 0; j < n; j++) { solvers[j].params_ = P; solvers[j].alloc(fs.kpCap()); res[j] = solvers[j].res_; }
+        const int rc = hvo_stream_pnp_ransac(fs.get(), cur, &cam, &P, n, kf_sides.data(), res.data());
+        for (int j = 0; j < n; j++) { solvers[j].res_ = res[j]; solvers[j].mnIterations = 0; }
+        if (rc != HVO_ERR_CAPACITY) check(rc, "hvo_stream_pnp_ransac");      // a candidate past max_events keeps its status; iterate() throws for that one
+    }
+    // cv::Mat iterate(nIterations, bNoMore, vbInliers, nInliers): true and Tcw (upper 3 x 4, row-major) when the reference returns a pose
+    bool iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers, float Tcw[12])
+    {
+        bNoMore = false; vbInliers.clear(); nInliers = 0;
+        if (res_.status != HVO_OK) throw Error(res_.status, "PnPsolver::iterate: more records than max_events");
+        if (res_.n < res_.min_inliers) { bNoMore = true; return false; }
+        int nCurrentIterations = 0;
+        while (mnIterations < res_.max_its || nCurrentIterations < nIterations) {
+            nCurrentIterations++; mnIterations++;
+            if (mnIterations > res_.n_hyp) { bNoMore = true; return false; }
+            const int e = hyp_event_[mnIterations - 1];
+            if (e >= 0) {
+                const hvo_pnp_event &V = events_[e];
+                nInliers = V.n_inliers; vbInliers.assign(V.inliers, V.inliers + res_.n_features);
+                for (int i = 0; i < 12; i++) Tcw[i] = V.Tcw[i];
+                return true;
+            }
+        }
+        if (mnIterations >= res_.max_its) {
+            bNoMore = true;
+            const hvo_pnp_event *last = nullptr;                 // mnBestInliers / mBestTcw now: the latest record at or before mnIterations
+            for (int e = 0; e < res_.n_events; e++) if (events_[e].iteration <= mnIterations) last = &events_[e];
+            if (last) {
+                nInliers = last->hyp_n_inliers; vbInliers.assign(last->hyp_inliers, last->hyp_inliers + res_.n_features);
+                for (int i = 0; i < 12; i++) Tcw[i] = last->hyp_Tcw[i];
+                return true;
+            }
+        }
+        return false;
+    }
+    bool find(std::vector<bool> &vbInliers, int &nInliers, float Tcw[12]) { bool f; return iterate(res_.max_its, f, vbInliers, nInliers, Tcw); }
+    const hvo_pnp_result &result() const { return res_; }
+    int mnIterations = 0;
+private:
+    void alloc(int n_features)
+    {
+        const int cap = std::min(1024, params_.max_iterations + params_.extra_iterations), E = params_.max_events;
+        hyp_inl_.assign(cap, 0); hyp_event_.assign(cap, -1); events_.assign(E, hvo_pnp_event()); inl_.assign((size_t)(2 * E + 1) * n_features, 0);
+        for (int e = 0; e < E; e++) { events_[e].inliers = inl_.data() + (size_t)(2 * e) * n_features; events_[e].hyp_inliers = inl_.data() + (size_t)(2 * e + 1) * n_features; }
+        res_ = hvo_pnp_result();
+        res_.cap_hyp = cap; res_.cap_events = E; res_.hyp_inliers = hyp_inl_.data(); res_.hyp_event = hyp_event_.data(); res_.hyp_sample = nullptr;
+        res_.events = events_.data(); res_.best_inliers = inl_.data() + (size_t)(2 * E) * n_features;
+    }
+    hvo_pnp_params params_; hvo_pnp_result res_ = hvo_pnp_result();
+    std::vector<int32_t> hyp_inl_, hyp_event_; std::vector<hvo_pnp_event> events_; std::vector<uint8_t> inl_;
+};
 
 }  // namespace hvo
