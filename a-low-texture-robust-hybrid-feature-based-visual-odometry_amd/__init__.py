@@ -271,34 +271,45 @@ def _ll_params(bounds4, log_scale_factor, th, nn_ratio):
     return p
 
 
-def _ll_io(n_kl, n_slots, held, seen_extra, want_rel):
-    """-> (LocalLinesIO, dict of the arrays it points at)"""
-    capq = max(1, min(n_slots, LINE_MAP_MAX_QUERIES)); nk = max(n_kl, 1)
+def _map_io(io, n_key, what, n_slots, max_queries, held, seen_extra, proj_cols, **more):
+    """the part of _ll_io / _lp_io that is the same: fills io (n_kl / n_kp already set) -> (io, dict of the arrays it points at); more: further
+    arrays (None: not wanted)"""
+    capq = max(1, min(n_slots, max_queries)); nk = max(n_key, 1)
     h = np.full(nk, -1, np.int32)
     if held is not None:
         hh = np.asarray(held, np.int32).reshape(-1)
-        if len(hh) != n_kl:
-            raise ValueError("held must have one entry per key line (%d)" % n_kl)
-        h[:n_kl] = hh
+        if len(hh) != n_key:
+            raise ValueError("held must have one entry per key %s (%d)" % (what, n_key))
+        h[:n_key] = hh
     ex = np.ascontiguousarray([] if seen_extra is None else seen_extra, np.int32).reshape(-1)
-    a = dict(held=h, seen_extra=ex, in_view_slot=np.zeros(capq, np.int32), proj=np.zeros((capq, 4), np.float32), view_cos=np.zeros(capq, np.float32),
-             level=np.zeros(capq, np.int32), match_idx=np.full(capq, -1, np.int32), match_dist=np.full(capq, 256, np.int32),
-             n_par=np.zeros(nk, np.int32), n_perp=np.zeros(nk, np.int32), rel_map=np.zeros(nk * capq, np.int8) if want_rel else None)
-    io = LocalLinesIO()
-    io.n_kl = n_kl; io.n_seen_extra = len(ex)
+    a = dict(held=h, seen_extra=ex, in_view_slot=np.zeros(capq, np.int32), proj=np.zeros((capq, proj_cols), np.float32), view_cos=np.zeros(capq, np.float32),
+             level=np.zeros(capq, np.int32), match_idx=np.full(capq, -1, np.int32), match_dist=np.full(capq, 256, np.int32), **more)
+    io.n_seen_extra = len(ex)
     for k, v in a.items():
-        if k == "seen_extra":
-            io.seen_extra = v.ctypes.data if len(v) else None
-        else:
-            setattr(io, k, None if v is None else v.ctypes.data)
+        setattr(io, k, None if v is None or (k == "seen_extra" and not len(v)) else v.ctypes.data)
     return io, a
 
 
-def _ll_finish(r, a, n_kl):
+def _map_finish(r, a, n_key):
+    """attaches held and the in-view arrays, cut to the counts -> the in-view count"""
     nq = r.n_in_view if r.status == HVO_OK else 0
-    r.held = a["held"][:n_kl]; r.n_par = a["n_par"][:n_kl]; r.n_perp = a["n_perp"][:n_kl]
+    r.held = a["held"][:n_key]
     for k in ("in_view_slot", "proj", "view_cos", "level", "match_idx", "match_dist"):
         setattr(r, k, a[k][:nq])
+    return nq
+
+
+def _ll_io(n_kl, n_slots, held, seen_extra, want_rel):
+    """-> (LocalLinesIO, dict of the arrays it points at)"""
+    capq = max(1, min(n_slots, LINE_MAP_MAX_QUERIES)); nk = max(n_kl, 1)
+    io = LocalLinesIO(); io.n_kl = n_kl
+    return _map_io(io, n_kl, "line", n_slots, LINE_MAP_MAX_QUERIES, held, seen_extra, 4, n_par=np.zeros(nk, np.int32), n_perp=np.zeros(nk, np.int32),
+                   rel_map=np.zeros(nk * capq, np.int8) if want_rel else None)
+
+
+def _ll_finish(r, a, n_kl):
+    nq = _map_finish(r, a, n_kl)
+    r.n_par = a["n_par"][:n_kl]; r.n_perp = a["n_perp"][:n_kl]
     r.rel_map = None if a["rel_map"] is None else a["rel_map"][: n_kl * nq].reshape(n_kl, nq)
     return r
 
@@ -351,31 +362,12 @@ def _lp_params(bounds4, log_scale_factor, n_levels, bf, th, th_high, nn_ratio, v
 
 def _lp_io(n_kp, n_slots, held, seen_extra):
     """-> (LocalPointsIO, dict of the arrays it points at)"""
-    capq = max(1, min(n_slots, POINT_MAP_MAX_QUERIES)); nk = max(n_kp, 1)
-    h = np.full(nk, -1, np.int32)
-    if held is not None:
-        hh = np.asarray(held, np.int32).reshape(-1)
-        if len(hh) != n_kp:
-            raise ValueError("held must have one entry per key point (%d)" % n_kp)
-        h[:n_kp] = hh
-    ex = np.ascontiguousarray([] if seen_extra is None else seen_extra, np.int32).reshape(-1)
-    a = dict(held=h, seen_extra=ex, in_view_slot=np.zeros(capq, np.int32), proj=np.zeros((capq, 3), np.float32), view_cos=np.zeros(capq, np.float32),
-             level=np.zeros(capq, np.int32), match_idx=np.full(capq, -1, np.int32), match_dist=np.full(capq, 256, np.int32))
-    io = LocalPointsIO()
-    io.n_kp = n_kp; io.n_seen_extra = len(ex)
-    for k, v in a.items():
-        if k == "seen_extra":
-            io.seen_extra = v.ctypes.data if len(v) else None
-        else:
-            setattr(io, k, v.ctypes.data)
-    return io, a
+    io = LocalPointsIO(); io.n_kp = n_kp
+    return _map_io(io, n_kp, "point", n_slots, POINT_MAP_MAX_QUERIES, held, seen_extra, 3)
 
 
 def _lp_finish(r, a, n_kp):
-    nq = r.n_in_view if r.status == HVO_OK else 0
-    r.held = a["held"][:n_kp]
-    for k in ("in_view_slot", "proj", "view_cos", "level", "match_idx", "match_dist"):
-        setattr(r, k, a[k][:nq])
+    _map_finish(r, a, n_kp)
     return r
 
 
@@ -912,118 +904,90 @@ class PlaneMap:
         return c, n.value, bool(b.value)
 
 
-class LineMap:
-    """hvo_line_map: mvpLocalMapLines resident on one device (world end points, world vector, normal, distance range, descriptor, bad and
-    has-observations flags per slot).  Slot index = position in the vector Tracking::SearchLocalLines walks.  Not thread-safe; usable from
-    any Context / Stream of its device."""
+class _SlotMap:
+    """what LineMap and PointMap share.  A subclass names its C prefix (_c), the dtype of its geometry (_dt) and the geometry's arrays as
+    (name, components) (_geo); distance range, descriptor and the two flags are the same for both"""
 
     def __init__(self, device=0, slots=0):
-        self.h = lib().hvo_line_map_create(device, slots)
+        self.h = self._f("create")(device, slots)
         if not self.h:
-            raise HvoError(-3, "hvo_line_map_create")
+            raise HvoError(-3, "hvo_%s_create" % self._c)
+
+    def _f(self, name):
+        return getattr(lib(), "hvo_%s_%s" % (self._c, name))
 
     def close(self):
         if getattr(self, "h", None):
-            lib().hvo_line_map_destroy(self.h)
+            self._f("destroy")(self.h)
             self.h = None
 
     __del__ = close
 
     def _chk(self, rc, what):
         if rc != HVO_OK:
-            raise HvoError(rc, what + ": " + lib().hvo_line_map_last_error(self.h).decode())
+            raise HvoError(rc, "%s_%s: %s" % (self._c, what, self._f("last_error")(self.h).decode()))
+
+    def _set(self, slot, geo, max_dist, min_dist, desc, observed):
+        a = [np.ascontiguousarray(v, self._dt).reshape(c) for v, (_, c) in zip(geo, self._geo)] + [np.ascontiguousarray(desc, np.uint8).reshape(32)]
+        self._chk(self._f("set")(self.h, slot, *[_p(v) for v in a[:-1]], float(max_dist), float(min_dist), _p(a[-1]), 1 if observed else 0), "set")
+
+    def _set_many(self, first, geo, max_dist, min_dist, desc, observed, bad):
+        n = len(np.ascontiguousarray(geo[0], self._dt).reshape(-1, self._geo[0][1]))
+        a = [np.ascontiguousarray(v, self._dt).reshape(n, c) for v, (_, c) in zip(geo, self._geo)]
+        a += [np.ascontiguousarray(max_dist, np.float32).reshape(n), np.ascontiguousarray(min_dist, np.float32).reshape(n), np.ascontiguousarray(desc, np.uint8).reshape(n, 32)]
+        a += [None if v is None else np.ascontiguousarray(np.asarray(v).astype(bool), np.uint8).reshape(n) for v in (observed, bad)]
+        self._chk(self._f("set_many")(self.h, first, n, *[None if v is None or v.size == 0 else _p(v) for v in a]), "set_many")
+
+    def set_bad(self, slot, bad=True):
+        self._chk(self._f("set_bad")(self.h, slot, 1 if bad else 0), "set_bad")
+
+    def set_observed(self, slot, observed=True):
+        self._chk(self._f("set_observed")(self.h, slot, 1 if observed else 0), "set_observed")
+
+    def counts(self):
+        """(slots, good slots, slots with observations)"""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self._f("counts")(self.h, C.byref(a), C.byref(b), C.byref(c)), "counts")
+        return a.value, b.value, c.value
+
+    def slot(self, slot):
+        """dict(pos, wvec (LineMap only), normal, max_dist, min_dist, desc, bad, observed) of one slot"""
+        g = {k: np.zeros(c, self._dt) for k, c in self._geo}; d = np.zeros(32, np.uint8)
+        mx, mn, b, o = C.c_float(0), C.c_float(0), C.c_int(0), C.c_int(0)
+        self._chk(self._f("slot")(self.h, slot, *[_p(v) for v in g.values()], C.byref(mx), C.byref(mn), _p(d), C.byref(b), C.byref(o)), "slot")
+        return dict(g, max_dist=mx.value, min_dist=mn.value, desc=d, bad=bool(b.value), observed=bool(o.value))
+
+
+class LineMap(_SlotMap):
+    """hvo_line_map: mvpLocalMapLines resident on one device (world end points, world vector, normal, distance range, descriptor, bad and
+    has-observations flags per slot).  Slot index = position in the vector Tracking::SearchLocalLines walks.  Not thread-safe; usable from
+    any Context / Stream of its device."""
+    _c, _dt, _geo = "line_map", np.float64, (("pos", 6), ("wvec", 3), ("normal", 3))
 
     def set(self, slot, pos, wvec, normal, max_dist, min_dist, desc, observed=True):
         """set or replace a slot: pos = GetWorldPos() (6), wvec = GetWorldVector(), normal = GetNormal(), the raw mfMaxDistance / mfMinDistance,
         desc = GetDescriptor() (32 bytes), observed = Observations() > 0"""
-        a = [np.ascontiguousarray(pos, np.float64).reshape(6), np.ascontiguousarray(wvec, np.float64).reshape(3),
-             np.ascontiguousarray(normal, np.float64).reshape(3), np.ascontiguousarray(desc, np.uint8).reshape(32)]
-        self._chk(lib().hvo_line_map_set(self.h, slot, _p(a[0]), _p(a[1]), _p(a[2]), float(max_dist), float(min_dist), _p(a[3]), 1 if observed else 0), "line_map_set")
+        self._set(slot, (pos, wvec, normal), max_dist, min_dist, desc, observed)
 
     def set_many(self, first, pos, wvec, normal, max_dist, min_dist, desc, observed=None, bad=None):
         """slots first .. first + n - 1 in one upload: pos (n, 6), wvec / normal (n, 3), max_dist / min_dist (n), desc (n, 32), observed / bad (n) or None"""
-        pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 6); n = len(pos)
-        a = [pos, np.ascontiguousarray(wvec, np.float64).reshape(n, 3), np.ascontiguousarray(normal, np.float64).reshape(n, 3),
-             np.ascontiguousarray(max_dist, np.float32).reshape(n), np.ascontiguousarray(min_dist, np.float32).reshape(n),
-             np.ascontiguousarray(desc, np.uint8).reshape(n, 32)]
-        fl = [None if v is None else np.ascontiguousarray(np.asarray(v).astype(bool), np.uint8).reshape(n) for v in (observed, bad)]
-        pp = lambda v: None if v is None or v.size == 0 else _p(v)
-        self._chk(lib().hvo_line_map_set_many(self.h, first, n, *[pp(v) for v in a], pp(fl[0]), pp(fl[1])), "line_map_set_many")
-
-    def set_bad(self, slot, bad=True):
-        self._chk(lib().hvo_line_map_set_bad(self.h, slot, 1 if bad else 0), "line_map_set_bad")
-
-    def set_observed(self, slot, observed=True):
-        self._chk(lib().hvo_line_map_set_observed(self.h, slot, 1 if observed else 0), "line_map_set_observed")
-
-    def counts(self):
-        """(slots, good slots, slots with observations)"""
-        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._chk(lib().hvo_line_map_counts(self.h, C.byref(a), C.byref(b), C.byref(c)), "line_map_counts")
-        return a.value, b.value, c.value
-
-    def slot(self, slot):
-        """dict(pos, wvec, normal, max_dist, min_dist, desc, bad, observed) of one slot"""
-        pos = np.zeros(6); w = np.zeros(3); nr = np.zeros(3); d = np.zeros(32, np.uint8)
-        mx, mn, b, o = C.c_float(0), C.c_float(0), C.c_int(0), C.c_int(0)
-        self._chk(lib().hvo_line_map_slot(self.h, slot, _p(pos), _p(w), _p(nr), C.byref(mx), C.byref(mn), _p(d), C.byref(b), C.byref(o)), "line_map_slot")
-        return dict(pos=pos, wvec=w, normal=nr, max_dist=mx.value, min_dist=mn.value, desc=d, bad=bool(b.value), observed=bool(o.value))
+        self._set_many(first, (pos, wvec, normal), max_dist, min_dist, desc, observed, bad)
 
 
-class PointMap:
+class PointMap(_SlotMap):
     """hvo_point_map: mvpLocalMapPoints resident on one device (world position, normal, distance range, descriptor, bad and has-observations
     flags per slot).  Slot index = position in the vector Tracking::SearchLocalPoints walks.  Not thread-safe; usable from any Context /
     Stream of its device."""
-
-    def __init__(self, device=0, slots=0):
-        self.h = lib().hvo_point_map_create(device, slots)
-        if not self.h:
-            raise HvoError(-3, "hvo_point_map_create")
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().hvo_point_map_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def _chk(self, rc, what):
-        if rc != HVO_OK:
-            raise HvoError(rc, what + ": " + lib().hvo_point_map_last_error(self.h).decode())
+    _c, _dt, _geo = "point_map", np.float32, (("pos", 3), ("normal", 3))
 
     def set(self, slot, pos, normal, max_dist, min_dist, desc, observed=True):
         """set or replace a slot: pos = GetWorldPos() (3), normal = GetNormal() (3), the raw mfMaxDistance / mfMinDistance, desc = GetDescriptor()
         (32 bytes), observed = Observations() > 0"""
-        a = [np.ascontiguousarray(pos, np.float32).reshape(3), np.ascontiguousarray(normal, np.float32).reshape(3), np.ascontiguousarray(desc, np.uint8).reshape(32)]
-        self._chk(lib().hvo_point_map_set(self.h, slot, _p(a[0]), _p(a[1]), float(max_dist), float(min_dist), _p(a[2]), 1 if observed else 0), "point_map_set")
+        self._set(slot, (pos, normal), max_dist, min_dist, desc, observed)
 
     def set_many(self, first, pos, normal, max_dist, min_dist, desc, observed=None, bad=None):
         """slots first .. first + n - 1 in one upload: pos / normal (n, 3), max_dist / min_dist (n), desc (n, 32), observed / bad (n) or None"""
-        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3); n = len(pos)
-        a = [pos, np.ascontiguousarray(normal, np.float32).reshape(n, 3), np.ascontiguousarray(max_dist, np.float32).reshape(n),
-             np.ascontiguousarray(min_dist, np.float32).reshape(n), np.ascontiguousarray(desc, np.uint8).reshape(n, 32)]
-        fl = [None if v is None else np.ascontiguousarray(np.asarray(v).astype(bool), np.uint8).reshape(n) for v in (observed, bad)]
-        pp = lambda v: None if v is None or v.size == 0 else _p(v)
-        self._chk(lib().hvo_point_map_set_many(self.h, first, n, *[pp(v) for v in a], pp(fl[0]), pp(fl[1])), "point_map_set_many")
-
-    def set_bad(self, slot, bad=True):
-        self._chk(lib().hvo_point_map_set_bad(self.h, slot, 1 if bad else 0), "point_map_set_bad")
-
-    def set_observed(self, slot, observed=True):
-        self._chk(lib().hvo_point_map_set_observed(self.h, slot, 1 if observed else 0), "point_map_set_observed")
-
-    def counts(self):
-        """(slots, good slots, slots with observations)"""
-        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._chk(lib().hvo_point_map_counts(self.h, C.byref(a), C.byref(b), C.byref(c)), "point_map_counts")
-        return a.value, b.value, c.value
-
-    def slot(self, slot):
-        """dict(pos, normal, max_dist, min_dist, desc, bad, observed) of one slot"""
-        pos = np.zeros(3, np.float32); nr = np.zeros(3, np.float32); d = np.zeros(32, np.uint8)
-        mx, mn, b, o = C.c_float(0), C.c_float(0), C.c_int(0), C.c_int(0)
-        self._chk(lib().hvo_point_map_slot(self.h, slot, _p(pos), _p(nr), C.byref(mx), C.byref(mn), _p(d), C.byref(b), C.byref(o)), "point_map_slot")
-        return dict(pos=pos, normal=nr, max_dist=mx.value, min_dist=mn.value, desc=d, bad=bool(b.value), observed=bool(o.value))
+        self._set_many(first, (pos, normal), max_dist, min_dist, desc, observed, bad)
 
 
 class Vocabulary:

@@ -3,27 +3,26 @@
 //   MapLine::PredictScale (src/MapLine.cpp:549-558), the search core of line_map.inc, the CosSita > 0.09 post-gate (3357-3386), and
 //   Manhattan::computeStructConstInMap (src/Manhattan.cpp:163-224, rotCW 217-224, computeAngle 1054-1071).
 //
-// The map.  Per slot (= position in mvpLocalMapLines): GetWorldPos() (6 doubles), GetWorldVector() (3), GetNormal() (3), mfMaxDistance and
-// mfMinDistance (raw floats), GetDescriptor() (32 bytes) and one flag byte (bit 0 bad, bit 1 Observations() > 0).  Every component is an
-// array of its own over the slots (pos: six arrays of `cap` doubles, and so on): the frustum kernel runs one lane per slot, so a wave's
-// load of one component covers 512 contiguous bytes; packed 48-byte positions would put the lanes' loads 48 bytes apart and touch every
-// line six times.  The descriptor is the exception: it is consumed whole, 32 bytes by one lane of the gather, and stays packed.  The host
-// mirror is the truth; storage grows only, by a new allocation and one upload of the mirror.
+// The map is a slot map (slot_map.hpp: the storage, its growth and uploads, the flag byte, the call's skeleton).  Per slot (= position in
+// mvpLocalMapLines) the line map keeps GetWorldPos() (6 doubles), GetWorldVector() (3), GetNormal() (3), mfMaxDistance and mfMinDistance (raw
+// floats) and GetDescriptor() (32 bytes).  Every component is an array of its own over the slots (pos: six arrays of `cap` doubles, and so
+// on): the frustum kernel runs one lane per slot, so a wave's load of one component covers 512 contiguous bytes; packed 48-byte positions
+// would put the lanes' loads 48 bytes apart and touch every line six times.  The descriptor is consumed whole, 32 bytes by one lane of the
+// gather, and stays packed.
 //
 // The call, the same kernels for the host, stream and batch forms (bit-identical results):
-//   k_ll_mark      per frame line: a held slot that is bad becomes -1; t_occupied = held and the slot has observations; the held slots and
-//                  the caller's seen_extra slots are marked seen (plain byte stores of 1)
+//   k_sm_mark      (slot_map.hip) held slots that are bad become -1; t_occupied = held and the slot has observations; held and seen_extra
+//                  slots are marked seen
 //   k_ll_frustum   one lane per slot, the slot loaded ONCE and tested under every frame's pose: bad / seen skip, isInFrustum as written,
 //                  PredictScale; per (frame, slot) a pass flag and the projections, per (frame, block) the number of survivors
-//   k_ll_compact   the survivors in ASCENDING SLOT ORDER: position = (sum of the counts of the blocks before) + (wave ballot prefix inside
-//                  the block).  No atomic decides an order.  The world vector, descriptor and observation flag are gathered by slot into
-//                  the query arrays the search core reads.
+//   k_ll_compact   the survivors in ASCENDING SLOT ORDER (sm_compact_pos).  The world vector, descriptor and observation flag are gathered
+//                  by slot into the query arrays the search core reads.
 //   -- the in-view counts come down here: the search core's grid is one wave per query, so the host has to know them; more than 16384
 //      in view is refused (HVO_ERR_UNSUPPORTED) with `held` untouched --
 //   k_lsbp_map_keys, k_lsbp_map_epilogue (line_map.inc, unchanged) on the device-resident queries; not run when nothing is in view
-//   k_ll_assign    held[match_idx[q]] = slot(q) in query order: the LAST query that matched a line wins, taken as an atomicMax of q per
-//                  line (a maximum does not depend on the order of its operands)
-//   k_ll_gate      only when the search matched something: for every line with held >= 0, lines held before the call included, CosSita
+//   k_sm_assign    (slot_map.hip) per frame line the LAST query in query order that matched it
+//   k_ll_gate      held[i] = the winning query's slot; then, only when the search matched something: for every line with held >= 0, lines
+//                  held before the call included, CosSita
 //   k_ll_struct    computeStructConstInMap: one thread per (frame line, in-view entry), the dense relation byte and the two counts
 //
 // Readings (OpenCV and Eigen are not in the reference tree; DESIGN.md section 7, tests/line_map_ref.py restates the same):
@@ -41,140 +40,48 @@
 //   Mat::cross                   in float; NormalVector_ /= norm_: each element divided in double, rounded to float
 //   rotCW                        Rcw converted to double times the double line equation, sums left to right (it multiplies by Rcw, as written)
 // No contraction (-ffp-contract=off, __f*_rn).  The predicted level is reported and never read.
-#include "hvo_internal.hpp"
+#include "slot_map.hpp"
 #include <math.h>
 #include <string.h>
 #include <string>
 #include <vector>
 
-#define LL_BLOCK 256
-#define LL_BAD 1
-#define LL_OBS 2
+#define LL_BLOCK SM_BLOCK
 
-struct hvo_line_map {
-    int device = 0;
-    hipStream_t st = nullptr;                                    // the map's own uploads
-    int n_slots = 0, cap = 0;
-    std::vector<double> h_pos, h_wvec, h_nrm;                    // component-major: component c of slot j at [c * cap + j]
-    std::vector<float> h_maxd, h_mind;
-    std::vector<uint8_t> h_desc, h_flags;
-    double *d_pos = nullptr, *d_wvec = nullptr, *d_nrm = nullptr;
-    float *d_maxd = nullptr, *d_mind = nullptr;
-    uint8_t *d_desc = nullptr, *d_flags = nullptr;
-    char *d_a = nullptr, *d_b = nullptr; size_t a_bytes = 0, b_bytes = 0;    // the calls' scratch (before / after the in-view counts), grow-only
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    std::string last_error;
+struct hvo_line_map : hvo_slot_map {
+    hvo_line_map() : hvo_slot_map("line map", "HVO_LINE_MAP_MAX_SLOTS", HVO_LINE_MAP_MAX_SLOTS, { { 8, 6 }, { 8, 3 }, { 8, 3 }, { 4, 1 }, { 4, 1 }, { 32, 1 }, { 1, 1, SM_BAD } }) {}
+    enum { POS, WVEC, NRM, MAXD, MIND, DESC };                   // pos, wvec, nrm: doubles; maxd, mind: floats; desc: 32 bytes packed; then the flags
 };
-
-#define LM_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { m->last_error = std::string(#call) + ": " + hipGetErrorString(e_); return HVO_ERR_HIP; } } while (0)
-
-static size_t ll_al(size_t v) { return (v + 255) & ~(size_t)255; }
-
-static void lm_free_device(hvo_line_map *m)
-{
-    void *p[] = { m->d_pos, m->d_wvec, m->d_nrm, m->d_maxd, m->d_mind, m->d_desc, m->d_flags };
-    for (void *q : p) if (q) (void)hipFree(q);
-    m->d_pos = m->d_wvec = m->d_nrm = nullptr; m->d_maxd = m->d_mind = nullptr; m->d_desc = m->d_flags = nullptr;
-}
-
-// slots [first, first + n) of the host mirror -> device
-static int lm_upload(hvo_line_map *m, int first, int n)
-{
-    if (n <= 0) return HVO_OK;
-    const size_t cap = (size_t)m->cap, f = (size_t)first, c = (size_t)n;
-    for (int k = 0; k < 6; k++) LM_HIP(hipMemcpyAsync(m->d_pos + k * cap + f, m->h_pos.data() + k * cap + f, c * 8, hipMemcpyHostToDevice, m->st));
-    for (int k = 0; k < 3; k++) LM_HIP(hipMemcpyAsync(m->d_wvec + k * cap + f, m->h_wvec.data() + k * cap + f, c * 8, hipMemcpyHostToDevice, m->st));
-    for (int k = 0; k < 3; k++) LM_HIP(hipMemcpyAsync(m->d_nrm + k * cap + f, m->h_nrm.data() + k * cap + f, c * 8, hipMemcpyHostToDevice, m->st));
-    LM_HIP(hipMemcpyAsync(m->d_maxd + f, m->h_maxd.data() + f, c * 4, hipMemcpyHostToDevice, m->st));
-    LM_HIP(hipMemcpyAsync(m->d_mind + f, m->h_mind.data() + f, c * 4, hipMemcpyHostToDevice, m->st));
-    LM_HIP(hipMemcpyAsync(m->d_desc + f * 32, m->h_desc.data() + f * 32, c * 32, hipMemcpyHostToDevice, m->st));
-    LM_HIP(hipMemcpyAsync(m->d_flags + f, m->h_flags.data() + f, c, hipMemcpyHostToDevice, m->st));
-    LM_HIP(hipStreamSynchronize(m->st));
-    return HVO_OK;
-}
-
-// room for `want` slots.  The new device arrays are allocated first: when one allocation fails nothing of the map has changed.  After a
-// regrowth (*regrown) the device arrays are empty and the caller uploads every slot in use.
-static int lm_reserve(hvo_line_map *m, int want, bool *regrown)
-{
-    *regrown = false;
-    if (want <= m->cap) return HVO_OK;
-    int cap = std::max(m->cap, 64);
-    while (cap < want) cap *= 2;
-    const size_t c = (size_t)cap;
-    const size_t bytes[7] = { c * 48, c * 24, c * 24, c * 4, c * 4, c * 32, c };
-    void *nd[7] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    for (int k = 0; k < 7; k++)
-        if (hipMalloc(&nd[k], bytes[k]) != hipSuccess) {
-            for (int q = 0; q < k; q++) (void)hipFree(nd[q]);
-            m->last_error = "line map: hipMalloc of the slot arrays"; return HVO_ERR_HIP;
-        }
-    // the mirror moves to the new component stride
-    auto regrid = [&](std::vector<double> &v, int comps) {
-        std::vector<double> nv((size_t)comps * cap, 0.0);
-        for (int k = 0; k < comps; k++) for (int j = 0; j < m->n_slots; j++) nv[(size_t)k * cap + j] = v[(size_t)k * m->cap + j];
-        v.swap(nv);
-    };
-    regrid(m->h_pos, 6); regrid(m->h_wvec, 3); regrid(m->h_nrm, 3);
-    m->h_maxd.resize(cap, 0.f); m->h_mind.resize(cap, 0.f); m->h_desc.resize((size_t)cap * 32, 0); m->h_flags.resize(cap, LL_BAD);
-    lm_free_device(m);
-    m->d_pos = (double *)nd[0]; m->d_wvec = (double *)nd[1]; m->d_nrm = (double *)nd[2]; m->d_maxd = (float *)nd[3]; m->d_mind = (float *)nd[4];
-    m->d_desc = (uint8_t *)nd[5]; m->d_flags = (uint8_t *)nd[6];
-    m->cap = cap; *regrown = true;
-    return HVO_OK;
-}
 
 extern "C" {
 
 hvo_line_map *hvo_line_map_create(int device, int slots)
 {
-    if (device < 0 || slots < 0 || slots > HVO_LINE_MAP_MAX_SLOTS) return nullptr;
-    if (hipSetDevice(device) != hipSuccess) return nullptr;
+    if (device < 0 || slots < 0 || slots > HVO_LINE_MAP_MAX_SLOTS || hipSetDevice(device) != hipSuccess) return nullptr;
     hvo_line_map *m = new hvo_line_map();
-    m->device = device;
-    if (hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking) != hipSuccess) { m->st = nullptr; hvo_line_map_destroy(m); return nullptr; }
-    for (int k = 0; k < 4; k++) if (hipEventCreate(&m->ev[k]) != hipSuccess) { m->ev[k] = nullptr; hvo_line_map_destroy(m); return nullptr; }
-    bool regrown;
-    if (lm_reserve(m, std::max(slots, 1), &regrown)) { hvo_line_map_destroy(m); return nullptr; }
+    if (sm_init(m, device, slots)) { hvo_line_map_destroy(m); return nullptr; }
     return m;
 }
 
-void hvo_line_map_destroy(hvo_line_map *m)
-{
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    if (m->st) { (void)hipStreamSynchronize(m->st); (void)hipStreamDestroy(m->st); }
-    for (int k = 0; k < 4; k++) if (m->ev[k]) (void)hipEventDestroy(m->ev[k]);
-    lm_free_device(m);
-    if (m->d_a) (void)hipFree(m->d_a);
-    if (m->d_b) (void)hipFree(m->d_b);
-    delete m;
-}
+void hvo_line_map_destroy(hvo_line_map *m) { if (m) { sm_release(m); delete m; } }
 
 int hvo_line_map_set_many(hvo_line_map *m, int first, int n, const double *pos, const double *wvec, const double *normal, const float *max_dist,
                           const float *min_dist, const uint8_t *desc, const uint8_t *observed, const uint8_t *bad)
 {
-    if (!m || first < 0 || n < 0) return HVO_ERR_INVALID_ARG;
-    if ((int64_t)first + n > HVO_LINE_MAP_MAX_SLOTS) { m->last_error = "line map: more than HVO_LINE_MAP_MAX_SLOTS slots"; return HVO_ERR_UNSUPPORTED; }
-    if (n == 0) return HVO_OK;
-    if (!pos || !wvec || !normal || !max_dist || !min_dist || !desc) return HVO_ERR_INVALID_ARG;
-    if (hipSetDevice(m->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    int rc; bool regrown;
-    if ((rc = lm_reserve(m, first + n, &regrown))) return rc;
+    bool regrown;
+    const int rc = sm_set_begin(m, first, n, pos && wvec && normal && max_dist && min_dist && desc, &regrown);
+    if (rc || n == 0) return rc;
     const size_t cap = (size_t)m->cap;
+    double *h_pos = m->host<double>(m->POS), *h_wvec = m->host<double>(m->WVEC), *h_nrm = m->host<double>(m->NRM);
     for (int i = 0; i < n; i++) {
         const size_t j = (size_t)first + i;
-        for (int k = 0; k < 6; k++) m->h_pos[k * cap + j] = pos[6 * (size_t)i + k];
-        for (int k = 0; k < 3; k++) { m->h_wvec[k * cap + j] = wvec[3 * (size_t)i + k]; m->h_nrm[k * cap + j] = normal[3 * (size_t)i + k]; }
-        m->h_maxd[j] = max_dist[i]; m->h_mind[j] = min_dist[i];
-        memcpy(&m->h_desc[j * 32], desc + 32 * (size_t)i, 32);
-        m->h_flags[j] = (uint8_t)(((bad && bad[i]) ? LL_BAD : 0) | ((!observed || observed[i]) ? LL_OBS : 0));
+        for (int k = 0; k < 6; k++) h_pos[k * cap + j] = pos[6 * (size_t)i + k];
+        for (int k = 0; k < 3; k++) { h_wvec[k * cap + j] = wvec[3 * (size_t)i + k]; h_nrm[k * cap + j] = normal[3 * (size_t)i + k]; }
+        m->host<float>(m->MAXD)[j] = max_dist[i]; m->host<float>(m->MIND)[j] = min_dist[i];
+        memcpy(m->host<uint8_t>(m->DESC) + j * 32, desc + 32 * (size_t)i, 32);
+        m->h_flags()[j] = sm_flag_byte(observed, bad, i);
     }
-    const int old = m->n_slots;                                  // the slots skipped over stay bad (the mirror's default)
-    if (first + n > m->n_slots) m->n_slots = first + n;
-    if (regrown) return lm_upload(m, 0, m->n_slots);             // fresh device arrays: every slot in use, once
-    const int lo = std::min(first, old), hi = first + n;
-    return lm_upload(m, lo, hi - lo);
+    return sm_set_end(m, first, n, regrown);
 }
 
 int hvo_line_map_set(hvo_line_map *m, int slot, const double pos[6], const double wvec[3], const double normal[3], float max_dist, float min_dist,
@@ -184,43 +91,23 @@ int hvo_line_map_set(hvo_line_map *m, int slot, const double pos[6], const doubl
     return hvo_line_map_set_many(m, slot, 1, pos, wvec, normal, &max_dist, &min_dist, desc, &o, nullptr);
 }
 
-static int lm_set_flag(hvo_line_map *m, int slot, int bit, int on)
-{
-    if (!m || slot < 0 || slot >= m->n_slots) return HVO_ERR_INVALID_ARG;
-    if (hipSetDevice(m->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    m->h_flags[slot] = (uint8_t)(on ? (m->h_flags[slot] | bit) : (m->h_flags[slot] & ~bit));
-    LM_HIP(hipMemcpyAsync(m->d_flags + slot, &m->h_flags[slot], 1, hipMemcpyHostToDevice, m->st));
-    LM_HIP(hipStreamSynchronize(m->st));
-    return HVO_OK;
-}
-
-int hvo_line_map_set_bad(hvo_line_map *m, int slot, int bad) { return lm_set_flag(m, slot, LL_BAD, bad); }
-int hvo_line_map_set_observed(hvo_line_map *m, int slot, int observed) { return lm_set_flag(m, slot, LL_OBS, observed); }
-
-int hvo_line_map_counts(const hvo_line_map *m, int *n_slots, int *n_good, int *n_observed)
-{
-    if (!m) return HVO_ERR_INVALID_ARG;
-    int g = 0, o = 0;
-    for (int j = 0; j < m->n_slots; j++) { g += (m->h_flags[j] & LL_BAD) ? 0 : 1; o += (m->h_flags[j] & LL_OBS) ? 1 : 0; }
-    if (n_slots) *n_slots = m->n_slots;
-    if (n_good) *n_good = g;
-    if (n_observed) *n_observed = o;
-    return HVO_OK;
-}
+int hvo_line_map_set_bad(hvo_line_map *m, int slot, int bad) { return sm_set_flag(m, slot, SM_BAD, bad); }
+int hvo_line_map_set_observed(hvo_line_map *m, int slot, int observed) { return sm_set_flag(m, slot, SM_OBS, observed); }
+int hvo_line_map_counts(const hvo_line_map *m, int *n_slots, int *n_good, int *n_observed) { return sm_counts(m, n_slots, n_good, n_observed); }
 
 int hvo_line_map_slot(const hvo_line_map *m, int slot, double pos[6], double wvec[3], double normal[3], float *max_dist, float *min_dist,
                       uint8_t desc[32], int *bad, int *observed)
 {
     if (!m || slot < 0 || slot >= m->n_slots) return HVO_ERR_INVALID_ARG;
     const size_t cap = (size_t)m->cap, j = (size_t)slot;
-    if (pos) for (int k = 0; k < 6; k++) pos[k] = m->h_pos[k * cap + j];
-    if (wvec) for (int k = 0; k < 3; k++) wvec[k] = m->h_wvec[k * cap + j];
-    if (normal) for (int k = 0; k < 3; k++) normal[k] = m->h_nrm[k * cap + j];
-    if (max_dist) *max_dist = m->h_maxd[j];
-    if (min_dist) *min_dist = m->h_mind[j];
-    if (desc) memcpy(desc, &m->h_desc[j * 32], 32);
-    if (bad) *bad = (m->h_flags[j] & LL_BAD) ? 1 : 0;
-    if (observed) *observed = (m->h_flags[j] & LL_OBS) ? 1 : 0;
+    if (pos) for (int k = 0; k < 6; k++) pos[k] = m->host<double>(m->POS)[k * cap + j];
+    if (wvec) for (int k = 0; k < 3; k++) wvec[k] = m->host<double>(m->WVEC)[k * cap + j];
+    if (normal) for (int k = 0; k < 3; k++) normal[k] = m->host<double>(m->NRM)[k * cap + j];
+    if (max_dist) *max_dist = m->host<float>(m->MAXD)[j];
+    if (min_dist) *min_dist = m->host<float>(m->MIND)[j];
+    if (desc) memcpy(desc, m->host<uint8_t>(m->DESC) + j * 32, 32);
+    if (bad) *bad = (m->h_flags()[j] & SM_BAD) ? 1 : 0;
+    if (observed) *observed = (m->h_flags()[j] & SM_OBS) ? 1 : 0;
     return HVO_OK;
 }
 
@@ -230,12 +117,10 @@ const char *hvo_line_map_last_error(const hvo_line_map *m) { return m ? m->last_
 
 // ---------------------------------------------------------------- kernels ----------------------------------------------------------------
 
-struct LlPose { float R[9], t[3], Ow[3], pad; };
-
 struct LlDev {
     int ns, cap, nframes, nblocks, capq;
     const double *pos, *wvec, *nrm; const float *maxd, *mind; const uint8_t *desc, *flags;
-    const LlPose *pose;                              // nframes
+    const SmPose *pose;                              // nframes
     float fx, fy, cx, cy, minX, maxX, minY, maxY, logsf;
     const uint8_t *seen;                             // nframes x ns
     uint8_t *pass; float4 *s_xyxy; float *s_vc; int *s_lvl;      // nframes x ns, by slot
@@ -243,30 +128,6 @@ struct LlDev {
     int *nview, *ntested;                            // nframes
     int *q_slot; float *q_xyxy; float *q_vc; int *q_lvl; double *q_wvec; uint8_t *q_desc, *q_blocks;   // frame f's queries at f * capq
 };
-
-// one row of Rcw * X + tcw: the reading of k_project_last (match.hip)
-static __device__ __forceinline__ float ll_row(const float *a, float b0, float b1, float b2, float c)
-{
-    float t = __fmul_rn(a[0], b0); t = __fadd_rn(t, __fmul_rn(a[1], b1)); t = __fadd_rn(t, __fmul_rn(a[2], b2));
-    return (float)((double)t * 1.0 + (double)c * 1.0);
-}
-
-__global__ __launch_bounds__(LL_BLOCK) void k_ll_mark(int nt, int ns, const uint8_t *__restrict__ flags, int32_t *__restrict__ held, uint8_t *__restrict__ t_occ,
-                                                        const int32_t *__restrict__ extra, int n_extra, uint8_t *__restrict__ seen)
-{
-    const int i = blockIdx.x * LL_BLOCK + threadIdx.x;
-    if (i < nt) {
-        int h = held[i];
-        if (h >= ns) h = -1;                                       // (refused on the host before the launch)
-        if (h >= 0 && (flags[h] & LL_BAD)) h = -1;                 // Tracking.cc:3296-3299
-        held[i] = h;
-        t_occ[i] = (h >= 0 && (flags[h] & LL_OBS)) ? 1 : 0;
-        if (h >= 0) seen[h] = 1;                                   // mnLastFrameSeen = mCurrentFrame.mnId (3304)
-    } else if (i - nt < n_extra) {
-        const int e = extra[i - nt];
-        if (e >= 0 && e < ns) seen[e] = 1;
-    }
-}
 
 __global__ __launch_bounds__(LL_BLOCK) void k_ll_frustum(LlDev a)
 {
@@ -277,15 +138,15 @@ __global__ __launch_bounds__(LL_BLOCK) void k_ll_frustum(LlDev a)
 #pragma unroll
     for (int k = 0; k < 3; k++) { sp[k] = (float)a.pos[k * cap + jj]; ep[k] = (float)a.pos[(k + 3) * cap + jj]; pn[k] = (float)a.nrm[k * cap + jj]; }
     const float mfMax = a.maxd[jj], mfMin = a.mind[jj];
-    const bool good = in && !(a.flags[jj] & LL_BAD);
+    const bool good = in && !(a.flags[jj] & SM_BAD);
     for (int f = 0; f < a.nframes; f++) {
-        const LlPose &P = a.pose[f];
+        const SmPose &P = a.pose[f];
         const size_t o = (size_t)f * a.ns + jj;
         const bool tested = good && !a.seen[o];
         bool pass = false;
         if (tested) {
-            const float sx = ll_row(P.R, sp[0], sp[1], sp[2], P.t[0]), sy = ll_row(P.R + 3, sp[0], sp[1], sp[2], P.t[1]), sz = ll_row(P.R + 6, sp[0], sp[1], sp[2], P.t[2]);
-            const float ex = ll_row(P.R, ep[0], ep[1], ep[2], P.t[0]), ey = ll_row(P.R + 3, ep[0], ep[1], ep[2], P.t[1]), ez = ll_row(P.R + 6, ep[0], ep[1], ep[2], P.t[2]);
+            const float sx = sm_row(P.R, sp[0], sp[1], sp[2], P.t[0]), sy = sm_row(P.R + 3, sp[0], sp[1], sp[2], P.t[1]), sz = sm_row(P.R + 6, sp[0], sp[1], sp[2], P.t[2]);
+            const float ex = sm_row(P.R, ep[0], ep[1], ep[2], P.t[0]), ey = sm_row(P.R + 3, ep[0], ep[1], ep[2], P.t[1]), ez = sm_row(P.R + 6, ep[0], ep[1], ep[2], P.t[2]);
             if (!(sz < 0.0f || ez < 0.0f)) {
                 const float invz1 = __fdiv_rn(1.0f, sz);
                 const float u1 = __fadd_rn(__fmul_rn(__fmul_rn(a.fx, sx), invz1), a.cx), v1 = __fadd_rn(__fmul_rn(__fmul_rn(a.fy, sy), invz1), a.cy);
@@ -307,58 +168,29 @@ __global__ __launch_bounds__(LL_BLOCK) void k_ll_frustum(LlDev a)
                             const float lv = ceilf(__fdiv_rn(logf(ratio), a.logsf));
                             pass = true;
                             a.s_xyxy[o] = make_float4(u1, v1, u2, v2); a.s_vc[o] = vc;
-                            a.s_lvl[o] = lv != lv ? 0 : lv >= 2147483648.0f ? 2147483647 : lv <= -2147483648.0f ? (-2147483647 - 1) : (int)lv;
+                            a.s_lvl[o] = sm_level(lv);
                         }
                     }
                 }
             }
         }
-        if (in) a.pass[o] = pass ? 1 : 0;
-        const int np = __syncthreads_count(pass), nt = __syncthreads_count(tested);
-        if (threadIdx.x == 0) { a.blockcnt[(size_t)f * a.nblocks + blockIdx.x] = np; if (nt) atomicAdd(&a.ntested[f], nt); }
+        sm_frustum_tail(in, pass, tested, &a.pass[o], &a.blockcnt[(size_t)f * a.nblocks + blockIdx.x], &a.ntested[f]);
     }
 }
 
 __global__ __launch_bounds__(LL_BLOCK) void k_ll_compact(LlDev a)
 {
-    __shared__ int red[LL_BLOCK / 64], wcnt[LL_BLOCK / 64];
-    const int f = blockIdx.y, b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // survivors of the blocks before this one (an integer sum: any order)
-    int s = 0;
-    for (int k = tid; k < b; k += LL_BLOCK) s += a.blockcnt[(size_t)f * a.nblocks + k];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const int j = b * LL_BLOCK + tid;
-    const size_t src = (size_t)f * a.ns + (j < a.ns ? j : 0);
-    const bool p = j < a.ns && a.pass[src];
-    const unsigned long long bm = __ballot(p);
-    if (lane == 0) { red[wave] = s; wcnt[wave] = __popcll(bm); }
-    __syncthreads();
-    int off = 0, before = 0, total = 0;
-    for (int w = 0; w < LL_BLOCK / 64; w++) { off += red[w]; before += w < wave ? wcnt[w] : 0; total += wcnt[w]; }
-    if (b == a.nblocks - 1 && tid == 0) a.nview[f] = off + total;
-    const int q = off + before + __popcll(bm & ((1ull << lane) - 1ull));
+    const int f = blockIdx.y, j = blockIdx.x * LL_BLOCK + threadIdx.x;
+    bool p;
+    const int q = sm_compact_pos(a.blockcnt, a.nblocks, a.ns, f, a.pass, a.nview, &p);
     if (p && q < a.capq) {
-        const size_t d = (size_t)f * a.capq + q, cap = (size_t)a.cap;
+        const size_t d = (size_t)f * a.capq + q, cap = (size_t)a.cap, src = (size_t)f * a.ns + j;
         a.q_slot[d] = j;
         *(float4 *)(a.q_xyxy + 4 * d) = a.s_xyxy[src]; a.q_vc[d] = a.s_vc[src]; a.q_lvl[d] = a.s_lvl[src];
         a.q_wvec[3 * d] = a.wvec[j]; a.q_wvec[3 * d + 1] = a.wvec[cap + j]; a.q_wvec[3 * d + 2] = a.wvec[2 * cap + j];
         *(ulonglong4 *)(a.q_desc + 32 * d) = *(const ulonglong4 *)(a.desc + 32 * (size_t)j);
-        a.q_blocks[d] = (a.flags[j] & LL_OBS) ? 1 : 0;
+        a.q_blocks[d] = (a.flags[j] & SM_OBS) ? 1 : 0;
     }
-}
-
-__global__ __launch_bounds__(LL_BLOCK) void k_ll_fill(int n, int32_t *__restrict__ idx, int32_t *__restrict__ dist)
-{
-    const int i = blockIdx.x * LL_BLOCK + threadIdx.x;
-    if (i < n) { idx[i] = -1; dist[i] = 256; }
-}
-
-__global__ __launch_bounds__(LL_BLOCK) void k_ll_assign(int nq, int nt, const int32_t *__restrict__ match_idx, int *__restrict__ win)
-{
-    const int q = blockIdx.x * LL_BLOCK + threadIdx.x;
-    if (q >= nq) return;
-    const int j = match_idx[q];
-    if (j >= 0 && j < nt) atomicMax(&win[j], q);
 }
 
 struct LlGate { float Ki[9], R[9]; };
@@ -420,19 +252,6 @@ __global__ __launch_bounds__(LL_BLOCK) void k_ll_struct(int nq, const hvo_line3d
 
 // ---------------------------------------------------------------- the call ----------------------------------------------------------------
 
-static int ll_grow(hvo_line_map *m, hipStream_t st, char **p, size_t *have, size_t want)
-{
-    if (*have >= want) return HVO_OK;
-    LM_HIP(hipStreamSynchronize(st));
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *have = 0;
-    size_t c = 1 << 20;
-    while (c < want) c *= 2;
-    LM_HIP(hipMalloc((void **)p, c));
-    *have = c;
-    return HVO_OK;
-}
-
 // K.inv() of the CV_32F camera matrix in closed form (double), entries rounded to float
 static void ll_kinv(const hvo_camera *cam, float Ki[9])
 {
@@ -452,6 +271,8 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
            const LlFrameDev *fr, const float *Tcw, hvo_local_lines_io *io, hvo_local_lines_result *res)
 {
     const int ns = m->n_slots, nblocks = std::max(1, (ns + LL_BLOCK - 1) / LL_BLOCK), capq = std::max(1, std::min(ns, LSBP_MAP_MAXQ));
+    std::vector<SmFrame> S(nframes);
+    int rc;
     for (int f = 0; f < nframes; f++) {
         memset(&res[f], 0, sizeof(res[f]));
         if (fr[f].nt > 2048) { m->last_error = match_lsbp_map_limit_text(0, fr[f].nt); res[f].status = HVO_ERR_UNSUPPORTED; return HVO_ERR_UNSUPPORTED; }
@@ -459,78 +280,49 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
         if ((fr[f].nt > 0 && (!io[f].held || !io[f].n_par || !io[f].n_perp)) || !io[f].in_view_slot || io[f].n_seen_extra < 0 || (io[f].n_seen_extra > 0 && !io[f].seen_extra)) {
             m->last_error = "local lines: held, n_par, n_perp or in_view_slot missing"; return HVO_ERR_INVALID_ARG;
         }
-        for (int i = 0; i < fr[f].nt; i++) if (io[f].held[i] >= ns) { m->last_error = "local lines: held names a slot beyond the map"; return HVO_ERR_INVALID_ARG; }
-        for (int i = 0; i < io[f].n_seen_extra; i++) if (io[f].seen_extra[i] < 0 || io[f].seen_extra[i] >= ns) { m->last_error = "local lines: seen_extra names a slot beyond the map"; return HVO_ERR_INVALID_ARG; }
+        S[f] = SmFrame{ fr[f].nt, io[f].n_seen_extra, io[f].held, io[f].seen_extra };
+        if ((rc = sm_check_seen(m, "local lines", "held names a slot beyond the map", INT32_MIN, S[f]))) return rc;
     }
     // ---- scratch A: everything whose size is known before the in-view counts ----
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += ll_al(bytes); return at; };
+    SmCarve C;
     const size_t F = (size_t)nframes, NS = (size_t)std::max(ns, 1);
-    const size_t o_pose = take(F * sizeof(LlPose)), o_seen = take(F * NS), o_pass = take(F * NS), o_sx = take(F * NS * 16), o_svc = take(F * NS * 4), o_slv = take(F * NS * 4);
-    const size_t o_bc = take(F * nblocks * 4), o_cnt = take(F * 2 * 4);
-    const size_t o_qs = take(F * capq * 4), o_qx = take(F * capq * 16), o_qv = take(F * capq * 4), o_ql = take(F * capq * 4), o_qw = take(F * capq * 24),
-                 o_qd = take(F * capq * 32), o_qb = take(F * capq);
-    const size_t o_mi = take(F * capq * 4), o_md = take(F * capq * 4);
-    std::vector<size_t> o_held(F), o_occ(F), o_ex(F), o_win(F), o_np(F), o_nq(F), o_k(F);
+    const size_t o_pose = C.take(F * sizeof(SmPose)), o_seen = C.take(F * NS), o_pass = C.take(F * NS), o_sx = C.take(F * NS * 16), o_svc = C.take(F * NS * 4), o_slv = C.take(F * NS * 4);
+    const size_t o_bc = C.take(F * nblocks * 4), o_cnt = C.take(F * 2 * 4);
+    const size_t o_qs = C.take(F * capq * 4), o_qx = C.take(F * capq * 16), o_qv = C.take(F * capq * 4), o_ql = C.take(F * capq * 4), o_qw = C.take(F * capq * 24),
+                 o_qd = C.take(F * capq * 32), o_qb = C.take(F * capq);
+    const size_t o_mi = C.take(F * capq * 4), o_md = C.take(F * capq * 4);
+    std::vector<size_t> o_np(F), o_nq(F), o_k(F);
     for (int f = 0; f < nframes; f++) {
         const size_t nt = (size_t)std::max(fr[f].nt, 1);
-        o_held[f] = take(nt * 4); o_occ[f] = take(nt); o_ex[f] = take((size_t)std::max(io[f].n_seen_extra, 1) * 4); o_win[f] = take(nt * 4);
-        o_np[f] = take(nt * 4); o_nq[f] = take(nt * 4); o_k[f] = take(2 * 4);        // n_matches, n_gated
+        sm_carve_frame(C, S[f]);
+        o_np[f] = C.take(nt * 4); o_nq[f] = C.take(nt * 4); o_k[f] = C.take(2 * 4);        // n_matches, n_gated
     }
-    int rc;
-    if ((rc = ll_grow(m, st, &m->d_a, &m->a_bytes, o))) return rc;
+    if ((rc = sm_grow(m, st, &m->d_a, &m->a_bytes, C.o))) return rc;
     char *A = m->d_a;
-    std::vector<LlPose> pose(F);
+    if ((rc = sm_stage_in(m, st, A, o_pose, o_seen, o_cnt, S, Tcw))) return rc;
     for (int f = 0; f < nframes; f++) {
-        const float *T = Tcw + 12 * (size_t)f; LlPose &p = pose[f];
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) p.R[3 * r + c] = T[4 * r + c]; p.t[r] = T[4 * r + 3]; }
-        for (int r = 0; r < 3; r++) {                              // mOw = -Rcw^T tcw
-            double s0 = 0;
-            for (int k = 0; k < 3; k++) s0 += (double)p.R[3 * k + r] * (double)p.t[k];
-            p.Ow[r] = (float)(s0 * -1.0);
-        }
-        p.pad = 0.f;
+        SM_HIP(hipMemsetAsync(A + o_np[f], 0, (size_t)std::max(fr[f].nt, 1) * 4, st));
+        SM_HIP(hipMemsetAsync(A + o_nq[f], 0, (size_t)std::max(fr[f].nt, 1) * 4, st));
+        SM_HIP(hipMemsetAsync(A + o_k[f], 0, 8, st));
     }
-    LM_HIP(hipMemcpyAsync(A + o_pose, pose.data(), F * sizeof(LlPose), hipMemcpyHostToDevice, st));
-    LM_HIP(hipMemsetAsync(A + o_seen, 0, F * NS, st));
-    LM_HIP(hipMemsetAsync(A + o_cnt, 0, F * 8, st));
-    for (int f = 0; f < nframes; f++) {
-        const int nt = fr[f].nt, ne = io[f].n_seen_extra;
-        if (nt) LM_HIP(hipMemcpyAsync(A + o_held[f], io[f].held, (size_t)nt * 4, hipMemcpyHostToDevice, st));
-        if (ne) LM_HIP(hipMemcpyAsync(A + o_ex[f], io[f].seen_extra, (size_t)ne * 4, hipMemcpyHostToDevice, st));
-        LM_HIP(hipMemsetAsync(A + o_win[f], 0xFF, (size_t)std::max(nt, 1) * 4, st));
-        LM_HIP(hipMemsetAsync(A + o_np[f], 0, (size_t)std::max(nt, 1) * 4, st));
-        LM_HIP(hipMemsetAsync(A + o_nq[f], 0, (size_t)std::max(nt, 1) * 4, st));
-        LM_HIP(hipMemsetAsync(A + o_k[f], 0, 8, st));
-    }
+    if ((rc = sm_mark(m, st, A, o_seen, S, 0))) return rc;
     LlDev a; memset(&a, 0, sizeof(a));
     a.ns = ns; a.cap = m->cap; a.nframes = nframes; a.nblocks = nblocks; a.capq = capq;
-    a.pos = m->d_pos; a.wvec = m->d_wvec; a.nrm = m->d_nrm; a.maxd = m->d_maxd; a.mind = m->d_mind; a.desc = m->d_desc; a.flags = m->d_flags;
-    a.pose = (const LlPose *)(A + o_pose);
+    a.pos = m->dev<double>(m->POS); a.wvec = m->dev<double>(m->WVEC); a.nrm = m->dev<double>(m->NRM); a.maxd = m->dev<float>(m->MAXD); a.mind = m->dev<float>(m->MIND);
+    a.desc = m->dev<uint8_t>(m->DESC); a.flags = m->d_flags();
+    a.pose = (const SmPose *)(A + o_pose);
     a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy; a.minX = bounds[0]; a.maxX = bounds[1]; a.minY = bounds[2]; a.maxY = bounds[3];
     a.logsf = P->log_scale_factor;
     a.seen = (const uint8_t *)(A + o_seen); a.pass = (uint8_t *)(A + o_pass); a.s_xyxy = (float4 *)(A + o_sx); a.s_vc = (float *)(A + o_svc); a.s_lvl = (int *)(A + o_slv);
     a.blockcnt = (int *)(A + o_bc); a.nview = (int *)(A + o_cnt); a.ntested = a.nview + nframes;
     a.q_slot = (int *)(A + o_qs); a.q_xyxy = (float *)(A + o_qx); a.q_vc = (float *)(A + o_qv); a.q_lvl = (int *)(A + o_ql); a.q_wvec = (double *)(A + o_qw);
     a.q_desc = (uint8_t *)(A + o_qd); a.q_blocks = (uint8_t *)(A + o_qb);
-    LM_HIP(hipEventRecord(m->ev[0], st));
-    for (int f = 0; f < nframes; f++) {
-        const int n = fr[f].nt + io[f].n_seen_extra;
-        if (n > 0 && ns > 0)
-            hipLaunchKernelGGL(k_ll_mark, dim3((n + LL_BLOCK - 1) / LL_BLOCK), dim3(LL_BLOCK), 0, st, fr[f].nt, ns, m->d_flags, (int32_t *)(A + o_held[f]),
-                               (uint8_t *)(A + o_occ[f]), (const int32_t *)(A + o_ex[f]), io[f].n_seen_extra, (uint8_t *)(A + o_seen) + (size_t)f * ns);
-        else if (fr[f].nt > 0)
-            LM_HIP(hipMemsetAsync(A + o_occ[f], 0, (size_t)fr[f].nt, st));
-    }
     if (ns > 0) {
         hipLaunchKernelGGL(k_ll_frustum, dim3(nblocks), dim3(LL_BLOCK), 0, st, a);
         hipLaunchKernelGGL(k_ll_compact, dim3(nblocks, nframes), dim3(LL_BLOCK), 0, st, a);
     }
-    if (hipGetLastError() != hipSuccess) { m->last_error = "local lines: frustum launch"; return HVO_ERR_HIP; }
-    LM_HIP(hipEventRecord(m->ev[1], st));
-    std::vector<int> cnt(2 * F, 0);
-    LM_HIP(hipMemcpyAsync(cnt.data(), A + o_cnt, F * 8, hipMemcpyDeviceToHost, st));
-    LM_HIP(hipStreamSynchronize(st));
+    std::vector<int> cnt;
+    if ((rc = sm_counts_down(m, st, "local lines: frustum launch", A + o_cnt, nframes, cnt))) return rc;
     size_t sb = 0, rb = 0;
     for (int f = 0; f < nframes; f++) {
         res[f].n_slots_tested = cnt[nframes + f]; res[f].n_in_view = cnt[f];
@@ -538,30 +330,30 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
             res[f].status = HVO_ERR_UNSUPPORTED; m->last_error = match_lsbp_map_limit_text(cnt[f], fr[f].nt); return HVO_ERR_UNSUPPORTED;
         }
         if (cnt[f] > 0 && fr[f].nt > 0) sb = std::max(sb, match_lsbp_map_scratch_bytes(cnt[f], fr[f].nt));
-        if (io[f].rel_map) rb = std::max(rb, ll_al((size_t)cnt[f] * (size_t)fr[f].nt));
+        if (io[f].rel_map) rb = std::max(rb, sm_al((size_t)cnt[f] * (size_t)fr[f].nt));
     }
     // ---- scratch B: the search's key rows and the relation matrix ----
-    if ((rc = ll_grow(m, st, &m->d_b, &m->b_bytes, ll_al(sb) + F * rb + 256))) return rc;
+    if ((rc = sm_grow(m, st, &m->d_b, &m->b_bytes, sm_al(sb) + F * rb + 256))) return rc;
     LlGate G;
     ll_kinv(cam, G.Ki);
     for (int f = 0; f < nframes; f++) {
         const int nq = cnt[f], nt = fr[f].nt;
         int32_t *d_mi = (int32_t *)(A + o_mi) + (size_t)f * capq, *d_md = (int32_t *)(A + o_md) + (size_t)f * capq;
         int *d_k = (int *)(A + o_k[f]);
-        if (nq > 0) hipLaunchKernelGGL(k_ll_fill, dim3((nq + LL_BLOCK - 1) / LL_BLOCK), dim3(LL_BLOCK), 0, st, nq, d_mi, d_md);
+        if (nq > 0) sm_fill_enqueue(st, nq, d_mi, d_md);
         if (nq > 0 && nt > 0) {                                    // nToMatch > 0 (Tracking.cc:3345)
             LsbpMapDev s; memset(&s, 0, sizeof(s));
             s.nq = nq; s.nt = nt;
             s.q_xyxy = a.q_xyxy + 4 * (size_t)f * capq; s.q_view_cos = a.q_vc + (size_t)f * capq; s.q_wvec = a.q_wvec + 3 * (size_t)f * capq;
             s.q_desc = a.q_desc + 32 * (size_t)f * capq; s.q_blocks = a.q_blocks + (size_t)f * capq;
-            s.t_kl = fr[f].kl; s.t_fn = fr[f].fn; s.t_l3d = fr[f].l3d; s.t_desc = fr[f].desc; s.t_occ = (const uint8_t *)(A + o_occ[f]);
+            s.t_kl = fr[f].kl; s.t_fn = fr[f].fn; s.t_l3d = fr[f].l3d; s.t_desc = fr[f].desc; s.t_occ = (const uint8_t *)(A + S[f].o_occ);
             s.cell_start = fr[f].cell_start; s.cell_items = fr[f].cell_items; s.n_items = fr[f].n_items;
             s.mnMinX = bounds[0]; s.mnMaxX = bounds[1]; s.mnMinY = bounds[2]; s.mnMaxY = bounds[3]; s.th = P->th; s.nn_ratio = P->nn_ratio;
             s.cos_normal = cos(15.0 / 180.0 * M_PI);
             s.match_idx = d_mi; s.match_dist = d_md; s.n_matches = d_k;
             if ((rc = match_lsbp_map_enqueue(st, s, m->d_b))) { m->last_error = rc == HVO_ERR_UNSUPPORTED ? match_lsbp_map_limit_text(nq, nt) : "local lines: search launch"; return rc; }
         }
-        if (f == nframes - 1) LM_HIP(hipEventRecord(m->ev[2], st));
+        if (f == nframes - 1) SM_HIP(hipEventRecord(m->ev[2], st));
     }
     for (int f = 0; f < nframes; f++) {
         const int nq = cnt[f], nt = fr[f].nt;
@@ -569,40 +361,40 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
         const float *T = Tcw + 12 * (size_t)f;
         for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) G.R[3 * r + c] = T[4 * r + c];
         int32_t *d_mi = (int32_t *)(A + o_mi) + (size_t)f * capq;
-        int *d_k = (int *)(A + o_k[f]), *d_win = (int *)(A + o_win[f]);
-        int8_t *d_rel = io[f].rel_map ? (int8_t *)(m->d_b + ll_al(sb) + (size_t)f * rb) : nullptr;
-        if (nq > 0) hipLaunchKernelGGL(k_ll_assign, dim3((nq + LL_BLOCK - 1) / LL_BLOCK), dim3(LL_BLOCK), 0, st, nq, nt, d_mi, d_win);
-        hipLaunchKernelGGL(k_ll_gate, dim3((nt + LL_BLOCK - 1) / LL_BLOCK), dim3(LL_BLOCK), 0, st, nt, (size_t)m->cap, m->d_wvec, fr[f].kl, d_win,
-                           a.q_slot + (size_t)f * capq, d_k, G, (int32_t *)(A + o_held[f]), d_k + 1);
+        int *d_k = (int *)(A + o_k[f]), *d_win = (int *)(A + S[f].o_win);
+        int8_t *d_rel = io[f].rel_map ? (int8_t *)(m->d_b + sm_al(sb) + (size_t)f * rb) : nullptr;
+        if (nq > 0) sm_assign_enqueue(st, nq, nt, d_mi, d_win);
+        hipLaunchKernelGGL(k_ll_gate, dim3((nt + LL_BLOCK - 1) / LL_BLOCK), dim3(LL_BLOCK), 0, st, nt, (size_t)m->cap, a.wvec, fr[f].kl, d_win,
+                           a.q_slot + (size_t)f * capq, d_k, G, (int32_t *)(A + S[f].o_held), d_k + 1);
         if (nq > 0)
             hipLaunchKernelGGL(k_ll_struct, dim3((nq + LL_BLOCK - 1) / LL_BLOCK, nt), dim3(LL_BLOCK), 0, st, nq, fr[f].l3d, a.q_wvec + 3 * (size_t)f * capq, G, d_rel,
                                (int32_t *)(A + o_np[f]), (int32_t *)(A + o_nq[f]));
     }
     if (hipGetLastError() != hipSuccess) { m->last_error = "local lines: post-gate launch"; return HVO_ERR_HIP; }
-    LM_HIP(hipEventRecord(m->ev[3], st));
+    SM_HIP(hipEventRecord(m->ev[3], st));
     std::vector<int> kk(2 * F, 0);
     for (int f = 0; f < nframes; f++) {
         const size_t nq = (size_t)cnt[f], nt = (size_t)fr[f].nt, q0 = (size_t)f * capq;
         hvo_local_lines_io &I = io[f];
-        LM_HIP(hipMemcpyAsync(&kk[2 * f], A + o_k[f], 8, hipMemcpyDeviceToHost, st));
+        SM_HIP(hipMemcpyAsync(&kk[2 * f], A + o_k[f], 8, hipMemcpyDeviceToHost, st));
         if (nt) {
-            LM_HIP(hipMemcpyAsync(I.held, A + o_held[f], nt * 4, hipMemcpyDeviceToHost, st));
-            LM_HIP(hipMemcpyAsync(I.n_par, A + o_np[f], nt * 4, hipMemcpyDeviceToHost, st));
-            LM_HIP(hipMemcpyAsync(I.n_perp, A + o_nq[f], nt * 4, hipMemcpyDeviceToHost, st));
+            SM_HIP(hipMemcpyAsync(I.held, A + S[f].o_held, nt * 4, hipMemcpyDeviceToHost, st));
+            SM_HIP(hipMemcpyAsync(I.n_par, A + o_np[f], nt * 4, hipMemcpyDeviceToHost, st));
+            SM_HIP(hipMemcpyAsync(I.n_perp, A + o_nq[f], nt * 4, hipMemcpyDeviceToHost, st));
         }
         if (nq) {
-            LM_HIP(hipMemcpyAsync(I.in_view_slot, a.q_slot + q0, nq * 4, hipMemcpyDeviceToHost, st));
-            if (I.proj) LM_HIP(hipMemcpyAsync(I.proj, a.q_xyxy + 4 * q0, nq * 16, hipMemcpyDeviceToHost, st));
-            if (I.view_cos) LM_HIP(hipMemcpyAsync(I.view_cos, a.q_vc + q0, nq * 4, hipMemcpyDeviceToHost, st));
-            if (I.level) LM_HIP(hipMemcpyAsync(I.level, a.q_lvl + q0, nq * 4, hipMemcpyDeviceToHost, st));
-            if (I.match_idx) LM_HIP(hipMemcpyAsync(I.match_idx, (int32_t *)(A + o_mi) + q0, nq * 4, hipMemcpyDeviceToHost, st));
-            if (I.match_dist) LM_HIP(hipMemcpyAsync(I.match_dist, (int32_t *)(A + o_md) + q0, nq * 4, hipMemcpyDeviceToHost, st));
-            if (I.rel_map && nt) LM_HIP(hipMemcpyAsync(I.rel_map, m->d_b + ll_al(sb) + (size_t)f * rb, nq * nt, hipMemcpyDeviceToHost, st));
+            SM_HIP(hipMemcpyAsync(I.in_view_slot, a.q_slot + q0, nq * 4, hipMemcpyDeviceToHost, st));
+            if (I.proj) SM_HIP(hipMemcpyAsync(I.proj, a.q_xyxy + 4 * q0, nq * 16, hipMemcpyDeviceToHost, st));
+            if (I.view_cos) SM_HIP(hipMemcpyAsync(I.view_cos, a.q_vc + q0, nq * 4, hipMemcpyDeviceToHost, st));
+            if (I.level) SM_HIP(hipMemcpyAsync(I.level, a.q_lvl + q0, nq * 4, hipMemcpyDeviceToHost, st));
+            if (I.match_idx) SM_HIP(hipMemcpyAsync(I.match_idx, (int32_t *)(A + o_mi) + q0, nq * 4, hipMemcpyDeviceToHost, st));
+            if (I.match_dist) SM_HIP(hipMemcpyAsync(I.match_dist, (int32_t *)(A + o_md) + q0, nq * 4, hipMemcpyDeviceToHost, st));
+            if (I.rel_map && nt) SM_HIP(hipMemcpyAsync(I.rel_map, m->d_b + sm_al(sb) + (size_t)f * rb, nq * nt, hipMemcpyDeviceToHost, st));
         }
     }
-    LM_HIP(hipStreamSynchronize(st));
-    float ms[3] = { 0.f, 0.f, 0.f };
-    for (int k = 0; k < 3; k++) if (hipEventElapsedTime(&ms[k], m->ev[k], m->ev[k + 1]) != hipSuccess) ms[k] = 0.f;
+    SM_HIP(hipStreamSynchronize(st));
+    float ms[3];
+    sm_kernel_ms(m, ms);
     for (int f = 0; f < nframes; f++) {
         res[f].n_matches = kk[2 * f]; res[f].n_gated = kk[2 * f + 1]; res[f].status = HVO_OK;
         for (int k = 0; k < 3; k++) res[f].kernel_ms[k] = ms[k];

@@ -583,18 +583,28 @@ private:
     float th_[4];
 };
 
+namespace detail {
+// What LineMap and PointMap share: the ownership of the handle, get() and lastError().
+template <class M, void (*Destroy)(M *), const char *(*LastError)(const M *)>
+class SlotMapHandle {
+public:
+    ~SlotMapHandle() { Destroy(m_); }
+    SlotMapHandle(const SlotMapHandle &) = delete;
+    SlotMapHandle &operator=(const SlotMapHandle &) = delete;
+    const char *lastError() const { return LastError(m_); }
+    M *get() const { return m_; }
+protected:
+    SlotMapHandle(M *m, const char *what) : m_(m) { if (!m_) throw Error(HVO_ERR_HIP, what); }
+    M *m_;
+};
+}  // namespace detail
+
 // The local map's lines resident on one device (hvo_line_map): per slot GetWorldPos(), GetWorldVector(), GetNormal(), mfMaxDistance,
 // mfMinDistance, GetDescriptor(), isBad() and Observations() > 0.  The slot index is the position in mvpLocalMapLines: the tracker calls
 // setMany() after UpdateLocalLines has rebuilt that vector.  Not thread-safe.
-class LineMap {
+class LineMap : public detail::SlotMapHandle<hvo_line_map, hvo_line_map_destroy, hvo_line_map_last_error> {
 public:
-    explicit LineMap(int device = 0, int slots = 0) : m_(hvo_line_map_create(device, slots))
-    {
-        if (!m_) throw Error(HVO_ERR_HIP, "hvo_line_map_create");
-    }
-    ~LineMap() { hvo_line_map_destroy(m_); }
-    LineMap(const LineMap &) = delete;
-    LineMap &operator=(const LineMap &) = delete;
+    explicit LineMap(int device = 0, int slots = 0) : SlotMapHandle(hvo_line_map_create(device, slots), "hvo_line_map_create") {}
     void set(int slot, const double pos[6], const double wvec[3], const double normal[3], float maxDistance, float minDistance, const uint8_t desc[32], bool observed = true)
     {
         check(hvo_line_map_set(m_, slot, pos, wvec, normal, maxDistance, minDistance, desc, observed ? 1 : 0), "hvo_line_map_set");
@@ -607,10 +617,6 @@ public:
     void setBad(int slot, bool bad = true) { check(hvo_line_map_set_bad(m_, slot, bad ? 1 : 0), "hvo_line_map_set_bad"); }
     void setObserved(int slot, bool observed = true) { check(hvo_line_map_set_observed(m_, slot, observed ? 1 : 0), "hvo_line_map_set_observed"); }
     int size() const { int n = 0; check(hvo_line_map_counts(m_, &n, nullptr, nullptr), "hvo_line_map_counts"); return n; }
-    const char *lastError() const { return hvo_line_map_last_error(m_); }
-    hvo_line_map *get() const { return m_; }
-private:
-    hvo_line_map *m_;
 };
 
 // Tracking::SearchLocalLines (src/Tracking.cc:3279-3392) together with Manhattan::computeStructConstInMap (src/Manhattan.cpp:163-224) over a
@@ -648,15 +654,9 @@ private:
 // The local map's points resident on one device (hvo_point_map): per slot GetWorldPos(), GetNormal(), mfMaxDistance, mfMinDistance,
 // GetDescriptor(), isBad() and Observations() > 0.  The slot index is the position in mvpLocalMapPoints: the tracker calls setMany() after
 // UpdateLocalPoints has rebuilt that vector.  Not thread-safe.
-class PointMap {
+class PointMap : public detail::SlotMapHandle<hvo_point_map, hvo_point_map_destroy, hvo_point_map_last_error> {
 public:
-    explicit PointMap(int device = 0, int slots = 0) : m_(hvo_point_map_create(device, slots))
-    {
-        if (!m_) throw Error(HVO_ERR_HIP, "hvo_point_map_create");
-    }
-    ~PointMap() { hvo_point_map_destroy(m_); }
-    PointMap(const PointMap &) = delete;
-    PointMap &operator=(const PointMap &) = delete;
+    explicit PointMap(int device = 0, int slots = 0) : SlotMapHandle(hvo_point_map_create(device, slots), "hvo_point_map_create") {}
     void set(int slot, const float pos[3], const float normal[3], float maxDistance, float minDistance, const uint8_t desc[32], bool observed = true)
     {
         check(hvo_point_map_set(m_, slot, pos, normal, maxDistance, minDistance, desc, observed ? 1 : 0), "hvo_point_map_set");
@@ -669,10 +669,6 @@ public:
     void setBad(int slot, bool bad = true) { check(hvo_point_map_set_bad(m_, slot, bad ? 1 : 0), "hvo_point_map_set_bad"); }
     void setObserved(int slot, bool observed = true) { check(hvo_point_map_set_observed(m_, slot, observed ? 1 : 0), "hvo_point_map_set_observed"); }
     int size() const { int n = 0; check(hvo_point_map_counts(m_, &n, nullptr, nullptr), "hvo_point_map_counts"); return n; }
-    const char *lastError() const { return hvo_point_map_last_error(m_); }
-    hvo_point_map *get() const { return m_; }
-private:
-    hvo_point_map *m_;
 };
 
 // Tracking::SearchLocalPoints (src/Tracking.cc:3227-3277) over a resident PointMap: io.held carries mvpMapPoints as slots (or -1,

@@ -193,6 +193,41 @@ def test_query_limit_leaves_held_untouched(hvo, synth, gpu_ctx):
         lm.close()
 
 
+def test_regrowth_carries_live_slots_through_the_regrid(hvo, synth, gpu_ctx):
+    """60 slots in a map of capacity 64, then slot 70: the storage regrows to 128 with live slots in it, whose components move to the new
+    stride of the mirror and go up again whole; 60 .. 69 are skipped and stay bad.  Then 130 slots: 256, every slot replaced"""
+    T = ref.scene_pose(); sub = subset(gpu_ctx, frame(hvo, synth), 8)
+    assert len(sub[0]) == 8
+    held = np.full(8, -1, np.int32)
+    M, _ = ref.make_map(60, "alt", T, seed=41)
+    M["bad"][::7] = 1
+    assert 0 < M["observed"].sum() < 60 and not M["bad"][2]
+    lm = hvo.LineMap(slots=0)                                             # capacity 64
+    try:
+        lm.set_many(0, M["pos"], M["wvec"], M["normal"], M["max_dist"], M["min_dist"], M["desc"], M["observed"], M["bad"])
+        lm.set(70, M["pos"][2], M["wvec"][2], M["normal"][2], M["max_dist"][2], M["min_dist"][2], M["desc"][2])
+        assert lm.counts() == (71, int((M["bad"] == 0).sum()) + 1, int(M["observed"].sum()) + 1)
+        M71 = {k: np.concatenate([v, np.zeros((10,) + v.shape[1:], v.dtype), v[2:3]]) for k, v in M.items()}
+        M71["bad"][60:70] = 1; M71["observed"][70] = 1
+        for j in (0, 59, 70):
+            s = lm.slot(j)
+            assert all(s[k].tobytes() == M71[k][j].tobytes() for k in ("pos", "wvec", "normal", "desc")), j
+            assert np.float32(s["max_dist"]).tobytes() == M71["max_dist"][j].tobytes() and np.float32(s["min_dist"]).tobytes() == M71["min_dist"][j].tobytes(), j
+            assert (s["bad"], s["observed"]) == (bool(M71["bad"][j]), bool(M71["observed"][j])), j
+        assert lm.slot(60)["bad"] and lm.slot(69)["bad"]
+        r, o = run_both(hvo, gpu_ctx, lm, M71, sub, T, held)
+        same(r, o, what="regrown to 128")
+        assert 2 in r.in_view_slot and 70 in r.in_view_slot and r.in_view_slot.max() == 70
+        B, _ = ref.make_map(130, "alt", T, seed=42)
+        lm.set_many(0, B["pos"], B["wvec"], B["normal"], B["max_dist"], B["min_dist"], B["desc"], B["observed"], B["bad"])
+        assert lm.counts() == (130, 130, int(B["observed"].sum()))
+        r, o = run_both(hvo, gpu_ctx, lm, B, sub, T, held)
+        same(r, o, what="regrown to 256")
+        assert r.n_in_view == 65
+    finally:
+        lm.close()
+
+
 def test_rel_map_200_by_1000(hvo, synth, gpu_ctx):
     fr = frame(hvo, synth); T = ref.scene_pose()
     R = np.asarray(T, np.float64)[:, :3]

@@ -292,6 +292,40 @@ def test_map_life_cycle(hvo, synth, gpu_ctx):
         pm.close()
 
 
+def test_regrowth_carries_live_slots_through_the_regrid(hvo, synth, gpu_ctx):
+    """60 slots in a map of capacity 64, then slot 70: the storage regrows to 128 with live slots in it, whose components move to the new
+    stride of the mirror and go up again whole; 60 .. 69 are skipped and stay bad.  Then 130 slots: 256, every slot replaced"""
+    T = ref.scene_pose(); sub = subset(frame(hvo, synth), 8)
+    assert len(sub[0]) == 8
+    M, _ = ref.make_map(60, "alt", T, seed=41)
+    M["bad"][::7] = 1
+    assert 0 < M["observed"].sum() < 60 and not M["bad"][2]
+    pm = hvo.PointMap(slots=0)                                            # capacity 64
+    try:
+        pm.set_many(0, M["pos"], M["normal"], M["max_dist"], M["min_dist"], M["desc"], M["observed"], M["bad"])
+        pm.set(70, M["pos"][2], M["normal"][2], M["max_dist"][2], M["min_dist"][2], M["desc"][2])
+        assert pm.counts() == (71, int((M["bad"] == 0).sum()) + 1, int(M["observed"].sum()) + 1)
+        M71 = {k: np.concatenate([v, np.zeros((10,) + v.shape[1:], v.dtype), v[2:3]]) for k, v in M.items()}
+        M71["bad"][60:70] = 1; M71["observed"][70] = 1
+        for j in (0, 59, 70):
+            s = pm.slot(j)
+            assert s["pos"].tobytes() == M71["pos"][j].tobytes() and s["normal"].tobytes() == M71["normal"][j].tobytes(), j
+            assert np.float32(s["max_dist"]).tobytes() == M71["max_dist"][j].tobytes() and np.float32(s["min_dist"]).tobytes() == M71["min_dist"][j].tobytes(), j
+            assert s["desc"].tobytes() == M71["desc"][j].tobytes() and (s["bad"], s["observed"]) == (bool(M71["bad"][j]), bool(M71["observed"][j])), j
+        assert pm.slot(60)["bad"] and pm.slot(69)["bad"]
+        r, o = run_both(gpu_ctx, pm, M71, sub, T)
+        same(r, o, what="regrown to 128")
+        assert 2 in r.in_view_slot and 70 in r.in_view_slot and r.in_view_slot.max() == 70
+        B, _ = ref.make_map(130, "alt", T, seed=42)
+        pm.set_many(0, B["pos"], B["normal"], B["max_dist"], B["min_dist"], B["desc"], B["observed"], B["bad"])
+        assert pm.counts() == (130, 130, int(B["observed"].sum()))
+        r, o = run_both(gpu_ctx, pm, B, sub, T)
+        same(r, o, what="regrown to 256")
+        assert r.n_in_view == 65
+    finally:
+        pm.close()
+
+
 def test_resident_forms_and_determinism(hvo, synth):
     """a 640 x 480 frame through a Stream equals the host-array form on its collected outputs; frame k of a batch of 3 under 3 poses equals the
     stream form bit for bit; the same call twice gives the same bytes"""
