@@ -1143,6 +1143,22 @@ class Context:
         self._chk(lib().hvo_surface_normals(self.h, _p(depth), w, h, depth.strides[0], _p(out), cap, C.byref(n)), "surface_normals")
         return out[: n.value].copy()
 
+    def lsd_images(self, frame=0):
+        """diagnostics (not part of the reference interface): what the streaming line kernels of the last batch_run(STAGE_LSD) left for
+        `frame` -- the defined mask (sh x words u32, a bit per scaled pixel), the 32-byte records {angle, cos, sin, modgrad} of the defined
+        pixels in raster order (n x 4 f64) and the LBD gradient image (h x w x 2 i16).  Only for a batch of at most one chunk."""
+        L = lib()
+        L.hvo_debug_lsd_images.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]
+        L.hvo_debug_lsd_images.restype = C.c_int
+        w, h = self._w, self._h
+        sw, sh = int(round(w * 0.8)), int(round(h * 0.8))
+        mask = np.zeros((sh, (sw + 31) // 32), np.uint32); rec = np.zeros((sw * sh, 4), np.float64); dxy = np.zeros((h, w, 2), np.int16)
+        n = C.c_longlong(0); csw = C.c_int(0); csh = C.c_int(0)
+        self._chk(L.hvo_debug_lsd_images(self.h, frame, C.byref(csw), C.byref(csh), _p(mask), _p(rec), len(rec), C.byref(n), _p(dxy)), "lsd_images")
+        if (csw.value, csh.value) != (sw, sh):
+            raise HvoError(-1, "lsd_images: the plan's scaled size is %d x %d" % (csw.value, csh.value))
+        return {"mask": mask, "records": rec[:n.value].copy(), "dxy": dxy}
+
     def peac_stats(self, frame=0):
         """diagnostics (not part of the reference interface): bookkeeping words of the last plane run of `frame`"""
         L = lib()

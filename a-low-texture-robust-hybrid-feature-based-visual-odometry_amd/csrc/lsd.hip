@@ -245,15 +245,26 @@ __global__ __launch_bounds__(256) void k_lsd_resize_grad(const double *__restric
 // k_lsd_pre: the whole preamble in one kernel -- the u8 image in, the 32-byte gradient records and the defined mask out.  The CV_64F
 // blurred image (2.46 MB per 640x480 frame written by k_lsd_blur and read back by k_lsd_resize_grad: 5.6 x the algorithmic bytes of
 // that pair) is never written.  A workgroup owns a band of PRE_TW scaled columns over PRE_SEG scaled rows and STREAMS down the source
-// rows it needs: a thread owns a source column, forms the row-pass value of the next source row (seven cached byte loads, RowFilter's
-// order), keeps the last seven in registers, and emits one blurred value per step (SymmColumnFilter's order) into a four-row LDS ring;
-// as soon as the two source rows a scaled row interpolates from are in the ring the scaled row is formed (scaled_at's expression) and,
-// with the previous scaled row, the gradients of that row (ll_angle as in k_lsd_resize_grad: defined-mask words by ballot, the ~15 % of
-// the pixels that have an angle queued for the double cos / sin on full workgroups).  No vertical halo but the seven-row start of a
-// segment (7 %), no horizontal one at all: every arithmetic step is the unfused pair's, in its order.
+// rows it needs, in CHUNKS of PRE_CH scaled rows (five source rows at the 0.8x scale; offsets and weights come from the resize tables,
+// so any geometry is walked correctly).  Three phases per chunk, one barrier after each:
+//   1. a thread owns a source column, forms the row-pass value of the next source row (seven cached byte loads, RowFilter's order),
+//      keeps the last seven in registers and emits one blurred value per row (SymmColumnFilter's order) into an LDS ring of PRE_RING rows;
+//   2. a thread owns a scaled column and forms the chunk's scaled rows (scaled_at's expression; the horizontal interpolation of a source
+//      row two consecutive scaled rows share is the same expression on the same values and is formed once);
+//   3. the gradients of the chunk's rows (ll_angle as in k_lsd_resize_grad): a ballot per row gives the defined-mask words, and the ~15 %
+//      of the pixels that have an angle are queued by their place in the chunk (a wave takes its queue places with one LDS atomic per row:
+//      the queue's order does not reach the result, every entry writes its own record).
+// Then the queue is emptied: sqrt, arctangent and the double cos / sin run on the compacted entries, which read their four scaled values
+// back from the chunk's rows (still in LDS) and form gx, gy and the squared magnitude again -- the same operations on the same values.
+// Every predicate that only kept a harmless store away is an index clamp (threads past the band's last source / scaled column repeat
+// that column's value).  No vertical halo but the six-row start of a segment (5 %), no horizontal one at all: every arithmetic step is
+// the unfused pair's, in its order.
 // ------------------------------------------------------------------------------------------------
 #define PRE_TW 192                                    // scaled columns of a band: six mask words
 #define PRE_SEG 96                                    // scaled rows a workgroup walks
+#define PRE_CH 4                                      // scaled rows of a chunk
+#define PRE_RING 8                                    // blurred source rows in the ring: what a chunk's scaled rows span (lsd_ensure_plan checks it)
+__attribute__((amdgpu_waves_per_eu(5)))
 __global__ __launch_bounds__(256) void k_lsd_pre(const uint8_t *__restrict__ gray, size_t gframe, int gpitch, int w, int h, int sw, int sh,
                                                  const int *__restrict__ xofs, const float *__restrict__ xa, const int *__restrict__ yofs, const float *__restrict__ yb,
                                                  double4 *__restrict__ px4, unsigned *__restrict__ defined, int nwords, double rhoT,
@@ -261,125 +272,156 @@ __global__ __launch_bounds__(256) void k_lsd_pre(const uint8_t *__restrict__ gra
 {
     // redo_flags: only the frames whose growing gave up (flag 4: k_lsd_grow_async's bounded wait) are formed again -- their availability mask was consumed
     if (redo_flags && !(redo_flags[blockIdx.z] & 4)) return;
-    __shared__ double bl[4][256];                     // ring of blurred source rows (row & 3), one value per thread's column
-    __shared__ double sc[2][PRE_TW + 1];              // the last two scaled rows
-    __shared__ double la[512], lm[512]; __shared__ int lpos[512];
-    __shared__ int wcnt[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ double bl[PRE_RING][256];              // ring of blurred source rows (row & 7), one value per thread's column
+    __shared__ double sc[PRE_CH + 1][PRE_TW + 1];     // [0]: the last scaled row of the chunk before, [1 ..]: this chunk's
+    __shared__ unsigned short qid[PRE_CH * PRE_TW];   // queued pixels: slot of the upper scaled row << 8 | column in the band
+    __shared__ int qn[2];                             // entries queued (by chunk parity: the other one is cleared meanwhile)
+    const int tid = threadIdx.x, lane = tid & 63;
     const int x0 = blockIdx.x * PRE_TW, y0 = blockIdx.y * PRE_SEG, f = blockIdx.z;
     const uint8_t *G = gray + (size_t)f * gframe;
     double4 *PX = px4 + (size_t)f * sh * sw;
     const int xe = min(x0 + PRE_TW, sw - 1), ye = min(y0 + PRE_SEG, sh - 1);          // last scaled column / row the band reads
     const int nsc = xe - x0 + 1;                                                       // scaled values per row (the gradient's right neighbour included)
-    const int cA = xofs[x0], cB = min(xofs[xe] + 1, w - 1), ncols = cB - cA + 1;      // source columns (host-checked: <= 256)
-    const int sya = yofs[y0] & 0xFFFF, syb = yofs[ye] >> 16;
-    const bool colt = tid < ncols;
+    const int cA = xofs[x0];                                                           // first source column (the band's are host-checked: <= 256)
+    const int sya = yofs[y0] & 0xFFFF;
     const int x = min(cA + tid, w - 1);
     // unsigned column offsets: a row's seven byte loads take the row pointer as a scalar base and the column as a 32-bit lane offset
     unsigned xm3 = (unsigned)refl(x - 3, w), xm2 = (unsigned)refl(x - 2, w), xm1 = (unsigned)refl(x - 1, w), x00 = (unsigned)x, xp1 = (unsigned)refl(x + 1, w), xp2 = (unsigned)refl(x + 2, w), xp3 = (unsigned)refl(x + 3, w);
-    // my scaled column's taps (threads < nsc) -- fixed over the rows
-    const int sxq = x0 + min(tid, nsc - 1);
+    // my scaled column's taps -- fixed over the rows (threads past the last scaled column repeat it)
+    const int sci = min(tid, nsc - 1), sxq = x0 + sci;
     const int tx0 = xofs[sxq] - cA, tx1 = min(xofs[sxq] + 1, w - 1) - cA;
-    const double a0 = (double)xa[2 * sxq], a1 = (double)xa[2 * sxq + 1];
+    const float a0f = xa[2 * sxq], a1f = xa[2 * sxq + 1];      // (kept as the table's floats: two registers less through the whole kernel)
+    // my gradient column: has a right neighbour inside the image (else never defined); which mask word my wave's half-ballot is
+    const int gi = min(tid, PRE_TW - 1);
+    const bool gcol = tid < PRE_TW && x0 + tid < sw - 1;
+    const bool wstore = (lane & 31) == 0 && tid < PRE_TW && x0 + tid < ((sw + 31) & ~31);
+    const bool whi = (lane & 32) != 0;
+    const int wpr = (sw + 31) / 32;
     double v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0, v6 = 0;
-    int ys = y0;                                        // next scaled row to form
-    int npend = 0;
+    // ---- row pass of a source row, into the window of seven ----
+    auto rowpass = [&](const uint8_t *S) {
+        // (the empty asm keeps the zero-extension of a lane offset in this block: the loads then take scalar base + 32-bit lane offset
+        // instead of seven 64-bit address additions per row)
+        asm("" : "+v"(xm3), "+v"(xm2), "+v"(xm1), "+v"(x00), "+v"(xp1), "+v"(xp2), "+v"(xp3));
+        const unsigned q0 = S[xm3], q1 = S[xm2], q2 = S[xm1], q3 = S[x00], q4 = S[xp1], q5 = S[xp2], q6 = S[xp3];
+        __builtin_amdgcn_sched_barrier(0);                 // all seven in flight before the first is converted
+        double s = k0 * (double)q0;
+        s += k1 * (double)q1;
+        s += k2 * (double)q2;
+        s += k3 * (double)q3;
+        s += k2 * (double)q4;
+        s += k1 * (double)q5;
+        s += k0 * (double)q6;
+        v0 = v1; v1 = v2; v2 = v3; v3 = v4; v4 = v5; v5 = v6; v6 = s;
+    };
+    // ---- column pass of the window's middle row rb, into the ring ----
+    auto colpass = [&](int rb) {
+        double s = k3 * v3;
+        s += k2 * (v4 + v2);
+        s += k1 * (v5 + v1);
+        s += k0 * (v6 + v0);
+        bl[rb & (PRE_RING - 1)][tid] = s;
+    };
     // What a pixel WITH an angle needs beyond the test -- the square root of its squared gradient magnitude, the arctangent, the double
-    // cos / sin -- is computed here, on the compacted queue (full workgroups of the ~15 % of the pixels that have one), not on every pixel:
-    // the queue holds (float gx, float gy) and the squared magnitude.
-    auto emit = [&](int i) {
-        const float2 gq = reinterpret_cast<const float2 *>(la)[i];
-        const double m = sqrt(lm[i]);
-        const double aa = (double)fatan2_deg(gq.x, -gq.y) * (LSD_PI / 180);
+    // cos / sin -- is computed here, on the compacted queue, not on every pixel.  ybase: the scaled row of slot 0.
+    auto emit = [&](int i, int ybase) {
+        const int id = qid[i], s = id >> 8, t = id & 255;
+        const double vprev = sc[s][t], vprev_r = sc[s][t + 1], vcur = sc[s + 1][t], vcur_r = sc[s + 1][t + 1];
+        const double DA = vcur_r - vprev, BC = vprev_r - vcur;
+        const double gx = DA + BC, gy = DA - BC;
+        const double xq = (gx * gx + gy * gy) / 4;
+        const double m = sqrt(xq);
+        const double aa = (double)fatan2_deg((float)gx, -(float)gy) * (LSD_PI / 180);
         // region_grow accumulates cos(float(angle)) / sin(float(angle)) evaluated in double
         const double af = (double)(float)aa;
         double sn, cs; sincos(af, &sn, &cs);
-        PX[lpos[i]] = make_double4(aa, cs, sn, m);
+        PX[(size_t)(ybase + s) * sw + (x0 + t)] = make_double4(aa, cs, sn, m);
     };
-    for (int j = sya - 3; j <= syb + 3; j++) {
-        // ---- row pass of source row j (reflected), the window of seven, the column pass of row j - 3 ----
-        {
-            const uint8_t *S = G + (size_t)refl(min(j, h + 2), h) * gpitch;
-            // (the empty asm keeps the zero-extension of a lane offset in this block: the loads then take scalar base + 32-bit lane offset
-            // instead of seven 64-bit address additions per row)
-            asm("" : "+v"(xm3), "+v"(xm2), "+v"(xm1), "+v"(x00), "+v"(xp1), "+v"(xp2), "+v"(xp3));
-            const unsigned q0 = S[xm3], q1 = S[xm2], q2 = S[xm1], q3 = S[x00], q4 = S[xp1], q5 = S[xp2], q6 = S[xp3];
-            __builtin_amdgcn_sched_barrier(0);                 // all seven in flight before the first is converted
-            double s = k0 * (double)q0;
-            s += k1 * (double)q1;
-            s += k2 * (double)q2;
-            s += k3 * (double)q3;
-            s += k2 * (double)q4;
-            s += k1 * (double)q5;
-            s += k0 * (double)q6;
-            v0 = v1; v1 = v2; v2 = v3; v3 = v4; v4 = v5; v5 = v6; v6 = s;
+    // the window fills: source rows sya - 3 .. sya + 2 (the only rows reflected at the top of the image)
+    for (int j = sya - 3; j < sya + 3; j++) rowpass(G + (size_t)refl(min(j, h + 2), h) * gpitch);
+    int rbn = sya;                                      // next blurred row to form (its last source row is rbn + 3)
+    const uint8_t *Sp = G + (size_t)(sya + 3) * gpitch; // that source row while it is inside the image: one scalar add per row
+    if (tid == 0) { qn[0] = 0; qn[1] = 0; }
+    double vlast = 0, tprev = 0;
+    int prow = -1, par = 0;
+    for (int ys = y0; ys <= ye; ys += PRE_CH) {         // scaled rows ys .. ys + nr - 1 (uniform control throughout)
+        const int nr = min(PRE_CH, ye - ys + 1);
+        // the chunk's entries of the row tables at once (the tables are padded by a chunk: lsd_ensure_plan)
+        int yo[PRE_CH]; float wb[2 * PRE_CH];
+#pragma unroll
+        for (int r = 0; r < PRE_CH; r++) { yo[r] = yofs[ys + r]; wb[2 * r] = yb[2 * (ys + r)]; wb[2 * r + 1] = yb[2 * (ys + r) + 1]; }
+        const int rt = (nr == 4 ? yo[3] : nr == 3 ? yo[2] : nr == 2 ? yo[1] : yo[0]) >> 16;      // the last blurred row the chunk interpolates from
+        // ---- 1. blurred rows up to rt ----
+        const int rfast = min(rt, h - 4);
+        // (five rows at a time, a chunk's worth in the steady state: the window's rotation is a renaming inside the unrolled body)
+        for (; rbn + 4 <= rfast; rbn += 5) {
+#pragma unroll
+            for (int u = 0; u < 5; u++) { rowpass(Sp); Sp += gpitch; colpass(rbn + u); }
         }
-        const int rb = j - 3;                           // the blurred row that is complete now
-        if (rb < sya) continue;                         // (uniform) the window is filling
-        {
-            double s = k3 * v3;
-            s += k2 * (v4 + v2);
-            s += k1 * (v5 + v1);
-            s += k0 * (v6 + v0);
-            if (colt) bl[rb & 3][tid] = s;
+        for (; rbn <= rfast; rbn++) { rowpass(Sp); Sp += gpitch; colpass(rbn); }
+        for (; rbn <= rt; rbn++) { rowpass(G + (size_t)refl(min(rbn + 3, h + 2), h) * gpitch); colpass(rbn); }      // reflected at the bottom of the image
+        __syncthreads();
+        // ---- 2. the chunk's scaled rows ----
+        if (tid == 0) qn[par ^ 1] = 0;
+        sc[0][sci] = vlast;
+        const double a0 = (double)a0f, a1 = (double)a1f;
+#pragma unroll
+        for (int r = 0; r < PRE_CH; r++) {
+            if (r < nr) {
+                const int sy0 = yo[r] & 0xFFFF, sy1 = yo[r] >> 16;
+                const double b0 = (double)wb[2 * r], b1 = (double)wb[2 * r + 1];
+                const double *S0 = bl[sy0 & (PRE_RING - 1)], *S1 = bl[sy1 & (PRE_RING - 1)];
+                double t0;
+                if (sy0 == prow) t0 = tprev; else t0 = S0[tx0] * a0 + S0[tx1] * a1;
+                const double t1 = S1[tx0] * a0 + S1[tx1] * a1;
+                tprev = t1; prow = sy1;
+                vlast = t0 * b0 + t1 * b1;
+                sc[r + 1][sci] = vlast;
+            }
         }
         __syncthreads();
-        // ---- every scaled row whose lower source row is rb (0, 1 or 2 of them) ----
-        while (ys <= ye && (yofs[ys] >> 16) <= rb) {     // uniform
-            const int yo = yofs[ys];
-            const int sy0 = yo & 0xFFFF, sy1 = yo >> 16;
-            if (tid < nsc) {
-                const double b0 = (double)yb[2 * ys], b1 = (double)yb[2 * ys + 1];
-                const double *S0 = bl[sy0 & 3], *S1 = bl[sy1 & 3];
-                const double t0 = S0[tx0] * a0 + S0[tx1] * a1;
-                const double t1 = S1[tx0] * a0 + S1[tx1] * a1;
-                sc[ys & 1][tid] = t0 * b0 + t1 * b1;
-            }
-            __syncthreads();
-            if (ys > y0) {
-                // ---- ll_angle of scaled row ys - 1 (its lower neighbours are row ys) ----
-                const int y = ys - 1, xg = x0 + tid;
-                // ll_angle's test `sqrt(x) <= rho` (x = (gx^2 + gy^2) / 4) is taken on x: rhoT is the largest double whose correctly rounded
-                // square root is <= rho (lsd_sqrt_threshold, host), so the two tests agree on every x
-                bool def = false;
-                double xq = 0; float fgx = 0, fgy = 0;
-                if (tid < PRE_TW && xg < sw - 1 && y < sh - 1) {
-                    const double vprev = sc[y & 1][tid], vprev_r = sc[y & 1][tid + 1], vcur = sc[ys & 1][tid], vcur_r = sc[ys & 1][tid + 1];
-                    const double DA = vcur_r - vprev, BC = vprev_r - vcur;
-                    const double gx = DA + BC, gy = DA - BC;
-                    xq = (gx * gx + gy * gy) / 4;
-                    def = !(xq <= rhoT);
-                    fgx = (float)gx; fgy = (float)gy;
-                }
+        // ---- 3. ll_angle of scaled rows ybase + s, s0 <= s < nr (the lower neighbours are slot s + 1; a segment's first chunk has no slot 0) ----
+        // ll_angle's test `sqrt(x) <= rho` (x = (gx^2 + gy^2) / 4) is taken on x: rhoT is the largest double whose correctly rounded
+        // square root is <= rho (lsd_sqrt_threshold, host), so the two tests agree on every x
+        const int s0 = ys == y0 ? 1 : 0, ybase = ys - 1;
+        double pl = sc[s0][gi], pr = sc[s0][gi + 1];
+        unsigned mw[PRE_CH];
+#pragma unroll
+        for (int s = 0; s < PRE_CH; s++) {
+            mw[s] = 0;
+            if (s >= s0 && s < nr) {
+                const double cl = sc[s + 1][gi], cr = sc[s + 1][gi + 1];
+                const double DA = cr - pl, BC = pr - cl;
+                const double gx = DA + BC, gy = DA - BC;
+                const double xq = (gx * gx + gy * gy) / 4;
+                const bool def = gcol && !(xq <= rhoT);
                 const unsigned long long bal = __ballot(def);
-                if (tid < PRE_TW && xg < ((sw + 31) & ~31)) {
-                    const int word = (y * ((sw + 31) / 32)) + (xg >> 5);
-                    if ((lane & 31) == 0) defined[(size_t)f * nwords + word] = (unsigned)(bal >> (lane & 32));
+                mw[s] = whi ? (unsigned)(bal >> 32) : (unsigned)bal;
+                if (bal) {                                 // (uniform per wave)
+                    int base = 0;
+                    if (lane == 0) base = atomicAdd(&qn[par], __popcll(bal));
+                    base = __builtin_amdgcn_readfirstlane(base);
+                    if (def) qid[base + __popcll(bal & ((1ull << lane) - 1))] = (unsigned short)((s << 8) | tid);
                 }
-                // the ~15 % of the pixels that have an angle are queued; the double cos / sin run on full workgroups (all four waves at once:
-                // a per-wave queue was tried -- the waves are tied by the barriers of the row loop and wait for whichever one is emitting)
-                if (lane == 0) wcnt[wv] = __popcll(bal);
-                __syncthreads();
-                int base = 0, total = 0;
-                for (int i = 0; i < 4; i++) { const int cn = wcnt[i]; if (i < wv) base += cn; total += cn; }
-                if (def) { const int p = npend + base + __popcll(bal & ((1ull << lane) - 1)); reinterpret_cast<float2 *>(la)[p] = make_float2(fgx, fgy); lm[p] = xq; lpos[p] = y * sw + xg; }
-                npend += total;
-                if (npend >= 256) {                       // a full workgroup of queued pixels (npend is the same in every thread)
-                    __syncthreads();
-                    emit(tid);
-                    const int rem = npend - 256;
-                    double ta = 0, tm = 0; int tp = 0;
-                    if (tid < rem) { ta = la[256 + tid]; tm = lm[256 + tid]; tp = lpos[256 + tid]; }
-                    __syncthreads();
-                    if (tid < rem) { la[tid] = ta; lm[tid] = tm; lpos[tid] = tp; }
-                    npend = rem;
-                }
+                pl = cl; pr = cr;
             }
-            __syncthreads();                              // the scaled row before this one (and the queue) may be written again
-            ys++;
         }
+        // 192 threads = 6 words of 32 bits; rows are padded to a multiple of 32 bits in the mask
+        if (wstore) {
+            // (a row's words from a scalar base plus the lane's word column, formed here: hoisted out of the loop as a 64-bit pointer it
+            // would be the one value too many for the register budget)
+            unsigned wcol = (unsigned)tid;
+            asm volatile("" : "+v"(wcol));
+            wcol = ((unsigned)x0 + wcol) >> 5;
+#pragma unroll
+            for (int s = 0; s < PRE_CH; s++)
+                if (s >= s0 && s < nr) (defined + (size_t)f * nwords + (size_t)(ybase + s) * wpr)[wcol] = mw[s];
+        }
+        __syncthreads();
+        const int n = qn[par];
+        for (int i = tid; i < n; i += 256) emit(i, ybase);
+        par ^= 1;
     }
-    if (tid < npend) emit(tid);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1137,95 +1179,146 @@ __global__ __launch_bounds__(256) void k_lbd_sobel(const uint8_t *__restrict__ b
     }
 }
 
-// Blur and Sobel in one pass: a thread owns 4 adjacent columns and LBD_BLUR_ROWS output rows.  Per source row it
+// Blur and Sobel in one pass: a thread owns 4 adjacent columns and LBD_FUSED_ROWS output rows.  Per source row it
 // fetches three aligned dwords (pixels x0-4 .. x0+7; strips on the left / right image border load from clamped
 // addresses and permute the reflected bytes into place, EdgeSel in hvo_internal.hpp) and forms the 5-tap row sums of the SIX columns x0-1 .. x0+4 with v_dot4 (the Sobel
-// needs the blurred neighbours of its own four); the last five row sums per column give one blurred row, the last
-// three blurred rows one Sobel row.  The u8 blurred image is never written.  Reflection of the blurred image at
-// the image border (refl(-1) = 1, refl(n) = n-2) is a substitution of the opposite neighbour.
+// needs the blurred neighbours of its own four).  The column pass is TRANSPOSED: a column keeps four partial sums of the blurred rows
+// still open and every new row sum is multiplied into them in place (five multiply-adds, nothing shifts down a register window); the
+// integer sums are those of k_lbd_blur5 in another order (row sums <= 65 280, column sums < 2^24: no overflow either way).  Two blurred
+// rows of Sobel terms are kept, in two register sets that swap roles (the row loop is unrolled by two).  The u8 blurred image is never
+// written.  Reflection of the blurred image at the image border (refl(-1) = 1, refl(n) = n-2) is a substitution of the opposite
+// neighbour: only the first and the last strip of a row have one, decided per thread before the loop; the top and the bottom image row
+// (blurred rows (1, 0, 1) and (h-2, h-1, h-2): gx = 2 hd + 2 hd', gy = 0) are written outside the loop.
+// AL: w % 4 == 0 -- every column of every strip takes OpenCV's SSE2 column path (round half to even), 16-byte stores; otherwise the
+// columns from w & ~3 on take its scalar tail (round half up), a per-thread constant per column.
+#define LBD_FUSED_ROWS 32
+template <bool AL>
+static __device__ __forceinline__ void lbd_blur_sobel_body(const uint8_t *__restrict__ G, int gpitch, short2 *__restrict__ out, int w, int h, int x0, int yb, int k0, int k1, int k2)
+{
+    const EdgeSel es = edge_sel(x0, w);
+    const unsigned o0 = (unsigned)max(x0 - 4, 0), o1 = (unsigned)x0, o2 = (unsigned)min(x0 + 4, gpitch - 4);     // window loads clamped into the row
+    const unsigned kA = (unsigned)k0 | ((unsigned)k1 << 8) | ((unsigned)k2 << 16) | ((unsigned)k1 << 24);
+    const unsigned kB0 = (unsigned)k0, kB1 = (unsigned)k0 << 8, kB2 = (unsigned)k0 << 16, kB3 = (unsigned)k0 << 24;   // the fifth tap, by its byte in the dword
+    const int v0 = max(yb - 1, 0), v1 = min(yb + LBD_FUSED_ROWS, h - 1);      // blurred rows formed here
+    const bool left = x0 == 0;
+    const int jr = w - 1 - x0;                             // the strip's column that is the image's last (0 .. 3), if any
+    // 1: the column rounds half up (scalar tail: columns from w & ~3 on -- the last strip's own four, and the right neighbour of the strip before)
+    const int hupT = !AL && x0 >= (w & ~3) ? 1 : 0, hup5 = !AL && x0 + 4 >= (w & ~3) ? 1 : 0;
+    int acc[4][6];                                         // open partial column sums: acc[0] lacks one row, acc[3] has one
+    // k0 and k1 each multiply a row sum twice.  Shared products cost an addition each (seven operations per column instead of five
+    // multiply-adds), so the second use goes through a copy of the tap the compiler cannot see through (no instruction is emitted)
+    int k0b = k0, k1b = k1;
+    asm("" : "+s"(k0b), "+s"(k1b));
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int c = 0; c < 6; c++) acc[q][c] = 0;
+    int sr = v0 - 2;                                       // next source row
+    // one source row: its six row sums into the open column sums; s[] = the column sums of blurred row sr - 2
+    auto step = [&](int (&s)[6]) {
+        const unsigned ro = __umul24((unsigned)refl(min(sr, h + 1), h), (unsigned)gpitch);
+        unsigned W0 = *reinterpret_cast<const uint32_t *>(G + (ro + o0)), W1 = *reinterpret_cast<const uint32_t *>(G + (ro + o1)),
+                 W2 = *reinterpret_cast<const uint32_t *>(G + (ro + o2));
+        edge_fix(es, W0, W1, W2);                          // REFLECT_101 at the left / right image border (identity elsewhere)
+        sr++;
+        // column c = pixel x0-1+c: taps at window bytes c+1 .. c+5 (window byte 0 = pixel x0-4)
+        int r[6];
+        r[0] = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(W1, W0, 1), kA, __builtin_amdgcn_udot4(W1, kB1, 0u, false), false);
+        r[1] = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(W1, W0, 2), kA, __builtin_amdgcn_udot4(W1, kB2, 0u, false), false);
+        r[2] = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(W1, W0, 3), kA, __builtin_amdgcn_udot4(W1, kB3, 0u, false), false);
+        r[3] = (int)__builtin_amdgcn_udot4(W1, kA, __builtin_amdgcn_udot4(W2, kB0, 0u, false), false);
+        r[4] = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(W2, W1, 1), kA, __builtin_amdgcn_udot4(W2, kB1, 0u, false), false);
+        r[5] = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(W2, W1, 2), kA, __builtin_amdgcn_udot4(W2, kB2, 0u, false), false);
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            // (24-bit multiply-adds: taps and row sums are far below 2^24.  k0b, k1b: see above)
+            s[c] = acc[0][c] + (int)__umul24((unsigned)k0b, (unsigned)r[c]);
+            acc[0][c] = acc[1][c] + (int)__umul24((unsigned)k1b, (unsigned)r[c]);
+            acc[1][c] = acc[2][c] + (int)__umul24((unsigned)k2, (unsigned)r[c]);
+            acc[2][c] = acc[3][c] + (int)__umul24((unsigned)k1, (unsigned)r[c]);
+            acc[3][c] = (int)__umul24((unsigned)k0, (unsigned)r[c]);
+            // (each sum as formed here: across two unrolled rows the compiler would regroup them into separate multiplies and three-input adds)
+            asm("" : "+v"(s[c]), "+v"(acc[0][c]), "+v"(acc[1][c]), "+v"(acc[2][c]));
+        }
+    };
+    // column sums -> rounded bytes -> the Sobel's horizontal terms of this blurred row, as 16-bit pairs: low half hd = e - a (|hd| <= 255),
+    // high half -hs = -(a + 2 c + e) (hs <= 1020).  A Sobel row is then two packed operations per column and comes out as the stored short2:
+    // (gx, gy) = (hd, hs) + (hdP, -hsP) + (2, 0) * (hdQ, .)
+    auto terms = [&](const int (&s)[6], unsigned (&n)[4]) {
+        int bl[6];
+#pragma unroll
+        for (int c = 0; c < 6; c++) bl[c] = min((s[c] + 32767 + (((s[c] >> 16) & 1) | (AL || c == 0 ? 0 : c == 5 ? hup5 : hupT))) >> 16, 255);
+        if (left) bl[0] = bl[2];
+        if (AL) { if (jr == 3) bl[5] = bl[3]; }
+        else {
+#pragma unroll
+            for (int j = 0; j < 4; j++) if (jr == j) bl[j + 2] = bl[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) n[j] = __builtin_amdgcn_perm((unsigned)(-(bl[j] + 2 * bl[j + 1] + bl[j + 2])), (unsigned)(bl[j + 2] - bl[j]), 0x05040100u);
+    };
+    typedef short lbd_s2 __attribute__((ext_vector_type(2)));
+    auto pk = [](unsigned u) { return __builtin_bit_cast(lbd_s2, u); };
+    auto store = [&](int y, const unsigned (&g)[4]) {
+        short2 *o = out + (size_t)y * w + x0;
+        if (AL) *reinterpret_cast<uint4 *>(o) = make_uint4(g[0], g[1], g[2], g[3]);
+        else {
+#pragma unroll
+            for (int j = 0; j < 4; j++) if (x0 + j < w) *reinterpret_cast<unsigned *>(o + j) = g[j];
+        }
+    };
+    const lbd_s2 two0 = { 2, 0 }, neg1 = { 1, -1 };
+    // an image row at the border: blurred rows (q, p, q): gx = 2 hd + 2 hd', gy = 0
+    auto store_edge = [&](int y, const unsigned (&np)[4], const unsigned (&nq)[4]) {
+        unsigned g[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) g[j] = __builtin_bit_cast(unsigned, (lbd_s2)((pk(np[j]) + pk(nq[j])) * two0));
+        store(y, g);
+    };
+    // blurred row v from the next source row; Sobel row v - 1 from (P: v - 2, Q: v - 1, the new one); the new terms take P's place
+    auto rowstep = [&](int v, unsigned (&nP)[4], const unsigned (&nQ)[4]) {
+        int s[6]; unsigned n[4], g[4];
+        step(s);
+        terms(s, n);
+#pragma unroll
+        for (int j = 0; j < 4; j++) { g[j] = __builtin_bit_cast(unsigned, (lbd_s2)(pk(nQ[j]) * two0 + (pk(nP[j]) + pk(n[j]) * neg1))); nP[j] = n[j]; }
+        store(v - 1, g);
+    };
+    int s[6]; unsigned nA[4], nB[4];
+    if (h == 1) {                                          // a single row: (0, 0, 0) has no gradient but the horizontal one, twice
+        for (int i = 0; i < 5; i++) step(s);
+        terms(s, nA);
+#pragma unroll
+        for (int j = 0; j < 4; j++) nB[j] = 0;
+        store_edge(0, nA, nB);
+        return;
+    }
+    for (int i = 0; i < 5; i++) step(s);                   // four rows fill the column sums, the fifth completes blurred row v0
+    terms(s, nA);
+    step(s);
+    terms(s, nB);                                          // blurred row v0 + 1 (<= v1: h >= 2)
+    if (yb == 0) store_edge(0, nA, nB);
+    int v = v0 + 2;
+    for (; v < v1; v += 2) {
+        rowstep(v, nA, nB);
+        __builtin_amdgcn_sched_barrier(0);                 // (one row's temporaries at a time: the two rows are independent up to the column sums)
+        rowstep(v + 1, nB, nA);
+    }
+    if (v == v1) rowstep(v, nA, nB);
+    if (yb + LBD_FUSED_ROWS >= h) store_edge(h - 1, nA, nB);            // (symmetric in the two sets: whichever holds row h - 1)
+}
+
+// AL (w % 4 == 0) is chosen at the launch (lsd_run)
+template <bool AL>
 __global__ __launch_bounds__(256) void k_lbd_blur_sobel(const uint8_t *__restrict__ gray, size_t gframe, int gpitch,
                                                         short2 *__restrict__ dxy, int w, int h, int k0, int k1, int k2)
 {
     const int nstrip = (w + 3) >> 2, item = blockIdx.x * 256 + threadIdx.x, f = blockIdx.z;
     const int rb = item / nstrip;
-    const int x0 = (item - rb * nstrip) * 4, yb = rb * LBD_BLUR_ROWS;
+    const int x0 = (item - rb * nstrip) * 4, yb = rb * LBD_FUSED_ROWS;
     if (yb >= h) return;
-    const uint8_t *G = gray + (size_t)f * gframe;          // rows are 4-byte aligned (pitch % 64 == 0)
-    const EdgeSel es = edge_sel(x0, w);
-    const int o0 = max(x0 - 4, 0), o2 = min(x0 + 4, gpitch - 4);     // window loads clamped into the row
-    const unsigned kA = (unsigned)k0 | ((unsigned)k1 << 8) | ((unsigned)k2 << 16) | ((unsigned)k1 << 24);
-    const int wv4 = w & ~3;
-    const int v0 = max(yb - 1, 0), v1 = min(yb + LBD_BLUR_ROWS, h - 1);      // blurred rows formed here
-    const int ylast = min(yb + LBD_BLUR_ROWS, h) - 1;
-    int rs[5][6];                                         // row sums of the last five source rows (oldest first)
-    int hd1[4], hs1[4], hd2[4], hs2[4];                    // Sobel row terms of blurred rows v-1 and v-2
-#pragma unroll
-    for (int j = 0; j < 4; j++) { hd1[j] = hs1[j] = hd2[j] = hs2[j] = 0; }
-#pragma unroll
-    for (int q = 0; q < 5; q++)
-#pragma unroll
-        for (int c = 0; c < 6; c++) rs[q][c] = 0;
-    short2 *out = dxy + (size_t)f * h * w;
-    const bool vecst = (w & 3) == 0;                       // 16-byte stores need every row start aligned
-    for (int sr = v0 - 2; sr <= v1 + 2; sr++) {
-        const uint8_t *S = G + (size_t)refl(min(sr, h + 1), h) * gpitch;
-        unsigned W0 = *reinterpret_cast<const uint32_t *>(S + o0), W1 = *reinterpret_cast<const uint32_t *>(S + x0),
-                 W2 = *reinterpret_cast<const uint32_t *>(S + o2);
-        edge_fix(es, W0, W1, W2);                          // REFLECT_101 at the left / right image border (identity elsewhere)
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-#pragma unroll
-            for (int c = 0; c < 6; c++) rs[q][c] = rs[q + 1][c];
-        // column c = pixel x0-1+c: taps at window bytes c+1 .. c+5 (window byte 0 = pixel x0-4)
-        rs[4][0] = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(W1, W0, 1), kA, (unsigned)k0 * ((W1 >> 8) & 0xFFu), false);
-        rs[4][1] = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(W1, W0, 2), kA, (unsigned)k0 * ((W1 >> 16) & 0xFFu), false);
-        rs[4][2] = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(W1, W0, 3), kA, (unsigned)k0 * (W1 >> 24), false);
-        rs[4][3] = (int)__builtin_amdgcn_udot4(W1, kA, (unsigned)k0 * (W2 & 0xFFu), false);
-        rs[4][4] = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(W2, W1, 1), kA, (unsigned)k0 * ((W2 >> 8) & 0xFFu), false);
-        rs[4][5] = (int)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(W2, W1, 2), kA, (unsigned)k0 * ((W2 >> 16) & 0xFFu), false);
-        const int v = sr - 2;                              // blurred row completed by this source row
-        if (v < v0) continue;
-        int bl[6];
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-            const int sv = k0 * (rs[0][c] + rs[4][c]) + k1 * (rs[1][c] + rs[3][c]) + k2 * rs[2][c];
-            int q;
-            if (x0 - 1 + c < wv4) { q = sv >> 16; const int rem = sv & 0xFFFF; if (rem > 32768 || (rem == 32768 && (q & 1))) q++; }   // SSE2 column path: half to even
-            else q = (sv + 32768) >> 16;                                                                                                   // scalar tail
-            bl[c] = min(q, 255);
-        }
-        int hd0[4], hs0[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int x = x0 + j;
-            const int a = x == 0 ? bl[j + 2] : bl[j], e = x == w - 1 ? bl[j] : bl[j + 2];
-            hd0[j] = e - a; hs0[j] = a + 2 * bl[j + 1] + e;
-        }
-        // Sobel row y = v-1 from blurred rows v-2 (reflected at the top: row 1), v-1, v; the bottom row y = h-1 uses row h-2 twice
-        for (int pass = 0; pass < 2; pass++) {
-            const int y = pass == 0 ? v - 1 : v;
-            if (pass == 1 && !(v == h - 1)) break;
-            if (y < yb || y > ylast) continue;
-            short2 g[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                int gx, gy;
-                if (pass == 0) {
-                    const int hdu = v >= 2 ? hd2[j] : hd0[j], hsu = v >= 2 ? hs2[j] : hs0[j];
-                    gx = hdu + 2 * hd1[j] + hd0[j]; gy = hs0[j] - hsu;
-                } else { gx = 2 * hd1[j] + 2 * hd0[j]; gy = 0; }         // rows (h-2, h-1, h-2)
-                g[j] = make_short2((short)gx, (short)gy);
-            }
-            short2 *o = out + (size_t)y * w + x0;
-            if (vecst) *reinterpret_cast<uint4 *>(o) = *reinterpret_cast<const uint4 *>(g);
-            else {
-#pragma unroll
-                for (int j = 0; j < 4; j++) if (x0 + j < w) o[j] = g[j];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) { hd2[j] = hd1[j]; hs2[j] = hs1[j]; hd1[j] = hd0[j]; hs1[j] = hs0[j]; }
-    }
+    // rows are 4-byte aligned (pitch % 64 == 0)
+    lbd_blur_sobel_body<AL>(gray + (size_t)f * gframe, gpitch, dxy + (size_t)f * h * w, w, h, x0, yb, k0, k1, k2);
 }
 
 __constant__ int c_lbd_comb[32][2] = {
@@ -1632,7 +1725,7 @@ static int lsd_build_plan(hvo_ctx *ctx, int w, int h, int batch)
         u = (9 * 7 - 1) / 2; sigma = u; inv = -1 / (2 * sigma * sigma);
         for (int i = 0; i < 63; i++) { double d = i - u; P->gG[i] = exp(d * d * inv); }
     }
-    std::vector<int> xofs(P->sw), yofs(P->sh); std::vector<float> xa(2 * P->sw), yb(2 * P->sh);
+    std::vector<int> xofs(P->sw), yofs(P->sh + PRE_CH, 0); std::vector<float> xa(2 * P->sw), yb(2 * (P->sh + PRE_CH), 0.f);      // (row tables padded by a chunk of k_lsd_pre)
     const double scale = 1. / SCALE;
     for (int dx = 0; dx < P->sw; dx++) {
         float fx = (float)((dx + 0.5) * scale - 0.5); int sx = cvfloor_f(fx); fx -= sx;
@@ -1688,19 +1781,22 @@ static int lsd_build_plan(hvo_ctx *ctx, int w, int h, int batch)
     PA(P->d_kl2, B * P->nfeat * sizeof(hvo_keyline)); PA(P->d_desc2, B * P->nfeat * 32); PA(P->d_fn2, B * P->nfeat * 24); PA(P->d_nkl2, B * 4);
     if (P->kn.lbd_split.set) PA(P->d_b5, CB * npix);
     PA(P->d_dxy, CB * npix * sizeof(short2));
-    PA(P->d_xofs, P->sw * 4); PA(P->d_yofs, P->sh * 4); PA(P->d_xa, P->sw * 8); PA(P->d_yb, P->sh * 8);
+    PA(P->d_xofs, P->sw * 4); PA(P->d_yofs, (P->sh + PRE_CH) * 4); PA(P->d_xa, P->sw * 8); PA(P->d_yb, (P->sh + PRE_CH) * 8);      // (k_lsd_pre reads the row tables a chunk at a time: padded)
     PA(P->d_gL, 21 * 4); PA(P->d_gG, 63 * 4); PA(P->d_stats, B * 64);
     if (P->pre_fused) {
         // a band's source columns must fit the workgroup's 256 threads (true for the 0.8x scale: 192 / 0.8 + 2; checked, not assumed)
         int maxc = 0;
         for (int x0 = 0; x0 < P->sw; x0 += PRE_TW) { const int xe = std::min(x0 + PRE_TW, P->sw - 1); maxc = std::max(maxc, std::min(xofs[xe] + 1, w - 1) - xofs[x0] + 1); }
-        if (maxc > 256) { P->pre_fused = false; PA(P->d_blur, CB * npix * 8); }
+        // the blurred rows a chunk's scaled rows interpolate from must fit the ring (six at the 0.8x scale)
+        int maxr = 0;
+        for (int ys = 0; ys < P->sh; ys += PRE_CH) maxr = std::max(maxr, (yofs[std::min(ys + PRE_CH - 1, P->sh - 1)] >> 16) - (yofs[ys] & 0xFFFF) + 1);
+        if (maxc > 256 || maxr > PRE_RING) { P->pre_fused = false; PA(P->d_blur, CB * npix * 8); }
     }
 #undef PA
     HVO_HIP(hipMemcpy(P->d_xofs, xofs.data(), P->sw * 4, hipMemcpyHostToDevice));
-    HVO_HIP(hipMemcpy(P->d_yofs, yofs.data(), P->sh * 4, hipMemcpyHostToDevice));
+    HVO_HIP(hipMemcpy(P->d_yofs, yofs.data(), yofs.size() * 4, hipMemcpyHostToDevice));
     HVO_HIP(hipMemcpy(P->d_xa, xa.data(), P->sw * 8, hipMemcpyHostToDevice));
-    HVO_HIP(hipMemcpy(P->d_yb, yb.data(), P->sh * 8, hipMemcpyHostToDevice));
+    HVO_HIP(hipMemcpy(P->d_yb, yb.data(), yb.size() * 4, hipMemcpyHostToDevice));
     HVO_HIP(hipMemcpy(P->d_gL, gLf.data(), 21 * 4, hipMemcpyHostToDevice));
     HVO_HIP(hipMemcpy(P->d_gG, gGf.data(), 63 * 4, hipMemcpyHostToDevice));
     HVO_HIP(hipMemsetAsync(P->d_defined, 0, B * P->nwords * 4, ctx->s_lsd));
@@ -1895,8 +1991,11 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
             hipLaunchKernelGGL(k_lbd_blur5, dim3((w + 255) / 256, (h + LBD_BLUR_ROWS - 1) / LBD_BLUR_ROWS, m), dim3(256), 0, st, gc, O.pyr_bytes, gpitch, P->d_b5, w, h, P->k5[0], P->k5[1], P->k5[2]);
             hipLaunchKernelGGL(k_lbd_sobel, dim3((w + 255) / 256, (h + LBD_BLUR_ROWS - 1) / LBD_BLUR_ROWS, m), dim3(256), 0, st, P->d_b5, P->d_dxy, w, h);
         } else
-            hipLaunchKernelGGL(k_lbd_blur_sobel, dim3((((w + 3) / 4) * ((h + LBD_BLUR_ROWS - 1) / LBD_BLUR_ROWS) + 255) / 256, 1, m), dim3(256), 0, st, gc, O.pyr_bytes, gpitch, P->d_dxy, w, h,
-                               P->k5[0], P->k5[1], P->k5[2]);
+{
+            const dim3 grid((((w + 3) / 4) * ((h + LBD_FUSED_ROWS - 1) / LBD_FUSED_ROWS) + 255) / 256, 1, m);
+            if ((w & 3) == 0) hipLaunchKernelGGL(k_lbd_blur_sobel<true>, grid, dim3(256), 0, st, gc, O.pyr_bytes, gpitch, P->d_dxy, w, h, P->k5[0], P->k5[1], P->k5[2]);
+            else hipLaunchKernelGGL(k_lbd_blur_sobel<false>, grid, dim3(256), 0, st, gc, O.pyr_bytes, gpitch, P->d_dxy, w, h, P->k5[0], P->k5[1], P->k5[2]);
+        }
         hvo_prof_end(ctx, id);
         id = hvo_prof_begin(ctx, "lbd_desc", st);
         hipLaunchKernelGGL(k_lbd_desc, dim3(P->nfeat, m), dim3(64), 0, st, P->d_dxy, w, h, P->d_kl + ko, P->d_nkl + c0, P->nfeat, P->d_gL, P->d_gG, P->d_desc + ko * 32);
@@ -2036,6 +2135,67 @@ extern "C" int hvo_debug_lsd_stats(hvo_ctx *ctx, int frame, long long *out8)
     LsdPlan *P = ctx ? plan_of(ctx) : nullptr;
     if (!P || frame < 0 || frame >= P->batch) return HVO_ERR_INVALID_ARG;
     HVO_HIP(hipMemcpy(out8, P->d_stats + (size_t)frame * 8, 64, hipMemcpyDeviceToHost));
+    return HVO_OK;
+}
+
+// diagnostics (not part of include/hvo.h): the images the streaming kernels of the last HVO_STAGE_LSD run left for `frame`, for tests that
+// compare two formulations of those kernels on every pixel (the key lines sample them near lines only):
+//   mask     nwords words: the defined mask (a bit per scaled pixel, rows padded to 32 bits)
+//   records  the 32-byte records {angle, cos, sin, modgrad} of the defined pixels, in raster order (at most rec_cap; *n_records: how many there are)
+//   dxy      w * h short2: the LBD gradient image (dx, dy)
+// The growing kernel consumes the mask as its availability mask, so the frame's preamble -- the kernels the plan selects, on the resident
+// image -- is launched once more for this frame and leaves the mask (and the same records) again.  Valid for a batch of at most one chunk
+// with one dense record per pixel and the default detector; anything else: HVO_ERR_UNSUPPORTED.
+extern "C" int hvo_debug_lsd_images(hvo_ctx *ctx, int frame, int *sw_out, int *sh_out, unsigned *mask, double *records, long long rec_cap, long long *n_records, short *dxy)
+{
+    LsdPlan *P = ctx ? plan_of(ctx) : nullptr;
+    if (!P || !mask || !records || !n_records || !dxy || rec_cap < 0) return HVO_ERR_INVALID_ARG;
+    if (!(ctx->last_stages & HVO_STAGE_LSD) || frame < 0 || frame >= ctx->batch_n) { ctx->last_error = "lsd images: no such frame in the last HVO_STAGE_LSD run"; return HVO_ERR_INVALID_ARG; }
+    if (ctx->batch_n > P->chunk || P->compact || (ctx->readings & (HVO_READING_LSD_8U | HVO_READING_BLUR_FLOAT))) {
+        ctx->last_error = "lsd images: only for a batch of at most one chunk with dense records and the default detector";
+        return HVO_ERR_UNSUPPORTED;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    OrbPlan &O = ctx->orb;
+    hipStream_t st = hvo_stream_lsd(ctx);
+    const int w = P->w, h = P->h, sw = P->sw, sh = P->sh, gpitch = O.lev[0].pitch;
+    const size_t nsp = (size_t)sw * sh;
+    const uint8_t *gray = O.d_pyr + O.lev[0].img_off + (size_t)frame * O.pyr_bytes;
+    double4 *px = P->d_px + (size_t)frame * nsp;
+    unsigned *def = P->d_defined + (size_t)frame * P->nwords;
+    HVO_HIP(hipStreamSynchronize(st));
+    // the records of the run itself first (the growing reads them, it does not write them)
+    std::vector<double> rec(nsp * 4);
+    HVO_HIP(hipMemcpy(rec.data(), px, nsp * sizeof(double4), hipMemcpyDeviceToHost));
+    HVO_HIP(hipMemcpy(dxy, P->d_dxy + (size_t)frame * w * h, (size_t)w * h * sizeof(short2), hipMemcpyDeviceToHost));
+    if (P->pre_fused)
+        hipLaunchKernelGGL(k_lsd_pre, dim3((sw + PRE_TW - 1) / PRE_TW, (sh - 1 + PRE_SEG - 1) / PRE_SEG, 1), dim3(256), 0, st, gray, O.pyr_bytes, gpitch,
+                           w, h, sw, sh, P->d_xofs, P->d_xa, P->d_yofs, P->d_yb, px, def, P->nwords, P->rhoT, P->k7[0], P->k7[1], P->k7[2], P->k7[3], (const int *)nullptr);
+    else {
+        hipLaunchKernelGGL(k_lsd_blur, dim3((w + 255) / 256, (h + LSD_BLUR_ROWS - 1) / LSD_BLUR_ROWS, 1), dim3(256), 0, st, gray, O.pyr_bytes, gpitch, P->d_blur, w, h,
+                           P->k7[0], P->k7[1], P->k7[2], P->k7[3]);
+        hipLaunchKernelGGL(k_lsd_resize_grad, dim3((((sw + 31) & ~31) + 255) / 256, (sh + GRAD_ROWS - 1) / GRAD_ROWS, 1), dim3(256), 0, st, P->d_blur, w, h, sw, sh,
+                           P->d_xofs, P->d_xa, P->d_yofs, P->d_yb, px, def, P->nwords, P->rho);
+    }
+    HVO_HIP(hipGetLastError());
+    HVO_HIP(hipStreamSynchronize(st));
+    HVO_HIP(hipMemcpy(mask, def, (size_t)P->nwords * 4, hipMemcpyDeviceToHost));
+    std::vector<double> rec2(nsp * 4);
+    HVO_HIP(hipMemcpy(rec2.data(), px, nsp * sizeof(double4), hipMemcpyDeviceToHost));
+    const int wpr = (sw + 31) / 32;
+    long long n = 0;
+    for (int y = 0; y < sh; y++)
+        for (int x = 0; x < sw; x++) {
+            if (!((mask[(size_t)y * wpr + (x >> 5)] >> (x & 31)) & 1u)) continue;
+            const size_t i = ((size_t)y * sw + x) * 4;
+            // formed twice from the same image by the same kernel: any difference is a defect of that kernel (an unwritten or racing record)
+            if (memcmp(&rec[i], &rec2[i], 32) != 0) { ctx->last_error = "lsd images: a record of the run differs from the one formed again"; return HVO_ERR_HIP; }
+            if (n < rec_cap) memcpy(records + n * 4, &rec[i], 32);
+            n++;
+        }
+    *n_records = n;
+    if (sw_out) *sw_out = sw;
+    if (sh_out) *sh_out = sh;
     return HVO_OK;
 }
 
