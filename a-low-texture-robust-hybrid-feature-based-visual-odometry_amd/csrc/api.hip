@@ -1,7 +1,7 @@
 // api.hip -- the extern "C" boundary of libhvo.so (include/hvo.h).  No compute here: argument
 // checks, device selection, staging, and dispatch to the per-subsystem batch runners.
 // There is deliberately no CPU path: without a usable gfx950 device every call fails.
-#include "hvo_internal.hpp"
+#include "frame_view.hpp"
 #include <stdio.h>
 #include <algorithm>
 #include <math.h>
@@ -674,25 +674,21 @@ int hvo_track_manhattan(hvo_ctx *ctx, const hvo_surface_normal *normals, int n_n
     return HVO_OK;
 }
 
+// bytes between the same array of two views: one launch chains a resident batch's frames (mf_enqueue, pa_match), so their callers pass view 0's
+// pointer and this stride (views 0 and n > 1: 0 for a single frame)
+static size_t view_stride(const void *p0, const void *p1) { return (size_t)((const char *)p1 - (const char *)p0); }
+
 // the resident batch as a sequence: frame k from frame k-1's R, one launch over the tail blocks of the last hvo_batch_run
 int hvo_batch_track_manhattan(hvo_ctx *ctx, int n, const float R0[9], hvo_mf_result *res)
 {
-    if (!ctx || !R0 || !res || n < 1 || n > ctx->batch_n) return HVO_ERR_INVALID_ARG;
-    const unsigned need = HVO_STAGE_PLANE_TAIL | HVO_STAGE_LINES3D;
-    if ((ctx->last_stages & need) != need) {
-        ctx->last_error = "Manhattan tracking: the last hvo_batch_run must include HVO_STAGE_PLANE_TAIL and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
-    }
-    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    char *d_out = nullptr; TailLayout L;
-    if (tail_batch_view(ctx, &d_out, &L)) { ctx->last_error = "Manhattan tracking: no resident tail results"; return HVO_ERR_INVALID_ARG; }
-    LsdView lv; memset(&lv, 0, sizeof(lv));
-    int rc;
-    if ((rc = lsd_prepare(ctx, ctx->batch_w, ctx->batch_h, std::max(n, ctx->p.max_batch), ctx->last_cull, &lv))) return rc;
+    if (!ctx || !R0 || !res || n < 1) return HVO_ERR_INVALID_ARG;
+    std::vector<FrameView> V; int rc;
+    if ((rc = batch_views(ctx, n, need_manhattan, V))) return rc;
     hvo_mf_result *d_r = (hvo_mf_result *)hvo_call_arena(ctx, (size_t)n * sizeof(hvo_mf_result));
     if (!d_r) return HVO_ERR_HIP;
     hipStream_t st = ctx->stream;
-    rc = mf_enqueue(st, (const hvo_surface_normal *)(d_out + L.normals), L.n_normals, L.total, (const hvo_line3d *)(d_out + L.lines3d), L.nfeat, L.total,
-                    lv.d_nkl, n, R0, d_r, nullptr, nullptr);
+    const FrameView &v = V[0], &v1 = V[n > 1];
+    rc = mf_enqueue(st, v.normals, v.n_normals, view_stride(v.normals, v1.normals), v.l3d, v.nfeat, view_stride(v.l3d, v1.l3d), v.d_nkl, n, R0, d_r, nullptr, nullptr);
     if (rc) { ctx->last_error = "Manhattan tracking launch"; return rc; }
     HVO_HIP(hipMemcpyAsync(res, d_r, (size_t)n * sizeof(hvo_mf_result), hipMemcpyDeviceToHost, st));
     HVO_HIP(hipStreamSynchronize(st));
@@ -712,18 +708,14 @@ int hvo_match_planes(hvo_ctx *ctx, hvo_plane_map *m, const float *coef, int n, c
     return rc;
 }
 
-// the same over the first n frames of the resident batch: the plane tail's records where the last hvo_batch_run left them, one Tcw per frame
+// the same over the first n frames of the resident batch: the plane tail's records, one Tcw per frame
 int hvo_batch_match_planes(hvo_ctx *ctx, hvo_plane_map *m, int n, const float *Tcw, const float th[4], hvo_plane_match *res)
 {
-    if (!ctx || !m || !Tcw || !res || n < 1 || n > ctx->batch_n) return HVO_ERR_INVALID_ARG;
-    if (!(ctx->last_stages & HVO_STAGE_PLANE_TAIL)) {
-        ctx->last_error = "plane association: the last hvo_batch_run must include HVO_STAGE_PLANE_TAIL"; return HVO_ERR_INVALID_ARG;
-    }
+    if (!ctx || !m || !Tcw || !res || n < 1) return HVO_ERR_INVALID_ARG;
+    std::vector<FrameView> V; int rc;
+    if ((rc = batch_views(ctx, n, need_planes, V))) return rc;
     if (pa_map_device(m) != ctx->device) { ctx->last_error = "plane association: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    char *d_out = nullptr; TailLayout L;
-    if (tail_batch_view(ctx, &d_out, &L)) { ctx->last_error = "plane association: no resident tail results"; return HVO_ERR_INVALID_ARG; }
-    const int rc = pa_match(ctx->stream, m, nullptr, 0, (const hvo_plane_cloud *)(d_out + L.pclouds), L.total, n, Tcw, th, res, nullptr, nullptr);
+    rc = pa_match(ctx->stream, m, nullptr, 0, V[0].pclouds, view_stride(V[0].pclouds, V[n > 1].pclouds), n, Tcw, th, res, nullptr, nullptr);
     if (rc) ctx->last_error = pa_map_error(m);
     return rc;
 }
@@ -734,41 +726,17 @@ int hvo_pose_optimize(hvo_ctx *ctx, const hvo_camera *cam, const hvo_pose_plane_
 {
     if (!ctx || !cam || !prob || !res || n < 1) return HVO_ERR_INVALID_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    float inv_s2[HVO_MAX_LEVELS];                                // mvInvLevelSigma2 (ORBextractor.cc:428-436)
-    for (int i = 0; i < HVO_MAX_LEVELS; i++) inv_s2[i] = i < ctx->p.orb_nlevels ? 1.0f / (ctx->scale[i] * ctx->scale[i]) : 1.0f;
-    return po_run(ctx, ctx->stream, cam, pp, inv_s2, n, prob, nullptr, res, flags, &ctx->last_error);
+    return po_run(ctx, ctx->stream, cam, pp, n, prob, nullptr, res, flags, &ctx->last_error);
 }
 
-// the same on the first n frames of the resident batch: the frame side where the last hvo_batch_run left it, mvuRight formed in the kernel
+// the same on the first n frames of the resident batch: mvuRight is formed in the kernel from the resident depth image
 int hvo_batch_pose_optimize(hvo_ctx *ctx, const hvo_camera *cam, const hvo_pose_plane_params *pp, int n, const hvo_pose_problem *prob,
                             hvo_pose_result *res, const hvo_pose_flags *flags)
 {
     if (!ctx || !cam || !prob || !res || n < 1) return HVO_ERR_INVALID_ARG;
-    if (n > ctx->batch_n) { ctx->last_error = "pose optimisation: n beyond the resident batch"; return HVO_ERR_INVALID_ARG; }
-    const unsigned need = HVO_STAGE_ORB | HVO_STAGE_LSD | HVO_STAGE_LINES3D | HVO_STAGE_PLANE_TAIL;
-    if ((ctx->last_stages & need) != need) {
-        ctx->last_error = "pose optimisation: the last hvo_batch_run must include HVO_STAGE_ORB, an LSD stage, HVO_STAGE_LINES3D and HVO_STAGE_PLANE_TAIL"; return HVO_ERR_INVALID_ARG;
-    }
-    if (!ctx->have_depth) { ctx->last_error = "pose optimisation: the batch was uploaded without depth (no mvuRight, 3-D lines or planes)"; return HVO_ERR_INVALID_ARG; }
-    if (!(cam->bf > 0)) { ctx->last_error = "pose optimisation: bf <= 0 (no mvuRight)"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    char *d_out = nullptr; TailLayout L;
-    if (tail_batch_view(ctx, &d_out, &L)) { ctx->last_error = "pose optimisation: no resident tail results"; return HVO_ERR_INVALID_ARG; }
-    LsdView lv; PeacView pv; memset(&lv, 0, sizeof(lv)); memset(&pv, 0, sizeof(pv));
-    int rc;
-    if ((rc = lsd_prepare(ctx, ctx->batch_w, ctx->batch_h, std::max(n, ctx->p.max_batch), ctx->last_cull, &lv))) return rc;
-    if ((rc = peac_prepare(ctx, ctx->batch_w, ctx->batch_h, std::max(n, ctx->p.max_batch), &pv))) return rc;
-    std::vector<PoResident> R((size_t)n);
-    for (int f = 0; f < n; f++) {
-        PoResident &r = R[f];
-        r.kp_un = ctx->orb.d_kp + (size_t)f * ctx->orb.kp_cap; r.uright = nullptr; r.d_nkp = ctx->orb.d_nkp + f;
-        r.linefn = lv.d_fn + (size_t)f * lv.nfeat * 3; r.d_nkl = lv.d_nkl + f;
-        r.l3d = (const hvo_line3d *)(d_out + (size_t)f * L.total + L.lines3d); r.pclouds = (const hvo_plane_cloud *)(d_out + (size_t)f * L.total + L.pclouds);
-        r.depth = pv.d_depth + (size_t)f * pv.dframe; r.pitch = pv.pitch; r.w = ctx->batch_w; r.h = ctx->batch_h; r.dfac = ctx->p.depth_map_factor;
-    }
-    float inv_s2[HVO_MAX_LEVELS];
-    for (int i = 0; i < HVO_MAX_LEVELS; i++) inv_s2[i] = i < ctx->p.orb_nlevels ? 1.0f / (ctx->scale[i] * ctx->scale[i]) : 1.0f;
-    return po_run(ctx, ctx->stream, cam, pp, inv_s2, n, prob, R.data(), res, flags, &ctx->last_error);
+    std::vector<FrameView> V; int rc;
+    if ((rc = batch_views(ctx, n, need_pose, V, cam->bf))) return rc;
+    return po_run(ctx, ctx->stream, cam, pp, n, prob, V.data(), res, flags, &ctx->last_error);
 }
 
 // Manhattan::computeStructConstrains for every key line + Optimizer::LineOptStruct (Tracking.cc:270-335) of n problems on host arrays (line_opt.hip)
@@ -782,33 +750,17 @@ int hvo_line_struct_optimize(hvo_ctx *ctx, const hvo_line_struct_params *params,
     return ls_run(ctx, ctx->stream, params, n_frames, nl.data(), problems, nullptr, rel, l3d_out, res, &ctx->last_error);
 }
 
-// the same on the first n frames of the resident batch: key-line functions and 3-D lines where the last hvo_batch_run left them; A, B of the
-// resident records are rewritten
+// the same on the first n frames of the resident batch: A, B of the resident 3-D line records are rewritten
 int hvo_batch_line_struct_optimize(hvo_ctx *ctx, const hvo_line_struct_params *params, int n, const int32_t *n_lines, int8_t *const *rel,
                                    double *const *l3d_out, hvo_line_opt_result *res)
 {
     if (!ctx || !n_lines || !rel || !res || n < 1) return HVO_ERR_INVALID_ARG;
-    if (n > ctx->batch_n) { ctx->last_error = "line structure: n beyond the resident batch"; return HVO_ERR_INVALID_ARG; }
-    const unsigned need = HVO_STAGE_LSD | HVO_STAGE_LINES3D;
-    if ((ctx->last_stages & need) != need) {
-        ctx->last_error = "line structure: the last hvo_batch_run must include an LSD stage and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
-    }
-    if (!ctx->have_depth) { ctx->last_error = "line structure: the batch was uploaded without depth (no 3-D lines)"; return HVO_ERR_INVALID_ARG; }
+    std::vector<FrameView> V; int rc;
+    if ((rc = batch_views(ctx, n, need_line_struct, V))) return rc;
     const bool opt = !params || (params->mode & HVO_LINE_STRUCT_OPTIMIZE);
     if (opt && ctx->ls_batch_done) { ctx->last_error = "line structure: the resident batch's 3-D lines have been optimised already"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    char *d_out = nullptr; TailLayout L;
-    if (tail_batch_view(ctx, &d_out, &L)) { ctx->last_error = "line structure: no resident tail results"; return HVO_ERR_INVALID_ARG; }
-    LsdView lv; memset(&lv, 0, sizeof(lv));
-    int rc;
-    if ((rc = lsd_prepare(ctx, ctx->batch_w, ctx->batch_h, std::max(n, ctx->p.max_batch), ctx->last_cull, &lv))) return rc;
-    for (int f = 0; f < n; f++) if (n_lines[f] > lv.nfeat) { ctx->last_error = "line structure: n_lines beyond the key-line capacity"; return HVO_ERR_INVALID_ARG; }
-    std::vector<LsResident> R((size_t)n);
-    for (int f = 0; f < n; f++) {
-        R[f].linefn = lv.d_fn + (size_t)f * lv.nfeat * 3; R[f].d_nkl = lv.d_nkl + f;
-        R[f].l3d = (hvo_line3d *)(d_out + (size_t)f * L.total + L.lines3d);
-    }
-    rc = ls_run(ctx, ctx->stream, params, n, n_lines, nullptr, R.data(), rel, l3d_out, res, &ctx->last_error);
+    for (int f = 0; f < n; f++) if (n_lines[f] > V[f].nfeat) { ctx->last_error = "line structure: n_lines beyond the key-line capacity"; return HVO_ERR_INVALID_ARG; }
+    rc = ls_run(ctx, ctx->stream, params, n, n_lines, nullptr, V.data(), rel, l3d_out, res, &ctx->last_error);
     if (rc == HVO_OK && opt) ctx->ls_batch_done = true;
     return rc;
 }
@@ -831,56 +783,34 @@ int hvo_search_local_lines(hvo_ctx *ctx, hvo_line_map *m, const hvo_camera *cam,
                  b_cs = al((size_t)ncell * 4), b_ci = al((size_t)n_items * 4);
     char *a = (char *)hvo_call_arena(ctx, b_kl + b_fn + b_l3 + b_d + b_cs + b_ci + 256);
     if (!a) return HVO_ERR_HIP;
-    LlFrameDev F; memset(&F, 0, sizeof(F));
-    F.nt = nt; F.n_items = n_items;
-    F.kl = (const hvo_keyline *)a; F.fn = (const double *)(a + b_kl); F.l3d = (const hvo_line3d *)(a + b_kl + b_fn); F.desc = (const uint8_t *)(a + b_kl + b_fn + b_l3);
-    F.cell_start = (const int32_t *)(a + b_kl + b_fn + b_l3 + b_d); F.cell_items = (const int32_t *)(a + b_kl + b_fn + b_l3 + b_d + b_cs);
+    FrameView F; memset(&F, 0, sizeof(F));
+    F.n_kl = nt; F.n_ln_items = n_items; memcpy(F.bounds, params->bounds, sizeof(F.bounds));
+    F.kl = (const hvo_keyline *)a; F.fn = (const double *)(a + b_kl); F.l3d = (hvo_line3d *)(a + b_kl + b_fn); F.ldesc = (const uint8_t *)(a + b_kl + b_fn + b_l3);
+    F.ln_start = (const int32_t *)(a + b_kl + b_fn + b_l3 + b_d); F.ln_items = (const int32_t *)(a + b_kl + b_fn + b_l3 + b_d + b_cs);
     hipStream_t st = ctx->stream;
     if (nt) {
         HVO_HIP(hipMemcpyAsync((void *)F.kl, frame->kl, (size_t)nt * sizeof(hvo_keyline), hipMemcpyHostToDevice, st));
         HVO_HIP(hipMemcpyAsync((void *)F.fn, frame->linefn, (size_t)nt * 24, hipMemcpyHostToDevice, st));
         HVO_HIP(hipMemcpyAsync((void *)F.l3d, frame->l3d, (size_t)nt * sizeof(hvo_line3d), hipMemcpyHostToDevice, st));
-        HVO_HIP(hipMemcpyAsync((void *)F.desc, frame->desc, (size_t)nt * 32, hipMemcpyHostToDevice, st));
-        HVO_HIP(hipMemcpyAsync((void *)F.cell_start, frame->cell_start, (size_t)ncell * 4, hipMemcpyHostToDevice, st));
-        if (n_items) HVO_HIP(hipMemcpyAsync((void *)F.cell_items, frame->cell_items, (size_t)n_items * 4, hipMemcpyHostToDevice, st));
+        HVO_HIP(hipMemcpyAsync((void *)F.ldesc, frame->desc, (size_t)nt * 32, hipMemcpyHostToDevice, st));
+        HVO_HIP(hipMemcpyAsync((void *)F.ln_start, frame->cell_start, (size_t)ncell * 4, hipMemcpyHostToDevice, st));
+        if (n_items) HVO_HIP(hipMemcpyAsync((void *)F.ln_items, frame->cell_items, (size_t)n_items * 4, hipMemcpyHostToDevice, st));
     }
-    const int rc = ll_run(st, m, cam, params, params->bounds, 1, &F, Tcw, io, res);
+    const int rc = ll_run(st, m, cam, params, 1, &F, Tcw, io, res);
     if (rc) ctx->last_error = ll_map_error(m);
     return rc;
 }
 
-// the same over the first n frames of the resident batch: the frame side where the last hvo_batch_run left it, one pose per frame
+// the same over the first n frames of the resident batch, one pose per frame
 int hvo_batch_search_local_lines(hvo_ctx *ctx, hvo_line_map *m, int n, const hvo_camera *cam, const float *Tcw, const hvo_local_lines_params *params,
                                  hvo_local_lines_io *io, hvo_local_lines_result *res)
 {
     if (!ctx || !m || !cam || !Tcw || !params || !io || !res || n < 1) return HVO_ERR_INVALID_ARG;
-    if (n > ctx->batch_n) { ctx->last_error = "local lines: n beyond the resident batch"; return HVO_ERR_INVALID_ARG; }
-    const unsigned need = HVO_STAGE_GRIDS | HVO_STAGE_LINES3D;
-    if (!(ctx->last_stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL)) || (ctx->last_stages & need) != need) {
-        ctx->last_error = "local lines: the last hvo_batch_run must include an LSD stage, HVO_STAGE_GRIDS and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
-    }
-    if (!ctx->have_depth) { ctx->last_error = "local lines: the batch was uploaded without depth (no 3-D lines)"; return HVO_ERR_INVALID_ARG; }
+    std::vector<FrameView> V; int rc;   // (the resident counts: io[f].n_kl may say more, never less)
+    if ((rc = batch_views(ctx, n, need_local_lines, V))) return rc;
     if (ll_map_device(m) != ctx->device) { ctx->last_error = "local lines: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    char *d_out = nullptr; TailLayout L;
-    if (tail_batch_view(ctx, &d_out, &L)) { ctx->last_error = "local lines: no resident tail results"; return HVO_ERR_INVALID_ARG; }
-    LsdView lv; memset(&lv, 0, sizeof(lv));
-    int rc;
-    if ((rc = lsd_prepare(ctx, ctx->batch_w, ctx->batch_h, std::max(n, ctx->p.max_batch), ctx->last_cull, &lv))) return rc;
-    std::vector<LlFrameDev> F((size_t)n);
-    std::vector<int> nkl((size_t)n);                              // the resident counts: io[f].n_kl may say more, never less
-    HVO_HIP(hipMemcpyAsync(nkl.data(), lv.d_nkl, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HVO_HIP(hipStreamSynchronize(ctx->stream));
-    for (int f = 0; f < n; f++) {
-        if (io[f].n_kl < 0) return HVO_ERR_INVALID_ARG;
-        nkl[f] = std::max(0, std::min(nkl[f], lv.nfeat));
-        char *o = d_out + (size_t)f * L.total;
-        F[f].kl = lv.d_kl + (size_t)f * lv.nfeat; F[f].fn = lv.d_fn + (size_t)f * lv.nfeat * 3; F[f].desc = lv.d_desc + (size_t)f * lv.nfeat * 32;
-        F[f].l3d = (const hvo_line3d *)(o + L.lines3d); F[f].cell_start = (const int32_t *)(o + L.ln_start); F[f].cell_items = (const int32_t *)(o + L.ln_items);
-        F[f].n_items = L.ln_cap; F[f].nt = nkl[f];                  // (the item list is bounded by its capacity: its count lives on the device)
-    }
-    const float bounds[4] = { 0.f, (float)ctx->batch_w, 0.f, (float)ctx->batch_h };   // as tail_batch_run builds the grids
-    rc = ll_run(ctx->stream, m, cam, params, bounds, n, F.data(), Tcw, io, res);
+    for (int f = 0; f < n; f++) if (io[f].n_kl < 0) return HVO_ERR_INVALID_ARG;
+    rc = ll_run(ctx->stream, m, cam, params, n, V.data(), Tcw, io, res);
     if (rc) ctx->last_error = ll_map_error(m);
     return rc;
 }
@@ -894,8 +824,8 @@ int hvo_search_local_points(hvo_ctx *ctx, hvo_point_map *m, const hvo_camera *ca
     if (nt > 0 && (!frame->kp_un || !frame->desc)) return HVO_ERR_INVALID_ARG;
     if (lp_map_device(m) != ctx->device) { ctx->last_error = "local points: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
     if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    LpFrameDev F; memset(&F, 0, sizeof(F));
-    F.nt = nt;
+    FrameView F; memset(&F, 0, sizeof(F));
+    F.n_kp = nt; F.sf = ctx->scale; memcpy(F.bounds, params->bounds, sizeof(F.bounds));
     hipStream_t st = ctx->stream;
     if (nt > 0 && nt <= 65535) {                                  // (more is refused by lp_run before anything is read)
         auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -907,38 +837,24 @@ int hvo_search_local_points(hvo_ctx *ctx, hvo_point_map *m, const hvo_camera *ca
         if (frame->uright) HVO_HIP(hipMemcpyAsync((void *)F.uright, frame->uright, (size_t)nt * 4, hipMemcpyHostToDevice, st));
         HVO_HIP(hipMemcpyAsync((void *)F.desc, frame->desc, (size_t)nt * 32, hipMemcpyHostToDevice, st));
     }
-    const int rc = lp_run(st, m, cam, params, params->bounds, ctx->scale, 1, &F, Tcw, io, res);
+    const int rc = lp_run(st, m, cam, params, 1, &F, Tcw, io, res);
     if (rc) ctx->last_error = lp_map_error(m);
     return rc;
 }
 
-// the same over the first n frames of the resident batch: key points and descriptors where the last hvo_batch_run left them, mvuRight formed
-// from the resident depth image, one pose per frame
+// the same over the first n frames of the resident batch: mvuRight is formed from the resident depth image, one pose per frame
 int hvo_batch_search_local_points(hvo_ctx *ctx, hvo_point_map *m, int n, const hvo_camera *cam, const float *Tcw, const hvo_local_points_params *params,
                                   hvo_local_points_io *io, hvo_local_points_result *res)
 {
     if (!ctx || !m || !cam || !Tcw || !params || !io || !res || n < 1) return HVO_ERR_INVALID_ARG;
-    if (n > ctx->batch_n) { ctx->last_error = "local points: n beyond the resident batch"; return HVO_ERR_INVALID_ARG; }
-    if (!(ctx->last_stages & HVO_STAGE_ORB)) { ctx->last_error = "local points: the last hvo_batch_run must include HVO_STAGE_ORB"; return HVO_ERR_INVALID_ARG; }
+    std::vector<FrameView> V; int rc;   // (the resident counts: io[f].n_kp may say more, never less)
+    if ((rc = batch_views(ctx, n, need_local_points, V))) return rc;
     if (lp_map_device(m) != ctx->device) { ctx->last_error = "local points: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    const bool stereo = ctx->have_depth && params->bf > 0;
-    PeacView pv; memset(&pv, 0, sizeof(pv));
-    int rc;
-    if (stereo && (rc = peac_prepare(ctx, ctx->batch_w, ctx->batch_h, std::max(n, ctx->p.max_batch), &pv))) return rc;
-    std::vector<LpFrameDev> F((size_t)n);
-    std::vector<int> nkp((size_t)n);                              // the resident counts: io[f].n_kp may say more, never less
-    HVO_HIP(hipMemcpyAsync(nkp.data(), ctx->orb.d_nkp, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HVO_HIP(hipStreamSynchronize(ctx->stream));
     for (int f = 0; f < n; f++) {
         if (io[f].n_kp < 0) return HVO_ERR_INVALID_ARG;
-        memset(&F[f], 0, sizeof(F[f]));
-        F[f].nt = std::max(0, std::min(nkp[f], ctx->orb.kp_cap));
-        F[f].kp_un = ctx->orb.d_kp + (size_t)f * ctx->orb.kp_cap; F[f].desc = ctx->orb.d_desc + (size_t)f * ctx->orb.kp_cap * 32;
-        if (stereo) { F[f].depth = pv.d_depth + (size_t)f * pv.dframe; F[f].pitch = pv.pitch; F[f].w = ctx->batch_w; F[f].h = ctx->batch_h; F[f].dfac = ctx->p.depth_map_factor; }
+        if (!(params->bf > 0)) V[f].depth = nullptr;              // no stereo gate
     }
-    const float bounds[4] = { 0.f, (float)ctx->batch_w, 0.f, (float)ctx->batch_h };   // as tail_batch_run builds the grids
-    rc = lp_run(ctx->stream, m, cam, params, bounds, ctx->scale, n, F.data(), Tcw, io, res);
+    rc = lp_run(ctx->stream, m, cam, params, n, V.data(), Tcw, io, res);
     if (rc) ctx->last_error = lp_map_error(m);
     return rc;
 }

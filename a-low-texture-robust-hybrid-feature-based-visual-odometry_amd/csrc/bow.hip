@@ -32,7 +32,7 @@
 //                   of the multiset); both start at 256.  The claimed flags are a 64-bit mask per lane (bit c: position 64 c + lane),
 //                   private to the node because a frame feature lies in exactly one node.  Then the 30-bin rotation histogram and
 //                   ComputeThreeMaxima (hvo_three_maxima, shared with the guided search).
-#include "hvo_internal.hpp"
+#include "frame_view.hpp"
 #include <string.h>
 #include <stdio.h>
 #include <math.h>
@@ -433,11 +433,14 @@ static void bow_ev_read(hvo_ctx *ctx, int which)               // after the stre
     ctx->bow_ev_on[which] = false;
 }
 
-int bow_transform(hvo_ctx *ctx, hipStream_t st, const hvo_vocabulary *v, int levelsup, int nframes, const uint8_t *d_desc, size_t desc_stride,
-                  const int *d_n, int n_stride, int cap, const int *h_n, BowState *keep, bool may_keep, hvo_bow *out, std::string *err)
+int bow_transform(hvo_ctx *ctx, hipStream_t st, const hvo_vocabulary *v, int levelsup, int nframes, const FrameView *fr, BowState *keep, bool may_keep,
+                  hvo_bow *out, std::string *err)
 {
+    // one launch walks the frames: frame f's descriptors at d_desc + f * desc_stride, its count at d_n[f * n_stride]
+    const uint8_t *d_desc = fr[0].desc; const int *d_n = fr[0].d_nkp; const int cap = fr[0].kp_cap;
+    const size_t desc_stride = nframes > 1 ? (size_t)(fr[1].desc - fr[0].desc) : 0; const int n_stride = nframes > 1 ? (int)(fr[1].d_nkp - fr[0].d_nkp) : 0;
     for (int f = 0; f < nframes; f++) {
-        const int n = std::max(0, std::min(h_n[f], cap));
+        const int n = fr[f].n_kp;
         if (n > BOW_MAXN) { *err = "bag of words: more than 4096 features in a frame"; return HVO_ERR_UNSUPPORTED; }
         if (out[f].cap < n) { *err = "bag of words: out.cap below the frame's feature count"; return HVO_ERR_INVALID_ARG; }
     }
@@ -477,7 +480,7 @@ int bow_transform(hvo_ctx *ctx, hipStream_t st, const hvo_vocabulary *v, int lev
     for (int f = 0; f < nframes; f++) {
         const char *b = h.data() + (size_t)f * L.total; const int *c = (const int *)(b + L.counts);
         hvo_bow &o = out[f];
-        const int n = std::max(0, std::min(h_n[f], cap));
+        const int n = fr[f].n_kp;
         o.n_features = n; o.n_words = empty ? 0 : c[1]; o.n_nodes = empty ? 0 : c[2]; o.n_valid = empty ? 0 : c[3]; o.n_short = empty ? 0 : c[4];
         o.computed = kept ? 0 : 1; o.status = HVO_OK;
         if (o.word_id) memcpy(o.word_id, b + L.word_id, (size_t)n * 4);
@@ -492,10 +495,10 @@ int bow_transform(hvo_ctx *ctx, hipStream_t st, const hvo_vocabulary *v, int lev
 }
 
 // ------------------------------------------------------------------------------------------------ host: SearchByBoW
-int bow_search(hvo_ctx *ctx, hipStream_t st, const BowFrameSide &F, int n_kf, const hvo_bow_keyframe *kf, const hvo_bow_search_params *P,
-               hvo_bow_matches *res, std::string *err)
+int bow_search(hvo_ctx *ctx, hipStream_t st, const hvo_bow_keyframe *F, const FrameView *fr, const BowState *bow, int n_kf, const hvo_bow_keyframe *kf,
+               const hvo_bow_search_params *P, hvo_bow_matches *res, std::string *err)
 {
-    const int nf = F.n;
+    const int nf = F ? F->n : fr->n_kp;
     int capk = 0;
     for (int j = 0; j < n_kf; j++) {
         if (kf[j].n < 0 || (kf[j].n > 0 && (!kf[j].desc || !kf[j].node_id || !kf[j].has_map_point || (P->check_orientation && !kf[j].angle)))) return HVO_ERR_INVALID_ARG;
@@ -505,7 +508,7 @@ int bow_search(hvo_ctx *ctx, hipStream_t st, const BowFrameSide &F, int n_kf, co
     for (int j = 0; j < n_kf; j++) { res[j].n_matches = 0; res[j].status = HVO_OK; if (nf > 0 && !res[j].match_kf) return HVO_ERR_INVALID_ARG; }
     if (nf == 0) return HVO_OK;
     if (capk == 0) { for (int j = 0; j < n_kf; j++) for (int i = 0; i < nf; i++) res[j].match_kf[i] = -1; return HVO_OK; }
-    const bool fhost = F.h_desc != nullptr;
+    const bool fhost = F != nullptr;
     // one carve of the context's arena: the key-frame side (n_kf slots of capk), the frame side when it comes from the host, the results
     const size_t k_desc = 0, k_node = k_desc + al256((size_t)n_kf * capk * 32), k_has = k_node + al256((size_t)n_kf * capk * 4), k_ang = k_has + al256((size_t)n_kf * capk),
                  k_n = k_ang + al256((size_t)n_kf * capk * 4), up_k = k_n + al256((size_t)n_kf * 4);
@@ -529,9 +532,9 @@ int bow_search(hvo_ctx *ctx, hipStream_t st, const BowFrameSide &F, int n_kf, co
     }
     ((int *)&h[f_n])[0] = nf;
     if (fhost) {
-        for (int i = 0; i < nf; i++) if (F.h_node[i] < -1) return HVO_ERR_INVALID_ARG;
-        memcpy(&h[f_desc], F.h_desc, (size_t)nf * 32); memcpy(&h[f_node], F.h_node, (size_t)nf * 4);
-        if (F.h_angle) memcpy(&h[f_ang], F.h_angle, (size_t)nf * 4);
+        for (int i = 0; i < nf; i++) if (F->node_id[i] < -1) return HVO_ERR_INVALID_ARG;
+        memcpy(&h[f_desc], F->desc, (size_t)nf * 32); memcpy(&h[f_node], F->node_id, (size_t)nf * 4);
+        if (F->angle) memcpy(&h[f_ang], F->angle, (size_t)nf * 4);
     }
     if (hipMemcpyAsync(d, h.data(), up_end, hipMemcpyHostToDevice, st) != hipSuccess) return HVO_ERR_HIP;
     BowSideDev K; memset(&K, 0, sizeof(K));
@@ -549,8 +552,10 @@ int bow_search(hvo_ctx *ctx, hipStream_t st, const BowFrameSide &F, int n_kf, co
         A.f_desc = (const uint8_t *)(d + f_desc); A.f_angle = (const float *)(d + f_ang); A.f_angle_step = 1;
         A.f_fv_node = G.fv_node; A.f_fv_start = G.fv_start; A.f_fv_idx = G.fv_idx; A.f_n_rows = G.n_rows;
     } else {
-        A.f_desc = F.d_desc; A.f_angle = F.d_angle; A.f_angle_step = F.angle_step;
-        A.f_fv_node = F.d_fv_node; A.f_fv_start = F.d_fv_start; A.f_fv_idx = F.d_fv_idx; A.f_n_rows = F.d_n_rows;
+        BowLayout L; bow_layout(bow->cap, L);
+        A.f_desc = fr->desc; A.f_angle = &fr->kp->angle; A.f_angle_step = (int)(sizeof(hvo_keypoint) / sizeof(float));      // F.mvKeys[i].angle
+        A.f_fv_node = (const int *)(bow->d_blk + L.fv_node); A.f_fv_start = (const int *)(bow->d_blk + L.fv_start); A.f_fv_idx = (const int *)(bow->d_blk + L.fv_idx);
+        A.f_n_rows = (const int *)(bow->d_blk + L.counts) + 2;
     }
     A.nnratio = P->nnratio; A.check_orientation = P->check_orientation ? 1 : 0; A.th_low = P->th_low;
     A.match_kf = (int *)(d + r_match); A.n_matches = (int *)(d + r_n);
@@ -635,23 +640,20 @@ int hvo_compute_bow(hvo_ctx *ctx, const hvo_vocabulary *voc, int levelsup, int n
     std::vector<char> h(b_desc + b_n, 0);
     for (int f = 0; f < n_frames; f++) { if (n_desc[f]) memcpy(&h[(size_t)f * cap * 32], desc[f], (size_t)n_desc[f] * 32); ((int *)&h[b_desc])[f] = n_desc[f]; }
     HVO_HIP(hipMemcpyAsync(a, h.data(), h.size(), hipMemcpyHostToDevice, ctx->stream));
-    return bow_transform(ctx, ctx->stream, voc, levelsup, n_frames, (const uint8_t *)a, (size_t)cap * 32, (const int *)(a + b_desc), 1, cap, n_desc, &ctx->bow_call, false,
-                         out, &ctx->last_error);
+    FrameView zero; memset(&zero, 0, sizeof(zero));
+    std::vector<FrameView> F((size_t)n_frames, zero);
+    for (int f = 0; f < n_frames; f++) { F[f].desc = (const uint8_t *)a + (size_t)f * cap * 32; F[f].d_nkp = (const int *)(a + b_desc) + f; F[f].kp_cap = cap; F[f].n_kp = n_desc[f]; }
+    return bow_transform(ctx, ctx->stream, voc, levelsup, n_frames, F.data(), &ctx->bow_call, false, out, &ctx->last_error);
 }
 
 // on the first n frames of the resident batch: the descriptors where HVO_STAGE_ORB left them; the result stays with the batch
 int hvo_batch_compute_bow(hvo_ctx *ctx, const hvo_vocabulary *voc, int n, int levelsup, hvo_bow *out)
 {
     if (!ctx || !voc || !out || n < 1) return HVO_ERR_INVALID_ARG;
-    if (n > ctx->batch_n) { ctx->last_error = "bag of words: n beyond the resident batch"; return HVO_ERR_INVALID_ARG; }
-    if (!(ctx->last_stages & HVO_STAGE_ORB)) { ctx->last_error = "bag of words: the last hvo_batch_run must include HVO_STAGE_ORB"; return HVO_ERR_INVALID_ARG; }
+    std::vector<FrameView> F; int rc;
+    if ((rc = batch_views(ctx, n, need_bow, F))) return rc;
     if (voc->device != ctx->device) { ctx->last_error = "bag of words: the vocabulary lives on another device (or on none)"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    const OrbPlan &O = ctx->orb;
-    std::vector<int> nkp((size_t)n);
-    HVO_HIP(hipMemcpyAsync(nkp.data(), O.d_nkp, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HVO_HIP(hipStreamSynchronize(ctx->stream));
-    return bow_transform(ctx, ctx->stream, voc, levelsup, n, O.d_desc, (size_t)O.kp_cap * 32, O.d_nkp, 1, O.kp_cap, nkp.data(), &ctx->bow_batch, true, out, &ctx->last_error);
+    return bow_transform(ctx, ctx->stream, voc, levelsup, n, F.data(), &ctx->bow_batch, true, out, &ctx->last_error);
 }
 
 // ORBmatcher::SearchByBoW on host arrays for both sides: n_kf key frames against one frame in one launch
@@ -660,10 +662,8 @@ int hvo_search_by_bow(hvo_ctx *ctx, const hvo_bow_keyframe *frame, int n_kf, con
     if (!ctx || !frame || !kf || !params || !res || n_kf < 1 || frame->n < 0) return HVO_ERR_INVALID_ARG;
     if (frame->n > 0 && (!frame->desc || !frame->node_id || (params->check_orientation && !frame->angle))) return HVO_ERR_INVALID_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    BowFrameSide F; memset(&F, 0, sizeof(F));
-    F.n = frame->n; F.h_desc = frame->n ? frame->desc : nullptr; F.h_node = frame->node_id; F.h_angle = frame->angle;
     if (frame->n == 0) { for (int j = 0; j < n_kf; j++) { res[j].n_matches = 0; res[j].status = HVO_OK; } return HVO_OK; }
-    return bow_search(ctx, ctx->stream, F, n_kf, kf, params, res, &ctx->last_error);
+    return bow_search(ctx, ctx->stream, frame, nullptr, nullptr, n_kf, kf, params, res, &ctx->last_error);
 }
 
 // device time of the context's last ComputeBoW (ms2[0]: descent + assembly; 0 when the kept result was returned) and last SearchByBoW

@@ -404,6 +404,8 @@ void frame_gather_angles_enqueue(hipStream_t st, const hvo_keypoint *d_kp, const
 int frame_points_to_grid(hvo_ctx *ctx, const hvo_keypoint *kp_un, int n, const float *bounds4, int32_t *cell_start, int32_t *cell_items, int *n_out);
 int frame_lines_to_grid(hvo_ctx *ctx, const hvo_keyline *kl, int n, const float *bounds4, int32_t *cell_start, int32_t *cell_items, int cap, int *n_out);
 
+struct FrameView;                          // frame_view.hpp: one resident frame as the resident operations see it
+
 // api.hip: device buffer of at least `bytes` that lives as long as the context (grows by reallocation after draining the context's streams)
 void *hvo_call_arena(hvo_ctx *ctx, size_t bytes);
 
@@ -464,22 +466,20 @@ int pa_map_device(const hvo_plane_map *m);
 const char *pa_map_error(const hvo_plane_map *m);
 
 // local_lines.hip: SearchLocalLines + computeStructConstInMap of nframes frames against a resident line map, on stream st; it returns after
-// the stream has drained, with io / res (host, nframes entries) filled.  fr: every frame's frame side as device pointers (nt key lines;
-// n_items bounds the line grid's item list).  Tcw: host, nframes x 12.  bounds: the image bounds the line grids were built with.
-struct LlFrameDev { const hvo_keyline *kl; const double *fn; const hvo_line3d *l3d; const uint8_t *desc; const int32_t *cell_start, *cell_items; int n_items, nt; };
-int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_local_lines_params *P, const float bounds[4], int nframes,
-           const LlFrameDev *fr, const float *Tcw, hvo_local_lines_io *io, hvo_local_lines_result *res);
+// the stream has drained, with io / res (host, nframes entries) filled.  fr: every frame's key lines, 3-D lines and line grid (n_kl key lines;
+// n_ln_items bounds the grid's item list; bounds: the image bounds the grids were built with).  Tcw: host, nframes x 12.
+int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_local_lines_params *P, int nframes,
+           const FrameView *fr, const float *Tcw, hvo_local_lines_io *io, hvo_local_lines_result *res);
 int ll_map_device(const hvo_line_map *m);
 const char *ll_map_error(const hvo_line_map *m);
 
 // match.hip: the window kernel of SearchByProjection(F, vpMapPoints, th) (radius, band [level - 1, level]); local_points.hip launches it too
 __global__ void k_track_windows(int n, const int *level, const float *view_cos, float th, int bfactor, ProjDev P, float *q_radius, int *q_min, int *q_max);
 // local_points.hip: SearchLocalPoints of nframes frames against a resident point map, on stream st; it returns after the stream has drained,
-// with io / res (host, nframes entries) filled.  fr: every frame's frame side as device pointers (nt features; uright null: no stereo gate;
-// depth set: mvuRight is formed from it first, like k_stereo_from_rgbd with mvKeysUn = mvKeys).  sf: mvScaleFactors (HVO_MAX_LEVELS entries).
-struct LpFrameDev { const hvo_keypoint *kp_un; const float *uright; const uint8_t *desc; int nt; const uint16_t *depth; int pitch, w, h; float dfac; };
-int lp_run(hipStream_t st, hvo_point_map *m, const hvo_camera *cam, const hvo_local_points_params *P, const float bounds[4], const float *sf, int nframes,
-           const LpFrameDev *fr, const float *Tcw, hvo_local_points_io *io, hvo_local_points_result *res);
+// with io / res (host, nframes entries) filled.  fr: every frame's key points (n_kp features; uright null: no stereo gate; depth set:
+// mvuRight is formed from it first, like k_stereo_from_rgbd with mvKeysUn = mvKeys), with the image bounds and mvScaleFactors.
+int lp_run(hipStream_t st, hvo_point_map *m, const hvo_camera *cam, const hvo_local_points_params *P, int nframes,
+           const FrameView *fr, const float *Tcw, hvo_local_points_io *io, hvo_local_points_result *res);
 int lp_map_device(const hvo_point_map *m);
 const char *lp_map_error(const hvo_point_map *m);
 
@@ -490,38 +490,33 @@ void bow_layout(int cap, BowLayout &L);
 void bow_state_free(BowState *b);
 int bow_voc_device(const hvo_vocabulary *v);
 unsigned long long bow_voc_uid(const hvo_vocabulary *v);
-// ComputeBoW of nframes frames on stream st: frame f's descriptors at d_desc + f * desc_stride, its count at d_n[f * n_stride] (h_n: the same
-// counts on the host), blocks of `cap` features kept in *keep.  may_keep: a call with the vocabulary and levelsup the kept result was made
-// with launches nothing.  Returns after the stream has drained, out[f] filled.
-int bow_transform(hvo_ctx *ctx, hipStream_t st, const hvo_vocabulary *v, int levelsup, int nframes, const uint8_t *d_desc, size_t desc_stride,
-                  const int *d_n, int n_stride, int cap, const int *h_n, BowState *keep, bool may_keep, hvo_bow *out, std::string *err);
-// SearchByBoW's frame side: host arrays (h_desc set) or a resident frame's descriptors, angles and the FeatureVector rows of its block
-struct BowFrameSide { int n; const uint8_t *h_desc; const int32_t *h_node; const float *h_angle;
-                      const uint8_t *d_desc; const float *d_angle; int angle_step; const int *d_fv_node, *d_fv_start, *d_fv_idx, *d_n_rows; };
-int bow_search(hvo_ctx *ctx, hipStream_t st, const BowFrameSide &F, int n_kf, const hvo_bow_keyframe *kf, const hvo_bow_search_params *P,
-               hvo_bow_matches *res, std::string *err);
+// ComputeBoW of nframes frames on stream st: fr[f]'s descriptors (desc, d_nkp and the host count n_kp; the frames lie a fixed stride apart:
+// one launch walks them), blocks of fr[0].kp_cap features kept in *keep.  may_keep: a call with the vocabulary and levelsup the kept result was
+// made with launches nothing.  Returns after the stream has drained, out[f] filled.
+int bow_transform(hvo_ctx *ctx, hipStream_t st, const hvo_vocabulary *v, int levelsup, int nframes, const FrameView *fr, BowState *keep, bool may_keep,
+                  hvo_bow *out, std::string *err);
+// SearchByBoW's frame side: host arrays (F: desc, node_id, angle), or a resident frame's descriptors and mvKeys angles (fr) with the FeatureVector rows of its block (bow)
+int bow_search(hvo_ctx *ctx, hipStream_t st, const hvo_bow_keyframe *F, const FrameView *fr, const BowState *bow, int n_kf, const hvo_bow_keyframe *kf,
+               const hvo_bow_search_params *P, hvo_bow_matches *res, std::string *err);
 
-// pnp.hip: PnPsolver's RANSAC of n_kf candidates on stream st, scratch from ctx's call arena; returns after the stream has drained.  rsd null:
-// prob's host arrays go up; else the frame side is the resident frame's undistorted key points (nf of them; sigma2 = mvLevelSigma2) and
+// pnp.hip: PnPsolver's RANSAC of n_kf candidates on stream st, scratch from ctx's call arena; returns after the stream has drained.  fr null:
+// prob's host arrays go up; else the frame side is the resident frame's undistorted key points (n_kp of them, mvLevelSigma2 of ctx) and
 // the constructor's compaction runs on the device over kf[j]'s map side.
-struct PnpResident { const hvo_keypoint *d_kp_un; int nf; float sigma2[HVO_MAX_LEVELS]; const hvo_pnp_keyframe_side *kf; };
-int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_params *P, int n_kf, const hvo_pnp_problem *prob, const PnpResident *rsd,
-            hvo_pnp_result *res, std::string *err);
+int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_params *P, int n_kf, const hvo_pnp_problem *prob, const FrameView *fr,
+            const hvo_pnp_keyframe_side *kf, hvo_pnp_result *res, std::string *err);
 
 // pose_opt.hip: Optimizer::PoseOptimization of n frames in one launch on stream st, scratch from ctx's call arena; returns after the stream
-// has drained.  rsd null: prob's frame-side host arrays go up too; else frame f's frame side is read at rsd[f]'s device pointers.
+// has drained.  fr null: prob's frame-side host arrays go up too; else frame f's frame side is read at fr[f]'s device pointers.
 // depth set (resident batch, which holds no mvuRight): uright is null and the kernel forms mvuRight from the depth image like k_stereo_from_rgbd.
-struct PoResident { const hvo_keypoint *kp_un; const float *uright; const double *linefn; const hvo_line3d *l3d; const hvo_plane_cloud *pclouds; const int *d_nkp, *d_nkl;
-                    const uint16_t *depth; int pitch, w, h; float dfac; };
-int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_plane_params *pp, const float *inv_level_sigma2,
-           int n, const hvo_pose_problem *prob, const PoResident *rsd, hvo_pose_result *res, const hvo_pose_flags *flags, std::string *err);
+// mvInvLevelSigma2 is ctx's.
+int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_plane_params *pp,
+           int n, const hvo_pose_problem *prob, const FrameView *fr, hvo_pose_result *res, const hvo_pose_flags *flags, std::string *err);
 
 // line_opt.hip: computeStructConstrains + LineOptStruct of n frames on stream st (one pair-pass launch, one optimisation launch), scratch from
-// ctx's call arena; returns after the stream has drained.  rsd null: prob's host arrays go up; else frame f reads (and part 2 rewrites A, B of)
-// the resident records at rsd[f].  n_lines[f] is the side of rel[f].
-struct LsResident { const double *linefn; hvo_line3d *l3d; const int *d_nkl; };
+// ctx's call arena; returns after the stream has drained.  fr null: prob's host arrays go up; else frame f reads (and part 2 rewrites A, B of)
+// the resident records at fr[f].  n_lines[f] is the side of rel[f].
 int ls_run(hvo_ctx *ctx, hipStream_t st, const hvo_line_struct_params *params, int n, const int32_t *n_lines, const hvo_line_struct_problem *prob,
-           const LsResident *rsd, int8_t *const *rel, double *const *l3d_out, hvo_line_opt_result *res, std::string *err);
+           const FrameView *fr, int8_t *const *rel, double *const *l3d_out, hvo_line_opt_result *res, std::string *err);
 
 // peac.hip
 struct PeacView { uint16_t *d_depth; int pitch; size_t dframe; int8_t *d_labels8; hvo_plane *d_planes; int *d_meta; int npix, max_planes; size_t lstride /* bytes between two frames' label images */; };

@@ -16,7 +16,7 @@
 // All arithmetic in double, uncontracted.  Readings (tests/line_opt_ref.py restates the same): a solve fails when a
 // pivot is exactly 0 or not finite, in any line's block; the step of a failed solve is taken as zero (the trial is rejected either way);
 // classification re-evaluates an edge at the end points of the round's last computeActiveErrors instead of storing _error.
-#include "hvo_internal.hpp"
+#include "frame_view.hpp"
 #include <math.h>
 #include <cmath>
 #include <string.h>
@@ -422,7 +422,7 @@ static size_t ls_al(size_t v) { return (v + 63) & ~(size_t)63; }
 //   [LsFrame x n | per frame: (host form) linefn, records | rel]  up to here the upload (rel only when the caller's is read)
 //   [per frame: rel | out6] [results]                              the download; then the kernel's own scratch (lev, est, trial, Hb, ent)
 int ls_run(hvo_ctx *ctx, hipStream_t st, const hvo_line_struct_params *params, int n, const int32_t *n_lines, const hvo_line_struct_problem *prob,
-           const LsResident *rsd, int8_t *const *rel, double *const *l3d_out, hvo_line_opt_result *res, std::string *err)
+           const FrameView *fr, int8_t *const *rel, double *const *l3d_out, hvo_line_opt_result *res, std::string *err)
 {
     hvo_line_struct_params P;
     if (params) P = *params; else hvo_line_struct_default_params(&P);
@@ -439,10 +439,10 @@ int ls_run(hvo_ctx *ctx, hipStream_t st, const hvo_line_struct_params *params, i
         if (c < 0) { *err = "line structure: n_lines < 0"; return HVO_ERR_INVALID_ARG; }
         if (c > LS_MAX_LINES) { *err = "line structure: at most 4096 lines per frame"; return HVO_ERR_UNSUPPORTED; }
         if (c && (!rel || !rel[f])) { *err = "line structure: rel is NULL"; return HVO_ERR_INVALID_ARG; }
-        if (c && !rsd && (!prob[f].lines3d || (part1 && !prob[f].linefn))) { *err = "line structure: a needed array is NULL"; return HVO_ERR_INVALID_ARG; }
+        if (c && !fr && (!prob[f].lines3d || (part1 && !prob[f].linefn))) { *err = "line structure: a needed array is NULL"; return HVO_ERR_INVALID_ARG; }
         cap_max = c > cap_max ? c : cap_max;
         O[f].fn = O[f].rec = 0;
-        if (!rsd) { O[f].fn = take((size_t)c * 24); O[f].rec = take((size_t)c * sizeof(hvo_line3d)); }
+        if (!fr) { O[f].fn = take((size_t)c * 24); O[f].rec = take((size_t)c * sizeof(hvo_line3d)); }
     }
     const size_t down0 = at;                                                 // rel is the first thing that comes down, and goes up when it is the caller's
     for (int f = 0; f < n; f++) O[f].rel = take((size_t)n_lines[f] * n_lines[f]);
@@ -462,7 +462,7 @@ int ls_run(hvo_ctx *ctx, hipStream_t st, const hvo_line_struct_params *params, i
         const size_t c = (size_t)n_lines[f];
         LsFrame &F = hf[f]; memset(&F, 0, sizeof(F));
         F.n_cap = (int)c;
-        if (rsd) { F.d_nkl = rsd[f].d_nkl; F.linefn = rsd[f].linefn; F.l3d = rsd[f].l3d; }
+        if (fr) { F.d_nkl = fr[f].d_nkl; F.linefn = fr[f].fn; F.l3d = fr[f].l3d; }
         else {
             if (c && prob[f].linefn) memcpy(h + O[f].fn, prob[f].linefn, c * 24);
             if (c) memcpy(h + O[f].rec, prob[f].lines3d, c * sizeof(hvo_line3d));

@@ -41,6 +41,7 @@
 //   rotCW                        Rcw converted to double times the double line equation, sums left to right (it multiplies by Rcw, as written)
 // No contraction (-ffp-contract=off, __f*_rn).  The predicted level is reported and never read.
 #include "slot_map.hpp"
+#include "frame_view.hpp"
 #include <math.h>
 #include <string.h>
 #include <string>
@@ -267,20 +268,21 @@ static void ll_kinv(const hvo_camera *cam, float Ki[9])
 int ll_map_device(const hvo_line_map *m) { return m->device; }
 const char *ll_map_error(const hvo_line_map *m) { return m->last_error.c_str(); }
 
-int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_local_lines_params *P, const float bounds[4], int nframes,
-           const LlFrameDev *fr, const float *Tcw, hvo_local_lines_io *io, hvo_local_lines_result *res)
+int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_local_lines_params *P, int nframes,
+           const FrameView *fr, const float *Tcw, hvo_local_lines_io *io, hvo_local_lines_result *res)
 {
     const int ns = m->n_slots, nblocks = std::max(1, (ns + LL_BLOCK - 1) / LL_BLOCK), capq = std::max(1, std::min(ns, LSBP_MAP_MAXQ));
+    const float *bounds = fr[0].bounds;                           // one call's frames share their geometry
     std::vector<SmFrame> S(nframes);
     int rc;
     for (int f = 0; f < nframes; f++) {
         memset(&res[f], 0, sizeof(res[f]));
-        if (fr[f].nt > 2048) { m->last_error = match_lsbp_map_limit_text(0, fr[f].nt); res[f].status = HVO_ERR_UNSUPPORTED; return HVO_ERR_UNSUPPORTED; }
-        if (fr[f].nt > io[f].n_kl) { m->last_error = "local lines: held is shorter than the frame's key-line count"; return HVO_ERR_INVALID_ARG; }
-        if ((fr[f].nt > 0 && (!io[f].held || !io[f].n_par || !io[f].n_perp)) || !io[f].in_view_slot || io[f].n_seen_extra < 0 || (io[f].n_seen_extra > 0 && !io[f].seen_extra)) {
+        if (fr[f].n_kl > 2048) { m->last_error = match_lsbp_map_limit_text(0, fr[f].n_kl); res[f].status = HVO_ERR_UNSUPPORTED; return HVO_ERR_UNSUPPORTED; }
+        if (fr[f].n_kl > io[f].n_kl) { m->last_error = "local lines: held is shorter than the frame's key-line count"; return HVO_ERR_INVALID_ARG; }
+        if ((fr[f].n_kl > 0 && (!io[f].held || !io[f].n_par || !io[f].n_perp)) || !io[f].in_view_slot || io[f].n_seen_extra < 0 || (io[f].n_seen_extra > 0 && !io[f].seen_extra)) {
             m->last_error = "local lines: held, n_par, n_perp or in_view_slot missing"; return HVO_ERR_INVALID_ARG;
         }
-        S[f] = SmFrame{ fr[f].nt, io[f].n_seen_extra, io[f].held, io[f].seen_extra };
+        S[f] = SmFrame{ fr[f].n_kl, io[f].n_seen_extra, io[f].held, io[f].seen_extra };
         if ((rc = sm_check_seen(m, "local lines", "held names a slot beyond the map", INT32_MIN, S[f]))) return rc;
     }
     // ---- scratch A: everything whose size is known before the in-view counts ----
@@ -293,7 +295,7 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
     const size_t o_mi = C.take(F * capq * 4), o_md = C.take(F * capq * 4);
     std::vector<size_t> o_np(F), o_nq(F), o_k(F);
     for (int f = 0; f < nframes; f++) {
-        const size_t nt = (size_t)std::max(fr[f].nt, 1);
+        const size_t nt = (size_t)std::max(fr[f].n_kl, 1);
         sm_carve_frame(C, S[f]);
         o_np[f] = C.take(nt * 4); o_nq[f] = C.take(nt * 4); o_k[f] = C.take(2 * 4);        // n_matches, n_gated
     }
@@ -301,8 +303,8 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
     char *A = m->d_a;
     if ((rc = sm_stage_in(m, st, A, o_pose, o_seen, o_cnt, S, Tcw))) return rc;
     for (int f = 0; f < nframes; f++) {
-        SM_HIP(hipMemsetAsync(A + o_np[f], 0, (size_t)std::max(fr[f].nt, 1) * 4, st));
-        SM_HIP(hipMemsetAsync(A + o_nq[f], 0, (size_t)std::max(fr[f].nt, 1) * 4, st));
+        SM_HIP(hipMemsetAsync(A + o_np[f], 0, (size_t)std::max(fr[f].n_kl, 1) * 4, st));
+        SM_HIP(hipMemsetAsync(A + o_nq[f], 0, (size_t)std::max(fr[f].n_kl, 1) * 4, st));
         SM_HIP(hipMemsetAsync(A + o_k[f], 0, 8, st));
     }
     if ((rc = sm_mark(m, st, A, o_seen, S, 0))) return rc;
@@ -327,17 +329,17 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
     for (int f = 0; f < nframes; f++) {
         res[f].n_slots_tested = cnt[nframes + f]; res[f].n_in_view = cnt[f];
         if (cnt[f] > LSBP_MAP_MAXQ) {                              // refused whole: nothing of the caller's is written
-            res[f].status = HVO_ERR_UNSUPPORTED; m->last_error = match_lsbp_map_limit_text(cnt[f], fr[f].nt); return HVO_ERR_UNSUPPORTED;
+            res[f].status = HVO_ERR_UNSUPPORTED; m->last_error = match_lsbp_map_limit_text(cnt[f], fr[f].n_kl); return HVO_ERR_UNSUPPORTED;
         }
-        if (cnt[f] > 0 && fr[f].nt > 0) sb = std::max(sb, match_lsbp_map_scratch_bytes(cnt[f], fr[f].nt));
-        if (io[f].rel_map) rb = std::max(rb, sm_al((size_t)cnt[f] * (size_t)fr[f].nt));
+        if (cnt[f] > 0 && fr[f].n_kl > 0) sb = std::max(sb, match_lsbp_map_scratch_bytes(cnt[f], fr[f].n_kl));
+        if (io[f].rel_map) rb = std::max(rb, sm_al((size_t)cnt[f] * (size_t)fr[f].n_kl));
     }
     // ---- scratch B: the search's key rows and the relation matrix ----
     if ((rc = sm_grow(m, st, &m->d_b, &m->b_bytes, sm_al(sb) + F * rb + 256))) return rc;
     LlGate G;
     ll_kinv(cam, G.Ki);
     for (int f = 0; f < nframes; f++) {
-        const int nq = cnt[f], nt = fr[f].nt;
+        const int nq = cnt[f], nt = fr[f].n_kl;
         int32_t *d_mi = (int32_t *)(A + o_mi) + (size_t)f * capq, *d_md = (int32_t *)(A + o_md) + (size_t)f * capq;
         int *d_k = (int *)(A + o_k[f]);
         if (nq > 0) sm_fill_enqueue(st, nq, d_mi, d_md);
@@ -346,8 +348,8 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
             s.nq = nq; s.nt = nt;
             s.q_xyxy = a.q_xyxy + 4 * (size_t)f * capq; s.q_view_cos = a.q_vc + (size_t)f * capq; s.q_wvec = a.q_wvec + 3 * (size_t)f * capq;
             s.q_desc = a.q_desc + 32 * (size_t)f * capq; s.q_blocks = a.q_blocks + (size_t)f * capq;
-            s.t_kl = fr[f].kl; s.t_fn = fr[f].fn; s.t_l3d = fr[f].l3d; s.t_desc = fr[f].desc; s.t_occ = (const uint8_t *)(A + S[f].o_occ);
-            s.cell_start = fr[f].cell_start; s.cell_items = fr[f].cell_items; s.n_items = fr[f].n_items;
+            s.t_kl = fr[f].kl; s.t_fn = fr[f].fn; s.t_l3d = fr[f].l3d; s.t_desc = fr[f].ldesc; s.t_occ = (const uint8_t *)(A + S[f].o_occ);
+            s.cell_start = fr[f].ln_start; s.cell_items = fr[f].ln_items; s.n_items = fr[f].n_ln_items;
             s.mnMinX = bounds[0]; s.mnMaxX = bounds[1]; s.mnMinY = bounds[2]; s.mnMaxY = bounds[3]; s.th = P->th; s.nn_ratio = P->nn_ratio;
             s.cos_normal = cos(15.0 / 180.0 * M_PI);
             s.match_idx = d_mi; s.match_dist = d_md; s.n_matches = d_k;
@@ -356,7 +358,7 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
         if (f == nframes - 1) SM_HIP(hipEventRecord(m->ev[2], st));
     }
     for (int f = 0; f < nframes; f++) {
-        const int nq = cnt[f], nt = fr[f].nt;
+        const int nq = cnt[f], nt = fr[f].n_kl;
         if (nt < 1) continue;
         const float *T = Tcw + 12 * (size_t)f;
         for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) G.R[3 * r + c] = T[4 * r + c];
@@ -374,7 +376,7 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
     SM_HIP(hipEventRecord(m->ev[3], st));
     std::vector<int> kk(2 * F, 0);
     for (int f = 0; f < nframes; f++) {
-        const size_t nq = (size_t)cnt[f], nt = (size_t)fr[f].nt, q0 = (size_t)f * capq;
+        const size_t nq = (size_t)cnt[f], nt = (size_t)fr[f].n_kl, q0 = (size_t)f * capq;
         hvo_local_lines_io &I = io[f];
         SM_HIP(hipMemcpyAsync(&kk[2 * f], A + o_k[f], 8, hipMemcpyDeviceToHost, st));
         if (nt) {

@@ -37,6 +37,7 @@
 //                                [0, mnScaleLevels - 1] is part of the function.  The search reads the level (radius, band).
 // No contraction (-ffp-contract=off, __f*_rn).
 #include "slot_map.hpp"
+#include "frame_view.hpp"
 #include <math.h>
 #include <string.h>
 #include <string>
@@ -204,22 +205,23 @@ static std::string lp_limit_text(int nq, int nt)
            std::to_string(LP_MAXT) + "); nothing was written";
 }
 
-int lp_run(hipStream_t st, hvo_point_map *m, const hvo_camera *cam, const hvo_local_points_params *P, const float bounds[4], const float *sf, int nframes,
-           const LpFrameDev *fr, const float *Tcw, hvo_local_points_io *io, hvo_local_points_result *res)
+int lp_run(hipStream_t st, hvo_point_map *m, const hvo_camera *cam, const hvo_local_points_params *P, int nframes,
+           const FrameView *fr, const float *Tcw, hvo_local_points_io *io, hvo_local_points_result *res)
 {
     const int ns = m->n_slots, nblocks = std::max(1, (ns + LP_BLOCK - 1) / LP_BLOCK), capq = std::max(1, std::min(ns, LP_MAXQ));
+    const float *bounds = fr[0].bounds, *sf = fr[0].sf;           // one call's frames share their geometry and pyramid
     if (P->n_levels < 1 || P->n_levels > HVO_MAX_LEVELS) { m->last_error = "local points: n_levels outside 1 .. 16"; return HVO_ERR_INVALID_ARG; }
     if (!(bounds[1] > bounds[0]) || !(bounds[3] > bounds[2])) { m->last_error = "local points: empty image bounds"; return HVO_ERR_INVALID_ARG; }
     std::vector<SmFrame> S(nframes);
     int rc;
     for (int f = 0; f < nframes; f++) {
         memset(&res[f], 0, sizeof(res[f]));
-        if (fr[f].nt > LP_MAXT) { m->last_error = lp_limit_text(0, fr[f].nt); res[f].status = HVO_ERR_UNSUPPORTED; return HVO_ERR_UNSUPPORTED; }
-        if (fr[f].nt > io[f].n_kp) { m->last_error = "local points: held is shorter than the frame's key-point count"; return HVO_ERR_INVALID_ARG; }
-        if ((fr[f].nt > 0 && !io[f].held) || !io[f].in_view_slot || io[f].n_seen_extra < 0 || (io[f].n_seen_extra > 0 && !io[f].seen_extra)) {
+        if (fr[f].n_kp > LP_MAXT) { m->last_error = lp_limit_text(0, fr[f].n_kp); res[f].status = HVO_ERR_UNSUPPORTED; return HVO_ERR_UNSUPPORTED; }
+        if (fr[f].n_kp > io[f].n_kp) { m->last_error = "local points: held is shorter than the frame's key-point count"; return HVO_ERR_INVALID_ARG; }
+        if ((fr[f].n_kp > 0 && !io[f].held) || !io[f].in_view_slot || io[f].n_seen_extra < 0 || (io[f].n_seen_extra > 0 && !io[f].seen_extra)) {
             m->last_error = "local points: held or in_view_slot missing"; return HVO_ERR_INVALID_ARG;
         }
-        S[f] = SmFrame{ fr[f].nt, io[f].n_seen_extra, io[f].held, io[f].seen_extra };
+        S[f] = SmFrame{ fr[f].n_kp, io[f].n_seen_extra, io[f].held, io[f].seen_extra };
         if ((rc = sm_check_seen(m, "local points", "held names a slot beyond the map or an unknown value", HVO_HELD_FOREIGN_UNOBSERVED, S[f]))) return rc;
     }
     // ---- scratch A: everything whose size is known before the in-view counts ----
@@ -235,7 +237,7 @@ int lp_run(hipStream_t st, hvo_point_map *m, const hvo_camera *cam, const hvo_lo
     for (int f = 0; f < nframes; f++) {
         sm_carve_frame(C, S[f]);
         o_k[f] = C.take(4);                                        // n_matches
-        o_ur[f] = fr[f].depth ? C.take(2 * (size_t)std::max(fr[f].nt, 1) * 4) : 0;      // mvuRight, mvDepth formed from the depth image
+        o_ur[f] = fr[f].depth ? C.take(2 * (size_t)std::max(fr[f].n_kp, 1) * 4) : 0;      // mvuRight, mvDepth formed from the depth image
     }
     if ((rc = sm_grow(m, st, &m->d_a, &m->a_bytes, C.o))) return rc;
     char *A = m->d_a;
@@ -262,16 +264,16 @@ int lp_run(hipStream_t st, hvo_point_map *m, const hvo_camera *cam, const hvo_lo
     for (int f = 0; f < nframes; f++) {
         res[f].n_slots_tested = cnt[nframes + f]; res[f].n_in_view = cnt[f];
         if (cnt[f] > LP_MAXQ) {                                    // refused whole: nothing of the caller's is written
-            res[f].status = HVO_ERR_UNSUPPORTED; m->last_error = lp_limit_text(cnt[f], fr[f].nt); return HVO_ERR_UNSUPPORTED;
+            res[f].status = HVO_ERR_UNSUPPORTED; m->last_error = lp_limit_text(cnt[f], fr[f].n_kp); return HVO_ERR_UNSUPPORTED;
         }
-        if (cnt[f] > 0 && fr[f].nt > 0) sb = std::max(sb, match_sbp_scratch_bytes(cnt[f]));
+        if (cnt[f] > 0 && fr[f].n_kp > 0) sb = std::max(sb, match_sbp_scratch_bytes(cnt[f]));
     }
     // ---- scratch B: the search's key rows (the frames' searches run one after the other on the stream and share them) ----
     if ((rc = sm_grow(m, st, &m->d_b, &m->b_bytes, sm_al(sb) + 256))) return rc;
     ProjDev W; memset(&W, 0, sizeof(W));
     for (int l = 0; l < HVO_MAX_LEVELS; l++) W.sf[l] = sf[l];
     for (int f = 0; f < nframes; f++) {
-        const int nq = cnt[f], nt = fr[f].nt;
+        const int nq = cnt[f], nt = fr[f].n_kp;
         const size_t q0 = (size_t)f * capq;
         int32_t *d_mi = (int32_t *)(A + o_mi) + q0, *d_md = (int32_t *)(A + o_md) + q0;
         if (nq > 0 && nt > 0) {                                    // nToMatch > 0 (Tracking.cc:3266)
@@ -301,7 +303,7 @@ int lp_run(hipStream_t st, hvo_point_map *m, const hvo_camera *cam, const hvo_lo
     if (hipGetLastError() != hipSuccess) { m->last_error = "local points: search launch"; return HVO_ERR_HIP; }
     SM_HIP(hipEventRecord(m->ev[2], st));
     for (int f = 0; f < nframes; f++) {
-        const int nq = cnt[f], nt = fr[f].nt;
+        const int nq = cnt[f], nt = fr[f].n_kp;
         if (nt < 1 || nq < 1) continue;
         const size_t q0 = (size_t)f * capq;
         int *d_win = (int *)(A + S[f].o_win);
@@ -312,7 +314,7 @@ int lp_run(hipStream_t st, hvo_point_map *m, const hvo_camera *cam, const hvo_lo
     SM_HIP(hipEventRecord(m->ev[3], st));
     std::vector<int> kk(F, 0);
     for (int f = 0; f < nframes; f++) {
-        const size_t nq = (size_t)cnt[f], nt = (size_t)fr[f].nt, q0 = (size_t)f * capq;
+        const size_t nq = (size_t)cnt[f], nt = (size_t)fr[f].n_kp, q0 = (size_t)f * capq;
         hvo_local_points_io &I = io[f];
         SM_HIP(hipMemcpyAsync(&kk[f], A + o_k[f], 4, hipMemcpyDeviceToHost, st));
         if (nt && ns > 0) SM_HIP(hipMemcpyAsync(I.held, A + S[f].o_held, nt * 4, hipMemcpyDeviceToHost, st));

@@ -17,7 +17,7 @@
 // xorshift32 stream, state seed ^ (0x9E3779B9 * (j * 1024 + it)) (0 -> 0x6D2B79F5: the mixing of csrc/vps.hip), a draw from a set of size
 // s is x % s, and removal is the reference's swap-with-last (:199-200).  A hypothesis whose pose is not finite has count 0.
 // SetRansacParameters' log / pow / ceil run on the host (pnp_set_ransac below), so a restatement on the host calls the same libm.
-#include "hvo_internal.hpp"
+#include "frame_view.hpp"
 #include <string.h>
 #include <math.h>
 #include <algorithm>
@@ -277,10 +277,10 @@ static void pnp_ev_begin(hvo_ctx *ctx, hipStream_t st)
     ctx->pnp_ev_on = hipEventRecord(ctx->pnp_ev[0], st) == hipSuccess;
 }
 
-// rsd null: prob's host arrays go up.  Else the frame side is the resident frame's key points at rsd->d_kp_un, rsd->kf[j]'s map side goes up,
+// fr null: prob's host arrays go up.  Else the frame side is the resident frame's key points at fr->kp_un, kf[j]'s map side goes up,
 // N[j] is counted on the host (SetRansacParameters needs it before the launch) and k_pnp_gather compacts on the device.
-int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_params *P, int n_kf, const hvo_pnp_problem *prob, const PnpResident *rsd,
-            hvo_pnp_result *res, std::string *err)
+int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_params *P, int n_kf, const hvo_pnp_problem *prob, const FrameView *fr,
+            const hvo_pnp_keyframe_side *kf, hvo_pnp_result *res, std::string *err)
 {
     if (P->min_set < 4) { *err = "pnp: min_set below 4"; return HVO_ERR_INVALID_ARG; }
     if (P->min_set > PNP_MAX_SET || n_kf > PNP_MAX_KF) { *err = "pnp: min_set above 64 or more than 256 candidates"; return HVO_ERR_UNSUPPORTED; }
@@ -294,12 +294,12 @@ int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_p
     int capN = 1, Tcap = 0, capF = 1, capK = 1;
     for (int j = 0; j < n_kf; j++) {
         int N, nfeat;
-        if (rsd) {
-            const hvo_pnp_keyframe_side &K = rsd->kf[j];
-            if (K.n < 0 || (K.n > 0 && (!K.pos || !K.bad)) || (rsd->nf > 0 && !K.match_kf)) { *err = "pnp: a key-frame side with n < 0 or a null array"; return HVO_ERR_INVALID_ARG; }
+        if (fr) {
+            const hvo_pnp_keyframe_side &K = kf[j];
+            if (K.n < 0 || (K.n > 0 && (!K.pos || !K.bad)) || (fr->n_kp > 0 && !K.match_kf)) { *err = "pnp: a key-frame side with n < 0 or a null array"; return HVO_ERR_INVALID_ARG; }
             N = 0;
-            for (int i = 0; i < rsd->nf; i++) { const int m = K.match_kf[i]; if (m >= 0 && m < K.n && !K.bad[m]) N++; }
-            nfeat = rsd->nf; capK = std::max(capK, (int)K.n);
+            for (int i = 0; i < fr->n_kp; i++) { const int m = K.match_kf[i]; if (m >= 0 && m < K.n && !K.bad[m]) N++; }
+            nfeat = fr->n_kp; capK = std::max(capK, (int)K.n);
         } else {
             const hvo_pnp_problem &Q = prob[j];
             if (Q.n < 0 || Q.n_features < 0 || (Q.n > 0 && (!Q.p3d || !Q.p2d || !Q.sigma2 || !Q.feature_index))) { *err = "pnp: a problem with n < 0, n_features < 0 or a null array"; return HVO_ERR_INVALID_ARG; }
@@ -327,8 +327,8 @@ int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_p
     const size_t a_cand = carve((size_t)n_kf * sizeof(PnpCand));
     const size_t a_p3d = carve((size_t)n_kf * capN * 12), a_p2d = carve((size_t)n_kf * capN * 8), a_me = carve((size_t)n_kf * capN * 4), a_fi = carve((size_t)n_kf * capN * 4);
     const size_t up_host = o;                                    // the host form uploads [0, up_host)
-    const size_t g_match = carve(rsd ? (size_t)n_kf * std::max(rsd->nf, 1) * 4 : 0), g_pos = carve(rsd ? (size_t)n_kf * capK * 12 : 0),
-                 g_bad = carve(rsd ? (size_t)n_kf * capK : 0), g_n = carve(rsd ? (size_t)n_kf * 4 : 0);
+    const size_t g_match = carve(fr ? (size_t)n_kf * std::max(fr->n_kp, 1) * 4 : 0), g_pos = carve(fr ? (size_t)n_kf * capK * 12 : 0),
+                 g_bad = carve(fr ? (size_t)n_kf * capK : 0), g_n = carve(fr ? (size_t)n_kf * 4 : 0);
     const size_t up_end = o;
     const size_t r0 = o;
     const size_t a_inl = carve((size_t)n_kf * Tc * 4), a_rec = carve((size_t)n_kf * Tc * 4), a_evt = carve((size_t)n_kf * Tc * 4), a_pose = carve((size_t)n_kf * Tc * 48),
@@ -344,16 +344,16 @@ int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_p
     std::vector<char> h(up_end, 0);
     memcpy(&h[a_cand], cand.data(), (size_t)n_kf * sizeof(PnpCand));
     PnpGather G; memset(&G, 0, sizeof(G));
-    if (rsd) {
+    if (fr) {
         for (int j = 0; j < n_kf; j++) {
-            const hvo_pnp_keyframe_side &K = rsd->kf[j];
-            if (rsd->nf) memcpy(&h[g_match + (size_t)j * rsd->nf * 4], K.match_kf, (size_t)rsd->nf * 4);
+            const hvo_pnp_keyframe_side &K = kf[j];
+            if (fr->n_kp) memcpy(&h[g_match + (size_t)j * fr->n_kp * 4], K.match_kf, (size_t)fr->n_kp * 4);
             if (K.n) { memcpy(&h[g_pos + (size_t)j * capK * 12], K.pos, (size_t)K.n * 12); memcpy(&h[g_bad + (size_t)j * capK], K.bad, (size_t)K.n); }
             ((int *)&h[g_n])[j] = K.n;
         }
-        G.kp_un = rsd->d_kp_un; G.match = (const int *)(d + g_match); G.kf_pos = (const float *)(d + g_pos); G.kf_bad = (const uint8_t *)(d + g_bad);
-        G.kf_n = (const int *)(d + g_n); G.nf = rsd->nf; G.capK = capK; G.th2 = P->th2;
-        for (int i = 0; i < HVO_MAX_LEVELS; i++) G.sigma2[i] = rsd->sigma2[i];
+        G.kp_un = fr->kp_un; G.match = (const int *)(d + g_match); G.kf_pos = (const float *)(d + g_pos); G.kf_bad = (const uint8_t *)(d + g_bad);
+        G.kf_n = (const int *)(d + g_n); G.nf = fr->n_kp; G.capK = capK; G.th2 = P->th2;
+        frame_level_sigma2(ctx, G.sigma2, nullptr);
         if (hipMemcpyAsync(d + a_cand, &h[a_cand], pal((size_t)n_kf * sizeof(PnpCand)), hipMemcpyHostToDevice, st) != hipSuccess ||
             hipMemcpyAsync(d + up_host, &h[up_host], up_end - up_host, hipMemcpyHostToDevice, st) != hipSuccess) return HVO_ERR_HIP;
     } else {
@@ -376,7 +376,7 @@ int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_p
     D.idx = (int *)(d + a_idx); D.ref_cnt = (int *)(d + a_rcnt); D.ref_pose = (float *)(d + a_rpose); D.ref_mask = (uint8_t *)(d + a_rmask);
     D.ev_inl = (uint8_t *)(d + a_evin); D.ev_hinl = (uint8_t *)(d + a_evh); D.best_inl = (uint8_t *)(d + a_bin);
     if (hipMemsetAsync(d + r0, 0, r1 - r0, st) != hipSuccess) return HVO_ERR_HIP;
-    if (rsd && rsd->nf > 0) hipLaunchKernelGGL(k_pnp_gather, dim3(n_kf), dim3(256), 0, st, G, capN, (float *)(d + a_p3d), (float *)(d + a_p2d), (float *)(d + a_me), (int *)(d + a_fi));
+    if (fr && fr->n_kp > 0) hipLaunchKernelGGL(k_pnp_gather, dim3(n_kf), dim3(256), 0, st, G, capN, (float *)(d + a_p3d), (float *)(d + a_p2d), (float *)(d + a_me), (int *)(d + a_fi));
     pnp_ev_begin(ctx, st);
     if (Tcap > 0) {
         const size_t dyn = 2 * ms > PNP_SEQ_ROWS ? (size_t)4 * PNP_TREE_BATCH * 256 * sizeof(double) : 0;
@@ -447,7 +447,7 @@ int hvo_pnp_ransac(hvo_ctx *ctx, const hvo_camera *cam, const hvo_pnp_params *pa
     if (!ctx) return HVO_ERR_INVALID_ARG;
     if (!cam || !params || !problems || !results || n_kf < 1) { ctx->last_error = "pnp: a null argument or n_kf < 1"; return HVO_ERR_INVALID_ARG; }
     if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    return pnp_run(ctx, ctx->stream, cam, params, n_kf, problems, nullptr, results, &ctx->last_error);
+    return pnp_run(ctx, ctx->stream, cam, params, n_kf, problems, nullptr, nullptr, results, &ctx->last_error);
 }
 
 int hvo_pnp_last_kernel_ms(const hvo_ctx *ctx, float ms2[2])

@@ -18,7 +18,7 @@
 // keeps a stale or uninitialised _error -- and flags the edge when a round's classification reads that evaluation; classification
 // re-evaluates an unflagged edge at the pose of the round's last computeActiveErrors (the last trial, accepted or not) instead of storing
 // _error per edge.  The host and stream forms launch this kernel alone on the same bytes, so they give bit-identical results.
-#include "hvo_internal.hpp"
+#include "frame_view.hpp"
 #include <math.h>
 #include <cmath>
 #include <string.h>
@@ -640,8 +640,8 @@ static void po_flag_layout(const hvo_pose_problem &p, size_t &total, size_t fo[4
 
 // One pinned staging block of the context (grow-only, hvo_stage_host) holds the upload and receives the download; the device side is the
 // context's call arena: nothing is allocated by a call once both have grown.
-int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_plane_params *pp, const float *inv_level_sigma2,
-           int n, const hvo_pose_problem *prob, const PoResident *rsd, hvo_pose_result *res, const hvo_pose_flags *flags, std::string *err)
+int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_plane_params *pp,
+           int n, const hvo_pose_problem *prob, const FrameView *fr, hvo_pose_result *res, const hvo_pose_flags *flags, std::string *err)
 {
     if (!pp) pp = &k_po_default_pp;
     size_t up = po_al((size_t)n * sizeof(PoFrame));
@@ -651,9 +651,9 @@ int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_p
             *err = "pose optimisation: at most 8192 points, 4096 lines and 64 planes per frame"; return HVO_ERR_UNSUPPORTED;
         }
         for (int i = 0; i < 12; i++) if (!std::isfinite(p.Tcw[i])) { *err = "pose optimisation: the initial pose is not finite"; return HVO_ERR_INVALID_ARG; }
-        const bool r = rsd != nullptr;
+        const bool r = fr != nullptr;
         const bool planes_ok = p.plane_map ? (p.slot_match || p.slot_parallel || p.slot_vertical) : (p.pl_has && p.pl_coef_w);
-        if ((p.n_points && (!p.pt_has || !p.pt_xyz || (!r && !p.kp_un) || (!r && !p.inv_sigma2 && !inv_level_sigma2))) ||
+        if ((p.n_points && (!p.pt_has || !p.pt_xyz || (!r && !p.kp_un))) ||
             (p.n_lines && (!p.ln_has || !p.ln_xyz || (!r && (!p.linefn || !p.lines3d)))) ||
             (p.n_planes && (!planes_ok || (!r && !p.plane_coef)))) { *err = "pose optimisation: a needed array is NULL"; return HVO_ERR_INVALID_ARG;
         }
@@ -670,7 +670,7 @@ int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_p
     size_t at_up = po_al((size_t)n * sizeof(PoFrame)), at_fl = down0;
     for (int f = 0; f < n; f++) {
         const hvo_pose_problem &p = prob[f];
-        PoLayout L; po_layout(p, rsd != nullptr, at_up, L);
+        PoLayout L; po_layout(p, fr != nullptr, at_up, L);
         size_t fo[4]; po_flag_layout(p, at_fl, fo);
         const size_t *o = L.o;
         const size_t np = (size_t)p.n_points, nl = (size_t)p.n_lines, m = (size_t)p.n_planes;
@@ -695,9 +695,9 @@ int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_p
         } else {
             F.pl_has = (const uint8_t *)put(o[4], p.pl_has, m * 3); F.pl_map = (const float *)put(o[5], p.pl_coef_w, m * 48);
         }
-        if (rsd) {
-            const PoResident &R = rsd[f];
-            F.kp_un = R.kp_un; F.uright = R.uright; F.inv_sigma2 = nullptr; F.linefn = R.linefn; F.l3d = R.l3d; F.pclouds = R.pclouds;
+        if (fr) {
+            const FrameView &R = fr[f];
+            F.kp_un = R.kp_un; F.uright = R.uright; F.inv_sigma2 = nullptr; F.linefn = R.fn; F.l3d = R.l3d; F.pclouds = R.pclouds;
             F.planes_from_tail = 1; F.d_nkp = R.d_nkp; F.d_nkl = R.d_nkl;
             F.depth = R.depth; F.pitch = R.pitch; F.w = R.w; F.h = R.h; F.dfac = R.dfac; F.bf32 = cam->bf;
         } else {
@@ -717,7 +717,7 @@ int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_p
     A.chi_plane = pp->chi; A.chi_vp = pp->vp_chi;
     A.d_mono = (double)(float)sqrt(5.991); A.d_stereo = (double)(float)sqrt(7.815); A.d_line = (double)(float)sqrt(3.84);     // Optimizer.cc:631-633
     A.d_plane = (double)(float)sqrt(pp->chi); A.d_vpl = (double)(float)sqrt(pp->vp_chi);                                      // :963, :966
-    for (int i = 0; i < HVO_MAX_LEVELS; i++) A.inv_level_sigma2[i] = inv_level_sigma2 ? inv_level_sigma2[i] : 1.f;
+    frame_level_sigma2(ctx, nullptr, A.inv_level_sigma2);
 #define PO_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *err = std::string(#call) + ": " + hipGetErrorString(e_); return HVO_ERR_HIP; } } while (0)
     if (!ctx->po_ev[0]) { PO_HIP(hipEventCreate(&ctx->po_ev[0])); PO_HIP(hipEventCreate(&ctx->po_ev[1])); }
     PO_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, st));

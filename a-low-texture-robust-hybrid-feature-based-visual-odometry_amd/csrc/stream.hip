@@ -12,57 +12,11 @@
 // every kernel and the result downloads, and returns; hvo_stream_collect waits for that frame's events and hands the
 // results out.  Nothing is allocated and no stream is drained on the submit path.  The matching calls take device-resident
 // descriptors, undistorted key points and mvuRight of the two frames (nothing but the per-query projections crosses PCIe).
-#include "hvo_internal.hpp"
+#include "frame_view.hpp"
 #include <string.h>
 #include <algorithm>
 #include <new>
 #include <vector>
-
-#define ST_MAX_DEPTH 16
-
-struct StreamSlot {
-    hvo_ctx *ctx = nullptr;
-    PeacView pv; LsdView lv;
-    // pinned host
-    uint8_t *h_gray = nullptr; uint16_t *h_depth = nullptr;
-    char *h_out = nullptr;
-    // device extras
-    hvo_keypoint *d_kp_un = nullptr; float *d_uright = nullptr, *d_zdepth = nullptr;
-    char *d_tail = nullptr, *d_tail_scratch = nullptr, *h_tail = nullptr;     // the Frame tail's result block (HBM + pinned copy) and scratch (tail.hip)
-    hipEvent_t ev_gray = nullptr, ev_depth = nullptr, ev_orb = nullptr, ev_lsd = nullptr, ev_peac = nullptr;
-    hipEvent_t ev_kern[3] = { nullptr, nullptr, nullptr };      // kernels done (before the downloads), per subsystem: latency accounting
-    hipEvent_t ev_t0 = nullptr;
-    int64_t ticket = -1; bool busy = false, had_depth = false;
-    bool line_opt_done = false;            // hvo_stream_line_struct_optimize has rewritten this frame's 3-D lines
-    BowState bow;                          // the frame's bag of words (hvo_stream_compute_bow), dropped when the slot takes its next frame
-};
-
-// layout of a slot's pinned result block
-struct OutLayout {
-    size_t counts, kp, desc, kp_un, uright, zdepth, kl, ldesc, fn, planes, labels, total;
-};
-
-struct hvo_stream {
-    hvo_params p; hvo_stream_params sp;
-    int depth = 0, w = 0, h = 0, kp_cap = 0, nfeat = 0;
-    bool culled = false;
-    StreamSlot slot[ST_MAX_DEPTH];
-    OutLayout lay;
-    int64_t next = 0;
-    TailLayout tl; unsigned tail_stages = 0; double tail_dist_th = 0.05, tail_vp_th = 1.0 / 180.0 * 3.1415926535897932384626433832795;
-    float bounds[4];                       // mnMinX, mnMaxX, mnMinY, mnMaxY (Frame::ComputeImageBounds)
-    const float *bounds4() const { return bounds; }
-    // matching scratch (device + pinned), sized for kp_cap queries
-    char *d_ms = nullptr, *h_ms = nullptr; size_t ms_bytes = 0;
-    // the local-map line search's scratch (hvo_stream_search_lines_by_projection_map): allocated on its first call, grow-only
-    char *d_lm = nullptr, *h_lm = nullptr; size_t lm_dbytes = 0, lm_hbytes = 0;
-    // Manhattan tracking's result block (hvo_stream_track_manhattan): allocated on its first call, grow-only
-    char *d_mf = nullptr, *h_mf = nullptr; size_t mf_bytes = 0;
-    hipStream_t s_match = nullptr;         // the matching calls run here, behind the two frames' events (not behind a frame's line chain)
-    std::string last_error;
-};
-
-#define ST_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { s->last_error = std::string(#call) + ": " + hipGetErrorString(e_); return HVO_ERR_HIP; } } while (0)
 
 static size_t al64(size_t v) { return (v + 63) & ~(size_t)63; }
 
@@ -334,13 +288,6 @@ static int stream_submit_enqueue(hvo_stream *s, StreamSlot &S, const uint8_t *gr
     return HVO_OK;
 }
 
-static StreamSlot *slot_of(hvo_stream *s, int64_t ticket)
-{
-    if (ticket < 0 || ticket >= s->next || ticket < s->next - s->depth) return nullptr;
-    StreamSlot &S = s->slot[ticket % s->depth];
-    return S.ticket == ticket ? &S : nullptr;
-}
-
 // 0: not finished, 1: every stage of that frame (and its downloads) is complete
 int hvo_stream_poll(hvo_stream *s, int64_t ticket)
 {
@@ -441,21 +388,14 @@ int hvo_stream_stage_ms(hvo_stream *s, int64_t ticket, float ms3[3])
     return HVO_OK;
 }
 
-// Frame::ComputeBoW (src/Frame.cc:1692-1699) on a resident frame: the ORB descriptors where the extractor left them (bow.hip)
+// Frame::ComputeBoW (src/Frame.cc:1692-1699) on a resident frame (bow.hip); the result stays with the frame's slot
 int hvo_stream_compute_bow(hvo_stream *s, int64_t ticket, const hvo_vocabulary *voc, int levelsup, hvo_bow *out)
 {
     if (!s || !voc || !out) return HVO_ERR_INVALID_ARG;
-    if (!(s->sp.stages & HVO_STAGE_ORB)) { s->last_error = "bag of words: the stream must run HVO_STAGE_ORB"; return HVO_ERR_INVALID_ARG; }
-    StreamSlot *C = slot_of(s, ticket);
-    if (!C) return HVO_ERR_INVALID_ARG;
+    FrameView C; int rc;
+    if ((rc = stream_view(s, ticket, need_bow, s->s_match, C))) return rc;
     if (bow_voc_device(voc) != s->p.device) { s->last_error = "bag of words: the vocabulary lives on another device (or on none)"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    hipStream_t st = s->s_match;
-    ST_HIP(hipStreamWaitEvent(st, C->ev_orb, 0));
-    ST_HIP(hipEventSynchronize(C->ev_orb));                    // the key-point count arrived with the frame's download
-    const int n = ((const int *)(C->h_out + s->lay.counts))[0];
-    const OrbPlan &O = C->ctx->orb;
-    return bow_transform(C->ctx, st, voc, levelsup, 1, O.d_desc, 0, O.d_nkp, 0, s->kp_cap, &n, &C->bow, true, out, &s->last_error);
+    return bow_transform(C.ctx, s->s_match, voc, levelsup, 1, &C, &slot_of(s, ticket)->bow, true, out, &s->last_error);
 }
 
 // ORBmatcher::SearchByBoW(pKF, F, ...) (src/ORBmatcher.cc:162-293) of n_kf key frames against the resident frame `cur`
@@ -463,29 +403,29 @@ int hvo_stream_search_by_bow(hvo_stream *s, int64_t cur, const hvo_vocabulary *v
                              hvo_bow_matches *res)
 {
     if (!s || !voc || !kf || !params || !res || n_kf < 1) return HVO_ERR_INVALID_ARG;
-    StreamSlot *C = slot_of(s, cur);
-    if (!C) return HVO_ERR_INVALID_ARG;
-    if (!C->bow.valid || C->bow.voc_uid != bow_voc_uid(voc)) {
+    const StreamSlot *B = slot_of(s, cur);
+    if (B && (!B->bow.valid || B->bow.voc_uid != bow_voc_uid(voc))) {
         s->last_error = "search by bag of words: the frame holds no bag of words of this vocabulary (hvo_stream_compute_bow first)"; return HVO_ERR_INVALID_ARG;
     }
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    ST_HIP(hipEventSynchronize(C->ev_orb));
-    BowLayout L; bow_layout(C->bow.cap, L);
-    BowFrameSide F; memset(&F, 0, sizeof(F));
-    F.n = std::max(0, std::min(((const int *)(C->h_out + s->lay.counts))[0], s->kp_cap));
-    const OrbPlan &O = C->ctx->orb;
-    F.d_desc = O.d_desc; F.d_angle = &O.d_kp->angle; F.angle_step = (int)(sizeof(hvo_keypoint) / sizeof(float));     // F.mvKeys[i].angle
-    F.d_fv_node = (const int *)(C->bow.d_blk + L.fv_node); F.d_fv_start = (const int *)(C->bow.d_blk + L.fv_start); F.d_fv_idx = (const int *)(C->bow.d_blk + L.fv_idx);
-    F.d_n_rows = (const int *)(C->bow.d_blk + L.counts) + 2;
-    if (F.n == 0) { for (int j = 0; j < n_kf; j++) { res[j].n_matches = 0; res[j].status = HVO_OK; } return HVO_OK; }
-    return bow_search(C->ctx, s->s_match, F, n_kf, kf, params, res, &s->last_error);
+    FrameView C; int rc;
+    if ((rc = stream_view(s, cur, need_bow_search, s->s_match, C))) return rc;
+    if (C.n_kp == 0) { for (int j = 0; j < n_kf; j++) { res[j].n_matches = 0; res[j].status = HVO_OK; } return HVO_OK; }
+    return bow_search(C.ctx, s->s_match, nullptr, &C, &B->bow, n_kf, kf, params, res, &s->last_error);
+}
+
+// two frames of the ring for the frame-to-frame matching on s_match; a frame is not matched with itself
+static int stream_views2(hvo_stream *s, int64_t a, const FrameNeed &na, FrameView &A, int64_t b, const FrameNeed &nb, FrameView &B)
+{
+    int rc;
+    if ((rc = stream_view(s, a, na, s->s_match, A)) || (rc = stream_view(s, b, nb, s->s_match, B))) return rc;
+    return a == b ? HVO_ERR_INVALID_ARG : HVO_OK;
 }
 
 // ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, mono) core (src/ORBmatcher.cc:1353-1497) between two resident
 // frames.  One query per last-frame map point that passed the projection tests: its last-frame feature index q_index[i]
 // (descriptor and key-point angle are read from the last frame's slot unless q_desc is given: pMP->GetDescriptor() may differ
 // from the last frame's own descriptor), the projected (u, v), radius, octave band, ur and "has observations" flag computed by
-// the tracker.  The current frame's undistorted key points, mvuRight and descriptors never leave HBM.
+// the tracker.
 int hvo_stream_search_by_projection(hvo_stream *s, int64_t cur, int64_t last, int nq, const int32_t *q_index, const uint8_t *q_desc,
                                     const float *q_u, const float *q_v, const float *q_radius, const int32_t *q_min_level, const int32_t *q_max_level,
                                     const float *q_ur, const uint8_t *q_blocks, const uint8_t *t_occupied, int th_high, int check_orientation,
@@ -495,20 +435,13 @@ int hvo_stream_search_by_projection(hvo_stream *s, int64_t cur, int64_t last, in
     *n_matches = 0;
     if (nq == 0) return HVO_OK;
     if (nq > s->kp_cap || !q_index || !q_u || !q_v || !q_radius || !q_min_level || !q_max_level || !q_blocks || !match_idx || !match_dist) return HVO_ERR_INVALID_ARG;
-    if (!(s->sp.stages & HVO_STAGE_ORB)) return HVO_ERR_INVALID_ARG;
-    StreamSlot *C = slot_of(s, cur), *Lz = slot_of(s, last);
-    if (!C || !Lz || C == Lz) return HVO_ERR_INVALID_ARG;
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
     hipStream_t st = s->s_match;
-    ST_HIP(hipStreamWaitEvent(st, Lz->ev_orb, 0));
-    ST_HIP(hipStreamWaitEvent(st, C->ev_orb, 0));
-    // the current frame's key-point count is needed on the host for the launch geometry: it arrived with the frame's download
-    ST_HIP(hipEventSynchronize(C->ev_orb));
-    const int nt = ((const int *)(C->h_out + s->lay.counts))[0];
+    FrameView C, Lz;                                            // (the current frame's count is the launch geometry)
+    int rc;
+    if ((rc = stream_views2(s, cur, need_guided_points, C, last, need_guided_points, Lz))) return rc;
     // q_index addresses the last frame's key points and descriptors on the device: an index outside [0, n_last) would be an
     // out-of-bounds gather there (a GPU fault aborts the process), so it is refused here
-    ST_HIP(hipEventSynchronize(Lz->ev_orb));
-    const int n_last = ((const int *)(Lz->h_out + s->lay.counts))[0];
+    const int nt = C.n_kp, n_last = Lz.n_kp;
     for (int i = 0; i < nq; i++) if (q_index[i] < 0 || q_index[i] >= n_last) return HVO_ERR_INVALID_ARG;
     for (int i = 0; i < nq; i++) { match_idx[i] = -1; match_dist[i] = 256; }
     if (nt <= 0) return HVO_OK;
@@ -522,7 +455,7 @@ int hvo_stream_search_by_projection(hvo_stream *s, int64_t cur, int64_t last, in
     };
     SbpDev a; memset(&a, 0, sizeof(a));
     if (q_desc) { a.q_desc = (const uint8_t *)up(q_desc, (size_t)nq * 32); a.q_desc_index = nullptr; }
-    else { a.q_desc = Lz->ctx->orb.d_desc; a.q_desc_index = (const int *)up(q_index, (size_t)nq * 4); }
+    else { a.q_desc = Lz.desc; a.q_desc_index = (const int *)up(q_index, (size_t)nq * 4); }
     a.q_u = (const float *)up(q_u, (size_t)nq * 4); a.q_v = (const float *)up(q_v, (size_t)nq * 4); a.q_radius = (const float *)up(q_radius, (size_t)nq * 4);
     a.q_min_level = (const int *)up(q_min_level, (size_t)nq * 4); a.q_max_level = (const int *)up(q_max_level, (size_t)nq * 4);
     a.q_ur = (const float *)up(q_ur, (size_t)nq * 4); a.q_blocks = (const uint8_t *)up(q_blocks, (size_t)nq);
@@ -530,17 +463,16 @@ int hvo_stream_search_by_projection(hvo_stream *s, int64_t cur, int64_t last, in
     // key-point angles of the queries: LastFrame.mvKeysUn[i].angle, gathered on the device
     float *d_angle = (float *)(d + off); off += al64((size_t)nq * 4);
     const int *d_qidx = a.q_desc_index ? a.q_desc_index : (const int *)up(q_index, (size_t)nq * 4);
-    frame_gather_angles_enqueue(st, Lz->d_kp_un, d_qidx, nq, d_angle);
+    frame_gather_angles_enqueue(st, Lz.kp_un, d_qidx, nq, d_angle);
     a.q_angle = d_angle;
-    a.t_kp = C->d_kp_un; a.t_uright = (C->had_depth && s->sp.bf > 0) ? C->d_uright : nullptr; a.t_desc = C->ctx->orb.d_desc;
+    a.t_kp = C.kp_un; a.t_uright = C.uright; a.t_desc = C.desc;
     a.nq = nq; a.nt = nt; a.mnMinX = s->bounds[0]; a.mnMaxX = s->bounds[1]; a.mnMinY = s->bounds[2]; a.mnMaxY = s->bounds[3];
     a.th_high = th_high; a.check_orientation = check_orientation; a.map_mode = 0; a.nn_ratio = 0.f;
     int32_t *dout = (int32_t *)(d + off); int32_t *hout = (int32_t *)(hh + off); off += al64((2 * (size_t)nq + 1) * 4);
     a.match_idx = dout; a.match_dist = dout + nq; a.n_matches = dout + 2 * nq;
     void *scratch = d + off; off += match_sbp_scratch_bytes(nq);
     if (off > s->ms_bytes) { s->last_error = "matching scratch too small"; return HVO_ERR_CAPACITY; }
-    int rc = match_sbp_enqueue(st, a, scratch);
-    if (rc) return rc;
+    if ((rc = match_sbp_enqueue(st, a, scratch))) return rc;
     ST_HIP(hipMemcpyAsync(hout, dout, (2 * (size_t)nq + 1) * 4, hipMemcpyDeviceToHost, st));
     ST_HIP(hipStreamSynchronize(st));
     memcpy(match_idx, hout, (size_t)nq * 4); memcpy(match_dist, hout + nq, (size_t)nq * 4);
@@ -557,17 +489,11 @@ int hvo_stream_project_last(hvo_stream *s, int64_t cur, int64_t last, const hvo_
     *n_matches = 0;
     if (nq == 0) return HVO_OK;
     if (nq > s->kp_cap || !cam || !Tcw || !Tlw || !q_index || !x3Dw || !q_blocks || !match_idx || !match_dist) return HVO_ERR_INVALID_ARG;
-    if (!(s->sp.stages & HVO_STAGE_ORB)) return HVO_ERR_INVALID_ARG;
-    StreamSlot *C = slot_of(s, cur), *Lz = slot_of(s, last);
-    if (!C || !Lz || C == Lz) return HVO_ERR_INVALID_ARG;
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
     hipStream_t st = s->s_match;
-    ST_HIP(hipStreamWaitEvent(st, Lz->ev_orb, 0));
-    ST_HIP(hipStreamWaitEvent(st, C->ev_orb, 0));
-    ST_HIP(hipEventSynchronize(C->ev_orb));
-    const int nt = ((const int *)(C->h_out + s->lay.counts))[0];
-    ST_HIP(hipEventSynchronize(Lz->ev_orb));
-    const int n_last = ((const int *)(Lz->h_out + s->lay.counts))[0];
+    FrameView C, Lz;
+    int rc;
+    if ((rc = stream_views2(s, cur, need_guided_points, C, last, need_guided_points, Lz))) return rc;
+    const int nt = C.n_kp, n_last = Lz.n_kp;
     for (int i = 0; i < nq; i++) if (q_index[i] < 0 || q_index[i] >= n_last) return HVO_ERR_INVALID_ARG;     // (a gather out of bounds on the device otherwise)
     for (int i = 0; i < nq; i++) { match_idx[i] = -1; match_dist[i] = 256; }
     if (q_uv) for (int i = 0; i < 2 * nq; i++) q_uv[i] = 1e30f;
@@ -584,7 +510,7 @@ int hvo_stream_project_last(hvo_stream *s, int64_t cur, int64_t last, const hvo_
     SbpDev a; memset(&a, 0, sizeof(a));
     const int *d_qidx = (const int *)up(q_index, (size_t)nq * 4);
     if (q_desc) { a.q_desc = (const uint8_t *)up(q_desc, (size_t)nq * 32); a.q_desc_index = nullptr; }
-    else { a.q_desc = Lz->ctx->orb.d_desc; a.q_desc_index = d_qidx; }
+    else { a.q_desc = Lz.desc; a.q_desc_index = d_qidx; }
     const float *d_x = (const float *)up(x3Dw, (size_t)nq * 12);
     a.q_blocks = (const uint8_t *)up(q_blocks, (size_t)nq);
     a.t_occ = (const uint8_t *)up(t_occupied, (size_t)nt);
@@ -595,17 +521,16 @@ int hvo_stream_project_last(hvo_stream *s, int64_t cur, int64_t last, const hvo_
     ProjDev P; memset(&P, 0, sizeof(P));
     match_project_setup(P, Tcw, Tlw, cam->b, mono);
     P.fx = cam->fx; P.fy = cam->fy; P.cx = cam->cx; P.cy = cam->cy; P.mbf = cam->bf; P.th = th;
-    for (int l = 0; l < HVO_MAX_LEVELS; l++) P.sf[l] = C->ctx->scale[l];
+    for (int l = 0; l < HVO_MAX_LEVELS; l++) P.sf[l] = C.sf[l];
     P.mnMinX = s->bounds[0]; P.mnMaxX = s->bounds[1]; P.mnMinY = s->bounds[2]; P.mnMaxY = s->bounds[3];
     int32_t *dout = (int32_t *)dev((2 * (size_t)nq + 1) * 4); int32_t *hout = (int32_t *)(hh + ((char *)dout - d));
     float *huv = (float *)(hh + ((char *)d_u - d));
     void *scratch = d + off; off += match_sbp_scratch_bytes(nq);
     if (off > s->ms_bytes) { s->last_error = "matching scratch too small"; return HVO_ERR_CAPACITY; }
-    int rc = match_project_last_enqueue(st, P, nq, d_x, d_qidx, Lz->d_kp_un, d_u, d_v, d_radius, d_min, d_max, d_ur);
-    if (rc) return rc;
-    frame_gather_angles_enqueue(st, Lz->d_kp_un, d_qidx, nq, d_angle);
+    if ((rc = match_project_last_enqueue(st, P, nq, d_x, d_qidx, Lz.kp_un, d_u, d_v, d_radius, d_min, d_max, d_ur))) return rc;
+    frame_gather_angles_enqueue(st, Lz.kp_un, d_qidx, nq, d_angle);
     a.q_u = d_u; a.q_v = d_v; a.q_radius = d_radius; a.q_min_level = d_min; a.q_max_level = d_max; a.q_ur = d_ur; a.q_angle = d_angle;
-    a.t_kp = C->d_kp_un; a.t_uright = (C->had_depth && s->sp.bf > 0) ? C->d_uright : nullptr; a.t_desc = C->ctx->orb.d_desc;
+    a.t_kp = C.kp_un; a.t_uright = C.uright; a.t_desc = C.desc;
     a.nq = nq; a.nt = nt; a.mnMinX = s->bounds[0]; a.mnMaxX = s->bounds[1]; a.mnMinY = s->bounds[2]; a.mnMaxY = s->bounds[3];
     a.th_high = th_high; a.check_orientation = check_orientation; a.map_mode = 0; a.nn_ratio = 0.f;
     a.match_idx = dout; a.match_dist = dout + nq; a.n_matches = dout + 2 * nq;
@@ -626,25 +551,19 @@ int hvo_stream_match_lines(hvo_stream *s, int64_t from, int64_t to, int mode, fl
 {
     if (!s || !matches12 || !n_matches || mode < 0 || mode > 2) return HVO_ERR_INVALID_ARG;
     *n_matches = 0;
-    if (!(s->sp.stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL))) return HVO_ERR_INVALID_ARG;
-    StreamSlot *A = slot_of(s, from), *B = slot_of(s, to);
-    if (!A || !B || A == B) return HVO_ERR_INVALID_ARG;
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    ST_HIP(hipEventSynchronize(A->ev_lsd));
-    ST_HIP(hipEventSynchronize(B->ev_lsd));
-    const int n1 = ((const int *)(A->h_out + s->lay.counts))[4], n2 = ((const int *)(B->h_out + s->lay.counts))[4];
+    hipStream_t st = s->s_match;
+    FrameView A, B;
+    int rc;
+    if ((rc = stream_views2(s, from, need_line_match, A, to, need_line_match, B))) return rc;
+    const int n1 = A.n_kl, n2 = B.n_kl;
     if (n_from) *n_from = n1;
     for (int i = 0; i < n1; i++) matches12[i] = -1;
     if (n1 <= 0 || n2 < 2 || (mode == HVO_LINE_MATCH_DOUBLE && n1 < 2)) return HVO_OK;
-    hipStream_t st = s->s_match;
-    ST_HIP(hipStreamWaitEvent(st, A->ev_lsd, 0));
-    ST_HIP(hipStreamWaitEvent(st, B->ev_lsd, 0));
     char *d = s->d_ms, *hh = s->h_ms; size_t off = 0;
     int32_t *dm = (int32_t *)(d + off); int32_t *hm = (int32_t *)(hh + off); off += al64(((size_t)n1 + 1) * 4);
     void *scratch = d + off; off += match_lines_scratch_bytes(n1, n2);
     if (off > s->ms_bytes) { s->last_error = "matching scratch too small"; return HVO_ERR_CAPACITY; }
-    int rc = match_lines_enqueue(st, A->lv.d_desc, n1, B->lv.d_desc, n2, th, nnratio, mode, scratch, dm, (int *)(dm + n1));
-    if (rc) return rc;
+    if ((rc = match_lines_enqueue(st, A.ldesc, n1, B.ldesc, n2, th, nnratio, mode, scratch, dm, (int *)(dm + n1)))) return rc;
     ST_HIP(hipMemcpyAsync(hm, dm, ((size_t)n1 + 1) * 4, hipMemcpyDeviceToHost, st));
     ST_HIP(hipStreamSynchronize(st));
     memcpy(matches12, hm, (size_t)n1 * 4);
@@ -659,17 +578,14 @@ int hvo_stream_match_lines_geom(hvo_stream *s, int64_t cur, int64_t last, float 
 {
     if (!s || !matches12 || !accepted || !n_accepted) return HVO_ERR_INVALID_ARG;
     *n_accepted = 0;
-    if (!(s->sp.stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL))) return HVO_ERR_INVALID_ARG;
-    StreamSlot *A = slot_of(s, last), *B = slot_of(s, cur);
-    if (!A || !B || A == B) return HVO_ERR_INVALID_ARG;
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    ST_HIP(hipEventSynchronize(A->ev_lsd));
-    ST_HIP(hipEventSynchronize(B->ev_lsd));
-    const int n1 = ((const int *)(A->h_out + s->lay.counts))[4], n2 = ((const int *)(B->h_out + s->lay.counts))[4];
+    hipStream_t st = s->s_match;
+    FrameView A, B;
+    int rc;
+    if ((rc = stream_views2(s, last, need_line_match, A, cur, need_line_match, B))) return rc;
+    const int n1 = A.n_kl, n2 = B.n_kl;
     if (n_last) *n_last = n1;
     for (int i = 0; i < n1; i++) { matches12[i] = -1; accepted[i] = 0; }
     if (n1 <= 0 || n2 < 2) return HVO_OK;
-    hipStream_t st = s->s_match;
     char *d = s->d_ms, *hh = s->h_ms; size_t off = 0;
     int32_t *dm = (int32_t *)(d + off); int32_t *hm = (int32_t *)(hh + off); off += al64(((size_t)n1 + 1) * 4);
     uint8_t *da = (uint8_t *)(d + off); uint8_t *ha = (uint8_t *)(hh + off); off += al64((size_t)n1);
@@ -677,7 +593,7 @@ int hvo_stream_match_lines_geom(hvo_stream *s, int64_t cur, int64_t last, float 
     void *scratch = d + off; off += match_lines_scratch_bytes(n1, n2);
     if (off > s->ms_bytes) { s->last_error = "matching scratch too small"; return HVO_ERR_CAPACITY; }
     if (last_has_mapline) { memcpy(hml, last_has_mapline, (size_t)n1); ST_HIP(hipMemcpyAsync(dml, hml, (size_t)n1, hipMemcpyHostToDevice, st)); }
-    int rc = match_lines_geom_enqueue(st, A->lv.d_desc, A->lv.d_kl, last_has_mapline ? dml : nullptr, n1, B->lv.d_desc, B->lv.d_kl, n2, desc_th, s->bounds4(), scratch, dm, da);
+    rc = match_lines_geom_enqueue(st, A.ldesc, A.kl, last_has_mapline ? dml : nullptr, n1, B.ldesc, B.kl, n2, desc_th, B.bounds, scratch, dm, da);
     if (rc) { s->last_error = "line matching launch"; return rc; }
     ST_HIP(hipMemcpyAsync(hm, dm, ((size_t)n1 + 1) * 4, hipMemcpyDeviceToHost, st));
     ST_HIP(hipMemcpyAsync(ha, da, (size_t)n1, hipMemcpyDeviceToHost, st));
@@ -688,29 +604,22 @@ int hvo_stream_match_lines_geom(hvo_stream *s, int64_t cur, int64_t last, float 
 }
 
 // LSDmatcher::SearchByProjection(Cur, Last, th) core between two resident frames (src/LSDmatcher.cpp:561-662): query i = last-frame line q_index[i]
-// (its key line and -- unless q_desc is given -- its descriptor are read from the last frame's slot), the current frame's key lines, line functions,
-// descriptors and LINE GRID are the resident ones (the stream must run HVO_STAGE_GRIDS); per query only the four projected coordinates go up
+// (its key line and -- unless q_desc is given -- its descriptor are the last frame's); per query only the four projected coordinates go up
 int hvo_stream_search_lines_by_projection(hvo_stream *s, int64_t cur, int64_t last, int nq, const int32_t *q_index, const float *q_xyxy, const uint8_t *q_desc,
                                           const uint8_t *q_blocks, const uint8_t *t_occupied, float th, int32_t *match_idx, int32_t *match_dist, int *n_matches)
 {
     if (!s || !match_idx || !match_dist || !n_matches || nq < 0) return HVO_ERR_INVALID_ARG;
     *n_matches = 0;
-    if (!(s->sp.stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL)) || !(s->tail_stages & HVO_STAGE_GRIDS)) return HVO_ERR_INVALID_ARG;
-    StreamSlot *A = slot_of(s, last), *B = slot_of(s, cur);
-    if (!A || !B || A == B) return HVO_ERR_INVALID_ARG;
+    hipStream_t st = s->s_match;
+    FrameView A, B;                                             // (ev_lsd is recorded behind the line grid and its download)
+    int rc;
+    if ((rc = stream_views2(s, cur, need_guided_lines, B, last, need_line_match, A))) return rc;
     for (int i = 0; i < nq; i++) { match_idx[i] = -1; match_dist[i] = 256; }
     if (nq == 0) return HVO_OK;
     if (!q_index || !q_xyxy) return HVO_ERR_INVALID_ARG;
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    ST_HIP(hipEventSynchronize(A->ev_lsd));
-    ST_HIP(hipEventSynchronize(B->ev_lsd));                     // (recorded behind the line grid and its download)
-    const int n1 = ((const int *)(A->h_out + s->lay.counts))[4], n2 = ((const int *)(B->h_out + s->lay.counts))[4];
+    const int n1 = A.n_kl, n2 = B.n_kl;
     for (int i = 0; i < nq; i++) if (q_index[i] < 0 || q_index[i] >= n1) return HVO_ERR_INVALID_ARG;
     if (n2 <= 0) return HVO_OK;
-    const TailLayout &T = s->tl;
-    const int n_items = ((const int *)(B->h_tail + T.counts))[3];
-    if (n_items < 0 || n_items > T.ln_cap) { s->last_error = "line grid overflowed its capacity"; return HVO_ERR_CAPACITY; }
-    hipStream_t st = s->s_match;
     char *d = s->d_ms, *hh = s->h_ms; size_t off = 0;
     auto up = [&](const void *src, size_t bytes) -> void * {
         void *dp = d + off, *hp = hh + off; off += al64(bytes);
@@ -722,20 +631,19 @@ int hvo_stream_search_lines_by_projection(hvo_stream *s, int64_t cur, int64_t la
     LsbpDev a; memset(&a, 0, sizeof(a));
     a.nq = nq; a.nt = n2;
     a.q_xyxy = (const float *)up(q_xyxy, (size_t)nq * 16); a.q_index = (const int32_t *)up(q_index, (size_t)nq * 4);
-    a.q_kl = A->lv.d_kl; a.q_desc_all = A->lv.d_desc;
+    a.q_kl = A.kl; a.q_desc_all = A.ldesc;
     a.q_desc = q_desc ? (const uint8_t *)up(q_desc, (size_t)nq * 32) : nullptr;
     a.q_blocks = q_blocks ? (const uint8_t *)up(q_blocks, (size_t)nq) : nullptr;
     a.t_occ = t_occupied ? (const uint8_t *)up(t_occupied, (size_t)n2) : nullptr;
     if (!a.q_xyxy || !a.q_index || (q_desc && !a.q_desc) || (q_blocks && !a.q_blocks) || (t_occupied && !a.t_occ)) { s->last_error = "matching scratch too small"; return HVO_ERR_CAPACITY; }
-    a.t_kl = B->lv.d_kl; a.t_fn = B->lv.d_fn; a.t_desc = B->lv.d_desc;
-    a.cell_start = (const int32_t *)(B->d_tail + T.ln_start); a.cell_items = (const int32_t *)(B->d_tail + T.ln_items); a.n_items = n_items;
+    a.t_kl = B.kl; a.t_fn = B.fn; a.t_desc = B.ldesc;
+    a.cell_start = B.ln_start; a.cell_items = B.ln_items; a.n_items = B.n_ln_items;
     a.mnMinX = s->bounds[0]; a.mnMaxX = s->bounds[1]; a.mnMinY = s->bounds[2]; a.mnMaxY = s->bounds[3]; a.th = th; a.cos_th = cos(10.0 / 180.0 * M_PI);
     int32_t *dout = (int32_t *)(d + off); int32_t *hout = (int32_t *)(hh + off); off += al64((2 * (size_t)nq + 1) * 4);
     void *scratch = d + off; off += match_lsbp_scratch_bytes(nq, n2);
     if (off > s->ms_bytes) { s->last_error = "matching scratch too small"; return HVO_ERR_CAPACITY; }
     a.match_idx = dout; a.match_dist = dout + nq; a.n_matches = dout + 2 * nq;
-    int rc = match_lsbp_enqueue(st, a, scratch);
-    if (rc) { s->last_error = rc == HVO_ERR_UNSUPPORTED ? "guided line search: more than 2048 current lines (or 2^22 line grid items)" : "guided line search launch"; return rc; }
+    if ((rc = match_lsbp_enqueue(st, a, scratch))) { s->last_error = rc == HVO_ERR_UNSUPPORTED ? "guided line search: more than 2048 current lines (or 2^22 line grid items)" : "guided line search launch"; return rc; }
     ST_HIP(hipMemcpyAsync(hout, dout, (2 * (size_t)nq + 1) * 4, hipMemcpyDeviceToHost, st));
     ST_HIP(hipStreamSynchronize(st));
     memcpy(match_idx, hout, (size_t)nq * 4); memcpy(match_dist, hout + nq, (size_t)nq * 4);
@@ -744,33 +652,22 @@ int hvo_stream_search_lines_by_projection(hvo_stream *s, int64_t cur, int64_t la
 }
 
 // LSDmatcher::SearchByProjection(F, vpMapLines, eval_orient, th) on the resident frame `cur` (src/LSDmatcher.cpp:709-801; Tracking::SearchLocalLines,
-// src/Tracking.cc:3279-3355): key lines, line functions, descriptors, LINE GRID and 3-D lines are the resident ones (HVO_STAGE_GRIDS | HVO_STAGE_LINES3D);
-// per query only the map line's projection, viewing cosine, world vector, descriptor and observation flag go up
+// src/Tracking.cc:3279-3355): per query only the map line's projection, viewing cosine, world vector, descriptor and observation flag go up
 int hvo_stream_search_lines_by_projection_map(hvo_stream *s, int64_t cur, int nq, const float *q_xyxy, const float *q_view_cos,
                                               const double *q_wvec, const uint8_t *q_desc, const uint8_t *q_blocks, const uint8_t *t_occupied, float th, float nn_ratio,
                                               int32_t *match_idx, int32_t *match_dist, int *n_matches)
 {
     if (!s || !match_idx || !match_dist || !n_matches || nq < 0) return HVO_ERR_INVALID_ARG;
     *n_matches = 0;
-    const unsigned need = HVO_STAGE_GRIDS | HVO_STAGE_LINES3D;
-    if (!(s->sp.stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL)) || (s->tail_stages & need) != need) {
-        s->last_error = "local-map line search: the stream must run HVO_STAGE_GRIDS and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
-    }
-    StreamSlot *B = slot_of(s, cur);
-    if (!B) return HVO_ERR_INVALID_ARG;
-    if (!B->had_depth) { s->last_error = "local-map line search: the frame was submitted without depth (no 3-D lines)"; return HVO_ERR_INVALID_ARG; }
+    hipStream_t st = s->s_match;
+    FrameView B; int rc;   // (ev_lsd is recorded behind the tail stages -- 3-D lines, line grid -- and their downloads)
+    if ((rc = stream_view(s, cur, need_map_lines, st, B))) return rc;
     for (int i = 0; i < nq; i++) { match_idx[i] = -1; match_dist[i] = 256; }
     if (nq == 0) return HVO_OK;
     if (!q_xyxy || !q_view_cos || !q_wvec || !q_desc) return HVO_ERR_INVALID_ARG;
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    ST_HIP(hipEventSynchronize(B->ev_lsd));                     // (recorded behind the tail stages -- 3-D lines, line grid -- and their downloads)
-    const int n2 = ((const int *)(B->h_out + s->lay.counts))[4];
+    const int n2 = B.n_kl, n_items = B.n_ln_items;
     if (n2 <= 0) return HVO_OK;
-    const TailLayout &T = s->tl;
-    const int n_items = ((const int *)(B->h_tail + T.counts))[3];
-    if (n_items < 0 || n_items > T.ln_cap) { s->last_error = "line grid overflowed its capacity"; return HVO_ERR_CAPACITY; }
     if (n2 > 2048 || nq > LSBP_MAP_MAXQ || n_items >= (1 << 22)) { s->last_error = match_lsbp_map_limit_text(nq, n2); return HVO_ERR_UNSUPPORTED; }
-    hipStream_t st = s->s_match;
     const size_t up_b = al64((size_t)nq * 16) + al64((size_t)nq * 4) + al64((size_t)nq * 24) + al64((size_t)nq * 32) + al64((size_t)nq) + al64((size_t)n2);
     const size_t out_b = al64((2 * (size_t)nq + 1) * 4), sb = match_lsbp_map_scratch_bytes(nq, n2);
     if (s->lm_dbytes < up_b + out_b + sb || s->lm_hbytes < up_b + out_b) {
@@ -797,16 +694,15 @@ int hvo_stream_search_lines_by_projection_map(hvo_stream *s, int64_t cur, int nq
     a.q_blocks = q_blocks ? (const uint8_t *)up(q_blocks, (size_t)nq) : nullptr;
     a.t_occ = t_occupied ? (const uint8_t *)up(t_occupied, (size_t)n2) : nullptr;
     if (!a.q_xyxy || !a.q_view_cos || !a.q_wvec || !a.q_desc || (q_blocks && !a.q_blocks) || (t_occupied && !a.t_occ)) { s->last_error = "local-map line search upload"; return HVO_ERR_HIP; }
-    a.t_kl = B->lv.d_kl; a.t_fn = B->lv.d_fn; a.t_desc = B->lv.d_desc; a.t_l3d = (const hvo_line3d *)(B->d_tail + T.lines3d);
-    a.cell_start = (const int32_t *)(B->d_tail + T.ln_start); a.cell_items = (const int32_t *)(B->d_tail + T.ln_items); a.n_items = n_items;
+    a.t_kl = B.kl; a.t_fn = B.fn; a.t_desc = B.ldesc; a.t_l3d = B.l3d;
+    a.cell_start = B.ln_start; a.cell_items = B.ln_items; a.n_items = n_items;
     a.mnMinX = s->bounds[0]; a.mnMaxX = s->bounds[1]; a.mnMinY = s->bounds[2]; a.mnMaxY = s->bounds[3]; a.th = th; a.nn_ratio = nn_ratio;
     a.cos_normal = cos(15.0 / 180.0 * M_PI);
     off = up_b;
     int32_t *dout = (int32_t *)(d + off); int32_t *hout = (int32_t *)(hh + off); off += out_b;
     void *scratch = d + off;
     a.match_idx = dout; a.match_dist = dout + nq; a.n_matches = dout + 2 * nq;
-    int rc = match_lsbp_map_enqueue(st, a, scratch);
-    if (rc) { s->last_error = "local-map line search launch"; return rc; }
+    if ((rc = match_lsbp_map_enqueue(st, a, scratch))) { s->last_error = "local-map line search launch"; return rc; }
     ST_HIP(hipMemcpyAsync(hout, dout, (2 * (size_t)nq + 1) * 4, hipMemcpyDeviceToHost, st));
     ST_HIP(hipStreamSynchronize(st));
     memcpy(match_idx, hout, (size_t)nq * 4); memcpy(match_dist, hout + nq, (size_t)nq * 4);
@@ -821,23 +717,15 @@ int hvo_stream_set_readings(hvo_stream *s, unsigned mask)
     return HVO_OK;
 }
 
-// Tracking::TrackManhattanFrame (src/Tracking.cc:1172-1348) on the resident frame `cur`: its surface normals (HVO_STAGE_PLANE_TAIL) and 3-D lines
-// (HVO_STAGE_LINES3D) are read where the tail stages left them; only R_last goes up (as a kernel argument) and the result comes down
+// Tracking::TrackManhattanFrame (src/Tracking.cc:1172-1348) on the resident frame `cur`: only R_last goes up (as a kernel argument)
 int hvo_stream_track_manhattan(hvo_stream *s, int64_t cur, const float R_last[9], hvo_mf_result *res, uint8_t *normal_axes, uint8_t *line_axes)
 {
     if (!s || !R_last || !res) return HVO_ERR_INVALID_ARG;
-    const unsigned need = HVO_STAGE_PLANE_TAIL | HVO_STAGE_LINES3D;
-    if ((s->tail_stages & need) != need) {
-        s->last_error = "Manhattan tracking: the stream must run HVO_STAGE_PLANE_TAIL and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
-    }
-    StreamSlot *B = slot_of(s, cur);
-    if (!B) { s->last_error = "Manhattan tracking: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
-    if (!B->had_depth) { s->last_error = "Manhattan tracking: the frame was submitted without depth (no normals, no 3-D lines)"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    const TailLayout &T = s->tl;
-    const int nn = T.n_normals, nf = T.nfeat;
-    const size_t b_r = al64(sizeof(hvo_mf_result)), b_na = al64((size_t)nn), b_la = al64((size_t)nf), bytes = b_r + b_na + b_la;
     hipStream_t st = s->s_match;
+    FrameView B; int rc;   // st waits for the normals (behind ev_orb, on the frame's ORB stream), the 3-D lines and the key-line count
+    if ((rc = stream_view(s, cur, need_manhattan, st, B))) return rc;
+    const int nn = B.n_normals, nf = B.nfeat;
+    const size_t b_r = al64(sizeof(hvo_mf_result)), b_na = al64((size_t)nn), b_la = al64((size_t)nf), bytes = b_r + b_na + b_la;
     if (s->mf_bytes < bytes) {
         ST_HIP(hipStreamSynchronize(st));
         if (s->d_mf) (void)hipFree(s->d_mf);
@@ -847,144 +735,84 @@ int hvo_stream_track_manhattan(hvo_stream *s, int64_t cur, const float R_last[9]
         ST_HIP(hipHostMalloc((void **)&s->h_mf, bytes, hipHostMallocDefault));
         s->mf_bytes = bytes;
     }
-    ST_HIP(hipStreamWaitEvent(st, B->ev_orb, 0));                // the normals (recorded behind them on the frame's ORB stream)
-    ST_HIP(hipStreamWaitEvent(st, B->ev_lsd, 0));                // the 3-D lines and the key-line count
     hvo_mf_result *d_r = (hvo_mf_result *)s->d_mf; uint8_t *d_na = (uint8_t *)s->d_mf + b_r, *d_la = d_na + b_na;
-    int rc = mf_enqueue(st, (const hvo_surface_normal *)(B->d_tail + T.normals), nn, 0, (const hvo_line3d *)(B->d_tail + T.lines3d), nf, 0, B->lv.d_nkl, 1,
-                        R_last, d_r, normal_axes ? d_na : nullptr, line_axes ? d_la : nullptr);
-    if (rc) { s->last_error = "Manhattan tracking launch"; return rc; }
+    if ((rc = mf_enqueue(st, B.normals, nn, 0, B.l3d, nf, 0, B.d_nkl, 1, R_last, d_r, normal_axes ? d_na : nullptr, line_axes ? d_la : nullptr))) {
+        s->last_error = "Manhattan tracking launch"; return rc;
+    }
     ST_HIP(hipMemcpyAsync(s->h_mf, s->d_mf, normal_axes || line_axes ? bytes : b_r, hipMemcpyDeviceToHost, st));
     ST_HIP(hipStreamSynchronize(st));
     memcpy(res, s->h_mf, sizeof(hvo_mf_result));
     if (normal_axes) memcpy(normal_axes, s->h_mf + b_r, (size_t)nn);
     if (line_axes) {
-        int n_kl = ((const int *)(B->h_out + s->lay.counts))[4];
-        n_kl = n_kl < 0 ? 0 : (n_kl > nf ? nf : n_kl);
-        memcpy(line_axes, s->h_mf + b_r + b_na, (size_t)n_kl);
+        frame_view_counts(B, FV_N_KL);                          // st has drained behind ev_lsd: the count is there
+        memcpy(line_axes, s->h_mf + b_r + b_na, (size_t)B.n_kl);
     }
     return HVO_OK;
 }
 
-// PlaneMatcher::SearchMapByCoefficients (src/PlaneMatcher.cpp:10-68) on the resident frame `cur` against a resident plane map: the frame's
-// hvo_plane_cloud records are read where HVO_STAGE_PLANE_TAIL left them; only Tcw and the thresholds go up.  The scratch is the map's.
+// PlaneMatcher::SearchMapByCoefficients (src/PlaneMatcher.cpp:10-68) on the resident frame `cur` against a resident plane map (its scratch is the map's)
 int hvo_stream_match_planes(hvo_stream *s, hvo_plane_map *m, int64_t cur, const float Tcw[12], const float th[4], hvo_plane_match *res)
 {
     if (!s || !m || !Tcw || !res) return HVO_ERR_INVALID_ARG;
-    if (!(s->tail_stages & HVO_STAGE_PLANE_TAIL)) { s->last_error = "plane association: the stream must run HVO_STAGE_PLANE_TAIL"; return HVO_ERR_INVALID_ARG; }
-    StreamSlot *B = slot_of(s, cur);
-    if (!B) { s->last_error = "plane association: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
-    if (!B->had_depth) { s->last_error = "plane association: the frame was submitted without depth (no planes)"; return HVO_ERR_INVALID_ARG; }
+    FrameView B; int rc;   // (the plane tail runs on the frame's plane stream: s_match waits for ev_peac)
+    if ((rc = stream_view(s, cur, need_planes, s->s_match, B))) return rc;
     if (pa_map_device(m) != s->p.device) { s->last_error = "plane association: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    hipStream_t st = s->s_match;
-    ST_HIP(hipStreamWaitEvent(st, B->ev_peac, 0));               // the plane tail runs on the frame's plane stream
-    const int rc = pa_match(st, m, nullptr, 0, (const hvo_plane_cloud *)(B->d_tail + s->tl.pclouds), 0, 1, Tcw, th, res, nullptr, nullptr);
+    rc = pa_match(s->s_match, m, nullptr, 0, B.pclouds, 0, 1, Tcw, th, res, nullptr, nullptr);
     if (rc) s->last_error = pa_map_error(m);
     return rc;
 }
 
-// Optimizer::PoseOptimization (src/Optimizer.cc:590-1478) on the resident frame `cur`: the frame side of every edge is read where the stages
-// left it; the pose and the map side go up.  Scratch: the slot's own context's call arena (grow-only).
+// Optimizer::PoseOptimization (src/Optimizer.cc:590-1478) on the resident frame `cur`: the pose and the map side go up
 int hvo_stream_pose_optimize(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_pose_plane_params *pp, const hvo_pose_problem *prob,
                              hvo_pose_result *res, const hvo_pose_flags *flags)
 {
     if (!s || !cam || !prob || !res) return HVO_ERR_INVALID_ARG;
-    const unsigned need = HVO_STAGE_PLANE_TAIL | HVO_STAGE_LINES3D;
-    if ((s->tail_stages & need) != need || !(s->sp.stages & HVO_STAGE_ORB)) {
-        s->last_error = "pose optimisation: the stream must run HVO_STAGE_ORB, HVO_STAGE_LINES3D and HVO_STAGE_PLANE_TAIL"; return HVO_ERR_INVALID_ARG;
-    }
-    if (!(s->sp.bf > 0)) { s->last_error = "pose optimisation: the stream was created with bf <= 0 (no mvuRight)"; return HVO_ERR_INVALID_ARG; }
-    StreamSlot *B = slot_of(s, cur);
-    if (!B) { s->last_error = "pose optimisation: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
-    if (!B->had_depth) { s->last_error = "pose optimisation: the frame was submitted without depth (no mvuRight, 3-D lines or planes)"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    hipStream_t st = s->s_match;
-    ST_HIP(hipStreamWaitEvent(st, B->ev_orb, 0));
-    ST_HIP(hipStreamWaitEvent(st, B->ev_lsd, 0));
-    ST_HIP(hipStreamWaitEvent(st, B->ev_peac, 0));
-    hvo_ctx *c = B->ctx;
-    PoResident R;
-    R.kp_un = B->d_kp_un; R.uright = B->d_uright; R.linefn = B->lv.d_fn; R.l3d = (const hvo_line3d *)(B->d_tail + s->tl.lines3d);
-    R.pclouds = (const hvo_plane_cloud *)(B->d_tail + s->tl.pclouds); R.d_nkp = c->orb.d_nkp; R.d_nkl = B->lv.d_nkl;
-    R.depth = nullptr; R.pitch = R.w = R.h = 0; R.dfac = 0.f;      // the slot holds mvuRight
-    float inv_s2[HVO_MAX_LEVELS];
-    for (int i = 0; i < HVO_MAX_LEVELS; i++) inv_s2[i] = i < c->p.orb_nlevels ? 1.0f / (c->scale[i] * c->scale[i]) : 1.0f;
-    return po_run(c, st, cam, pp, inv_s2, 1, prob, &R, res, flags, &s->last_error);
+    FrameView B; int rc;
+    if ((rc = stream_view(s, cur, need_pose, s->s_match, B))) return rc;
+    return po_run(B.ctx, s->s_match, cam, pp, 1, prob, &B, res, flags, &s->last_error);
 }
 
-// Manhattan::computeStructConstrains for every key line + Optimizer::LineOptStruct (src/Tracking.cc:270-335) on the resident frame `cur`:
-// key-line functions and 3-D lines are read where the stages left them, A and B of the resident records are rewritten
+// Manhattan::computeStructConstrains for every key line + Optimizer::LineOptStruct (src/Tracking.cc:270-335) on the resident frame `cur`: A, B of its 3-D lines are rewritten
 int hvo_stream_line_struct_optimize(hvo_stream *s, int64_t cur, const hvo_line_struct_params *params, int n_lines, int8_t *rel,
                                     double *l3d_out, hvo_line_opt_result *res)
 {
     if (!s || !res || n_lines < 0 || (n_lines && !rel)) return HVO_ERR_INVALID_ARG;
     if (n_lines > s->nfeat && n_lines <= 4096) { s->last_error = "line structure: n_lines beyond the key-line capacity"; return HVO_ERR_INVALID_ARG; }
-    if (!(s->sp.stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL)) || !(s->tail_stages & HVO_STAGE_LINES3D)) {
-        s->last_error = "line structure: the stream must run an LSD stage and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
-    }
-    StreamSlot *B = slot_of(s, cur);
-    if (!B) { s->last_error = "line structure: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
-    if (!B->had_depth) { s->last_error = "line structure: the frame was submitted without depth (no 3-D lines)"; return HVO_ERR_INVALID_ARG; }
+    FrameView B; int rc;   // (s_match waits for ev_lsd: the 3-D lines and the key-line count)
+    if ((rc = stream_view(s, cur, need_line_struct, s->s_match, B))) return rc;
+    StreamSlot *slot = slot_of(s, cur);
     const bool opt = !params || (params->mode & HVO_LINE_STRUCT_OPTIMIZE);
-    if (opt && B->line_opt_done) { s->last_error = "line structure: this frame's 3-D lines have been optimised already"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    hipStream_t st = s->s_match;
-    ST_HIP(hipStreamWaitEvent(st, B->ev_lsd, 0));                // the 3-D lines and the key-line count
-    LsResident R;
-    R.linefn = B->lv.d_fn; R.l3d = (hvo_line3d *)(B->d_tail + s->tl.lines3d); R.d_nkl = B->lv.d_nkl;
+    if (opt && slot->line_opt_done) { s->last_error = "line structure: this frame's 3-D lines have been optimised already"; return HVO_ERR_INVALID_ARG; }
     const int32_t nl = n_lines;
     int8_t *const relp[1] = { rel }; double *const outp[1] = { l3d_out };
-    const int rc = ls_run(B->ctx, st, params, 1, &nl, nullptr, &R, relp, outp, res, &s->last_error);
-    if (rc == HVO_OK && opt) B->line_opt_done = true;
+    rc = ls_run(B.ctx, s->s_match, params, 1, &nl, nullptr, &B, relp, outp, res, &s->last_error);
+    if (rc == HVO_OK && opt) slot->line_opt_done = true;
     return rc;
 }
 
-// Tracking::SearchLocalLines + Manhattan::computeStructConstInMap on the resident frame `cur` against a resident line map: the frame side is
-// read where the stages left it; the pose, held and seen_extra go up.  The scratch is the map's.
+// Tracking::SearchLocalLines + Manhattan::computeStructConstInMap on the resident frame `cur` against a resident line map: the pose, held and seen_extra go up
 int hvo_stream_search_local_lines(hvo_stream *s, hvo_line_map *m, int64_t cur, const hvo_camera *cam, const float Tcw[12],
                                   const hvo_local_lines_params *params, hvo_local_lines_io *io, hvo_local_lines_result *res)
 {
     if (!s || !m || !cam || !Tcw || !params || !io || !res) return HVO_ERR_INVALID_ARG;
-    const unsigned need = HVO_STAGE_GRIDS | HVO_STAGE_LINES3D;
-    if (!(s->sp.stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL)) || (s->tail_stages & need) != need) {
-        s->last_error = "local lines: the stream must run an LSD stage, HVO_STAGE_GRIDS and HVO_STAGE_LINES3D"; return HVO_ERR_INVALID_ARG;
-    }
-    StreamSlot *B = slot_of(s, cur);
-    if (!B) { s->last_error = "local lines: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
-    if (!B->had_depth) { s->last_error = "local lines: the frame was submitted without depth (no 3-D lines)"; return HVO_ERR_INVALID_ARG; }
+    FrameView B; int rc;   // (ev_lsd is recorded behind the tail stages -- 3-D lines, line grid -- and their downloads)
+    if ((rc = stream_view(s, cur, need_local_lines, s->s_match, B))) return rc;
     if (ll_map_device(m) != s->p.device) { s->last_error = "local lines: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    ST_HIP(hipEventSynchronize(B->ev_lsd));                     // (recorded behind the tail stages -- 3-D lines, line grid -- and their downloads)
-    int n2 = ((const int *)(B->h_out + s->lay.counts))[4];
-    if (n2 < 0) n2 = 0;
-    const TailLayout &T = s->tl;
-    const int n_items = ((const int *)(B->h_tail + T.counts))[3];
-    if (n_items < 0 || n_items > T.ln_cap) { s->last_error = "line grid overflowed its capacity"; return HVO_ERR_CAPACITY; }
-    if (n2 > 2048 || n_items >= (1 << 22)) { s->last_error = match_lsbp_map_limit_text(0, n2); return HVO_ERR_UNSUPPORTED; }
-    LlFrameDev F;
-    F.kl = B->lv.d_kl; F.fn = B->lv.d_fn; F.desc = B->lv.d_desc; F.l3d = (const hvo_line3d *)(B->d_tail + T.lines3d);
-    F.cell_start = (const int32_t *)(B->d_tail + T.ln_start); F.cell_items = (const int32_t *)(B->d_tail + T.ln_items); F.n_items = n_items; F.nt = n2;
-    const int rc = ll_run(s->s_match, m, cam, params, s->bounds, 1, &F, Tcw, io, res);
+    if (B.n_kl > 2048 || B.n_ln_items >= (1 << 22)) { s->last_error = match_lsbp_map_limit_text(0, B.n_kl); return HVO_ERR_UNSUPPORTED; }
+    rc = ll_run(s->s_match, m, cam, params, 1, &B, Tcw, io, res);
     if (rc) s->last_error = ll_map_error(m);
     return rc;
 }
 
-// Tracking::SearchLocalPoints on the resident frame `cur` against a resident point map: undistorted key points, mvuRight and descriptors are
-// read where the stages left them; the pose, held and seen_extra go up.  The scratch is the map's.
+// Tracking::SearchLocalPoints on the resident frame `cur` against a resident point map: the pose, held and seen_extra go up
 int hvo_stream_search_local_points(hvo_stream *s, hvo_point_map *m, int64_t cur, const hvo_camera *cam, const float Tcw[12],
                                    const hvo_local_points_params *params, hvo_local_points_io *io, hvo_local_points_result *res)
 {
     if (!s || !m || !cam || !Tcw || !params || !io || !res) return HVO_ERR_INVALID_ARG;
-    if (!(s->sp.stages & HVO_STAGE_ORB)) { s->last_error = "local points: the stream must run HVO_STAGE_ORB"; return HVO_ERR_INVALID_ARG; }
-    StreamSlot *B = slot_of(s, cur);
-    if (!B) { s->last_error = "local points: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    FrameView B; int rc;   // (ev_orb is recorded behind the undistortion, mvuRight and the frame's download)
+    if ((rc = stream_view(s, cur, need_local_points, s->s_match, B))) return rc;
     if (lp_map_device(m) != s->p.device) { s->last_error = "local points: the map lives on another device"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    ST_HIP(hipEventSynchronize(B->ev_orb));                     // (recorded behind the undistortion, mvuRight and the frame's download)
-    const int nt = std::max(0, std::min(((const int *)(B->h_out + s->lay.counts))[0], s->kp_cap));
-    LpFrameDev F; memset(&F, 0, sizeof(F));
-    F.kp_un = B->d_kp_un; F.uright = (B->had_depth && s->sp.bf > 0) ? B->d_uright : nullptr; F.desc = B->ctx->orb.d_desc; F.nt = nt;
-    const int rc = lp_run(s->s_match, m, cam, params, s->bounds, B->ctx->scale, 1, &F, Tcw, io, res);
+    rc = lp_run(s->s_match, m, cam, params, 1, &B, Tcw, io, res);
     if (rc) s->last_error = lp_map_error(m);
     return rc;
 }
@@ -1012,16 +840,9 @@ int hvo_stream_pnp_ransac(hvo_stream *s, int64_t cur, const hvo_camera *cam, con
 {
     if (!s) return HVO_ERR_INVALID_ARG;
     if (!cam || !params || !kf_sides || !results || n_kf < 1) { s->last_error = "pnp: a null argument or n_kf < 1"; return HVO_ERR_INVALID_ARG; }
-    if (!(s->sp.stages & HVO_STAGE_ORB)) { s->last_error = "pnp: the stream must run HVO_STAGE_ORB"; return HVO_ERR_INVALID_ARG; }
-    StreamSlot *B = slot_of(s, cur);
-    if (!B) { s->last_error = "pnp: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
-    if (hipSetDevice(s->p.device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    ST_HIP(hipEventSynchronize(B->ev_orb));
-    hvo_ctx *c = B->ctx;
-    PnpResident R;
-    R.d_kp_un = B->d_kp_un; R.nf = std::max(0, std::min(((const int *)(B->h_out + s->lay.counts))[0], s->kp_cap)); R.kf = kf_sides;
-    for (int i = 0; i < HVO_MAX_LEVELS; i++) R.sigma2[i] = i < c->p.orb_nlevels ? c->scale[i] * c->scale[i] : 1.0f;
-    return pnp_run(c, s->s_match, cam, params, n_kf, nullptr, &R, results, &s->last_error);
+    FrameView B; int rc;
+    if ((rc = stream_view(s, cur, need_pnp, s->s_match, B))) return rc;
+    return pnp_run(B.ctx, s->s_match, cam, params, n_kf, nullptr, &B, kf_sides, results, &s->last_error);
 }
 
 int hvo_stream_pnp_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2])
