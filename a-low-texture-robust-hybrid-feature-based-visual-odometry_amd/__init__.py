@@ -89,6 +89,7 @@ EXPORTS = [
     "hvo_compute_bow", "hvo_stream_compute_bow", "hvo_batch_compute_bow", "hvo_search_by_bow", "hvo_stream_search_by_bow",
     "hvo_bow_last_kernel_ms", "hvo_stream_bow_last_kernel_ms",
     "hvo_pnp_default_params", "hvo_pnp_ransac", "hvo_stream_pnp_ransac", "hvo_pnp_last_kernel_ms", "hvo_stream_pnp_last_kernel_ms",
+    "hvo_search_by_projection_keyframe", "hvo_stream_search_by_projection_keyframe",
 ]
 
 
@@ -549,6 +550,75 @@ def pnp_iterate(res, state, n_iterations):
     return None, False, None, 0
 
 
+KF_SEARCH_MAX_ENTRIES, KF_SEARCH_MAX_FEATURES = 16384, 65535
+KF_GATES = ("searched", "skip", "u < minX", "u > maxX", "v < minY", "v > maxY", "dist < 0.8 min", "dist > 1.2 max")     # hvo_kf_search_result.gate
+
+
+class KfSearchCandidate(C.Structure):
+    """hvo_kf_search_candidate: one candidate key frame's map points, the frame's pose for it and the frame's occupancy at entry"""
+    _fields_ = [("n", C.c_int32), ("pos", C.c_void_p), ("skip", C.c_void_p), ("max_dist", C.c_void_p), ("min_dist", C.c_void_p), ("desc", C.c_void_p),
+                ("angle", C.c_void_p), ("Tcw", C.c_float * 12), ("occupied", C.c_void_p)]
+
+
+class KfSearchParams(C.Structure):
+    """hvo_kf_search_params"""
+    _fields_ = [("th", C.c_float), ("orb_dist", C.c_int32), ("check_orientation", C.c_int32), ("log_scale_factor", C.c_float), ("n_levels", C.c_int32),
+                ("bounds", C.c_float * 4)]
+
+
+class KfSearchResult(C.Structure):
+    """hvo_kf_search_result"""
+    _fields_ = [("match_idx", C.c_void_p), ("match_dist", C.c_void_p), ("feature_kf", C.c_void_p), ("proj", C.c_void_p), ("level", C.c_void_p),
+                ("gate", C.c_void_p), ("n_matches", C.c_int32), ("n_searched", C.c_int32), ("status", C.c_int32), ("kernel_ms", C.c_float * 2)]
+
+
+assert C.sizeof(KfSearchCandidate) == 112 and C.sizeof(KfSearchParams) == 36 and C.sizeof(KfSearchResult) == 72
+
+KF_UNTOUCHED = -7           # what the outputs hold before the call: a refusal leaves them so
+
+
+def _kfs_args(n_frame, kfs, bounds4, th, orb_dist, check_orientation, log_scale_factor, n_levels):
+    """-> (KfSearchParams, candidates, results, the arrays they point at).  kfs: one dict per candidate with pos (n x 3), skip (n), max_dist,
+    min_dist (n, raw), desc (n x 32), angle (n, or None), Tcw (3 x 4), occupied (frame features, or None)"""
+    P = KfSearchParams(); P.th = th; P.orb_dist = orb_dist; P.check_orientation = 1 if check_orientation else 0
+    P.log_scale_factor = log_scale_factor; P.n_levels = n_levels
+    b = (0.0, 1.0, 0.0, 1.0) if bounds4 is None else [float(v) for v in np.asarray(bounds4).reshape(4)]
+    for k in range(4): P.bounds[k] = b[k]
+    K = (KfSearchCandidate * len(kfs))(); R = (KfSearchResult * len(kfs))(); keep = []
+    for j, kf in enumerate(kfs):
+        pos = np.ascontiguousarray(kf["pos"], np.float32).reshape(-1, 3); n = len(pos)
+        a = dict(pos=pos, skip=np.ascontiguousarray(kf["skip"], np.uint8).reshape(-1), max_dist=np.ascontiguousarray(kf["max_dist"], np.float32).reshape(-1),
+                 min_dist=np.ascontiguousarray(kf["min_dist"], np.float32).reshape(-1), desc=np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32))
+        if any(len(a[k]) != n for k in a):
+            raise ValueError("search_by_projection_keyframe: a candidate's arrays differ in length")
+        a["angle"] = None if kf.get("angle") is None else np.ascontiguousarray(kf["angle"], np.float32).reshape(n)
+        a["occupied"] = None if kf.get("occupied") is None else np.ascontiguousarray(kf["occupied"], np.uint8).reshape(n_frame)
+        K[j].n = n
+        for k in ("pos", "skip", "max_dist", "min_dist", "desc", "angle", "occupied"):
+            setattr(K[j], k, a[k].ctypes.data if a[k] is not None and a[k].size else None)
+        if n == 0:                                                # (an empty array has no address worth passing; the call reads nothing)
+            for k in ("pos", "skip", "max_dist", "min_dist", "desc"): setattr(K[j], k, None)
+        T = np.asarray(kf["Tcw"], np.float32).reshape(12)
+        for k in range(12): K[j].Tcw[k] = T[k]
+        o = dict(match_idx=np.full(max(n, 1), KF_UNTOUCHED, np.int32), match_dist=np.full(max(n, 1), KF_UNTOUCHED, np.int32),
+                 feature_kf=np.full(max(n_frame, 1), KF_UNTOUCHED, np.int32), proj=np.full((max(n, 1), 2), KF_UNTOUCHED, np.float32),
+                 level=np.full(max(n, 1), KF_UNTOUCHED, np.int32), gate=np.full(max(n, 1), KF_UNTOUCHED, np.int8))
+        for k in o: setattr(R[j], k, o[k].ctypes.data)
+        R[j].n_matches = R[j].n_searched = R[j].status = KF_UNTOUCHED
+        keep.append((a, o, n))
+    return P, K, R, keep
+
+
+def _kfs_finish(R, keep, n_frame):
+    out = []
+    for j, (_, o, n) in enumerate(keep):
+        d = dict(n_matches=R[j].n_matches, n_searched=R[j].n_searched, status=R[j].status, kernel_ms=tuple(R[j].kernel_ms))
+        for k in ("match_idx", "match_dist", "proj", "level", "gate"): d[k] = o[k][:n]
+        d["feature_kf"] = o["feature_kf"][:n_frame]
+        out.append(d)
+    return out
+
+
 def line_struct_params(**kw):
     """the reference's values (hvo_line_struct_default_params) with the given fields replaced (mode, row_rule, ...)"""
     p = LineStructParams()
@@ -792,6 +862,10 @@ def lib():
         L.hvo_pnp_ransac.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(PnpParams), C.c_int, C.POINTER(PnpProblem), C.POINTER(PnpResult)]
         L.hvo_stream_pnp_ransac.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(PnpParams), C.c_int, C.POINTER(PnpKeyframeSide), C.POINTER(PnpResult)]
         L.hvo_pnp_last_kernel_ms.argtypes = [C.c_void_p, C.c_void_p]
+        L.hvo_search_by_projection_keyframe.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(KfSearchParams), C.POINTER(LocalPointsFrame), C.c_int,
+                                                        C.POINTER(KfSearchCandidate), C.POINTER(KfSearchResult)]
+        L.hvo_stream_search_by_projection_keyframe.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(KfSearchParams), C.c_int,
+                                                               C.POINTER(KfSearchCandidate), C.POINTER(KfSearchResult)]
         L.hvo_stream_pnp_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.hvo_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_stream_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
@@ -1498,6 +1572,24 @@ class Context:
             self._chk(rc, "pnp_ransac")
         return _pnp_finish(R, rk, P.min_set)
 
+    def search_by_projection_keyframe(self, cam, t_kp_un, t_desc, bounds4, kfs, th=10.0, orb_dist=100, check_orientation=True,
+                                      log_scale_factor=float(np.log(np.float32(1.2))), n_levels=8, check=True):
+        """ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1499-1628) of a frame on host arrays
+        (mvKeysUn, mDescriptors) for every candidate of kfs (dicts: pos, skip, max_dist, min_dist, desc, angle, Tcw, occupied) in one call.
+        Returns one dict per candidate: match_idx, match_dist (per key-frame entry), feature_kf (per frame feature), proj, level, gate,
+        n_matches, n_searched, status, kernel_ms.  check=False: (return code, message, the dicts) instead of an exception; a refused call
+        leaves every output at KF_UNTOUCHED."""
+        kp = np.ascontiguousarray(t_kp_un, KEYPOINT_DT); nt = len(kp)
+        d = np.ascontiguousarray(t_desc, np.uint8).reshape(nt, 32)
+        F = LocalPointsFrame(); F.n = nt; F.kp_un = kp.ctypes.data if nt else None; F.uright = None; F.desc = d.ctypes.data if nt else None
+        P, K, R, keep = _kfs_args(nt, kfs, bounds4, th, orb_dist, check_orientation, log_scale_factor, n_levels)
+        cm = _pose_cam(cam)
+        rc = lib().hvo_search_by_projection_keyframe(self.h, C.byref(cm), C.byref(P), C.byref(F), len(kfs), K, R)
+        if not check:
+            return rc, lib().hvo_last_error(self.h).decode(), _kfs_finish(R, keep, nt)
+        self._chk(rc, "search_by_projection_keyframe")
+        return _kfs_finish(R, keep, nt)
+
     def pnp_last_kernel_ms(self):
         """(hypothesis kernels, refine kernels): device ms of the last pnp_ransac"""
         ms = np.zeros(2, np.float32)
@@ -1954,6 +2046,19 @@ class Stream:
         if rc != -5 or check:
             self._chk(rc, "stream_pnp_ransac")
         return _pnp_finish(R, rk, P.min_set)
+
+    def search_by_projection_keyframe(self, cur, cam, n_kp, kfs, th=10.0, orb_dist=100, check_orientation=True,
+                                      log_scale_factor=float(np.log(np.float32(1.2))), n_levels=8, check=True):
+        """Context.search_by_projection_keyframe on the resident frame `cur` (needs STAGE_ORB): key points and descriptors stay on the
+        device, the bounds are the frame grid's, only the candidates go up.  n_kp: the frame's key-point count (the length of occupied and
+        feature_kf)."""
+        P, K, R, keep = _kfs_args(int(n_kp), kfs, None, th, orb_dist, check_orientation, log_scale_factor, n_levels)
+        cm = _pose_cam(cam)
+        rc = lib().hvo_stream_search_by_projection_keyframe(self.h, cur, C.byref(cm), C.byref(P), len(kfs), K, R)
+        if not check:
+            return rc, lib().hvo_stream_last_error(self.h).decode(), _kfs_finish(R, keep, int(n_kp))
+        self._chk(rc, "stream_search_by_projection_keyframe")
+        return _kfs_finish(R, keep, int(n_kp))
 
     def pnp_last_kernel_ms(self, cur):
         ms = np.zeros(2, np.float32)

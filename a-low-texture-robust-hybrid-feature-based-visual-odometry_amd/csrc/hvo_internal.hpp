@@ -156,6 +156,7 @@ struct hvo_ctx {
     void *tail = nullptr;                  // resident-batch Frame tail (tail.hip)
     hipEvent_t bow_ev[4] = { nullptr, nullptr, nullptr, nullptr }; float bow_ms[2] = { 0.f, 0.f }; bool bow_ev_on[2] = { false, false };   // bow.hip: events around the last calls' launches
     hipEvent_t pnp_ev[3] = { nullptr, nullptr, nullptr }; float pnp_ms[2] = { 0.f, 0.f }; bool pnp_ev_on = false;   // pnp.hip: events around the last call's two kernel groups
+    hipEvent_t kfs_ev[3] = { nullptr, nullptr, nullptr };   // kf_search.hip: events around the last call's prologue and its searches
     BowState bow_batch, bow_call;          // bow.hip: the resident batch's bag of words (cleared by hvo_batch_run), the host-array form's block
     // opaque per-subsystem state (peac.hip / lsd.hip own these)
     void *peac = nullptr;
@@ -504,6 +505,13 @@ int bow_search(hvo_ctx *ctx, hipStream_t st, const hvo_bow_keyframe *F, const Fr
 // the constructor's compaction runs on the device over kf[j]'s map side.
 int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_params *P, int n_kf, const hvo_pnp_problem *prob, const FrameView *fr,
             const hvo_pnp_keyframe_side *kf, hvo_pnp_result *res, std::string *err);
+
+// kf_search.hip: ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) of n_kf candidates on stream st, staging and
+// scratch from ctx's call arena; returns after the stream has drained (its only synchronisation).  fr: the frame's undistorted key points and
+// descriptors on the device (n_kp of them), its bounds and mvScaleFactors; host set: fr's arrays are null and the host arrays go up with the
+// candidates.
+int kfs_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_kf_search_params *P, const FrameView *fr, const hvo_local_points_frame *host,
+            int n_kf, const hvo_kf_search_candidate *kf, hvo_kf_search_result *res, std::string *err);
 
 // pose_opt.hip: Optimizer::PoseOptimization of n frames in one launch on stream st, scratch from ctx's call arena; returns after the stream
 // has drained.  fr null: prob's frame-side host arrays go up too; else frame f's frame side is read at fr[f]'s device pointers.

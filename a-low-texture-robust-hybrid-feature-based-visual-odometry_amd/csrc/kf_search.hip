@@ -1,0 +1,258 @@
+// kf_search.hip -- ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (reference src/ORBmatcher.cc:1499-1628), the
+// refinement Tracking::Relocalization runs between its pose optimisations (src/Tracking.cc:3871 with (10, 100), :3885 with (3, 64)), for
+// n_kf candidate key frames in one call, each under its own pose and its own occupancy of the frame's features.
+//
+//   k_kf_project   one launch for all candidates (blockIdx.y = candidate), one lane per key-frame entry: skip, projection, the four bounds
+//                  tests, the distance range, MapPoint::PredictScale against the current frame (src/MapPoint.cc:400-415); it writes the query
+//                  arrays SbpDev names (u, v, radius, band [level - 1, level + 1], blocks) and proj / level / gate for the caller.  An entry
+//                  that fails a gate gets k_project_last's out-of-grid sentinel: the search core touches no train feature for it.
+//   k_search_by_projection, k_sbp_epilogue (match.hip, unchanged, map_mode = 0) once per candidate: ranked window candidates, the in-order
+//                  pass under the occupancy bit set (t_occ = occupied, q_blocks = 1 for every entry), the rescan, the 30-bin rotation
+//                  histogram of kf angle - frame angle and ComputeThreeMaxima.  th_high = ORBdist: bestDist starts at 256, only strictly
+//                  smaller distances enter, and bestDist <= ORBdist accepts -- no ratio test, no mvuRight gate (q_ur and t_uright are null).
+//   k_kf_inverse   feature_kf[match_idx[i]] = i (every match blocks, so no feature is taken twice); an entry without a match gets distance 256
+//
+// The grid of every launch is sized by n, which the host knows: all candidates are enqueued before the call's single synchronisation.
+// Staging (the candidates, and the frame's arrays in the host-array form) and scratch come from the context's call arena.
+//
+// What distinguishes this call from its siblings (k_project_last, k_lp_frustum):
+//   no depth-sign test     a point behind the camera whose projection lands inside the bounds and whose distance is in range IS searched;
+//                          z == 0 gives inf (a bounds gate) or NaN, and a NaN passes the four bounds tests and finds no candidate
+//   every feature blocks   CurrentFrame.mvpMapPoints[i2] != NULL skips i2, whatever that point's observations; every accepted match is such
+//                          a point for the entries after it, also one the rotation cull removes at the end
+//   bestDist <= ORBdist    ORBdist > 255 would accept bestIdx2 = -1 and write mvpMapPoints[-1]: refused
+//
+// Readings (OpenCV is not in the reference tree; DESIGN.md section 7, tests/kf_search_ref.py restates the same):
+//   Rcw * x3Dw + tcw       gemm3_row (match.hip; sm_row is the same text): the row's products summed in FLOAT left to right, then
+//                          (float)((double)sum * 1.0 + (double)t * 1.0)
+//   invzc = 1.0 / z        k_project_last's reading: the text divides the double 1.0, the quotient is rounded to float
+//   u, v                   fx * xc * invzc + cx in float, left to right
+//   Ow                     -Rcw^T tcw with double sums, times -1.0, rounded to float (match_project_setup's twc)
+//   x3Dw - Ow              float, element-wise
+//   cv::norm               sqrt of the double sum of squares, stored to float
+//   1.2f * mfMaxDistance   float products (GetMaxDistanceInvariance / GetMinDistanceInvariance)
+//   PredictScale           exactly k_lp_frustum's: float ratio, logf, float division, ceilf, saturating conversion (NaN -> 0), clamp to
+//                          [0, n_levels - 1]
+//   radius                 th * mvScaleFactors[level], a float product; the scale factors are the context's
+// No contraction (-ffp-contract=off, __f*_rn).
+#include "slot_map.hpp"
+#include "frame_view.hpp"
+#include <math.h>
+#include <string.h>
+#include <string>
+#include <vector>
+
+#define KFS_BLOCK 256
+#define KFS_MAXQ 16384            // entries per candidate (SBP_MAXQ of match.hip)
+#define KFS_MAXT 65535            // frame features (the search core's keys hold the feature in 16 bits)
+
+struct KfsCand { float R[9], t[3], Ow[3]; int n; };
+struct KfsDev {
+    const KfsCand *cand; int cq, n_levels;                       // candidate j's arrays start at j * cq (pos: component c at (3 j + c) * cq)
+    const float *pos, *maxd, *mind; const uint8_t *skip;
+    float fx, fy, cx, cy, minX, maxX, minY, maxY, logsf, th; float sf[HVO_MAX_LEVELS];
+    float *q_u, *q_v, *q_rad; int *q_min, *q_max; uint8_t *q_blocks;
+    float *proj; int32_t *level; int8_t *gate; int32_t *mi, *md; int *counters;     // counters: (n_matches, n_searched) per candidate
+};
+
+__global__ __launch_bounds__(KFS_BLOCK) void k_kf_project(KfsDev a)
+{
+    const int j = blockIdx.y, i = blockIdx.x * KFS_BLOCK + threadIdx.x;
+    const KfsCand &c = a.cand[j];
+    const bool in = i < c.n;
+    const size_t cq = (size_t)a.cq, o = (size_t)j * cq + (in ? (size_t)i : 0);
+    int g = HVO_KF_GATE_SKIP, lvl = -1, lo = 0, hi = -1;
+    float u = 1e30f, v = 1e30f, radius = 0.f, pu = 0.f, pv = 0.f;  // an entry that fails a gate: no grid cell, never searched (k_project_last)
+    if (in && !a.skip[o]) {
+        const size_t p = (size_t)j * 3 * cq + (size_t)i;
+        const float X = a.pos[p], Y = a.pos[p + cq], Z = a.pos[p + 2 * cq];
+        const float xc = sm_row(c.R, X, Y, Z, c.t[0]), yc = sm_row(c.R + 3, X, Y, Z, c.t[1]), zc = sm_row(c.R + 6, X, Y, Z, c.t[2]);
+        const float invzc = (float)(1.0 / (double)zc);             // ORBmatcher.cc:1529; no sign test follows
+        pu = __fadd_rn(__fmul_rn(__fmul_rn(a.fx, xc), invzc), a.cx); pv = __fadd_rn(__fmul_rn(__fmul_rn(a.fy, yc), invzc), a.cy);
+        g = pu < a.minX ? HVO_KF_GATE_U_MIN : pu > a.maxX ? HVO_KF_GATE_U_MAX : pv < a.minY ? HVO_KF_GATE_V_MIN : pv > a.maxY ? HVO_KF_GATE_V_MAX : 0;   // (a NaN compares false four times)
+        if (g == 0) {
+            const float mfMax = a.maxd[o], mfMin = a.mind[o];
+            const float maxD = __fmul_rn(1.2f, mfMax), minD = __fmul_rn(0.8f, mfMin);
+            const double d0 = __fsub_rn(X, c.Ow[0]), d1 = __fsub_rn(Y, c.Ow[1]), d2 = __fsub_rn(Z, c.Ow[2]);
+            const float dist = (float)sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+            g = dist < minD ? HVO_KF_GATE_DIST_MIN : dist > maxD ? HVO_KF_GATE_DIST_MAX : 0;
+            if (g == 0) {
+                const float ratio = __fdiv_rn(mfMax, dist);
+                const float lv = ceilf(__fdiv_rn(logf(ratio), a.logsf));
+                int l = sm_level(lv);
+                if (l < 0) l = 0; else if (l >= a.n_levels) l = a.n_levels - 1;      // MapPoint.cc:409-412
+                lvl = l; u = pu; v = pv; radius = __fmul_rn(a.th, a.sf[l]); lo = l - 1; hi = l + 1;
+            }
+        }
+    }
+    if (in) {
+        a.q_u[o] = u; a.q_v[o] = v; a.q_rad[o] = radius; a.q_min[o] = lo; a.q_max[o] = hi; a.q_blocks[o] = 1;
+        reinterpret_cast<float2 *>(a.proj)[o] = make_float2(pu, pv); a.level[o] = lvl; a.gate[o] = (int8_t)g;
+        a.mi[o] = -1; a.md[o] = 256;                               // what stays where no search runs (a frame without features)
+    }
+    const unsigned long long s = __ballot(in && g == 0);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(&a.counters[2 * j + 1], __popcll(s));
+}
+
+__global__ __launch_bounds__(KFS_BLOCK) void k_kf_inverse(int n, int nt, const int32_t *__restrict__ mi, int32_t *__restrict__ md, int32_t *__restrict__ fk)
+{
+    const int i = blockIdx.x * KFS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int m = mi[i];
+    if (m >= 0 && m < nt) fk[m] = i;                               // CurrentFrame.mvpMapPoints[bestIdx2] = pMP
+    else md[i] = 256;                                              // no match, or culled by the rotation histogram
+}
+
+static std::string kfs_limit_text(int n, int nt)
+{
+    return "key-frame search: " + std::to_string(n) + " key-frame entries, " + std::to_string(nt) + " frame features (limits: " + std::to_string(KFS_MAXQ) +
+           ", " + std::to_string(KFS_MAXT) + "); nothing was written";
+}
+
+int kfs_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_kf_search_params *P, const FrameView *fr, const hvo_local_points_frame *host,
+            int n_kf, const hvo_kf_search_candidate *kf, hvo_kf_search_result *res, std::string *err)
+{
+    const int nt = fr->n_kp;
+    // ---- refusals: whole, before anything is written ----
+    if (P->orb_dist > 255) { *err = "key-frame search: orb_dist above 255 (bestDist starts at 256: the reference would write mvpMapPoints[-1])"; return HVO_ERR_INVALID_ARG; }
+    if (P->n_levels < 1 || P->n_levels > HVO_MAX_LEVELS) { *err = "key-frame search: n_levels outside 1 .. 16"; return HVO_ERR_INVALID_ARG; }
+    if (!(fr->bounds[1] > fr->bounds[0]) || !(fr->bounds[3] > fr->bounds[2])) { *err = "key-frame search: empty image bounds"; return HVO_ERR_INVALID_ARG; }
+    if (nt < 0 || (host && nt > 0 && (!host->kp_un || !host->desc))) { *err = "key-frame search: a frame with n < 0 or a null array"; return HVO_ERR_INVALID_ARG; }
+    int nmax = 0;
+    for (int j = 0; j < n_kf; j++) {
+        const hvo_kf_search_candidate &K = kf[j];
+        if (K.n < 0 || (K.n > 0 && (!K.pos || !K.skip || !K.max_dist || !K.min_dist || !K.desc)) || !res[j].match_idx) {
+            *err = "key-frame search: a candidate with n < 0, a null array or no match_idx"; return HVO_ERR_INVALID_ARG;
+        }
+        if (K.n > 0 && P->check_orientation && !K.angle) { *err = "key-frame search: check_orientation without the key frame's angles"; return HVO_ERR_INVALID_ARG; }
+        nmax = std::max(nmax, (int)K.n);
+    }
+    for (int j = 0; j < n_kf; j++) if (kf[j].n > KFS_MAXQ || nt > KFS_MAXT) { *err = kfs_limit_text(kf[j].n, nt); return HVO_ERR_UNSUPPORTED; }
+    // ---- one carve of the context's arena: what goes up, the queries, what comes down, the search's key rows ----
+    const size_t cq = (size_t)std::max(64, (nmax + 63) & ~63), ntp = (size_t)std::max(64, (nt + 63) & ~63), F = (size_t)n_kf;
+    SmCarve C;
+    const size_t u_cand = C.take(F * sizeof(KfsCand)), u_pos = C.take(F * 3 * cq * 4), u_maxd = C.take(F * cq * 4), u_mind = C.take(F * cq * 4), u_ang = C.take(F * cq * 4),
+                 u_desc = C.take(F * cq * 32), u_skip = C.take(F * cq), u_occ = C.take(F * ntp);
+    const size_t u_kp = C.take(host ? ntp * sizeof(hvo_keypoint) : 0), u_fd = C.take(host ? ntp * 32 : 0);
+    const size_t up_end = C.o;
+    const size_t q_u = C.take(F * cq * 4), q_v = C.take(F * cq * 4), q_rad = C.take(F * cq * 4), q_min = C.take(F * cq * 4), q_max = C.take(F * cq * 4), q_blk = C.take(F * cq);
+    const size_t r0 = C.o;
+    const size_t r_cnt = C.take(F * 2 * 4), r_fk = C.take(F * ntp * 4), r_mi = C.take(F * cq * 4), r_md = C.take(F * cq * 4), r_lvl = C.take(F * cq * 4),
+                 r_proj = C.take(F * cq * 8), r_gate = C.take(F * cq);
+    const size_t r1 = C.o;                                       // [r0, r1) comes down
+    const size_t s_keys = C.take(match_sbp_scratch_bytes((int)cq));      // the candidates' searches run one after the other on the stream and share the key rows
+    char *d = (char *)hvo_call_arena(ctx, C.o);
+    if (!d) { *err = "key-frame search: arena"; return HVO_ERR_HIP; }
+    std::vector<char> h(up_end, 0);
+    for (int j = 0; j < n_kf; j++) {
+        const hvo_kf_search_candidate &K = kf[j];
+        KfsCand &c = ((KfsCand *)&h[u_cand])[j];
+        for (int r = 0; r < 3; r++) { for (int k = 0; k < 3; k++) c.R[3 * r + k] = K.Tcw[4 * r + k]; c.t[r] = K.Tcw[4 * r + 3]; }
+        for (int r = 0; r < 3; r++) {                              // Ow = -Rcw^T tcw (match_project_setup's twc)
+            double s0 = 0;
+            for (int k = 0; k < 3; k++) s0 += (double)c.R[3 * k + r] * (double)c.t[k];
+            c.Ow[r] = (float)(s0 * -1.0);
+        }
+        c.n = K.n;
+        const size_t n = (size_t)K.n;
+        float *hp = (float *)&h[u_pos] + (size_t)j * 3 * cq;
+        for (size_t i = 0; i < n; i++) if (!K.skip[i]) for (int k = 0; k < 3; k++) hp[k * cq + i] = K.pos[3 * i + k];      // by component: a wave's load is contiguous
+        if (n) {
+            memcpy((float *)&h[u_maxd] + j * cq, K.max_dist, n * 4); memcpy((float *)&h[u_mind] + j * cq, K.min_dist, n * 4);
+            if (K.angle) memcpy((float *)&h[u_ang] + j * cq, K.angle, n * 4);
+            memcpy(&h[u_desc] + j * cq * 32, K.desc, n * 32); memcpy(&h[u_skip] + j * cq, K.skip, n);
+        }
+        if (nt && K.occupied) memcpy(&h[u_occ] + j * ntp, K.occupied, (size_t)nt);
+    }
+    FrameView V = *fr;
+    if (host) {
+        if (nt) { memcpy(&h[u_kp], host->kp_un, (size_t)nt * sizeof(hvo_keypoint)); memcpy(&h[u_fd], host->desc, (size_t)nt * 32); }
+        V.kp_un = (const hvo_keypoint *)(d + u_kp); V.desc = (const uint8_t *)(d + u_fd);
+    }
+    if (hipMemcpyAsync(d, h.data(), up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = "key-frame search: upload"; return HVO_ERR_HIP; }
+    // (the memsets follow the copy: a copy from pageable memory waits for what the stream holds)
+    if (hipMemsetAsync(d + r_cnt, 0, F * 2 * 4, st) != hipSuccess || hipMemsetAsync(d + r_fk, 0xFF, F * ntp * 4, st) != hipSuccess) { *err = "key-frame search: memset"; return HVO_ERR_HIP; }
+    bool ev_on = true;
+    for (int i = 0; i < 3; i++) if (!ctx->kfs_ev[i] && hipEventCreate(&ctx->kfs_ev[i]) != hipSuccess) ev_on = false;
+    if (ev_on) ev_on = hipEventRecord(ctx->kfs_ev[0], st) == hipSuccess;
+    KfsDev a; memset(&a, 0, sizeof(a));
+    a.cand = (const KfsCand *)(d + u_cand); a.cq = (int)cq; a.n_levels = P->n_levels;
+    a.pos = (const float *)(d + u_pos); a.maxd = (const float *)(d + u_maxd); a.mind = (const float *)(d + u_mind); a.skip = (const uint8_t *)(d + u_skip);
+    a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy;
+    a.minX = V.bounds[0]; a.maxX = V.bounds[1]; a.minY = V.bounds[2]; a.maxY = V.bounds[3]; a.logsf = P->log_scale_factor; a.th = P->th;
+    for (int l = 0; l < HVO_MAX_LEVELS; l++) a.sf[l] = V.sf[l];
+    a.q_u = (float *)(d + q_u); a.q_v = (float *)(d + q_v); a.q_rad = (float *)(d + q_rad); a.q_min = (int *)(d + q_min); a.q_max = (int *)(d + q_max); a.q_blocks = (uint8_t *)(d + q_blk);
+    a.proj = (float *)(d + r_proj); a.level = (int32_t *)(d + r_lvl); a.gate = (int8_t *)(d + r_gate); a.mi = (int32_t *)(d + r_mi); a.md = (int32_t *)(d + r_md);
+    a.counters = (int *)(d + r_cnt);
+    if (nmax > 0) hipLaunchKernelGGL(k_kf_project, dim3((nmax + KFS_BLOCK - 1) / KFS_BLOCK, n_kf), dim3(KFS_BLOCK), 0, st, a);
+    if (ev_on) ev_on = hipEventRecord(ctx->kfs_ev[1], st) == hipSuccess;
+    for (int j = 0; j < n_kf; j++) {
+        const int n = kf[j].n;
+        if (n < 1 || nt < 1) continue;
+        const size_t q0 = (size_t)j * cq;
+        SbpDev s; memset(&s, 0, sizeof(s));
+        s.q_desc = (const uint8_t *)(d + u_desc) + 32 * q0; s.q_desc_index = nullptr;
+        s.q_u = a.q_u + q0; s.q_v = a.q_v + q0; s.q_radius = a.q_rad + q0; s.q_min_level = a.q_min + q0; s.q_max_level = a.q_max + q0; s.q_ur = nullptr;
+        s.q_angle = (const float *)(d + u_ang) + q0; s.q_blocks = a.q_blocks + q0;
+        s.t_kp = V.kp_un; s.t_uright = nullptr; s.t_occ = kf[j].occupied ? (const uint8_t *)(d + u_occ) + (size_t)j * ntp : nullptr; s.t_desc = V.desc;
+        s.nq = n; s.nt = nt; s.mnMinX = V.bounds[0]; s.mnMaxX = V.bounds[1]; s.mnMinY = V.bounds[2]; s.mnMaxY = V.bounds[3];
+        s.th_high = P->orb_dist; s.check_orientation = P->check_orientation ? 1 : 0; s.map_mode = 0; s.nn_ratio = 0.f;
+        s.match_idx = a.mi + q0; s.match_dist = a.md + q0; s.n_matches = a.counters + 2 * j;
+        const int rc = match_sbp_enqueue(st, s, d + s_keys);
+        if (rc) { *err = rc == HVO_ERR_UNSUPPORTED ? kfs_limit_text(n, nt) : "key-frame search: search launch"; return rc; }
+        hipLaunchKernelGGL(k_kf_inverse, dim3((n + KFS_BLOCK - 1) / KFS_BLOCK), dim3(KFS_BLOCK), 0, st, n, nt, (const int32_t *)s.match_idx, s.match_dist,
+                           (int32_t *)(d + r_fk) + (size_t)j * ntp);
+    }
+    if (ev_on) ev_on = hipEventRecord(ctx->kfs_ev[2], st) == hipSuccess;
+    if (hipGetLastError() != hipSuccess) { *err = "key-frame search: launch"; return HVO_ERR_HIP; }
+    std::vector<char> hr(r1 - r0);
+    if (hipMemcpyAsync(hr.data(), d + r0, r1 - r0, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        *err = std::string("key-frame search: ") + hipGetErrorString(hipGetLastError()); return HVO_ERR_HIP;
+    }
+    float ms[2] = { 0.f, 0.f };
+    if (ev_on) {
+        if (hipEventElapsedTime(&ms[0], ctx->kfs_ev[0], ctx->kfs_ev[1]) != hipSuccess) ms[0] = 0.f;
+        if (hipEventElapsedTime(&ms[1], ctx->kfs_ev[1], ctx->kfs_ev[2]) != hipSuccess) ms[1] = 0.f;
+    }
+    const char *b = hr.data() - r0;
+    for (int j = 0; j < n_kf; j++) {
+        hvo_kf_search_result &R = res[j];
+        const size_t n = (size_t)kf[j].n, q0 = (size_t)j * cq;
+        const int *cnt = (const int *)(b + r_cnt) + 2 * j;
+        R.n_matches = cnt[0]; R.n_searched = cnt[1]; R.status = HVO_OK; R.kernel_ms[0] = ms[0]; R.kernel_ms[1] = ms[1];
+        if (n) {
+            memcpy(R.match_idx, (const int32_t *)(b + r_mi) + q0, n * 4);
+            if (R.match_dist) memcpy(R.match_dist, (const int32_t *)(b + r_md) + q0, n * 4);
+            if (R.proj) memcpy(R.proj, (const float *)(b + r_proj) + 2 * q0, n * 8);
+            if (R.level) memcpy(R.level, (const int32_t *)(b + r_lvl) + q0, n * 4);
+            if (R.gate) memcpy(R.gate, (const int8_t *)(b + r_gate) + q0, n);
+        }
+        if (R.feature_kf && nt) memcpy(R.feature_kf, (const int32_t *)(b + r_fk) + (size_t)j * ntp, (size_t)nt * 4);
+    }
+    return HVO_OK;
+}
+
+extern "C" {
+
+int hvo_search_by_projection_keyframe(hvo_ctx *ctx, const hvo_camera *cam, const hvo_kf_search_params *params, const hvo_local_points_frame *frame,
+                                      int n_kf, const hvo_kf_search_candidate *candidates, hvo_kf_search_result *results)
+{
+    if (!ctx) return HVO_ERR_INVALID_ARG;
+    if (!cam || !params || !frame || !candidates || !results || n_kf < 1) { ctx->last_error = "key-frame search: a null argument or n_kf < 1"; return HVO_ERR_INVALID_ARG; }
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    FrameView F; memset(&F, 0, sizeof(F));
+    F.ctx = ctx; F.n_kp = frame->n; F.sf = ctx->scale; memcpy(F.bounds, params->bounds, sizeof(F.bounds));
+    return kfs_run(ctx, ctx->stream, cam, params, &F, frame, n_kf, candidates, results, &ctx->last_error);
+}
+
+int hvo_stream_search_by_projection_keyframe(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_kf_search_params *params,
+                                             int n_kf, const hvo_kf_search_candidate *candidates, hvo_kf_search_result *results)
+{
+    if (!s) return HVO_ERR_INVALID_ARG;
+    if (!cam || !params || !candidates || !results || n_kf < 1) { s->last_error = "key-frame search: a null argument or n_kf < 1"; return HVO_ERR_INVALID_ARG; }
+    FrameView B; int rc;
+    if ((rc = stream_view(s, cur, need_kf_search, s->s_match, B))) return rc;
+    return kfs_run(B.ctx, s->s_match, cam, params, &B, nullptr, n_kf, candidates, results, &s->last_error);
+}
+
+}   // extern "C"

@@ -4,8 +4,8 @@
 // `iterate(5, bNoMore, vbInliers, nInliers)` loop as a host replay, and Optimizer::PoseOptimization with the accepted candidate's inliers.
 // The frames but the last play the candidate key frames (camera = world for each: its features with depth are its map points); the last
 // frame is the one to relocalise.  Between its upload and the optimised pose only the key frames' arrays, the match vectors and the matched
-// positions cross PCIe.  The candidate query (DetectRelocalizationCandidates) and SearchByProjection(Frame, KeyFrame, ...) stay on the host
-// and are not part of this example.  No vocabulary file is needed: a small random k = 8, L = 3 tree is generated.
+// positions cross PCIe.  The candidate query (DetectRelocalizationCandidates) stays on the host; SearchByProjection(Frame, KeyFrame, ...) and
+// the optimisations around it are examples/relocalization_refine.cpp.  Neither is part of this example.  No vocabulary file is needed: a small random k = 8, L = 3 tree is generated.
 // Reads raw 640x480 gray (u8) + depth (u16) pairs.
 //
 // build:  g++ -std=c++14 -Iinclude examples/relocalization_pnp.cpp -L<csrc> -lhvo -Wl,-rpath,<csrc> -o relocalization_pnp
@@ -133,7 +133,7 @@ int main(int argc, char **argv)
                 printf("candidate %d at iteration %d: PnP %d inliers, PoseOptimization %d good, t = (%.5f %.5f %.5f)\n", i, solvers[c].mnIterations, nInliers, nGood,
                        r.Tcw[3], r.Tcw[7], r.Tcw[11]);
                 if (nGood < 10) continue;
-                // (nGood < 50: SearchByProjection(mCurrentFrame, vpCandidateKFs[i], ...) would widen the match set here -- the host's, out of scope)
+                // (nGood < 50: SearchByProjection(mCurrentFrame, vpCandidateKFs[i], ...) would widen the match set here: examples/relocalization_refine.cpp)
                 bMatch = true; accepted = i;
             }
         }

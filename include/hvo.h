@@ -1075,6 +1075,57 @@ int hvo_stream_pnp_ransac(hvo_stream *s, int64_t cur, const hvo_camera *cam, con
 int hvo_pnp_last_kernel_ms(const hvo_ctx *ctx, float ms2[2]);
 int hvo_stream_pnp_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2]);
 
+/* ---- ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1499-1628; csrc/kf_search.hip) ----
+ * The refinement Tracking::Relocalization runs between its pose optimisations (Tracking.cc:3871 with (10, 100), :3885 with (3, 64)): every
+ * map point of a candidate key frame that is not bad and not already found is projected under the frame's pose, gated by the image bounds
+ * and its distance range, given a predicted level, and searched in the frame's grid within [level - 1, level + 1].  n_kf candidates go in
+ * one call, each with its own pose and its own occupancy.  Unlike the other guided searches there is NO depth-sign test (a point behind
+ * the camera whose projection lands inside the bounds is searched; z == 0 gives inf or NaN, and a NaN passes the bounds tests and finds
+ * nothing), EVERY non-NULL feature blocks (occupied at entry, or taken by an earlier entry of the same candidate), and a match is accepted
+ * when bestDist <= orb_dist (no ratio test, no mvuRight gate).  Entries are walked in order; a later entry takes its next best free feature. */
+typedef struct {
+    int32_t n;                 /* pKF->GetMapPointMatches().size() */
+    const float   *pos;        /* n x 3, GetWorldPos() (CV_32F); not read where skip[i] */
+    const uint8_t *skip;       /* n: !pMP || pMP->isBad() || sAlreadyFound.count(pMP) */
+    const float   *max_dist, *min_dist;   /* RAW mfMaxDistance / mfMinDistance; the 1.2f / 0.8f factors are applied by the call, as in hvo_point_map */
+    const uint8_t *desc;       /* n x 32, pMP->GetDescriptor() */
+    const float   *angle;      /* n, pKF->mvKeysUn[i].angle; may be NULL when check_orientation == 0 */
+    float Tcw[12];             /* CurrentFrame.mTcw rows 0..2 for THIS candidate */
+    const uint8_t *occupied;   /* frame's N: CurrentFrame.mvpMapPoints[i2] != NULL at entry (NULL: none) */
+} hvo_kf_search_candidate;
+typedef struct {
+    float th; int32_t orb_dist; int32_t check_orientation; float log_scale_factor; int32_t n_levels;
+    float bounds[4];           /* mnMinX, mnMaxX, mnMinY, mnMaxY (host-array form; the stream form takes the bounds of its feature grid) */
+} hvo_kf_search_params;
+/* gate codes, in the reference's order */
+#define HVO_KF_GATE_SEARCHED 0
+#define HVO_KF_GATE_SKIP     1      /* skip[i] */
+#define HVO_KF_GATE_U_MIN    2      /* u < mnMinX */
+#define HVO_KF_GATE_U_MAX    3      /* u > mnMaxX */
+#define HVO_KF_GATE_V_MIN    4      /* v < mnMinY */
+#define HVO_KF_GATE_V_MAX    5      /* v > mnMaxY */
+#define HVO_KF_GATE_DIST_MIN 6      /* dist3D < 0.8f * mfMinDistance */
+#define HVO_KF_GATE_DIST_MAX 7      /* dist3D > 1.2f * mfMaxDistance */
+typedef struct {               /* per candidate; every pointer but match_idx may be NULL */
+    int32_t *match_idx, *match_dist;   /* n: the frame feature entry i was assigned to, after the rotation cull (-1 / 256 = none) */
+    int32_t *feature_kf;               /* frame's N: the key-frame entry now holding feature i2, -1 = none (the inverse; occupied features stay -1) */
+    float *proj; int32_t *level; int8_t *gate;   /* n x 2 (u, v), n, n: what the prologue decided.  proj is (0, 0) for a skipped entry;
+                                                  * level is -1 for every entry that was not searched */
+    int32_t n_matches, n_searched, status; float kernel_ms[2];   /* return value; entries with gate 0; prologue and search device time (of the whole call) */
+} hvo_kf_search_result;
+/* On host arrays.  cam: fx, fy, cx, cy are read; frame: kp_un, desc, n (uright is not read); the scale factors are the context's.
+ * Limits: 16384 entries per candidate, 65535 frame features (HVO_ERR_UNSUPPORTED beyond); n_levels outside 1 .. 16, empty bounds, a
+ * missing array or orb_dist > 255 (the reference would then write mvpMapPoints[-1]) are HVO_ERR_INVALID_ARG.  Every refusal is whole:
+ * nothing is written and hvo_last_error says why.  A candidate with n == 0 and a frame without features are HVO_OK with no match.
+ * All candidates are enqueued before the call's single synchronisation. */
+int hvo_search_by_projection_keyframe(hvo_ctx *ctx, const hvo_camera *cam, const hvo_kf_search_params *params, const hvo_local_points_frame *frame,
+                                      int n_kf, const hvo_kf_search_candidate *candidates, hvo_kf_search_result *results);
+/* On the resident frame `cur`: undistorted key points and descriptors are read where the stages left them, the bounds are the frame grid's
+ * (params->bounds is ignored); only the candidates go up.  The stream must run HVO_STAGE_ORB: otherwise HVO_ERR_INVALID_ARG with
+ * hvo_stream_last_error set.  The result is the host-array form's on the downloaded frame, bit for bit. */
+int hvo_stream_search_by_projection_keyframe(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_kf_search_params *params,
+                                             int n_kf, const hvo_kf_search_candidate *candidates, hvo_kf_search_result *results);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer. Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

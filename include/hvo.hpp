@@ -245,9 +245,40 @@ private:
     hvo_ctx *ctx_;
 };
 
+class FrameStream;
+// A candidate key frame as SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) reads it: one entry per feature of
+// pKF->GetMapPointMatches() -- GetWorldPos(), the RAW mfMaxDistance / mfMinDistance, GetDescriptor(), mvKeysUn[i].angle.  What the call skips
+// (!pMP, isBad(), sAlreadyFound.count(pMP)) is the `skip` argument, a byte per entry; positions of skipped entries are not read.
+struct KeyFrameSide {
+    int n = 0;
+    const float *pos = nullptr, *max_dist = nullptr, *min_dist = nullptr; const uint8_t *desc = nullptr; const float *angle = nullptr;
+};
+// what the search leaves: per key-frame entry the frame feature it was assigned to (-1: none) and the distance; per frame feature the entry
+// that now holds it (-1: none) -- CurrentFrame.mvpMapPoints[i2] = vpMPs[feature_kf[i2]] where feature_kf[i2] >= 0
+struct KeyFrameMatches { std::vector<int> match_idx, match_dist, feature_kf; int n_searched = 0; float kernel_ms[2] = { 0.f, 0.f }; };
+
 class ORBmatcher {
 public:
     static const int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;       // ORBmatcher.cc:37-39
+    // SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:1499-1628), Relocalization's refinement, on the resident
+    // frame `cur` under the pose Tcw (rows 0..2 of mTcw): nothing of the frame comes down.  occupied: a byte per frame feature,
+    // mvpMapPoints[i2] != NULL at entry (n_features of them).  Returns nmatches; see hvo.h for the three things that set this search apart.
+    int SearchByProjection(FrameStream &fs, int64_t cur, const hvo_camera &cam, const float Tcw[12], const KeyFrameSide &kf, const uint8_t *skip,
+                           const uint8_t *occupied, int n_features, float th, int ORBdist, KeyFrameMatches &res, bool checkOrientation = true,
+                           float logScaleFactor = 0.18232161f, int nLevels = 8) const;
+    // the same on host arrays: mvKeysUn, mDescriptors and the image bounds (mnMinX, mnMaxX, mnMinY, mnMaxY) go up with the call
+    int SearchByProjection(const hvo_camera &cam, const float bounds[4], const KeyPoint *kp_un, const uint8_t *desc, int n_features, const float Tcw[12],
+                           const KeyFrameSide &kf, const uint8_t *skip, const uint8_t *occupied, float th, int ORBdist, KeyFrameMatches &res,
+                           bool checkOrientation = true, float logScaleFactor = 0.18232161f, int nLevels = 8) const
+    {
+        hvo_kf_search_candidate c; hvo_kf_search_params p; hvo_kf_search_result r;
+        kf_search_fill(Tcw, kf, skip, occupied, n_features, th, ORBdist, checkOrientation, logScaleFactor, nLevels, res, c, p, r);
+        for (int k = 0; k < 4; k++) p.bounds[k] = bounds[k];
+        hvo_local_points_frame f = { kp_un, nullptr, desc, n_features };
+        check(hvo_search_by_projection_keyframe(ctx_, &cam, &p, &f, 1, &c, &r), "hvo_search_by_projection_keyframe");
+        res.n_searched = r.n_searched; res.kernel_ms[0] = r.kernel_ms[0]; res.kernel_ms[1] = r.kernel_ms[1];
+        return r.n_matches;
+    }
     explicit ORBmatcher(hvo_ctx *ctx) : ctx_(ctx) {}
     // DescriptorDistance(a, b): 32-byte descriptors
     int DescriptorDistance(const uint8_t *a, const uint8_t *b) const
@@ -317,6 +348,17 @@ public:
         return r.n_matches;
     }
 private:
+    static void kf_search_fill(const float Tcw[12], const KeyFrameSide &kf, const uint8_t *skip, const uint8_t *occupied, int n_features, float th, int ORBdist,
+                               bool checkOrientation, float logScaleFactor, int nLevels, KeyFrameMatches &res, hvo_kf_search_candidate &c,
+                               hvo_kf_search_params &p, hvo_kf_search_result &r)
+    {
+        c = hvo_kf_search_candidate(); p = hvo_kf_search_params(); r = hvo_kf_search_result();
+        c.n = kf.n; c.pos = kf.pos; c.skip = skip; c.max_dist = kf.max_dist; c.min_dist = kf.min_dist; c.desc = kf.desc; c.angle = kf.angle; c.occupied = occupied;
+        for (int k = 0; k < 12; k++) c.Tcw[k] = Tcw[k];
+        p.th = th; p.orb_dist = ORBdist; p.check_orientation = checkOrientation ? 1 : 0; p.log_scale_factor = logScaleFactor; p.n_levels = nLevels;
+        res.match_idx.assign((size_t)std::max(kf.n, 1), -1); res.match_dist.assign((size_t)std::max(kf.n, 1), 256); res.feature_kf.assign((size_t)std::max(n_features, 1), -1);
+        r.match_idx = res.match_idx.data(); r.match_dist = res.match_dist.data(); r.feature_kf = res.feature_kf.data();
+    }
     hvo_ctx *ctx_;
 };
 
@@ -779,6 +821,17 @@ struct Frame {
         for (int j = 0; j < n_kf; j++) nmatches[j] = r[j].n_matches;
     }
 };
+
+inline int ORBmatcher::SearchByProjection(FrameStream &fs, int64_t cur, const hvo_camera &cam, const float Tcw[12], const KeyFrameSide &kf, const uint8_t *skip,
+                                          const uint8_t *occupied, int n_features, float th, int ORBdist, KeyFrameMatches &res, bool checkOrientation,
+                                          float logScaleFactor, int nLevels) const
+{
+    hvo_kf_search_candidate c; hvo_kf_search_params p; hvo_kf_search_result r;
+    kf_search_fill(Tcw, kf, skip, occupied, n_features, th, ORBdist, checkOrientation, logScaleFactor, nLevels, res, c, p, r);
+    check(hvo_stream_search_by_projection_keyframe(fs.get(), cur, &cam, &p, 1, &c, &r), "hvo_stream_search_by_projection_keyframe");
+    res.n_searched = r.n_searched; res.kernel_ms[0] = r.kernel_ms[0]; res.kernel_ms[1] = r.kernel_ms[1];
+    return r.n_matches;
+}
 
 // Optimizer (include/Optimizer.h, src/Optimizer.cc:590-1478): PoseOptimization on the mirror's frame handle.  The map side (one row per feature:
 // the matched map point's / map line's world position, the planes of the three roles as world coefficients or as slots of a PlaneMap) is what
