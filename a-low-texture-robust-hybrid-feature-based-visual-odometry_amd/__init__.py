@@ -90,6 +90,7 @@ EXPORTS = [
     "hvo_bow_last_kernel_ms", "hvo_stream_bow_last_kernel_ms",
     "hvo_pnp_default_params", "hvo_pnp_ransac", "hvo_stream_pnp_ransac", "hvo_pnp_last_kernel_ms", "hvo_stream_pnp_last_kernel_ms",
     "hvo_search_by_projection_keyframe", "hvo_stream_search_by_projection_keyframe",
+    "hvo_update_map_planes", "hvo_stream_update_map_planes", "hvo_plane_map_get_points", "hvo_plane_update_transform",
 ]
 
 
@@ -162,6 +163,43 @@ class PlaneMatch(C.Structure):
 
 
 assert C.sizeof(PlaneMatch) == 8 + 5 * 64 * 4 + 64 * 16
+
+PLANE_UPDATE_MERGE, PLANE_UPDATE_INSERT, PLANE_UPDATE_MAX_POINTS = 0, 1, 1 << 20
+
+
+class PlaneUpdate(C.Structure):
+    """hvo_plane_update: up to 64 operations (frame plane, slot, PLANE_UPDATE_MERGE / _INSERT), applied in list order"""
+    _fields_ = [("n", C.c_int32), ("plane", C.c_int32 * 64), ("slot", C.c_int32 * 64), ("op", C.c_int32 * 64)]
+
+
+class PlaneUpdateResult(C.Structure):
+    _fields_ = [("status", C.c_int32 * 64), ("n_frame", C.c_int32 * 64), ("n_before", C.c_int32 * 64), ("n_after", C.c_int32 * 64), ("n_done", C.c_int32)]
+
+    def to_dict(self, n):
+        return dict(n_done=self.n_done, **{k: np.array(getattr(self, k)[:n], np.int32) for k in ("status", "n_frame", "n_before", "n_after")})
+
+
+def _plane_update_arg(ops):
+    """ops: a PlaneUpdate, or a sequence of (plane, slot, op)"""
+    if isinstance(ops, PlaneUpdate):
+        return ops, max(0, min(ops.n, 64))
+    ops = list(ops)
+    if len(ops) > 64:
+        raise ValueError("at most 64 plane updates per call")
+    u = PlaneUpdate(); u.n = len(ops)
+    for k, (p, s_, o) in enumerate(ops):
+        u.plane[k] = p; u.slot[k] = s_; u.op[k] = o
+    return u, len(ops)
+
+
+def plane_update_transform(Tcw):
+    """the matrix a MERGE applies to the frame's cloud: rows 0..2 of inverse(toSE3Quat(Tcw)) as (3, 4) doubles (host arithmetic, no device)"""
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(12); M = np.zeros(12, np.float64)
+    rc = lib().hvo_plane_update_transform(_p(T), _p(M))
+    if rc != HVO_OK:
+        raise HvoError(rc, "plane_update_transform")
+    return M.reshape(3, 4)
+
 
 PLANE_MATCH_DEFAULT_TH = (0.1, 0.86, 0.08716, 0.9962)       # PlaneMatcher's constructor defaults (include/PlaneMatcher.h:17)
 
@@ -815,6 +853,10 @@ def lib():
         L.hvo_match_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PlaneMatch), C.c_void_p, C.c_void_p]
         L.hvo_stream_match_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PlaneMatch)]
         L.hvo_batch_match_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hvo_update_map_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PlaneUpdate), C.POINTER(PlaneUpdateResult)]
+        L.hvo_stream_update_map_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PlaneUpdate), C.POINTER(PlaneUpdateResult)]
+        L.hvo_plane_map_get_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.hvo_plane_update_transform.argtypes = [C.c_void_p, C.c_void_p]
         L.hvo_line_map_create.argtypes = [C.c_int, C.c_int]; L.hvo_line_map_create.restype = C.c_void_p
         L.hvo_line_map_destroy.argtypes = [C.c_void_p]; L.hvo_line_map_destroy.restype = None
         L.hvo_line_map_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int]
@@ -976,6 +1018,13 @@ class PlaneMap:
         c = np.zeros(4, np.float32); n, b = C.c_int(0), C.c_int(0)
         self._chk(lib().hvo_plane_map_slot(self.h, slot, _p(c), C.byref(n), C.byref(b)), "plane_map_slot")
         return c, n.value, bool(b.value)
+
+    def points(self, slot):
+        """the slot's cloud as the map holds it -> (n, 3) float32"""
+        n = self.slot(slot)[1]
+        x = np.zeros((n, 3), np.float32); m = C.c_int(0)
+        self._chk(lib().hvo_plane_map_get_points(self.h, slot, _p(x) if n else None, n, C.byref(m)), "plane_map_get_points")
+        return x
 
 
 class _SlotMap:
@@ -1446,6 +1495,20 @@ class Context:
         self._chk(lib().hvo_match_planes(self.h, pmap.h, _p(c) if len(c) else None, len(c), _p(T), None if t is None else _p(t), C.byref(res),
                                          _p(dm) if matrices and dm.size else None, _p(am) if matrices and am.size else None), "match_planes")
         return (res, dm, am) if matrices else res
+
+    def update_map_planes(self, pmap, records, cloud, Tcw, ops, Twc=None):
+        """MapPlane::UpdateCoefficientsAndPoints (src/MapPlane.cc:300-368) on the resident PlaneMap from host arrays: records (PLANE_CLOUD_DT) and
+        cloud ((n, 3) floats) as plane_clouds / collect_tail return them; ops = (frame plane as match_planes numbers them, slot,
+        PLANE_UPDATE_MERGE / _INSERT) in list order; Twc (3 x 4, GetPoseInverse()) for an INSERT -> dict(status, n_frame, n_before, n_after, n_done)"""
+        r = np.ascontiguousarray(records, PLANE_CLOUD_DT).reshape(-1)
+        c = np.ascontiguousarray(cloud, np.float32).reshape(-1, 3)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12)
+        W = None if Twc is None else np.ascontiguousarray(Twc, np.float32).reshape(12)
+        u, n = _plane_update_arg(ops)
+        res = PlaneUpdateResult()
+        self._chk(lib().hvo_update_map_planes(self.h, pmap.h, _p(r) if len(r) else None, len(r), _p(c) if len(c) else None, len(c), _p(T),
+                                              None if W is None else _p(W), C.byref(u), C.byref(res)), "update_map_planes")
+        return res.to_dict(n)
 
     def batch_match_planes(self, pmap, Tcw, th=None):
         """the first len(Tcw) frames of the resident batch (needs STAGE_PLANE_TAIL in the last batch_run), frame k under Tcw[k] (3 x 4), every
@@ -2181,6 +2244,16 @@ class Stream:
         res = PlaneMatch()
         self._chk(lib().hvo_stream_match_planes(self.h, pmap.h, cur, _p(T), None if t is None else _p(t), C.byref(res)), "stream_match_planes")
         return res
+
+    def update_map_planes(self, pmap, cur, Tcw, ops, Twc=None):
+        """MapPlane::UpdateCoefficientsAndPoints on the resident frame `cur` (needs STAGE_PLANES | STAGE_PLANE_TAIL and depth): the frame's plane
+        clouds stay on the device; ops and the result as Context.update_map_planes"""
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12)
+        W = None if Twc is None else np.ascontiguousarray(Twc, np.float32).reshape(12)
+        u, n = _plane_update_arg(ops)
+        res = PlaneUpdateResult()
+        self._chk(lib().hvo_stream_update_map_planes(self.h, pmap.h, cur, _p(T), None if W is None else _p(W), C.byref(u), C.byref(res)), "stream_update_map_planes")
+        return res.to_dict(n)
 
     def match_lines(self, frm, to, mode=LINE_MATCH_NNR, th=50.0, nnratio=0.95):
         m = np.full(self.kl_cap, -1, np.int32); n1 = C.c_int(0); n = C.c_int(0)

@@ -25,6 +25,9 @@ const FrameNeed need_guided_lines  = { "guided line search", HVO_STAGE_GRIDS, tr
 const FrameNeed need_map_lines     = { "local-map line search", HVO_STAGE_GRIDS | HVO_STAGE_LINES3D, true, FV_DEPTH_STREAM, "no 3-D lines", false, false, FV_N_KL | FV_N_LN, FV_EV_LSD,
                                        "HVO_STAGE_GRIDS and HVO_STAGE_LINES3D", "HVO_STAGE_GRIDS and HVO_STAGE_LINES3D" };
 
+static const char k_pu_list[] = "HVO_STAGE_PLANES and HVO_STAGE_PLANE_TAIL";
+const FrameNeed need_plane_update  = { "plane map update", HVO_STAGE_PLANES | HVO_STAGE_PLANE_TAIL, false, FV_DEPTH_STREAM, "no plane clouds", false, false, FV_N_PC, FV_EV_PEAC, k_pu_list, k_pu_list };
+
 static int refuse(std::string &err, const FrameNeed &nd, const char *a, const char *b = "", const char *c = "")
 {
     err = std::string(nd.what) + ": " + a + b + c;
@@ -90,6 +93,7 @@ int batch_views(hvo_ctx *ctx, int n, const FrameNeed &nd, std::vector<FrameView>
         if (d_out) {
             char *o = d_out + (size_t)f * L.total;
             v.l3d = (hvo_line3d *)(o + L.lines3d); v.pclouds = (const hvo_plane_cloud *)(o + L.pclouds); v.normals = (const hvo_surface_normal *)(o + L.normals);
+            v.cloud_xyz = (const float *)(o + L.cloud); v.cloud_cap = L.cloud_cap;
             v.n_normals = L.n_normals; v.ln_start = (const int32_t *)(o + L.ln_start); v.ln_items = (const int32_t *)(o + L.ln_items); v.n_ln_items = L.ln_cap;
         }
         if (pv.d_depth) { v.depth = pv.d_depth + (size_t)f * pv.dframe; v.pitch = pv.pitch; v.w = ctx->batch_w; v.h = ctx->batch_h; v.dfac = ctx->p.depth_map_factor; }
@@ -121,12 +125,17 @@ int stream_view(hvo_stream *s, int64_t ticket, const FrameNeed &nd, hipStream_t 
     v.kl = B->lv.d_kl; v.fn = B->lv.d_fn; v.ldesc = B->lv.d_desc; v.d_nkl = B->lv.d_nkl; v.nfeat = s->nfeat;
     if (B->d_tail) {
         v.l3d = (hvo_line3d *)(B->d_tail + T.lines3d); v.pclouds = (const hvo_plane_cloud *)(B->d_tail + T.pclouds); v.normals = (const hvo_surface_normal *)(B->d_tail + T.normals);
+        v.cloud_xyz = (const float *)(B->d_tail + T.cloud); v.cloud_cap = T.cloud_cap;
         v.n_normals = T.n_normals; v.ln_start = (const int32_t *)(B->d_tail + T.ln_start); v.ln_items = (const int32_t *)(B->d_tail + T.ln_items);
     }
     v.sf = B->ctx->scale;
     for (int k = 0; k < 4; k++) v.bounds[k] = s->bounds[k];
     v.h_counts = (const int *)(B->h_out + s->lay.counts);
     frame_view_counts(v, nd.counts);
+    if (nd.counts & FV_N_PC) {
+        v.h_pclouds = (const hvo_plane_cloud *)(B->h_tail + T.pclouds);
+        v.n_cloud = std::max(0, std::min(((const int *)(B->h_tail + T.counts))[0], T.cloud_cap));
+    }
     if (nd.counts & FV_N_LN) {
         v.n_ln_items = ((const int *)(B->h_tail + T.counts))[3];
         if (v.n_ln_items < 0 || v.n_ln_items > T.ln_cap) { err = "line grid overflowed its capacity"; return HVO_ERR_CAPACITY; }

@@ -18,6 +18,8 @@ struct FrameView {
     int nfeat, n_kl;                        // n_kl: host count clamped to [0, nfeat]; -1: not fetched
     // frame tail: 3-D lines (line structure rewrites A, B), plane records, surface normals, the line grid
     hvo_line3d *l3d; const hvo_plane_cloud *pclouds; const hvo_surface_normal *normals; int n_normals;
+    const float *cloud_xyz; int cloud_cap;  // the plane tail's voxel clouds, packed xyz: record i's at [first, first + n_points)
+    const hvo_plane_cloud *h_pclouds; int n_cloud;          // stream, with FV_N_PC: the records as they came down, and the cloud's point count clamped to cloud_cap
     const int32_t *ln_start, *ln_items; int n_ln_items;     // stream: the downloaded item count; batch: the list's capacity (its count lives on the device)
     // depth image (batch only: it holds no mvuRight, the kernels form it like k_stereo_from_rgbd)
     const uint16_t *depth; int pitch, w, h; float dfac;
@@ -26,7 +28,7 @@ struct FrameView {
     const int *h_counts;                    // stream: where the frame's downloaded counts land (frame_view_counts)
 };
 
-enum : unsigned { FV_N_KP = 1, FV_N_KL = 2, FV_N_LN = 4 };                  // host counts an operation reads
+enum : unsigned { FV_N_KP = 1, FV_N_KL = 2, FV_N_LN = 4, FV_N_PC = 8 };     // host counts an operation reads (FV_N_PC: the plane records too)
 enum : unsigned { FV_EV_ORB = 1, FV_EV_LSD = 2, FV_EV_PEAC = 4 };           // a slot's events an operation's inputs lie behind
 enum : unsigned { FV_DEPTH_STREAM = 1, FV_DEPTH_BATCH = 2, FV_DEPTH = 3 };  // the forms that refuse a frame without depth
 
@@ -42,7 +44,7 @@ struct FrameNeed {
 
 // the rows (frame_view.hip)
 extern const FrameNeed need_manhattan, need_planes, need_pose, need_line_struct, need_local_lines, need_local_points, need_bow, need_bow_search, need_pnp, need_kf_search,
-                       need_guided_points, need_line_match, need_guided_lines, need_map_lines;
+                       need_guided_points, need_line_match, need_guided_lines, need_map_lines, need_plane_update;
 
 // The first n frames of ctx's resident batch.  Refusals in the batch calls' order: n within the batch, stages, depth, bf; then
 // hipSetDevice, the plan lookups and ONE count copy for all n frames.

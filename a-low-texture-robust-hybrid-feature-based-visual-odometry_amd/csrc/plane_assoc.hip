@@ -29,33 +29,11 @@
 #include <string>
 #include <vector>
 
-#define PA_MAXP 64                 // frame planes per frame = the tail's plane_clouds records
-#define PA_CHUNK 1024              // points per wave of the distance pass: 4 dwordx4 per lane and coordinate
-#define PA_DIST_WAVES 4
-
-struct PaChunk { long long xoff; int cap, count, slot, pad; };   // xoff: pool index of the chunk's first x; count: points, a multiple of 4
-
-struct PaSlot { size_t first = 0; int cap = 0, npts = 0; };
-
-struct hvo_plane_map {
-    int device = 0;
-    hipStream_t st = nullptr;                                    // the map's own uploads
-    int n_slots = 0, slot_cap = 0;
-    std::vector<PaSlot> slot; std::vector<float> h_coef; std::vector<int32_t> h_bad;
-    float *d_coef = nullptr; int32_t *d_bad = nullptr;           // slot_cap entries
-    float *d_pool = nullptr; size_t pool_cap = 0, pool_used = 0; // floats
-    float *h_stage = nullptr; size_t stage_cap = 0;              // pinned: one cloud transposed
-    std::vector<PaChunk> chunks; bool chunks_dirty = true;
-    PaChunk *d_chunks = nullptr; size_t chunk_cap = 0;
-    char *d_scr = nullptr, *h_scr = nullptr; size_t scr_bytes = 0, hscr_bytes = 0;   // the matching calls' scratch, grow-only
-    std::string last_error;
-};
-
-#define PM_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { m->last_error = std::string(#call) + ": " + hipGetErrorString(e_); return HVO_ERR_HIP; } } while (0)
+#include "plane_map.hpp"
 
 static size_t pa_al(size_t v) { return (v + 255) & ~(size_t)255; }
 
-static int pm_reserve_slots(hvo_plane_map *m, int want)
+int pm_reserve_slots(hvo_plane_map *m, int want)
 {
     if (want <= m->slot_cap) return HVO_OK;
     int cap = std::max(m->slot_cap, 64);
@@ -75,7 +53,7 @@ static int pm_reserve_slots(hvo_plane_map *m, int want)
     return HVO_OK;
 }
 
-static int pm_reserve_pool(hvo_plane_map *m, size_t want)
+int pm_reserve_pool(hvo_plane_map *m, size_t want)
 {
     if (want <= m->pool_cap) return HVO_OK;
     size_t cap = std::max(m->pool_cap, (size_t)3 * 4096);
@@ -89,6 +67,29 @@ static int pm_reserve_pool(hvo_plane_map *m, size_t want)
     }
     if (m->d_pool) (void)hipFree(m->d_pool);
     m->d_pool = np; m->pool_cap = cap;
+    return HVO_OK;
+}
+
+int pm_scratch(hvo_plane_map *m, hipStream_t st, size_t dbytes, size_t hbytes)
+{
+    if (m->scr_bytes < dbytes) {
+        size_t cap = std::max(m->scr_bytes, (size_t)1 << 16);
+        while (cap < dbytes) cap *= 2;
+        PM_HIP(hipStreamSynchronize(st));
+        if (m->d_scr) (void)hipFree(m->d_scr);
+        m->d_scr = nullptr; m->scr_bytes = 0;
+        PM_HIP(hipMalloc((void **)&m->d_scr, cap));
+        m->scr_bytes = cap;
+    }
+    if (m->hscr_bytes < hbytes) {
+        size_t cap = std::max(m->hscr_bytes, (size_t)1 << 14);
+        while (cap < hbytes) cap *= 2;
+        PM_HIP(hipStreamSynchronize(st));
+        if (m->h_scr) (void)hipHostFree(m->h_scr);
+        m->h_scr = nullptr; m->hscr_bytes = 0;
+        PM_HIP(hipHostMalloc((void **)&m->h_scr, cap, hipHostMallocDefault));
+        m->hscr_bytes = cap;
+    }
     return HVO_OK;
 }
 
@@ -415,20 +416,7 @@ int pa_match(hipStream_t st, hvo_plane_map *m, const float *coef, int n, const h
     const size_t b_in = pa_al((size_t)nframes * 48 + PA_MAXP * 16), b_res = pa_al((size_t)nframes * sizeof(hvo_plane_match)),
                  b_gate = pa_al((size_t)nframes * ns * 8), b_mat = pa_al((size_t)nframes * PA_MAXP * ns * 4);
     const size_t bytes = b_in + b_res + b_gate + 2 * b_mat, hbytes = b_in + b_res;
-    if (m->scr_bytes < bytes) {
-        PM_HIP(hipStreamSynchronize(st));
-        if (m->d_scr) (void)hipFree(m->d_scr);
-        m->d_scr = nullptr; m->scr_bytes = 0;
-        PM_HIP(hipMalloc((void **)&m->d_scr, bytes));
-        m->scr_bytes = bytes;
-    }
-    if (m->hscr_bytes < hbytes) {
-        PM_HIP(hipStreamSynchronize(st));
-        if (m->h_scr) (void)hipHostFree(m->h_scr);
-        m->h_scr = nullptr; m->hscr_bytes = 0;
-        PM_HIP(hipHostMalloc((void **)&m->h_scr, hbytes, hipHostMallocDefault));
-        m->hscr_bytes = hbytes;
-    }
+    if ((rc = pm_scratch(m, st, bytes, hbytes))) return rc;
     float *h_in = (float *)m->h_scr;
     memcpy(h_in, Tcw, (size_t)nframes * 48);
     if (coef && n) memcpy(h_in + (size_t)nframes * 12, coef, (size_t)n * 16);

@@ -535,7 +535,7 @@ int hvo_batch_track_manhattan(hvo_ctx *ctx, int n, const float R0[9], hvo_mf_res
  *
  * hvo_plane_map: the map's planes resident on one device -- per slot the world coefficients, a bad flag and the cloud (mvPlanePoints' xyz).
  * A slot's index is its position in the vector the tracker would have passed.  The map belongs to a device, not to a context: any hvo_ctx or
- * hvo_stream of that device may match against it.  Like a context it is NOT thread-safe: one call at a time on a map, the matching calls
+ * hvo_stream of that device may match against it.  Like a context it is NOT thread-safe: one call at a time on a map, the matching and update calls
  * included (they use the map's grow-only scratch).  Every call here returns after its device work has finished, so a set is visible to the
  * next match, and nothing is allocated by a call once the slot table, the point pool and the scratch have grown to the sizes in use. */
 typedef struct hvo_plane_map hvo_plane_map;
@@ -578,6 +578,52 @@ int hvo_stream_match_planes(hvo_stream *s, hvo_plane_map *m, int64_t cur, const 
 /* The first n frames of the resident batch (after hvo_batch_run with HVO_STAGE_PLANE_TAIL), frame k under Tcw + 12 k, in one launch
  * sequence: the map's clouds are read once for all n frames.  res: n entries. */
 int hvo_batch_match_planes(hvo_ctx *ctx, hvo_plane_map *m, int n, const float *Tcw, const float th[4], hvo_plane_match *res);
+
+/* ---- MapPlane::UpdateCoefficientsAndPoints on the resident plane map (csrc/plane_update.hip) ----
+ * The call Tracking::Track() makes for every matched plane of every tracked frame (reference src/Tracking.cc:796-804, body
+ * src/MapPlane.cc:337-368) and the no-argument overload CreateNewKeyFrame / StereoInitialization run on a new MapPlane (MapPlane.cc:300-335,
+ * Tracking.cc:3208-3213, :1407), on clouds that stay on the device.
+ *   MERGE   the frame's voxel cloud of plane i under inverse(toSE3Quat(Tcw)) (hvo_plane_update_transform), the slot's cloud appended,
+ *           pcl::VoxelGrid(0.1) over both, the result is the slot's new cloud.  The slot's coefficients and flag stay; a bad slot is updated
+ *           like a good one (Tracking.cc:800 does not look at isBad()).
+ *   INSERT  the frame's voxel cloud of plane i under Twc (the caller's float GetPoseInverse(), each entry widened to double), the voxel grid,
+ *           nothing appended; the slot's coefficients become ComputePlaneWorldCoeff(i) = the pM[i] of hvo_plane_match under Tcw.  The slot is
+ *           set or replaced with hvo_plane_map_set's rules: a slot past the end extends the map, the skipped ones start bad and empty, a new
+ *           slot starts good, a replaced one keeps its flag.
+ * A transformed point is (float)(M00 x + M01 y + M02 z + M03) per row, in double, left to right.  The voxel grid is the one of
+ * hvo_plane_clouds (oracle/planes_tail.c): float bounding box, inverse_leaf = 1.0f / 0.1f, min_b = floor(min * inverse_leaf), voxel
+ * (int)(floorf(p * inverse_leaf) - (float)min_b) per axis, index i + j div0 + k div0 div1, one centroid per non-empty voxel in ascending
+ * index order, the centroid the exact mean (2^-24 m fixed point in 64-bit integers, rounded to float once): no result depends on the order
+ * of the points.  A point with a coordinate that is not finite is dropped before the bounding box.  The pcl::SACSegmentation block that
+ * follows in the reference writes only locals and is not run; mWorldPos is not changed by a MERGE.
+ * `plane`: frame plane i as hvo_plane_match numbers them (the i-th valid record).  Operations apply in list order: a later operation on the
+ * same slot sees the earlier one's result; operations on different slots run at once.
+ * A refused operation -- more than HVO_PLANE_UPDATE_MAX_POINTS frame + slot points, or a voxel index that overflows (a min_b / max_b outside
+ * int32, or dx dy dz > INT32_MAX, where PCL returns the cloud unfiltered) -- gets status HVO_ERR_UNSUPPORTED and its slot stays bit for bit
+ * as it was (an INSERT that would have extended the map does not); the others are done and the call returns HVO_OK.
+ * A malformed list -- n outside 0..64, a plane index not below the frame's valid planes, a record whose cloud lies outside cloud_xyz, a
+ * MERGE into a slot that does not exist (an INSERT earlier in the list makes it exist), an INSERT without Twc, a slot outside
+ * 0..HVO_PLANE_MAP_MAX_SLOTS-1, an unknown op -- is HVO_ERR_INVALID_ARG before anything is touched, with the reason in the last-error text.
+ * result: status / n_frame / n_before (the slot's points that entered: 0 for an INSERT) / n_after per operation, n_done = operations
+ * with status HVO_OK.  The call returns with its device work done: the next match sees the update. */
+#define HVO_PLANE_UPDATE_MERGE   0
+#define HVO_PLANE_UPDATE_INSERT  1
+#define HVO_PLANE_UPDATE_MAX_POINTS (1 << 20)
+typedef struct { int32_t n; int32_t plane[64], slot[64], op[64]; } hvo_plane_update;
+typedef struct { int32_t status[64], n_frame[64], n_before[64], n_after[64]; int32_t n_done; } hvo_plane_update_result;
+/* on host arrays: records (n_records <= 64) and cloud_xyz (n_cloud x 3 floats) as hvo_plane_clouds / hvo_stream_collect_tail return them */
+int hvo_update_map_planes(hvo_ctx *ctx, hvo_plane_map *m, const hvo_plane_cloud *records, int n_records, const float *cloud_xyz, int n_cloud,
+                          const float Tcw[12], const float Twc[12], const hvo_plane_update *upd, hvo_plane_update_result *res);
+/* on the resident frame `cur`: the clouds are read where HVO_STAGE_PLANE_TAIL left them; only the matrices and the list go up.  The stream
+ * must run HVO_STAGE_PLANES | HVO_STAGE_PLANE_TAIL and the frame must have been submitted with depth, else HVO_ERR_INVALID_ARG with
+ * hvo_stream_last_error set.  The frame's own results (hvo_stream_collect_tail, hvo_stream_collect) are not changed. */
+int hvo_stream_update_map_planes(hvo_stream *s, hvo_plane_map *m, int64_t cur, const float Tcw[12], const float Twc[12], const hvo_plane_update *upd,
+                                 hvo_plane_update_result *res);
+/* the slot's cloud as the map holds it: n x 3 floats into xyz (cap points; HVO_ERR_CAPACITY with *n set when cap is too small; xyz may be
+ * NULL when cap is 0) */
+int hvo_plane_map_get_points(const hvo_plane_map *m, int slot, float *xyz, int cap, int *n);
+/* the MERGE's matrix alone (host arithmetic in double, no device): rows 0..2 of inverse(toSE3Quat(Tcw)), row-major 3 x 4 */
+int hvo_plane_update_transform(const float Tcw[12], double M[12]);
 
 /* ---- Motion-only pose optimisation (csrc/pose_opt.hip) ----
  * Optimizer::PoseOptimization(Frame *) of the RGB-D tracker (reference src/Optimizer.cc:590-1478; called from src/Tracking.cc:2026, :2418, :2836

@@ -584,7 +584,9 @@ private:
 
 // The map's planes resident on one device (hvo_plane_map): per slot GetWorldPos(), isBad() and mvPlanePoints' xyz.  The slot index is the
 // position in the vector PlaneMatcher::SearchMapByCoefficients would have received (mpMap->GetAllMapPlanes()).  The local mapper calls set()
-// where MapPlane's constructor / UpdateCoefficientsAndPoints produce a cloud and setBad() where SetBadFlag runs.  Not thread-safe.
+// where a cloud is made on the host (MapPlane::Replace, the local mapper's multi-observation update) and setBad() where SetBadFlag runs.
+// MapPlane::UpdateCoefficientsAndPoints, both overloads as Tracking calls them, runs on the device: UpdateCoefficientsAndPoints() / insert().
+// Not thread-safe.
 class PlaneMap {
 public:
     explicit PlaneMap(int device = 0, int slots = 0, int64_t points = 0) : m_(hvo_plane_map_create(device, slots, points))
@@ -598,6 +600,56 @@ public:
     void setBad(int slot, bool bad = true) { check(hvo_plane_map_set_bad(m_, slot, bad ? 1 : 0), "hvo_plane_map_set_bad"); }
     int size() const { int n = 0; check(hvo_plane_map_counts(m_, &n, nullptr, nullptr), "hvo_plane_map_counts"); return n; }
     int64_t points() const { int64_t n = 0; check(hvo_plane_map_counts(m_, nullptr, nullptr, &n), "hvo_plane_map_counts"); return n; }
+    // mvPlanePoints of one slot as n x 3 floats (a viewer's read-back: nothing else needs the cloud on the host)
+    std::vector<float> points(int slot) const
+    {
+        int n = 0;
+        check(hvo_plane_map_slot(m_, slot, nullptr, &n, nullptr), "hvo_plane_map_slot");
+        std::vector<float> xyz(3 * (size_t)n);
+        check(hvo_plane_map_get_points(m_, slot, n ? xyz.data() : nullptr, n, &n), "hvo_plane_map_get_points");
+        return xyz;
+    }
+    // The loop of Tracking::Track() after the pose is known (src/Tracking.cc:796-804):
+    //   for i < mnPlaneNum: if mvpMapPlanes[i]: UpdateCoefficientsAndPoints(mCurrentFrame, i)   else if !mvbPlaneOutlier[i]: newPlane = true
+    // match: the association's result for that frame.  outlier: mvbPlaneOutlier, the flag of frame plane i at outlier[i * outlier_stride]
+    // (null = no plane is an outlier).  A tracker's own mvbPlaneOutlier is one byte per plane: stride 1.  The pose optimiser writes
+    // hvo_pose_flags.pl_outlier as n_planes x 3 bytes, per plane [mvbPlaneOutlier, mvbParPlaneOutlier, mvbVerPlaneOutlier]: pass that
+    // buffer with outlier_stride = kPoseFlagsPlaneStride, and only the first byte of each triple is read.
+    // Matched planes are updated whether or not they are outliers, as in the reference.
+    static const int kPoseFlagsPlaneStride = 3;
+    // the list of that loop alone (host only): the MERGE operations in `u`, the reference's flag in newPlane
+    static void trackUpdateList(const hvo_plane_match &match, const uint8_t *outlier, int outlier_stride, hvo_plane_update &u, bool &newPlane)
+    {
+        u = hvo_plane_update();
+        newPlane = false;
+        for (int i = 0; i < match.n_planes && i < 64; i++) {
+            if (match.match[i] >= 0) { u.plane[u.n] = i; u.slot[u.n] = match.match[i]; u.op[u.n] = HVO_PLANE_UPDATE_MERGE; u.n++; }
+            else if (!outlier || !outlier[(size_t)i * outlier_stride]) newPlane = true;
+        }
+    }
+    // the loop on the resident frame `cur`; returns the operations done
+    int UpdateCoefficientsAndPoints(FrameStream &fs, int64_t cur, const float Tcw[12], const hvo_plane_match &match, const uint8_t *outlier, bool &newPlane,
+                                    int outlier_stride = 1, hvo_plane_update_result *result = nullptr)
+    {
+        if (outlier_stride < 1) throw Error(HVO_ERR_INVALID_ARG, "PlaneMap::UpdateCoefficientsAndPoints: outlier_stride < 1");
+        hvo_plane_update u;
+        trackUpdateList(match, outlier, outlier_stride, u, newPlane);
+        hvo_plane_update_result r;
+        check(hvo_stream_update_map_planes(fs.get(), m_, cur, Tcw, nullptr, &u, &r), "hvo_stream_update_map_planes");
+        if (result) *result = r;
+        return r.n_done;
+    }
+    // CreateNewKeyFrame / StereoInitialization (src/Tracking.cc:3208-3213, :1407): new MapPlane(ComputePlaneWorldCoeff(i), pKF, i) and its
+    // UpdateCoefficientsAndPoints() for frame plane i of the resident frame `cur`, into `slot` (size() appends).  Twc: GetPoseInverse().
+    // Returns the points of the new cloud, or -1 when the operation was refused.
+    int insert(FrameStream &fs, int64_t cur, const float Tcw[12], const float Twc[12], int plane, int slot)
+    {
+        hvo_plane_update u = hvo_plane_update();
+        u.n = 1; u.plane[0] = plane; u.slot[0] = slot; u.op[0] = HVO_PLANE_UPDATE_INSERT;
+        hvo_plane_update_result r;
+        check(hvo_stream_update_map_planes(fs.get(), m_, cur, Tcw, Twc, &u, &r), "hvo_stream_update_map_planes");
+        return r.status[0] == HVO_OK ? r.n_after[0] : -1;
+    }
     hvo_plane_map *get() const { return m_; }
 private:
     hvo_plane_map *m_;
