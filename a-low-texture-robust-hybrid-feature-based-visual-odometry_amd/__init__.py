@@ -1282,6 +1282,19 @@ class Context:
             raise HvoError(-1, "lsd_images: the plan's scaled size is %d x %d" % (csw.value, csh.value))
         return {"mask": mask, "records": rec[:n.value].copy(), "dxy": dxy}
 
+    def lbd_desc(self, gray, keylines):
+        """diagnostics (not part of the reference interface): the 32-byte LBD descriptors of caller-supplied key lines (KEYLINE_DT) on one
+        image, by the plan's blur / Sobel and the descriptor kernels HVO_LBD_DESC selected when the plan was built.  The image is uploaded
+        as a batch of one: the resident batch and the results of the last batch_run are gone afterwards (upload and run again)"""
+        L = lib()
+        L.hvo_debug_lbd_desc.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.hvo_debug_lbd_desc.restype = C.c_int
+        gray = np.ascontiguousarray(gray, np.uint8); h, w = gray.shape
+        kl = np.ascontiguousarray(keylines, KEYLINE_DT)
+        desc = np.zeros((len(kl), 32), np.uint8)
+        self._chk(L.hvo_debug_lbd_desc(self.h, _p(gray), w, h, gray.strides[0], _p(kl), len(kl), _p(desc)), "lbd_desc")
+        return desc
+
     def peac_stats(self, frame=0):
         """diagnostics (not part of the reference interface): bookkeeping words of the last plane run of `frame`"""
         L = lib()

@@ -21,8 +21,10 @@
 //                                 emits segments, key-lines, the top-N selection and the line functions
 //   k_lbd_blur_sobel              GaussianBlur 5x5 sigma 1 (u8 fixed point) fused with Sobel dx, dy (s16);
 //                                 k_lbd_blur5 / k_lbd_sobel are the two-kernel formulation (HVO_LBD_SPLIT=1)
+//   k_lbd_line_setup              one line per lane: direction (the two fp64 calls), length, the 63 band rows' starts
 //   k_lbd_desc                    one 64-thread workgroup per line: 63 row sums, 9 band sums,
-//                                 normalisation, 32-byte binary descriptor
+//                                 normalisation, 32-byte binary descriptor; k_lbd_desc_v1 is the one-kernel
+//                                 formulation that starts from the key line (HVO_LBD_DESC=0)
 //
 // fp64/fp32 steps follow the oracle operation by operation (-ffp-contract=off).
 #include "hvo_internal.hpp"
@@ -66,6 +68,7 @@ struct LsdPlan {
     hvo_keyline *d_kl = nullptr; uint8_t *d_desc = nullptr; double *d_fn = nullptr; int *d_nkl = nullptr; int *d_flags = nullptr;
     hvo_keyline *d_kl2 = nullptr; uint8_t *d_desc2 = nullptr; double *d_fn2 = nullptr; int *d_nkl2 = nullptr;   // after cullingLine
     uint8_t *d_b5 = nullptr; short2 *d_dxy = nullptr;       // Sobel (dx, dy) interleaved
+    struct LbdLine *d_lbdl = nullptr;                       // k_lbd_line_setup's records for the lines of a chunk (nullptr: k_lbd_desc_v1 describes the lines)
     int *d_xofs = nullptr, *d_yofs = nullptr; float *d_xa = nullptr, *d_yb = nullptr;   // resize tables
     double k7[4] = { 0, 0, 0, 0 };                          // gaussian taps (double): k[0..3], symmetric
     int k5[3] = { 0, 0, 0 };
@@ -77,7 +80,7 @@ struct LsdPlan {
     // k_lsd_grow_async (lsd_async.inc), allocated at its first launch for the first `async_b` frames of the plan
     bool pre_fused = true;             // k_lsd_pre instead of k_lsd_blur + k_lsd_resize_grad (HVO_LSD_PRE_SPLIT=1: the pair, with its fp64 image)
     // tuning variables, read when the plan is built (lsd_build_plan)
-    struct { Knob dense, lat, async_w, async_early, async_lds, lat_lds, lbd_split, spin_max; } kn;
+    struct { Knob dense, lat, async_w, async_early, async_lds, lat_lds, lbd_split, lbd_desc, spin_max; } kn;
     uint8_t *d_b8 = nullptr, *d_s8 = nullptr; int *d_rs8tab = nullptr;      // HVO_READING_LSD_8U: the u8 blurred image and the u8 scaled image of a chunk, the resize tables (readings.hip)
     size_t async_w_cap = 0;            // (frame, worker) pairs the per-worker scratch holds
     int *d_redo = nullptr; int async_last_n = 0, async_last_w = 0;      // frames the one-wave kernel grew again after the async growing gave up; the last async launch
@@ -1326,10 +1329,12 @@ __constant__ int c_lbd_comb[32][2] = {
     { 2, 3 }, { 2, 4 }, { 2, 5 }, { 2, 6 }, { 2, 7 }, { 2, 8 }, { 3, 4 }, { 3, 5 }, { 3, 6 }, { 3, 7 }, { 3, 8 },
     { 4, 5 }, { 4, 6 }, { 4, 7 }, { 4, 8 }, { 5, 6 }, { 5, 7 }, { 5, 8 }, { 6, 7 }, { 6, 8 }, { 7, 8 } };
 
+// The descriptor as one kernel that starts from the key line (HVO_LBD_DESC=0, and every image with a side above LBD_SHORT_SAFE): the
+// formulation k_lbd_line_setup + k_lbd_desc below are checked against, byte for byte (tests/test_lbd_desc_forms_gpu.py)
 #define LBD_UNR 8
-__global__ __launch_bounds__(64) void k_lbd_desc(const short2 *__restrict__ dxyImg, int w, int h,
-                                                 const hvo_keyline *__restrict__ kls, const int *__restrict__ nkl, int kl_cap,
-                                                 const float *__restrict__ gL, const float *__restrict__ gG, uint8_t *__restrict__ desc)
+__global__ __launch_bounds__(64) void k_lbd_desc_v1(const short2 *__restrict__ dxyImg, int w, int h,
+                                                    const hvo_keyline *__restrict__ kls, const int *__restrict__ nkl, int kl_cap,
+                                                    const float *__restrict__ gL, const float *__restrict__ gG, uint8_t *__restrict__ desc)
 {
     __shared__ float rows[63][4];       // pgdL, ngdL, pgdO, ngdO row sums (already scaled by the global weight)
     __shared__ float band[9][8];
@@ -1490,6 +1495,236 @@ __global__ __launch_bounds__(64) void k_lbd_desc(const short2 *__restrict__ dxyI
         for (int i = 0; i < 72; i++) tmp = __fadd_rn(tmp, i < 64 ? lane_of(p0, i & 63) : lane_of(p1, i & 7));
         tmp = __fdiv_rn(1.f, sqrtf(tmp));
         __syncthreads();                                           // every lane has read its value(s)
+        dv[t] = __fmul_rn(v0, tmp);
+        if (t < 8) dv[64 + t] = __fmul_rn(v1, tmp);
+    }
+    __syncthreads();
+    if (t < 32) {
+        const float *f1 = dv + 8 * c_lbd_comb[t][0], *f2 = dv + 8 * c_lbd_comb[t][1];
+        unsigned r = 0;
+        for (int b = 0; b < 8; b++) if (f1[b] > f2[b]) r |= 1u << b;
+        desc[((size_t)f * kl_cap + line) * 32 + t] = (uint8_t)r;
+    }
+}
+
+// ---- the descriptor in two kernels (the default) ----
+// k_lbd_desc_v1 spends a quarter of its instructions on what is one line's scalar work, done by all 64 lanes: two fp64 libm calls and the
+// 62-step chain that takes band row t to its start.  k_lbd_line_setup does that work with one LINE per lane and leaves it in a per-chunk
+// scratch; k_lbd_desc (one workgroup per line, lane = band row, as before) loads it.  Every float operation of the reference is kept, in
+// its order; what changed is how many instructions surround it:
+//   addresses     (short)roundf(x) and two compare/select clamps -> (int)(x + copysign(0.49999997, x)) and one three-operand median.  The
+//                 sum-and-truncate is roundf for every |x| < 2^31 (tools/microbench/lbd_round_check.c walks the bit patterns); the
+//                 reference's wrap to short cannot happen while the sample coordinates stay inside +-32767, which LBD_SHORT_SAFE
+//                 guarantees for a detector's lines (image +- (length / 2 + 31)): larger images take k_lbd_desc_v1
+//   lengths       whole blocks of positions run without a test, the remainder in blocks of 16 / 8 / 4 / 2 / 1 chosen by the bits of the
+//                 (wave-uniform) count; the LDS tile of the along-rows branch is built and read back for the remainder's columns only
+//   sums          p += max(g, 0), n -= min(g, 0): the accumulators are +0 or positive, so adding +-0 leaves them as they are
+//   band sums     72 (band, quantity) chains on 64 lanes (+ 8 second values), 21 steps each in the reference's row order; rows outside
+//                 the image of bands (seven before, seven after) are zero rows: a +0 term leaves a sum that is +0 or positive unchanged
+//   norms         the ordered 36- and 72-term sums are read from LDS four terms at a time by every lane (no v_readlane per term): lanes
+//                 that scale a mean add the means' squares, lanes that scale a deviation the deviations', in one instruction stream
+#define LBD_SHORT_SAFE 16000
+struct LbdLine { float2 row[63]; float dL0, dL1; int len, pad; };      // the start of every band row, the direction, lengthOfLSP
+
+__global__ __launch_bounds__(64) void k_lbd_line_setup(const hvo_keyline *__restrict__ kls, const int *__restrict__ nkl, int kl_cap, int nframes,
+                                                       LbdLine *__restrict__ out)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= nframes * kl_cap) return;
+    const int f = i / kl_cap;
+    if (i - f * kl_cap >= nkl[f]) return;
+    const hvo_keyline kl = kls[i];
+    const short halfHeight = 31;
+    const short lengthOfLSP = (short)kl.num_pixels;
+    const short halfWidth = (short)((lengthOfLSP - 1) / 2);
+    const float midX = (float)(0.5 * (double)__fadd_rn(kl.sox, kl.eox));
+    const float midY = (float)(0.5 * (double)__fadd_rn(kl.soy, kl.eoy));
+    const float dL0 = (float)cos((double)kl.angle), dL1 = (float)sin((double)kl.angle);
+    // sCorX0/sCorY0 of row hID are reached by hID sequential updates in the reference
+    float sCorX0 = __fadd_rn(__fadd_rn(__fmul_rn(-dL0, (float)halfWidth), __fmul_rn(dL1, (float)halfHeight)), midX);
+    float sCorY0 = __fadd_rn(__fsub_rn(__fmul_rn(-dL1, (float)halfWidth), __fmul_rn(dL0, (float)halfHeight)), midY);
+    LbdLine *o = out + i;
+    o->row[0] = make_float2(sCorX0, sCorY0);
+    for (int q = 1; q < 63; q++) {
+        sCorX0 = __fsub_rn(sCorX0, dL1); sCorY0 = __fadd_rn(sCorY0, dL0);
+        o->row[q] = make_float2(sCorX0, sCorY0);
+    }
+    o->dL0 = dL0; o->dL1 = dL1; o->len = (int)lengthOfLSP; o->pad = 0;
+}
+
+// nearest integer, ties away from zero (roundf), clamped to [0, hi].  The clamp is applied to the float before it is truncated (one
+// v_med3_f32): a sum above hi, or below 0, truncates to a value the integer clamp would have brought to the same end, and hi is exact
+static __device__ __forceinline__ unsigned lbd_round_clamp(float x, float hi)
+{
+    return (unsigned)__builtin_amdgcn_fmed3f(__fadd_rn(x, copysignf(0x1.fffffep-2f, x)), 0.f, hi);
+}
+template <int N> struct LbdN { static constexpr int value = N; };
+
+__global__ __launch_bounds__(64) void k_lbd_desc(const int *__restrict__ dxyImg, int w, int h,
+                                                 const LbdLine *__restrict__ lines, const int *__restrict__ nkl, int kl_cap,
+                                                 const float *__restrict__ gL, const float *__restrict__ gG, uint8_t *__restrict__ desc)
+{
+    // The address tile of the along-rows branch (64 rows x 32 positions, pitch 33); the row sums and everything after them lie over it
+    __shared__ __align__(16) int tile[64 * 33];
+    float (*rows)[4] = reinterpret_cast<float (*)[4]>(tile);          // [7 + 63 + 7][4]: pgdL, ngdL, pgdO, ngdO row sums between zero rows
+    float *band = reinterpret_cast<float *>(tile) + 320;              // [72]: band sum 8 b + q
+    float *sqMS = reinterpret_cast<float *>(tile) + 400;              // [2][36]: squares of the means, of the deviations, in value order
+    float *sqAll = reinterpret_cast<float *>(tile) + 480;             // [72]: squares of the clipped values
+    float *dv = reinterpret_cast<float *>(tile) + 560;                // [72]
+    const int line = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
+    if (line >= nkl[f]) return;
+    const LbdLine *L = lines + ((size_t)f * kl_cap + line);
+    const float dL0 = L->dL0, dL1 = L->dL1;
+    const int len = max(L->len, 0);
+    const char *DXY = reinterpret_cast<const char *>(dxyImg + (size_t)f * w * h);     // (dx, dy) as one word, addressed by a 32-bit byte offset
+    const float xmax = (float)(w - 1), ymax = (float)(h - 1);
+    const unsigned pitch = 4u * (unsigned)w;                          // (24-bit products: h, 4 w < 2^24)
+    auto sample = [&](unsigned a) { return *reinterpret_cast<const int *>(DXY + a); };
+    // lane = band row; lane 63 walks row 62 once more (every address is clamped into the image) and its sums are dropped: no lane tests
+    const float2 start = L->row[min(t, 62)];
+    float sCorX = start.x, sCorY = start.y, pL = 0, nL = 0, pO = 0, nO = 0;
+    auto next_addr = [&]() {
+        const unsigned xCor = lbd_round_clamp(sCorX, xmax), yCor = lbd_round_clamp(sCorY, ymax);
+        sCorX = __fadd_rn(sCorX, dL0); sCorY = __fadd_rn(sCorY, dL1);
+        return __umul24(yCor, pitch) + (xCor << 2);
+    };
+    auto accumulate = [&](int g) {
+        const float ddx = (float)(short)(g & 0xFFFF), ddy = (float)(g >> 16);
+        const float gDL = __fadd_rn(__fmul_rn(ddx, dL0), __fmul_rn(ddy, dL1));
+        const float gDO = __fadd_rn(__fmul_rn(ddx, -dL1), __fmul_rn(ddy, dL0));
+        pL = __fadd_rn(pL, fmaxf(gDL, 0.f)); nL = __fsub_rn(nL, fminf(gDL, 0.f));
+        pO = __fadd_rn(pO, fmaxf(gDO, 0.f)); nO = __fsub_rn(nO, fminf(gDO, 0.f));
+    };
+    if (fabsf(dL0) > fabsf(dL1)) {
+        // along the image rows: 32 positions' addresses per row into the tile (lane = row), gathered with lane = position, accumulated with
+        // lane = row (k_lbd_desc_v1 says why)
+        int *mine = tile + t * 33;
+        auto fill = [&](auto n, int u0) {
+#pragma unroll
+            for (int u = 0; u < decltype(n)::value; u++) mine[u0 + u] = (int)next_addr();
+        };
+        auto take = [&](auto n, int u0) {
+#pragma unroll
+            for (int u = 0; u < decltype(n)::value; u++) accumulate(mine[u0 + u]);
+        };
+        for (int w0 = 0; w0 < len; w0 += 32) {
+            const int nu = min(32, len - w0);
+            if (nu == 32) { for (int u0 = 0; u0 < 32; u0 += 8) fill(LbdN<8>(), u0); }
+            else {
+                int u0 = 0;
+                if (nu & 16) { fill(LbdN<16>(), u0); u0 += 16; }
+                if (nu & 8) { fill(LbdN<8>(), u0); u0 += 8; }
+                if (nu & 4) { fill(LbdN<4>(), u0); u0 += 4; }
+                if (nu & 2) { fill(LbdN<2>(), u0); u0 += 2; }
+                if (nu & 1) fill(LbdN<1>(), u0);
+            }
+            __syncthreads();
+            {
+                const int u = t & 31, rh = t >> 5;
+                if (u < nu) {
+                    for (int r0 = 0; r0 < 64; r0 += 16) {          // eight instructions' loads in flight
+                        int av[8], gv[8];
+#pragma unroll
+                        for (int k = 0; k < 8; k++) av[k] = tile[(r0 + 2 * k + rh) * 33 + u];
+#pragma unroll
+                        for (int k = 0; k < 8; k++) gv[k] = sample((unsigned)av[k]);
+#pragma unroll
+                        for (int k = 0; k < 8; k++) tile[(r0 + 2 * k + rh) * 33 + u] = gv[k];
+                    }
+                }
+            }
+            __syncthreads();
+            if (nu == 32) { for (int u0 = 0; u0 < 32; u0 += 8) take(LbdN<8>(), u0); }
+            else {
+                int u0 = 0;
+                if (nu & 16) { take(LbdN<16>(), u0); u0 += 16; }
+                if (nu & 8) { take(LbdN<8>(), u0); u0 += 8; }
+                if (nu & 4) { take(LbdN<4>(), u0); u0 += 4; }
+                if (nu & 2) { take(LbdN<2>(), u0); u0 += 2; }
+                if (nu & 1) take(LbdN<1>(), u0);
+            }
+            __syncthreads();
+        }
+    } else {
+        // the gathers of a block are all issued before the first one is consumed; the signed sums are accumulated in the reference's order
+        auto block = [&](auto n) {
+            int g[decltype(n)::value];
+#pragma unroll
+            for (int u = 0; u < decltype(n)::value; u++) g[u] = sample(next_addr());
+#pragma unroll
+            for (int u = 0; u < decltype(n)::value; u++) accumulate(g[u]);
+        };
+        int w0 = 0;
+        for (; w0 + LBD_UNR <= len; w0 += LBD_UNR) block(LbdN<LBD_UNR>());
+        const int nu = len - w0;
+        if (nu & 4) block(LbdN<4>());
+        if (nu & 2) block(LbdN<2>());
+        if (nu & 1) block(LbdN<1>());
+    }
+    // (the along-rows loop ends in a barrier: the tile is free)
+    if (t < 28) { reinterpret_cast<float *>(tile)[t] = 0.f; reinterpret_cast<float *>(tile)[70 * 4 + t] = 0.f; }
+    if (t < 63) {
+        const float coef = gG[t];
+        *reinterpret_cast<float4 *>(rows[7 + t]) = make_float4(__fmul_rn(coef, pL), __fmul_rn(coef, nL), __fmul_rn(coef, pO), __fmul_rn(coef, nO));
+    }
+    __syncthreads();
+    // Band sums.  Value 8 b + q of the reference's eight sums per band (q: 0 pgdL, 1 ngdL, 2 pgdL2, 3 ngdL2, 4 pgdO, 5 ngdO, 6 pgdO2, 7 ngdO2)
+    // is one chain over band b's 21 rows 7 (b - 1) .. 7 (b + 1) + 6 in row order, step j with the weight gL[j] ("below", own, "above" are
+    // j / 7 = 0, 1, 2).  Lane t owns value t; value 64 + t (band 8) runs beside it on every lane and lanes 0..7 keep it.
+    {
+        const int q = t & 7;
+        const bool sq = (q & 2) != 0;
+        const float *r0 = &rows[7 * (t >> 3)][(q & 1) + 2 * (q >> 2)], *r1 = &rows[56][(q & 1) + 2 * (q >> 2)];
+        float s0 = 0, s1 = 0;
+#pragma unroll
+        for (int j = 0; j < 21; j++) {
+            const float c = gL[j], cc = __fmul_rn(c, c);
+            const float k = sq ? cc : c;
+            const float a0 = r0[4 * j], a1 = r1[4 * j];
+            s0 = __fadd_rn(s0, __fmul_rn(k, sq ? __fmul_rn(a0, a0) : a0));
+            s1 = __fadd_rn(s1, __fmul_rn(k, sq ? __fmul_rn(a1, a1) : a1));
+        }
+        band[t] = s0;
+        if (t < 8) band[64 + t] = s1;
+    }
+    __syncthreads();
+    // Mean / standard deviation of the nine bands, the three normalisations and the clip (binary_descriptor_custom.cpp:1256-1341): value
+    // 8 b + o is the mean of quantity (0, 1, 4, 5)[o] for o < 4, the deviation of the same quantity for o - 4 otherwise
+    float v0, v1;
+    {
+        const int o = t & 7, qm = (o & 1) | ((o & 2) << 1);
+        auto value = [&](int b) {
+            const float invN = (b == 0 || b == 8) ? (float)(1.0 / 14.0) : (float)(1.0 / 21.0);
+            const float tmp = __fmul_rn(band[8 * b + qm], invN);
+            const float dev = sqrtf(__fsub_rn(__fmul_rn(band[8 * b + qm + 2], invN), __fmul_rn(tmp, tmp)));
+            return o < 4 ? tmp : dev;
+        };
+        v0 = value(t >> 3); v1 = value(8);
+        float *dst = sqMS + 36 * (o >> 2) + (o & 3);
+        dst[4 * (t >> 3)] = __fmul_rn(v0, v0);
+        if (t < 8) dst[32] = __fmul_rn(v1, v1);
+    }
+    __syncthreads();
+    auto ordered_sum = [](const float *p, int n4) {
+        float s = 0;
+        for (int i = 0; i < n4; i++) {
+            const float4 x = reinterpret_cast<const float4 *>(p)[i];
+            s = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(s, x.x), x.y), x.z), x.w);
+        }
+        return s;
+    };
+    {
+        // tempM on the lanes that hold a mean, tempS on those that hold a deviation
+        const float scale = __fdiv_rn(1.f, sqrtf(ordered_sum(sqMS + 36 * ((t & 7) >> 2), 9)));
+        v0 = __fmul_rn(v0, scale); v1 = __fmul_rn(v1, scale);
+        if ((double)v0 > 0.4) v0 = (float)0.4;
+        if ((double)v1 > 0.4) v1 = (float)0.4;
+        sqAll[t] = __fmul_rn(v0, v0);
+        if (t < 8) sqAll[64 + t] = __fmul_rn(v1, v1);
+    }
+    __syncthreads();
+    {
+        const float tmp = __fdiv_rn(1.f, sqrtf(ordered_sum(sqAll, 18)));
         dv[t] = __fmul_rn(v0, tmp);
         if (t < 8) dv[64 + t] = __fmul_rn(v1, tmp);
     }
@@ -1673,7 +1908,7 @@ void lsd_free(hvo_ctx *ctx)
     if (!P) return;
     void *ptrs[] = { P->d_kl2, P->d_desc2, P->d_fn2, P->d_nkl2, P->d_blur, P->d_px, P->d_defined, P->d_reg, P->d_segs, P->d_kl_all, P->d_kl,
                      P->d_desc, P->d_fn, P->d_nkl, P->d_flags, P->d_b5, P->d_dxy, P->d_xofs, P->d_yofs, P->d_xa, P->d_yb, P->d_gL, P->d_gG, P->d_stats,
-                     P->d_pool, P->d_defmask, P->d_wprefix, P->d_fbase, P->d_fcount, P->d_pooltop, P->d_atags, P->d_actl, P->d_alists, P->d_ablk, P->d_afreg, P->d_ainreg, P->d_redo, P->d_b8, P->d_s8, P->d_rs8tab };
+                     P->d_pool, P->d_defmask, P->d_wprefix, P->d_fbase, P->d_fcount, P->d_pooltop, P->d_atags, P->d_actl, P->d_alists, P->d_ablk, P->d_afreg, P->d_ainreg, P->d_redo, P->d_b8, P->d_s8, P->d_rs8tab, P->d_lbdl };
     for (void *q : ptrs) if (q) (void)hipFree(q);
     delete P;
     ctx->lsd = nullptr;
@@ -1746,7 +1981,7 @@ static int lsd_build_plan(hvo_ctx *ctx, int w, int h, int batch)
     // transient images (the fp64 blurred image between k_lsd_blur and k_lsd_resize_grad, the Sobel image between k_lbd_blur_sobel and
     // k_lbd_desc) exist for a CHUNK of the batch only: lsd_run walks the batch chunk by chunk through those kernels (3.7 MB per frame saved)
     P->kn.dense.read("HVO_LSD_DENSE"); P->kn.lat.read("HVO_LSD_LAT"); P->kn.async_w.read("HVO_LSD_ASYNC"); P->kn.async_early.read("HVO_LSD_ASYNC_EARLY");
-    P->kn.async_lds.read("HVO_LSD_ASYNC_LDS"); P->kn.lat_lds.read("HVO_LSD_LAT_LDS"); P->kn.lbd_split.read("HVO_LBD_SPLIT"); P->kn.spin_max.read("HVO_LSD_ASYNC_SPIN_MAX");
+    P->kn.async_lds.read("HVO_LSD_ASYNC_LDS"); P->kn.lat_lds.read("HVO_LSD_LAT_LDS"); P->kn.lbd_split.read("HVO_LBD_SPLIT"); P->kn.lbd_desc.read("HVO_LBD_DESC"); P->kn.spin_max.read("HVO_LSD_ASYNC_SPIN_MAX");
     P->chunk = (int)std::min<size_t>(B, 512);
     { const char *e = getenv("HVO_LSD_CHUNK"); if (e && atoi(e) > 0) P->chunk = (int)std::min<size_t>(B, (size_t)atoi(e)); }
     // compact records (HVO_LSD_COMPACT): the dense record image exists for a chunk only
@@ -1781,6 +2016,8 @@ static int lsd_build_plan(hvo_ctx *ctx, int w, int h, int batch)
     PA(P->d_kl2, B * P->nfeat * sizeof(hvo_keyline)); PA(P->d_desc2, B * P->nfeat * 32); PA(P->d_fn2, B * P->nfeat * 24); PA(P->d_nkl2, B * 4);
     if (P->kn.lbd_split.set) PA(P->d_b5, CB * npix);
     PA(P->d_dxy, CB * npix * sizeof(short2));
+    // HVO_LBD_DESC=0: the one-kernel descriptor, kept for A/B runs; it also serves images whose coordinates could leave a short (LBD_SHORT_SAFE)
+    if (!P->kn.lbd_desc.off() && std::max(w, h) <= LBD_SHORT_SAFE) PA(P->d_lbdl, CB * P->nfeat * sizeof(LbdLine));
     PA(P->d_xofs, P->sw * 4); PA(P->d_yofs, (P->sh + PRE_CH) * 4); PA(P->d_xa, P->sw * 8); PA(P->d_yb, (P->sh + PRE_CH) * 8);      // (k_lsd_pre reads the row tables a chunk at a time: padded)
     PA(P->d_gL, 21 * 4); PA(P->d_gG, 63 * 4); PA(P->d_stats, B * 64);
     if (P->pre_fused) {
@@ -1815,6 +2052,39 @@ int lsd_prepare(hvo_ctx *ctx, int w, int h, int batch, bool culled, LsdView *v)
     v->d_kl = culled ? P->d_kl2 : P->d_kl; v->d_desc = culled ? P->d_desc2 : P->d_desc; v->d_fn = culled ? P->d_fn2 : P->d_fn;
     v->d_nkl = culled ? P->d_nkl2 : P->d_nkl; v->d_flags = P->d_flags; v->nfeat = P->nfeat;
     return HVO_OK;
+}
+
+// The LBD gradient image of m frames (gc: the first one's gray image in the pyramid slab) into P->d_dxy
+static int lbd_sobel_enqueue(hvo_ctx *ctx, LsdPlan *P, hipStream_t st, const uint8_t *gc, int m)
+{
+    OrbPlan &O = ctx->orb;
+    const int w = P->w, h = P->h, gpitch = O.lev[0].pitch;
+    int rc;
+    if (ctx->readings & HVO_READING_BLUR_FLOAT) {  // GaussianBlur(5 x 5, sigma 1) in the float-kernel reading (readings.hip), then the Sobel pair
+        if (!P->d_b5) HVO_HIP(hipMalloc((void **)&P->d_b5, (size_t)P->chunk * w * h));
+        if ((rc = readings_gblur_enqueue(st, gc, O.pyr_bytes, gpitch, w, h, P->d_b5, (size_t)w * h, w, m, 5, 1.0, true))) return rc;
+        hipLaunchKernelGGL(k_lbd_sobel, dim3((w + 255) / 256, (h + LBD_BLUR_ROWS - 1) / LBD_BLUR_ROWS, m), dim3(256), 0, st, P->d_b5, P->d_dxy, w, h);
+    } else if (P->d_b5) {                           // the two-kernel formulation (blurred u8 image materialised), kept for A/B runs (HVO_LBD_SPLIT)
+        hipLaunchKernelGGL(k_lbd_blur5, dim3((w + 255) / 256, (h + LBD_BLUR_ROWS - 1) / LBD_BLUR_ROWS, m), dim3(256), 0, st, gc, O.pyr_bytes, gpitch, P->d_b5, w, h, P->k5[0], P->k5[1], P->k5[2]);
+        hipLaunchKernelGGL(k_lbd_sobel, dim3((w + 255) / 256, (h + LBD_BLUR_ROWS - 1) / LBD_BLUR_ROWS, m), dim3(256), 0, st, P->d_b5, P->d_dxy, w, h);
+    } else {
+        const dim3 grid((((w + 3) / 4) * ((h + LBD_FUSED_ROWS - 1) / LBD_FUSED_ROWS) + 255) / 256, 1, m);
+        if ((w & 3) == 0) hipLaunchKernelGGL(k_lbd_blur_sobel<true>, grid, dim3(256), 0, st, gc, O.pyr_bytes, gpitch, P->d_dxy, w, h, P->k5[0], P->k5[1], P->k5[2]);
+        else hipLaunchKernelGGL(k_lbd_blur_sobel<false>, grid, dim3(256), 0, st, gc, O.pyr_bytes, gpitch, P->d_dxy, w, h, P->k5[0], P->k5[1], P->k5[2]);
+    }
+    return HVO_OK;
+}
+
+// The descriptors of up to kl_cap key lines in each of m frames whose gradient images are in P->d_dxy.  scratch: kl_cap * m records for
+// k_lbd_line_setup + k_lbd_desc; nullptr selects k_lbd_desc_v1
+static void lbd_desc_enqueue(const LsdPlan *P, hipStream_t st, int m, const hvo_keyline *kl, const int *nkl, int kl_cap, LbdLine *scratch, uint8_t *desc)
+{
+    if (!scratch) {
+        hipLaunchKernelGGL(k_lbd_desc_v1, dim3(kl_cap, m), dim3(64), 0, st, P->d_dxy, P->w, P->h, kl, nkl, kl_cap, P->d_gL, P->d_gG, desc);
+        return;
+    }
+    hipLaunchKernelGGL(k_lbd_line_setup, dim3((unsigned)(((size_t)kl_cap * m + 63) / 64)), dim3(64), 0, st, kl, nkl, kl_cap, m, scratch);
+    hipLaunchKernelGGL(k_lbd_desc, dim3(kl_cap, m), dim3(64), 0, st, reinterpret_cast<const int *>(P->d_dxy), P->w, P->h, (const LbdLine *)scratch, nkl, kl_cap, P->d_gL, P->d_gG, desc);
 }
 
 int lsd_run(hvo_ctx *ctx, int n, bool cull)
@@ -1982,23 +2252,10 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
         const uint8_t *gc = gray + (size_t)c0 * O.pyr_bytes;
         const size_t ko = (size_t)c0 * P->nfeat;
         id = hvo_prof_begin(ctx, "lbd_sobel", st);
-        if (ctx->readings & HVO_READING_BLUR_FLOAT) {  // GaussianBlur(5 x 5, sigma 1) in the float-kernel reading (readings.hip), then the Sobel pair
-            if (!P->d_b5) HVO_HIP(hipMalloc((void **)&P->d_b5, (size_t)P->chunk * w * h));
-            if ((rc = readings_gblur_enqueue(st, gc, O.pyr_bytes, gpitch, w, h, P->d_b5, (size_t)w * h, w, m, 5, 1.0, true))) return rc;
-            hipLaunchKernelGGL(k_lbd_sobel, dim3((w + 255) / 256, (h + LBD_BLUR_ROWS - 1) / LBD_BLUR_ROWS, m), dim3(256), 0, st, P->d_b5, P->d_dxy, w, h);
-        } else
-        if (P->d_b5) {                                  // the two-kernel formulation (blurred u8 image materialised), kept for A/B runs (HVO_LBD_SPLIT)
-            hipLaunchKernelGGL(k_lbd_blur5, dim3((w + 255) / 256, (h + LBD_BLUR_ROWS - 1) / LBD_BLUR_ROWS, m), dim3(256), 0, st, gc, O.pyr_bytes, gpitch, P->d_b5, w, h, P->k5[0], P->k5[1], P->k5[2]);
-            hipLaunchKernelGGL(k_lbd_sobel, dim3((w + 255) / 256, (h + LBD_BLUR_ROWS - 1) / LBD_BLUR_ROWS, m), dim3(256), 0, st, P->d_b5, P->d_dxy, w, h);
-        } else
-{
-            const dim3 grid((((w + 3) / 4) * ((h + LBD_FUSED_ROWS - 1) / LBD_FUSED_ROWS) + 255) / 256, 1, m);
-            if ((w & 3) == 0) hipLaunchKernelGGL(k_lbd_blur_sobel<true>, grid, dim3(256), 0, st, gc, O.pyr_bytes, gpitch, P->d_dxy, w, h, P->k5[0], P->k5[1], P->k5[2]);
-            else hipLaunchKernelGGL(k_lbd_blur_sobel<false>, grid, dim3(256), 0, st, gc, O.pyr_bytes, gpitch, P->d_dxy, w, h, P->k5[0], P->k5[1], P->k5[2]);
-        }
+        if ((rc = lbd_sobel_enqueue(ctx, P, st, gc, m))) return rc;
         hvo_prof_end(ctx, id);
         id = hvo_prof_begin(ctx, "lbd_desc", st);
-        hipLaunchKernelGGL(k_lbd_desc, dim3(P->nfeat, m), dim3(64), 0, st, P->d_dxy, w, h, P->d_kl + ko, P->d_nkl + c0, P->nfeat, P->d_gL, P->d_gG, P->d_desc + ko * 32);
+        lbd_desc_enqueue(P, st, m, P->d_kl + ko, P->d_nkl + c0, P->nfeat, P->d_lbdl, P->d_desc + ko * 32);
         hvo_prof_end(ctx, id);
         if (cull) {                                     // Frame::cullingLine + the second LBD pass (Frame.cc:934, 952-1116)
             id = hvo_prof_begin(ctx, "lsd_cull", st);
@@ -2009,7 +2266,7 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
             const int maxl = (P->nfeat + 63) & ~63;
             if (hvo_ensure_dyn_lds(reinterpret_cast<const void *>(k_cull_lines), cull_lds_bytes(maxl))) return HVO_ERR_HIP;
             hipLaunchKernelGGL(k_cull_lines, dim3(m), dim3(64), cull_lds_bytes(maxl), st, c, maxl);
-            hipLaunchKernelGGL(k_lbd_desc, dim3(P->nfeat, m), dim3(64), 0, st, P->d_dxy, w, h, P->d_kl2 + ko, P->d_nkl2 + c0, P->nfeat, P->d_gL, P->d_gG, P->d_desc2 + ko * 32);
+            lbd_desc_enqueue(P, st, m, P->d_kl2 + ko, P->d_nkl2 + c0, P->nfeat, P->d_lbdl, P->d_desc2 + ko * 32);
             hvo_prof_end(ctx, id);
         }
     }
@@ -2197,6 +2454,45 @@ extern "C" int hvo_debug_lsd_images(hvo_ctx *ctx, int frame, int *sw_out, int *s
     if (sw_out) *sw_out = sw;
     if (sh_out) *sh_out = sh;
     return HVO_OK;
+}
+
+// diagnostics (not part of include/hvo.h): the descriptors of n caller-supplied key lines on one image, for tests that need lengths, angles
+// and positions the detector does not produce: the image is uploaded as a batch of one, the plan's blur / Sobel forms its gradient image and
+// the descriptor form the plan selected (HVO_LBD_DESC) describes the lines.  desc_out: n x 32 bytes.  The lines' sample coordinates must
+// stay inside a short (the reference wraps there, the two-kernel form does not): anything else is HVO_ERR_INVALID_ARG.
+extern "C" int hvo_debug_lbd_desc(hvo_ctx *ctx, const uint8_t *gray, int w, int h, int stride, const hvo_keyline *keylines, int n, uint8_t *desc_out)
+{
+    if (!ctx || !gray || !keylines || !desc_out || w <= 0 || h <= 0 || stride < w || n < 1 || n > (1 << 20)) return HVO_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++) {
+        const hvo_keyline &k = keylines[i];
+        const float reach = 0.5f * (float)k.num_pixels + 32.f, mx = 0.5f * (k.sox + k.eox), my = 0.5f * (k.soy + k.eoy);
+        if (k.num_pixels < 0 || k.num_pixels > 32767 || !(fabsf(mx) + reach < 32000.f) || !(fabsf(my) + reach < 32000.f) || !(fabsf(k.angle) < 1e6f)) {
+            ctx->last_error = "lbd desc: a key line's samples would leave the range of a short"; return HVO_ERR_INVALID_ARG;
+        }
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    hvo_frame_in in; memset(&in, 0, sizeof(in));
+    in.gray = gray; in.gray_stride = stride;
+    int rc = orb_upload(ctx, 1, &in, w, h);
+    if (rc) return rc;
+    ctx->last_stages = 0;                                  // slot 0 of the resident batch has been overwritten
+    OrbPlan &O = ctx->orb;
+    if ((rc = lsd_ensure_plan(ctx, O.w, O.h, std::max(1, ctx->p.max_batch)))) return rc;
+    LsdPlan *P = plan_of(ctx);
+    hipStream_t st = hvo_stream_lsd(ctx);
+    hvo_keyline *d_kl = nullptr; int *d_n = nullptr; uint8_t *d_desc = nullptr; LbdLine *d_rec = nullptr;
+    bool ok = hipMalloc((void **)&d_kl, (size_t)n * sizeof(hvo_keyline)) == hipSuccess && hipMalloc((void **)&d_n, 4) == hipSuccess &&
+              hipMalloc((void **)&d_desc, (size_t)n * 32) == hipSuccess && (!P->d_lbdl || hipMalloc((void **)&d_rec, (size_t)n * sizeof(LbdLine)) == hipSuccess);
+    ok = ok && hipMemcpy(d_kl, keylines, (size_t)n * sizeof(hvo_keyline), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_n, &n, 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        rc = lbd_sobel_enqueue(ctx, P, st, O.d_pyr + O.lev[0].img_off, 1);
+        if (!rc) {
+            lbd_desc_enqueue(P, st, 1, d_kl, d_n, n, d_rec, d_desc);
+            ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess && hipMemcpy(desc_out, d_desc, (size_t)n * 32, hipMemcpyDeviceToHost) == hipSuccess;
+        }
+    }
+    (void)hipFree(d_kl); (void)hipFree(d_n); (void)hipFree(d_desc); (void)hipFree(d_rec);
+    return rc ? rc : ok ? HVO_OK : HVO_ERR_HIP;
 }
 
 // What the last async line growing (batches of a few frames, the streamed mode) had to fall back on: frames the one-wave kernel grew again
