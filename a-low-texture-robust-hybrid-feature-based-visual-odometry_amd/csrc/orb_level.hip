@@ -74,8 +74,10 @@ static __device__ __forceinline__ int lt_min3(int a, int b, int c) { int r; asm(
 static __device__ __forceinline__ int lt_max3(int a, int b, int c) { int r; asm("v_max3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 
 // cornerScore<16> (OpenCV 3.2) on the LDS tile; v = centre.  With d = v - ring and e = ring - v the score is
-// max over the 16 nine-arcs of max(min d, min e) - 1; a nine-arc minimum is a min3 of three min3 (explicit v_min3_i32: the
-// compiler's reassociation of the min chains yields twice the instructions).
+// max over the 16 nine-arcs of max(min d, min e) - 1.  Over an arc, min d = v - max ring and min e = min ring - v, so the score is
+// max(v - min over arcs of (max ring), max over arcs of (min ring) - v) - 1: the ring bytes themselves go through the min3 / max3
+// trees (a nine-arc extremum is a max3 of three max3; explicit v_max3_i32: the compiler's reassociation of the chains yields twice
+// the instructions), one chain after the other, and no difference is formed or kept per ring pixel.
 static __device__ __forceinline__ int lt_fast_score(const uint8_t *p, int v)
 {
     constexpr int tp = LT_TP;
@@ -84,16 +86,26 @@ static __device__ __forceinline__ int lt_fast_score(const uint8_t *p, int v)
     r[4] = p[3];         r[5] = p[-tp + 3];      r[6] = p[-2 * tp + 2];  r[7] = p[-3 * tp + 1];
     r[8] = p[-3 * tp];   r[9] = p[-3 * tp - 1];  r[10] = p[-2 * tp - 2]; r[11] = p[-tp - 3];
     r[12] = p[-3];       r[13] = p[tp - 3];      r[14] = p[2 * tp - 2];  r[15] = p[3 * tp - 1];
-    int d[16], e[16], a3[16], b3[16];
+    int lo, hi;                                         // min over the arcs of the arc's maximum; max over the arcs of its minimum
+    {
+        int x3[16];
 #pragma unroll
-    for (int k = 0; k < 16; k++) { d[k] = v - r[k]; e[k] = r[k] - v; }
+        for (int k = 0; k < 16; k++) x3[k] = lt_max3(r[k], r[(k + 1) & 15], r[(k + 2) & 15]);
+        lo = lt_max3(x3[0], x3[3], x3[6]);
 #pragma unroll
-    for (int k = 0; k < 16; k++) { a3[k] = lt_min3(d[k], d[(k + 1) & 15], d[(k + 2) & 15]); b3[k] = lt_min3(e[k], e[(k + 1) & 15], e[(k + 2) & 15]); }
-    int best = -1000;
+        for (int k = 1; k < 15; k += 2) lo = lt_min3(lo, lt_max3(x3[k], x3[(k + 3) & 15], x3[(k + 6) & 15]), lt_max3(x3[k + 1], x3[(k + 4) & 15], x3[(k + 7) & 15]));
+        lo = min(lo, lt_max3(x3[15], x3[2], x3[5]));
+    }
+    {
+        int n3[16];
 #pragma unroll
-    for (int k = 0; k < 16; k++)
-        best = lt_max3(best, lt_min3(a3[k], a3[(k + 3) & 15], a3[(k + 6) & 15]), lt_min3(b3[k], b3[(k + 3) & 15], b3[(k + 6) & 15]));
-    return best - 1;
+        for (int k = 0; k < 16; k++) n3[k] = lt_min3(r[k], r[(k + 1) & 15], r[(k + 2) & 15]);
+        hi = lt_min3(n3[0], n3[3], n3[6]);
+#pragma unroll
+        for (int k = 1; k < 15; k += 2) hi = lt_max3(hi, lt_min3(n3[k], n3[(k + 3) & 15], n3[(k + 6) & 15]), lt_min3(n3[k + 1], n3[(k + 4) & 15], n3[(k + 7) & 15]));
+        hi = max(hi, lt_min3(n3[15], n3[2], n3[5]));
+    }
+    return max(v - lo, hi - v) - 1;
 }
 
 static __device__ __forceinline__ void lt_row_sums(unsigned W0, unsigned W1, unsigned W2, unsigned klo, unsigned khi, unsigned hs[4])
@@ -112,11 +124,18 @@ static __device__ __forceinline__ unsigned lt_dot2(unsigned a, unsigned w, unsig
     return __builtin_amdgcn_udot2(__builtin_bit_cast(lt_us2, a), __builtin_bit_cast(lt_us2, w), c, false);
 }
 
+// Registers: 80 per lane, so that a wave of this kernel fits beside two AHC waves and an LSD-preamble wave ("The register
+// file as a budget").  The allocator takes the six-wave band only if the LDS it can see allows six waves, and a static LtWave[NW]
+// (five waves per SIMD) makes it ignore the hint: the same bytes are therefore passed as dynamic LDS (orb_level_run).
 template <int NW>
-__global__ __launch_bounds__(64 * NW, 5) void k_orb_level(const LevelArgs A)
+__attribute__((amdgpu_waves_per_eu(6, 6)))
+__global__ __launch_bounds__(64 * NW) void k_orb_level(const LevelArgs A)
 {
-    __shared__ LtWave lds_[NW];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lt_lds_[];
+    LtWave *lds_ = reinterpret_cast<LtWave *>(lt_lds_);
+    // the wave's number is the same in all of its lanes; said so, the tile record, everything derived from it and the wave's LDS base
+    // are scalars (SGPRs, s_load, SALU) and not 64 copies in vector registers
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     // blocks b and b + 8 share an XCD: all groups of a frame go to one XCD
     const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
     const int fr8 = q / A.groups, g = q - fr8 * A.groups;
@@ -576,10 +595,11 @@ int orb_level_run(hvo_ctx *ctx, int c0, int n, hipStream_t st, int k0, int k1, i
         if (ctx->readings & HVO_READING_BLUR_FLOAT) A.skip |= 2;      // the float-kernel reading of GaussianBlur: the blurred levels come from readings.hip (orb_blur_float_run)
         A.flags = P.d_flags + c0; A.k0 = k0; A.k1 = k1; A.k2 = k2; A.k3 = k3;
         if (A.ntiles < 1) continue;
+        // LtWave[nw] as dynamic LDS (see k_orb_level): at most 4 x 8176 B, below the size a launch needs an attribute for
         const int n8 = (n + 7) / 8 * 8;
-        if (nw == 1) hipLaunchKernelGGL(k_orb_level<1>, dim3((unsigned)(n8 * A.groups)), dim3(64), 0, st, A);
-        else if (nw == 2) hipLaunchKernelGGL(k_orb_level<2>, dim3((unsigned)(n8 * A.groups)), dim3(128), 0, st, A);
-        else hipLaunchKernelGGL(k_orb_level<4>, dim3((unsigned)(n8 * A.groups)), dim3(256), 0, st, A);
+        if (nw == 1) hipLaunchKernelGGL(k_orb_level<1>, dim3((unsigned)(n8 * A.groups)), dim3(64), 1 * sizeof(LtWave), st, A);
+        else if (nw == 2) hipLaunchKernelGGL(k_orb_level<2>, dim3((unsigned)(n8 * A.groups)), dim3(128), 2 * sizeof(LtWave), st, A);
+        else hipLaunchKernelGGL(k_orb_level<4>, dim3((unsigned)(n8 * A.groups)), dim3(256), 4 * sizeof(LtWave), st, A);
     }
     return HVO_OK;
 }

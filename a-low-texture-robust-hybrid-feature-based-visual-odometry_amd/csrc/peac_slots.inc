@@ -101,6 +101,12 @@ struct TQUpdateS {
     }
 };
 
+// how many lanes of the wave below me have their bit set in m (v_mbcnt: no (1 << lane) - 1 mask is kept in registers for it)
+static __device__ __forceinline__ int sl_below(unsigned long long m)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
 // eight entries of a list in registers: where D and K are among the first n
 static __device__ __forceinline__ void sl_find8(const int (&u)[8], int n, int x0, int D, int K, int &iD, int &iK)
 {
@@ -125,6 +131,10 @@ static __device__ __forceinline__ void sl_find(const int *pool, int off, int cnt
     }
 }
 
+// Three waves per SIMD = 168 registers: two of these waves then leave 176, an LSD-preamble wave (96) and an ORB-level wave (80), where
+// 184 left room for one of them (DESIGN 4, "The register file as a budget"; tests/test_kernel_budget.py holds the sum).  The hint only
+// makes the allocator hold the band: the kernel fits it without scratch.
+__attribute__((amdgpu_waves_per_eu(3, 3)))
 __global__ __launch_bounds__(64) void k_peac_cluster_slots(ClArgs a, int nframes)
 {
     constexpr int GL = 16, NG = 4;
@@ -229,7 +239,6 @@ __global__ __launch_bounds__(64) void k_peac_cluster_slots(ClArgs a, int nframes
     int nseg = nblk, pooltop = nblk * 4, next = 0, flags = 0;   // nseg counts LABELS
     int *ext = a.extracted + (size_t)frame * 2 * MAX_PLANES;
     const unsigned long long lt_mask = (1ull << gl) - 1;       // lanes of my group below me
-    const unsigned long long wave_lt = (1ull << lane) - 1;     // lanes of the wave below me
     __syncthreads();
     int ptop = hn > 0 ? tq_top(Q, gl) : -1;                    // packed
     double nps[9], npn[3]; int n_cnt = 0, n_off = 0, n_N = 0, n_rid = 0, n_dsr = 0, n_dss = 0;
@@ -250,7 +259,7 @@ __global__ __launch_bounds__(64) void k_peac_cluster_slots(ClArgs a, int nframes
         if (X > 0) {                                            // uniform
             const bool idle = gl >= c;
             const unsigned long long im = __ballot(idle);
-            const int r = __popcll(im & wave_lt), I = __popcll(im);
+            const int r = sl_below(im), I = __popcll(im);
             const int b1 = x0, b2 = x0 + x1, b3 = b2 + x2;
             const int g2 = r < b1 ? 0 : r < b2 ? 1 : r < b3 ? 2 : 3;
             const int xb = g2 == 0 ? 0 : g2 == 1 ? b1 : g2 == 2 ? b2 : b3;
@@ -580,7 +589,7 @@ __global__ __launch_bounds__(64) void k_peac_cluster_slots(ClArgs a, int nframes
                 const unsigned long long km = __ballot(keep);
                 const unsigned long long s0 = __ballot(c1v && cg == 0), s1 = __ballot(c1v && cg == 1), s2 = __ballot(c1v && cg == 2), s3 = __ballot(c1v && cg == 3);
                 const unsigned long long sc_ = cg == 0 ? s0 : cg == 1 ? s1 : cg == 2 ? s2 : s3, so_ = gi == 0 ? s0 : gi == 1 ? s1 : gi == 2 ? s2 : s3;
-                if (keep) poolc[moff_c + mB_c + __popcll(km & sc_ & wave_lt)] = aid;
+                if (keep) poolc[moff_c + mB_c + sl_below(km & sc_)] = aid;
                 mcnt += __popcll(km & so_);
             }
         }
