@@ -952,6 +952,55 @@ def lib():
     return _LIB
 
 
+PEAC_CLUSTER_FORMS = ("heads", "c64", "c32", "c16", "c16_lend", "slots")
+LSD_GROW_FORMS = ("async", "lat", "grow", "dense", "grow_c", "dense_c")
+LSD_PRE_FORMS = ("fused", "split", "u8")
+LBD_GRADIENT_FORMS = ("fused", "split", "float")
+_PEAC_REPORT_FIELDS = ("cluster", "heads", "heads_big", "ldsq", "edges_done", "poolcap", "group", "cluster_wgs", "perm_items", "blkmap_y",
+                       "flood_t", "flood_epl", "flood_slim", "flood_perm_items", "n", "slots_fit")
+_LSD_REPORT_FIELDS = ("pre", "compact", "chunk", "chunks", "grow", "async_w", "async_fallback", "async_lds", "lat_lds", "lbd_gradient", "lbd_desc",
+                      "perm_items", "n", "cull", "plan_batch", "async_early")
+_BATCH_REPORT_FIELDS = ("sched", "orb_first", "lsd_first", "peac_last", "prio_orb", "prio_lsd", "prio_peac", "stages")
+
+
+def _launch_report_dict(m):
+    """the 48 ints of hvo_debug_launch_report / hvo_debug_plan_select as {"peac": {...}, "lsd": {...}, "batch": {...}}; a part that was
+    not filled (a stage that has not run, or refuses the geometry) is None.  Forms are named (PEAC_CLUSTER_FORMS, LSD_GROW_FORMS, ...)"""
+    m = [int(v) for v in m]
+    r = {"peac": None, "lsd": None, "batch": None}
+    if m[40] & 1:
+        d = dict(zip(_PEAC_REPORT_FIELDS, m[0:16])); d["cluster"] = PEAC_CLUSTER_FORMS[d["cluster"]]; r["peac"] = d
+    if m[40] & 2:
+        d = dict(zip(_LSD_REPORT_FIELDS, m[16:32])); d["pre"] = LSD_PRE_FORMS[d["pre"]]; d["grow"] = LSD_GROW_FORMS[d["grow"]]
+        d["lbd_gradient"] = LBD_GRADIENT_FORMS[d["lbd_gradient"]]; r["lsd"] = d
+    if m[40] & 4:
+        d = dict(zip(_BATCH_REPORT_FIELDS, m[32:40])); d["n"] = m[41]; r["batch"] = d
+    return r
+
+
+def plan_select(w, h, n, max_batch=None, stages=STAGE_ALL):
+    """diagnostics: the kernels a batch of n frames of w x h would take in a context of max_batch frames (default: n) under the current
+    environment -- the selection functions the launches use, evaluated on the host: no context, no device"""
+    L = lib()
+    L.hvo_debug_plan_select.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p]; L.hvo_debug_plan_select.restype = C.c_int
+    m = np.zeros(48, np.int32)
+    rc = L.hvo_debug_plan_select(int(w), int(h), int(n), int(max_batch if max_batch is not None else n), int(stages), _p(m))
+    if rc:
+        raise HvoError(rc, "plan_select")
+    return _launch_report_dict(m)
+
+
+def frame_perm(n):
+    """diagnostics: the launch order of n items (the bit-reversal order the one-wave-per-frame kernels take their frames in), host only"""
+    L = lib()
+    L.hvo_debug_frame_perm.argtypes = [C.c_int, C.c_void_p]; L.hvo_debug_frame_perm.restype = C.c_int
+    m = np.zeros(int(n), np.int32)
+    rc = L.hvo_debug_frame_perm(int(n), _p(m))
+    if rc:
+        raise HvoError(rc, "frame_perm")
+    return m
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -1303,6 +1352,15 @@ class Context:
         self._chk(L.hvo_debug_peac_stats(self.h, frame, _p(m)), "peac_stats")
         return {"segments": int(m[0]), "coarse_planes": int(m[2]), "flags": int(m[3]), "planes": int(m[4]), "queue_entries": int(m[5]),
                 "flood_rounds": int(m[8]), "flood_ranked_rounds": int(m[9]), "flood_serial_rounds": int(m[10]), "ahc_rounds": int(m[11]), "ahc_stops_no_head": int(m[12]), "ahc_stops_conflict": int(m[13]), "ahc_stops_key_order": int(m[14])}
+
+    def launch_report(self):
+        """diagnostics (not part of the reference interface): which kernels the last batch_run / compute_planes / extract_lsd of this
+        context launched, as _launch_report_dict lays them out; the same record plan_select() gives without a device"""
+        L = lib()
+        L.hvo_debug_launch_report.argtypes = [C.c_void_p, C.c_void_p]; L.hvo_debug_launch_report.restype = C.c_int
+        m = np.zeros(48, np.int32)
+        self._chk(L.hvo_debug_launch_report(self.h, _p(m)), "launch_report")
+        return _launch_report_dict(m)
 
     # ---- matching ----
     def hamming_matrix(self, q, t):
@@ -1766,14 +1824,18 @@ class Context:
         return start, items[: n.value]
 
     # ---- batch ----
-    def batch_upload(self, gray, depth=None, repeat=1):
+    def batch_upload(self, gray, depth=None, repeat=1, n=None):
         """gray: (B,H,W) u8; depth: (B,H,W) u16 or None.  repeat > 1 uploads the B frames cyclically
-        B*repeat times (frames are passed by pointer, host memory is not replicated)."""
+        B*repeat times (frames are passed by pointer, host memory is not replicated); n: only the first n of them
+        (a batch size that is no multiple of B: frame f is gray[f % B])."""
         gray = np.ascontiguousarray(gray, np.uint8)
         B0, h, w = gray.shape
         if depth is not None:
             depth = np.ascontiguousarray(depth, np.uint16)
         B = B0 * repeat
+        if n is not None:
+            if not 1 <= n <= B: raise ValueError("n = %r outside 1 .. %d" % (n, B))
+            B = int(n)
         fi = (FrameIn * B)()
         for b in range(B):
             s = b % B0

@@ -28,17 +28,23 @@ int hvo_ensure_dyn_lds(const void *kernel, size_t bytes)
     return HVO_OK;
 }
 
+void hvo_frame_perm_host(int n, std::vector<int> &p)
+{
+    int bits = 0; while ((1 << bits) < n) bits++;
+    p.clear(); p.reserve(n);
+    for (unsigned i = 0; i < (1u << bits); i++) {
+        unsigned r = 0; for (int b = 0; b < bits; b++) r |= ((i >> b) & 1u) << (bits - 1 - b);
+        if ((int)r < n) p.push_back((int)r);
+    }
+}
+
 const int *hvo_frame_perm(hvo_ctx *ctx, int n)
 {
     if (n < 2) return nullptr;
     if (ctx->kn_frame_perm.off()) return nullptr;                // HVO_FRAME_PERM=0: A/B knob
     for (auto &e : ctx->perms) if (e.first == n) return e.second;
-    int bits = 0; while ((1 << bits) < n) bits++;
-    std::vector<int> p; p.reserve(n);
-    for (unsigned i = 0; i < (1u << bits); i++) {
-        unsigned r = 0; for (int b = 0; b < bits; b++) r |= ((i >> b) & 1u) << (bits - 1 - b);
-        if ((int)r < n) p.push_back((int)r);
-    }
+    std::vector<int> p;
+    hvo_frame_perm_host(n, p);
     if (ctx->perms.size() >= 8) { for (auto &e : ctx->perms) (void)hipFree(e.second); ctx->perms.clear(); }      // (lengths change with the batch: keep a few)
     int *d = nullptr;
     if (hipMalloc((void **)&d, (size_t)n * sizeof(int)) != hipSuccess) return nullptr;
@@ -47,7 +53,85 @@ const int *hvo_frame_perm(hvo_ctx *ctx, int n)
     return d;
 }
 
+// What hvo_create and hvo_batch_run choose by the batch size themselves: the stream priorities (by max_batch) and the overlap policy with
+// the order it enqueues the stages in.  Plain host arithmetic (hvo_debug_plan_select evaluates it without a device)
+void hvo_prio_select(int max_batch, int pr[3])
+{
+    // stream priorities (experiment knob HVO_PRIO="orb,lsd,peac", lower number = higher priority)
+    // Three priority classes, not one: a priority class has its own hardware queues (4 by default), and the streamed mode keeps
+    // depth x 3 streams busy -- with equal priorities its frames in flight serialised (92 -> 65 frames/s at depth 4).  For the
+    // batch that fills the machine equal priorities are 1.5 % faster (profiles/r02_sched_sweep.txt): contexts made for one get them.
+    pr[0] = 0; pr[1] = -1; pr[2] = 1;
+    if (max_batch >= 3072) pr[1] = pr[2] = 0;
+    { const char *e = getenv("HVO_PRIO"); if (e) sscanf(e, "%d,%d,%d", &pr[0], &pr[1], &pr[2]); }
+}
+BatchSel hvo_batch_select(int n, int w, int h, int sched_cfg, bool serialize, unsigned stages)
+{
+    BatchSel b;
+    // The serial stages go first so that their long single-wave kernels overlap the streaming ones (sched 0-2);
+    // sched 3 / 4 (experiments): the plane stage is enqueued last, after LSD then ORB (3) or ORB then LSD (4)
+    // measured (profiles/r02_sched_sweep.txt): policy 5 wins once the batch fills the wave slots (8192 frames: 207 against 218 ms,
+    // 4096: 112 against 115), policy 1 below (2048 frames: 69 against 77 ms; 2048 frames of 1280x960: 344 against 387)
+    // round 3 (tools/sweep.sh preset knobs1280): frames of 1280x960 prefer 7 -- their growing kernel is six times longer and loses more by waiting
+    // for FAST than FAST loses beside it (3072 frames: 340 against 389 ms); 640x480 keeps 5 (188.8 against 191.3 ms at 8192 frames)
+    const bool big_frames = (long long)w * h >= 2LL * 640 * 480;
+    b.sched = sched_cfg >= 0 ? sched_cfg : (n >= 3072 ? (big_frames ? 7 : 5) : 1);
+    b.peac_last = b.sched >= 3 && b.sched != 5 && b.sched != 7 && !serialize;
+    b.orb_first = (b.sched == 5 || b.sched == 7) && !serialize && (stages & HVO_STAGE_ORB);      // sched 5 (experiment): ORB, planes (flood behind k_fast_cells), LSD
+    // a few frames at once: the slowest frame's line growing is the longest chain (it grows with the number of frames, the AHC does not), so
+    // its kernels are enqueued before the plane stage's dozen launches (8 <= n <= 64; a lone frame waits for its planes, 256 frames are a throughput case
+    // that prefers the planes first: 9.6 against 9.1 k frames/s)
+    b.lsd_first = !b.orb_first && !b.peac_last && !serialize && b.sched != 2 && b.sched != 4 && b.sched != 6 &&
+                  n >= 8 && n <= 64 && (stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL)) != 0;
+    b.stages = stages; b.n = n;
+    return b;
+}
+
 extern "C" {
+
+// diagnostics (not part of include/hvo.h).  out48: [0..15] the plane stage's selection (PeacSel, peac.hip), [16..31] the line stage's
+// (LsdSel, lsd.hip), [32..39] { overlap policy, ORB first, LSD first, planes last, priority of the ORB / LSD / plane stream, stages },
+// [40] which of the three parts are filled (1 planes, 2 lines, 4 batch), [41] frames.
+// hvo_debug_launch_report: what the context's last hvo_batch_run, hvo_compute_planes or hvo_extract_lsd launched
+int hvo_debug_launch_report(hvo_ctx *ctx, int *out48)
+{
+    if (!ctx || !out48) return HVO_ERR_INVALID_ARG;
+    memset(out48, 0, 48 * sizeof(int));
+    if (peac_last_report(ctx, out48) == HVO_OK) out48[40] |= 1;
+    if (lsd_last_report(ctx, out48 + 16) == HVO_OK) out48[40] |= 2;
+    if (ctx->last_batch_valid) {
+        const BatchSel &b = ctx->last_batch;
+        const int v[8] = { b.sched, b.orb_first, b.lsd_first, b.peac_last, ctx->prio[0], ctx->prio[1], ctx->prio[2], (int)b.stages };
+        memcpy(out48 + 32, v, sizeof v); out48[40] |= 4; out48[41] = b.n;
+    }
+    return HVO_OK;
+}
+// hvo_debug_plan_select: the same selections for n frames of w x h in a context of max_batch frames, under the environment as it stands,
+// evaluated on the host alone: no context, no device.  (stages: HVO_STAGE_*; a stage that refuses the geometry leaves its part unfilled)
+int hvo_debug_plan_select(int w, int h, int n, int max_batch, unsigned stages, int *out48)
+{
+    if (!out48 || n < 1 || max_batch < 1 || w < 1 || h < 1) return HVO_ERR_INVALID_ARG;
+    memset(out48, 0, 48 * sizeof(int));
+    if (peac_plan_select_env(w, h, n, out48) == HVO_OK) out48[40] |= 1;
+    if (lsd_plan_select_env(w, h, n, max_batch, out48 + 16) == HVO_OK) out48[40] |= 2;
+    int sched_cfg = -1, pr[3];
+    { const char *e = getenv("HVO_SCHED"); if (e) sched_cfg = atoi(e); }
+    hvo_prio_select(std::max(n, max_batch), pr);
+    const BatchSel b = hvo_batch_select(n, w, h, sched_cfg, false, stages);
+    const int v[8] = { b.sched, b.orb_first, b.lsd_first, b.peac_last, pr[0], pr[1], pr[2], (int)b.stages };
+    memcpy(out48 + 32, v, sizeof v); out48[40] |= 4; out48[41] = n;
+    return HVO_OK;
+}
+// the launch order hvo_frame_perm gives n items (out: n ints), on the host alone
+int hvo_debug_frame_perm(int n, int *out)
+{
+    if (n < 1 || !out) return HVO_ERR_INVALID_ARG;
+    std::vector<int> p;
+    hvo_frame_perm_host(n, p);
+    if ((int)p.size() != n) return HVO_ERR_INVALID_ARG;
+    memcpy(out, p.data(), (size_t)n * sizeof(int));
+    return HVO_OK;
+}
 
 int hvo_abi_version(void) { return HVO_ABI_VERSION; }
 
@@ -98,13 +182,8 @@ int hvo_create(const hvo_params *p, hvo_ctx **out)
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) { delete ctx; return HVO_ERR_NO_DEVICE; }
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { delete ctx; return HVO_ERR_NO_DEVICE; }   // code object is gfx950 only
-    // stream priorities (experiment knob HVO_PRIO="orb,lsd,peac", lower number = higher priority)
-    // Three priority classes, not one: a priority class has its own hardware queues (4 by default), and the streamed mode keeps
-    // depth x 3 streams busy -- with equal priorities its frames in flight serialised (92 -> 65 frames/s at depth 4).  For the
-    // batch that fills the machine equal priorities are 1.5 % faster (profiles/r02_sched_sweep.txt): contexts made for one get them.
-    int pr[3] = { 0, -1, 1 };
-    if (ctx->p.max_batch >= 3072) pr[1] = pr[2] = 0;
-    { const char *e = getenv("HVO_PRIO"); if (e) sscanf(e, "%d,%d,%d", &pr[0], &pr[1], &pr[2]); }
+    int *const pr = ctx->prio;
+    hvo_prio_select(ctx->p.max_batch, pr);
     if (hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, pr[0]) != hipSuccess ||
         hipStreamCreateWithPriority(&ctx->s_lsd, hipStreamNonBlocking, pr[1]) != hipSuccess ||
         hipStreamCreateWithPriority(&ctx->s_peac, hipStreamNonBlocking, pr[2]) != hipSuccess ||
@@ -326,22 +405,11 @@ int hvo_batch_run(hvo_ctx *ctx, unsigned stages)
     for (int i = 0; i < ctx->nprof; i++) ctx->prof[i].used = false;
     int rc;
     if ((stages & HVO_STAGE_PLANES) && !ctx->have_depth) return HVO_ERR_INVALID_ARG;
-    // The serial stages go first so that their long single-wave kernels overlap the streaming ones (sched 0-2);
-    // sched 3 / 4 (experiments): the plane stage is enqueued last, after LSD then ORB (3) or ORB then LSD (4)
-    // measured (profiles/r02_sched_sweep.txt): policy 5 wins once the batch fills the wave slots (8192 frames: 207 against 218 ms,
-    // 4096: 112 against 115), policy 1 below (2048 frames: 69 against 77 ms; 2048 frames of 1280x960: 344 against 387)
-    // round 3 (tools/sweep.sh preset knobs1280): frames of 1280x960 prefer 7 -- their growing kernel is six times longer and loses more by waiting
-    // for FAST than FAST loses beside it (3072 frames: 340 against 389 ms); 640x480 keeps 5 (188.8 against 191.3 ms at 8192 frames)
-    const bool big_frames = (long long)ctx->batch_w * ctx->batch_h >= 2LL * 640 * 480;
-    ctx->sched = ctx->sched_cfg >= 0 ? ctx->sched_cfg : (ctx->batch_n >= 3072 ? (big_frames ? 7 : 5) : 1);
-    const bool peac_last = ctx->sched >= 3 && ctx->sched != 5 && ctx->sched != 7 && !ctx->serialize;
-    const bool orb_first = (ctx->sched == 5 || ctx->sched == 7) && !ctx->serialize && (stages & HVO_STAGE_ORB);      // sched 5 (experiment): ORB, planes (flood behind k_fast_cells), LSD
+    const BatchSel bsel = hvo_batch_select(ctx->batch_n, ctx->batch_w, ctx->batch_h, ctx->sched_cfg, ctx->serialize, stages);
+    ctx->last_batch = bsel; ctx->last_batch_valid = true;
+    ctx->sched = bsel.sched;
+    const bool peac_last = bsel.peac_last, orb_first = bsel.orb_first, lsd_first = bsel.lsd_first;
     if (orb_first) { ctx->fast_recorded = false; rc = orb_run(ctx, ctx->batch_n); if (rc) return rc; }
-    // a few frames at once: the slowest frame's line growing is the longest chain (it grows with the number of frames, the AHC does not), so
-    // its kernels are enqueued before the plane stage's dozen launches (8 <= n <= 64; a lone frame waits for its planes, 256 frames are a throughput case
-    // that prefers the planes first: 9.6 against 9.1 k frames/s)
-    const bool lsd_first = !orb_first && !peac_last && !ctx->serialize && ctx->sched != 2 && ctx->sched != 4 && ctx->sched != 6 &&
-                           ctx->batch_n >= 8 && ctx->batch_n <= 64 && (stages & (HVO_STAGE_LSD | HVO_STAGE_LSD_CULL)) != 0;
     if ((stages & HVO_STAGE_PLANES) && !peac_last && !lsd_first) { rc = peac_run(ctx, ctx->batch_n); if (rc) return rc; }
     // Overlap policy (HVO_SCHED; measured in profiles/r02_sched_sweep.txt).  The long serial kernels mostly exclude each other and
     // stretch whatever streams beside them; what the order CAN do is keep them from starving a kernel the others wait for.

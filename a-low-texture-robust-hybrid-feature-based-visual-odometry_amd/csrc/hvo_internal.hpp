@@ -100,8 +100,13 @@ struct Knob {
 // lock, per device -- contexts are driven from several host threads (api.hip)
 int hvo_ensure_dyn_lds(const void *kernel, size_t bytes);
 
+// what hvo_batch_run chooses by the batch size itself (api.hip: hvo_batch_select)
+struct BatchSel { int sched = 1; bool orb_first = false, lsd_first = false, peac_last = false; unsigned stages = 0; int n = 0; };
+
 struct hvo_ctx {
     hvo_params p;
+    int prio[3] = { 0, 0, 0 };             // priorities the ORB / LSD / plane streams were made with (hvo_prio_select)
+    BatchSel last_batch; bool last_batch_valid = false;      // the last hvo_batch_run's choices (hvo_debug_launch_report)
     Knob kn_frame_perm, kn_upload_single;  // HVO_FRAME_PERM, HVO_UPLOAD_SINGLE (read by hvo_create)
     unsigned readings = 0;                 // HVO_READING_* (hvo_set_readings): alternative readings of two OpenCV calls, readings.hip
     int device = 0;
@@ -290,6 +295,7 @@ void orb_free_plan(hvo_ctx *ctx);
 // workgroups a fixed stride apart, and frames a fixed stride apart in a batch tend to be alike (the same camera, or a synthetic
 // batch's period), so whole SIMDs got only long or only short frames and the kernel lasted as long as the unluckiest one.
 const int *hvo_frame_perm(hvo_ctx *ctx, int n);
+void hvo_frame_perm_host(int n, std::vector<int> &p);      // the order itself (host; hvo_frame_perm uploads it)
 // Strided copies between pinned host memory and device slabs are executed by copy kernels, which queue like any other kernel: beside
 // another context's compute on streams of equal priority a BatchPipeline's download took 80-140 ms instead of 30.  hvo_batch_upload /
 // hvo_batch_download therefore move their copies to ctx->s_copy (highest priority); everything else keeps its compute stream's order.
@@ -534,6 +540,10 @@ int peac_upload(hvo_ctx *ctx, int n, const hvo_frame_in *in, int w, int h, bool 
 int peac_run(hvo_ctx *ctx, int n);
 int peac_download(hvo_ctx *ctx, int n, hvo_frame_out *out);
 void peac_free(hvo_ctx *ctx);
+// diagnostics (hvo_debug_launch_report / hvo_debug_plan_select, api.hip): HVO_REPORT_STAGE_INTS ints per stage, the fields of PeacSel / LsdSel in order
+#define HVO_REPORT_STAGE_INTS 16
+int peac_plan_select_env(int w, int h, int n, int *out);
+int peac_last_report(hvo_ctx *ctx, int *out);
 
 // lsd.hip (+ lbd)
 struct LsdView { hvo_keyline *d_kl; uint8_t *d_desc; double *d_fn; int *d_nkl; int *d_flags; int nfeat; };
@@ -541,6 +551,8 @@ int lsd_prepare(hvo_ctx *ctx, int w, int h, int batch, bool culled, LsdView *v);
 int lsd_run(hvo_ctx *ctx, int n, bool cull = false);
 int lsd_download(hvo_ctx *ctx, int n, hvo_frame_out *out, bool culled = false);
 void lsd_free(hvo_ctx *ctx);
+int lsd_plan_select_env(int w, int h, int n, int max_batch, int *out);
+int lsd_last_report(hvo_ctx *ctx, int *out);
 
 static inline hipStream_t hvo_stream_lsd(hvo_ctx *c) { return (c->serialize || c->lsd_on_orb_stream) ? c->stream : c->s_lsd; }
 static inline hipStream_t hvo_stream_peac(hvo_ctx *c) { return c->serialize ? c->stream : c->s_peac; }

@@ -51,6 +51,44 @@ static double lsd_sqrt_threshold(double rho)
     return c;
 }
 
+// tuning variables as the environment has them (a plan keeps the copy made when it was built)
+struct LsdKnobs {
+    Knob dense, lat, async_w, async_early, async_lds, lat_lds, lbd_split, lbd_desc, spin_max;
+    int chunk_env = 0;                 // HVO_LSD_CHUNK (> 0), 0: not set
+    bool compact = false;              // HVO_LSD_COMPACT
+    bool pre_split = false;            // HVO_LSD_PRE_SPLIT
+    void read_env()
+    {
+        dense.read("HVO_LSD_DENSE"); lat.read("HVO_LSD_LAT"); async_w.read("HVO_LSD_ASYNC"); async_early.read("HVO_LSD_ASYNC_EARLY");
+        async_lds.read("HVO_LSD_ASYNC_LDS"); lat_lds.read("HVO_LSD_LAT_LDS"); lbd_split.read("HVO_LBD_SPLIT"); lbd_desc.read("HVO_LBD_DESC"); spin_max.read("HVO_LSD_ASYNC_SPIN_MAX");
+        { const char *e = getenv("HVO_LSD_CHUNK"); chunk_env = (e && atoi(e) > 0) ? atoi(e) : 0; }
+        { const char *e = getenv("HVO_LSD_COMPACT"); compact = e && atoi(e) != 0; }
+        { const char *e = getenv("HVO_LSD_PRE_SPLIT"); pre_split = e && atoi(e) != 0; }
+    }
+};
+// what the selection depends on besides the batch size
+struct LsdGeom { int w = 0, h = 0, sw = 0, sh = 0, nwords = 0; bool pre_fits = true; /* k_lsd_pre's tile and ring hold this geometry */ };
+// The kernels one lsd_run launches for n frames, chosen by lsd_select and by nothing else: lsd_build_plan sizes the plan and lsd_run launches
+// from this record, hvo_debug_launch_report / hvo_debug_plan_select print it (the fields in order, one int each)
+enum { LSD_GROW_ASYNC = 0, LSD_GROW_LAT = 1, LSD_GROW = 2, LSD_GROW_DENSE = 3, LSD_GROW_C = 4, LSD_GROW_DENSE_C = 5 };
+struct LsdSel {
+    int pre_form = 0;         // 0: k_lsd_pre, 1: k_lsd_blur + k_lsd_resize_grad, 2: the CV_8U reading
+    int compact = 0;          // compact records
+    int chunk = 0;            // frames per chunk of the preamble, LBD and culling loops
+    int chunks = 0;           // chunks a run of n frames walks
+    int grow = -1;            // LSD_GROW_*
+    int async_w = 0;          // workers per frame of k_lsd_grow_async, 0: not async
+    int async_fallback = 0;   // the fall-back relaunch (preamble + k_lsd_grow with redo) is enqueued behind the async kernel
+    int async_lds = 0;        // LDS bytes the async workgroups request
+    int lat_lds = 0;          // LDS bytes k_lsd_grow_lat requests
+    int lbd_split = 0;        // 0: k_lbd_blur_sobel, 1: k_lbd_blur5 + k_lbd_sobel, 2: the float-kernel reading + k_lbd_sobel
+    int lbd_desc = 0;         // 1: k_lbd_line_setup + k_lbd_desc, 0: k_lbd_desc_v1
+    int perm_items = 0;       // frames the growing kernel's launch order permutes, 0: in order
+    int n = 0;                // frames of the run
+    int cull = 0;             // the culling pass ran
+    int plan_batch = 0;       // frames the plan holds
+    int async_early = 0;      // HVO_LSD_ASYNC_EARLY as the async kernel got it
+};
 struct LsdPlan {
     int w = 0, h = 0, sw = 0, sh = 0, batch = 0, nfeat = 0, nwords = 0;
     double *d_blur = nullptr;                               // w*h doubles per frame of a chunk
@@ -80,7 +118,10 @@ struct LsdPlan {
     // k_lsd_grow_async (lsd_async.inc), allocated at its first launch for the first `async_b` frames of the plan
     bool pre_fused = true;             // k_lsd_pre instead of k_lsd_blur + k_lsd_resize_grad (HVO_LSD_PRE_SPLIT=1: the pair, with its fp64 image)
     // tuning variables, read when the plan is built (lsd_build_plan)
-    struct { Knob dense, lat, async_w, async_early, async_lds, lat_lds, lbd_split, lbd_desc, spin_max; } kn;
+    LsdKnobs kn;
+    LsdGeom geom;
+    LsdSel last;                       // what the last lsd_run launched (hvo_debug_launch_report)
+    bool ran = false;
     uint8_t *d_b8 = nullptr, *d_s8 = nullptr; int *d_rs8tab = nullptr;      // HVO_READING_LSD_8U: the u8 blurred image and the u8 scaled image of a chunk, the resize tables (readings.hip)
     size_t async_w_cap = 0;            // (frame, worker) pairs the per-worker scratch holds
     int *d_redo = nullptr; int async_last_n = 0, async_last_w = 0;      // frames the one-wave kernel grew again after the async growing gave up; the last async launch
@@ -1928,6 +1969,110 @@ static int lsd_ensure_plan(hvo_ctx *ctx, int w, int h, int batch)
     return rc;
 }
 
+// the LBD gradient image's form: 2 the float-kernel reading + k_lbd_sobel, 1 k_lbd_blur5 + k_lbd_sobel (its u8 image exists), 0 k_lbd_blur_sobel
+static int lbd_split_form(unsigned readings, bool have_b5) { return (readings & HVO_READING_BLUR_FLOAT) ? 2 : have_b5 ? 1 : 0; }
+// Which kernels n frames take in a plan of plan_batch frames of geometry g under the knobs kn.  Plain host arithmetic, no HIP call
+// (tests/test_launch_plan.py holds the thresholds as data)
+static LsdSel lsd_select(int n, int plan_batch, const LsdGeom &g, const LsdKnobs &kn, unsigned readings, bool have_b5, bool frame_perm_on, bool cull)
+{
+    LsdSel s;
+    s.n = n; s.plan_batch = plan_batch; s.cull = cull ? 1 : 0;
+    const size_t nsp = (size_t)g.sw * g.sh;
+    // transient images (the fp64 blurred image between k_lsd_blur and k_lsd_resize_grad, the Sobel image between k_lbd_blur_sobel and
+    // k_lbd_desc) exist for a CHUNK of the batch only: lsd_run walks the batch chunk by chunk through those kernels (3.7 MB per frame saved)
+    s.chunk = (int)std::min<size_t>((size_t)plan_batch, 512);
+    if (kn.chunk_env > 0) s.chunk = (int)std::min<size_t>((size_t)plan_batch, (size_t)kn.chunk_env);
+    // compact records (HVO_LSD_COMPACT): the dense record image exists for a chunk only
+    // (at most ~3.3 GB of it), the batch keeps a pool sized for HVO_LSD_COMPACT_FRAC of the pixels (lsd_run grows it when a batch asks for more)
+    // Opt-in (HVO_LSD_COMPACT=1): it buys memory, not time.  Measured: 22.1 -> 18.0 MB per 640x480 frame for 5 % of the step (the compaction
+    // pass and the longer index arithmetic of an issue-bound kernel); 1280x960: 78 -> ~60 MB, 4096 frames resident instead of 3072, but
+    // 8.5 k frames/s at 4096 against 8.95 k at 3072 with one record per pixel -- the wave slots are full by then.
+    s.compact = kn.compact ? 1 : 0;
+    if (kn.compact) {
+        const size_t fit = std::max<size_t>(64, (size_t)(3.3e9 / (double)(nsp * sizeof(double4))) / 64 * 64);
+        s.chunk = (int)std::min<size_t>((size_t)s.chunk, std::min<size_t>(fit, 512));
+    }
+    s.chunks = (n + s.chunk - 1) / s.chunk;
+    const bool pre_fused = !kn.pre_split && g.pre_fits;
+    s.pre_form = (readings & HVO_READING_LSD_8U) ? 2 : pre_fused ? 0 : 1;
+    s.lbd_split = lbd_split_form(readings, have_b5 || kn.lbd_split.set);
+    // HVO_LBD_DESC=0: the one-kernel descriptor, kept for A/B runs; it also serves images whose coordinates could leave a short (LBD_SHORT_SAFE)
+    s.lbd_desc = (!kn.lbd_desc.off() && std::max(g.w, g.h) <= LBD_SHORT_SAFE) ? 1 : 0;
+    s.perm_items = (n >= 2 && frame_perm_on) ? n : 0;
+    bool dense = n > 5 * 1024;
+    if (kn.dense.set) dense = kn.dense.v != 0;              // HVO_LSD_DENSE: tests force either kernel on small batches
+    // a handful of frames (the streamed mode, a tracker's small batches): the latency variant with the mask in LDS
+    bool lat = n <= 64 && (size_t)g.nwords * 4 <= 150 * 1024 && !kn.compact;
+    if (kn.lat.set) lat = kn.lat.v != 0 && (size_t)g.nwords * 4 <= 150 * 1024 && !kn.compact;      // HVO_LSD_LAT
+    // a handful of frames: W waves per frame grow regions side by side and commit them in seed order (lsd_async.inc); HVO_LSD_ASYNC = W, 0: off
+    // (default: up to 16 frames; at 32 frames the one-wave kernel beside the plane chain is the faster whole, tools/latency.py)
+    // Workers per frame.  A handful of frames: as many as pay (32 / 16; 64 for a lone large frame).  Round 5 lifted the 16-frame limit of the
+    // scratch (allocated per (frames, W) now: HVO_LSD_ASYNC = W works for up to 1024 frames) and MEASURED 64-512 frames with W = 2-16
+    // (profiles/r05_async_midsize_batches.txt): slower than one wave per frame everywhere but at 128 frames (-7 %) -- batch256 26.5 -> 31.3 ms
+    // at W = 4, 33.5 at W = 8, 34.8 at W = 2 -- the workers that wait for their turn poll, and with a wave on every SIMD already their polling
+    // takes the issue slots the growing workers need.  The default stays: async up to 16 frames.
+    int aw = n <= 8 ? 32 : n <= 16 ? 16 : 0;
+    if (n <= 2 && nsp >= 600000) aw = 64;                  // a lone large frame (1280x960: 5.4 k seeds): more regions in flight
+    if (kn.async_w.set) aw = std::min(std::max(kn.async_w.v, 0), LA_MAXW);
+    if (readings & HVO_READING_LSD_8U) aw = 0;              // (the async growing's fall-back forms a frame again with the default preamble)
+    // the fall-back of the split preamble forms the frames again from d_blur, which holds the last chunk only: with more frames than a
+    // chunk it could not (HVO_LSD_PRE_SPLIT=1 with HVO_LSD_CHUNK < n, an A/B layout), so such a batch is not grown async
+    if (!pre_fused && n > s.chunk) aw = 0;
+    if (!(aw > 0 && n <= 1024 && !kn.compact)) aw = 0;
+    if (aw > 0) {
+        s.grow = LSD_GROW_ASYNC; s.async_w = aw; s.async_fallback = 1; s.async_early = kn.async_early.or_(1);
+        // (an LDS request keeps these one-wave workgroups off the CUs where a frame's AHC waves sit -- k_peac_cluster_heads takes 108 KB --:
+        // both are bound by instruction issue and a shared SIMD slows both; HVO_LSD_ASYNC_LDS: bytes [0 for a lone frame's 32-64 workers, 56 K beside other frames])
+        size_t alds = (n > 2 && n <= 16) ? 56 * 1024 : 0;       // (more frames: the workers ARE the machine's load, nothing to keep them away from)
+        if (kn.async_lds.set) alds = (size_t)std::min(std::max(kn.async_lds.v, 0), 150 * 1024);
+        s.async_lds = (int)alds;
+    } else if (lat) {
+        s.grow = LSD_GROW_LAT;
+        // The LDS request also keeps this one-wave workgroup off the CUs where a frame's five AHC waves sit (k_peac_cluster_heads takes
+        // 108 KB): both are bound by instruction issue and a shared SIMD slows both (HVO_LSD_LAT_LDS: bytes requested at least [56 K])
+        size_t lds = (size_t)g.nwords * 4, floor_ = 56 * 1024;
+        if (kn.lat_lds.set) floor_ = (size_t)std::max(kn.lat_lds.v, 0);      // HVO_LSD_LAT_LDS
+        if (lds < floor_ && floor_ <= 150 * 1024) lds = floor_;
+        s.lat_lds = (int)lds;
+    } else if (kn.compact) s.grow = dense ? LSD_GROW_DENSE_C : LSD_GROW_C;
+    else s.grow = dense ? LSD_GROW_DENSE : LSD_GROW;     // dense: more frames than five waves per SIMD hold
+    return s;
+}
+
+
+// the resize tables of the 0.8x scale (cv::resize INTER_LINEAR): source column / rows and weights of every scaled column / row
+static void lsd_resize_tables(int w, int h, int sw, int sh, std::vector<int> &xofs, std::vector<int> &yofs, std::vector<float> &xa, std::vector<float> &yb)
+{
+    xofs.assign(sw, 0); yofs.assign(sh + PRE_CH, 0); xa.assign(2 * sw, 0.f); yb.assign(2 * (sh + PRE_CH), 0.f);      // (row tables padded by a chunk of k_lsd_pre)
+    const double scale = 1. / 0.8;
+    for (int dx = 0; dx < sw; dx++) {
+        float fx = (float)((dx + 0.5) * scale - 0.5); int sx = cvfloor_f(fx); fx -= sx;
+        if (sx < 0) { fx = 0; sx = 0; }
+        if (sx >= w - 1) { fx = 0; sx = w - 1; }
+        xofs[dx] = sx; xa[2 * dx] = 1.f - fx; xa[2 * dx + 1] = fx;
+    }
+    for (int dy = 0; dy < sh; dy++) {
+        float fy = (float)((dy + 0.5) * scale - 0.5); int sy = cvfloor_f(fy); fy -= sy;
+        int sy0 = std::min(std::max(sy, 0), h - 1), sy1 = std::min(std::max(sy + 1, 0), h - 1);
+        yofs[dy] = sy0 | (sy1 << 16); yb[2 * dy] = 1.f - fy; yb[2 * dy + 1] = fy;
+    }
+}
+static bool lsd_geom(int w, int h, LsdGeom *g, std::vector<int> &xofs, std::vector<int> &yofs, std::vector<float> &xa, std::vector<float> &yb)
+{
+    g->w = w; g->h = h; g->sw = (int)lrint(w * 0.8); g->sh = (int)lrint(h * 0.8);
+    if (g->sw < 8 || g->sh < 8 || w > 32767 || h > 32767) return false;
+    g->nwords = ((g->sw + 31) / 32) * g->sh;
+    lsd_resize_tables(w, h, g->sw, g->sh, xofs, yofs, xa, yb);
+    // a band's source columns must fit the workgroup's 256 threads (true for the 0.8x scale: 192 / 0.8 + 2; checked, not assumed)
+    int maxc = 0;
+    for (int x0 = 0; x0 < g->sw; x0 += PRE_TW) { const int xe = std::min(x0 + PRE_TW, g->sw - 1); maxc = std::max(maxc, std::min(xofs[xe] + 1, w - 1) - xofs[x0] + 1); }
+    // the blurred rows a chunk's scaled rows interpolate from must fit the ring (six at the 0.8x scale)
+    int maxr = 0;
+    for (int ys = 0; ys < g->sh; ys += PRE_CH) maxr = std::max(maxr, (yofs[std::min(ys + PRE_CH - 1, g->sh - 1)] >> 16) - (yofs[ys] & 0xFFFF) + 1);
+    g->pre_fits = !(maxc > 256 || maxr > PRE_RING);
+    return true;
+}
+
 static int lsd_build_plan(hvo_ctx *ctx, int w, int h, int batch)
 {
     LsdPlan *P = new LsdPlan();
@@ -1960,19 +2105,8 @@ static int lsd_build_plan(hvo_ctx *ctx, int w, int h, int batch)
         u = (9 * 7 - 1) / 2; sigma = u; inv = -1 / (2 * sigma * sigma);
         for (int i = 0; i < 63; i++) { double d = i - u; P->gG[i] = exp(d * d * inv); }
     }
-    std::vector<int> xofs(P->sw), yofs(P->sh + PRE_CH, 0); std::vector<float> xa(2 * P->sw), yb(2 * (P->sh + PRE_CH), 0.f);      // (row tables padded by a chunk of k_lsd_pre)
-    const double scale = 1. / SCALE;
-    for (int dx = 0; dx < P->sw; dx++) {
-        float fx = (float)((dx + 0.5) * scale - 0.5); int sx = cvfloor_f(fx); fx -= sx;
-        if (sx < 0) { fx = 0; sx = 0; }
-        if (sx >= w - 1) { fx = 0; sx = w - 1; }
-        xofs[dx] = sx; xa[2 * dx] = 1.f - fx; xa[2 * dx + 1] = fx;
-    }
-    for (int dy = 0; dy < P->sh; dy++) {
-        float fy = (float)((dy + 0.5) * scale - 0.5); int sy = cvfloor_f(fy); fy -= sy;
-        int sy0 = std::min(std::max(sy, 0), h - 1), sy1 = std::min(std::max(sy + 1, 0), h - 1);
-        yofs[dy] = sy0 | (sy1 << 16); yb[2 * dy] = 1.f - fy; yb[2 * dy + 1] = fy;
-    }
+    std::vector<int> xofs, yofs; std::vector<float> xa, yb;
+    if (!lsd_geom(w, h, &P->geom, xofs, yofs, xa, yb)) return HVO_ERR_UNSUPPORTED;
     std::vector<float> gLf(21), gGf(63);
     for (int i = 0; i < 21; i++) gLf[i] = (float)P->gL[i];
     for (int i = 0; i < 63; i++) gGf[i] = (float)P->gG[i];
@@ -1980,26 +2114,14 @@ static int lsd_build_plan(hvo_ctx *ctx, int w, int h, int batch)
 #define PA(ptr, n) HVO_HIP(hipMalloc((void **)&(ptr), (n)))
     // transient images (the fp64 blurred image between k_lsd_blur and k_lsd_resize_grad, the Sobel image between k_lbd_blur_sobel and
     // k_lbd_desc) exist for a CHUNK of the batch only: lsd_run walks the batch chunk by chunk through those kernels (3.7 MB per frame saved)
-    P->kn.dense.read("HVO_LSD_DENSE"); P->kn.lat.read("HVO_LSD_LAT"); P->kn.async_w.read("HVO_LSD_ASYNC"); P->kn.async_early.read("HVO_LSD_ASYNC_EARLY");
-    P->kn.async_lds.read("HVO_LSD_ASYNC_LDS"); P->kn.lat_lds.read("HVO_LSD_LAT_LDS"); P->kn.lbd_split.read("HVO_LBD_SPLIT"); P->kn.lbd_desc.read("HVO_LBD_DESC"); P->kn.spin_max.read("HVO_LSD_ASYNC_SPIN_MAX");
-    P->chunk = (int)std::min<size_t>(B, 512);
-    { const char *e = getenv("HVO_LSD_CHUNK"); if (e && atoi(e) > 0) P->chunk = (int)std::min<size_t>(B, (size_t)atoi(e)); }
-    // compact records (HVO_LSD_COMPACT): the dense record image exists for a chunk only
-    // (at most ~3.3 GB of it), the batch keeps a pool sized for HVO_LSD_COMPACT_FRAC of the pixels (lsd_run grows it when a batch asks for more)
-    // Opt-in (HVO_LSD_COMPACT=1): it buys memory, not time.  Measured: 22.1 -> 18.0 MB per 640x480 frame for 5 % of the step (the compaction
-    // pass and the longer index arithmetic of an issue-bound kernel); 1280x960: 78 -> ~60 MB, 4096 frames resident instead of 3072, but
-    // 8.5 k frames/s at 4096 against 8.95 k at 3072 with one record per pixel -- the wave slots are full by then.
-    P->compact = false;
-    { const char *e = getenv("HVO_LSD_COMPACT"); if (e) P->compact = atoi(e) != 0; }
+    // (chunk, compact records and the preamble's form: lsd_select)
+    P->kn.read_env();
+    const LsdSel ps = lsd_select((int)B, (int)B, P->geom, P->kn, 0u, false, true, false);
+    P->chunk = ps.chunk; P->compact = ps.compact != 0; P->pre_fused = ps.pre_form == 0;
     double frac = 0.27;
     { const char *e = getenv("HVO_LSD_COMPACT_FRAC"); if (e && atof(e) > 0) frac = std::min(1.0, atof(e)); }
-    if (P->compact) {
-        const size_t fit = std::max<size_t>(64, (size_t)(3.3e9 / (double)(nsp * sizeof(double4))) / 64 * 64);
-        P->chunk = (int)std::min<size_t>((size_t)P->chunk, std::min<size_t>(fit, 512));
-    }
     const size_t CB = (size_t)P->chunk;
-    { const char *e = getenv("HVO_LSD_PRE_SPLIT"); P->pre_fused = !(e && atoi(e) != 0); }
-    // the tile of k_lsd_pre holds the source rectangle of PRE_TW x PRE_TR scaled pixels: true for the 0.8 scale of every geometry (asserted here)
+    // the tile of k_lsd_pre holds the source rectangle of PRE_TW x PRE_TR scaled pixels: true for the 0.8 scale of every geometry (checked by lsd_geom)
     if (!P->pre_fused) PA(P->d_blur, CB * npix * 8);
     if (P->compact) {
         PA(P->d_px, CB * nsp * sizeof(double4));
@@ -2017,18 +2139,9 @@ static int lsd_build_plan(hvo_ctx *ctx, int w, int h, int batch)
     if (P->kn.lbd_split.set) PA(P->d_b5, CB * npix);
     PA(P->d_dxy, CB * npix * sizeof(short2));
     // HVO_LBD_DESC=0: the one-kernel descriptor, kept for A/B runs; it also serves images whose coordinates could leave a short (LBD_SHORT_SAFE)
-    if (!P->kn.lbd_desc.off() && std::max(w, h) <= LBD_SHORT_SAFE) PA(P->d_lbdl, CB * P->nfeat * sizeof(LbdLine));
+    if (ps.lbd_desc) PA(P->d_lbdl, CB * P->nfeat * sizeof(LbdLine));
     PA(P->d_xofs, P->sw * 4); PA(P->d_yofs, (P->sh + PRE_CH) * 4); PA(P->d_xa, P->sw * 8); PA(P->d_yb, (P->sh + PRE_CH) * 8);      // (k_lsd_pre reads the row tables a chunk at a time: padded)
     PA(P->d_gL, 21 * 4); PA(P->d_gG, 63 * 4); PA(P->d_stats, B * 64);
-    if (P->pre_fused) {
-        // a band's source columns must fit the workgroup's 256 threads (true for the 0.8x scale: 192 / 0.8 + 2; checked, not assumed)
-        int maxc = 0;
-        for (int x0 = 0; x0 < P->sw; x0 += PRE_TW) { const int xe = std::min(x0 + PRE_TW, P->sw - 1); maxc = std::max(maxc, std::min(xofs[xe] + 1, w - 1) - xofs[x0] + 1); }
-        // the blurred rows a chunk's scaled rows interpolate from must fit the ring (six at the 0.8x scale)
-        int maxr = 0;
-        for (int ys = 0; ys < P->sh; ys += PRE_CH) maxr = std::max(maxr, (yofs[std::min(ys + PRE_CH - 1, P->sh - 1)] >> 16) - (yofs[ys] & 0xFFFF) + 1);
-        if (maxc > 256 || maxr > PRE_RING) { P->pre_fused = false; PA(P->d_blur, CB * npix * 8); }
-    }
 #undef PA
     HVO_HIP(hipMemcpy(P->d_xofs, xofs.data(), P->sw * 4, hipMemcpyHostToDevice));
     HVO_HIP(hipMemcpy(P->d_yofs, yofs.data(), yofs.size() * 4, hipMemcpyHostToDevice));
@@ -2055,16 +2168,16 @@ int lsd_prepare(hvo_ctx *ctx, int w, int h, int batch, bool culled, LsdView *v)
 }
 
 // The LBD gradient image of m frames (gc: the first one's gray image in the pyramid slab) into P->d_dxy
-static int lbd_sobel_enqueue(hvo_ctx *ctx, LsdPlan *P, hipStream_t st, const uint8_t *gc, int m)
+static int lbd_sobel_enqueue(hvo_ctx *ctx, LsdPlan *P, hipStream_t st, const uint8_t *gc, int m, int form /* lbd_split_form */)
 {
     OrbPlan &O = ctx->orb;
     const int w = P->w, h = P->h, gpitch = O.lev[0].pitch;
     int rc;
-    if (ctx->readings & HVO_READING_BLUR_FLOAT) {  // GaussianBlur(5 x 5, sigma 1) in the float-kernel reading (readings.hip), then the Sobel pair
+    if (form == 2) {                                // GaussianBlur(5 x 5, sigma 1) in the float-kernel reading (readings.hip), then the Sobel pair
         if (!P->d_b5) HVO_HIP(hipMalloc((void **)&P->d_b5, (size_t)P->chunk * w * h));
         if ((rc = readings_gblur_enqueue(st, gc, O.pyr_bytes, gpitch, w, h, P->d_b5, (size_t)w * h, w, m, 5, 1.0, true))) return rc;
         hipLaunchKernelGGL(k_lbd_sobel, dim3((w + 255) / 256, (h + LBD_BLUR_ROWS - 1) / LBD_BLUR_ROWS, m), dim3(256), 0, st, P->d_b5, P->d_dxy, w, h);
-    } else if (P->d_b5) {                           // the two-kernel formulation (blurred u8 image materialised), kept for A/B runs (HVO_LBD_SPLIT)
+    } else if (form == 1) {                         // the two-kernel formulation (blurred u8 image materialised), kept for A/B runs (HVO_LBD_SPLIT)
         hipLaunchKernelGGL(k_lbd_blur5, dim3((w + 255) / 256, (h + LBD_BLUR_ROWS - 1) / LBD_BLUR_ROWS, m), dim3(256), 0, st, gc, O.pyr_bytes, gpitch, P->d_b5, w, h, P->k5[0], P->k5[1], P->k5[2]);
         hipLaunchKernelGGL(k_lbd_sobel, dim3((w + 255) / 256, (h + LBD_BLUR_ROWS - 1) / LBD_BLUR_ROWS, m), dim3(256), 0, st, P->d_b5, P->d_dxy, w, h);
     } else {
@@ -2087,6 +2200,31 @@ static void lbd_desc_enqueue(const LsdPlan *P, hipStream_t st, int m, const hvo_
     hipLaunchKernelGGL(k_lbd_desc, dim3(kl_cap, m), dim3(64), 0, st, reinterpret_cast<const int *>(P->d_dxy), P->w, P->h, (const LbdLine *)scratch, nkl, kl_cap, P->d_gL, P->d_gG, desc);
 }
 
+static void lsd_sel_ints(const LsdSel &s, int *o)
+{
+    const int v[HVO_REPORT_STAGE_INTS] = { s.pre_form, s.compact, s.chunk, s.chunks, s.grow, s.async_w, s.async_fallback, s.async_lds, s.lat_lds, s.lbd_split, s.lbd_desc,
+                                           s.perm_items, s.n, s.cull, s.plan_batch, s.async_early };
+    memcpy(o, v, sizeof v);
+}
+// diagnostics: the selection for n frames of w x h in a context of max_batch frames under the environment as it stands, without a plan or a device
+int lsd_plan_select_env(int w, int h, int n, int max_batch, int *out)
+{
+    LsdGeom g; std::vector<int> xofs, yofs; std::vector<float> xa, yb;
+    if (n < 1 || w < 1 || h < 1 || !lsd_geom(w, h, &g, xofs, yofs, xa, yb)) return HVO_ERR_UNSUPPORTED;
+    LsdKnobs kn; kn.read_env();
+    Knob fp; fp.read("HVO_FRAME_PERM");
+    lsd_sel_ints(lsd_select(n, std::max(n, max_batch), g, kn, 0u, false, !fp.off(), false), out);
+    return HVO_OK;
+}
+// ... and what the last lsd_run of this context launched (HVO_ERR_INVALID_ARG: none yet)
+int lsd_last_report(hvo_ctx *ctx, int *out)
+{
+    LsdPlan *P = plan_of(ctx);
+    if (!P || !P->ran) return HVO_ERR_INVALID_ARG;
+    lsd_sel_ints(P->last, out);
+    return HVO_OK;
+}
+
 int lsd_run(hvo_ctx *ctx, int n, bool cull)
 {
     // input: level 0 of the ORB pyramid slab (the uploaded gray image)
@@ -2096,6 +2234,9 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
     if (rc) return rc;
     LsdPlan *P = plan_of(ctx);
     P->async_last_n = P->async_last_w = 0;                     // hvo_lsd_async_report describes THIS launch: nothing async until it is
+    const LsdSel sel = lsd_select(n, P->batch, P->geom, P->kn, ctx->readings, P->d_b5 != nullptr, !ctx->kn_frame_perm.off(), cull);
+    if (sel.chunk != P->chunk || (sel.compact != 0) != P->compact) return HVO_ERR_INVALID_ARG;      // (the plan was sized from the same function)
+    P->last = sel; P->ran = true;
     hipStream_t st = hvo_stream_lsd(ctx);
     const int w = P->w, h = P->h, sw = P->sw, sh = P->sh;
     const uint8_t *gray = O.d_pyr + O.lev[0].img_off;
@@ -2107,7 +2248,7 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
         if (P->compact) HVO_HIP(hipMemsetAsync(P->d_pooltop, 0, 16, st));
         for (int c0 = 0; c0 < n; c0 += P->chunk) {
             const int m = std::min(P->chunk, n - c0);
-            if (ctx->readings & HVO_READING_LSD_8U) {
+            if (sel.pre_form == 2) {
                 // the detector on CV_8U (readings.hip): u8 GaussianBlur 7 x 7 sigma 0.75, u8 resize 0.8x, gradients of the rounded bytes
                 id = hvo_prof_begin(ctx, "lsd_gradient", st);
                 const size_t npix_ = (size_t)w * h;
@@ -2120,7 +2261,7 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
                 if ((rc = readings_resize_enqueue(st, P->d_b8, npix_, w, w, P->d_s8, nsp, sw, sw, sh, m, P->d_rs8tab))) return rc;
                 if ((rc = readings_lsd_grad8_enqueue(st, P->d_s8, nsp, sw, sh, P->d_px + (P->compact ? 0 : (size_t)c0 * nsp), P->d_defined + (size_t)c0 * P->nwords, P->nwords, P->rho, m))) return rc;
             } else
-            if (P->pre_fused) {
+            if (sel.pre_form == 0) {
                 // one kernel from the u8 image to the records (k_lsd_pre); the fp64 blurred image is never written
                 id = hvo_prof_begin(ctx, "lsd_gradient", st);
                 hipLaunchKernelGGL(k_lsd_pre, dim3((sw + PRE_TW - 1) / PRE_TW, (sh - 1 + PRE_SEG - 1) / PRE_SEG, m), dim3(256), 0, st, gray + (size_t)c0 * O.pyr_bytes, O.pyr_bytes, gpitch,
@@ -2164,31 +2305,13 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
     if ((ctx->sched == 2 || ctx->sched == 5 || ctx->sched == 6) && ctx->fast_recorded && !ctx->serialize) HVO_HIP(hipStreamWaitEvent(st, ctx->ev_fast, 0));
     id = hvo_prof_begin(ctx, "lsd_grow", st);
     GrowArgs g;
-    g.px4 = P->compact ? P->d_pool : P->d_px; g.avail = P->d_defined; g.reg = P->d_reg; g.segs = P->d_segs; g.perm = hvo_frame_perm(ctx, n);
+    g.px4 = P->compact ? P->d_pool : P->d_px; g.avail = P->d_defined; g.reg = P->d_reg; g.segs = P->d_segs; g.perm = sel.perm_items ? hvo_frame_perm(ctx, sel.perm_items) : nullptr;
     g.defmask = P->d_defmask; g.wprefix = P->d_wprefix; g.fbase = P->d_fbase;
     g.stats = P->d_stats; g.kl_all = P->d_kl_all; g.kl = P->d_kl; g.fn = P->d_fn; g.nkl = P->d_nkl; g.flags = P->d_flags;
     g.sw = sw; g.sh = sh; g.nwords = P->nwords; g.w = w; g.h = h; g.nfeat = P->nfeat; g.kl_cap = P->nfeat;
     g.rho = P->rho; g.prec = P->prec; g.p = P->p; g.min_reg = P->min_reg; g.maxseg = P->maxseg; g.redo = 0; g.redo_count = nullptr;
-    bool dense = n > 5 * 1024;
-    if (P->kn.dense.set) dense = P->kn.dense.v != 0;              // HVO_LSD_DENSE: tests force either kernel on small batches
-    // a handful of frames (the streamed mode, a tracker's small batches): the latency variant with the mask in LDS
-    bool lat = n <= 64 && (size_t)P->nwords * 4 <= 150 * 1024 && !P->compact;
-    if (P->kn.lat.set) lat = P->kn.lat.v != 0 && (size_t)P->nwords * 4 <= 150 * 1024 && !P->compact;      // HVO_LSD_LAT
-    // a handful of frames: W waves per frame grow regions side by side and commit them in seed order (lsd_async.inc); HVO_LSD_ASYNC = W, 0: off
-    // (default: up to 16 frames; at 32 frames the one-wave kernel beside the plane chain is the faster whole, tools/latency.py)
-    // Workers per frame.  A handful of frames: as many as pay (32 / 16; 64 for a lone large frame).  Round 5 lifted the 16-frame limit of the
-    // scratch (allocated per (frames, W) now: HVO_LSD_ASYNC = W works for up to 1024 frames) and MEASURED 64-512 frames with W = 2-16
-    // (profiles/r05_async_midsize_batches.txt): slower than one wave per frame everywhere but at 128 frames (-7 %) -- batch256 26.5 -> 31.3 ms
-    // at W = 4, 33.5 at W = 8, 34.8 at W = 2 -- the workers that wait for their turn poll, and with a wave on every SIMD already their polling
-    // takes the issue slots the growing workers need.  The default stays: async up to 16 frames.
-    int aw = n <= 8 ? 32 : n <= 16 ? 16 : 0;
-    if (n <= 2 && (size_t)sw * sh >= 600000) aw = 64;          // a lone large frame (1280x960: 5.4 k seeds): more regions in flight
-    if (P->kn.async_w.set) aw = std::min(std::max(P->kn.async_w.v, 0), LA_MAXW);
-    if (ctx->readings & HVO_READING_LSD_8U) aw = 0;             // (the async growing's fall-back forms a frame again with the default preamble)
-    // the fall-back of the split preamble forms the frames again from d_blur, which holds the last chunk only: with more frames than a
-    // chunk it could not (HVO_LSD_PRE_SPLIT=1 with HVO_LSD_CHUNK < n, an A/B layout), so such a batch is not grown async
-    if (!P->pre_fused && n > P->chunk) aw = 0;
-    if (aw > 0 && n <= 1024 && !P->compact) {
+    const int aw = sel.async_w;
+    if (sel.grow == LSD_GROW_ASYNC) {
         // scratch for (n frames, aw workers): owner tags and control block per frame; region list, held-pixel list and membership byte map per worker
         const size_t need_f = (size_t)n, need_w = (size_t)n * aw;
         if (need_f > (size_t)P->async_b || need_w > P->async_w_cap) {
@@ -2210,13 +2333,10 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
             // left some behind, so every launch starts from a clean state (7 MB per 640x480 frame at 32 workers, microseconds)
             HVO_HIP(hipMemsetAsync(P->d_atags, 0xFF, (size_t)n * P->nwords * 32 * 4, st));
             HVO_HIP(hipMemsetAsync(P->d_ainreg, 0, (size_t)n * aw * P->nwords * 32, st));
-            LaArgs a; a.g = g; a.tags = P->d_atags; a.inreg = P->d_ainreg; a.ctl = (LaCtl *)P->d_actl; a.lists = P->d_alists; a.blocked = P->d_ablk; a.freg = P->d_afreg; a.W = aw; a.n = n; a.early = P->kn.async_early.or_(1);
+            LaArgs a; a.g = g; a.tags = P->d_atags; a.inreg = P->d_ainreg; a.ctl = (LaCtl *)P->d_actl; a.lists = P->d_alists; a.blocked = P->d_ablk; a.freg = P->d_afreg; a.W = aw; a.n = n; a.early = sel.async_early;
             // the turn's wait is bounded (a frame whose wait expires is grown again below, by the one-wave kernel); HVO_LSD_ASYNC_SPIN_MAX: a test hook
             a.spin_max = P->kn.spin_max.set ? (unsigned)std::max(P->kn.spin_max.v, 0) : LA_SPIN_MAX;
-            // (an LDS request keeps these one-wave workgroups off the CUs where a frame's AHC waves sit -- k_peac_cluster_heads takes 108 KB --:
-            // both are bound by instruction issue and a shared SIMD slows both; HVO_LSD_ASYNC_LDS: bytes [0 for a lone frame's 32-64 workers, 56 K beside other frames])
-            size_t alds = (n > 2 && n <= 16) ? 56 * 1024 : 0;       // (more frames: the workers ARE the machine's load, nothing to keep them away from)
-            if (P->kn.async_lds.set) alds = (size_t)std::min(std::max(P->kn.async_lds.v, 0), 150 * 1024);
+            const size_t alds = (size_t)sel.async_lds;
             if (hvo_ensure_dyn_lds(reinterpret_cast<const void *>(k_lsd_grow_async), alds)) return HVO_ERR_HIP;
             hipLaunchKernelGGL(k_lsd_grow_async, dim3(((n + 7) / 8) * 8 * aw), dim3(64), alds, st, a);      // workgroups b, b + 8, ... of a frame: one XCD
             // FAIL SOFT: a frame the workers gave up on (flag 4: the bounded wait expired, or no worker sat on the frame's XCD) is
@@ -2230,20 +2350,14 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
                                    P->d_px, P->d_defined, P->nwords, P->rho);      // (the split preamble: n <= chunk, checked above, so the blurred images of all n frames are still in d_blur; every frame is formed again)
             { GrowArgs g2 = g; g2.redo = 1; g2.redo_count = P->d_redo; g2.perm = nullptr; hipLaunchKernelGGL(k_lsd_grow, dim3(n), dim3(64), 0, st, g2); }
         }
-    } else aw = 0;
-    if (aw > 0) {
-    } else if (lat) {
-        // The LDS request also keeps this one-wave workgroup off the CUs where a frame's five AHC waves sit (k_peac_cluster_heads takes
-        // 108 KB): both are bound by instruction issue and a shared SIMD slows both (HVO_LSD_LAT_LDS: bytes requested at least [56 K])
-        size_t lds = (size_t)P->nwords * 4, floor_ = 56 * 1024;
-        if (P->kn.lat_lds.set) floor_ = (size_t)std::max(P->kn.lat_lds.v, 0);      // HVO_LSD_LAT_LDS
-        if (lds < floor_ && floor_ <= 150 * 1024) lds = floor_;
+    } else if (sel.grow == LSD_GROW_LAT) {
+        const size_t lds = (size_t)sel.lat_lds;
         if (hvo_ensure_dyn_lds(reinterpret_cast<const void *>(k_lsd_grow_lat), lds)) return HVO_ERR_HIP;
         hipLaunchKernelGGL(k_lsd_grow_lat, dim3(n), dim3(64), lds, st, g);
-    } else if (P->compact) {
-        if (dense) hipLaunchKernelGGL(k_lsd_grow_dense_c, dim3(n), dim3(64), 0, st, g);
-        else hipLaunchKernelGGL(k_lsd_grow_c, dim3(n), dim3(64), 0, st, g);
-    } else if (dense) hipLaunchKernelGGL(k_lsd_grow_dense, dim3(n), dim3(64), 0, st, g);     // more frames than five waves per SIMD hold
+    }
+    else if (sel.grow == LSD_GROW_DENSE_C) hipLaunchKernelGGL(k_lsd_grow_dense_c, dim3(n), dim3(64), 0, st, g);
+    else if (sel.grow == LSD_GROW_C) hipLaunchKernelGGL(k_lsd_grow_c, dim3(n), dim3(64), 0, st, g);
+    else if (sel.grow == LSD_GROW_DENSE) hipLaunchKernelGGL(k_lsd_grow_dense, dim3(n), dim3(64), 0, st, g);     // more frames than five waves per SIMD hold
     else hipLaunchKernelGGL(k_lsd_grow, dim3(n), dim3(64), 0, st, g);
     hvo_prof_end(ctx, id);
     if (cull && P->nfeat > CULL_MAXL) return HVO_ERR_UNSUPPORTED;
@@ -2252,7 +2366,7 @@ int lsd_run(hvo_ctx *ctx, int n, bool cull)
         const uint8_t *gc = gray + (size_t)c0 * O.pyr_bytes;
         const size_t ko = (size_t)c0 * P->nfeat;
         id = hvo_prof_begin(ctx, "lbd_sobel", st);
-        if ((rc = lbd_sobel_enqueue(ctx, P, st, gc, m))) return rc;
+        if ((rc = lbd_sobel_enqueue(ctx, P, st, gc, m, sel.lbd_split))) return rc;
         hvo_prof_end(ctx, id);
         id = hvo_prof_begin(ctx, "lbd_desc", st);
         lbd_desc_enqueue(P, st, m, P->d_kl + ko, P->d_nkl + c0, P->nfeat, P->d_lbdl, P->d_desc + ko * 32);
@@ -2320,6 +2434,7 @@ extern "C" int hvo_extract_lsd(hvo_ctx *ctx, const uint8_t *gray, int w, int h, 
     int rc = orb_upload(ctx, 1, &in, w, h);
     if (rc) return rc;
     ctx->last_stages = 0;                                  // slot 0 of the resident batch has been overwritten
+    ctx->last_batch_valid = false;
     for (int i = 0; i < ctx->nprof; i++) ctx->prof[i].used = false;
     if ((rc = lsd_run(ctx, 1))) return rc;
     hvo_frame_out out; memset(&out, 0, sizeof(out));
@@ -2344,6 +2459,7 @@ extern "C" int hvo_extract_lsd_culled(hvo_ctx *ctx, const uint8_t *gray, int w, 
     int rc = orb_upload(ctx, 1, &in, w, h);
     if (rc) return rc;
     ctx->last_stages = 0;                                  // slot 0 of the resident batch has been overwritten
+    ctx->last_batch_valid = false;
     for (int i = 0; i < ctx->nprof; i++) ctx->prof[i].used = false;
     if ((rc = lsd_run(ctx, 1, true))) return rc;
     hvo_frame_out out; memset(&out, 0, sizeof(out));
@@ -2476,6 +2592,7 @@ extern "C" int hvo_debug_lbd_desc(hvo_ctx *ctx, const uint8_t *gray, int w, int 
     int rc = orb_upload(ctx, 1, &in, w, h);
     if (rc) return rc;
     ctx->last_stages = 0;                                  // slot 0 of the resident batch has been overwritten
+    ctx->last_batch_valid = false;
     OrbPlan &O = ctx->orb;
     if ((rc = lsd_ensure_plan(ctx, O.w, O.h, std::max(1, ctx->p.max_batch)))) return rc;
     LsdPlan *P = plan_of(ctx);
@@ -2485,7 +2602,7 @@ extern "C" int hvo_debug_lbd_desc(hvo_ctx *ctx, const uint8_t *gray, int w, int 
               hipMalloc((void **)&d_desc, (size_t)n * 32) == hipSuccess && (!P->d_lbdl || hipMalloc((void **)&d_rec, (size_t)n * sizeof(LbdLine)) == hipSuccess);
     ok = ok && hipMemcpy(d_kl, keylines, (size_t)n * sizeof(hvo_keyline), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_n, &n, 4, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
-        rc = lbd_sobel_enqueue(ctx, P, st, O.d_pyr + O.lev[0].img_off, 1);
+        rc = lbd_sobel_enqueue(ctx, P, st, O.d_pyr + O.lev[0].img_off, 1, lbd_split_form(ctx->readings, P->d_b5 != nullptr));
         if (!rc) {
             lbd_desc_enqueue(P, st, 1, d_kl, d_n, n, d_rec, d_desc);
             ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess && hipMemcpy(desc_out, d_desc, (size_t)n * 32, hipMemcpyDeviceToHost) == hipSuccess;

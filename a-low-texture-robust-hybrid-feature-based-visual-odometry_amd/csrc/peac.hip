@@ -34,6 +34,44 @@
 #define SEG_I 8           // ints per seg: N, rid, nouse, nb_off, nb_cnt, nb_cap, valid, pad
 #define LCAP 1024         // neighbour-list length staged in LDS
 
+// tuning variables as the environment has them (a plan keeps the copy made when it was built)
+struct PeacKnobs {
+    Knob edges, gl, perm, lend, slots, heads_maxn, heads, heads_big, poolcap, ldsq, flood_t, flood_epl, flood_perm, flood_delay, flood_slim;
+    void read_env()
+    {
+        edges.read("HVO_PEAC_EDGES"); gl.read("HVO_PEAC_GL"); perm.read("HVO_PEAC_PERM"); lend.read("HVO_PEAC_LEND"); slots.read("HVO_PEAC_SLOTS"); heads_maxn.read("HVO_PEAC_HEADS_MAXN");
+        heads.read("HVO_PEAC_HEADS"); heads_big.read("HVO_PEAC_HEADS_BIG"); poolcap.read("HVO_PEAC_POOLCAP"); ldsq.read("HVO_PEAC_LDSQ");
+        flood_t.read("HVO_FLOOD_T"); flood_epl.read("HVO_FLOOD_EPL"); flood_perm.read("HVO_FLOOD_PERM"); flood_delay.read("HVO_FLOOD_DELAY"); flood_slim.read("HVO_FLOOD_SLIM");
+    }
+};
+// what the selection depends on besides the batch size: sizes that follow from (w, h), and whether the slot form's scratch exists
+struct PeacGeom {
+    int nblk = 0, segcap = 0, poolcap = 0, tq_n0 = 0; bool have_lq = true;
+    void set(int w, int h) { nblk = (w / WIN) * (h / WIN); segcap = 2 * nblk + 2 * MAX_PLANES; poolcap = 16 * nblk + 2 * MAX_PLANES * MAX_PLANES; tq_n0 = (segcap + 255) / 256; }
+};
+// The kernels one peac_run launches for n frames, chosen by peac_select and by nothing else: peac_run launches from this record and
+// hvo_debug_launch_report / hvo_debug_plan_select print it (PEAC_REPORT_INTS ints in the order of the fields)
+enum { PEAC_CL_HEADS = 0, PEAC_CL_64 = 1, PEAC_CL_32 = 2, PEAC_CL_16 = 3, PEAC_CL_16_LEND = 4, PEAC_CL_SLOTS = 5 };
+#define PEAC_REPORT_INTS 16
+struct PeacSel {
+    int cluster = -1;         // PEAC_CL_*
+    int heads = 0;            // queue heads of k_peac_cluster_heads (2..4), 0 for the other forms
+    int heads_big = 0;        // ... its BIG form (keys in global memory)
+    int ldsq = 0;             // k_peac_cluster<64>: keys in LDS
+    int edges_done = 0;       // k_peac_edges ran before the clustering kernel
+    int poolcap = 0;          // forced pool capacity (HVO_PEAC_POOLCAP), 0: the plan's
+    int group = 0;            // lanes per frame of the grouped forms (64 / 32 / 16 ...)
+    int cluster_wgs = 0;      // workgroups of the clustering kernel
+    int perm_items = 0;       // items the clustering kernel's launch order permutes (frames or waves), 0: in order
+    int blkmap_y = 0;         // k_peac_blkmap: blocks per frame
+    int flood_t = 0;          // threads per frame of the flood
+    int flood_epl = 0;        // queue entries per thread and round
+    int flood_slim = 0;       // the slim first launch ran
+    int flood_perm_items = 0; // frames the flood's launch order permutes, 0: in order
+    int n = 0;                // frames of the run
+    int slots_fit = 0;        // labels fit the slot form's 16-bit halves
+};
+
 struct PeacPlan {
     int w = 0, h = 0, pitch = 0, Nw = 0, Nh = 0, nblk = 0, segcap = 0, poolcap = 0, qcap = 0, batch = 0;
     uint16_t *d_depth = nullptr;
@@ -51,7 +89,9 @@ struct PeacPlan {
     double c15 = 0, c60 = 0, c30 = 0;   // cos thresholds evaluated on the host (glibc), like the oracle
     double ang_factor = 0, ang_near = 0;
     // tuning variables, read when the plan is built (peac_build_plan)
-    struct { Knob edges, gl, perm, lend, slots, heads_maxn, heads, heads_big, poolcap, ldsq, flood_t, flood_epl, flood_perm, flood_delay, flood_slim; } kn;
+    PeacKnobs kn;
+    PeacSel last;                       // what the last peac_run launched (hvo_debug_launch_report)
+    bool ran = false;
 };
 
 static PeacPlan *plan_of(hvo_ctx *ctx) { return (PeacPlan *)ctx->peac; }
@@ -2053,9 +2093,7 @@ static int peac_build_plan(hvo_ctx *ctx, int w, int h, int batch)
 {
     PeacPlan *P = new PeacPlan();
     ctx->peac = P;
-    P->kn.edges.read("HVO_PEAC_EDGES"); P->kn.gl.read("HVO_PEAC_GL"); P->kn.perm.read("HVO_PEAC_PERM"); P->kn.lend.read("HVO_PEAC_LEND"); P->kn.slots.read("HVO_PEAC_SLOTS"); P->kn.heads_maxn.read("HVO_PEAC_HEADS_MAXN");
-    P->kn.heads.read("HVO_PEAC_HEADS"); P->kn.heads_big.read("HVO_PEAC_HEADS_BIG"); P->kn.poolcap.read("HVO_PEAC_POOLCAP"); P->kn.ldsq.read("HVO_PEAC_LDSQ");
-    P->kn.flood_t.read("HVO_FLOOD_T"); P->kn.flood_epl.read("HVO_FLOOD_EPL"); P->kn.flood_perm.read("HVO_FLOOD_PERM"); P->kn.flood_delay.read("HVO_FLOOD_DELAY"); P->kn.flood_slim.read("HVO_FLOOD_SLIM");
+    P->kn.read_env();
     P->w = w; P->h = h; P->pitch = (w + 31) & ~31; P->Nw = w / WIN; P->Nh = h / WIN; P->nblk = P->Nw * P->Nh;
     P->segcap = 2 * P->nblk + 2 * MAX_PLANES; P->poolcap = 16 * P->nblk + 2 * MAX_PLANES * MAX_PLANES; P->qcap = 2 * w * h + 65536; P->batch = batch;
 #define HVO_DEG2RAD(d) ((d) * 3.14159265358979323846 / 180.0)      /* MACRO_DEG2RAD, AHCParamSet.hpp:33: (d)*M_PI/180.0, in that order */
@@ -2134,6 +2172,103 @@ int peac_upload(hvo_ctx *ctx, int n, const hvo_frame_in *in, int w, int h, bool 
     return HVO_OK;
 }
 
+// Which kernels n frames of geometry g take under the knobs kn.  Plain host arithmetic, no HIP call: peac_run launches from the result,
+// hvo_debug_plan_select evaluates it without a device (tests/test_launch_plan.py holds the thresholds as data)
+static PeacSel peac_select(int n, const PeacGeom &g, const PeacKnobs &kn, bool frame_perm_on)
+{
+    PeacSel s;
+    s.n = n;
+    // HVO_PEAC_EDGES=0: the passes stay inside the clustering kernels (A/B runs, tests)
+    s.edges_done = ((size_t)g.nblk * 34 + 16 <= 150 * 1024 && !kn.edges.off()) ? 1 : 0;
+    // 4 frames per wave pay off once the wave slots are saturated (measured: >= ~3000 resident frames);
+    // HVO_PEAC_GL forces a group width (tests run the 16-lane path on small batches with it)
+    const int gl = kn.gl.or_(-1);
+    const int use = gl > 0 ? gl : (n >= 3072 ? 16 : 64);
+    s.group = use;
+    // the waves that share a SIMD are a fixed stride apart: their frames are decorrelated (hvo_frame_perm over the waves; the
+    // frames of one wave stay consecutive, lockstep likes them alike); HVO_PEAC_PERM=0 for A/B runs
+    const int per_wave = std::max(64 / std::max(use, 1), 1), waves = (n + per_wave - 1) / per_wave;
+    s.perm_items = (waves >= 2 && frame_perm_on && !kn.perm.off()) ? waves : 0;
+    // the slot form packs a label into a signed 16-bit half (peac_slots.inc); labels run up to segcap - 1 (nblk <= 16320: 1280x960 has
+    // 12 288 blocks).  Larger frames take ah_cluster_lend, as HVO_PEAC_SLOTS=0 does
+    const bool slots_fit = g.segcap <= 32768;
+    s.slots_fit = slots_fit;
+    // a handful of frames (the latency case): several queue heads per round, one wave each (peac_heads.inc); HVO_PEAC_HEADS = 0 / 2 / 3 / 4
+    const int heads_max = kn.heads_maxn.or_(256);
+    // three heads + the queue wave = one wave per SIMD of the frame's CU: 256 frames fill the chip exactly, and a lone frame loses nothing
+    // against four (a round costs 7.3 instead of 8.0 us for 2.12 instead of 2.34 pops; batch256 9.6 against 9.0 k frames/s)
+    // frames whose per-id keys and list headers do not fit LDS (1280x960: 24 704 node ids) take the BIG form: bucket minima, front and
+    // conflict bitmaps in LDS, keys in global memory, headers in the node records
+    const bool heads_fit = g.tq_n0 * 16 <= 64 * MH_MAXE, heads_big = !heads_fit && g.tq_n0 * 16 <= 64 * MH_MAXE_BIG;
+    int heads = (gl <= 0 && n <= heads_max && (heads_fit || heads_big)) ? 3 : 0;
+    if (kn.heads.set && (heads_fit || heads_big)) heads = kn.heads.v;
+    // The LDS form takes 108 KB: one workgroup per CU.  From ~130 frames on the workgroups need (nearly) every CU AT ONCE, and whichever
+    // streaming kernel holds more than 52 KB of a CU's LDS at that moment (the ORB tiles, the LSD preamble, the flood) sends one of them
+    // into a second turn: batch256 took 27.5 or 33 ms from step to step (profiles/r04_batch256_modes.txt).  The BIG form (32 KB) shares
+    // a CU: 10 % slower for a lone frame, no second mode at 256 frames.
+    bool big = heads_big || n > 128;
+    if (kn.heads_big.set && heads_fit) big = kn.heads_big.v != 0;      // tests: the BIG form on a frame that would fit
+    const bool force_pool = kn.poolcap.set && kn.poolcap.v >= 7 * g.nblk && kn.poolcap.v < g.poolcap;   // tests: force the pool's compaction
+    if (heads >= 2 && heads <= 4) {
+        s.cluster = PEAC_CL_HEADS; s.heads = heads; s.heads_big = big ? 1 : 0; s.cluster_wgs = n;
+        if (force_pool) s.poolcap = kn.poolcap.v;
+    }
+    else if (use == 64) {
+        s.cluster = PEAC_CL_64; s.cluster_wgs = n;
+        bool ldsq = n <= 256;                                  // at most one such frame per CU
+        if (kn.ldsq.set) ldsq = kn.ldsq.v != 0;
+        const size_t lq = (size_t)g.tq_n0 * 12, full = ((lq + 15) & ~(size_t)15) + (size_t)g.tq_n0 * (256 * 8 + 16 * 12);
+        s.ldsq = (ldsq && full <= 150 * 1024) ? 1 : 0;
+    }
+    else if (use == 32) { s.cluster = PEAC_CL_32; s.cluster_wgs = (n + 1) / 2; }
+    else {
+        if (use == 16 && force_pool) s.poolcap = kn.poolcap.v;      // tests: force the pool's compaction in the four-frames-per-wave kernels
+        s.cluster = (!kn.slots.off() && !kn.lend.off() && slots_fit && g.have_lq) ? PEAC_CL_SLOTS : kn.lend.off() ? PEAC_CL_16 : PEAC_CL_16_LEND;
+        s.cluster_wgs = (n + 3) / 4;
+    }
+    s.blkmap_y = n <= 64 ? 32 : n <= 1024 ? 4 : 1;
+    // threads per frame (one queue entry = 4 events per thread and round); HVO_FLOOD_T overrides
+    const int flood_t = kn.flood_t.or_(-1);
+    // measured: 256 threads per frame up to ~4096 resident frames, one wave per frame (less LDS, all frames in flight) beyond
+    // a lone frame (the latency case) takes 512: the flood's rounds are serial, so its time goes with the events a round retires
+    const int ft = flood_t > 0 ? flood_t : (n >= 6144 ? 64 : n <= 8 ? 512 : 256);
+    const int fe = kn.flood_epl.or_(1);             // HVO_FLOOD_EPL: queue entries per thread and round (one-wave variant only)
+    s.flood_t = (ft == 64 || ft == 512 || ft == 256) ? ft : 128;
+    s.flood_epl = (ft == 64 && fe == 2) ? 2 : 1;
+    s.flood_slim = (ft == 64 && fe != 2 && !kn.flood_slim.off()) ? 1 : 0;
+    s.flood_perm_items = (n >= 2 && frame_perm_on && !kn.flood_perm.off()) ? n : 0;
+    return s;
+}
+static PeacGeom peac_geom_of(const PeacPlan *P)
+{
+    PeacGeom g; g.nblk = P->nblk; g.segcap = P->segcap; g.poolcap = P->poolcap; g.tq_n0 = (P->segcap + 255) / 256; g.have_lq = P->d_lq != nullptr;
+    return g;
+}
+static void peac_sel_ints(const PeacSel &s, int *o)
+{
+    const int v[PEAC_REPORT_INTS] = { s.cluster, s.heads, s.heads_big, s.ldsq, s.edges_done, s.poolcap, s.group, s.cluster_wgs, s.perm_items, s.blkmap_y,
+                                      s.flood_t, s.flood_epl, s.flood_slim, s.flood_perm_items, s.n, s.slots_fit };
+    memcpy(o, v, sizeof v);
+}
+// diagnostics: the selection for n frames of w x h under the environment as it stands, without a plan or a device
+int peac_plan_select_env(int w, int h, int n, int *out)
+{
+    if (w < 2 * WIN || h < 2 * WIN || w > 4096 || h > 4096 || n < 1) return HVO_ERR_UNSUPPORTED;
+    PeacKnobs kn; kn.read_env();
+    Knob fp; fp.read("HVO_FRAME_PERM");
+    PeacGeom g; g.set(w, h);
+    peac_sel_ints(peac_select(n, g, kn, !fp.off()), out);
+    return HVO_OK;
+}
+// ... and what the last peac_run of this context launched (HVO_ERR_INVALID_ARG: none yet)
+int peac_last_report(hvo_ctx *ctx, int *out)
+{
+    PeacPlan *P = plan_of(ctx);
+    if (!P || !P->ran) return HVO_ERR_INVALID_ARG;
+    peac_sel_ints(P->last, out);
+    return HVO_OK;
+}
+
 int peac_run(hvo_ctx *ctx, int n)
 {
     PeacPlan *P = plan_of(ctx);
@@ -2155,49 +2290,24 @@ int peac_run(hvo_ctx *ctx, int n)
         if (ctx->fast_recorded) HVO_HIP(hipStreamWaitEvent(st, ctx->ev_fast, 0));
         if (ctx->lsd_pre_recorded) HVO_HIP(hipStreamWaitEvent(st, ctx->ev_lsd_pre, 0));
     }
+    const PeacSel sel = peac_select(n, peac_geom_of(P), P->kn, !ctx->kn_frame_perm.off());
+    P->last = sel; P->ran = true;
     id = hvo_prof_begin(ctx, "peac_cluster", st);
-    a.edges_done = 0;
-    {
+    a.edges_done = sel.edges_done;
+    if (sel.edges_done) {
         const size_t elds = (size_t)P->nblk * 34 + 16;
-        // HVO_PEAC_EDGES=0: the passes stay inside the clustering kernels (A/B runs, tests)
-        if (elds <= 150 * 1024 && !P->kn.edges.off()) {
-            if (hvo_ensure_dyn_lds(reinterpret_cast<const void *>(k_peac_edges), elds)) return HVO_ERR_HIP;
-            hipLaunchKernelGGL(k_peac_edges, dim3(n), dim3(512), elds, st, a, n);
-            a.edges_done = 1;
-        }
+        if (hvo_ensure_dyn_lds(reinterpret_cast<const void *>(k_peac_edges), elds)) return HVO_ERR_HIP;
+        hipLaunchKernelGGL(k_peac_edges, dim3(n), dim3(512), elds, st, a, n);
     }
     {
-        // 4 frames per wave pay off once the wave slots are saturated (measured: >= ~3000 resident frames);
-        // HVO_PEAC_GL forces a group width (tests run the 16-lane path on small batches with it)
-        const int gl = P->kn.gl.or_(-1);
-        const int use = gl > 0 ? gl : (n >= 3072 ? 16 : 64);
         const size_t lq = (size_t)a.tq_n0 * 12;                  // LDS per group: the queue's top level
-        // the waves that share a SIMD are a fixed stride apart: their frames are decorrelated (hvo_frame_perm over the waves; the
-        // frames of one wave stay consecutive, lockstep likes them alike); HVO_PEAC_PERM=0 for A/B runs
-        a.perm = hvo_frame_perm(ctx, (n + (64 / use) - 1) / (64 / use));
-        if (P->kn.perm.off()) a.perm = nullptr;
+        a.perm = sel.perm_items ? hvo_frame_perm(ctx, sel.perm_items) : nullptr;
         a.tq_lds_keys = 0;
-        // the slot form packs a label into a signed 16-bit half (peac_slots.inc); labels run up to segcap - 1 (nblk <= 16320: 1280x960 has
-        // 12 288 blocks).  Larger frames take ah_cluster_lend, as HVO_PEAC_SLOTS=0 does
-        const bool slots_fit = a.segcap <= 32768;
-        // a handful of frames (the latency case): several queue heads per round, one wave each (peac_heads.inc); HVO_PEAC_HEADS = 0 / 2 / 3 / 4
-        const int heads_max = P->kn.heads_maxn.or_(256);
-        // three heads + the queue wave = one wave per SIMD of the frame's CU: 256 frames fill the chip exactly, and a lone frame loses nothing
-        // against four (a round costs 7.3 instead of 8.0 us for 2.12 instead of 2.34 pops; batch256 9.6 against 9.0 k frames/s)
-        // frames whose per-id keys and list headers do not fit LDS (1280x960: 24 704 node ids) take the BIG form: bucket minima, front and
-        // conflict bitmaps in LDS, keys in global memory, headers in the node records
-        const bool heads_fit = a.tq_n0 * 16 <= 64 * MH_MAXE, heads_big = !heads_fit && a.tq_n0 * 16 <= 64 * MH_MAXE_BIG;
-        int heads = (gl <= 0 && n <= heads_max && (heads_fit || heads_big)) ? 3 : 0;
-        if (P->kn.heads.set && (heads_fit || heads_big)) heads = P->kn.heads.v;
-        // The LDS form takes 108 KB: one workgroup per CU.  From ~130 frames on the workgroups need (nearly) every CU AT ONCE, and whichever
-        // streaming kernel holds more than 52 KB of a CU's LDS at that moment (the ORB tiles, the LSD preamble, the flood) sends one of them
-        // into a second turn: batch256 took 27.5 or 33 ms from step to step (profiles/r04_batch256_modes.txt).  The BIG form (32 KB) shares
-        // a CU: 10 % slower for a lone frame, no second mode at 256 frames.
-        bool big = heads_big || n > 128;
-        if (P->kn.heads_big.set && heads_fit) big = P->kn.heads_big.v != 0;      // tests: the BIG form on a frame that would fit
-        if (heads >= 2 && heads <= 4) {
-            ClArgs b = a;
-            if (P->kn.poolcap.set && P->kn.poolcap.v >= 7 * a.nblk && P->kn.poolcap.v < a.poolcap) b.poolcap = P->kn.poolcap.v;   // tests: force the pool's compaction
+        ClArgs b = a;
+        if (sel.poolcap) b.poolcap = sel.poolcap;                // tests: force the pool's compaction
+        const dim3 grid(sel.cluster_wgs);
+        if (sel.cluster == PEAC_CL_HEADS) {
+            const int heads = sel.heads; const bool big = sel.heads_big != 0;
             const size_t segpad = (size_t)a.tq_n0 * 256;
             const size_t lds = (big ? 0 : segpad * 8) + (size_t)a.tq_n0 * 16 * 12 + segpad / 8 * 4 + 4 * sizeof(MhHead) + 32 + (big ? 0 : segpad * 8) + 512;
             {
@@ -2206,40 +2316,31 @@ int peac_run(hvo_ctx *ctx, int n)
                 if (hvo_ensure_dyn_lds(kf, lds)) return HVO_ERR_HIP;
             }
             if (big) {
-                if (heads == 2) hipLaunchKernelGGL((k_peac_cluster_heads<2, true>), dim3(n), dim3(192), lds, st, b, n);
-                else if (heads == 3) hipLaunchKernelGGL((k_peac_cluster_heads<3, true>), dim3(n), dim3(256), lds, st, b, n);
-                else hipLaunchKernelGGL((k_peac_cluster_heads<4, true>), dim3(n), dim3(320), lds, st, b, n);
+                if (heads == 2) hipLaunchKernelGGL((k_peac_cluster_heads<2, true>), grid, dim3(192), lds, st, b, n);
+                else if (heads == 3) hipLaunchKernelGGL((k_peac_cluster_heads<3, true>), grid, dim3(256), lds, st, b, n);
+                else hipLaunchKernelGGL((k_peac_cluster_heads<4, true>), grid, dim3(320), lds, st, b, n);
             } else {
-                if (heads == 2) hipLaunchKernelGGL((k_peac_cluster_heads<2, false>), dim3(n), dim3(192), lds, st, b, n);
-                else if (heads == 3) hipLaunchKernelGGL((k_peac_cluster_heads<3, false>), dim3(n), dim3(256), lds, st, b, n);
-                else hipLaunchKernelGGL((k_peac_cluster_heads<4, false>), dim3(n), dim3(320), lds, st, b, n);
+                if (heads == 2) hipLaunchKernelGGL((k_peac_cluster_heads<2, false>), grid, dim3(192), lds, st, b, n);
+                else if (heads == 3) hipLaunchKernelGGL((k_peac_cluster_heads<3, false>), grid, dim3(256), lds, st, b, n);
+                else hipLaunchKernelGGL((k_peac_cluster_heads<4, false>), grid, dim3(320), lds, st, b, n);
             }
         }
-        else if (use == 64) {
+        else if (sel.cluster == PEAC_CL_64) {
             size_t lds = lq;
-            bool ldsq = n <= 256;                                  // at most one such frame per CU
-            if (P->kn.ldsq.set) ldsq = P->kn.ldsq.v != 0;
-            const size_t full = ((lq + 15) & ~(size_t)15) + (size_t)a.tq_n0 * (256 * 8 + 16 * 12);
-            if (ldsq && full <= 150 * 1024) {
-                a.tq_lds_keys = 1; lds = full;
+            if (sel.ldsq) {
+                a.tq_lds_keys = 1; lds = ((lq + 15) & ~(size_t)15) + (size_t)a.tq_n0 * (256 * 8 + 16 * 12);
                 if (hvo_ensure_dyn_lds(reinterpret_cast<const void *>(k_peac_cluster<64, false>), lds)) return HVO_ERR_HIP;
             }
-            hipLaunchKernelGGL((k_peac_cluster<64, false>), dim3(n), dim3(64), lds, st, a, n);
+            hipLaunchKernelGGL((k_peac_cluster<64, false>), grid, dim3(64), lds, st, a, n);
         }
-        else if (use == 32) hipLaunchKernelGGL((k_peac_cluster<32, false>), dim3((n + 1) / 2), dim3(64), 2 * lq, st, a, n);
-        else if (use == 16 && P->kn.poolcap.set && P->kn.poolcap.v >= 7 * a.nblk && P->kn.poolcap.v < a.poolcap) {   // tests: force the pool's compaction in the four-frames-per-wave kernels
-            ClArgs b = a; b.poolcap = P->kn.poolcap.v;
-            if (!P->kn.slots.off() && !P->kn.lend.off() && slots_fit && P->d_lq) hipLaunchKernelGGL(k_peac_cluster_slots, dim3((n + 3) / 4), dim3(64), 4 * lq, st, b, n);
-            else if (P->kn.lend.off()) hipLaunchKernelGGL((k_peac_cluster<16, false>), dim3((n + 3) / 4), dim3(64), 4 * lq, st, b, n);
-            else hipLaunchKernelGGL((k_peac_cluster<16, true>), dim3((n + 3) / 4), dim3(64), 4 * lq, st, b, n);
-        }
-        else if (!P->kn.slots.off() && !P->kn.lend.off() && slots_fit && P->d_lq) hipLaunchKernelGGL(k_peac_cluster_slots, dim3((n + 3) / 4), dim3(64), 4 * lq, st, a, n);   // HVO_PEAC_SLOTS=0: a new record per merge
-        else if (P->kn.lend.off()) hipLaunchKernelGGL((k_peac_cluster<16, false>), dim3((n + 3) / 4), dim3(64), 4 * lq, st, a, n);
-        else hipLaunchKernelGGL((k_peac_cluster<16, true>), dim3((n + 3) / 4), dim3(64), 4 * lq, st, a, n);   // HVO_PEAC_LEND=0: the lanes of a frame stay with it
+        else if (sel.cluster == PEAC_CL_32) hipLaunchKernelGGL((k_peac_cluster<32, false>), grid, dim3(64), 2 * lq, st, a, n);
+        else if (sel.cluster == PEAC_CL_SLOTS) hipLaunchKernelGGL(k_peac_cluster_slots, grid, dim3(64), 4 * lq, st, b, n);   // HVO_PEAC_SLOTS=0: a new record per merge
+        else if (sel.cluster == PEAC_CL_16) hipLaunchKernelGGL((k_peac_cluster<16, false>), grid, dim3(64), 4 * lq, st, b, n);
+        else hipLaunchKernelGGL((k_peac_cluster<16, true>), grid, dim3(64), 4 * lq, st, b, n);   // HVO_PEAC_LEND=0: the lanes of a frame stay with it
     }
     hvo_prof_end(ctx, id);
     id = hvo_prof_begin(ctx, "peac_refine", st);
-    hipLaunchKernelGGL(k_peac_blkmap, dim3(n, n <= 64 ? 32 : n <= 1024 ? 4 : 1), dim3(256), 0, st, P->d_parent, P->d_dsize, P->d_segI, P->d_extracted, P->d_meta, P->d_blkmap,
+    hipLaunchKernelGGL(k_peac_blkmap, dim3(n, sel.blkmap_y), dim3(256), 0, st, P->d_parent, P->d_dsize, P->d_segI, P->d_extracted, P->d_meta, P->d_blkmap,
                        P->d_isvalid, P->d_state, P->d_depth, dframe, P->pitch, P->nblk, P->Nw, P->Nh, P->w, P->h, P->segcap);
     RfArgs r;
     r.c = a; r.depth = P->d_depth; r.dframe = dframe; r.pitch = P->pitch; r.w = P->w; r.h = P->h;
@@ -2248,20 +2349,14 @@ int peac_run(hvo_ctx *ctx, int n)
     r.qcap = P->qcap; r.plidmap = P->d_plidmap; r.planes = P->d_planes; r.c30 = P->c30;
     r.flood_delay = std::min(std::max(P->kn.flood_delay.or_(0), 0), 64);     // HVO_FLOOD_DELAY: sleeps of 127 x 64 clocks per ranked round, at most 64
     {
-        // threads per frame (one queue entry = 4 events per thread and round); HVO_FLOOD_T overrides
-        const int flood_t = P->kn.flood_t.or_(-1);
-        // measured: 256 threads per frame up to ~4096 resident frames, one wave per frame (less LDS, all frames in flight) beyond
-        // a lone frame (the latency case) takes 512: the flood's rounds are serial, so its time goes with the events a round retires
-        const int ft = flood_t > 0 ? flood_t : (n >= 6144 ? 64 : n <= 8 ? 512 : 256);
-        const int fe = P->kn.flood_epl.or_(1);             // HVO_FLOOD_EPL: queue entries per thread and round (one-wave variant only)
-        r.perm = hvo_frame_perm(ctx, n);                   // one wave per frame for its whole life: frames of a SIMD decorrelated
+        const int ft = sel.flood_t, fe = sel.flood_epl;
+        r.perm = sel.flood_perm_items ? hvo_frame_perm(ctx, sel.flood_perm_items) : nullptr;      // one wave per frame for its whole life: frames of a SIMD decorrelated
         if ((ctx->sched == 5 || ctx->sched == 7) && ctx->fast_recorded && !ctx->serialize) HVO_HIP(hipStreamWaitEvent(st, ctx->ev_fast, 0));      // experiment: the flood takes all LDS, k_fast_cells needs some
-        if (P->kn.flood_perm.off()) r.perm = nullptr;
         // the one-wave form in two launches on the stream: frames with at most 16 coarse planes (nearly all) take the slim plane table and
         // fit five waves per SIMD, the rest the MAX_PLANES form; a frame that is not a launch's own costs an empty workgroup.
         // HVO_FLOOD_SLIM=0: the MAX_PLANES form takes every frame
         r.flood_lo = -1;
-        if (ft == 64 && fe != 2 && !P->kn.flood_slim.off()) {
+        if (sel.flood_slim) {
             hipLaunchKernelGGL((k_peac_flood<64, 1, 16>), dim3(n), dim3(64), 0, st, r, P->d_adj);
             r.flood_lo = 16;
         }
@@ -2323,6 +2418,7 @@ extern "C" int hvo_compute_planes(hvo_ctx *ctx, const uint16_t *depth, int w, in
     int rc = peac_upload(ctx, 1, &in, w, h);
     if (rc) return rc;
     ctx->last_stages = 0;                                  // slot 0 of the resident batch has been overwritten
+    ctx->last_batch_valid = false;
     for (int i = 0; i < ctx->nprof; i++) ctx->prof[i].used = false;
     if ((rc = peac_run(ctx, 1))) return rc;
     hvo_frame_out out; memset(&out, 0, sizeof(out));

@@ -73,6 +73,7 @@ def keylines(hvo, w, h):
 def describe(hvo, setting, g, kl):
     """a new context per setting: the plan reads the switch once, when it is built"""
     with lbd_desc_setting(setting):
+        assert hvo.plan_select(g.shape[1], g.shape[0], 1)["lsd"]["lbd_desc"] == (0 if setting == "0" else 1)      # the switch selects the other form
         ctx = hvo.Context(max_batch=1, orb_nlevels=1)
         try:
             first = ctx.lbd_desc(g, kl)
@@ -135,6 +136,8 @@ def run_detector(hvo, setting, g):
             for stages in (hvo.STAGE_LSD, hvo.STAGE_LSD | hvo.STAGE_LSD_CULL):
                 ctx.batch_run(stages)
                 res = ctx.batch_download(stages)
+                rep = ctx.launch_report()["lsd"]
+                assert (rep["lbd_desc"], rep["cull"]) == (0 if setting == "0" else 1, int(stages != hvo.STAGE_LSD)), rep
                 assert all(r["status"] == 0 for r in res)
                 out.append([(r["kl"].copy(), r["ldesc"].copy()) for r in res])
         finally:

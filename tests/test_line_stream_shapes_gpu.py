@@ -10,6 +10,8 @@ Geometries (w, h) -> scaled (sw, sh) = (round(0.8 w), round(0.8 h)).  The contex
 below ~137 pixels, one level accepts 64.  The issue's rows-per-block cases h = R - 1, R, R + 1 are below that limit too, so the same
 three positions are taken one and two blocks further down (h = 2R, 2R + 1, 3R - 1, 3R, 3R + 1), and 64 x 64 is the smallest image the
 chain accepts.  A segment starts at a multiple of 96 scaled rows, which is a multiple of the chunk: no segment starts in mid-period."""
+import os
+
 import numpy as np
 import pytest
 
@@ -73,6 +75,9 @@ def run(hvo, g, twice):
         for _ in range(2 if twice else 1):
             ctx.batch_run(hvo.STAGE_LSD)
             res = ctx.batch_download(hvo.STAGE_LSD)
+            rep = ctx.launch_report()["lsd"]
+            split = os.environ.get("HVO_LSD_PRE_SPLIT") == "1"                 # the forms the caller asked for are the ones that ran
+            assert (rep["pre"], rep["lbd_gradient"]) == (("split", "split") if split else ("fused", "fused")), rep
             out.append(([(r["status"], r["kl"].copy(), r["ldesc"].copy(), r["linefn"].copy()) for r in res], [ctx.lsd_images(b) for b in range(n)]))
     finally:
         ctx.close()

@@ -31,16 +31,19 @@ def test_lines_parity_640(gpu_ctx, orc, synth, kind, seed):
 @pytest.mark.parametrize("dense", ["0", "1"])
 def test_lines_both_grow_kernels(hvo, orc, synth, monkeypatch, dense):
     """k_lsd_grow (five waves per SIMD, small batches) and k_lsd_grow_dense (eight, batches that fill the wave slots) are the
-    same body under two register budgets; HVO_LSD_DENSE forces either on a small batch"""
-    monkeypatch.setenv("HVO_LSD_DENSE", dense)
+    same body under two register budgets; HVO_LSD_DENSE forces either on a small batch -- once the async and the latency forms, which
+    three frames take before either, are switched off (the launch report says which kernel grew the lines)"""
+    monkeypatch.setenv("HVO_LSD_DENSE", dense); monkeypatch.setenv("HVO_LSD_ASYNC", "0"); monkeypatch.setenv("HVO_LSD_LAT", "0")
     g = np.stack([synth.make_gray(k, s) for k, s in (("std", 0x5EED0002), ("lowtex", 0x5EED0001), ("std", 0x5EED1003))])
     ctx = hvo.Context(max_batch=3)
     try:
         ctx.batch_upload(g, np.zeros((3, 480, 640), np.uint16))
         ctx.batch_run(hvo.STAGE_LSD)
         res = ctx.batch_download(hvo.STAGE_LSD)
+        rep = ctx.launch_report()["lsd"]
     finally:
         ctx.close()
+    assert (rep["grow"], rep["async_w"], rep["async_fallback"], rep["n"]) == ("dense" if dense == "1" else "grow", 0, 0, 3), rep
     for b in range(3):
         kl_o, d_o, fn_o = orc.line_extract(g[b])
         check(res[b]["kl"], res[b]["ldesc"], res[b]["linefn"], kl_o, d_o, fn_o)
@@ -64,6 +67,8 @@ def test_lines_compact_records(hvo, orc, synth, monkeypatch, dense, frac, chunk)
             for _ in range(2):                                    # the second run starts from the pool the first one left
                 ctx.batch_run(hvo.STAGE_LSD)
                 res = ctx.batch_download(hvo.STAGE_LSD)
+                rep = ctx.launch_report()["lsd"]
+                assert (rep["compact"], rep["grow"], rep["chunk"], rep["chunks"]) == (1, "dense_c" if dense == "1" else "grow_c", int(chunk or 5), 3 if chunk else 1), rep
                 for b in range(5):
                     kl_o, d_o, fn_o = orc.line_extract(g[b])
                     assert res[b]["status"] == 0
@@ -87,6 +92,8 @@ def test_lines_preamble_fused_and_split(hvo, orc, synth, monkeypatch, split, hh,
         for _ in range(2):
             ctx.batch_run(hvo.STAGE_LSD)
             res = ctx.batch_download(hvo.STAGE_LSD)
+            rep = ctx.launch_report()["lsd"]
+            assert (rep["pre"], rep["grow"], rep["async_fallback"]) == ("split" if split == "1" else "fused", "async", 1), rep
             for b in range(2):
                 kl_o, d_o, fn_o = orc.line_extract(g[b])
                 assert res[b]["status"] == 0 and len(kl_o) > 10
@@ -108,6 +115,7 @@ def test_lines_lbd_split(hvo, orc, synth, monkeypatch, hh, ww):
         for _ in range(2):
             ctx.batch_run(hvo.STAGE_LSD)
             res = ctx.batch_download(hvo.STAGE_LSD)
+            assert ctx.launch_report()["lsd"]["lbd_gradient"] == "split"
             for b in range(3):
                 assert res[b]["status"] == 0
                 check(res[b]["kl"], res[b]["ldesc"], res[b]["linefn"], *ref[b])
@@ -269,6 +277,8 @@ def test_lines_async_growing(hvo, orc, synth, monkeypatch, workers, early):
             for _ in range(2):                                    # the second run starts from the tags and lists the first one left
                 ctx.batch_run(hvo.STAGE_LSD)
                 res = ctx.batch_download(hvo.STAGE_LSD)
+                rep = ctx.launch_report()["lsd"]
+                assert (rep["grow"], rep["async_w"], rep["async_early"], rep["async_fallback"]) == ("async", int(workers), int(early), 1), rep
                 for b in range(5):
                     kl_o, d_o, fn_o = orc.line_extract(g[b])
                     assert res[b]["status"] == 0
@@ -293,8 +303,10 @@ def test_lines_async_1280(hvo, orc, synth, monkeypatch):
     ctx = hvo.Context()
     try:
         kl_g, d_g, fn_g = ctx.extract_lsd(g)
+        rep = ctx.launch_report()
     finally:
         ctx.close()
+    assert rep["batch"] is None and (rep["lsd"]["grow"], rep["lsd"]["async_w"], rep["lsd"]["n"]) == ("async", 32, 1), rep       # (64 workers without the variable)
     check(kl_g, d_g, fn_g, kl_o, d_o, fn_o)
 
 
@@ -369,6 +381,8 @@ def test_lines_async_gives_up_and_the_frame_is_grown_again(hvo, orc, synth, monk
             res = ctx.batch_download(hvo.STAGE_LSD)
             regrown, foreign, wpf = ctx.lsd_async_report()
             assert wpf == int(workers) and foreign == 0 and 0 <= regrown <= n
+            rep = ctx.launch_report()["lsd"]
+            assert (rep["grow"], rep["async_w"], rep["async_fallback"], rep["pre"]) == ("async", int(workers), 1, "fused"), rep      # the fall-back was enqueued
             regrown_total += regrown
             for b in range(n):
                 assert res[b]["status"] == 0
@@ -400,6 +414,8 @@ def test_lines_async_growing_on_a_mid_size_batch(hvo, orc, synth, monkeypatch):
             ctx.batch_run(hvo.STAGE_LSD)
             res = ctx.batch_download(hvo.STAGE_LSD)
             assert ctx.lsd_async_report()[2] == 3
+            rep = ctx.launch_report()["lsd"]
+            assert (rep["grow"], rep["async_w"], rep["n"], rep["plan_batch"]) == ("async", 3, n, 40), rep
             for b in range(n):
                 assert res[b]["status"] == 0
                 check(res[b]["kl"], res[b]["ldesc"], res[b]["linefn"], *ref[b])

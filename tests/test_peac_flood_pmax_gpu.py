@@ -29,9 +29,10 @@ def run_batch(hvo, depth):
         ctx.batch_run(hvo.STAGE_PLANES)
         res = ctx.batch_download(hvo.STAGE_PLANES)
         stats = [ctx.peac_stats(f) for f in range(len(depth))]
+        rep = ctx.launch_report()["peac"]
     finally:
         ctx.close()
-    return res, stats
+    return res, stats, rep
 
 
 def test_flood_slim_and_full_forms_in_one_batch(hvo, orc, synth, monkeypatch):
@@ -39,9 +40,11 @@ def test_flood_slim_and_full_forms_in_one_batch(hvo, orc, synth, monkeypatch):
     kinds = [("synth", 0x5EED0002), ("grid", 5), ("grid", 16), ("synth", 0x5EED1000), ("grid", 17), ("grid", 49), ("grid", 16), ("synth", 77)]
     depth = np.stack([synth.make_depth(s) if k == "synth" else grid_depth(s, 7 + f) for f, (k, s) in enumerate(kinds)])
     monkeypatch.delenv("HVO_FLOOD_SLIM", raising=False)
-    res, stats = run_batch(hvo, depth)
+    res, stats, rep = run_batch(hvo, depth)
     monkeypatch.setenv("HVO_FLOOD_SLIM", "0")
-    res_full, stats_full = run_batch(hvo, depth)
+    res_full, stats_full, rep_full = run_batch(hvo, depth)
+    # the slim first launch ran in the first batch and not in the second; both took the one-wave flood
+    assert (rep["flood_t"], rep["flood_epl"], rep["flood_slim"]) == (64, 1, 1) and (rep_full["flood_t"], rep_full["flood_epl"], rep_full["flood_slim"]) == (64, 1, 0), (rep, rep_full)
     for f, (k, s) in enumerate(kinds):
         lo, po = orc.peac(depth[f])
         r = res[f]

@@ -92,6 +92,8 @@ def test_peac_three_plane_corner_flood_variants(hvo, orc, monkeypatch, flood_t, 
             lo, po = orc.peac(d)
             lg, pg = ctx.compute_planes(d)
             check(lg, pg, lo, po)
+            rep = ctx.launch_report()["peac"]
+            assert (rep["flood_t"], rep["flood_epl"], rep["flood_slim"]) == (flood_t, epl, int(flood_t == 64 and epl == 1)), rep
             st = ctx.peac_stats(0)
             ranked += st["flood_ranked_rounds"]; serial += st["flood_serial_rounds"]
         assert ranked > 0 and serial > 0, (ranked, serial)
@@ -135,6 +137,8 @@ def test_peac_random_polyhedra(hvo, orc, monkeypatch, flood_t):
         ctx.batch_upload(gray, depth)
         ctx.batch_run(hvo.STAGE_PLANES)
         res = ctx.batch_download(hvo.STAGE_PLANES)
+        rep = ctx.launch_report()["peac"]
+        assert (rep["flood_t"], rep["flood_slim"], rep["n"]) == (flood_t, int(flood_t == 64), len(seeds)), rep
         nplanes = 0
         for f, s in enumerate(seeds):
             lo, po = orc.peac(depth[f])
@@ -227,12 +231,18 @@ def test_peac_four_frames_per_wave_variants(hvo, orc, synth, monkeypatch, slots,
         ctx.batch_run(hvo.STAGE_PLANES)
         res = ctx.batch_download(hvo.STAGE_PLANES)
         stats = ctx.peac_stats(1)
+        rep = ctx.launch_report()["peac"]
     finally:
         ctx.close()
+    # the form that was asked for is the one that ran
+    form = "slots" if (slots, lend) == ("1", "1") else "c16_lend" if lend == "1" else "c16"
+    assert (rep["cluster"], rep["group"], rep["cluster_wgs"], rep["poolcap"], rep["edges_done"]) == (form, 16, 3, int(poolcap or 0), 0 if edges == "0" else 1), rep
     for b in range(len(depth)):
         lo, po = orc.peac(depth[b])
         assert res[b]["status"] == 0
         check(res[b]["labels"], res[b]["planes"], lo, po)
+    # frame 1's bookkeeping: 3072 blocks became segments and were merged, nothing overflowed, the planes are the oracle's
+    assert stats["flags"] == 0 and stats["segments"] > 3072 and stats["planes"] == len(orc.peac(depth[1])[1]), stats
 
 
 @pytest.mark.parametrize("gl,flood_t", [(16, 64), (16, 128), (32, 128), (64, 256)])
@@ -251,8 +261,11 @@ def test_peac_batch_grouped_paths(hvo, orc, synth, monkeypatch, gl, flood_t):
         ctx.batch_upload(gray, depth)
         ctx.batch_run(hvo.STAGE_PLANES)
         res = ctx.batch_download(hvo.STAGE_PLANES)
+        rep = ctx.launch_report()["peac"]
     finally:
         ctx.close()
+    assert (rep["cluster"], rep["group"], rep["flood_t"]) == ({16: "slots", 32: "c32", 64: "c64"}[gl], gl, flood_t), rep
+    assert rep["cluster_wgs"] == (6 * gl + 63) // 64 and rep["flood_slim"] == int(flood_t == 64), rep
     for b in range(6):
         lo, po = orc.peac(depth[b])
         assert res[b]["status"] == 0
@@ -267,11 +280,14 @@ def test_peac_large_batch_adaptive(hvo, orc, synth):
     try:
         ctx.batch_upload(gray, depth, repeat=192)
         ctx.batch_run(hvo.STAGE_PLANES)
-        res = ctx.batch_download(hvo.STAGE_PLANES, n=40)
+        res = ctx.batch_download(hvo.STAGE_PLANES, labels8=True)
+        rep = ctx.launch_report()["peac"]
     finally:
         ctx.close()
+    assert (rep["cluster"], rep["group"], rep["cluster_wgs"], rep["perm_items"], rep["flood_t"], rep["blkmap_y"]) == ("slots", 16, 768, 768, 256, 1), rep
     ref = [orc.peac(depth[b]) for b in range(16)]
-    for b in range(40):
+    # the first 40 frames, the last 40, and the frames on both sides of index 3071 - 16
+    for b in list(range(40)) + list(range(3055 - 8, 3055 + 8)) + list(range(3072 - 40, 3072)):
         lo, po = ref[b % 16]
         assert res[b]["status"] == 0
         check(res[b]["labels"], res[b]["planes"], lo, po)
@@ -299,9 +315,14 @@ def test_peac_queue_heads(hvo, orc, synth, monkeypatch, heads, poolcap, big):
         ctx.batch_run(hvo.STAGE_PLANES)
         res = ctx.batch_download(hvo.STAGE_PLANES)
         stats = ctx.peac_stats(1)
+        rep = ctx.launch_report()["peac"]
         one = ctx.compute_planes(depth[1])                       # the single-frame entry point takes the same kernel
+        rep_one = ctx.launch_report()["peac"]
     finally:
         ctx.close()
+    want = dict(cluster="heads", heads=int(heads), heads_big=int(big or 0), poolcap=int(poolcap or 0)) if heads != "0" else dict(cluster="c64", heads=0, ldsq=1)
+    for r, nfr in ((rep, len(depth)), (rep_one, 1)):
+        assert {k: r[k] for k in want} == want and r["n"] == nfr, r
     for b in range(len(depth)):
         lo, po = orc.peac(depth[b])
         assert res[b]["status"] == 0
@@ -328,8 +349,10 @@ def test_peac_one_frame_per_wave_queue_keys(hvo, orc, synth, monkeypatch, ldsq):
         ctx.batch_upload(np.zeros((len(depth), 480, 640), np.uint8), depth)
         ctx.batch_run(hvo.STAGE_PLANES)
         res = ctx.batch_download(hvo.STAGE_PLANES)
+        rep = ctx.launch_report()["peac"]
     finally:
         ctx.close()
+    assert (rep["cluster"], rep["heads"], rep["ldsq"], rep["cluster_wgs"]) == ("c64", 0, int(ldsq), 6), rep
     for b in range(len(depth)):
         lo, po = orc.peac(depth[b])
         assert res[b]["status"] == 0
@@ -348,8 +371,10 @@ def test_peac_four_frames_per_wave_1280(hvo, orc, synth, monkeypatch):
         ctx.batch_upload(np.zeros((len(d), h, w), np.uint8), d)
         ctx.batch_run(hvo.STAGE_PLANES)
         res = ctx.batch_download(hvo.STAGE_PLANES)
+        rep = ctx.launch_report()["peac"]
     finally:
         ctx.close()
+    assert (rep["cluster"], rep["edges_done"], rep["slots_fit"], rep["cluster_wgs"]) == ("slots", 0, 1, 2), rep
     for b in range(len(d)):
         lo, po = orc.peac(d[b])
         assert res[b]["status"] == 0

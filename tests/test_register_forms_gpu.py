@@ -153,7 +153,7 @@ def ahc_three_ways(hvo, orc, monkeypatch, depth, poolcap=None, K=None):
     if poolcap: monkeypatch.setenv("HVO_PEAC_POOLCAP", str(poolcap))
     n, h, w = depth.shape
     kw = dict(fx=K["fx"], fy=K["fy"], cx=K["cx"], cy=K["cy"]) if K else {}
-    res = {}
+    res, rep = {}, {}
     for slots in ("1", "0"):
         monkeypatch.setenv("HVO_PEAC_SLOTS", slots)
         ctx = hvo.Context(max_batch=n, **kw)
@@ -161,8 +161,13 @@ def ahc_three_ways(hvo, orc, monkeypatch, depth, poolcap=None, K=None):
             ctx.batch_upload(np.zeros((n, h, w), np.uint8), depth)
             ctx.batch_run(hvo.STAGE_PLANES)
             res[slots] = ctx.batch_download(hvo.STAGE_PLANES)
+            rep[slots] = ctx.launch_report()["peac"]
         finally:
             ctx.close()
+    # two different kernels were compared: the slot form and the lending form, each with the pool that was asked for
+    assert rep["1"]["cluster"] == "slots" and rep["0"]["cluster"] == "c16_lend", (rep["1"], rep["0"])
+    for r in rep.values():
+        assert (r["group"], r["cluster_wgs"], r["poolcap"], r["n"]) == (16, (n + 3) // 4, int(poolcap or 0), n), r
     okw = {k: np.float32(v) for k, v in kw.items()}
     counts = []
     for b in range(n):
