@@ -76,7 +76,10 @@ __global__ __launch_bounds__(256) void k_vp_pairs(const double *__restrict__ par
 // formulation had the owner of every one of the 32 400 cells scan all 19 900 pairs: 1.1 ms.)
 #define VP_CPT 32                                    // cells per thread: 1024 x 32 >= 32 400
 #define VP_BIG 48                                    // a cell with more pairs than this is ordered by the whole workgroup
-#define VP_BIGMAX 2048                               // such cells a frame can have (523 776 pairs / 48 would be 10 912: the rest keep the owner's sort)
+// such cells the table holds.  n lines make n (n - 1) / 2 pairs, so up to that / 49 cells can be this full: 10 689 at the host form's 1024
+// lines (523 776 pairs), and more in the resident forms, whose n is the context's lsd_nfeatures and has no such cap (1280 lines: 818 560
+// pairs).  A cell that finds the table full keeps the owner's sort; which cells those are depends on arrival order, the sums do not.
+#define VP_BIGMAX 2048
 __global__ __launch_bounds__(1024) void k_vp_grid(const int *__restrict__ cell, const double *__restrict__ val, const int *__restrict__ n_ptr, int n_fixed, double *__restrict__ raw,
                                                   int *__restrict__ order, int *__restrict__ order2)
 {

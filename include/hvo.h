@@ -231,7 +231,9 @@ int hvo_search_lines_by_projection_map(hvo_ctx *ctx, int nq, const float *q_xyxy
  * cluster of every line, thAngle = 1 degree in Frame.h:365).  kl are the (undistorted) key lines (mvKeylinesUn), intrinsics
  * the context's.  The reference draws from a time-seeded rand(); the caller passes a seed, group i of 360 hypotheses draws its
  * pair of lines from its own xorshift32 stream (seed, i).  vp_idx[i] = 0..2 (isStructLine[i] = true) or 3 (none);
- * grid (optional) receives the 90 x 360 smoothed sphere grid.  n < 2: nothing is computed (as the reference), all vp_idx = 3. */
+ * grid (optional) receives the 90 x 360 smoothed sphere grid.  n < 2: nothing is computed (as the reference), all vp_idx = 3.
+ * This host-array form accepts 0 <= n <= 1024 lines; more is HVO_ERR_INVALID_ARG and nothing is launched.  The resident forms
+ * (HVO_STAGE_VP below) are sized by the context's lsd_nfeatures instead and take every key line of the frame. */
 typedef struct {
     double vps[3][3];           /* tmp_vps: the best hypothesis, three unit vectors (camera frame) */
     double score;               /* its summed grid length (0 when no hypothesis scored) */
@@ -325,6 +327,8 @@ int hvo_stereo_from_rgbd(hvo_ctx *ctx, const hvo_keypoint *kp, const hvo_keypoin
  * label image, planes and key points where the stages above left them in HBM (nothing is uploaded twice, nothing allocated per frame). */
 #define HVO_STAGE_LINES3D    16u  /* Frame::isLineGood of every key line (src/Frame.cc:934-939, 1205-1322) = hvo_lines_3d; needs LSD + depth */
 #define HVO_STAGE_VP         32u  /* vanishing points + line2Vps (src/Frame.cc:328-337, 442-778) = hvo_vanishing_points; needs LSD */
+/* HVO_STAGE_VP runs on all of a frame's key lines, up to lsd_nfeatures: the 1024-line limit of hvo_vanishing_points does not apply (its
+ * scratch is 20 bytes per PAIR of lsd_nfeatures lines and frame slot: 16 MB at 1280).  It returns no sphere grid. */
 #define HVO_STAGE_PLANE_TAIL 64u  /* ComputePlanes' tail (src/Frame.cc:2110-2274) = hvo_plane_clouds + hvo_surface_normals; needs PLANES */
 #define HVO_STAGE_GRIDS     128u  /* AssignFeaturesToGrid / ForLine (src/Frame.cc:832-872) = hvo_assign_*_to_grid; needs ORB + LSD */
 #define HVO_STAGE_FRAME     (HVO_STAGE_ORB | HVO_STAGE_LSD_CULL | HVO_STAGE_LSD | HVO_STAGE_PLANES | HVO_STAGE_LINES3D | HVO_STAGE_VP | HVO_STAGE_PLANE_TAIL | HVO_STAGE_GRIDS)
