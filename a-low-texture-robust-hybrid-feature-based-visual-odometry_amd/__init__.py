@@ -88,6 +88,9 @@ EXPORTS = [
     "hvo_vocabulary_create", "hvo_vocabulary_load_text", "hvo_vocabulary_destroy", "hvo_vocabulary_info",
     "hvo_compute_bow", "hvo_stream_compute_bow", "hvo_batch_compute_bow", "hvo_search_by_bow", "hvo_stream_search_by_bow",
     "hvo_bow_last_kernel_ms", "hvo_stream_bow_last_kernel_ms",
+    "hvo_keyframe_db_create", "hvo_keyframe_db_destroy", "hvo_keyframe_db_last_error", "hvo_keyframe_db_add", "hvo_stream_keyframe_db_add",
+    "hvo_keyframe_db_erase", "hvo_keyframe_db_clear", "hvo_keyframe_db_set_covisible", "hvo_keyframe_db_get", "hvo_keyframe_db_info",
+    "hvo_keyframe_db_query", "hvo_stream_keyframe_db_query", "hvo_batch_keyframe_db_query", "hvo_keyframe_db_last_kernel_ms",
     "hvo_pnp_default_params", "hvo_pnp_ransac", "hvo_stream_pnp_ransac", "hvo_pnp_last_kernel_ms", "hvo_stream_pnp_last_kernel_ms",
     "hvo_search_by_projection_keyframe", "hvo_stream_search_by_projection_keyframe",
     "hvo_update_map_planes", "hvo_stream_update_map_planes", "hvo_plane_map_get_points", "hvo_plane_update_transform",
@@ -435,6 +438,50 @@ class BowSearchParams(C.Structure):
 
 class BowMatches(C.Structure):
     _fields_ = [("match_kf", C.c_void_p), ("n_matches", C.c_int32), ("status", C.c_int32)]
+
+
+KFDB_MAX_SLOTS, KFDB_MAX_COVISIBLE = 16384, 10
+KFDB_RELOC, KFDB_LOOP = 0, 1
+
+
+class KeyframeDbDesc(C.Structure):
+    _fields_ = [("n_slots", C.c_int32), ("n_live", C.c_int32), ("scoring", C.c_int32), ("device", C.c_int32),
+                ("pooled_words", C.c_int64), ("pool_capacity", C.c_int64), ("next_sequence", C.c_int64)]
+
+
+class KfdbParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("min_score", C.c_float), ("connected", C.c_void_p), ("n_connected", C.c_int32)]
+
+
+class KfdbResult(C.Structure):
+    _fields_ = [("cap", C.c_int32), ("candidate", C.c_void_p), ("n_candidates", C.c_int32),
+                ("slot_cap", C.c_int32), ("words", C.c_void_p), ("score", C.c_void_p), ("acc", C.c_void_p), ("best", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("n_sharing", "max_common", "min_common", "n_scored")] + [("best_acc_score", C.c_float), ("status", C.c_int32)]
+
+
+def _kfdb_args(n_slots, mode, min_score, connected, views, cap=None):
+    """(hvo_kfdb_params, hvo_kfdb_result, the arrays behind them) for a database of n_slots slots"""
+    conn = np.ascontiguousarray([] if connected is None else connected, np.int32).reshape(-1)
+    P = KfdbParams(); P.mode = mode; P.min_score = float(min_score); P.connected = conn.ctypes.data if len(conn) else None; P.n_connected = len(conn)
+    cap = max(n_slots, 1) if cap is None else int(cap)
+    a = dict(candidate=np.zeros(max(cap, 1), np.int32), connected=conn)
+    R = KfdbResult(); R.cap = cap; R.candidate = a["candidate"].ctypes.data; R.slot_cap = n_slots if views else 0
+    if views:
+        a.update(words=np.zeros(max(n_slots, 1), np.int32), score=np.zeros(max(n_slots, 1), np.float32), acc=np.zeros(max(n_slots, 1), np.float32),
+                 best=np.zeros(max(n_slots, 1), np.int32))
+        for k in ("words", "score", "acc", "best"):
+            setattr(R, k, a[k].ctypes.data)
+    return P, R, a
+
+
+def _kfdb_finish(R, a, n_slots, views):
+    """dict(candidates (slots, the reference's order), n_sharing, max_common, min_common, n_scored, best_acc_score; with views: words, score, acc,
+    best per slot)"""
+    r = dict(candidates=a["candidate"][:R.n_candidates].copy(), best_acc_score=np.float32(R.best_acc_score))
+    r.update({k: getattr(R, k) for k in ("n_sharing", "max_common", "min_common", "n_scored")})
+    if views:
+        r.update({k: a[k][:n_slots].copy() for k in ("words", "score", "acc", "best")})
+    return r
 
 
 def _bow_out(cap):
@@ -900,6 +947,20 @@ def lib():
         L.hvo_stream_search_by_bow.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(BowKeyframe), C.POINTER(BowSearchParams), C.POINTER(BowMatches)]
         L.hvo_bow_last_kernel_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.hvo_stream_bow_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.hvo_keyframe_db_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.hvo_keyframe_db_destroy.argtypes = [C.c_void_p]; L.hvo_keyframe_db_destroy.restype = None
+        L.hvo_keyframe_db_last_error.argtypes = [C.c_void_p]; L.hvo_keyframe_db_last_error.restype = C.c_char_p
+        L.hvo_keyframe_db_add.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.hvo_stream_keyframe_db_add.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
+        L.hvo_keyframe_db_erase.argtypes = [C.c_void_p, C.c_int]
+        L.hvo_keyframe_db_clear.argtypes = [C.c_void_p]
+        L.hvo_keyframe_db_set_covisible.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.hvo_keyframe_db_get.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
+        L.hvo_keyframe_db_info.argtypes = [C.c_void_p, C.POINTER(KeyframeDbDesc)]
+        L.hvo_keyframe_db_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(KfdbParams), C.POINTER(KfdbResult)]
+        L.hvo_stream_keyframe_db_query.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(KfdbParams), C.POINTER(KfdbResult)]
+        L.hvo_batch_keyframe_db_query.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(KfdbParams), C.POINTER(KfdbResult)]
+        L.hvo_keyframe_db_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.hvo_pnp_default_params.argtypes = [C.POINTER(PnpParams)]; L.hvo_pnp_default_params.restype = None
         L.hvo_pnp_ransac.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(PnpParams), C.c_int, C.POINTER(PnpProblem), C.POINTER(PnpResult)]
         L.hvo_stream_pnp_ransac.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(PnpParams), C.c_int, C.POINTER(PnpKeyframeSide), C.POINTER(PnpResult)]
@@ -1201,6 +1262,94 @@ class Vocabulary:
         if rc != HVO_OK:
             raise HvoError(rc, "hvo_vocabulary_info")
         return {k: getattr(d, k) for k, _ in VocabularyDesc._fields_}
+
+
+class KeyFrameDatabase:
+    """hvo_keyframe_db: the key-frame database resident on the vocabulary's device.  A key frame is a slot (0 <= slot < 16384) the caller
+    numbers; it holds the key frame's bag of words, up to 10 covisible slots and the scores the last queries left on it.  Both detections
+    return the slots of the candidates in the reference's order.  Not thread-safe."""
+
+    def __init__(self, voc):
+        h = C.c_void_p()
+        rc = lib().hvo_keyframe_db_create(voc.h, C.byref(h))
+        if rc != HVO_OK:
+            raise HvoError(rc, "hvo_keyframe_db_create")
+        self.h = h; self.voc = voc
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().hvo_keyframe_db_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _chk(self, rc, what):
+        if rc != HVO_OK:
+            raise HvoError(rc, what + ": " + lib().hvo_keyframe_db_last_error(self.h).decode())
+
+    def last_error(self):
+        return lib().hvo_keyframe_db_last_error(self.h).decode()
+
+    def info(self):
+        """dict(n_slots, n_live, scoring, device, pooled_words, pool_capacity, next_sequence)"""
+        d = KeyframeDbDesc()
+        self._chk(lib().hvo_keyframe_db_info(self.h, C.byref(d)), "keyframe_db_info")
+        return {k: getattr(d, k) for k, _ in KeyframeDbDesc._fields_}
+
+    def add(self, slot, bow_word, bow_value=None, ticket=None):
+        """KeyFrameDatabase::add: add(slot, bow_word, bow_value) with the bag as compute_bow returns it, or add(slot, stream, ticket=t) with the
+        bag Stream.compute_bow left on the resident frame t (device to device)"""
+        if ticket is not None:
+            return bow_word.keyframe_db_add(ticket, self, slot)
+        w = np.ascontiguousarray(bow_word, np.int32).reshape(-1); v = np.ascontiguousarray(bow_value, np.float64).reshape(-1)
+        if len(w) != len(v):
+            raise ValueError("bow_word and bow_value differ in length")
+        self._chk(lib().hvo_keyframe_db_add(self.h, slot, len(w), _p(w) if len(w) else None, _p(v) if len(v) else None), "keyframe_db_add")
+
+    def erase(self, slot):
+        self._chk(lib().hvo_keyframe_db_erase(self.h, slot), "keyframe_db_erase")
+
+    def clear(self):
+        self._chk(lib().hvo_keyframe_db_clear(self.h), "keyframe_db_clear")
+
+    def set_covisible(self, slot, slots):
+        """the slot's GetBestCovisibilityKeyFrames(10), in that order"""
+        a = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        self._chk(lib().hvo_keyframe_db_set_covisible(self.h, slot, len(a), _p(a) if len(a) else None), "keyframe_db_set_covisible")
+
+    setCovisible = set_covisible
+
+    def get(self, slot):
+        """(bow_word, bow_value, (kept reloc score, kept loop score)) of a live slot as the device holds them"""
+        n = C.c_int32(0); sc = np.zeros(2, np.float32)
+        self._chk(lib().hvo_keyframe_db_get(self.h, slot, 0, None, None, C.byref(n), _p(sc)), "keyframe_db_get")
+        w = np.zeros(max(n.value, 1), np.int32); v = np.zeros(max(n.value, 1), np.float64)
+        self._chk(lib().hvo_keyframe_db_get(self.h, slot, len(w), _p(w), _p(v), C.byref(n), _p(sc)), "keyframe_db_get")
+        return w[:n.value].copy(), v[:n.value].copy(), sc
+
+    def query(self, bow_word, bow_value, mode=KFDB_RELOC, min_score=0.0, connected=None, views=False, cap=None):
+        """either detection with the bag on the host; see _kfdb_finish for the result"""
+        w = np.ascontiguousarray(bow_word, np.int32).reshape(-1); v = np.ascontiguousarray(bow_value, np.float64).reshape(-1)
+        if len(w) != len(v):
+            raise ValueError("bow_word and bow_value differ in length")
+        ns = self.info()["n_slots"]
+        P, R, a = _kfdb_args(ns, mode, min_score, connected, views, cap)
+        self._chk(lib().hvo_keyframe_db_query(self.h, len(w), _p(w) if len(w) else None, _p(v) if len(v) else None, C.byref(P), C.byref(R)), "keyframe_db_query")
+        return _kfdb_finish(R, a, ns, views)
+
+    def DetectRelocalizationCandidates(self, stream, ticket):
+        """the candidates' slots for the resident frame `ticket` (Stream.compute_bow first)"""
+        return stream.keyframe_db_query(ticket, self)["candidates"].tolist()
+
+    def DetectLoopCandidates(self, bow, connected, minScore):
+        """bow: (bow_word, bow_value) of the query key frame or the dict compute_bow returned; connected: the slots of its connected key frames"""
+        w, v = (bow["bow_word"], bow["bow_value"]) if isinstance(bow, dict) else bow
+        return self.query(w, v, KFDB_LOOP, minScore, connected)["candidates"].tolist()
+
+    def last_kernel_ms(self):
+        ms = C.c_float(0)
+        self._chk(lib().hvo_keyframe_db_last_kernel_ms(self.h, C.byref(ms)), "keyframe_db_last_kernel_ms")
+        return ms.value
 
 
 class Context:
@@ -1683,6 +1832,21 @@ class Context:
         self._chk(lib().hvo_bow_last_kernel_ms(self.h, _p(ms)), "bow_last_kernel_ms")
         return float(ms[0]), float(ms[1])
 
+    def keyframe_db_query(self, db, bow_word, bow_value, mode=KFDB_RELOC, min_score=0.0, connected=None, views=False):
+        """KeyFrameDatabase.query (the database has its own stream; the context only names the call like its siblings)"""
+        return db.query(bow_word, bow_value, mode, min_score, connected, views)
+
+    def batch_keyframe_db_query(self, voc, db, n, mode=KFDB_RELOC, min_score=0.0, connected=None, views=False):
+        """frames 0 .. n-1 of the resident batch (batch_compute_bow first), queried one after the other; a list of n results"""
+        ns = db.info()["n_slots"]
+        P = (KfdbParams * n)(); R = (KfdbResult * n)(); keep = []
+        for f in range(n):
+            P[f], R[f], a = _kfdb_args(ns, mode, min_score, connected, views); keep.append(a)
+        rc = lib().hvo_batch_keyframe_db_query(self.h, voc.h, db.h, n, P, R)
+        if rc != HVO_OK:
+            raise HvoError(rc, "batch_keyframe_db_query: " + db.last_error())
+        return [_kfdb_finish(R[f], keep[f], ns, views) for f in range(n)]
+
     def pnp_ransac(self, cam, problems, params=None, want_sample=False, check=True, spare_events=0):
         """PnPsolver's EPnP RANSAC of every candidate in one call.  cam = (fx, fy, cx, cy); problems: a list of dict(p3d (n x 3), p2d (n x 2),
         sigma2 (n), feature_index (n), n_features); params: pnp_params(...).  Returns one dict per candidate (hyp_inliers, hyp_event, events,
@@ -2162,6 +2326,21 @@ class Stream:
         ms = np.zeros(2, np.float32)
         self._chk(lib().hvo_stream_bow_last_kernel_ms(self.h, cur, _p(ms)), "stream_bow_last_kernel_ms")
         return float(ms[0]), float(ms[1])
+
+    def keyframe_db_add(self, ticket, db, slot):
+        """KeyFrameDatabase::add with the bag compute_bow left on the resident frame `ticket`: device to device"""
+        rc = lib().hvo_stream_keyframe_db_add(self.h, ticket, db.voc.h, db.h, slot)
+        if rc != HVO_OK:
+            raise HvoError(rc, "stream_keyframe_db_add: " + db.last_error())
+
+    def keyframe_db_query(self, ticket, db, mode=KFDB_RELOC, min_score=0.0, connected=None, views=False, voc=None):
+        """either detection with the bag compute_bow left on the resident frame `ticket`; nothing of the bag crosses the bus"""
+        ns = db.info()["n_slots"]
+        P, R, a = _kfdb_args(ns, mode, min_score, connected, views)
+        rc = lib().hvo_stream_keyframe_db_query(self.h, ticket, (voc or db.voc).h, db.h, C.byref(P), C.byref(R))
+        if rc != HVO_OK:
+            raise HvoError(rc, "stream_keyframe_db_query: " + db.last_error())
+        return _kfdb_finish(R, a, ns, views)
 
     def pnp_ransac(self, cur, cam, kf_sides, params=None, want_sample=False, check=True):
         """PnPsolver's RANSAC of every candidate against the resident frame `cur`: kf_sides is a list of dict(match_kf (as search_by_bow returned

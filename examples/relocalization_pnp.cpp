@@ -4,7 +4,7 @@
 // `iterate(5, bNoMore, vbInliers, nInliers)` loop as a host replay, and Optimizer::PoseOptimization with the accepted candidate's inliers.
 // The frames but the last play the candidate key frames (camera = world for each: its features with depth are its map points); the last
 // frame is the one to relocalise.  Between its upload and the optimised pose only the key frames' arrays, the match vectors and the matched
-// positions cross PCIe.  The candidate query (DetectRelocalizationCandidates) stays on the host; SearchByProjection(Frame, KeyFrame, ...) and
+// positions cross PCIe.  The candidate query (DetectRelocalizationCandidates) is examples/keyframe_db.cpp; SearchByProjection(Frame, KeyFrame, ...) and
 // the optimisations around it are examples/relocalization_refine.cpp.  Neither is part of this example.  No vocabulary file is needed: a small random k = 8, L = 3 tree is generated.
 // Reads raw 640x480 gray (u8) + depth (u16) pairs.
 //

@@ -1055,6 +1055,78 @@ int hvo_stream_search_by_bow(hvo_stream *s, int64_t cur, const hvo_vocabulary *v
 int hvo_bow_last_kernel_ms(const hvo_ctx *ctx, float ms2[2]);
 int hvo_stream_bow_last_kernel_ms(hvo_stream *s, int64_t cur, float ms2[2]);
 
+/* ---- The key-frame database resident on the device: KeyFrameDatabase and both candidate detections (csrc/kf_db.hip) ----
+ * Restated: KeyFrameDatabase::add / erase / clear (src/KeyFrameDatabase.cc:40-73), DetectLoopCandidates (:76-197),
+ * DetectRelocalizationCandidates (:199-309) and the vocabulary's score() (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-310).
+ *
+ * A key frame is a SLOT (0 <= slot < HVO_KFDB_MAX_SLOTS) the caller numbers: it holds the key frame's bag of words (ascending word ids,
+ * double values, at most 4096 words), the order number of its add, up to 10 neighbour slots (the key frame's
+ * GetBestCovisibilityKeyFrames(10), in that order; the host owns the covisibility graph and sets them) and the two scores the last
+ * queries left on it (mRelocScore, mLoopScore), which persist from query to query as they do on a KeyFrame.  DEFINED BEHAVIOUR: a slot
+ * that has never been scored holds 0.0f where the reference reads an uninitialised float; add resets both.
+ *
+ * The database belongs to the vocabulary's device like hvo_plane_map (a host-only vocabulary is refused), has its own HIP stream and is
+ * not thread-safe: guard it by the mutex that guards the reference's database.  Every call returns with its device work done.  Every
+ * refusal is whole -- nothing of the database changes -- and leaves its reason in hvo_keyframe_db_last_error:
+ *   slot outside [0, 16384); add on a live slot (erase first); more than 4096 words (HVO_ERR_UNSUPPORTED); word ids that are not strictly
+ *   ascending or not below the vocabulary's word count; a value that is negative or not finite (no DBoW2 weighting produces one, and it
+ *   keeps NaN out of the scores); set_covisible / get on a slot that is not live; more than 10 neighbours; a query on a vocabulary with KL
+ *   scoring (HVO_ERR_UNSUPPORTED: it needs log); result.cap below the candidate count (HVO_ERR_CAPACITY with n_candidates = the count
+ *   needed and the kept scores left as they were); slot_cap below the slot count when a view is asked for.
+ * erase of a slot that is not live does nothing.  A neighbour id or a connected id that is out of range or erased is skipped. */
+#define HVO_KFDB_MAX_SLOTS 16384
+#define HVO_KFDB_MAX_COVISIBLE 10
+enum { HVO_KFDB_RELOC = 0, HVO_KFDB_LOOP = 1 };
+typedef struct hvo_keyframe_db hvo_keyframe_db;
+typedef struct {
+    int32_t n_slots;              /* highest slot ever added + 1 (0 after clear): the length of the per-slot views */
+    int32_t n_live;
+    int32_t scoring, device;
+    int64_t pooled_words;         /* words of pool in use (rooms are multiples of 64; an erased slot keeps its room) */
+    int64_t pool_capacity;
+    int64_t next_sequence;        /* the order number the next add gets */
+} hvo_keyframe_db_desc;
+int hvo_keyframe_db_create(const hvo_vocabulary *voc, hvo_keyframe_db **db);
+void hvo_keyframe_db_destroy(hvo_keyframe_db *db);
+const char *hvo_keyframe_db_last_error(const hvo_keyframe_db *db);
+int hvo_keyframe_db_add(hvo_keyframe_db *db, int slot, int n_words, const int32_t *word, const double *value);
+/* add with the bag hvo_stream_compute_bow left on the resident frame `ticket` for `voc`: device to device, only the word count comes down */
+int hvo_stream_keyframe_db_add(hvo_stream *s, int64_t ticket, const hvo_vocabulary *voc, hvo_keyframe_db *db, int slot);
+int hvo_keyframe_db_erase(hvo_keyframe_db *db, int slot);
+int hvo_keyframe_db_clear(hvo_keyframe_db *db);
+int hvo_keyframe_db_set_covisible(hvo_keyframe_db *db, int slot, int n, const int32_t *slots);
+/* read-back (tests, a viewer): a live slot's bag (cap entries; HVO_ERR_CAPACITY with *n_words set when too small; word / value may be
+ * NULL) and score2 = { kept reloc score, kept loop score } as the device holds them */
+int hvo_keyframe_db_get(const hvo_keyframe_db *db, int slot, int cap, int32_t *word, double *value, int32_t *n_words, float score2[2]);
+int hvo_keyframe_db_info(const hvo_keyframe_db *db, hvo_keyframe_db_desc *info);
+
+typedef struct {
+    int32_t mode;                 /* HVO_KFDB_RELOC: DetectRelocalizationCandidates; HVO_KFDB_LOOP: DetectLoopCandidates */
+    float min_score;              /* loop form: minScore */
+    const int32_t *connected;     /* loop form: the slots of pKF->GetConnectedKeyFrames(); they are never "in the query" */
+    int32_t n_connected;
+} hvo_kfdb_params;
+typedef struct {
+    int32_t cap; int32_t *candidate; int32_t n_candidates;      /* the returned vector: slots (pBestKF), in the reference's order */
+    /* optional views (NULL: not wanted) of slot_cap >= n_slots entries, entry = slot: the common words (0: not in the query), the score
+     * THIS query wrote (NaN: none), accScore (NaN: the slot did not enter lScoreAndMatch) and pBestKF (-1 likewise) */
+    int32_t slot_cap; int32_t *words; float *score; float *acc; int32_t *best;
+    int32_t n_sharing, max_common, min_common, n_scored;        /* lKFsSharingWords.size(), maxCommonWords, minCommonWords, nscores */
+    float best_acc_score;         /* bestAccScore (its start value, 0 or min_score, when nothing entered) */
+    int32_t status;
+} hvo_kfdb_result;
+/* An empty database, a query without words and a query that shares no word with any slot are HVO_OK with n_candidates = 0.  Candidates
+ * are ordered as the reference's list walk orders them: by (smallest word in common with the query, order of add).  The host form takes
+ * the bag as hvo_bow returns it; the stream form reads the bag hvo_stream_compute_bow left on the frame `ticket` for `voc` and the batch
+ * form the bags hvo_batch_compute_bow left on frames 0 .. n-1, queried one after the other in that order (the kept scores make the order
+ * matter): frame k's answer is bit for bit that of the k-th of n stream calls.  A frame without a bag of words for `voc` (or a database
+ * created for another vocabulary) is HVO_ERR_INVALID_ARG.  Each query synchronises once, at its end. */
+int hvo_keyframe_db_query(hvo_keyframe_db *db, int n_words, const int32_t *word, const double *value, const hvo_kfdb_params *p, hvo_kfdb_result *res);
+int hvo_stream_keyframe_db_query(hvo_stream *s, int64_t ticket, const hvo_vocabulary *voc, hvo_keyframe_db *db, const hvo_kfdb_params *p, hvo_kfdb_result *res);
+int hvo_batch_keyframe_db_query(hvo_ctx *ctx, const hvo_vocabulary *voc, hvo_keyframe_db *db, int n, const hvo_kfdb_params *p, hvo_kfdb_result *res);
+/* device time in ms of the last query's four kernels (0 when it launched nothing) */
+int hvo_keyframe_db_last_kernel_ms(const hvo_keyframe_db *db, float *ms);
+
 /* ---- The relocalisation PnP solver: PnPsolver's EPnP RANSAC for all candidates of a relocalisation in one call (csrc/pnp.hip) ----
  * Restated: the PnPsolver constructor (src/PnPsolver.cc:67-110), SetRansacParameters (:121-157), iterate (:165-258), Refine (:260-305),
  * CheckInliers (:308-339) and EPnP (:342-950), as Tracking::Relocalization drives them (src/Tracking.cc:3789-3909).  There is no batch

@@ -874,6 +874,53 @@ struct Frame {
     }
 };
 
+// KeyFrameDatabase (src/KeyFrameDatabase.cc) resident on the vocabulary's device.  A key frame is a slot (0 <= slot < 16384) the caller
+// numbers -- the index of the KeyFrame in whatever table the tracker keeps; both detections return slots, in the reference's order.  The
+// host owns the covisibility graph: after UpdateConnections it hands each touched key frame's GetBestCovisibilityKeyFrames(10) to
+// setCovisible.  Not thread-safe: guard it by the mutex the reference's database has.
+class KeyFrameDatabase {
+public:
+    explicit KeyFrameDatabase(const ORBVocabulary &voc) : db_(nullptr), voc_(voc.get()) { check(hvo_keyframe_db_create(voc_, &db_), "hvo_keyframe_db_create"); }
+    ~KeyFrameDatabase() { hvo_keyframe_db_destroy(db_); }
+    KeyFrameDatabase(const KeyFrameDatabase &) = delete;
+    KeyFrameDatabase &operator=(const KeyFrameDatabase &) = delete;
+    // add(pKF) with pKF->mBowVec on the host, or with the bag Frame::ComputeBoW left on the resident frame (device to device)
+    void add(int slot, const BowVectors &bow) { chk(hvo_keyframe_db_add(db_, slot, (int)bow.bow_word.size(), bow.bow_word.data(), bow.bow_value.data()), "hvo_keyframe_db_add"); }
+    void add(FrameStream &fs, int64_t ticket, int slot) { chk(hvo_stream_keyframe_db_add(fs.get(), ticket, voc_, db_, slot), "hvo_stream_keyframe_db_add"); }
+    void erase(int slot) { chk(hvo_keyframe_db_erase(db_, slot), "hvo_keyframe_db_erase"); }
+    void clear() { chk(hvo_keyframe_db_clear(db_), "hvo_keyframe_db_clear"); }
+    void setCovisible(int slot, const std::vector<int> &slots) { chk(hvo_keyframe_db_set_covisible(db_, slot, (int)slots.size(), slots.data()), "hvo_keyframe_db_set_covisible"); }
+    int size() const { hvo_keyframe_db_desc d; check(hvo_keyframe_db_info(db_, &d), "hvo_keyframe_db_info"); return d.n_live; }
+    // Tracking.cc:3767: the frame's bag of words is the one Frame::ComputeBoW left on it
+    std::vector<int> DetectRelocalizationCandidates(FrameStream &fs, int64_t ticket)
+    {
+        hvo_kfdb_params p = { HVO_KFDB_RELOC, 0.f, nullptr, 0 };
+        hvo_kfdb_result r = result();
+        chk(hvo_stream_keyframe_db_query(fs.get(), ticket, voc_, db_, &p, &r), "hvo_stream_keyframe_db_query");
+        return std::vector<int>(cand_.begin(), cand_.begin() + r.n_candidates);
+    }
+    // LoopClosing::DetectLoop: the query key frame's bag, the slots of its GetConnectedKeyFrames(), minScore
+    std::vector<int> DetectLoopCandidates(const BowVectors &bow, const std::vector<int> &connected, float minScore)
+    {
+        hvo_kfdb_params p = { HVO_KFDB_LOOP, minScore, connected.data(), (int32_t)connected.size() };
+        hvo_kfdb_result r = result();
+        chk(hvo_keyframe_db_query(db_, (int)bow.bow_word.size(), bow.bow_word.data(), bow.bow_value.data(), &p, &r), "hvo_keyframe_db_query");
+        return std::vector<int>(cand_.begin(), cand_.begin() + r.n_candidates);
+    }
+    float lastKernelMs() const { float ms = 0.f; check(hvo_keyframe_db_last_kernel_ms(db_, &ms), "hvo_keyframe_db_last_kernel_ms"); return ms; }
+    hvo_keyframe_db *get() const { return db_; }
+private:
+    void chk(int rc, const char *what) const { if (rc != HVO_OK) throw Error(rc, std::string(what) + ": " + hvo_keyframe_db_last_error(db_)); }
+    hvo_kfdb_result result()
+    {
+        hvo_keyframe_db_desc d; check(hvo_keyframe_db_info(db_, &d), "hvo_keyframe_db_info");
+        cand_.assign((size_t)(d.n_slots < 1 ? 1 : d.n_slots), -1);
+        hvo_kfdb_result r = hvo_kfdb_result(); r.cap = (int32_t)cand_.size(); r.candidate = cand_.data();
+        return r;
+    }
+    hvo_keyframe_db *db_; const hvo_vocabulary *voc_; std::vector<int32_t> cand_;
+};
+
 inline int ORBmatcher::SearchByProjection(FrameStream &fs, int64_t cur, const hvo_camera &cam, const float Tcw[12], const KeyFrameSide &kf, const uint8_t *skip,
                                           const uint8_t *occupied, int n_features, float th, int ORBdist, KeyFrameMatches &res, bool checkOrientation,
                                           float logScaleFactor, int nLevels) const
