@@ -93,6 +93,7 @@ EXPORTS = [
     "hvo_keyframe_db_query", "hvo_stream_keyframe_db_query", "hvo_batch_keyframe_db_query", "hvo_keyframe_db_last_kernel_ms",
     "hvo_pnp_default_params", "hvo_pnp_ransac", "hvo_stream_pnp_ransac", "hvo_pnp_last_kernel_ms", "hvo_stream_pnp_last_kernel_ms",
     "hvo_search_by_projection_keyframe", "hvo_stream_search_by_projection_keyframe",
+    "hvo_fuse_points", "hvo_fuse_points_slots", "hvo_stream_fuse_points",
     "hvo_update_map_planes", "hvo_stream_update_map_planes", "hvo_plane_map_get_points", "hvo_plane_update_transform",
 ]
 
@@ -704,6 +705,109 @@ def _kfs_finish(R, keep, n_frame):
     return out
 
 
+FUSE_MAX_FEATURES, FUSE_MAX_ENTRIES = 65535, 1 << 20
+FUSE_GATES = ("searched", "skip", "behind", "out of image", "dist < 0.8 min", "dist > 1.2 max", "view angle")     # hvo_fuse_result.gate
+FUSE_UNTOUCHED = -7         # what the outputs hold before the call: a refusal leaves them so
+
+
+class FuseKeyframe(C.Structure):
+    """hvo_fuse_keyframe: a key frame's features, its pose and the skip bytes of its map entries"""
+    _fields_ = [("n", C.c_int32), ("kp_un", C.c_void_p), ("uright", C.c_void_p), ("desc", C.c_void_p), ("Tcw", C.c_float * 12), ("skip", C.c_void_p)]
+
+
+class FuseMap(C.Structure):
+    """hvo_fuse_map: a map side on host arrays"""
+    _fields_ = [("n", C.c_int32), ("pos", C.c_void_p), ("normal", C.c_void_p), ("max_dist", C.c_void_p), ("min_dist", C.c_void_p), ("desc", C.c_void_p)]
+
+
+class FuseParams(C.Structure):
+    """hvo_fuse_params"""
+    _fields_ = [("th", C.c_float), ("th_low", C.c_int32), ("log_scale_factor", C.c_float), ("n_levels", C.c_int32), ("bf", C.c_float),
+                ("bounds", C.c_float * 4), ("map_per_keyframe", C.c_int32)]
+
+
+class FuseResult(C.Structure):
+    """hvo_fuse_result"""
+    _fields_ = [("best_idx", C.c_void_p), ("best_dist", C.c_void_p), ("gate", C.c_void_p), ("level", C.c_void_p), ("proj", C.c_void_p),
+                ("fused_entry", C.c_void_p), ("fused_idx", C.c_void_p), ("n_fused", C.c_int32), ("n_searched", C.c_int32), ("status", C.c_int32),
+                ("kernel_ms", C.c_float * 3)]
+
+
+assert C.sizeof(FuseKeyframe) == 88 and C.sizeof(FuseMap) == 48 and C.sizeof(FuseParams) == 40 and C.sizeof(FuseResult) == 80
+
+
+def _fuse_params(cam, bounds4, th, th_low, log_scale_factor, n_levels, per_keyframe):
+    P = FuseParams(); P.th = th; P.th_low = th_low; P.log_scale_factor = log_scale_factor; P.n_levels = n_levels; P.bf = float(cam[4])
+    b = (0.0, 1.0, 0.0, 1.0) if bounds4 is None else [float(v) for v in np.asarray(bounds4).reshape(4)]
+    for k in range(4): P.bounds[k] = b[k]
+    P.map_per_keyframe = 1 if per_keyframe else 0
+    return P
+
+
+def _fuse_map(mp):
+    """dict(pos, normal (n x 3), max_dist, min_dist (n, raw), desc (n x 32)) -> (FuseMap fields as arrays, n)"""
+    pos = np.ascontiguousarray(mp["pos"], np.float32).reshape(-1, 3); n = len(pos)
+    a = dict(pos=pos, normal=np.ascontiguousarray(mp["normal"], np.float32).reshape(-1, 3), max_dist=np.ascontiguousarray(mp["max_dist"], np.float32).reshape(-1),
+             min_dist=np.ascontiguousarray(mp["min_dist"], np.float32).reshape(-1), desc=np.ascontiguousarray(mp["desc"], np.uint8).reshape(-1, 32))
+    if any(len(v) != n for v in a.values()):
+        raise ValueError("fuse_points: a map side's arrays differ in length")
+    return a, n
+
+
+def _fuse_maps(maps):
+    M = (FuseMap * len(maps))(); keep = []
+    for s, mp in enumerate(maps):
+        a, n = _fuse_map(mp)
+        M[s].n = n
+        for k, v in a.items(): setattr(M[s], k, v.ctypes.data if n else None)
+        keep.append(a)
+    return M, keep, [M[s].n for s in range(len(maps))]
+
+
+def _fuse_keyframes(kfs, n_entries, resident=False):
+    """kfs: dicts of kp_un, uright (or None), desc, Tcw, skip (or None); n_entries[j]: the entries of key frame j's map side"""
+    K = (FuseKeyframe * len(kfs))(); keep = []
+    for j, kf in enumerate(kfs):
+        a = {}
+        if not resident:
+            a["kp_un"] = np.ascontiguousarray(kf["kp_un"], KEYPOINT_DT); nt = len(a["kp_un"])
+            a["desc"] = np.ascontiguousarray(kf["desc"], np.uint8).reshape(nt, 32)
+            a["uright"] = None if kf.get("uright") is None else np.ascontiguousarray(kf["uright"], np.float32).reshape(nt)
+            K[j].n = nt
+            for k in ("kp_un", "desc", "uright"): setattr(K[j], k, a[k].ctypes.data if a[k] is not None and nt else None)
+        a["skip"] = None if kf.get("skip") is None else np.ascontiguousarray(np.asarray(kf["skip"]).astype(bool), np.uint8).reshape(n_entries[j])
+        K[j].skip = a["skip"].ctypes.data if a["skip"] is not None and a["skip"].size else None
+        T = np.asarray(kf["Tcw"], np.float32).reshape(12)
+        for k in range(12): K[j].Tcw[k] = T[k]
+        keep.append(a)
+    return K, keep
+
+
+def _fuse_results(n_entries):
+    R = (FuseResult * len(n_entries))(); keep = []
+    for j, n in enumerate(n_entries):
+        m = max(n, 1)
+        o = dict(best_idx=np.full(m, FUSE_UNTOUCHED, np.int32), best_dist=np.full(m, FUSE_UNTOUCHED, np.int32), gate=np.full(m, FUSE_UNTOUCHED, np.int8),
+                 level=np.full(m, FUSE_UNTOUCHED, np.int32), proj=np.full((m, 3), FUSE_UNTOUCHED, np.float32),
+                 fused_entry=np.full(m, FUSE_UNTOUCHED, np.int32), fused_idx=np.full(m, FUSE_UNTOUCHED, np.int32))
+        for k in o: setattr(R[j], k, o[k].ctypes.data)
+        R[j].n_fused = R[j].n_searched = R[j].status = FUSE_UNTOUCHED
+        keep.append((o, n))
+    return R, keep
+
+
+def _fuse_finish(R, keep, ok):
+    """one dict per key frame; after a refusal (ok False) every array is returned whole, as the call left it"""
+    out = []
+    for j, (o, n) in enumerate(keep):
+        d = dict(n_fused=R[j].n_fused, n_searched=R[j].n_searched, status=R[j].status, kernel_ms=tuple(R[j].kernel_ms))
+        for k in ("best_idx", "best_dist", "gate", "level", "proj"): d[k] = o[k][:n] if ok else o[k]
+        nf = max(0, min(R[j].n_fused, n)) if ok else len(o["fused_entry"])
+        d["fused_entry"] = o["fused_entry"][:nf]; d["fused_idx"] = o["fused_idx"][:nf]
+        out.append(d)
+    return out
+
+
 def line_struct_params(**kw):
     """the reference's values (hvo_line_struct_default_params) with the given fields replaced (mode, row_rule, ...)"""
     p = LineStructParams()
@@ -969,6 +1073,11 @@ def lib():
                                                         C.POINTER(KfSearchCandidate), C.POINTER(KfSearchResult)]
         L.hvo_stream_search_by_projection_keyframe.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(KfSearchParams), C.c_int,
                                                                C.POINTER(KfSearchCandidate), C.POINTER(KfSearchResult)]
+        L.hvo_fuse_points.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.POINTER(FuseMap), C.c_int, C.POINTER(FuseKeyframe), C.POINTER(FuseResult)]
+        L.hvo_fuse_points_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.c_int, C.POINTER(FuseKeyframe),
+                                            C.POINTER(FuseResult)]
+        L.hvo_stream_fuse_points.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.c_void_p, C.c_void_p, C.POINTER(FuseMap), C.c_void_p,
+                                             C.c_int, C.c_void_p, C.POINTER(FuseResult)]
         L.hvo_stream_pnp_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.hvo_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         L.hvo_stream_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
@@ -1888,6 +1997,42 @@ class Context:
         self._chk(rc, "search_by_projection_keyframe")
         return _kfs_finish(R, keep, nt)
 
+    def fuse_points(self, cam, kfs, maps, bounds4, th=3.0, th_low=50, log_scale_factor=float(np.log(np.float32(1.2))), n_levels=8, check=True):
+        """ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:838-994) for every key frame of kfs (dicts: kp_un, uright or None, desc, Tcw,
+        skip or None) in one call.  maps: ONE dict (pos, normal, max_dist, min_dist, desc), shared by all key frames and uploaded once, or a
+        list with one dict per key frame.  cam: (fx, fy, cx, cy, bf).  Returns one dict per key frame: best_idx, best_dist, gate, level, proj
+        (n x 3), fused_entry, fused_idx (the list the caller walks), n_fused, n_searched, status, kernel_ms.  check=False: (return code,
+        message, the dicts) instead of an exception; a refused call leaves every output at FUSE_UNTOUCHED."""
+        per_kf = not isinstance(maps, dict)
+        if per_kf and len(maps) != len(kfs):
+            raise ValueError("fuse_points: one map side per key frame, or one dict for all")
+        M, mk, ns = _fuse_maps(list(maps) if per_kf else [maps])
+        ne = ns if per_kf else ns * len(kfs)
+        K, kk = _fuse_keyframes(kfs, ne)
+        R, rk = _fuse_results(ne)
+        P = _fuse_params(cam, bounds4, th, th_low, log_scale_factor, n_levels, per_kf)
+        cm = _pose_cam(cam)
+        rc = lib().hvo_fuse_points(self.h, C.byref(cm), C.byref(P), M, len(kfs), K, R)
+        if not check:
+            return rc, lib().hvo_last_error(self.h).decode(), _fuse_finish(R, rk, rc == HVO_OK)
+        self._chk(rc, "fuse_points")
+        return _fuse_finish(R, rk, True)
+
+    def fuse_points_slots(self, point_map, slots, cam, kfs, bounds4, th=3.0, th_low=50, log_scale_factor=float(np.log(np.float32(1.2))), n_levels=8, check=True):
+        """fuse_points with the map side given as slots of a resident PointMap, shared by all key frames: the map's device arrays are read in
+        place, only the slot list and the skip bytes go up.  A bad slot counts as skipped; a slot outside the map refuses the whole call."""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1); n = len(sl)
+        ne = [n] * len(kfs)
+        K, kk = _fuse_keyframes(kfs, ne)
+        R, rk = _fuse_results(ne)
+        P = _fuse_params(cam, bounds4, th, th_low, log_scale_factor, n_levels, False)
+        cm = _pose_cam(cam)
+        rc = lib().hvo_fuse_points_slots(self.h, point_map.h, n, sl.ctypes.data if n else None, C.byref(cm), C.byref(P), len(kfs), K, R)
+        if not check:
+            return rc, lib().hvo_last_error(self.h).decode(), _fuse_finish(R, rk, rc == HVO_OK)
+        self._chk(rc, "fuse_points_slots")
+        return _fuse_finish(R, rk, True)
+
     def pnp_last_kernel_ms(self):
         """(hypothesis kernels, refine kernels): device ms of the last pnp_ransac"""
         ms = np.zeros(2, np.float32)
@@ -2376,6 +2521,26 @@ class Stream:
             return rc, lib().hvo_stream_last_error(self.h).decode(), _kfs_finish(R, keep, int(n_kp))
         self._chk(rc, "stream_search_by_projection_keyframe")
         return _kfs_finish(R, keep, int(n_kp))
+
+    def fuse_points(self, cur, cam, Tcw, maps=None, point_map=None, slots=None, skip=None, th=3.0, th_low=50,
+                    log_scale_factor=float(np.log(np.float32(1.2))), n_levels=8, check=True):
+        """ORBmatcher::Fuse(mpCurrentKeyFrame, vpFuseCandidates) with the resident frame `cur` as the key frame under Tcw (needs STAGE_ORB):
+        its undistorted key points, mvuRight and descriptors stay on the device, the bounds are the frame grid's.  The map side is `maps`
+        (one dict of host arrays) or `slots` of `point_map`.  Returns one dict as Context.fuse_points does per key frame."""
+        if maps is not None:
+            M, mk, ns = _fuse_maps([maps]); n = ns[0]; sl = None
+        else:
+            M = None; sl = np.ascontiguousarray(slots, np.int32).reshape(-1); n = len(sl)
+        K, kk = _fuse_keyframes([dict(Tcw=Tcw, skip=skip)], [n], resident=True)
+        R, rk = _fuse_results([n])
+        P = _fuse_params(cam, None, th, th_low, log_scale_factor, n_levels, False)
+        cm = _pose_cam(cam)
+        rc = lib().hvo_stream_fuse_points(self.h, cur, C.byref(cm), C.byref(P), C.addressof(K[0].Tcw), K[0].skip, M, point_map.h if point_map is not None else None,
+                                          n, sl.ctypes.data if sl is not None and n else None, R)
+        if not check:
+            return rc, lib().hvo_stream_last_error(self.h).decode(), _fuse_finish(R, rk, rc == HVO_OK)[0]
+        self._chk(rc, "stream_fuse_points")
+        return _fuse_finish(R, rk, True)[0]
 
     def pnp_last_kernel_ms(self, cur):
         ms = np.zeros(2, np.float32)

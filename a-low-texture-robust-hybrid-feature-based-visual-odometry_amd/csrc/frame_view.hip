@@ -18,6 +18,7 @@ const FrameNeed need_bow           = { "bag of words", HVO_STAGE_ORB, false, 0, 
 const FrameNeed need_bow_search    = { "search by bag of words", 0, false, 0, "", false, false, FV_N_KP, FV_EV_ORB, "", "" };     // (the frame's kept bag of words is the caller's check)
 const FrameNeed need_pnp           = { "pnp", HVO_STAGE_ORB, false, 0, "", false, false, FV_N_KP, FV_EV_ORB, "HVO_STAGE_ORB", "HVO_STAGE_ORB" };
 const FrameNeed need_kf_search     = { "key-frame search", HVO_STAGE_ORB, false, 0, "", false, false, FV_N_KP, FV_EV_ORB, "HVO_STAGE_ORB", "HVO_STAGE_ORB" };
+const FrameNeed need_fuse          = { "fuse", HVO_STAGE_ORB, false, 0, "", true, false, FV_N_KP, FV_EV_ORB, "HVO_STAGE_ORB", "HVO_STAGE_ORB" };
 // the guided frame-to-frame matching of the stream
 const FrameNeed need_guided_points = { "guided search", HVO_STAGE_ORB, false, 0, "", true, false, FV_N_KP, FV_EV_ORB, "HVO_STAGE_ORB", "HVO_STAGE_ORB" };
 const FrameNeed need_line_match    = { "line matching", 0, true, 0, "", false, false, FV_N_KL, FV_EV_LSD, k_lines, k_lines };

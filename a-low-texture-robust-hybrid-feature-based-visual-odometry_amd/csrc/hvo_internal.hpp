@@ -162,7 +162,8 @@ struct hvo_ctx {
     hipEvent_t bow_ev[4] = { nullptr, nullptr, nullptr, nullptr }; float bow_ms[2] = { 0.f, 0.f }; bool bow_ev_on[2] = { false, false };   // bow.hip: events around the last calls' launches
     hipEvent_t pnp_ev[3] = { nullptr, nullptr, nullptr }; float pnp_ms[2] = { 0.f, 0.f }; bool pnp_ev_on = false;   // pnp.hip: events around the last call's two kernel groups
     hipEvent_t kfs_ev[3] = { nullptr, nullptr, nullptr };   // kf_search.hip: events around the last call's prologue and its searches
-    BowState bow_batch, bow_call;          // bow.hip: the resident batch's bag of words (cleared by hvo_batch_run), the host-array form's block
+    hipEvent_t fuse_ev[4] = { nullptr, nullptr, nullptr, nullptr };   // fuse.hip: events around the last call's grid, projection and search kernels
+    BowState bow_batch, bow_call;         // bow.hip: the resident batch's bag of words (cleared by hvo_batch_run), the host-array form's block
     // opaque per-subsystem state (peac.hip / lsd.hip own these)
     void *peac = nullptr;
     void *lsd = nullptr;

@@ -47,11 +47,6 @@
 #define LP_MAXQ 16384             // points in view per call (SBP_MAXQ of match.hip)
 #define LP_MAXT 65535             // frame features (the search core's keys hold the feature in 16 bits)
 
-struct hvo_point_map : hvo_slot_map {
-    hvo_point_map() : hvo_slot_map("point map", "HVO_POINT_MAP_MAX_SLOTS", HVO_POINT_MAP_MAX_SLOTS, { { 4, 3 }, { 4, 3 }, { 4, 1 }, { 4, 1 }, { 32, 1 }, { 1, 1, SM_BAD } }) {}
-    enum { POS, NRM, MAXD, MIND, DESC };                         // pos, nrm, maxd, mind: floats; desc: 32 bytes packed; then the flags
-};
-
 extern "C" {
 
 hvo_point_map *hvo_point_map_create(int device, int slots)

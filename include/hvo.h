@@ -1248,6 +1248,85 @@ int hvo_search_by_projection_keyframe(hvo_ctx *ctx, const hvo_camera *cam, const
 int hvo_stream_search_by_projection_keyframe(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_kf_search_params *params,
                                              int n_kf, const hvo_kf_search_candidate *candidates, hvo_kf_search_result *results);
 
+/* ---- ORBmatcher::Fuse(KeyFrame *, const vector<MapPoint *> &, float th) (src/ORBmatcher.cc:838-994; csrc/fuse.hip) ----
+ * The matcher of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:1567-1696): every map point of a list that is not bad and not already
+ * in the key frame is projected into the key frame, gated (depth sign, image, distance range, viewing angle), given a predicted level and
+ * compared with the key frame's features in a window of th * mvScaleFactors[level] within the levels [level - 1, level] under a chi-square
+ * test on the reprojection error (7.8 with mvuRight, 5.99 without, scaled by mvInvLevelSigma2).  Fuse has NO occupancy: an entry's best
+ * feature does not depend on what other entries took, so all (key frame, entry) pairs of n_kf key frames are searched in one launch.
+ * The pointer part stays with the caller, who walks fused_entry / fused_idx in order and re-tests `isBad() || IsInKeyFrame(pKF)` per entry
+ * (it only ever turns from "not skipped" to "skipped" during the walk): Replace against AddObservation + AddMapPoint.
+ *
+ * Readings a caller can observe (DESIGN.md section 7 has all of them): Rcw P + tcw and mOw as for the point map; `z < 0.0f` as written
+ * (z == 0 and -0.0 pass and divide); invz = 1 / z is ONE FLOAT division (the text has the int literal 1); u = fx * (X * invz) + cx, two
+ * float products; IsInImage is u >= minX && u < maxX && v >= minY && v < maxY, so a NaN projection FAILS; ur = u - bf * invz; cv::norm is
+ * the square root of the double sum of squares stored to float; PO.dot(Pn) accumulates in double and is compared with the double
+ * 0.5 * dist3D; PredictScale as in the key-frame search; the radius is a float product; GetFeaturesInArea's cell range is applied as
+ * written IN ADDITION to the two fabs tests; e2 is float, left to right, e2 * mvInvLevelSigma2[octave] a float product compared with the
+ * double literals 7.8 / 5.99 (mvuRight >= 0 chooses; a NaN there takes the mono gate).  A feature whose octave is negative is in no band.
+ * The strict `dist < bestDist` keeps the first of equal distances in GetFeaturesInArea's visiting order: cell column, then cell row, then
+ * feature index.  No arithmetic is contracted. */
+typedef struct {               /* the key-frame side on host arrays */
+    int32_t n;                 /* pKF->N */
+    const hvo_keypoint *kp_un; /* mvKeysUn: x, y, octave are read */
+    const float   *uright;     /* mvuRight; NULL: every feature takes the mono gate */
+    const uint8_t *desc;       /* n x 32, mDescriptors */
+    float Tcw[12];             /* rows 0..2 of the key frame's pose, row-major 3 x 4 */
+    const uint8_t *skip;       /* one byte per map entry FOR THIS key frame: !pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF); NULL: none */
+} hvo_fuse_keyframe;
+typedef struct {               /* a map side on host arrays: vpMapPoints */
+    int32_t n;
+    const float   *pos, *normal;          /* n x 3 each: GetWorldPos(), GetNormal() (CV_32F) */
+    const float   *max_dist, *min_dist;   /* RAW mfMaxDistance / mfMinDistance; the call applies 1.2f / 0.8f, as in hvo_point_map */
+    const uint8_t *desc;                  /* n x 32, GetDescriptor() */
+} hvo_fuse_map;
+typedef struct {
+    float th;                  /* 3 */
+    int32_t th_low;            /* TH_LOW (50); above 255 is refused (bestDist starts at 256: the reference would accept bestIdx = -1) */
+    float log_scale_factor;    /* pKF->mfLogScaleFactor */
+    int32_t n_levels;          /* pKF->mnScaleLevels, 1 .. 16; mvScaleFactors and mvInvLevelSigma2 are the context's */
+    float bf;                  /* pKF->mbf */
+    float bounds[4];           /* mnMinX, mnMaxX, mnMinY, mnMaxY (host-array form; the stream form takes the bounds of its feature grid) */
+    int32_t map_per_keyframe;  /* hvo_fuse_points: 0 = map_side[0] is shared by all key frames (uploaded once: the first loop of
+                                * SearchInNeighbors); 1 = key frame j is searched with map_side[j] */
+} hvo_fuse_params;
+/* gate codes, in the reference's order */
+#define HVO_FUSE_GATE_SEARCHED     0   /* also an entry whose area holds no feature: best_idx stays -1 */
+#define HVO_FUSE_GATE_SKIP         1   /* skip[i], or a bad slot */
+#define HVO_FUSE_GATE_BEHIND       2   /* z < 0.0f */
+#define HVO_FUSE_GATE_OUT_OF_IMAGE 3   /* !IsInImage(u, v) */
+#define HVO_FUSE_GATE_DIST_MIN     4   /* dist3D < 0.8f * mfMinDistance */
+#define HVO_FUSE_GATE_DIST_MAX     5   /* dist3D > 1.2f * mfMaxDistance */
+#define HVO_FUSE_GATE_VIEW_ANGLE   6   /* PO.dot(Pn) < 0.5 * dist3D */
+typedef struct {               /* per key frame; every pointer but best_idx may be NULL.  n = the entries of this key frame's map side */
+    int32_t *best_idx, *best_dist;   /* n: bestIdx / bestDist after the loop (-1 / 256 where no candidate survived or the entry was not searched) */
+    int8_t  *gate;                   /* n */
+    int32_t *level;                  /* n: nPredictedLevel; -1 where the entry was not searched */
+    float   *proj;                   /* n x 3: u, v, ur as far as the reference computed them (skip, behind: 0, 0, 0; out of image: u, v, 0) */
+    int32_t *fused_entry, *fused_idx;   /* room for n each: the entries with best_dist <= th_low in ascending order and their features:
+                                         * the list the caller walks */
+    int32_t n_fused, n_searched, status; float kernel_ms[3];   /* entries in the list; entries with gate 0; device time of the whole call's
+                                                                * grid, projection and search (with the compaction) kernels */
+} hvo_fuse_result;
+/* On host arrays: n_kf key frames against map_side[0] (shared) or map_side[j].  cam: fx, fy, cx, cy are read.  Limits: 65535 features per
+ * key frame (the search key holds the candidate's rank in 16 bits), 1048576 entries per key frame (HVO_ERR_UNSUPPORTED beyond); th_low > 255,
+ * n_levels outside 1 .. 16, empty bounds or a missing array are HVO_ERR_INVALID_ARG.  Every refusal is whole: nothing is written and
+ * hvo_last_error says why.  n == 0 on either side is HVO_OK with no match.  One synchronisation per call. */
+int hvo_fuse_points(hvo_ctx *ctx, const hvo_camera *cam, const hvo_fuse_params *params, const hvo_fuse_map *map_side,
+                    int n_kf, const hvo_fuse_keyframe *keyframes, hvo_fuse_result *results);
+/* The map side as n slots of a resident point map, shared by all key frames: the map's device arrays are read in place, only the slot list
+ * and the skip bytes go up.  A bad slot counts as skipped; a slot outside the map is HVO_ERR_INVALID_ARG (whole).  The map must live on the
+ * context's device.  The refusal's text is in hvo_last_error and in hvo_point_map_last_error. */
+int hvo_fuse_points_slots(hvo_ctx *ctx, hvo_point_map *m, int n, const int32_t *slots, const hvo_camera *cam, const hvo_fuse_params *params,
+                          int n_kf, const hvo_fuse_keyframe *keyframes, hvo_fuse_result *results);
+/* The resident frame `cur` is the one key frame, under Tcw: Fuse(mpCurrentKeyFrame, vpFuseCandidates), valid while the frame is in the
+ * ring.  Its undistorted key points, mvuRight (when it was submitted with depth and the stream's bf is > 0) and descriptors are read where
+ * the stages left them; the bounds are its grid's (params->bounds is ignored).  The map side is map_side (host arrays) or, when map_side is
+ * NULL, n slots of m.  skip: one byte per entry or NULL.  The stream must run HVO_STAGE_ORB: otherwise HVO_ERR_INVALID_ARG with
+ * hvo_stream_last_error set.  The result is the host-array form's on the downloaded frame, bit for bit. */
+int hvo_stream_fuse_points(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_fuse_params *params, const float Tcw[12], const uint8_t *skip,
+                           const hvo_fuse_map *map_side, hvo_point_map *m, int n, const int32_t *slots, hvo_fuse_result *result);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer. Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

@@ -257,9 +257,38 @@ struct KeyFrameSide {
 // that now holds it (-1: none) -- CurrentFrame.mvpMapPoints[i2] = vpMPs[feature_kf[i2]] where feature_kf[i2] >= 0
 struct KeyFrameMatches { std::vector<int> match_idx, match_dist, feature_kf; int n_searched = 0; float kernel_ms[2] = { 0.f, 0.f }; };
 
+// What Fuse(pKF, vpMapPoints, th) leaves per key frame: bestIdx / bestDist per entry and the entries with bestDist <= TH_LOW in ascending
+// order with their features.  The caller walks fused_entry / fused_idx in order, re-tests `pMP->isBad() || pMP->IsInKeyFrame(pKF)` per entry
+// and does Replace (by observation count) or AddObservation + AddMapPoint: the pointer part of ORBmatcher.cc:967-990.
+struct FuseMatches {
+    std::vector<int> best_idx, best_dist, fused_entry, fused_idx; std::vector<int8_t> gate;
+    int n_fused = 0, n_searched = 0; float kernel_ms[3] = { 0.f, 0.f, 0.f };
+};
+
 class ORBmatcher {
 public:
     static const int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;       // ORBmatcher.cc:37-39
+    // Fuse(pKF, vpMapPoints, th) (ORBmatcher.cc:838-994) for n_kf key frames on host arrays against ONE map side (the first loop of
+    // LocalMapping::SearchInNeighbors, LocalMapping.cc:1596-1603) in one device call.  kf[j].skip: a byte per entry, !pMP || isBad() ||
+    // IsInKeyFrame(pKF_j).  Returns the sum of nFused's upper bound (the fused lists' lengths); res gets one FuseMatches per key frame.
+    int Fuse(const hvo_camera &cam, const float bounds[4], float bf, const hvo_fuse_map &vpMapPoints, int n_kf, const hvo_fuse_keyframe *kf,
+             std::vector<FuseMatches> &res, float th = 3.0f, float logScaleFactor = 0.18232161f, int nLevels = 8) const
+    {
+        hvo_fuse_params p = fuse_params(bf, th, logScaleFactor, nLevels);
+        for (int k = 0; k < 4; k++) p.bounds[k] = bounds[k];
+        std::vector<hvo_fuse_result> r((size_t)std::max(n_kf, 1));
+        res.assign((size_t)std::max(n_kf, 0), FuseMatches());
+        for (int j = 0; j < n_kf; j++) r[j] = fuse_result(res[j], vpMapPoints.n);
+        check(hvo_fuse_points(ctx_, &cam, &p, &vpMapPoints, n_kf, kf, r.data()), "hvo_fuse_points");
+        int total = 0;
+        for (int j = 0; j < n_kf; j++) total += fuse_take(res[j], r[j]);
+        return total;
+    }
+    // Fuse(mpCurrentKeyFrame, vpFuseCandidates) (LocalMapping.cc:1627) with the resident frame `cur` as the key frame under Tcw: its key
+    // points, mvuRight and descriptors stay on the device.  The map side is host arrays, or (vpMapPoints == nullptr) n slots of a resident
+    // point map.  Valid while the frame is in the ring.
+    int Fuse(FrameStream &fs, int64_t cur, const hvo_camera &cam, float bf, const float Tcw[12], const uint8_t *skip, const hvo_fuse_map *vpMapPoints,
+             hvo_point_map *map, int n_slots, const int32_t *slots, FuseMatches &res, float th = 3.0f, float logScaleFactor = 0.18232161f, int nLevels = 8) const;
     // SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:1499-1628), Relocalization's refinement, on the resident
     // frame `cur` under the pose Tcw (rows 0..2 of mTcw): nothing of the frame comes down.  occupied: a byte per frame feature,
     // mvpMapPoints[i2] != NULL at entry (n_features of them).  Returns nmatches; see hvo.h for the three things that set this search apart.
@@ -348,6 +377,27 @@ public:
         return r.n_matches;
     }
 private:
+    static hvo_fuse_params fuse_params(float bf, float th, float logScaleFactor, int nLevels)
+    {
+        hvo_fuse_params p = hvo_fuse_params();
+        p.th = th; p.th_low = TH_LOW; p.log_scale_factor = logScaleFactor; p.n_levels = nLevels; p.bf = bf;
+        return p;
+    }
+    static hvo_fuse_result fuse_result(FuseMatches &m, int n)
+    {
+        const size_t k = (size_t)std::max(n, 1);
+        m.best_idx.assign(k, -1); m.best_dist.assign(k, 256); m.fused_entry.assign(k, -1); m.fused_idx.assign(k, -1); m.gate.assign(k, 0);
+        hvo_fuse_result r = hvo_fuse_result();
+        r.best_idx = m.best_idx.data(); r.best_dist = m.best_dist.data(); r.fused_entry = m.fused_entry.data(); r.fused_idx = m.fused_idx.data(); r.gate = m.gate.data();
+        return r;
+    }
+    static int fuse_take(FuseMatches &m, const hvo_fuse_result &r)
+    {
+        m.n_fused = r.n_fused; m.n_searched = r.n_searched;
+        for (int k = 0; k < 3; k++) m.kernel_ms[k] = r.kernel_ms[k];
+        m.fused_entry.resize((size_t)r.n_fused); m.fused_idx.resize((size_t)r.n_fused);
+        return r.n_fused;
+    }
     static void kf_search_fill(const float Tcw[12], const KeyFrameSide &kf, const uint8_t *skip, const uint8_t *occupied, int n_features, float th, int ORBdist,
                                bool checkOrientation, float logScaleFactor, int nLevels, KeyFrameMatches &res, hvo_kf_search_candidate &c,
                                hvo_kf_search_params &p, hvo_kf_search_result &r)
@@ -930,6 +980,15 @@ inline int ORBmatcher::SearchByProjection(FrameStream &fs, int64_t cur, const hv
     check(hvo_stream_search_by_projection_keyframe(fs.get(), cur, &cam, &p, 1, &c, &r), "hvo_stream_search_by_projection_keyframe");
     res.n_searched = r.n_searched; res.kernel_ms[0] = r.kernel_ms[0]; res.kernel_ms[1] = r.kernel_ms[1];
     return r.n_matches;
+}
+
+inline int ORBmatcher::Fuse(FrameStream &fs, int64_t cur, const hvo_camera &cam, float bf, const float Tcw[12], const uint8_t *skip, const hvo_fuse_map *vpMapPoints,
+                            hvo_point_map *map, int n_slots, const int32_t *slots, FuseMatches &res, float th, float logScaleFactor, int nLevels) const
+{
+    hvo_fuse_params p = fuse_params(bf, th, logScaleFactor, nLevels);
+    hvo_fuse_result r = fuse_result(res, vpMapPoints ? vpMapPoints->n : n_slots);
+    check(hvo_stream_fuse_points(fs.get(), cur, &cam, &p, Tcw, skip, vpMapPoints, map, n_slots, slots, &r), "hvo_stream_fuse_points");
+    return fuse_take(res, r);
 }
 
 // Optimizer (include/Optimizer.h, src/Optimizer.cc:590-1478): PoseOptimization on the mirror's frame handle.  The map side (one row per feature:
