@@ -94,6 +94,7 @@ EXPORTS = [
     "hvo_pnp_default_params", "hvo_pnp_ransac", "hvo_stream_pnp_ransac", "hvo_pnp_last_kernel_ms", "hvo_stream_pnp_last_kernel_ms",
     "hvo_search_by_projection_keyframe", "hvo_stream_search_by_projection_keyframe",
     "hvo_fuse_points", "hvo_fuse_points_slots", "hvo_stream_fuse_points",
+    "hvo_create_new_map_points", "hvo_stream_create_new_map_points",
     "hvo_update_map_planes", "hvo_stream_update_map_planes", "hvo_plane_map_get_points", "hvo_plane_update_transform",
 ]
 
@@ -808,6 +809,85 @@ def _fuse_finish(R, keep, ok):
     return out
 
 
+NP_MAX_FEATURES, NP_MAX_NEIGHBOURS = 4096, 64
+NP_OUTCOMES = ("created", "occupied", "no match", "low parallax", "w == 0", "no depth", "behind 1", "behind 2", "reproj 1", "reproj 2", "zero dist", "scale")
+NP_UNTOUCHED = -7           # what the outputs hold before the call: a refusal leaves them so
+
+
+class NpKeyframe(C.Structure):
+    """hvo_np_keyframe: the current key frame, and each neighbour"""
+    _fields_ = [("n", C.c_int32), ("kp_un", C.c_void_p), ("kp", C.c_void_p), ("uright", C.c_void_p), ("depth", C.c_void_p), ("desc", C.c_void_p),
+                ("node_id", C.c_void_p), ("has_map_point", C.c_void_p), ("Tcw", C.c_float * 12), ("mb", C.c_float), ("skip", C.c_uint8)]
+
+
+class NpParams(C.Structure):
+    """hvo_np_params"""
+    _fields_ = [("th_low", C.c_int32), ("n_levels", C.c_int32), ("scale_factor", C.c_float), ("bf", C.c_float)]
+
+
+class NpResult(C.Structure):
+    """hvo_np_result"""
+    _fields_ = [("match_idx2", C.c_void_p), ("match_dist", C.c_void_p), ("outcome", C.c_void_p), ("branch", C.c_void_p), ("x3d", C.c_void_p),
+                ("created_idx1", C.c_void_p), ("created_idx2", C.c_void_p), ("n_created", C.c_int32), ("gate", C.c_int32), ("status", C.c_int32)]
+
+
+class NpSummary(C.Structure):
+    """hvo_np_summary"""
+    _fields_ = [("owner", C.c_void_p), ("n_new", C.c_int32), ("kernel_ms", C.c_float * 3)]
+
+
+assert C.sizeof(NpKeyframe) == 120 and C.sizeof(NpParams) == 16 and C.sizeof(NpResult) == 72 and C.sizeof(NpSummary) == 24
+
+
+def _np_keyframe(K, kf, resident=False):
+    """kf: dict of kp_un, kp (or None), uright, depth (both or None), desc, node_id, has_map_point, Tcw, mb, skip; a missing array stays NULL and
+    is the library's to refuse.  resident: only has_map_point, Tcw and mb are read"""
+    a = {}
+    get = lambda k: None if kf.get(k) is None else kf[k]
+    if not resident:
+        a["kp_un"] = None if get("kp_un") is None else np.ascontiguousarray(kf["kp_un"], KEYPOINT_DT)
+        n = K.n = int(kf["n"]) if "n" in kf else (len(a["kp_un"]) if a["kp_un"] is not None else 0)
+        a["kp"] = None if get("kp") is None else np.ascontiguousarray(kf["kp"], KEYPOINT_DT)
+        for k, dt in (("uright", np.float32), ("depth", np.float32), ("node_id", np.int32)):
+            a[k] = None if get(k) is None else np.ascontiguousarray(kf[k], dt).reshape(-1)
+        a["desc"] = None if get("desc") is None else np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32)
+    a["has_map_point"] = None if get("has_map_point") is None else np.ascontiguousarray(np.asarray(kf["has_map_point"]).astype(bool), np.uint8).reshape(-1)
+    for k, v in a.items(): setattr(K, k, v.ctypes.data if v is not None and v.size else None)
+    T = np.asarray(kf["Tcw"], np.float32).reshape(12)
+    for k in range(12): K.Tcw[k] = T[k]
+    K.mb = float(kf.get("mb", 0.0)); K.skip = 1 if kf.get("skip") else 0
+    return a
+
+
+def _np_args(n1, kfs, th_low, n_levels, scale_factor, bf):
+    nk = len(kfs); m = max(n1, 1)
+    K = (NpKeyframe * max(nk, 1))(); R = (NpResult * max(nk, 1))(); keep = []; outs = []
+    for j, kf in enumerate(kfs):
+        keep.append(_np_keyframe(K[j], kf))
+        o = dict(match_idx2=np.full(m, NP_UNTOUCHED, np.int32), match_dist=np.full(m, NP_UNTOUCHED, np.int32), outcome=np.full(m, NP_UNTOUCHED, np.int8),
+                 branch=np.full(m, NP_UNTOUCHED, np.int8), x3d=np.full((m, 3), NP_UNTOUCHED, np.float32),
+                 created_idx1=np.full(m, NP_UNTOUCHED, np.int32), created_idx2=np.full(m, NP_UNTOUCHED, np.int32))
+        for k in o: setattr(R[j], k, o[k].ctypes.data)
+        R[j].n_created = R[j].gate = R[j].status = NP_UNTOUCHED
+        outs.append(o)
+    S = NpSummary(); owner = np.full(m, NP_UNTOUCHED, np.int32)
+    S.owner = owner.ctypes.data; S.n_new = NP_UNTOUCHED
+    P = NpParams(); P.th_low = th_low; P.n_levels = n_levels; P.scale_factor = scale_factor; P.bf = bf
+    return K, R, S, P, owner, outs, keep
+
+
+def _np_finish(n1, R, S, owner, outs, ok):
+    """(one dict per neighbour, the summary); after a refusal (ok False) every array is returned whole, as the call left it"""
+    res = []
+    for j, o in enumerate(outs):
+        d = dict(n_created=R[j].n_created, gate=R[j].gate, status=R[j].status)
+        for k in ("match_idx2", "match_dist", "outcome", "branch", "x3d"): d[k] = o[k][:n1] if ok else o[k]
+        nc = max(0, min(R[j].n_created, n1)) if ok else len(o["created_idx1"])
+        d["created_idx1"] = o["created_idx1"][:nc]; d["created_idx2"] = o["created_idx2"][:nc]
+        res.append(d)
+    return res, dict(owner=owner[:n1] if ok else owner, n_new=S.n_new, kernel_ms=tuple(S.kernel_ms))
+
+
 def line_struct_params(**kw):
     """the reference's values (hvo_line_struct_default_params) with the given fields replaced (mode, row_rule, ...)"""
     p = LineStructParams()
@@ -1076,6 +1156,10 @@ def lib():
         L.hvo_fuse_points.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.POINTER(FuseMap), C.c_int, C.POINTER(FuseKeyframe), C.POINTER(FuseResult)]
         L.hvo_fuse_points_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.c_int, C.POINTER(FuseKeyframe),
                                             C.POINTER(FuseResult)]
+        L.hvo_create_new_map_points.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(NpParams), C.POINTER(NpKeyframe), C.c_int, C.POINTER(NpKeyframe),
+                                                C.POINTER(NpResult), C.POINTER(NpSummary)]
+        L.hvo_stream_create_new_map_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(PoseCamera), C.POINTER(NpParams), C.c_void_p, C.c_void_p, C.c_int,
+                                                       C.POINTER(NpKeyframe), C.POINTER(NpResult), C.POINTER(NpSummary)]
         L.hvo_stream_fuse_points.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.c_void_p, C.c_void_p, C.POINTER(FuseMap), C.c_void_p,
                                              C.c_int, C.c_void_p, C.POINTER(FuseResult)]
         L.hvo_stream_pnp_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
@@ -2033,6 +2117,23 @@ class Context:
         self._chk(rc, "fuse_points_slots")
         return _fuse_finish(R, rk, True)
 
+    def create_new_map_points(self, cam, cur, kfs, th_low=50, n_levels=8, scale_factor=1.2, check=True):
+        """LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:335-580): the epipolar search and the triangulation of the current key frame
+        `cur` against every neighbour of kfs in one call.  cur and each neighbour: dict(kp_un, kp or None, uright, depth (both or None), desc,
+        node_id, has_map_point, Tcw, mb; a neighbour also skip).  cam: fx, fy, cx, cy, bf.  Returns (one dict per neighbour: match_idx2, match_dist,
+        outcome (NP_OUTCOMES), branch, x3d, created_idx1, created_idx2 (the list the caller walks), n_created, gate, status; the summary:
+        owner, n_new, kernel_ms).  check=False: (return code, message, the two) instead of an exception; a refused call leaves every output
+        at NP_UNTOUCHED."""
+        ck = NpKeyframe(); keep1 = _np_keyframe(ck, cur); n1 = ck.n
+        K, R, S, P, owner, outs, keep = _np_args(n1, kfs, th_low, n_levels, scale_factor, float(cam[4]))
+        cm = _pose_cam(cam)
+        rc = lib().hvo_create_new_map_points(self.h, C.byref(cm), C.byref(P), C.byref(ck), len(kfs), K, R, C.byref(S))
+        del keep1, keep
+        if not check:
+            return (rc, lib().hvo_last_error(self.h).decode()) + _np_finish(n1, R, S, owner, outs, rc == HVO_OK)
+        self._chk(rc, "create_new_map_points")
+        return _np_finish(n1, R, S, owner, outs, True)
+
     def pnp_last_kernel_ms(self):
         """(hypothesis kernels, refine kernels): device ms of the last pnp_ransac"""
         ms = np.zeros(2, np.float32)
@@ -2546,6 +2647,23 @@ class Stream:
         ms = np.zeros(2, np.float32)
         self._chk(lib().hvo_stream_pnp_last_kernel_ms(self.h, cur, _p(ms)), "stream_pnp_last_kernel_ms")
         return float(ms[0]), float(ms[1])
+
+    def create_new_map_points(self, cur, voc, cam, Tcw, has_map_point, kfs, th_low=50, n_levels=8, scale_factor=1.2, check=True):
+        """LocalMapping::CreateNewMapPoints with the resident frame `cur` as the current key frame under Tcw (needs STAGE_ORB and the bag of words
+        compute_bow left on it for voc): key points, mvuRight, mvDepth, descriptors and node ids are read where the stages left them; only the
+        occupancy bytes (one per feature of the frame), the pose and the neighbours go up.  cam: fx, fy, cx, cy, bf, b (the current key frame's
+        mb).  Returns what Context.create_new_map_points returns."""
+        hm = np.asarray(has_map_point).astype(bool).reshape(-1); n1 = len(hm)
+        has = np.zeros(max(n1, self.kp_cap, 1), np.uint8); has[:n1] = hm          # (a frame with more features than bytes given reads zeros, not past the end)
+        K, R, S, P, owner, outs, keep = _np_args(max(n1, self.kp_cap), kfs, th_low, n_levels, scale_factor, float(cam[4]))
+        cm = _pose_cam(cam)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12)
+        rc = lib().hvo_stream_create_new_map_points(self.h, cur, voc.h, C.byref(cm), C.byref(P), T.ctypes.data, has.ctypes.data, len(kfs), K, R, C.byref(S))
+        del keep
+        if not check:
+            return (rc, lib().hvo_stream_last_error(self.h).decode()) + _np_finish(n1, R, S, owner, outs, rc == HVO_OK)
+        self._chk(rc, "stream_create_new_map_points")
+        return _np_finish(n1, R, S, owner, outs, True)
 
     def search_by_bow(self, cur, voc, kfs, nnratio=0.7, check_orientation=True, th_low=50):
         """SearchByBoW of the key frames kfs (dicts of desc, node_id, has_map_point, angle) against the resident frame `cur`, which holds its bag

@@ -272,6 +272,13 @@ __global__ __launch_bounds__(256) void k_bow_csr(BowSideDev K)
     if (tid == 0) K.n_rows[j] = nr;
 }
 
+void bow_csr_enqueue(hipStream_t st, int count, int cap, const int *node, const int *n, int *fv_node, int *fv_start, int *fv_idx, int *n_rows)
+{
+    BowSideDev K; memset(&K, 0, sizeof(K));
+    K.node = node; K.n = n; K.cap = cap; K.fv_node = fv_node; K.fv_start = fv_start; K.fv_idx = fv_idx; K.n_rows = n_rows;
+    hipLaunchKernelGGL(k_bow_csr, dim3(count), dim3(256), 0, st, K);
+}
+
 struct BowSearchDev {
     BowSideDev kf;                                             // key frame j
     const uint8_t *f_desc; const float *f_angle; int f_angle_step; const int *f_n; int f_cap;

@@ -18,6 +18,7 @@ const FrameNeed need_bow           = { "bag of words", HVO_STAGE_ORB, false, 0, 
 const FrameNeed need_bow_search    = { "search by bag of words", 0, false, 0, "", false, false, FV_N_KP, FV_EV_ORB, "", "" };     // (the frame's kept bag of words is the caller's check)
 const FrameNeed need_pnp           = { "pnp", HVO_STAGE_ORB, false, 0, "", false, false, FV_N_KP, FV_EV_ORB, "HVO_STAGE_ORB", "HVO_STAGE_ORB" };
 const FrameNeed need_kf_search     = { "key-frame search", HVO_STAGE_ORB, false, 0, "", false, false, FV_N_KP, FV_EV_ORB, "HVO_STAGE_ORB", "HVO_STAGE_ORB" };
+const FrameNeed need_new_points    = { "create new map points", HVO_STAGE_ORB, false, 0, "", true, false, FV_N_KP, FV_EV_ORB, "HVO_STAGE_ORB", "HVO_STAGE_ORB" };
 const FrameNeed need_fuse          = { "fuse", HVO_STAGE_ORB, false, 0, "", true, false, FV_N_KP, FV_EV_ORB, "HVO_STAGE_ORB", "HVO_STAGE_ORB" };
 // the guided frame-to-frame matching of the stream
 const FrameNeed need_guided_points = { "guided search", HVO_STAGE_ORB, false, 0, "", true, false, FV_N_KP, FV_EV_ORB, "HVO_STAGE_ORB", "HVO_STAGE_ORB" };
@@ -122,7 +123,7 @@ int stream_view(hvo_stream *s, int64_t ticket, const FrameNeed &nd, hipStream_t 
     memset(&v, 0, sizeof(v));
     const OrbPlan &O = B->ctx->orb; const TailLayout &T = s->tl;
     v.ctx = B->ctx; v.n_kp = v.n_kl = -1;
-    v.kp = O.d_kp; v.kp_un = B->d_kp_un; v.uright = (B->had_depth && s->sp.bf > 0) ? B->d_uright : nullptr; v.desc = O.d_desc; v.d_nkp = O.d_nkp; v.kp_cap = s->kp_cap;
+    v.kp = O.d_kp; v.kp_un = B->d_kp_un; v.uright = (B->had_depth && s->sp.bf > 0) ? B->d_uright : nullptr; v.zdepth = v.uright ? B->d_zdepth : nullptr; v.desc = O.d_desc; v.d_nkp = O.d_nkp; v.kp_cap = s->kp_cap;
     v.kl = B->lv.d_kl; v.fn = B->lv.d_fn; v.ldesc = B->lv.d_desc; v.d_nkl = B->lv.d_nkl; v.nfeat = s->nfeat;
     if (B->d_tail) {
         v.l3d = (hvo_line3d *)(B->d_tail + T.lines3d); v.pclouds = (const hvo_plane_cloud *)(B->d_tail + T.pclouds); v.normals = (const hvo_surface_normal *)(B->d_tail + T.normals);

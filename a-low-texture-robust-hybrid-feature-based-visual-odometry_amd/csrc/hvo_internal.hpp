@@ -163,6 +163,7 @@ struct hvo_ctx {
     hipEvent_t pnp_ev[3] = { nullptr, nullptr, nullptr }; float pnp_ms[2] = { 0.f, 0.f }; bool pnp_ev_on = false;   // pnp.hip: events around the last call's two kernel groups
     hipEvent_t kfs_ev[3] = { nullptr, nullptr, nullptr };   // kf_search.hip: events around the last call's prologue and its searches
     hipEvent_t fuse_ev[4] = { nullptr, nullptr, nullptr, nullptr };   // fuse.hip: events around the last call's grid, projection and search kernels
+    hipEvent_t np_ev[4] = { nullptr, nullptr, nullptr, nullptr };     // new_points.hip: events around the last call's search, triangulation and resolve kernels
     BowState bow_batch, bow_call;         // bow.hip: the resident batch's bag of words (cleared by hvo_batch_run), the host-array form's block
     // opaque per-subsystem state (peac.hip / lsd.hip own these)
     void *peac = nullptr;
@@ -497,6 +498,9 @@ struct BowLayout { int cap; size_t counts, word_id, node_id, flag, weight, bow_w
 void bow_layout(int cap, BowLayout &L);
 void bow_state_free(BowState *b);
 int bow_voc_device(const hvo_vocabulary *v);
+// k_bow_csr for `count` sides of `cap` features each on st: side j's node ids at node + j * cap, its count at n[j]; rows at fv_node + j * cap,
+// fv_start + j * (cap + 1), fv_idx + j * cap, their number at n_rows[j].  cap <= HVO_BOW_MAXN.  A launch failure shows in the caller's hipGetLastError
+void bow_csr_enqueue(hipStream_t st, int count, int cap, const int *node, const int *n, int *fv_node, int *fv_start, int *fv_idx, int *n_rows);
 unsigned long long bow_voc_uid(const hvo_vocabulary *v);
 // ComputeBoW of nframes frames on stream st: fr[f]'s descriptors (desc, d_nkp and the host count n_kp; the frames lie a fixed stride apart:
 // one launch walks them), blocks of fr[0].kp_cap features kept in *keep.  may_keep: a call with the vocabulary and levelsup the kept result was

@@ -1327,6 +1327,84 @@ int hvo_fuse_points_slots(hvo_ctx *ctx, hvo_point_map *m, int n, const int32_t *
 int hvo_stream_fuse_points(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_fuse_params *params, const float Tcw[12], const uint8_t *skip,
                            const hvo_fuse_map *map_side, hvo_point_map *m, int n, const int32_t *slots, hvo_fuse_result *result);
 
+/* ---- LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:335-580; csrc/new_points.hip) ----
+ * The epipolar search (ComputeF12 :1779-1796, ORBmatcher::SearchForTriangulation src/ORBmatcher.cc:668-836 with CheckDistEpipolarLine
+ * :143-160) and the triangulation of every match (parallax test, 4 x 4 linear triangulation or KeyFrame::UnprojectStereo, two depth signs,
+ * two chi-square tests, scale consistency) of the current key frame against n_kf neighbours in one call with one synchronisation.
+ * SearchForTriangulation never sets vbMatched2 and runs without the rotation histogram here, so every (neighbour, idx1) pair is
+ * independent; the only coupling between neighbours is AddMapPoint(pMP, idx1), which makes later neighbours skip idx1.  The call evaluates
+ * every pair under the INITIAL occupancy and resolves the chain: the point at idx1 is created by the first neighbour, in list order, whose
+ * match passes every gate.  A caller that leaves after neighbour i (`if(i>0 && CheckNewKeyFrames()) return;`) uses the lists of neighbours
+ * 0 .. i: a prefix's results do not depend on what follows.  new MapPoint, AddObservation, AddMapPoint, ComputeDistinctiveDescriptors,
+ * UpdateNormalAndDepth and mlpRecentAddedMapPoints stay with the caller (examples/create_map_points.cpp).  Two idx1 may be given the same
+ * idx2 (the reference never marks vbMatched2): both are listed.
+ *
+ * Readings a caller can observe (csrc/new_points.hip and DESIGN.md section 7 have all of them; tests/new_points_ref.py is the definition):
+ * only + - * / sqrt in a written order, nothing contracted.  Among equal descriptor distances the LAST candidate in index order wins (the
+ * reference refuses `dist > bestDist`, not `>=`).  A feature whose octave is outside [0, n_levels) is refused for the pair.  The stereo
+ * parallax cos(2 atan2(mb / 2, d)) is evaluated as (d d - h h) / (d d + h h), h = mb / 2, in double.  cv::SVD::compute of the 4 x 4 A is a
+ * one-sided Jacobi iteration of exactly 12 sweeps in double on the float entries of A, its vector rounded to float once; bit parity with an OpenCV binary is NOT claimed.
+ * u2_r uses the current key frame's bf; UnprojectStereo reads the distorted mvKeys; z <= 0 fails, so a NaN passes on; den == 0 fails. */
+typedef struct {               /* the current key frame, and each neighbour */
+    int32_t n;                 /* N */
+    const hvo_keypoint *kp_un; /* mvKeysUn: x, y, octave are read */
+    const hvo_keypoint *kp;    /* mvKeys, which UnprojectStereo reads; NULL: kp_un */
+    const float   *uright, *depth;   /* mvuRight, mvDepth; NULL for both: every feature is monocular (one without the other is refused) */
+    const uint8_t *desc;       /* n x 32 */
+    const int32_t *node_id;    /* per feature, as hvo_*_compute_bow returns it; negative: the feature is in no node */
+    const uint8_t *has_map_point;    /* one byte per feature: GetMapPoint(idx) != NULL (bad points included, as in the text) */
+    float Tcw[12];             /* rows 0..2 of the pose, row-major 3 x 4 */
+    float mb;                  /* the key frame's mb: the stereo parallax, and `baseline < pKF2->mb` for a neighbour (0: never too short) */
+    uint8_t skip;              /* neighbours only: the caller's own pre-gate (the monocular median-depth ratio needs the map and stays on the host) */
+} hvo_np_keyframe;
+typedef struct {
+    int32_t th_low;            /* TH_LOW (50); above 255 is refused */
+    int32_t n_levels;          /* mnScaleLevels, 1 .. 16; mvScaleFactors and mvLevelSigma2 are the context's */
+    float scale_factor;        /* mfScaleFactor: ratioFactor = 1.5f * mfScaleFactor */
+    float bf;                  /* mpCurrentKeyFrame->mbf (both sides' u_r use it) */
+} hvo_np_params;
+/* outcome codes: the first `continue` the pair runs into, in the reference's order */
+#define HVO_NP_CREATED      0
+#define HVO_NP_OCCUPIED     1   /* idx1 holds a map point */
+#define HVO_NP_NO_MATCH     2   /* also: every pair of a neighbour that was not searched (gate != 0) */
+#define HVO_NP_LOW_PARALLAX 3   /* no stereo and very low parallax */
+#define HVO_NP_W_ZERO       4   /* x3D.at<float>(3) == 0 */
+#define HVO_NP_NO_DEPTH     5   /* UnprojectStereo returns an empty Mat for z <= 0: DEFINED here as a refusal of the pair */
+#define HVO_NP_BEHIND_1     6
+#define HVO_NP_BEHIND_2     7
+#define HVO_NP_REPROJ_1     8
+#define HVO_NP_REPROJ_2     9
+#define HVO_NP_ZERO_DIST    10
+#define HVO_NP_SCALE        11
+#define HVO_NP_GATE_SEARCHED 0
+#define HVO_NP_GATE_SKIP     1   /* the neighbour's skip byte */
+#define HVO_NP_GATE_BASELINE 2   /* baseline < mb */
+typedef struct {               /* per neighbour; n1 = the current key frame's feature count.  Every pointer but match_idx2 may be NULL */
+    int32_t *match_idx2, *match_dist;   /* n1: vMatches12 of SearchForTriangulation under the initial occupancy and its distance; -1 / 256 where none */
+    int8_t  *outcome, *branch;          /* n1: HVO_NP_*; 0 none, 1 linear triangulation, 2 UnprojectStereo of the current key frame, 3 of the neighbour */
+    float   *x3d;                       /* n1 x 3: the point as far as the reference computed it, zeros otherwise */
+    int32_t *created_idx1, *created_idx2;   /* room for n1 each: the points this neighbour creates after the chain is resolved, ascending idx1
+                                             * (the order of vMatchedPairs) */
+    int32_t n_created, gate, status;    /* gate: HVO_NP_GATE_* */
+} hvo_np_result;
+typedef struct {
+    int32_t *owner;            /* n1 (may be NULL): the neighbour that creates the point at idx1, or -1; neighbour j's list is {idx1 : owner == j} */
+    int32_t n_new;
+    float kernel_ms[3];        /* device time of the neighbours' rows + the search, of the triangulation, of resolve + compaction */
+} hvo_np_summary;
+/* On host arrays.  cam: fx, fy, cx, cy are read (one camera for both sides, as in the reference's data sets).  Limits: 4096 features per side
+ * (the rows are built by the bag-of-words kernel), 64 neighbours per call (HVO_ERR_UNSUPPORTED beyond); th_low > 255, n_levels outside
+ * 1 .. 16 or a missing array are HVO_ERR_INVALID_ARG.  Every refusal is whole: nothing is written and hvo_last_error says why.  n == 0 on
+ * either side or n_kf == 0 is HVO_OK with nothing created.  One synchronisation per call. */
+int hvo_create_new_map_points(hvo_ctx *ctx, const hvo_camera *cam, const hvo_np_params *params, const hvo_np_keyframe *current,
+                              int n_kf, const hvo_np_keyframe *neighbours, hvo_np_result *results, hvo_np_summary *summary);
+/* The resident frame `cur` is the current key frame under Tcw.  It must hold the bag of words hvo_stream_compute_bow left on it for voc:
+ * otherwise HVO_ERR_INVALID_ARG with hvo_stream_last_error set.  Key points, mvuRight, mvDepth, descriptors and node ids are read where the
+ * stages left them; only the occupancy bytes, the pose and the neighbours go up.  The current key frame's mb is cam->b.  The result is the
+ * host-array form's on the downloaded frame, bit for bit. */
+int hvo_stream_create_new_map_points(hvo_stream *s, int64_t cur, const hvo_vocabulary *voc, const hvo_camera *cam, const hvo_np_params *params, const float Tcw[12],
+                                     const uint8_t *has_map_point, int n_kf, const hvo_np_keyframe *neighbours, hvo_np_result *results, hvo_np_summary *summary);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer. Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

@@ -246,6 +246,7 @@ private:
 };
 
 class FrameStream;
+class ORBVocabulary;
 // A candidate key frame as SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) reads it: one entry per feature of
 // pKF->GetMapPointMatches() -- GetWorldPos(), the RAW mfMaxDistance / mfMinDistance, GetDescriptor(), mvKeysUn[i].angle.  What the call skips
 // (!pMP, isBad(), sAlreadyFound.count(pMP)) is the `skip` argument, a byte per entry; positions of skipped entries are not read.
@@ -408,6 +409,62 @@ private:
         p.th = th; p.orb_dist = ORBdist; p.check_orientation = checkOrientation ? 1 : 0; p.log_scale_factor = logScaleFactor; p.n_levels = nLevels;
         res.match_idx.assign((size_t)std::max(kf.n, 1), -1); res.match_dist.assign((size_t)std::max(kf.n, 1), 256); res.feature_kf.assign((size_t)std::max(n_features, 1), -1);
         r.match_idx = res.match_idx.data(); r.match_dist = res.match_dist.data(); r.feature_kf = res.feature_kf.data();
+    }
+    hvo_ctx *ctx_;
+};
+
+// What LocalMapping::CreateNewMapPoints leaves per neighbour: vMatches12 of SearchForTriangulation under the initial occupancy, the outcome of
+// every pair (HVO_NP_*), the branch, the point, and -- after the chain over the neighbours is resolved -- the points this neighbour creates in
+// ascending idx1.  The caller walks created_idx1 / created_idx2 in order: new MapPoint(x3d[idx1]), AddObservation on both sides, AddMapPoint,
+// ComputeDistinctiveDescriptors, UpdateNormalAndDepth, mlpRecentAddedMapPoints (LocalMapping.cc:562-577).
+struct NewMapPoints {
+    std::vector<int> match_idx2, match_dist, created_idx1, created_idx2; std::vector<int8_t> outcome, branch; std::vector<float> x3d;
+    int n_created = 0, gate = 0;
+};
+
+class LocalMapping {
+public:
+    explicit LocalMapping(hvo_ctx *ctx) : ctx_(ctx) {}
+    // CreateNewMapPoints (LocalMapping.cc:335-580) on host arrays: the current key frame against vpNeighKFs in list order, one device call.
+    // A caller that leaves after neighbour i (`if(i>0 && CheckNewKeyFrames()) return;`) walks res[0 .. i] only.  Returns nnew; owner (may be
+    // null) gets the neighbour that creates the point at idx1, or -1.
+    int CreateNewMapPoints(const hvo_camera &cam, const hvo_np_keyframe &current, int n_kf, const hvo_np_keyframe *vpNeighKFs, std::vector<NewMapPoints> &res,
+                           std::vector<int> *owner = nullptr, float mfScaleFactor = 1.2f, int nLevels = 8, float kernel_ms[3] = nullptr) const
+    {
+        hvo_np_params p = { ORBmatcher::TH_LOW, nLevels, mfScaleFactor, cam.bf };
+        std::vector<hvo_np_result> r; hvo_np_summary s = np_begin(current.n, n_kf, res, r, owner);
+        check(hvo_create_new_map_points(ctx_, &cam, &p, &current, n_kf, vpNeighKFs, r.data(), &s), "hvo_create_new_map_points");
+        return np_end(res, r, s, kernel_ms);
+    }
+    // the resident frame `cur` is the current key frame under Tcw and carries the bag of words ComputeBoW left on it for voc: its key points,
+    // mvuRight, mvDepth, descriptors and node ids stay on the device.  n_features: the frame's feature count (has_map_point has as many bytes)
+    int CreateNewMapPoints(FrameStream &fs, int64_t cur, const ORBVocabulary &voc, const hvo_camera &cam, const float Tcw[12], const uint8_t *has_map_point, int n_features,
+                           int n_kf, const hvo_np_keyframe *vpNeighKFs, std::vector<NewMapPoints> &res, std::vector<int> *owner = nullptr, float mfScaleFactor = 1.2f,
+                           int nLevels = 8, float kernel_ms[3] = nullptr) const;
+private:
+    static hvo_np_summary np_begin(int n1, int n_kf, std::vector<NewMapPoints> &res, std::vector<hvo_np_result> &r, std::vector<int> *owner)
+    {
+        const size_t k = (size_t)std::max(n1, 1);
+        res.assign((size_t)std::max(n_kf, 0), NewMapPoints()); r.assign((size_t)std::max(n_kf, 1), hvo_np_result());
+        for (int j = 0; j < n_kf; j++) {
+            NewMapPoints &m = res[j];
+            m.match_idx2.assign(k, -1); m.match_dist.assign(k, 256); m.created_idx1.assign(k, -1); m.created_idx2.assign(k, -1);
+            m.outcome.assign(k, HVO_NP_NO_MATCH); m.branch.assign(k, 0); m.x3d.assign(3 * k, 0.f);
+            r[j].match_idx2 = m.match_idx2.data(); r[j].match_dist = m.match_dist.data(); r[j].outcome = m.outcome.data(); r[j].branch = m.branch.data();
+            r[j].x3d = m.x3d.data(); r[j].created_idx1 = m.created_idx1.data(); r[j].created_idx2 = m.created_idx2.data();
+        }
+        hvo_np_summary s = hvo_np_summary();
+        if (owner) { owner->assign(k, -1); s.owner = owner->data(); }
+        return s;
+    }
+    static int np_end(std::vector<NewMapPoints> &res, const std::vector<hvo_np_result> &r, const hvo_np_summary &s, float kernel_ms[3])
+    {
+        for (size_t j = 0; j < res.size(); j++) {
+            res[j].n_created = r[j].n_created; res[j].gate = r[j].gate;
+            res[j].created_idx1.resize((size_t)r[j].n_created); res[j].created_idx2.resize((size_t)r[j].n_created);
+        }
+        if (kernel_ms) for (int k = 0; k < 3; k++) kernel_ms[k] = s.kernel_ms[k];
+        return s.n_new;
     }
     hvo_ctx *ctx_;
 };
@@ -989,6 +1046,16 @@ inline int ORBmatcher::Fuse(FrameStream &fs, int64_t cur, const hvo_camera &cam,
     hvo_fuse_result r = fuse_result(res, vpMapPoints ? vpMapPoints->n : n_slots);
     check(hvo_stream_fuse_points(fs.get(), cur, &cam, &p, Tcw, skip, vpMapPoints, map, n_slots, slots, &r), "hvo_stream_fuse_points");
     return fuse_take(res, r);
+}
+
+inline int LocalMapping::CreateNewMapPoints(FrameStream &fs, int64_t cur, const ORBVocabulary &voc, const hvo_camera &cam, const float Tcw[12], const uint8_t *has_map_point,
+                                            int n_features, int n_kf, const hvo_np_keyframe *vpNeighKFs, std::vector<NewMapPoints> &res, std::vector<int> *owner,
+                                            float mfScaleFactor, int nLevels, float kernel_ms[3]) const
+{
+    hvo_np_params p = { ORBmatcher::TH_LOW, nLevels, mfScaleFactor, cam.bf };
+    std::vector<hvo_np_result> r; hvo_np_summary s = np_begin(n_features, n_kf, res, r, owner);
+    check(hvo_stream_create_new_map_points(fs.get(), cur, voc.get(), &cam, &p, Tcw, has_map_point, n_kf, vpNeighKFs, r.data(), &s), "hvo_stream_create_new_map_points");
+    return np_end(res, r, s, kernel_ms);
 }
 
 // Optimizer (include/Optimizer.h, src/Optimizer.cc:590-1478): PoseOptimization on the mirror's frame handle.  The map side (one row per feature:

@@ -1,0 +1,34 @@
+"""The kernels of csrc/new_points.hip keep everything in registers: no scratch, no spills.  The 4 x 4 solve of k_np_triangulate holds A and V
+in private arrays whose every index is a compile-time constant once its loops unroll; an index the compiler cannot resolve would move them to
+scratch, and this test is what notices.  The figures are the compiler's own remarks (tools/kernel_resources.py); no assembly is inspected
+and no GPU is needed."""
+import importlib.util
+import os
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "a-low-texture-robust-hybrid-feature-based-visual-odometry_amd", "csrc")
+KERNELS = ("k_np_search", "k_np_triangulate", "k_np_resolve", "k_np_compact")
+
+
+@pytest.fixture(scope="module")
+def res():
+    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
+    kr = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kr)
+    if not kr.hipcc():
+        pytest.skip("hipcc not found")
+    return kr.resources(os.path.join(CSRC, "new_points.hip"))
+
+
+def test_every_kernel_is_reported(res):
+    assert sorted(res) == sorted(KERNELS), sorted(res)
+
+
+@pytest.mark.parametrize("name", KERNELS)
+def test_no_scratch_and_no_spills(res, name):
+    r = res[name]
+    print("%-18s VGPRs %3d allocated %3d SGPRs %3d spills s/v %d/%d scratch %d LDS %d" % (
+        name, r["vgprs"], r["alloc"], r["sgprs"], r["sgpr_spills"], r["vgpr_spills"], r["scratch"], r["lds"]))
+    assert r["scratch"] == 0 and r["sgpr_spills"] == 0 and r["vgpr_spills"] == 0, r
