@@ -689,6 +689,9 @@ int hvo_search_lines_by_projection(hvo_ctx *ctx, int nq, const float *q_xyxy, co
                                    int32_t *match_idx, int32_t *match_dist, int *n_matches)
 {
     if (!ctx || !match_idx || !match_dist || !n_matches || !bounds4 || nq < 0 || nt < 0) return HVO_ERR_INVALID_ARG;
+    if (nq > 0 && nt > 0 && (nt > 2048 || nq > 65535)) {           // the search's limits (line_track.inc), before any output is written
+        ctx->last_error = "guided line search: more than 2048 current lines, 65535 queries or 2^22 line grid items"; return HVO_ERR_UNSUPPORTED;
+    }
     *n_matches = 0;
     for (int i = 0; i < nq; i++) { match_idx[i] = -1; match_dist[i] = 256; }
     if (nq == 0 || nt == 0) return HVO_OK;
@@ -709,6 +712,7 @@ int hvo_search_lines_by_projection_map(hvo_ctx *ctx, int nq, const float *q_xyxy
                                        int32_t *match_idx, int32_t *match_dist, int *n_matches)
 {
     if (!ctx || !match_idx || !match_dist || !n_matches || !bounds4 || nq < 0 || nt < 0) return HVO_ERR_INVALID_ARG;
+    if (nt > 2048 || nq > LSBP_MAP_MAXQ) { ctx->last_error = match_lsbp_map_limit_text(nq, nt); return HVO_ERR_UNSUPPORTED; }   // before any output is written
     *n_matches = 0;
     for (int i = 0; i < nq; i++) { match_idx[i] = -1; match_dist[i] = 256; }
     if (nq > 0 && (!q_xyxy || !q_view_cos || !q_wvec || !q_desc)) return HVO_ERR_INVALID_ARG;

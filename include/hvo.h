@@ -158,7 +158,8 @@ int hvo_match_lines_geom(hvo_ctx *ctx, const uint8_t *d_last, const hvo_keyline 
                          int32_t *matches12, uint8_t *accepted, int *n_accepted);
 /* LSDmatcher::SearchByProjection(Cur, Last, th) core (reference src/LSDmatcher.cpp:561-662, Frame::GetFeaturesInAreaForLine src/Frame.cc:1557-1627)
  * on host arrays: q_kl[i] = LastFrame.mvKeylinesUn of query i; t_linefn (nt x 3) = mvKeyLineFunctions; cell_start / cell_items = the current frame's
- * line grid as hvo_assign_lines_to_grid returns it; at most 2048 current lines.  See hvo_stream_search_lines_by_projection. */
+ * line grid as hvo_assign_lines_to_grid returns it; at most 2048 current lines and 65535 queries (HVO_ERR_UNSUPPORTED: match_idx / match_dist /
+ * n_matches are left as they were).  See hvo_stream_search_lines_by_projection. */
 int hvo_search_lines_by_projection(hvo_ctx *ctx, int nq, const float *q_xyxy, const hvo_keyline *q_kl, const uint8_t *q_desc, const uint8_t *q_blocks,
                                    const hvo_keyline *t_kl, const double *t_linefn, const uint8_t *t_desc, const uint8_t *t_occupied, int nt,
                                    const int32_t *cell_start, const int32_t *cell_items, const float bounds4[4], float th,
@@ -217,7 +218,7 @@ int hvo_lines_3d(hvo_ctx *ctx, const hvo_keyline *kl, int n, const uint16_t *dep
  * lines already holding a map line with observations.  Best and second best distance; accepted if best <= 95 and not (same octave && best >
  * nn_ratio * second).  match_idx[i] = the current line or -1, match_dist[i] = its distance or 256; the reference assigns F.mvpMapLines[match_idx[i]]
  * in query order (a later acceptance overwrites a claim by a map line without observations).  At most 2048 current lines and 16384 queries
- * (HVO_ERR_UNSUPPORTED).  See hvo_stream_search_lines_by_projection_map. */
+ * (HVO_ERR_UNSUPPORTED: match_idx / match_dist / n_matches are left as they were).  See hvo_stream_search_lines_by_projection_map. */
 int hvo_search_lines_by_projection_map(hvo_ctx *ctx, int nq, const float *q_xyxy, const float *q_view_cos, const double *q_wvec,
                                        const uint8_t *q_desc, const uint8_t *q_blocks,
                                        const hvo_keyline *t_kl, const double *t_linefn, const hvo_line3d *t_l3d, const uint8_t *t_desc, const uint8_t *t_occupied, int nt,

@@ -1,6 +1,7 @@
 """The local-map line search, LSDmatcher::SearchByProjection(F, vpMapLines, eval_orient, th) (reference src/LSDmatcher.cpp:709-801): the
 C ABI declares and exports it, the C++ mirror's example compiles, and the CPU restatement (tests/local_map_lines_ref.py) gives the known
-answers of hand-built scenes for every detail that decides bits.  No GPU."""
+answers of hand-built scenes for every detail that decides bits.  No GPU here: tests/line_search_cases.py holds the scenes (Scene, desc_bits)
+and states each of them again as a named case, which tests/test_line_search_edges_gpu.py runs on the device."""
 import ctypes
 import os
 import re
@@ -10,9 +11,9 @@ import numpy as np
 
 from conftest import ROOT, PKG_DIR
 import local_map_lines_ref as ref
+from line_search_cases import Scene, desc_bits
 
 NAMES = ("hvo_search_lines_by_projection_map", "hvo_stream_search_lines_by_projection_map")
-BOUNDS = np.array([0.0, 640.0, 0.0, 480.0], np.float32)           # 10 x 10 pixel cells
 
 
 def test_header_library_and_binding_carry_the_call(hvo):
@@ -28,38 +29,6 @@ def test_header_library_and_binding_carry_the_call(hvo):
 def test_example_compiles():
     subprocess.check_call(["g++", "-std=c++14", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
                            "-fsyntax-only", os.path.join(ROOT, "examples", "local_map_lines.cpp")])
-
-
-def desc_bits(k, offset=0):
-    """a descriptor at Hamming distance k from the zero descriptor (bits offset .. offset + k - 1 set)"""
-    b = np.zeros(256, np.uint8); b[offset:offset + k] = 1
-    return np.packbits(b)
-
-
-class Scene:
-    """horizontal current lines from x = 100 to 200 at the given heights, each in the grid cell of its start point; line function y - y0;
-    3-D line A - B = (1, 0, 0)"""
-
-    def __init__(self, hvo, ys, octaves=None, descs=None):
-        n = len(ys)
-        self.kl = np.zeros(n, hvo.KEYLINE_DT)
-        self.kl["sx"] = 100.0; self.kl["ex"] = 200.0; self.kl["sy"] = ys; self.kl["ey"] = ys
-        self.kl["octave"] = 0 if octaves is None else octaves
-        self.fn = np.stack([np.zeros(n), np.ones(n), -np.asarray(ys, np.float64)], axis=1)
-        self.l3d = np.zeros(n, hvo.LINE3D_DT); self.l3d["A"][:, 0] = 1.0
-        self.desc = np.zeros((n, 32), np.uint8) if descs is None else np.asarray(descs, np.uint8)
-        cells = {}
-        for j, y in enumerate(ys):
-            cells.setdefault((10, int(y // 10)), []).append(j)
-        self.cs, self.ci = ref.grid_from_cells(cells)
-
-    def run(self, q_y, view_cos=1.0, wvec=(1.0, 0.0, 0.0), qdesc=None, blocks=None, occ=None, th=1.0, nn_ratio=0.95):
-        q_y = np.atleast_1d(np.asarray(q_y, np.float32)); nq = len(q_y)
-        q = np.stack([np.full(nq, 100.0), q_y, np.full(nq, 200.0), q_y], axis=1).astype(np.float32)
-        vc = np.broadcast_to(np.asarray(view_cos, np.float32), (nq,)).copy()
-        wv = np.broadcast_to(np.asarray(wvec, np.float64), (nq, 3)).copy()
-        qd = np.zeros((nq, 32), np.uint8) if qdesc is None else np.broadcast_to(np.asarray(qdesc, np.uint8), (nq, 32)).copy()
-        return ref.search_lines_by_projection_map(q, vc, wv, qd, blocks, self.kl, self.fn, self.l3d, self.desc, occ, self.cs, self.ci, BOUNDS, th, nn_ratio)
 
 
 def test_window_uses_the_0998_direction_gate(hvo):
