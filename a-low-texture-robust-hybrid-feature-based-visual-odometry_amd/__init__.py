@@ -1367,6 +1367,11 @@ class _SlotMap:
     def set_bad(self, slot, bad=True):
         self._chk(self._f("set_bad")(self.h, slot, 1 if bad else 0), "set_bad")
 
+    def debug_fill_scratch(self, byte):
+        """test door, not product API: the map's two call-scratch buffers, at the sizes they have, set to `byte`"""
+        f = getattr(lib(), "hvo_debug_%s_scratch" % self._c); f.argtypes = [C.c_void_p, C.c_int]; f.restype = C.c_int
+        self._chk(f(self.h, int(byte)), "debug_fill_scratch")
+
     def set_observed(self, slot, observed=True):
         self._chk(self._f("set_observed")(self.h, slot, 1 if observed else 0), "set_observed")
 
@@ -1569,6 +1574,21 @@ class Context:
     def _chk(self, rc, what):
         if rc != HVO_OK:
             raise HvoError(rc, what + ": " + lib().hvo_last_error(self.h).decode())
+
+    def debug_call_arena(self, fill=None, min_bytes=0):
+        """test door, not product API: grow the context's call arena to at least min_bytes the way a call would, set its whole capacity to the byte
+        `fill` (None: leave it) and return the capacity in bytes"""
+        L = lib(); f = L.hvo_debug_call_arena; f.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]; f.restype = C.c_int
+        cap = C.c_size_t(0)
+        self._chk(f(self.h, -1 if fill is None else int(fill), int(min_bytes), C.byref(cap)), "debug_call_arena")
+        return cap.value
+
+    def debug_call_arena_peek(self, offset, n):
+        """test door, not product API: n bytes of the call arena from `offset` -> uint8 array"""
+        L = lib(); f = L.hvo_debug_call_arena_peek; f.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]; f.restype = C.c_int
+        out = np.zeros(int(n), np.uint8)
+        self._chk(f(self.h, int(offset), int(n), _p(out)), "debug_call_arena_peek")
+        return out
 
     # ---- single frame ----
     def extract_orb(self, gray):
@@ -2462,6 +2482,21 @@ class Stream:
     def _chk(self, rc, what):
         if rc != HVO_OK:
             raise HvoError(rc, what + ": " + lib().hvo_stream_last_error(self.h).decode())
+
+    def debug_call_arena(self, ticket, fill=None, min_bytes=0):
+        """test door, not product API: Context.debug_call_arena on the context of the ring slot that holds frame `ticket`, the arena the
+        stream forms of the matching, fusing and solving calls stage through"""
+        L = lib(); f = L.hvo_debug_stream_call_arena; f.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]; f.restype = C.c_int
+        cap = C.c_size_t(0)
+        self._chk(f(self.h, int(ticket), -1 if fill is None else int(fill), int(min_bytes), C.byref(cap)), "debug_call_arena")
+        return cap.value
+
+    def debug_call_arena_peek(self, ticket, offset, n):
+        """test door, not product API: n bytes of that arena from `offset` -> uint8 array"""
+        L = lib(); f = L.hvo_debug_stream_call_arena_peek; f.argtypes = [C.c_void_p, C.c_int64, C.c_size_t, C.c_size_t, C.c_void_p]; f.restype = C.c_int
+        out = np.zeros(int(n), np.uint8)
+        self._chk(f(self.h, int(ticket), int(offset), int(n), _p(out)), "debug_call_arena_peek")
+        return out
 
     def submit(self, gray, depth=None):
         assert gray.dtype == np.uint8 and gray.shape == (self.hgt, self.w) and gray.strides[1] == 1

@@ -66,6 +66,9 @@ hvo_line_map *hvo_line_map_create(int device, int slots)
 
 void hvo_line_map_destroy(hvo_line_map *m) { if (m) { sm_release(m); delete m; } }
 
+// test door, not product API and not in include/hvo.h
+int hvo_debug_line_map_scratch(hvo_line_map *m, int fill_byte) { return sm_debug_fill_scratch(m, fill_byte); }
+
 int hvo_line_map_set_many(hvo_line_map *m, int first, int n, const double *pos, const double *wvec, const double *normal, const float *max_dist,
                           const float *min_dist, const uint8_t *desc, const uint8_t *observed, const uint8_t *bad)
 {

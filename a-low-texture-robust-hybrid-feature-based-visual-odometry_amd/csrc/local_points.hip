@@ -59,6 +59,9 @@ hvo_point_map *hvo_point_map_create(int device, int slots)
 
 void hvo_point_map_destroy(hvo_point_map *m) { if (m) { sm_release(m); delete m; } }
 
+// test door, not product API and not in include/hvo.h
+int hvo_debug_point_map_scratch(hvo_point_map *m, int fill_byte) { return sm_debug_fill_scratch(m, fill_byte); }
+
 int hvo_point_map_set_many(hvo_point_map *m, int first, int n, const float *pos, const float *normal, const float *max_dist, const float *min_dist,
                            const uint8_t *desc, const uint8_t *observed, const uint8_t *bad)
 {

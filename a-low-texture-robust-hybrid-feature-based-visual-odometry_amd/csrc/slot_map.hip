@@ -126,6 +126,19 @@ int sm_grow(hvo_slot_map *m, hipStream_t st, char **p, size_t *have, size_t want
     return HVO_OK;
 }
 
+// Test door behind hvo_debug_point_map_scratch / hvo_debug_line_map_scratch (not product API): both scratch buffers, at the sizes they have,
+// set to fill_byte on the map's own stream, which is drained before it returns
+int sm_debug_fill_scratch(hvo_slot_map *m, int fill_byte)
+{
+    if (!m || fill_byte < 0 || fill_byte > 255) return HVO_ERR_INVALID_ARG;
+    if (hipSetDevice(m->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
+    SM_HIP(hipDeviceSynchronize());                              // a call's stream is the caller's: nothing of it may still be in flight
+    if (m->d_a && m->a_bytes) SM_HIP(hipMemsetAsync(m->d_a, fill_byte, m->a_bytes, m->st));
+    if (m->d_b && m->b_bytes) SM_HIP(hipMemsetAsync(m->d_b, fill_byte, m->b_bytes, m->st));
+    SM_HIP(hipStreamSynchronize(m->st));
+    return HVO_OK;
+}
+
 // ---------------------------------------------------------------- kernels ----------------------------------------------------------------
 
 __global__ __launch_bounds__(SM_BLOCK) void k_sm_mark(int nt, int ns, const uint8_t *__restrict__ flags, int32_t *__restrict__ held, uint8_t *__restrict__ t_occ,

@@ -60,6 +60,7 @@ static inline uint8_t sm_flag_byte(const uint8_t *observed, const uint8_t *bad, 
 int sm_set_flag(hvo_slot_map *m, int slot, int bit, int on);
 int sm_counts(const hvo_slot_map *m, int *n_slots, int *n_good, int *n_observed);
 int sm_grow(hvo_slot_map *m, hipStream_t st, char **p, size_t *have, size_t want);
+int sm_debug_fill_scratch(hvo_slot_map *m, int fill_byte);      // test door: d_a and d_b at their current sizes
 
 // ---- the call (slot_map.hip) ----
 struct SmCarve { size_t o = 0; size_t take(size_t bytes) { const size_t at = o; o += sm_al(bytes); return at; } };    // 256-byte pieces of scratch A

@@ -862,4 +862,31 @@ int hvo_stream_pose_last_kernel_ms(hvo_stream *s, int64_t cur, float *ms)
     return HVO_OK;
 }
 
+// Test doors, not product API and not in include/hvo.h: hvo_debug_call_arena / _peek on the context of the ring slot that holds frame `ticket`
+// (the arena the stream forms of the matching, fusing and solving calls stage through).  The matching stream is drained first.
+int hvo_debug_call_arena(hvo_ctx *ctx, int fill_byte, size_t min_bytes, size_t *cap_out);
+int hvo_debug_call_arena_peek(hvo_ctx *ctx, size_t offset, size_t n, uint8_t *out);
+
+int hvo_debug_stream_call_arena(hvo_stream *s, int64_t ticket, int fill_byte, size_t min_bytes, size_t *cap_out)
+{
+    if (!s) return HVO_ERR_INVALID_ARG;
+    StreamSlot *B = slot_of(s, ticket);
+    if (!B) { s->last_error = "debug call arena: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    if (s->s_match) ST_HIP(hipStreamSynchronize(s->s_match));
+    const int rc = hvo_debug_call_arena(B->ctx, fill_byte, min_bytes, cap_out);
+    if (rc) s->last_error = "debug call arena: " + B->ctx->last_error;
+    return rc;
+}
+
+int hvo_debug_stream_call_arena_peek(hvo_stream *s, int64_t ticket, size_t offset, size_t n, uint8_t *out)
+{
+    if (!s) return HVO_ERR_INVALID_ARG;
+    StreamSlot *B = slot_of(s, ticket);
+    if (!B) { s->last_error = "debug call arena: no such frame in the ring"; return HVO_ERR_INVALID_ARG; }
+    if (s->s_match) ST_HIP(hipStreamSynchronize(s->s_match));
+    const int rc = hvo_debug_call_arena_peek(B->ctx, offset, n, out);
+    if (rc) s->last_error = "debug call arena peek: " + B->ctx->last_error;
+    return rc;
+}
+
 }  // extern "C"

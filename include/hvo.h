@@ -1281,6 +1281,8 @@ typedef struct {               /* a map side on host arrays: vpMapPoints */
     const float   *max_dist, *min_dist;   /* RAW mfMaxDistance / mfMinDistance; the call applies 1.2f / 0.8f, as in hvo_point_map */
     const uint8_t *desc;                  /* n x 32, GetDescriptor() */
 } hvo_fuse_map;
+/* n = 0 is served on either side, alone or inside a longer list, and its arrays may then be NULL: a key frame without features searches its
+ * entries and finds nothing (best_idx -1, n_fused 0), a map side without entries gives n_searched = n_fused = 0 and writes no array. */
 typedef struct {
     float th;                  /* 3 */
     int32_t th_low;            /* TH_LOW (50); above 255 is refused (bestDist starts at 256: the reference would accept bestIdx = -1) */

@@ -351,3 +351,18 @@ def vacuity(w, n):
     assert w["n_fused"] * 4 >= n, ("fused", w["n_fused"], n)
     assert set(np.unique(w["gate"]).tolist()) == set(range(7)), np.unique(w["gate"])
     assert (w["n_ties"] > 1).any(), "no entry with more than one candidate at the best distance"
+
+
+RAGGED = ((65, 257), (0, 40), (300, 0), (64, 17))     # (features, map entries) of the four key frames of one call
+
+
+def ragged_keyframes(kp_dt):
+    """four key frames for ONE call with a map side each: an empty key frame and an empty map side inside the list, uright = None on key frame
+    2, skip = None on key frame 1; then the same key frames against one shared map side made from key frame 2's own features (skip bytes
+    of the shared length) -> (kfs, maps, shared_kfs, shared_map)"""
+    sc = [random_scene(kp_dt, nt, n, seed=400 + j, pose=j, pose_dx=0.001 * (j + 1)) for j, (nt, n) in enumerate(RAGGED)]
+    kfs = [s[0] for s in sc]; maps = [s[1] for s in sc]
+    kfs[2] = dict(kfs[2], uright=None); kfs[1] = dict(kfs[1], skip=None)
+    _, shared = random_scene(kp_dt, 300, 257, seed=402, pose=2, pose_dx=0.003)
+    shared_kfs = [dict(kf, skip=None if j == 1 else ((np.arange(257) + j) % 7 == 0).astype(np.uint8)) for j, kf in enumerate(kfs)]
+    return kfs, maps, shared_kfs, shared

@@ -409,6 +409,33 @@ def random_scene(n=1000, seed=SCENE_SEED, poses=SCENE_POSES, per_node=8, other_n
     return cur, kfs
 
 
+RAGGED = (65, 0, 300, 1, 17)                            # the feature counts the five neighbours of ragged_scene are cut to
+RAGGED_CREATED, FULL_SIZE_CREATED = (39, 0, 156, 0, 0), 2563      # what the restatement creates on ragged_scene and on full_size_scene
+
+
+def cut(side, n):
+    """the first n features of a key frame"""
+    return dict(side, **{k: (None if side.get(k) is None else side[k][:n]) for k in ("kp_un", "kp", "uright", "depth", "desc", "node_id", "has_map_point")})
+
+
+def ragged_scene():
+    """one call whose neighbours differ in everything the staging pads or leaves out: 65, 0, 300, 1 and 17 features (the stride is the
+    largest count), an empty neighbour inside the list, neighbour 2 monocular, neighbour 0 alone with raw key points (a quarter pixel off its
+    undistorted ones, so that the unprojection of its stereo branch reads them)"""
+    poses = (SCENE_POSES[0], SCENE_POSES[1], SCENE_POSES[3], (np.eye(3), (-0.2, 0.1, 0)), (yaw(0.01), (0.15, 0, 0.05)))
+    cur, kfs = random_scene(n=300, seed=11, poses=poses, twins=5)
+    kfs = [cut(k, n) for k, n in zip(kfs, RAGGED)]
+    kfs[2] = dict(kfs[2], uright=None, depth=None)
+    raw = kfs[0]["kp_un"].copy(); raw["x"] += F32(0.25)
+    kfs[0] = dict(kfs[0], kp=raw)
+    return cur, kfs
+
+
+def full_size_scene():
+    """4096 features on both sides in 64 nodes of 64: the CSR sort fills its 32 KB of keys and the search key's 16-bit position is largest"""
+    return random_scene(n=MAX_FEATURES, seed=12, poses=SCENE_POSES[:1], per_node=64, twins=0)
+
+
 def neighbours_of_frame(kp_un, uright, depth, desc, node_id, poses, cam, seed, mb):
     """neighbours that see a real frame's features: each feature is unprojected at its depth (a feature without depth at a drawn one) from
     the identity pose and observed from every pose of `poses`, in reversed feature order, with up to six descriptor bits flipped"""

@@ -142,6 +142,21 @@ def test_the_random_scene_is_not_vacuous():
     assert w["n_cand"].max() >= 8 and w["n_fused"] * 4 >= 257
 
 
+def test_the_ragged_key_frames_say_something(hvo):
+    """fuse_ref.ragged_keyframes, on the restatement: an empty key frame and an empty map side inside the list give empty answers, the others
+    fuse, the monocular key frame among them; against the shared map side the key frame whose features made it fuses most of it"""
+    kfs, maps, shared_kfs, shared = ref.ragged_keyframes(hvo.KEYPOINT_DT)
+    assert [(len(k["kp_un"]), len(m["pos"])) for k, m in zip(kfs, maps)] == list(ref.RAGGED) == [(65, 257), (0, 40), (300, 0), (64, 17)]
+    assert kfs[2]["uright"] is None and kfs[1]["skip"] is None and all(k["uright"] is not None for j, k in enumerate(kfs) if j != 2)
+    w = [ref.fuse(kf, mp, pm.CAM) for kf, mp in zip(kfs, maps)]
+    assert w[0]["n_fused"] > 40 and w[3]["n_fused"] > 3 and w[0]["n_searched"] > w[0]["n_fused"]
+    assert w[1]["n_fused"] == 0 and w[1]["n_searched"] == 40 and (w[1]["best_idx"] == -1).all()        # searched, and no feature to find
+    assert w[2]["n_fused"] == w[2]["n_searched"] == 0 and len(w[2]["best_idx"]) == 0
+    ws = [ref.fuse(kf, shared, pm.CAM) for kf in shared_kfs]
+    assert len(shared["pos"]) == 257 and ws[2]["n_fused"] > 40 and ws[1]["n_fused"] == 0 and ws[1]["n_searched"] > 100
+    assert all(kf["skip"] is None or len(kf["skip"]) == 257 for kf in shared_kfs)
+
+
 def test_the_host_restatement_agrees(tmp_path):
     """tools/fuse_host.cpp, the single-thread host restatement the timing tool measures beside the device, gives fuse_ref's answer"""
     exe = str(tmp_path / "fuse_host")

@@ -164,6 +164,27 @@ def test_key_frames_in_one_call(hvo):
     assert nf > 31 * 5 and len({r["n_fused"] for r in shared}) > 1
 
 
+def test_ragged_key_frames(hvo):
+    """four key frames in ONE call with a map side each: 65, 0, 300 and 64 features against 257, 40, 0 and 17 entries -- an empty key frame
+    and an empty map side inside the list --, uright = NULL on key frame 2, skip = NULL on key frame 1.  include/hvo.h allows n = 0 on either
+    side with NULL arrays and a NULL skip: each key frame equals the restatement and its own single call.  Then the same four key frames
+    against ONE shared map side"""
+    ctx = ctx_of(hvo)
+    kfs, maps, shared_kfs, shared = ref.ragged_keyframes(hvo.KEYPOINT_DT)
+    assert [(len(k["kp_un"]), len(m["pos"])) for k, m in zip(kfs, maps)] == list(ref.RAGGED)
+    got = ctx.fuse_points(pm.CAM, kfs, maps, B4)
+    for j, (kf, mp) in enumerate(zip(kfs, maps)):
+        same(got[j], ref.fuse(kf, mp, pm.CAM), "ragged %d" % j)
+        identical(got[j], run(hvo, kf, mp), "ragged %d alone" % j)
+    assert got[0]["n_fused"] > 40 and got[3]["n_fused"] > 3 and got[1]["n_fused"] == got[2]["n_fused"] == 0
+    assert got[1]["n_searched"] == 40 and (got[1]["best_idx"] == -1).all() and len(got[2]["best_idx"]) == 0 and got[2]["status"] == 0
+    sh = ctx.fuse_points(pm.CAM, shared_kfs, shared, B4)
+    for j, kf in enumerate(shared_kfs):
+        same(sh[j], ref.fuse(kf, shared, pm.CAM), "shared %d" % j)
+        identical(sh[j], run(hvo, kf, shared), "shared %d alone" % j)
+    assert sh[2]["n_fused"] > 40 and sh[1]["n_fused"] == 0 and sh[1]["n_searched"] > 100
+
+
 def test_slot_form(hvo):
     """the map side as slots of a resident point map equals the array form on the same points: a permuted subset of the slots, a bad slot
     (counted as skipped), and a slot past the map's end, which is refused whole"""

@@ -114,6 +114,37 @@ def test_the_chain_equals_independent_pairs_plus_resolve():
             assert np.array_equal(pres[j]["created_idx1"], res[j]["created_idx1"])
 
 
+def test_the_ragged_scene_says_something():
+    """the restatement's own answer on new_points_ref.ragged_scene: neighbours of 65, 0, 300, 1 and 17 features in one call, the empty one inside
+    the list, neighbour 2 monocular, neighbour 0 alone with raw key points.  At least two neighbours create, one is empty, and the created
+    points come from the triangulation and from a stereo branch, on the stereo neighbour and on the monocular one"""
+    cur, kfs = ref.ragged_scene()
+    assert tuple(len(k["kp_un"]) for k in kfs) == ref.RAGGED and ref.RAGGED[1] == 0 and max(ref.RAGGED) == len(cur["kp_un"]) == 300
+    assert kfs[2]["uright"] is None and kfs[2]["depth"] is None and all(k["uright"] is not None for j, k in enumerate(kfs) if j != 2)
+    assert [k["kp"] is not None for k in kfs] == [True, False, False, False, False] and not np.array_equal(kfs[0]["kp"]["x"], kfs[0]["kp_un"]["x"])
+    res, summ = ref.full(cur, kfs, ref.CAM, ref.CAM[4])
+    assert tuple(r["n_created"] for r in res) == ref.RAGGED_CREATED and [r["gate"] for r in res] == [0] * 5 and summ["n_new"] == 195
+    assert sum(r["n_created"] > 0 for r in res) >= 2
+    for j in (0, 2):
+        br = np.bincount(res[j]["branch"][res[j]["outcome"] == ref.CREATED], minlength=4)
+        assert br[1] > 0 and br[2] + br[3] > 0, (j, br)
+    br0 = np.bincount(res[0]["branch"][res[0]["outcome"] == ref.CREATED], minlength=4)
+    assert br0[3] > 0                                                  # the neighbour's own stereo branch: the one that unprojects its RAW key point
+    assert (res[1]["match_idx2"] == -1).all() and (res[1]["outcome"][cur["has_map_point"] == 0] == ref.NO_MATCH).all()
+
+
+def test_the_full_size_scene_says_something():
+    """4096 features on both sides (one more is refused), 64 nodes of 64 features each: the restatement creates 2563 points"""
+    cur, kfs = ref.full_size_scene()
+    assert len(cur["kp_un"]) == len(kfs[0]["kp_un"]) == ref.MAX_FEATURES == 4096 and len(kfs) == 1
+    assert np.bincount(cur["node_id"]).max() == 64 and len(set(cur["node_id"].tolist())) == 64
+    res, summ = ref.full(cur, kfs, ref.CAM, ref.CAM[4])
+    assert summ["n_new"] == res[0]["n_created"] == ref.FULL_SIZE_CREATED and res[0]["gate"] == 0
+    full = dict(cur, has_map_point=np.ones(4096, np.uint8))
+    ores, osum = ref.full(full, kfs, ref.CAM, ref.CAM[4])
+    assert (ores[0]["outcome"] == ref.OCCUPIED).all() and osum["n_new"] == 0 and (osum["owner"] == -1).all()
+
+
 def test_jacobi_reading_accuracy():
     """noise-free planted points, 200 pairs, baselines 0.1 .. 0.5 m, depths 0.5 .. 8 m: the restatement's linear triangulation against the same
     float32 A solved by numpy.linalg.svd in float64; at most 4 times the error of numpy.linalg.svd on the float32 A against the same solution

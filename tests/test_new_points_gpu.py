@@ -189,6 +189,41 @@ def test_widths(hvo, width):
         same((res, summ), ref.full(cur, kfs, ref.CAM, ref.CAM[4]), "ten neighbours")
 
 
+def test_ragged_neighbours(hvo):
+    """neighbours of 65, 0, 300, 1 and 17 features in ONE call (every neighbour is padded to the stride of the largest), the empty one
+    inside the list, neighbour 2 monocular, neighbour 0 alone with raw key points: the call equals the restatement, each neighbour's pair
+    results equal its own single-neighbour call byte for byte, and so does the list with the empty neighbour moved to the front and to the end"""
+    cur, kfs = ref.ragged_scene()
+    want = ref.full(cur, kfs, ref.CAM, ref.CAM[4])
+    assert tuple(r["n_created"] for r in want[0]) == ref.RAGGED_CREATED and want[1]["n_new"] == 195
+    got = run(hvo, cur, kfs)
+    same(got, want, "ragged")
+    for j, k in enumerate(kfs):
+        one = run(hvo, cur, [k])[0][0]
+        for key in PAIR_KEYS:
+            assert one[key].tobytes() == got[0][j][key].tobytes(), (j, key)
+    for order in ((1, 0, 2, 3, 4), (0, 2, 3, 4, 1)):
+        perm = [kfs[j] for j in order]
+        pgot = run(hvo, cur, perm)
+        same(pgot, ref.full(cur, perm, ref.CAM, ref.CAM[4]), "empty neighbour at %d" % order.index(1))
+        for pos, j in enumerate(order):
+            for key in PAIR_KEYS:
+                assert pgot[0][pos][key].tobytes() == got[0][j][key].tobytes(), (order, j, key)
+
+
+def test_full_size(hvo):
+    """4096 features on both sides, the limit itself (4097 is refused above): k_bow_csr sorts a full 32 KB of keys and the search key's 16-bit
+    CSR position reaches its largest value.  Then every current feature occupied: every outcome is OCCUPIED and nothing is created"""
+    cur, kfs = ref.full_size_scene()
+    want = ref.full(cur, kfs, ref.CAM, ref.CAM[4])
+    assert want[1]["n_new"] == ref.FULL_SIZE_CREATED
+    got = run(hvo, cur, kfs)
+    same(got, want, "4096 x 4096")
+    res, summ = run(hvo, dict(cur, has_map_point=np.ones(ref.MAX_FEATURES, np.uint8)), kfs)
+    assert (res[0]["outcome"] == ref.OCCUPIED).all() and (res[0]["branch"] == 0).all() and res[0]["n_created"] == 0 and len(res[0]["created_idx1"]) == 0
+    assert summ["n_new"] == 0 and (summ["owner"] == -1).all() and res[0]["status"] == 0
+
+
 def test_stream_form_equals_the_host_form(hvo, synth):
     """the current key frame resident with its bag of words: the stream form equals the host-array form on the downloaded frame bit for bit,
     and the restatement; a frame without its bag of words is refused with the stream's error text"""
