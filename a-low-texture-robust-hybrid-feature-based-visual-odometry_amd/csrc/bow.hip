@@ -33,6 +33,7 @@
 //                   private to the node because a frame feature lies in exactly one node.  Then the 30-bin rotation histogram and
 //                   ComputeThreeMaxima (hvo_three_maxima, shared with the guided search).
 #include "frame_view.hpp"
+#include "call_stage.hpp"
 #include <string.h>
 #include <stdio.h>
 #include <math.h>
@@ -60,23 +61,20 @@ static std::atomic<unsigned long long> g_voc_uid{ 1 };
 
 int bow_voc_device(const hvo_vocabulary *v) { return v->device; }
 unsigned long long bow_voc_uid(const hvo_vocabulary *v) { return v->uid; }
-
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 void bow_layout(int cap, BowLayout &L)
 {
     size_t o = 0; const size_t c = (size_t)(cap < 1 ? 1 : cap);
     L.cap = cap;
     L.counts = o; o += 256;
-    L.word_id = o; o += al256(c * 4);
-    L.node_id = o; o += al256(c * 4);
-    L.flag = o; o += al256(c * 4);
-    L.weight = o; o += al256(c * 8);
-    L.bow_word = o; o += al256(c * 4);
-    L.bow_val = o; o += al256(c * 8);
-    L.fv_node = o; o += al256(c * 4);
-    L.fv_start = o; o += al256((c + 1) * 4);
-    L.fv_idx = o; o += al256(c * 4);
+    L.word_id = o; o += stage_align(c * 4);
+    L.node_id = o; o += stage_align(c * 4);
+    L.flag = o; o += stage_align(c * 4);
+    L.weight = o; o += stage_align(c * 8);
+    L.bow_word = o; o += stage_align(c * 4);
+    L.bow_val = o; o += stage_align(c * 8);
+    L.fv_node = o; o += stage_align(c * 4);
+    L.fv_start = o; o += stage_align((c + 1) * 4);
+    L.fv_idx = o; o += stage_align(c * 4);
     L.total = o;
 }
 
@@ -399,8 +397,8 @@ static int voc_build(int device, int k, int L, int scoring, int weighting, int n
     v->device = device; v->k = k; v->L = L; v->scoring = scoring; v->weighting = weighting; v->n_nodes = nn; v->n_words = n_words;
     v->uid = g_voc_uid.fetch_add(1);
     if (device >= 0) {
-        const size_t o_desc = 0, o_child = al256((size_t)nn * 32), o_ref = o_child + al256((size_t)nn * 8), o_word = o_ref + al256((size_t)nn * 4),
-                     o_w = o_word + al256((size_t)nn * 4), total = o_w + al256((size_t)nn * 8);
+        const size_t o_desc = 0, o_child = stage_align((size_t)nn * 32), o_ref = o_child + stage_align((size_t)nn * 8), o_word = o_ref + stage_align((size_t)nn * 4),
+                     o_w = o_word + stage_align((size_t)nn * 4), total = o_w + stage_align((size_t)nn * 8);
         std::vector<char> h;
         try { h.assign(total, 0); } catch (const std::bad_alloc &) { delete v; throw; }
         for (int q = 0; q < nn; q++) {
@@ -517,46 +515,48 @@ int bow_search(hvo_ctx *ctx, hipStream_t st, const hvo_bow_keyframe *F, const Fr
     if (capk == 0) { for (int j = 0; j < n_kf; j++) for (int i = 0; i < nf; i++) res[j].match_kf[i] = -1; return HVO_OK; }
     const bool fhost = F != nullptr;
     // one carve of the context's arena: the key-frame side (n_kf slots of capk), the frame side when it comes from the host, the results
-    const size_t k_desc = 0, k_node = k_desc + al256((size_t)n_kf * capk * 32), k_has = k_node + al256((size_t)n_kf * capk * 4), k_ang = k_has + al256((size_t)n_kf * capk),
-                 k_n = k_ang + al256((size_t)n_kf * capk * 4), up_k = k_n + al256((size_t)n_kf * 4);
-    const size_t f_desc = up_k, f_node = f_desc + al256((size_t)nf * 32), f_ang = f_node + al256((size_t)nf * 4), f_n = f_ang + al256((size_t)nf * 4), up_end = f_n + 256;
-    const size_t c_node = up_end, c_start = c_node + al256((size_t)n_kf * capk * 4), c_idx = c_start + al256((size_t)n_kf * (capk + 1) * 4),
-                 c_rows = c_idx + al256((size_t)n_kf * capk * 4), g_node = c_rows + al256((size_t)n_kf * 4), g_start = g_node + al256((size_t)nf * 4),
-                 g_idx = g_start + al256((size_t)(nf + 1) * 4), g_rows = g_idx + al256((size_t)nf * 4), r_match = g_rows + 256,
-                 r_n = r_match + al256((size_t)n_kf * nf * 4), total = r_n + al256((size_t)n_kf * 4);
-    char *d = (char *)hvo_call_arena(ctx, total);
+    const size_t Kf = (size_t)n_kf, ck = (size_t)capk, cf = (size_t)nf;
+    StageCarver C(256);
+    const auto k_desc = C.take<uint8_t>(Kf, ck * 32); const auto k_node = C.take<int>(Kf, ck); const auto k_has = C.take<uint8_t>(Kf, ck);
+    const auto k_ang = C.take<float>(Kf, ck); const auto k_n = C.take<int>(Kf);
+    const auto f_desc = C.take<uint8_t>(cf * 32); const auto f_node = C.take<int>(cf); const auto f_ang = C.take<float>(cf); const auto f_n = C.take<int>(1);
+    const size_t up_end = C.mark();
+    const auto c_node = C.take<int>(Kf, ck), c_start = C.take<int>(Kf, ck + 1), c_idx = C.take<int>(Kf, ck), c_rows = C.take<int>(Kf);
+    const auto g_node = C.take<int>(cf), g_start = C.take<int>(cf + 1), g_idx = C.take<int>(cf), g_rows = C.take<int>(1);
+    const auto r_match = C.take<int>(Kf, cf), r_n = C.take<int>(Kf);
+    char *d = (char *)hvo_call_arena(ctx, C.mark());
     if (!d) { *err = "search by bag of words: arena"; return HVO_ERR_HIP; }
-    std::vector<char> h(up_end, 0);
+    std::vector<char> hv(up_end, 0); char *const h = hv.data();
     for (int j = 0; j < n_kf; j++) {
         const int n = kf[j].n;
-        ((int *)&h[k_n])[j] = n;
+        k_n.host(h)[j] = n;
         if (!n) continue;
         for (int i = 0; i < n; i++) if (kf[j].node_id[i] < -1) return HVO_ERR_INVALID_ARG;
-        memcpy(&h[k_desc + (size_t)j * capk * 32], kf[j].desc, (size_t)n * 32);
-        memcpy(&h[k_node + (size_t)j * capk * 4], kf[j].node_id, (size_t)n * 4);
-        memcpy(&h[k_has + (size_t)j * capk], kf[j].has_map_point, (size_t)n);
-        if (kf[j].angle) memcpy(&h[k_ang + (size_t)j * capk * 4], kf[j].angle, (size_t)n * 4);
+        memcpy(k_desc.host(h, j), kf[j].desc, (size_t)n * 32);
+        memcpy(k_node.host(h, j), kf[j].node_id, (size_t)n * 4);
+        memcpy(k_has.host(h, j), kf[j].has_map_point, (size_t)n);
+        if (kf[j].angle) memcpy(k_ang.host(h, j), kf[j].angle, (size_t)n * 4);
     }
-    ((int *)&h[f_n])[0] = nf;
+    f_n.host(h)[0] = nf;
     if (fhost) {
         for (int i = 0; i < nf; i++) if (F->node_id[i] < -1) return HVO_ERR_INVALID_ARG;
-        memcpy(&h[f_desc], F->desc, (size_t)nf * 32); memcpy(&h[f_node], F->node_id, (size_t)nf * 4);
-        if (F->angle) memcpy(&h[f_ang], F->angle, (size_t)nf * 4);
+        memcpy(f_desc.host(h), F->desc, (size_t)nf * 32); memcpy(f_node.host(h), F->node_id, (size_t)nf * 4);
+        if (F->angle) memcpy(f_ang.host(h), F->angle, (size_t)nf * 4);
     }
-    if (hipMemcpyAsync(d, h.data(), up_end, hipMemcpyHostToDevice, st) != hipSuccess) return HVO_ERR_HIP;
+    if (hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st) != hipSuccess) return HVO_ERR_HIP;
     BowSideDev K; memset(&K, 0, sizeof(K));
-    K.desc = (const uint8_t *)(d + k_desc); K.node = (const int *)(d + k_node); K.has_mp = (const uint8_t *)(d + k_has); K.angle = (const float *)(d + k_ang); K.angle_step = 1;
-    K.fv_node = (int *)(d + c_node); K.fv_start = (int *)(d + c_start); K.fv_idx = (int *)(d + c_idx); K.n_rows = (int *)(d + c_rows); K.n = (const int *)(d + k_n); K.cap = capk;
+    K.desc = k_desc.dev(d); K.node = k_node.dev(d); K.has_mp = k_has.dev(d); K.angle = k_ang.dev(d); K.angle_step = 1;
+    K.fv_node = c_node.dev(d); K.fv_start = c_start.dev(d); K.fv_idx = c_idx.dev(d); K.n_rows = c_rows.dev(d); K.n = k_n.dev(d); K.cap = capk;
     bow_ev_begin(ctx, st, 1);
     hipLaunchKernelGGL(k_bow_csr, dim3(n_kf), dim3(256), 0, st, K);
     BowSearchDev A; memset(&A, 0, sizeof(A));
-    A.kf = K; A.f_n = (const int *)(d + f_n); A.f_cap = nf;
+    A.kf = K; A.f_n = f_n.dev(d); A.f_cap = nf;
     if (fhost) {
         BowSideDev G; memset(&G, 0, sizeof(G));
-        G.node = (const int *)(d + f_node); G.fv_node = (int *)(d + g_node); G.fv_start = (int *)(d + g_start); G.fv_idx = (int *)(d + g_idx); G.n_rows = (int *)(d + g_rows);
+        G.node = f_node.dev(d); G.fv_node = g_node.dev(d); G.fv_start = g_start.dev(d); G.fv_idx = g_idx.dev(d); G.n_rows = g_rows.dev(d);
         G.n = A.f_n; G.cap = nf;
         hipLaunchKernelGGL(k_bow_csr, dim3(1), dim3(256), 0, st, G);
-        A.f_desc = (const uint8_t *)(d + f_desc); A.f_angle = (const float *)(d + f_ang); A.f_angle_step = 1;
+        A.f_desc = f_desc.dev(d); A.f_angle = f_ang.dev(d); A.f_angle_step = 1;
         A.f_fv_node = G.fv_node; A.f_fv_start = G.fv_start; A.f_fv_idx = G.fv_idx; A.f_n_rows = G.n_rows;
     } else {
         BowLayout L; bow_layout(bow->cap, L);
@@ -565,13 +565,13 @@ int bow_search(hvo_ctx *ctx, hipStream_t st, const hvo_bow_keyframe *F, const Fr
         A.f_n_rows = (const int *)(bow->d_blk + L.counts) + 2;
     }
     A.nnratio = P->nnratio; A.check_orientation = P->check_orientation ? 1 : 0; A.th_low = P->th_low;
-    A.match_kf = (int *)(d + r_match); A.n_matches = (int *)(d + r_n);
+    A.match_kf = r_match.dev(d); A.n_matches = r_n.dev(d);
     hipLaunchKernelGGL(k_bow_search, dim3(n_kf), dim3(64 * BOW_WAVES), 0, st, A);
     bow_ev_end(ctx, st, 1);
     if (hipGetLastError() != hipSuccess) { *err = "search by bag of words: launch"; return HVO_ERR_HIP; }
-    std::vector<int> hm((size_t)n_kf * nf), hn((size_t)n_kf);
-    if (hipMemcpyAsync(hm.data(), d + r_match, hm.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(hn.data(), d + r_n, hn.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    std::vector<int> hm(r_match.count()), hn(r_n.count());
+    if (hipMemcpyAsync(hm.data(), r_match.dev(d), r_match.bytes(), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(hn.data(), r_n.dev(d), r_n.bytes(), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
         *err = std::string("search by bag of words: ") + hipGetErrorString(hipGetLastError()); return HVO_ERR_HIP;
     }
     bow_ev_read(ctx, 1);
@@ -641,7 +641,7 @@ int hvo_compute_bow(hvo_ctx *ctx, const hvo_vocabulary *voc, int levelsup, int n
     for (int f = 0; f < n_frames; f++) { if (n_desc[f] < 0 || (n_desc[f] > 0 && !desc[f])) return HVO_ERR_INVALID_ARG; cap = std::max(cap, (int)n_desc[f]); }
     if (cap > BOW_MAXN) { ctx->last_error = "bag of words: more than 4096 features in a frame"; return HVO_ERR_UNSUPPORTED; }
     if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    const size_t b_desc = al256((size_t)n_frames * std::max(cap, 1) * 32), b_n = al256((size_t)n_frames * 4);
+    const size_t b_desc = stage_align((size_t)n_frames * std::max(cap, 1) * 32), b_n = stage_align((size_t)n_frames * 4);
     char *a = (char *)hvo_call_arena(ctx, b_desc + b_n);
     if (!a) return HVO_ERR_HIP;
     std::vector<char> h(b_desc + b_n, 0);

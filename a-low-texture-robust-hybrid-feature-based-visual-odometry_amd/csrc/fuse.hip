@@ -289,82 +289,80 @@ static int fuse_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const h
     }
     // ---- one carve of the context's arena: what goes up, the grid, the queries, what comes down ----
     const size_t S = m ? 0 : (per_kf ? F : 1), nb = cq / FU_BLOCK;
-    SmCarve C;
-    const size_t u_kf = C.take(F * sizeof(FuKf)), u_tab = C.take(2 * HVO_MAX_LEVELS * 4), u_skip = C.take(F * cq);
-    const size_t u_kp = C.take(fr ? 0 : F * ct * sizeof(hvo_keypoint)), u_ur = C.take(fr ? 0 : F * ct * 4), u_fd = C.take(fr ? 0 : F * ct * 32);
-    const size_t u_pos = C.take(S * 3 * cq * 4), u_nrm = C.take(S * 3 * cq * 4), u_maxd = C.take(S * cq * 4), u_mind = C.take(S * cq * 4), u_md = C.take(S * cq * 32);
-    const size_t u_slots = C.take(m ? cq * 4 : 0);
-    const size_t up_end = C.o;
-    const size_t g_start = C.take(F * (FU_CELLS + 1) * 4), g_rec = C.take(F * ct * sizeof(float4)), g_item = C.take(F * ct * 4);
-    const size_t q_u = C.take(F * cq * 4), q_v = C.take(F * cq * 4), q_ur = C.take(F * cq * 4), q_rad = C.take(F * cq * 4);
-    const size_t z0 = C.o;                                           // [z0, z1) is zeroed
-    const size_t s_pass = C.take(F * cq), s_bc = C.take(F * nb * 4);
-    const size_t r0 = C.o;                                           // [r0, r1) comes down; its head belongs to the zeroed range
-    const size_t r_cnt = C.take(F * 2 * 4);
-    const size_t z1 = C.o;
-    const size_t r_bi = C.take(F * cq * 4), r_bd = C.take(F * cq * 4), r_lvl = C.take(F * cq * 4), r_proj = C.take(F * cq * 12), r_gate = C.take(F * cq),
-                 r_fe = C.take(F * cq * 4), r_fi = C.take(F * cq * 4);
-    const size_t r1 = C.o;
-    char *d = (char *)hvo_call_arena(ctx, C.o);
+    StageCarver C(256);
+    const size_t Fh = fr ? 0 : F;                                    // key-frame sides that go up
+    const auto u_kf = C.take<FuKf>(F); const auto u_tab = C.take<float>(2 * HVO_MAX_LEVELS); const auto u_skip = C.take<uint8_t>(F, cq);
+    const auto u_kp = C.take<hvo_keypoint>(Fh, ct); const auto u_ur = C.take<float>(Fh, ct); const auto u_fd = C.take<uint8_t>(Fh, ct * 32);
+    const auto u_pos = C.take<float>(3 * S, cq), u_nrm = C.take<float>(3 * S, cq), u_maxd = C.take<float>(S, cq), u_mind = C.take<float>(S, cq);      // pos, nrm by component: row 3 s + q
+    const auto u_md = C.take<uint8_t>(S, cq * 32); const auto u_slots = C.take<int32_t>(m ? cq : 0);
+    const size_t up_end = C.mark();
+    const auto g_start = C.take<int>(F, FU_CELLS + 1); const auto g_rec = C.take<float4>(F, ct); const auto g_item = C.take<int32_t>(F, ct);
+    const auto q_u = C.take<float>(F, cq), q_v = C.take<float>(F, cq), q_ur = C.take<float>(F, cq), q_rad = C.take<float>(F, cq);
+    const size_t z0 = C.mark();                                      // [z0, z1) is zeroed
+    const auto s_pass = C.take<uint8_t>(F, cq); const auto s_bc = C.take<int>(F, nb);
+    const size_t r0 = C.mark();                                      // [r0, r1) comes down; its head belongs to the zeroed range
+    const auto r_cnt = C.take<int>(2, F);                            // row 0: searched, row 1: fused
+    const size_t z1 = C.mark();
+    const auto r_bi = C.take<int32_t>(F, cq), r_bd = C.take<int32_t>(F, cq), r_lvl = C.take<int32_t>(F, cq);
+    const auto r_proj = C.take<float>(F, cq * 3); const auto r_gate = C.take<int8_t>(F, cq);
+    const auto r_fe = C.take<int32_t>(F, cq), r_fi = C.take<int32_t>(F, cq);
+    const size_t r1 = C.mark();
+    char *d = (char *)hvo_call_arena(ctx, C.mark());
     if (!d) { *err = "fuse: arena"; return HVO_ERR_HIP; }
-    std::vector<char> h(up_end, 0);
-    float *tab = (float *)&h[u_tab];
+    std::vector<char> hv(up_end, 0); char *const h = hv.data();
+    float *tab = u_tab.host(h);
     for (int l = 0; l < HVO_MAX_LEVELS; l++) tab[l] = fr ? fr->sf[l] : ctx->scale[l];
     frame_level_sigma2(fr ? fr->ctx : ctx, nullptr, tab + HVO_MAX_LEVELS);
     for (int j = 0; j < n_kf; j++) {
         const hvo_fuse_keyframe &K = kf[j];
-        FuKf &c = ((FuKf *)&h[u_kf])[j];
-        for (int r = 0; r < 3; r++) { for (int q = 0; q < 3; q++) c.R[3 * r + q] = K.Tcw[4 * r + q]; c.t[r] = K.Tcw[4 * r + 3]; }
-        for (int r = 0; r < 3; r++) {                              // Ow = -Rcw^T tcw (match_project_setup's twc)
-            double s0 = 0;
-            for (int q = 0; q < 3; q++) s0 += (double)c.R[3 * q + r] * (double)c.t[q];
-            c.Ow[r] = (float)(s0 * -1.0);
-        }
+        FuKf &c = *u_kf.host(h, j);
+        pose_split(K.Tcw, c.R, c.t, c.Ow);                         // Ow = -Rcw^T tcw (match_project_setup's twc)
         c.n_feat = n_feat[j]; c.n_ent = n_ent[j];
         if (fr) { c.kp = fr->kp_un; c.ur = fr->uright; c.desc = fr->desc; }
         else {
             const size_t nf = (size_t)n_feat[j];
-            c.kp = (const hvo_keypoint *)(d + u_kp) + j * ct; c.ur = K.uright ? (const float *)(d + u_ur) + j * ct : nullptr; c.desc = (const uint8_t *)(d + u_fd) + j * ct * 32;
+            c.kp = u_kp.dev(d, j); c.ur = K.uright ? u_ur.dev(d, j) : nullptr; c.desc = u_fd.dev(d, j);
             if (nf) {
-                memcpy((hvo_keypoint *)&h[u_kp] + j * ct, K.kp_un, nf * sizeof(hvo_keypoint)); memcpy(&h[u_fd] + j * ct * 32, K.desc, nf * 32);
-                if (K.uright) memcpy((float *)&h[u_ur] + j * ct, K.uright, nf * 4);
+                memcpy(u_kp.host(h, j), K.kp_un, nf * sizeof(hvo_keypoint)); memcpy(u_fd.host(h, j), K.desc, nf * 32);
+                if (K.uright) memcpy(u_ur.host(h, j), K.uright, nf * 4);
             }
         }
-        if (K.skip && n_ent[j]) memcpy(&h[u_skip] + j * cq, K.skip, (size_t)n_ent[j]);
+        if (K.skip && n_ent[j]) memcpy(u_skip.host(h, j), K.skip, (size_t)n_ent[j]);
     }
     for (size_t s = 0; s < S; s++) {
         const hvo_fuse_map &M = maps[s];
         const size_t n = (size_t)M.n;
-        float *hp = (float *)&h[u_pos] + s * 3 * cq, *hn = (float *)&h[u_nrm] + s * 3 * cq;
-        for (size_t i = 0; i < n; i++) for (int q = 0; q < 3; q++) { hp[q * cq + i] = M.pos[3 * i + q]; hn[q * cq + i] = M.normal[3 * i + q]; }     // by component
-        if (n) { memcpy((float *)&h[u_maxd] + s * cq, M.max_dist, n * 4); memcpy((float *)&h[u_mind] + s * cq, M.min_dist, n * 4); memcpy(&h[u_md] + s * cq * 32, M.desc, n * 32); }
+        float *const hp[3] = { u_pos.host(h, 3 * s), u_pos.host(h, 3 * s + 1), u_pos.host(h, 3 * s + 2) };
+        float *const hn[3] = { u_nrm.host(h, 3 * s), u_nrm.host(h, 3 * s + 1), u_nrm.host(h, 3 * s + 2) };
+        for (size_t i = 0; i < n; i++) for (int q = 0; q < 3; q++) { hp[q][i] = M.pos[3 * i + q]; hn[q][i] = M.normal[3 * i + q]; }     // by component
+        if (n) { memcpy(u_maxd.host(h, s), M.max_dist, n * 4); memcpy(u_mind.host(h, s), M.min_dist, n * 4); memcpy(u_md.host(h, s), M.desc, n * 32); }
     }
-    if (m && n_slots) memcpy(&h[u_slots], slots, (size_t)n_slots * 4);
-    if (hipMemcpyAsync(d, h.data(), up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = "fuse: upload"; return HVO_ERR_HIP; }
+    if (m && n_slots) memcpy(u_slots.host(h), slots, (size_t)n_slots * 4);
+    if (hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = "fuse: upload"; return HVO_ERR_HIP; }
     // (the memset follows the copy: a copy from pageable memory waits for what the stream holds)
     if (hipMemsetAsync(d + z0, 0, z1 - z0, st) != hipSuccess) { *err = "fuse: memset"; return HVO_ERR_HIP; }
     bool ev_on = true;
     for (int i = 0; i < 4; i++) if (!ctx->fuse_ev[i] && hipEventCreate(&ctx->fuse_ev[i]) != hipSuccess) ev_on = false;
     if (ev_on) ev_on = hipEventRecord(ctx->fuse_ev[0], st) == hipSuccess;
     FuDev a; memset(&a, 0, sizeof(a));
-    a.kf = (const FuKf *)(d + u_kf); a.cq = (int)cq; a.ct = (int)ct; a.n_levels = P->n_levels; a.per_kf = per_kf ? 1 : 0; a.nb = (int)nb;
+    a.kf = u_kf.dev(d); a.cq = (int)cq; a.ct = (int)ct; a.n_levels = P->n_levels; a.per_kf = per_kf ? 1 : 0; a.nb = (int)nb;
     if (m) {
         a.pos = m->dev<float>(m->POS); a.nrm = m->dev<float>(m->NRM); a.maxd = m->dev<float>(m->MAXD); a.mind = m->dev<float>(m->MIND); a.mdesc = m->dev<uint8_t>(m->DESC);
-        a.flags = m->d_flags(); a.slots = (const int32_t *)(d + u_slots); a.cstride = (size_t)m->cap;
+        a.flags = m->d_flags(); a.slots = u_slots.dev(d); a.cstride = (size_t)m->cap;
     } else {
-        a.pos = (const float *)(d + u_pos); a.nrm = (const float *)(d + u_nrm); a.maxd = (const float *)(d + u_maxd); a.mind = (const float *)(d + u_mind);
-        a.mdesc = (const uint8_t *)(d + u_md); a.cstride = cq;
+        a.pos = u_pos.dev(d); a.nrm = u_nrm.dev(d); a.maxd = u_maxd.dev(d); a.mind = u_mind.dev(d);
+        a.mdesc = u_md.dev(d); a.cstride = cq;
     }
-    a.skip = (const uint8_t *)(d + u_skip); a.tab = (const float *)(d + u_tab);
+    a.skip = u_skip.dev(d); a.tab = u_tab.dev(d);
     a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy; a.bf = P->bf;
     a.minX = bounds[0]; a.maxX = bounds[1]; a.minY = bounds[2]; a.maxY = bounds[3];
     a.invW = (float)FU_COLS / (bounds[1] - bounds[0]); a.invH = (float)FU_ROWS / (bounds[3] - bounds[2]);      // mfGridElementWidthInv / HeightInv (Frame.cc:184-185)
     a.logsf = P->log_scale_factor; a.th = P->th; a.th_low = P->th_low;
-    a.cstart = (int *)(d + g_start); a.rec = (float4 *)(d + g_rec); a.item = (int32_t *)(d + g_item);
-    a.q_u = (float *)(d + q_u); a.q_v = (float *)(d + q_v); a.q_ur = (float *)(d + q_ur); a.q_rad = (float *)(d + q_rad);
-    a.proj = (float *)(d + r_proj); a.level = (int32_t *)(d + r_lvl); a.gate = (int8_t *)(d + r_gate); a.bi = (int32_t *)(d + r_bi); a.bd = (int32_t *)(d + r_bd);
-    a.fe = (int32_t *)(d + r_fe); a.fi = (int32_t *)(d + r_fi); a.pass = (uint8_t *)(d + s_pass); a.blockcnt = (int *)(d + s_bc);
-    a.nsearched = (int *)(d + r_cnt); a.nfused = (int *)(d + r_cnt) + F;
+    a.cstart = g_start.dev(d); a.rec = g_rec.dev(d); a.item = g_item.dev(d);
+    a.q_u = q_u.dev(d); a.q_v = q_v.dev(d); a.q_ur = q_ur.dev(d); a.q_rad = q_rad.dev(d);
+    a.proj = r_proj.dev(d); a.level = r_lvl.dev(d); a.gate = r_gate.dev(d); a.bi = r_bi.dev(d); a.bd = r_bd.dev(d);
+    a.fe = r_fe.dev(d); a.fi = r_fi.dev(d); a.pass = s_pass.dev(d); a.blockcnt = s_bc.dev(d);
+    a.nsearched = r_cnt.dev(d, 0); a.nfused = r_cnt.dev(d, 1);
     hipLaunchKernelGGL(k_fuse_grid, dim3(n_kf), dim3(FU_BLOCK), 0, st, a);
     if (ev_on) ev_on = hipEventRecord(ctx->fuse_ev[1], st) == hipSuccess;
     hipLaunchKernelGGL(k_fuse_project, dim3((unsigned)nb, n_kf), dim3(FU_BLOCK), 0, st, a);
@@ -379,22 +377,21 @@ static int fuse_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const h
     }
     float ms[3] = { 0.f, 0.f, 0.f };
     if (ev_on) for (int i = 0; i < 3; i++) if (hipEventElapsedTime(&ms[i], ctx->fuse_ev[i], ctx->fuse_ev[i + 1]) != hipSuccess) ms[i] = 0.f;
-    const char *b = hr.data() - r0;
+    const StageDown b = { hr.data(), r0 };
     for (int j = 0; j < n_kf; j++) {
         hvo_fuse_result &R = res[j];
-        const size_t n = (size_t)n_ent[j], q0 = (size_t)j * cq;
-        const int *cnt = (const int *)(b + r_cnt);
-        R.n_searched = cnt[j]; R.n_fused = cnt[F + j]; R.status = HVO_OK;
+        const size_t n = (size_t)n_ent[j];
+        R.n_searched = r_cnt.down(b, 0)[j]; R.n_fused = r_cnt.down(b, 1)[j]; R.status = HVO_OK;
         for (int i = 0; i < 3; i++) R.kernel_ms[i] = ms[i];
         if (!n) continue;
-        memcpy(R.best_idx, (const int32_t *)(b + r_bi) + q0, n * 4);
-        if (R.best_dist) memcpy(R.best_dist, (const int32_t *)(b + r_bd) + q0, n * 4);
-        if (R.gate) memcpy(R.gate, (const int8_t *)(b + r_gate) + q0, n);
-        if (R.level) memcpy(R.level, (const int32_t *)(b + r_lvl) + q0, n * 4);
-        if (R.proj) memcpy(R.proj, (const float *)(b + r_proj) + 3 * q0, n * 12);
+        memcpy(R.best_idx, r_bi.down(b, j), n * 4);
+        if (R.best_dist) memcpy(R.best_dist, r_bd.down(b, j), n * 4);
+        if (R.gate) memcpy(R.gate, r_gate.down(b, j), n);
+        if (R.level) memcpy(R.level, r_lvl.down(b, j), n * 4);
+        if (R.proj) memcpy(R.proj, r_proj.down(b, j), n * 12);
         const size_t nf = (size_t)std::max(0, std::min(R.n_fused, (int32_t)n));
-        if (R.fused_entry) memcpy(R.fused_entry, (const int32_t *)(b + r_fe) + q0, nf * 4);
-        if (R.fused_idx) memcpy(R.fused_idx, (const int32_t *)(b + r_fi) + q0, nf * 4);
+        if (R.fused_entry) memcpy(R.fused_entry, r_fe.down(b, j), nf * 4);
+        if (R.fused_idx) memcpy(R.fused_idx, r_fi.down(b, j), nf * 4);
     }
     return HVO_OK;
 }

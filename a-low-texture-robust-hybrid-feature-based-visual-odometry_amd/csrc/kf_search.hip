@@ -130,78 +130,73 @@ int kfs_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_kf_se
     for (int j = 0; j < n_kf; j++) if (kf[j].n > KFS_MAXQ || nt > KFS_MAXT) { *err = kfs_limit_text(kf[j].n, nt); return HVO_ERR_UNSUPPORTED; }
     // ---- one carve of the context's arena: what goes up, the queries, what comes down, the search's key rows ----
     const size_t cq = (size_t)std::max(64, (nmax + 63) & ~63), ntp = (size_t)std::max(64, (nt + 63) & ~63), F = (size_t)n_kf;
-    SmCarve C;
-    const size_t u_cand = C.take(F * sizeof(KfsCand)), u_pos = C.take(F * 3 * cq * 4), u_maxd = C.take(F * cq * 4), u_mind = C.take(F * cq * 4), u_ang = C.take(F * cq * 4),
-                 u_desc = C.take(F * cq * 32), u_skip = C.take(F * cq), u_occ = C.take(F * ntp);
-    const size_t u_kp = C.take(host ? ntp * sizeof(hvo_keypoint) : 0), u_fd = C.take(host ? ntp * 32 : 0);
-    const size_t up_end = C.o;
-    const size_t q_u = C.take(F * cq * 4), q_v = C.take(F * cq * 4), q_rad = C.take(F * cq * 4), q_min = C.take(F * cq * 4), q_max = C.take(F * cq * 4), q_blk = C.take(F * cq);
-    const size_t r0 = C.o;
-    const size_t r_cnt = C.take(F * 2 * 4), r_fk = C.take(F * ntp * 4), r_mi = C.take(F * cq * 4), r_md = C.take(F * cq * 4), r_lvl = C.take(F * cq * 4),
-                 r_proj = C.take(F * cq * 8), r_gate = C.take(F * cq);
-    const size_t r1 = C.o;                                       // [r0, r1) comes down
-    const size_t s_keys = C.take(match_sbp_scratch_bytes((int)cq));      // the candidates' searches run one after the other on the stream and share the key rows
-    char *d = (char *)hvo_call_arena(ctx, C.o);
+    StageCarver C(256);
+    const auto u_cand = C.take<KfsCand>(F);
+    const auto u_pos = C.take<float>(3 * F, cq), u_maxd = C.take<float>(F, cq), u_mind = C.take<float>(F, cq), u_ang = C.take<float>(F, cq);      // pos by component: row 3 j + k
+    const auto u_desc = C.take<uint8_t>(F, cq * 32), u_skip = C.take<uint8_t>(F, cq), u_occ = C.take<uint8_t>(F, ntp);
+    const auto u_kp = C.take<hvo_keypoint>(host ? ntp : 0); const auto u_fd = C.take<uint8_t>(host ? ntp * 32 : 0);
+    const size_t up_end = C.mark();
+    const auto q_u = C.take<float>(F, cq), q_v = C.take<float>(F, cq), q_rad = C.take<float>(F, cq);
+    const auto q_min = C.take<int>(F, cq), q_max = C.take<int>(F, cq); const auto q_blk = C.take<uint8_t>(F, cq);
+    const size_t r0 = C.mark();
+    const auto r_cnt = C.take<int>(F, 2), r_fk = C.take<int32_t>(F, ntp), r_mi = C.take<int32_t>(F, cq), r_md = C.take<int32_t>(F, cq), r_lvl = C.take<int32_t>(F, cq);
+    const auto r_proj = C.take<float>(F, cq * 2); const auto r_gate = C.take<int8_t>(F, cq);
+    const size_t r1 = C.mark();                                  // [r0, r1) comes down
+    const auto s_keys = C.take<char>(match_sbp_scratch_bytes((int)cq));  // the candidates' searches run one after the other on the stream and share the key rows
+    char *d = (char *)hvo_call_arena(ctx, C.mark());
     if (!d) { *err = "key-frame search: arena"; return HVO_ERR_HIP; }
-    std::vector<char> h(up_end, 0);
+    std::vector<char> hv(up_end, 0); char *const h = hv.data();
     for (int j = 0; j < n_kf; j++) {
         const hvo_kf_search_candidate &K = kf[j];
-        KfsCand &c = ((KfsCand *)&h[u_cand])[j];
-        for (int r = 0; r < 3; r++) { for (int k = 0; k < 3; k++) c.R[3 * r + k] = K.Tcw[4 * r + k]; c.t[r] = K.Tcw[4 * r + 3]; }
-        for (int r = 0; r < 3; r++) {                              // Ow = -Rcw^T tcw (match_project_setup's twc)
-            double s0 = 0;
-            for (int k = 0; k < 3; k++) s0 += (double)c.R[3 * k + r] * (double)c.t[k];
-            c.Ow[r] = (float)(s0 * -1.0);
-        }
+        KfsCand &c = *u_cand.host(h, j);
+        pose_split(K.Tcw, c.R, c.t, c.Ow);                         // Ow = -Rcw^T tcw (match_project_setup's twc)
         c.n = K.n;
         const size_t n = (size_t)K.n;
-        float *hp = (float *)&h[u_pos] + (size_t)j * 3 * cq;
-        for (size_t i = 0; i < n; i++) if (!K.skip[i]) for (int k = 0; k < 3; k++) hp[k * cq + i] = K.pos[3 * i + k];      // by component: a wave's load is contiguous
+        float *const hp[3] = { u_pos.host(h, 3 * j), u_pos.host(h, 3 * j + 1), u_pos.host(h, 3 * j + 2) };
+        for (size_t i = 0; i < n; i++) if (!K.skip[i]) for (int k = 0; k < 3; k++) hp[k][i] = K.pos[3 * i + k];      // by component: a wave's load is contiguous
         if (n) {
-            memcpy((float *)&h[u_maxd] + j * cq, K.max_dist, n * 4); memcpy((float *)&h[u_mind] + j * cq, K.min_dist, n * 4);
-            if (K.angle) memcpy((float *)&h[u_ang] + j * cq, K.angle, n * 4);
-            memcpy(&h[u_desc] + j * cq * 32, K.desc, n * 32); memcpy(&h[u_skip] + j * cq, K.skip, n);
+            memcpy(u_maxd.host(h, j), K.max_dist, n * 4); memcpy(u_mind.host(h, j), K.min_dist, n * 4);
+            if (K.angle) memcpy(u_ang.host(h, j), K.angle, n * 4);
+            memcpy(u_desc.host(h, j), K.desc, n * 32); memcpy(u_skip.host(h, j), K.skip, n);
         }
-        if (nt && K.occupied) memcpy(&h[u_occ] + j * ntp, K.occupied, (size_t)nt);
+        if (nt && K.occupied) memcpy(u_occ.host(h, j), K.occupied, (size_t)nt);
     }
     FrameView V = *fr;
     if (host) {
-        if (nt) { memcpy(&h[u_kp], host->kp_un, (size_t)nt * sizeof(hvo_keypoint)); memcpy(&h[u_fd], host->desc, (size_t)nt * 32); }
-        V.kp_un = (const hvo_keypoint *)(d + u_kp); V.desc = (const uint8_t *)(d + u_fd);
+        if (nt) { memcpy(u_kp.host(h), host->kp_un, (size_t)nt * sizeof(hvo_keypoint)); memcpy(u_fd.host(h), host->desc, (size_t)nt * 32); }
+        V.kp_un = u_kp.dev(d); V.desc = u_fd.dev(d);
     }
-    if (hipMemcpyAsync(d, h.data(), up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = "key-frame search: upload"; return HVO_ERR_HIP; }
+    if (hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = "key-frame search: upload"; return HVO_ERR_HIP; }
     // (the memsets follow the copy: a copy from pageable memory waits for what the stream holds)
-    if (hipMemsetAsync(d + r_cnt, 0, F * 2 * 4, st) != hipSuccess || hipMemsetAsync(d + r_fk, 0xFF, F * ntp * 4, st) != hipSuccess) { *err = "key-frame search: memset"; return HVO_ERR_HIP; }
+    if (hipMemsetAsync(r_cnt.dev(d), 0, r_cnt.bytes(), st) != hipSuccess || hipMemsetAsync(r_fk.dev(d), 0xFF, r_fk.bytes(), st) != hipSuccess) { *err = "key-frame search: memset"; return HVO_ERR_HIP; }
     bool ev_on = true;
     for (int i = 0; i < 3; i++) if (!ctx->kfs_ev[i] && hipEventCreate(&ctx->kfs_ev[i]) != hipSuccess) ev_on = false;
     if (ev_on) ev_on = hipEventRecord(ctx->kfs_ev[0], st) == hipSuccess;
     KfsDev a; memset(&a, 0, sizeof(a));
-    a.cand = (const KfsCand *)(d + u_cand); a.cq = (int)cq; a.n_levels = P->n_levels;
-    a.pos = (const float *)(d + u_pos); a.maxd = (const float *)(d + u_maxd); a.mind = (const float *)(d + u_mind); a.skip = (const uint8_t *)(d + u_skip);
+    a.cand = u_cand.dev(d); a.cq = (int)cq; a.n_levels = P->n_levels;
+    a.pos = u_pos.dev(d); a.maxd = u_maxd.dev(d); a.mind = u_mind.dev(d); a.skip = u_skip.dev(d);
     a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy;
     a.minX = V.bounds[0]; a.maxX = V.bounds[1]; a.minY = V.bounds[2]; a.maxY = V.bounds[3]; a.logsf = P->log_scale_factor; a.th = P->th;
     for (int l = 0; l < HVO_MAX_LEVELS; l++) a.sf[l] = V.sf[l];
-    a.q_u = (float *)(d + q_u); a.q_v = (float *)(d + q_v); a.q_rad = (float *)(d + q_rad); a.q_min = (int *)(d + q_min); a.q_max = (int *)(d + q_max); a.q_blocks = (uint8_t *)(d + q_blk);
-    a.proj = (float *)(d + r_proj); a.level = (int32_t *)(d + r_lvl); a.gate = (int8_t *)(d + r_gate); a.mi = (int32_t *)(d + r_mi); a.md = (int32_t *)(d + r_md);
-    a.counters = (int *)(d + r_cnt);
+    a.q_u = q_u.dev(d); a.q_v = q_v.dev(d); a.q_rad = q_rad.dev(d); a.q_min = q_min.dev(d); a.q_max = q_max.dev(d); a.q_blocks = q_blk.dev(d);
+    a.proj = r_proj.dev(d); a.level = r_lvl.dev(d); a.gate = r_gate.dev(d); a.mi = r_mi.dev(d); a.md = r_md.dev(d);
+    a.counters = r_cnt.dev(d);
     if (nmax > 0) hipLaunchKernelGGL(k_kf_project, dim3((nmax + KFS_BLOCK - 1) / KFS_BLOCK, n_kf), dim3(KFS_BLOCK), 0, st, a);
     if (ev_on) ev_on = hipEventRecord(ctx->kfs_ev[1], st) == hipSuccess;
     for (int j = 0; j < n_kf; j++) {
         const int n = kf[j].n;
         if (n < 1 || nt < 1) continue;
-        const size_t q0 = (size_t)j * cq;
         SbpDev s; memset(&s, 0, sizeof(s));
-        s.q_desc = (const uint8_t *)(d + u_desc) + 32 * q0; s.q_desc_index = nullptr;
-        s.q_u = a.q_u + q0; s.q_v = a.q_v + q0; s.q_radius = a.q_rad + q0; s.q_min_level = a.q_min + q0; s.q_max_level = a.q_max + q0; s.q_ur = nullptr;
-        s.q_angle = (const float *)(d + u_ang) + q0; s.q_blocks = a.q_blocks + q0;
-        s.t_kp = V.kp_un; s.t_uright = nullptr; s.t_occ = kf[j].occupied ? (const uint8_t *)(d + u_occ) + (size_t)j * ntp : nullptr; s.t_desc = V.desc;
+        s.q_desc = u_desc.dev(d, j); s.q_desc_index = nullptr;
+        s.q_u = q_u.dev(d, j); s.q_v = q_v.dev(d, j); s.q_radius = q_rad.dev(d, j); s.q_min_level = q_min.dev(d, j); s.q_max_level = q_max.dev(d, j); s.q_ur = nullptr;
+        s.q_angle = u_ang.dev(d, j); s.q_blocks = q_blk.dev(d, j);
+        s.t_kp = V.kp_un; s.t_uright = nullptr; s.t_occ = kf[j].occupied ? u_occ.dev(d, j) : nullptr; s.t_desc = V.desc;
         s.nq = n; s.nt = nt; s.mnMinX = V.bounds[0]; s.mnMaxX = V.bounds[1]; s.mnMinY = V.bounds[2]; s.mnMaxY = V.bounds[3];
         s.th_high = P->orb_dist; s.check_orientation = P->check_orientation ? 1 : 0; s.map_mode = 0; s.nn_ratio = 0.f;
-        s.match_idx = a.mi + q0; s.match_dist = a.md + q0; s.n_matches = a.counters + 2 * j;
-        const int rc = match_sbp_enqueue(st, s, d + s_keys);
+        s.match_idx = r_mi.dev(d, j); s.match_dist = r_md.dev(d, j); s.n_matches = r_cnt.dev(d, j);
+        const int rc = match_sbp_enqueue(st, s, s_keys.dev(d));
         if (rc) { *err = rc == HVO_ERR_UNSUPPORTED ? kfs_limit_text(n, nt) : "key-frame search: search launch"; return rc; }
-        hipLaunchKernelGGL(k_kf_inverse, dim3((n + KFS_BLOCK - 1) / KFS_BLOCK), dim3(KFS_BLOCK), 0, st, n, nt, (const int32_t *)s.match_idx, s.match_dist,
-                           (int32_t *)(d + r_fk) + (size_t)j * ntp);
+        hipLaunchKernelGGL(k_kf_inverse, dim3((n + KFS_BLOCK - 1) / KFS_BLOCK), dim3(KFS_BLOCK), 0, st, n, nt, (const int32_t *)s.match_idx, s.match_dist, r_fk.dev(d, j));
     }
     if (ev_on) ev_on = hipEventRecord(ctx->kfs_ev[2], st) == hipSuccess;
     if (hipGetLastError() != hipSuccess) { *err = "key-frame search: launch"; return HVO_ERR_HIP; }
@@ -214,20 +209,20 @@ int kfs_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_kf_se
         if (hipEventElapsedTime(&ms[0], ctx->kfs_ev[0], ctx->kfs_ev[1]) != hipSuccess) ms[0] = 0.f;
         if (hipEventElapsedTime(&ms[1], ctx->kfs_ev[1], ctx->kfs_ev[2]) != hipSuccess) ms[1] = 0.f;
     }
-    const char *b = hr.data() - r0;
+    const StageDown b = { hr.data(), r0 };
     for (int j = 0; j < n_kf; j++) {
         hvo_kf_search_result &R = res[j];
-        const size_t n = (size_t)kf[j].n, q0 = (size_t)j * cq;
-        const int *cnt = (const int *)(b + r_cnt) + 2 * j;
+        const size_t n = (size_t)kf[j].n;
+        const int *cnt = r_cnt.down(b, j);
         R.n_matches = cnt[0]; R.n_searched = cnt[1]; R.status = HVO_OK; R.kernel_ms[0] = ms[0]; R.kernel_ms[1] = ms[1];
         if (n) {
-            memcpy(R.match_idx, (const int32_t *)(b + r_mi) + q0, n * 4);
-            if (R.match_dist) memcpy(R.match_dist, (const int32_t *)(b + r_md) + q0, n * 4);
-            if (R.proj) memcpy(R.proj, (const float *)(b + r_proj) + 2 * q0, n * 8);
-            if (R.level) memcpy(R.level, (const int32_t *)(b + r_lvl) + q0, n * 4);
-            if (R.gate) memcpy(R.gate, (const int8_t *)(b + r_gate) + q0, n);
+            memcpy(R.match_idx, r_mi.down(b, j), n * 4);
+            if (R.match_dist) memcpy(R.match_dist, r_md.down(b, j), n * 4);
+            if (R.proj) memcpy(R.proj, r_proj.down(b, j), n * 8);
+            if (R.level) memcpy(R.level, r_lvl.down(b, j), n * 4);
+            if (R.gate) memcpy(R.gate, r_gate.down(b, j), n);
         }
-        if (R.feature_kf && nt) memcpy(R.feature_kf, (const int32_t *)(b + r_fk) + (size_t)j * ntp, (size_t)nt * 4);
+        if (R.feature_kf && nt) memcpy(R.feature_kf, r_fk.down(b, j), (size_t)nt * 4);
     }
     return HVO_OK;
 }

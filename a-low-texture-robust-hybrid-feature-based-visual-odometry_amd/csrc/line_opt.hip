@@ -17,6 +17,7 @@
 // pivot is exactly 0 or not finite, in any line's block; the step of a failed solve is taken as zero (the trial is rejected either way);
 // classification re-evaluates an edge at the end points of the round's last computeActiveErrors instead of storing _error.
 #include "frame_view.hpp"
+#include "call_stage.hpp"
 #include <math.h>
 #include <cmath>
 #include <string.h>
@@ -416,8 +417,6 @@ extern "C" int hvo_line_struct_default_params(hvo_line_struct_params *p)
     return HVO_OK;
 }
 
-static size_t ls_al(size_t v) { return (v + 63) & ~(size_t)63; }
-
 // Layout of one call in the context's call arena / pinned staging block:
 //   [LsFrame x n | per frame: (host form) linefn, records | rel]  up to here the upload (rel only when the caller's is read)
 //   [per frame: rel | out6] [results]                              the download; then the kernel's own scratch (lev, est, trial, Hb, ent)
@@ -429,10 +428,10 @@ int ls_run(hvo_ctx *ctx, hipStream_t st, const hvo_line_struct_params *params, i
     const bool part1 = (P.mode & HVO_LINE_STRUCT_CONSTRAINTS) != 0, part2 = (P.mode & HVO_LINE_STRUCT_OPTIMIZE) != 0;
     if (!part1 && !part2) { *err = "line structure: mode selects neither part"; return HVO_ERR_INVALID_ARG; }
     if (P.iterations < 0 || (P.row_rule != HVO_LINE_STRUCT_ROW_UNSET && P.row_rule != HVO_LINE_STRUCT_ROW_Z0)) { *err = "line structure: bad params"; return HVO_ERR_INVALID_ARG; }
-    struct Off { size_t fn, rec, rel, out6, lev, est, trial, Hb, ent; };
-    std::vector<Off> O((size_t)n);
-    size_t at = ls_al((size_t)n * sizeof(LsFrame));
-    auto take = [&](size_t bytes) { const size_t a = at; at += ls_al(bytes); return a; };
+    struct Pieces { StagePiece<double> fn, out6, est, trial, Hb; StagePiece<hvo_line3d> rec; StagePiece<int8_t> rel; StagePiece<uint8_t> lev, ent; };
+    std::vector<Pieces> O((size_t)n);
+    StageCarver C(64);
+    const auto frames = C.take<LsFrame>((size_t)n);
     int cap_max = 0;
     for (int f = 0; f < n; f++) {
         const int c = n_lines[f];
@@ -441,43 +440,42 @@ int ls_run(hvo_ctx *ctx, hipStream_t st, const hvo_line_struct_params *params, i
         if (c && (!rel || !rel[f])) { *err = "line structure: rel is NULL"; return HVO_ERR_INVALID_ARG; }
         if (c && !fr && (!prob[f].lines3d || (part1 && !prob[f].linefn))) { *err = "line structure: a needed array is NULL"; return HVO_ERR_INVALID_ARG; }
         cap_max = c > cap_max ? c : cap_max;
-        O[f].fn = O[f].rec = 0;
-        if (!fr) { O[f].fn = take((size_t)c * 24); O[f].rec = take((size_t)c * sizeof(hvo_line3d)); }
+        if (!fr) { O[f].fn = C.take<double>((size_t)c, 3); O[f].rec = C.take<hvo_line3d>((size_t)c); }
     }
-    const size_t down0 = at;                                                 // rel is the first thing that comes down, and goes up when it is the caller's
-    for (int f = 0; f < n; f++) O[f].rel = take((size_t)n_lines[f] * n_lines[f]);
-    const size_t up_end = part1 ? down0 : at;
-    for (int f = 0; f < n; f++) O[f].out6 = take((size_t)n_lines[f] * 48);
-    const size_t res_off = take((size_t)n * sizeof(hvo_line_opt_result));
-    const size_t down_end = at;
+    const size_t down0 = C.mark();                                           // rel is the first thing that comes down, and goes up when it is the caller's
+    for (int f = 0; f < n; f++) O[f].rel = C.take<int8_t>((size_t)n_lines[f], (size_t)n_lines[f]);
+    const size_t up_end = part1 ? down0 : C.mark();
+    for (int f = 0; f < n; f++) O[f].out6 = C.take<double>((size_t)n_lines[f], 6);
+    const auto results = C.take<hvo_line_opt_result>((size_t)n);
+    const size_t down_end = C.mark();
     for (int f = 0; f < n; f++) {
         const size_t c = (size_t)n_lines[f];
-        O[f].lev = take(part2 ? c * c : 0); O[f].est = take(c * 48); O[f].trial = take(c * 48); O[f].Hb = take(c * 27 * 8); O[f].ent = take(c * 2);
+        O[f].lev = C.take<uint8_t>(part2 ? c : 0, c); O[f].est = C.take<double>(c, 6); O[f].trial = C.take<double>(c, 6); O[f].Hb = C.take<double>(c, 27);
+        O[f].ent = C.take<uint8_t>(c, 2);
     }
-    char *d = (char *)hvo_call_arena(ctx, at);
-    char *h = (char *)hvo_stage_host(ctx, down_end);
+    char *d = (char *)hvo_call_arena(ctx, C.mark());
+    char *h = (char *)hvo_stage_host(ctx, down_end);                         // the arena's [0, down_end) at the same offsets
     if (!d || !h) { *err = "line structure: scratch"; return HVO_ERR_HIP; }
-    LsFrame *hf = (LsFrame *)h;
     for (int f = 0; f < n; f++) {
         const size_t c = (size_t)n_lines[f];
-        LsFrame &F = hf[f]; memset(&F, 0, sizeof(F));
+        LsFrame &F = *frames.host(h, f); memset(&F, 0, sizeof(F));
         F.n_cap = (int)c;
         if (fr) { F.d_nkl = fr[f].d_nkl; F.linefn = fr[f].fn; F.l3d = fr[f].l3d; }
         else {
-            if (c && prob[f].linefn) memcpy(h + O[f].fn, prob[f].linefn, c * 24);
-            if (c) memcpy(h + O[f].rec, prob[f].lines3d, c * sizeof(hvo_line3d));
-            F.linefn = (const double *)(d + O[f].fn); F.l3d = (hvo_line3d *)(d + O[f].rec);
+            if (c && prob[f].linefn) memcpy(O[f].fn.host(h), prob[f].linefn, c * 24);
+            if (c) memcpy(O[f].rec.host(h), prob[f].lines3d, c * sizeof(hvo_line3d));
+            F.linefn = O[f].fn.dev(d); F.l3d = O[f].rec.dev(d);
         }
         if (!part1 && c) {
             for (size_t i = 0; i < c * c; i++) { const int8_t v = rel[f][i]; if (v < -2 || v > 2) { *err = "line structure: rel holds a value outside -2 .. 2"; return HVO_ERR_INVALID_ARG; } }
-            memcpy(h + O[f].rel, rel[f], c * c);
+            memcpy(O[f].rel.host(h), rel[f], c * c);
         }
-        F.rel = (int8_t *)(d + O[f].rel); F.lev = (uint8_t *)(d + O[f].lev);
-        F.est = (double *)(d + O[f].est); F.trial = (double *)(d + O[f].trial); F.Hb = (double *)(d + O[f].Hb); F.ent = (uint8_t *)(d + O[f].ent);
-        F.out6 = (double *)(d + O[f].out6);
+        F.rel = O[f].rel.dev(d); F.lev = O[f].lev.dev(d);
+        F.est = O[f].est.dev(d); F.trial = O[f].trial.dev(d); F.Hb = O[f].Hb.dev(d); F.ent = O[f].ent.dev(d);
+        F.out6 = O[f].out6.dev(d);
     }
     LsArgs A; memset(&A, 0, sizeof(A));
-    A.frames = (const LsFrame *)d; A.res = (hvo_line_opt_result *)(d + res_off);
+    A.frames = frames.dev(d); A.res = results.dev(d);
     A.cos_par = P.cos_par; A.cos_perp = P.cos_perp; A.delta = P.huber_delta; A.chi2_reject = P.chi2_reject;
     A.chi2_round[0] = P.chi2_round[0]; A.chi2_round[1] = P.chi2_round[1];
     A.min_constraints = P.min_constraints; A.iterations = P.iterations; A.row_rule = P.row_rule;
@@ -502,11 +500,11 @@ int ls_run(hvo_ctx *ctx, hipStream_t st, const hvo_line_struct_params *params, i
 #undef LS_HIP
     if (!part1) ctx->ls_ms[0] = 0.f;
     if (!part2) ctx->ls_ms[1] = 0.f;
-    memcpy(res, h + res_off, (size_t)n * sizeof(hvo_line_opt_result));
+    memcpy(res, results.host(h), results.bytes());
     for (int f = 0; f < n; f++) {
         const size_t c = (size_t)n_lines[f];
-        if (c) memcpy(rel[f], h + O[f].rel, c * c);
-        if (c && l3d_out && l3d_out[f]) memcpy(l3d_out[f], h + O[f].out6, c * 48);
+        if (c) memcpy(rel[f], O[f].rel.host(h), c * c);
+        if (c && l3d_out && l3d_out[f]) memcpy(l3d_out[f], O[f].out6.host(h), c * 48);
     }
     return HVO_OK;
 }

@@ -335,10 +335,10 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
             res[f].status = HVO_ERR_UNSUPPORTED; m->last_error = match_lsbp_map_limit_text(cnt[f], fr[f].n_kl); return HVO_ERR_UNSUPPORTED;
         }
         if (cnt[f] > 0 && fr[f].n_kl > 0) sb = std::max(sb, match_lsbp_map_scratch_bytes(cnt[f], fr[f].n_kl));
-        if (io[f].rel_map) rb = std::max(rb, sm_al((size_t)cnt[f] * (size_t)fr[f].n_kl));
+        if (io[f].rel_map) rb = std::max(rb, stage_align((size_t)cnt[f] * (size_t)fr[f].n_kl));
     }
     // ---- scratch B: the search's key rows and the relation matrix ----
-    if ((rc = sm_grow(m, st, &m->d_b, &m->b_bytes, sm_al(sb) + F * rb + 256))) return rc;
+    if ((rc = sm_grow(m, st, &m->d_b, &m->b_bytes, stage_align(sb) + F * rb + 256))) return rc;
     LlGate G;
     ll_kinv(cam, G.Ki);
     for (int f = 0; f < nframes; f++) {
@@ -367,7 +367,7 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
         for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) G.R[3 * r + c] = T[4 * r + c];
         int32_t *d_mi = (int32_t *)(A + o_mi) + (size_t)f * capq;
         int *d_k = (int *)(A + o_k[f]), *d_win = (int *)(A + S[f].o_win);
-        int8_t *d_rel = io[f].rel_map ? (int8_t *)(m->d_b + sm_al(sb) + (size_t)f * rb) : nullptr;
+        int8_t *d_rel = io[f].rel_map ? (int8_t *)(m->d_b + stage_align(sb) + (size_t)f * rb) : nullptr;
         if (nq > 0) sm_assign_enqueue(st, nq, nt, d_mi, d_win);
         hipLaunchKernelGGL(k_ll_gate, dim3((nt + LL_BLOCK - 1) / LL_BLOCK), dim3(LL_BLOCK), 0, st, nt, (size_t)m->cap, a.wvec, fr[f].kl, d_win,
                            a.q_slot + (size_t)f * capq, d_k, G, (int32_t *)(A + S[f].o_held), d_k + 1);
@@ -394,7 +394,7 @@ int ll_run(hipStream_t st, hvo_line_map *m, const hvo_camera *cam, const hvo_loc
             if (I.level) SM_HIP(hipMemcpyAsync(I.level, a.q_lvl + q0, nq * 4, hipMemcpyDeviceToHost, st));
             if (I.match_idx) SM_HIP(hipMemcpyAsync(I.match_idx, (int32_t *)(A + o_mi) + q0, nq * 4, hipMemcpyDeviceToHost, st));
             if (I.match_dist) SM_HIP(hipMemcpyAsync(I.match_dist, (int32_t *)(A + o_md) + q0, nq * 4, hipMemcpyDeviceToHost, st));
-            if (I.rel_map && nt) SM_HIP(hipMemcpyAsync(I.rel_map, m->d_b + sm_al(sb) + (size_t)f * rb, nq * nt, hipMemcpyDeviceToHost, st));
+            if (I.rel_map && nt) SM_HIP(hipMemcpyAsync(I.rel_map, m->d_b + stage_align(sb) + (size_t)f * rb, nq * nt, hipMemcpyDeviceToHost, st));
         }
     }
     SM_HIP(hipStreamSynchronize(st));

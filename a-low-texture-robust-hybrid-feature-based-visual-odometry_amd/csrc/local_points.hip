@@ -267,7 +267,7 @@ int lp_run(hipStream_t st, hvo_point_map *m, const hvo_camera *cam, const hvo_lo
         if (cnt[f] > 0 && fr[f].n_kp > 0) sb = std::max(sb, match_sbp_scratch_bytes(cnt[f]));
     }
     // ---- scratch B: the search's key rows (the frames' searches run one after the other on the stream and share them) ----
-    if ((rc = sm_grow(m, st, &m->d_b, &m->b_bytes, sm_al(sb) + 256))) return rc;
+    if ((rc = sm_grow(m, st, &m->d_b, &m->b_bytes, stage_align(sb) + 256))) return rc;
     ProjDev W; memset(&W, 0, sizeof(W));
     for (int l = 0; l < HVO_MAX_LEVELS; l++) W.sf[l] = sf[l];
     for (int f = 0; f < nframes; f++) {

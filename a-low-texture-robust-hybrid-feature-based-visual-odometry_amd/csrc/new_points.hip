@@ -345,19 +345,10 @@ static void np_mul3(const float *A, const float *B, float *C)
 {
     for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) C[3 * r + c] = np_dot3f(A[3 * r], A[3 * r + 1], A[3 * r + 2], B[c], B[3 + c], B[6 + c]);
 }
-static void np_pose(const float *Tcw, float *R, float *t, float *Ow)
-{
-    for (int r = 0; r < 3; r++) { for (int q = 0; q < 3; q++) R[3 * r + q] = Tcw[4 * r + q]; t[r] = Tcw[4 * r + 3]; }
-    for (int r = 0; r < 3; r++) {
-        double s0 = 0;
-        for (int q = 0; q < 3; q++) s0 += (double)R[3 * q + r] * (double)t[q];
-        Ow[r] = (float)(s0 * -1.0);
-    }
-}
 // Ow2, the baseline gate, ComputeF12 and the epipole of one neighbour (about 60 float operations; the restatement fixes the bits)
 static void np_neighbour(const hvo_camera *cam, const float *R1, const float *t1, const float *Ow1, const hvo_np_keyframe &K, NpKf &c)
 {
-    np_pose(K.Tcw, c.R, c.t, c.Ow);
+    pose_split(K.Tcw, c.R, c.t, c.Ow);
     c.mb = K.mb; c.n = K.n; c.stereo = (K.uright && K.depth) ? 1 : 0;
     const float baseline = (float)np_normd(c.Ow[0] - Ow1[0], c.Ow[1] - Ow1[1], c.Ow[2] - Ow1[2]);
     c.gate = K.skip ? HVO_NP_GATE_SKIP : (baseline < K.mb ? HVO_NP_GATE_BASELINE : HVO_NP_GATE_SEARCHED);
@@ -407,7 +398,7 @@ static int np_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo
     const size_t F = (size_t)n_kf;
     std::vector<NpKf> hk(F);
     float R1[9], t1[3], Ow1[3];
-    np_pose(cur->Tcw, R1, t1, Ow1);
+    pose_split(cur->Tcw, R1, t1, Ow1);
     for (int j = 0; j < n_kf; j++) np_neighbour(cam, R1, t1, Ow1, kf[j], hk[j]);
     sum->n_new = 0; for (int q = 0; q < 3; q++) sum->kernel_ms[q] = 0.f;
     if (n1 == 0 || n_kf == 0) {
@@ -420,47 +411,50 @@ static int np_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo
     const bool c_raw = !fr && cur->kp, c_st = !fr && cur->uright;
     bool k_raw = false;
     for (int j = 0; j < n_kf; j++) k_raw = k_raw || kf[j].kp;
-    SmCarve C;
-    const size_t u_kf = C.take(F * sizeof(NpKf)), u_tab = C.take(2 * HVO_MAX_LEVELS * 4), u_n = C.take(F * 4), u_chas = C.take(cq);
-    const size_t u_ckp = C.take(fr ? 0 : cq * sizeof(hvo_keypoint)), u_ckr = C.take(c_raw ? cq * sizeof(hvo_keypoint) : 0), u_cur = C.take(c_st ? cq * 4 : 0),
-                 u_cdp = C.take(c_st ? cq * 4 : 0), u_cds = C.take(fr ? 0 : cq * 32), u_cnd = C.take(fr ? 0 : cq * 4);
-    const size_t u_kp = C.take(F * ct * sizeof(hvo_keypoint)), u_kr = C.take(k_raw ? F * ct * sizeof(hvo_keypoint) : 0), u_ur = C.take(F * ct * 4), u_dp = C.take(F * ct * 4),
-                 u_ds = C.take(F * ct * 32), u_nd = C.take(F * ct * 4), u_has = C.take(F * ct);
-    const size_t up_end = C.o;
-    const size_t g_node = C.take(F * ct * 4), g_start = C.take(F * (ct + 1) * 4), g_idx = C.take(F * ct * 4), g_rows = C.take(F * 4);
-    const size_t z0 = C.o;                                           // [z0, z1) is zeroed
-    const size_t s_pass = C.take(F * cq), s_bc = C.take(F * nb * 4);
-    const size_t r0 = C.o;                                           // [r0, r1) comes down; its head belongs to the zeroed range
-    const size_t r_cnt = C.take(F * 4);
-    const size_t z1 = C.o;
-    const size_t r_mi = C.take(F * cq * 4), r_md = C.take(F * cq * 4), r_out = C.take(F * cq), r_br = C.take(F * cq), r_x = C.take(F * cq * 12),
-                 r_c1 = C.take(F * cq * 4), r_c2 = C.take(F * cq * 4), r_own = C.take(cq * 4);
-    const size_t r1 = C.o;
-    char *d = (char *)hvo_call_arena(ctx, C.o);
+    StageCarver C(256);
+    const auto u_kf = C.take<NpKf>(F); const auto u_tab = C.take<float>(2 * HVO_MAX_LEVELS); const auto u_n = C.take<int>(F); const auto u_chas = C.take<uint8_t>(cq);
+    const auto u_ckp = C.take<hvo_keypoint>(fr ? 0 : cq), u_ckr = C.take<hvo_keypoint>(c_raw ? cq : 0);
+    const auto u_cur = C.take<float>(c_st ? cq : 0), u_cdp = C.take<float>(c_st ? cq : 0);
+    const auto u_cds = C.take<uint8_t>(fr ? 0 : cq * 32); const auto u_cnd = C.take<int>(fr ? 0 : cq);
+    const auto u_kp = C.take<hvo_keypoint>(F, ct), u_kr = C.take<hvo_keypoint>(k_raw ? F : 0, ct);
+    const auto u_ur = C.take<float>(F, ct), u_dp = C.take<float>(F, ct);
+    const auto u_ds = C.take<uint8_t>(F, ct * 32); const auto u_nd = C.take<int>(F, ct); const auto u_has = C.take<uint8_t>(F, ct);
+    const size_t up_end = C.mark();
+    const auto g_node = C.take<int>(F, ct), g_start = C.take<int>(F, ct + 1), g_idx = C.take<int>(F, ct), g_rows = C.take<int>(F);
+    const size_t z0 = C.mark();                                      // [z0, z1) is zeroed
+    const auto s_pass = C.take<uint8_t>(F, cq); const auto s_bc = C.take<int>(F, nb);
+    const size_t r0 = C.mark();                                      // [r0, r1) comes down; its head belongs to the zeroed range
+    const auto r_cnt = C.take<int>(F);
+    const size_t z1 = C.mark();
+    const auto r_mi = C.take<int32_t>(F, cq), r_md = C.take<int32_t>(F, cq);
+    const auto r_out = C.take<int8_t>(F, cq), r_br = C.take<int8_t>(F, cq); const auto r_x = C.take<float>(F, cq * 3);
+    const auto r_c1 = C.take<int32_t>(F, cq), r_c2 = C.take<int32_t>(F, cq), r_own = C.take<int32_t>(cq);
+    const size_t r1 = C.mark();
+    char *d = (char *)hvo_call_arena(ctx, C.mark());
     if (!d) { *err = "create new map points: arena"; return HVO_ERR_HIP; }
-    std::vector<char> h(up_end, 0);
-    memcpy(&h[u_kf], hk.data(), F * sizeof(NpKf));
-    float *tab = (float *)&h[u_tab];
+    std::vector<char> hv(up_end, 0); char *const h = hv.data();
+    memcpy(u_kf.host(h), hk.data(), F * sizeof(NpKf));
+    float *tab = u_tab.host(h);
     const hvo_ctx *tc = fr ? fr->ctx : ctx;
     for (int l = 0; l < HVO_MAX_LEVELS; l++) tab[l] = fr ? fr->sf[l] : ctx->scale[l];
     frame_level_sigma2(tc, tab + HVO_MAX_LEVELS, nullptr);
-    memcpy(&h[u_chas], cur->has_map_point, (size_t)n1);
+    memcpy(u_chas.host(h), cur->has_map_point, (size_t)n1);
     if (!fr) {
-        memcpy(&h[u_ckp], cur->kp_un, (size_t)n1 * sizeof(hvo_keypoint)); memcpy(&h[u_cds], cur->desc, (size_t)n1 * 32); memcpy(&h[u_cnd], cur->node_id, (size_t)n1 * 4);
-        if (c_raw) memcpy(&h[u_ckr], cur->kp, (size_t)n1 * sizeof(hvo_keypoint));
-        if (c_st) { memcpy(&h[u_cur], cur->uright, (size_t)n1 * 4); memcpy(&h[u_cdp], cur->depth, (size_t)n1 * 4); }
+        memcpy(u_ckp.host(h), cur->kp_un, (size_t)n1 * sizeof(hvo_keypoint)); memcpy(u_cds.host(h), cur->desc, (size_t)n1 * 32); memcpy(u_cnd.host(h), cur->node_id, (size_t)n1 * 4);
+        if (c_raw) memcpy(u_ckr.host(h), cur->kp, (size_t)n1 * sizeof(hvo_keypoint));
+        if (c_st) { memcpy(u_cur.host(h), cur->uright, (size_t)n1 * 4); memcpy(u_cdp.host(h), cur->depth, (size_t)n1 * 4); }
     }
     for (int j = 0; j < n_kf; j++) {
         const hvo_np_keyframe &K = kf[j];
         const size_t n = (size_t)K.n;
-        ((int *)&h[u_n])[j] = K.n;
+        u_n.host(h)[j] = K.n;
         if (!n) continue;
-        memcpy((hvo_keypoint *)&h[u_kp] + j * ct, K.kp_un, n * sizeof(hvo_keypoint));
-        if (k_raw) memcpy((hvo_keypoint *)&h[u_kr] + j * ct, K.kp ? K.kp : K.kp_un, n * sizeof(hvo_keypoint));
-        if (K.uright) { memcpy((float *)&h[u_ur] + j * ct, K.uright, n * 4); memcpy((float *)&h[u_dp] + j * ct, K.depth, n * 4); }
-        memcpy(&h[u_ds] + j * ct * 32, K.desc, n * 32); memcpy((int *)&h[u_nd] + j * ct, K.node_id, n * 4); memcpy(&h[u_has] + j * ct, K.has_map_point, n);
+        memcpy(u_kp.host(h, j), K.kp_un, n * sizeof(hvo_keypoint));
+        if (k_raw) memcpy(u_kr.host(h, j), K.kp ? K.kp : K.kp_un, n * sizeof(hvo_keypoint));
+        if (K.uright) { memcpy(u_ur.host(h, j), K.uright, n * 4); memcpy(u_dp.host(h, j), K.depth, n * 4); }
+        memcpy(u_ds.host(h, j), K.desc, n * 32); memcpy(u_nd.host(h, j), K.node_id, n * 4); memcpy(u_has.host(h, j), K.has_map_point, n);
     }
-    if (hipMemcpyAsync(d, h.data(), up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = "create new map points: upload"; return HVO_ERR_HIP; }
+    if (hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = "create new map points: upload"; return HVO_ERR_HIP; }
     // (the memset follows the copy: a copy from pageable memory waits for what the stream holds)
     if (hipMemsetAsync(d + z0, 0, z1 - z0, st) != hipSuccess) { *err = "create new map points: memset"; return HVO_ERR_HIP; }
     bool ev_on = true;
@@ -469,22 +463,22 @@ static int np_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo
     NpDev a; memset(&a, 0, sizeof(a));
     if (fr) { a.c_kpun = fr->kp_un; a.c_kp = fr->kp; a.c_ur = fr->uright; a.c_depth = fr->zdepth; a.c_desc = fr->desc; a.c_node = d_node; }
     else {
-        a.c_kpun = (const hvo_keypoint *)(d + u_ckp); a.c_kp = c_raw ? (const hvo_keypoint *)(d + u_ckr) : a.c_kpun;
-        a.c_ur = c_st ? (const float *)(d + u_cur) : nullptr; a.c_depth = c_st ? (const float *)(d + u_cdp) : nullptr;
-        a.c_desc = (const uint8_t *)(d + u_cds); a.c_node = (const int *)(d + u_cnd);
+        a.c_kpun = u_ckp.dev(d); a.c_kp = c_raw ? u_ckr.dev(d) : a.c_kpun;
+        a.c_ur = c_st ? u_cur.dev(d) : nullptr; a.c_depth = c_st ? u_cdp.dev(d) : nullptr;
+        a.c_desc = u_cds.dev(d); a.c_node = u_cnd.dev(d);
     }
-    a.c_has = (const uint8_t *)(d + u_chas); a.n1 = n1; a.mb1 = cur->mb;
+    a.c_has = u_chas.dev(d); a.n1 = n1; a.mb1 = cur->mb;
     memcpy(a.R, R1, sizeof(R1)); memcpy(a.t, t1, sizeof(t1)); memcpy(a.Ow, Ow1, sizeof(Ow1));
-    a.kf = (const NpKf *)(d + u_kf); a.k_kpun = (const hvo_keypoint *)(d + u_kp); a.k_kp = k_raw ? (const hvo_keypoint *)(d + u_kr) : a.k_kpun;
-    a.k_ur = (const float *)(d + u_ur); a.k_depth = (const float *)(d + u_dp); a.k_desc = (const uint8_t *)(d + u_ds); a.k_has = (const uint8_t *)(d + u_has);
-    a.fv_node = (const int *)(d + g_node); a.fv_start = (const int *)(d + g_start); a.fv_idx = (const int *)(d + g_idx); a.n_rows = (const int *)(d + g_rows);
+    a.kf = u_kf.dev(d); a.k_kpun = u_kp.dev(d); a.k_kp = k_raw ? u_kr.dev(d) : a.k_kpun;
+    a.k_ur = u_ur.dev(d); a.k_depth = u_dp.dev(d); a.k_desc = u_ds.dev(d); a.k_has = u_has.dev(d);
+    a.fv_node = g_node.dev(d); a.fv_start = g_start.dev(d); a.fv_idx = g_idx.dev(d); a.n_rows = g_rows.dev(d);
     a.cq = (int)cq; a.ct = (int)ct; a.n_kf = n_kf; a.nb = (int)nb; a.n_levels = P->n_levels; a.th_low = P->th_low;
     a.fx = cam->fx; a.fy = cam->fy; a.cx = cam->cx; a.cy = cam->cy; a.invfx = 1.0f / cam->fx; a.invfy = 1.0f / cam->fy; a.bf = P->bf;
-    a.ratio_factor = 1.5f * P->scale_factor; a.tab = (const float *)(d + u_tab);
-    a.midx = (int32_t *)(d + r_mi); a.mdist = (int32_t *)(d + r_md); a.outcome = (int8_t *)(d + r_out); a.branch = (int8_t *)(d + r_br); a.x3d = (float *)(d + r_x);
-    a.owner = (int32_t *)(d + r_own); a.pass = (uint8_t *)(d + s_pass); a.blockcnt = (int *)(d + s_bc); a.ncreated = (int *)(d + r_cnt);
-    a.c1 = (int32_t *)(d + r_c1); a.c2 = (int32_t *)(d + r_c2);
-    bow_csr_enqueue(st, n_kf, (int)ct, (const int *)(d + u_nd), (const int *)(d + u_n), (int *)(d + g_node), (int *)(d + g_start), (int *)(d + g_idx), (int *)(d + g_rows));
+    a.ratio_factor = 1.5f * P->scale_factor; a.tab = u_tab.dev(d);
+    a.midx = r_mi.dev(d); a.mdist = r_md.dev(d); a.outcome = r_out.dev(d); a.branch = r_br.dev(d); a.x3d = r_x.dev(d);
+    a.owner = r_own.dev(d); a.pass = s_pass.dev(d); a.blockcnt = s_bc.dev(d); a.ncreated = r_cnt.dev(d);
+    a.c1 = r_c1.dev(d); a.c2 = r_c2.dev(d);
+    bow_csr_enqueue(st, n_kf, (int)ct, u_nd.dev(d), u_n.dev(d), g_node.dev(d), g_start.dev(d), g_idx.dev(d), g_rows.dev(d));
     hipLaunchKernelGGL(k_np_search, dim3((unsigned)(cq / (NP_BLOCK / NP_GROUP)), n_kf), dim3(NP_BLOCK), 0, st, a);
     if (ev_on) ev_on = hipEventRecord(ctx->np_ev[1], st) == hipSuccess;
     hipLaunchKernelGGL(k_np_triangulate, dim3((unsigned)nb, n_kf), dim3(NP_BLOCK), 0, st, a);
@@ -498,24 +492,23 @@ static int np_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo
         *err = std::string("create new map points: ") + hipGetErrorString(hipGetLastError()); return HVO_ERR_HIP;
     }
     if (ev_on) for (int i = 0; i < 3; i++) if (hipEventElapsedTime(&sum->kernel_ms[i], ctx->np_ev[i], ctx->np_ev[i + 1]) != hipSuccess) sum->kernel_ms[i] = 0.f;
-    const char *b = hr.data() - r0;
+    const StageDown b = { hr.data(), r0 };
     const size_t n = (size_t)n1;
     int n_new = 0;
     for (int j = 0; j < n_kf; j++) {
         hvo_np_result &R = res[j];
-        const size_t q0 = (size_t)j * cq;
-        R.n_created = ((const int *)(b + r_cnt))[j]; R.gate = hk[j].gate; R.status = HVO_OK;
+        R.n_created = r_cnt.down(b)[j]; R.gate = hk[j].gate; R.status = HVO_OK;
         n_new += R.n_created;
-        memcpy(R.match_idx2, (const int32_t *)(b + r_mi) + q0, n * 4);
-        if (R.match_dist) memcpy(R.match_dist, (const int32_t *)(b + r_md) + q0, n * 4);
-        if (R.outcome) memcpy(R.outcome, (const int8_t *)(b + r_out) + q0, n);
-        if (R.branch) memcpy(R.branch, (const int8_t *)(b + r_br) + q0, n);
-        if (R.x3d) memcpy(R.x3d, (const float *)(b + r_x) + 3 * q0, n * 12);
+        memcpy(R.match_idx2, r_mi.down(b, j), n * 4);
+        if (R.match_dist) memcpy(R.match_dist, r_md.down(b, j), n * 4);
+        if (R.outcome) memcpy(R.outcome, r_out.down(b, j), n);
+        if (R.branch) memcpy(R.branch, r_br.down(b, j), n);
+        if (R.x3d) memcpy(R.x3d, r_x.down(b, j), n * 12);
         const size_t nc = (size_t)std::max(0, std::min(R.n_created, (int32_t)n));
-        if (R.created_idx1) memcpy(R.created_idx1, (const int32_t *)(b + r_c1) + q0, nc * 4);
-        if (R.created_idx2) memcpy(R.created_idx2, (const int32_t *)(b + r_c2) + q0, nc * 4);
+        if (R.created_idx1) memcpy(R.created_idx1, r_c1.down(b, j), nc * 4);
+        if (R.created_idx2) memcpy(R.created_idx2, r_c2.down(b, j), nc * 4);
     }
-    if (sum->owner) memcpy(sum->owner, b + r_own, n * 4);
+    if (sum->owner) memcpy(sum->owner, r_own.down(b), n * 4);
     sum->n_new = n_new;
     return HVO_OK;
 }

@@ -18,6 +18,7 @@
 // s is x % s, and removal is the reference's swap-with-last (:199-200).  A hypothesis whose pose is not finite has count 0.
 // SetRansacParameters' log / pow / ceil run on the host (pnp_set_ransac below), so a restatement on the host calls the same libm.
 #include "frame_view.hpp"
+#include "call_stage.hpp"
 #include <string.h>
 #include <math.h>
 #include <algorithm>
@@ -248,8 +249,6 @@ __global__ __launch_bounds__(256) void k_pnp_gather(PnpGather G, int capN, float
 }
 
 // ------------------------------------------------------------------------------------------------ host
-static inline size_t pal(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // SetRansacParameters (:121-157) for N correspondences, with the host's libm like the reference
 static void pnp_set_ransac(const hvo_pnp_params *P, int N, PnpCand *c)
 {
@@ -322,61 +321,59 @@ int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_p
     for (int j = 0; j < n_kf; j++) want_sample = want_sample || res[j].hyp_sample != nullptr;
     const int Tc = std::max(Tcap, 1);
     // one carve of the context's arena: what goes up, then the scratch and the results
-    size_t o = 0;
-    auto carve = [&](size_t b) { const size_t at = o; o += pal(b); return at; };
-    const size_t a_cand = carve((size_t)n_kf * sizeof(PnpCand));
-    const size_t a_p3d = carve((size_t)n_kf * capN * 12), a_p2d = carve((size_t)n_kf * capN * 8), a_me = carve((size_t)n_kf * capN * 4), a_fi = carve((size_t)n_kf * capN * 4);
-    const size_t up_host = o;                                    // the host form uploads [0, up_host)
-    const size_t g_match = carve(fr ? (size_t)n_kf * std::max(fr->n_kp, 1) * 4 : 0), g_pos = carve(fr ? (size_t)n_kf * capK * 12 : 0),
-                 g_bad = carve(fr ? (size_t)n_kf * capK : 0), g_n = carve(fr ? (size_t)n_kf * 4 : 0);
-    const size_t up_end = o;
-    const size_t r0 = o;
-    const size_t a_inl = carve((size_t)n_kf * Tc * 4), a_rec = carve((size_t)n_kf * Tc * 4), a_evt = carve((size_t)n_kf * Tc * 4), a_pose = carve((size_t)n_kf * Tc * 48),
-                 a_nrec = carve((size_t)n_kf * 4), a_recit = carve((size_t)n_kf * E * 4), a_best = carve((size_t)n_kf * 8), a_rcnt = carve((size_t)n_kf * E * 4),
-                 a_rpose = carve((size_t)n_kf * E * 48), a_evin = carve((size_t)n_kf * E * capF), a_evh = carve((size_t)n_kf * E * capF), a_bin = carve((size_t)n_kf * capF),
-                 a_samp = carve(want_sample ? (size_t)n_kf * Tc * ms * 4 : 0);
-    const size_t r1 = o;                                         // [r0, r1) comes down
-    const size_t a_mask = carve((size_t)n_kf * Tc * capN), a_idx = carve((size_t)n_kf * E * capN * 4), a_rmask = carve((size_t)n_kf * E * capN);
-    const size_t total = o;
+    const size_t F = (size_t)n_kf, nkp = fr ? (size_t)std::max(fr->n_kp, 1) : 0, FE = F * E, FT = F * Tc;    // rows: a candidate, its event e at j E + e, its hypothesis at j Tc + it
+    StageCarver C(256);
+    const auto a_cand = C.take<PnpCand>(F);
+    const auto a_p3d = C.take<float>(F, (size_t)capN * 3), a_p2d = C.take<float>(F, (size_t)capN * 2), a_me = C.take<float>(F, capN); const auto a_fi = C.take<int>(F, capN);
+    const size_t up_host = C.mark(), Fr = fr ? F : 0;            // the host form uploads [0, up_host); the resident form adds the key-frame sides
+    const auto g_match = C.take<int>(Fr, nkp); const auto g_pos = C.take<float>(Fr, (size_t)capK * 3); const auto g_bad = C.take<uint8_t>(Fr, capK); const auto g_n = C.take<int>(Fr);
+    const size_t up_end = C.mark(), r0 = up_end;
+    const auto a_inl = C.take<int>(F, Tc), a_rec = C.take<int>(F, Tc), a_evt = C.take<int>(F, Tc); const auto a_pose = C.take<float>(FT, 12);
+    const auto a_nrec = C.take<int>(F), a_recit = C.take<int>(F, E), a_best = C.take<int>(F, 2), a_rcnt = C.take<int>(F, E); const auto a_rpose = C.take<float>(FE, 12);
+    const auto a_evin = C.take<uint8_t>(FE, capF), a_evh = C.take<uint8_t>(FE, capF), a_bin = C.take<uint8_t>(F, capF);
+    const auto a_samp = C.take<int>(want_sample ? F : 0, (size_t)Tc * ms);
+    const size_t r1 = C.mark();                                  // [r0, r1) comes down
+    const auto a_mask = C.take<uint8_t>(FT, capN); const auto a_idx = C.take<int>(FE, capN); const auto a_rmask = C.take<uint8_t>(FE, capN);
+    const size_t total = C.mark();
     if (total > PNP_ARENA_LIMIT) { *err = "pnp: the call's device scratch would pass 1 GiB (candidates x hypotheses x correspondences)"; return HVO_ERR_UNSUPPORTED; }
     char *d = (char *)hvo_call_arena(ctx, total);
     if (!d) { *err = "pnp: arena"; return HVO_ERR_HIP; }
-    std::vector<char> h(up_end, 0);
-    memcpy(&h[a_cand], cand.data(), (size_t)n_kf * sizeof(PnpCand));
+    std::vector<char> hv(up_end, 0); char *const h = hv.data();
+    memcpy(a_cand.host(h), cand.data(), a_cand.bytes());
     PnpGather G; memset(&G, 0, sizeof(G));
     if (fr) {
         for (int j = 0; j < n_kf; j++) {
             const hvo_pnp_keyframe_side &K = kf[j];
-            if (fr->n_kp) memcpy(&h[g_match + (size_t)j * fr->n_kp * 4], K.match_kf, (size_t)fr->n_kp * 4);
-            if (K.n) { memcpy(&h[g_pos + (size_t)j * capK * 12], K.pos, (size_t)K.n * 12); memcpy(&h[g_bad + (size_t)j * capK], K.bad, (size_t)K.n); }
-            ((int *)&h[g_n])[j] = K.n;
+            if (fr->n_kp) memcpy(g_match.host(h, j), K.match_kf, (size_t)fr->n_kp * 4);
+            if (K.n) { memcpy(g_pos.host(h, j), K.pos, (size_t)K.n * 12); memcpy(g_bad.host(h, j), K.bad, (size_t)K.n); }
+            g_n.host(h)[j] = K.n;
         }
-        G.kp_un = fr->kp_un; G.match = (const int *)(d + g_match); G.kf_pos = (const float *)(d + g_pos); G.kf_bad = (const uint8_t *)(d + g_bad);
-        G.kf_n = (const int *)(d + g_n); G.nf = fr->n_kp; G.capK = capK; G.th2 = P->th2;
+        G.kp_un = fr->kp_un; G.match = g_match.dev(d); G.kf_pos = g_pos.dev(d); G.kf_bad = g_bad.dev(d);
+        G.kf_n = g_n.dev(d); G.nf = fr->n_kp; G.capK = capK; G.th2 = P->th2;
         frame_level_sigma2(ctx, G.sigma2, nullptr);
-        if (hipMemcpyAsync(d + a_cand, &h[a_cand], pal((size_t)n_kf * sizeof(PnpCand)), hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(d + up_host, &h[up_host], up_end - up_host, hipMemcpyHostToDevice, st) != hipSuccess) return HVO_ERR_HIP;
+        if (hipMemcpyAsync(a_cand.dev(d), a_cand.host(h), stage_align(a_cand.bytes()), hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(d + up_host, h + up_host, up_end - up_host, hipMemcpyHostToDevice, st) != hipSuccess) return HVO_ERR_HIP;
     } else {
         for (int j = 0; j < n_kf; j++) {
             const hvo_pnp_problem &Q = prob[j];
             if (!Q.n) continue;
-            memcpy(&h[a_p3d + (size_t)j * capN * 12], Q.p3d, (size_t)Q.n * 12); memcpy(&h[a_p2d + (size_t)j * capN * 8], Q.p2d, (size_t)Q.n * 8);
-            float *me = (float *)&h[a_me + (size_t)j * capN * 4];
+            memcpy(a_p3d.host(h, j), Q.p3d, (size_t)Q.n * 12); memcpy(a_p2d.host(h, j), Q.p2d, (size_t)Q.n * 8);
+            float *me = a_me.host(h, j);
             for (int i = 0; i < Q.n; i++) { volatile float m = Q.sigma2[i] * P->th2; me[i] = m; }       // mvMaxError (:156)
-            memcpy(&h[a_fi + (size_t)j * capN * 4], Q.feature_index, (size_t)Q.n * 4);
+            memcpy(a_fi.host(h, j), Q.feature_index, (size_t)Q.n * 4);
         }
-        if (hipMemcpyAsync(d, h.data(), up_host, hipMemcpyHostToDevice, st) != hipSuccess) return HVO_ERR_HIP;
+        if (hipMemcpyAsync(d, h, up_host, hipMemcpyHostToDevice, st) != hipSuccess) return HVO_ERR_HIP;
     }
     PnpDev D; memset(&D, 0, sizeof(D));
-    D.p3d = (const float *)(d + a_p3d); D.p2d = (const float *)(d + a_p2d); D.max_err = (const float *)(d + a_me); D.fidx = (const int *)(d + a_fi);
-    D.cand = (const PnpCand *)(d + a_cand); D.capN = capN; D.Tcap = Tc; D.min_set = ms; D.E = E; D.capF = capF; D.seed = P->seed;
+    D.p3d = a_p3d.dev(d); D.p2d = a_p2d.dev(d); D.max_err = a_me.dev(d); D.fidx = a_fi.dev(d);
+    D.cand = a_cand.dev(d); D.capN = capN; D.Tcap = Tc; D.min_set = ms; D.E = E; D.capF = capF; D.seed = P->seed;
     D.fu = cam->fx; D.fv = cam->fy; D.uc = cam->cx; D.vc = cam->cy;
-    D.hyp_inl = (int *)(d + a_inl); D.hyp_mask = (uint8_t *)(d + a_mask); D.hyp_pose = (float *)(d + a_pose); D.hyp_sample = want_sample ? (int *)(d + a_samp) : nullptr;
-    D.hyp_rec = (int *)(d + a_rec); D.hyp_event = (int *)(d + a_evt); D.n_rec = (int *)(d + a_nrec); D.rec_it = (int *)(d + a_recit); D.best = (int *)(d + a_best);
-    D.idx = (int *)(d + a_idx); D.ref_cnt = (int *)(d + a_rcnt); D.ref_pose = (float *)(d + a_rpose); D.ref_mask = (uint8_t *)(d + a_rmask);
-    D.ev_inl = (uint8_t *)(d + a_evin); D.ev_hinl = (uint8_t *)(d + a_evh); D.best_inl = (uint8_t *)(d + a_bin);
+    D.hyp_inl = a_inl.dev(d); D.hyp_mask = a_mask.dev(d); D.hyp_pose = a_pose.dev(d); D.hyp_sample = want_sample ? a_samp.dev(d) : nullptr;
+    D.hyp_rec = a_rec.dev(d); D.hyp_event = a_evt.dev(d); D.n_rec = a_nrec.dev(d); D.rec_it = a_recit.dev(d); D.best = a_best.dev(d);
+    D.idx = a_idx.dev(d); D.ref_cnt = a_rcnt.dev(d); D.ref_pose = a_rpose.dev(d); D.ref_mask = a_rmask.dev(d);
+    D.ev_inl = a_evin.dev(d); D.ev_hinl = a_evh.dev(d); D.best_inl = a_bin.dev(d);
     if (hipMemsetAsync(d + r0, 0, r1 - r0, st) != hipSuccess) return HVO_ERR_HIP;
-    if (fr && fr->n_kp > 0) hipLaunchKernelGGL(k_pnp_gather, dim3(n_kf), dim3(256), 0, st, G, capN, (float *)(d + a_p3d), (float *)(d + a_p2d), (float *)(d + a_me), (int *)(d + a_fi));
+    if (fr && fr->n_kp > 0) hipLaunchKernelGGL(k_pnp_gather, dim3(n_kf), dim3(256), 0, st, G, capN, a_p3d.dev(d), a_p2d.dev(d), a_me.dev(d), a_fi.dev(d));
     pnp_ev_begin(ctx, st);
     if (Tcap > 0) {
         const size_t dyn = 2 * ms > PNP_SEQ_ROWS ? (size_t)4 * PNP_TREE_BATCH * 256 * sizeof(double) : 0;
@@ -398,35 +395,36 @@ int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_p
         if (hipEventElapsedTime(&ctx->pnp_ms[1], ctx->pnp_ev[1], ctx->pnp_ev[2]) != hipSuccess) ctx->pnp_ms[1] = 0.f;
         ctx->pnp_ev_on = false;
     }
-    const char *b = hr.data() - r0;
+    const StageDown b = { hr.data(), r0 };
     int rc = HVO_OK;
     for (int j = 0; j < n_kf; j++) {
         hvo_pnp_result &R = res[j]; const PnpCand &c = cand[j];
-        const int T = c.T, nrec = ((const int *)(b + a_nrec))[j], ne = std::min(nrec, E);
+        const int T = c.T, nrec = a_nrec.down(b)[j], ne = std::min(nrec, E);
         R.n = c.N; R.min_inliers = c.min_inl; R.max_its = c.max_its; R.epsilon = c.eps; R.n_hyp = T; R.no_more = c.no_more; R.n_features = NFj[j];
         R.n_events = ne; R.status = nrec > E ? HVO_ERR_CAPACITY : HVO_OK;
         if (nrec > E) rc = HVO_ERR_CAPACITY;
         if (T) {
-            memcpy(R.hyp_inliers, b + a_inl + (size_t)j * Tc * 4, (size_t)T * 4);
-            memcpy(R.hyp_event, b + a_evt + (size_t)j * Tc * 4, (size_t)T * 4);
-            if (R.hyp_sample) memcpy(R.hyp_sample, b + a_samp + (size_t)j * Tc * ms * 4, (size_t)T * ms * 4);
+            memcpy(R.hyp_inliers, a_inl.down(b, j), (size_t)T * 4);
+            memcpy(R.hyp_event, a_evt.down(b, j), (size_t)T * 4);
+            if (R.hyp_sample) memcpy(R.hyp_sample, a_samp.down(b, j), (size_t)T * ms * 4);
         }
         for (int e = 0; e < ne; e++) {
             hvo_pnp_event &V = R.events[e];
-            V.iteration = ((const int *)(b + a_recit))[j * E + e] + 1;
-            V.n_inliers = ((const int *)(b + a_rcnt))[j * E + e];
+            const size_t je = (size_t)j * E + e;
+            V.iteration = a_recit.down(b, j)[e] + 1;
+            V.n_inliers = a_rcnt.down(b, j)[e];
             V.success = V.n_inliers > c.min_inl ? 1 : 0;
-            memcpy(V.Tcw, b + a_rpose + ((size_t)j * E + e) * 48, 48);
+            memcpy(V.Tcw, a_rpose.down(b, je), 48);
             const int it0 = V.iteration - 1;
-            V.hyp_n_inliers = ((const int *)(b + a_inl))[(size_t)j * Tc + it0];
-            memcpy(V.hyp_Tcw, b + a_pose + ((size_t)j * Tc + it0) * 48, 48);
-            if (NFj[j]) { memcpy(V.inliers, b + a_evin + ((size_t)j * E + e) * capF, (size_t)NFj[j]); memcpy(V.hyp_inliers, b + a_evh + ((size_t)j * E + e) * capF, (size_t)NFj[j]); }
+            V.hyp_n_inliers = a_inl.down(b, j)[it0];
+            memcpy(V.hyp_Tcw, a_pose.down(b, (size_t)j * Tc + it0), 48);
+            if (NFj[j]) { memcpy(V.inliers, a_evin.down(b, je), (size_t)NFj[j]); memcpy(V.hyp_inliers, a_evh.down(b, je), (size_t)NFj[j]); }
         }
-        const int bc = ((const int *)(b + a_best))[2 * j], bit = ((const int *)(b + a_best))[2 * j + 1];
+        const int bc = a_best.down(b, j)[0], bit = a_best.down(b, j)[1];
         R.best_n_inliers = bc; R.best_valid = (bit >= 0 && bc >= c.min_inl) ? 1 : 0; R.best_iteration = bit + 1;
         if (bit >= 0) {
-            memcpy(R.best_Tcw, b + a_pose + ((size_t)j * Tc + bit) * 48, 48);
-            if (NFj[j]) memcpy(R.best_inliers, b + a_bin + (size_t)j * capF, (size_t)NFj[j]);
+            memcpy(R.best_Tcw, a_pose.down(b, (size_t)j * Tc + bit), 48);
+            if (NFj[j]) memcpy(R.best_inliers, a_bin.down(b, j), (size_t)NFj[j]);
         } else memset(R.best_Tcw, 0, 48);
     }
     if (rc == HVO_ERR_CAPACITY) *err = "pnp: a candidate has more records than max_events (its status says which)";

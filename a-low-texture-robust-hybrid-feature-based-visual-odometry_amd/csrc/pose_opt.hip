@@ -19,6 +19,7 @@
 // re-evaluates an unflagged edge at the pose of the round's last computeActiveErrors (the last trial, accepted or not) instead of storing
 // _error per edge.  The host and stream forms launch this kernel alone on the same bytes, so they give bit-identical results.
 #include "frame_view.hpp"
+#include "call_stage.hpp"
 #include <math.h>
 #include <cmath>
 #include <string.h>
@@ -618,33 +619,23 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoArgs A)
 // ---- host side ----
 static const hvo_pose_plane_params k_po_default_pp = { 0.5, 50.0, 0.1, 0.1, 100.0, 50.0 };    // TUM3.yaml
 
-struct PoLayout { size_t o[12]; };
-static size_t po_al(size_t v) { return (v + 63) & ~(size_t)63; }
-// where frame p's host arrays lie in the one upload, advancing `up`
-static void po_layout(const hvo_pose_problem &p, bool resident, size_t &up, PoLayout &L)
-{
-    const size_t np = (size_t)p.n_points, nl = (size_t)p.n_lines, m = (size_t)p.n_planes;
-    auto take = [&](size_t bytes) { const size_t at = up; up += po_al(bytes); return at; };
-    L.o[0] = take(np); L.o[1] = take(np * 12); L.o[2] = take(nl); L.o[3] = take(nl * 48); L.o[4] = take(m * 3); L.o[5] = take(m * 48);
-    for (int k = 6; k < 12; k++) L.o[k] = 0;
-    if (!resident) {
-        L.o[6] = take(np * sizeof(hvo_keypoint)); L.o[7] = p.uright ? take(np * 4) : 0; L.o[8] = p.inv_sigma2 ? take(np * 4) : 0;
-        L.o[9] = take(nl * 24); L.o[10] = take(nl * sizeof(hvo_line3d)); L.o[11] = take(m * 16);
-    }
-}
-static void po_flag_layout(const hvo_pose_problem &p, size_t &total, size_t fo[4])
-{
-    auto take = [&](size_t bytes) { const size_t at = total; total += po_al(bytes); return at; };
-    fo[0] = take((size_t)p.n_points); fo[1] = take((size_t)p.n_lines); fo[2] = take((size_t)p.n_lines); fo[3] = take((size_t)p.n_planes * 3);
-}
+// where one frame's host arrays lie in the one upload (the frame side only when it is not resident) and its flags in the download
+struct PoPieces {
+    StagePiece<uint8_t> pt_has, ln_has, pl_has, pt_out, ln_out, vp_out, pl_out;
+    StagePiece<float> pt_xyz, pl_map, uright, inv_sigma2, pl_coef;
+    StagePiece<double> ln_xyz, linefn;
+    StagePiece<hvo_keypoint> kp_un; StagePiece<hvo_line3d> l3d;
+};
 
-// One pinned staging block of the context (grow-only, hvo_stage_host) holds the upload and receives the download; the device side is the
-// context's call arena: nothing is allocated by a call once both have grown.
+// One pinned staging block of the context (grow-only, hvo_stage_host) holds the upload and receives the download at the arena's own offsets;
+// the device side is the context's call arena: nothing is allocated by a call once both have grown.
 int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_plane_params *pp,
            int n, const hvo_pose_problem *prob, const FrameView *fr, hvo_pose_result *res, const hvo_pose_flags *flags, std::string *err)
 {
     if (!pp) pp = &k_po_default_pp;
-    size_t up = po_al((size_t)n * sizeof(PoFrame));
+    StageCarver C(64);
+    const auto frames = C.take<PoFrame>((size_t)n);
+    std::vector<PoPieces> pieces((size_t)n);
     for (int f = 0; f < n; f++) {
         const hvo_pose_problem &p = prob[f];
         if (p.n_points < 0 || p.n_lines < 0 || p.n_planes < 0 || p.n_points > PO_MAX_POINTS || p.n_lines > PO_MAX_LINES || p.n_planes > PO_MAX_PLANES) {
@@ -657,31 +648,39 @@ int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_p
             (p.n_lines && (!p.ln_has || !p.ln_xyz || (!r && (!p.linefn || !p.lines3d)))) ||
             (p.n_planes && (!planes_ok || (!r && !p.plane_coef)))) { *err = "pose optimisation: a needed array is NULL"; return HVO_ERR_INVALID_ARG;
         }
-        PoLayout L; po_layout(p, r, up, L);
+        const size_t np = (size_t)p.n_points, nl = (size_t)p.n_lines, m = (size_t)p.n_planes;
+        PoPieces &L = pieces[f];
+        L.pt_has = C.take<uint8_t>(np); L.pt_xyz = C.take<float>(np, 3); L.ln_has = C.take<uint8_t>(nl); L.ln_xyz = C.take<double>(nl, 6);
+        L.pl_has = C.take<uint8_t>(m, 3); L.pl_map = C.take<float>(m, 12);
+        if (!r) {
+            L.kp_un = C.take<hvo_keypoint>(np); L.uright = C.take<float>(p.uright ? np : 0); L.inv_sigma2 = C.take<float>(p.inv_sigma2 ? np : 0);
+            L.linefn = C.take<double>(nl, 3); L.l3d = C.take<hvo_line3d>(nl); L.pl_coef = C.take<float>(m, 4);
+        }
     }
-    const size_t down0 = up;
-    size_t total = up;
-    for (int f = 0; f < n; f++) { size_t fo[4]; po_flag_layout(prob[f], total, fo); }
-    const size_t res_off = total; total += po_al((size_t)n * sizeof(hvo_pose_result));
+    const size_t up = C.mark(), down0 = up;                                  // [0, up) goes up, [down0, total) comes down
+    for (int f = 0; f < n; f++) {
+        const hvo_pose_problem &p = prob[f];
+        PoPieces &L = pieces[f];
+        L.pt_out = C.take<uint8_t>((size_t)p.n_points); L.ln_out = C.take<uint8_t>((size_t)p.n_lines); L.vp_out = C.take<uint8_t>((size_t)p.n_lines);
+        L.pl_out = C.take<uint8_t>((size_t)p.n_planes, 3);
+    }
+    const auto results = C.take<hvo_pose_result>((size_t)n);
+    const size_t total = C.mark();
     char *d = (char *)hvo_call_arena(ctx, total);
     char *h = (char *)hvo_stage_host(ctx, total);
     if (!d || !h) { *err = "pose optimisation: scratch"; return HVO_ERR_HIP; }
-    PoFrame *hf = (PoFrame *)h;
-    size_t at_up = po_al((size_t)n * sizeof(PoFrame)), at_fl = down0;
     for (int f = 0; f < n; f++) {
         const hvo_pose_problem &p = prob[f];
-        PoLayout L; po_layout(p, fr != nullptr, at_up, L);
-        size_t fo[4]; po_flag_layout(p, at_fl, fo);
-        const size_t *o = L.o;
-        const size_t np = (size_t)p.n_points, nl = (size_t)p.n_lines, m = (size_t)p.n_planes;
-        PoFrame &F = hf[f]; memset(&F, 0, sizeof(F));
+        const PoPieces &L = pieces[f];
+        const size_t m = (size_t)p.n_planes;
+        PoFrame &F = *frames.host(h, f); memset(&F, 0, sizeof(F));
         memcpy(F.Tcw, p.Tcw, sizeof(F.Tcw));
         F.n_pts = p.n_points; F.n_lines = p.n_lines; F.n_planes = p.n_planes;
-        auto put = [&](size_t at, const void *src, size_t bytes) { if (bytes) memcpy(h + at, src, bytes); return d + at; };
-        F.pt_has = (const uint8_t *)put(o[0], p.pt_has, np); F.pt_xyz = (const float *)put(o[1], p.pt_xyz, np * 12);
-        F.ln_has = (const uint8_t *)put(o[2], p.ln_has, nl); F.ln_xyz = (const double *)put(o[3], p.ln_xyz, nl * 48);
+        auto put = [&](const auto &piece, const void *src) { if (piece.bytes()) memcpy(piece.host(h), src, piece.bytes()); return piece.dev(d); };
+        F.pt_has = put(L.pt_has, p.pt_has); F.pt_xyz = put(L.pt_xyz, p.pt_xyz);
+        F.ln_has = put(L.ln_has, p.ln_has); F.ln_xyz = put(L.ln_xyz, p.ln_xyz);
         if (p.plane_map) {                                                   // an hvo_plane_match result as it is: slots, -1 = none; coefficients from the map
-            uint8_t *has = (uint8_t *)h + o[4]; float *cw = (float *)(h + o[5]);
+            uint8_t *has = L.pl_has.host(h); float *cw = L.pl_map.host(h);
             const int32_t *sl[3] = { p.slot_match, p.slot_parallel, p.slot_vertical };
             for (size_t i = 0; i < m; i++) for (int r = 0; r < 3; r++) {
                 const int slot = sl[r] ? sl[r][i] : -1;
@@ -691,9 +690,9 @@ int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_p
                 if (hvo_plane_map_slot(p.plane_map, slot, c, nullptr, nullptr)) { *err = "pose optimisation: no such slot in the plane map"; return HVO_ERR_INVALID_ARG; }
                 has[3 * i + r] = 1;
             }
-            F.pl_has = (const uint8_t *)(d + o[4]); F.pl_map = (const float *)(d + o[5]);
+            F.pl_has = L.pl_has.dev(d); F.pl_map = L.pl_map.dev(d);
         } else {
-            F.pl_has = (const uint8_t *)put(o[4], p.pl_has, m * 3); F.pl_map = (const float *)put(o[5], p.pl_coef_w, m * 48);
+            F.pl_has = put(L.pl_has, p.pl_has); F.pl_map = put(L.pl_map, p.pl_coef_w);
         }
         if (fr) {
             const FrameView &R = fr[f];
@@ -701,16 +700,16 @@ int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_p
             F.planes_from_tail = 1; F.d_nkp = R.d_nkp; F.d_nkl = R.d_nkl;
             F.depth = R.depth; F.pitch = R.pitch; F.w = R.w; F.h = R.h; F.dfac = R.dfac; F.bf32 = cam->bf;
         } else {
-            F.kp_un = (const hvo_keypoint *)put(o[6], p.kp_un, np * sizeof(hvo_keypoint));
-            F.uright = p.uright ? (const float *)put(o[7], p.uright, np * 4) : nullptr;
-            F.inv_sigma2 = p.inv_sigma2 ? (const float *)put(o[8], p.inv_sigma2, np * 4) : nullptr;
-            F.linefn = (const double *)put(o[9], p.linefn, nl * 24); F.l3d = (const hvo_line3d *)put(o[10], p.lines3d, nl * sizeof(hvo_line3d));
-            F.pl_coef = (const float *)put(o[11], p.plane_coef, m * 16);
+            F.kp_un = put(L.kp_un, p.kp_un);
+            F.uright = p.uright ? put(L.uright, p.uright) : nullptr;
+            F.inv_sigma2 = p.inv_sigma2 ? put(L.inv_sigma2, p.inv_sigma2) : nullptr;
+            F.linefn = put(L.linefn, p.linefn); F.l3d = put(L.l3d, p.lines3d);
+            F.pl_coef = put(L.pl_coef, p.plane_coef);
         }
-        F.pt_out = (uint8_t *)d + fo[0]; F.ln_out = (uint8_t *)d + fo[1]; F.vp_out = (uint8_t *)d + fo[2]; F.pl_out = (uint8_t *)d + fo[3];
+        F.pt_out = L.pt_out.dev(d); F.ln_out = L.ln_out.dev(d); F.vp_out = L.vp_out.dev(d); F.pl_out = L.pl_out.dev(d);
     }
     PoArgs A; memset(&A, 0, sizeof(A));
-    A.frames = (const PoFrame *)d; A.res = (hvo_pose_result *)(d + res_off); A.nframes = n;
+    A.frames = frames.dev(d); A.res = results.dev(d); A.nframes = n;
     A.fx = cam->fx; A.fy = cam->fy; A.cx = cam->cx; A.cy = cam->cy; A.bf = cam->bf;
     A.info_angle = 3282.8 / (pp->angle_info * pp->angle_info); A.info_dis = pp->distance_info * pp->distance_info;
     A.info_par = 3282.8 / (pp->parallel_info * pp->parallel_info); A.info_ver = 3282.8 / (pp->vertical_info * pp->vertical_info);
@@ -729,17 +728,12 @@ int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_p
     PO_HIP(hipStreamSynchronize(st));
     PO_HIP(hipEventElapsedTime(&ctx->po_ms, ctx->po_ev[0], ctx->po_ev[1]));
 #undef PO_HIP
-    memcpy(res, h + res_off, (size_t)n * sizeof(hvo_pose_result));
+    memcpy(res, results.host(h), results.bytes());
     // the reference writes a flag only where there is a correspondence (Optimizer.cc:650, :757, :976): the caller's other entries stay
-    at_fl = down0;
-    for (int f = 0; f < n; f++) {
+    for (int f = 0; flags && f < n; f++) {
         const hvo_pose_problem &p = prob[f];
-        size_t fo[4]; po_flag_layout(p, at_fl, fo);
-        if (!flags) continue;
         const hvo_pose_flags &G = flags[f];
-        const uint8_t *o_pt = (const uint8_t *)h + fo[0], *o_ln = (const uint8_t *)h + fo[1], *o_vp = (const uint8_t *)h + fo[2], *o_pl = (const uint8_t *)h + fo[3];
-        size_t at = po_al((size_t)n * sizeof(PoFrame));
-        (void)at;
+        const uint8_t *o_pt = pieces[f].pt_out.host(h), *o_ln = pieces[f].ln_out.host(h), *o_vp = pieces[f].vp_out.host(h), *o_pl = pieces[f].pl_out.host(h);
         for (int i = 0; G.pt_outlier && i < p.n_points; i++) if (p.pt_has[i]) G.pt_outlier[i] = o_pt[i];
         for (int i = 0; G.ln_outlier && i < p.n_lines; i++) if (p.ln_has[i]) G.ln_outlier[i] = o_ln[i];
         for (int i = 0; G.vp_outlier && i < p.n_lines; i++) G.vp_outlier[i] = o_vp[i];

@@ -205,13 +205,8 @@ int sm_stage_in(hvo_slot_map *m, hipStream_t st, char *A, size_t o_pose, size_t 
     std::vector<SmPose> &pose = m->pose;                           // the map's: the asynchronous copy below reads it after this function has returned
     pose.resize(F);
     for (size_t f = 0; f < F; f++) {
-        const float *T = Tcw + 12 * f; SmPose &p = pose[f];
-        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) p.R[3 * r + c] = T[4 * r + c]; p.t[r] = T[4 * r + 3]; }
-        for (int r = 0; r < 3; r++) {                              // mOw = -Rcw^T tcw
-            double s0 = 0;
-            for (int k = 0; k < 3; k++) s0 += (double)p.R[3 * k + r] * (double)p.t[k];
-            p.Ow[r] = (float)(s0 * -1.0);
-        }
+        SmPose &p = pose[f];
+        pose_split(Tcw + 12 * f, p.R, p.t, p.Ow);                  // mOw = -Rcw^T tcw
         p.pad = 0.f;
     }
     SM_HIP(hipMemcpyAsync(A + o_pose, pose.data(), F * sizeof(SmPose), hipMemcpyHostToDevice, st));

@@ -9,6 +9,7 @@
 // set_many / slot; a call adds its frustum test, its gather, its search and its post stage.
 #pragma once
 #include "hvo_internal.hpp"
+#include "call_stage.hpp"
 #include <string>
 #include <vector>
 
@@ -47,8 +48,6 @@ struct hvo_point_map : hvo_slot_map {
 
 #define SM_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { m->last_error = std::string(#call) + ": " + hipGetErrorString(e_); return HVO_ERR_HIP; } } while (0)
 
-static inline size_t sm_al(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // ---- the map (slot_map.hip) ----
 int sm_init(hvo_slot_map *m, int device, int slots);             // stream, events, room for `slots`; on failure the caller destroys the map
 void sm_release(hvo_slot_map *m);                                // everything but the object itself
@@ -63,7 +62,7 @@ int sm_grow(hvo_slot_map *m, hipStream_t st, char **p, size_t *have, size_t want
 int sm_debug_fill_scratch(hvo_slot_map *m, int fill_byte);      // test door: d_a and d_b at their current sizes
 
 // ---- the call (slot_map.hip) ----
-struct SmCarve { size_t o = 0; size_t take(size_t bytes) { const size_t at = o; o += sm_al(bytes); return at; } };    // 256-byte pieces of scratch A
+struct SmCarve : StageCarver { SmCarve() : StageCarver(256) {} size_t take(size_t bytes) { return StageCarver::take<char>(bytes).off; } };    // 256-byte pieces of scratch A, by their offsets
 // one frame's side of the stage before the in-view counts: nt features with their held slots, ne seen_extra slots, and where they live in scratch A
 struct SmFrame { int nt, ne; const int32_t *held, *extra; size_t o_held, o_occ, o_ex, o_win; };
 // held below held_min or beyond the map, seen_extra outside the map: last_error = prefix + ": " + text, HVO_ERR_INVALID_ARG

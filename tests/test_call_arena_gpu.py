@@ -125,6 +125,67 @@ def test_regrowth(env):
         ctx.close()
 
 
+# ---------------------------------------------------------------------------------------------------------------- the layouts' totals
+# debug_call_arena() after ONE call on a fresh context = arena_capacity(the layout's total): the capacities commit 4d54914 gave on the device,
+# whose layouts were hand arithmetic on bytes.  They pin every total of the typed layouts (csrc/call_stage.hpp) to 4 KiB.
+CAPACITY = {("search_by_projection_keyframe", "S"): 32768, ("search_by_projection_keyframe", "L"): 380928,
+            ("fuse_points", "S"): 69632, ("fuse_points", "L"): 126976,
+            ("fuse_points_slots", "S"): 49152, ("fuse_points_slots", "L"): 69632,
+            ("create_new_map_points", "S"): 61440, ("create_new_map_points", "L"): 159744,
+            ("pnp_ransac", "S"): 16384, ("pnp_ransac", "L"): 81920,
+            ("search_by_bow", "S"): 20480, ("search_by_bow", "L"): 139264,
+            ("pose_optimize", "S"): 12288, ("pose_optimize", "L"): 102400,
+            ("line_struct_optimize", "S"): 32768, ("line_struct_optimize", "L"): 225280}
+
+
+@pytest.mark.parametrize("name,size", sorted(CAPACITY))
+def test_layout_total_of_one_call(env, name, size):
+    c = ac.BY_NAME[name]
+    i, _ = ac.inputs(env, name, size)
+    ctx = env.hvo.Context(max_batch=4)
+    o = opened(env, c, i)
+    try:
+        c.run(env, ctx, i, o)
+        assert ctx.debug_call_arena() == CAPACITY[(name, size)]
+    finally:
+        closed(o); ctx.close()
+
+
+def _times_ok(ms, n):
+    ms = tuple(ms)
+    assert len(ms) == n and all(np.isfinite(v) and v >= 0 for v in ms), ms
+
+
+def test_kernel_times(env):
+    """the last call's device times: 0.0 on a context whose calls launched nothing (no candidate, no frame feature), finite and not negative
+    after a call that ran, and of the documented length in the three results that carry them.  No magnitude is asserted"""
+    hvo = env.hvo
+    ctx = hvo.Context(max_batch=4)
+    try:
+        with pytest.raises(hvo.HvoError):
+            ctx.pnp_ransac(ac.pnp_ref.CAM, [], hvo.pnp_params(**ac.PNP_P))
+        assert ctx.pnp_last_kernel_ms() == (0.0, 0.0)
+        with pytest.raises(hvo.HvoError):
+            ctx.line_struct_optimize([])
+        assert ctx.line_opt_last_kernel_ms() == (0.0, 0.0)
+        i, _ = ac.inputs(env, "search_by_bow", "S")
+        none = dict(desc=np.zeros((0, 32), np.uint8), node_id=np.zeros(0, np.int32), angle=np.zeros(0, np.float32))
+        got = ctx.search_by_bow(none, [i["kf"]])
+        assert got[0][1] == 0 and len(got[0][0]) == 0 and ctx.bow_last_kernel_ms() == (0.0, 0.0)
+        for name, last, n in (("pnp_ransac", ctx.pnp_last_kernel_ms, 2), ("search_by_bow", ctx.bow_last_kernel_ms, 2), ("line_struct_optimize", ctx.line_opt_last_kernel_ms, 2)):
+            ac.BY_NAME[name].run(env, ctx, ac.inputs(env, name, "S")[0], {})
+            _times_ok(last(), n)
+        assert ctx.bow_last_kernel_ms()[0] == 0.0                                      # no ComputeBoW ran on this context
+        kfs = ac.BY_NAME["search_by_projection_keyframe"].run(env, ctx, ac.inputs(env, "search_by_projection_keyframe", "S")[0], {})
+        _times_ok(kfs[0]["kernel_ms"], 2)
+        fused = ac.BY_NAME["fuse_points"].run(env, ctx, ac.inputs(env, "fuse_points", "S")[0], {})
+        _times_ok(fused[0]["kernel_ms"], 3)
+        _, summary = ac.BY_NAME["create_new_map_points"].run(env, ctx, ac.inputs(env, "create_new_map_points", "S")[0], {})
+        _times_ok(summary["kernel_ms"], 3)
+    finally:
+        ctx.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------- 5. the stream forms
 @pytest.fixture(scope="module")
 def world(env):
