@@ -94,7 +94,7 @@ EXPORTS = [
     "hvo_pnp_default_params", "hvo_pnp_ransac", "hvo_stream_pnp_ransac", "hvo_pnp_last_kernel_ms", "hvo_stream_pnp_last_kernel_ms",
     "hvo_search_by_projection_keyframe", "hvo_stream_search_by_projection_keyframe",
     "hvo_fuse_points", "hvo_fuse_points_slots", "hvo_stream_fuse_points",
-    "hvo_create_new_map_points", "hvo_stream_create_new_map_points",
+    "hvo_create_new_map_points", "hvo_stream_create_new_map_points", "hvo_create_new_map_lines", "hvo_stream_create_new_map_lines",
     "hvo_update_map_planes", "hvo_stream_update_map_planes", "hvo_plane_map_get_points", "hvo_plane_update_transform",
 ]
 
@@ -886,6 +886,99 @@ def _np_finish(n1, R, S, owner, outs, ok):
         d["created_idx1"] = o["created_idx1"][:nc]; d["created_idx2"] = o["created_idx2"][:nc]
         res.append(d)
     return res, dict(owner=owner[:n1] if ok else owner, n_new=S.n_new, kernel_ms=tuple(S.kernel_ms))
+
+
+NL_MAX_LINES, NL_MAX_NEIGHBOURS = 2048, 16
+NL_PAIR_AS_WRITTEN, NL_PAIR_ALIGNED = 0, 1
+NL_OUTCOMES = ("created", "no match", "idx range", "occupied 1", "occupied 2", "occupied 3", "bad octave", "epipolar parallel", "norm zero 23", "norm zero 1",
+               "not coplanar", "w == 0 start", "w == 0 end", "parallax start", "parallax end", "ratio 1", "ratio 2", "ratio 3",
+               "behind 1s", "behind 1e", "behind 2s", "behind 2e", "behind 3s", "behind 3e", "reproj 1s", "reproj 1e", "reproj 2s", "reproj 2e", "reproj 3s", "reproj 3e",
+               "disjoint 1", "overlap 1", "disjoint 2", "overlap 2", "disjoint 3", "overlap 3")
+NL_UNTOUCHED = -7           # what the outputs hold before the call: a refusal leaves them so
+
+
+class NlKeyframe(C.Structure):
+    """hvo_nl_keyframe: the current key frame, and each neighbour"""
+    _fields_ = [("n", C.c_int32), ("kl", C.c_void_p), ("linefn", C.c_void_p), ("desc", C.c_void_p), ("has_map_line", C.c_void_p), ("Tcw", C.c_float * 12),
+                ("cam", C.c_float * 6), ("mb", C.c_float), ("median_depth", C.c_float), ("skip", C.c_uint8)]
+
+
+class NlParams(C.Structure):
+    """hvo_nl_params"""
+    _fields_ = [("th_high", C.c_int32), ("nn_ratio", C.c_float), ("n_levels", C.c_int32), ("scale_factor", C.c_float), ("pairing", C.c_int32)]
+
+
+class NlMatch(C.Structure):
+    """hvo_nl_match"""
+    _fields_ = [("match_idx", C.c_void_p), ("n_matched", C.c_int32), ("gate", C.c_int32)]
+
+
+class NlResult(C.Structure):
+    """hvo_nl_result"""
+    _fields_ = [("kf2", C.c_int32), ("kf3", C.c_int32), ("mv2", C.c_int32), ("mv3", C.c_int32), ("outcome", C.c_void_p), ("line3d", C.c_void_p),
+                ("created_idx0", C.c_void_p), ("created_idx1", C.c_void_p), ("created_idx2", C.c_void_p), ("n_created", C.c_int32), ("status", C.c_int32)]
+
+
+class NlSummary(C.Structure):
+    """hvo_nl_summary"""
+    _fields_ = [("owner_pair", C.c_void_p), ("n_new", C.c_int32), ("n_pairs", C.c_int32), ("kernel_ms", C.c_float * 3)]
+
+
+assert C.sizeof(NlKeyframe) == 128 and C.sizeof(NlParams) == 20 and C.sizeof(NlMatch) == 16 and C.sizeof(NlResult) == 64 and C.sizeof(NlSummary) == 32
+
+
+def _nl_keyframe(K, kf, resident=False):
+    """kf: dict of kl, linefn, desc, has_map_line, Tcw, cam (fx, fy, cx, cy), mb, median_depth, skip; a missing array stays NULL and is the
+    library's to refuse.  resident: only has_map_line, Tcw and cam are read"""
+    a = {}
+    get = lambda k: None if kf.get(k) is None else kf[k]
+    if not resident:
+        a["kl"] = None if get("kl") is None else np.ascontiguousarray(kf["kl"], KEYLINE_DT)
+        K.n = int(kf["n"]) if "n" in kf else (len(a["kl"]) if a["kl"] is not None else 0)
+        a["linefn"] = None if get("linefn") is None else np.ascontiguousarray(kf["linefn"], np.float64).reshape(-1, 3)
+        a["desc"] = None if get("desc") is None else np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32)
+    a["has_map_line"] = None if get("has_map_line") is None else np.ascontiguousarray(np.asarray(kf["has_map_line"]).astype(bool), np.uint8).reshape(-1)
+    for k, v in a.items(): setattr(K, k, v.ctypes.data if v is not None and v.size else None)
+    T = np.asarray(kf["Tcw"], np.float32).reshape(12)
+    for k in range(12): K.Tcw[k] = T[k]
+    for k in range(4): K.cam[k] = float(kf["cam"][k])
+    K.mb = float(kf.get("mb", 0.0)); K.median_depth = float(kf.get("median_depth", 1.0)); K.skip = 1 if kf.get("skip") else 0
+    return a
+
+
+def _nl_args(n1, kfs, th_high, nn_ratio, n_levels, scale_factor, pairing, n_pairs_cap):
+    nk = len(kfs); m = max(n1, 1)
+    cap = nk * (nk - 1) // 2 if n_pairs_cap is None else int(n_pairs_cap)
+    K = (NlKeyframe * max(nk, 1))(); M = (NlMatch * max(nk, 1))(); R = (NlResult * max(cap, 1))(); keep = []; mouts = []; outs = []
+    for j, kf in enumerate(kfs):
+        keep.append(_nl_keyframe(K[j], kf))
+        mi = np.full(m, NL_UNTOUCHED, np.int32)
+        M[j].match_idx = mi.ctypes.data; M[j].n_matched = M[j].gate = NL_UNTOUCHED
+        mouts.append(mi)
+    for p in range(cap):
+        o = dict(outcome=np.full(m, NL_UNTOUCHED, np.int8), line3d=np.full((m, 6), NL_UNTOUCHED, np.float32), created_idx0=np.full(m, NL_UNTOUCHED, np.int32),
+                 created_idx1=np.full(m, NL_UNTOUCHED, np.int32), created_idx2=np.full(m, NL_UNTOUCHED, np.int32))
+        for k in o: setattr(R[p], k, o[k].ctypes.data)
+        R[p].kf2 = R[p].kf3 = R[p].mv2 = R[p].mv3 = R[p].n_created = R[p].status = NL_UNTOUCHED
+        outs.append(o)
+    S = NlSummary(); owner = np.full(m, NL_UNTOUCHED, np.int32)
+    S.owner_pair = owner.ctypes.data; S.n_new = S.n_pairs = NL_UNTOUCHED
+    P = NlParams(); P.th_high = th_high; P.nn_ratio = nn_ratio; P.n_levels = n_levels; P.scale_factor = scale_factor; P.pairing = pairing
+    return K, M, R, S, P, cap, owner, mouts, outs, keep
+
+
+def _nl_finish(n1, M, R, S, owner, mouts, outs, ok):
+    """(one dict per neighbour, one dict per pair, the summary); after a refusal (ok False) every array is returned whole, as the call left it,
+    and every result record the caller made room for is listed"""
+    matches = [dict(match_idx=mi[:n1] if ok else mi, n_matched=M[j].n_matched, gate=M[j].gate) for j, mi in enumerate(mouts)]
+    res = []
+    for p, o in enumerate(outs[:max(S.n_pairs, 0)] if ok else outs):
+        d = dict(kf2=R[p].kf2, kf3=R[p].kf3, mv2=R[p].mv2, mv3=R[p].mv3, n_created=R[p].n_created, status=R[p].status)
+        for k in ("outcome", "line3d"): d[k] = o[k][:n1] if ok else o[k]
+        nc = max(0, min(R[p].n_created, n1)) if ok else len(o["created_idx0"])
+        for k in ("created_idx0", "created_idx1", "created_idx2"): d[k] = o[k][:nc]
+        res.append(d)
+    return matches, res, dict(owner_pair=owner[:n1] if ok else owner, n_new=S.n_new, n_pairs=S.n_pairs, kernel_ms=tuple(S.kernel_ms))
 
 
 def line_struct_params(**kw):
@@ -2154,6 +2247,40 @@ class Context:
         self._chk(rc, "create_new_map_points")
         return _np_finish(n1, R, S, owner, outs, True)
 
+    def create_new_map_lines(self, cur, kfs, th_high=80, nn_ratio=0.85, n_levels=8, scale_factor=1.2, pairing=NL_PAIR_AS_WRITTEN, n_pairs_cap=None, check=True):
+        """LocalMapping::CreateNewMapLinesConstraint (src/LocalMapping.cc:1064-1565): SearchForTriangulation of the current key frame `cur` against
+        every neighbour of kfs that passes the baseline gate, and the three-view triangulation of every pair of searched neighbours, in one call.
+        cur and each neighbour: dict(kl, linefn, desc, has_map_line, Tcw, cam (fx, fy, cx, cy); a neighbour also mb, median_depth, skip).
+        n_levels / scale_factor: the LINE pyramid.  Returns (one dict per neighbour: match_idx, n_matched, gate; one dict per pair: kf2, kf3, mv2, mv3,
+        outcome (NL_OUTCOMES), line3d, created_idx0 / idx1 / idx2 (the list the caller walks), n_created, status; the summary: owner_pair, n_new,
+        n_pairs, kernel_ms).  check=False: (return code, message, the three) instead of an exception; a refused call leaves every output at
+        NL_UNTOUCHED."""
+        ck = NlKeyframe(); keep1 = _nl_keyframe(ck, cur); n1 = ck.n
+        K, M, R, S, P, cap, owner, mouts, outs, keep = _nl_args(n1, kfs, th_high, nn_ratio, n_levels, scale_factor, pairing, n_pairs_cap)
+        f = lib().hvo_create_new_map_lines; f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        rc = f(self.h, C.addressof(P), C.addressof(ck), len(kfs), C.addressof(K), C.addressof(M), cap, C.addressof(R), C.addressof(S))
+        del keep1, keep
+        if not check:
+            return (rc, lib().hvo_last_error(self.h).decode()) + _nl_finish(n1, M, R, S, owner, mouts, outs, rc == HVO_OK)
+        self._chk(rc, "create_new_map_lines")
+        return _nl_finish(n1, M, R, S, owner, mouts, outs, True)
+
+    def debug_match_arena(self, fill=None, min_bytes=0):
+        """test door (not in include/hvo.h): grow the matching arena to min_bytes the way a call would, set its whole device capacity to the
+        byte `fill` (None: leave it), return the capacity"""
+        L = lib(); f = L.hvo_debug_match_arena; f.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]; f.restype = C.c_int
+        cap = C.c_size_t(0)
+        self._chk(f(self.h, -1 if fill is None else int(fill), int(min_bytes), C.byref(cap)), "debug_match_arena")
+        return cap.value
+
+    def debug_match_arena_peek(self, offset, n):
+        """test door: n bytes of the matching arena's device block from `offset`"""
+        L = lib(); f = L.hvo_debug_match_arena_peek; f.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]; f.restype = C.c_int
+        out = np.zeros(int(n), np.uint8)
+        self._chk(f(self.h, int(offset), int(n), _p(out)), "debug_match_arena_peek")
+        return out
+
     def pnp_last_kernel_ms(self):
         """(hypothesis kernels, refine kernels): device ms of the last pnp_ransac"""
         ms = np.zeros(2, np.float32)
@@ -2699,6 +2826,25 @@ class Stream:
             return (rc, lib().hvo_stream_last_error(self.h).decode()) + _np_finish(n1, R, S, owner, outs, rc == HVO_OK)
         self._chk(rc, "stream_create_new_map_points")
         return _np_finish(n1, R, S, owner, outs, True)
+
+    def create_new_map_lines(self, cur, cam, Tcw, has_map_line, kfs, th_high=80, nn_ratio=0.85, n_levels=8, scale_factor=1.2, pairing=NL_PAIR_AS_WRITTEN,
+                             n_pairs_cap=None, check=True):
+        """LocalMapping::CreateNewMapLinesConstraint with the resident frame `cur` (either LSD stage) as the current key frame under Tcw with camera
+        cam (fx, fy, cx, cy): key lines, line functions and descriptors are read where the stage left them; only the occupancy bytes (one per
+        line of the frame), the pose and the neighbours go up.  Returns what Context.create_new_map_lines returns."""
+        hm = np.asarray(has_map_line).astype(bool).reshape(-1); n1 = len(hm)
+        has = np.zeros(max(n1, self.kl_cap, 1), np.uint8); has[:n1] = hm           # (a frame with more lines than bytes given reads zeros, not past the end)
+        K, M, R, S, P, cap, owner, mouts, outs, keep = _nl_args(max(n1, self.kl_cap), kfs, th_high, nn_ratio, n_levels, scale_factor, pairing, n_pairs_cap)
+        cm = (C.c_float * 6)(*([float(v) for v in cam[:4]] + [0.0, 0.0]))
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12)
+        f = lib().hvo_stream_create_new_map_lines; f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        rc = f(self.h, cur, C.addressof(cm), C.addressof(P), T.ctypes.data, has.ctypes.data, len(kfs), C.addressof(K), C.addressof(M), cap, C.addressof(R), C.addressof(S))
+        del keep
+        if not check:
+            return (rc, lib().hvo_stream_last_error(self.h).decode()) + _nl_finish(n1, M, R, S, owner, mouts, outs, rc == HVO_OK)
+        self._chk(rc, "stream_create_new_map_lines")
+        return _nl_finish(n1, M, R, S, owner, mouts, outs, True)
 
     def search_by_bow(self, cur, voc, kfs, nnratio=0.7, check_orientation=True, th_low=50):
         """SearchByBoW of the key frames kfs (dicts of desc, node_id, has_map_point, angle) against the resident frame `cur`, which holds its bag

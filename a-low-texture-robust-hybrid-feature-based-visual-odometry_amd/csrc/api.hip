@@ -235,6 +235,7 @@ void hvo_destroy(hvo_ctx *ctx)
     for (hipEvent_t e : ctx->kfs_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->fuse_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->np_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->nl_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ls_ev) if (e) (void)hipEventDestroy(e);
     delete ctx;
 }

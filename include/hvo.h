@@ -1408,6 +1408,106 @@ int hvo_create_new_map_points(hvo_ctx *ctx, const hvo_camera *cam, const hvo_np_
 int hvo_stream_create_new_map_points(hvo_stream *s, int64_t cur, const hvo_vocabulary *voc, const hvo_camera *cam, const hvo_np_params *params, const float Tcw[12],
                                      const uint8_t *has_map_point, int n_kf, const hvo_np_keyframe *neighbours, hvo_np_result *results, hvo_np_summary *summary);
 
+/* ---- LocalMapping::CreateNewMapLinesConstraint (reference src/LocalMapping.cc:1064-1565; csrc/line_triang.inc) ----
+ * LSDmatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, true) (src/LSDmatcher.cpp:1195-1231: FrameBFMatch both ways with
+ * lineDescriptorMAD, the mutual check, the two occupancy bytes) of the current key frame against every neighbour that passes the baseline
+ * gate, and for every pair a < b of the searched neighbours and every current line the three-view triangulation with all of its gates, in
+ * one call with one synchronisation.  The matches are mutual, so a match vector maps current lines to neighbour lines injectively and a key
+ * frame at list position p is only indexed through match vector p: a created line can block nothing but later triples of the same current
+ * line.  The call evaluates every (pair, line) under the occupancy at entry; the line at ikl is created by the first pair, in (a, b) order,
+ * that passes.  `if(i>1 && CheckNewKeyFrames()) return;` leaves before anything is created: a caller that sees a new key frame discards
+ * the call's result.  new MapLine, AddObservation, AddMapLine, ComputeDistinctiveDescriptors and UpdateAverageDir stay with the caller
+ * (examples/create_map_lines.cpp).  A context is not thread-safe: the thread that runs this call beside CreateNewMapPoints owns a context.
+ *
+ * The reference skips a gated neighbour BEFORE it pushes the match vector, so its list of match vectors is compacted, and then reads
+ * pKF2 = vpNeighKFs[a] by LIST POSITION.  After a gated neighbour match vectors are applied to the wrong key frames, and only `idx >= NL`
+ * guards that.  HVO_NL_PAIR_AS_WRITTEN does exactly this; HVO_NL_PAIR_ALIGNED takes the searched neighbour itself.  Every pair reports
+ * both positions.  Readings: csrc/line_triang.inc and DESIGN.md section 7; tests/new_lines_ref.py is the definition. */
+typedef struct {               /* the current key frame, and each neighbour */
+    int32_t n;                 /* NL */
+    const hvo_keyline *kl;     /* mvKeyLines: sx, sy, ex, ey, angle and octave are read */
+    const double  *linefn;     /* mvKeyLineFunctions, n x 3 */
+    const uint8_t *desc;       /* mLineDescriptors, n x 32 */
+    const uint8_t *has_map_line;     /* one byte per line: GetMapLine(idx) != NULL */
+    float Tcw[12];             /* rows 0..2 of the pose, row-major 3 x 4 */
+    hvo_camera cam;            /* the key frame's own mK: fx, fy, cx, cy are read */
+    float mb;                  /* neighbours: `baseline < pKF2->mb` (0: never too short) */
+    float median_depth;        /* neighbours: pKF2->ComputeSceneMedianDepth(2) as the caller read it (the map's points change beside this call) */
+    uint8_t skip;              /* neighbours: the caller's own pre-gate (the monocular baseline / depth ratio) */
+} hvo_nl_keyframe;
+#define HVO_NL_PAIR_AS_WRITTEN 0
+#define HVO_NL_PAIR_ALIGNED    1
+typedef struct {
+    int32_t th_high;           /* TH_HIGH (80); above 255 is refused */
+    float nn_ratio;            /* lmatcher(0.85) */
+    int32_t n_levels;          /* of the LINE pyramid, 1 .. 16 */
+    float scale_factor;        /* of the LINE pyramid: mvLevelSigma2Line[l] = sf[l] * sf[l], sf[0] = 1, sf[l] = sf[l - 1] * scale_factor, all in float
+                                * (LINEextractor's constructor; its level 0 is 1) */
+    int32_t pairing;           /* HVO_NL_PAIR_* */
+} hvo_nl_params;
+/* outcome codes: the first `continue` the triple runs into, in the reference's order; one code per `continue` (the six depth signs, the six
+ * line distances and the three overlap tests each have their own: view 1 is the current key frame, S / E the start / end point) */
+#define HVO_NL_CREATED       0
+#define HVO_NL_NO_MATCH      1   /* idx1 == -1 || idx2 == -1 */
+#define HVO_NL_IDX_RANGE     2   /* idx1 >= pKF2->NL || idx2 >= pKF3->NL (a shifted pair under HVO_NL_PAIR_AS_WRITTEN) */
+#define HVO_NL_OCCUPIED_1    3   /* never reached by a call: the search drops a match of an occupied current line, so the index test fires first */
+#define HVO_NL_OCCUPIED_2    4   /* _2 and _3: reached by a shifted pair only (the search drops a match whose own line is occupied) */
+#define HVO_NL_OCCUPIED_3    5
+#define HVO_NL_BAD_OCTAVE    6   /* an octave of the three outside [0, n_levels): the reference would read mvLevelSigma2Line out of range */
+#define HVO_NL_EPI_PARALLEL  7   /* abs(Result1) > 0.996 || abs(Result2) > 0.996 */
+#define HVO_NL_NORM_ZERO_23  8
+#define HVO_NL_NORM_ZERO_1   9
+#define HVO_NL_NOT_COPLANAR  10  /* CosSita > 0.0087 */
+#define HVO_NL_W_ZERO_S      11
+#define HVO_NL_W_ZERO_E      12
+#define HVO_NL_PARALLAX_S    13
+#define HVO_NL_PARALLAX_E    14
+#define HVO_NL_RATIO_1       15
+#define HVO_NL_RATIO_2       16
+#define HVO_NL_RATIO_3       17
+#define HVO_NL_BEHIND_1S     18  /* .. _1E 19, _2S 20, _2E 21, _3S 22, _3E 23 */
+#define HVO_NL_REPROJ_1S     24  /* .. _1E 25, _2S 26, _2E 27, _3S 28, _3E 29 */
+#define HVO_NL_DISJOINT_1    30  /* the projected and the observed segment do not overlap on the chosen axis */
+#define HVO_NL_OVERLAP_1     31  /* an overlap ratio below 0.85 */
+#define HVO_NL_DISJOINT_2    32
+#define HVO_NL_OVERLAP_2     33
+#define HVO_NL_DISJOINT_3    34
+#define HVO_NL_OVERLAP_3     35
+#define HVO_NL_GATE_SEARCHED 0   /* as HVO_NP_GATE_* */
+#define HVO_NL_GATE_SKIP     1
+#define HVO_NL_GATE_BASELINE 2
+#define HVO_NL_MAX_LINES      2048
+#define HVO_NL_MAX_NEIGHBOURS 16
+typedef struct {               /* per neighbour; n1 = the current key frame's line count */
+    int32_t *match_idx;        /* n1: vMatchedIndices, -1 for no match (all -1 for a neighbour that was not searched) */
+    int32_t n_matched, gate;   /* nlmatch; HVO_NL_GATE_* */
+} hvo_nl_match;
+typedef struct {               /* per pair.  outcome must be given; every other pointer may be NULL */
+    int32_t kf2, kf3, mv2, mv3;         /* neighbour positions: which served as pKF2 / pKF3, and whose match vectors were applied */
+    int8_t  *outcome;                   /* n1: HVO_NL_* */
+    float   *line3d;                    /* n1 x 6: start and end point as far as they were computed, zeros otherwise */
+    int32_t *created_idx0, *created_idx1, *created_idx2;   /* room for n1 each: ikl ascending, with its idx1 and idx2, after the chain is resolved */
+    int32_t n_created, status;
+} hvo_nl_result;
+typedef struct {
+    int32_t *owner_pair;       /* n1 (may be NULL): the pair that creates the line at ikl, or -1 */
+    int32_t n_new, n_pairs;    /* n_pairs: results written, ns (ns - 1) / 2 for ns searched neighbours */
+    float kernel_ms[3];        /* device time of the search, of the triangulation, of resolve + compaction */
+} hvo_nl_summary;
+/* On host arrays.  Limits: 2048 lines per side, 16 neighbours (120 pairs) per call, HVO_ERR_UNSUPPORTED beyond.  A missing array,
+ * th_high > 255, n_levels outside 1 .. 16, an unknown pairing or n_pairs_cap below the number of pairs are HVO_ERR_INVALID_ARG.  Every
+ * refusal is whole: nothing is written and hvo_last_error says why.  Fewer than 2 neighbours, fewer than 2 searched, or n == 0 on the current
+ * side is HVO_OK with nothing created (the matches' gates are still reported).  A neighbour with fewer than 2 lines matches nothing, and so
+ * does a current key frame with fewer than 2 (knnMatch(k = 2) needs two train descriptors).  One synchronisation per call. */
+int hvo_create_new_map_lines(hvo_ctx *ctx, const hvo_nl_params *params, const hvo_nl_keyframe *current, int n_kf, const hvo_nl_keyframe *neighbours,
+                             hvo_nl_match *matches, int n_pairs_cap, hvo_nl_result *results, hvo_nl_summary *summary);
+/* The resident frame `cur` (either LSD stage) is the current key frame under Tcw with camera cam: key lines, line functions and descriptors
+ * are read where the stage left them; only the occupancy bytes, the pose and the neighbours go up.  The result is the host-array form's on
+ * the downloaded frame, bit for bit. */
+int hvo_stream_create_new_map_lines(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_nl_params *params, const float Tcw[12],
+                                    const uint8_t *has_map_line, int n_kf, const hvo_nl_keyframe *neighbours, hvo_nl_match *matches, int n_pairs_cap,
+                                    hvo_nl_result *results, hvo_nl_summary *summary);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer. Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

@@ -422,9 +422,40 @@ struct NewMapPoints {
     int n_created = 0, gate = 0;
 };
 
+// What LocalMapping::CreateNewMapLinesConstraint leaves: per neighbour vMatchedIndices of SearchForTriangulation (-1: none), nlmatch and the gate;
+// per pair of searched neighbours the positions that served as key frames (kf2, kf3) and as match vectors (mv2, mv3), the outcome of every
+// current line (HVO_NL_*), both end points as far as they were computed and -- after the chain is resolved -- the lines this pair creates in
+// ascending ikl.  The caller walks the pairs in order (LocalMapping.cc:1541-1559): new MapLine(line3d[ikl], vManhAxisIdx[ikl]), three
+// AddObservation, three AddMapLine, ComputeDistinctiveDescriptors, UpdateAverageDir, mpMap->AddMapLine, mlpRecentAddedMapLines.  A caller
+// that saw CheckNewKeyFrames() during the call discards the result.  A context is not thread-safe: the thread that runs this beside
+// CreateNewMapPoints has a context of its own.
+struct NewMapLineMatches { std::vector<int> match_idx; int n_matched = 0, gate = 0; };
+struct NewMapLines {
+    int kf2 = -1, kf3 = -1, mv2 = -1, mv3 = -1, n_created = 0;
+    std::vector<int8_t> outcome; std::vector<float> line3d; std::vector<int> created_idx0, created_idx1, created_idx2;
+};
+
 class LocalMapping {
 public:
     explicit LocalMapping(hvo_ctx *ctx) : ctx_(ctx) {}
+    // CreateNewMapLinesConstraint (LocalMapping.cc:1064-1565) on host arrays: one device call.  Returns nnew; res has one entry per pair of searched
+    // neighbours; owner_pair (may be null) gets the pair that creates the line at ikl, or -1.  nLevels / scale: the LINE pyramid
+    int CreateNewMapLinesConstraint(const hvo_nl_keyframe &current, int n_kf, const hvo_nl_keyframe *vpNeighKFs, std::vector<NewMapLineMatches> &matches,
+                                    std::vector<NewMapLines> &res, std::vector<int> *owner_pair = nullptr, int pairing = HVO_NL_PAIR_AS_WRITTEN, int nLevels = 8,
+                                    float scale = 1.2f, float kernel_ms[3] = nullptr) const
+    {
+        hvo_nl_params p = { 80, 0.85f, nLevels, scale, pairing };
+        std::vector<hvo_nl_match> m; std::vector<hvo_nl_result> r; hvo_nl_summary s = nl_begin(current.n, n_kf, matches, res, m, r, owner_pair);
+        check(hvo_create_new_map_lines(ctx_, &p, &current, n_kf, vpNeighKFs, m.data(), (int)r.size(), r.data(), &s), "hvo_create_new_map_lines");
+        return nl_end(matches, res, m, r, s, kernel_ms);
+    }
+    // the resident frame `cur` (either LSD stage) is the current key frame under Tcw: its key lines, line functions and descriptors stay on the
+    // device.  n_lines: the number of occupancy bytes given, the frame's line count; the result arrays have the stream's key-line capacity
+    // (entries past the frame's count keep their initial values), so a wrong n_lines reads zeros and overruns nothing
+    int CreateNewMapLinesConstraint(FrameStream &fs, int64_t cur, const hvo_camera &cam, const float Tcw[12], const uint8_t *has_map_line, int n_lines, int n_kf,
+                                    const hvo_nl_keyframe *vpNeighKFs, std::vector<NewMapLineMatches> &matches, std::vector<NewMapLines> &res,
+                                    std::vector<int> *owner_pair = nullptr, int pairing = HVO_NL_PAIR_AS_WRITTEN, int nLevels = 8, float scale = 1.2f,
+                                    float kernel_ms[3] = nullptr) const;
     // CreateNewMapPoints (LocalMapping.cc:335-580) on host arrays: the current key frame against vpNeighKFs in list order, one device call.
     // A caller that leaves after neighbour i (`if(i>0 && CheckNewKeyFrames()) return;`) walks res[0 .. i] only.  Returns nnew; owner (may be
     // null) gets the neighbour that creates the point at idx1, or -1.
@@ -442,6 +473,36 @@ public:
                            int n_kf, const hvo_np_keyframe *vpNeighKFs, std::vector<NewMapPoints> &res, std::vector<int> *owner = nullptr, float mfScaleFactor = 1.2f,
                            int nLevels = 8, float kernel_ms[3] = nullptr) const;
 private:
+    static hvo_nl_summary nl_begin(int n1, int n_kf, std::vector<NewMapLineMatches> &matches, std::vector<NewMapLines> &res, std::vector<hvo_nl_match> &m,
+                                   std::vector<hvo_nl_result> &r, std::vector<int> *owner_pair)
+    {
+        const size_t k = (size_t)std::max(n1, 1), nk = (size_t)std::max(n_kf, 0), np = nk * (nk > 0 ? nk - 1 : 0) / 2;
+        matches.assign(nk, NewMapLineMatches()); res.assign(np, NewMapLines()); m.assign(std::max<size_t>(nk, 1), hvo_nl_match()); r.assign(std::max<size_t>(np, 1), hvo_nl_result());
+        for (size_t j = 0; j < nk; j++) { matches[j].match_idx.assign(k, -1); m[j].match_idx = matches[j].match_idx.data(); }
+        for (size_t q = 0; q < np; q++) {
+            NewMapLines &x = res[q];
+            x.outcome.assign(k, HVO_NL_NO_MATCH); x.line3d.assign(6 * k, 0.f); x.created_idx0.assign(k, -1); x.created_idx1.assign(k, -1); x.created_idx2.assign(k, -1);
+            r[q].outcome = x.outcome.data(); r[q].line3d = x.line3d.data();
+            r[q].created_idx0 = x.created_idx0.data(); r[q].created_idx1 = x.created_idx1.data(); r[q].created_idx2 = x.created_idx2.data();
+        }
+        if (np == 0) r.clear();
+        hvo_nl_summary s; memset(&s, 0, sizeof(s));
+        if (owner_pair) { owner_pair->assign(k, -1); s.owner_pair = owner_pair->data(); }
+        return s;
+    }
+    static int nl_end(std::vector<NewMapLineMatches> &matches, std::vector<NewMapLines> &res, const std::vector<hvo_nl_match> &m, const std::vector<hvo_nl_result> &r,
+                      const hvo_nl_summary &s, float kernel_ms[3])
+    {
+        for (size_t j = 0; j < matches.size(); j++) { matches[j].n_matched = m[j].n_matched; matches[j].gate = m[j].gate; }
+        res.resize((size_t)std::max(s.n_pairs, 0));
+        for (size_t q = 0; q < res.size(); q++) {
+            NewMapLines &x = res[q];
+            x.kf2 = r[q].kf2; x.kf3 = r[q].kf3; x.mv2 = r[q].mv2; x.mv3 = r[q].mv3; x.n_created = r[q].n_created;
+            x.created_idx0.resize((size_t)x.n_created); x.created_idx1.resize((size_t)x.n_created); x.created_idx2.resize((size_t)x.n_created);
+        }
+        if (kernel_ms) for (int q = 0; q < 3; q++) kernel_ms[q] = s.kernel_ms[q];
+        return s.n_new;
+    }
     static hvo_np_summary np_begin(int n1, int n_kf, std::vector<NewMapPoints> &res, std::vector<hvo_np_result> &r, std::vector<int> *owner)
     {
         const size_t k = (size_t)std::max(n1, 1);
@@ -1046,6 +1107,21 @@ inline int ORBmatcher::Fuse(FrameStream &fs, int64_t cur, const hvo_camera &cam,
     hvo_fuse_result r = fuse_result(res, vpMapPoints ? vpMapPoints->n : n_slots);
     check(hvo_stream_fuse_points(fs.get(), cur, &cam, &p, Tcw, skip, vpMapPoints, map, n_slots, slots, &r), "hvo_stream_fuse_points");
     return fuse_take(res, r);
+}
+
+inline int LocalMapping::CreateNewMapLinesConstraint(FrameStream &fs, int64_t cur, const hvo_camera &cam, const float Tcw[12], const uint8_t *has_map_line, int n_lines,
+                                                     int n_kf, const hvo_nl_keyframe *vpNeighKFs, std::vector<NewMapLineMatches> &matches, std::vector<NewMapLines> &res,
+                                                     std::vector<int> *owner_pair, int pairing, int nLevels, float scale, float kernel_ms[3]) const
+{
+    hvo_nl_params p = { 80, 0.85f, nLevels, scale, pairing };
+    // The library reads one occupancy byte and writes one entry per line the frame HOLDS, and the C ABI takes no count: every array is sized by
+    // the stream's key-line capacity, which bounds that count, and the occupancy bytes are copied into a zero-padded buffer of that size.
+    const int cap = std::max(std::max(n_lines, 0), fs.klCap());
+    std::vector<uint8_t> has((size_t)std::max(cap, 1), 0);
+    if (has_map_line && n_lines > 0) memcpy(has.data(), has_map_line, (size_t)n_lines);
+    std::vector<hvo_nl_match> m; std::vector<hvo_nl_result> r; hvo_nl_summary s = nl_begin(cap, n_kf, matches, res, m, r, owner_pair);
+    check(hvo_stream_create_new_map_lines(fs.get(), cur, &cam, &p, Tcw, has.data(), n_kf, vpNeighKFs, m.data(), (int)r.size(), r.data(), &s), "hvo_stream_create_new_map_lines");
+    return nl_end(matches, res, m, r, s, kernel_ms);
 }
 
 inline int LocalMapping::CreateNewMapPoints(FrameStream &fs, int64_t cur, const ORBVocabulary &voc, const hvo_camera &cam, const float Tcw[12], const uint8_t *has_map_point,
