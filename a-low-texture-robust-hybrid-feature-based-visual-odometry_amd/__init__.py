@@ -95,6 +95,7 @@ EXPORTS = [
     "hvo_search_by_projection_keyframe", "hvo_stream_search_by_projection_keyframe",
     "hvo_fuse_points", "hvo_fuse_points_slots", "hvo_stream_fuse_points",
     "hvo_create_new_map_points", "hvo_stream_create_new_map_points", "hvo_create_new_map_lines", "hvo_stream_create_new_map_lines",
+    "hvo_refresh_map_points", "hvo_refresh_map_lines", "hvo_point_map_refresh", "hvo_line_map_refresh",
     "hvo_update_map_planes", "hvo_stream_update_map_planes", "hvo_plane_map_get_points", "hvo_plane_update_transform",
 ]
 
@@ -980,6 +981,93 @@ def _nl_finish(n1, M, R, S, owner, mouts, outs, ok):
         res.append(d)
     return matches, res, dict(owner_pair=owner[:n1] if ok else owner, n_new=S.n_new, n_pairs=S.n_pairs, kernel_ms=tuple(S.kernel_ms))
 
+MR_DESCRIPTOR, MR_GEOMETRY = 1, 2
+MR_MAX_OBS, MR_MAX_FEATURES, MR_MAX_OBS_TOTAL = 256, 65536, 1 << 20
+MR_REFRESHED, MR_SKIPPED, MR_NO_OBS, MR_DESC_KEPT, MR_BAD_LEVEL = range(5)
+MR_STATUS = ("refreshed", "skipped", "no observations", "descriptor kept", "bad level")
+MR_UNTOUCHED = 119          # what the outputs hold before the call: an entry that is not written stays so
+
+
+class MrParams(C.Structure):
+    """hvo_mr_params"""
+    _fields_ = [("n_levels", C.c_int32), ("scale_factor", C.c_float), ("what", C.c_int32)]
+
+
+class MrInput(C.Structure):
+    """hvo_mr_input"""
+    _fields_ = [("n", C.c_int32), ("obs_start", C.c_void_p), ("obs_desc", C.c_void_p), ("obs_Ow", C.c_void_p), ("kf_bad", C.c_void_p), ("ref_Ow", C.c_void_p),
+                ("ref_level", C.c_void_p), ("skip", C.c_void_p)]
+
+
+class MrPointOut(C.Structure):
+    """hvo_mr_point_out"""
+    _fields_ = [("best_obs", C.c_void_p), ("best_median", C.c_void_p), ("desc", C.c_void_p), ("normal", C.c_void_p), ("max_dist", C.c_void_p), ("min_dist", C.c_void_p),
+                ("status", C.c_void_p), ("kernel_ms", C.c_float)]
+
+
+class MrLineOut(C.Structure):
+    """hvo_mr_line_out"""
+    _fields_ = [("best_obs", C.c_void_p), ("best_median", C.c_void_p), ("desc", C.c_void_p), ("normal", C.c_void_p), ("wvec", C.c_void_p), ("max_dist", C.c_void_p),
+                ("min_dist", C.c_void_p), ("status", C.c_void_p), ("kernel_ms", C.c_float)]
+
+
+assert C.sizeof(MrParams) == 12 and C.sizeof(MrInput) == 64 and C.sizeof(MrPointOut) == 64 and C.sizeof(MrLineOut) == 72
+
+
+def map_refresh_check(obs_start):
+    """the limits of one refresh call, refused here as the library refuses them (HvoError, HVO_ERR_UNSUPPORTED): needs no device"""
+    st = np.asarray(obs_start, np.int64).reshape(-1)
+    n = len(st) - 1
+    if n > MR_MAX_FEATURES:
+        raise HvoError(-4, "map refresh: %d features (limit %d)" % (n, MR_MAX_FEATURES))
+    if n > 0:
+        most = int(np.diff(st).max())
+        if most > MR_MAX_OBS:
+            raise HvoError(-4, "map refresh: %d observations of one feature (limit %d)" % (most, MR_MAX_OBS))
+        if int(st[-1]) > MR_MAX_OBS_TOTAL:
+            raise HvoError(-4, "map refresh: %d observations (limit %d)" % (int(st[-1]), MR_MAX_OBS_TOTAL))
+
+
+def _mr_args(line, obs_start, obs_desc, obs_Ow, ref_Ow, ref_level, kf_bad, skip, n_levels, scale_factor, what, want):
+    """(params, input, output struct, the output arrays, what must stay alive).  An array given as None stays NULL and is the library's to
+    refuse; want: the outputs to make room for (the others are passed as NULL)"""
+    st = np.ascontiguousarray(obs_start, np.int32).reshape(-1)
+    n = max(len(st) - 1, 0); m = max(n, 1); rdt = np.float64 if line else np.float32
+    byte = lambda v: None if v is None else np.ascontiguousarray(np.asarray(v).astype(bool), np.uint8).reshape(-1)
+    a = dict(obs_start=st, obs_desc=None if obs_desc is None else np.ascontiguousarray(obs_desc, np.uint8).reshape(-1, 32),
+             obs_Ow=None if obs_Ow is None else np.ascontiguousarray(obs_Ow, np.float32).reshape(-1, 3), kf_bad=byte(kf_bad),
+             ref_Ow=None if ref_Ow is None else np.ascontiguousarray(ref_Ow, np.float32).reshape(-1, 3),
+             ref_level=None if ref_level is None else np.ascontiguousarray(ref_level, np.int32).reshape(-1), skip=byte(skip))
+    I = MrInput(); I.n = n
+    for k, v in a.items(): setattr(I, k, v.ctypes.data if v is not None and v.size else None)
+    o = dict(best_obs=np.full(m, MR_UNTOUCHED, np.int32), best_median=np.full(m, MR_UNTOUCHED, np.int32), desc=np.full((m, 32), MR_UNTOUCHED, np.uint8),
+             normal=np.full((m, 3), MR_UNTOUCHED, rdt), max_dist=np.full(m, MR_UNTOUCHED, np.float32), min_dist=np.full(m, MR_UNTOUCHED, np.float32),
+             status=np.full(m, MR_UNTOUCHED, np.uint8))
+    if line: o["wvec"] = np.full((m, 3), MR_UNTOUCHED, np.float64)
+    O = MrLineOut() if line else MrPointOut()
+    for k, v in o.items(): setattr(O, k, v.ctypes.data if (want is None or k in want) else None)
+    O.kernel_ms = 0.0
+    P = MrParams(); P.n_levels = n_levels; P.scale_factor = scale_factor; P.what = what
+    return P, I, O, o, n, a
+
+
+def _mr_finish(O, o, n):
+    return dict({k: v[:n] for k, v in o.items()}, kernel_ms=O.kernel_ms)
+
+
+def _mr_call(ctx, name, line, pre, post, obs, n_levels, scale_factor, what, want, check):
+    map_refresh_check(obs["obs_start"])
+    P, I, O, o, n, keep = _mr_args(line, obs["obs_start"], obs.get("obs_desc"), obs.get("obs_Ow"), obs.get("ref_Ow"), obs.get("ref_level"), obs.get("kf_bad"),
+                                   obs.get("skip"), n_levels, scale_factor, what, want)
+    f = getattr(lib(), name); f.restype = C.c_int
+    f.argtypes = [C.c_void_p] * (len(pre) + len(post) + 4)
+    rc = f(ctx.h, *pre, C.addressof(P), C.addressof(I), *post, C.addressof(O))
+    del keep
+    if not check:
+        return rc, lib().hvo_last_error(ctx.h).decode(), _mr_finish(O, o, n)
+    ctx._chk(rc, name[4:])
+    return _mr_finish(O, o, n)
+
 
 def line_struct_params(**kw):
     """the reference's values (hvo_line_struct_default_params) with the given fields replaced (mode, row_rule, ...)"""
@@ -1456,6 +1544,13 @@ class _SlotMap:
         a += [np.ascontiguousarray(max_dist, np.float32).reshape(n), np.ascontiguousarray(min_dist, np.float32).reshape(n), np.ascontiguousarray(desc, np.uint8).reshape(n, 32)]
         a += [None if v is None else np.ascontiguousarray(np.asarray(v).astype(bool), np.uint8).reshape(n) for v in (observed, bad)]
         self._chk(self._f("set_many")(self.h, first, n, *[None if v is None or v.size == 0 else _p(v) for v in a]), "set_many")
+
+    def refresh(self, ctx, slots, obs, n_levels=8, scale_factor=1.2, what=MR_DESCRIPTOR | MR_GEOMETRY, want=None, check=True):
+        """Context.refresh_map_points / refresh_map_lines on slots of this map: the position is the slot's, and descriptor, normal, distance range
+        (and world vector) are rewritten in place; observed and bad are never touched.  Returns what the array form returns"""
+        sl = None if slots is None else np.ascontiguousarray(slots, np.int32).reshape(-1)
+        line = self._c == "line_map"
+        return _mr_call(ctx, "hvo_%s_refresh" % self._c, line, (self.h, sl.ctypes.data if sl is not None and sl.size else None), (), obs, n_levels, scale_factor, what, want, check)
 
     def set_bad(self, slot, bad=True):
         self._chk(self._f("set_bad")(self.h, slot, 1 if bad else 0), "set_bad")
@@ -2265,6 +2360,22 @@ class Context:
             return (rc, lib().hvo_last_error(self.h).decode()) + _nl_finish(n1, M, R, S, owner, mouts, outs, rc == HVO_OK)
         self._chk(rc, "create_new_map_lines")
         return _nl_finish(n1, M, R, S, owner, mouts, outs, True)
+
+    def refresh_map_points(self, pos, obs, n_levels=8, what=MR_DESCRIPTOR | MR_GEOMETRY, want=None, check=True):
+        """MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (src/MapPoint.cc:240-305, 328-369) for n points in one call.  pos (n, 3);
+        obs: dict(obs_start (n + 1, CSR), obs_desc (n_obs, 32), obs_Ow (n_obs, 3), kf_bad (n_obs) or None, ref_Ow (n, 3), ref_level (n), skip (n) or
+        None), the observations in mObservations' order.  The scale table is the context's.  Returns dict(best_obs, best_median, desc, normal,
+        max_dist, min_dist, status (MR_STATUS), kernel_ms); an entry the status says was not written holds MR_UNTOUCHED.  want: the outputs to
+        ask for (None: all).  check=False: (return code, message, the dict); the limits of map_refresh_check raise either way, before the library is called"""
+        p = None if pos is None else np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        return _mr_call(self, "hvo_refresh_map_points", False, (), (p.ctypes.data if p is not None and p.size else None,), obs, n_levels, 1.2, what, want, check)
+
+    def refresh_map_lines(self, pos, obs, n_levels=8, scale_factor=1.2, what=MR_DESCRIPTOR | MR_GEOMETRY, want=None, check=True):
+        """MapLine::ComputeDistinctiveDescriptors + UpdateAverageDir (src/MapLine.cpp:331-396, 404-455) for n lines in one call.  pos (n, 6) doubles;
+        obs as for refresh_map_points (LBD rows, mvKeyLines octaves); n_levels / scale_factor: the LINE pyramid.  Returns the same dict with
+        normal in float64 and wvec"""
+        p = None if pos is None else np.ascontiguousarray(pos, np.float64).reshape(-1, 6)
+        return _mr_call(self, "hvo_refresh_map_lines", True, (), (p.ctypes.data if p is not None and p.size else None,), obs, n_levels, scale_factor, what, want, check)
 
     def debug_match_arena(self, fill=None, min_bytes=0):
         """test door (not in include/hvo.h): grow the matching arena to min_bytes the way a call would, set its whole device capacity to the

@@ -49,11 +49,6 @@
 
 #define LL_BLOCK SM_BLOCK
 
-struct hvo_line_map : hvo_slot_map {
-    hvo_line_map() : hvo_slot_map("line map", "HVO_LINE_MAP_MAX_SLOTS", HVO_LINE_MAP_MAX_SLOTS, { { 8, 6 }, { 8, 3 }, { 8, 3 }, { 4, 1 }, { 4, 1 }, { 32, 1 }, { 1, 1, SM_BAD } }) {}
-    enum { POS, WVEC, NRM, MAXD, MIND, DESC };                   // pos, wvec, nrm: doubles; maxd, mind: floats; desc: 32 bytes packed; then the flags
-};
-
 extern "C" {
 
 hvo_line_map *hvo_line_map_create(int device, int slots)

@@ -40,10 +40,16 @@ struct hvo_slot_map {
     uint8_t *d_flags() const { return (uint8_t *)arr.back().d; }
 };
 
-// the resident point map (local_points.hip owns its calls; fuse.hip reads its arrays in place)
+// the resident point map (local_points.hip owns its calls; fuse.hip reads its arrays in place, map_refresh.inc rewrites them)
 struct hvo_point_map : hvo_slot_map {
     hvo_point_map() : hvo_slot_map("point map", "HVO_POINT_MAP_MAX_SLOTS", HVO_POINT_MAP_MAX_SLOTS, { { 4, 3 }, { 4, 3 }, { 4, 1 }, { 4, 1 }, { 32, 1 }, { 1, 1, SM_BAD } }) {}
     enum { POS, NRM, MAXD, MIND, DESC };                         // pos, nrm, maxd, mind: floats; desc: 32 bytes packed; then the flags
+};
+
+// the resident line map (local_lines.hip owns its calls; map_refresh.inc rewrites its arrays in place)
+struct hvo_line_map : hvo_slot_map {
+    hvo_line_map() : hvo_slot_map("line map", "HVO_LINE_MAP_MAX_SLOTS", HVO_LINE_MAP_MAX_SLOTS, { { 8, 6 }, { 8, 3 }, { 8, 3 }, { 4, 1 }, { 4, 1 }, { 32, 1 }, { 1, 1, SM_BAD } }) {}
+    enum { POS, WVEC, NRM, MAXD, MIND, DESC };                   // pos, wvec, nrm: doubles; maxd, mind: floats; desc: 32 bytes packed; then the flags
 };
 
 #define SM_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { m->last_error = std::string(#call) + ": " + hipGetErrorString(e_); return HVO_ERR_HIP; } } while (0)

@@ -1508,6 +1508,74 @@ int hvo_stream_create_new_map_lines(hvo_stream *s, int64_t cur, const hvo_camera
                                     const uint8_t *has_map_line, int n_kf, const hvo_nl_keyframe *neighbours, hvo_nl_match *matches, int n_pairs_cap,
                                     hvo_nl_result *results, hvo_nl_summary *summary);
 
+/* ---- MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (reference src/MapPoint.cc:240-305, 328-369) and
+ * MapLine::ComputeDistinctiveDescriptors + UpdateAverageDir (src/MapLine.cpp:331-396, 404-455); csrc/map_refresh.inc ----
+ * One call refreshes n map points (or lines) from their observations: the descriptor with the least median Hamming distance to the other
+ * observers' descriptors, the mean viewing direction, the distance range and, for a line, the world vector.  No feature reads another's
+ * result.  The observations are a ragged list in the order mObservations iterates (std::map<KeyFrame *, size_t>: the caller's pointer
+ * order): the order decides which of equal medians wins (the first) and the rounding of the sums.  The caller resolves
+ * `observations[pRefKF]` itself; see INTEGRATION.md for operator[] on the copied map when pRefKF is not an observer.
+ * Readings: csrc/map_refresh.inc and DESIGN.md section 7; tests/map_refresh_ref.py is the definition. */
+#define HVO_MR_DESCRIPTOR 1    /* hvo_mr_params.what: ComputeDistinctiveDescriptors */
+#define HVO_MR_GEOMETRY   2    /* UpdateNormalAndDepth / UpdateAverageDir (the optimiser calls only this half) */
+#define HVO_MR_MAX_OBS        256        /* observations per feature */
+#define HVO_MR_MAX_FEATURES   65536      /* features per call */
+#define HVO_MR_MAX_OBS_TOTAL  1048576    /* observations per call */
+/* status, one per feature: the first that applies */
+#define HVO_MR_REFRESHED  0
+#define HVO_MR_SKIPPED    1    /* skip (mbBad), or a bad slot in the slot form: nothing is written */
+#define HVO_MR_NO_OBS     2    /* observations.empty(): nothing is written */
+#define HVO_MR_DESC_KEPT  3    /* DESCRIPTOR asked for and every observer is bad: the descriptor is kept, the geometry is written */
+#define HVO_MR_BAD_LEVEL  4    /* GEOMETRY asked for and ref_level outside [0, n_levels): the reference would read its table out of bounds.
+                                * max_dist and min_dist are left as they were (also under status 3); descriptor, normal and wvec are written */
+typedef struct {
+    int32_t n_levels;          /* 1 .. 16: mnScaleLevels (points) / mnScaleLevelsLine (lines) */
+    float scale_factor;        /* lines: sf[0] = 1, sf[l] = sf[l - 1] * scale_factor in float (as hvo_nl_params).  Points read the context's
+                                * ORB pyramid table (n_levels may not exceed the context's levels) and ignore this field */
+    int32_t what;              /* HVO_MR_DESCRIPTOR | HVO_MR_GEOMETRY, not 0 */
+} hvo_mr_params;
+typedef struct {               /* what goes up.  n_obs = obs_start[n] */
+    int32_t n;
+    const int32_t *obs_start;  /* n + 1: CSR over the observations, obs_start[0] = 0, non-decreasing */
+    const uint8_t *obs_desc;   /* n_obs x 32: the observing key frame's descriptor row (ORB / LBD) */
+    const float   *obs_Ow;     /* n_obs x 3: its GetCameraCenter() */
+    const uint8_t *kf_bad;     /* n_obs, or NULL for none: pKF->isBad().  A bad observer stays out of the descriptor list and still counts in the normal */
+    const float   *ref_Ow;     /* n x 3: pRefKF->GetCameraCenter() */
+    const int32_t *ref_level;  /* n: pRefKF->mvKeysUn[observations[pRefKF]].octave (mvKeyLines for a line) */
+    const uint8_t *skip;       /* n, or NULL for none: mbBad */
+} hvo_mr_input;
+typedef struct {               /* every pointer may be NULL.  An entry that the status says was not written is left as the caller had it */
+    int32_t *best_obs;         /* n: the winner's index within the feature's own observation list (bad observers counted), -1 when no descriptor was written */
+    int32_t *best_median;      /* n: its median, -1 likewise */
+    uint8_t *desc;             /* n x 32 */
+    float   *normal;           /* n x 3: mNormalVector */
+    float   *max_dist, *min_dist;      /* n: RAW mfMaxDistance / mfMinDistance */
+    uint8_t *status;           /* n: HVO_MR_* */
+    float   kernel_ms;         /* device time of the kernel */
+} hvo_mr_point_out;
+typedef struct {
+    int32_t *best_obs, *best_median;
+    uint8_t *desc;
+    double  *normal;           /* n x 3 */
+    double  *wvec;             /* n x 3: mWorldVector */
+    float   *max_dist, *min_dist;
+    uint8_t *status;
+    float   kernel_ms;
+} hvo_mr_line_out;
+/* On host arrays: pos is n x 3 floats (mWorldPos) / n x 6 doubles (start, end).  Limits: HVO_MR_MAX_*; beyond them the call is refused
+ * whole with HVO_ERR_UNSUPPORTED.  A missing array, obs_start[0] != 0, a decreasing obs_start, what == 0 or with unknown bits, or n_levels
+ * outside 1 .. 16 is HVO_ERR_INVALID_ARG.  On a refusal nothing is written and hvo_last_error says why.  n == 0 is HVO_OK.  One
+ * synchronisation per call. */
+int hvo_refresh_map_points(hvo_ctx *ctx, const hvo_mr_params *params, const hvo_mr_input *in, const float *pos, hvo_mr_point_out *out);
+int hvo_refresh_map_lines(hvo_ctx *ctx, const hvo_mr_params *params, const hvo_mr_input *in, const double *pos, hvo_mr_line_out *out);
+/* On n slots of a resident map: the position is the slot's, and descriptor, normal, distance range (and world vector) are rewritten in
+ * place, in the map's device arrays and in its host mirror (hvo_*_map_slot reads back exactly what `out` reports); observed and bad are
+ * never touched.  Only the observation arrays and the per-feature side go up.  A bad slot counts as skipped.  A slot outside the map or
+ * listed twice is HVO_ERR_INVALID_ARG (whole); the map must live on the context's device.  A refusal's text is in hvo_last_error and in
+ * the map's last error.  Bit for bit the host-array form on the slots' positions. */
+int hvo_point_map_refresh(hvo_ctx *ctx, hvo_point_map *m, const int32_t *slots, const hvo_mr_params *params, const hvo_mr_input *in, hvo_mr_point_out *out);
+int hvo_line_map_refresh(hvo_ctx *ctx, hvo_line_map *m, const int32_t *slots, const hvo_mr_params *params, const hvo_mr_input *in, hvo_mr_line_out *out);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer. Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

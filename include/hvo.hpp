@@ -879,6 +879,16 @@ public:
     void setBad(int slot, bool bad = true) { check(hvo_line_map_set_bad(m_, slot, bad ? 1 : 0), "hvo_line_map_set_bad"); }
     void setObserved(int slot, bool observed = true) { check(hvo_line_map_set_observed(m_, slot, observed ? 1 : 0), "hvo_line_map_set_observed"); }
     int size() const { int n = 0; check(hvo_line_map_counts(m_, &n, nullptr, nullptr), "hvo_line_map_counts"); return n; }
+    // MapLine::ComputeDistinctiveDescriptors + UpdateAverageDir (src/MapLine.cpp:331-396, 404-455) on in.n slots: descriptor, normal, world
+    // vector and distance range are rewritten in place from the observations; `what`: HVO_MR_DESCRIPTOR | HVO_MR_GEOMETRY (the optimiser
+    // passes HVO_MR_GEOMETRY alone).  nLevels / scale: the LINE pyramid.  out's pointers may be null; returns the kernel's device ms
+    float refresh(hvo_ctx *ctx, const int32_t *slots, const hvo_mr_input &in, hvo_mr_line_out &out, int what = HVO_MR_DESCRIPTOR | HVO_MR_GEOMETRY, int nLevels = 8,
+                  float scale = 1.2f)
+    {
+        const hvo_mr_params p = { nLevels, scale, what };
+        check(hvo_line_map_refresh(ctx, m_, slots, &p, &in, &out), "hvo_line_map_refresh");
+        return out.kernel_ms;
+    }
 };
 
 // Tracking::SearchLocalLines (src/Tracking.cc:3279-3392) together with Manhattan::computeStructConstInMap (src/Manhattan.cpp:163-224) over a
@@ -931,7 +941,31 @@ public:
     void setBad(int slot, bool bad = true) { check(hvo_point_map_set_bad(m_, slot, bad ? 1 : 0), "hvo_point_map_set_bad"); }
     void setObserved(int slot, bool observed = true) { check(hvo_point_map_set_observed(m_, slot, observed ? 1 : 0), "hvo_point_map_set_observed"); }
     int size() const { int n = 0; check(hvo_point_map_counts(m_, &n, nullptr, nullptr), "hvo_point_map_counts"); return n; }
+    // MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (src/MapPoint.cc:240-305, 328-369) on in.n slots: descriptor, normal and
+    // distance range are rewritten in place from the observations; the scale table is the context's.  Returns the kernel's device ms
+    float refresh(hvo_ctx *ctx, const int32_t *slots, const hvo_mr_input &in, hvo_mr_point_out &out, int what = HVO_MR_DESCRIPTOR | HVO_MR_GEOMETRY, int nLevels = 8)
+    {
+        const hvo_mr_params p = { nLevels, 1.2f, what };
+        check(hvo_point_map_refresh(ctx, m_, slots, &p, &in, &out), "hvo_point_map_refresh");
+        return out.kernel_ms;
+    }
 };
+
+// the same two sweeps on host arrays: pos is in.n x 3 floats (mWorldPos) / in.n x 6 doubles (start and end point).  An entry of `out` that a
+// feature's status (HVO_MR_*) says was not written keeps what the caller put there
+inline float refreshMapPoints(hvo_ctx *ctx, const hvo_mr_input &in, const float *pos, hvo_mr_point_out &out, int what = HVO_MR_DESCRIPTOR | HVO_MR_GEOMETRY, int nLevels = 8)
+{
+    const hvo_mr_params p = { nLevels, 1.2f, what };
+    check(hvo_refresh_map_points(ctx, &p, &in, pos, &out), "hvo_refresh_map_points");
+    return out.kernel_ms;
+}
+inline float refreshMapLines(hvo_ctx *ctx, const hvo_mr_input &in, const double *pos, hvo_mr_line_out &out, int what = HVO_MR_DESCRIPTOR | HVO_MR_GEOMETRY, int nLevels = 8,
+                             float scale = 1.2f)
+{
+    const hvo_mr_params p = { nLevels, scale, what };
+    check(hvo_refresh_map_lines(ctx, &p, &in, pos, &out), "hvo_refresh_map_lines");
+    return out.kernel_ms;
+}
 
 // Tracking::SearchLocalPoints (src/Tracking.cc:3227-3277) over a resident PointMap: io.held carries mvpMapPoints as slots (or -1,
 // HVO_HELD_FOREIGN_OBSERVED, HVO_HELD_FOREIGN_UNOBSERVED) in and out, io.in_view_slot returns the points with mbTrackInView; the return value

@@ -1,0 +1,36 @@
+"""The two kernels of csrc/map_refresh.inc keep everything in registers and LDS: no scratch, no spills.  Each lane holds its row's descriptor
+(eight words) across the nine bisection steps, and the line kernel its double sums beside them; this test is what notices if that stops
+fitting.  The kernels share match.hip's translation unit, so the report is filtered by name.  The figures are the compiler's own remarks
+(tools/kernel_resources.py); no assembly is inspected and no GPU is needed."""
+import importlib.util
+import os
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "a-low-texture-robust-hybrid-feature-based-visual-odometry_amd", "csrc")
+KERNELS = ("k_mr_points", "k_mr_lines")
+LDS_LIMIT = 160 * 1024 // 4                                     # a quarter of a compute unit's LDS: four work groups fit beside each other
+
+
+@pytest.fixture(scope="module")
+def res():
+    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
+    kr = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kr)
+    if not kr.hipcc():
+        pytest.skip("hipcc not found")
+    return {k: v for k, v in kr.resources(os.path.join(CSRC, "match.hip")).items() if k.startswith("k_mr_")}
+
+
+def test_every_kernel_is_reported(res):
+    assert sorted(res) == sorted(KERNELS), sorted(res)
+
+
+@pytest.mark.parametrize("name", KERNELS)
+def test_no_scratch_and_no_spills(res, name):
+    r = res[name]
+    print("%-12s VGPRs %3d allocated %3d SGPRs %3d spills s/v %d/%d scratch %d LDS %d" % (
+        name, r["vgprs"], r["alloc"], r["sgprs"], r["sgpr_spills"], r["vgpr_spills"], r["scratch"], r["lds"]))
+    assert r["scratch"] == 0 and r["sgpr_spills"] == 0 and r["vgpr_spills"] == 0, r
+    assert 256 * 32 <= r["lds"] <= LDS_LIMIT, r                  # the descriptors of 256 observers are in LDS
