@@ -94,6 +94,7 @@ EXPORTS = [
     "hvo_pnp_default_params", "hvo_pnp_ransac", "hvo_stream_pnp_ransac", "hvo_pnp_last_kernel_ms", "hvo_stream_pnp_last_kernel_ms",
     "hvo_search_by_projection_keyframe", "hvo_stream_search_by_projection_keyframe",
     "hvo_fuse_points", "hvo_fuse_points_slots", "hvo_stream_fuse_points",
+    "hvo_fuse_lines", "hvo_fuse_lines_slots", "hvo_stream_fuse_lines",
     "hvo_create_new_map_points", "hvo_stream_create_new_map_points", "hvo_create_new_map_lines", "hvo_stream_create_new_map_lines",
     "hvo_refresh_map_points", "hvo_refresh_map_lines", "hvo_point_map_refresh", "hvo_line_map_refresh",
     "hvo_update_map_planes", "hvo_stream_update_map_planes", "hvo_plane_map_get_points", "hvo_plane_update_transform",
@@ -810,6 +811,108 @@ def _fuse_finish(R, keep, ok):
     return out
 
 
+LF_MAX_LINES, LF_MAX_ENTRIES, LF_MAX_PAIRS = 2048, 65536, 1 << 24
+LF_GATES = ("searched", "skip", "behind", "out of image", "dist < 0.8 min", "dist > 1.2 max", "view angle", "level")      # hvo_lf_result.gate
+LF_LEVEL_RULES = ("clamped", "as written")                         # HVO_LF_LEVEL_*
+
+
+class LfKeyframe(C.Structure):
+    """hvo_lf_keyframe: a key frame's key lines, the rows its candidates are compared with, its pose, bounds, camera and skip bytes"""
+    _fields_ = [("n", C.c_int32), ("kl", C.c_void_p), ("desc_rows", C.c_void_p), ("n_desc_rows", C.c_int32), ("Tcw", C.c_float * 12), ("bounds", C.c_float * 4),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("skip", C.c_void_p)]
+
+
+class LfMap(C.Structure):
+    """hvo_lf_map: a map side on host arrays"""
+    _fields_ = [("n", C.c_int32), ("pos", C.c_void_p), ("normal", C.c_void_p), ("max_distance", C.c_void_p), ("min_distance", C.c_void_p), ("desc", C.c_void_p)]
+
+
+class LfParams(C.Structure):
+    """hvo_lf_params"""
+    _fields_ = [("th", C.c_float), ("th_low", C.c_int32), ("log_scale_factor", C.c_float), ("n_levels", C.c_int32), ("scale_factor", C.c_float),
+                ("level_rule", C.c_int32), ("map_per_keyframe", C.c_int32)]
+
+
+class LfResult(C.Structure):
+    """hvo_lf_result"""
+    _fields_ = [("best_idx", C.c_void_p), ("best_dist", C.c_void_p), ("gate", C.c_void_p), ("level", C.c_void_p), ("proj", C.c_void_p),
+                ("fused_entry", C.c_void_p), ("fused_idx", C.c_void_p), ("behind_entry", C.c_void_p), ("n_fused", C.c_int32), ("n_behind", C.c_int32),
+                ("n_searched", C.c_int32), ("status", C.c_int32), ("kernel_ms", C.c_float * 3)]
+
+
+assert C.sizeof(LfKeyframe) == 120 and C.sizeof(LfMap) == 48 and C.sizeof(LfParams) == 28 and C.sizeof(LfResult) == 96
+
+
+def _lf_params(th, th_low, log_scale_factor, n_levels, scale_factor, level_rule, per_keyframe):
+    P = LfParams(); P.th = th; P.th_low = th_low; P.log_scale_factor = log_scale_factor; P.n_levels = n_levels; P.scale_factor = scale_factor
+    P.level_rule = LF_LEVEL_RULES.index(level_rule) if isinstance(level_rule, str) else int(level_rule)
+    P.map_per_keyframe = 1 if per_keyframe else 0
+    return P
+
+
+def _lf_maps(maps):
+    """dicts of pos (n x 6 doubles), normal (n x 3 doubles), max_distance, min_distance (n, raw), desc (n x 32)"""
+    M = (LfMap * len(maps))(); keep = []
+    for s, mp in enumerate(maps):
+        pos = np.ascontiguousarray(mp["pos"], np.float64).reshape(-1, 6); n = len(pos)
+        a = dict(pos=pos, normal=np.ascontiguousarray(mp["normal"], np.float64).reshape(-1, 3), max_distance=np.ascontiguousarray(mp["max_distance"], np.float32).reshape(-1),
+                 min_distance=np.ascontiguousarray(mp["min_distance"], np.float32).reshape(-1), desc=np.ascontiguousarray(mp["desc"], np.uint8).reshape(-1, 32))
+        if any(len(v) != n for v in a.values()):
+            raise ValueError("fuse_lines: a map side's arrays differ in length")
+        M[s].n = n
+        for k, v in a.items(): setattr(M[s], k, v.ctypes.data if n else None)
+        keep.append(a)
+    return M, keep, [M[s].n for s in range(len(maps))]
+
+
+def _lf_keyframes(kfs, n_entries, resident=False):
+    """kfs: dicts of kl, desc_rows, Tcw, cam (fx, fy, cx, cy), bounds, skip (or None); n_entries[j]: the entries of key frame j's map side"""
+    K = (LfKeyframe * len(kfs))(); keep = []
+    for j, kf in enumerate(kfs):
+        a = {}
+        if not resident:
+            # (an array given as None with a count "n" / "n_desc_rows" beside it reaches the library as a missing array: its refusal is tested)
+            a["kl"] = np.ascontiguousarray(kf["kl"] if kf.get("kl") is not None else np.zeros(0, KEYLINE_DT), KEYLINE_DT)
+            a["desc_rows"] = np.ascontiguousarray(kf["desc_rows"] if kf.get("desc_rows") is not None else np.zeros((0, 32), np.uint8), np.uint8).reshape(-1, 32)
+            K[j].n = len(a["kl"]) if kf.get("kl") is not None else int(kf.get("n", 0))
+            K[j].n_desc_rows = len(a["desc_rows"]) if kf.get("desc_rows") is not None else int(kf.get("n_desc_rows", 0))
+            for k in ("kl", "desc_rows"): setattr(K[j], k, a[k].ctypes.data if len(a[k]) else None)
+            b = [float(v) for v in np.asarray(kf["bounds"]).reshape(4)]
+            for k in range(4): K[j].bounds[k] = b[k]
+            K[j].fx, K[j].fy, K[j].cx, K[j].cy = (float(v) for v in kf["cam"][:4])
+        a["skip"] = None if kf.get("skip") is None else np.ascontiguousarray(np.asarray(kf["skip"]).astype(bool), np.uint8).reshape(n_entries[j])
+        K[j].skip = a["skip"].ctypes.data if a["skip"] is not None and a["skip"].size else None
+        T = np.asarray(kf["Tcw"], np.float32).reshape(12)
+        for k in range(12): K[j].Tcw[k] = T[k]
+        keep.append(a)
+    return K, keep
+
+
+def _lf_results(n_entries):
+    R = (LfResult * len(n_entries))(); keep = []
+    for j, n in enumerate(n_entries):
+        m = max(n, 1)
+        o = dict(best_idx=np.full(m, FUSE_UNTOUCHED, np.int32), best_dist=np.full(m, FUSE_UNTOUCHED, np.int32), gate=np.full(m, FUSE_UNTOUCHED, np.int8),
+                 level=np.full(m, FUSE_UNTOUCHED, np.int32), proj=np.full((m, 4), FUSE_UNTOUCHED, np.float32),
+                 fused_entry=np.full(m, FUSE_UNTOUCHED, np.int32), fused_idx=np.full(m, FUSE_UNTOUCHED, np.int32), behind_entry=np.full(m, FUSE_UNTOUCHED, np.int32))
+        for k in o: setattr(R[j], k, o[k].ctypes.data)
+        R[j].n_fused = R[j].n_behind = R[j].n_searched = R[j].status = FUSE_UNTOUCHED
+        keep.append((o, n))
+    return R, keep
+
+
+def _lf_finish(R, keep, ok):
+    """one dict per key frame; after a refusal (ok False) every array is returned whole, as the call left it"""
+    out = []
+    for j, (o, n) in enumerate(keep):
+        d = dict(n_fused=R[j].n_fused, n_behind=R[j].n_behind, n_searched=R[j].n_searched, status=R[j].status, kernel_ms=tuple(R[j].kernel_ms))
+        for k in ("best_idx", "best_dist", "gate", "level", "proj"): d[k] = o[k][:n] if ok else o[k]
+        nf = max(0, min(R[j].n_fused, n)) if ok else len(o["fused_entry"]); nb = max(0, min(R[j].n_behind, n)) if ok else len(o["behind_entry"])
+        d["fused_entry"] = o["fused_entry"][:nf]; d["fused_idx"] = o["fused_idx"][:nf]; d["behind_entry"] = o["behind_entry"][:nb]
+        out.append(d)
+    return out
+
+
 NP_MAX_FEATURES, NP_MAX_NEIGHBOURS = 4096, 64
 NP_OUTCOMES = ("created", "occupied", "no match", "low parallax", "w == 0", "no depth", "behind 1", "behind 2", "reproj 1", "reproj 2", "zero dist", "scale")
 NP_UNTOUCHED = -7           # what the outputs hold before the call: a refusal leaves them so
@@ -1341,6 +1444,10 @@ def lib():
                                                 C.POINTER(NpResult), C.POINTER(NpSummary)]
         L.hvo_stream_create_new_map_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(PoseCamera), C.POINTER(NpParams), C.c_void_p, C.c_void_p, C.c_int,
                                                        C.POINTER(NpKeyframe), C.POINTER(NpResult), C.POINTER(NpSummary)]
+        L.hvo_fuse_lines.argtypes = [C.c_void_p, C.POINTER(LfParams), C.POINTER(LfMap), C.c_int, C.POINTER(LfKeyframe), C.POINTER(LfResult)]
+        L.hvo_fuse_lines_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(LfParams), C.c_int, C.POINTER(LfKeyframe), C.POINTER(LfResult)]
+        L.hvo_stream_fuse_lines.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(LfParams), C.c_void_p, C.c_void_p, C.POINTER(LfMap), C.c_void_p,
+                                            C.c_int, C.c_void_p, C.POINTER(LfResult)]
         L.hvo_stream_fuse_points.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.c_void_p, C.c_void_p, C.POINTER(FuseMap), C.c_void_p,
                                              C.c_int, C.c_void_p, C.POINTER(FuseResult)]
         L.hvo_stream_pnp_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
@@ -2325,6 +2432,43 @@ class Context:
         self._chk(rc, "fuse_points_slots")
         return _fuse_finish(R, rk, True)
 
+    def fuse_lines(self, kfs, maps, th=3.0, th_low=50, log_scale_factor=float(np.log(np.float32(1.2))), n_levels=1, scale_factor=1.2, level_rule="clamped", check=True):
+        """LSDmatcher::Fuse(pKF, vpMapLines, th) (src/LSDmatcher.cpp:1297-1434) for every key frame of kfs (dicts: kl, desc_rows, Tcw, cam
+        (fx, fy, cx, cy), bounds, skip or None) in one call.  desc_rows are the rows the candidates are compared with: mLineDescriptors, or
+        mDescriptors for the text as written.  maps: ONE dict (pos n x 6, normal n x 3, max_distance, min_distance, desc), shared by all key
+        frames, or a list with one dict per key frame.  n_levels / scale_factor: the line extractor's octaves (mvScaleFactorsLine).  level_rule:
+        "clamped" or "as written".  Returns one dict per key frame: best_idx,
+        best_dist, gate (LF_GATES), level, proj (n x 4), fused_entry, fused_idx, behind_entry, n_fused, n_behind, n_searched, status,
+        kernel_ms.  check=False: (return code, message, the dicts); a refused call leaves every output at FUSE_UNTOUCHED."""
+        per_kf = not isinstance(maps, dict)
+        if per_kf and len(maps) != len(kfs):
+            raise ValueError("fuse_lines: one map side per key frame, or one dict for all")
+        M, mk, ns = _lf_maps(list(maps) if per_kf else [maps])
+        ne = ns if per_kf else ns * len(kfs)
+        K, kk = _lf_keyframes(kfs, ne)
+        R, rk = _lf_results(ne)
+        P = _lf_params(th, th_low, log_scale_factor, n_levels, scale_factor, level_rule, per_kf)
+        rc = lib().hvo_fuse_lines(self.h, C.byref(P), M, len(kfs), K, R)
+        if not check:
+            return rc, lib().hvo_last_error(self.h).decode(), _lf_finish(R, rk, rc == HVO_OK)
+        self._chk(rc, "fuse_lines")
+        return _lf_finish(R, rk, True)
+
+    def fuse_lines_slots(self, line_map, slots, kfs, th=3.0, th_low=50, log_scale_factor=float(np.log(np.float32(1.2))), n_levels=1, scale_factor=1.2,
+                         level_rule="clamped", check=True):
+        """fuse_lines with the map side given as slots of a resident LineMap, shared by all key frames: the map's device arrays are read in
+        place, only the slot list and the skip bytes go up.  A bad slot counts as skipped; a slot outside the map refuses the whole call."""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1); n = len(sl)
+        ne = [n] * len(kfs)
+        K, kk = _lf_keyframes(kfs, ne)
+        R, rk = _lf_results(ne)
+        P = _lf_params(th, th_low, log_scale_factor, n_levels, scale_factor, level_rule, False)
+        rc = lib().hvo_fuse_lines_slots(self.h, line_map.h, n, sl.ctypes.data if n else None, C.byref(P), len(kfs), K, R)
+        if not check:
+            return rc, lib().hvo_last_error(self.h).decode(), _lf_finish(R, rk, rc == HVO_OK)
+        self._chk(rc, "fuse_lines_slots")
+        return _lf_finish(R, rk, True)
+
     def create_new_map_points(self, cam, cur, kfs, th_low=50, n_levels=8, scale_factor=1.2, check=True):
         """LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:335-580): the epipolar search and the triangulation of the current key frame
         `cur` against every neighbour of kfs in one call.  cur and each neighbour: dict(kp_un, kp or None, uright, depth (both or None), desc,
@@ -2915,6 +3059,26 @@ class Stream:
             return rc, lib().hvo_stream_last_error(self.h).decode(), _fuse_finish(R, rk, rc == HVO_OK)[0]
         self._chk(rc, "stream_fuse_points")
         return _fuse_finish(R, rk, True)[0]
+
+    def fuse_lines(self, cur, cam, Tcw, maps=None, line_map=None, slots=None, skip=None, th=3.0, th_low=50, log_scale_factor=float(np.log(np.float32(1.2))),
+                   n_levels=1, scale_factor=1.2, level_rule="clamped", check=True):
+        """LSDmatcher::Fuse(mpCurrentKeyFrame, vpFuseCandidates) with the resident frame `cur` as the key frame under Tcw and cam (needs an LSD
+        stage): its key lines and LBD descriptors stay on the device, the bounds are the frame grid's.  The map side is `maps` (one dict of
+        host arrays) or `slots` of `line_map`.  Returns one dict as Context.fuse_lines does per key frame."""
+        if maps is not None:
+            M, mk, ns = _lf_maps([maps]); n = ns[0]; sl = None
+        else:
+            M = None; sl = np.ascontiguousarray(slots, np.int32).reshape(-1); n = len(sl)
+        K, kk = _lf_keyframes([dict(Tcw=Tcw, skip=skip)], [n], resident=True)
+        R, rk = _lf_results([n])
+        P = _lf_params(th, th_low, log_scale_factor, n_levels, scale_factor, level_rule, False)
+        cm = _pose_cam(cam)
+        rc = lib().hvo_stream_fuse_lines(self.h, cur, C.byref(cm), C.byref(P), C.addressof(K[0].Tcw), K[0].skip, M, line_map.h if line_map is not None else None,
+                                         n, sl.ctypes.data if sl is not None and n else None, R)
+        if not check:
+            return rc, lib().hvo_stream_last_error(self.h).decode(), _lf_finish(R, rk, rc == HVO_OK)[0]
+        self._chk(rc, "stream_fuse_lines")
+        return _lf_finish(R, rk, True)[0]
 
     def pnp_last_kernel_ms(self, cur):
         ms = np.zeros(2, np.float32)

@@ -24,6 +24,7 @@ const FrameNeed need_fuse          = { "fuse", HVO_STAGE_ORB, false, 0, "", true
 const FrameNeed need_guided_points = { "guided search", HVO_STAGE_ORB, false, 0, "", true, false, FV_N_KP, FV_EV_ORB, "HVO_STAGE_ORB", "HVO_STAGE_ORB" };
 const FrameNeed need_line_match    = { "line matching", 0, true, 0, "", false, false, FV_N_KL, FV_EV_LSD, k_lines, k_lines };
 const FrameNeed need_new_lines     = { "create new map lines", 0, true, 0, "", false, false, FV_N_KL, FV_EV_LSD, k_lines, k_lines };
+const FrameNeed need_fuse_lines    = { "fuse lines", 0, true, 0, "", false, false, FV_N_KL, FV_EV_LSD, k_lines, k_lines };
 const FrameNeed need_guided_lines  = { "guided line search", HVO_STAGE_GRIDS, true, 0, "", false, false, FV_N_KL | FV_N_LN, FV_EV_LSD, "an LSD stage and HVO_STAGE_GRIDS", "an LSD stage and HVO_STAGE_GRIDS" };
 const FrameNeed need_map_lines     = { "local-map line search", HVO_STAGE_GRIDS | HVO_STAGE_LINES3D, true, FV_DEPTH_STREAM, "no 3-D lines", false, false, FV_N_KL | FV_N_LN, FV_EV_LSD,
                                        "HVO_STAGE_GRIDS and HVO_STAGE_LINES3D", "HVO_STAGE_GRIDS and HVO_STAGE_LINES3D" };

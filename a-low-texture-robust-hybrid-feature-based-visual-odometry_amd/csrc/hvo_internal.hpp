@@ -164,7 +164,7 @@ struct hvo_ctx {
     hipEvent_t kfs_ev[3] = { nullptr, nullptr, nullptr };   // kf_search.hip: events around the last call's prologue and its searches
     hipEvent_t fuse_ev[4] = { nullptr, nullptr, nullptr, nullptr };   // fuse.hip: events around the last call's grid, projection and search kernels
     hipEvent_t np_ev[4] = { nullptr, nullptr, nullptr, nullptr };     // new_points.hip: events around the last call's search, triangulation and resolve kernels
-    hipEvent_t nl_ev[4] = { nullptr, nullptr, nullptr, nullptr };     // line_triang.inc: the same for CreateNewMapLinesConstraint; map_refresh.inc brackets its kernel with the first two
+    hipEvent_t nl_ev[4] = { nullptr, nullptr, nullptr, nullptr };     // line_triang.inc: the same for CreateNewMapLinesConstraint; map_refresh.inc brackets its kernel with the first two; line_fuse.inc uses all four
     BowState bow_batch, bow_call;         // bow.hip: the resident batch's bag of words (cleared by hvo_batch_run), the host-array form's block
     // opaque per-subsystem state (peac.hip / lsd.hip own these)
     void *peac = nullptr;

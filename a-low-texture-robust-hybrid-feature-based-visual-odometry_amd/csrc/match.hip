@@ -738,3 +738,4 @@ extern "C" int hvo_debug_match_rate(hvo_ctx *ctx, const uint8_t *q, int nq, cons
 #include "line_map.inc"
 #include "line_triang.inc"
 #include "map_refresh.inc"
+#include "line_fuse.inc"

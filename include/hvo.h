@@ -1330,6 +1330,97 @@ int hvo_fuse_points_slots(hvo_ctx *ctx, hvo_point_map *m, int n, const int32_t *
 int hvo_stream_fuse_points(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_fuse_params *params, const float Tcw[12], const uint8_t *skip,
                            const hvo_fuse_map *map_side, hvo_point_map *m, int n, const int32_t *slots, hvo_fuse_result *result);
 
+/* ---- LSDmatcher::Fuse(KeyFrame *, const vector<MapLine *> &, float th) (src/LSDmatcher.cpp:1297-1434; csrc/line_fuse.inc) ----
+ * The line matcher of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:1651, :1677): every map line of a list that is not skipped is
+ * projected into the key frame by both end points, gated (depth sign of both ends, image bounds of both ends, distance range, viewing
+ * angle), given a predicted level and compared with the key lines KeyFrame::GetLinesInArea (src/KeyFrame.cc:668-702) returns: it uses no
+ * grid and tests EVERY key line of the key frame (squared mid-point distance <= r * r, |cos| of the two directions >= 0.998f), so the work
+ * is key frames x entries x lines.  Among those in the levels [level - 1, level] the lowest Hamming distance wins, the lowest line index
+ * among equals; it is accepted at best_dist <= th_low.  There is no occupancy, so all (key frame, entry) pairs are searched in one launch.
+ * The pointer part stays with the caller (hvo::LSDmatcher::walkFused in hvo.hpp): Replace against AddObservation + AddMapLine.
+ *
+ * Three readings are decided here (tests/line_fuse_ref.py):
+ *  1. Which descriptors.  The text compares the map line's LBD descriptor with pKF->mDescriptors.row(idx): ORB rows under a line index
+ *     (mLineDescriptors is fetched and never used).  desc_rows / n_desc_rows are "the rows the candidates are compared with":
+ *     mLineDescriptors (the intended reading) or mDescriptors (as written).  A candidate idx >= n_desc_rows is not compared.  No flag.
+ *  2. The predicted level.  MapLine::PredictScale does not clamp and indexes mvScaleFactorsLine.  HVO_LF_LEVEL_CLAMPED (the default) clamps to
+ *     [0, n_levels - 1] before the radius and the band; HVO_LF_LEVEL_AS_WRITTEN keeps the level, and an entry whose level is outside
+ *     [0, n_levels) gets HVO_LF_GATE_LEVEL and is not searched.  log_scale_factor is the key frame's mfLogScaleFactorLine (the reference
+ *     sets it to the log of the ORB factor); the table is sf[0] = 1, sf[l] = sf[l - 1] * scale_factor in float (the line extractor's).
+ *  3. `return false` on a negative depth (:1340-1341) stops the reference's call at the first entry that lies behind and is still not
+ *     skipped when the walk reaches it.  The device applies no stop: every entry is evaluated, such an entry reports HVO_LF_GATE_BEHIND,
+ *     and behind_entry / n_behind list them in ascending order, for the walk to apply the stop or not.
+ * Arithmetic a caller can observe: Mat_<float> << double rounds to float; Rcw P + tcw as for the line map; invz = 1.0f / z is one float
+ * division and u = fx * X * invz + cx goes left to right; IsInImage(u1, v1) is tested before u2, v2 exist and a NaN fails it;
+ * 0.5 * (SP + EP) is the float of SP * 0.5 + EP * 0.5 formed in double; cv::norm and Mat::dot as in hvo_fuse_points; the angle gate
+ * compares with the double 0.5 * dist; inside GetLinesInArea the mid-point distance is formed in double and rounded to float, compared
+ * with the float r * r by `>`; both directions are normalised in float; `CosSita < 0.998f` lets a NaN (a line of zero length on either
+ * side) PASS.  An octave of -1 lies in the band at level 0.  No arithmetic is contracted. */
+typedef struct {               /* the key-frame side on host arrays */
+    int32_t n;                 /* mvKeyLines.size() */
+    const hvo_keyline *kl;     /* pt_x, pt_y, sx, sy, ex, ey, octave are read */
+    const uint8_t *desc_rows;  /* n_desc_rows x 32: the rows the candidates are compared with (reading 1) */
+    int32_t n_desc_rows;
+    float Tcw[12];             /* rows 0..2 of the key frame's pose, row-major 3 x 4 */
+    float bounds[4];           /* mnMinX, mnMaxX, mnMinY, mnMaxY */
+    float fx, fy, cx, cy;      /* the key frame's own */
+    const uint8_t *skip;       /* one byte per map entry FOR THIS key frame: !pML || pML->isBad() || pML->IsInKeyFrame(pKF); NULL: none */
+} hvo_lf_keyframe;
+typedef struct {               /* a map side on host arrays: vpMapLines */
+    int32_t n;
+    const double  *pos;                         /* n x 6: GetWorldPos(), start then end */
+    const double  *normal;                      /* n x 3: GetNormal() */
+    const float   *max_distance, *min_distance; /* RAW mfMaxDistance / mfMinDistance; the call applies 1.2f / 0.8f, as in hvo_line_map */
+    const uint8_t *desc;                        /* n x 32, mLDescriptor */
+} hvo_lf_map;
+#define HVO_LF_LEVEL_CLAMPED    0
+#define HVO_LF_LEVEL_AS_WRITTEN 1
+typedef struct {
+    float th;                  /* 3 */
+    int32_t th_low;            /* TH_LOW (50); above 255 is refused */
+    float log_scale_factor;    /* pKF->mfLogScaleFactorLine */
+    int32_t n_levels;          /* levels of mvScaleFactorsLine, 1 .. 16 */
+    float scale_factor;        /* the line extractor's: the table is built from it */
+    int32_t level_rule;        /* HVO_LF_LEVEL_* (reading 2) */
+    int32_t map_per_keyframe;  /* hvo_fuse_lines: 0 = map_side[0] is shared by all key frames; 1 = key frame j is searched with map_side[j] */
+} hvo_lf_params;
+/* gate codes, in the reference's order */
+#define HVO_LF_GATE_SEARCHED     0   /* also an entry for which GetLinesInArea returns nothing: best_idx stays -1 */
+#define HVO_LF_GATE_SKIP         1   /* skip[i], or a bad slot */
+#define HVO_LF_GATE_BEHIND       2   /* SPcZ < 0.0f || EPcZ < 0.0f: where the reference returns */
+#define HVO_LF_GATE_OUT_OF_IMAGE 3   /* !IsInImage(u1, v1), or !IsInImage(u2, v2) */
+#define HVO_LF_GATE_DIST_MIN     4   /* dist < 0.8f * mfMinDistance */
+#define HVO_LF_GATE_DIST_MAX     5   /* dist > 1.2f * mfMaxDistance */
+#define HVO_LF_GATE_VIEW_ANGLE   6   /* OM.dot(pn) < 0.5 * dist */
+#define HVO_LF_GATE_LEVEL        7   /* HVO_LF_LEVEL_AS_WRITTEN only: the predicted level is outside [0, n_levels) */
+typedef struct {               /* per key frame; every pointer but best_idx may be NULL.  n = the entries of this key frame's map side */
+    int32_t *best_idx, *best_dist;   /* n: bestIdx / bestDist after the loop (-1 / 256 where no candidate survived or the entry was not searched) */
+    int8_t  *gate;                   /* n */
+    int32_t *level;                  /* n: nPredictedLevel (unclamped under HVO_LF_GATE_LEVEL); -1 where the reference did not compute it */
+    float   *proj;                   /* n x 4: u1 v1 u2 v2 as far as the reference computed them (skip, behind: zeros; u1, v1 out of image: u1 v1 0 0) */
+    int32_t *fused_entry, *fused_idx;   /* room for n each: the entries with best_dist <= th_low in ascending order and their key lines */
+    int32_t *behind_entry;              /* room for n: the entries with HVO_LF_GATE_BEHIND in ascending order */
+    int32_t n_fused, n_behind, n_searched, status; float kernel_ms[3];   /* device time of the whole call's records + projection, search, and
+                                                                          * count + compaction kernels */
+} hvo_lf_result;
+/* On host arrays: n_kf key frames against map_side[0] (shared) or map_side[j].  Limits: 2048 lines per key frame, 65536 entries per key
+ * frame, 2^24 padded (key frame, entry) pairs per call (HVO_ERR_UNSUPPORTED beyond); th_low > 255, n_levels outside 1 .. 16, an unknown
+ * level_rule, empty bounds or a missing array are HVO_ERR_INVALID_ARG.  Every refusal is whole: nothing is written and hvo_last_error says
+ * why.  n == 0 on either side is HVO_OK with no match.  One synchronisation per call. */
+int hvo_fuse_lines(hvo_ctx *ctx, const hvo_lf_params *params, const hvo_lf_map *map_side, int n_kf, const hvo_lf_keyframe *keyframes, hvo_lf_result *results);
+/* The map side as n slots of a resident line map, shared by all key frames: the map's device arrays are read in place (end points and
+ * normal rounded to float as Mat_<float> << does), only the slot list and the skip bytes go up.  A bad slot counts as skipped; a slot
+ * outside the map is HVO_ERR_INVALID_ARG (whole).  The map must live on the context's device.  The refusal's text is in hvo_last_error and
+ * in hvo_line_map_last_error. */
+int hvo_fuse_lines_slots(hvo_ctx *ctx, hvo_line_map *m, int n, const int32_t *slots, const hvo_lf_params *params, int n_kf, const hvo_lf_keyframe *keyframes,
+                         hvo_lf_result *results);
+/* The resident frame `cur` is the one key frame, under Tcw and cam (fx, fy, cx, cy), valid while the frame is in the ring.  Its key lines
+ * and LBD descriptors are read where the stages left them (n_desc_rows = its line count); the bounds are its grid's.  The map side is
+ * map_side (host arrays) or, when map_side is NULL, n slots of m.  skip: one byte per entry or NULL.  The stream must run an LSD stage:
+ * otherwise HVO_ERR_INVALID_ARG with hvo_stream_last_error set.  The result is the host-array form's on the downloaded frame, bit for bit. */
+int hvo_stream_fuse_lines(hvo_stream *s, int64_t cur, const hvo_camera *cam, const hvo_lf_params *params, const float Tcw[12], const uint8_t *skip,
+                          const hvo_lf_map *map_side, hvo_line_map *m, int n, const int32_t *slots, hvo_lf_result *result);
+
 /* ---- LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:335-580; csrc/new_points.hip) ----
  * The epipolar search (ComputeF12 :1779-1796, ORBmatcher::SearchForTriangulation src/ORBmatcher.cc:668-836 with CheckDistEpipolarLine
  * :143-160) and the triangulation of every match (parallax test, 4 x 4 linear triangulation or KeyFrame::UnprojectStereo, two depth signs,

@@ -530,9 +530,78 @@ private:
     hvo_ctx *ctx_;
 };
 
+// What LSDmatcher::Fuse(pKF, vpMapLines, th) leaves per key frame: bestIdx / bestDist per entry, the entries with bestDist <= TH_LOW in ascending
+// order with their key lines, and the entries at which the reference's `return false` (a negative depth) would fire, in ascending order.
+struct LineFuseMatches {
+    std::vector<int> best_idx, best_dist, fused_entry, fused_idx, behind_entry; std::vector<int8_t> gate;
+    int n_fused = 0, n_behind = 0, n_searched = 0; float kernel_ms[3] = { 0.f, 0.f, 0.f };
+};
+// what a walk did: the fusions made, the behind entry that ended it (-1: none), and whether on_fused reported a Replace.  Within one (key
+// frame, list) pair the walk is exact.  Across the key frames of one shared-map call a Replace can change the descriptor of an entry that
+// later key frames were already searched with (MapLine::Replace -> ComputeDistinctiveDescriptors on the survivor): a caller that wants the
+// sequential result calls Fuse again for the remaining key frames when `replaced` is set.
+struct LineFuseWalk { int n_fused = 0, stopped_at = -1; bool replaced = false; };
+
 class LSDmatcher {
 public:
     static const int TH_HIGH = 80, TH_LOW = 50;                            // LSDmatcher.cpp:12-14
+    // hvo_lf_params for Fuse: th, the key frame's mfLogScaleFactorLine, the levels and factor of mvScaleFactorsLine, HVO_LF_LEVEL_*
+    static hvo_lf_params fuseParams(float th = 3.0f, float logScaleFactor = 0.18232161f, int nLevels = 1, float scaleFactor = 1.2f, int levelRule = HVO_LF_LEVEL_CLAMPED)
+    {
+        hvo_lf_params p = hvo_lf_params();
+        p.th = th; p.th_low = TH_LOW; p.log_scale_factor = logScaleFactor; p.n_levels = nLevels; p.scale_factor = scaleFactor; p.level_rule = levelRule;
+        return p;
+    }
+    // Fuse(pKF, vpMapLines, th) (LSDmatcher.cpp:1297-1434) for n_kf key frames on host arrays against ONE map side (LocalMapping.cc:1651) in one
+    // device call.  kf[j].desc_rows: the rows the candidates are compared with (mLineDescriptors, or mDescriptors for the text as written);
+    // kf[j].skip: a byte per entry, !pML || isBad() || IsInKeyFrame(pKF_j).  Returns the fused lists' total length.
+    int Fuse(const hvo_lf_map &vpMapLines, int n_kf, const hvo_lf_keyframe *kf, std::vector<LineFuseMatches> &res, const hvo_lf_params &p = fuseParams()) const
+    {
+        std::vector<hvo_lf_result> r((size_t)std::max(n_kf, 1));
+        res.assign((size_t)std::max(n_kf, 0), LineFuseMatches());
+        for (int j = 0; j < n_kf; j++) r[j] = lf_result(res[j], vpMapLines.n);
+        hvo_lf_params q = p; q.map_per_keyframe = 0;
+        check(hvo_fuse_lines(ctx_, &q, &vpMapLines, n_kf, kf, r.data()), "hvo_fuse_lines");
+        int total = 0;
+        for (int j = 0; j < n_kf; j++) total += lf_take(res[j], r[j]);
+        return total;
+    }
+    // the map side as n_slots slots of a resident line map (the tracker's, LocalMapping.cc:1677): its arrays are read in place
+    int Fuse(hvo_line_map *map, int n_slots, const int32_t *slots, int n_kf, const hvo_lf_keyframe *kf, std::vector<LineFuseMatches> &res, const hvo_lf_params &p = fuseParams()) const
+    {
+        std::vector<hvo_lf_result> r((size_t)std::max(n_kf, 1));
+        res.assign((size_t)std::max(n_kf, 0), LineFuseMatches());
+        for (int j = 0; j < n_kf; j++) r[j] = lf_result(res[j], n_slots);
+        check(hvo_fuse_lines_slots(ctx_, map, n_slots, slots, &p, n_kf, kf, r.data()), "hvo_fuse_lines_slots");
+        int total = 0;
+        for (int j = 0; j < n_kf; j++) total += lf_take(res[j], r[j]);
+        return total;
+    }
+    // the resident frame `cur` as the one key frame under Tcw and cam; the map side is host arrays or (vpMapLines == nullptr) slots of a line map
+    int Fuse(FrameStream &fs, int64_t cur, const hvo_camera &cam, const float Tcw[12], const uint8_t *skip, const hvo_lf_map *vpMapLines, hvo_line_map *map,
+             int n_slots, const int32_t *slots, LineFuseMatches &res, const hvo_lf_params &p = fuseParams()) const;
+    // The pointer part of LSDmatcher.cpp:1340-1341 and :1411-1431 for one key frame: the fused and the behind entries merged in entry order.
+    // still_skipped(entry): `pML->isBad() || pML->IsInKeyFrame(pKF)` NOW (it only ever turns from "not skipped" to "skipped" during the walk);
+    // on_fused(entry, idx) does Replace or AddObservation + AddMapLine and returns true when it called Replace.  stop_on_behind (as written):
+    // the walk ends at the first behind entry that is still not skipped when it is reached; false: it continues, as `continue` would have.
+    template <class StillSkipped, class OnFused>
+    static LineFuseWalk walkFused(const LineFuseMatches &r, bool stop_on_behind, StillSkipped still_skipped, OnFused on_fused)
+    {
+        LineFuseWalk w;
+        size_t f = 0, b = 0;
+        const size_t nf = (size_t)std::max(r.n_fused, 0), nb = (size_t)std::max(r.n_behind, 0);
+        while (f < nf || b < nb) {
+            const bool behind = f >= nf || (b < nb && r.behind_entry[b] < r.fused_entry[f]);      // an entry is in one list at most
+            const int e = behind ? r.behind_entry[b] : r.fused_entry[f];
+            const int idx = behind ? -1 : r.fused_idx[f];
+            if (behind) b++; else f++;
+            if (still_skipped(e)) continue;
+            if (behind) { if (stop_on_behind) { w.stopped_at = e; break; } continue; }
+            if (on_fused(e, idx)) w.replaced = true;
+            w.n_fused++;
+        }
+        return w;
+    }
     // FrameBFMatch(ldesc1, ldesc2, LineMatches, TH) (LSDmatcher.cpp:942-966)
     void FrameBFMatch(const uint8_t *ldesc1, int n1, const uint8_t *ldesc2, int n2, std::vector<int> &LineMatches, float TH, float nnratio) const
     {
@@ -600,6 +669,22 @@ public:
         return n;
     }
 private:
+    static hvo_lf_result lf_result(LineFuseMatches &m, int n)
+    {
+        const size_t k = (size_t)std::max(n, 1);
+        m.best_idx.assign(k, -1); m.best_dist.assign(k, 256); m.fused_entry.assign(k, -1); m.fused_idx.assign(k, -1); m.behind_entry.assign(k, -1); m.gate.assign(k, 0);
+        hvo_lf_result r = hvo_lf_result();
+        r.best_idx = m.best_idx.data(); r.best_dist = m.best_dist.data(); r.fused_entry = m.fused_entry.data(); r.fused_idx = m.fused_idx.data();
+        r.behind_entry = m.behind_entry.data(); r.gate = m.gate.data();
+        return r;
+    }
+    static int lf_take(LineFuseMatches &m, const hvo_lf_result &r)
+    {
+        m.n_fused = r.n_fused; m.n_behind = r.n_behind; m.n_searched = r.n_searched;
+        for (int k = 0; k < 3; k++) m.kernel_ms[k] = r.kernel_ms[k];
+        m.fused_entry.resize((size_t)r.n_fused); m.fused_idx.resize((size_t)r.n_fused); m.behind_entry.resize((size_t)r.n_behind);
+        return r.n_fused;
+    }
     hvo_ctx *ctx_;
     float mfNNratio;
 };
@@ -1141,6 +1226,14 @@ inline int ORBmatcher::Fuse(FrameStream &fs, int64_t cur, const hvo_camera &cam,
     hvo_fuse_result r = fuse_result(res, vpMapPoints ? vpMapPoints->n : n_slots);
     check(hvo_stream_fuse_points(fs.get(), cur, &cam, &p, Tcw, skip, vpMapPoints, map, n_slots, slots, &r), "hvo_stream_fuse_points");
     return fuse_take(res, r);
+}
+
+inline int LSDmatcher::Fuse(FrameStream &fs, int64_t cur, const hvo_camera &cam, const float Tcw[12], const uint8_t *skip, const hvo_lf_map *vpMapLines, hvo_line_map *map,
+                            int n_slots, const int32_t *slots, LineFuseMatches &res, const hvo_lf_params &p) const
+{
+    hvo_lf_result r = lf_result(res, vpMapLines ? vpMapLines->n : n_slots);
+    check(hvo_stream_fuse_lines(fs.get(), cur, &cam, &p, Tcw, skip, vpMapLines, map, n_slots, slots, &r), "hvo_stream_fuse_lines");
+    return lf_take(res, r);
 }
 
 inline int LocalMapping::CreateNewMapLinesConstraint(FrameStream &fs, int64_t cur, const hvo_camera &cam, const float Tcw[12], const uint8_t *has_map_line, int n_lines,
