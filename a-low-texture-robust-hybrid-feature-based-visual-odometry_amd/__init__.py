@@ -2521,21 +2521,6 @@ class Context:
         p = None if pos is None else np.ascontiguousarray(pos, np.float64).reshape(-1, 6)
         return _mr_call(self, "hvo_refresh_map_lines", True, (), (p.ctypes.data if p is not None and p.size else None,), obs, n_levels, scale_factor, what, want, check)
 
-    def debug_match_arena(self, fill=None, min_bytes=0):
-        """test door (not in include/hvo.h): grow the matching arena to min_bytes the way a call would, set its whole device capacity to the
-        byte `fill` (None: leave it), return the capacity"""
-        L = lib(); f = L.hvo_debug_match_arena; f.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]; f.restype = C.c_int
-        cap = C.c_size_t(0)
-        self._chk(f(self.h, -1 if fill is None else int(fill), int(min_bytes), C.byref(cap)), "debug_match_arena")
-        return cap.value
-
-    def debug_match_arena_peek(self, offset, n):
-        """test door: n bytes of the matching arena's device block from `offset`"""
-        L = lib(); f = L.hvo_debug_match_arena_peek; f.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]; f.restype = C.c_int
-        out = np.zeros(int(n), np.uint8)
-        self._chk(f(self.h, int(offset), int(n), _p(out)), "debug_match_arena_peek")
-        return out
-
     def pnp_last_kernel_ms(self):
         """(hypothesis kernels, refine kernels): device ms of the last pnp_ransac"""
         ms = np.zeros(2, np.float32)

@@ -209,7 +209,6 @@ void hvo_destroy(hvo_ctx *ctx)
     bow_state_free(&ctx->bow_batch); bow_state_free(&ctx->bow_call);
     if (ctx->call_arena) (void)hipFree(ctx->call_arena);
     orb_free_plan(ctx);
-    match_free(ctx);
     peac_free(ctx);
     lsd_free(ctx);
     if (ctx->d_pattern) (void)hipFree(ctx->d_pattern);
@@ -229,14 +228,7 @@ void hvo_destroy(hvo_ctx *ctx)
     if (ctx->s_peac) (void)hipStreamDestroy(ctx->s_peac);
     if (ctx->ev_lsd_pre) (void)hipEventDestroy(ctx->ev_lsd_pre);
     if (ctx->ev_fast) (void)hipEventDestroy(ctx->ev_fast);
-    for (hipEvent_t e : ctx->po_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->bow_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->pnp_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->kfs_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->fuse_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->np_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->nl_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ls_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->call_ev) if (e) (void)hipEventDestroy(e);
     delete ctx;
 }
 
@@ -1133,14 +1125,4 @@ extern "C" int hvo_unpin_host(void *p)
 {
     if (!p) return HVO_ERR_INVALID_ARG;
     return hipHostUnregister(p) == hipSuccess ? HVO_OK : HVO_ERR_HIP;
-}
-
-void *hvo_stage_host(hvo_ctx *ctx, size_t bytes)
-{
-    if (ctx->h_stage_cap >= bytes) return ctx->h_stage;
-    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-    ctx->h_stage = nullptr; ctx->h_stage_cap = 0;
-    if (hipHostMalloc(&ctx->h_stage, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
-    ctx->h_stage_cap = bytes;
-    return ctx->h_stage;
 }

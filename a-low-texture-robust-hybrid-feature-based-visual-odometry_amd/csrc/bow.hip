@@ -33,7 +33,7 @@
 //                   private to the node because a frame feature lies in exactly one node.  Then the 30-bin rotation histogram and
 //                   ComputeThreeMaxima (hvo_three_maxima, shared with the guided search).
 #include "frame_view.hpp"
-#include "call_stage.hpp"
+#include "staged_call.hpp"
 #include <string.h>
 #include <stdio.h>
 #include <math.h>
@@ -420,24 +420,6 @@ static int voc_build(int device, int k, int L, int scoring, int weighting, int n
 }
 
 // ------------------------------------------------------------------------------------------------ host: ComputeBoW
-// events around a call's launches (which = 0: ComputeBoW's two kernels, 1: SearchByBoW's CSR + search kernels); ms stays 0 when nothing ran
-static void bow_ev_begin(hvo_ctx *ctx, hipStream_t st, int which)
-{
-    ctx->bow_ms[which] = 0.f; ctx->bow_ev_on[which] = false;
-    hipEvent_t *e = ctx->bow_ev + 2 * which;
-    if (!e[0] && (hipEventCreate(&e[0]) != hipSuccess || hipEventCreate(&e[1]) != hipSuccess)) return;
-    ctx->bow_ev_on[which] = hipEventRecord(e[0], st) == hipSuccess;
-}
-static void bow_ev_end(hvo_ctx *ctx, hipStream_t st, int which)
-{
-    if (ctx->bow_ev_on[which]) ctx->bow_ev_on[which] = hipEventRecord(ctx->bow_ev[2 * which + 1], st) == hipSuccess;
-}
-static void bow_ev_read(hvo_ctx *ctx, int which)               // after the stream has drained
-{
-    if (ctx->bow_ev_on[which] && hipEventElapsedTime(&ctx->bow_ms[which], ctx->bow_ev[2 * which], ctx->bow_ev[2 * which + 1]) != hipSuccess) ctx->bow_ms[which] = 0.f;
-    ctx->bow_ev_on[which] = false;
-}
-
 int bow_transform(hvo_ctx *ctx, hipStream_t st, const hvo_vocabulary *v, int levelsup, int nframes, const FrameView *fr, BowState *keep, bool may_keep,
                   hvo_bow *out, std::string *err)
 {
@@ -452,7 +434,8 @@ int bow_transform(hvo_ctx *ctx, hipStream_t st, const hvo_vocabulary *v, int lev
     BowLayout L; bow_layout(cap, L);
     const bool kept = may_keep && keep->valid && keep->voc_uid == v->uid && keep->levelsup == levelsup && keep->n >= nframes && keep->cap == cap;
     const bool empty = v->n_words == 0;
-    ctx->bow_ms[0] = 0.f; ctx->bow_ev_on[0] = false;
+    ctx->bow_ms[0] = 0.f;                                       // stays 0 when the kept result is returned or nothing is launched
+    CallTimer timer(ctx, st);
     if (!kept) {
         keep->valid = false;
         const size_t need = (size_t)nframes * L.total;
@@ -467,11 +450,11 @@ int bow_transform(hvo_ctx *ctx, hipStream_t st, const hvo_vocabulary *v, int lev
         } else if (cap > 0) {
             const int tf = v->weighting == HVO_VOC_TF_IDF || v->weighting == HVO_VOC_TF;
             const int norm = v->scoring == HVO_VOC_DOT_PRODUCT ? 0 : (v->scoring == HVO_VOC_L2_NORM ? 2 : 1);
-            bow_ev_begin(ctx, st, 0);
+            timer.tick();
             hipLaunchKernelGGL(k_bow_descend, dim3((cap + 256 / BOW_GROUP - 1) / (256 / BOW_GROUP), nframes), dim3(256), 0, st, v->d, v->L - levelsup, d_desc, desc_stride,
                                d_n, n_stride, keep->d_blk, L);
             hipLaunchKernelGGL(k_bow_assemble, dim3(nframes), dim3(256), 0, st, tf, norm, d_n, n_stride, keep->d_blk, L);
-            bow_ev_end(ctx, st, 0);
+            timer.tick();
             if (hipGetLastError() != hipSuccess) { *err = "bag of words: launch"; return HVO_ERR_HIP; }
         } else if (hipMemsetAsync(keep->d_blk, 0, need, st) != hipSuccess) return HVO_ERR_HIP;
         keep->voc_uid = v->uid; keep->levelsup = levelsup; keep->n = nframes; keep->cap = cap;
@@ -481,7 +464,8 @@ int bow_transform(hvo_ctx *ctx, hipStream_t st, const hvo_vocabulary *v, int lev
         *err = std::string("bag of words: ") + hipGetErrorString(hipGetLastError()); return HVO_ERR_HIP;
     }
     keep->valid = true;
-    bow_ev_read(ctx, 0);
+    float ms[3];
+    timer.read(ms); ctx->bow_ms[0] = ms[0];
     for (int f = 0; f < nframes; f++) {
         const char *b = h.data() + (size_t)f * L.total; const int *c = (const int *)(b + L.counts);
         hvo_bow &o = out[f];
@@ -524,9 +508,11 @@ int bow_search(hvo_ctx *ctx, hipStream_t st, const hvo_bow_keyframe *F, const Fr
     const auto c_node = C.take<int>(Kf, ck), c_start = C.take<int>(Kf, ck + 1), c_idx = C.take<int>(Kf, ck), c_rows = C.take<int>(Kf);
     const auto g_node = C.take<int>(cf), g_start = C.take<int>(cf + 1), g_idx = C.take<int>(cf), g_rows = C.take<int>(1);
     const auto r_match = C.take<int>(Kf, cf), r_n = C.take<int>(Kf);
-    char *d = (char *)hvo_call_arena(ctx, C.mark());
-    if (!d) { *err = "search by bag of words: arena"; return HVO_ERR_HIP; }
-    std::vector<char> hv(up_end, 0); char *const h = hv.data();
+    const size_t r0 = r_match.off, r1 = C.mark();               // the two results come down
+    StagedCall sc(ctx, st, "search by bag of words: ", err); int rc;
+    ctx->bow_ms[1] = 0.f;
+    if ((rc = sc.begin(r1, up_end, r1 - r0))) return rc;
+    char *const d = sc.d, *const h = sc.h;
     for (int j = 0; j < n_kf; j++) {
         const int n = kf[j].n;
         k_n.host(h)[j] = n;
@@ -543,11 +529,11 @@ int bow_search(hvo_ctx *ctx, hipStream_t st, const hvo_bow_keyframe *F, const Fr
         memcpy(f_desc.host(h), F->desc, (size_t)nf * 32); memcpy(f_node.host(h), F->node_id, (size_t)nf * 4);
         if (F->angle) memcpy(f_ang.host(h), F->angle, (size_t)nf * 4);
     }
-    if (hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st) != hipSuccess) return HVO_ERR_HIP;
+    if ((rc = sc.up(0, up_end))) return rc;
     BowSideDev K; memset(&K, 0, sizeof(K));
     K.desc = k_desc.dev(d); K.node = k_node.dev(d); K.has_mp = k_has.dev(d); K.angle = k_ang.dev(d); K.angle_step = 1;
     K.fv_node = c_node.dev(d); K.fv_start = c_start.dev(d); K.fv_idx = c_idx.dev(d); K.n_rows = c_rows.dev(d); K.n = k_n.dev(d); K.cap = capk;
-    bow_ev_begin(ctx, st, 1);
+    sc.tick();
     hipLaunchKernelGGL(k_bow_csr, dim3(n_kf), dim3(256), 0, st, K);
     BowSearchDev A; memset(&A, 0, sizeof(A));
     A.kf = K; A.f_n = f_n.dev(d); A.f_cap = nf;
@@ -567,15 +553,11 @@ int bow_search(hvo_ctx *ctx, hipStream_t st, const hvo_bow_keyframe *F, const Fr
     A.nnratio = P->nnratio; A.check_orientation = P->check_orientation ? 1 : 0; A.th_low = P->th_low;
     A.match_kf = r_match.dev(d); A.n_matches = r_n.dev(d);
     hipLaunchKernelGGL(k_bow_search, dim3(n_kf), dim3(64 * BOW_WAVES), 0, st, A);
-    bow_ev_end(ctx, st, 1);
-    if (hipGetLastError() != hipSuccess) { *err = "search by bag of words: launch"; return HVO_ERR_HIP; }
-    std::vector<int> hm(r_match.count()), hn(r_n.count());
-    if (hipMemcpyAsync(hm.data(), r_match.dev(d), r_match.bytes(), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(hn.data(), r_n.dev(d), r_n.bytes(), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        *err = std::string("search by bag of words: ") + hipGetErrorString(hipGetLastError()); return HVO_ERR_HIP;
-    }
-    bow_ev_read(ctx, 1);
-    for (int j = 0; j < n_kf; j++) { memcpy(res[j].match_kf, &hm[(size_t)j * nf], (size_t)nf * 4); res[j].n_matches = hn[j]; }
+    sc.tick();
+    StageDown b;
+    if ((rc = sc.down(r0, r1, &b))) return rc;
+    ctx->bow_ms[1] = sc.ms[0];
+    for (int j = 0; j < n_kf; j++) { memcpy(res[j].match_kf, r_match.down(b, j), (size_t)nf * 4); res[j].n_matches = r_n.down(b)[j]; }
     return HVO_OK;
 }
 

@@ -45,6 +45,7 @@
 // No contraction (-ffp-contract=off, __f*_rn, __d*_rn).
 #include "slot_map.hpp"
 #include "frame_view.hpp"
+#include "staged_call.hpp"
 #include <math.h>
 #include <string.h>
 #include <string>
@@ -307,9 +308,9 @@ static int fuse_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const h
     const auto r_proj = C.take<float>(F, cq * 3); const auto r_gate = C.take<int8_t>(F, cq);
     const auto r_fe = C.take<int32_t>(F, cq), r_fi = C.take<int32_t>(F, cq);
     const size_t r1 = C.mark();
-    char *d = (char *)hvo_call_arena(ctx, C.mark());
-    if (!d) { *err = "fuse: arena"; return HVO_ERR_HIP; }
-    std::vector<char> hv(up_end, 0); char *const h = hv.data();
+    StagedCall sc(ctx, st, "fuse: ", err); int rc;
+    if ((rc = sc.begin(C.mark(), up_end, r1 - r0))) return rc;
+    char *const d = sc.d, *const h = sc.h;
     float *tab = u_tab.host(h);
     for (int l = 0; l < HVO_MAX_LEVELS; l++) tab[l] = fr ? fr->sf[l] : ctx->scale[l];
     frame_level_sigma2(fr ? fr->ctx : ctx, nullptr, tab + HVO_MAX_LEVELS);
@@ -338,12 +339,8 @@ static int fuse_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const h
         if (n) { memcpy(u_maxd.host(h, s), M.max_dist, n * 4); memcpy(u_mind.host(h, s), M.min_dist, n * 4); memcpy(u_md.host(h, s), M.desc, n * 32); }
     }
     if (m && n_slots) memcpy(u_slots.host(h), slots, (size_t)n_slots * 4);
-    if (hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = "fuse: upload"; return HVO_ERR_HIP; }
-    // (the memset follows the copy: a copy from pageable memory waits for what the stream holds)
-    if (hipMemsetAsync(d + z0, 0, z1 - z0, st) != hipSuccess) { *err = "fuse: memset"; return HVO_ERR_HIP; }
-    bool ev_on = true;
-    for (int i = 0; i < 4; i++) if (!ctx->fuse_ev[i] && hipEventCreate(&ctx->fuse_ev[i]) != hipSuccess) ev_on = false;
-    if (ev_on) ev_on = hipEventRecord(ctx->fuse_ev[0], st) == hipSuccess;
+    if ((rc = sc.up(0, up_end)) || (rc = sc.clear(z0, z1))) return rc;
+    sc.tick();
     FuDev a; memset(&a, 0, sizeof(a));
     a.kf = u_kf.dev(d); a.cq = (int)cq; a.ct = (int)ct; a.n_levels = P->n_levels; a.per_kf = per_kf ? 1 : 0; a.nb = (int)nb;
     if (m) {
@@ -364,25 +361,19 @@ static int fuse_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const h
     a.fe = r_fe.dev(d); a.fi = r_fi.dev(d); a.pass = s_pass.dev(d); a.blockcnt = s_bc.dev(d);
     a.nsearched = r_cnt.dev(d, 0); a.nfused = r_cnt.dev(d, 1);
     hipLaunchKernelGGL(k_fuse_grid, dim3(n_kf), dim3(FU_BLOCK), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->fuse_ev[1], st) == hipSuccess;
+    sc.tick();
     hipLaunchKernelGGL(k_fuse_project, dim3((unsigned)nb, n_kf), dim3(FU_BLOCK), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->fuse_ev[2], st) == hipSuccess;
+    sc.tick();
     if (nmax > 0 && tmax > 0) hipLaunchKernelGGL(k_fuse_search, dim3((unsigned)(cq / (FU_BLOCK / FU_GROUP)), n_kf), dim3(FU_BLOCK), 0, st, a);
     hipLaunchKernelGGL(k_fuse_compact, dim3((unsigned)nb, n_kf), dim3(FU_BLOCK), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->fuse_ev[3], st) == hipSuccess;
-    if (hipGetLastError() != hipSuccess) { *err = "fuse: launch"; return HVO_ERR_HIP; }
-    std::vector<char> hr(r1 - r0);
-    if (hipMemcpyAsync(hr.data(), d + r0, r1 - r0, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        *err = std::string("fuse: ") + hipGetErrorString(hipGetLastError()); return HVO_ERR_HIP;
-    }
-    float ms[3] = { 0.f, 0.f, 0.f };
-    if (ev_on) for (int i = 0; i < 3; i++) if (hipEventElapsedTime(&ms[i], ctx->fuse_ev[i], ctx->fuse_ev[i + 1]) != hipSuccess) ms[i] = 0.f;
-    const StageDown b = { hr.data(), r0 };
+    sc.tick();
+    StageDown b;
+    if ((rc = sc.down(r0, r1, &b))) return rc;
     for (int j = 0; j < n_kf; j++) {
         hvo_fuse_result &R = res[j];
         const size_t n = (size_t)n_ent[j];
         R.n_searched = r_cnt.down(b, 0)[j]; R.n_fused = r_cnt.down(b, 1)[j]; R.status = HVO_OK;
-        for (int i = 0; i < 3; i++) R.kernel_ms[i] = ms[i];
+        for (int i = 0; i < 3; i++) R.kernel_ms[i] = sc.ms[i];
         if (!n) continue;
         memcpy(R.best_idx, r_bi.down(b, j), n * 4);
         if (R.best_dist) memcpy(R.best_dist, r_bd.down(b, j), n * 4);

@@ -142,9 +142,7 @@ struct hvo_ctx {
     // resident batch
     int batch_n = 0, batch_w = 0, batch_h = 0;
     bool have_depth = false;
-    // matcher staging arena (match.hip)
-    void *marena = nullptr;
-    // host staging (pinned)
+    // host staging (pinned, grow-only: hvo_stage_host)
     void *h_stage = nullptr; size_t h_stage_cap = 0;
     hipEvent_t ev_stage[2] = { nullptr, nullptr };     // download staging (hvo_staged_d2h)
     // profiling
@@ -152,19 +150,16 @@ struct hvo_ctx {
     bool serialize = false;                // profiling mode 2: all stages on one stream (clean per-kernel times)
     bool lsd_on_orb_stream = false;        // streamed mode: ORB (0.6 ms) then the line chain on one stream, planes on the other (two HW queues per frame in flight)
     ProfileRec prof[HVO_MAX_PROFILE]; int nprof = 0;
-    // staging arena of the host-array entry points of the Frame tail (hvo_lines_3d, hvo_vanishing_points, hvo_plane_clouds, ...): one
-    // grow-only device buffer per context instead of hipMalloc / hipFree per call (hvo_call_arena)
-    void *call_arena = nullptr; size_t call_arena_cap = 0;
-    hipEvent_t po_ev[2] = { nullptr, nullptr }; float po_ms = 0.f;   // pose_opt.hip: events around the last launch (hvo_pose_last_kernel_ms)
-    hipEvent_t ls_ev[3] = { nullptr, nullptr, nullptr }; float ls_ms[2] = { 0.f, 0.f };   // line_opt.hip: events around the last call's two launches
+    // staging arena of every host-array entry point (arena.hip): one grow-only device buffer per context instead of hipMalloc / hipFree per
+    // call (hvo_call_arena).  bump_d / bump_h: where match.hip's older matchers stand in it and in the pinned block (arena_begin rewinds both)
+    void *call_arena = nullptr; size_t call_arena_cap = 0, bump_d = 0, bump_h = 0;
+    hipEvent_t call_ev[4] = { nullptr, nullptr, nullptr, nullptr };   // the one timer of the staged calls (staged_call.hpp): calls on a context do not overlap
+    float po_ms = 0.f;                     // pose_opt.hip: device time of the last launch (hvo_pose_last_kernel_ms)
+    float ls_ms[2] = { 0.f, 0.f };         // line_opt.hip: device time of the last call's two launches
     bool ls_batch_done = false;            // hvo_batch_line_struct_optimize has optimised the resident batch's 3-D lines (cleared by hvo_batch_run)
     void *tail = nullptr;                  // resident-batch Frame tail (tail.hip)
-    hipEvent_t bow_ev[4] = { nullptr, nullptr, nullptr, nullptr }; float bow_ms[2] = { 0.f, 0.f }; bool bow_ev_on[2] = { false, false };   // bow.hip: events around the last calls' launches
-    hipEvent_t pnp_ev[3] = { nullptr, nullptr, nullptr }; float pnp_ms[2] = { 0.f, 0.f }; bool pnp_ev_on = false;   // pnp.hip: events around the last call's two kernel groups
-    hipEvent_t kfs_ev[3] = { nullptr, nullptr, nullptr };   // kf_search.hip: events around the last call's prologue and its searches
-    hipEvent_t fuse_ev[4] = { nullptr, nullptr, nullptr, nullptr };   // fuse.hip: events around the last call's grid, projection and search kernels
-    hipEvent_t np_ev[4] = { nullptr, nullptr, nullptr, nullptr };     // new_points.hip: events around the last call's search, triangulation and resolve kernels
-    hipEvent_t nl_ev[4] = { nullptr, nullptr, nullptr, nullptr };     // line_triang.inc: the same for CreateNewMapLinesConstraint; map_refresh.inc brackets its kernel with the first two; line_fuse.inc uses all four
+    float bow_ms[2] = { 0.f, 0.f };        // bow.hip: device time of the last ComputeBoW and the last SearchByBoW
+    float pnp_ms[2] = { 0.f, 0.f };        // pnp.hip: device time of the last call's two kernel groups
     BowState bow_batch, bow_call;         // bow.hip: the resident batch's bag of words (cleared by hvo_batch_run), the host-array form's block
     // opaque per-subsystem state (peac.hip / lsd.hip own these)
     void *peac = nullptr;
@@ -285,7 +280,6 @@ static inline hipStream_t hvo_stream_peac(hvo_ctx *c);
 // profiling scope helpers (api.hip)
 int  hvo_prof_begin(hvo_ctx *ctx, const char *name, hipStream_t st);
 void hvo_prof_end(hvo_ctx *ctx, int id);
-void *hvo_stage_host(hvo_ctx *ctx, size_t bytes);
 int hvo_staged_d2h(hvo_ctx *ctx, hipStream_t st, const void *dev_base, size_t dev_stride, int n, void *const *dst, const size_t *bytes, int widen8 = 0);
 
 // orb.hip
@@ -339,7 +333,6 @@ int match_search_by_projection_tracked(hvo_ctx *ctx, const uint8_t *q_desc, int 
 int match_matrix(hvo_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, uint16_t *d);
 int match_knn2(hvo_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt, int32_t *idx2, int32_t *dist2);
 int match_knn2_enqueue(hipStream_t st, const uint8_t *dq, int nq, const uint8_t *dt, int nt, int32_t *d_idx2, int32_t *d_dist2);
-void match_free(hvo_ctx *ctx);
 size_t match_sbp_scratch_bytes(int nq);
 int match_sbp_enqueue(hipStream_t st, SbpDev a, void *scratch);
 int match_search_by_projection(hvo_ctx *ctx, const uint8_t *q_desc, int nq, const float *q_u, const float *q_v, const float *q_radius,
@@ -416,8 +409,11 @@ int frame_lines_to_grid(hvo_ctx *ctx, const hvo_keyline *kl, int n, const float 
 
 struct FrameView;                          // frame_view.hpp: one resident frame as the resident operations see it
 
-// api.hip: device buffer of at least `bytes` that lives as long as the context (grows by reallocation after draining the context's streams)
+// arena.hip: the context's two staging blocks, both grow-only.  hvo_call_arena: device buffer of at least `bytes` that lives as long as the
+// context (grows by reallocation after draining the context's stream, to hvo_arena_capacity(bytes)); hvo_stage_host: the pinned host block
+static inline size_t hvo_arena_capacity(size_t bytes) { return (bytes + (bytes >> 2) + 4095) & ~(size_t)4095; }
 void *hvo_call_arena(hvo_ctx *ctx, size_t bytes);
+void *hvo_stage_host(hvo_ctx *ctx, size_t bytes);
 
 // line3d.hip
 int lines3d_enqueue(hvo_ctx *ctx, hipStream_t st, const hvo_keyline *d_kl, const int *d_n, int n_max, const uint16_t *d_depth, int pitch, int w, int h,

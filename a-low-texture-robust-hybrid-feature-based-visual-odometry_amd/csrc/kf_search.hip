@@ -37,6 +37,7 @@
 // No contraction (-ffp-contract=off, __f*_rn).
 #include "slot_map.hpp"
 #include "frame_view.hpp"
+#include "staged_call.hpp"
 #include <math.h>
 #include <string.h>
 #include <string>
@@ -143,9 +144,9 @@ int kfs_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_kf_se
     const auto r_proj = C.take<float>(F, cq * 2); const auto r_gate = C.take<int8_t>(F, cq);
     const size_t r1 = C.mark();                                  // [r0, r1) comes down
     const auto s_keys = C.take<char>(match_sbp_scratch_bytes((int)cq));  // the candidates' searches run one after the other on the stream and share the key rows
-    char *d = (char *)hvo_call_arena(ctx, C.mark());
-    if (!d) { *err = "key-frame search: arena"; return HVO_ERR_HIP; }
-    std::vector<char> hv(up_end, 0); char *const h = hv.data();
+    StagedCall sc(ctx, st, "key-frame search: ", err); int rc;
+    if ((rc = sc.begin(C.mark(), up_end, r1 - r0))) return rc;
+    char *const d = sc.d, *const h = sc.h;
     for (int j = 0; j < n_kf; j++) {
         const hvo_kf_search_candidate &K = kf[j];
         KfsCand &c = *u_cand.host(h, j);
@@ -166,12 +167,8 @@ int kfs_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_kf_se
         if (nt) { memcpy(u_kp.host(h), host->kp_un, (size_t)nt * sizeof(hvo_keypoint)); memcpy(u_fd.host(h), host->desc, (size_t)nt * 32); }
         V.kp_un = u_kp.dev(d); V.desc = u_fd.dev(d);
     }
-    if (hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = "key-frame search: upload"; return HVO_ERR_HIP; }
-    // (the memsets follow the copy: a copy from pageable memory waits for what the stream holds)
-    if (hipMemsetAsync(r_cnt.dev(d), 0, r_cnt.bytes(), st) != hipSuccess || hipMemsetAsync(r_fk.dev(d), 0xFF, r_fk.bytes(), st) != hipSuccess) { *err = "key-frame search: memset"; return HVO_ERR_HIP; }
-    bool ev_on = true;
-    for (int i = 0; i < 3; i++) if (!ctx->kfs_ev[i] && hipEventCreate(&ctx->kfs_ev[i]) != hipSuccess) ev_on = false;
-    if (ev_on) ev_on = hipEventRecord(ctx->kfs_ev[0], st) == hipSuccess;
+    if ((rc = sc.up(0, up_end)) || (rc = sc.clear(r_cnt.off, r_cnt.off + r_cnt.bytes())) || (rc = sc.clear(r_fk.off, r_fk.off + r_fk.bytes(), 0xFF))) return rc;
+    sc.tick();
     KfsDev a; memset(&a, 0, sizeof(a));
     a.cand = u_cand.dev(d); a.cq = (int)cq; a.n_levels = P->n_levels;
     a.pos = u_pos.dev(d); a.maxd = u_maxd.dev(d); a.mind = u_mind.dev(d); a.skip = u_skip.dev(d);
@@ -182,7 +179,7 @@ int kfs_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_kf_se
     a.proj = r_proj.dev(d); a.level = r_lvl.dev(d); a.gate = r_gate.dev(d); a.mi = r_mi.dev(d); a.md = r_md.dev(d);
     a.counters = r_cnt.dev(d);
     if (nmax > 0) hipLaunchKernelGGL(k_kf_project, dim3((nmax + KFS_BLOCK - 1) / KFS_BLOCK, n_kf), dim3(KFS_BLOCK), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->kfs_ev[1], st) == hipSuccess;
+    sc.tick();
     for (int j = 0; j < n_kf; j++) {
         const int n = kf[j].n;
         if (n < 1 || nt < 1) continue;
@@ -194,27 +191,17 @@ int kfs_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_kf_se
         s.nq = n; s.nt = nt; s.mnMinX = V.bounds[0]; s.mnMaxX = V.bounds[1]; s.mnMinY = V.bounds[2]; s.mnMaxY = V.bounds[3];
         s.th_high = P->orb_dist; s.check_orientation = P->check_orientation ? 1 : 0; s.map_mode = 0; s.nn_ratio = 0.f;
         s.match_idx = r_mi.dev(d, j); s.match_dist = r_md.dev(d, j); s.n_matches = r_cnt.dev(d, j);
-        const int rc = match_sbp_enqueue(st, s, s_keys.dev(d));
-        if (rc) { *err = rc == HVO_ERR_UNSUPPORTED ? kfs_limit_text(n, nt) : "key-frame search: search launch"; return rc; }
+        if ((rc = match_sbp_enqueue(st, s, s_keys.dev(d)))) { *err = rc == HVO_ERR_UNSUPPORTED ? kfs_limit_text(n, nt) : "key-frame search: search launch"; return rc; }
         hipLaunchKernelGGL(k_kf_inverse, dim3((n + KFS_BLOCK - 1) / KFS_BLOCK), dim3(KFS_BLOCK), 0, st, n, nt, (const int32_t *)s.match_idx, s.match_dist, r_fk.dev(d, j));
     }
-    if (ev_on) ev_on = hipEventRecord(ctx->kfs_ev[2], st) == hipSuccess;
-    if (hipGetLastError() != hipSuccess) { *err = "key-frame search: launch"; return HVO_ERR_HIP; }
-    std::vector<char> hr(r1 - r0);
-    if (hipMemcpyAsync(hr.data(), d + r0, r1 - r0, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        *err = std::string("key-frame search: ") + hipGetErrorString(hipGetLastError()); return HVO_ERR_HIP;
-    }
-    float ms[2] = { 0.f, 0.f };
-    if (ev_on) {
-        if (hipEventElapsedTime(&ms[0], ctx->kfs_ev[0], ctx->kfs_ev[1]) != hipSuccess) ms[0] = 0.f;
-        if (hipEventElapsedTime(&ms[1], ctx->kfs_ev[1], ctx->kfs_ev[2]) != hipSuccess) ms[1] = 0.f;
-    }
-    const StageDown b = { hr.data(), r0 };
+    sc.tick();
+    StageDown b;
+    if ((rc = sc.down(r0, r1, &b))) return rc;
     for (int j = 0; j < n_kf; j++) {
         hvo_kf_search_result &R = res[j];
         const size_t n = (size_t)kf[j].n;
         const int *cnt = r_cnt.down(b, j);
-        R.n_matches = cnt[0]; R.n_searched = cnt[1]; R.status = HVO_OK; R.kernel_ms[0] = ms[0]; R.kernel_ms[1] = ms[1];
+        R.n_matches = cnt[0]; R.n_searched = cnt[1]; R.status = HVO_OK; R.kernel_ms[0] = sc.ms[0]; R.kernel_ms[1] = sc.ms[1];
         if (n) {
             memcpy(R.match_idx, r_mi.down(b, j), n * 4);
             if (R.match_dist) memcpy(R.match_dist, r_md.down(b, j), n * 4);

@@ -1,7 +1,7 @@
-// line_fuse.inc -- LSDmatcher::Fuse(KeyFrame *pKF, const vector<MapLine *> &vpMapLines, float th) (reference src/LSDmatcher.cpp:1297-1434), the
+// line_fuse.hip -- LSDmatcher::Fuse(KeyFrame *pKF, const vector<MapLine *> &vpMapLines, float th) (reference src/LSDmatcher.cpp:1297-1434), the
 // line matcher of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:1651, :1677), for n_kf key frames in one call with one synchronisation.
 // With it: KeyFrame::GetLinesInArea (src/KeyFrame.cc:668-702), KeyFrame::IsInImage, MapLine::PredictScale (src/MapLine.cpp:549-558).
-// Included by match.hip: it stages through the matching arena (arena_begin / arena_of) with one StageCarver layout.
+// A staged call (staged_call.hpp) with one StageCarver layout.
 //
 // As in ORBmatcher::Fuse there is no occupancy: pKF->GetMapLine(bestIdx) is read after the search, so every (key frame, entry) pair is
 // independent.  GetLinesInArea has no grid: it tests EVERY key line of the key frame for every entry, so the work is
@@ -45,8 +45,12 @@
 // Inside GetLinesInArea: the mid-point distance is formed in double (0.5 * (x1 + x2) has a double literal; x1 + x2 is a float sum) and
 // rounded to the float `distance`; it is compared with the float product r * r with `>`; CosSita = fabsf of the float sum of two float
 // products; `CosSita < 0.998f` continues, so a NaN (a projected or stored line of zero length) PASSES.  Nothing is contracted.
+#include "hvo_internal.hpp"
 #include "slot_map.hpp"
 #include "frame_view.hpp"
+#include "staged_call.hpp"
+#include <string.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -259,7 +263,7 @@ static int lf_run(hvo_ctx *ctx, hipStream_t st, const hvo_lf_params *P, const Fr
                std::to_string(LF_MAXQ) + ", " + std::to_string(LF_MAXL) + ", " + std::to_string(LF_MAXTOTAL) + "); nothing was written";
         return HVO_ERR_UNSUPPORTED;
     }
-    // ---- one carve of the matching arena: what goes up, the records and radii, the flags and counts, what comes down ----
+    // ---- one carve of the context's arena: what goes up, the records and radii, the flags and counts, what comes down ----
     const size_t S = m ? 0 : (per_kf ? F : 1), nb = cq / LF_BLOCK, Fh = fr ? 0 : F;     // Fh: key-frame sides that go up
     size_t rmax = 0;
     for (int j = 0; j < n_kf; j++) rmax = std::max(rmax, (size_t)n_rows[j]);
@@ -279,10 +283,9 @@ static int lf_run(hvo_ctx *ctx, hipStream_t st, const hvo_lf_params *P, const Fr
     const auto r_proj = C.take<float>(F, cq * 4); const auto r_gate = C.take<int8_t>(F, cq);
     const auto r_fe = C.take<int32_t>(F, cq), r_fi = C.take<int32_t>(F, cq), r_be = C.take<int32_t>(F, cq);
     const size_t r1 = C.mark();
-    if (arena_begin(ctx, r1, up_end + (r1 - r0))) { *err = "fuse lines: arena"; return HVO_ERR_HIP; }
-    MatchArena *A = arena_of(ctx);
-    char *const d = A->d, *const h = A->h, *const hr = A->h + up_end;
-    memset(h, 0, up_end);
+    StagedCall sc(ctx, st, "fuse lines: ", err); int rc;
+    if ((rc = sc.begin(r1, up_end, r1 - r0))) return rc;
+    char *const d = sc.d, *const h = sc.h;
     float *tab = u_tab.host(h), sf = 1.0f;
     for (int l = 0; l < HVO_MAX_LEVELS; l++) { if (l > 0 && l < P->n_levels) sf = sf * P->scale_factor; tab[l] = l < P->n_levels ? sf : 1.0f; }
     for (int j = 0; j < n_kf; j++) {
@@ -307,10 +310,8 @@ static int lf_run(hvo_ctx *ctx, hipStream_t st, const hvo_lf_params *P, const Fr
         if (n) { memcpy(u_maxd.host(h, s), M.max_distance, n * 4); memcpy(u_mind.host(h, s), M.min_distance, n * 4); memcpy(u_md.host(h, s), M.desc, n * 32); }
     }
     if (m && n_slots) memcpy(u_slots.host(h), slots, (size_t)n_slots * 4);
-    if (hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = "fuse lines: upload"; return HVO_ERR_HIP; }
-    bool ev_on = true;
-    for (int i = 0; i < 4; i++) if (!ctx->nl_ev[i] && hipEventCreate(&ctx->nl_ev[i]) != hipSuccess) ev_on = false;
-    if (ev_on) ev_on = hipEventRecord(ctx->nl_ev[0], st) == hipSuccess;
+    if ((rc = sc.up(0, up_end))) return rc;
+    sc.tick();
     LfDev a; memset(&a, 0, sizeof(a));
     a.kf = u_kf.dev(d); a.cq = (int)cq; a.ct = (int)ct; a.n_levels = P->n_levels; a.per_kf = per_kf ? 1 : 0; a.nb = (int)nb;
     a.as_written = P->level_rule == HVO_LF_LEVEL_AS_WRITTEN ? 1 : 0;
@@ -327,26 +328,21 @@ static int lf_run(hvo_ctx *ctx, hipStream_t st, const hvo_lf_params *P, const Fr
     a.bcF = s_bcF.dev(d); a.bcB = s_bcB.dev(d); a.bcS = r_bcS.dev(d); a.nfused = r_cnt.dev(d, 0); a.nbehind = r_cnt.dev(d, 1);
     if (tmax > 0) hipLaunchKernelGGL(k_lf_lines, dim3((unsigned)((ct + LF_BLOCK - 1) / LF_BLOCK), n_kf), dim3(LF_BLOCK), 0, st, a);
     hipLaunchKernelGGL(k_lf_project, dim3((unsigned)nb, n_kf), dim3(LF_BLOCK), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->nl_ev[1], st) == hipSuccess;
+    sc.tick();
     if (nmax > 0 && tmax > 0) hipLaunchKernelGGL(k_lf_search, dim3((unsigned)(cq / (LF_BLOCK / LF_GROUP)), n_kf), dim3(LF_BLOCK), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->nl_ev[2], st) == hipSuccess;
+    sc.tick();
     hipLaunchKernelGGL(k_lf_count, dim3((unsigned)nb, n_kf), dim3(LF_BLOCK), 0, st, a);
     hipLaunchKernelGGL(k_lf_compact, dim3((unsigned)nb, n_kf, 2), dim3(LF_BLOCK), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->nl_ev[3], st) == hipSuccess;
-    if (hipGetLastError() != hipSuccess) { *err = "fuse lines: launch"; return HVO_ERR_HIP; }
-    if (hipMemcpyAsync(hr, d + r0, r1 - r0, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        *err = std::string("fuse lines: ") + hipGetErrorString(hipGetLastError()); return HVO_ERR_HIP;
-    }
-    float ms[3] = { 0.f, 0.f, 0.f };
-    if (ev_on) for (int i = 0; i < 3; i++) if (hipEventElapsedTime(&ms[i], ctx->nl_ev[i], ctx->nl_ev[i + 1]) != hipSuccess) ms[i] = 0.f;
-    const StageDown b = { hr, r0 };
+    sc.tick();
+    StageDown b;
+    if ((rc = sc.down(r0, r1, &b))) return rc;
     for (int j = 0; j < n_kf; j++) {
         hvo_lf_result &R = res[j];
         const size_t n = (size_t)n_ent[j];
         int ns = 0;
         for (size_t q = 0; q < nb; q++) ns += r_bcS.down(b, j)[q];
         R.n_searched = ns; R.n_fused = r_cnt.down(b, 0)[j]; R.n_behind = r_cnt.down(b, 1)[j]; R.status = HVO_OK;
-        for (int i = 0; i < 3; i++) R.kernel_ms[i] = ms[i];
+        for (int i = 0; i < 3; i++) R.kernel_ms[i] = sc.ms[i];
         if (!n) continue;
         memcpy(R.best_idx, r_bi.down(b, j), n * 4);
         if (R.best_dist) memcpy(R.best_dist, r_bd.down(b, j), n * 4);

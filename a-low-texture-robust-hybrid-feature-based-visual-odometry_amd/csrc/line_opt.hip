@@ -17,7 +17,7 @@
 // pivot is exactly 0 or not finite, in any line's block; the step of a failed solve is taken as zero (the trial is rejected either way);
 // classification re-evaluates an edge at the end points of the round's last computeActiveErrors instead of storing _error.
 #include "frame_view.hpp"
-#include "call_stage.hpp"
+#include "staged_call.hpp"
 #include <math.h>
 #include <cmath>
 #include <string.h>
@@ -453,9 +453,9 @@ int ls_run(hvo_ctx *ctx, hipStream_t st, const hvo_line_struct_params *params, i
         O[f].lev = C.take<uint8_t>(part2 ? c : 0, c); O[f].est = C.take<double>(c, 6); O[f].trial = C.take<double>(c, 6); O[f].Hb = C.take<double>(c, 27);
         O[f].ent = C.take<uint8_t>(c, 2);
     }
-    char *d = (char *)hvo_call_arena(ctx, C.mark());
-    char *h = (char *)hvo_stage_host(ctx, down_end);                         // the arena's [0, down_end) at the same offsets
-    if (!d || !h) { *err = "line structure: scratch"; return HVO_ERR_HIP; }
+    StagedCall sc(ctx, st, "line structure: ", err); int rc;
+    if ((rc = sc.begin(C.mark(), up_end, down_end - down0, false))) return rc;     // every piece is copied whole: nothing relies on zero padding
+    char *const d = sc.d, *const h = sc.h;
     for (int f = 0; f < n; f++) {
         const size_t c = (size_t)n_lines[f];
         LsFrame &F = *frames.host(h, f); memset(&F, 0, sizeof(F));
@@ -479,32 +479,24 @@ int ls_run(hvo_ctx *ctx, hipStream_t st, const hvo_line_struct_params *params, i
     A.cos_par = P.cos_par; A.cos_perp = P.cos_perp; A.delta = P.huber_delta; A.chi2_reject = P.chi2_reject;
     A.chi2_round[0] = P.chi2_round[0]; A.chi2_round[1] = P.chi2_round[1];
     A.min_constraints = P.min_constraints; A.iterations = P.iterations; A.row_rule = P.row_rule;
-#define LS_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *err = std::string(#call) + ": " + hipGetErrorString(e_); return HVO_ERR_HIP; } } while (0)
-    for (int i = 0; i < 3; i++) if (!ctx->ls_ev[i]) LS_HIP(hipEventCreate(&ctx->ls_ev[i]));
-    LS_HIP(hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st));
-    LS_HIP(hipEventRecord(ctx->ls_ev[0], st));
+    if ((rc = sc.up(0, up_end))) return rc;
+    sc.tick();
     if (part1 && cap_max > 0) {
         const long long blocks = ((long long)cap_max * cap_max + 255) / 256;
         hipLaunchKernelGGL(k_ls_pairs, dim3(n, (unsigned)(blocks < 64 ? blocks : 64)), dim3(256), 0, st, A);
-        LS_HIP(hipGetLastError());
     }
-    LS_HIP(hipEventRecord(ctx->ls_ev[1], st));
+    sc.tick();
     if (part2) hipLaunchKernelGGL(k_line_opt, dim3(n), dim3(LS_THREADS), 0, st, A);
     else hipLaunchKernelGGL(k_ls_copy6, dim3(n), dim3(256), 0, st, A);
-    LS_HIP(hipGetLastError());
-    LS_HIP(hipEventRecord(ctx->ls_ev[2], st));
-    LS_HIP(hipMemcpyAsync(h + down0, d + down0, down_end - down0, hipMemcpyDeviceToHost, st));
-    LS_HIP(hipStreamSynchronize(st));
-    LS_HIP(hipEventElapsedTime(&ctx->ls_ms[0], ctx->ls_ev[0], ctx->ls_ev[1]));
-    LS_HIP(hipEventElapsedTime(&ctx->ls_ms[1], ctx->ls_ev[1], ctx->ls_ev[2]));
-#undef LS_HIP
-    if (!part1) ctx->ls_ms[0] = 0.f;
-    if (!part2) ctx->ls_ms[1] = 0.f;
-    memcpy(res, results.host(h), results.bytes());
+    sc.tick();
+    StageDown b;
+    if ((rc = sc.down(down0, down_end, &b))) return rc;
+    ctx->ls_ms[0] = part1 ? sc.ms[0] : 0.f; ctx->ls_ms[1] = part2 ? sc.ms[1] : 0.f;
+    memcpy(res, results.down(b), results.bytes());
     for (int f = 0; f < n; f++) {
         const size_t c = (size_t)n_lines[f];
-        if (c) memcpy(rel[f], O[f].rel.host(h), c * c);
-        if (c && l3d_out && l3d_out[f]) memcpy(l3d_out[f], O[f].out6.host(h), c * 48);
+        if (c) memcpy(rel[f], O[f].rel.down(b), c * c);
+        if (c && l3d_out && l3d_out[f]) memcpy(l3d_out[f], O[f].out6.down(b), c * 48);
     }
     return HVO_OK;
 }

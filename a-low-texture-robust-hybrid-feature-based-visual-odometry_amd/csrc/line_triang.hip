@@ -1,5 +1,5 @@
-// line_triang.inc -- LocalMapping::CreateNewMapLinesConstraint (reference src/LocalMapping.cc:1064-1565) for all neighbour key frames in one
-// call with one synchronisation (included by match.hip after line_map.inc; it stages through the matching arena like every LSDmatcher call).
+// line_triang.hip -- LocalMapping::CreateNewMapLinesConstraint (reference src/LocalMapping.cc:1064-1565) for all neighbour key frames in one
+// call with one synchronisation (a staged call: staged_call.hpp; the searches are match.hip's match_lines_enqueue).
 //
 // Why one launch sequence serves the loops.  LSDmatcher::SearchForTriangulation(.., true) (src/LSDmatcher.cpp:1195-1231) keeps i -> j only
 // if j -> i, so a match vector maps current lines to a neighbour's lines injectively, and the key frame at list position p is only ever
@@ -44,11 +44,16 @@
 //                         std::max(a, b) = a < b ? b : a on floats in the argument order of the text; the ratios in float, compared as
 //                         doubles with 0.85.  A zero-length segment makes a ratio inf or NaN: the comparison is false and the triple passes on
 //   octaves               an octave of the three lines outside [0, n_levels) refuses the triple (HVO_NL_BAD_OCTAVE) after the occupancy tests
+#include "hvo_internal.hpp"
 #include "slot_map.hpp"
 #include "frame_view.hpp"
+#include "staged_call.hpp"
 #include "triangulate4.inc"
 #include <math.h>
+#include <string.h>
+#include <algorithm>
 #include <string>
+#include <vector>
 
 #define NL_BLOCK SM_BLOCK
 #define NL_MAXN HVO_NL_MAX_LINES
@@ -368,7 +373,7 @@ static int nl_run(hvo_ctx *ctx, hipStream_t st, const hvo_nl_params *P, const hv
         if (sum->owner_pair) for (int i = 0; i < n1; i++) sum->owner_pair[i] = -1;
         return HVO_OK;
     }
-    // ---- one carve of the matching arena: what goes up, the search's scratch, what is cleared, what comes down ----
+    // ---- one carve of the context's arena: what goes up, the search's scratch, what is cleared, what comes down ----
     const size_t cq = (size_t)((n1 + NL_BLOCK - 1) / NL_BLOCK * NL_BLOCK), ct = (size_t)std::max(64, (tmax + 63) & ~63), nb = cq / NL_BLOCK;
     StageCarver C(256);
     const auto u_kf = C.take<NlKf>(F + 1); const auto u_pr = C.take<NlPair>(NP); const auto u_sig = C.take<float>(HVO_MAX_LEVELS); const auto u_chas = C.take<uint8_t>(cq);
@@ -386,10 +391,9 @@ static int nl_run(hvo_ctx *ctx, hipStream_t st, const hvo_nl_params *P, const hv
     const auto r_out = C.take<int8_t>(NP, cq); const auto r_x = C.take<float>(NP, cq * 6);
     const auto r_c0 = C.take<int32_t>(NP, cq), r_c1 = C.take<int32_t>(NP, cq), r_c2 = C.take<int32_t>(NP, cq), r_own = C.take<int32_t>(cq);
     const size_t r1 = C.mark();
-    if (arena_begin(ctx, r1, up_end + (r1 - r0))) { *err = "create new map lines: arena"; return HVO_ERR_HIP; }
-    MatchArena *A = arena_of(ctx);
-    char *const d = A->d, *const h = A->h, *const hr = A->h + up_end;
-    memset(h, 0, up_end);
+    StagedCall sc(ctx, st, "create new map lines: ", err); int rc;
+    if ((rc = sc.begin(r1, up_end, r1 - r0))) return rc;
+    char *const d = sc.d, *const h = sc.h;
     memcpy(u_kf.host(h), hk.data(), (F + 1) * sizeof(NlKf)); memcpy(u_pr.host(h), hp.data(), NP * sizeof(NlPair));
     float *sig = u_sig.host(h), sf = 1.0f;
     for (int l = 0; l < HVO_MAX_LEVELS; l++) { if (l > 0 && l < P->n_levels) sf = sf * P->scale_factor; sig[l] = l < P->n_levels ? sf * sf : 1.0f; }
@@ -402,11 +406,8 @@ static int nl_run(hvo_ctx *ctx, hipStream_t st, const hvo_nl_params *P, const hv
         memcpy(u_kl.host(h, j), K.kl, n * sizeof(hvo_keyline)); memcpy(u_fn.host(h, j), K.linefn, n * 24);
         memcpy(u_ds.host(h, j), K.desc, n * 32); memcpy(u_has.host(h, j), K.has_map_line, n);
     }
-    if (hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = "create new map lines: upload"; return HVO_ERR_HIP; }
-    if (hipMemsetAsync(d + z0, 0, z1 - z0, st) != hipSuccess || hipMemsetAsync(d + z1, 0xFF, m1 - z1, st) != hipSuccess) { *err = "create new map lines: memset"; return HVO_ERR_HIP; }
-    bool ev_on = true;
-    for (int i = 0; i < 4; i++) if (!ctx->nl_ev[i] && hipEventCreate(&ctx->nl_ev[i]) != hipSuccess) ev_on = false;
-    if (ev_on) ev_on = hipEventRecord(ctx->nl_ev[0], st) == hipSuccess;
+    if ((rc = sc.up(0, up_end)) || (rc = sc.clear(z0, z1)) || (rc = sc.clear(z1, m1, 0xFF))) return rc;
+    sc.tick();
     NlDev a; memset(&a, 0, sizeof(a));
     const uint8_t *c_desc;
     if (fr) { a.c_kl = fr->kl; a.c_fn = fr->fn; c_desc = fr->ldesc; }
@@ -422,18 +423,15 @@ static int nl_run(hvo_ctx *ctx, hipStream_t st, const hvo_nl_params *P, const hv
         if (match_lines_enqueue(st, c_desc, n1, u_ds.dev(d, j), kf[j].n, (float)P->th_high, P->nn_ratio, 2, s_ml.dev(d), r_M.dev(d, j), r_nm.dev(d) + j)) { *err = "create new map lines: search launch"; return HVO_ERR_HIP; }
         hipLaunchKernelGGL(k_nl_occupancy, dim3(1), dim3(256), 0, st, r_M.dev(d, j), n1, (int)kf[j].n, u_chas.dev(d), u_has.dev(d, j), r_nm.dev(d) + j);
     }
-    if (ev_on) ev_on = hipEventRecord(ctx->nl_ev[1], st) == hipSuccess;
+    sc.tick();
     hipLaunchKernelGGL(k_nl_triangulate, dim3((unsigned)nb, (unsigned)NP), dim3(NL_BLOCK), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->nl_ev[2], st) == hipSuccess;
+    sc.tick();
     hipLaunchKernelGGL(k_nl_resolve, dim3((unsigned)nb), dim3(NL_BLOCK), 0, st, a);
     hipLaunchKernelGGL(k_nl_compact, dim3((unsigned)nb, (unsigned)NP), dim3(NL_BLOCK), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->nl_ev[3], st) == hipSuccess;
-    if (hipGetLastError() != hipSuccess) { *err = "create new map lines: launch"; return HVO_ERR_HIP; }
-    if (hipMemcpyAsync(hr, d + r0, r1 - r0, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        *err = std::string("create new map lines: ") + hipGetErrorString(hipGetLastError()); return HVO_ERR_HIP;
-    }
-    if (ev_on) for (int i = 0; i < 3; i++) if (hipEventElapsedTime(&sum->kernel_ms[i], ctx->nl_ev[i], ctx->nl_ev[i + 1]) != hipSuccess) sum->kernel_ms[i] = 0.f;
-    const StageDown b = { hr, r0 };
+    sc.tick();
+    StageDown b;
+    if ((rc = sc.down(r0, r1, &b))) return rc;
+    for (int i = 0; i < 3; i++) sum->kernel_ms[i] = sc.ms[i];
     const size_t n = (size_t)n1;
     for (int j = 0; j < n_kf; j++) { mt[j].n_matched = r_nm.down(b)[j]; mt[j].gate = gate[j]; memcpy(mt[j].match_idx, r_M.down(b, j), n * 4); }
     int n_new = 0;
@@ -476,36 +474,6 @@ int hvo_stream_create_new_map_lines(hvo_stream *s, int64_t cur, const hvo_camera
     hvo_nl_keyframe K; memset(&K, 0, sizeof(K));
     memcpy(K.Tcw, Tcw, sizeof(K.Tcw)); K.has_map_line = has_map_line; K.cam = *cam; K.n = V.n_kl;
     return nl_run(V.ctx, s->s_match, params, &K, &V, n_kf, neighbours, matches, n_pairs_cap, results, summary, &s->last_error);
-}
-
-// Test doors (tests/test_new_lines_gpu.py), not product API and not in include/hvo.h: hvo_debug_call_arena / _peek on the matching arena's
-// device block.  The first grows it to min_bytes the way a call would, sets its whole capacity to fill_byte when that is >= 0 and reports it
-int hvo_debug_match_arena(hvo_ctx *ctx, int fill_byte, size_t min_bytes, size_t *cap_out)
-{
-    if (!ctx || fill_byte > 255) return HVO_ERR_INVALID_ARG;
-    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    MatchArena *A = arena_of(ctx);
-    if (min_bytes && arena_begin(ctx, min_bytes, 0)) return HVO_ERR_HIP;
-    if (fill_byte >= 0 && A->dcap) {
-        if (hipMemsetAsync(A->d, fill_byte, A->dcap, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            ctx->last_error = "hvo_debug_match_arena: fill"; return HVO_ERR_HIP;
-        }
-    }
-    if (cap_out) *cap_out = A->dcap;
-    return HVO_OK;
-}
-
-int hvo_debug_match_arena_peek(hvo_ctx *ctx, size_t offset, size_t n, uint8_t *out)
-{
-    if (!ctx) return HVO_ERR_INVALID_ARG;
-    MatchArena *A = arena_of(ctx);
-    if ((n && !out) || offset > A->dcap || n > A->dcap - offset) return HVO_ERR_INVALID_ARG;
-    if (n == 0) return HVO_OK;
-    if (hipSetDevice(ctx->device) != hipSuccess) return HVO_ERR_NO_DEVICE;
-    if (hipMemcpyAsync(out, A->d + offset, n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-        ctx->last_error = "hvo_debug_match_arena_peek: copy"; return HVO_ERR_HIP;
-    }
-    return HVO_OK;
 }
 
 }   // extern "C"

@@ -1,6 +1,6 @@
-// map_refresh.inc -- MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (reference src/MapPoint.cc:240-305, 328-369) and
+// map_refresh.hip -- MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (reference src/MapPoint.cc:240-305, 328-369) and
 // MapLine::ComputeDistinctiveDescriptors + UpdateAverageDir (src/MapLine.cpp:331-396, 404-455) for n features in one call with one
-// synchronisation (included by match.hip after line_triang.inc; it stages through the matching arena like line_triang.inc).
+// synchronisation (a staged call: staged_call.hpp).
 //
 // No feature reads another's result, so the call is one launch: ONE WAVE (a work group of 64 lanes) PER FEATURE.
 //   k_mr_points / k_mr_lines   the feature's good observers (kf_bad == 0) are listed in order by ballots; their descriptors are gathered
@@ -36,7 +36,13 @@
 //                           would divide by zero
 //   distance range          mfMaxDistance = dist * sf[level] and mfMinDistance = mfMaxDistance / sf[n_levels - 1], float.  sf is the
 //                           context's ORB table for points; for lines sf[0] = 1, sf[l] = sf[l - 1] * scale_factor in float
+#include "hvo_internal.hpp"
 #include "slot_map.hpp"
+#include "staged_call.hpp"
+#include "triangulate4.inc"                 // np_normd
+#include <limits.h>
+#include <string.h>
+#include <algorithm>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -228,7 +234,7 @@ template <bool LINE> static int mr_run(hvo_ctx *ctx, hvo_slot_map *m, const MrMa
     if (most > MR_MAXOBS) { *err = std::string(who) + std::to_string(most) + " observations of one feature (limit " + std::to_string(MR_MAXOBS) + "); nothing was written"; return HVO_ERR_UNSUPPORTED; }
     if (no > HVO_MR_MAX_OBS_TOTAL) { *err = std::string(who) + std::to_string(no) + " observations (limit " + std::to_string(HVO_MR_MAX_OBS_TOTAL) + "); nothing was written"; return HVO_ERR_UNSUPPORTED; }
     *out.kernel_ms = 0.f;
-    // ---- one carve of the matching arena: what goes up, then what is cleared and comes down ----
+    // ---- one carve of the context's arena: what goes up, then what is cleared and comes down ----
     const size_t N = (size_t)n, npos = LINE ? 6 : 3;
     hipStream_t st = ctx->stream;
     StageCarver C(256);
@@ -239,10 +245,9 @@ template <bool LINE> static int mr_run(hvo_ctx *ctx, hvo_slot_map *m, const MrMa
     const auto r_bo = C.take<int32_t>(N), r_bm = C.take<int32_t>(N); const auto r_desc = C.take<uint8_t>(N * 32); const auto r_nrm = C.take<real>(N * 3);
     const auto r_wv = C.take<double>(LINE ? N * 3 : 0); const auto r_mx = C.take<float>(N), r_mi = C.take<float>(N); const auto r_st = C.take<uint8_t>(N);
     const size_t r1 = C.mark();
-    if (arena_begin(ctx, r1, up_end + (r1 - r0))) { *err = std::string(who) + "arena"; return HVO_ERR_HIP; }
-    MatchArena *A = arena_of(ctx);
-    char *const d = A->d, *const h = A->h, *const hr = A->h + up_end;
-    memset(h, 0, up_end);
+    StagedCall sc(ctx, st, who, err); int rc;
+    if ((rc = sc.begin(r1, up_end, r1 - r0))) return rc;
+    char *const d = sc.d, *const h = sc.h;
     memcpy(u_start.host(h), in->obs_start, (N + 1) * 4);
     if (no) { memcpy(u_desc.host(h), in->obs_desc, no * 32); memcpy(u_ow.host(h), in->obs_Ow, no * 12); if (in->kf_bad) memcpy(u_bad.host(h), in->kf_bad, no); }
     memcpy(u_row.host(h), in->ref_Ow, N * 12); memcpy(u_lvl.host(h), in->ref_level, N * 4);
@@ -253,11 +258,8 @@ template <bool LINE> static int mr_run(hvo_ctx *ctx, hvo_slot_map *m, const MrMa
         else sf[l] = l < P->n_levels ? ctx->scale[l] : 1.0f;
     }
     if (m) memcpy(u_slot.host(h), slots, N * 4); else memcpy(u_pos.host(h), pos, N * npos * sizeof(real));
-    if (hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = std::string(who) + "upload"; return HVO_ERR_HIP; }
-    if (hipMemsetAsync(d + r0, 0, r1 - r0, st) != hipSuccess) { *err = std::string(who) + "memset"; return HVO_ERR_HIP; }
-    bool ev_on = true;
-    for (int i = 0; i < 2; i++) if (!ctx->nl_ev[i] && hipEventCreate(&ctx->nl_ev[i]) != hipSuccess) ev_on = false;
-    if (ev_on) ev_on = hipEventRecord(ctx->nl_ev[0], st) == hipSuccess;
+    if ((rc = sc.up(0, up_end)) || (rc = sc.clear(r0, r1))) return rc;
+    sc.tick();
     MrDev a; memset(&a, 0, sizeof(a));
     a.n = n; a.n_levels = P->n_levels; a.what = P->what;
     a.obs_start = u_start.dev(d); a.obs_desc = u_desc.dev(d); a.obs_Ow = u_ow.dev(d); a.kf_bad = u_bad.dev(d);
@@ -270,14 +272,11 @@ template <bool LINE> static int mr_run(hvo_ctx *ctx, hvo_slot_map *m, const MrMa
     } else a.pos = u_pos.dev(d);
     if (LINE) hipLaunchKernelGGL(k_mr_lines, dim3((unsigned)n), dim3(64), 0, st, a);
     else hipLaunchKernelGGL(k_mr_points, dim3((unsigned)n), dim3(64), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->nl_ev[1], st) == hipSuccess;
-    if (hipGetLastError() != hipSuccess) { *err = std::string(who) + "launch"; return HVO_ERR_HIP; }
-    if (hipMemcpyAsync(hr, d + r0, r1 - r0, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        *err = std::string(who) + hipGetErrorString(hipGetLastError()); return HVO_ERR_HIP;
-    }
-    if (ev_on && hipEventElapsedTime(out.kernel_ms, ctx->nl_ev[0], ctx->nl_ev[1]) != hipSuccess) *out.kernel_ms = 0.f;
+    sc.tick();
+    StageDown b;
+    if ((rc = sc.down(r0, r1, &b))) return rc;
+    *out.kernel_ms = sc.ms[0];
     // ---- what the status says was written goes to the caller's arrays and, in the slot form, to the map's mirror ----
-    const StageDown b = { hr, r0 };
     const int32_t *bo = r_bo.down(b), *bm = r_bm.down(b); const uint8_t *ds = r_desc.down(b), *stt = r_st.down(b);
     const real *nr = r_nrm.down(b); const double *wv = LINE ? r_wv.down(b) : nullptr; const float *mx = r_mx.down(b), *mi = r_mi.down(b);
     const size_t cap = m ? (size_t)m->cap : 0;

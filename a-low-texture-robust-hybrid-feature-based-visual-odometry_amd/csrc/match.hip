@@ -15,8 +15,8 @@
 //
 // Every pipeline exists in a device-resident form (match_*_enqueue: device pointers in, device results out, no
 // allocation, no synchronisation) used by the streamed-sequence mode (stream.hip), and behind the host-array entry
-// points of include/hvo.h, which stage their arguments through a grow-only arena (one device + one pinned host block
-// per context) instead of a hipMalloc / hipFree pair per argument.
+// points of include/hvo.h, which stage their arguments through the context's grow-only call arena and pinned host block
+// (arena.hip) instead of a hipMalloc / hipFree pair per argument.
 #include "hvo_internal.hpp"
 #include <limits.h>
 #include <string.h>
@@ -68,54 +68,28 @@ __global__ __launch_bounds__(256) void k_hamming_knn2(const ulonglong4 *__restri
 }
 
 // ------------------------------------------------------------------------------------------------
-// staging arena: one device block and one pinned host block per context, grown on demand
+// the older host-array matchers: a bump allocator over the context's call arena and pinned block (arena.hip).  Each of them is a leaf that
+// ends in a synchronisation, so none holds arena memory while another staged call runs.
 // ------------------------------------------------------------------------------------------------
-struct MatchArena {
-    char *d = nullptr, *h = nullptr; size_t dcap = 0, hcap = 0, doff = 0, hoff = 0;
-};
-static MatchArena *arena_of(hvo_ctx *ctx)
-{
-    if (!ctx->marena) ctx->marena = new MatchArena();
-    return (MatchArena *)ctx->marena;
-}
 // makes room for `dbytes` of device and `hbytes` of pinned host staging and rewinds both
 static int arena_begin(hvo_ctx *ctx, size_t dbytes, size_t hbytes)
 {
-    MatchArena *A = arena_of(ctx);
-    dbytes += 4096; hbytes += 4096;                            // alignment slack
-    if (A->dcap < dbytes) {
-        HVO_HIP(hipStreamSynchronize(ctx->stream));
-        if (A->d) (void)hipFree(A->d);
-        A->d = nullptr; A->dcap = 0;
-        const size_t want = dbytes + dbytes / 2;
-        HVO_HIP(hipMalloc((void **)&A->d, want));
-        A->dcap = want;
-    }
-    if (A->hcap < hbytes) {
-        HVO_HIP(hipStreamSynchronize(ctx->stream));
-        if (A->h) (void)hipHostFree(A->h);
-        A->h = nullptr; A->hcap = 0;
-        const size_t want = hbytes + hbytes / 2;
-        HVO_HIP(hipHostMalloc((void **)&A->h, want, hipHostMallocDefault));
-        A->hcap = want;
-    }
-    A->doff = A->hoff = 0;
+    if (!hvo_call_arena(ctx, dbytes + 4096) || !hvo_stage_host(ctx, hvo_arena_capacity(hbytes + 4096))) return HVO_ERR_HIP;     // alignment slack
+    ctx->bump_d = ctx->bump_h = 0;
     return HVO_OK;
 }
 template <class T> static T *arena_dev(hvo_ctx *ctx, size_t n)
 {
-    MatchArena *A = arena_of(ctx);
-    A->doff = (A->doff + 63) & ~(size_t)63;
-    T *p = (T *)(A->d + A->doff);
-    A->doff += n * sizeof(T);
+    ctx->bump_d = (ctx->bump_d + 63) & ~(size_t)63;
+    T *p = (T *)((char *)ctx->call_arena + ctx->bump_d);
+    ctx->bump_d += n * sizeof(T);
     return p;
 }
 template <class T> static T *arena_host(hvo_ctx *ctx, size_t n)
 {
-    MatchArena *A = arena_of(ctx);
-    A->hoff = (A->hoff + 63) & ~(size_t)63;
-    T *p = (T *)(A->h + A->hoff);
-    A->hoff += n * sizeof(T);
+    ctx->bump_h = (ctx->bump_h + 63) & ~(size_t)63;
+    T *p = (T *)((char *)ctx->h_stage + ctx->bump_h);
+    ctx->bump_h += n * sizeof(T);
     return p;
 }
 // host array -> pinned staging -> device (async on the ctx stream); returns the device pointer (nullptr for a null source)
@@ -166,17 +140,6 @@ int match_knn2(hvo_ctx *ctx, const uint8_t *q, int nq, const uint8_t *t, int nt,
     HVO_HIP(hipStreamSynchronize(ctx->stream));
     memcpy(idx2, hi, ob); memcpy(dist2, hd, ob);
     return HVO_OK;
-}
-
-void match_free(hvo_ctx *ctx)
-{
-    MatchArena *A = (MatchArena *)ctx->marena;
-    if (A) {
-        if (A->d) (void)hipFree(A->d);
-        if (A->h) (void)hipHostFree(A->h);
-        delete A;
-        ctx->marena = nullptr;
-    }
 }
 
 // =================================================================================================
@@ -736,6 +699,3 @@ extern "C" int hvo_debug_match_rate(hvo_ctx *ctx, const uint8_t *q, int nq, cons
 
 #include "line_track.inc"
 #include "line_map.inc"
-#include "line_triang.inc"
-#include "map_refresh.inc"
-#include "line_fuse.inc"

@@ -61,6 +61,7 @@
 //   scale                 dist = (float)norm(x3D - Ow); ratioDist = dist2 / dist1; ratioOctave = sf[o1] / sf[o2]; ratioFactor = 1.5f * scale_factor
 #include "slot_map.hpp"
 #include "frame_view.hpp"
+#include "staged_call.hpp"
 #include <math.h>
 #include <string.h>
 #include <string>
@@ -347,9 +348,9 @@ static int np_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo
     const auto r_out = C.take<int8_t>(F, cq), r_br = C.take<int8_t>(F, cq); const auto r_x = C.take<float>(F, cq * 3);
     const auto r_c1 = C.take<int32_t>(F, cq), r_c2 = C.take<int32_t>(F, cq), r_own = C.take<int32_t>(cq);
     const size_t r1 = C.mark();
-    char *d = (char *)hvo_call_arena(ctx, C.mark());
-    if (!d) { *err = "create new map points: arena"; return HVO_ERR_HIP; }
-    std::vector<char> hv(up_end, 0); char *const h = hv.data();
+    StagedCall sc(ctx, st, "create new map points: ", err); int rc;
+    if ((rc = sc.begin(C.mark(), up_end, r1 - r0))) return rc;
+    char *const d = sc.d, *const h = sc.h;
     memcpy(u_kf.host(h), hk.data(), F * sizeof(NpKf));
     float *tab = u_tab.host(h);
     const hvo_ctx *tc = fr ? fr->ctx : ctx;
@@ -371,12 +372,8 @@ static int np_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo
         if (K.uright) { memcpy(u_ur.host(h, j), K.uright, n * 4); memcpy(u_dp.host(h, j), K.depth, n * 4); }
         memcpy(u_ds.host(h, j), K.desc, n * 32); memcpy(u_nd.host(h, j), K.node_id, n * 4); memcpy(u_has.host(h, j), K.has_map_point, n);
     }
-    if (hipMemcpyAsync(d, h, up_end, hipMemcpyHostToDevice, st) != hipSuccess) { *err = "create new map points: upload"; return HVO_ERR_HIP; }
-    // (the memset follows the copy: a copy from pageable memory waits for what the stream holds)
-    if (hipMemsetAsync(d + z0, 0, z1 - z0, st) != hipSuccess) { *err = "create new map points: memset"; return HVO_ERR_HIP; }
-    bool ev_on = true;
-    for (int i = 0; i < 4; i++) if (!ctx->np_ev[i] && hipEventCreate(&ctx->np_ev[i]) != hipSuccess) ev_on = false;
-    if (ev_on) ev_on = hipEventRecord(ctx->np_ev[0], st) == hipSuccess;
+    if ((rc = sc.up(0, up_end)) || (rc = sc.clear(z0, z1))) return rc;
+    sc.tick();
     NpDev a; memset(&a, 0, sizeof(a));
     if (fr) { a.c_kpun = fr->kp_un; a.c_kp = fr->kp; a.c_ur = fr->uright; a.c_depth = fr->zdepth; a.c_desc = fr->desc; a.c_node = d_node; }
     else {
@@ -397,19 +394,15 @@ static int np_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo
     a.c1 = r_c1.dev(d); a.c2 = r_c2.dev(d);
     bow_csr_enqueue(st, n_kf, (int)ct, u_nd.dev(d), u_n.dev(d), g_node.dev(d), g_start.dev(d), g_idx.dev(d), g_rows.dev(d));
     hipLaunchKernelGGL(k_np_search, dim3((unsigned)(cq / (NP_BLOCK / NP_GROUP)), n_kf), dim3(NP_BLOCK), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->np_ev[1], st) == hipSuccess;
+    sc.tick();
     hipLaunchKernelGGL(k_np_triangulate, dim3((unsigned)nb, n_kf), dim3(NP_BLOCK), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->np_ev[2], st) == hipSuccess;
+    sc.tick();
     hipLaunchKernelGGL(k_np_resolve, dim3((unsigned)nb), dim3(NP_BLOCK), 0, st, a);
     hipLaunchKernelGGL(k_np_compact, dim3((unsigned)nb, n_kf), dim3(NP_BLOCK), 0, st, a);
-    if (ev_on) ev_on = hipEventRecord(ctx->np_ev[3], st) == hipSuccess;
-    if (hipGetLastError() != hipSuccess) { *err = "create new map points: launch"; return HVO_ERR_HIP; }
-    std::vector<char> hr(r1 - r0);
-    if (hipMemcpyAsync(hr.data(), d + r0, r1 - r0, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        *err = std::string("create new map points: ") + hipGetErrorString(hipGetLastError()); return HVO_ERR_HIP;
-    }
-    if (ev_on) for (int i = 0; i < 3; i++) if (hipEventElapsedTime(&sum->kernel_ms[i], ctx->np_ev[i], ctx->np_ev[i + 1]) != hipSuccess) sum->kernel_ms[i] = 0.f;
-    const StageDown b = { hr.data(), r0 };
+    sc.tick();
+    StageDown b;
+    if ((rc = sc.down(r0, r1, &b))) return rc;
+    for (int i = 0; i < 3; i++) sum->kernel_ms[i] = sc.ms[i];
     const size_t n = (size_t)n1;
     int n_new = 0;
     for (int j = 0; j < n_kf; j++) {

@@ -18,7 +18,7 @@
 // s is x % s, and removal is the reference's swap-with-last (:199-200).  A hypothesis whose pose is not finite has count 0.
 // SetRansacParameters' log / pow / ceil run on the host (pnp_set_ransac below), so a restatement on the host calls the same libm.
 #include "frame_view.hpp"
-#include "call_stage.hpp"
+#include "staged_call.hpp"
 #include <string.h>
 #include <math.h>
 #include <algorithm>
@@ -269,13 +269,6 @@ static void pnp_set_ransac(const hvo_pnp_params *P, int N, PnpCand *c)
     c->pad = 0;
 }
 
-static void pnp_ev_begin(hvo_ctx *ctx, hipStream_t st)
-{
-    ctx->pnp_ms[0] = ctx->pnp_ms[1] = 0.f; ctx->pnp_ev_on = false;
-    for (int i = 0; i < 3; i++) if (!ctx->pnp_ev[i] && hipEventCreate(&ctx->pnp_ev[i]) != hipSuccess) return;
-    ctx->pnp_ev_on = hipEventRecord(ctx->pnp_ev[0], st) == hipSuccess;
-}
-
 // fr null: prob's host arrays go up.  Else the frame side is the resident frame's key points at fr->kp_un, kf[j]'s map side goes up,
 // N[j] is counted on the host (SetRansacParameters needs it before the launch) and k_pnp_gather compacts on the device.
 int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_params *P, int n_kf, const hvo_pnp_problem *prob, const FrameView *fr,
@@ -336,9 +329,10 @@ int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_p
     const auto a_mask = C.take<uint8_t>(FT, capN); const auto a_idx = C.take<int>(FE, capN); const auto a_rmask = C.take<uint8_t>(FE, capN);
     const size_t total = C.mark();
     if (total > PNP_ARENA_LIMIT) { *err = "pnp: the call's device scratch would pass 1 GiB (candidates x hypotheses x correspondences)"; return HVO_ERR_UNSUPPORTED; }
-    char *d = (char *)hvo_call_arena(ctx, total);
-    if (!d) { *err = "pnp: arena"; return HVO_ERR_HIP; }
-    std::vector<char> hv(up_end, 0); char *const h = hv.data();
+    StagedCall sc(ctx, st, "pnp: ", err); int rc;
+    ctx->pnp_ms[0] = ctx->pnp_ms[1] = 0.f;
+    if ((rc = sc.begin(total, up_end, r1 - r0))) return rc;
+    char *const d = sc.d, *const h = sc.h;
     memcpy(a_cand.host(h), cand.data(), a_cand.bytes());
     PnpGather G; memset(&G, 0, sizeof(G));
     if (fr) {
@@ -351,8 +345,7 @@ int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_p
         G.kp_un = fr->kp_un; G.match = g_match.dev(d); G.kf_pos = g_pos.dev(d); G.kf_bad = g_bad.dev(d);
         G.kf_n = g_n.dev(d); G.nf = fr->n_kp; G.capK = capK; G.th2 = P->th2;
         frame_level_sigma2(ctx, G.sigma2, nullptr);
-        if (hipMemcpyAsync(a_cand.dev(d), a_cand.host(h), stage_align(a_cand.bytes()), hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(d + up_host, h + up_host, up_end - up_host, hipMemcpyHostToDevice, st) != hipSuccess) return HVO_ERR_HIP;
+        if ((rc = sc.up(a_cand.off, a_cand.off + stage_align(a_cand.bytes()))) || (rc = sc.up(up_host, up_end))) return rc;
     } else {
         for (int j = 0; j < n_kf; j++) {
             const hvo_pnp_problem &Q = prob[j];
@@ -362,7 +355,7 @@ int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_p
             for (int i = 0; i < Q.n; i++) { volatile float m = Q.sigma2[i] * P->th2; me[i] = m; }       // mvMaxError (:156)
             memcpy(a_fi.host(h, j), Q.feature_index, (size_t)Q.n * 4);
         }
-        if (hipMemcpyAsync(d, h, up_host, hipMemcpyHostToDevice, st) != hipSuccess) return HVO_ERR_HIP;
+        if ((rc = sc.up(0, up_host))) return rc;
     }
     PnpDev D; memset(&D, 0, sizeof(D));
     D.p3d = a_p3d.dev(d); D.p2d = a_p2d.dev(d); D.max_err = a_me.dev(d); D.fidx = a_fi.dev(d);
@@ -372,31 +365,22 @@ int pnp_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pnp_p
     D.hyp_rec = a_rec.dev(d); D.hyp_event = a_evt.dev(d); D.n_rec = a_nrec.dev(d); D.rec_it = a_recit.dev(d); D.best = a_best.dev(d);
     D.idx = a_idx.dev(d); D.ref_cnt = a_rcnt.dev(d); D.ref_pose = a_rpose.dev(d); D.ref_mask = a_rmask.dev(d);
     D.ev_inl = a_evin.dev(d); D.ev_hinl = a_evh.dev(d); D.best_inl = a_bin.dev(d);
-    if (hipMemsetAsync(d + r0, 0, r1 - r0, st) != hipSuccess) return HVO_ERR_HIP;
+    if ((rc = sc.clear(r0, r1))) return rc;
     if (fr && fr->n_kp > 0) hipLaunchKernelGGL(k_pnp_gather, dim3(n_kf), dim3(256), 0, st, G, capN, a_p3d.dev(d), a_p2d.dev(d), a_me.dev(d), a_fi.dev(d));
-    pnp_ev_begin(ctx, st);
+    sc.tick();
     if (Tcap > 0) {
         const size_t dyn = 2 * ms > PNP_SEQ_ROWS ? (size_t)4 * PNP_TREE_BATCH * 256 * sizeof(double) : 0;
         if (dyn && hvo_ensure_dyn_lds((const void *)k_pnp_hypotheses, dyn) != HVO_OK) { *err = "pnp: dynamic LDS"; return HVO_ERR_HIP; }
         hipLaunchKernelGGL(k_pnp_hypotheses, dim3((Tcap + 3) / 4, n_kf), dim3(64), dyn, st, D);
     }
     hipLaunchKernelGGL(k_pnp_scan, dim3(n_kf), dim3(1), 0, st, D);
-    if (ctx->pnp_ev_on) ctx->pnp_ev_on = hipEventRecord(ctx->pnp_ev[1], st) == hipSuccess;
+    sc.tick();
     if (Tcap > 0) hipLaunchKernelGGL(k_pnp_refine, dim3(E, n_kf), dim3(256), 0, st, D);
     hipLaunchKernelGGL(k_pnp_events, dim3(n_kf), dim3(256), 0, st, D);
-    if (ctx->pnp_ev_on) ctx->pnp_ev_on = hipEventRecord(ctx->pnp_ev[2], st) == hipSuccess;
-    if (hipGetLastError() != hipSuccess) { *err = "pnp: launch"; return HVO_ERR_HIP; }
-    std::vector<char> hr(r1 - r0);
-    if (hipMemcpyAsync(hr.data(), d + r0, r1 - r0, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        *err = std::string("pnp: ") + hipGetErrorString(hipGetLastError()); return HVO_ERR_HIP;
-    }
-    if (ctx->pnp_ev_on) {
-        if (hipEventElapsedTime(&ctx->pnp_ms[0], ctx->pnp_ev[0], ctx->pnp_ev[1]) != hipSuccess) ctx->pnp_ms[0] = 0.f;
-        if (hipEventElapsedTime(&ctx->pnp_ms[1], ctx->pnp_ev[1], ctx->pnp_ev[2]) != hipSuccess) ctx->pnp_ms[1] = 0.f;
-        ctx->pnp_ev_on = false;
-    }
-    const StageDown b = { hr.data(), r0 };
-    int rc = HVO_OK;
+    sc.tick();
+    StageDown b;
+    if ((rc = sc.down(r0, r1, &b))) return rc;
+    ctx->pnp_ms[0] = sc.ms[0]; ctx->pnp_ms[1] = sc.ms[1];
     for (int j = 0; j < n_kf; j++) {
         hvo_pnp_result &R = res[j]; const PnpCand &c = cand[j];
         const int T = c.T, nrec = a_nrec.down(b)[j], ne = std::min(nrec, E);

@@ -19,7 +19,7 @@
 // re-evaluates an unflagged edge at the pose of the round's last computeActiveErrors (the last trial, accepted or not) instead of storing
 // _error per edge.  The host and stream forms launch this kernel alone on the same bytes, so they give bit-identical results.
 #include "frame_view.hpp"
-#include "call_stage.hpp"
+#include "staged_call.hpp"
 #include <math.h>
 #include <cmath>
 #include <string.h>
@@ -627,8 +627,8 @@ struct PoPieces {
     StagePiece<hvo_keypoint> kp_un; StagePiece<hvo_line3d> l3d;
 };
 
-// One pinned staging block of the context (grow-only, hvo_stage_host) holds the upload and receives the download at the arena's own offsets;
-// the device side is the context's call arena: nothing is allocated by a call once both have grown.
+// A staged call (staged_call.hpp): the context's pinned block holds the upload and receives the download, the device side is the context's
+// call arena: nothing is allocated by a call once both have grown.
 int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_plane_params *pp,
            int n, const hvo_pose_problem *prob, const FrameView *fr, hvo_pose_result *res, const hvo_pose_flags *flags, std::string *err)
 {
@@ -666,9 +666,9 @@ int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_p
     }
     const auto results = C.take<hvo_pose_result>((size_t)n);
     const size_t total = C.mark();
-    char *d = (char *)hvo_call_arena(ctx, total);
-    char *h = (char *)hvo_stage_host(ctx, total);
-    if (!d || !h) { *err = "pose optimisation: scratch"; return HVO_ERR_HIP; }
+    StagedCall sc(ctx, st, "pose optimisation: ", err); int rc;
+    if ((rc = sc.begin(total, up, total - down0, false))) return rc;     // every piece is copied whole: nothing relies on zero padding
+    char *const d = sc.d, *const h = sc.h;
     for (int f = 0; f < n; f++) {
         const hvo_pose_problem &p = prob[f];
         const PoPieces &L = pieces[f];
@@ -717,23 +717,19 @@ int po_run(hvo_ctx *ctx, hipStream_t st, const hvo_camera *cam, const hvo_pose_p
     A.d_mono = (double)(float)sqrt(5.991); A.d_stereo = (double)(float)sqrt(7.815); A.d_line = (double)(float)sqrt(3.84);     // Optimizer.cc:631-633
     A.d_plane = (double)(float)sqrt(pp->chi); A.d_vpl = (double)(float)sqrt(pp->vp_chi);                                      // :963, :966
     frame_level_sigma2(ctx, nullptr, A.inv_level_sigma2);
-#define PO_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *err = std::string(#call) + ": " + hipGetErrorString(e_); return HVO_ERR_HIP; } } while (0)
-    if (!ctx->po_ev[0]) { PO_HIP(hipEventCreate(&ctx->po_ev[0])); PO_HIP(hipEventCreate(&ctx->po_ev[1])); }
-    PO_HIP(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, st));
-    PO_HIP(hipEventRecord(ctx->po_ev[0], st));
+    if ((rc = sc.up(0, up))) return rc;
+    sc.tick();
     hipLaunchKernelGGL(k_pose_opt, dim3(n), dim3(PO_THREADS), 0, st, A);
-    PO_HIP(hipGetLastError());
-    PO_HIP(hipEventRecord(ctx->po_ev[1], st));
-    PO_HIP(hipMemcpyAsync(h + down0, d + down0, total - down0, hipMemcpyDeviceToHost, st));
-    PO_HIP(hipStreamSynchronize(st));
-    PO_HIP(hipEventElapsedTime(&ctx->po_ms, ctx->po_ev[0], ctx->po_ev[1]));
-#undef PO_HIP
-    memcpy(res, results.host(h), results.bytes());
+    sc.tick();
+    StageDown b;
+    if ((rc = sc.down(down0, total, &b))) return rc;
+    ctx->po_ms = sc.ms[0];
+    memcpy(res, results.down(b), results.bytes());
     // the reference writes a flag only where there is a correspondence (Optimizer.cc:650, :757, :976): the caller's other entries stay
     for (int f = 0; flags && f < n; f++) {
         const hvo_pose_problem &p = prob[f];
         const hvo_pose_flags &G = flags[f];
-        const uint8_t *o_pt = pieces[f].pt_out.host(h), *o_ln = pieces[f].ln_out.host(h), *o_vp = pieces[f].vp_out.host(h), *o_pl = pieces[f].pl_out.host(h);
+        const uint8_t *o_pt = pieces[f].pt_out.down(b), *o_ln = pieces[f].ln_out.down(b), *o_vp = pieces[f].vp_out.down(b), *o_pl = pieces[f].pl_out.down(b);
         for (int i = 0; G.pt_outlier && i < p.n_points; i++) if (p.pt_has[i]) G.pt_outlier[i] = o_pt[i];
         for (int i = 0; G.ln_outlier && i < p.n_lines; i++) if (p.ln_has[i]) G.ln_outlier[i] = o_ln[i];
         for (int i = 0; G.vp_outlier && i < p.n_lines; i++) G.vp_outlier[i] = o_vp[i];

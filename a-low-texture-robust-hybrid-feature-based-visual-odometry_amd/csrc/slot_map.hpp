@@ -40,13 +40,13 @@ struct hvo_slot_map {
     uint8_t *d_flags() const { return (uint8_t *)arr.back().d; }
 };
 
-// the resident point map (local_points.hip owns its calls; fuse.hip reads its arrays in place, map_refresh.inc rewrites them)
+// the resident point map (local_points.hip owns its calls; fuse.hip reads its arrays in place, map_refresh.hip rewrites them)
 struct hvo_point_map : hvo_slot_map {
     hvo_point_map() : hvo_slot_map("point map", "HVO_POINT_MAP_MAX_SLOTS", HVO_POINT_MAP_MAX_SLOTS, { { 4, 3 }, { 4, 3 }, { 4, 1 }, { 4, 1 }, { 32, 1 }, { 1, 1, SM_BAD } }) {}
     enum { POS, NRM, MAXD, MIND, DESC };                         // pos, nrm, maxd, mind: floats; desc: 32 bytes packed; then the flags
 };
 
-// the resident line map (local_lines.hip owns its calls; map_refresh.inc rewrites its arrays in place)
+// the resident line map (local_lines.hip owns its calls; map_refresh.hip rewrites its arrays in place)
 struct hvo_line_map : hvo_slot_map {
     hvo_line_map() : hvo_slot_map("line map", "HVO_LINE_MAP_MAX_SLOTS", HVO_LINE_MAP_MAX_SLOTS, { { 8, 6 }, { 8, 3 }, { 8, 3 }, { 4, 1 }, { 4, 1 }, { 32, 1 }, { 1, 1, SM_BAD } }) {}
     enum { POS, WVEC, NRM, MAXD, MIND, DESC };                   // pos, wvec, nrm: doubles; maxd, mind: floats; desc: 32 bytes packed; then the flags

@@ -1,5 +1,5 @@
-// triangulate4.inc -- the float / double readings that the two triangulating calls share (included by new_points.hip and, through
-// line_triang.inc, by match.hip): the 3-term sums, cv::norm, OpenCV's closed 3 x 3 inverse, the float 3 x 3 product and the 4 x 4
+// triangulate4.inc -- the float / double readings that the two triangulating calls share (included by new_points.hip, line_triang.hip
+// and, for cv::norm, map_refresh.hip): the 3-term sums, cv::norm, OpenCV's closed 3 x 3 inverse, the float 3 x 3 product and the 4 x 4
 // cv::SVD::compute of a linear triangulation.  The readings themselves are stated at the head of new_points.hip; tests/new_points_ref.py is
 // their definition.  Only + - * / sqrt in the written order: the including file is compiled with -ffp-contract=off.
 #pragma once

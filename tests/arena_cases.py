@@ -1,4 +1,4 @@
-"""One entry per entry point that stages through the context's call arena (hvo_call_arena, csrc/tail.hip) or through a slot map's call
+"""One entry per entry point that stages through the context's call arena (hvo_call_arena, csrc/arena.hip) or through a slot map's call
 scratch (hvo_slot_map::d_a / d_b, csrc/slot_map.hpp).  tests/test_call_arena.py counts the call sites in csrc/*.hip against the sites the
 cases claim and asserts on the CPU that no input is vacuous; tests/test_call_arena_gpu.py runs every case on a dirty arena, on its own
 leftovers, on the other cases' leftovers and across a regrowth.
@@ -21,9 +21,12 @@ import numpy as np
 import bow_ref
 import fuse_ref
 import kf_search_ref
+import line_fuse_ref
 import line_map_ref
 import line_opt_ref
 import manhattan_ref
+import map_refresh_ref
+import new_lines_ref
 import new_points_ref
 import pnp_ref
 import point_map_ref as pm
@@ -599,6 +602,115 @@ case(name="search_local_lines", sites=[("api.hip", "hvo_search_local_lines"), ("
      want=lambda e, i: line_map_ref.search_local_lines(i["M"], LCAM, i["T"], line_map_ref.BOUNDS, line_map_ref.LOG_SF, 5.0, 0.95, i["kl"], i["fn"], i["l3"], i["ld"],
                                                        i["cs"], i["ci"], i["held"], i["extra"]),
      check=_ll_check, vacuous=lambda e, i, w: _true(w["n_matches"] > 2 and w["n_in_view"] > 20 and (i["l3"]["good"] == 1).sum() >= 5))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the line calls and the map refresh
+# S stays below one block of 256 with ragged counts; L crosses the 256 boundaries (an entry block, an LDS chunk of LF_CHUNK records, a wave's
+# four rows per lane).  The seeds are chosen so that the vacuity conditions hold; they are no part of them.
+def _nl_build(e, size):
+    n, poses, cuts = (40, new_lines_ref.SCENE_POSES[:2], (33, 40)) if size == "S" else (300, new_lines_ref.SCENE_POSES[:3], (300, 257, 190))
+    cur, kfs = new_lines_ref.random_scene(n=n, seed=35, poses=poses)
+    return dict(cur=cur, kfs=[new_lines_ref.cut(k, m) for k, m in zip(kfs, cuts)])
+
+
+def _nl_check(e, g, w):
+    import test_new_lines_gpu
+    test_new_lines_gpu.same(g, w)
+
+
+def _nl_vac(e, i, w):
+    """every neighbour is searched, and every pair creates a line and rejects a triple it evaluated (an outcome past 'no match on a side')"""
+    m, p, s = w
+    assert len(p) == len(i["kfs"]) * (len(i["kfs"]) - 1) // 2 and all(x["gate"] == 0 for x in m)
+    for x in p:
+        assert x["n_created"] >= 1 and (np.asarray(x["outcome"]) > new_lines_ref.NO_MATCH).any(), np.unique(x["outcome"])
+
+
+case(name="create_new_map_lines", sites=[("line_triang.hip", "nl_run")], build=_nl_build,
+     run=lambda e, c, i, o: c.create_new_map_lines(i["cur"], i["kfs"]), want=lambda e, i: new_lines_ref.full(i["cur"], i["kfs"]), check=_nl_check, vacuous=_nl_vac)
+
+
+def _lf_build(e, size):
+    if size == "S":
+        kfs, mp = line_fuse_ref.random_scene(e.hvo.KEYLINE_DT, n_kf=2, n_lines=70, n=37, seed=83)
+        kfs = [kfs[0], line_fuse_ref.cut(kfs[1], 3)]
+    else:
+        kfs, mp = line_fuse_ref.random_scene(e.hvo.KEYLINE_DT, n_kf=3, n_lines=300, n=300, seed=84)
+        kfs = [kfs[0], line_fuse_ref.cut(kfs[1], 257), line_fuse_ref.cut(kfs[2], 130)]
+    return dict(kfs=kfs, mp=mp)
+
+
+def _lf_want(e, i):
+    return [line_fuse_ref.fuse(kf, i["mp"]) for kf in i["kfs"]]
+
+
+def _lf_check(e, g, w):
+    import test_line_fuse_gpu
+    test_line_fuse_gpu.same(g, w)
+
+
+def _lf_vac(e, i, w):
+    """every key frame fuses an entry and rejects one: at a gate, and among the searched"""
+    for x in w:
+        assert x["n_fused"] >= 1 and (x["gate"] != 0).any() and x["n_searched"] > x["n_fused"], (x["n_fused"], x["n_searched"])
+
+
+case(name="fuse_lines", sites=[("line_fuse.hip", "lf_run")], build=_lf_build,
+     run=lambda e, c, i, o: c.fuse_lines(i["kfs"], i["mp"], n_levels=3), want=_lf_want, check=_lf_check, vacuous=_lf_vac)
+
+
+def _lfs_build(e, size):
+    i = _lf_build(e, size)
+    n = len(i["mp"]["pos"])
+    i["slots"] = np.random.RandomState(9).permutation(n + 5)[:n].astype(np.int32)             # entry k lives in slot slots[k]; five slots nobody names
+    return i
+
+
+def _lfs_open(e, i):
+    mp, sl = i["mp"], i["slots"]; n = len(sl) + 5
+    pos, nrm, mx, mn, desc = np.zeros((n, 6)), np.zeros((n, 3)), np.ones(n, F32), np.ones(n, F32), np.zeros((n, 32), np.uint8)
+    pos[sl] = mp["pos"]; nrm[sl] = mp["normal"]; mx[sl] = mp["max_distance"]; mn[sl] = mp["min_distance"]; desc[sl] = mp["desc"]
+    m = e.hvo.LineMap(slots=16)
+    m.set_many(0, pos, pos[:, 3:] - pos[:, :3], nrm, mx, mn, desc)
+    return dict(map=m)
+
+
+case(name="fuse_lines_slots", sites=[("line_fuse.hip", "lf_run")], build=_lfs_build, open=_lfs_open,
+     run=lambda e, c, i, o: c.fuse_lines_slots(o["map"], i["slots"], i["kfs"], n_levels=3), want=_lf_want, check=_lf_check, vacuous=_lf_vac)
+
+
+def _mr_build(line):
+    def build(e, size):
+        rng = np.random.RandomState(91 if line else 90)
+        if size == "S":
+            counts = rng.randint(0, 6, 33)                                # at most 5 observations
+        else:
+            counts = rng.randint(0, 12, 300); counts[77] = 256            # one feature at the limit: four rows per lane
+        counts[:12] = np.maximum(counts[:12], 2)                          # the features plant_statuses works on have observers
+        obs = map_refresh_ref.plant_statuses(map_refresh_ref.make_obs(counts, rng, bad_rate=0.15), rng)
+        return dict(pos=map_refresh_ref.line_positions(len(counts), rng) if line else map_refresh_ref.point_positions(len(counts), rng), obs=obs)
+    return build
+
+
+def _mr_check(line):
+    def check(e, g, w):
+        import test_map_refresh_gpu
+        test_map_refresh_gpu.same(g, w, line)
+    return check
+
+
+def _mr_vac(e, i, w):
+    assert len(set(w["status"].tolist())) >= 3 and (w["status"] == 0).sum() > len(w["status"]) // 2, np.unique(w["status"])
+    assert np.diff(i["obs"]["obs_start"]).max() == (256 if len(w["status"]) > 256 else 5)
+
+
+case(name="refresh_map_points", sites=[("map_refresh.hip", "mr_run")], build=_mr_build(False),
+     run=lambda e, c, i, o: c.refresh_map_points(i["pos"], i["obs"]), want=lambda e, i: map_refresh_ref.refresh_points(i["pos"], i["obs"]),
+     check=_mr_check(False), vacuous=_mr_vac)
+
+case(name="refresh_map_lines", sites=[("map_refresh.hip", "mr_run")], build=_mr_build(True),
+     run=lambda e, c, i, o: c.refresh_map_lines(i["pos"], i["obs"]), want=lambda e, i: map_refresh_ref.refresh_lines(i["pos"], i["obs"]),
+     check=_mr_check(True), vacuous=_mr_vac)
 
 BY_NAME = {c.name: c for c in CASES}
 _inputs = {}

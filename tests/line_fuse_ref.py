@@ -4,7 +4,7 @@ infrastructure only, and the DEFINITION the device is compared with: numpy float
 of the reference, the loops sequential: per entry, per key line, with a real vIndices list from a real GetLinesInArea (it normalises every key
 line's direction again for every entry; the device forms it once per key frame).
 
-The readings (csrc/line_fuse.inc, include/hvo.h and DESIGN.md section 7 state the same):
+The readings (csrc/line_fuse.hip, include/hvo.h and DESIGN.md section 7 state the same):
   1. Which descriptors.  The text compares the map line's LBD descriptor with pKF->mDescriptors.row(idx): ORB rows under a line index.  Here
      kf["desc_rows"] are "the rows the candidates are compared with": mLineDescriptors (intended) or mDescriptors (as written).  A candidate
      idx >= len(desc_rows) is not compared.  No flag.

@@ -1,6 +1,6 @@
 """CPU restatement of MapPoint::ComputeDistinctiveDescriptors + MapPoint::UpdateNormalAndDepth (reference src/MapPoint.cc:240-305, 328-369) and
 MapLine::ComputeDistinctiveDescriptors + MapLine::UpdateAverageDir (src/MapLine.cpp:331-396, 404-455).  Test infrastructure only, and THE
-DEFINITION of the readings csrc/map_refresh.inc states at its head: Python floats are IEEE doubles, f32() rounds to float (a double result of
+DEFINITION of the readings csrc/map_refresh.hip states at its head: Python floats are IEEE doubles, f32() rounds to float (a double result of
 + - * / sqrt of two floats rounds to the same float as the float operation: 53 >= 2 * 24 + 2), one step per step of the reference.  The
 descriptor half builds the real N x N matrix, sorts every row and indexes it as written.
 

@@ -1,6 +1,6 @@
 """CPU restatement of LocalMapping::CreateNewMapLinesConstraint (reference src/LocalMapping.cc:1064-1565) with
 LSDmatcher::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, true) (src/LSDmatcher.cpp:1195-1231), LSDmatcher::FrameBFMatch (:942-966) and
-LSDmatcher::lineDescriptorMAD (:1110-1135).  Test infrastructure only, and THE DEFINITION of the readings csrc/line_triang.inc states at its
+LSDmatcher::lineDescriptorMAD (:1110-1135).  Test infrastructure only, and THE DEFINITION of the readings csrc/line_triang.hip states at its
 head.  Python floats are IEEE doubles, f32() rounds to float (a double result of + - * / sqrt of two floats rounds to the same float as the
 float operation), one step per step of the reference.  The readings of tests/new_points_ref.py are reused as they stand: dot3f, dotd, normd,
 inv3, mul3, pose and the Jacobi reading svd4_last of cv::SVD::compute.

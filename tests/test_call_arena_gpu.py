@@ -1,4 +1,4 @@
-"""Every entry point that stages through the context's call arena (hvo_call_arena, csrc/tail.hip) or a slot map's call scratch, run on an
+"""Every entry point that stages through the context's call arena (hvo_call_arena, csrc/arena.hip) or a slot map's call scratch, run on an
 arena whose contents the test controls.  The modules' own GPU tests compare each call with its restatement but find the arena holding what
 hipMalloc returned or what the same call left there at a similar size; an application runs fuse after create_new_map_points after pnp on
 one context at changing sizes.  A kernel that reads a counter, a pass byte, a padded tail entry or a margin nobody initialised, or a
@@ -135,7 +135,15 @@ CAPACITY = {("search_by_projection_keyframe", "S"): 32768, ("search_by_projectio
             ("pnp_ransac", "S"): 16384, ("pnp_ransac", "L"): 81920,
             ("search_by_bow", "S"): 20480, ("search_by_bow", "L"): 139264,
             ("pose_optimize", "S"): 12288, ("pose_optimize", "L"): 102400,
-            ("line_struct_optimize", "S"): 32768, ("line_struct_optimize", "L"): 225280}
+            ("line_struct_optimize", "S"): 32768, ("line_struct_optimize", "L"): 225280,
+            # the three sites that staged through match.hip's own arena until they became staged calls: measured on the commit before (dd67507)
+            # as that arena's capacity after one call, (total + 4096) * 3 / 2, inverted to the layout's total (a multiple of 256 every time:
+            # 75776, 276992; 85504, 248064; 57856, 192768; 8704, 117248; 12544, 135424) and pinned as arena_capacity(total)
+            ("create_new_map_lines", "S"): 98304, ("create_new_map_lines", "L"): 348160,
+            ("fuse_lines", "S"): 110592, ("fuse_lines", "L"): 311296,
+            ("fuse_lines_slots", "S"): 73728, ("fuse_lines_slots", "L"): 241664,
+            ("refresh_map_points", "S"): 12288, ("refresh_map_points", "L"): 147456,
+            ("refresh_map_lines", "S"): 16384, ("refresh_map_lines", "L"): 172032}
 
 
 @pytest.mark.parametrize("name,size", sorted(CAPACITY))

@@ -1,6 +1,6 @@
-"""The kernels of csrc/line_fuse.inc keep everything in registers: no scratch, no spills, and k_lf_search's chunk of records is a small part
-of a compute unit's LDS, so the search's occupancy is not set by it.  The kernels share match.hip's translation unit, so the report is
-filtered by name.  The figures are the compiler's own remarks (tools/kernel_resources.py); no assembly is inspected and no GPU is needed."""
+"""The kernels of csrc/line_fuse.hip keep everything in registers: no scratch, no spills, and k_lf_search's chunk of records is a small part
+of a compute unit's LDS, so the search's occupancy is not set by it.  The report is filtered by name.
+The figures are the compiler's own remarks (tools/kernel_resources.py); no assembly is inspected and no GPU is needed."""
 import importlib.util
 import os
 
@@ -19,7 +19,7 @@ def res():
     spec.loader.exec_module(kr)
     if not kr.hipcc():
         pytest.skip("hipcc not found")
-    return {k: v for k, v in kr.resources(os.path.join(CSRC, "match.hip")).items() if k.startswith("k_lf_")}
+    return {k: v for k, v in kr.resources(os.path.join(CSRC, "line_fuse.hip")).items() if k.startswith("k_lf_")}
 
 
 def test_every_kernel_is_reported(res):

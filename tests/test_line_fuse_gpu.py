@@ -1,4 +1,4 @@
-"""LSDmatcher::Fuse on the GPU (csrc/line_fuse.inc) against tests/line_fuse_ref.py, the definition.  Every returned field is compared: integers
+"""LSDmatcher::Fuse on the GPU (csrc/line_fuse.hip) against tests/line_fuse_ref.py, the definition.  Every returned field is compared: integers
 exactly, floats by their bits (a NaN by being one).  tests/test_line_fuse.py asserts on the CPU that every crafted case says what it is
 meant to say and that the random scene is not vacuous.  The restatement runs the sequential loop per entry and per key line and normalises
 a key line's direction for every entry; the device forms it once per key frame and sweeps LDS chunks with 16 lanes per entry."""
@@ -250,31 +250,32 @@ def _leftovers(hvo, ctx):
 
 @pytest.mark.parametrize("fill", [0x00, 0xFF, 0x7F])
 def test_dirty_matching_arena(hvo, fill):
-    """the census's three conditions for this site: a pre-filled arena (proven by peeking), the same call's and other calls' leftovers, a regrowth"""
+    """the census's three conditions for this site: a pre-filled arena (proven by peeking), the same call's and other calls' leftovers (the
+    older matchers of match.hip among them, which share the context's call arena), a regrowth"""
     ctx = hvo.Context(max_batch=1)
     try:
         kfs, mp, want = scene(hvo)
         kS, mS = ref.random_scene(hvo.KEYLINE_DT, n_kf=1, n_lines=40, n=50, seed=61)
         wS = [ref.fuse(kf, mS) for kf in kS]
         assert wS[0]["n_fused"] > 10 and wS[0]["n_behind"] > 0
-        cap = ctx.debug_match_arena(fill, 60000)
-        assert cap >= 60000 and (ctx.debug_match_arena_peek(0, cap) == fill).all()
+        cap = ctx.debug_call_arena(fill, 60000)
+        assert cap >= 60000 and (ctx.debug_call_arena_peek(0, cap) == fill).all()
         first = call(ctx, kS, mS)
         same(first, wS, "S on a filled arena")
-        assert ctx.debug_match_arena(None) == cap                      # S fits: no regrowth so far
+        assert ctx.debug_call_arena(None) == cap                      # S fits: no regrowth so far
         for k in range(2):
             identical(call(ctx, kS, mS), first, "S again")
-        ctx.debug_match_arena(fill)
+        ctx.debug_call_arena(fill)
         L = call(ctx, kfs, mp)                                     # grows the arena
         same(L, want[ref.CLAMPED], "L")
-        cap2 = ctx.debug_match_arena(None)
+        cap2 = ctx.debug_call_arena(None)
         assert cap2 > cap
         identical(call(ctx, kS, mS), first, "S after L")
         identical(call(ctx, kfs, mp), L, "L after S")
         _leftovers(hvo, ctx)
         identical(call(ctx, kS, mS), first, "S after other calls")
-        ctx.debug_match_arena(fill)
-        assert (ctx.debug_match_arena_peek(cap2 - 4096, 4096) == fill).all()
+        ctx.debug_call_arena(fill)
+        assert (ctx.debug_call_arena_peek(cap2 - 4096, 4096) == fill).all()
         identical(call(ctx, kS, mS), first, "S on the regrown, filled arena")
     finally:
         ctx.close()

@@ -1,6 +1,6 @@
-"""The two kernels of csrc/map_refresh.inc keep everything in registers and LDS: no scratch, no spills.  Each lane holds its row's descriptor
+"""The two kernels of csrc/map_refresh.hip keep everything in registers and LDS: no scratch, no spills.  Each lane holds its row's descriptor
 (eight words) across the nine bisection steps, and the line kernel its double sums beside them; this test is what notices if that stops
-fitting.  The kernels share match.hip's translation unit, so the report is filtered by name.  The figures are the compiler's own remarks
+fitting.  The report is filtered by name.  The figures are the compiler's own remarks
 (tools/kernel_resources.py); no assembly is inspected and no GPU is needed."""
 import importlib.util
 import os
@@ -20,7 +20,7 @@ def res():
     spec.loader.exec_module(kr)
     if not kr.hipcc():
         pytest.skip("hipcc not found")
-    return {k: v for k, v in kr.resources(os.path.join(CSRC, "match.hip")).items() if k.startswith("k_mr_")}
+    return {k: v for k, v in kr.resources(os.path.join(CSRC, "map_refresh.hip")).items() if k.startswith("k_mr_")}
 
 
 def test_every_kernel_is_reported(res):

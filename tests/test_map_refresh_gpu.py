@@ -1,4 +1,4 @@
-"""MapPoint / MapLine ComputeDistinctiveDescriptors + UpdateNormalAndDepth / UpdateAverageDir on the GPU (csrc/map_refresh.inc) against
+"""MapPoint / MapLine ComputeDistinctiveDescriptors + UpdateNormalAndDepth / UpdateAverageDir on the GPU (csrc/map_refresh.hip) against
 tests/map_refresh_ref.py.  Integers are compared exactly, floats by their bits (a NaN by being one); an entry the status says is not written
 must hold what the caller put there.  tests/test_map_refresh.py asserts on the CPU that the crafted cases say what they are meant to say and
 that the random scenes (map_refresh_ref.SCENE_*) meet every status code and at least 20 ties."""
@@ -281,8 +281,8 @@ def test_dirty_arena(hvo, line):
     first = run(hvo, line, pos, obs)
     same(first, want_of(line, pos, obs), line, "dirty arena: the case itself")
     for fill in (0xFF, 0x5A):
-        cap = c.debug_match_arena(fill=fill, min_bytes=1 << 20)
-        assert cap >= 1 << 20 and (c.debug_match_arena_peek(cap - 64, 64) == fill).all()
+        cap = c.debug_call_arena(fill=fill, min_bytes=1 << 20)
+        assert cap >= 1 << 20 and (c.debug_call_arena_peek(cap - 64, 64) == fill).all()
         identical(run(hvo, line, pos, obs), first, line, "fill %#x" % fill)
     spos, sobs, swant = scene(not line)
     run(hvo, not line, spos, sobs)                                           # another call's leftovers, larger than this one

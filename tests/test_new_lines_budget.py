@@ -1,7 +1,7 @@
-"""The kernels of csrc/line_triang.inc keep everything in registers: no scratch, no spills.  k_nl_triangulate holds two 4 x 4 double Jacobi
+"""The kernels of csrc/line_triang.hip keep everything in registers: no scratch, no spills.  k_nl_triangulate holds two 4 x 4 double Jacobi
 solves and three key-frame records per lane; its gates are evaluated without early exits so that no saved exec mask is spilled, and this
-test is what notices if that changes.  The kernels share match.hip's translation unit, so the report is filtered by name.  The figures are
-the compiler's own remarks (tools/kernel_resources.py); no assembly is inspected and no GPU is needed."""
+test is what notices if that changes.  The report is filtered by name.  The figures are the compiler's own remarks
+(tools/kernel_resources.py); no assembly is inspected and no GPU is needed."""
 import importlib.util
 import os
 
@@ -19,7 +19,7 @@ def res():
     spec.loader.exec_module(kr)
     if not kr.hipcc():
         pytest.skip("hipcc not found")
-    return {k: v for k, v in kr.resources(os.path.join(CSRC, "match.hip")).items() if k.startswith("k_nl_")}
+    return {k: v for k, v in kr.resources(os.path.join(CSRC, "line_triang.hip")).items() if k.startswith("k_nl_")}
 
 
 def test_every_kernel_is_reported(res):

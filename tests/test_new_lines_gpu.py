@@ -1,4 +1,4 @@
-"""LocalMapping::CreateNewMapLinesConstraint on the GPU (csrc/line_triang.inc) against tests/new_lines_ref.py.  Integers are compared exactly,
+"""LocalMapping::CreateNewMapLinesConstraint on the GPU (csrc/line_triang.hip) against tests/new_lines_ref.py.  Integers are compared exactly,
 floats by their bits (a NaN by being one).  tests/test_new_lines.py asserts on the CPU that every crafted case says what it is meant to say
 and that the random scene (seed new_lines_ref.SCENE_SEED) is not vacuous.  The restatement runs the sequential loops; the device evaluates
 independent triples and resolves."""
@@ -220,31 +220,32 @@ def _leftovers(hvo, ctx):
 
 @pytest.mark.parametrize("fill", [0x00, 0xFF, 0x7F])
 def test_dirty_matching_arena(hvo, fill):
-    """the census's three conditions for this site: a pre-filled arena (proven by peeking), the same call's and other calls' leftovers, a regrowth"""
+    """the census's three conditions for this site: a pre-filled arena (proven by peeking), the same call's and other calls' leftovers (the
+    older matchers of match.hip among them, which share the context's call arena), a regrowth"""
     ctx = hvo.Context(max_batch=1)
     try:
         cur, kfs, want = scene()
         S = (ref.cut(cur, 50), [ref.cut(k, 60) for k in kfs[:3]])
         wS = ref.full(*S)
         assert wS[2]["n_new"] > 0
-        cap = ctx.debug_match_arena(fill, 120000)
-        assert cap >= 120000 and (ctx.debug_match_arena_peek(0, cap) == fill).all()
+        cap = ctx.debug_call_arena(fill, 120000)
+        assert cap >= 120000 and (ctx.debug_call_arena_peek(0, cap) == fill).all()
         first = ctx.create_new_map_lines(*S)
         same(first, wS, "S on a filled arena")
-        assert ctx.debug_match_arena(None) == cap                      # S fits: no regrowth so far
+        assert ctx.debug_call_arena(None) == cap                      # S fits: no regrowth so far
         for k in range(2):
             identical(ctx.create_new_map_lines(*S), first, "S again")
-        ctx.debug_match_arena(fill)
+        ctx.debug_call_arena(fill)
         L = ctx.create_new_map_lines(cur, kfs)                          # grows the arena
         same(L, want, "L")
-        cap2 = ctx.debug_match_arena(None)
+        cap2 = ctx.debug_call_arena(None)
         assert cap2 > cap
         identical(ctx.create_new_map_lines(*S), first, "S after L")
         identical(ctx.create_new_map_lines(cur, kfs), L, "L after S")
         _leftovers(hvo, ctx)
         identical(ctx.create_new_map_lines(*S), first, "S after other calls")
-        ctx.debug_match_arena(fill)
-        assert (ctx.debug_match_arena_peek(cap2 - 4096, 4096) == fill).all()
+        ctx.debug_call_arena(fill)
+        assert (ctx.debug_call_arena_peek(cap2 - 4096, 4096) == fill).all()
         identical(ctx.create_new_map_lines(*S), first, "S on the regrown, filled arena")
     finally:
         ctx.close()

@@ -1,7 +1,7 @@
 // line_fuse_host.cpp -- LSDmatcher::Fuse (reference src/LSDmatcher.cpp:1297-1434) with KeyFrame::GetLinesInArea (src/KeyFrame.cc:668-702) as a
 // plain single-thread host loop: one call per key frame, per entry a sweep over every key line with a real vIndices vector, each key line's
 // direction normalised again for every entry, as the reference does it.  The arithmetic and the three readings are those of
-// csrc/line_fuse.inc and tests/line_fuse_ref.py (no stop at an entry behind the camera: every entry is evaluated).  It is what
+// csrc/line_fuse.hip and tests/line_fuse_ref.py (no stop at an entry behind the camera: every entry is evaluated).  It is what
 // tools/line_fuse_timing.py puts beside the device call; it does not pay for cv::Mat temporaries, mutexes or the pointer walk.
 //
 //   line_fuse_host <case> <result> [reps]      prints the median wall ms of `reps` runs of all key frames

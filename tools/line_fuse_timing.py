@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times LSDmatcher::Fuse on the device (csrc/line_fuse.inc) for the two line calls of LocalMapping::SearchInNeighbors:
+"""Times LSDmatcher::Fuse on the device (csrc/line_fuse.hip) for the two line calls of LocalMapping::SearchInNeighbors:
 
   arrays         hvo_fuse_lines: 200 entries (one shared map side) x 30 key frames of 200 lines, on host arrays
   slots          hvo_fuse_lines_slots: the same, the map side as 200 slots of a resident line map

@@ -1,6 +1,6 @@
 // map_refresh_host.cpp -- MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (reference src/MapPoint.cc:240-305, 328-369) and
 // MapLine::ComputeDistinctiveDescriptors + UpdateAverageDir (src/MapLine.cpp:331-396, 404-455) as a plain single-thread host program: the loops
-// AS WRITTEN (the N x N matrix, every row copied and sorted, the sums in list order) with the readings of csrc/map_refresh.inc.
+// AS WRITTEN (the N x N matrix, every row copied and sorted, the sums in list order) with the readings of csrc/map_refresh.hip.
 // tools/map_refresh_timing.py times it beside the device call; tests/test_map_refresh.py compares its answers with the restatement.
 //
 //   map_refresh_host <case file> <result file> <reps>        prints the median wall ms of the sweep over <reps> runs

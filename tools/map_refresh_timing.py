@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the map refresh on the device (csrc/map_refresh.inc): MapPoint / MapLine ComputeDistinctiveDescriptors + UpdateNormalAndDepth /
+"""Times the map refresh on the device (csrc/map_refresh.hip): MapPoint / MapLine ComputeDistinctiveDescriptors + UpdateNormalAndDepth /
 UpdateAverageDir for every feature of a key frame in one call.
 
   arrays   hvo_refresh_map_points / hvo_refresh_map_lines: the positions go up with the observations

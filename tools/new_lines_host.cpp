@@ -1,6 +1,6 @@
 // new_lines_host.cpp -- LocalMapping::CreateNewMapLinesConstraint (reference src/LocalMapping.cc:1064-1565) as a plain single-thread host
 // program: the SEQUENTIAL loops as written (the searches neighbour by neighbour, the compacted list of match vectors, key frames by list
-// position or aligned, every triple in (a, b, ikl) order under the occupancy as it stands) with the readings of csrc/line_triang.inc, whose
+// position or aligned, every triple in (a, b, ikl) order under the occupancy as it stands) with the readings of csrc/line_triang.hip, whose
 // shared arithmetic (csrc/triangulate4.inc) it includes.  tools/new_lines_timing.py times it beside the device call and compares the answers.
 //
 //   new_lines_host <case file> <result file> <reps>        prints the median wall ms of the loop over <reps> runs

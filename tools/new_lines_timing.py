@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times LocalMapping::CreateNewMapLinesConstraint on the device (csrc/line_triang.inc):
+"""Times LocalMapping::CreateNewMapLinesConstraint on the device (csrc/line_triang.hip):
 
   stream   hvo_stream_create_new_map_lines: one resident 640 x 480 frame as the current key frame, 5 and 10 neighbours that see its lines
   arrays   hvo_create_new_map_lines: the same frame downloaded and the same neighbours, everything on host arrays (the same work)
