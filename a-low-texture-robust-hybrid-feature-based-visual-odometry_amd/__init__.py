@@ -98,6 +98,7 @@ EXPORTS = [
     "hvo_create_new_map_points", "hvo_stream_create_new_map_points", "hvo_create_new_map_lines", "hvo_stream_create_new_map_lines",
     "hvo_refresh_map_points", "hvo_refresh_map_lines", "hvo_point_map_refresh", "hvo_line_map_refresh",
     "hvo_update_map_planes", "hvo_stream_update_map_planes", "hvo_plane_map_get_points", "hvo_plane_update_transform",
+    "hvo_local_ba_create", "hvo_local_ba_destroy", "hvo_local_ba_last_error", "hvo_local_ba_last_ms", "hvo_local_ba_last_profile", "hvo_local_ba_default_params", "hvo_local_ba_optimize",
 ]
 
 
@@ -451,6 +452,40 @@ KFDB_RELOC, KFDB_LOOP = 0, 1
 class KeyframeDbDesc(C.Structure):
     _fields_ = [("n_slots", C.c_int32), ("n_live", C.c_int32), ("scoring", C.c_int32), ("device", C.c_int32),
                 ("pooled_words", C.c_int64), ("pool_capacity", C.c_int64), ("next_sequence", C.c_int64)]
+
+
+class LocalBAParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32 * 2), ("max_trials", C.c_int32), ("stop_at_poll", C.c_int32), ("huber_delta", C.c_double * 3),
+                ("chi2_gate", C.c_double * 3), ("inv_sigma", C.c_double * 3)]
+
+
+LOCAL_BA_GRAPH_ARRAYS = (("Tcw", np.float32), ("fixed", np.uint8), ("cam", np.float32), ("pt_pos", np.float32), ("pt_obs_start", np.int32),
+                         ("pt_obs_kf", np.int32), ("pt_obs_uv", np.float32), ("pt_obs_inv_sigma2", np.float32), ("ln_pos", np.float64),
+                         ("ln_manh_idx", np.int32), ("ln_obs_start", np.int32), ("ln_obs_kf", np.int32), ("ln_obs_fn", np.float64),
+                         ("par_start", np.int32), ("par_kf", np.int32), ("par_idx", np.int32), ("par_fn", np.float64), ("par_map_size", np.int32),
+                         ("perp_start", np.int32), ("perp_kf", np.int32), ("perp_idx", np.int32), ("perp_fn", np.float64), ("perp_map_size", np.int32),
+                         ("manh_axis", np.float64))
+
+
+class LocalBAGraph(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("n_points", C.c_int32), ("n_lines", C.c_int32), ("manh_available", C.c_int32)] + \
+               [(n, C.c_void_p) for n, _ in LOCAL_BA_GRAPH_ARRAYS]
+
+
+LOCAL_BA_RESULT_ARRAYS = ("Tcw_f", "Tcw_d", "pt_f", "pt_d", "ln_f", "ln_d", "pt_erase", "ln_erase", "manh_erase", "par_erase", "perp_erase",
+                          "par_made", "perp_made", "line_made")
+
+
+class LocalBAResult(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in LOCAL_BA_RESULT_ARRAYS] + \
+               [("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2), ("lam", C.c_double * 2), ("chi2", C.c_double * 2),
+                ("n_free_kf", C.c_int32), ("n_pt_edges", C.c_int32), ("n_line_obs", C.c_int32), ("n_manh_edges", C.c_int32),
+                ("n_par_edges", C.c_int32), ("n_perp_edges", C.c_int32), ("n_lines_made", C.c_int32), ("rounds", C.c_int32),
+                ("stopped_at", C.c_int32), ("status", C.c_int32)]
+
+
+LBA_OPTIMISED, LBA_NOTHING, LBA_STOPPED = 0, 1, 2
+LBA_LIMITS = dict(free_kf=64, kf=1024, points=65536, lines=16384, pt_obs=1 << 20, ln_obs=1 << 18, struct=1 << 18)
 
 
 class KfdbParams(C.Structure):
@@ -1372,6 +1407,13 @@ def lib():
         L.hvo_stream_update_map_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PlaneUpdate), C.POINTER(PlaneUpdateResult)]
         L.hvo_plane_map_get_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.hvo_plane_update_transform.argtypes = [C.c_void_p, C.c_void_p]
+        L.hvo_local_ba_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.hvo_local_ba_destroy.argtypes = [C.c_void_p]; L.hvo_local_ba_destroy.restype = None
+        L.hvo_local_ba_last_error.argtypes = [C.c_void_p]; L.hvo_local_ba_last_error.restype = C.c_char_p
+        L.hvo_local_ba_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.hvo_local_ba_last_profile.argtypes = [C.c_void_p, C.POINTER(C.c_float * 4), C.POINTER(C.c_int32 * 2)]
+        L.hvo_local_ba_default_params.argtypes = [C.POINTER(LocalBAParams)]; L.hvo_local_ba_default_params.restype = None
+        L.hvo_local_ba_optimize.argtypes = [C.c_void_p, C.POINTER(LocalBAParams), C.POINTER(LocalBAGraph), C.c_void_p, C.POINTER(LocalBAResult)]
         L.hvo_line_map_create.argtypes = [C.c_int, C.c_int]; L.hvo_line_map_create.restype = C.c_void_p
         L.hvo_line_map_destroy.argtypes = [C.c_void_p]; L.hvo_line_map_destroy.restype = None
         L.hvo_line_map_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int]
@@ -1567,6 +1609,139 @@ def default_params(**kw):
             raise TypeError("unknown hvo_params field " + k)
         setattr(p, k, v)
     return p
+
+
+def local_ba_graph_arrays(graph, limits=True):
+    """the graph dict of LocalBA.optimize as contiguous arrays of the C ABI's types, with the counts; refuses what can be refused without
+    a device (the limits of include/hvo.h) by raising HvoError(HVO_ERR_UNSUPPORTED) with the reason.  limits=False leaves the limits to
+    the library (tests of its own refusals)."""
+    a = {}
+    for name, dt in LOCAL_BA_GRAPH_ARRAYS:
+        v = graph.get(name)
+        a[name] = np.ascontiguousarray(np.zeros(0, dt) if v is None else v, dt)
+    n_kf = a["Tcw"].size // 12; n_pts = a["pt_pos"].size // 3; n_ln = a["ln_pos"].size // 6
+    if a["fixed"].size != n_kf or a["cam"].size != 4 * n_kf:
+        raise ValueError("fixed / cam do not match Tcw")
+    for start, n in (("pt_obs_start", n_pts), ("ln_obs_start", n_ln), ("par_start", n_ln), ("perp_start", n_ln)):
+        if a[start].size == 0 and n == 0:
+            a[start] = np.zeros(1, np.int32)
+        if a[start].size != n + 1:
+            raise ValueError(start + " needs one entry more than its landmarks")
+    for name in ("ln_manh_idx", "par_map_size", "perp_map_size"):
+        if a[name].size != n_ln:
+            raise ValueError(name + " needs one entry per line")
+    for kf, other, per in (("pt_obs_kf", ("pt_obs_uv", "pt_obs_inv_sigma2"), (2, 1)), ("ln_obs_kf", ("ln_obs_fn",), (3,)),
+                           ("par_kf", ("par_idx", "par_fn"), (1, 3)), ("perp_kf", ("perp_idx", "perp_fn"), (1, 3))):
+        start = {"pt_obs_kf": "pt_obs_start", "ln_obs_kf": "ln_obs_start", "par_kf": "par_start", "perp_kf": "perp_start"}[kf]
+        if a[kf].size != int(a[start][-1]) or any(a[o].size != k * a[kf].size for o, k in zip(other, per)):
+            raise ValueError(kf + " and its companions do not match " + start)
+    if int(graph.get("manh_available", 0)) and a["manh_axis"].size != 9:
+        raise ValueError("manh_axis must be 3 x 3")
+
+    def no(why):
+        raise HvoError(-4, "local_ba_optimize: " + why)
+    L = LBA_LIMITS
+    if not limits:
+        return a, n_kf, n_pts, n_ln
+    if n_kf > L["kf"]: no("more than 1024 key frames")
+    if n_pts > L["points"]: no("more than 65536 points")
+    if n_ln > L["lines"]: no("more than 16384 lines")
+    if a["pt_obs_kf"].size > L["pt_obs"]: no("more than 2^20 point observations")
+    if a["ln_obs_kf"].size > L["ln_obs"]: no("more than 2^18 line observations")
+    if a["par_kf"].size + a["perp_kf"].size > L["struct"]: no("more than 2^18 par plus perp entries")
+    if int((a["fixed"] == 0).sum()) > L["free_kf"]: no("more than 64 free key frames")
+    for kf in ("pt_obs_kf", "ln_obs_kf", "par_kf", "perp_kf"):
+        if a[kf].size and (int(a[kf].min()) < 0 or int(a[kf].max()) >= n_kf): no("a key-frame index outside the call's list")
+    for start, kf, what in (("pt_obs_start", "pt_obs_kf", "point"), ("ln_obs_start", "ln_obs_kf", "line")):
+        if a[kf].size:
+            owner = np.repeat(np.arange(a[start].size - 1, dtype=np.int64), np.diff(a[start]))
+            if np.unique(owner * max(n_kf, 1) + a[kf]).size != a[kf].size: no("a key frame observes one %s twice" % what)
+    return a, n_kf, n_pts, n_ln
+
+
+class LocalBA:
+    """hvo_local_ba: Optimizer::LocalMapOptimization on the device (reference src/Optimizer.cc:3014-3940).  The object owns a grow-only
+    workspace on its device; create it once beside the map and reuse it for every key frame.  Not thread-safe.
+
+    optimize(graph, params=None, stop=None) -> LocalBAOutput.  graph: a dict of the arrays of hvo_local_ba_graph (include/hvo.h;
+    key frame 0 is the current key frame, observations are CSR lists naming their observer by its index) plus manh_available; params: a
+    dict of changes to the defaults (iterations, max_trials, stop_at_poll, huber_delta, chi2_gate, inv_sigma); stop: None or a
+    ctypes.c_int the caller may set from another thread (mbAbortBA)."""
+
+    def __init__(self, device=0):
+        h = C.c_void_p()
+        rc = lib().hvo_local_ba_create(device, C.byref(h))
+        if rc != HVO_OK:
+            raise HvoError(rc, "hvo_local_ba_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().hvo_local_ba_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def last_error(self):
+        return lib().hvo_local_ba_last_error(self.h).decode()
+
+    def last_ms(self):
+        ms = C.c_float(0)
+        lib().hvo_local_ba_last_ms(self.h, C.byref(ms))
+        return ms.value
+
+    def last_profile(self):
+        """dict(linearise_ms, trials_ms, factor_ms, call_ms, linearisations, trials) of the last call (hvo_local_ba_last_profile)"""
+        ms = (C.c_float * 4)(); n = (C.c_int32 * 2)()
+        lib().hvo_local_ba_last_profile(self.h, C.byref(ms), C.byref(n))
+        return dict(linearise_ms=ms[0], trials_ms=ms[1], factor_ms=ms[2], call_ms=ms[3], linearisations=n[0], trials=n[1])
+
+    @staticmethod
+    def default_params():
+        p = LocalBAParams()
+        lib().hvo_local_ba_default_params(C.byref(p))
+        return p
+
+    def optimize(self, graph, params=None, stop=None, limits=True):
+        a, n_kf, n_pts, n_ln = local_ba_graph_arrays(graph, limits)
+        p = self.default_params()
+        for k, v in (params or {}).items():
+            if k in ("iterations", "huber_delta", "chi2_gate", "inv_sigma"):
+                for i, x in enumerate(v):
+                    getattr(p, k)[i] = x
+            else:
+                setattr(p, k, v)
+        G = LocalBAGraph(n_kf=n_kf, n_points=n_pts, n_lines=n_ln, manh_available=int(graph.get("manh_available", 0)))
+        for name, _ in LOCAL_BA_GRAPH_ARRAYS:
+            setattr(G, name, _p(a[name]) if a[name].size else None)
+        n_po, n_lo, n_pa, n_pe = a["pt_obs_kf"].size, a["ln_obs_kf"].size, a["par_kf"].size, a["perp_kf"].size
+        out = LocalBAOutput()
+        shapes = dict(Tcw_f=((n_kf, 3, 4), np.float32), Tcw_d=((n_kf, 3, 4), np.float64), pt_f=((n_pts, 3), np.float32), pt_d=((n_pts, 3), np.float64),
+                      ln_f=((n_ln, 6), np.float32), ln_d=((n_ln, 6), np.float64), pt_erase=((n_po,), np.uint8), ln_erase=((n_lo,), np.uint8),
+                      manh_erase=((n_ln,), np.uint8), par_erase=((n_pa,), np.uint8), perp_erase=((n_pe,), np.uint8), par_made=((n_pa,), np.uint8),
+                      perp_made=((n_pe,), np.uint8), line_made=((n_ln,), np.uint8))
+        R = LocalBAResult()
+        for name in LOCAL_BA_RESULT_ARRAYS:
+            shp, dt = shapes[name]
+            arr = np.full(shp, 0xEE, dt) if dt == np.uint8 else np.full(shp, np.nan, dt)       # a refusal leaves them as they are
+            setattr(out, name, arr)
+            setattr(R, name, _p(arr) if arr.size else None)
+        rc = lib().hvo_local_ba_optimize(self.h, C.byref(p), C.byref(G), C.byref(stop) if stop is not None else None, C.byref(R))
+        out.rc = rc
+        if rc != HVO_OK:
+            err = HvoError(rc, "local_ba_optimize: " + self.last_error())
+            err.output = out                                                  # the arrays as the library left them
+            raise err
+        for k in ("iterations", "trials", "lam", "chi2"):
+            setattr(out, k, list(getattr(R, k)))
+        for k in ("n_free_kf", "n_pt_edges", "n_line_obs", "n_manh_edges", "n_par_edges", "n_perp_edges", "n_lines_made", "rounds", "stopped_at", "status"):
+            setattr(out, k, getattr(R, k))
+        out.ms = self.last_ms()
+        return out
+
+
+class LocalBAOutput:
+    """what LocalBA.optimize returns: the arrays and fields of hvo_local_ba_result (lambda is `lam`) and `ms`"""
 
 
 class PlaneMap:

@@ -1667,6 +1667,113 @@ int hvo_refresh_map_lines(hvo_ctx *ctx, const hvo_mr_params *params, const hvo_m
 int hvo_point_map_refresh(hvo_ctx *ctx, hvo_point_map *m, const int32_t *slots, const hvo_mr_params *params, const hvo_mr_input *in, hvo_mr_point_out *out);
 int hvo_line_map_refresh(hvo_ctx *ctx, hvo_line_map *m, const int32_t *slots, const hvo_mr_params *params, const hvo_mr_input *in, hvo_mr_line_out *out);
 
+/* ---- Optimizer::LocalMapOptimization (reference src/Optimizer.cc:3014-3940, called at src/LocalMapping.cc:122; csrc/local_ba.hip) ----
+ * Local bundle adjustment over the covisibility window: one SE3 vertex per key frame (free unless `fixed`), one XYZ vertex per map point,
+ * a start and an end XYZ vertex per map line; EdgeSE3ProjectXYZ per point observation, two DistPt2Line2DMultiFrame per line observation,
+ * ParEptsNVector3DSingleFrame against the Manhattan axis, ParEptsNVector2DMultiFrame / PerpEptsNVector2DMultiFrame per parallel /
+ * perpendicular entry, all under Huber kernels; Levenberg with optimize(5), the classification of :3656-3743, optimize(10), and the
+ * erase tests of :3753-3847 as flags.  A line is ONE 6-dimensional landmark here: every landmark (3 x 3 or 6 x 6 block, plus lambda) is
+ * eliminated and the dense reduced system over the free key frames (at most 384 unknowns) is factored by LDL^T without pivoting -- the
+ * step g2o solves, with another rounding.  The Levenberg loop runs on the host over the launches; two calls on the same bytes return the
+ * same bytes (no floating-point atomic, every sum in a fixed order).
+ *
+ * The object owns a grow-only workspace (graph, per-edge blocks, reduced system, one pinned block) on its device; create it once beside
+ * the map and reuse it for every key frame.  Not thread-safe.
+ *
+ * Conventions.  Key frame 0 of the list is the CURRENT key frame (pKF); the local key frames come first, the outside observers after
+ * them with fixed = 1; a local key frame is fixed iff its mnId == 0.  Observations are CSR lists per point / per line (obs_start has
+ * n + 1 entries), each naming its observer by its index in the key-frame list; the caller leaves out bad key frames, bad points and bad
+ * lines.  par / perp entries are the (key frame, k) entries of GetParObservations() / GetPerpObservations() in map order with idx =
+ * observation.second[k] and linefn = that key frame's mvKeyLineFunctions[idx]; entries of key frames with mnId > maxKFid or isBad() are
+ * left out by the caller; par_map_size / perp_map_size are the maps' numbers of KEYS.  manh_axis is 3 x 3 row-major, column a - 1 =
+ * axis a.
+ *
+ * The readings taken (the restatement tests/local_ba_ref.py makes the same ones):
+ *  1. the END-point edge and the par / perp edges take fx fy cx cy of key frame 0, the start-point edge its observer's (:3459, :3518, :3579);
+ *  2. chi2() is read from the error an edge HOLDS: an edge put on level 1 after round 1 is never evaluated again and its erase test
+ *     reads round 1's last evaluation (the last trial, accepted or not); isDepthPositive() is evaluated at the final estimate;
+ *  3. the erase test of a line observation reads its START-point edge twice (:3772-3774); the classification between the rounds reads
+ *     start or end;
+ *  4. flags come back per observation; pairing an erased line observation with a key frame (vpLineEdgeKF holds two entries per
+ *     observation and is indexed by observation, :3782) is host logic (hvo::walkErased);
+ *  5. vpLineManhKF is never filled (:3800 reads past its end): manh_erase is a flag per line and the caller decides;
+ *  6. zero points or zero lines are ordinary inputs (the reference reads MapPointID[-1]);
+ *  7. a par / perp entry's key frame must be in the list: an index outside it is refused (the reference passes a null vertex);
+ *  8. isBad() is read as false throughout: the graph holds only non-bad elements.
+ * Also: SE3Quat::map is the quaternion's rotation matrix applied to the point; landmark blocks and the reduced system are inverted /
+ * factored by LDL^T without pivoting, "not positive" = a pivot <= 0 of the reduced system; every key frame's returned pose is its
+ * quaternion estimate written out (Converter::toCvMat), fixed ones included.
+ *
+ * Limits, refused whole with HVO_ERR_UNSUPPORTED, the reason in hvo_local_ba_last_error and NO output written: more than 64 free or
+ * 1024 key frames, 65536 points, 16384 lines, 2^20 point observations, 2^18 line observations, 2^18 par plus perp entries, a key-frame
+ * index out of range, a key frame observing one point or one line twice.  No free key frame or no edge at all: status
+ * HVO_LBA_NOTHING, outputs = inputs, no launch.  A landmark or key frame without active edges keeps its estimate. */
+typedef struct hvo_local_ba hvo_local_ba;
+#define HVO_LBA_MAX_FREE_KF   64
+#define HVO_LBA_MAX_KF        1024
+#define HVO_LBA_MAX_POINTS    65536
+#define HVO_LBA_MAX_LINES     16384
+#define HVO_LBA_MAX_PT_OBS    (1 << 20)
+#define HVO_LBA_MAX_LN_OBS    (1 << 18)
+#define HVO_LBA_MAX_STRUCT    (1 << 18)
+#define HVO_LBA_OPTIMISED 0       /* status: both rounds ran (or the stop flag ended them) */
+#define HVO_LBA_NOTHING   1       /*         no free key frame or no edge: outputs = inputs */
+#define HVO_LBA_STOPPED   2       /*         the stop flag was set at the test before the first round (:3641): outputs = inputs */
+typedef struct {
+    int32_t iterations[2];         /* optimize(5), optimize(10) */
+    int32_t max_trials;            /* 10: g2o's maxTrialsAfterFailure */
+    int32_t stop_at_poll;          /* -1: off; k: the k-th read of the stop flag (0-based) and every later one reads "stop" (tests) */
+    double huber_delta[3];         /* point, line end point, parallel / perpendicular / Manhattan: (float)sqrt(5.991), sqrt(3.84), sqrt(0.08) */
+    double chi2_gate[3];           /* 5.991, 3.84, 0.13 */
+    double inv_sigma[3];           /* line end points 0.3, Manhattan 0.3, structural 0.5 (+ map_size / 10) */
+} hvo_local_ba_params;
+typedef struct {
+    int32_t n_kf, n_points, n_lines, manh_available;
+    const float *Tcw;              /* n_kf x 12: rows 0..2 of GetPose() */
+    const uint8_t *fixed;          /* n_kf */
+    const float *cam;              /* n_kf x 4: fx fy cx cy */
+    const float *pt_pos;           /* n_points x 3 */
+    const int32_t *pt_obs_start;   /* n_points + 1 */
+    const int32_t *pt_obs_kf;
+    const float *pt_obs_uv;        /* x 2: mvKeysUn[idx].pt */
+    const float *pt_obs_inv_sigma2;
+    const double *ln_pos;          /* n_lines x 6 */
+    const int32_t *ln_manh_idx;    /* n_lines: GetManhIdx() */
+    const int32_t *ln_obs_start;   /* n_lines + 1 */
+    const int32_t *ln_obs_kf;
+    const double *ln_obs_fn;       /* x 3: mvKeyLineFunctions[idx] */
+    const int32_t *par_start, *par_kf, *par_idx; const double *par_fn; const int32_t *par_map_size;
+    const int32_t *perp_start, *perp_kf, *perp_idx; const double *perp_fn; const int32_t *perp_map_size;
+    const double *manh_axis;       /* 9, may be NULL when manh_available == 0 */
+} hvo_local_ba_graph;
+typedef struct {
+    float *Tcw_f; double *Tcw_d;   /* n_kf x 12 */
+    float *pt_f; double *pt_d;     /* n_points x 3 */
+    float *ln_f; double *ln_d;     /* n_lines x 6; SetWorldPos receives the float values (Converter::toCvMat) */
+    uint8_t *pt_erase, *ln_erase;  /* per point / line observation */
+    uint8_t *manh_erase;           /* per line */
+    uint8_t *par_erase, *perp_erase;   /* per entry */
+    uint8_t *par_made, *perp_made; /* per entry: 0 = no edge (idx < 0, linefn[0] == 0 or -1, a NaN, or the line was skipped) */
+    uint8_t *line_made;            /* per line: 0 = skipped whole (:3358-3366) */
+    int32_t iterations[2], trials[2];
+    double lambda[2], chi2[2];
+    int32_t n_free_kf, n_pt_edges, n_line_obs, n_manh_edges, n_par_edges, n_perp_edges, n_lines_made, rounds;
+    int32_t stopped_at;            /* index of the first poll that read "stop", or -1 */
+    int32_t status;                /* HVO_LBA_* */
+} hvo_local_ba_result;
+int hvo_local_ba_create(int device, hvo_local_ba **ba);
+void hvo_local_ba_destroy(hvo_local_ba *ba);
+const char *hvo_local_ba_last_error(const hvo_local_ba *ba);
+/* device time of the last call's launches (hipEvents around every linearisation's and every trial's group of kernels, summed) */
+int hvo_local_ba_last_ms(const hvo_local_ba *ba, float *ms);
+/* its parts: ms[0] the linearisations, ms[1] the trials, ms[2] of the trials the one-workgroup factorisation, ms[3] the whole call on the
+ * stream from the upload to the last download (the host's Levenberg bookkeeping between the launches included); n = their counts */
+int hvo_local_ba_last_profile(const hvo_local_ba *ba, float ms[4], int32_t n[2]);
+void hvo_local_ba_default_params(hvo_local_ba_params *p);
+/* stop: the caller's abort flag (mbAbortBA), polled where g2o calls terminate() and at :3641 / :3650; may be NULL */
+int hvo_local_ba_optimize(hvo_local_ba *ba, const hvo_local_ba_params *params, const hvo_local_ba_graph *graph, const volatile int *stop,
+                          hvo_local_ba_result *res);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer. Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

@@ -1273,8 +1273,129 @@ struct PoseMapSide {
     const PlaneMap *plane_map = nullptr; const hvo_plane_match *plane_match = nullptr;    // instead of pl_has / pl_coef_w
     hvo_pose_flags flags = { nullptr, nullptr, nullptr, nullptr };
 };
+// Optimizer::LocalMapOptimization (src/Optimizer.cc:3014-3940) on the device: hvo_local_ba.  The object owns its grow-only workspace;
+// create it once beside the map.  LocalMapGraph is what the adaptor gathers: key frame 0 is the CURRENT key
+// frame, the local key frames first, the outside observers after them with fixed = 1; observations name their key frame by its index.
+class LocalBA {
+public:
+    explicit LocalBA(int device = 0) : ba_(nullptr) { check(hvo_local_ba_create(device, &ba_), "hvo_local_ba_create"); }
+    ~LocalBA() { hvo_local_ba_destroy(ba_); }
+    LocalBA(const LocalBA &) = delete;
+    LocalBA &operator=(const LocalBA &) = delete;
+    hvo_local_ba *get() const { return ba_; }
+    std::string lastError() const { return hvo_local_ba_last_error(ba_); }
+    float lastMs() const { float ms = 0.f; hvo_local_ba_last_ms(ba_, &ms); return ms; }
+private:
+    hvo_local_ba *ba_;
+};
+struct LocalMapGraph {
+    std::vector<float> Tcw, cam; std::vector<uint8_t> fixed;                              // n_kf x 12, x 4, x 1
+    std::vector<float> pt_pos, pt_obs_uv, pt_obs_inv_sigma2; std::vector<int32_t> pt_obs_start = { 0 }, pt_obs_kf;
+    std::vector<double> ln_pos, ln_obs_fn, par_fn, perp_fn;
+    std::vector<int32_t> ln_manh_idx, ln_obs_start = { 0 }, ln_obs_kf, par_start = { 0 }, par_kf, par_idx, par_map_size, perp_start = { 0 }, perp_kf, perp_idx, perp_map_size;
+    double manh_axis[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }; bool manh_available = false;       // row-major, column a - 1 = axis a
+    hvo_local_ba_params params;
+    LocalMapGraph() { hvo_local_ba_default_params(&params); }
+    int nKF() const { return (int)fixed.size(); }
+    int nPoints() const { return (int)pt_obs_start.size() - 1; }
+    int nLines() const { return (int)ln_obs_start.size() - 1; }
+    // the builders follow the reference's loops: one call per key frame, per map point with its observations, per map line
+    int addKeyFrame(const float Tcw12[12], bool isFixed, float fx, float fy, float cx, float cy)
+    {
+        Tcw.insert(Tcw.end(), Tcw12, Tcw12 + 12); fixed.push_back(isFixed ? 1 : 0);
+        cam.push_back(fx); cam.push_back(fy); cam.push_back(cx); cam.push_back(cy);
+        return nKF() - 1;
+    }
+    int addPoint(const float pos[3]) { pt_pos.insert(pt_pos.end(), pos, pos + 3); pt_obs_start.push_back(pt_obs_start.back()); return nPoints() - 1; }
+    void addPointObservation(int kf, float u, float v, float invSigma2)                  // of the point added last
+    {
+        pt_obs_kf.push_back(kf); pt_obs_uv.push_back(u); pt_obs_uv.push_back(v); pt_obs_inv_sigma2.push_back(invSigma2); pt_obs_start.back()++;
+    }
+    int addLine(const double pos[6], int manhIdx, int parMapSize, int perpMapSize)
+    {
+        ln_pos.insert(ln_pos.end(), pos, pos + 6); ln_manh_idx.push_back(manhIdx); par_map_size.push_back(parMapSize); perp_map_size.push_back(perpMapSize);
+        ln_obs_start.push_back(ln_obs_start.back()); par_start.push_back(par_start.back()); perp_start.push_back(perp_start.back());
+        return nLines() - 1;
+    }
+    void addLineObservation(int kf, const double fn[3]) { ln_obs_kf.push_back(kf); ln_obs_fn.insert(ln_obs_fn.end(), fn, fn + 3); ln_obs_start.back()++; }
+    void addParEntry(int kf, int idx, const double fn[3]) { par_kf.push_back(kf); par_idx.push_back(idx); par_fn.insert(par_fn.end(), fn, fn + 3); par_start.back()++; }
+    void addPerpEntry(int kf, int idx, const double fn[3]) { perp_kf.push_back(kf); perp_idx.push_back(idx); perp_fn.insert(perp_fn.end(), fn, fn + 3); perp_start.back()++; }
+    hvo_local_ba_graph view() const
+    {
+        hvo_local_ba_graph g = {};
+        g.n_kf = nKF(); g.n_points = nPoints(); g.n_lines = nLines(); g.manh_available = manh_available ? 1 : 0;
+        g.Tcw = Tcw.data(); g.fixed = fixed.data(); g.cam = cam.data();
+        g.pt_pos = pt_pos.data(); g.pt_obs_start = pt_obs_start.data(); g.pt_obs_kf = pt_obs_kf.data(); g.pt_obs_uv = pt_obs_uv.data(); g.pt_obs_inv_sigma2 = pt_obs_inv_sigma2.data();
+        g.ln_pos = ln_pos.data(); g.ln_manh_idx = ln_manh_idx.data(); g.ln_obs_start = ln_obs_start.data(); g.ln_obs_kf = ln_obs_kf.data(); g.ln_obs_fn = ln_obs_fn.data();
+        g.par_start = par_start.data(); g.par_kf = par_kf.data(); g.par_idx = par_idx.data(); g.par_fn = par_fn.data(); g.par_map_size = par_map_size.data();
+        g.perp_start = perp_start.data(); g.perp_kf = perp_kf.data(); g.perp_idx = perp_idx.data(); g.perp_fn = perp_fn.data(); g.perp_map_size = perp_map_size.data();
+        g.manh_axis = manh_axis;
+        return g;
+    }
+};
+struct LocalMapResult {
+    std::vector<float> Tcw, points, lines;                                                 // what SetPose / SetWorldPos receive (Converter::toCvMat)
+    std::vector<double> Tcw_d, points_d, lines_d;
+    std::vector<uint8_t> pt_erase, ln_erase, manh_erase, par_erase, perp_erase, par_made, perp_made, line_made;
+    hvo_local_ba_result res = hvo_local_ba_result();
+    void bind(const LocalMapGraph &g)
+    {
+        const size_t one = 1;                                                              // never hand over a null pointer for an empty list
+        Tcw.assign(std::max(one, g.Tcw.size()), 0.f); Tcw_d.assign(Tcw.size(), 0.0); points.assign(std::max(one, g.pt_pos.size()), 0.f); points_d.assign(points.size(), 0.0);
+        lines.assign(std::max(one, g.ln_pos.size()), 0.f); lines_d.assign(lines.size(), 0.0);
+        pt_erase.assign(std::max(one, g.pt_obs_kf.size()), 0); ln_erase.assign(std::max(one, g.ln_obs_kf.size()), 0); manh_erase.assign(std::max(one, (size_t)g.nLines()), 0);
+        par_erase.assign(std::max(one, g.par_kf.size()), 0); perp_erase.assign(std::max(one, g.perp_kf.size()), 0); par_made = par_erase; perp_made = perp_erase; line_made = manh_erase;
+        res = hvo_local_ba_result();
+        res.Tcw_f = Tcw.data(); res.Tcw_d = Tcw_d.data(); res.pt_f = points.data(); res.pt_d = points_d.data(); res.ln_f = lines.data(); res.ln_d = lines_d.data();
+        res.pt_erase = pt_erase.data(); res.ln_erase = ln_erase.data(); res.manh_erase = manh_erase.data(); res.par_erase = par_erase.data(); res.perp_erase = perp_erase.data();
+        res.par_made = par_made.data(); res.perp_made = perp_made.data(); res.line_made = line_made.data();
+    }
+};
+// The host walk of :3849-3901 over the flags, under the caller's mMutexMapUpdate.  Each callback receives indices of the graph; the walk
+// re-tests isBad() through them (reading 8: return without erasing when the element turned bad meanwhile).
+//   erasePoint(kf, point)        pKFi->EraseMapPointMatch(pMP); pMP->EraseObservation(pKFi)
+//   eraseLine(kf, line)          pKFi->EraseMapLineMatch(pML); pML->EraseObservation(pKFi)
+//   erasePar / erasePerp(line, kf, k)   pML->EraseParObs(pKFi, k): k is the entry's position in its key frame's vector
+// Reading 4: vpLineEdgeKF holds TWO entries per observation and is indexed by observation, so the reference pairs the erased line
+// observation i (in push order over the made lines) with the key frame of observation i / 2.  asWritten = true reproduces that;
+// false pairs an observation with its own key frame.  Reading 5: no Manhattan observation is erased (vpLineManhKF is never filled);
+// LocalMapResult::manh_erase is the caller's to use.
+template <class EP, class EL, class EPar, class EPerp>
+inline void walkErased(const LocalMapGraph &g, const LocalMapResult &r, EP erasePoint, EL eraseLine, EPar erasePar, EPerp erasePerp, bool asWritten = true)
+{
+    for (int p = 0; p < g.nPoints(); p++)
+        for (int o = g.pt_obs_start[p]; o < g.pt_obs_start[p + 1]; o++) if (r.pt_erase[o]) erasePoint(g.pt_obs_kf[o], p);
+    std::vector<int> push;                                                                 // vpLineEdgesSP's order: the observations of the made lines
+    for (int l = 0; l < g.nLines(); l++) if (r.line_made[l]) for (int o = g.ln_obs_start[l]; o < g.ln_obs_start[l + 1]; o++) push.push_back(o);
+    std::vector<int> owner(g.ln_obs_kf.size(), 0);
+    for (int l = 0; l < g.nLines(); l++) for (int o = g.ln_obs_start[l]; o < g.ln_obs_start[l + 1]; o++) owner[o] = l;
+    for (size_t i = 0; i < push.size(); i++)
+        if (r.ln_erase[push[i]]) eraseLine(g.ln_obs_kf[asWritten ? push[i / 2] : push[i]], owner[push[i]]);
+    for (int s = 0; s < 2; s++) {
+        const std::vector<int32_t> &start = s ? g.perp_start : g.par_start, &kf = s ? g.perp_kf : g.par_kf;
+        const std::vector<uint8_t> &flag = s ? r.perp_erase : r.par_erase;
+        for (int l = 0; l < g.nLines(); l++)
+            for (int o = start[l]; o < start[l + 1]; o++) {
+                if (!flag[o]) continue;
+                int first = o;
+                while (first > start[l] && kf[first - 1] == kf[o]) first--;
+                if (s) erasePerp(l, kf[o], o - first); else erasePar(l, kf[o], o - first);
+            }
+    }
+}
+
 class Optimizer {
 public:
+    // Optimizer::LocalMapOptimization(mManhAxis, mpCurrentKeyFrame, &mbAbortBA, mpMap, mAvailableOptManh) becomes
+    // Optimizer::LocalMapOptimization(ba, graph, &abort, result); stop may be null.  Returns the status (HVO_LBA_*).
+    static int LocalMapOptimization(LocalBA &ba, const LocalMapGraph &g, const int *stop, LocalMapResult &r)
+    {
+        r.bind(g);
+        const hvo_local_ba_graph v = g.view();
+        const int rc = hvo_local_ba_optimize(ba.get(), &g.params, &v, stop, &r.res);
+        if (rc != HVO_OK) throw Error(rc, "hvo_local_ba_optimize: " + ba.lastError());
+        return r.res.status;
+    }
     explicit Optimizer(const hvo_camera &cam, const hvo_pose_plane_params *pp = nullptr) : cam_(cam), has_pp_(pp != nullptr) { if (pp) pp_ = *pp; }
     // int nInliers = Optimizer::PoseOptimization(&mCurrentFrame)  becomes  optimizer.PoseOptimization(fs, ticket, Tcw, side, res)
     int PoseOptimization(FrameStream &fs, int64_t cur, const float Tcw[12], const PoseMapSide &m, hvo_pose_result &res) const
