@@ -34,6 +34,7 @@
 //                   ComputeThreeMaxima (hvo_three_maxima, shared with the guided search).
 #include "frame_view.hpp"
 #include "staged_call.hpp"
+#include "map_gates.hpp"      // ham256
 #include <string.h>
 #include <stdio.h>
 #include <math.h>
@@ -85,11 +86,6 @@ void bow_state_free(BowState *b)
 }
 
 // ------------------------------------------------------------------------------------------------ kernels
-static __device__ __forceinline__ int bow_ham(const ulonglong4 &a, const ulonglong4 &b)
-{
-    return __popcll(a.x ^ b.x) + __popcll(a.y ^ b.y) + __popcll(a.z ^ b.z) + __popcll(a.w ^ b.w);
-}
-
 // grid (ceil(cap / 16), frames); frame f: descriptors at desc + f * desc_stride, count d_n[f * n_stride] (clamped to cap), block at blk + f * L.total
 __global__ __launch_bounds__(256) void k_bow_descend(VocDev V, int nid_level, const uint8_t *__restrict__ desc, size_t desc_stride, const int *__restrict__ d_n,
                                                      int n_stride, char *__restrict__ blk, BowLayout L)
@@ -105,7 +101,7 @@ __global__ __launch_bounds__(256) void k_bow_descend(VocDev V, int nid_level, co
         level++;
         unsigned best = 0xFFFFFFFFu;
         for (int c = gl; c < ch.y; c += BOW_GROUP) {
-            const unsigned key = ((unsigned)bow_ham(q, V.desc[ch.x + c]) << 8) | (unsigned)c;
+            const unsigned key = ((unsigned)ham256(q, V.desc[ch.x + c]) << 8) | (unsigned)c;
             best = min(best, key);
         }
 #pragma unroll
@@ -320,7 +316,7 @@ __global__ __launch_bounds__(64 * BOW_WAVES) void k_bow_search(BowSearchDev a)
             for (int c = 0; c < nchunk; c++) {
                 const int p = c * 64 + lane;
                 if (p < nb && !((claimed >> c) & 1ull)) {
-                    const int d = c == 0 ? bow_ham(kd, fd0) : bow_ham(kd, reinterpret_cast<const ulonglong4 *>(a.f_desc)[a.f_fv_idx[fb + p]]);
+                    const int d = c == 0 ? ham256(kd, fd0) : ham256(kd, reinterpret_cast<const ulonglong4 *>(a.f_desc)[a.f_fv_idx[fb + p]]);
                     const unsigned key = ((unsigned)d << 16) | (unsigned)p;
                     if (key < k1) { k2 = k1; k1 = key; } else if (key < k2) k2 = key;
                 }

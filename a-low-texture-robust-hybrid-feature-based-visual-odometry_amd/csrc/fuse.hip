@@ -29,13 +29,13 @@
 //   Rcw * p3Dw + tcw       sm_row: the row's products summed in FLOAT left to right, then (float)((double)sum * 1.0 + (double)t * 1.0)
 //   z < 0.0f               as written: z == 0 and -0.0 pass and divide
 //   invz = 1 / z           ONE FLOAT division: the text has the int literal 1 (the siblings divide the double 1.0)
-//   u = fx * x + cx        x = X * invz: two float products (the siblings form fx * xc * invzc left to right)
+//   u = fx * x + cx        x = X * invz: two float products, NOT sm_pinhole (the siblings form fx * xc * invzc left to right)
 //   IsInImage              u >= minX && u < maxX && v >= minY && v < maxY: a NaN FAILS (kf_search's four one-sided tests let it pass)
 //   ur = u - bf * invz     float
-//   Ow, p3Dw - Ow, norm    as kf_search: -Rcw^T tcw with double sums times -1.0 rounded to float; float difference; sqrt of the double sum
-//                          of squares stored to float
+//   Ow, p3Dw - Ow, norm    as kf_search: -Rcw^T tcw with double sums times -1.0 rounded to float; float difference; sm_dist3; the
+//                          1.2 / 0.8 band is sm_dist_band
 //   PO.dot(Pn)             cv::Mat::dot on CV_32F accumulates in double, in order; compared with the double 0.5 * dist3D
-//   PredictScale           exactly k_kf_project's: float ratio, logf, float division, ceilf, saturating conversion (NaN -> 0), clamp
+//   PredictScale           sm_predict_level, then sm_clamp_level (map_gates.hpp, shared with every sibling)
 //   radius                 th * mvScaleFactors[level], a float product; the scale factors and mvInvLevelSigma2 are the context's
 //   cell range             max(0, (int)floor((u - minX - r) * invW)) .. min(cols - 1, (int)ceil((u - minX + r) * invW)) with the four early
 //                          returns, applied as written IN ADDITION to the fabs tests (float rounding can make the two disagree by a cell)
@@ -161,21 +161,17 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_project(FuDev a)
                 g = HVO_FUSE_GATE_OUT_OF_IMAGE;
                 if (u >= a.minX && u < a.maxX && v >= a.minY && v < a.maxY) {          // KeyFrame::IsInImage: a NaN fails
                     ur = __fsub_rn(u, __fmul_rn(a.bf, invz));
-                    const float mfMax = a.maxd[e], mfMin = a.mind[e];
-                    const float maxD = __fmul_rn(1.2f, mfMax), minD = __fmul_rn(0.8f, mfMin);
+                    const float mfMax = a.maxd[e]; float maxD, minD; sm_dist_band(mfMax, a.mind[e], &maxD, &minD);
                     const double d0 = __fsub_rn(X, k.Ow[0]), d1 = __fsub_rn(Y, k.Ow[1]), d2 = __fsub_rn(Z, k.Ow[2]);
-                    const float dist = (float)sqrt(__dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2)));
+                    const float dist = sm_dist3(d0, d1, d2);
                     g = dist < minD ? HVO_FUSE_GATE_DIST_MIN : dist > maxD ? HVO_FUSE_GATE_DIST_MAX : 0;
                     if (g == 0) {
                         const double n0 = a.nrm[p], n1 = a.nrm[p + a.cstride], n2 = a.nrm[p + 2 * a.cstride];
                         const double dot = __dadd_rn(__dadd_rn(__dmul_rn(d0, n0), __dmul_rn(d1, n1)), __dmul_rn(d2, n2));
                         if (dot < __dmul_rn(0.5, (double)dist)) g = HVO_FUSE_GATE_VIEW_ANGLE;          // :897
                         else {
-                            const float ratio = __fdiv_rn(mfMax, dist);
-                            const float lv = ceilf(__fdiv_rn(logf(ratio), a.logsf));
-                            int l = sm_level(lv);
-                            if (l < 0) l = 0; else if (l >= a.n_levels) l = a.n_levels - 1;            // MapPoint.cc:392-395
-                            lvl = l; radius = __fmul_rn(a.th, a.tab[l]);
+                            lvl = sm_clamp_level(sm_predict_level(mfMax, dist, a.logsf), a.n_levels);           // MapPoint.cc:383-398
+                            radius = __fmul_rn(a.th, a.tab[lvl]);
                         }
                     }
                 }
@@ -208,8 +204,7 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_search(FuDev a)
     x0 = x0 < 0 ? 0 : x0; x1 = x1 > FU_COLS - 1 ? FU_COLS - 1 : x1; y0 = y0 < 0 ? 0 : y0; y1 = y1 > FU_ROWS - 1 ? FU_ROWS - 1 : y1;
     if (x0 >= FU_COLS || x1 < 0 || y0 >= FU_ROWS || y1 < 0) return;  // vIndices.empty(): bestIdx stays -1
     const size_t e = a.slots ? (size_t)a.slots[i] : (a.per_kf ? (size_t)j * a.cq : 0) + (size_t)i;
-    const unsigned long long *qd = reinterpret_cast<const unsigned long long *>(a.mdesc + e * 32);
-    const unsigned long long q0 = qd[0], q1 = qd[1], q2 = qd[2], q3 = qd[3];
+    const ulonglong4 qd = ld256(a.mdesc + e * 32);
     const int *start = a.cstart + (size_t)j * (FU_CELLS + 1);
     const float4 *rec = a.rec + (size_t)j * a.ct; const int32_t *item = a.item + (size_t)j * a.ct;
     const float *isig = a.tab + HVO_MAX_LEVELS;
@@ -226,8 +221,7 @@ __global__ __launch_bounds__(FU_BLOCK) void k_fuse_search(FuDev a)
             double lim = 5.99;
             if (f.z >= 0.f) { const float er = __fsub_rn(ur, f.z); e2 = __fadd_rn(e2, __fmul_rn(er, er)); lim = 7.8; }
             if ((double)__fmul_rn(e2, isig[oct]) > lim) continue;    // :938, :949
-            const unsigned long long *d = reinterpret_cast<const unsigned long long *>(k.desc + (size_t)item[p] * 32);
-            const unsigned dist = __popcll(q0 ^ d[0]) + __popcll(q1 ^ d[1]) + __popcll(q2 ^ d[2]) + __popcll(q3 ^ d[3]);
+            const unsigned dist = ham256(qd, ld256(k.desc + (size_t)item[p] * 32));
             const unsigned key = (dist << 16) | (unsigned)p;
             best = key < best ? key : best;
         }

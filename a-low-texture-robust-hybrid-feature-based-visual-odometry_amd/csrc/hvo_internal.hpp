@@ -228,6 +228,9 @@ static __device__ __forceinline__ double hvo_div_const(double a, double b, doubl
     return fma(fma(-q1, b, a), y, q1);
 }
 
+// xorshift32 (13, 17, 5): the one generator behind the RANSAC draws of line3d.hip, pnp.hip and vps.hip
+static __device__ __forceinline__ unsigned xs32(unsigned &s) { unsigned x = s; x ^= x << 13; x ^= x >> 17; x ^= x << 5; s = x; return x; }
+
 // cv::fastAtan2, float, evaluated without contraction (the same text as lsd.hip's and orb.hip's own copies)
 static __device__ __forceinline__ float hvo_fatan2_deg(float y, float x)
 {

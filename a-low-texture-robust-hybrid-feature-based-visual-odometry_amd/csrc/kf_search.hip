@@ -26,13 +26,12 @@
 //   Rcw * x3Dw + tcw       gemm3_row (match.hip; sm_row is the same text): the row's products summed in FLOAT left to right, then
 //                          (float)((double)sum * 1.0 + (double)t * 1.0)
 //   invzc = 1.0 / z        k_project_last's reading: the text divides the double 1.0, the quotient is rounded to float
-//   u, v                   fx * xc * invzc + cx in float, left to right
+//   u, v                   sm_pinhole: fx * xc * invzc + cx in float, left to right
 //   Ow                     -Rcw^T tcw with double sums, times -1.0, rounded to float (match_project_setup's twc)
 //   x3Dw - Ow              float, element-wise
-//   cv::norm               sqrt of the double sum of squares, stored to float
-//   1.2f * mfMaxDistance   float products (GetMaxDistanceInvariance / GetMinDistanceInvariance)
-//   PredictScale           exactly k_lp_frustum's: float ratio, logf, float division, ceilf, saturating conversion (NaN -> 0), clamp to
-//                          [0, n_levels - 1]
+//   cv::norm               sm_dist3: sqrt of the double sum of squares, stored to float
+//   1.2f * mfMaxDistance   sm_dist_band: float products (GetMaxDistanceInvariance / GetMinDistanceInvariance)
+//   PredictScale           sm_predict_level, then sm_clamp_level to [0, n_levels - 1] (map_gates.hpp, shared with every sibling)
 //   radius                 th * mvScaleFactors[level], a float product; the scale factors are the context's
 // No contraction (-ffp-contract=off, __f*_rn).
 #include "slot_map.hpp"
@@ -69,19 +68,14 @@ __global__ __launch_bounds__(KFS_BLOCK) void k_kf_project(KfsDev a)
         const float X = a.pos[p], Y = a.pos[p + cq], Z = a.pos[p + 2 * cq];
         const float xc = sm_row(c.R, X, Y, Z, c.t[0]), yc = sm_row(c.R + 3, X, Y, Z, c.t[1]), zc = sm_row(c.R + 6, X, Y, Z, c.t[2]);
         const float invzc = (float)(1.0 / (double)zc);             // ORBmatcher.cc:1529; no sign test follows
-        pu = __fadd_rn(__fmul_rn(__fmul_rn(a.fx, xc), invzc), a.cx); pv = __fadd_rn(__fmul_rn(__fmul_rn(a.fy, yc), invzc), a.cy);
+        pu = sm_pinhole(a.fx, xc, invzc, a.cx); pv = sm_pinhole(a.fy, yc, invzc, a.cy);
         g = pu < a.minX ? HVO_KF_GATE_U_MIN : pu > a.maxX ? HVO_KF_GATE_U_MAX : pv < a.minY ? HVO_KF_GATE_V_MIN : pv > a.maxY ? HVO_KF_GATE_V_MAX : 0;   // (a NaN compares false four times)
         if (g == 0) {
-            const float mfMax = a.maxd[o], mfMin = a.mind[o];
-            const float maxD = __fmul_rn(1.2f, mfMax), minD = __fmul_rn(0.8f, mfMin);
-            const double d0 = __fsub_rn(X, c.Ow[0]), d1 = __fsub_rn(Y, c.Ow[1]), d2 = __fsub_rn(Z, c.Ow[2]);
-            const float dist = (float)sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+            const float mfMax = a.maxd[o]; float maxD, minD; sm_dist_band(mfMax, a.mind[o], &maxD, &minD);
+            const float dist = sm_dist3(__fsub_rn(X, c.Ow[0]), __fsub_rn(Y, c.Ow[1]), __fsub_rn(Z, c.Ow[2]));
             g = dist < minD ? HVO_KF_GATE_DIST_MIN : dist > maxD ? HVO_KF_GATE_DIST_MAX : 0;
             if (g == 0) {
-                const float ratio = __fdiv_rn(mfMax, dist);
-                const float lv = ceilf(__fdiv_rn(logf(ratio), a.logsf));
-                int l = sm_level(lv);
-                if (l < 0) l = 0; else if (l >= a.n_levels) l = a.n_levels - 1;      // MapPoint.cc:409-412
+                const int l = sm_clamp_level(sm_predict_level(mfMax, dist, a.logsf), a.n_levels);      // MapPoint.cc:400-415
                 lvl = l; u = pu; v = pv; radius = __fmul_rn(a.th, a.sf[l]); lo = l - 1; hi = l + 1;
             }
         }

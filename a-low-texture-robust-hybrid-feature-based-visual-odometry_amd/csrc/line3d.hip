@@ -126,8 +126,6 @@ static __device__ void compute_line3d_dev(const double (*P)[3], unsigned mask, i
     drct[0] = V[0][2]; drct[1] = V[1][2]; drct[2] = V[2][2];
 }
 
-static __device__ __forceinline__ unsigned xs32(unsigned &s) { unsigned x = s; x ^= x << 13; x ^= x >> 17; x ^= x << 5; s = x; return x; }
-
 __global__ __launch_bounds__(64) void k_lines_3d(const hvo_keyline *__restrict__ kl, const int *__restrict__ n_ptr, int n_fixed,
                                                  const uint16_t *__restrict__ depth, int pitch, int w, int h,
                                                  float fx, float fy, float cx, float cy, float dfac, unsigned seed, hvo_line3d *__restrict__ out)

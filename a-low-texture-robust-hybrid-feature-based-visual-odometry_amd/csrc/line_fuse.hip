@@ -38,10 +38,10 @@
 // before u2, v2 are computed, a NaN fails; the two distance gates (two codes); the double 0.5 * dist of the angle gate; the band
 // [level - 1, level] on kl.octave (an octave of -1 is inside it at level 0); an empty vIndices is no match; strict `<`; bestDist <= th_low.
 // Arithmetic: Mat_<float> << double rounds to float; Rcw * SP + tcw is sm_row (tests/fuse_ref.py: point_map_ref.transform); invz = 1.0f / z
-// is one float division and u = fx * X * invz + cx goes left to right (the literal is 1.0f here, and the products are not regrouped);
+// is one float division and u = fx * X * invz + cx is sm_pinhole (the literal is 1.0f here, and the products are not regrouped);
 // 0.5 * (SP + EP) is f32(SP * 0.5 + EP * 0.5) with the products and the sum in double (tests/map_refresh_ref.py), minus Ow in float;
-// cv::norm is the square root of the double sum of squares stored to float and Mat::dot accumulates in double (tests/fuse_ref.py);
-// PredictScale is float: logf, float division, ceilf, saturating conversion (NaN -> 0).
+// cv::norm is sm_dist3, the band sm_dist_band, and Mat::dot accumulates in double (tests/fuse_ref.py);
+// PredictScale is sm_predict_level, clamped by sm_clamp_level or gated as written (reading 2); the Hamming distance is ham256 (map_gates.hpp).
 // Inside GetLinesInArea: the mid-point distance is formed in double (0.5 * (x1 + x2) has a double literal; x1 + x2 is a float sum) and
 // rounded to the float `distance`; it is compared with the float product r * r with `>`; CosSita = fabsf of the float sum of two float
 // products; `CosSita < 0.998f` continues, so a NaN (a projected or stored line of zero length) PASSES.  Nothing is contracted.
@@ -108,30 +108,28 @@ __global__ __launch_bounds__(LF_BLOCK) void k_lf_project(LfDev a)
             g = HVO_LF_GATE_BEHIND;
             if (!(sz < 0.0f || ez < 0.0f)) {                         // LSDmatcher.cpp:1340
                 const float invz1 = __fdiv_rn(1.0f, sz);
-                u1 = __fadd_rn(__fmul_rn(__fmul_rn(k.fx, sx), invz1), k.cx); v1 = __fadd_rn(__fmul_rn(__fmul_rn(k.fy, sy), invz1), k.cy);
+                u1 = sm_pinhole(k.fx, sx, invz1, k.cx); v1 = sm_pinhole(k.fy, sy, invz1, k.cy);
                 g = HVO_LF_GATE_OUT_OF_IMAGE;
                 if (u1 >= k.minX && u1 < k.maxX && v1 >= k.minY && v1 < k.maxY) {          // :1347, a NaN fails
                     const float invz2 = __fdiv_rn(1.0f, ez);
-                    u2 = __fadd_rn(__fmul_rn(__fmul_rn(k.fx, ex), invz2), k.cx); v2 = __fadd_rn(__fmul_rn(__fmul_rn(k.fy, ey), invz2), k.cy);
+                    u2 = sm_pinhole(k.fx, ex, invz2, k.cx); v2 = sm_pinhole(k.fy, ey, invz2, k.cy);
                     if (u2 >= k.minX && u2 < k.maxX && v2 >= k.minY && v2 < k.maxY) {      // :1355
-                        const float mfMax = a.maxd[e], mfMin = a.mind[e];
-                        const float maxD = __fmul_rn(1.2f, mfMax), minD = __fmul_rn(0.8f, mfMin);
-                        double d[3];                                 // OM = 0.5 * (SP + EP) - Ow
+                        const float mfMax = a.maxd[e]; float maxD, minD; sm_dist_band(mfMax, a.mind[e], &maxD, &minD);
+                        double d[3];                                 // OM = 0.5 * (SP + EP) - Ow, the midpoint in DOUBLE (local_lines.hip forms it in float)
                         for (int c = 0; c < 3; c++) {
                             const float mid = (float)__dadd_rn(__dmul_rn((double)S[c], 0.5), __dmul_rn((double)E[c], 0.5));
                             d[c] = (double)__fsub_rn(mid, k.Ow[c]);
                         }
-                        const float dist = (float)sqrt(__dadd_rn(__dadd_rn(__dmul_rn(d[0], d[0]), __dmul_rn(d[1], d[1])), __dmul_rn(d[2], d[2])));
+                        const float dist = sm_dist3(d[0], d[1], d[2]);
                         g = dist < minD ? HVO_LF_GATE_DIST_MIN : dist > maxD ? HVO_LF_GATE_DIST_MAX : HVO_LF_GATE_SEARCHED;
                         if (g == HVO_LF_GATE_SEARCHED) {
                             const double n0 = (double)(float)a.nrm[pn], n1 = (double)(float)a.nrm[pn + a.cstride], n2 = (double)(float)a.nrm[pn + 2 * a.cstride];
                             const double dot = __dadd_rn(__dadd_rn(__dmul_rn(d[0], n0), __dmul_rn(d[1], n1)), __dmul_rn(d[2], n2));
                             if (dot < __dmul_rn(0.5, (double)dist)) g = HVO_LF_GATE_VIEW_ANGLE;        // :1371
                             else {
-                                const float ratio = __fdiv_rn(mfMax, dist);
-                                int l = sm_level(ceilf(__fdiv_rn(logf(ratio), a.logsf)));             // MapLine.cpp:557
+                                int l = sm_predict_level(mfMax, dist, a.logsf);                       // MapLine.cpp:557
                                 if (a.as_written) { if (l < 0 || l >= a.n_levels) g = HVO_LF_GATE_LEVEL; }
-                                else l = l < 0 ? 0 : l >= a.n_levels ? a.n_levels - 1 : l;
+                                else l = sm_clamp_level(l, a.n_levels);
                                 lvl = l;
                                 if (g == HVO_LF_GATE_SEARCHED) radius = __fmul_rn(a.th, a.tab[l]);
                             }
@@ -165,8 +163,7 @@ __global__ __launch_bounds__(LF_BLOCK) void k_lf_search(LfDev a)
         mx = __dmul_rn(0.5, (double)__fadd_rn(x1, x2)); my = __dmul_rn(0.5, (double)__fadd_rn(y1, y2));
         rr = __fmul_rn(r, r); lvl = a.level[o];
         const size_t e = a.slots ? (size_t)a.slots[i] : (a.per_kf ? (size_t)j * a.cq : 0) + (size_t)i;
-        const unsigned long long *qd = reinterpret_cast<const unsigned long long *>(a.mdesc + e * 32);
-        q0 = qd[0]; q1 = qd[1]; q2 = qd[2]; q3 = qd[3];
+        const ulonglong4 qd = ld256(a.mdesc + e * 32); q0 = qd.x; q1 = qd.y; q2 = qd.z; q3 = qd.w;
     }
     const float4 *rec = a.rec + (size_t)j * a.ct; const int32_t *oct = a.oct + (size_t)j * a.ct;
     const int n = k.n_lines, rows = k.n_rows;
@@ -186,8 +183,7 @@ __global__ __launch_bounds__(LF_BLOCK) void k_lf_search(LfDev a)
             const int oc = s_oct[p], idx = base + p;
             if (oc < lvl - 1 || oc > lvl) continue;                  // LSDmatcher.cpp:1395
             if (idx >= rows) continue;                               // no such row (reading 1)
-            const unsigned long long *d = reinterpret_cast<const unsigned long long *>(k.desc + (size_t)idx * 32);
-            const unsigned dist = __popcll(q0 ^ d[0]) + __popcll(q1 ^ d[1]) + __popcll(q2 ^ d[2]) + __popcll(q3 ^ d[3]);
+            const unsigned dist = ham256(make_ulonglong4(q0, q1, q2, q3), ld256(k.desc + (size_t)idx * 32));
             const unsigned key = (dist << 16) | (unsigned)idx;
             best = key < best ? key : best;
         }

@@ -18,6 +18,7 @@
 // classification re-evaluates an edge at the end points of the round's last computeActiveErrors instead of storing _error.
 #include "frame_view.hpp"
 #include "staged_call.hpp"
+#include "se3quat.hpp"        // huber, wave_sum_down
 #include <math.h>
 #include <cmath>
 #include <string.h>
@@ -101,22 +102,11 @@ static __device__ __forceinline__ double ls_err(int kind, const double *p, const
     const double c = ls_cos(p, p + 3, m, nm);
     return kind == 1 ? 1 - c : c;
 }
-static __device__ __forceinline__ void ls_huber(double e, double delta, double &r0, double &r1)     // core/robust_kernel_impl.cpp:78-91
-{
-    const double dsqr = delta * delta;
-    if (e <= dsqr) { r0 = e; r1 = 1.0; }
-    else { const double s = sqrt(e); r0 = 2 * s * delta - dsqr; r1 = delta / s; }
-}
 static __device__ __forceinline__ void ls_meas(const LsFrame &F, int i, double *m, double &nm)
 {
     const float *q = F.l3d[i].line_eq;
     m[0] = (double)q[0]; m[1] = (double)q[1]; m[2] = (double)q[2];
     nm = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
-}
-static __device__ __forceinline__ double ls_wave_sum(double x)
-{
-    for (int off = 32; off > 0; off >>= 1) x = x + __shfl_down(x, off, 64);
-    return x;
 }
 // sum of sh.lv[0..n) -> return value on every thread: thread t adds lines t, t + 256, ... in order, a wave halves, the waves in order
 static __device__ double ls_reduce_lines(LsShared &sh, int n)
@@ -124,7 +114,7 @@ static __device__ double ls_reduce_lines(LsShared &sh, int n)
     const int tid = threadIdx.x;
     double x = 0.0;
     for (int k = tid; k < n; k += LS_THREADS) x = x + sh.lv[k];
-    x = ls_wave_sum(x);
+    x = wave_sum_down(x);
     __syncthreads();
     if ((tid & 63) == 0) sh.red[tid >> 6] = x;
     __syncthreads();
@@ -152,7 +142,7 @@ static __device__ void ls_line_pass(const LsArgs &A, const LsFrame &F, LsShared 
             double m[3], nm; ls_meas(F, i, m, nm);
             const double e0 = ls_err(kind, p, m, nm);
             const double c = e0 * e0;
-            double r0, r1; ls_huber(c, A.delta, r0, r1);
+            double r0, r1; huber(c, A.delta, r0, r1);
             acc[27] = acc[27] + r0; cnt++;
             if (with_sys) {
                 double J[6];
@@ -171,7 +161,7 @@ static __device__ void ls_line_pass(const LsArgs &A, const LsFrame &F, LsShared 
                 }
             }
         }
-        for (int j = with_sys ? 0 : 27; j < 28; j++) acc[j] = ls_wave_sum(acc[j]);
+        for (int j = with_sys ? 0 : 27; j < 28; j++) acc[j] = wave_sum_down(acc[j]);
         for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
         if (lane == 0) {
             sh.lv[k] = acc[27];
@@ -191,6 +181,8 @@ static __device__ bool ls_solve6(const double *Hb, double lam, double *x)
     int h = 0;
     for (int i = 0; i < 6; i++) for (int j = i; j < 6; j++, h++) { H[6 * i + j] = Hb[h]; H[6 * j + i] = Hb[h]; }
     for (int j = 0; j < 6; j++) H[7 * j] = H[7 * j] + lam;
+    // ldlt6_solve's text (se3quat.hpp) with this call's pivot rule, kept in place: through the shared function k_line_opt is scheduled
+    // differently and its 256-frame batch measured above both parent runs (profiles/shared_readings.txt)
     for (int j = 0; j < 6; j++) {
         double s = H[6 * j + j];
         for (int k = 0; k < j; k++) s = s - L[6 * j + k] * L[6 * j + k] * D[k];

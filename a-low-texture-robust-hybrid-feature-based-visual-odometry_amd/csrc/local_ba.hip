@@ -15,6 +15,7 @@
 // chi2() of the erase tests is the error an edge HOLDS (reading 2): chi_held[e] is written by every evaluation of an ACTIVE edge and
 // by nothing else, so a level-1 edge keeps round 1's last evaluation.  The classification and the flags are host code.
 #include "hvo_internal.hpp"
+#include "se3quat.hpp"        // quat_from_R .. se3_map, huber, wave_sum_down
 #include <math.h>
 #include <cmath>
 #include <string.h>
@@ -57,85 +58,6 @@ struct LbArgs {
     double *out;                    // chi2, scale, ok, largest diagonal
 };
 
-// ---- SE3Quat (Thirdparty/g2o/g2o/types/se3quat.h), as csrc/pose_opt.hip reads it ----
-static __host__ __device__ void lb_quat_from_R(const double *m, double *q)
-{
-    double t = m[0] + m[4] + m[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0); q[0] = 0.5 * t; t = 0.5 / t;
-        q[1] = (m[7] - m[5]) * t; q[2] = (m[2] - m[6]) * t; q[3] = (m[3] - m[1]) * t;
-    } else {
-        int i = 0;
-        if (m[4] > m[0]) i = 1;
-        if (m[8] > m[4 * i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0); q[1 + i] = 0.5 * t; t = 0.5 / t;
-        q[0] = (m[3 * k + j] - m[3 * j + k]) * t; q[1 + j] = (m[3 * j + i] + m[3 * i + j]) * t; q[1 + k] = (m[3 * k + i] + m[3 * i + k]) * t;
-    }
-}
-static __host__ __device__ void lb_quat_normalize(double *q)
-{
-    if (q[0] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    q[0] = q[0] / n; q[1] = q[1] / n; q[2] = q[2] / n; q[3] = q[3] / n;
-}
-static __host__ __device__ void lb_quat_to_R(const double *q, double *R)
-{
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-static __device__ void lb_mat3(const double *A, const double *B, double *C)
-{
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
-// SE3Quat::exp(update) (se3quat.h:229-263): q[4], t[3] into o[7]
-static __device__ void lb_exp(const double *u, double *o)
-{
-    const double th = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    const double Om[9] = { 0, -u[2], u[1], u[2], 0, -u[0], -u[1], u[0], 0 };
-    double Om2[9]; lb_mat3(Om, Om, Om2);
-    double R[9], V[9];
-    if (th < 0.00001) {
-        for (int i = 0; i < 9; i++) { R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + Om[i]) + Om2[i]; V[i] = R[i]; }
-    } else {
-        const double s = sin(th), c = cos(th);
-        const double a = s / th, b = (1 - c) / (th * th), g = (th - s) / (th * th * th);
-        for (int i = 0; i < 9; i++) {
-            const double I = i % 4 == 0 ? 1.0 : 0.0;
-            R[i] = (I + a * Om[i]) + b * Om2[i];
-            V[i] = (I + b * Om[i]) + g * Om2[i];
-        }
-    }
-    lb_quat_from_R(R, o); lb_quat_normalize(o);
-    for (int i = 0; i < 3; i++) o[4 + i] = (V[3 * i] * u[3] + V[3 * i + 1] * u[4]) + V[3 * i + 2] * u[5];
-}
-// SE3Quat::operator*
-static __device__ void lb_mul(const double *a, const double *b, double *o)
-{
-    const double *p = a, *q = b;
-    double r[4];
-    r[0] = p[0] * q[0] - p[1] * q[1] - p[2] * q[2] - p[3] * q[3];
-    r[1] = p[0] * q[1] + p[1] * q[0] + p[2] * q[3] - p[3] * q[2];
-    r[2] = p[0] * q[2] + p[2] * q[0] + p[3] * q[1] - p[1] * q[3];
-    r[3] = p[0] * q[3] + p[3] * q[0] + p[1] * q[2] - p[2] * q[1];
-    double Ra[9]; lb_quat_to_R(a, Ra);
-    double t[3];
-    for (int i = 0; i < 3; i++) t[i] = a[4 + i] + ((Ra[3 * i] * b[4] + Ra[3 * i + 1] * b[5]) + Ra[3 * i + 2] * b[6]);
-    lb_quat_normalize(r);
-    for (int i = 0; i < 4; i++) o[i] = r[i];
-    for (int i = 0; i < 3; i++) o[4 + i] = t[i];
-}
-static __host__ __device__ __forceinline__ void lb_map(const double *Rt, const double *X, double *Y)
-{
-    Y[0] = ((Rt[0] * X[0] + Rt[1] * X[1]) + Rt[2] * X[2]) + Rt[9];
-    Y[1] = ((Rt[3] * X[0] + Rt[4] * X[1]) + Rt[5] * X[2]) + Rt[10];
-    Y[2] = ((Rt[6] * X[0] + Rt[7] * X[1]) + Rt[8] * X[2]) + Rt[11];
-}
-
 // R, t of every key frame's pose (slot 0) and, with full != 0, of exp(+-delta e_d) * pose for the free ones (slots 1 + 2 d, 2 + 2 d)
 __global__ __launch_bounds__(LBA_THREADS) void k_lba_poses(LbArgs a, int trial, int full)
 {
@@ -149,12 +71,12 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_poses(LbArgs a, int trial, 
     else {
         double u[6] = { 0, 0, 0, 0, 0, 0 };
         u[(s - 1) >> 1] = ((s - 1) & 1) ? -LBA_DELTA : LBA_DELTA;
-        double e[7]; lb_exp(u, e);
+        double e[7]; se3_exp(u, e);
         double b[7]; for (int i = 0; i < 7; i++) b[i] = P[i];
-        lb_mul(e, b, p);
+        se3_mul(e, b, p);
     }
     double *Rt = a.Rt + ((size_t)kf * 13 + s) * 12;
-    double R[9]; lb_quat_to_R(p, R);
+    double R[9]; quat_to_R(p, R);
     for (int i = 0; i < 9; i++) Rt[i] = R[i];
     Rt[9] = p[4]; Rt[10] = p[5]; Rt[11] = p[6];
 }
@@ -162,7 +84,7 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_poses(LbArgs a, int trial, 
 // computeError of the five edge types: X holds the landmark (3 or 6 doubles), Rt the observer's pose; err[1] is 0 for the line edges
 static __device__ __forceinline__ void lb_project(const double *Rt, const double *X, const double *cam, double *uv)
 {
-    double Y[3]; lb_map(Rt, X, Y);
+    double Y[3]; se3_map(Rt, X, Y);
     uv[0] = Y[0] / Y[2] * cam[0] + cam[2];
     uv[1] = Y[1] / Y[2] * cam[1] + cam[3];
 }
@@ -214,17 +136,14 @@ __global__ __launch_bounds__(LBA_THREADS) void k_lba_edges(LbArgs a)
     const double chi = E.info * err[0] * err[0] + E.info * err[1] * err[1];
     a.chi_held[e] = chi;
     double r0 = chi, r1 = 1.0;
-    if (a.robust || E.kind == LBA_MANH) {                                       // RobustKernelHuber::robustify; the Manhattan edge keeps its kernel in round 2
-        const double dsqr = E.delta * E.delta;
-        if (!(chi <= dsqr)) { const double s = sqrt(chi); r0 = 2 * s * E.delta - dsqr; r1 = E.delta / s; }
-    }
+    if (a.robust || E.kind == LBA_MANH) huber(chi, E.delta, r0, r1);            // the Manhattan edge keeps its kernel in round 2
     a.rho[e] = r0;
     if (!LIN) return;
     ew[0] = err[0]; ew[1] = err[1]; ew[2] = r1; ew[3] = E.info;
     for (int i = 0; i < 12; i++) { Jl[i] = 0.0; Jp[i] = 0.0; }
     const bool free_kf = E.pair >= 0;
     if (E.kind == LBA_PT) {                                                     // EdgeSE3ProjectXYZ::linearizeOplus
-        double Y[3]; lb_map(Rt, X, Y);
+        double Y[3]; se3_map(Rt, X, Y);
         const double x = Y[0], y = Y[1], z = Y[2], z_2 = z * z, fx = E.cam[0], fy = E.cam[1];
         const double c = -1. / z;
         const double t0[3] = { c * fx, c * 0.0, c * (-x / z * fx) }, t1[3] = { c * 0.0, c * fy, c * (-y / z * fy) };
@@ -337,7 +256,9 @@ __global__ __launch_bounds__(64) void k_lba_diag(LbArgs a)
     }
 }
 
-// one thread per landmark: (Hll + lambda I)^-1 by LDL^T without pivoting, column by column, and Y = W Hll^-1 for its pairs
+// one thread per landmark: (Hll + lambda I)^-1 by LDL^T without pivoting, column by column, and Y = W Hll^-1 for its pairs.
+// Not ldlt6_solve (se3quat.hpp), though the recurrences are the same: the order is 3 or 6 at run time, lambda is added while the diagonal
+// is read, no pivot is judged, and one factorisation serves `dim` right-hand sides.
 __global__ __launch_bounds__(64) void k_lba_invert(LbArgs a, double lambda)
 {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
@@ -487,7 +408,7 @@ __global__ __launch_bounds__(64) void k_lba_update(LbArgs a, double lambda)
     double u[6], e[7], b[7], o[7], sc = 0.0;
     for (int i = 0; i < 6; i++) { u[i] = a.dx[6 * f + i]; sc = sc + u[i] * (lambda * u[i] + a.bfull[(size_t)f * 6 + i]); }
     for (int i = 0; i < 7; i++) b[i] = P[i];
-    lb_exp(u, e); lb_mul(e, b, o);
+    se3_exp(u, e); se3_mul(e, b, o);
     for (int i = 0; i < 7; i++) Pt[i] = o[i];
     Pt[7] = 0.0;
     a.sc[a.n_lm + f] = sc;
@@ -500,7 +421,7 @@ static __device__ double lb_tree(const double *v, int n, double *red)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     double x = 0.0;
     for (int i = t; i < n; i += LBA_THREADS) x = x + v[i];
-    for (int off = 32; off > 0; off >>= 1) x = x + __shfl_down(x, off, 64);
+    x = wave_sum_down(x);
     __syncthreads();
     if (lane == 0) red[wave] = x;
     __syncthreads();
@@ -773,7 +694,7 @@ extern "C" int hvo_local_ba_optimize(hvo_local_ba *B, const hvo_local_ba_params 
         const float *T = G->Tcw + 12 * (size_t)k;
         const double Rm[9] = { T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10] };
         double *p = &H.state[(size_t)k * 8];
-        lb_quat_from_R(Rm, p); lb_quat_normalize(p);
+        quat_from_R(Rm, p); quat_normalize(p);
         p[4] = T[3]; p[5] = T[7]; p[6] = T[11];
     }
     for (size_t i = 0; i < lm_pos.size(); i++) H.state[(size_t)nkf * 8 + i] = lm_pos[i];
@@ -877,8 +798,8 @@ extern "C" int hvo_local_ba_optimize(hvo_local_ba *B, const hvo_local_ba_params 
     auto depth_positive = [&](int e) {
         const LbEdge &E = H.edge[e];
         double Rt[12]; const double *p = h_state + (size_t)E.kf * 8;
-        lb_quat_to_R(p, Rt); Rt[9] = p[4]; Rt[10] = p[5]; Rt[11] = p[6];
-        double Y[3]; lb_map(Rt, h_state + (size_t)nkf * 8 + (size_t)E.lm * 6, Y);
+        quat_to_R(p, Rt); Rt[9] = p[4]; Rt[10] = p[5]; Rt[11] = p[6];
+        double Y[3]; se3_map(Rt, h_state + (size_t)nkf * 8 + (size_t)E.lm * 6, Y);
         return Y[2] > 0.0;
     };
     write_counts();
@@ -969,7 +890,7 @@ extern "C" int hvo_local_ba_optimize(hvo_local_ba *B, const hvo_local_ba_params 
     for (int o = 0; o < n_perp; o++) { const int e = H.perp_edge[o]; R->perp_erase[o] = e >= 0 && h_chi[e] > P.chi2_gate[2]; }
     for (int k = 0; k < nkf; k++) {
         const double *p = h_state + (size_t)k * 8;
-        double Rm[9]; lb_quat_to_R(p, Rm);
+        double Rm[9]; quat_to_R(p, Rm);
         double *T = R->Tcw_d + 12 * (size_t)k;
         for (int r = 0; r < 3; r++) { T[4 * r] = Rm[3 * r]; T[4 * r + 1] = Rm[3 * r + 1]; T[4 * r + 2] = Rm[3 * r + 2]; T[4 * r + 3] = p[4 + r]; }
         for (int i = 0; i < 12; i++) R->Tcw_f[12 * (size_t)k + i] = (float)T[i];

@@ -31,9 +31,9 @@
 //                                (float)((double)sum * 1.0 + (double)t * 1.0) -- gemm's small-matrix path with alpha = beta = 1
 //   mOw                          -Rcw^T tcw with double sums, times -1.0, rounded to float (match_project_setup's twc)
 //   0.5 * (SP + EP) - mOw        float, element-wise
-//   cv::norm                     sqrt of the double sum of squares, stored to float
+//   cv::norm                     sm_dist3: sqrt of the double sum of squares, stored to float; the 1.2 / 0.8 band is sm_dist_band
 //   Mat::dot on CV_32F           accumulates in double; / the float dist in double; rounded to the float viewCos
-//   PredictScale                 float ratio; log is the FLOAT overload (MapLine.cpp sees <cmath> and `using namespace std` through its
+//   PredictScale                 sm_predict_level (map_gates.hpp), stored without sm_clamp_level: float ratio; log is the FLOAT overload (MapLine.cpp sees <cmath> and `using namespace std` through its
 //                                headers, as DESIGN.md takes elsewhere); float division by logScaleFactor; ceil's float overload
 //   K.inv() (3 x 3 CV_32F)       closed form, cofactors and determinant in double, each entry times 1/det rounded to float
 //   K.inv() * tkl, Rcw * wvec    GEMM with a double work type: products and sums in double, left to right, rounded to float once
@@ -148,26 +148,25 @@ __global__ __launch_bounds__(LL_BLOCK) void k_ll_frustum(LlDev a)
             const float ex = sm_row(P.R, ep[0], ep[1], ep[2], P.t[0]), ey = sm_row(P.R + 3, ep[0], ep[1], ep[2], P.t[1]), ez = sm_row(P.R + 6, ep[0], ep[1], ep[2], P.t[2]);
             if (!(sz < 0.0f || ez < 0.0f)) {
                 const float invz1 = __fdiv_rn(1.0f, sz);
-                const float u1 = __fadd_rn(__fmul_rn(__fmul_rn(a.fx, sx), invz1), a.cx), v1 = __fadd_rn(__fmul_rn(__fmul_rn(a.fy, sy), invz1), a.cy);
+                const float u1 = sm_pinhole(a.fx, sx, invz1, a.cx), v1 = sm_pinhole(a.fy, sy, invz1, a.cy);
                 const float invz2 = __fdiv_rn(1.0f, ez);
-                const float u2 = __fadd_rn(__fmul_rn(__fmul_rn(a.fx, ex), invz2), a.cx), v2 = __fadd_rn(__fmul_rn(__fmul_rn(a.fy, ey), invz2), a.cy);
+                const float u2 = sm_pinhole(a.fx, ex, invz2, a.cx), v2 = sm_pinhole(a.fy, ey, invz2, a.cy);
                 const bool out = (u1 < a.minX || u1 > a.maxX) || (v1 < a.minY || v1 > a.maxY) || (u2 < a.minX || u2 > a.maxX) || (v2 < a.minY || v2 > a.maxY);
                 if (!out) {
-                    const float maxD = __fmul_rn(1.2f, mfMax), minD = __fmul_rn(0.8f, mfMin);
-                    float om[3];
+                    float maxD, minD; sm_dist_band(mfMax, mfMin, &maxD, &minD);
+                    float om[3];                                   // the midpoint in FLOAT (line_fuse.hip forms it in double)
 #pragma unroll
                     for (int k = 0; k < 3; k++) om[k] = __fsub_rn(__fmul_rn(0.5f, __fadd_rn(sp[k], ep[k])), P.Ow[k]);
                     const double d0 = om[0], d1 = om[1], d2 = om[2];
-                    const float dist = (float)sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+                    const float dist = sm_dist3(d0, d1, d2);
                     if (!(dist < minD || dist > maxD)) {
                         const double dot = (d0 * (double)pn[0] + d1 * (double)pn[1]) + d2 * (double)pn[2];
                         const float vc = (float)(dot / (double)dist);
                         if (!(vc < 0.5f)) {
-                            const float ratio = __fdiv_rn(mfMax, dist);
-                            const float lv = ceilf(__fdiv_rn(logf(ratio), a.logsf));
+                            const float lv = sm_predict_lv(mfMax, dist, a.logsf);
                             pass = true;
                             a.s_xyxy[o] = make_float4(u1, v1, u2, v2); a.s_vc[o] = vc;
-                            a.s_lvl[o] = sm_level(lv);
+                            a.s_lvl[o] = sm_level(lv);                 // = sm_predict_level, unclamped (reported and never read), converted after the stores as before
                         }
                     }
                 }

@@ -26,12 +26,12 @@
 //   mRcw * P + mtcw              as k_project_last (match.hip): the row's three products summed in FLOAT left to right, then
 //                                (float)((double)sum * 1.0 + (double)t * 1.0)
 //   PcZ < 0.0f                   as written: z == 0 and -0.0 pass and divide; a NaN projection passes the four bounds tests
-//   invz, u, v, ur               one float division; fx * PcX * invz + cx in float, left to right; u - mbf * invz
+//   invz, u, v, ur               one float division; sm_pinhole (fx * PcX * invz + cx in float, left to right); u - mbf * invz
 //   mOw                          -Rcw^T tcw with double sums, times -1.0, rounded to float (match_project_setup's twc)
 //   P - mOw                      float, element-wise
-//   cv::norm                     sqrt of the double sum of squares, stored to float
+//   cv::norm                     sm_dist3: sqrt of the double sum of squares, stored to float; the 1.2 / 0.8 band is sm_dist_band
 //   PO.dot(Pn) / dist            Mat::dot accumulates in double; / the float dist in double; rounded to the float viewCos
-//   PredictScale                 float ratio; MapPoint.cc writes unique_lock<mutex> unqualified, so it sits under `using namespace std` with
+//   PredictScale                 sm_predict_level and sm_clamp_level (map_gates.hpp): float ratio; MapPoint.cc writes unique_lock<mutex> unqualified, so it sits under `using namespace std` with
 //                                <cmath> reached through its headers, as MapLine.cpp does: log and ceil are the FLOAT overloads, the division
 //                                by mfLogScaleFactor is float; the conversion to int saturates (NaN -> 0) and the clamp to
 //                                [0, mnScaleLevels - 1] is part of the function.  The search reads the level (radius, band).
@@ -142,20 +142,17 @@ __global__ __launch_bounds__(LP_BLOCK) void k_lp_frustum(LpDev a)
             const float xc = sm_row(P.R, X, Y, Z, P.t[0]), yc = sm_row(P.R + 3, X, Y, Z, P.t[1]), zc = sm_row(P.R + 6, X, Y, Z, P.t[2]);
             if (!(zc < 0.0f)) {                                    // Frame.cc:1385: z == 0 and -0.0 pass and divide
                 const float invz = __fdiv_rn(1.0f, zc);
-                const float u = __fadd_rn(__fmul_rn(__fmul_rn(a.fx, xc), invz), a.cx), v = __fadd_rn(__fmul_rn(__fmul_rn(a.fy, yc), invz), a.cy);
+                const float u = sm_pinhole(a.fx, xc, invz, a.cx), v = sm_pinhole(a.fy, yc, invz, a.cy);
                 const bool out = (u < a.minX || u > a.maxX) || (v < a.minY || v > a.maxY);       // (a NaN compares false four times)
                 if (!out) {
-                    const float maxD = __fmul_rn(1.2f, mfMax), minD = __fmul_rn(0.8f, mfMin);
+                    float maxD, minD; sm_dist_band(mfMax, mfMin, &maxD, &minD);
                     const double d0 = __fsub_rn(X, P.Ow[0]), d1 = __fsub_rn(Y, P.Ow[1]), d2 = __fsub_rn(Z, P.Ow[2]);
-                    const float dist = (float)sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+                    const float dist = sm_dist3(d0, d1, d2);
                     if (!(dist < minD || dist > maxD)) {
                         const double dot = (d0 * (double)n0 + d1 * (double)n1) + d2 * (double)n2;
                         const float vc = (float)(dot / (double)dist);
                         if (!(vc < a.vclimit)) {
-                            const float ratio = __fdiv_rn(mfMax, dist);
-                            const float lv = ceilf(__fdiv_rn(logf(ratio), a.logsf));
-                            int l = sm_level(lv);
-                            if (l < 0) l = 0; else if (l >= a.n_levels) l = a.n_levels - 1;      // MapPoint.cc:409-412
+                            const int l = sm_clamp_level(sm_predict_level(mfMax, dist, a.logsf), a.n_levels);     // MapPoint.cc:400-415
                             pass = true;
                             a.s_proj[o] = make_float4(u, v, __fsub_rn(u, __fmul_rn(a.bf, invz)), vc);
                             a.s_lvl[o] = l;

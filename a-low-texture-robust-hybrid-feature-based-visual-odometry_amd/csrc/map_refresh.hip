@@ -60,6 +60,7 @@ struct MrDev {
     void *m_nrm; double *m_wvec; float *m_maxd, *m_mind; uint8_t *m_desc; const uint8_t *m_flags;                            // the map (slot form)
 };
 
+// ham256 (map_gates.hpp) over 32-bit words: the rows lie in LDS as uint32_t and are read word by word; ham256's 64-bit operands would change those loads
 static __device__ __forceinline__ int mr_ham(const uint32_t *d, const uint32_t *e)
 {
     int h = 0;

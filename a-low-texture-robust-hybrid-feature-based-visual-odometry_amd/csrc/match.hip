@@ -18,14 +18,10 @@
 // points of include/hvo.h, which stage their arguments through the context's grow-only call arena and pinned host block
 // (arena.hip) instead of a hipMalloc / hipFree pair per argument.
 #include "hvo_internal.hpp"
+#include "map_gates.hpp"      // ham256
 #include <limits.h>
 #include <string.h>
 #include <vector>
-
-static __device__ __forceinline__ int ham256(const ulonglong4 a, const ulonglong4 b)
-{
-    return __popcll(a.x ^ b.x) + __popcll(a.y ^ b.y) + __popcll(a.z ^ b.z) + __popcll(a.w ^ b.w);
-}
 
 __global__ __launch_bounds__(256) void k_hamming_matrix(const ulonglong4 *__restrict__ q, int nq,
                                                         const ulonglong4 *__restrict__ t, int nt,

@@ -111,8 +111,7 @@ __global__ __launch_bounds__(NP_BLOCK) void k_np_search(NpDev a)
         while (lo < hi) { const int m = (lo + hi) >> 1; if (rnode[m] < node) lo = m + 1; else hi = m; }
         if (!(den == 0.f) && lo < nr && rnode[lo] == node) {
             const bool mono1 = !(a.c_ur && a.c_ur[i] >= 0.f);
-            const unsigned long long *qd = reinterpret_cast<const unsigned long long *>(a.c_desc + (size_t)i * 32);
-            const unsigned long long q0 = qd[0], q1 = qd[1], q2 = qd[2], q3 = qd[3];
+            const ulonglong4 qd = ld256(a.c_desc + (size_t)i * 32);
             const hvo_keypoint *kp2 = a.k_kpun + (size_t)j * a.ct; const float *ur2 = a.k_ur + (size_t)j * a.ct;
             const uint8_t *has2 = a.k_has + (size_t)j * a.ct, *desc2 = a.k_desc + (size_t)j * a.ct * 32;
             const float *sf = a.tab, *sig = a.tab + HVO_MAX_LEVELS;
@@ -120,8 +119,7 @@ __global__ __launch_bounds__(NP_BLOCK) void k_np_search(NpDev a)
             for (int p = p0 + sub; p < pe; p += NP_GROUP) {
                 const int i2 = kidx[p];
                 if (has2[i2]) continue;                                  // ORBmatcher.cc:736 (vbMatched2 is never set)
-                const unsigned long long *d = reinterpret_cast<const unsigned long long *>(desc2 + (size_t)i2 * 32);
-                const int dist = __popcll(q0 ^ d[0]) + __popcll(q1 ^ d[1]) + __popcll(q2 ^ d[2]) + __popcll(q3 ^ d[3]);
+                const int dist = ham256(qd, ld256(desc2 + (size_t)i2 * 32));
                 if (dist > a.th_low) continue;                           // :751
                 const float x2 = kp2[i2].x, y2 = kp2[i2].y; const int o2 = kp2[i2].octave;
                 if (o2 < 0 || o2 >= a.n_levels) continue;

@@ -48,8 +48,6 @@ struct PnpDev {
     uint8_t *ev_inl, *ev_hinl, *best_inl;                       // by frame feature: an event's refined inliers, its record's own inliers, the overall best's
 };
 
-static __device__ __forceinline__ unsigned pnp_xs32(unsigned &s) { unsigned x = s; x ^= x << 13; x ^= x >> 17; x ^= x << 5; s = x; return x; }
-
 // ------------------------------------------------------------------------------------------------ k_pnp_hypotheses
 // block = one wave = four hypotheses of candidate blockIdx.y; a group past the candidate's T repeats hypothesis T - 1 and writes nothing
 // (every lane of the block has to reach every barrier).  Dynamic LDS: the tree buffers, present only when 2 * min_set > 64 rows.
@@ -70,7 +68,7 @@ __global__ __launch_bounds__(64) void k_pnp_hypotheses(PnpDev D)
         unsigned rs = D.seed ^ (0x9E3779B9u * (unsigned)(j * 1024 + it + 1)); if (rs == 0) rs = 0x6D2B79F5u;
         int size = cd.N, nov = 0;
         for (int s = 0; s < ms; s++) {
-            const int r = (int)(pnp_xs32(rs) % (unsigned)size), last = size - 1;
+            const int r = (int)(xs32(rs) % (unsigned)size), last = size - 1;
             int idx = r, lv = last, found = -1;
             for (int q = 0; q < nov; q++) { if (ovp[g][q] == r) { idx = ovv[g][q]; found = q; } if (ovp[g][q] == last) lv = ovv[g][q]; }
             samp[g][s] = idx;

@@ -20,6 +20,7 @@
 // _error per edge.  The host and stream forms launch this kernel alone on the same bytes, so they give bit-identical results.
 #include "frame_view.hpp"
 #include "staged_call.hpp"
+#include "se3quat.hpp"        // quat_from_R .. se3_map, huber, ldlt6_solve
 #include <math.h>
 #include <cmath>
 #include <string.h>
@@ -55,7 +56,8 @@ struct PoArgs {
     float inv_level_sigma2[HVO_MAX_LEVELS];
 };
 
-struct PoPose { double q[4], t[3]; };
+struct PoPose { double q[4], t[3]; };  // se3quat.hpp's pose, passed as .q: seven doubles in a row
+static_assert(offsetof(PoPose, t) == 4 * sizeof(double) && sizeof(PoPose) == 7 * sizeof(double), "q then t, no padding");
 
 struct PoShared {
     double P[13][12];                  // R (row-major) and t of the estimate [0] and the 12 perturbed poses
@@ -68,87 +70,6 @@ struct PoShared {
     int go, robust;
     uint8_t f_pt[PO_MAX_POINTS], f_ln[PO_MAX_LINES], f_vp[PO_MAX_LINES], f_pl[3 * PO_MAX_PLANES];
 };
-
-// ---- SE3Quat (Thirdparty/g2o/g2o/types/se3quat.h) ----
-static __device__ void po_quat_from_R(const double *m, double *q)          // Eigen::Quaterniond(Matrix3d): (w, x, y, z)
-{
-    double t = m[0] + m[4] + m[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0); q[0] = 0.5 * t; t = 0.5 / t;
-        q[1] = (m[7] - m[5]) * t; q[2] = (m[2] - m[6]) * t; q[3] = (m[3] - m[1]) * t;
-    } else {
-        int i = 0;
-        if (m[4] > m[0]) i = 1;
-        if (m[8] > m[4 * i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0); q[1 + i] = 0.5 * t; t = 0.5 / t;
-        q[0] = (m[3 * k + j] - m[3 * j + k]) * t; q[1 + j] = (m[3 * j + i] + m[3 * i + j]) * t; q[1 + k] = (m[3 * k + i] + m[3 * i + k]) * t;
-    }
-}
-static __device__ void po_quat_normalize(double *q)                         // SE3Quat::normalizeRotation
-{
-    if (q[0] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    q[0] = q[0] / n; q[1] = q[1] / n; q[2] = q[2] / n; q[3] = q[3] / n;
-}
-static __device__ void po_quat_to_R(const double *q, double *R)             // Eigen's toRotationMatrix
-{
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-static __device__ void po_mat3(const double *A, const double *B, double *C)
-{
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
-// SE3Quat::exp(update) (se3quat.h:229-263)
-static __device__ void po_exp(const double *u, PoPose &o)
-{
-    const double th = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    const double Om[9] = { 0, -u[2], u[1], u[2], 0, -u[0], -u[1], u[0], 0 };
-    double Om2[9]; po_mat3(Om, Om, Om2);
-    double R[9], V[9];
-    if (th < 0.00001) {
-        for (int i = 0; i < 9; i++) { R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + Om[i]) + Om2[i]; V[i] = R[i]; }
-    } else {
-        const double s = sin(th), c = cos(th);
-        const double a = s / th, b = (1 - c) / (th * th), g = (th - s) / (th * th * th);
-        for (int i = 0; i < 9; i++) {
-            const double I = i % 4 == 0 ? 1.0 : 0.0;
-            R[i] = (I + a * Om[i]) + b * Om2[i];
-            V[i] = (I + b * Om[i]) + g * Om2[i];
-        }
-    }
-    po_quat_from_R(R, o.q); po_quat_normalize(o.q);
-    for (int i = 0; i < 3; i++) o.t[i] = (V[3 * i] * u[3] + V[3 * i + 1] * u[4]) + V[3 * i + 2] * u[5];
-}
-// SE3Quat::operator*
-static __device__ void po_mul(const PoPose &a, const PoPose &b, PoPose &o)
-{
-    const double *p = a.q, *q = b.q;
-    double r[4];
-    r[0] = p[0] * q[0] - p[1] * q[1] - p[2] * q[2] - p[3] * q[3];
-    r[1] = p[0] * q[1] + p[1] * q[0] + p[2] * q[3] - p[3] * q[2];
-    r[2] = p[0] * q[2] + p[2] * q[0] + p[3] * q[1] - p[1] * q[3];
-    r[3] = p[0] * q[3] + p[3] * q[0] + p[1] * q[2] - p[2] * q[1];
-    double Ra[9]; po_quat_to_R(a.q, Ra);
-    double t[3];
-    for (int i = 0; i < 3; i++) t[i] = a.t[i] + ((Ra[3 * i] * b.t[0] + Ra[3 * i + 1] * b.t[1]) + Ra[3 * i + 2] * b.t[2]);
-    po_quat_normalize(r);
-    for (int i = 0; i < 4; i++) o.q[i] = r[i];
-    for (int i = 0; i < 3; i++) o.t[i] = t[i];
-}
-static __device__ void po_pose_Rt(const PoPose &p, double *Rt) { po_quat_to_R(p.q, Rt); Rt[9] = p.t[0]; Rt[10] = p.t[1]; Rt[11] = p.t[2]; }
-
-static __device__ __forceinline__ void po_map(const double *Rt, const double *X, double *Y)
-{
-    Y[0] = ((Rt[0] * X[0] + Rt[1] * X[1]) + Rt[2] * X[2]) + Rt[9];
-    Y[1] = ((Rt[3] * X[0] + Rt[4] * X[1]) + Rt[5] * X[2]) + Rt[10];
-    Y[2] = ((Rt[6] * X[0] + Rt[7] * X[1]) + Rt[8] * X[2]) + Rt[11];
-}
 
 // ---- Plane3D (g2oAddition/Plane3D.h) ----
 static __device__ void po_plane_normalize(double *c)                        // :175-180
@@ -243,22 +164,22 @@ static __device__ bool po_error(const PoArgs &A, const PoEdge &E, const double *
     err[0] = err[1] = err[2] = 0.0;
     switch (E.kind) {
     case PO_MONO: {
-        double X[3]; po_map(Rt, E.a, X);
+        double X[3]; se3_map(Rt, E.a, X);
         err[0] = E.m[0] - (X[0] / X[2] * A.fx + A.cx); err[1] = E.m[1] - (X[1] / X[2] * A.fy + A.cy);
         return false; }
     case PO_STEREO: {
-        double X[3]; po_map(Rt, E.a, X);
+        double X[3]; se3_map(Rt, E.a, X);
         const double iz = (double)(float)(1.0 / X[2]);                      // const float invz = 1.0f / trans_xyz[2]
         const double u = X[0] * iz * A.fx + A.cx;
         err[0] = E.m[0] - u; err[1] = E.m[1] - (X[1] * iz * A.fy + A.cy); err[2] = E.m[2] - (u - A.bf * iz);
         return false; }
     case PO_LINEPT: {
-        double X[3]; po_map(Rt, E.a, X);
+        double X[3]; se3_map(Rt, E.a, X);
         const double u = X[0] / X[2] * A.fx + A.cx, v = X[1] / X[2] * A.fy + A.cy;
         err[0] = (E.m[0] * u + E.m[1] * v) + E.m[2];
         return false; }
     case PO_VP: {
-        double S[3], T[3]; po_map(Rt, E.a, S); po_map(Rt, E.a + 3, T);
+        double S[3], T[3]; se3_map(Rt, E.a, S); se3_map(Rt, E.a + 3, T);
         double dc[3] = { T[0] - S[0], T[1] - S[1], T[2] - S[2] };
         const double *m = E.m;
         const double dot = (m[0] * dc[0] + m[1] * dc[1]) + m[2] * dc[2];
@@ -305,13 +226,6 @@ static __device__ __forceinline__ double po_chi2(const PoEdge &E, const double *
 {
     return (E.info[0] * err[0] * err[0] + E.info[1] * err[1] * err[1]) + E.info[2] * err[2] * err[2];
 }
-// RobustKernelHuber::robustify (core/robust_kernel_impl.cpp:78-91): rho and rho'
-static __device__ __forceinline__ void po_huber(double e, double delta, double &r0, double &r1)
-{
-    const double dsqr = delta * delta;
-    if (e <= dsqr) { r0 = e; r1 = 1.0; }
-    else { const double s = sqrt(e); r0 = 2 * s * delta - dsqr; r1 = delta / s; }
-}
 static __device__ __forceinline__ bool po_level1(const PoShared &sh, int e)
 {
     const int n = sh.n_pts, nl = sh.n_lines;
@@ -327,32 +241,12 @@ static __device__ void po_reduce(PoShared &sh, double *v, int cnt)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int k = 0; k < cnt; k++) {
         double x = v[k];
-        for (int off = 32; off > 0; off >>= 1) x = x + __shfl_down(x, off, 64);
-        if (lane == 0) sh.red[wave][k] = x;
+        for (int off = 32; off > 0; off >>= 1) x = x + __shfl_down(x, off, 64);   // wave_sum_down's text (se3quat.hpp), kept in place: as a call
+        if (lane == 0) sh.red[wave][k] = x;                                        // it reorders k_pose_opt (profiles/shared_readings.txt)
     }
     __syncthreads();
     if (tid < cnt) sh.sum[tid] = ((sh.red[0][tid] + sh.red[1][tid]) + sh.red[2][tid]) + sh.red[3][tid];
     __syncthreads();
-}
-
-// H x = b by LDL^T without pivoting; false when a pivot is not positive
-static __device__ bool po_solve6(const double *H, const double *b, double *x)
-{
-    double L[36], D[6], y[6]; bool ok = true;
-    for (int j = 0; j < 6; j++) {
-        double s = H[6 * j + j];
-        for (int k = 0; k < j; k++) s = s - L[6 * j + k] * L[6 * j + k] * D[k];
-        D[j] = s;
-        if (!(s > 0)) ok = false;
-        for (int i = j + 1; i < 6; i++) {
-            double s2 = H[6 * i + j];
-            for (int k = 0; k < j; k++) s2 = s2 - L[6 * i + k] * L[6 * j + k] * D[k];
-            L[6 * i + j] = s2 / D[j];
-        }
-    }
-    for (int i = 0; i < 6; i++) { double s = b[i]; for (int k = 0; k < i; k++) s = s - L[6 * i + k] * y[k]; y[i] = s; }
-    for (int i = 5; i >= 0; i--) { double s = y[i] / D[i]; for (int k = i + 1; k < 6; k++) s = s - L[6 * k + i] * x[k]; x[i] = s; }
-    return ok;
 }
 
 // robust chi2 of the active edges at pose Rt -> sh.sum[0]
@@ -365,7 +259,7 @@ static __device__ void po_chi_pass(const PoArgs &A, const PoFrame &F, PoShared &
         if (E.kind == PO_NONE) continue;
         double err[3]; po_error(A, E, Rt, err);
         double c = po_chi2(E, err), r0 = c, r1;
-        if (sh.robust) po_huber(c, E.delta, r0, r1);
+        if (sh.robust) huber(c, E.delta, r0, r1);
         acc = acc + r0;
     }
     po_reduce(sh, &acc, 1);
@@ -383,10 +277,10 @@ static __device__ void po_sys_pass(const PoArgs &A, const PoFrame &F, PoShared &
         double err[3]; po_error(A, E, sh.P[0], err);
         const double c = po_chi2(E, err);
         double r0 = c, r1 = 1.0;
-        if (sh.robust) po_huber(c, E.delta, r0, r1);
+        if (sh.robust) huber(c, E.delta, r0, r1);
         double J[3][6];
         if (E.kind <= PO_STEREO) {                                           // types_six_dof_expmap.cpp:266-288, :335-364
-            double X[3]; po_map(sh.P[0], E.a, X);
+            double X[3]; se3_map(sh.P[0], E.a, X);
             const double x = X[0], y = X[1], invz = 1.0 / X[2], iz2 = invz * invz, fx = A.fx, fy = A.fy;
             J[0][0] = x * y * iz2 * fx; J[0][1] = -(1 + (x * x * iz2)) * fx; J[0][2] = y * invz * fx; J[0][3] = -invz * fx; J[0][4] = 0; J[0][5] = x * iz2 * fx;
             J[1][0] = (1 + y * y * iz2) * fy; J[1][1] = -x * y * iz2 * fy; J[1][2] = -x * invz * fy; J[1][3] = 0; J[1][4] = -invz * fy; J[1][5] = y * iz2 * fy;
@@ -475,7 +369,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoArgs A)
         PoPose init;
         {
             const double R[9] = { T0[0], T0[1], T0[2], T0[4], T0[5], T0[6], T0[8], T0[9], T0[10] };
-            po_quat_from_R(R, init.q); po_quat_normalize(init.q);            // Converter::toSE3Quat
+            quat_from_R(R, init.q); quat_normalize(init.q);            // Converter::toSE3Quat
             init.t[0] = T0[3]; init.t[1] = T0[7]; init.t[2] = T0[11];
         }
         for (int rnd = 0; rnd < 4; rnd++) {
@@ -483,11 +377,11 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoArgs A)
             __syncthreads();
             double lam = 0.0, ni = 2.0; int nbad_it = 0, its = 0, trials = 0; double chi_final = 0.0;     // thread 0's
             for (int it = 0; it < 10; it++) {
-                if (tid == 0) po_pose_Rt(sh.est, sh.P[0]);
+                if (tid == 0) se3_Rt(sh.est.q, sh.P[0]);
                 else if (tid <= 12) {
                     const int d = (tid - 1) >> 1;
                     double u[6] = { 0, 0, 0, 0, 0, 0 }; u[d] = ((tid - 1) & 1) ? -PO_DELTA : PO_DELTA;
-                    PoPose ex, p; po_exp(u, ex); po_mul(ex, sh.est, p); po_pose_Rt(p, sh.P[tid]);
+                    PoPose ex, p; se3_exp(u, ex.q); se3_mul(ex.q, sh.est.q, p.q); se3_Rt(p.q, sh.P[tid]);
                 }
                 __syncthreads();
                 po_sys_pass(A, F, sh, nE);
@@ -510,9 +404,9 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoArgs A)
                         double Hl[36];
                         for (int i = 0; i < 36; i++) Hl[i] = H[i];
                         for (int j = 0; j < 6; j++) Hl[7 * j] = Hl[7 * j] + lam;
-                        ok2 = po_solve6(Hl, b, x);
-                        PoPose ex; po_exp(x, ex); po_mul(ex, sh.est, sh.trial);
-                        po_pose_Rt(sh.trial, sh.Plast);
+                        ok2 = ldlt6_solve(Hl, b, x, [](double s) { return !(s > 0); });             // fails on a pivot <= 0 or NaN
+                        PoPose ex; se3_exp(x, ex.q); se3_mul(ex.q, sh.est.q, sh.trial.q);
+                        se3_Rt(sh.trial.q, sh.Plast);
                         for (int j = 0; j < 6; j++) scale = scale + x[j] * (lam * x[j] + b[j]);
                     }
                     __syncthreads();
@@ -552,7 +446,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoArgs A)
             }
             if (tid == 0) {
                 res->iterations[rnd] = its; res->trials[rnd] = trials; res->lambda[rnd] = lam; res->chi2[rnd] = chi_final; res->rounds = rnd + 1;
-                po_pose_Rt(sh.est, sh.Pest);
+                se3_Rt(sh.est.q, sh.Pest);
                 sh.cnt[2] = sh.cnt[3] = 0;
             }
             __syncthreads();

@@ -10,6 +10,7 @@
 #pragma once
 #include "hvo_internal.hpp"
 #include "call_stage.hpp"
+#include "map_gates.hpp"      // sm_level, sm_predict_level .. sm_pinhole, ham256
 #include <string>
 #include <vector>
 
@@ -91,12 +92,6 @@ static __device__ __forceinline__ float sm_row(const float *a, float b0, float b
 {
     float t = __fmul_rn(a[0], b0); t = __fadd_rn(t, __fmul_rn(a[1], b1)); t = __fadd_rn(t, __fmul_rn(a[2], b2));
     return (float)((double)t * 1.0 + (double)c * 1.0);
-}
-
-// the predicted level's conversion to int: saturating, NaN -> 0
-static __device__ __forceinline__ int sm_level(float lv)
-{
-    return lv != lv ? 0 : lv >= 2147483648.0f ? 2147483647 : lv <= -2147483648.0f ? (-2147483647 - 1) : (int)lv;
 }
 
 // the end of a frustum kernel's round for one frame: the slot's pass flag, the block's survivors and the frame's tested slots

@@ -25,7 +25,6 @@ static __device__ __forceinline__ void vcross(const double *a, const double *b, 
 {
     c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
 }
-static __device__ __forceinline__ unsigned vxs32(unsigned &s) { unsigned x = s; x ^= x << 13; x ^= x >> 17; x ^= x << 5; s = x; return x; }
 
 // src/Frame.cc:454-473
 // (every kernel takes the line count from n_ptr when it is given: in the pipelines it only exists on the device)
@@ -195,9 +194,9 @@ __global__ __launch_bounds__(384) void k_vp_hyp(const double *__restrict__ para,
             if (j < VP_NUM2) { const size_t h = (size_t)i * VP_NUM2 + j; for (int q = 0; q < 9; q++) hyp[h * 9 + q] = 0.0; score[h] = 0.0; }
             return;
         }
-        const int idx1 = (int)((vxs32(rs) & 0x7fffffffu) % (unsigned)n);
-        int idx2 = (int)((vxs32(rs) & 0x7fffffffu) % (unsigned)n);
-        while (idx2 == idx1) idx2 = (int)((vxs32(rs) & 0x7fffffffu) % (unsigned)n);
+        const int idx1 = (int)((xs32(rs) & 0x7fffffffu) % (unsigned)n);
+        int idx2 = (int)((xs32(rs) & 0x7fffffffu) % (unsigned)n);
+        while (idx2 == idx1) idx2 = (int)((xs32(rs) & 0x7fffffffu) % (unsigned)n);
         double v[3];
         vcross(para + 3 * idx1, para + 3 * idx2, v);
         if (v[2] == 0) continue;
