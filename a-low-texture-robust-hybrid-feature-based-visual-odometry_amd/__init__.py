@@ -99,6 +99,7 @@ EXPORTS = [
     "hvo_refresh_map_points", "hvo_refresh_map_lines", "hvo_point_map_refresh", "hvo_line_map_refresh",
     "hvo_update_map_planes", "hvo_stream_update_map_planes", "hvo_plane_map_get_points", "hvo_plane_update_transform",
     "hvo_local_ba_create", "hvo_local_ba_destroy", "hvo_local_ba_last_error", "hvo_local_ba_last_ms", "hvo_local_ba_last_profile", "hvo_local_ba_default_params", "hvo_local_ba_optimize",
+    "hvo_kfi_default_params", "hvo_kf_insert_create", "hvo_kf_insert_destroy", "hvo_kf_insert_last_error", "hvo_create_keyframe_features", "hvo_stream_create_keyframe_features",
 ]
 
 
@@ -486,6 +487,74 @@ class LocalBAResult(C.Structure):
 
 LBA_OPTIMISED, LBA_NOTHING, LBA_STOPPED = 0, 1, 2
 LBA_LIMITS = dict(free_kf=64, kf=1024, points=65536, lines=16384, pt_obs=1 << 20, ln_obs=1 << 18, struct=1 << 18)
+
+
+KFI_KEYFRAME, KFI_INIT, KFI_TEMPORAL = 0, 1, 2
+KFI_CREATED, KFI_BAD_LEVEL = 0, 1
+KFI_MAX_FEATURES, KFI_MAX_LINES = 16384, 2048
+
+
+class KfiParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("th_depth", C.c_float), ("n_levels", C.c_int32), ("line_n_levels", C.c_int32), ("line_scale_factor", C.c_float),
+                ("line_geometry", C.c_int32), ("cos_par", C.c_double), ("cos_perp", C.c_double), ("first_point_slot", C.c_int32), ("first_line_slot", C.c_int32)]
+
+
+class KfiFrame(C.Structure):
+    _fields_ = [("kp_un", C.c_void_p), ("depth", C.c_void_p), ("desc", C.c_void_p), ("n_kp", C.c_int32),
+                ("keylines", C.c_void_p), ("ldesc", C.c_void_p), ("lines3d", C.c_void_p), ("n_kl", C.c_int32)]
+
+
+_KFI_IO = (("held_points", np.int32, 1, 0), ("held_lines", np.int32, 1, 1),
+           ("pt_index", np.int32, 1, 0), ("pt_slot", np.int32, 1, 0), ("pt_status", np.uint8, 1, 0), ("pt_pos", np.float32, 3, 0), ("pt_normal", np.float32, 3, 0),
+           ("pt_max_dist", np.float32, 1, 0), ("pt_min_dist", np.float32, 1, 0),
+           ("ln_index", np.int32, 1, 1), ("ln_slot", np.int32, 1, 1), ("ln_status", np.uint8, 1, 1), ("ln_pos", np.float64, 6, 1), ("ln_wvec", np.float64, 3, 1),
+           ("ln_normal", np.float64, 3, 1), ("ln_max_dist", np.float32, 1, 1), ("ln_min_dist", np.float32, 1, 1))
+
+
+class KfiIO(C.Structure):
+    _fields_ = [("n_kp", C.c_int32), ("n_kl", C.c_int32)] + [(k, C.c_void_p) for k, _, _, _ in _KFI_IO] + [("ln_rel", C.c_void_p)]
+
+
+class KfiResult(C.Structure):
+    _fields_ = [("n_kp", C.c_int32), ("n_kl", C.c_int32), ("n_point_entries", C.c_int32), ("n_points_created", C.c_int32), ("n_line_entries", C.c_int32),
+                ("n_lines_created", C.c_int32), ("n_point_candidates", C.c_int32), ("n_line_candidates", C.c_int32), ("kernel_ms", C.c_float), ("status", C.c_int32)]
+
+
+KFI_UNTOUCHED = 119                # the byte the binding fills its output arrays with: an entry the call did not write keeps it
+
+
+def _kfi_args(n_kp, n_kl, mode, th_depth, n_levels, line_n_levels, line_scale_factor, line_geometry, cos_par, cos_perp, first_point_slot, first_line_slot,
+              held_points, held_lines):
+    p = KfiParams(); lib().hvo_kfi_default_params(C.byref(p))
+    p.mode = mode; p.th_depth = th_depth; p.n_levels = n_levels; p.line_n_levels = line_n_levels; p.line_scale_factor = line_scale_factor
+    p.line_geometry = 1 if line_geometry else 0; p.first_point_slot = first_point_slot; p.first_line_slot = first_line_slot
+    if cos_par is not None: p.cos_par = cos_par
+    if cos_perp is not None: p.cos_perp = cos_perp
+    n = (int(n_kp), int(n_kl))
+    a = {k: np.full((max(n[side], 1), comps) if comps > 1 else max(n[side], 1), KFI_UNTOUCHED, dt) for k, dt, comps, side in _KFI_IO}
+    for k, given, side in (("held_points", held_points, 0), ("held_lines", held_lines, 1)):
+        a[k][:] = -1
+        if given is not None: a[k][:n[side]] = np.asarray(given, np.int32).reshape(-1)[:n[side]]
+    a["ln_rel"] = np.full((max(n[1], 1), max(n[1], 1)), KFI_UNTOUCHED, np.uint8)
+    io = KfiIO(); io.n_kp, io.n_kl = n
+    for k in a: setattr(io, k, a[k].ctypes.data)
+    return p, io, a
+
+
+class KfiOutput:
+    """what create_keyframe_features returns: .held_points / .held_lines after the call; per selected point, in creation order, .pt_index,
+    .pt_slot, .pt_status, .pt_pos, .pt_normal, .pt_max_dist, .pt_min_dist; per selected line .ln_index .. .ln_min_dist with .ln_wvec, and
+    .ln_rel (entries x key lines; HVO_KFI_KEYFRAME only); the counts of hvo_kfi_result and .kernel_ms"""
+
+
+def _kfi_finish(r, a, n_kp, n_kl, mode):
+    o = KfiOutput()
+    for f, _ in KfiResult._fields_: setattr(o, f, getattr(r, f))
+    ne = (r.n_point_entries, r.n_line_entries)
+    for k, _, _, side in _KFI_IO:
+        setattr(o, k, a[k][:(n_kp, n_kl)[side]] if k.startswith("held") else a[k][:ne[side]])
+    o.ln_rel = a["ln_rel"].reshape(-1)[:ne[1] * n_kl].reshape(ne[1], n_kl) if mode == KFI_KEYFRAME and n_kl else np.zeros((0, n_kl), np.uint8)
+    return o
 
 
 class KfdbParams(C.Structure):
@@ -1446,6 +1515,14 @@ def lib():
                                                      C.POINTER(LocalPointsIO), C.POINTER(LocalPointsResult)]
         L.hvo_batch_search_local_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalPointsParams),
                                                     C.POINTER(LocalPointsIO), C.POINTER(LocalPointsResult)]
+        L.hvo_kfi_default_params.argtypes = [C.POINTER(KfiParams)]; L.hvo_kfi_default_params.restype = None
+        L.hvo_kf_insert_create.argtypes = [C.c_int]; L.hvo_kf_insert_create.restype = C.c_void_p
+        L.hvo_kf_insert_destroy.argtypes = [C.c_void_p]; L.hvo_kf_insert_destroy.restype = None
+        L.hvo_kf_insert_last_error.argtypes = [C.c_void_p]; L.hvo_kf_insert_last_error.restype = C.c_char_p
+        L.hvo_create_keyframe_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(KfiParams),
+                                                   C.POINTER(KfiFrame), C.POINTER(KfiIO), C.POINTER(KfiResult)]
+        L.hvo_stream_create_keyframe_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p,
+                                                          C.POINTER(KfiParams), C.POINTER(KfiIO), C.POINTER(KfiResult)]
         L.hvo_vocabulary_create.argtypes = [C.c_int] * 6 + [C.c_void_p] * 4 + [C.POINTER(C.c_void_p)]
         L.hvo_vocabulary_load_text.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
         L.hvo_vocabulary_destroy.argtypes = [C.c_void_p]; L.hvo_vocabulary_destroy.restype = None
@@ -1791,6 +1868,35 @@ class PlaneMap:
         x = np.zeros((n, 3), np.float32); m = C.c_int(0)
         self._chk(lib().hvo_plane_map_get_points(self.h, slot, _p(x) if n else None, n, C.byref(m)), "plane_map_get_points")
         return x
+
+
+class KeyFrameInsert:
+    """hvo_kf_insert: the workspace of Context.create_keyframe_features / Stream.create_keyframe_features (a device block, a pinned block,
+    events; grow-only).  Create it once beside the maps and reuse it for every key frame.  Not thread-safe."""
+
+    def __init__(self, device=0):
+        self.h = lib().hvo_kf_insert_create(device)
+        if not self.h:
+            raise HvoError(-3, "hvo_kf_insert_create")
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().hvo_kf_insert_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def last_error(self):
+        return lib().hvo_kf_insert_last_error(self.h).decode()
+
+    def _chk(self, rc, what):
+        if rc != HVO_OK:
+            raise HvoError(rc, "%s: %s" % (what, self.last_error()))
+
+    def debug_fill(self, byte):
+        """test door, not product API: the workspace's two blocks, at the sizes they have, set to `byte`"""
+        f = lib().hvo_debug_kf_insert_fill; f.argtypes = [C.c_void_p, C.c_int]; f.restype = C.c_int
+        self._chk(f(self.h, int(byte)), "debug_fill")
 
 
 class _SlotMap:
@@ -2472,6 +2578,27 @@ class Context:
         r = LocalPointsResult()
         self._chk(lib().hvo_search_local_points(self.h, pmap.h, C.byref(c), _p(T), C.byref(p), C.byref(F), C.byref(io), C.byref(r)), "search_local_points")
         return _lp_finish(r, a, nt)
+
+    def create_keyframe_features(self, kfi, pmap, lmap, cam, Tcw, kp_un=None, depth=None, desc=None, keylines=None, ldesc=None, lines3d=None, mode=KFI_KEYFRAME,
+                                 th_depth=3.0, held_points=None, held_lines=None, first_point_slot=-1, first_line_slot=-1, n_levels=8, line_n_levels=1,
+                                 line_scale_factor=1.2, line_geometry=1, cos_par=None, cos_perp=None):
+        """The new map points and map lines of Tracking::CreateNewKeyFrame (src/Tracking.cc:3032-3187; mode KFI_KEYFRAME), StereoInitialization
+        (KFI_INIT) or the temporal points of UpdateLastFrame (KFI_TEMPORAL) from a frame on host arrays (mvKeysUn, mvDepth, mDescriptors;
+        mvKeylinesUn, mLdesc, mvLines3D), written into the resident PointMap / LineMap from first_*_slot on (-1: returned only; the map may
+        then be None).  kfi: a KeyFrameInsert.  held_*: what each feature holds at entry -> KfiOutput"""
+        n_kp = 0 if kp_un is None else len(kp_un); n_kl = 0 if keylines is None else len(keylines)
+        F = KfiFrame(); F.n_kp = n_kp; F.n_kl = n_kl; keep = []
+        for name, v, dt, n in (("kp_un", kp_un, KEYPOINT_DT, n_kp), ("depth", depth, np.float32, n_kp), ("desc", desc, np.uint8, n_kp),
+                               ("keylines", keylines, KEYLINE_DT, n_kl), ("ldesc", ldesc, np.uint8, n_kl), ("lines3d", lines3d, LINE3D_DT, n_kl)):
+            if n:
+                keep.append(np.ascontiguousarray(v, dt)); setattr(F, name, keep[-1].ctypes.data)
+                assert keep[-1].size == n * (32 if dt is np.uint8 else 1), name
+        p, io, a = _kfi_args(n_kp, n_kl, mode, th_depth, n_levels, line_n_levels, line_scale_factor, line_geometry, cos_par, cos_perp, first_point_slot,
+                             first_line_slot, held_points, held_lines)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12); c = _pose_cam(cam); r = KfiResult()
+        kfi._chk(lib().hvo_create_keyframe_features(kfi.h, self.h, pmap.h if pmap is not None else None, lmap.h if lmap is not None else None, C.byref(c), _p(T),
+                                                    C.byref(p), C.byref(F), C.byref(io), C.byref(r)), "create_keyframe_features")
+        return _kfi_finish(r, a, n_kp, 0 if mode == KFI_TEMPORAL else n_kl, mode)
 
     def batch_search_local_points(self, pmap, cam, Tcw, n_kp, held=None, seen_extra=None, log_scale_factor=float(np.log(np.float32(1.2))), n_levels=8,
                                   bf=None, th=1.0, th_high=100, nn_ratio=0.8, view_cos_limit=0.5):
@@ -3346,6 +3473,20 @@ class Stream:
         r = LocalPointsResult()
         self._chk(lib().hvo_stream_search_local_points(self.h, pmap.h, cur, C.byref(c), _p(T), C.byref(p), C.byref(io), C.byref(r)), "stream_search_local_points")
         return _lp_finish(r, a, int(n_kp))
+
+    def create_keyframe_features(self, kfi, pmap, lmap, cur, cam, Tcw, n_kp, n_kl, mode=KFI_KEYFRAME, th_depth=3.0, held_points=None, held_lines=None,
+                                 first_point_slot=-1, first_line_slot=-1, n_levels=8, line_n_levels=1, line_scale_factor=1.2, line_geometry=1,
+                                 cos_par=None, cos_perp=None):
+        """Context.create_keyframe_features on the resident frame `cur` (needs STAGE_ORB, an LSD stage, STAGE_LINES3D, bf > 0 and depth): the
+        frame's arrays are read where they lie (after line_struct_optimize: the optimised 3-D lines), only held goes up.  n_kp / n_kl: the
+        frame's counts (the lengths of held_points / held_lines) -> KfiOutput"""
+        p, io, a = _kfi_args(n_kp, n_kl, mode, th_depth, n_levels, line_n_levels, line_scale_factor, line_geometry, cos_par, cos_perp, first_point_slot,
+                             first_line_slot, held_points, held_lines)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(12); c = _pose_cam(cam); r = KfiResult()
+        rc = lib().hvo_stream_create_keyframe_features(kfi.h, self.h, pmap.h if pmap is not None else None, lmap.h if lmap is not None else None, cur, C.byref(c), _p(T),
+                                                       C.byref(p), C.byref(io), C.byref(r))
+        kfi._chk(rc, "stream_create_keyframe_features")
+        return _kfi_finish(r, a, r.n_kp, r.n_kl, mode)
 
     def track_manhattan(self, cur, R_last, axes=False):
         """Tracking::TrackManhattanFrame on the resident frame `cur` (needs STAGE_PLANE_TAIL | STAGE_LINES3D and depth): its normals and 3-D

@@ -32,6 +32,10 @@ const FrameNeed need_map_lines     = { "local-map line search", HVO_STAGE_GRIDS 
 static const char k_pu_list[] = "HVO_STAGE_PLANES and HVO_STAGE_PLANE_TAIL";
 const FrameNeed need_plane_update  = { "plane map update", HVO_STAGE_PLANES | HVO_STAGE_PLANE_TAIL, false, FV_DEPTH_STREAM, "no plane clouds", false, false, FV_N_PC, FV_EV_PEAC, k_pu_list, k_pu_list };
 
+static const char k_kfi_list[] = "HVO_STAGE_ORB, an LSD stage and HVO_STAGE_LINES3D";
+const FrameNeed need_new_keyframe  = { "create key-frame features", HVO_STAGE_ORB | HVO_STAGE_LINES3D, true, FV_DEPTH_STREAM, "no mvDepth, no 3-D lines", true, true, FV_N_KP | FV_N_KL,
+                                       FV_EV_ORB | FV_EV_LSD, k_kfi_list, k_kfi_list };
+
 static int refuse(std::string &err, const FrameNeed &nd, const char *a, const char *b = "", const char *c = "")
 {
     err = std::string(nd.what) + ": " + a + b + c;

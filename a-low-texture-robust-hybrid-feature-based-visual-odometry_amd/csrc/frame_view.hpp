@@ -2,7 +2,7 @@
 //
 // A frame stays on the device in two shapes: frame f of a context's resident batch (hvo_batch_run) and a slot of a stream's ring
 // (hvo_stream_submit).  Every resident operation -- Manhattan tracking, plane association, pose optimisation, line structure, the two
-// local-map searches, bag of words, the PnP solver, the key-frame search, Fuse (points and lines), CreateNewMapPoints, CreateNewMapLinesConstraint, the guided frame-to-frame matching -- reads the same arrays of it.  The two builders
+// local-map searches, bag of words, the PnP solver, the key-frame search, Fuse (points and lines), CreateNewMapPoints, CreateNewMapLinesConstraint, CreateNewKeyFrame's points and lines, the guided frame-to-frame matching -- reads the same arrays of it.  The two builders
 // below are the only places that know where those arrays live in an OrbPlan, an LsdView, a PeacView, a TailLayout or a StreamSlot, and
 // the only places that refuse a frame that lacks what an operation needs; the entry points and the *_run functions read a FrameView.
 #pragma once
@@ -44,7 +44,7 @@ struct FrameNeed {
 
 // the rows (frame_view.hip)
 extern const FrameNeed need_manhattan, need_planes, need_pose, need_line_struct, need_local_lines, need_local_points, need_bow, need_bow_search, need_pnp, need_kf_search, need_fuse, need_new_points,
-                       need_guided_points, need_line_match, need_new_lines, need_guided_lines, need_map_lines, need_plane_update, need_fuse_lines;
+                       need_guided_points, need_line_match, need_new_lines, need_guided_lines, need_map_lines, need_plane_update, need_fuse_lines, need_new_keyframe;
 
 // The first n frames of ctx's resident batch.  Refusals in the batch calls' order: n within the batch, stages, depth, bf; then
 // hipSetDevice, the plan lookups and ONE count copy for all n frames.

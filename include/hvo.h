@@ -1774,6 +1774,91 @@ void hvo_local_ba_default_params(hvo_local_ba_params *p);
 int hvo_local_ba_optimize(hvo_local_ba *ba, const hvo_local_ba_params *params, const hvo_local_ba_graph *graph, const volatile int *stop,
                           hvo_local_ba_result *res);
 
+/* ---- Tracking::CreateNewKeyFrame (reference src/Tracking.cc:3032-3187, points and lines), Tracking::StereoInitialization (1364-1400) and
+ * Tracking::UpdateLastFrame (2194-2246); csrc/new_keyframe.hip ----
+ * One call makes the new map points and map lines of a key frame from the frame's own arrays and writes them into the resident maps: the
+ * selection (the depth order, the counters and their breaks), Frame::UnprojectStereo / PtToWorldCoord, the descriptor, the normal and
+ * the distance range of the sole observer, and the structural relation of every new line to the frame's lines.  tests/new_keyframe_ref.py
+ * is the definition; the readings are in csrc/new_keyframe.hip and DESIGN.md section 7.
+ *   HVO_KFI_KEYFRAME   points: the features with depth > 0 in (depth, index) order; the first min(M, max(c, 100) + 1) are processed (c: those
+ *                      with depth <= th_depth) and a processed one is created when held is -1, an unobserved slot or
+ *                      HVO_HELD_FOREIGN_UNOBSERVED.  Lines: the lines whose end points both have z != 0, in ((float)max(sz, ez), index)
+ *                      order; the counter runs over the creatable ones only: the first max(c', 100) + 1 of them are created
+ *   HVO_KFI_INIT       index order, no limit: points with depth > 0; lines with keyline sx > 0 and A[0] != 0.  held is ignored on input
+ *   HVO_KFI_TEMPORAL   the point rule of HVO_KFI_KEYFRAME; nothing is written to a map, lines are not read, the normal is the Frame
+ *                      constructor's (src/MapPoint.cc:45-69: a -0.0 component stays -0.0, where UpdateNormalAndDepth's sum gives +0.0)
+ * A created entry k (creation order) goes to slot first + k, good and observed, and held[i] becomes its slot; with first = -1 (and always in
+ * HVO_KFI_TEMPORAL) the values are returned only and held[i] becomes HVO_HELD_FOREIGN_OBSERVED (HVO_HELD_FOREIGN_UNOBSERVED in
+ * HVO_KFI_TEMPORAL).  In HVO_KFI_KEYFRAME a processed unobserved entry is cleared (-1) before it is created, in HVO_KFI_INIT every entry that is
+ * not created becomes -1.  n_slots moves to first + n_created; slots outside [first, first + n_created) keep their bytes. */
+#define HVO_KFI_KEYFRAME 0
+#define HVO_KFI_INIT     1
+#define HVO_KFI_TEMPORAL 2
+#define HVO_KFI_MAX_FEATURES 16384       /* key points of the frame; more is HVO_ERR_UNSUPPORTED, nothing is written */
+#define HVO_KFI_MAX_LINES    2048        /* key lines of the frame */
+#define HVO_KFI_CREATED   0
+#define HVO_KFI_BAD_LEVEL 1              /* the octave is outside [0, n_levels): the reference would read its table out of bounds.  The entry is counted
+                                          * by the selection, takes no slot and is not created */
+typedef struct hvo_kf_insert hvo_kf_insert;
+typedef struct {
+    int32_t mode;                 /* HVO_KFI_* */
+    float   th_depth;             /* mThDepth */
+    int32_t n_levels;             /* points: mnScaleLevels, 1 .. the context's ORB levels (mvScaleFactors is the context's table) */
+    int32_t line_n_levels;        /* lines: 1 .. 16, with the table sf[0] = 1, sf[l] = sf[l - 1] * line_scale_factor in float (as hvo_mr_params) */
+    float   line_scale_factor;
+    int32_t line_geometry;        /* 1 (default): normal and distance range of a new line as MapLine::UpdateAverageDir gives them for the sole
+                                   * observer (Tracking.cc:3171 uncommented); 0: normal zero and both distances 0, the constructor's members */
+    double  cos_par, cos_perp;    /* mCosThPar, mCosThPerp (src/Manhattan.cpp:28-30) */
+    int32_t first_point_slot, first_line_slot;     /* -1: return the values only */
+} hvo_kfi_params;
+/* HVO_KFI_KEYFRAME, th_depth 3, 8 point levels, 1 line level with scale 1.2, line_geometry 1, cos(3 * 0.0174533) and cos(87 * 0.0174533), both
+ * first slots -1.  th_depth is the caller's mThDepth (mbf * ThDepth / fx of the settings file) */
+void hvo_kfi_default_params(hvo_kfi_params *p);
+typedef struct {                  /* the frame side on host arrays.  Lines are skipped when n_kl == 0 */
+    const hvo_keypoint *kp_un; const float *depth; const uint8_t *desc; int32_t n_kp;      /* mvKeysUn, mvDepth, mDescriptors */
+    const hvo_keyline *keylines; const uint8_t *ldesc; const hvo_line3d *lines3d; int32_t n_kl;    /* mvKeylinesUn, mLdesc, mvLines3D */
+} hvo_kfi_frame;
+typedef struct {                  /* held_*: in and out; every other pointer is an output, may be NULL, and has room for n_kp (points) / n_kl (lines) entries */
+    int32_t n_kp, n_kl;           /* the lengths of held_points / held_lines: at least the frame's counts (the resident form reads the frame's own) */
+    int32_t *held_points;         /* mvpMapPoints[i]: a slot, -1, HVO_HELD_FOREIGN_OBSERVED or HVO_HELD_FOREIGN_UNOBSERVED */
+    int32_t *held_lines;          /* mvpMapLines[i] likewise, against the line map */
+    /* per selected point, in creation order (n_point_entries of them) */
+    int32_t *pt_index, *pt_slot;  /* the feature; its slot (-1: returned only, or not created) */
+    uint8_t *pt_status;           /* HVO_KFI_CREATED / HVO_KFI_BAD_LEVEL */
+    float *pt_pos, *pt_normal;    /* x 3 */
+    float *pt_max_dist, *pt_min_dist;
+    /* per selected line (n_line_entries of them) */
+    int32_t *ln_index, *ln_slot; uint8_t *ln_status;
+    double *ln_pos, *ln_wvec, *ln_normal;          /* x 6 (start, end), x 3, x 3 */
+    float *ln_max_dist, *ln_min_dist;
+    uint8_t *ln_rel;              /* HVO_KFI_KEYFRAME only: n_line_entries x (the frame's key-line count), rows packed: 0 / 1 parallel / 2 perpendicular
+                                   * of the new line against frame line i; frame lines with A[0] == 0.0 and rows of entries that were not created are 0.
+                                   * Room for n_kl x n_kl.  The mvParallelLines[i]->size() > 0 gate stays with the caller */
+} hvo_kfi_io;
+typedef struct {
+    int32_t n_kp, n_kl;                            /* the frame's counts as the call read them */
+    int32_t n_point_entries, n_points_created;     /* entries = created + those refused for their level */
+    int32_t n_line_entries, n_lines_created;
+    int32_t n_point_candidates, n_line_candidates;
+    float   kernel_ms;                             /* device time of the call's launches */
+    int32_t status;
+} hvo_kfi_result;
+/* The handle owns a grow-only workspace on its device (a device block, a pinned block, events): create it once beside the maps. */
+hvo_kf_insert *hvo_kf_insert_create(int device);
+void hvo_kf_insert_destroy(hvo_kf_insert *k);
+const char *hvo_kf_insert_last_error(const hvo_kf_insert *k);
+/* On host arrays.  pmap / lmap may be NULL where the matching first_*_slot is -1 and held names no slot.  Refusals are whole and write
+ * nothing (held, the maps' bytes and n_slots stay): more than HVO_KFI_MAX_* features (HVO_ERR_UNSUPPORTED); a NaN among the line depths, which
+ * leaves the reference's sort undefined, a held value outside the map, a missing array (HVO_ERR_INVALID_ARG).  One launch sequence, one
+ * download, one synchronisation. */
+int hvo_create_keyframe_features(hvo_kf_insert *k, hvo_ctx *ctx, hvo_point_map *pmap, hvo_line_map *lmap, const hvo_camera *cam, const float Tcw[12],
+                                 const hvo_kfi_params *params, const hvo_kfi_frame *frame, hvo_kfi_io *io, hvo_kfi_result *res);
+/* On the resident frame `cur` of a stream: mvKeysUn, mvDepth, the descriptors, the key lines and the 3-D lines are read where they lie (after
+ * hvo_stream_line_struct_optimize: the optimised lines); only held goes up.  The stream must run HVO_STAGE_ORB, an LSD stage and
+ * HVO_STAGE_LINES3D, with bf > 0, and the frame must have been submitted with depth. */
+int hvo_stream_create_keyframe_features(hvo_kf_insert *k, hvo_stream *s, hvo_point_map *pmap, hvo_line_map *lmap, int64_t cur, const hvo_camera *cam,
+                                        const float Tcw[12], const hvo_kfi_params *params, hvo_kfi_io *io, hvo_kfi_result *res);
+
 /* Page-lock (hipHostRegister) / unlock a caller's host buffer. Images handed to hvo_batch_upload / hvo_stream_submit and result
  * slabs handed to hvo_batch_download move by DMA at the link rate when they are pinned (no staging copy on either side); equally
  * sized, equally spaced pinned destinations (e.g. labels8 of consecutive frames in one slab) take a single strided DMA. */

@@ -1088,6 +1088,70 @@ private:
     hvo_camera cam_; hvo_local_points_params p_;
 };
 
+// The map-making steps of Tracking over the resident maps (hvo_kf_insert, csrc/new_keyframe.hip): the new map points and map lines of
+// CreateNewKeyFrame (src/Tracking.cc:3032-3187), of StereoInitialization (1364-1400) and the temporal points of UpdateLastFrame (2194-2246).
+// io.held_points / io.held_lines carry mvpMapPoints / mvpMapLines as slots in and out; per created entry io returns the feature index, the
+// slot, position, normal and distance range for `new MapPoint` / `new MapLine`.  AddObservation, AddMapPoint, UpdateManhAxis, ids and the
+// KeyFrame object stay with the caller, and so does the mvParallelLines[i]->size() > 0 gate on io.ln_rel.  The object owns the call's
+// workspace: make one beside the maps.  Not thread-safe.
+class Tracking {
+public:
+    explicit Tracking(const hvo_camera &cam, float thDepth, int nLevels = 8, int lineLevels = 1, float lineScale = 1.2f, int device = 0)
+        : k_(hvo_kf_insert_create(device)), cam_(cam)
+    {
+        if (!k_) throw Error(HVO_ERR_HIP, "hvo_kf_insert_create");
+        hvo_kfi_default_params(&p_);
+        p_.th_depth = thDepth; p_.n_levels = nLevels; p_.line_n_levels = lineLevels; p_.line_scale_factor = lineScale;
+    }
+    ~Tracking() { hvo_kf_insert_destroy(k_); }
+    Tracking(const Tracking &) = delete;
+    Tracking &operator=(const Tracking &) = delete;
+    hvo_kfi_params &params() { return p_; }                      // line_geometry, cos_par, cos_perp
+    const char *lastError() const { return hvo_kf_insert_last_error(k_); }
+    // on host arrays; the new entries go to firstPointSlot / firstLineSlot onwards (-1: returned only)
+    hvo_kfi_result CreateNewKeyFrame(hvo_ctx *ctx, PointMap &points, LineMap &lines, const float Tcw[12], const hvo_kfi_frame &frame, hvo_kfi_io &io,
+                                     int firstPointSlot, int firstLineSlot)
+    {
+        return run(ctx, nullptr, 0, &points, &lines, HVO_KFI_KEYFRAME, Tcw, &frame, io, firstPointSlot, firstLineSlot);
+    }
+    hvo_kfi_result StereoInitialization(hvo_ctx *ctx, PointMap &points, LineMap &lines, const float Tcw[12], const hvo_kfi_frame &frame, hvo_kfi_io &io,
+                                        int firstPointSlot = 0, int firstLineSlot = 0)
+    {
+        return run(ctx, nullptr, 0, &points, &lines, HVO_KFI_INIT, Tcw, &frame, io, firstPointSlot, firstLineSlot);
+    }
+    // the temporal points of the last frame: returned only, io.held_points[i] becomes HVO_HELD_FOREIGN_UNOBSERVED
+    hvo_kfi_result UpdateLastFrame(hvo_ctx *ctx, const PointMap &points, const float Tcw[12], const hvo_kfi_frame &frame, hvo_kfi_io &io)
+    {
+        return run(ctx, nullptr, 0, &points, nullptr, HVO_KFI_TEMPORAL, Tcw, &frame, io, -1, -1);
+    }
+    // on the resident frame `cur` of a stream (HVO_STAGE_ORB, an LSD stage, HVO_STAGE_LINES3D, bf > 0, depth); call before collect() releases the slot
+    hvo_kfi_result CreateNewKeyFrame(FrameStream &fs, int64_t cur, PointMap &points, LineMap &lines, const float Tcw[12], hvo_kfi_io &io, int firstPointSlot, int firstLineSlot)
+    {
+        return run(nullptr, fs.get(), cur, &points, &lines, HVO_KFI_KEYFRAME, Tcw, nullptr, io, firstPointSlot, firstLineSlot);
+    }
+    hvo_kfi_result StereoInitialization(FrameStream &fs, int64_t cur, PointMap &points, LineMap &lines, const float Tcw[12], hvo_kfi_io &io, int firstPointSlot = 0,
+                                        int firstLineSlot = 0)
+    {
+        return run(nullptr, fs.get(), cur, &points, &lines, HVO_KFI_INIT, Tcw, nullptr, io, firstPointSlot, firstLineSlot);
+    }
+    hvo_kfi_result UpdateLastFrame(FrameStream &fs, int64_t last, const PointMap &points, const float Tcw[12], hvo_kfi_io &io)
+    {
+        return run(nullptr, fs.get(), last, &points, nullptr, HVO_KFI_TEMPORAL, Tcw, nullptr, io, -1, -1);
+    }
+private:
+    hvo_kfi_result run(hvo_ctx *ctx, hvo_stream *s, int64_t cur, const PointMap *pm, const LineMap *lm, int mode, const float Tcw[12], const hvo_kfi_frame *frame,
+                       hvo_kfi_io &io, int fp, int fl)
+    {
+        hvo_kfi_params p = p_; p.mode = mode; p.first_point_slot = fp; p.first_line_slot = fl;
+        hvo_kfi_result res;
+        hvo_point_map *hp = pm ? pm->get() : nullptr; hvo_line_map *hl = lm ? lm->get() : nullptr;
+        if (s) check(hvo_stream_create_keyframe_features(k_, s, hp, hl, cur, &cam_, Tcw, &p, &io, &res), "hvo_stream_create_keyframe_features");
+        else check(hvo_create_keyframe_features(k_, ctx, hp, hl, &cam_, Tcw, &p, frame, &io, &res), "hvo_create_keyframe_features");
+        return res;
+    }
+    hvo_kf_insert *k_; hvo_camera cam_; hvo_kfi_params p_;
+};
+
 // ORBVocabulary (include/ORBVocabulary.h = DBoW2's TemplatedVocabulary<FORB::TDescriptor, FORB>) resident on one device, read-only.  BowVectors is
 // what Frame holds afterwards: mBowVec as (word, value) pairs in ascending word order, mFeatVec as CSR (node ids ascending, rows of ascending
 // feature indices), and the per-feature node ids SearchByBoW takes for a key frame.
