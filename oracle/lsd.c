@@ -53,6 +53,15 @@ typedef struct {
     uint8_t *used;
 } lsd_t;
 
+/* Path counters (orc_lsd_detect_paths): which branches of the growing a given image reaches.  NULL outside that entry, so
+ * orc_lsd_detect computes what it always did; the counters only observe.  Counted per region or per expanded point, never per
+ * neighbour test.  Not thread safe (one static pointer), like the readings. */
+static long long *g_cnt = NULL;
+static long long g_big = 0;
+static int g_wrap = 0;         /* the growth in progress took the 0 / 2pi wrap branch of is_aligned for a point it then added */
+#define CNT_ADD(k)      do { if (g_cnt) g_cnt[k]++; } while (0)
+#define CNT_MAX(k, v)   do { if (g_cnt && (long long)(v) > g_cnt[k]) g_cnt[k] = (long long)(v); } while (0)
+
 static int reflect101(int p, int n)
 {
     if (n == 1) return 0;
@@ -139,7 +148,10 @@ static int is_aligned(const lsd_t *L, int addr, double theta, double prec)
     if (a == NOTDEF) return 0;
     double n_theta = theta - a;
     if (n_theta < 0) n_theta = -n_theta;
-    if (n_theta > M_3_2_PI) { n_theta -= M_2__PI; if (n_theta < 0) n_theta = -n_theta; }
+    if (n_theta > M_3_2_PI) {
+        n_theta -= M_2__PI; if (n_theta < 0) n_theta = -n_theta;
+        if (g_cnt && n_theta <= prec) g_wrap++;
+    }
     return n_theta <= prec;
 }
 
@@ -154,7 +166,9 @@ static void region_grow(lsd_t *L, int sx, int sy, regpt *reg, int *reg_size, dou
     float sumdx = (float)cos(*reg_angle);
     float sumdy = (float)sin(*reg_angle);
     L->used[addr] = USED;
-    for (int i = 0; i < *reg_size; ++i)
+    g_wrap = 0;
+    for (int i = 0; i < *reg_size; ++i) {
+        CNT_MAX(ORC_LSD_MAX_PENDING, *reg_size - i);         /* points added and not yet expanded, this one included */
         for (int xx = reg[i].x - 1; xx <= reg[i].x + 1; ++xx)
             for (int yy = reg[i].y - 1; yy <= reg[i].y + 1; ++yy) {
                 int c_addr = xx + yy * L->w;
@@ -172,6 +186,8 @@ static void region_grow(lsd_t *L, int sx, int sy, regpt *reg, int *reg_size, dou
                     *reg_angle = orc_fast_atan2(sumdy, sumdx) * DEG_TO_RADS;
                 }
             }
+    }
+    if (g_wrap) { CNT_ADD(ORC_LSD_WRAP_GROWTHS); if (g_cnt) g_cnt[ORC_LSD_WRAP_POINTS] += g_wrap; }
 }
 
 static double get_theta(const regpt *reg, int reg_size, double x, double y, double reg_angle, double prec)
@@ -227,6 +243,8 @@ static int reduce_region_radius(lsd_t *L, regpt *reg, int *reg_size, double reg_
     double radSq = radSq1 > radSq2 ? radSq1 : radSq2;
     while (density < density_th) {
         radSq *= 0.75 * 0.75;
+        CNT_ADD(ORC_LSD_REDUCE_ROUNDS); CNT_MAX(ORC_LSD_MAX_REDUCE_START, *reg_size);
+        if (*reg_size > g_big) CNT_ADD(ORC_LSD_REDUCE_ROUNDS_BIG);
         for (int i = 0; i < *reg_size; ++i) {
             if (dist2(xc, yc, (double)reg[i].x, (double)reg[i].y) > radSq) {
                 L->used[reg[i].x + reg[i].y * L->w] = NOTUSED;
@@ -235,7 +253,7 @@ static int reduce_region_radius(lsd_t *L, regpt *reg, int *reg_size, double reg_
                 --i;
             }
         }
-        if (*reg_size < 2) return 0;
+        if (*reg_size < 2) { CNT_ADD(ORC_LSD_REJECT_REDUCE); return 0; }
         region2rect(reg, *reg_size, reg_angle, prec, p, rec);
         density = (double)*reg_size / (distd(rec->x1, rec->y1, rec->x2, rec->y2) * rec->width);
     }
@@ -246,6 +264,9 @@ static int refine(lsd_t *L, regpt *reg, int *reg_size, double reg_angle, double 
 {
     double density = (double)*reg_size / (distd(rec->x1, rec->y1, rec->x2, rec->y2) * rec->width);
     if (density >= density_th) return 1;
+    const int n_first = *reg_size;
+    CNT_ADD(ORC_LSD_REFINES); CNT_MAX(ORC_LSD_MAX_REFINE, n_first);
+    if (n_first > g_big) CNT_ADD(ORC_LSD_REFINES_BIG);
     double xc = (double)reg[0].x, yc = (double)reg[0].y;
     const double ang_c = reg[0].angle;
     double sum = 0, s_sum = 0;
@@ -261,8 +282,13 @@ static int refine(lsd_t *L, regpt *reg, int *reg_size, double reg_angle, double 
     }
     double mean_angle = sum / (double)n;
     double tau = 2.0 * sqrt((s_sum - 2.0 * mean_angle * sum) / (double)n + mean_angle * mean_angle);
+    if (tau <= 0) CNT_ADD(ORC_LSD_TAU_LE_0);
+    else if (tau > prec) CNT_ADD(ORC_LSD_TAU_GT_PREC);
+    else if (!(tau == tau)) CNT_ADD(ORC_LSD_TAU_NAN);
     region_grow(L, reg[0].x, reg[0].y, reg, reg_size, &reg_angle, tau);
-    if (*reg_size < 2) return 0;
+    if (*reg_size > n_first) CNT_ADD(ORC_LSD_REGROW_LARGER);
+    CNT_MAX(ORC_LSD_MAX_FIRST_PLUS_REGROW, n_first + *reg_size);
+    if (*reg_size < 2) { CNT_ADD(ORC_LSD_REJECT_REGROW); return 0; }
     region2rect(reg, *reg_size, reg_angle, prec, p, rec);
     density = (double)*reg_size / (distd(rec->x1, rec->y1, rec->x2, rec->y2) * rec->width);
     if (density < density_th) return reduce_region_radius(L, reg, reg_size, reg_angle, prec, p, rec, density, density_th);
@@ -324,6 +350,8 @@ int orc_lsd_detect(const uint8_t *gray, int w, int h, int stride, float *segs, i
             if (L.used[adx] != NOTUSED || L.angles[adx] == NOTDEF) continue;
             int reg_size; double reg_angle;
             region_grow(&L, x, y, reg, &reg_size, &reg_angle, prec);
+            CNT_ADD(ORC_LSD_REGIONS); CNT_MAX(ORC_LSD_MAX_REGION, reg_size);
+            if (reg_size > g_big) CNT_ADD(ORC_LSD_REGIONS_BIG);
             if ((unsigned)reg_size < min_reg_size) continue;
             rect_t rec;
             region2rect(reg, reg_size, reg_angle, prec, p, &rec);
@@ -336,6 +364,19 @@ int orc_lsd_detect(const uint8_t *gray, int w, int h, int stride, float *segs, i
     *n_out = n;
     free(reg); free(L.scaled); free(L.angles); free(L.modgrad); free(L.used);
     return 0;
+}
+
+/* orc_lsd_detect with the path counters on: counts[ORC_LSD_NCOUNT] (oracle.h), `big` = the size above which the *_BIG counters count.
+ * The segments are computed as always and dropped but for their number. */
+int orc_lsd_detect_paths(const uint8_t *gray, int w, int h, int stride, int big, long long *counts)
+{
+    float seg4[4]; int n = 0;
+    memset(counts, 0, sizeof(long long) * ORC_LSD_NCOUNT);
+    g_cnt = counts; g_big = big;
+    const int rc = orc_lsd_detect(gray, w, h, stride, seg4, 1, &n);
+    g_cnt = NULL;
+    counts[ORC_LSD_SEGMENTS] = n;
+    return rc;
 }
 
 /* LSDDetectorC::detectImpl keyline construction for octave 0 (LSDDetector_custom.cpp:161-196) */

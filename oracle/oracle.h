@@ -126,6 +126,32 @@ int   orc_grid_line_cells(double x1, double y1, double x2, double y2, int *cx, i
 /* ---------------- lines (lsd.c, lbd.c) ---------------- */
 /* cv::LineSegmentDetector (LSD_REFINE_STD defaults) on a CV_8UC1 image: segs = n x 4 floats */
 int  orc_lsd_detect(const uint8_t *gray, int w, int h, int stride, float *segs, int cap, int *n_out);
+/* the same run with path counters: which branches of region growing / refine / reduce_region_radius the image reaches (tests/lsd_cases.py).
+ * `big`: the size above which the *_BIG counters count.  Counted per region or per expanded point. */
+enum {
+    ORC_LSD_REGIONS = 0,            /* regions grown from a seed */
+    ORC_LSD_MAX_REGION,             /* largest first growth */
+    ORC_LSD_REGIONS_BIG,            /* first growths of more than `big` points */
+    ORC_LSD_REFINES,                /* refine() below the density threshold: the region is released and grown again */
+    ORC_LSD_MAX_REFINE,             /* largest region that was */
+    ORC_LSD_REFINES_BIG,
+    ORC_LSD_REDUCE_ROUNDS,          /* rounds of reduce_region_radius */
+    ORC_LSD_MAX_REDUCE_START,       /* largest region at the start of a round */
+    ORC_LSD_REDUCE_ROUNDS_BIG,
+    ORC_LSD_TAU_LE_0,               /* re-growths with tau <= 0 (alignment = equality of angles) */
+    ORC_LSD_TAU_GT_PREC,            /* re-growths more tolerant than the first growth */
+    ORC_LSD_TAU_NAN,
+    ORC_LSD_REGROW_LARGER,          /* re-growths larger than the first growth */
+    ORC_LSD_MAX_FIRST_PLUS_REGROW,  /* largest first growth + re-growth (what a list holding both must hold) */
+    ORC_LSD_REJECT_REGROW,          /* re-growth of fewer than 2 points */
+    ORC_LSD_REJECT_REDUCE,          /* reduce_region_radius left fewer than 2 points */
+    ORC_LSD_MAX_PENDING,            /* most points added and not yet expanded */
+    ORC_LSD_WRAP_GROWTHS,           /* growths that added a point through the 0 / 2pi wrap branch of isAligned */
+    ORC_LSD_WRAP_POINTS,            /* points added through it */
+    ORC_LSD_SEGMENTS,
+    ORC_LSD_NCOUNT
+};
+int  orc_lsd_detect_paths(const uint8_t *gray, int w, int h, int stride, int big, long long *counts);
 /* LINEextractor::operator() (src/LineExtractor.cpp:329-380) */
 int  orc_line_extract(const uint8_t *gray, int w, int h, int stride, int nfeatures,
                       orc_keyline *kls, uint8_t *desc32, double *linefn3, int cap, int *n_out);

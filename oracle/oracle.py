@@ -84,6 +84,8 @@ def _bind_optional(L):
     if hasattr(L, "orc_lsd_detect"):
         L.orc_lsd_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                      C.POINTER(C.c_int)]
+    if hasattr(L, "orc_lsd_detect_paths"):
+        L.orc_lsd_detect_paths.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "orc_line_extract"):
         L.orc_line_extract.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -371,6 +373,20 @@ def lsd_detect(gray, cap=16384):
     segs = np.zeros((cap, 4), np.float32); n = C.c_int(0)
     lib().orc_lsd_detect(_p(gray), w, h, gray.strides[0], _p(segs), cap, C.byref(n))
     return segs[: min(n.value, cap)].copy()
+
+
+LSD_PATH_COUNTERS = ("regions", "max_region", "regions_big", "refines", "max_refine", "refines_big", "reduce_rounds", "max_reduce_start",
+                     "reduce_rounds_big", "tau_le_0", "tau_gt_prec", "tau_nan", "regrow_larger", "max_first_plus_regrow", "reject_regrow",
+                     "reject_reduce", "max_pending", "wrap_growths", "wrap_points", "segments")         # oracle.h: ORC_LSD_*
+
+
+def lsd_path_counts(gray, big=4096):
+    """orc_lsd_detect with its path counters on -> {name: count}: which branches of region growing, refine and reduce_region_radius
+    the image reaches; `big`: the region size above which the *_big counters count"""
+    gray = np.ascontiguousarray(gray, np.uint8); h, w = gray.shape
+    cnt = np.zeros(len(LSD_PATH_COUNTERS), np.int64)
+    lib().orc_lsd_detect_paths(_p(gray), w, h, gray.strides[0], int(big), _p(cnt))
+    return dict(zip(LSD_PATH_COUNTERS, (int(v) for v in cnt)))
 
 
 def line_extract(gray, nfeatures=200):

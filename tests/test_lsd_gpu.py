@@ -296,7 +296,8 @@ def test_lines_async_growing(hvo, orc, synth, monkeypatch, workers, early):
 
 
 def test_lines_async_1280(hvo, orc, synth, monkeypatch):
-    """the async growing at 1280x960 (5.4 k seeds, regions of up to thousands of points: private lists that overflow go to the frontier)"""
+    """the async growing at 1280x960 (5.1 k seeds, regions of up to 573 points: every one fits a worker's private list, so no list overflows
+    here -- tests/test_lsd_crafted.py asserts that, and tests/test_lsd_crafted_gpu.py is where lists that overflow go to the frontier)"""
     monkeypatch.setenv("HVO_LSD_ASYNC", "32")
     g = synth.make_gray("std", 0x5EED0003, 1280, 960)
     kl_o, d_o, fn_o = orc.line_extract(g)
