@@ -20,6 +20,8 @@ import os
 import subprocess
 import numpy as np
 
+from . import _marshal as _m
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 # HVO_LIB: developer knob, points the binding at an experimental build of the same library (A/B measurements)
@@ -57,9 +59,6 @@ LINE3D_DT = np.dtype([("A", "<f8", 3), ("B", "<f8", 3), ("line_nor", "<f8", 3), 
                       ("n_samples", "<i4"), ("n_inliers", "<i4"), ("inlier_mask", "<u4"), ("pad", "<i4")])
 PLANE_CLOUD_DT = np.dtype([("coef", "<f4", 4), ("valid", "<i4"), ("gate_ok", "<i4"), ("first", "<i4"), ("n_points", "<i4"), ("n_pixels", "<i4"), ("n_inliers", "<i4")])
 SURFACE_NORMAL_DT = np.dtype([("normal", "<f4", 3), ("position", "<f4", 3), ("frame_x", "<i4"), ("frame_y", "<i4")])
-assert KEYPOINT_DT.itemsize == 28 and KEYLINE_DT.itemsize == 68 and PLANE_DT.itemsize == 64 and LINE3D_DT.itemsize == 104
-assert PLANE_CLOUD_DT.itemsize == 40 and SURFACE_NORMAL_DT.itemsize == 32
-
 READING_BLUR_FLOAT, READING_LSD_8U = 1, 2
 
 EXPORTS = [
@@ -155,10 +154,6 @@ class MfResult(C.Structure):
                     density=np.array(self.density[:], np.float32), found=list(self.found), n_found=self.n_found, n_in_cone=list(self.n_in_cone),
                     n_selected=list(self.n_selected), min_num_sn=self.min_num_sn, tracked=self.tracked, status=self.status)
 
-
-assert C.sizeof(MfResult) == 21 * 4 + 13 * 4
-
-
 class PlaneMatch(C.Structure):
     """hvo_plane_match: one PlaneMatcher::SearchMapByCoefficients call (slots, -1 = none)"""
     _fields_ = [("n_planes", C.c_int32), ("n_matches", C.c_int32), ("match", C.c_int32 * 64), ("vertical", C.c_int32 * 64),
@@ -169,9 +164,6 @@ class PlaneMatch(C.Structure):
         return dict(n_planes=n, n_matches=self.n_matches, match=np.array(self.match[:n], np.int32), vertical=np.array(self.vertical[:n], np.int32),
                     parallel=np.array(self.parallel[:n], np.int32), plane_idx=np.array(self.plane_idx[:n], np.int32),
                     dist=np.array(self.dist[:n], np.float32), pM=np.array([r[:] for r in self.pM], np.float32).reshape(64, 4)[:n])
-
-
-assert C.sizeof(PlaneMatch) == 8 + 5 * 64 * 4 + 64 * 16
 
 PLANE_UPDATE_MERGE, PLANE_UPDATE_INSERT, PLANE_UPDATE_MAX_POINTS = 0, 1, 1 << 20
 
@@ -269,10 +261,6 @@ class LineOptResult(C.Structure):
                 ("rounds", C.c_int32), ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2), ("n_flagged", C.c_int32 * 2),
                 ("written_back", C.c_int32), ("status", C.c_int32), ("lam", C.c_double * 2), ("chi2", C.c_double * 2)]
 
-
-assert C.sizeof(LineStructParams) == 56 and C.sizeof(LineStructProblem) == 24 and C.sizeof(LineOptResult) == 88
-
-
 LINE_MAP_MAX_QUERIES = 16384      # lines in view per call (the search core's limit)
 
 
@@ -307,59 +295,109 @@ class LocalLinesResult(C.Structure):
             d[k] = getattr(self, k, None)
         return d
 
+# ---------------------------------------------------------------------------------------
+# the binding records (_marshal): each call family's arrays declared once, and the argument building its Context and Stream forms share
+# ---------------------------------------------------------------------------------------
+_i8, _u8, _i32, _f32, _f64 = np.int8, np.uint8, np.int32, np.float32, np.float64
+REQ, OPT = _m.REQ, _m.OPT
 
-assert C.sizeof(LocalLinesResult) == 32
+
+def _ret(obj, rc, name, finish, check=True):
+    """the return path of a Context or Stream call: obj._chk raises, obj._last_error is its handle's message"""
+    return _m.returned(rc, obj._last_error, name, obj._chk, finish, check, HVO_OK)
+
+
+def _results(table, R, lens):
+    """one result record of R per entry of lens (the table's lengths) -> (R, what _finished needs)"""
+    return R, [(table.alloc(R[j], **l), l) for j, l in enumerate(lens)]
+
+
+def _finished(table, R, keep, ok=True):
+    return [table.finish(R[j], a, ok, **l) for j, (a, l) in enumerate(keep)]
+
+
+def _entry(f, dt, cols=1, length="n"):
+    return (f, dt, cols, length, None)
+
+
+# ---- the local-map searches: held per key feature, everything else per slot in view; 0 / -1 / 256 before the call
+def _map_out(proj_cols, per_key=()):
+    q = lambda f, dt, cols=1: (f, dt, cols, "capq", "n_in_view")
+    return _m.Outputs([_entry("held", _i32, 1, "n_key"), q("in_view_slot", _i32), q("proj", _f32, proj_cols), q("view_cos", _f32), q("level", _i32),
+                       q("match_idx", _i32), q("match_dist", _i32)] + [_entry(f, _i32, 1, "n_key") for f in per_key], 0,
+                      fill=dict(held=-1, match_idx=-1, match_dist=256))
+
+
+LL_OUT, LP_OUT = _map_out(4, ("n_par", "n_perp")), _map_out(3)
 
 
 def _ll_params(bounds4, log_scale_factor, th, nn_ratio):
-    p = LocalLinesParams()
-    b = (0.0, 1.0, 0.0, 1.0) if bounds4 is None else [float(v) for v in np.asarray(bounds4).reshape(4)]
-    for k in range(4): p.bounds[k] = b[k]
+    p = LocalLinesParams(); _m.bounds(p.bounds, bounds4)
     p.log_scale_factor = log_scale_factor; p.th = th; p.nn_ratio = nn_ratio
     return p
 
 
-def _map_io(io, n_key, what, n_slots, max_queries, held, seen_extra, proj_cols, **more):
-    """the part of _ll_io / _lp_io that is the same: fills io (n_kl / n_kp already set) -> (io, dict of the arrays it points at); more: further
-    arrays (None: not wanted)"""
-    capq = max(1, min(n_slots, max_queries)); nk = max(n_key, 1)
-    h = np.full(nk, -1, np.int32)
+def _lp_params(bounds4, log_scale_factor, n_levels, bf, th, th_high, nn_ratio, view_cos_limit):
+    p = LocalPointsParams(); _m.bounds(p.bounds, bounds4)
+    p.log_scale_factor = log_scale_factor; p.n_levels = n_levels; p.bf = bf; p.th = th; p.th_high = th_high; p.nn_ratio = nn_ratio
+    p.view_cos_limit = view_cos_limit
+    return p
+
+
+def _map_io(io, table, n_key, what, n_slots, max_queries, held, seen_extra):
+    """fills io (n_kl / n_kp already set) -> (io, the arrays it points at).  held stays -1 beyond the given entries"""
+    a = table.alloc(io, n_key=n_key, capq=max(1, min(n_slots, max_queries)))
     if held is not None:
         hh = np.asarray(held, np.int32).reshape(-1)
         if len(hh) != n_key:
             raise ValueError("held must have one entry per key %s (%d)" % (what, n_key))
-        h[:n_key] = hh
-    ex = np.ascontiguousarray([] if seen_extra is None else seen_extra, np.int32).reshape(-1)
-    a = dict(held=h, seen_extra=ex, in_view_slot=np.zeros(capq, np.int32), proj=np.zeros((capq, proj_cols), np.float32), view_cos=np.zeros(capq, np.float32),
-             level=np.zeros(capq, np.int32), match_idx=np.full(capq, -1, np.int32), match_dist=np.full(capq, 256, np.int32), **more)
-    io.n_seen_extra = len(ex)
-    for k, v in a.items():
-        setattr(io, k, None if v is None or (k == "seen_extra" and not len(v)) else v.ctypes.data)
+        a["held"][:n_key] = hh
+    a["seen_extra"] = ex = np.ascontiguousarray([] if seen_extra is None else seen_extra, np.int32).reshape(-1)
+    io.seen_extra = _m.ptr(ex); io.n_seen_extra = len(ex)
     return io, a
 
 
-def _map_finish(r, a, n_key):
-    """attaches held and the in-view arrays, cut to the counts -> the in-view count"""
-    nq = r.n_in_view if r.status == HVO_OK else 0
-    r.held = a["held"][:n_key]
-    for k in ("in_view_slot", "proj", "view_cos", "level", "match_idx", "match_dist"):
-        setattr(r, k, a[k][:nq])
-    return nq
+def _map_finish(r, table, a, n_key):
+    """attaches held and the in-view arrays, cut to the counts (nothing in view after a refusal) -> the in-view count"""
+    ok = r.status == HVO_OK
+    for k, v in table.cut(r, a, n_key=n_key, capq=len(a["in_view_slot"]) if ok else 0).items():
+        setattr(r, k, v)
+    return r.n_in_view if ok else 0
 
 
 def _ll_io(n_kl, n_slots, held, seen_extra, want_rel):
     """-> (LocalLinesIO, dict of the arrays it points at)"""
-    capq = max(1, min(n_slots, LINE_MAP_MAX_QUERIES)); nk = max(n_kl, 1)
     io = LocalLinesIO(); io.n_kl = n_kl
-    return _map_io(io, n_kl, "line", n_slots, LINE_MAP_MAX_QUERIES, held, seen_extra, 4, n_par=np.zeros(nk, np.int32), n_perp=np.zeros(nk, np.int32),
-                   rel_map=np.zeros(nk * capq, np.int8) if want_rel else None)
+    io, a = _map_io(io, LL_OUT, n_kl, "line", n_slots, LINE_MAP_MAX_QUERIES, held, seen_extra)
+    a["rel_map"] = np.zeros(max(n_kl, 1) * len(a["in_view_slot"]), np.int8) if want_rel else None
+    io.rel_map = _m.ptr(a["rel_map"])
+    return io, a
 
 
 def _ll_finish(r, a, n_kl):
-    nq = _map_finish(r, a, n_kl)
-    r.n_par = a["n_par"][:n_kl]; r.n_perp = a["n_perp"][:n_kl]
+    nq = _map_finish(r, LL_OUT, a, n_kl)
     r.rel_map = None if a["rel_map"] is None else a["rel_map"][: n_kl * nq].reshape(n_kl, nq)
     return r
+
+
+def _lp_io(n_kp, n_slots, held, seen_extra):
+    """-> (LocalPointsIO, dict of the arrays it points at)"""
+    io = LocalPointsIO(); io.n_kp = n_kp
+    return _map_io(io, LP_OUT, n_kp, "point", n_slots, POINT_MAP_MAX_QUERIES, held, seen_extra)
+
+
+def _lp_finish(r, a, n_kp):
+    _map_finish(r, LP_OUT, a, n_kp)
+    return r
+
+
+LP_FRAME = _m.Inputs([("kp_un", KEYPOINT_DT, (), REQ, "n"), ("uright", _f32, (), OPT, "n"), ("desc", _u8, (32,), REQ, "n")])
+
+
+def _lp_frame(kp_un, uright, desc):
+    """a frame on host arrays (mvKeysUn, mvuRight or None, mDescriptors) -> (LocalPointsFrame, the arrays, its key-point count)"""
+    F = LocalPointsFrame()
+    return (F,) + LP_FRAME.fill(F, dict(kp_un=kp_un, uright=uright, desc=desc))
 
 
 POINT_MAP_MAX_SLOTS = 1 << 20
@@ -394,30 +432,6 @@ class LocalPointsResult(C.Structure):
         for k in ("held", "in_view_slot", "proj", "view_cos", "level", "match_idx", "match_dist"):
             d[k] = getattr(self, k, None)
         return d
-
-
-assert C.sizeof(LocalPointsResult) == 28
-
-
-def _lp_params(bounds4, log_scale_factor, n_levels, bf, th, th_high, nn_ratio, view_cos_limit):
-    p = LocalPointsParams()
-    b = (0.0, 1.0, 0.0, 1.0) if bounds4 is None else [float(v) for v in np.asarray(bounds4).reshape(4)]
-    for k in range(4): p.bounds[k] = b[k]
-    p.log_scale_factor = log_scale_factor; p.n_levels = n_levels; p.bf = bf; p.th = th; p.th_high = th_high; p.nn_ratio = nn_ratio
-    p.view_cos_limit = view_cos_limit
-    return p
-
-
-def _lp_io(n_kp, n_slots, held, seen_extra):
-    """-> (LocalPointsIO, dict of the arrays it points at)"""
-    io = LocalPointsIO(); io.n_kp = n_kp
-    return _map_io(io, n_kp, "point", n_slots, POINT_MAP_MAX_QUERIES, held, seen_extra, 3)
-
-
-def _lp_finish(r, a, n_kp):
-    _map_finish(r, a, n_kp)
-    return r
-
 
 VOC_TF_IDF, VOC_TF, VOC_IDF, VOC_BINARY = 0, 1, 2, 3                                                  # DBoW2::WeightingType
 VOC_L1_NORM, VOC_L2_NORM, VOC_CHI_SQUARE, VOC_KL, VOC_BHATTACHARYYA, VOC_DOT_PRODUCT = 0, 1, 2, 3, 4, 5    # DBoW2::ScoringType
@@ -523,6 +537,11 @@ class KfiResult(C.Structure):
 KFI_UNTOUCHED = 119                # the byte the binding fills its output arrays with: an entry the call did not write keeps it
 
 
+# ---- CreateNewKeyFrame: KFI_UNTOUCHED before the call, but held_* start at -1 (the call's own "holds nothing")
+KFI_OUT = _m.Outputs([(k, dt, c, ("n_kp", "n_kl")[s], None if k.startswith("held") else ("n_point_entries", "n_line_entries")[s]) for k, dt, c, s in _KFI_IO],
+                     KFI_UNTOUCHED, fill=dict(held_points=-1, held_lines=-1), scalars=[f for f, _ in KfiResult._fields_])
+
+
 def _kfi_args(n_kp, n_kl, mode, th_depth, n_levels, line_n_levels, line_scale_factor, line_geometry, cos_par, cos_perp, first_point_slot, first_line_slot,
               held_points, held_lines):
     p = KfiParams(); lib().hvo_kfi_default_params(C.byref(p))
@@ -530,14 +549,12 @@ def _kfi_args(n_kp, n_kl, mode, th_depth, n_levels, line_n_levels, line_scale_fa
     p.line_geometry = 1 if line_geometry else 0; p.first_point_slot = first_point_slot; p.first_line_slot = first_line_slot
     if cos_par is not None: p.cos_par = cos_par
     if cos_perp is not None: p.cos_perp = cos_perp
-    n = (int(n_kp), int(n_kl))
-    a = {k: np.full((max(n[side], 1), comps) if comps > 1 else max(n[side], 1), KFI_UNTOUCHED, dt) for k, dt, comps, side in _KFI_IO}
-    for k, given, side in (("held_points", held_points, 0), ("held_lines", held_lines, 1)):
-        a[k][:] = -1
-        if given is not None: a[k][:n[side]] = np.asarray(given, np.int32).reshape(-1)[:n[side]]
-    a["ln_rel"] = np.full((max(n[1], 1), max(n[1], 1)), KFI_UNTOUCHED, np.uint8)
-    io = KfiIO(); io.n_kp, io.n_kl = n
-    for k in a: setattr(io, k, a[k].ctypes.data)
+    n_kp, n_kl = int(n_kp), int(n_kl)
+    io = KfiIO(); io.n_kp, io.n_kl = n_kp, n_kl
+    a = KFI_OUT.alloc(io, n_kp=n_kp, n_kl=n_kl)
+    for k, given, n in (("held_points", held_points, n_kp), ("held_lines", held_lines, n_kl)):
+        if given is not None: a[k][:n] = np.asarray(given, np.int32).reshape(-1)[:n]
+    a["ln_rel"] = np.full((max(n_kl, 1), max(n_kl, 1)), KFI_UNTOUCHED, np.uint8); io.ln_rel = a["ln_rel"].ctypes.data
     return p, io, a
 
 
@@ -549,11 +566,9 @@ class KfiOutput:
 
 def _kfi_finish(r, a, n_kp, n_kl, mode):
     o = KfiOutput()
-    for f, _ in KfiResult._fields_: setattr(o, f, getattr(r, f))
-    ne = (r.n_point_entries, r.n_line_entries)
-    for k, _, _, side in _KFI_IO:
-        setattr(o, k, a[k][:(n_kp, n_kl)[side]] if k.startswith("held") else a[k][:ne[side]])
-    o.ln_rel = a["ln_rel"].reshape(-1)[:ne[1] * n_kl].reshape(ne[1], n_kl) if mode == KFI_KEYFRAME and n_kl else np.zeros((0, n_kl), np.uint8)
+    for k, v in KFI_OUT.finish(r, a, n_kp=n_kp, n_kl=n_kl).items(): setattr(o, k, v)
+    ne = r.n_line_entries
+    o.ln_rel = a["ln_rel"].reshape(-1)[:ne * n_kl].reshape(ne, n_kl) if mode == KFI_KEYFRAME and n_kl else np.zeros((0, n_kl), np.uint8)
     return o
 
 
@@ -567,58 +582,55 @@ class KfdbResult(C.Structure):
                [(k, C.c_int32) for k in ("n_sharing", "max_common", "min_common", "n_scored")] + [("best_acc_score", C.c_float), ("status", C.c_int32)]
 
 
+# ---- the key-frame database and the bag of words: zeros (-1 for the per-feature ids) before the call, copies afterwards
+KFDB_OUT = _m.Outputs([("candidate", _i32, 1, "cap", "n_candidates")], 0, scalars=("n_sharing", "max_common", "min_common", "n_scored"), copy=True)
+KFDB_VIEWS = _m.Outputs([_entry(k, dt, 1, "n_slots") for k, dt in (("words", _i32), ("score", _f32), ("acc", _f32), ("best", _i32))], 0, copy=True)
+
+
 def _kfdb_args(n_slots, mode, min_score, connected, views, cap=None):
     """(hvo_kfdb_params, hvo_kfdb_result, the arrays behind them) for a database of n_slots slots"""
     conn = np.ascontiguousarray([] if connected is None else connected, np.int32).reshape(-1)
-    P = KfdbParams(); P.mode = mode; P.min_score = float(min_score); P.connected = conn.ctypes.data if len(conn) else None; P.n_connected = len(conn)
-    cap = max(n_slots, 1) if cap is None else int(cap)
-    a = dict(candidate=np.zeros(max(cap, 1), np.int32), connected=conn)
-    R = KfdbResult(); R.cap = cap; R.candidate = a["candidate"].ctypes.data; R.slot_cap = n_slots if views else 0
+    P = KfdbParams(); P.mode = mode; P.min_score = float(min_score); P.connected = _m.ptr(conn); P.n_connected = len(conn)
+    R = KfdbResult(); R.cap = max(n_slots, 1) if cap is None else int(cap); R.slot_cap = n_slots if views else 0
+    a = dict(KFDB_OUT.alloc(R, cap=R.cap), connected=conn)
     if views:
-        a.update(words=np.zeros(max(n_slots, 1), np.int32), score=np.zeros(max(n_slots, 1), np.float32), acc=np.zeros(max(n_slots, 1), np.float32),
-                 best=np.zeros(max(n_slots, 1), np.int32))
-        for k in ("words", "score", "acc", "best"):
-            setattr(R, k, a[k].ctypes.data)
+        a.update(KFDB_VIEWS.alloc(R, n_slots=n_slots))
     return P, R, a
 
 
 def _kfdb_finish(R, a, n_slots, views):
     """dict(candidates (slots, the reference's order), n_sharing, max_common, min_common, n_scored, best_acc_score; with views: words, score, acc,
     best per slot)"""
-    r = dict(candidates=a["candidate"][:R.n_candidates].copy(), best_acc_score=np.float32(R.best_acc_score))
-    r.update({k: getattr(R, k) for k in ("n_sharing", "max_common", "min_common", "n_scored")})
+    r = KFDB_OUT.finish(R, a, cap=len(a["candidate"])); r["candidates"] = r.pop("candidate"); r["best_acc_score"] = np.float32(R.best_acc_score)
     if views:
-        r.update({k: a[k][:n_slots].copy() for k in ("words", "score", "acc", "best")})
+        r.update(KFDB_VIEWS.cut(R, a, n_slots=n_slots))
     return r
+
+
+BOW_OUT = _m.Outputs([("word_id", _i32, 1, "cap", "n_features"), ("node_id", _i32, 1, "cap", "n_features"), ("bow_word", _i32, 1, "cap", "n_words"),
+                      ("bow_value", _f64, 1, "cap", "n_words"), ("fv_node", _i32, 1, "cap", "n_nodes"), ("fv_start", _i32, 1, "cap1", ("n_nodes", 1)),
+                      ("fv_index", _i32, 1, "cap", "n_valid")], 0, fill=dict(word_id=-1, node_id=-1), scalars=("n_short", "computed"), copy=True)
+BOW_SIDE = _m.Inputs([("desc", _u8, (32,), REQ, "n"), ("node_id", _i32, (), REQ, "n"), ("has_map_point", bool, (), OPT, "n"), ("angle", _f32, (), OPT, "n")])
 
 
 def _bow_out(cap):
     """an hvo_bow with room for `cap` features and the arrays behind it"""
-    cap = max(int(cap), 1)
-    a = dict(word_id=np.full(cap, -1, np.int32), node_id=np.full(cap, -1, np.int32), bow_word=np.zeros(cap, np.int32), bow_value=np.zeros(cap, np.float64),
-             fv_node=np.zeros(cap, np.int32), fv_start=np.zeros(cap + 1, np.int32), fv_index=np.zeros(cap, np.int32))
-    b = Bow(); b.cap = cap
-    for k, v in a.items():
-        setattr(b, k, v.ctypes.data)
-    return b, a
+    b = Bow(); b.cap = max(int(cap), 1)
+    return b, BOW_OUT.alloc(b, cap=b.cap, cap1=b.cap + 1)
 
 
 def _bow_finish(b, a):
     """dict(word_id, node_id per feature; bow_word, bow_value; fv_node, fv_start, fv_index; n_short, computed)"""
-    n = b.n_features
-    return dict(word_id=a["word_id"][:n].copy(), node_id=a["node_id"][:n].copy(), bow_word=a["bow_word"][:b.n_words].copy(), bow_value=a["bow_value"][:b.n_words].copy(),
-                fv_node=a["fv_node"][:b.n_nodes].copy(), fv_start=a["fv_start"][:b.n_nodes + 1].copy(), fv_index=a["fv_index"][:b.n_valid].copy(),
-                n_short=b.n_short, computed=bool(b.computed))
+    d = BOW_OUT.finish(b, a, cap=b.cap, cap1=b.cap + 1); d["computed"] = bool(d["computed"])
+    return d
 
 
 def _bow_side(desc, node_id, has_map_point=None, angle=None):
-    d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32); n = len(d)
-    keep = [d, np.ascontiguousarray(node_id, np.int32).reshape(n),
-            np.ones(n, np.uint8) if has_map_point is None else np.ascontiguousarray(np.asarray(has_map_point).astype(bool), np.uint8).reshape(n),
-            np.zeros(n, np.float32) if angle is None else np.ascontiguousarray(angle, np.float32).reshape(n)]
-    k = BowKeyframe(); k.n = n
-    k.desc, k.node_id, k.has_map_point, k.angle = [v.ctypes.data if n else None for v in keep]
-    return k, keep
+    k = BowKeyframe()
+    a, n = BOW_SIDE.fill(k, dict(desc=desc, node_id=node_id, has_map_point=has_map_point, angle=angle))
+    if has_map_point is None: a["has_map_point"] = np.ones(n, np.uint8); k.has_map_point = _m.ptr(a["has_map_point"])     # every feature holds a map point
+    if angle is None: a["angle"] = np.zeros(n, np.float32); k.angle = _m.ptr(a["angle"])
+    return k, a
 
 
 def _bow_search_args(n_frame, kfs, nnratio, check_orientation, th_low):
@@ -660,6 +672,14 @@ class PnpKeyframeSide(C.Structure):
 
 
 PNP_MAX_HYP = 1024
+
+
+# ---- the relocalisation PnP: its result block stays written out (_pnp_results / _pnp_finish): the sentinel is a byte pattern read through three
+# dtypes, hyp_sample's width is a parameter of the call, and the events are records whose two inlier rows are wired one by one
+PNP_PROBLEM = _m.Inputs([("p3d", _f32, (3,), REQ, "n"), ("p2d", _f32, (2,), REQ, "n"), ("sigma2", _f32, (), REQ, "n"), ("feature_index", _i32, (), REQ, "n")],
+                        differ="pnp_ransac: a problem's arrays differ in length")
+PNP_KF_SIDE = _m.Inputs([("match_kf", _i32, (), REQ, None), ("pos", _f32, (3,), REQ, "n"), ("bad", bool, (), REQ, "n")],
+                        differ="pnp_ransac: pos and bad differ in length")
 
 
 def pnp_params(**kw):
@@ -764,52 +784,34 @@ class KfSearchResult(C.Structure):
     _fields_ = [("match_idx", C.c_void_p), ("match_dist", C.c_void_p), ("feature_kf", C.c_void_p), ("proj", C.c_void_p), ("level", C.c_void_p),
                 ("gate", C.c_void_p), ("n_matches", C.c_int32), ("n_searched", C.c_int32), ("status", C.c_int32), ("kernel_ms", C.c_float * 2)]
 
-
-assert C.sizeof(KfSearchCandidate) == 112 and C.sizeof(KfSearchParams) == 36 and C.sizeof(KfSearchResult) == 72
-
 KF_UNTOUCHED = -7           # what the outputs hold before the call: a refusal leaves them so
+
+
+# ---- SearchByProjection(Frame, KeyFrame): KF_UNTOUCHED before the call
+KFS_IN = _m.Inputs([("pos", _f32, (3,), REQ, "n"), ("skip", _u8, (), REQ, "n"), ("max_dist", _f32, (), REQ, "n"), ("min_dist", _f32, (), REQ, "n"),
+                    ("desc", _u8, (32,), REQ, "n"), ("angle", _f32, (), OPT, "n"), ("occupied", _u8, (), OPT, "n_frame")],
+                   differ="search_by_projection_keyframe: a candidate's arrays differ in length")
+KFS_OUT = _m.Outputs([_entry("match_idx", _i32), _entry("match_dist", _i32), _entry("feature_kf", _i32, 1, "n_frame"), _entry("proj", _f32, 2), _entry("level", _i32),
+                      _entry("gate", _i8)], KF_UNTOUCHED, counts=("n_matches", "n_searched", "status"), scalars=("n_matches", "n_searched", "status", "kernel_ms"))
 
 
 def _kfs_args(n_frame, kfs, bounds4, th, orb_dist, check_orientation, log_scale_factor, n_levels):
     """-> (KfSearchParams, candidates, results, the arrays they point at).  kfs: one dict per candidate with pos (n x 3), skip (n), max_dist,
     min_dist (n, raw), desc (n x 32), angle (n, or None), Tcw (3 x 4), occupied (frame features, or None)"""
     P = KfSearchParams(); P.th = th; P.orb_dist = orb_dist; P.check_orientation = 1 if check_orientation else 0
-    P.log_scale_factor = log_scale_factor; P.n_levels = n_levels
-    b = (0.0, 1.0, 0.0, 1.0) if bounds4 is None else [float(v) for v in np.asarray(bounds4).reshape(4)]
-    for k in range(4): P.bounds[k] = b[k]
-    K = (KfSearchCandidate * len(kfs))(); R = (KfSearchResult * len(kfs))(); keep = []
+    P.log_scale_factor = log_scale_factor; P.n_levels = n_levels; _m.bounds(P.bounds, bounds4)
+    K = (KfSearchCandidate * len(kfs))(); keep = []; lens = []
     for j, kf in enumerate(kfs):
-        pos = np.ascontiguousarray(kf["pos"], np.float32).reshape(-1, 3); n = len(pos)
-        a = dict(pos=pos, skip=np.ascontiguousarray(kf["skip"], np.uint8).reshape(-1), max_dist=np.ascontiguousarray(kf["max_dist"], np.float32).reshape(-1),
-                 min_dist=np.ascontiguousarray(kf["min_dist"], np.float32).reshape(-1), desc=np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32))
-        if any(len(a[k]) != n for k in a):
-            raise ValueError("search_by_projection_keyframe: a candidate's arrays differ in length")
-        a["angle"] = None if kf.get("angle") is None else np.ascontiguousarray(kf["angle"], np.float32).reshape(n)
-        a["occupied"] = None if kf.get("occupied") is None else np.ascontiguousarray(kf["occupied"], np.uint8).reshape(n_frame)
-        K[j].n = n
-        for k in ("pos", "skip", "max_dist", "min_dist", "desc", "angle", "occupied"):
-            setattr(K[j], k, a[k].ctypes.data if a[k] is not None and a[k].size else None)
-        if n == 0:                                                # (an empty array has no address worth passing; the call reads nothing)
-            for k in ("pos", "skip", "max_dist", "min_dist", "desc"): setattr(K[j], k, None)
-        T = np.asarray(kf["Tcw"], np.float32).reshape(12)
-        for k in range(12): K[j].Tcw[k] = T[k]
-        o = dict(match_idx=np.full(max(n, 1), KF_UNTOUCHED, np.int32), match_dist=np.full(max(n, 1), KF_UNTOUCHED, np.int32),
-                 feature_kf=np.full(max(n_frame, 1), KF_UNTOUCHED, np.int32), proj=np.full((max(n, 1), 2), KF_UNTOUCHED, np.float32),
-                 level=np.full(max(n, 1), KF_UNTOUCHED, np.int32), gate=np.full(max(n, 1), KF_UNTOUCHED, np.int8))
-        for k in o: setattr(R[j], k, o[k].ctypes.data)
-        R[j].n_matches = R[j].n_searched = R[j].status = KF_UNTOUCHED
-        keep.append((a, o, n))
-    return P, K, R, keep
+        a, n = KFS_IN.fill(K[j], kf, n_frame=n_frame)      # (a candidate without entries passes NULL for all its arrays; the call reads nothing)
+        _m.vec(K[j].Tcw, kf["Tcw"])
+        keep.append(a); lens.append(dict(n=n, n_frame=n_frame))
+    R, rk = _results(KFS_OUT, (KfSearchResult * len(kfs))(), lens)
+    return P, K, R, (keep, rk)
 
 
-def _kfs_finish(R, keep, n_frame):
-    out = []
-    for j, (_, o, n) in enumerate(keep):
-        d = dict(n_matches=R[j].n_matches, n_searched=R[j].n_searched, status=R[j].status, kernel_ms=tuple(R[j].kernel_ms))
-        for k in ("match_idx", "match_dist", "proj", "level", "gate"): d[k] = o[k][:n]
-        d["feature_kf"] = o["feature_kf"][:n_frame]
-        out.append(d)
-    return out
+def _kfs_finish(R, keep):
+    """one dict per candidate, cut to its entries and the frame's features even after a refusal (every entry is then KF_UNTOUCHED)"""
+    return _finished(KFS_OUT, R, keep[1], True)
 
 
 FUSE_MAX_FEATURES, FUSE_MAX_ENTRIES = 65535, 1 << 20
@@ -839,82 +841,6 @@ class FuseResult(C.Structure):
                 ("fused_entry", C.c_void_p), ("fused_idx", C.c_void_p), ("n_fused", C.c_int32), ("n_searched", C.c_int32), ("status", C.c_int32),
                 ("kernel_ms", C.c_float * 3)]
 
-
-assert C.sizeof(FuseKeyframe) == 88 and C.sizeof(FuseMap) == 48 and C.sizeof(FuseParams) == 40 and C.sizeof(FuseResult) == 80
-
-
-def _fuse_params(cam, bounds4, th, th_low, log_scale_factor, n_levels, per_keyframe):
-    P = FuseParams(); P.th = th; P.th_low = th_low; P.log_scale_factor = log_scale_factor; P.n_levels = n_levels; P.bf = float(cam[4])
-    b = (0.0, 1.0, 0.0, 1.0) if bounds4 is None else [float(v) for v in np.asarray(bounds4).reshape(4)]
-    for k in range(4): P.bounds[k] = b[k]
-    P.map_per_keyframe = 1 if per_keyframe else 0
-    return P
-
-
-def _fuse_map(mp):
-    """dict(pos, normal (n x 3), max_dist, min_dist (n, raw), desc (n x 32)) -> (FuseMap fields as arrays, n)"""
-    pos = np.ascontiguousarray(mp["pos"], np.float32).reshape(-1, 3); n = len(pos)
-    a = dict(pos=pos, normal=np.ascontiguousarray(mp["normal"], np.float32).reshape(-1, 3), max_dist=np.ascontiguousarray(mp["max_dist"], np.float32).reshape(-1),
-             min_dist=np.ascontiguousarray(mp["min_dist"], np.float32).reshape(-1), desc=np.ascontiguousarray(mp["desc"], np.uint8).reshape(-1, 32))
-    if any(len(v) != n for v in a.values()):
-        raise ValueError("fuse_points: a map side's arrays differ in length")
-    return a, n
-
-
-def _fuse_maps(maps):
-    M = (FuseMap * len(maps))(); keep = []
-    for s, mp in enumerate(maps):
-        a, n = _fuse_map(mp)
-        M[s].n = n
-        for k, v in a.items(): setattr(M[s], k, v.ctypes.data if n else None)
-        keep.append(a)
-    return M, keep, [M[s].n for s in range(len(maps))]
-
-
-def _fuse_keyframes(kfs, n_entries, resident=False):
-    """kfs: dicts of kp_un, uright (or None), desc, Tcw, skip (or None); n_entries[j]: the entries of key frame j's map side"""
-    K = (FuseKeyframe * len(kfs))(); keep = []
-    for j, kf in enumerate(kfs):
-        a = {}
-        if not resident:
-            a["kp_un"] = np.ascontiguousarray(kf["kp_un"], KEYPOINT_DT); nt = len(a["kp_un"])
-            a["desc"] = np.ascontiguousarray(kf["desc"], np.uint8).reshape(nt, 32)
-            a["uright"] = None if kf.get("uright") is None else np.ascontiguousarray(kf["uright"], np.float32).reshape(nt)
-            K[j].n = nt
-            for k in ("kp_un", "desc", "uright"): setattr(K[j], k, a[k].ctypes.data if a[k] is not None and nt else None)
-        a["skip"] = None if kf.get("skip") is None else np.ascontiguousarray(np.asarray(kf["skip"]).astype(bool), np.uint8).reshape(n_entries[j])
-        K[j].skip = a["skip"].ctypes.data if a["skip"] is not None and a["skip"].size else None
-        T = np.asarray(kf["Tcw"], np.float32).reshape(12)
-        for k in range(12): K[j].Tcw[k] = T[k]
-        keep.append(a)
-    return K, keep
-
-
-def _fuse_results(n_entries):
-    R = (FuseResult * len(n_entries))(); keep = []
-    for j, n in enumerate(n_entries):
-        m = max(n, 1)
-        o = dict(best_idx=np.full(m, FUSE_UNTOUCHED, np.int32), best_dist=np.full(m, FUSE_UNTOUCHED, np.int32), gate=np.full(m, FUSE_UNTOUCHED, np.int8),
-                 level=np.full(m, FUSE_UNTOUCHED, np.int32), proj=np.full((m, 3), FUSE_UNTOUCHED, np.float32),
-                 fused_entry=np.full(m, FUSE_UNTOUCHED, np.int32), fused_idx=np.full(m, FUSE_UNTOUCHED, np.int32))
-        for k in o: setattr(R[j], k, o[k].ctypes.data)
-        R[j].n_fused = R[j].n_searched = R[j].status = FUSE_UNTOUCHED
-        keep.append((o, n))
-    return R, keep
-
-
-def _fuse_finish(R, keep, ok):
-    """one dict per key frame; after a refusal (ok False) every array is returned whole, as the call left it"""
-    out = []
-    for j, (o, n) in enumerate(keep):
-        d = dict(n_fused=R[j].n_fused, n_searched=R[j].n_searched, status=R[j].status, kernel_ms=tuple(R[j].kernel_ms))
-        for k in ("best_idx", "best_dist", "gate", "level", "proj"): d[k] = o[k][:n] if ok else o[k]
-        nf = max(0, min(R[j].n_fused, n)) if ok else len(o["fused_entry"])
-        d["fused_entry"] = o["fused_entry"][:nf]; d["fused_idx"] = o["fused_idx"][:nf]
-        out.append(d)
-    return out
-
-
 LF_MAX_LINES, LF_MAX_ENTRIES, LF_MAX_PAIRS = 2048, 65536, 1 << 24
 LF_GATES = ("searched", "skip", "behind", "out of image", "dist < 0.8 min", "dist > 1.2 max", "view angle", "level")      # hvo_lf_result.gate
 LF_LEVEL_RULES = ("clamped", "as written")                         # HVO_LF_LEVEL_*
@@ -943,8 +869,26 @@ class LfResult(C.Structure):
                 ("fused_entry", C.c_void_p), ("fused_idx", C.c_void_p), ("behind_entry", C.c_void_p), ("n_fused", C.c_int32), ("n_behind", C.c_int32),
                 ("n_searched", C.c_int32), ("status", C.c_int32), ("kernel_ms", C.c_float * 3)]
 
+# ---- Fuse, points and lines: FUSE_UNTOUCHED before the call, whole arrays after a refusal
+def _fuse_out(proj_cols, lists, counts):
+    return _m.Outputs([_entry("best_idx", _i32), _entry("best_dist", _i32), _entry("gate", _i8), _entry("level", _i32), _entry("proj", _f32, proj_cols)] +
+                      [(f, _i32, 1, "n", c) for f, c in lists], FUSE_UNTOUCHED, counts=counts, scalars=counts + ("kernel_ms",))
 
-assert C.sizeof(LfKeyframe) == 120 and C.sizeof(LfMap) == 48 and C.sizeof(LfParams) == 28 and C.sizeof(LfResult) == 96
+
+FUSE_OUT = _fuse_out(3, (("fused_entry", "n_fused"), ("fused_idx", "n_fused")), ("n_fused", "n_searched", "status"))
+LF_OUT = _fuse_out(4, (("fused_entry", "n_fused"), ("fused_idx", "n_fused"), ("behind_entry", "n_behind")), ("n_fused", "n_behind", "n_searched", "status"))
+FUSE_MAP = _m.Inputs([("pos", _f32, (3,), REQ, "n"), ("normal", _f32, (3,), REQ, "n"), ("max_dist", _f32, (), REQ, "n"), ("min_dist", _f32, (), REQ, "n"),
+                      ("desc", _u8, (32,), REQ, "n")], differ="fuse_points: a map side's arrays differ in length")
+LF_MAP = _m.Inputs([("pos", _f64, (6,), REQ, "n"), ("normal", _f64, (3,), REQ, "n"), ("max_distance", _f32, (), REQ, "n"), ("min_distance", _f32, (), REQ, "n"),
+                    ("desc", _u8, (32,), REQ, "n")], differ="fuse_lines: a map side's arrays differ in length")
+FUSE_KF = _m.Inputs([("kp_un", KEYPOINT_DT, (), REQ, "n"), ("desc", _u8, (32,), REQ, "n"), ("uright", _f32, (), OPT, "n"), ("skip", bool, (), OPT, "entries")])
+LF_KF = _m.Inputs([("kl", KEYLINE_DT, (), OPT, None), ("desc_rows", _u8, (32,), OPT, None), ("skip", bool, (), OPT, "entries")], count_from="kl")
+
+
+def _fuse_params(cam, bounds4, th, th_low, log_scale_factor, n_levels, per_keyframe):
+    P = FuseParams(); P.th = th; P.th_low = th_low; P.log_scale_factor = log_scale_factor; P.n_levels = n_levels; P.bf = float(cam[4])
+    _m.bounds(P.bounds, bounds4); P.map_per_keyframe = 1 if per_keyframe else 0
+    return P
 
 
 def _lf_params(th, th_low, log_scale_factor, n_levels, scale_factor, level_rule, per_keyframe):
@@ -954,67 +898,66 @@ def _lf_params(th, th_low, log_scale_factor, n_levels, scale_factor, level_rule,
     return P
 
 
+def _map_sides(table, M, maps):
+    """the map sides (dicts of the table's arrays) -> (the records M, the arrays, the entries of each)"""
+    keep = [table.fill(M[s], mp)[0] for s, mp in enumerate(maps)]
+    return M, keep, [M[s].n for s in range(len(maps))]
+
+
 def _lf_maps(maps):
     """dicts of pos (n x 6 doubles), normal (n x 3 doubles), max_distance, min_distance (n, raw), desc (n x 32)"""
-    M = (LfMap * len(maps))(); keep = []
-    for s, mp in enumerate(maps):
-        pos = np.ascontiguousarray(mp["pos"], np.float64).reshape(-1, 6); n = len(pos)
-        a = dict(pos=pos, normal=np.ascontiguousarray(mp["normal"], np.float64).reshape(-1, 3), max_distance=np.ascontiguousarray(mp["max_distance"], np.float32).reshape(-1),
-                 min_distance=np.ascontiguousarray(mp["min_distance"], np.float32).reshape(-1), desc=np.ascontiguousarray(mp["desc"], np.uint8).reshape(-1, 32))
-        if any(len(v) != n for v in a.values()):
-            raise ValueError("fuse_lines: a map side's arrays differ in length")
-        M[s].n = n
-        for k, v in a.items(): setattr(M[s], k, v.ctypes.data if n else None)
-        keep.append(a)
-    return M, keep, [M[s].n for s in range(len(maps))]
+    return _map_sides(LF_MAP, (LfMap * len(maps))(), maps)
+
+
+def _fuse_keyframes(kfs, n_entries, resident=False):
+    """kfs: dicts of kp_un, uright (or None), desc, Tcw, skip (or None); n_entries[j]: the entries of key frame j's map side.  resident: the
+    features are the resident frame's, only skip and Tcw are read"""
+    K = (FuseKeyframe * len(kfs))(); keep = []
+    for j, kf in enumerate(kfs):
+        keep.append(FUSE_KF.fill(K[j], kf, only=("skip",) if resident else None, entries=n_entries[j])[0])
+        _m.vec(K[j].Tcw, kf["Tcw"])
+    return K, keep
 
 
 def _lf_keyframes(kfs, n_entries, resident=False):
     """kfs: dicts of kl, desc_rows, Tcw, cam (fx, fy, cx, cy), bounds, skip (or None); n_entries[j]: the entries of key frame j's map side"""
     K = (LfKeyframe * len(kfs))(); keep = []
     for j, kf in enumerate(kfs):
-        a = {}
+        # (an array given as None with a count "n" / "n_desc_rows" beside it reaches the library as a missing array: its refusal is tested)
+        a, _ = LF_KF.fill(K[j], kf, n=int(kf.get("n", 0)) if kf.get("kl") is None else None, only=("skip",) if resident else None, entries=n_entries[j])
         if not resident:
-            # (an array given as None with a count "n" / "n_desc_rows" beside it reaches the library as a missing array: its refusal is tested)
-            a["kl"] = np.ascontiguousarray(kf["kl"] if kf.get("kl") is not None else np.zeros(0, KEYLINE_DT), KEYLINE_DT)
-            a["desc_rows"] = np.ascontiguousarray(kf["desc_rows"] if kf.get("desc_rows") is not None else np.zeros((0, 32), np.uint8), np.uint8).reshape(-1, 32)
-            K[j].n = len(a["kl"]) if kf.get("kl") is not None else int(kf.get("n", 0))
-            K[j].n_desc_rows = len(a["desc_rows"]) if kf.get("desc_rows") is not None else int(kf.get("n_desc_rows", 0))
-            for k in ("kl", "desc_rows"): setattr(K[j], k, a[k].ctypes.data if len(a[k]) else None)
-            b = [float(v) for v in np.asarray(kf["bounds"]).reshape(4)]
-            for k in range(4): K[j].bounds[k] = b[k]
+            K[j].n_desc_rows = len(a["desc_rows"]) if a["desc_rows"] is not None else int(kf.get("n_desc_rows", 0))
+            _m.vec(K[j].bounds, kf["bounds"])
             K[j].fx, K[j].fy, K[j].cx, K[j].cy = (float(v) for v in kf["cam"][:4])
-        a["skip"] = None if kf.get("skip") is None else np.ascontiguousarray(np.asarray(kf["skip"]).astype(bool), np.uint8).reshape(n_entries[j])
-        K[j].skip = a["skip"].ctypes.data if a["skip"] is not None and a["skip"].size else None
-        T = np.asarray(kf["Tcw"], np.float32).reshape(12)
-        for k in range(12): K[j].Tcw[k] = T[k]
+        _m.vec(K[j].Tcw, kf["Tcw"])
         keep.append(a)
     return K, keep
 
 
-def _lf_results(n_entries):
-    R = (LfResult * len(n_entries))(); keep = []
-    for j, n in enumerate(n_entries):
-        m = max(n, 1)
-        o = dict(best_idx=np.full(m, FUSE_UNTOUCHED, np.int32), best_dist=np.full(m, FUSE_UNTOUCHED, np.int32), gate=np.full(m, FUSE_UNTOUCHED, np.int8),
-                 level=np.full(m, FUSE_UNTOUCHED, np.int32), proj=np.full((m, 4), FUSE_UNTOUCHED, np.float32),
-                 fused_entry=np.full(m, FUSE_UNTOUCHED, np.int32), fused_idx=np.full(m, FUSE_UNTOUCHED, np.int32), behind_entry=np.full(m, FUSE_UNTOUCHED, np.int32))
-        for k in o: setattr(R[j], k, o[k].ctypes.data)
-        R[j].n_fused = R[j].n_behind = R[j].n_searched = R[j].status = FUSE_UNTOUCHED
-        keep.append((o, n))
-    return R, keep
+class _FuseFamily:
+    """what fuse_points and fuse_lines differ in: the records, their tables and the key-frame builder"""
+    def __init__(self, name, Map, Result, map_in, out, keyframes):
+        self.name, self.Map, self.Result, self.map_in, self.out, self.keyframes = name, Map, Result, map_in, out, keyframes
+
+    def build(self, kfs, maps=None, slots=None, resident=False):
+        """the arguments the three forms of a fuse call share.  maps: ONE dict for all key frames or a list with one per key frame; else slots
+        of a resident map -> (key frames K, map sides M or None, slot array or None, per_keyframe, results R, finish(ok), what must stay alive)"""
+        per_kf = maps is not None and not isinstance(maps, dict)
+        if per_kf and len(maps) != len(kfs):
+            raise ValueError("%s: one map side per key frame, or one dict for all" % self.name)
+        if maps is not None:
+            sides = list(maps) if per_kf else [maps]
+            M, mk, ns = _map_sides(self.map_in, (self.Map * len(sides))(), sides); sl = None
+            ne = ns if per_kf else ns * len(kfs)
+        else:
+            M = mk = None; sl = np.ascontiguousarray(slots, np.int32).reshape(-1); ne = [len(sl)] * len(kfs)
+        K, kk = self.keyframes(kfs, ne, resident)
+        R, rk = _results(self.out, (self.Result * len(ne))(), [dict(n=n) for n in ne])
+        return K, M, sl, per_kf, R, lambda ok: _finished(self.out, R, rk, ok), (mk, kk)
 
 
-def _lf_finish(R, keep, ok):
-    """one dict per key frame; after a refusal (ok False) every array is returned whole, as the call left it"""
-    out = []
-    for j, (o, n) in enumerate(keep):
-        d = dict(n_fused=R[j].n_fused, n_behind=R[j].n_behind, n_searched=R[j].n_searched, status=R[j].status, kernel_ms=tuple(R[j].kernel_ms))
-        for k in ("best_idx", "best_dist", "gate", "level", "proj"): d[k] = o[k][:n] if ok else o[k]
-        nf = max(0, min(R[j].n_fused, n)) if ok else len(o["fused_entry"]); nb = max(0, min(R[j].n_behind, n)) if ok else len(o["behind_entry"])
-        d["fused_entry"] = o["fused_entry"][:nf]; d["fused_idx"] = o["fused_idx"][:nf]; d["behind_entry"] = o["behind_entry"][:nb]
-        out.append(d)
-    return out
+_FUSE = _FuseFamily("fuse_points", FuseMap, FuseResult, FUSE_MAP, FUSE_OUT, _fuse_keyframes)
+_LF = _FuseFamily("fuse_lines", LfMap, LfResult, LF_MAP, LF_OUT, _lf_keyframes)
 
 
 NP_MAX_FEATURES, NP_MAX_NEIGHBOURS = 4096, 64
@@ -1042,59 +985,6 @@ class NpResult(C.Structure):
 class NpSummary(C.Structure):
     """hvo_np_summary"""
     _fields_ = [("owner", C.c_void_p), ("n_new", C.c_int32), ("kernel_ms", C.c_float * 3)]
-
-
-assert C.sizeof(NpKeyframe) == 120 and C.sizeof(NpParams) == 16 and C.sizeof(NpResult) == 72 and C.sizeof(NpSummary) == 24
-
-
-def _np_keyframe(K, kf, resident=False):
-    """kf: dict of kp_un, kp (or None), uright, depth (both or None), desc, node_id, has_map_point, Tcw, mb, skip; a missing array stays NULL and
-    is the library's to refuse.  resident: only has_map_point, Tcw and mb are read"""
-    a = {}
-    get = lambda k: None if kf.get(k) is None else kf[k]
-    if not resident:
-        a["kp_un"] = None if get("kp_un") is None else np.ascontiguousarray(kf["kp_un"], KEYPOINT_DT)
-        n = K.n = int(kf["n"]) if "n" in kf else (len(a["kp_un"]) if a["kp_un"] is not None else 0)
-        a["kp"] = None if get("kp") is None else np.ascontiguousarray(kf["kp"], KEYPOINT_DT)
-        for k, dt in (("uright", np.float32), ("depth", np.float32), ("node_id", np.int32)):
-            a[k] = None if get(k) is None else np.ascontiguousarray(kf[k], dt).reshape(-1)
-        a["desc"] = None if get("desc") is None else np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32)
-    a["has_map_point"] = None if get("has_map_point") is None else np.ascontiguousarray(np.asarray(kf["has_map_point"]).astype(bool), np.uint8).reshape(-1)
-    for k, v in a.items(): setattr(K, k, v.ctypes.data if v is not None and v.size else None)
-    T = np.asarray(kf["Tcw"], np.float32).reshape(12)
-    for k in range(12): K.Tcw[k] = T[k]
-    K.mb = float(kf.get("mb", 0.0)); K.skip = 1 if kf.get("skip") else 0
-    return a
-
-
-def _np_args(n1, kfs, th_low, n_levels, scale_factor, bf):
-    nk = len(kfs); m = max(n1, 1)
-    K = (NpKeyframe * max(nk, 1))(); R = (NpResult * max(nk, 1))(); keep = []; outs = []
-    for j, kf in enumerate(kfs):
-        keep.append(_np_keyframe(K[j], kf))
-        o = dict(match_idx2=np.full(m, NP_UNTOUCHED, np.int32), match_dist=np.full(m, NP_UNTOUCHED, np.int32), outcome=np.full(m, NP_UNTOUCHED, np.int8),
-                 branch=np.full(m, NP_UNTOUCHED, np.int8), x3d=np.full((m, 3), NP_UNTOUCHED, np.float32),
-                 created_idx1=np.full(m, NP_UNTOUCHED, np.int32), created_idx2=np.full(m, NP_UNTOUCHED, np.int32))
-        for k in o: setattr(R[j], k, o[k].ctypes.data)
-        R[j].n_created = R[j].gate = R[j].status = NP_UNTOUCHED
-        outs.append(o)
-    S = NpSummary(); owner = np.full(m, NP_UNTOUCHED, np.int32)
-    S.owner = owner.ctypes.data; S.n_new = NP_UNTOUCHED
-    P = NpParams(); P.th_low = th_low; P.n_levels = n_levels; P.scale_factor = scale_factor; P.bf = bf
-    return K, R, S, P, owner, outs, keep
-
-
-def _np_finish(n1, R, S, owner, outs, ok):
-    """(one dict per neighbour, the summary); after a refusal (ok False) every array is returned whole, as the call left it"""
-    res = []
-    for j, o in enumerate(outs):
-        d = dict(n_created=R[j].n_created, gate=R[j].gate, status=R[j].status)
-        for k in ("match_idx2", "match_dist", "outcome", "branch", "x3d"): d[k] = o[k][:n1] if ok else o[k]
-        nc = max(0, min(R[j].n_created, n1)) if ok else len(o["created_idx1"])
-        d["created_idx1"] = o["created_idx1"][:nc]; d["created_idx2"] = o["created_idx2"][:nc]
-        res.append(d)
-    return res, dict(owner=owner[:n1] if ok else owner, n_new=S.n_new, kernel_ms=tuple(S.kernel_ms))
-
 
 NL_MAX_LINES, NL_MAX_NEIGHBOURS = 2048, 16
 NL_PAIR_AS_WRITTEN, NL_PAIR_ALIGNED = 0, 1
@@ -1131,62 +1021,70 @@ class NlSummary(C.Structure):
     """hvo_nl_summary"""
     _fields_ = [("owner_pair", C.c_void_p), ("n_new", C.c_int32), ("n_pairs", C.c_int32), ("kernel_ms", C.c_float * 3)]
 
+# ---- CreateNewMapPoints / CreateNewMapLinesConstraint: NP_UNTOUCHED / NL_UNTOUCHED before the call, whole arrays after a refusal.  A key
+# frame's arrays may all be missing (they stay NULL and are the library's to refuse) and an explicit "n" beside them is honoured
+NP_KF = _m.Inputs([("kp_un", KEYPOINT_DT, (), OPT, None), ("kp", KEYPOINT_DT, (), OPT, None), ("uright", _f32, (), OPT, None), ("depth", _f32, (), OPT, None),
+                   ("node_id", _i32, (), OPT, None), ("desc", _u8, (32,), OPT, None), ("has_map_point", bool, (), OPT, None)], count_from="kp_un")
+NP_OUT = _m.Outputs([_entry("match_idx2", _i32), _entry("match_dist", _i32), _entry("outcome", _i8), _entry("branch", _i8), _entry("x3d", _f32, 3),
+                     ("created_idx1", _i32, 1, "n", "n_created"), ("created_idx2", _i32, 1, "n", "n_created")], NP_UNTOUCHED,
+                    counts=("n_created", "gate", "status"), scalars=("n_created", "gate", "status"))
+NP_SUMMARY = _m.Outputs([_entry("owner", _i32)], NP_UNTOUCHED, counts=("n_new",), scalars=("n_new", "kernel_ms"))
+NL_KF = _m.Inputs([("kl", KEYLINE_DT, (), OPT, None), ("linefn", _f64, (3,), OPT, None), ("desc", _u8, (32,), OPT, None), ("has_map_line", bool, (), OPT, None)],
+                  count_from="kl")
+NL_MATCH = _m.Outputs([_entry("match_idx", _i32)], NL_UNTOUCHED, counts=("n_matched", "gate"), scalars=("n_matched", "gate"))
+NL_OUT = _m.Outputs([_entry("outcome", _i8), _entry("line3d", _f32, 6)] + [("created_idx%d" % k, _i32, 1, "n", "n_created") for k in range(3)], NL_UNTOUCHED,
+                    counts=("kf2", "kf3", "mv2", "mv3", "n_created", "status"), scalars=("kf2", "kf3", "mv2", "mv3", "n_created", "status"))
+NL_SUMMARY = _m.Outputs([_entry("owner_pair", _i32)], NL_UNTOUCHED, counts=("n_new", "n_pairs"), scalars=("n_new", "n_pairs", "kernel_ms"))
 
-assert C.sizeof(NlKeyframe) == 128 and C.sizeof(NlParams) == 20 and C.sizeof(NlMatch) == 16 and C.sizeof(NlResult) == 64 and C.sizeof(NlSummary) == 32
+
+def _np_keyframe(K, kf, resident=False):
+    """kf: dict of kp_un, kp (or None), uright, depth (both or None), desc, node_id, has_map_point, Tcw, mb, skip.  resident: only
+    has_map_point, Tcw and mb are read"""
+    a, _ = NP_KF.fill(K, kf, n=int(kf["n"]) if "n" in kf else None, only=("has_map_point",) if resident else None)
+    _m.vec(K.Tcw, kf["Tcw"])
+    K.mb = float(kf.get("mb", 0.0)); K.skip = 1 if kf.get("skip") else 0
+    return a
+
+
+def _np_args(m, kfs, th_low, n_levels, scale_factor, bf):
+    """room for m features per neighbour -> (K, R, S, P, finish(n1) -> what _ret calls, what must stay alive).  finish(n1)(ok): (one dict per
+    neighbour, the summary), cut to the n1 features the caller named"""
+    nk = len(kfs)
+    K = (NpKeyframe * max(nk, 1))(); R = (NpResult * max(nk, 1))()
+    keep = [_np_keyframe(K[j], kf) for j, kf in enumerate(kfs)]
+    outs = [NP_OUT.alloc(R[j], n=m) for j in range(nk)]
+    S = NpSummary(); owner = NP_SUMMARY.alloc(S, n=m)
+    P = NpParams(); P.th_low = th_low; P.n_levels = n_levels; P.scale_factor = scale_factor; P.bf = bf
+    finish = lambda n1: lambda ok: ([NP_OUT.finish(R[j], o, ok, n=n1) for j, o in enumerate(outs)], NP_SUMMARY.finish(S, owner, ok, n=n1))
+    return K, R, S, P, finish, keep
 
 
 def _nl_keyframe(K, kf, resident=False):
-    """kf: dict of kl, linefn, desc, has_map_line, Tcw, cam (fx, fy, cx, cy), mb, median_depth, skip; a missing array stays NULL and is the
-    library's to refuse.  resident: only has_map_line, Tcw and cam are read"""
-    a = {}
-    get = lambda k: None if kf.get(k) is None else kf[k]
-    if not resident:
-        a["kl"] = None if get("kl") is None else np.ascontiguousarray(kf["kl"], KEYLINE_DT)
-        K.n = int(kf["n"]) if "n" in kf else (len(a["kl"]) if a["kl"] is not None else 0)
-        a["linefn"] = None if get("linefn") is None else np.ascontiguousarray(kf["linefn"], np.float64).reshape(-1, 3)
-        a["desc"] = None if get("desc") is None else np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32)
-    a["has_map_line"] = None if get("has_map_line") is None else np.ascontiguousarray(np.asarray(kf["has_map_line"]).astype(bool), np.uint8).reshape(-1)
-    for k, v in a.items(): setattr(K, k, v.ctypes.data if v is not None and v.size else None)
-    T = np.asarray(kf["Tcw"], np.float32).reshape(12)
-    for k in range(12): K.Tcw[k] = T[k]
-    for k in range(4): K.cam[k] = float(kf["cam"][k])
+    """kf: dict of kl, linefn, desc, has_map_line, Tcw, cam (fx, fy, cx, cy), mb, median_depth, skip.  resident: only has_map_line, Tcw and cam
+    are read"""
+    a, _ = NL_KF.fill(K, kf, n=int(kf["n"]) if "n" in kf else None, only=("has_map_line",) if resident else None)
+    _m.vec(K.Tcw, kf["Tcw"]); _m.vec(K.cam, kf["cam"], 4)
     K.mb = float(kf.get("mb", 0.0)); K.median_depth = float(kf.get("median_depth", 1.0)); K.skip = 1 if kf.get("skip") else 0
     return a
 
 
-def _nl_args(n1, kfs, th_high, nn_ratio, n_levels, scale_factor, pairing, n_pairs_cap):
-    nk = len(kfs); m = max(n1, 1)
-    cap = nk * (nk - 1) // 2 if n_pairs_cap is None else int(n_pairs_cap)
-    K = (NlKeyframe * max(nk, 1))(); M = (NlMatch * max(nk, 1))(); R = (NlResult * max(cap, 1))(); keep = []; mouts = []; outs = []
-    for j, kf in enumerate(kfs):
-        keep.append(_nl_keyframe(K[j], kf))
-        mi = np.full(m, NL_UNTOUCHED, np.int32)
-        M[j].match_idx = mi.ctypes.data; M[j].n_matched = M[j].gate = NL_UNTOUCHED
-        mouts.append(mi)
-    for p in range(cap):
-        o = dict(outcome=np.full(m, NL_UNTOUCHED, np.int8), line3d=np.full((m, 6), NL_UNTOUCHED, np.float32), created_idx0=np.full(m, NL_UNTOUCHED, np.int32),
-                 created_idx1=np.full(m, NL_UNTOUCHED, np.int32), created_idx2=np.full(m, NL_UNTOUCHED, np.int32))
-        for k in o: setattr(R[p], k, o[k].ctypes.data)
-        R[p].kf2 = R[p].kf3 = R[p].mv2 = R[p].mv3 = R[p].n_created = R[p].status = NL_UNTOUCHED
-        outs.append(o)
-    S = NlSummary(); owner = np.full(m, NL_UNTOUCHED, np.int32)
-    S.owner_pair = owner.ctypes.data; S.n_new = S.n_pairs = NL_UNTOUCHED
+def _nl_args(m, kfs, th_high, nn_ratio, n_levels, scale_factor, pairing, n_pairs_cap):
+    """room for m lines per neighbour and per pair -> (K, M, R, S, P, the pair capacity, finish(n1), what must stay alive).  finish(n1)(ok):
+    (one dict per neighbour, one per pair, the summary); after a refusal every result record the caller made room for is listed"""
+    nk = len(kfs); cap = nk * (nk - 1) // 2 if n_pairs_cap is None else int(n_pairs_cap)
+    K = (NlKeyframe * max(nk, 1))(); M = (NlMatch * max(nk, 1))(); R = (NlResult * max(cap, 1))()
+    keep = [_nl_keyframe(K[j], kf) for j, kf in enumerate(kfs)]
+    mouts = [NL_MATCH.alloc(M[j], n=m) for j in range(nk)]
+    outs = [NL_OUT.alloc(R[p], n=m) for p in range(cap)]
+    S = NlSummary(); owner = NL_SUMMARY.alloc(S, n=m)
     P = NlParams(); P.th_high = th_high; P.nn_ratio = nn_ratio; P.n_levels = n_levels; P.scale_factor = scale_factor; P.pairing = pairing
-    return K, M, R, S, P, cap, owner, mouts, outs, keep
 
+    def finish(n1):
+        return lambda ok: ([NL_MATCH.finish(M[j], mo, ok, n=n1) for j, mo in enumerate(mouts)],
+                           [NL_OUT.finish(R[p], o, ok, n=n1) for p, o in enumerate(outs[:max(S.n_pairs, 0)] if ok else outs)],
+                           NL_SUMMARY.finish(S, owner, ok, n=n1))
+    return K, M, R, S, P, cap, finish, keep
 
-def _nl_finish(n1, M, R, S, owner, mouts, outs, ok):
-    """(one dict per neighbour, one dict per pair, the summary); after a refusal (ok False) every array is returned whole, as the call left it,
-    and every result record the caller made room for is listed"""
-    matches = [dict(match_idx=mi[:n1] if ok else mi, n_matched=M[j].n_matched, gate=M[j].gate) for j, mi in enumerate(mouts)]
-    res = []
-    for p, o in enumerate(outs[:max(S.n_pairs, 0)] if ok else outs):
-        d = dict(kf2=R[p].kf2, kf3=R[p].kf3, mv2=R[p].mv2, mv3=R[p].mv3, n_created=R[p].n_created, status=R[p].status)
-        for k in ("outcome", "line3d"): d[k] = o[k][:n1] if ok else o[k]
-        nc = max(0, min(R[p].n_created, n1)) if ok else len(o["created_idx0"])
-        for k in ("created_idx0", "created_idx1", "created_idx2"): d[k] = o[k][:nc]
-        res.append(d)
-    return matches, res, dict(owner_pair=owner[:n1] if ok else owner, n_new=S.n_new, n_pairs=S.n_pairs, kernel_ms=tuple(S.kernel_ms))
 
 MR_DESCRIPTOR, MR_GEOMETRY = 1, 2
 MR_MAX_OBS, MR_MAX_FEATURES, MR_MAX_OBS_TOTAL = 256, 65536, 1 << 20
@@ -1217,8 +1115,12 @@ class MrLineOut(C.Structure):
     _fields_ = [("best_obs", C.c_void_p), ("best_median", C.c_void_p), ("desc", C.c_void_p), ("normal", C.c_void_p), ("wvec", C.c_void_p), ("max_dist", C.c_void_p),
                 ("min_dist", C.c_void_p), ("status", C.c_void_p), ("kernel_ms", C.c_float)]
 
-
-assert C.sizeof(MrParams) == 12 and C.sizeof(MrInput) == 64 and C.sizeof(MrPointOut) == 64 and C.sizeof(MrLineOut) == 72
+# ---- the map refresh: MR_UNTOUCHED before the call; every input may be missing (NULL, the library's to refuse)
+MR_IN = _m.Inputs([("obs_start", _i32, (), REQ, None), ("obs_desc", _u8, (32,), OPT, None), ("obs_Ow", _f32, (3,), OPT, None), ("kf_bad", bool, (), OPT, None),
+                   ("ref_Ow", _f32, (3,), OPT, None), ("ref_level", _i32, (), OPT, None), ("skip", bool, (), OPT, None)], count=None)
+MR_OUT = tuple(_m.Outputs([_entry("best_obs", _i32), _entry("best_median", _i32), _entry("desc", _u8, 32), _entry("normal", rdt, 3), _entry("max_dist", _f32),
+                           _entry("min_dist", _f32), _entry("status", _u8)] + more, MR_UNTOUCHED, scalars=("kernel_ms",))
+               for rdt, more in ((_f32, []), (_f64, [_entry("wvec", _f64, 3)])))            # [line]: points, lines
 
 
 def map_refresh_check(obs_start):
@@ -1236,44 +1138,24 @@ def map_refresh_check(obs_start):
 
 
 def _mr_args(line, obs_start, obs_desc, obs_Ow, ref_Ow, ref_level, kf_bad, skip, n_levels, scale_factor, what, want):
-    """(params, input, output struct, the output arrays, what must stay alive).  An array given as None stays NULL and is the library's to
-    refuse; want: the outputs to make room for (the others are passed as NULL)"""
-    st = np.ascontiguousarray(obs_start, np.int32).reshape(-1)
-    n = max(len(st) - 1, 0); m = max(n, 1); rdt = np.float64 if line else np.float32
-    byte = lambda v: None if v is None else np.ascontiguousarray(np.asarray(v).astype(bool), np.uint8).reshape(-1)
-    a = dict(obs_start=st, obs_desc=None if obs_desc is None else np.ascontiguousarray(obs_desc, np.uint8).reshape(-1, 32),
-             obs_Ow=None if obs_Ow is None else np.ascontiguousarray(obs_Ow, np.float32).reshape(-1, 3), kf_bad=byte(kf_bad),
-             ref_Ow=None if ref_Ow is None else np.ascontiguousarray(ref_Ow, np.float32).reshape(-1, 3),
-             ref_level=None if ref_level is None else np.ascontiguousarray(ref_level, np.int32).reshape(-1), skip=byte(skip))
-    I = MrInput(); I.n = n
-    for k, v in a.items(): setattr(I, k, v.ctypes.data if v is not None and v.size else None)
-    o = dict(best_obs=np.full(m, MR_UNTOUCHED, np.int32), best_median=np.full(m, MR_UNTOUCHED, np.int32), desc=np.full((m, 32), MR_UNTOUCHED, np.uint8),
-             normal=np.full((m, 3), MR_UNTOUCHED, rdt), max_dist=np.full(m, MR_UNTOUCHED, np.float32), min_dist=np.full(m, MR_UNTOUCHED, np.float32),
-             status=np.full(m, MR_UNTOUCHED, np.uint8))
-    if line: o["wvec"] = np.full((m, 3), MR_UNTOUCHED, np.float64)
+    """(params, input, output struct, the output arrays, n, what must stay alive).  want: the outputs to hand to the call; the others are
+    passed as NULL, and their arrays come back untouched"""
+    I = MrInput()
+    a, _ = MR_IN.fill(I, dict(obs_start=obs_start, obs_desc=obs_desc, obs_Ow=obs_Ow, kf_bad=kf_bad, ref_Ow=ref_Ow, ref_level=ref_level, skip=skip))
+    n = I.n = max(len(a["obs_start"]) - 1, 0)
     O = MrLineOut() if line else MrPointOut()
-    for k, v in o.items(): setattr(O, k, v.ctypes.data if (want is None or k in want) else None)
-    O.kernel_ms = 0.0
+    o = MR_OUT[line].alloc(O, want, n=n)
     P = MrParams(); P.n_levels = n_levels; P.scale_factor = scale_factor; P.what = what
     return P, I, O, o, n, a
-
-
-def _mr_finish(O, o, n):
-    return dict({k: v[:n] for k, v in o.items()}, kernel_ms=O.kernel_ms)
 
 
 def _mr_call(ctx, name, line, pre, post, obs, n_levels, scale_factor, what, want, check):
     map_refresh_check(obs["obs_start"])
     P, I, O, o, n, keep = _mr_args(line, obs["obs_start"], obs.get("obs_desc"), obs.get("obs_Ow"), obs.get("ref_Ow"), obs.get("ref_level"), obs.get("kf_bad"),
                                    obs.get("skip"), n_levels, scale_factor, what, want)
-    f = getattr(lib(), name); f.restype = C.c_int
-    f.argtypes = [C.c_void_p] * (len(pre) + len(post) + 4)
-    rc = f(ctx.h, *pre, C.addressof(P), C.addressof(I), *post, C.addressof(O))
+    rc = getattr(lib(), name)(ctx.h, *pre, C.addressof(P), C.addressof(I), *post, C.addressof(O))
     del keep
-    if not check:
-        return rc, lib().hvo_last_error(ctx.h).decode(), _mr_finish(O, o, n)
-    ctx._chk(rc, name[4:])
-    return _mr_finish(O, o, n)
+    return _ret(ctx, rc, name[4:], lambda ok: MR_OUT[line].finish(O, o, n=n), check)
 
 
 def line_struct_params(**kw):
@@ -1396,8 +1278,6 @@ def _tail_result(b, t, n_kl, n_planes, stages):
     if stages & STAGE_GRIDS:
         r["pt_grid"] = (b["pt_cell_start"], b["pt_cell_items"][: t.n_pt_items]); r["ln_grid"] = (b["ln_cell_start"], b["ln_cell_items"][: t.n_ln_items])
     return r
-
-
 def build(force=False):
     """compile libhvo.so in-tree with hipcc --offload-arch=gfx950 (cross-compiles without a GPU)"""
     if force:
@@ -1413,7 +1293,238 @@ def torch_order_check():
                            "Import torch (and call torch.cuda.init()) BEFORE the first hvo call in processes that use hvo_amd.dist.")
 
 
+# argtypes / restype of every hvo_* function the binding calls, applied once by lib(); name -> (restype, argtypes)
+SIGNATURES = {
+    "hvo_strerror": (C.c_char_p, [C.c_int]),
+    "hvo_last_error": (C.c_char_p, [C.c_void_p]),
+    "hvo_default_params": (None, [C.POINTER(Params)]),
+    "hvo_create": (C.c_int, [C.POINTER(Params), C.POINTER(C.c_void_p)]),
+    "hvo_destroy": (None, [C.c_void_p]),
+    "hvo_extract_orb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "hvo_extract_lsd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "hvo_compute_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "hvo_hamming_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "hvo_hamming_knn2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hvo_match_nnr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_int)]),
+    "hvo_search_by_projection": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "hvo_frame_bf_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int)]),
+    "hvo_match_lines_geom": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "hvo_search_lines_by_projection": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "hvo_stream_match_lines_geom": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hvo_stream_search_lines_by_projection": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "hvo_pose_optimize": (C.c_int, [C.c_void_p, C.POINTER(PoseCamera), C.c_void_p, C.c_int, C.POINTER(PoseProblem), C.POINTER(PoseResult), C.POINTER(PoseFlags)]),
+    "hvo_pose_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "hvo_stream_pose_last_kernel_ms": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_float)]),
+    "hvo_stream_pose_optimize": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(PoseProblem), C.POINTER(PoseResult), C.POINTER(PoseFlags)]),
+    "hvo_line_struct_default_params": (C.c_int, [C.POINTER(LineStructParams)]),
+    "hvo_line_struct_optimize": (C.c_int, [C.c_void_p, C.POINTER(LineStructParams), C.c_int, C.POINTER(LineStructProblem), C.c_void_p, C.c_void_p, C.POINTER(LineOptResult)]),
+    "hvo_batch_line_struct_optimize": (C.c_int, [C.c_void_p, C.POINTER(LineStructParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LineOptResult)]),
+    "hvo_stream_line_struct_optimize": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(LineStructParams), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(LineOptResult)]),
+    "hvo_line_opt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "hvo_stream_line_opt_last_kernel_ms": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_float)]),
+    "hvo_track_manhattan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MfResult), C.c_void_p, C.c_void_p]),
+    "hvo_stream_track_manhattan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MfResult), C.c_void_p, C.c_void_p]),
+    "hvo_batch_track_manhattan": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hvo_plane_map_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int64]),
+    "hvo_plane_map_destroy": (None, [C.c_void_p]),
+    "hvo_plane_map_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "hvo_plane_map_set_bad": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "hvo_plane_map_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "hvo_plane_map_slot": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hvo_plane_map_last_error": (C.c_char_p, [C.c_void_p]),
+    "hvo_match_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PlaneMatch), C.c_void_p, C.c_void_p]),
+    "hvo_stream_match_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PlaneMatch)]),
+    "hvo_batch_match_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hvo_update_map_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PlaneUpdate), C.POINTER(PlaneUpdateResult)]),
+    "hvo_stream_update_map_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PlaneUpdate), C.POINTER(PlaneUpdateResult)]),
+    "hvo_plane_map_get_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "hvo_plane_update_transform": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hvo_local_ba_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "hvo_local_ba_destroy": (None, [C.c_void_p]),
+    "hvo_local_ba_last_error": (C.c_char_p, [C.c_void_p]),
+    "hvo_local_ba_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "hvo_local_ba_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_float * 4), C.POINTER(C.c_int32 * 2)]),
+    "hvo_local_ba_default_params": (None, [C.POINTER(LocalBAParams)]),
+    "hvo_local_ba_optimize": (C.c_int, [C.c_void_p, C.POINTER(LocalBAParams), C.POINTER(LocalBAGraph), C.c_void_p, C.POINTER(LocalBAResult)]),
+    "hvo_line_map_create": (C.c_void_p, [C.c_int, C.c_int]),
+    "hvo_line_map_destroy": (None, [C.c_void_p]),
+    "hvo_line_map_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int]),
+    "hvo_line_map_set_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8),
+    "hvo_line_map_set_bad": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "hvo_line_map_set_observed": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "hvo_line_map_counts": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 3),
+    "hvo_line_map_slot": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hvo_line_map_last_error": (C.c_char_p, [C.c_void_p]),
+    "hvo_search_local_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalLinesParams), C.POINTER(LocalLinesFrame), C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]),
+    "hvo_stream_search_local_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalLinesParams), C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]),
+    "hvo_batch_search_local_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalLinesParams), C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]),
+    "hvo_point_map_create": (C.c_void_p, [C.c_int, C.c_int]),
+    "hvo_point_map_destroy": (None, [C.c_void_p]),
+    "hvo_point_map_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int]),
+    "hvo_point_map_set_many": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7),
+    "hvo_point_map_set_bad": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "hvo_point_map_set_observed": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "hvo_point_map_counts": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 3),
+    "hvo_point_map_slot": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hvo_point_map_last_error": (C.c_char_p, [C.c_void_p]),
+    "hvo_search_local_points": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalPointsParams), C.POINTER(LocalPointsFrame), C.POINTER(LocalPointsIO), C.POINTER(LocalPointsResult)]),
+    "hvo_stream_search_local_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalPointsParams), C.POINTER(LocalPointsIO), C.POINTER(LocalPointsResult)]),
+    "hvo_batch_search_local_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalPointsParams), C.POINTER(LocalPointsIO), C.POINTER(LocalPointsResult)]),
+    "hvo_kfi_default_params": (None, [C.POINTER(KfiParams)]),
+    "hvo_kf_insert_create": (C.c_void_p, [C.c_int]),
+    "hvo_kf_insert_destroy": (None, [C.c_void_p]),
+    "hvo_kf_insert_last_error": (C.c_char_p, [C.c_void_p]),
+    "hvo_create_keyframe_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(KfiParams), C.POINTER(KfiFrame), C.POINTER(KfiIO), C.POINTER(KfiResult)]),
+    "hvo_stream_create_keyframe_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(KfiParams), C.POINTER(KfiIO), C.POINTER(KfiResult)]),
+    "hvo_vocabulary_create": (C.c_int, [C.c_int] * 6 + [C.c_void_p] * 4 + [C.POINTER(C.c_void_p)]),
+    "hvo_vocabulary_load_text": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "hvo_vocabulary_destroy": (None, [C.c_void_p]),
+    "hvo_vocabulary_info": (C.c_int, [C.c_void_p, C.POINTER(VocabularyDesc)]),
+    "hvo_compute_bow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Bow)]),
+    "hvo_stream_compute_bow": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(Bow)]),
+    "hvo_batch_compute_bow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Bow)]),
+    "hvo_search_by_bow": (C.c_int, [C.c_void_p, C.POINTER(BowKeyframe), C.c_int, C.POINTER(BowKeyframe), C.POINTER(BowSearchParams), C.POINTER(BowMatches)]),
+    "hvo_stream_search_by_bow": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(BowKeyframe), C.POINTER(BowSearchParams), C.POINTER(BowMatches)]),
+    "hvo_bow_last_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hvo_stream_bow_last_kernel_ms": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "hvo_keyframe_db_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "hvo_keyframe_db_destroy": (None, [C.c_void_p]),
+    "hvo_keyframe_db_last_error": (C.c_char_p, [C.c_void_p]),
+    "hvo_keyframe_db_add": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "hvo_stream_keyframe_db_add": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
+    "hvo_keyframe_db_erase": (C.c_int, [C.c_void_p, C.c_int]),
+    "hvo_keyframe_db_clear": (C.c_int, [C.c_void_p]),
+    "hvo_keyframe_db_set_covisible": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "hvo_keyframe_db_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "hvo_keyframe_db_info": (C.c_int, [C.c_void_p, C.POINTER(KeyframeDbDesc)]),
+    "hvo_keyframe_db_query": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(KfdbParams), C.POINTER(KfdbResult)]),
+    "hvo_stream_keyframe_db_query": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(KfdbParams), C.POINTER(KfdbResult)]),
+    "hvo_batch_keyframe_db_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(KfdbParams), C.POINTER(KfdbResult)]),
+    "hvo_keyframe_db_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "hvo_pnp_default_params": (None, [C.POINTER(PnpParams)]),
+    "hvo_pnp_ransac": (C.c_int, [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(PnpParams), C.c_int, C.POINTER(PnpProblem), C.POINTER(PnpResult)]),
+    "hvo_stream_pnp_ransac": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(PnpParams), C.c_int, C.POINTER(PnpKeyframeSide), C.POINTER(PnpResult)]),
+    "hvo_pnp_last_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hvo_search_by_projection_keyframe": (C.c_int, [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(KfSearchParams), C.POINTER(LocalPointsFrame), C.c_int, C.POINTER(KfSearchCandidate), C.POINTER(KfSearchResult)]),
+    "hvo_stream_search_by_projection_keyframe": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(KfSearchParams), C.c_int, C.POINTER(KfSearchCandidate), C.POINTER(KfSearchResult)]),
+    "hvo_fuse_points": (C.c_int, [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.POINTER(FuseMap), C.c_int, C.POINTER(FuseKeyframe), C.POINTER(FuseResult)]),
+    "hvo_fuse_points_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.c_int, C.POINTER(FuseKeyframe), C.POINTER(FuseResult)]),
+    "hvo_create_new_map_points": (C.c_int, [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(NpParams), C.POINTER(NpKeyframe), C.c_int, C.POINTER(NpKeyframe), C.POINTER(NpResult), C.POINTER(NpSummary)]),
+    "hvo_stream_create_new_map_points": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(PoseCamera), C.POINTER(NpParams), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(NpKeyframe), C.POINTER(NpResult), C.POINTER(NpSummary)]),
+    "hvo_fuse_lines": (C.c_int, [C.c_void_p, C.POINTER(LfParams), C.POINTER(LfMap), C.c_int, C.POINTER(LfKeyframe), C.POINTER(LfResult)]),
+    "hvo_fuse_lines_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(LfParams), C.c_int, C.POINTER(LfKeyframe), C.POINTER(LfResult)]),
+    "hvo_stream_fuse_lines": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(LfParams), C.c_void_p, C.c_void_p, C.POINTER(LfMap), C.c_void_p, C.c_int, C.c_void_p, C.POINTER(LfResult)]),
+    "hvo_stream_fuse_points": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.c_void_p, C.c_void_p, C.POINTER(FuseMap), C.c_void_p, C.c_int, C.c_void_p, C.POINTER(FuseResult)]),
+    "hvo_stream_pnp_last_kernel_ms": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "hvo_search_lines_by_projection_map": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "hvo_stream_search_lines_by_projection_map": (C.c_int, [C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "hvo_search_by_projection_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "hvo_stereo_from_rgbd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "hvo_set_line_culling": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double]),
+    "hvo_vanishing_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hvo_lines_3d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]),
+    "hvo_plane_clouds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "hvo_surface_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "hvo_undistort_keypoints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hvo_image_bounds": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "hvo_assign_features_to_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "hvo_assign_lines_to_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "hvo_batch_upload": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrameIn), C.c_int, C.c_int]),
+    "hvo_batch_run": (C.c_int, [C.c_void_p, C.c_uint]),
+    "hvo_batch_download": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrameOut)]),
+    "hvo_extract_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrameIn), C.POINTER(FrameOut), C.c_int, C.c_int, C.c_uint]),
+    "hvo_batch_slab_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "hvo_batch_pack_results": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "hvo_profile_last": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
+    "hvo_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
+    "hvo_pin_host": (C.c_int, [C.c_void_p, C.c_size_t]),
+    "hvo_unpin_host": (C.c_int, [C.c_void_p]),
+    "hvo_stream_create": (C.c_int, [C.POINTER(Params), C.POINTER(StreamParams), C.POINTER(C.c_void_p)]),
+    "hvo_stream_destroy": (None, [C.c_void_p]),
+    "hvo_stream_last_error": (C.c_char_p, [C.c_void_p]),
+    "hvo_stream_capacity": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 3),
+    "hvo_stream_image_bounds": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hvo_stream_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
+    "hvo_stream_poll": (C.c_int, [C.c_void_p, C.c_int64]),
+    "hvo_stream_collect": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(FrameOut), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hvo_stream_stage_ms": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "hvo_stream_search_by_projection": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "hvo_stream_match_lines": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hvo_normals_lpvo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "hvo_tail_capacity": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3),
+    "hvo_set_tail_params": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_double]),
+    "hvo_batch_download_tail": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(FrameTail)]),
+    "hvo_stream_collect_tail": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(FrameTail)]),
+}
+SIGNATURES["hvo_search_double"] = SIGNATURES["hvo_frame_bf_match"]
+SIGNATURES["hvo_batch_pose_optimize"] = SIGNATURES["hvo_pose_optimize"]
+SIGNATURES["hvo_extract_lsd_culled"] = SIGNATURES["hvo_extract_lsd"]
+SIGNATURES["hvo_batch_stage_upload"] = SIGNATURES["hvo_batch_upload"]
+SIGNATURES.update({
+    "hvo_batch_commit_staged": (C.c_int, [C.c_void_p]),
+    "hvo_batch_results_wait": (C.c_int, [C.c_void_p]),
+    "hvo_batch_results_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p]),
+    "hvo_batch_slab_layout_ex": (C.c_int, [C.c_void_p, C.c_uint] + [C.c_void_p] * 5),
+    "hvo_batch_pack_results_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
+    "hvo_lsd_async_report": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 3),
+    "hvo_set_readings": (C.c_int, [C.c_void_p, C.c_uint]),
+    "hvo_stream_set_readings": (C.c_int, [C.c_void_p, C.c_uint]),
+    "hvo_stream_project_last": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 +
+                                [C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "hvo_search_by_projection_tracked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int] +
+                                         [C.c_float] * 4 + [C.c_int, C.c_float] + [C.c_void_p] * 3),
+    # (ctx, params, current, n, neighbours, matches, pair capacity, results, summary); the stream form: (s, cur, cam[6], params, Tcw, has, n, ...)
+    "hvo_create_new_map_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hvo_stream_create_new_map_lines": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_int, C.c_void_p, C.c_void_p]),
+    # (ctx, params, input, positions, output) and (ctx, map, slots, params, input, output)
+    "hvo_refresh_map_points": (C.c_int, [C.c_void_p] * 5), "hvo_refresh_map_lines": (C.c_int, [C.c_void_p] * 5),
+    "hvo_point_map_refresh": (C.c_int, [C.c_void_p] * 6), "hvo_line_map_refresh": (C.c_int, [C.c_void_p] * 6),
+})
+# the test doors: exported by the library, not declared in include/hvo.h, so outside EXPORTS
+DEBUG_SIGNATURES = {
+    "hvo_debug_plan_select": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p]),
+    "hvo_debug_frame_perm": (C.c_int, [C.c_int, C.c_void_p]),
+    "hvo_debug_kf_insert_fill": (C.c_int, [C.c_void_p, C.c_int]),
+    "hvo_debug_line_map_scratch": (C.c_int, [C.c_void_p, C.c_int]), "hvo_debug_point_map_scratch": (C.c_int, [C.c_void_p, C.c_int]),
+    "hvo_debug_call_arena": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "hvo_debug_call_arena_peek": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "hvo_debug_stream_call_arena": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "hvo_debug_stream_call_arena_peek": (C.c_int, [C.c_void_p, C.c_int64, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "hvo_debug_lsd_images": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_longlong,
+                                       C.POINTER(C.c_longlong), C.c_void_p]),
+    "hvo_debug_lbd_desc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "hvo_debug_peac_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "hvo_debug_launch_report": (C.c_int, [C.c_void_p, C.c_void_p]),
+}
+
+# every mirror and the include/hvo.h type it mirrors.  Field names are the header's, except those Python cannot spell (HEADER_NAMES)
+HEADER_NAMES = {"lam": "lambda"}
+RECORDS = {
+    "hvo_keypoint": KEYPOINT_DT, "hvo_keyline": KEYLINE_DT, "hvo_plane": PLANE_DT, "hvo_line3d": LINE3D_DT, "hvo_plane_cloud": PLANE_CLOUD_DT,
+    "hvo_surface_normal": SURFACE_NORMAL_DT, "hvo_vp_result": VpResult, "hvo_params": Params, "hvo_frame_in": FrameIn, "hvo_frame_out": FrameOut,
+    "hvo_stream_params": StreamParams, "hvo_frame_tail": FrameTail, "hvo_mf_result": MfResult, "hvo_plane_match": PlaneMatch,
+    "hvo_plane_update": PlaneUpdate, "hvo_plane_update_result": PlaneUpdateResult, "hvo_pose_plane_params": PosePlaneParams, "hvo_camera": PoseCamera,
+    "hvo_pose_problem": PoseProblem, "hvo_pose_flags": PoseFlags, "hvo_pose_result": PoseResult, "hvo_line_struct_params": LineStructParams,
+    "hvo_line_struct_problem": LineStructProblem, "hvo_line_opt_result": LineOptResult, "hvo_local_lines_params": LocalLinesParams,
+    "hvo_local_lines_frame": LocalLinesFrame, "hvo_local_lines_io": LocalLinesIO, "hvo_local_lines_result": LocalLinesResult,
+    "hvo_local_points_params": LocalPointsParams, "hvo_local_points_frame": LocalPointsFrame, "hvo_local_points_io": LocalPointsIO,
+    "hvo_local_points_result": LocalPointsResult, "hvo_vocabulary_desc": VocabularyDesc, "hvo_bow": Bow, "hvo_bow_keyframe": BowKeyframe,
+    "hvo_bow_search_params": BowSearchParams, "hvo_bow_matches": BowMatches, "hvo_keyframe_db_desc": KeyframeDbDesc, "hvo_kfdb_params": KfdbParams,
+    "hvo_kfdb_result": KfdbResult, "hvo_local_ba_params": LocalBAParams, "hvo_local_ba_graph": LocalBAGraph, "hvo_local_ba_result": LocalBAResult,
+    "hvo_kfi_params": KfiParams, "hvo_kfi_frame": KfiFrame, "hvo_kfi_io": KfiIO, "hvo_kfi_result": KfiResult, "hvo_pnp_params": PnpParams,
+    "hvo_pnp_problem": PnpProblem, "hvo_pnp_event": PnpEvent, "hvo_pnp_result": PnpResult, "hvo_pnp_keyframe_side": PnpKeyframeSide,
+    "hvo_kf_search_candidate": KfSearchCandidate, "hvo_kf_search_params": KfSearchParams, "hvo_kf_search_result": KfSearchResult,
+    "hvo_fuse_keyframe": FuseKeyframe, "hvo_fuse_map": FuseMap, "hvo_fuse_params": FuseParams, "hvo_fuse_result": FuseResult,
+    "hvo_lf_keyframe": LfKeyframe, "hvo_lf_map": LfMap, "hvo_lf_params": LfParams, "hvo_lf_result": LfResult,
+    "hvo_np_keyframe": NpKeyframe, "hvo_np_params": NpParams, "hvo_np_result": NpResult, "hvo_np_summary": NpSummary,
+    "hvo_nl_keyframe": NlKeyframe, "hvo_nl_params": NlParams, "hvo_nl_match": NlMatch, "hvo_nl_result": NlResult, "hvo_nl_summary": NlSummary,
+    "hvo_mr_params": MrParams, "hvo_mr_input": MrInput, "hvo_mr_point_out": MrPointOut, "hvo_mr_line_out": MrLineOut,
+}
+
+
 def lib():
+    """libhvo.so, loaded on first use, every function with the signature SIGNATURES / DEBUG_SIGNATURES gives it"""
     global _LIB
     if _LIB is None:
         if not os.path.exists(_LIBPATH):
@@ -1422,193 +1533,8 @@ def lib():
         global _LOADED_BEFORE_TORCH
         _LOADED_BEFORE_TORCH = "torch" not in sys.modules
         L = C.CDLL(_LIBPATH)
-        L.hvo_strerror.restype = C.c_char_p
-        L.hvo_strerror.argtypes = [C.c_int]
-        L.hvo_last_error.restype = C.c_char_p
-        L.hvo_last_error.argtypes = [C.c_void_p]
-        L.hvo_default_params.argtypes = [C.POINTER(Params)]
-        L.hvo_default_params.restype = None
-        L.hvo_create.argtypes = [C.POINTER(Params), C.POINTER(C.c_void_p)]
-        L.hvo_destroy.argtypes = [C.c_void_p]
-        L.hvo_destroy.restype = None
-        L.hvo_extract_orb.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                      C.c_int, C.POINTER(C.c_int)]
-        L.hvo_extract_lsd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-        L.hvo_compute_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                         C.c_int, C.POINTER(C.c_int)]
-        L.hvo_hamming_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        L.hvo_hamming_knn2.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.hvo_match_nnr.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p,
-                                    C.POINTER(C.c_int)]
-        L.hvo_search_by_projection.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        L.hvo_frame_bf_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int)]
-        L.hvo_search_double.argtypes = L.hvo_frame_bf_match.argtypes
-        L.hvo_match_lines_geom.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        L.hvo_search_lines_by_projection.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        L.hvo_stream_match_lines_geom.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.hvo_stream_search_lines_by_projection.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        L.hvo_pose_optimize.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.c_void_p, C.c_int, C.POINTER(PoseProblem), C.POINTER(PoseResult), C.POINTER(PoseFlags)]
-        L.hvo_batch_pose_optimize.argtypes = L.hvo_pose_optimize.argtypes
-        L.hvo_pose_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        L.hvo_stream_pose_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
-        L.hvo_stream_pose_optimize.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(PoseProblem), C.POINTER(PoseResult), C.POINTER(PoseFlags)]
-        L.hvo_line_struct_default_params.argtypes = [C.POINTER(LineStructParams)]
-        L.hvo_line_struct_optimize.argtypes = [C.c_void_p, C.POINTER(LineStructParams), C.c_int, C.POINTER(LineStructProblem), C.c_void_p, C.c_void_p, C.POINTER(LineOptResult)]
-        L.hvo_batch_line_struct_optimize.argtypes = [C.c_void_p, C.POINTER(LineStructParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LineOptResult)]
-        L.hvo_stream_line_struct_optimize.argtypes = [C.c_void_p, C.c_int64, C.POINTER(LineStructParams), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(LineOptResult)]
-        L.hvo_line_opt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        L.hvo_stream_line_opt_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
-        L.hvo_track_manhattan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MfResult), C.c_void_p, C.c_void_p]
-        L.hvo_stream_track_manhattan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MfResult), C.c_void_p, C.c_void_p]
-        L.hvo_batch_track_manhattan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.hvo_plane_map_create.argtypes = [C.c_int, C.c_int, C.c_int64]; L.hvo_plane_map_create.restype = C.c_void_p
-        L.hvo_plane_map_destroy.argtypes = [C.c_void_p]; L.hvo_plane_map_destroy.restype = None
-        L.hvo_plane_map_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-        L.hvo_plane_map_set_bad.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.hvo_plane_map_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
-        L.hvo_plane_map_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.hvo_plane_map_last_error.argtypes = [C.c_void_p]; L.hvo_plane_map_last_error.restype = C.c_char_p
-        L.hvo_match_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PlaneMatch), C.c_void_p, C.c_void_p]
-        L.hvo_stream_match_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PlaneMatch)]
-        L.hvo_batch_match_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.hvo_update_map_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PlaneUpdate), C.POINTER(PlaneUpdateResult)]
-        L.hvo_stream_update_map_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(PlaneUpdate), C.POINTER(PlaneUpdateResult)]
-        L.hvo_plane_map_get_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-        L.hvo_plane_update_transform.argtypes = [C.c_void_p, C.c_void_p]
-        L.hvo_local_ba_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.hvo_local_ba_destroy.argtypes = [C.c_void_p]; L.hvo_local_ba_destroy.restype = None
-        L.hvo_local_ba_last_error.argtypes = [C.c_void_p]; L.hvo_local_ba_last_error.restype = C.c_char_p
-        L.hvo_local_ba_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        L.hvo_local_ba_last_profile.argtypes = [C.c_void_p, C.POINTER(C.c_float * 4), C.POINTER(C.c_int32 * 2)]
-        L.hvo_local_ba_default_params.argtypes = [C.POINTER(LocalBAParams)]; L.hvo_local_ba_default_params.restype = None
-        L.hvo_local_ba_optimize.argtypes = [C.c_void_p, C.POINTER(LocalBAParams), C.POINTER(LocalBAGraph), C.c_void_p, C.POINTER(LocalBAResult)]
-        L.hvo_line_map_create.argtypes = [C.c_int, C.c_int]; L.hvo_line_map_create.restype = C.c_void_p
-        L.hvo_line_map_destroy.argtypes = [C.c_void_p]; L.hvo_line_map_destroy.restype = None
-        L.hvo_line_map_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int]
-        L.hvo_line_map_set_many.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8
-        L.hvo_line_map_set_bad.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.hvo_line_map_set_observed.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.hvo_line_map_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
-        L.hvo_line_map_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
-                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.hvo_line_map_last_error.argtypes = [C.c_void_p]; L.hvo_line_map_last_error.restype = C.c_char_p
-        L.hvo_search_local_lines.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalLinesParams), C.POINTER(LocalLinesFrame),
-                                             C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]
-        L.hvo_stream_search_local_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalLinesParams),
-                                                    C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]
-        L.hvo_batch_search_local_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalLinesParams),
-                                                   C.POINTER(LocalLinesIO), C.POINTER(LocalLinesResult)]
-        L.hvo_point_map_create.argtypes = [C.c_int, C.c_int]; L.hvo_point_map_create.restype = C.c_void_p
-        L.hvo_point_map_destroy.argtypes = [C.c_void_p]; L.hvo_point_map_destroy.restype = None
-        L.hvo_point_map_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int]
-        L.hvo_point_map_set_many.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
-        L.hvo_point_map_set_bad.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.hvo_point_map_set_observed.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.hvo_point_map_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
-        L.hvo_point_map_slot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
-                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.hvo_point_map_last_error.argtypes = [C.c_void_p]; L.hvo_point_map_last_error.restype = C.c_char_p
-        L.hvo_search_local_points.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalPointsParams), C.POINTER(LocalPointsFrame),
-                                              C.POINTER(LocalPointsIO), C.POINTER(LocalPointsResult)]
-        L.hvo_stream_search_local_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalPointsParams),
-                                                     C.POINTER(LocalPointsIO), C.POINTER(LocalPointsResult)]
-        L.hvo_batch_search_local_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(LocalPointsParams),
-                                                    C.POINTER(LocalPointsIO), C.POINTER(LocalPointsResult)]
-        L.hvo_kfi_default_params.argtypes = [C.POINTER(KfiParams)]; L.hvo_kfi_default_params.restype = None
-        L.hvo_kf_insert_create.argtypes = [C.c_int]; L.hvo_kf_insert_create.restype = C.c_void_p
-        L.hvo_kf_insert_destroy.argtypes = [C.c_void_p]; L.hvo_kf_insert_destroy.restype = None
-        L.hvo_kf_insert_last_error.argtypes = [C.c_void_p]; L.hvo_kf_insert_last_error.restype = C.c_char_p
-        L.hvo_create_keyframe_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseCamera), C.c_void_p, C.POINTER(KfiParams),
-                                                   C.POINTER(KfiFrame), C.POINTER(KfiIO), C.POINTER(KfiResult)]
-        L.hvo_stream_create_keyframe_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.c_void_p,
-                                                          C.POINTER(KfiParams), C.POINTER(KfiIO), C.POINTER(KfiResult)]
-        L.hvo_vocabulary_create.argtypes = [C.c_int] * 6 + [C.c_void_p] * 4 + [C.POINTER(C.c_void_p)]
-        L.hvo_vocabulary_load_text.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
-        L.hvo_vocabulary_destroy.argtypes = [C.c_void_p]; L.hvo_vocabulary_destroy.restype = None
-        L.hvo_vocabulary_info.argtypes = [C.c_void_p, C.POINTER(VocabularyDesc)]
-        L.hvo_compute_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Bow)]
-        L.hvo_stream_compute_bow.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(Bow)]
-        L.hvo_batch_compute_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Bow)]
-        L.hvo_search_by_bow.argtypes = [C.c_void_p, C.POINTER(BowKeyframe), C.c_int, C.POINTER(BowKeyframe), C.POINTER(BowSearchParams), C.POINTER(BowMatches)]
-        L.hvo_stream_search_by_bow.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(BowKeyframe), C.POINTER(BowSearchParams), C.POINTER(BowMatches)]
-        L.hvo_bow_last_kernel_ms.argtypes = [C.c_void_p, C.c_void_p]
-        L.hvo_stream_bow_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-        L.hvo_keyframe_db_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        L.hvo_keyframe_db_destroy.argtypes = [C.c_void_p]; L.hvo_keyframe_db_destroy.restype = None
-        L.hvo_keyframe_db_last_error.argtypes = [C.c_void_p]; L.hvo_keyframe_db_last_error.restype = C.c_char_p
-        L.hvo_keyframe_db_add.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.hvo_stream_keyframe_db_add.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
-        L.hvo_keyframe_db_erase.argtypes = [C.c_void_p, C.c_int]
-        L.hvo_keyframe_db_clear.argtypes = [C.c_void_p]
-        L.hvo_keyframe_db_set_covisible.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.hvo_keyframe_db_get.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
-        L.hvo_keyframe_db_info.argtypes = [C.c_void_p, C.POINTER(KeyframeDbDesc)]
-        L.hvo_keyframe_db_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(KfdbParams), C.POINTER(KfdbResult)]
-        L.hvo_stream_keyframe_db_query.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(KfdbParams), C.POINTER(KfdbResult)]
-        L.hvo_batch_keyframe_db_query.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(KfdbParams), C.POINTER(KfdbResult)]
-        L.hvo_keyframe_db_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        L.hvo_pnp_default_params.argtypes = [C.POINTER(PnpParams)]; L.hvo_pnp_default_params.restype = None
-        L.hvo_pnp_ransac.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(PnpParams), C.c_int, C.POINTER(PnpProblem), C.POINTER(PnpResult)]
-        L.hvo_stream_pnp_ransac.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(PnpParams), C.c_int, C.POINTER(PnpKeyframeSide), C.POINTER(PnpResult)]
-        L.hvo_pnp_last_kernel_ms.argtypes = [C.c_void_p, C.c_void_p]
-        L.hvo_search_by_projection_keyframe.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(KfSearchParams), C.POINTER(LocalPointsFrame), C.c_int,
-                                                        C.POINTER(KfSearchCandidate), C.POINTER(KfSearchResult)]
-        L.hvo_stream_search_by_projection_keyframe.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(KfSearchParams), C.c_int,
-                                                               C.POINTER(KfSearchCandidate), C.POINTER(KfSearchResult)]
-        L.hvo_fuse_points.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.POINTER(FuseMap), C.c_int, C.POINTER(FuseKeyframe), C.POINTER(FuseResult)]
-        L.hvo_fuse_points_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.c_int, C.POINTER(FuseKeyframe),
-                                            C.POINTER(FuseResult)]
-        L.hvo_create_new_map_points.argtypes = [C.c_void_p, C.POINTER(PoseCamera), C.POINTER(NpParams), C.POINTER(NpKeyframe), C.c_int, C.POINTER(NpKeyframe),
-                                                C.POINTER(NpResult), C.POINTER(NpSummary)]
-        L.hvo_stream_create_new_map_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(PoseCamera), C.POINTER(NpParams), C.c_void_p, C.c_void_p, C.c_int,
-                                                       C.POINTER(NpKeyframe), C.POINTER(NpResult), C.POINTER(NpSummary)]
-        L.hvo_fuse_lines.argtypes = [C.c_void_p, C.POINTER(LfParams), C.POINTER(LfMap), C.c_int, C.POINTER(LfKeyframe), C.POINTER(LfResult)]
-        L.hvo_fuse_lines_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(LfParams), C.c_int, C.POINTER(LfKeyframe), C.POINTER(LfResult)]
-        L.hvo_stream_fuse_lines.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(LfParams), C.c_void_p, C.c_void_p, C.POINTER(LfMap), C.c_void_p,
-                                            C.c_int, C.c_void_p, C.POINTER(LfResult)]
-        L.hvo_stream_fuse_points.argtypes = [C.c_void_p, C.c_int64, C.POINTER(PoseCamera), C.POINTER(FuseParams), C.c_void_p, C.c_void_p, C.POINTER(FuseMap), C.c_void_p,
-                                             C.c_int, C.c_void_p, C.POINTER(FuseResult)]
-        L.hvo_stream_pnp_last_kernel_ms.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-        L.hvo_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int] + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        L.hvo_stream_search_lines_by_projection_map.argtypes = [C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        L.hvo_search_by_projection_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        L.hvo_stereo_from_rgbd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
-        L.hvo_extract_lsd_culled.argtypes = L.hvo_extract_lsd.argtypes
-        L.hvo_set_line_culling.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
-        L.hvo_vanishing_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.hvo_lines_3d.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]
-        L.hvo_plane_clouds.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
-        L.hvo_surface_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-        L.hvo_undistort_keypoints.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.hvo_image_bounds.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.hvo_assign_features_to_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        L.hvo_assign_lines_to_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-        L.hvo_batch_upload.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameIn), C.c_int, C.c_int]
-        L.hvo_batch_run.argtypes = [C.c_void_p, C.c_uint]
-        L.hvo_batch_download.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameOut)]
-        L.hvo_extract_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameIn), C.POINTER(FrameOut), C.c_int, C.c_int, C.c_uint]
-        L.hvo_batch_slab_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
-        L.hvo_batch_pack_results.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.hvo_profile_last.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
-        L.hvo_profile_enable.argtypes = [C.c_void_p, C.c_int]
-        L.hvo_pin_host.argtypes = [C.c_void_p, C.c_size_t]; L.hvo_unpin_host.argtypes = [C.c_void_p]
-        L.hvo_stream_create.argtypes = [C.POINTER(Params), C.POINTER(StreamParams), C.POINTER(C.c_void_p)]
-        L.hvo_stream_destroy.argtypes = [C.c_void_p]; L.hvo_stream_destroy.restype = None
-        L.hvo_stream_last_error.argtypes = [C.c_void_p]; L.hvo_stream_last_error.restype = C.c_char_p
-        L.hvo_stream_capacity.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
-        L.hvo_stream_image_bounds.argtypes = [C.c_void_p, C.c_void_p]
-        L.hvo_stream_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
-        L.hvo_stream_poll.argtypes = [C.c_void_p, C.c_int64]
-        L.hvo_stream_collect.argtypes = [C.c_void_p, C.c_int64, C.POINTER(FrameOut), C.c_void_p, C.c_void_p, C.c_void_p]
-        L.hvo_stream_stage_ms.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-        L.hvo_stream_search_by_projection.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        L.hvo_stream_match_lines.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.hvo_normals_lpvo.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-        L.hvo_tail_capacity.argtypes = [C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
-        L.hvo_set_tail_params.argtypes = [C.c_void_p, C.c_uint32, C.c_double, C.c_double]
-        L.hvo_batch_download_tail.argtypes = [C.c_void_p, C.c_int, C.POINTER(FrameTail)]
-        L.hvo_stream_collect_tail.argtypes = [C.c_void_p, C.c_int64, C.POINTER(FrameTail)]
+        for name, (restype, argtypes) in list(SIGNATURES.items()) + [kv for kv in DEBUG_SIGNATURES.items() if hasattr(L, kv[0])]:
+            f = getattr(L, name); f.restype = restype; f.argtypes = argtypes
         _LIB = L
     return _LIB
 
@@ -1643,7 +1569,6 @@ def plan_select(w, h, n, max_batch=None, stages=STAGE_ALL):
     """diagnostics: the kernels a batch of n frames of w x h would take in a context of max_batch frames (default: n) under the current
     environment -- the selection functions the launches use, evaluated on the host: no context, no device"""
     L = lib()
-    L.hvo_debug_plan_select.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p]; L.hvo_debug_plan_select.restype = C.c_int
     m = np.zeros(48, np.int32)
     rc = L.hvo_debug_plan_select(int(w), int(h), int(n), int(max_batch if max_batch is not None else n), int(stages), _p(m))
     if rc:
@@ -1654,7 +1579,6 @@ def plan_select(w, h, n, max_batch=None, stages=STAGE_ALL):
 def frame_perm(n):
     """diagnostics: the launch order of n items (the bit-reversal order the one-wave-per-frame kernels take their frames in), host only"""
     L = lib()
-    L.hvo_debug_frame_perm.argtypes = [C.c_int, C.c_void_p]; L.hvo_debug_frame_perm.restype = C.c_int
     m = np.zeros(int(n), np.int32)
     rc = L.hvo_debug_frame_perm(int(n), _p(m))
     if rc:
@@ -1895,7 +1819,7 @@ class KeyFrameInsert:
 
     def debug_fill(self, byte):
         """test door, not product API: the workspace's two blocks, at the sizes they have, set to `byte`"""
-        f = lib().hvo_debug_kf_insert_fill; f.argtypes = [C.c_void_p, C.c_int]; f.restype = C.c_int
+        f = lib().hvo_debug_kf_insert_fill
         self._chk(f(self.h, int(byte)), "debug_fill")
 
 
@@ -1938,14 +1862,14 @@ class _SlotMap:
         (and world vector) are rewritten in place; observed and bad are never touched.  Returns what the array form returns"""
         sl = None if slots is None else np.ascontiguousarray(slots, np.int32).reshape(-1)
         line = self._c == "line_map"
-        return _mr_call(ctx, "hvo_%s_refresh" % self._c, line, (self.h, sl.ctypes.data if sl is not None and sl.size else None), (), obs, n_levels, scale_factor, what, want, check)
+        return _mr_call(ctx, "hvo_%s_refresh" % self._c, line, (self.h, _m.ptr(sl)), (), obs, n_levels, scale_factor, what, want, check)
 
     def set_bad(self, slot, bad=True):
         self._chk(self._f("set_bad")(self.h, slot, 1 if bad else 0), "set_bad")
 
     def debug_fill_scratch(self, byte):
         """test door, not product API: the map's two call-scratch buffers, at the sizes they have, set to `byte`"""
-        f = getattr(lib(), "hvo_debug_%s_scratch" % self._c); f.argtypes = [C.c_void_p, C.c_int]; f.restype = C.c_int
+        f = getattr(lib(), "hvo_debug_%s_scratch" % self._c)
         self._chk(f(self.h, int(byte)), "debug_fill_scratch")
 
     def set_observed(self, slot, observed=True):
@@ -2147,21 +2071,24 @@ class Context:
 
     __del__ = close
 
+    def _last_error(self):
+        return lib().hvo_last_error(self.h)
+
     def _chk(self, rc, what):
         if rc != HVO_OK:
-            raise HvoError(rc, what + ": " + lib().hvo_last_error(self.h).decode())
+            raise HvoError(rc, what + ": " + self._last_error().decode())
 
     def debug_call_arena(self, fill=None, min_bytes=0):
         """test door, not product API: grow the context's call arena to at least min_bytes the way a call would, set its whole capacity to the byte
         `fill` (None: leave it) and return the capacity in bytes"""
-        L = lib(); f = L.hvo_debug_call_arena; f.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]; f.restype = C.c_int
+        L = lib(); f = L.hvo_debug_call_arena
         cap = C.c_size_t(0)
         self._chk(f(self.h, -1 if fill is None else int(fill), int(min_bytes), C.byref(cap)), "debug_call_arena")
         return cap.value
 
     def debug_call_arena_peek(self, offset, n):
         """test door, not product API: n bytes of the call arena from `offset` -> uint8 array"""
-        L = lib(); f = L.hvo_debug_call_arena_peek; f.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]; f.restype = C.c_int
+        L = lib(); f = L.hvo_debug_call_arena_peek
         out = np.zeros(int(n), np.uint8)
         self._chk(f(self.h, int(offset), int(n), _p(out)), "debug_call_arena_peek")
         return out
@@ -2258,8 +2185,6 @@ class Context:
         `frame` -- the defined mask (sh x words u32, a bit per scaled pixel), the 32-byte records {angle, cos, sin, modgrad} of the defined
         pixels in raster order (n x 4 f64) and the LBD gradient image (h x w x 2 i16).  Only for a batch of at most one chunk."""
         L = lib()
-        L.hvo_debug_lsd_images.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]
-        L.hvo_debug_lsd_images.restype = C.c_int
         w, h = self._w, self._h
         sw, sh = int(round(w * 0.8)), int(round(h * 0.8))
         mask = np.zeros((sh, (sw + 31) // 32), np.uint32); rec = np.zeros((sw * sh, 4), np.float64); dxy = np.zeros((h, w, 2), np.int16)
@@ -2274,8 +2199,6 @@ class Context:
         image, by the plan's blur / Sobel and the descriptor kernels HVO_LBD_DESC selected when the plan was built.  The image is uploaded
         as a batch of one: the resident batch and the results of the last batch_run are gone afterwards (upload and run again)"""
         L = lib()
-        L.hvo_debug_lbd_desc.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        L.hvo_debug_lbd_desc.restype = C.c_int
         gray = np.ascontiguousarray(gray, np.uint8); h, w = gray.shape
         kl = np.ascontiguousarray(keylines, KEYLINE_DT)
         desc = np.zeros((len(kl), 32), np.uint8)
@@ -2285,7 +2208,6 @@ class Context:
     def peac_stats(self, frame=0):
         """diagnostics (not part of the reference interface): bookkeeping words of the last plane run of `frame`"""
         L = lib()
-        L.hvo_debug_peac_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]; L.hvo_debug_peac_stats.restype = C.c_int
         m = np.zeros(16, np.int32)
         self._chk(L.hvo_debug_peac_stats(self.h, frame, _p(m)), "peac_stats")
         return {"segments": int(m[0]), "coarse_planes": int(m[2]), "flags": int(m[3]), "planes": int(m[4]), "queue_entries": int(m[5]),
@@ -2295,7 +2217,6 @@ class Context:
         """diagnostics (not part of the reference interface): which kernels the last batch_run / compute_planes / extract_lsd of this
         context launched, as _launch_report_dict lays them out; the same record plan_select() gives without a device"""
         L = lib()
-        L.hvo_debug_launch_report.argtypes = [C.c_void_p, C.c_void_p]; L.hvo_debug_launch_report.restype = C.c_int
         m = np.zeros(48, np.int32)
         self._chk(L.hvo_debug_launch_report(self.h, _p(m)), "launch_report")
         return _launch_report_dict(m)
@@ -2469,7 +2390,7 @@ class Context:
             if fn is not None and len(fn) != len(l3): raise ValueError("linefn: %d rows for %d lines" % (len(fn), len(l3)))
             if not (p.mode & LINE_STRUCT_CONSTRAINTS) and d.get("rel") is None: raise ValueError("rel is needed without LINE_STRUCT_CONSTRAINTS")
             keep += [l3, fn]
-            P[i].n_lines = len(l3); P[i].lines3d = l3.ctypes.data if len(l3) else None; P[i].linefn = fn.ctypes.data if fn is not None and len(fn) else None
+            P[i].n_lines = len(l3); P[i].lines3d = _m.ptr(l3); P[i].linefn = _m.ptr(fn)
         out = self._ls_call(lib().hvo_line_struct_optimize, "line_struct_optimize", p, [int(q.n_lines) for q in P], P, [d.get("rel") for d in probs])
         return out[0] if single else out
 
@@ -2539,7 +2460,7 @@ class Context:
                 np.ascontiguousarray(cell_start, np.int32), np.ascontiguousarray(cell_items, np.int32)]
         F = LocalLinesFrame(); F.n_kl = nt
         for k, v in zip(("kl", "linefn", "l3d", "desc", "cell_start", "cell_items"), keep):
-            setattr(F, k, v.ctypes.data if v.size else None)
+            setattr(F, k, _m.ptr(v))
         io, a = _ll_io(nt, lmap.counts()[0], held, seen_extra, rel_map)
         T = np.ascontiguousarray(Tcw, np.float32).reshape(12); c = _pose_cam(cam); p = _ll_params(bounds4, log_scale_factor, th, nn_ratio)
         r = LocalLinesResult()
@@ -2567,11 +2488,7 @@ class Context:
         the resident PointMap under the pose Tcw (3 x 4): frustum test of every slot, SearchByProjection(F, vpMapPoints, th) on the points in
         view, the assignment.  held: what each key point holds at entry (a slot, -1, HELD_FOREIGN_OBSERVED, HELD_FOREIGN_UNOBSERVED) ->
         LocalPointsResult with .held, .in_view_slot, .proj (u, v, ur), .view_cos, .level, .match_idx, .match_dist"""
-        kp = np.ascontiguousarray(t_kp_un, KEYPOINT_DT); nt = len(kp)
-        ur = None if t_uright is None else np.ascontiguousarray(t_uright, np.float32).reshape(nt)
-        d = np.ascontiguousarray(t_desc, np.uint8).reshape(nt, 32)
-        F = LocalPointsFrame(); F.n = nt
-        F.kp_un = kp.ctypes.data if nt else None; F.uright = None if ur is None or not nt else ur.ctypes.data; F.desc = d.ctypes.data if nt else None
+        F, keep, nt = _lp_frame(t_kp_un, t_uright, t_desc)
         io, a = _lp_io(nt, pmap.counts()[0], held, seen_extra)
         T = np.ascontiguousarray(Tcw, np.float32).reshape(12); c = _pose_cam(cam)
         p = _lp_params(bounds4, log_scale_factor, n_levels, float(cam[4]) if bf is None else bf, th, th_high, nn_ratio, view_cos_limit)
@@ -2622,7 +2539,7 @@ class Context:
         nf = len(ds); B = (Bow * nf)(); keep = []
         for f, d in enumerate(ds):
             B[f], a = _bow_out(len(d)); keep.append(a)
-        ptr = (C.c_void_p * nf)(*[d.ctypes.data if len(d) else None for d in ds]); nd = np.array([len(d) for d in ds], np.int32)
+        ptr = (C.c_void_p * nf)(*[_m.ptr(d) for d in ds]); nd = np.array([len(d) for d in ds], np.int32)
         self._chk(lib().hvo_compute_bow(self.h, voc.h, levelsup, nf, ptr, _p(nd), B), "compute_bow")
         r = [_bow_finish(B[f], keep[f]) for f in range(nf)]
         return r[0] if single else r
@@ -2666,13 +2583,7 @@ class Context:
         P = params or pnp_params()
         Q = (PnpProblem * len(problems))(); keep = []
         for j, pr in enumerate(problems):
-            a = [np.ascontiguousarray(pr["p3d"], np.float32).reshape(-1, 3), np.ascontiguousarray(pr["p2d"], np.float32).reshape(-1, 2),
-                 np.ascontiguousarray(pr["sigma2"], np.float32).reshape(-1), np.ascontiguousarray(pr["feature_index"], np.int32).reshape(-1)]
-            n = len(a[0])
-            if not (len(a[1]) == len(a[2]) == len(a[3]) == n):
-                raise ValueError("pnp_ransac: a problem's arrays differ in length")
-            Q[j].p3d, Q[j].p2d, Q[j].sigma2, Q[j].feature_index = [v.ctypes.data if n else None for v in a]
-            Q[j].n = n; Q[j].n_features = int(pr["n_features"]); keep.append(a)
+            keep.append(PNP_PROBLEM.fill(Q[j], pr)[0]); Q[j].n_features = int(pr["n_features"])
         R, rk = _pnp_results(len(problems), [pr["n_features"] for pr in problems], P, want_sample, spare_events)
         cm = _pose_cam(tuple(cam[:4]) + (0.0,))
         rc = lib().hvo_pnp_ransac(self.h, C.byref(cm), C.byref(P), len(problems), Q, R)
@@ -2687,16 +2598,11 @@ class Context:
         Returns one dict per candidate: match_idx, match_dist (per key-frame entry), feature_kf (per frame feature), proj, level, gate,
         n_matches, n_searched, status, kernel_ms.  check=False: (return code, message, the dicts) instead of an exception; a refused call
         leaves every output at KF_UNTOUCHED."""
-        kp = np.ascontiguousarray(t_kp_un, KEYPOINT_DT); nt = len(kp)
-        d = np.ascontiguousarray(t_desc, np.uint8).reshape(nt, 32)
-        F = LocalPointsFrame(); F.n = nt; F.kp_un = kp.ctypes.data if nt else None; F.uright = None; F.desc = d.ctypes.data if nt else None
+        F, fkeep, nt = _lp_frame(t_kp_un, None, t_desc)
         P, K, R, keep = _kfs_args(nt, kfs, bounds4, th, orb_dist, check_orientation, log_scale_factor, n_levels)
         cm = _pose_cam(cam)
         rc = lib().hvo_search_by_projection_keyframe(self.h, C.byref(cm), C.byref(P), C.byref(F), len(kfs), K, R)
-        if not check:
-            return rc, lib().hvo_last_error(self.h).decode(), _kfs_finish(R, keep, nt)
-        self._chk(rc, "search_by_projection_keyframe")
-        return _kfs_finish(R, keep, nt)
+        return _ret(self, rc, "search_by_projection_keyframe", lambda ok: _kfs_finish(R, keep), check)
 
     def fuse_points(self, cam, kfs, maps, bounds4, th=3.0, th_low=50, log_scale_factor=float(np.log(np.float32(1.2))), n_levels=8, check=True):
         """ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:838-994) for every key frame of kfs (dicts: kp_un, uright or None, desc, Tcw,
@@ -2704,35 +2610,18 @@ class Context:
         list with one dict per key frame.  cam: (fx, fy, cx, cy, bf).  Returns one dict per key frame: best_idx, best_dist, gate, level, proj
         (n x 3), fused_entry, fused_idx (the list the caller walks), n_fused, n_searched, status, kernel_ms.  check=False: (return code,
         message, the dicts) instead of an exception; a refused call leaves every output at FUSE_UNTOUCHED."""
-        per_kf = not isinstance(maps, dict)
-        if per_kf and len(maps) != len(kfs):
-            raise ValueError("fuse_points: one map side per key frame, or one dict for all")
-        M, mk, ns = _fuse_maps(list(maps) if per_kf else [maps])
-        ne = ns if per_kf else ns * len(kfs)
-        K, kk = _fuse_keyframes(kfs, ne)
-        R, rk = _fuse_results(ne)
-        P = _fuse_params(cam, bounds4, th, th_low, log_scale_factor, n_levels, per_kf)
-        cm = _pose_cam(cam)
+        K, M, _, per_kf, R, finish, keep = _FUSE.build(kfs, maps)
+        P = _fuse_params(cam, bounds4, th, th_low, log_scale_factor, n_levels, per_kf); cm = _pose_cam(cam)
         rc = lib().hvo_fuse_points(self.h, C.byref(cm), C.byref(P), M, len(kfs), K, R)
-        if not check:
-            return rc, lib().hvo_last_error(self.h).decode(), _fuse_finish(R, rk, rc == HVO_OK)
-        self._chk(rc, "fuse_points")
-        return _fuse_finish(R, rk, True)
+        return _ret(self, rc, "fuse_points", finish, check)
 
     def fuse_points_slots(self, point_map, slots, cam, kfs, bounds4, th=3.0, th_low=50, log_scale_factor=float(np.log(np.float32(1.2))), n_levels=8, check=True):
         """fuse_points with the map side given as slots of a resident PointMap, shared by all key frames: the map's device arrays are read in
         place, only the slot list and the skip bytes go up.  A bad slot counts as skipped; a slot outside the map refuses the whole call."""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1); n = len(sl)
-        ne = [n] * len(kfs)
-        K, kk = _fuse_keyframes(kfs, ne)
-        R, rk = _fuse_results(ne)
-        P = _fuse_params(cam, bounds4, th, th_low, log_scale_factor, n_levels, False)
-        cm = _pose_cam(cam)
-        rc = lib().hvo_fuse_points_slots(self.h, point_map.h, n, sl.ctypes.data if n else None, C.byref(cm), C.byref(P), len(kfs), K, R)
-        if not check:
-            return rc, lib().hvo_last_error(self.h).decode(), _fuse_finish(R, rk, rc == HVO_OK)
-        self._chk(rc, "fuse_points_slots")
-        return _fuse_finish(R, rk, True)
+        K, _, sl, _, R, finish, keep = _FUSE.build(kfs, slots=slots)
+        P = _fuse_params(cam, bounds4, th, th_low, log_scale_factor, n_levels, False); cm = _pose_cam(cam)
+        rc = lib().hvo_fuse_points_slots(self.h, point_map.h, len(sl), _m.ptr(sl), C.byref(cm), C.byref(P), len(kfs), K, R)
+        return _ret(self, rc, "fuse_points_slots", finish, check)
 
     def fuse_lines(self, kfs, maps, th=3.0, th_low=50, log_scale_factor=float(np.log(np.float32(1.2))), n_levels=1, scale_factor=1.2, level_rule="clamped", check=True):
         """LSDmatcher::Fuse(pKF, vpMapLines, th) (src/LSDmatcher.cpp:1297-1434) for every key frame of kfs (dicts: kl, desc_rows, Tcw, cam
@@ -2742,34 +2631,19 @@ class Context:
         "clamped" or "as written".  Returns one dict per key frame: best_idx,
         best_dist, gate (LF_GATES), level, proj (n x 4), fused_entry, fused_idx, behind_entry, n_fused, n_behind, n_searched, status,
         kernel_ms.  check=False: (return code, message, the dicts); a refused call leaves every output at FUSE_UNTOUCHED."""
-        per_kf = not isinstance(maps, dict)
-        if per_kf and len(maps) != len(kfs):
-            raise ValueError("fuse_lines: one map side per key frame, or one dict for all")
-        M, mk, ns = _lf_maps(list(maps) if per_kf else [maps])
-        ne = ns if per_kf else ns * len(kfs)
-        K, kk = _lf_keyframes(kfs, ne)
-        R, rk = _lf_results(ne)
+        K, M, _, per_kf, R, finish, keep = _LF.build(kfs, maps)
         P = _lf_params(th, th_low, log_scale_factor, n_levels, scale_factor, level_rule, per_kf)
         rc = lib().hvo_fuse_lines(self.h, C.byref(P), M, len(kfs), K, R)
-        if not check:
-            return rc, lib().hvo_last_error(self.h).decode(), _lf_finish(R, rk, rc == HVO_OK)
-        self._chk(rc, "fuse_lines")
-        return _lf_finish(R, rk, True)
+        return _ret(self, rc, "fuse_lines", finish, check)
 
     def fuse_lines_slots(self, line_map, slots, kfs, th=3.0, th_low=50, log_scale_factor=float(np.log(np.float32(1.2))), n_levels=1, scale_factor=1.2,
                          level_rule="clamped", check=True):
         """fuse_lines with the map side given as slots of a resident LineMap, shared by all key frames: the map's device arrays are read in
         place, only the slot list and the skip bytes go up.  A bad slot counts as skipped; a slot outside the map refuses the whole call."""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1); n = len(sl)
-        ne = [n] * len(kfs)
-        K, kk = _lf_keyframes(kfs, ne)
-        R, rk = _lf_results(ne)
+        K, _, sl, _, R, finish, keep = _LF.build(kfs, slots=slots)
         P = _lf_params(th, th_low, log_scale_factor, n_levels, scale_factor, level_rule, False)
-        rc = lib().hvo_fuse_lines_slots(self.h, line_map.h, n, sl.ctypes.data if n else None, C.byref(P), len(kfs), K, R)
-        if not check:
-            return rc, lib().hvo_last_error(self.h).decode(), _lf_finish(R, rk, rc == HVO_OK)
-        self._chk(rc, "fuse_lines_slots")
-        return _lf_finish(R, rk, True)
+        rc = lib().hvo_fuse_lines_slots(self.h, line_map.h, len(sl), _m.ptr(sl), C.byref(P), len(kfs), K, R)
+        return _ret(self, rc, "fuse_lines_slots", finish, check)
 
     def create_new_map_points(self, cam, cur, kfs, th_low=50, n_levels=8, scale_factor=1.2, check=True):
         """LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:335-580): the epipolar search and the triangulation of the current key frame
@@ -2779,14 +2653,11 @@ class Context:
         owner, n_new, kernel_ms).  check=False: (return code, message, the two) instead of an exception; a refused call leaves every output
         at NP_UNTOUCHED."""
         ck = NpKeyframe(); keep1 = _np_keyframe(ck, cur); n1 = ck.n
-        K, R, S, P, owner, outs, keep = _np_args(n1, kfs, th_low, n_levels, scale_factor, float(cam[4]))
+        K, R, S, P, finish, keep = _np_args(n1, kfs, th_low, n_levels, scale_factor, float(cam[4]))
         cm = _pose_cam(cam)
         rc = lib().hvo_create_new_map_points(self.h, C.byref(cm), C.byref(P), C.byref(ck), len(kfs), K, R, C.byref(S))
         del keep1, keep
-        if not check:
-            return (rc, lib().hvo_last_error(self.h).decode()) + _np_finish(n1, R, S, owner, outs, rc == HVO_OK)
-        self._chk(rc, "create_new_map_points")
-        return _np_finish(n1, R, S, owner, outs, True)
+        return _ret(self, rc, "create_new_map_points", finish(n1), check)
 
     def create_new_map_lines(self, cur, kfs, th_high=80, nn_ratio=0.85, n_levels=8, scale_factor=1.2, pairing=NL_PAIR_AS_WRITTEN, n_pairs_cap=None, check=True):
         """LocalMapping::CreateNewMapLinesConstraint (src/LocalMapping.cc:1064-1565): SearchForTriangulation of the current key frame `cur` against
@@ -2797,15 +2668,10 @@ class Context:
         n_pairs, kernel_ms).  check=False: (return code, message, the three) instead of an exception; a refused call leaves every output at
         NL_UNTOUCHED."""
         ck = NlKeyframe(); keep1 = _nl_keyframe(ck, cur); n1 = ck.n
-        K, M, R, S, P, cap, owner, mouts, outs, keep = _nl_args(n1, kfs, th_high, nn_ratio, n_levels, scale_factor, pairing, n_pairs_cap)
-        f = lib().hvo_create_new_map_lines; f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        rc = f(self.h, C.addressof(P), C.addressof(ck), len(kfs), C.addressof(K), C.addressof(M), cap, C.addressof(R), C.addressof(S))
+        K, M, R, S, P, cap, finish, keep = _nl_args(n1, kfs, th_high, nn_ratio, n_levels, scale_factor, pairing, n_pairs_cap)
+        rc = lib().hvo_create_new_map_lines(self.h, C.addressof(P), C.addressof(ck), len(kfs), C.addressof(K), C.addressof(M), cap, C.addressof(R), C.addressof(S))
         del keep1, keep
-        if not check:
-            return (rc, lib().hvo_last_error(self.h).decode()) + _nl_finish(n1, M, R, S, owner, mouts, outs, rc == HVO_OK)
-        self._chk(rc, "create_new_map_lines")
-        return _nl_finish(n1, M, R, S, owner, mouts, outs, True)
+        return _ret(self, rc, "create_new_map_lines", finish(n1), check)
 
     def refresh_map_points(self, pos, obs, n_levels=8, what=MR_DESCRIPTOR | MR_GEOMETRY, want=None, check=True):
         """MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (src/MapPoint.cc:240-305, 328-369) for n points in one call.  pos (n, 3);
@@ -2814,14 +2680,14 @@ class Context:
         max_dist, min_dist, status (MR_STATUS), kernel_ms); an entry the status says was not written holds MR_UNTOUCHED.  want: the outputs to
         ask for (None: all).  check=False: (return code, message, the dict); the limits of map_refresh_check raise either way, before the library is called"""
         p = None if pos is None else np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
-        return _mr_call(self, "hvo_refresh_map_points", False, (), (p.ctypes.data if p is not None and p.size else None,), obs, n_levels, 1.2, what, want, check)
+        return _mr_call(self, "hvo_refresh_map_points", False, (), (_m.ptr(p),), obs, n_levels, 1.2, what, want, check)
 
     def refresh_map_lines(self, pos, obs, n_levels=8, scale_factor=1.2, what=MR_DESCRIPTOR | MR_GEOMETRY, want=None, check=True):
         """MapLine::ComputeDistinctiveDescriptors + UpdateAverageDir (src/MapLine.cpp:331-396, 404-455) for n lines in one call.  pos (n, 6) doubles;
         obs as for refresh_map_points (LBD rows, mvKeyLines octaves); n_levels / scale_factor: the LINE pyramid.  Returns the same dict with
         normal in float64 and wvec"""
         p = None if pos is None else np.ascontiguousarray(pos, np.float64).reshape(-1, 6)
-        return _mr_call(self, "hvo_refresh_map_lines", True, (), (p.ctypes.data if p is not None and p.size else None,), obs, n_levels, scale_factor, what, want, check)
+        return _mr_call(self, "hvo_refresh_map_lines", True, (), (_m.ptr(p),), obs, n_levels, scale_factor, what, want, check)
 
     def pnp_last_kernel_ms(self):
         """(hypothesis kernels, refine kernels): device ms of the last pnp_ransac"""
@@ -2839,13 +2705,11 @@ class Context:
 
     def set_readings(self, blur_float=False, lsd_8u=False):
         """the alternative readings of cv::GaussianBlur / cv::LineSegmentDetector (include/hvo.h HVO_READING_*); the next extraction uses them"""
-        lib().hvo_set_readings.argtypes = [C.c_void_p, C.c_uint]
         self._chk(lib().hvo_set_readings(self.h, (READING_BLUR_FLOAT if blur_float else 0) | (READING_LSD_8U if lsd_8u else 0)), "set_readings")
 
     def lsd_async_report(self):
         """(frames grown again by the one-wave kernel, workers that sat on a foreign XCD, workers per frame) of the last async line growing"""
         a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
-        lib().hvo_lsd_async_report.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         self._chk(lib().hvo_lsd_async_report(self.h, C.byref(a), C.byref(b), C.byref(c)), "lsd_async_report")
         return a.value, b.value, c.value
 
@@ -2879,7 +2743,6 @@ class Context:
         t_kp = np.ascontiguousarray(t_kp); t_uright = f32(t_uright)
         mi = np.zeros(nq, np.int32); md = np.zeros(nq, np.int32); n = C.c_int(0)
         fn = lib().hvo_search_by_projection_tracked
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_float] + [C.c_void_p] * 3
         self._chk(fn(self.h, _p(q_desc), nq, _p(proj_x), _p(proj_y), _p(proj_xr) if proj_xr is not None else None, _p(level), _p(view_cos), _p(q_blocks), float(th),
                      _p(t_kp), _p(t_uright), _p(t_occupied), _p(t_desc), nt, bounds[0], bounds[1], bounds[2], bounds[3], th_high, nn_ratio,
                      _p(mi), _p(md), C.byref(n)), "search_by_projection_tracked")
@@ -2976,7 +2839,6 @@ class Context:
         """pack the first n frames' results (hvo_batch_pack_results_ex) and start ONE copy of the slabs into `host_slabs` (a page-locked
         uint8 array of n * slab_bytes); batch_results_wait() waits for it.  The resident batch may run again at once."""
         fn = lib().hvo_batch_results_async
-        fn.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_void_p]
         self._chk(fn(self.h, n, SLAB_LABELS if labels else 0, host_slabs.ctypes.data), "batch_results_async")
 
     def batch_results_wait(self):
@@ -3062,14 +2924,12 @@ class Context:
         the end of every slab (HVO_SLAB_LABELS) -> (kp_cap, kl_cap, pl_cap, slab_bytes, labels_off)"""
         a, b, c, d, e = C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0), C.c_size_t(0)
         fn = lib().hvo_batch_slab_layout_ex
-        fn.argtypes = [C.c_void_p, C.c_uint] + [C.c_void_p] * 5
         self._chk(fn(self.h, SLAB_LABELS if labels else 0, C.byref(a), C.byref(b), C.byref(c), C.byref(e), C.byref(d)), "batch_slab_layout")
         return (a.value, b.value, c.value, d.value, e.value) if labels else (a.value, b.value, c.value, d.value)
 
     def pack_results(self, n, device_ptr, labels=False):
         """write the first n frames' result slabs to device memory at `device_ptr` (n * slab_bytes bytes)"""
         fn = lib().hvo_batch_pack_results_ex
-        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint]
         self._chk(fn(self.h, n, C.c_void_p(device_ptr), SLAB_LABELS if labels else 0), "batch_pack_results")
 
     def profile_enable(self, mode=1):
@@ -3148,21 +3008,24 @@ class Stream:
 
     __del__ = close
 
+    def _last_error(self):
+        return lib().hvo_stream_last_error(self.h)
+
     def _chk(self, rc, what):
         if rc != HVO_OK:
-            raise HvoError(rc, what + ": " + lib().hvo_stream_last_error(self.h).decode())
+            raise HvoError(rc, what + ": " + self._last_error().decode())
 
     def debug_call_arena(self, ticket, fill=None, min_bytes=0):
         """test door, not product API: Context.debug_call_arena on the context of the ring slot that holds frame `ticket`, the arena the
         stream forms of the matching, fusing and solving calls stage through"""
-        L = lib(); f = L.hvo_debug_stream_call_arena; f.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]; f.restype = C.c_int
+        L = lib(); f = L.hvo_debug_stream_call_arena
         cap = C.c_size_t(0)
         self._chk(f(self.h, int(ticket), -1 if fill is None else int(fill), int(min_bytes), C.byref(cap)), "debug_call_arena")
         return cap.value
 
     def debug_call_arena_peek(self, ticket, offset, n):
         """test door, not product API: n bytes of that arena from `offset` -> uint8 array"""
-        L = lib(); f = L.hvo_debug_stream_call_arena_peek; f.argtypes = [C.c_void_p, C.c_int64, C.c_size_t, C.c_size_t, C.c_void_p]; f.restype = C.c_int
+        L = lib(); f = L.hvo_debug_stream_call_arena_peek
         out = np.zeros(int(n), np.uint8)
         self._chk(f(self.h, int(ticket), int(offset), int(n), _p(out)), "debug_call_arena_peek")
         return out
@@ -3229,8 +3092,6 @@ class Stream:
         """ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) whole between two resident frames: projection prologue
         (src/ORBmatcher.cc:1364-1405) + search core on the device.  cam = (fx, fy, cx, cy, mbf, mb); Tcw / Tlw: 3 x 4 row-major.
         -> (nmatches, idx, dist[, uv])"""
-        class Cam(C.Structure):
-            _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "bf", "b")]
         q_index = np.ascontiguousarray(q_index, np.int32); nq = len(q_index)
         x3Dw = np.ascontiguousarray(x3Dw, np.float32).reshape(-1, 3); assert len(x3Dw) == nq
         Tcw = np.ascontiguousarray(Tcw, np.float32).reshape(12); Tlw = np.ascontiguousarray(Tlw, np.float32).reshape(12)
@@ -3240,9 +3101,8 @@ class Stream:
         mi = np.zeros(max(nq, 1), np.int32); md = np.zeros(max(nq, 1), np.int32); n = C.c_int(0)
         uv = np.zeros((max(nq, 1), 2), np.float32) if want_uv else None
         pp = lambda a: _p(a) if a is not None else None
-        c = Cam(*[float(v) for v in cam])
+        c = PoseCamera(*[float(v) for v in cam])
         fn = lib().hvo_stream_project_last
-        fn.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
         self._chk(fn(self.h, cur, last, C.byref(c), _p(Tcw), _p(Tlw), nq, _p(q_index), _p(x3Dw), _p(q_blocks), pp(q_desc), pp(t_occupied),
                      float(th), 1 if mono else 0, th_high, 1 if check_orientation else 0, _p(mi), _p(md), C.byref(n), pp(uv)), "stream_project_last")
         return (n.value, mi[:nq], md[:nq], uv[:nq]) if want_uv else (n.value, mi[:nq], md[:nq])
@@ -3298,15 +3158,10 @@ class Stream:
         P = params or pnp_params()
         K = (PnpKeyframeSide * len(kf_sides))(); keep = []
         for j, kf in enumerate(kf_sides):
-            a = [np.ascontiguousarray(kf["match_kf"], np.int32).reshape(-1), np.ascontiguousarray(kf["pos"], np.float32).reshape(-1, 3),
-                 np.ascontiguousarray(np.asarray(kf["bad"]).astype(bool), np.uint8).reshape(-1)]
-            if len(a[0]) < self.kp_cap:
-                a[0] = np.concatenate([a[0], np.full(self.kp_cap - len(a[0]), -1, np.int32)])
-            if len(a[1]) != len(a[2]):
-                raise ValueError("pnp_ransac: pos and bad differ in length")
-            K[j].match_kf = a[0].ctypes.data; K[j].n = len(a[1])
-            K[j].pos, K[j].bad = [v.ctypes.data if len(a[1]) else None for v in a[1:]]
-            keep.append(a)
+            mk = np.ascontiguousarray(kf["match_kf"], np.int32).reshape(-1)
+            if len(mk) < self.kp_cap:                                   # (the call reads one entry per feature the frame can hold: -1 past the given ones)
+                mk = np.concatenate([mk, np.full(self.kp_cap - len(mk), -1, np.int32)])
+            keep.append(PNP_KF_SIDE.fill(K[j], dict(kf, match_kf=mk))[0])
         R, rk = _pnp_results(len(kf_sides), [self.kp_cap] * len(kf_sides), P, want_sample)
         cm = _pose_cam(tuple(cam[:4]) + (0.0,))
         rc = lib().hvo_stream_pnp_ransac(self.h, cur, C.byref(cm), C.byref(P), len(kf_sides), K, R)
@@ -3322,50 +3177,29 @@ class Stream:
         P, K, R, keep = _kfs_args(int(n_kp), kfs, None, th, orb_dist, check_orientation, log_scale_factor, n_levels)
         cm = _pose_cam(cam)
         rc = lib().hvo_stream_search_by_projection_keyframe(self.h, cur, C.byref(cm), C.byref(P), len(kfs), K, R)
-        if not check:
-            return rc, lib().hvo_stream_last_error(self.h).decode(), _kfs_finish(R, keep, int(n_kp))
-        self._chk(rc, "stream_search_by_projection_keyframe")
-        return _kfs_finish(R, keep, int(n_kp))
+        return _ret(self, rc, "stream_search_by_projection_keyframe", lambda ok: _kfs_finish(R, keep), check)
 
     def fuse_points(self, cur, cam, Tcw, maps=None, point_map=None, slots=None, skip=None, th=3.0, th_low=50,
                     log_scale_factor=float(np.log(np.float32(1.2))), n_levels=8, check=True):
         """ORBmatcher::Fuse(mpCurrentKeyFrame, vpFuseCandidates) with the resident frame `cur` as the key frame under Tcw (needs STAGE_ORB):
         its undistorted key points, mvuRight and descriptors stay on the device, the bounds are the frame grid's.  The map side is `maps`
         (one dict of host arrays) or `slots` of `point_map`.  Returns one dict as Context.fuse_points does per key frame."""
-        if maps is not None:
-            M, mk, ns = _fuse_maps([maps]); n = ns[0]; sl = None
-        else:
-            M = None; sl = np.ascontiguousarray(slots, np.int32).reshape(-1); n = len(sl)
-        K, kk = _fuse_keyframes([dict(Tcw=Tcw, skip=skip)], [n], resident=True)
-        R, rk = _fuse_results([n])
-        P = _fuse_params(cam, None, th, th_low, log_scale_factor, n_levels, False)
-        cm = _pose_cam(cam)
+        K, M, sl, _, R, finish, keep = _FUSE.build([dict(Tcw=Tcw, skip=skip)], maps, slots, resident=True)
+        P = _fuse_params(cam, None, th, th_low, log_scale_factor, n_levels, False); cm = _pose_cam(cam)
         rc = lib().hvo_stream_fuse_points(self.h, cur, C.byref(cm), C.byref(P), C.addressof(K[0].Tcw), K[0].skip, M, point_map.h if point_map is not None else None,
-                                          n, sl.ctypes.data if sl is not None and n else None, R)
-        if not check:
-            return rc, lib().hvo_stream_last_error(self.h).decode(), _fuse_finish(R, rk, rc == HVO_OK)[0]
-        self._chk(rc, "stream_fuse_points")
-        return _fuse_finish(R, rk, True)[0]
+                                          M[0].n if sl is None else len(sl), _m.ptr(sl), R)
+        return _ret(self, rc, "stream_fuse_points", lambda ok: finish(ok)[0], check)
 
     def fuse_lines(self, cur, cam, Tcw, maps=None, line_map=None, slots=None, skip=None, th=3.0, th_low=50, log_scale_factor=float(np.log(np.float32(1.2))),
                    n_levels=1, scale_factor=1.2, level_rule="clamped", check=True):
         """LSDmatcher::Fuse(mpCurrentKeyFrame, vpFuseCandidates) with the resident frame `cur` as the key frame under Tcw and cam (needs an LSD
         stage): its key lines and LBD descriptors stay on the device, the bounds are the frame grid's.  The map side is `maps` (one dict of
         host arrays) or `slots` of `line_map`.  Returns one dict as Context.fuse_lines does per key frame."""
-        if maps is not None:
-            M, mk, ns = _lf_maps([maps]); n = ns[0]; sl = None
-        else:
-            M = None; sl = np.ascontiguousarray(slots, np.int32).reshape(-1); n = len(sl)
-        K, kk = _lf_keyframes([dict(Tcw=Tcw, skip=skip)], [n], resident=True)
-        R, rk = _lf_results([n])
-        P = _lf_params(th, th_low, log_scale_factor, n_levels, scale_factor, level_rule, False)
-        cm = _pose_cam(cam)
+        K, M, sl, _, R, finish, keep = _LF.build([dict(Tcw=Tcw, skip=skip)], maps, slots, resident=True)
+        P = _lf_params(th, th_low, log_scale_factor, n_levels, scale_factor, level_rule, False); cm = _pose_cam(cam)
         rc = lib().hvo_stream_fuse_lines(self.h, cur, C.byref(cm), C.byref(P), C.addressof(K[0].Tcw), K[0].skip, M, line_map.h if line_map is not None else None,
-                                         n, sl.ctypes.data if sl is not None and n else None, R)
-        if not check:
-            return rc, lib().hvo_stream_last_error(self.h).decode(), _lf_finish(R, rk, rc == HVO_OK)[0]
-        self._chk(rc, "stream_fuse_lines")
-        return _lf_finish(R, rk, True)[0]
+                                         M[0].n if sl is None else len(sl), _m.ptr(sl), R)
+        return _ret(self, rc, "stream_fuse_lines", lambda ok: finish(ok)[0], check)
 
     def pnp_last_kernel_ms(self, cur):
         ms = np.zeros(2, np.float32)
@@ -3379,15 +3213,12 @@ class Stream:
         mb).  Returns what Context.create_new_map_points returns."""
         hm = np.asarray(has_map_point).astype(bool).reshape(-1); n1 = len(hm)
         has = np.zeros(max(n1, self.kp_cap, 1), np.uint8); has[:n1] = hm          # (a frame with more features than bytes given reads zeros, not past the end)
-        K, R, S, P, owner, outs, keep = _np_args(max(n1, self.kp_cap), kfs, th_low, n_levels, scale_factor, float(cam[4]))
+        K, R, S, P, finish, keep = _np_args(max(n1, self.kp_cap), kfs, th_low, n_levels, scale_factor, float(cam[4]))
         cm = _pose_cam(cam)
         T = np.ascontiguousarray(Tcw, np.float32).reshape(12)
         rc = lib().hvo_stream_create_new_map_points(self.h, cur, voc.h, C.byref(cm), C.byref(P), T.ctypes.data, has.ctypes.data, len(kfs), K, R, C.byref(S))
         del keep
-        if not check:
-            return (rc, lib().hvo_stream_last_error(self.h).decode()) + _np_finish(n1, R, S, owner, outs, rc == HVO_OK)
-        self._chk(rc, "stream_create_new_map_points")
-        return _np_finish(n1, R, S, owner, outs, True)
+        return _ret(self, rc, "stream_create_new_map_points", finish(n1), check)
 
     def create_new_map_lines(self, cur, cam, Tcw, has_map_line, kfs, th_high=80, nn_ratio=0.85, n_levels=8, scale_factor=1.2, pairing=NL_PAIR_AS_WRITTEN,
                              n_pairs_cap=None, check=True):
@@ -3396,17 +3227,13 @@ class Stream:
         line of the frame), the pose and the neighbours go up.  Returns what Context.create_new_map_lines returns."""
         hm = np.asarray(has_map_line).astype(bool).reshape(-1); n1 = len(hm)
         has = np.zeros(max(n1, self.kl_cap, 1), np.uint8); has[:n1] = hm           # (a frame with more lines than bytes given reads zeros, not past the end)
-        K, M, R, S, P, cap, owner, mouts, outs, keep = _nl_args(max(n1, self.kl_cap), kfs, th_high, nn_ratio, n_levels, scale_factor, pairing, n_pairs_cap)
+        K, M, R, S, P, cap, finish, keep = _nl_args(max(n1, self.kl_cap), kfs, th_high, nn_ratio, n_levels, scale_factor, pairing, n_pairs_cap)
         cm = (C.c_float * 6)(*([float(v) for v in cam[:4]] + [0.0, 0.0]))
         T = np.ascontiguousarray(Tcw, np.float32).reshape(12)
-        f = lib().hvo_stream_create_new_map_lines; f.restype = C.c_int
-        f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        rc = f(self.h, cur, C.addressof(cm), C.addressof(P), T.ctypes.data, has.ctypes.data, len(kfs), C.addressof(K), C.addressof(M), cap, C.addressof(R), C.addressof(S))
+        rc = lib().hvo_stream_create_new_map_lines(self.h, cur, C.addressof(cm), C.addressof(P), T.ctypes.data, has.ctypes.data, len(kfs), C.addressof(K), C.addressof(M), cap,
+                                                   C.addressof(R), C.addressof(S))
         del keep
-        if not check:
-            return (rc, lib().hvo_stream_last_error(self.h).decode()) + _nl_finish(n1, M, R, S, owner, mouts, outs, rc == HVO_OK)
-        self._chk(rc, "stream_create_new_map_lines")
-        return _nl_finish(n1, M, R, S, owner, mouts, outs, True)
+        return _ret(self, rc, "stream_create_new_map_lines", finish(n1), check)
 
     def search_by_bow(self, cur, voc, kfs, nnratio=0.7, check_orientation=True, th_low=50):
         """SearchByBoW of the key frames kfs (dicts of desc, node_id, has_map_point, angle) against the resident frame `cur`, which holds its bag
@@ -3416,7 +3243,6 @@ class Stream:
         return [(m[j].copy(), R[j].n_matches) for j in range(len(kfs))]
 
     def set_readings(self, blur_float=False, lsd_8u=False):
-        lib().hvo_stream_set_readings.argtypes = [C.c_void_p, C.c_uint]
         self._chk(lib().hvo_stream_set_readings(self.h, (READING_BLUR_FLOAT if blur_float else 0) | (READING_LSD_8U if lsd_8u else 0)), "stream_set_readings")
 
     def match_lines_geom(self, cur, last, desc_th=0.9, last_has_mapline=None):
@@ -3558,6 +3384,8 @@ class Stream:
 # ---------------------------------------------------------------------------------------
 # host-side mirrors of the reference's operator interfaces
 # ---------------------------------------------------------------------------------------
+
+
 class ORBextractor:
     """ORB_SLAM2::ORBextractor (include/ORBextractor.h:53-61).  operator()(image) -> (keypoints, descriptors)."""
 
